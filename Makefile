@@ -1,5 +1,5 @@
 # Convenience targets; the contract entry points are build.sh, bench.py and __graft_entry__.py.
-.PHONY: build test gpu-test bench smoke goldens clean
+.PHONY: build test gpu-test bench bench-full smoke goldens clean
 
 build:            ## hipcc --offload-arch=gfx950, in-tree: detikzify_amd/lib/libdtk_hip.so
 	bash build.sh
@@ -13,8 +13,11 @@ gpu-test:         ## parity on an MI355X
 smoke:
 	python -c "import __graft_entry__ as g; g.smoke()"
 
-bench:            ## one JSON line: tokens/s, roofline, cpu_baseline
+bench:            ## one JSON line: the headline tokens/s
 	python bench.py
+
+bench-full:       ## the same line + batched rollouts, MCTS, roofline, cpu_baseline
+	python bench.py --full
 
 goldens:          ## build container only (reads /root/reference); deterministic: regenerating changes no byte
 	python tests/golden/make_golden.py

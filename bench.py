@@ -12,7 +12,11 @@ the prefill time are reported beside it.  N > 1 (torchrun, one rank per GPU): ev
 independent rollouts on a full replica (root-parallel rollouts), the generated TikZ strings
 are gathered to rank 0 over RCCL inside the timed region; scaling is weak.
 
-Phases after the headline loop (each can be switched off):
+A plain run sets up, warms up, times --steps rollouts and prints the headline line (`value`, `ms_per_step`, the decode-only
+rate, prefill / ViT times).  `--dump-outputs DIR` writes what the last timed rollout returned (DIR/sequences.npy: the token ids
+of model.generate, as float64).  Everything below runs only with `--full`.
+
+Phases after the headline loop, with --full (each can be switched off):
   batched_rollouts  B independent sampled rollouts per GPU as ONE batched decode (the weights stream once per step)
   mcts              the search itself (DetikzifyGenerator / MonteCarlo, reference semantics): `sequential` = ONE tree per
                     GPU, expansion k+1 selects on what expansion k back-propagated (reference infer/generate.py:195-207,
@@ -52,6 +56,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--model", default="detikzify-ds-7b")
     ap.add_argument("--new-tokens", type=int, default=512)
+    ap.add_argument("--full", action="store_true", help="after the headline: secondary rooflines, batched rollouts, MCTS, the dominant "
+                    "kernel's roofline and the CPU baselines (a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed rollout's output (sequences.npy: "
+                    "prompt + generated token ids, float64) to DIR")
     ap.add_argument("--sample", action="store_true", help="sampling decode (T=.8, p=.95) instead of greedy")
     ap.add_argument("--reuse", action="store_true", help="SURVEY §8 f1: reuse image embeds / prefix KV across rollouts")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -316,6 +324,15 @@ def cpu_baseline_config1(budget_s):
                       f"(built in {t_build:.0f} s), 243-position prefix (prefill {t_prefill:.1f} s, not timed), {n} greedy tokens"}
 
 
+def dump_outputs(dirname, sequences):
+    """--dump-outputs: what the caller of the timed path received in its last step — model.generate's [1, prompt + new] token
+    ids, stored as float64 (exact for token ids) so that two builds can be compared output for output"""
+    import numpy as np
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "sequences.npy", sequences.detach().cpu().numpy().astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     args = parse()
@@ -369,7 +386,7 @@ def main():
     def rollout(i):
         out = model.generate(input_ids=ids, seed=1000 + rank + 7919 * i, **gen_kw)
         assert out.shape[1] == T0 + n_new
-        return out[0, T0:]
+        return out
 
     def fence():
         model.synchronize()
@@ -392,7 +409,8 @@ def main():
     codes, first_tokens = [], None
     for i in range(args.steps):
         ts = time.perf_counter()
-        toks = rollout(i)
+        out = rollout(i)
+        toks = out[0, T0:]
         per_step.append(time.perf_counter() - ts)
         st = model.stats()
         prefill_ms.append(st["last_prefill_ms"]); vit_ms.append(st["last_vit_ms"])
@@ -430,6 +448,15 @@ def main():
                         "roofline_tokens_per_sec": HBM_PEAK_GBS * 1e9 / bytes_per_token},
         "ranks": placement,
     }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- the two MFMA-shaped stages of a rollout against THEIR rooflines (VERDICT r5 weak 10 / missing 5).  The decoder prefill at
     # M = 243 rows has an arithmetic intensity of ~243 FLOP/B, below the ~312 FLOP/B ridge of this part (2.5 PFLOP/s / 8 TB/s): its
     # floor is ONE pass over the decoder weights, i.e. HBM; the ViT (729 rows) is matrix-core bound.

@@ -1,7 +1,7 @@
 """bench.py end to end on the CPU: the model behind `load` is the scripted device of test_generate_loop (the real generate
 loop, batch engine and MCTS stack run), torch.cuda.synchronize is a no-op.  Checks the one-JSON-line contract the driver
-parses — keys, types, arithmetic consistency — and that every optional phase (batched rollouts over several images, the
-MCTS phase, --skip-batched) runs through.  The numbers themselves mean nothing here."""
+parses — keys, types, arithmetic consistency — that every optional phase of --full (batched rollouts over several images, the
+MCTS phase, --skip-batched) runs through, and that a plain run is the headline alone.  The numbers themselves mean nothing here."""
 import json
 import sys
 from collections import defaultdict
@@ -52,7 +52,7 @@ def _run_bench(monkeypatch, capsys, argv):
 
 
 def test_bench_json_contract_and_phases(monkeypatch, capsys):
-    d = _run_bench(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--new-tokens", "24", "--no-cpu-baseline",
+    d = _run_bench(monkeypatch, capsys, ["--full", "--steps", "2", "--warmup", "1", "--new-tokens", "24", "--no-cpu-baseline",
                                          "--batch", "8", "--batch-images", "3", "--mcts-trees", "4", "--mcts-expansions", "2",
                                          "--probe-tokens", "2", "--config5-images", "3", "--config5-trees", "2", "--config5-expansions", "2",
                                          "--reward-latency", "0.05"])
@@ -116,19 +116,38 @@ def test_bench_json_contract_and_phases(monkeypatch, capsys):
 
 
 def test_bench_skip_batched_and_no_batch(monkeypatch, capsys):
-    d = _run_bench(monkeypatch, capsys, ["--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
+    d = _run_bench(monkeypatch, capsys, ["--full", "--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
                                          "--batch", "4", "--skip-batched", "--mcts-trees", "2", "--mcts-expansions", "1",
                                          "--probe-tokens", "2"])
     assert "batched_rollouts" not in d and d["mcts"]["parallel"]["rollouts"] == 2 and d["mcts"]["sequential"]["rollouts"] == 3
-    d = _run_bench(monkeypatch, capsys, ["--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
+    d = _run_bench(monkeypatch, capsys, ["--full", "--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
                                          "--batch", "0", "--probe-tokens", "2", "--sample", "--mcts-seq-expansions", "0"])
     assert "batched_rollouts" not in d and d["value"] > 0 and set(d["mcts"]) >= {"config5"} and "sequential" not in d["mcts"]
-    d = _run_bench(monkeypatch, capsys, ["--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
+    d = _run_bench(monkeypatch, capsys, ["--full", "--steps", "1", "--warmup", "0", "--new-tokens", "16", "--no-cpu-baseline",
                                          "--batch", "0", "--probe-tokens", "2", "--mcts-seq-expansions", "0", "--no-config5"])
     assert "mcts" not in d
 
 
-def _rank_main(rank, world, port, outdir):
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_outputs(monkeypatch, capsys, tmp_path):
+    """without --full the line holds the headline and nothing that takes runs of its own; --dump-outputs writes the last timed
+    rollout's token ids, the same on every run with the same arguments"""
+    argv = ["--steps", "3", "--warmup", "1", "--new-tokens", "16", "--sample"]
+    d = _run_bench(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["metric"] == "tikz_tokens_per_sec" and d["unit"] == "tokens/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(3 * 16 / (3 * d["ms_per_step"] / 1e3), rel=0.05)
+    for key in ("roofline", "secondary_rooflines", "batched_rollouts", "mcts", "cpu_baseline"):
+        assert key not in d, key
+    import numpy as np
+    a = np.load(tmp_path / "a" / "sequences.npy")
+    assert a.dtype == np.float64 and a.shape == (1, d["config"]["prefix_tokens"] + 16) and (a == np.round(a)).all()
+    _run_bench(monkeypatch, capsys, argv + ["--dump-outputs", str(tmp_path / "b")])
+    assert (np.load(tmp_path / "b" / "sequences.npy") == a).all()
+    _run_bench(monkeypatch, capsys, ["--steps", "2", "--warmup", "1", "--new-tokens", "16", "--sample", "--dump-outputs", str(tmp_path / "c")])
+    assert not (np.load(tmp_path / "c" / "sequences.npy") == a).all()       # the last step's rollout (its own seed), not the first's
+
+
+def _rank_main(rank, world, port, outdir, full=True):
     import os
     from pathlib import Path
     root = str(Path(__file__).resolve().parents[1])
@@ -149,7 +168,7 @@ def _rank_main(rank, world, port, outdir):
     dm.load = load
     torch.cuda.synchronize = lambda *a, **k: None
     torch.cuda.set_device = lambda *a, **k: None
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--new-tokens", "16", "--no-cpu-baseline",
+    sys.argv = ["bench.py"] + (["--full"] if full else []) + ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--new-tokens", "16", "--no-cpu-baseline",
                 "--batch", "4", "--probe-tokens", "2", "--config5-images", "4", "--config5-trees", "2", "--config5-expansions", "1"]
     buf = io.StringIO()
     with redirect_stdout(buf):
@@ -180,6 +199,22 @@ def test_bench_two_ranks_gloo(tmp_path):
     c4, c5 = d["mcts"]["config4"]["fixed_length"], d["mcts"]["config5"]["fixed_length"]
     assert c4["rollouts"] == 2 * 4 and c4["trees_per_gpu"] == 4 and c4["gather_seconds"] >= 0
     assert c5["rollouts"] == 4 * 2 * 1 and c5["images_per_gpu"] == 2 and len(c5["per_rank_rollouts_per_sec_min_max"]) == 2
+
+
+def test_bench_two_ranks_gloo_plain_run(tmp_path):
+    """the plain N > 1 run: every rank leaves after the headline together, rank 0 prints the whole-job line and nothing else"""
+    import socket
+
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_rank_main, args=(2, port, str(tmp_path), False), nprocs=2, join=True)
+    out0 = [ln for ln in (tmp_path / "rank0.out").read_text().splitlines() if ln.startswith("{")]
+    assert len(out0) == 1 and not [ln for ln in (tmp_path / "rank1.out").read_text().splitlines() if ln.startswith("{")]
+    d = json.loads(out0[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["value"] == pytest.approx(2 * 2 * 16 / (2 * d["ms_per_step"] / 1e3), rel=0.2)
+    assert "mcts" not in d and "batched_rollouts" not in d and "roofline" not in d
 
 
 def test_a_rank_that_cannot_load_config5_takes_every_rank_out_of_it(tmp_path, monkeypatch):

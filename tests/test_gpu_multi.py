@@ -100,12 +100,12 @@ def test_single_gpu_world_one_needs_no_process_group():
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs on one node (RCCL over xGMI)")
 def test_bench_two_gpus_runs_the_drivers_command(tmp_path):
-    """the exact command the driver's scaling run uses (`python -m torch.distributed.run ... bench.py --gpus N --steps K
-    --warmup W`) at N = 2 with the smallest model and short rollouts: one JSON line from rank 0, whole-job totals, both GPUs
+    """the command the driver's scaling run uses (`python -m torch.distributed.run ... bench.py --gpus N --steps K
+    --warmup W`), with --full, at N = 2 with the smallest model and short rollouts: one JSON line from rank 0, whole-job totals, both GPUs
     distinct, the MCTS phases (config 4 = 16 rollouts over the ranks, config 5 = images striped over the ranks) present"""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                          "--master-addr", "127.0.0.1", "--master-port", "29543", str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1",
+                          "--master-addr", "127.0.0.1", "--master-port", "29543", str(ROOT / "bench.py"), "--full", "--gpus", "2", "--steps", "1",
                           "--warmup", "1", "--model", "detikzify-ds-1.3b", "--config5-model", "detikzify-ds-1.3b", "--new-tokens", "48",
                           "--batch", "16", "--config5-images", "4", "--config5-trees", "2", "--config5-expansions", "1", "--probe-tokens", "4"],
                          capture_output=True, text=True, timeout=1500, env=env, cwd=str(ROOT))

@@ -1,5 +1,5 @@
 """Summarise a DTK_TRACE_MCTS file (infer/batching.py): when the trees were ready, how long rollouts / rewards took, how many
-trees were decoding over time.   DTK_TRACE_MCTS=/tmp/t.json python bench.py ... ; python tools/mcts_timeline.py /tmp/t.json"""
+trees were decoding over time.   DTK_TRACE_MCTS=/tmp/t.json python bench.py --full ... ; python tools/mcts_timeline.py /tmp/t.json"""
 import json, sys
 ev = json.load(open(sys.argv[1]))
 t0 = ev[0][0]
