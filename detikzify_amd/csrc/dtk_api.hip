@@ -102,7 +102,7 @@ struct dtk_ctx {
   bf16_t *ap_latent, *ap_qw, *ap_qb, *ap_kvw, *ap_kvb, *ap_pw, *ap_pb, *ap_nw, *ap_nb, *ap_f1w,
       *ap_f1b, *ap_f2w, *ap_f2b;
 
-  // KV cache [L][2][H][Tmax][128]
+  // KV cache [L][2][KVH][Tmax][hd]
   bf16_t* kv = nullptr;
 
   // activations: decoder prefill
@@ -144,6 +144,7 @@ struct dtk_ctx {
   bool have_image = false;
   // ---- batched decode (dtk_*_slot / dtk_decode_batch_*): up to 64 decoding slots (+1) with their own KV
   int KVH = 0;                       // key/value heads (dtk_config.reserved[2]; 0 -> heads)
+  int hd = 128;                      // decoder head dim: 128, or 64 (TinyLlama; no batched slots)
   bool proj_bias = true;             // mm_projector has a bias (v1) / bias-free connector (v2)
   int nb = 0;                        // number of batch slots (dtk_config.reserved[0])
   bool share_reads = true;           // forked slots read their shared prefix from the source slot (dtk_set_option "share_prefix_reads")
@@ -305,7 +306,7 @@ void add_tensor(dtk_ctx* c, const std::string& name, bf16_t* ptr, int64_t rows, 
 // Lays out every device buffer.  Called twice (size pass with base == nullptr, then for real).
 void plan(dtk_ctx* c, Planner& P, bool reg) {
   const int d = c->d, L = c->L, ff = c->ff, V = c->V, T = c->Tmax;
-  const int kvd = c->KVH * 128, qkvn = d + 2 * kvd;   // fused QKV rows: [H q heads | KVH k heads | KVH v heads] x 128
+  const int kvd = c->KVH * c->hd, qkvn = d + 2 * kvd;   // fused QKV rows: [H q heads | KVH k heads | KVH v heads] x hd
   const int D = c->vD, N = c->vN, mlp = c->vMlp;
   const float ws = 0.02f;
   auto R = [&](const std::string& n, bf16_t* p, int64_t r, int64_t cl, int64_t st, float sc,
@@ -345,10 +346,11 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
   R("model.mm_projector.weight", c->mm_w, d, (int64_t)c->cfg.concat_patches * D,
     (int64_t)c->cfg.concat_patches * D, ws, 0.f);
   if (c->proj_bias) R("model.mm_projector.bias", c->mm_b, 1, d, d, 0.01f, 0.f);   // v2 connector is bias-free
-  c->rope_cos = P.take<bf16_t>((size_t)T * 64);
-  c->rope_sin = P.take<bf16_t>((size_t)T * 64);
-  R("rope.cos", c->rope_cos, T, 64, 64, 0.f, 0.f);
-  R("rope.sin", c->rope_sin, T, 64, 64, 0.f, 0.f);
+  const int hd2 = c->hd / 2;
+  c->rope_cos = P.take<bf16_t>((size_t)T * hd2);
+  c->rope_sin = P.take<bf16_t>((size_t)T * hd2);
+  R("rope.cos", c->rope_cos, T, hd2, hd2, 0.f, 0.f);
+  R("rope.sin", c->rope_sin, T, hd2, hd2, 0.f, 0.f);
   // ---- vision tower (timm VisionTransformer state-dict names)
   const std::string vp = "vision_model.";
   c->pe_w = P.take<bf16_t>((size_t)D * c->vPatchLd);
@@ -408,7 +410,7 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
   R(vp + "attn_pool.mlp.fc2.bias", c->ap_f2b, 1, D, D, 0.01f, 0.f);
 
   // ---- KV cache + activations
-  c->kv = P.take<bf16_t>((size_t)L * 2 * c->KVH * T * 128);
+  c->kv = P.take<bf16_t>((size_t)L * 2 * c->KVH * T * c->hd);
   c->X = P.take<bf16_t>((size_t)T * d);
   c->Xn = P.take<bf16_t>((size_t)T * d);
   c->QKV = P.take<bf16_t>((size_t)T * qkvn);
@@ -593,7 +595,7 @@ void gemm_role(dtk_ctx* c, const bf16_t* A, int lda, const bf16_t* W, const bf16
 // q/k/v of n <= SK_CHUNK_ROWS prefill rows as a sliced-K GEMM whose reduction is fused with RoPE + the KV append (no [n][qkvn] buffer);
 // false = the role is not sliced here (the caller runs Linear + k_rope_scatter).  Same values as that pair, bit for bit.
 bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, bf16_t* vc, hipStream_t s) {
-  const int d = c->d, qkvn = d + 2 * c->KVH * 128;
+  const int d = c->d, qkvn = d + 2 * c->KVH * c->hd;
   const int S = c->prefill_sk ? std::min(sk_role_slices(qkvn, d), c->prefill_sk == 1 ? 8 : c->prefill_sk) : 1;
   if (S <= 1 || c->gemm_naive || !c->qkv_rope_fused || n > SK_CHUNK_ROWS || n > c->sk_sl_min_rows || (size_t)S * SK_CHUNK_ROWS * (size_t)qkvn > c->skpart_floats) return false;
   GemmArgs g;
@@ -602,14 +604,14 @@ bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, b
   g.part = c->skpart; g.part_stride = (long)SK_CHUNK_ROWS * qkvn;
   if (!gemm_sk_supported(g)) return false;
   if (!launch_gemm_sk_partials(g, s)) { c->launch_refused = true; return true; }
-  launch_sk_rope_scatter(g.part, g.part_stride, S, c->Qh, kc, vc, c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s);
+  launch_sk_rope_scatter(g.part, g.part_stride, S, c->Qh, kc, vc, c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, c->hd);
   return true;
 }
 
 int gelu_flag(const dtk_ctx* c) { return c->cfg.vit_gelu_tanh ? GEMM_GELU_TANH : GEMM_GELU_ERF; }
 
-bf16_t* kcache(dtk_ctx* c, int layer) { return c->kv + (size_t)layer * 2 * c->KVH * c->Tmax * 128; }
-bf16_t* vcache(dtk_ctx* c, int layer) { return kcache(c, layer) + (size_t)c->KVH * c->Tmax * 128; }
+bf16_t* kcache(dtk_ctx* c, int layer) { return c->kv + (size_t)layer * 2 * c->KVH * c->Tmax * c->hd; }
+bf16_t* vcache(dtk_ctx* c, int layer) { return kcache(c, layer) + (size_t)c->KVH * c->Tmax * c->hd; }
 
 // ViT trunk + (optionally) MAP head for the image already in pixels_dev.
 void vit_forward(dtk_ctx* c, bool want_pooled, hipStream_t s, int B = 1) {
@@ -698,22 +700,22 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   sa.x = c->x; sa.d = c->d; sa.tok_ring = c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
   if (c->mb_single) launch_sample_mb(sa, s); else launch_sample(sa, s);
-  const float scale = 1.0f / sqrtf(128.f);
+  const float scale = 1.0f / sqrtf((float)c->hd);
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
     GemvArgs g{};
-    g.eps = c->cfg.rms_eps; g.st = c->st; g.T_max = c->Tmax; g.d = c->d; g.ff = c->ff; g.H = c->H; g.KVH = c->KVH;
+    g.eps = c->cfg.rms_eps; g.st = c->st; g.T_max = c->Tmax; g.d = c->d; g.ff = c->ff; g.H = c->H; g.KVH = c->KVH; g.hd = c->hd;
     g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin;
     g.pm = c->pm; g.pl = c->pl; g.po = c->po; g.S = c->S;
     // 1. input_layernorm + q/k/v projections + RoPE + KV append
-    g.W = w.wqkv; g.W8 = w.q_wqkv; g.wscale = w.s_wqkv; g.N = c->d + 2 * c->KVH * 128; g.K = c->d; g.x = c->x; g.norm_w = w.ln1;
+    g.W = w.wqkv; g.W8 = w.q_wqkv; g.wscale = w.s_wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1;
     g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l);
     launch_gemv(PRO_RMSNORM, EPI_QKV, g, s);
     // 2. split-K attention over the cache
     AttnDecArgs ad;
     ad.q = c->q; ad.kcache = kcache(c, l); ad.vcache = vcache(c, l); ad.st = c->st;
     ad.pm = c->pm; ad.pl = c->pl; ad.po = c->po; ad.H = c->H; ad.S = c->S; ad.T_max = c->Tmax; ad.G = c->H / c->KVH;
-    ad.scale = scale;
+    ad.scale = scale; ad.hd = c->hd;
     ad.threads = c->attn_threads;
     ad.combine = (!ad.threads && short_ctx && c->attn_combine == 2) ? 3 : c->attn_combine; ad.out = c->attn_out; ad.counters = c->attn_ctr;
     if (ad.threads && ad.combine == 1) ad.combine = 2;      // the tile kernel has no in-kernel combine
@@ -911,7 +913,7 @@ void ensure_fp8_weights(dtk_ctx* c) {
   if (c->wfmt != 1 || c->fp8_ready) return;
   for (int l = 0; l < c->L; ++l) {
     LayerW& w = c->layers[l];
-    launch_quant_fp8_rows(w.wqkv, w.q_wqkv, w.s_wqkv, c->d + 2 * c->KVH * 128, c->d, c->stream);
+    launch_quant_fp8_rows(w.wqkv, w.q_wqkv, w.s_wqkv, c->d + 2 * c->KVH * c->hd, c->d, c->stream);
     launch_quant_fp8_rows(w.wo, w.q_wo, w.s_wo, c->d, c->d, c->stream);
     launch_quant_fp8_rows(w.wgu, w.q_wgu, w.s_wgu, 2 * c->ff, c->d, c->stream);
     launch_quant_fp8_rows(w.wdown, w.q_wdown, w.s_wdown, c->d, c->ff, c->stream);
@@ -932,7 +934,7 @@ void ensure_prefill_tiles(dtk_ctx* c) {
   if (c->nb > 0 && c->wfmt != 1) { ensure_tiled_weights(c); c->ptiled_ready = true; return; }
   for (int l = 0; l < c->L; ++l) {
     LayerW& w = c->layers[l];
-    launch_retile(w.wqkv, w.p_wqkv, c->d + 2 * c->KVH * 128, c->d, c->stream);
+    launch_retile(w.wqkv, w.p_wqkv, c->d + 2 * c->KVH * c->hd, c->d, c->stream);
     launch_retile(w.wo, w.p_wo, c->d, c->d, c->stream);
     launch_retile(w.wgu, w.p_wgu, 2 * c->ff, c->d, c->stream);
     launch_retile(w.wdown, w.p_wdown, c->d, c->ff, c->stream);
@@ -1034,15 +1036,15 @@ int ensure_graph(dtk_ctx* c) {
 void compute_rope_tables(const dtk_config& cfg, std::vector<uint16_t>& cosv, std::vector<uint16_t>& sinv) {
   // HF LlamaRotaryEmbedding: inv_freq = 1/theta^(2i/hd) (/factor for 'linear'), fp32;
   // freqs = pos * inv_freq in fp32; cos/sin cast to the activation dtype (bf16).
-  const int T = cfg.max_positions;
-  cosv.resize((size_t)T * 64); sinv.resize((size_t)T * 64);
-  for (int i = 0; i < 64; ++i) {
-    float inv = (float)(1.0 / pow((double)cfg.rope_theta, (double)(2 * i) / 128.0));
+  const int T = cfg.max_positions, hd = cfg.head_dim, hd2 = hd / 2;
+  cosv.resize((size_t)T * hd2); sinv.resize((size_t)T * hd2);
+  for (int i = 0; i < hd2; ++i) {
+    float inv = (float)(1.0 / pow((double)cfg.rope_theta, (double)(2 * i) / (double)hd));
     if (cfg.rope_factor > 0.f && cfg.rope_factor != 1.f) inv = inv / cfg.rope_factor;
     for (int p = 0; p < T; ++p) {
       const float fr = inv * (float)p;
-      cosv[(size_t)p * 64 + i] = host_f2bf((float)cos((double)fr));
-      sinv[(size_t)p * 64 + i] = host_f2bf((float)sin((double)fr));
+      cosv[(size_t)p * hd2 + i] = host_f2bf((float)cos((double)fr));
+      sinv[(size_t)p * hd2 + i] = host_f2bf((float)sin((double)fr));
     }
   }
 }
@@ -1082,7 +1084,13 @@ const char* dtk_last_error(const dtk_ctx* ctx) {
 int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   if (!cfg || !out) return fail(nullptr, DTK_ERR_ARG, "dtk_create: null argument");
   *out = nullptr;
-  if (cfg->head_dim != 128) return fail(nullptr, DTK_ERR_ARG, "head_dim must be 128 (got %d)", cfg->head_dim);
+  if (cfg->head_dim != 128 && cfg->head_dim != 64) return fail(nullptr, DTK_ERR_ARG, "head_dim must be 128 or 64 (got %d)", cfg->head_dim);
+  // head_dim 64 (TinyLlama) has the single-sequence kernels only: the batched-slot step (its q/k/v epilogues, prefix / tail attention,
+  // MXFP8 path, kv_fork) is written for 128 — refused here, before anything is allocated or launched
+  if (cfg->head_dim == 64 && cfg->reserved[0] > 0)
+    return fail(nullptr, DTK_ERR_ARG, "head_dim 64: batched decode slots (batch_slots = %d) have no head_dim-64 kernels yet", cfg->reserved[0]);
+  if (cfg->head_dim == 64 && getenv("DTK_ATTN_THREADS") && atoi(getenv("DTK_ATTN_THREADS")) == 0)   // k_attn_decode / _head: hd 128 only
+    return fail(nullptr, DTK_ERR_ARG, "DTK_ATTN_THREADS=0: the contiguous-split decode attention has no head_dim-64 kernel (256, 512 or 1024)");
   if (cfg->hidden != cfg->heads * cfg->head_dim)
     return fail(nullptr, DTK_ERR_ARG, "hidden (%d) != heads*head_dim", cfg->hidden);
   if (cfg->reserved[2] < 0 || (cfg->reserved[2] > 0 && cfg->heads % cfg->reserved[2] != 0))
@@ -1107,7 +1115,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   dtk_ctx* c = new dtk_ctx();
   c->cfg = *cfg;
   c->device = device;
-  c->d = cfg->hidden; c->L = cfg->layers; c->H = cfg->heads; c->ff = cfg->ffn; c->V = cfg->vocab;
+  c->d = cfg->hidden; c->L = cfg->layers; c->H = cfg->heads; c->ff = cfg->ffn; c->V = cfg->vocab; c->hd = cfg->head_dim;
   c->mb_single = c->mb_batch = sample_mb_supported(cfg->vocab);   // default sampling is greedy: the multi-block chain serves it
   c->KVH = cfg->reserved[2] > 0 ? cfg->reserved[2] : cfg->heads;      // GQA (v2: LLaMA-3.1, 32 / 8)
   c->proj_bias = (cfg->reserved[3] & DTK_ARCH_PROJ_NO_BIAS) == 0;     // v2 connector: Linear(3*D -> d, bias=False)
@@ -1136,6 +1144,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   c->attn_combine = !ac ? 0 : (!strcmp(ac, "consumer") ? 0 : (!strcmp(ac, "inkernel") ? 1 : 2));
   c->attn_threads = 512;
   if (const char* at = getenv("DTK_ATTN_THREADS")) c->attn_threads = atoi(at);
+
   if (c->S > 16) c->S = 16;
   if (const char* fm = getenv("DTK_ATTN_FULL_MAX")) c->attn_full_max = atoi(fm);
   if (const char* gv = getenv("DTK_GEMV_VARIANTS")) {  // "epi:variant,epi:variant" (tuning aid)
@@ -1190,7 +1199,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   CCHK(hipStreamSynchronize(c->stream));
 #undef CCHK
   // accounting: W = decoder layers + final norm + lm_head, K = 2*L*d*2
-  const uint64_t kvd = (uint64_t)c->KVH * 128;
+  const uint64_t kvd = (uint64_t)c->KVH * c->hd;
   const uint64_t attn_lin = (uint64_t)2 * c->d * c->d + 2 * kvd * c->d;   // q, o: d x d; k, v: kvd x d
   const uint64_t per_layer = attn_lin + (uint64_t)3 * c->d * c->ff + 2 * (uint64_t)c->d;
   c->stats.weight_bytes_per_token = 2 * (per_layer * c->L + (uint64_t)c->d + (uint64_t)c->V * c->d);
@@ -1378,9 +1387,10 @@ int dtk_vit_encode(dtk_ctx* c, const float* pixels, int batch, void* feats_out, 
 
 static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_dst, DecState* st_dst, bool is_single,
                         const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
-  const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
+  const int hd = c ? c->hd : 128;
+  const size_t kv_layer = c ? (size_t)2 * c->KVH * c->Tmax * hd : 0;
   auto kc = [&](int l) { return kvbase + (size_t)l * kv_layer; };
-  auto vc = [&](int l) { return kvbase + (size_t)l * kv_layer + (size_t)c->KVH * c->Tmax * 128; };
+  auto vc = [&](int l) { return kvbase + (size_t)l * kv_layer + (size_t)c->KVH * c->Tmax * hd; };
   if (!c || !ids || T < 1) return fail(c, DTK_ERR_ARG, "dtk_prefill: bad argument");
   if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
   std::lock_guard<std::mutex> vit_guard(c->vit_mu);
@@ -1442,22 +1452,22 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
     const int lo = std::max(img_start, start), hi = img_start + c->nImg;
     if (hi > lo) launch_copy_rows(c->IMG + (size_t)(lo - img_start) * d, d, c->X + (size_t)(lo - start) * d, d, hi - lo, d, s);
   }
-  const float scale = 1.0f / sqrtf(128.f);
+  const float scale = 1.0f / sqrtf((float)hd);
   c->launch_refused = false;      // (a batched step that was refused leaves it set: this prefill judges its own launches)
   launch_rmsnorm_rows(c->X, d, c->layers[0].ln1, c->Xn, d, n, d, c->cfg.rms_eps, s);
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
-    const int qkvn = d + 2 * c->KVH * 128;
+    const int qkvn = d + 2 * c->KVH * hd;
     if (!qkv_rope_fused(c, w, n, start, kc(l), vc(l), s)) {
       gemm_role(c, c->Xn, d, w.wqkv, w.p_wqkv, d, nullptr, 0, c->QKV, qkvn, n, qkvn, d, 0, nullptr, nullptr, 0);
-      launch_rope_scatter(c->QKV, c->Qh, kc(l), vc(l), c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s);
+      launch_rope_scatter(c->QKV, c->Qh, kc(l), vc(l), c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, hd);
     }
     AttnArgs a;
-    a.Q = c->Qh; a.q_sh = (long)n * 128; a.q_st = 128;
-    a.K = kc(l); a.k_sh = (long)c->Tmax * 128; a.k_st = 128;
-    a.V = vc(l); a.v_sh = (long)c->Tmax * 128; a.v_st = 128;
-    a.O = c->AO; a.o_sh = 128; a.o_st = d;
-    a.H = c->H; a.Tq = n; a.Tk = T; a.hd = 128; a.causal = 1; a.q_offset = start; a.scale = scale; a.impl = c->attn_impl; a.kv_group = c->H / c->KVH;
+    a.Q = c->Qh; a.q_sh = (long)n * hd; a.q_st = hd;
+    a.K = kc(l); a.k_sh = (long)c->Tmax * hd; a.k_st = hd;
+    a.V = vc(l); a.v_sh = (long)c->Tmax * hd; a.v_st = hd;
+    a.O = c->AO; a.o_sh = hd; a.o_st = d;
+    a.H = c->H; a.Tq = n; a.Tk = T; a.hd = hd; a.causal = 1; a.q_offset = start; a.scale = scale; a.impl = c->attn_impl; a.kv_group = c->H / c->KVH;
     launch_attention(a, s);
     gemm_role(c, c->AO, d, w.wo, w.p_wo, d, c->X, d, c->X, d, n, d, d, GEMM_RESIDUAL, w.ln2, c->Xn, d);     // + post_attention_layernorm -> Xn
     bool fused = false;      // gate/up + SiLU*mul in one launch where the role is one chain and the shape takes k_gemm_g3 (bit-identical to the pair below)
@@ -1956,7 +1966,7 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
       GemvArgs g{};
       if (plain) {   // cost of the fused prologue / epilogue = full role - this
         g.eps = c->cfg.rms_eps; g.y = c->GU;
-        if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * 128; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; }
+        if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; }
         else if (role == 1) { g.W = w.wo; g.N = c->d; g.K = c->d; g.x = c->attn_out; g.norm_w = w.ln1; }
         else if (role == 2) { g.W = w.wgu; g.N = 2 * c->ff; g.K = c->d; g.x = c->x; g.norm_w = w.ln2; }
         else if (role == 3) { g.W = w.wdown; g.N = c->d; g.K = c->ff; g.x = c->act; g.norm_w = w.ln2; }
@@ -1964,9 +1974,9 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
         launch_gemv_variant(plain == 2 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, variant, g, s);
         continue;
       }
-      g.eps = c->cfg.rms_eps; g.st = c->st; g.T_max = c->Tmax; g.d = c->d; g.ff = c->ff; g.H = c->H; g.KVH = c->KVH;
+      g.eps = c->cfg.rms_eps; g.st = c->st; g.T_max = c->Tmax; g.d = c->d; g.ff = c->ff; g.H = c->H; g.KVH = c->KVH; g.hd = c->hd;
       g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.pm = c->pm; g.pl = c->pl; g.po = c->po; g.S = c->S;
-      if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * 128; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l); launch(PRO_RMSNORM, EPI_QKV, g); }
+      if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l); launch(PRO_RMSNORM, EPI_QKV, g); }
       else if (role == 1) { g.W = w.wo; g.N = c->d; g.K = c->d; g.x = c->attn_out; g.y = c->q; launch(PRO_COPY, EPI_RESID, g); }
       else if (role == 2) { g.W = w.wgu; g.N = 2 * c->ff; g.K = c->d; g.x = c->x; g.norm_w = w.ln2; g.y = c->act; launch(PRO_RMSNORM, EPI_SWIGLU, g); }
       else if (role == 3) { g.W = w.wdown; g.N = c->d; g.K = c->ff; g.x = c->act; g.y = c->q; launch(PRO_COPY, EPI_RESID, g); }
@@ -2127,6 +2137,7 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
   else if (!strcmp(name, "attn_threads") || !strcmp(name, "attn_splits") || !strcmp(name, "attn_combine")) {
     if (!strcmp(name, "attn_threads")) {
       if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(c, DTK_ERR_ARG, "attn_threads must be 0, 256, 512 or 1024");
+      if (value == 0 && c->hd == 64) return fail(c, DTK_ERR_ARG, "attn_threads 0 (contiguous splits) has no head_dim-64 kernel: 256, 512 or 1024");
       c->attn_threads = value;
     } else if (!strcmp(name, "attn_splits")) {
       if (value < 1 || value > 16) return fail(c, DTK_ERR_ARG, "attn_splits must be 1..16");

@@ -37,6 +37,7 @@ struct GemvArgs {
   int ff;                // EPI_SWIGLU: N == 2*ff
   int H;                 // EPI_QKV: query heads; rows = [H q heads | KVH k heads | KVH v heads] x 128, N == (H + 2*KVH)*128
   int KVH;               //          key/value heads (GQA: H % KVH == 0; MHA: KVH == H)
+  int hd = 128;          // EPI_QKV / PRO_ATTN: head dim, 128 or 64 (the "128" of the layouts above; every other role ignores it)
 };
 
 void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s);
@@ -55,6 +56,7 @@ struct AttnDecArgs {
   unsigned* counters;    // [H] arrival tickets, zero between launches
   int G;                 // query heads per kv head (1 = MHA)
   int threads;           // 0: contiguous key ranges per split (k_attn_decode); 256 | 512 | 1024: k_attn_decode_t, tiles dealt round-robin to the splits
+  int hd = 128;          // head dim (the "128" of the layouts above): 128, or 64 with threads != 0 (k_attn_decode_t / k_attn_combine only)
 };
 void launch_attn_decode(const AttnDecArgs& a, hipStream_t s);
 
@@ -251,7 +253,8 @@ bool launch_gemm_g3_sliced(const GemmArgs& a, hipStream_t s);        // the same
 bool launch_gemm_sk_partials(const GemmArgs& a, hipStream_t s);     // the GEMM alone: a.part holds the slices' sums afterwards
 // the q/k/v role's reduction fused with k_rope_scatter (same rounding points: bf16 of the summed slices, then RoPE)
 void launch_sk_rope_scatter(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
-                            const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s);
+                            const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s,
+                            int hd = 128);
 void launch_sk_reduce_swiglu(const GemmArgs& a, bf16_t* ACT, int ldact, hipStream_t s);    // a sliced gate/up role's partials (a.part, a.N = 2 ff) -> SiLU(gate) * up, [M][ff]
 void launch_sk_reduce(const GemmArgs& a, const bf16_t* norm_w, bf16_t* Y, int ldy, float eps, hipStream_t s);
 void set_gemm_bk(int v);     // k-tile of the 64x64 GEMM: 64 | 128
@@ -274,10 +277,10 @@ void launch_copy_rows(const bf16_t* src, int lds_, bf16_t* dst, int ldd, int M, 
                       hipStream_t s);
 void launch_im2col(const float* pixels, bf16_t* patches, int image, int patch, int ldp,
                    hipStream_t s);
-// q,k RoPE + scatter of one prefill chunk: QKV [T][3d] -> Qh [H][T][128], caches at start_pos+t
+// q,k RoPE + scatter of one prefill chunk: QKV [T][(H + 2 KVH) hd] -> Qh [H][T][hd], caches at start_pos+t (hd 128 or 64)
 void launch_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                          const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos,
-                         int H, int KVH, int T_max, hipStream_t s);
+                         int H, int KVH, int T_max, hipStream_t s, int hd = 128);
 
 struct AttnArgs {
   const bf16_t* Q; long q_sh; long q_st;   // element strides: head, token

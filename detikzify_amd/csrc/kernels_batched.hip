@@ -1133,50 +1133,57 @@ void launch_im2col(const float* pixels, bf16_t* patches, int image, int patch, i
   hipLaunchKernelGGL(k_im2col, dim3(np * np), dim3(256), 0, s, pixels, patches, image, patch, ldp);
 }
 
-// grid (T, H), 64 threads: thread i owns the RoPE pair (i, i+64) of q head h; blocks h < KVH also rotate k head h
-// and copy v head h.  QKV row layout: [H q heads | KVH k heads | KVH v heads] x 128.
+// grid (T, H), HD / 2 threads: thread i owns the RoPE pair (i, i + HD/2) of q head h; blocks h < KVH also rotate k head h
+// and copy v head h.  QKV row layout: [H q heads | KVH k heads | KVH v heads] x HD (HD = 128, or 64: TinyLlama).
+template <int HD>
 __global__ void k_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                                const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos,
                                int H, int KVH, int T_max) {
+  constexpr int HD2 = HD / 2;
   const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;
-  const int qd = H * 128, kvd = KVH * 128;
+  const int qd = H * HD, kvd = KVH * HD;
   const int pos = start_pos + t;
   const bf16_t* row = QKV + (size_t)t * (qd + 2 * kvd);
-  const float c = bf2f(cos_t[(size_t)pos * 64 + i]);
-  const float s = bf2f(sin_t[(size_t)pos * 64 + i]);
+  const float c = bf2f(cos_t[(size_t)pos * HD2 + i]);
+  const float s = bf2f(sin_t[(size_t)pos * HD2 + i]);
   {
-    const float x1 = bf2f(row[h * 128 + i]), x2 = bf2f(row[h * 128 + i + 64]);
-    bf16_t* dst = Qh + ((size_t)h * T + t) * 128;
+    const float x1 = bf2f(row[h * HD + i]), x2 = bf2f(row[h * HD + i + HD2]);
+    bf16_t* dst = Qh + ((size_t)h * T + t) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + 64] = f2bf(rbf(x2 * c) + rbf(x1 * s));
+    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   if (h >= KVH) return;
   {
-    const float x1 = bf2f(row[qd + h * 128 + i]), x2 = bf2f(row[qd + h * 128 + i + 64]);
-    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * 128;
+    const float x1 = bf2f(row[qd + h * HD + i]), x2 = bf2f(row[qd + h * HD + i + HD2]);
+    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + 64] = f2bf(rbf(x2 * c) + rbf(x1 * s));
+    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   {
-    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * 128;
-    dst[i] = row[qd + kvd + h * 128 + i];
-    dst[i + 64] = row[qd + kvd + h * 128 + i + 64];
+    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * HD;
+    dst[i] = row[qd + kvd + h * HD + i];
+    dst[i + HD2] = row[qd + kvd + h * HD + i + HD2];
   }
 }
 void launch_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                          const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH,
-                         int T_max, hipStream_t s) {
-  hipLaunchKernelGGL(k_rope_scatter, dim3(T, H), dim3(64), 0, s, QKV, Qh, kcache, vcache, cos_t,
-                     sin_t, T, start_pos, H, KVH, T_max);
+                         int T_max, hipStream_t s, int hd) {
+  if (hd == 64)
+    hipLaunchKernelGGL(k_rope_scatter<64>, dim3(T, H), dim3(32), 0, s, QKV, Qh, kcache, vcache, cos_t,
+                       sin_t, T, start_pos, H, KVH, T_max);
+  else
+    hipLaunchKernelGGL(k_rope_scatter<128>, dim3(T, H), dim3(64), 0, s, QKV, Qh, kcache, vcache, cos_t,
+                       sin_t, T, start_pos, H, KVH, T_max);
 }
 
 // The q/k/v role as a sliced-K GEMM: its reduction IS k_rope_scatter's input — the slices' fp32 sums added in order, rounded to bf16 (the
 // Linear's output: what k_sk_reduce would have stored), then k_rope_scatter's arithmetic; no [T][qkvn] buffer in between.
-template <int S>
+template <int S, int HD>
 __global__ void k_sk_rope_scatter(const float* part, long part_stride, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                                   const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max) {
+  constexpr int HD2 = HD / 2;
   const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;
-  const int qd = H * 128, kvd = KVH * 128, N = qd + 2 * kvd;
+  const int qd = H * HD, kvd = KVH * HD, N = qd + 2 * kvd;
   const int pos = start_pos + t;
   const float* row = part + (size_t)t * N;
   auto val = [&](int n) {
@@ -1185,30 +1192,32 @@ __global__ void k_sk_rope_scatter(const float* part, long part_stride, bf16_t* Q
     for (int k = 1; k < S; ++k) v += row[(size_t)k * (size_t)part_stride + n];
     return rbf(v);
   };
-  const float c = bf2f(cos_t[(size_t)pos * 64 + i]);
-  const float s = bf2f(sin_t[(size_t)pos * 64 + i]);
+  const float c = bf2f(cos_t[(size_t)pos * HD2 + i]);
+  const float s = bf2f(sin_t[(size_t)pos * HD2 + i]);
   {
-    const float x1 = val(h * 128 + i), x2 = val(h * 128 + i + 64);
-    bf16_t* dst = Qh + ((size_t)h * T + t) * 128;
+    const float x1 = val(h * HD + i), x2 = val(h * HD + i + HD2);
+    bf16_t* dst = Qh + ((size_t)h * T + t) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + 64] = f2bf(rbf(x2 * c) + rbf(x1 * s));
+    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   if (h >= KVH) return;
   {
-    const float x1 = val(qd + h * 128 + i), x2 = val(qd + h * 128 + i + 64);
-    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * 128;
+    const float x1 = val(qd + h * HD + i), x2 = val(qd + h * HD + i + HD2);
+    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + 64] = f2bf(rbf(x2 * c) + rbf(x1 * s));
+    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   {
-    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * 128;
-    dst[i] = f2bf(val(qd + kvd + h * 128 + i));
-    dst[i + 64] = f2bf(val(qd + kvd + h * 128 + i + 64));
+    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * HD;
+    dst[i] = f2bf(val(qd + kvd + h * HD + i));
+    dst[i + HD2] = f2bf(val(qd + kvd + h * HD + i + HD2));
   }
 }
 void launch_sk_rope_scatter(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
-                            const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s) {
-#define SK_ROPE(S_) case S_: hipLaunchKernelGGL(k_sk_rope_scatter<S_>, dim3(T, H), dim3(64), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, start_pos, H, KVH, T_max); break;
+                            const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s,
+                            int hd) {
+#define SK_ROPE(S_) case S_: if (hd == 64) hipLaunchKernelGGL((k_sk_rope_scatter<S_, 64>), dim3(T, H), dim3(32), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, start_pos, H, KVH, T_max); \
+                             else hipLaunchKernelGGL((k_sk_rope_scatter<S_, 128>), dim3(T, H), dim3(64), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, start_pos, H, KVH, T_max); break;
   switch (kslices) { SK_ROPE(1) SK_ROPE(2) SK_ROPE(3) SK_ROPE(4) SK_ROPE(5) SK_ROPE(6) SK_ROPE(7) SK_ROPE(8) default: break; }
 #undef SK_ROPE
 }
@@ -1292,7 +1301,8 @@ __global__ __launch_bounds__(256) void k_attention(AttnArgs a) {
   }
 }
 
-// MFMA flash attention for the ViT (hd 72, 729 x 729, bidirectional) and the decoder prefill (hd 128, causal).
+// MFMA flash attention for the ViT (hd 72, 729 x 729, bidirectional) and the decoder prefill (hd 128 / 64, causal; hd 64 = TinyLlama:
+// 8 chunks per row, 2 k-steps, 4 O^T tiles, row stride 72 like hd 72).
 // One block = 4 waves = 64 queries, a wave owns 16 queries; key tiles of 64 staged through LDS (register
 // prefetch of the next tile under the MFMAs).  Everything is computed TRANSPOSED so that a lane's MFMA
 // column is always "its" query (lane & 15):
@@ -1467,7 +1477,7 @@ __global__ __launch_bounds__(256) void k_attention_mfma(AttnArgs a) {
 }
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {
-  const bool can_mfma = (a.hd == 72 || a.hd == 128) && (a.q_st % 8 == 0) && (a.k_st % 8 == 0) && (a.v_st % 8 == 0) &&
+  const bool can_mfma = (a.hd == 64 || a.hd == 72 || a.hd == 128) && (a.q_st % 8 == 0) && (a.k_st % 8 == 0) && (a.v_st % 8 == 0) &&
                         (a.o_st % 4 == 0) && (a.q_sh % 8 == 0) && (a.k_sh % 8 == 0) && (a.v_sh % 8 == 0) && (a.o_sh % 4 == 0);
   // the choice must not depend on Tq: a tail prefill after a KV-prefix reuse (1 query) and the full prefill (all queries) have
   // to round identically, and they do when the same kernel scans the same 64-key tiles (a query's result does not depend on
@@ -1476,6 +1486,7 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
   if (mfma) {
     dim3 grid((a.Tq + 63) / 64, a.H, a.nbatch > 0 ? a.nbatch : 1);
     if (a.hd == 72) hipLaunchKernelGGL((k_attention_mfma<72>), grid, dim3(256), 0, s, a);
+    else if (a.hd == 64) hipLaunchKernelGGL((k_attention_mfma<64>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_attention_mfma<128>), grid, dim3(256), 0, s, a);
     return;
   }

@@ -23,17 +23,19 @@
 #include "gemv_inl.h"
 
 // Epilogue of one output unit (one lane per wave): `a0` is the fp32 dot product of the unit's row (paired epilogues:
-// a0 / a1 = the two rows of the pair: RoPE partners i, i+64 or gate, up).  Same HF rounding points as the reference.
+// a0 / a1 = the two rows of the pair: RoPE partners i, i + HD/2 or gate, up).  HD = head dim (EPI_QKV): 128, or 64 (TinyLlama).  Same HF rounding points as the reference.
 // `pre0` / `pre1`: operands the epilogue needs from memory, loaded at kernel start by the lane that runs it (EPI_RESID: the
 // residual value y[u]; EPI_QKV: cos / sin of (pos, i)) — a dependent load in the epilogue was ~1 us of exposed latency at
 // the very end of every wave; `pos` likewise (read once at kernel start).
-template <int EPI, bool F8>
+template <int EPI, bool F8, int HD = 128>
 __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0, float a1, float pre0, float pre1, int pos) {
+    constexpr int HD2 = HD / 2, HSH = HD == 128 ? 6 : 5;   // u >> HSH = head block of unit u
+    static_assert(HD == 128 || HD == 64, "head dim 128 or 64");
     if (F8) {  // per-output-channel power-of-two scale (exact)
       if (EPI == EPI_QKV) {
-        const int r0 = (u >> 6) * 128 + (u & 63);
+        const int r0 = (u >> HSH) * HD + (u & (HD2 - 1));
         a0 *= a.wscale[r0];
-        a1 *= a.wscale[r0 + 64];
+        a1 *= a.wscale[r0 + HD2];
       } else if (EPI == EPI_SWIGLU) {
         a0 *= a.wscale[u];
         a1 *= a.wscale[a.ff + u];
@@ -54,24 +56,24 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0
       const float sl = rbf(gte / (1.f + expf(-gte)));
       a.y[u] = f2bf(sl * up);
     } else if (EPI == EPI_QKV) {
-      const int hb = u >> 6, i = u & 63;
+      const int hb = u >> HSH, i = u & (HD2 - 1);
       const int sec = hb < a.H ? 0 : (hb < a.H + a.KVH ? 1 : 2);
       const int head = sec == 0 ? hb : (sec == 1 ? hb - a.H : hb - a.H - a.KVH);
       const float x1 = rbf(a0);      // dim i
-      const float x2 = rbf(a1);  // dim i + 64
+      const float x2 = rbf(a1);  // dim i + HD/2
       if (sec == 2) {
-        bf16_t* dst = a.vcache + ((size_t)head * a.T_max + pos) * 128;
+        bf16_t* dst = a.vcache + ((size_t)head * a.T_max + pos) * HD;
         dst[i] = f2bf(x1);
-        dst[i + 64] = f2bf(x2);
+        dst[i + HD2] = f2bf(x2);
       } else {
         // HF apply_rotary_pos_emb: q*cos + rotate_half(q)*sin, every product a bf16 tensor
         const float c = pre0, s = pre1;
         const float o1 = rbf(rbf(x1 * c) + rbf(-x2 * s));
         const float o2 = rbf(rbf(x2 * c) + rbf(x1 * s));
-        bf16_t* dst = (sec == 0) ? (a.q_out + head * 128)
-                                 : (a.kcache + ((size_t)head * a.T_max + pos) * 128);
+        bf16_t* dst = (sec == 0) ? (a.q_out + head * HD)
+                                 : (a.kcache + ((size_t)head * a.T_max + pos) * HD);
         dst[i] = f2bf(o1);
-        dst[i + 64] = f2bf(o2);
+        dst[i + HD2] = f2bf(o2);
       }
     }
 }
@@ -83,12 +85,16 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0
 // KS > 1: split-K over KS waves of the block — the k-groups of a row (pair) are dealt round-robin to KS waves, whose partial
 // sums meet in LDS in a fixed order (deterministic).  For the N = d roles (o_proj, down: only d rows) this puts KS times the
 // waves, hence loads, in flight per row; the block then owns WAVES / KS row-chunks.
-template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1>
+// HD: head dim of the EPI_QKV rows / the PRO_ATTN partials (128, or 64: a unit is the pair (i, i+32), a head 8 chunks of x).
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128>
 __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   constexpr bool PAIRED = (EPI == EPI_QKV) || (EPI == EPI_SWIGLU);
   constexpr int NR = PAIRED ? 2 * R : R;
   constexpr int THREADS = WAVES * 64;
   constexpr int RW = WAVES / KS;               // row-chunks (of R units) per block
+  constexpr int HD2 = HD / 2, HC = HD / 8;     // RoPE pair distance; 16-byte chunks of x per head
+  constexpr int HSH = HD == 128 ? 6 : 5, CSH = HSH - 2;   // log2(HD2), log2(HC)
+  static_assert(HD == 128 || HD == 64, "head dim 128 or 64");
   static_assert(WAVES % KS == 0 && (KS == 1 || !PERSIST), "split-K variants are not persistent");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* xs = reinterpret_cast<u32x4*>(smem);
@@ -119,9 +125,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       int u = u0 + j;
       if (u >= n_units) u = n_units - 1;  // clamped: inactive tails never fault
       int r0, r1 = 0;
-      if (EPI == EPI_QKV) {   // unit = RoPE pair (i, i+64) of head block hb over [H q | KVH k | KVH v]
-        r0 = (u >> 6) * 128 + (u & 63);
-        r1 = r0 + 64;
+      if (EPI == EPI_QKV) {   // unit = RoPE pair (i, i+HD/2) of head block hb over [H q | KVH k | KVH v]
+        r0 = (u >> HSH) * HD + (u & (HD2 - 1));
+        r1 = r0 + HD2;
       } else if (EPI == EPI_SWIGLU) {
         r0 = u;
         r1 = a.ff + u;
@@ -161,8 +167,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
         if (u >= n_units) u = n_units - 1;
         if (EPI == EPI_RESID) pre0[j] = bf2f(a.y[u]);
         if (EPI == EPI_QKV) {
-          pre0[j] = bf2f(a.rope_cos[(size_t)pos * 64 + (u & 63)]);
-          pre1[j] = bf2f(a.rope_sin[(size_t)pos * 64 + (u & 63)]);
+          pre0[j] = bf2f(a.rope_cos[(size_t)pos * HD2 + (u & (HD2 - 1))]);
+          pre1[j] = bf2f(a.rope_sin[(size_t)pos * HD2 + (u & (HD2 - 1))]);
         }
       }
     }
@@ -249,8 +255,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
     // s = 0, 1, 2, ... in that order, as in k_attn_combine.
     const int S = a.S;
     for (int c = tid; c < K8; c += THREADS) {
-      const int head = c >> 4;       // 16 chunks of 8 dims per 128-dim head
-      const int d0 = (c & 15) * 8;
+      const int head = c >> CSH;     // HC chunks of 8 dims per head (16 at hd 128, 8 at hd 64)
+      const int d0 = (c & (HC - 1)) * 8;
       const float* pmh = a.pm + head * S;
       const float* plh = a.pl + head * S;
       float M = -1e30f;
@@ -274,7 +280,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
           const int sj = ok ? s0 + j : s0;
           m4[j] = ok ? pmh[sj] : -1e30f;
           l4[j] = ok ? plh[sj] : 0.f;
-          const f32x4* po4 = reinterpret_cast<const f32x4*>(a.po + ((size_t)(head * S + sj)) * 128 + d0);
+          const f32x4* po4 = reinterpret_cast<const f32x4*>(a.po + ((size_t)(head * S + sj)) * HD + d0);
           p0[j] = po4[0];
           p1[j] = po4[1];
         }
@@ -352,7 +358,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       for (int j = 0; j < R; ++j) {
         const int u = cur + j;
         if (u >= n_units) break;
-        gemv_epilogue<EPI, F8>(a, u, PAIRED ? acc[2 * j] : acc[j], PAIRED ? acc[2 * j + 1] : 0.f, q0[j], q1[j], pos);
+        gemv_epilogue<EPI, F8, HD>(a, u, PAIRED ? acc[2 * j] : acc[j], PAIRED ? acc[2 * j + 1] : 0.f, q0[j], q1[j], pos);
       }
     }
     if (!PERSIST || unit0 >= n_units) break;
@@ -382,6 +388,9 @@ static void launch_gemv_t(const GemvArgs& a, hipStream_t s, int blocks_per_cu) {
     if (grid > cap) grid = cap;
   }
   const size_t lds = (size_t)(a.K >> 3) * 16 + 64 + 1024;   // x (bf16) + per-wave RMSNorm partials + split-K partials
+  if constexpr (EPI == EPI_QKV || PRO == PRO_ATTN) {         // the roles whose layout is per head
+    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 64>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
+  }
   hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS>), dim3(grid), dim3(WAVES * 64), lds, s, a);
 }
 
@@ -490,6 +499,9 @@ static void launch_gemv_f8_t(const GemvArgs& a, hipStream_t s) {
   int grid = (n_units + per_block - 1) / per_block;
   if (PERSIST && grid > num_cus() * BPC) grid = num_cus() * BPC;
   const size_t lds = (size_t)(a.K >> 3) * 16 + 64 + 1024;
+  if constexpr (EPI == EPI_QKV || PRO == PRO_ATTN) {
+    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, true, 1, 64>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
+  }
   hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, true>), dim3(grid), dim3(WAVES * 64), lds, s, a);
 }
 // fp8-weight decode GEMVs (requires K % 16 == 0); same roles as the bf16 defaults.  An fp8 row is half
@@ -723,11 +735,12 @@ __global__ __launch_bounds__(256) void k_attn_decode(AttnDecArgs a) {
   }
 }
 
-// Reduction of the S split-K partials of every head: one 128-thread block per head, thread = dim.
+// Reduction of the S split-K partials of every head: one HD-thread block per head, thread = dim.
 // A kernel boundary (not an in-launch hand-off) publishes the partials: measured cheaper than both
 // the consumer-side combine in o_proj's prologue (133 KB re-read by every block) and a
 // last-arriver combine inside k_attn_decode (agent-scope stores + ticket + serialized loads).
-__global__ __launch_bounds__(128) void k_attn_combine(AttnDecArgs a) {
+template <int HD = 128>
+__global__ __launch_bounds__(HD) void k_attn_combine(AttnDecArgs a) {
   const int h = blockIdx.x, t = threadIdx.x;
   const int S = a.S;
   // all loads first (one memory round trip), then the arithmetic
@@ -738,7 +751,7 @@ __global__ __launch_bounds__(128) void k_attn_combine(AttnDecArgs a) {
     const int ss = ok ? s : 0;
     pm[s] = ok ? a.pm[h * S + ss] : -1e30f;
     pl[s] = ok ? a.pl[h * S + ss] : 0.f;
-    po[s] = ok ? a.po[((size_t)(h * S + ss)) * 128 + t] : 0.f;
+    po[s] = ok ? a.po[((size_t)(h * S + ss)) * HD + t] : 0.f;
   }
   float M = -1e30f;
 #pragma unroll
@@ -750,7 +763,7 @@ __global__ __launch_bounds__(128) void k_attn_combine(AttnDecArgs a) {
     L += w * pl[s];
     o += w * po[s];
   }
-  a.out[h * 128 + t] = f2bf(o / L);
+  a.out[h * HD + t] = f2bf(o / L);
 }
 
 // Short-context variant: ONE 1024-thread block per head scans all keys (16 waves x 4 row-groups, 4 rows
@@ -853,28 +866,34 @@ __global__ __launch_bounds__(1024) void k_attn_decode_head(AttnDecArgs a) {
 // been read — one dependent memory trip less on the critical path of a latency-bound kernel — and are masked once it has.
 // THREADS = 256 / 512 / 1024 trades blocks for rows per memory round trip (64 / 128 / 256); with S splits one round trip
 // covers S * ROWS keys.  S == 1 writes the normalised bf16 head output itself (no partials, no combine).
-template <int THREADS>
+// HD = 128: a K / V row is 256 B = 16 lanes x 16 B, a wave-load covers 4 rows.  HD = 64 (TinyLlama): a row is 128 B = 8 lanes x
+// 16 B, a wave-load covers 8 rows and each of the 8 lane groups keeps its own online-softmax stream (ROWS = 32 * WAVES).
+template <int THREADS, int HD = 128>
 __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
-  constexpr int WAVES = THREADS / 64, ROWS = WAVES * 16;
+  static_assert(HD == 128 || HD == 64, "head dim 128 or 64");
+  constexpr int LPR = HD / 8;                  // lanes per K / V row (16 B each)
+  constexpr int GPW = 64 / LPR;                // row groups per wave (rows per wave-load)
+  constexpr int LSH = HD == 128 ? 4 : 3;       // log2(LPR)
+  constexpr int WAVES = THREADS / 64, ROWS = WAVES * GPW * 4;
   const int h = blockIdx.x, sp = blockIdx.y, S = a.S;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int sub = lane & 15, grp = lane >> 4;
+  const int sub = lane & (LPR - 1), grp = lane >> LSH;
   const int kvh = h / a.G;
-  const bf16_t* kbase = a.kcache + (size_t)kvh * a.T_max * 128;
-  const bf16_t* vbase = a.vcache + (size_t)kvh * a.T_max * 128;
+  const bf16_t* kbase = a.kcache + (size_t)kvh * a.T_max * HD;
+  const bf16_t* vbase = a.vcache + (size_t)kvh * a.T_max * HD;
   u32x4 kv[4], vv[4];
   auto load_tile = [&](int t) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      int j = t * ROWS + i * (ROWS / 4) + wave * 4 + grp;
+      int j = t * ROWS + i * (ROWS / 4) + wave * GPW + grp;
       j = min(j, a.T_max - 1);        // always a row of the cache; rows at or beyond the context are masked below
-      kv[i] = ld_nt(reinterpret_cast<const u32x4*>(kbase + (size_t)j * 128) + sub);      // a K / V row is read once per token by one block:
-      vv[i] = ld_nt(reinterpret_cast<const u32x4*>(vbase + (size_t)j * 128) + sub);      // non-temporal, like the weights
+      kv[i] = ld_nt(reinterpret_cast<const u32x4*>(kbase + (size_t)j * HD) + sub);      // a K / V row is read once per token by one block:
+      vv[i] = ld_nt(reinterpret_cast<const u32x4*>(vbase + (size_t)j * HD) + sub);      // non-temporal, like the weights
     }
   };
   int t = sp;
   load_tile(t);
-  const u32x4 qv = reinterpret_cast<const u32x4*>(a.q + h * 128)[sub];
+  const u32x4 qv = reinterpret_cast<const u32x4*>(a.q + h * HD)[sub];
   const int n = a.st->pos + 1;        // keys 0..pos (this step's k/v were appended by the QKV kernel)
 
   float m = -1e30f, l = 0.f;
@@ -890,12 +909,12 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
     if (t * ROWS < n) load_tile(t);   // contexts beyond S * ROWS keys: next tile in flight under this one's arithmetic
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int j = tcur * ROWS + i * (ROWS / 4) + wave * 4 + grp;
+      const int j = tcur * ROWS + i * (ROWS / 4) + wave * GPW + grp;
       float s = dot8(qv, kc[i], 0.f);
       s += __shfl_xor(s, 1, 64);
       s += __shfl_xor(s, 2, 64);
       s += __shfl_xor(s, 4, 64);
-      s += __shfl_xor(s, 8, 64);
+      if (LPR == 16) s += __shfl_xor(s, 8, 64);
       s *= a.scale;
       if (j < n) {
         const float mn = fmaxf(m, s);
@@ -911,9 +930,9 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
       }
     }
   }
-  // merge the 4 row-groups of the wave (lanes with equal sub)
+  // merge the GPW row-groups of the wave (lanes with equal sub)
 #pragma unroll
-  for (int off = 16; off <= 32; off <<= 1) {
+  for (int off = LPR; off <= 32; off <<= 1) {
     const float m2 = __shfl_xor(m, off, 64);
     const float l2 = __shfl_xor(l, off, 64);
     const float mn = fmaxf(m, m2);
@@ -926,7 +945,7 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
     }
     m = mn;
   }
-  __shared__ float sm_m[WAVES][16], sm_l[WAVES][16], sm_o[WAVES][16][8];
+  __shared__ float sm_m[WAVES][LPR], sm_l[WAVES][LPR], sm_o[WAVES][LPR][8];
   if (grp == 0) {
     sm_m[wave][sub] = m;
     sm_l[wave][sub] = l;
@@ -934,7 +953,7 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
     for (int e = 0; e < 8; ++e) sm_o[wave][sub][e] = o[e];
   }
   __syncthreads();
-  if (tid < 16) {
+  if (tid < LPR) {
     float M = sm_m[0][tid];
 #pragma unroll
     for (int w = 1; w < WAVES; ++w) M = fmaxf(M, sm_m[w][tid]);
@@ -954,11 +973,11 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
       u32x4 ov;
 #pragma unroll
       for (int e = 0; e < 4; ++e) ov[e] = pack2(oo[2 * e] * invL, oo[2 * e + 1] * invL);
-      reinterpret_cast<u32x4*>(a.out + h * 128)[tid] = ov;
+      reinterpret_cast<u32x4*>(a.out + h * HD)[tid] = ov;
       return;
     }
     const size_t slot = (size_t)h * S + sp;   // partials for k_attn_combine / the consumer-side combine (k_gemv<PRO_ATTN>)
-    f32x4* dst = reinterpret_cast<f32x4*>(a.po + slot * 128 + tid * 8);
+    f32x4* dst = reinterpret_cast<f32x4*>(a.po + slot * HD + tid * 8);
     dst[0] = (f32x4){oo[0], oo[1], oo[2], oo[3]};
     dst[1] = (f32x4){oo[4], oo[5], oo[6], oo[7]};
     if (tid == 0) {
@@ -969,12 +988,21 @@ __global__ __launch_bounds__(THREADS) void k_attn_decode_t(AttnDecArgs a) {
 }
 
 void launch_attn_decode(const AttnDecArgs& a, hipStream_t s) {
+  if (a.hd == 64) {  // TinyLlama: the tile kernel and the combine kernel only (dtk_set_option refuses attn_threads 0 at hd 64)
+    if (!a.threads) return;
+    const dim3 grid(a.H, a.S);
+    if (a.threads >= 1024) hipLaunchKernelGGL((k_attn_decode_t<1024, 64>), grid, dim3(1024), 0, s, a);
+    else if (a.threads >= 512) hipLaunchKernelGGL((k_attn_decode_t<512, 64>), grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((k_attn_decode_t<256, 64>), grid, dim3(256), 0, s, a);
+    if (a.S > 1 && a.combine == 2) hipLaunchKernelGGL(k_attn_combine<64>, dim3(a.H), dim3(64), 0, s, a);
+    return;
+  }
   if (a.threads) {   // tile-interleaved splits (k_attn_decode_t); a.combine: 0 consumer reduces the partials, 2 own kernel; S == 1: direct
     const dim3 grid(a.H, a.S);
     if (a.threads >= 1024) hipLaunchKernelGGL(k_attn_decode_t<1024>, grid, dim3(1024), 0, s, a);
     else if (a.threads >= 512) hipLaunchKernelGGL(k_attn_decode_t<512>, grid, dim3(512), 0, s, a);
     else hipLaunchKernelGGL(k_attn_decode_t<256>, grid, dim3(256), 0, s, a);
-    if (a.S > 1 && a.combine == 2) hipLaunchKernelGGL(k_attn_combine, dim3(a.H), dim3(128), 0, s, a);
+    if (a.S > 1 && a.combine == 2) hipLaunchKernelGGL(k_attn_combine<128>, dim3(a.H), dim3(128), 0, s, a);
     return;
   }
   if (a.combine == 3) {  // one block per head, output written directly
@@ -982,7 +1010,7 @@ void launch_attn_decode(const AttnDecArgs& a, hipStream_t s) {
     return;
   }
   hipLaunchKernelGGL(k_attn_decode, dim3(a.H, a.S), dim3(256), 0, s, a);
-  if (a.combine == 2) hipLaunchKernelGGL(k_attn_combine, dim3(a.H), dim3(128), 0, s, a);
+  if (a.combine == 2) hipLaunchKernelGGL(k_attn_combine<128>, dim3(a.H), dim3(128), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------

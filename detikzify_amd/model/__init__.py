@@ -71,12 +71,12 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
         import json
         cfg = DetikzifyConfig.from_hf_json(str(path / "config.json"))
         cfg.name_or_path = str(path)
-        _require_supported(cfg)
         if max_positions:
             cfg.max_positions = max_positions
         if vit_gelu_tanh is not None:
             cfg.vit_gelu_tanh = int(bool(vit_gelu_tanh))
         cfg.batch_slots, cfg.weight_format = batch_slots, weight_format
+        _require_supported(cfg)
         if synthetic_tokenizer or json.loads((path / "config.json").read_text()).get("synthetic_tokenizer"):
             tokenizer = _synthetic_tokenizer(cfg)
         else:
@@ -93,12 +93,12 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
         _announce_gelu(cfg, path)
     else:
         cfg = preset(model_name_or_path)
-        _require_supported(cfg)
         if max_positions:
             cfg.max_positions = max_positions
         if vit_gelu_tanh is not None:
             cfg.vit_gelu_tanh = int(bool(vit_gelu_tanh))
         cfg.batch_slots, cfg.weight_format = batch_slots, weight_format
+        _require_supported(cfg)
         if synthetic is None:
             raise FileNotFoundError(
                 f"{model_name_or_path!r} is not a local checkpoint directory and there is no network; "
@@ -122,10 +122,14 @@ def _synthetic_tokenizer(cfg: DetikzifyConfig) -> SyntheticTokenizer:
 
 def _require_supported(cfg: DetikzifyConfig) -> None:
     """Shapes the kernels are written for; everything else fails here with the reason, not deep inside dtk_create."""
-    if cfg.head_dim != 128:
+    if cfg.head_dim not in (128, 64):
         raise NotImplementedError(
             f"{cfg.name_or_path or 'this checkpoint'}: decoder head_dim {cfg.head_dim} — the decode / prefill kernels are built "
-            "for head_dim 128 (ds-1.3b, ds-7b, cl-7b, v2-8b); nllg/detikzify-tl-1.1b (TinyLlama, head_dim 64) is not supported yet")
+            "for head_dim 128 (ds-1.3b, ds-7b, cl-7b, v2-8b) and 64 (tl-1.1b)")
+    if cfg.head_dim == 64 and cfg.batch_slots > 0:
+        raise NotImplementedError(
+            f"{cfg.name_or_path or 'this checkpoint'}: batch_slots={cfg.batch_slots} — batched decode slots have no head_dim-64 "
+            "kernels yet (head_dim 64 runs one sequence per context: load with batch_slots=0)")
     if cfg.concat_patches < 1 or ((cfg.vit_image // cfg.vit_patch) ** 2) % cfg.concat_patches:
         raise ValueError(f"concat_patches={cfg.concat_patches} does not divide the tower's {(cfg.vit_image // cfg.vit_patch) ** 2} patches")
 

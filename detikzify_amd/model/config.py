@@ -195,16 +195,40 @@ def _tiny_v2() -> DetikzifyConfig:
                            vision_tower="siglip", name_or_path="detikzify-tiny-v2")
 
 
+def _tiny_tl() -> DetikzifyConfig:
+    # the TinyLlama differences at toy size: decoder head_dim 64 and GQA with G = 8 (8 query heads, 1 kv head), no RoPE
+    # scaling; the same toy ViT as detikzify-tiny
+    return DetikzifyConfig(hidden=512, layers=2, heads=8, kv_heads=1, head_dim=64, ffn=688, vocab=512, max_positions=160,
+                           rms_eps=1e-5, rope_theta=10000.0, rope_factor=1.0,
+                           bos_token_id=1, eos_token_id=2, pad_token_id=0, patch_token_id=1,
+                           vit_dim=144, vit_depth=2, vit_heads=2, vit_mlp=304, vit_patch=14,
+                           vit_image=90, vit_feature_layer=1, attn_splits=4,
+                           name_or_path="detikzify-tiny-tl")
+
+
+def tl_1_1b() -> DetikzifyConfig:
+    """nllg/detikzify-tl-1.1b: TinyLlama-1.1B (d 2048, 22 layers, 32 query / 4 kv heads, head_dim 64, ffn 5632, rms_eps 1e-5,
+    RoPE theta 1e4 unscaled) + the same timm so400m tower as the other v1 models.  Dimensions from the upstream model card; a
+    real config.json overrides them.  vocab / pad are INFERRED from the reference's loader (v1/__init__.py:43-44): adding
+    <pad> to the 32 000-entry LLaMA tokenizer gives pad id 32000, and the embedding resize pads the vocab to a multiple of 8
+    (32 001 -> 32 008), the reasoning that gives cl-7b 32024 / 32016."""
+    return DetikzifyConfig(hidden=2048, layers=22, heads=32, kv_heads=4, head_dim=64, ffn=5632, vocab=32008, rms_eps=1e-5,
+                           rope_theta=10000.0, rope_factor=1.0, bos_token_id=1, eos_token_id=2, pad_token_id=32000,
+                           patch_token_id=1, name_or_path="nllg/detikzify-tl-1.1b")
+
+
 PRESETS = {
     # dimensions from the upstream model cards (SURVEY.md §8a) — real checkpoints override them
     # through from_hf_json; these presets exist for synthetic-weight runs.
     "detikzify-tiny": _tiny,
     "detikzify-tiny-v2": _tiny_v2,
+    "detikzify-tiny-tl": _tiny_tl,
     "detikzify-v2-8b": lambda: v2_8b("nllg/detikzify-v2-8b"),
     "detikzify-v2.5-8b": lambda: v2_8b("nllg/detikzify-v2.5-8b"),
     "detikzify-ds-1.3b": lambda: DetikzifyConfig(hidden=2048, layers=24, heads=16, ffn=5504, vocab=32256,
                                                  name_or_path="nllg/detikzify-ds-1.3b"),
     "detikzify-ds-7b": lambda: DetikzifyConfig(name_or_path="nllg/detikzify-ds-7b"),
+    "detikzify-tl-1.1b": tl_1_1b,
     "detikzify-cl-7b": lambda: DetikzifyConfig(vocab=32024, rms_eps=1e-5, rope_theta=1e6, rope_factor=1.0,
                                                bos_token_id=1, eos_token_id=2, pad_token_id=32016,
                                                patch_token_id=1, name_or_path="nllg/detikzify-cl-7b"),

@@ -51,7 +51,7 @@ typedef struct dtk_config {
   int32_t hidden;          /* d                                   */
   int32_t layers;          /* L                                   */
   int32_t heads;           /* H query heads (kv heads: reserved[2]) */
-  int32_t head_dim;        /* hd (must be 128)                    */
+  int32_t head_dim;        /* hd: 128, or 64 (no batch slots)      */
   int32_t ffn;             /* intermediate_size                   */
   int32_t vocab;           /* V                                   */
   int32_t max_positions;   /* KV capacity in tokens (<= 2048 for v1, generate.py:383) */
