@@ -8,7 +8,7 @@ from pathlib import Path
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "lib" / "libdtk_hip.so"
 
-DTK_ABI_VERSION = 6          # include/dtk.h DTK_ABI_VERSION
+DTK_ABI_VERSION = 7          # include/dtk.h DTK_ABI_VERSION
 DTK_VIT_BATCH = 8            # include/dtk.h: images per pass of dtk_vit_encode
 DTK_F32, DTK_BF16, DTK_F16 = 0, 1, 2
 DTK_ARCH_PROJ_NO_BIAS = 1   # include/dtk.h: dtk_config.reserved[3] flag
@@ -31,6 +31,17 @@ class DtkConfig(C.Structure):
         ("vit_feature_layer", C.c_int32), ("vit_ln_eps", C.c_float), ("vit_gelu_tanh", C.c_int32),
         ("concat_patches", C.c_int32), ("image_token_id", C.c_int32), ("attn_splits", C.c_int32),
         ("reserved", C.c_int32 * 7),
+    ]
+
+
+class DtkAdapterConfig(C.Structure):
+    """dtk_adapter_config: the TikZero adapter and its embedding model (include/dtk.h, ABI 7)"""
+    _fields_ = [
+        ("every_n", C.c_int32), ("text_max", C.c_int32),
+        ("hidden", C.c_int32), ("layers", C.c_int32), ("heads", C.c_int32), ("kv_heads", C.c_int32), ("head_dim", C.c_int32),
+        ("ffn", C.c_int32), ("vocab", C.c_int32), ("rms_eps", C.c_float), ("rope_theta", C.c_float), ("rope_factor", C.c_float),
+        ("rope_low_freq_factor", C.c_float), ("rope_high_freq_factor", C.c_float), ("rope_original_max_position", C.c_int32),
+        ("reserved", C.c_int32 * 3),
     ]
 
 
@@ -154,6 +165,15 @@ SYMBOLS = {
     "dtk_set_gemv_variant": (C.c_int, [_P, C.c_int, C.c_int]),
     "dtk_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
     "dtk_op_gemm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dtk_adapter_create": (C.c_int, [_P, C.POINTER(DtkAdapterConfig)]),
+    "dtk_adapter_destroy": (C.c_int, [_P]),
+    "dtk_has_adapter": (C.c_int, [_P]),
+    "dtk_vit_encode_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_uint64, _P, _P]),
+    "dtk_prefill_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_int, _P]),
+    "dtk_prefill_slot_text": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_int, _P]),
+    "dtk_adapter_embed": (C.c_int, [_P, _P, C.c_int, _P]),
+    "dtk_text_image_key": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "dtk_op_gemm_gated": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
@@ -199,6 +219,9 @@ def load_library() -> C.CDLL:
         if lib.dtk_abi_struct_size(which) != ours:     # a drifted struct would corrupt every call: refuse to run
             raise DtkError(f"struct layout mismatch with include/dtk.h: {struct.__name__}{'.' + field if field else ''} "
                            f"is {ours} here, {lib.dtk_abi_struct_size(which)} in the library")
+    if lib.dtk_abi_struct_size(11) != C.sizeof(DtkAdapterConfig):
+        raise DtkError(f"struct layout mismatch with include/dtk.h: DtkAdapterConfig is {C.sizeof(DtkAdapterConfig)} here, "
+                       f"{lib.dtk_abi_struct_size(11)} in the library")
     _lib = lib
     return lib
 

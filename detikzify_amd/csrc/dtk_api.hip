@@ -72,6 +72,23 @@ struct LayerW {
 struct VitBlockW {
   bf16_t *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
 };
+// one CrossAttentionLayer of the TikZero adapter (reference adapter/modeling_adapter.py) + the text's keys / values it attends to
+struct CrossW {
+  bf16_t *ln1w, *ln1b, *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *qnw, *qnb, *knw, *knb, *ln2w, *ln2b, *f1w, *f1b, *f2w, *f2b;
+  bf16_t *gate_a, *gate_m;           // cross_attn_attn_gate / cross_attn_mlp_gate: one bf16 logit each
+  bf16_t *K, *V;                     // the cached text's k_norm(k_proj(c)) / v_proj(c): [text_max][D]
+};
+struct Adapter {
+  dtk_adapter_config cfg{};
+  dtk_ctx* emb = nullptr;            // the embedding model: a decoder-only context (its tower is a 1-patch stub that never runs)
+  unsigned char* arena = nullptr;
+  size_t first_tensor = 0;           // the adapter's entries are the tail of the owner's tensor table from here on
+  bf16_t *conn_w = nullptr, *conn_b = nullptr, *dummy = nullptr, *ctext = nullptr;
+  std::vector<CrossW> layers;        // per ViT block; present[i]: a cross layer runs before block i
+  std::vector<char> present;
+  std::vector<int64_t> text_ids;     // the text whose connector output and k / v are cached (empty: none)
+  std::vector<float> dummy_host;     // dummy_input.clamp(-1, 1) as fp32 pixels (empty: not built since the last weight load)
+};
 
 }  // namespace
 
@@ -130,6 +147,7 @@ struct dtk_ctx {
   bf16_t *patches, *VX, *VN, *VQKV, *VAO, *VH, *feats, *last_hidden;
   bf16_t *pq, *pkv, *pao, *px, *pn, *ph, *pooled;
   bf16_t* IMG;  // projected image embeddings [nImg][d]
+  Adapter* ad = nullptr;             // TikZero text adapter (dtk_adapter_create), or none
   // op-level scratch
   unsigned char* scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -544,10 +562,10 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
 }
 
 void gemm(dtk_ctx* c, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
-          const bf16_t* res, int ldr, bf16_t* C, int ldc, int M, int N, int K, int flags) {
+          const bf16_t* res, int ldr, bf16_t* C, int ldc, int M, int N, int K, int flags, const bf16_t* gate = nullptr) {
   GemmArgs g;
   g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.residual = res; g.ldr = ldr;
-  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.flags = flags;
+  g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.flags = flags; g.gate = gate;
   hipStream_t s = c->cur_stream ? c->cur_stream : c->stream;
   if (c->gemm_naive) launch_gemm_naive(g, s);
   else launch_gemm_mfma(g, s);
@@ -613,8 +631,35 @@ int gelu_flag(const dtk_ctx* c) { return c->cfg.vit_gelu_tanh ? GEMM_GELU_TANH :
 bf16_t* kcache(dtk_ctx* c, int layer) { return c->kv + (size_t)layer * 2 * c->KVH * c->Tmax * c->hd; }
 bf16_t* vcache(dtk_ctx* c, int layer) { return kcache(c, layer) + (size_t)c->KVH * c->Tmax * c->hd; }
 
-// ViT trunk + (optionally) MAP head for the image already in pixels_dev.
-void vit_forward(dtk_ctx* c, bool want_pooled, hipStream_t s, int B = 1) {
+// The adapter's CrossAttentionLayer before ViT block i (reference modeling_adapter.py CrossAttentionLayer.forward) on the B images' rows
+// in VX, attending to the cached text.  q_norm is the row LayerNorm over the [rows x heads] x 72 view, in place; the two gated residuals
+// are the epilogues of out_proj / fc2 (GEMM_GATED_RESIDUAL).
+void cross_layer(dtk_ctx* c, int i, int B, hipStream_t s) {
+  const Adapter& A = *c->ad;
+  if (!A.present[(size_t)i]) return;
+  const CrossW& w = A.layers[(size_t)i];
+  const int D = c->vD, N = c->vN, mlp = c->vMlp, Hh = c->vH, hd = c->vHd, R = B * N;
+  const float eps = c->cfg.vit_ln_eps;
+  launch_layernorm_rows(c->VX, D, w.ln1w, w.ln1b, c->VN, D, R, D, eps, s);
+  gemm(c, c->VN, D, w.qw, D, w.qb, nullptr, 0, c->VQKV, D, R, D, D, GEMM_BIAS);
+  launch_layernorm_rows(c->VQKV, hd, w.qnw, w.qnb, c->VQKV, hd, R * Hh, hd, eps, s);
+  AttnArgs a;
+  a.Q = c->VQKV; a.q_sh = hd; a.q_st = D;
+  a.K = w.K; a.k_sh = hd; a.k_st = D;
+  a.V = w.V; a.v_sh = hd; a.v_st = D;
+  a.O = c->VAO; a.o_sh = hd; a.o_st = D;
+  a.H = Hh; a.Tq = N; a.Tk = (int)A.text_ids.size(); a.hd = hd; a.causal = 0; a.q_offset = 0; a.scale = 1.0f / sqrtf((float)hd);
+  a.impl = c->attn_impl; a.kv_group = 1;
+  a.nbatch = B; a.q_sb = (long)N * D; a.k_sb = a.v_sb = 0; a.o_sb = (long)N * D;     // every image attends to the same text
+  launch_attention(a, s);
+  gemm(c, c->VAO, D, w.ow, D, w.ob, c->VX, D, c->VX, D, R, D, D, GEMM_BIAS | GEMM_RESIDUAL | GEMM_GATED_RESIDUAL, w.gate_a);
+  launch_layernorm_rows(c->VX, D, w.ln2w, w.ln2b, c->VN, D, R, D, eps, s);
+  gemm(c, c->VN, D, w.f1w, D, w.f1b, nullptr, 0, c->VH, mlp, R, mlp, D, GEMM_BIAS | gelu_flag(c));
+  gemm(c, c->VH, mlp, w.f2w, mlp, w.f2b, c->VX, D, c->VX, D, R, D, mlp, GEMM_BIAS | GEMM_RESIDUAL | GEMM_GATED_RESIDUAL, w.gate_m);
+}
+
+// ViT trunk + (optionally) MAP head for the image already in pixels_dev; `cross`: with the adapter's layers on the cached text.
+void vit_forward(dtk_ctx* c, bool want_pooled, hipStream_t s, int B = 1, bool cross = false) {
   // B images (<= DTK_VIT_BATCH) in one pass: every row-wise op (LayerNorm, the Linear layers) sees B x N rows, attention and the
   // position-embedding add run per image.  Per row the arithmetic is the single-image arithmetic (a GEMM row does not depend on
   // the other rows of its tile), so image b's features are bit-identical to encoding it alone (tested).
@@ -634,6 +679,7 @@ void vit_forward(dtk_ctx* c, bool want_pooled, hipStream_t s, int B = 1) {
   const int last = want_pooled ? c->vDepth - 1 : fl;
   for (int i = 0; i <= last; ++i) {
     const VitBlockW& w = c->vblocks[i];
+    if (cross) cross_layer(c, i, B, s);
     launch_layernorm_rows(c->VX, D, w.n1w, w.n1b, c->VN, D, R, D, c->cfg.vit_ln_eps, s);
     gemm(c, c->VN, D, w.qkvw, D, w.qkvb, nullptr, 0, c->VQKV, 3 * D, R, 3 * D, D, GEMM_BIAS);
     {   // the B images' attention problems in ONE launch (grid z = image): 8 launches of 192 blocks each left the chip a quarter empty
@@ -1071,6 +1117,7 @@ int dtk_abi_struct_size(int which) {
     case 8: return (int)sizeof(dtk_engine_ops);
     case 9: return (int)offsetof(dtk_join, sampling);
     case 10: return (int)offsetof(dtk_join, error_out);
+    case 11: return (int)sizeof(dtk_adapter_config);
     default: return -1;
   }
 }
@@ -1240,6 +1287,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
 void dtk_destroy(dtk_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
+  if (c->ad) (void)dtk_adapter_destroy(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
   if (c->graph) (void)hipGraphDestroy(c->graph);
@@ -1304,6 +1352,7 @@ int dtk_load_tensor(dtk_ctx* c, const char* name, const void* host, int dtype, c
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy2D(t.ptr, (size_t)t.stride * 2, src16, (size_t)t.cols * 2, (size_t)t.cols * 2, (size_t)t.rows, hipMemcpyHostToDevice));
   t.loaded = true;
+  if (c->ad) { c->ad->text_ids.clear(); c->ad->dummy_host.clear(); c->ad->emb->ptiled_ready = false; }
   c->have_image = false;
   c->seq0.cached_ids.clear();
   for (auto& b : c->bseq) b.cached_ids.clear();
@@ -1331,7 +1380,7 @@ int dtk_fill_synthetic(dtk_ctx* c, uint64_t seed) {
   HIPCHK(c, hipSetDevice(c->device));
   for (size_t i = 0; i < c->tensors.size(); ++i) {
     TensorEntry& t = c->tensors[i];
-    if (t.name == "rope.cos" || t.name == "rope.sin") continue;
+    if (t.name == "rope.cos" || t.name == "rope.sin" || t.name == "embedding_model.rope.cos" || t.name == "embedding_model.rope.sin") continue;
     t.loaded = true;
     if (t.stride == t.cols) {
       launch_fill_synth(t.ptr, t.numel(), seed, (uint32_t)i, t.synth_scale, t.synth_offset, c->stream);
@@ -1343,6 +1392,7 @@ int dtk_fill_synthetic(dtk_ctx* c, uint64_t seed) {
     }
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->ad) { c->ad->text_ids.clear(); c->ad->dummy_host.clear(); c->ad->emb->ptiled_ready = false; }
   c->have_image = false;
   c->seq0.cached_ids.clear();
   for (auto& b : c->bseq) b.cached_ids.clear();
@@ -1352,7 +1402,13 @@ int dtk_fill_synthetic(dtk_ctx* c, uint64_t seed) {
   return DTK_OK;
 }
 
+static int vit_encode_impl(dtk_ctx* c, const float* pixels, int batch, void* feats_out, void* pooled_out, const int64_t* text_ids, int T_text);
+static int text_prepare(dtk_ctx* c, const int64_t* ids, int T, hipStream_t s);
 int dtk_vit_encode(dtk_ctx* c, const float* pixels, int batch, void* feats_out, void* pooled_out) {
+  return vit_encode_impl(c, pixels, batch, feats_out, pooled_out, nullptr, 0);
+}
+
+static int vit_encode_impl(dtk_ctx* c, const float* pixels, int batch, void* feats_out, void* pooled_out, const int64_t* text_ids, int T_text) {
   if (!c || !pixels || batch < 1) return fail(c, DTK_ERR_ARG, "dtk_vit_encode: bad argument");
   if (pooled_out) {   // forward_head needs the attention-pool weights: a checkpoint without them must not pool with zeros
     for (const TensorEntry& t : c->tensors)
@@ -1366,11 +1422,12 @@ int dtk_vit_encode(dtk_ctx* c, const float* pixels, int batch, void* feats_out, 
   // forward() semantics (pooled requested): last_hidden_state = forward_features = ALL blocks + final norm; without the
   // head: get_intermediate_layers(n=[feature_layer], norm=True).  The two differ when feature_layer != depth - 1.
   const bf16_t* hidden = (pooled_out && c->cfg.vit_feature_layer != c->vDepth - 1) ? c->last_hidden : c->feats;
+  if (text_ids) { const int rc = text_prepare(c, text_ids, T_text, sv); if (rc != DTK_OK) return rc; }
   for (int b0 = 0; b0 < batch; b0 += DTK_VIT_BATCH) {
     const int B = std::min(batch - b0, (int)DTK_VIT_BATCH);
     HIPCHK(c, hipMemcpyAsync(c->pixels_dev, pixels + (size_t)b0 * img, (size_t)B * img * 4, hipMemcpyHostToDevice, sv));
     HIPCHK(c, hipEventRecord(c->ev_va, sv));
-    vit_forward(c, pooled_out != nullptr, sv, B);
+    vit_forward(c, pooled_out != nullptr, sv, B, text_ids != nullptr);
     HIPCHK(c, hipEventRecord(c->ev_vb, sv));
     if (feats_out)
       HIPCHK(c, hipMemcpyAsync((bf16_t*)feats_out + (size_t)b0 * c->vN * c->vD, hidden, (size_t)B * c->vN * c->vD * 2, hipMemcpyDeviceToHost, sv));
@@ -1385,76 +1442,15 @@ int dtk_vit_encode(dtk_ctx* c, const float* pixels, int batch, void* feats_out, 
   return DTK_OK;  // IMG (the projected prefix of the cached prefill image) is left untouched
 }
 
-static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_dst, DecState* st_dst, bool is_single,
-                        const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
-  const int hd = c ? c->hd : 128;
-  const size_t kv_layer = c ? (size_t)2 * c->KVH * c->Tmax * hd : 0;
+// The decoder layers of a prefill: n rows at positions start .. start + n - 1 of a T-token context, X (+ Xn = layer 0's input norm) in,
+// X = the last layer's output out, K / V appended at kvbase ([L][2][KVH][Tmax][hd]).  Everything it reads — weights, dimensions, RoPE
+// tables, activation and KV scratch — is the context's own: the checkpoint's decoder, or the adapter's embedding model (Adapter::emb).
+static void decoder_layers(dtk_ctx* c, int n, int start, int T, bf16_t* kvbase, hipStream_t s) {
+  const int hd = c->hd, d = c->d, ff = c->ff;
+  const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * hd;
   auto kc = [&](int l) { return kvbase + (size_t)l * kv_layer; };
   auto vc = [&](int l) { return kvbase + (size_t)l * kv_layer + (size_t)c->KVH * c->Tmax * hd; };
-  if (!c || !ids || T < 1) return fail(c, DTK_ERR_ARG, "dtk_prefill: bad argument");
-  if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
-  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
-  HIPCHK(c, hipSetDevice(c->device));
-  // drain pending decode steps (their tokens are dropped)
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  ensure_prefill_tiles(c);
-  if (is_single) c->waited = c->launched = 0;  // the device draw counter restarts with this prefill
-  else c->bwaited = c->blaunched;
-  // ---- locate the image placeholder run (reference v1/modeling_detikzify.py:179-184)
-  int img_start = -1, img_count = 0;
-  for (int t = 0; t < T; ++t) {
-    if (ids[t] < 0 || ids[t] >= c->V) return fail(c, DTK_ERR_ARG, "token id %lld out of range", (long long)ids[t]);
-    if (ids[t] == c->cfg.image_token_id) { if (img_start < 0) img_start = t; img_count++; }
-  }
-  const bool has_img = img_count > 0;
-  const bool use_img = has_img && (pixels != nullptr || ((flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key));
-  if (use_img) {
-    if (img_count != c->nImg)
-      return fail(c, DTK_ERR_ARG, "The number of image patch tokens should be the same as the number of image patches.");
-    for (int t = 0; t < c->nImg; ++t)
-      if (ids[img_start + t] != c->cfg.image_token_id)
-        return fail(c, DTK_ERR_ARG, "The image patch tokens should be consecutive.");
-  }
-  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
-  // ---- longest common prefix with the cached sequence (output-identical KV reuse).  The KV of the image positions
-  // depends on the image, not on the (all equal) placeholder ids: the cached sequence must have been computed with the
-  // same image key, and with / without spliced image features never mixes.
-  int start = 0;
-  const bool same_image = !has_img || (sh.cached_with_image == use_img && (!use_img || (image_key != 0 && sh.image_key == image_key)));
-  if ((flags & DTK_PREFILL_REUSE_PREFIX) && same_image && !sh.cached_ids.empty()) {
-    const int lim = (int)std::min<size_t>(sh.cached_ids.size(), (size_t)T - 1);
-    while (start < lim && sh.cached_ids[start] == ids[start]) ++start;
-  }
-  // ---- image features are needed only if an image position has to be recomputed
-  if (use_img && start < img_start + c->nImg) {
-    const bool reuse = (flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key;
-    if (!reuse) {
-      if (!pixels) return fail(c, DTK_ERR_ARG, "pixels required (no cached image for this key)");
-      const size_t img = (size_t)3 * c->cfg.vit_image * c->cfg.vit_image;
-      HIPCHK(c, hipMemcpyAsync(c->pixels_dev, pixels, img * 4, hipMemcpyHostToDevice, c->stream));
-      vit_forward(c, false, c->stream);
-      project_image(c);
-      c->stats.vit_images++;
-      c->have_image = true;
-      c->cached_image_key = image_key;
-    }
-  }
-  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
-  sh.last_reuse_start = start;
-  const int n = T - start;
-  std::vector<int32_t> ids32((size_t)n);
-  for (int t = 0; t < n; ++t) ids32[(size_t)t] = (int32_t)ids[start + t];
-  HIPCHK(c, hipMemcpyAsync(c->ids_dev, ids32.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  hipStream_t s = c->stream;
-  const int d = c->d, ff = c->ff;
-  launch_embed_gather(c->ids_dev, c->embed, c->X, n, d, s);
-  if (use_img) {  // splice projected image features over the placeholder embeddings
-    const int lo = std::max(img_start, start), hi = img_start + c->nImg;
-    if (hi > lo) launch_copy_rows(c->IMG + (size_t)(lo - img_start) * d, d, c->X + (size_t)(lo - start) * d, d, hi - lo, d, s);
-  }
   const float scale = 1.0f / sqrtf((float)hd);
-  c->launch_refused = false;      // (a batched step that was refused leaves it set: this prefill judges its own launches)
-  launch_rmsnorm_rows(c->X, d, c->layers[0].ln1, c->Xn, d, n, d, c->cfg.rms_eps, s);
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
     const int qkvn = d + 2 * c->KVH * hd;
@@ -1497,6 +1493,141 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
     // + the next layer's input_layernorm -> Xn (the final norm runs on the last row only, inside the lm_head GEMV below)
     gemm_role(c, c->ACT, ff, w.wdown, w.p_wdown, ff, c->X, d, c->X, d, n, d, ff, GEMM_RESIDUAL, l + 1 < c->L ? c->layers[l + 1].ln1 : nullptr, c->Xn, d);
   }
+}
+
+// The adapter's embedding pass (reference: self.embedding_model(**adapter_inputs).last_hidden_state): T text tokens through the embedding
+// model's layers (decoder_layers on its own context) and its final RMSNorm, every row -> c->Xn [T][d].  Synchronous.
+static int embed_pass(dtk_ctx* c, const int64_t* ids, int T) {
+  if (T < 1 || T > c->Tmax) return fail(c, DTK_ERR_RANGE, "text of %d tokens (the adapter takes 1 .. %d)", T, c->Tmax);
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<int32_t> ids32((size_t)T);
+  for (int t = 0; t < T; ++t) {
+    if (ids[t] < 0 || ids[t] >= c->V) return fail(c, DTK_ERR_ARG, "text token id %lld out of range", (long long)ids[t]);
+    ids32[(size_t)t] = (int32_t)ids[t];
+  }
+  ensure_prefill_tiles(c);
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->ids_dev, ids32.data(), (size_t)T * 4, hipMemcpyHostToDevice, s));
+  launch_embed_gather(c->ids_dev, c->embed, c->X, T, c->d, s);
+  c->launch_refused = false;
+  launch_rmsnorm_rows(c->X, c->d, c->layers[0].ln1, c->Xn, c->d, T, c->d, c->cfg.rms_eps, s);
+  decoder_layers(c, T, 0, T, c->kv, s);
+  launch_rmsnorm_rows(c->X, c->d, c->final_norm, c->Xn, c->d, T, c->d, c->cfg.rms_eps, s);
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  if (c->launch_refused) { c->launch_refused = false; return fail(c, DTK_ERR_STATE, "embedding pass: a sliced-K projection was refused by its kernel"); }
+  return DTK_OK;
+}
+
+// Connector output and every cross layer's k / v for this text, unless they are cached already (same ids).  Synchronous, on stream s.
+static int text_prepare(dtk_ctx* c, const int64_t* ids, int T, hipStream_t s) {
+  Adapter& A = *c->ad;
+  if (!ids || T < 1 || T > A.cfg.text_max) return fail(c, DTK_ERR_RANGE, "text of %d tokens (the adapter takes 1 .. %d)", T, A.cfg.text_max);
+  if ((int)A.text_ids.size() == T && std::equal(ids, ids + T, A.text_ids.begin())) return DTK_OK;
+  A.text_ids.clear();
+  dtk_ctx* e = A.emb;
+  if (embed_pass(e, ids, T) != DTK_OK) return fail(c, DTK_ERR_STATE, "adapter embedding pass: %s", e->err.c_str());
+  struct StreamScope { dtk_ctx* c; hipStream_t prev; ~StreamScope() { c->cur_stream = prev; } } scope{c, c->cur_stream};
+  c->cur_stream = s;
+  const int D = c->vD, hd = c->vHd, de = e->d;
+  gemm(c, e->Xn, de, A.conn_w, de, A.conn_b, nullptr, 0, A.ctext, D, T, D, de, GEMM_BIAS);
+  for (size_t i = 0; i < A.layers.size(); ++i) {
+    if (!A.present[i]) continue;
+    const CrossW& w = A.layers[i];
+    gemm(c, A.ctext, D, w.kw, D, w.kb, nullptr, 0, w.K, D, T, D, D, GEMM_BIAS);
+    launch_layernorm_rows(w.K, hd, w.knw, w.knb, w.K, hd, T * c->vH, hd, c->cfg.vit_ln_eps, s);   // k_norm per head, in place
+    gemm(c, A.ctext, D, w.vw, D, w.vb, nullptr, 0, w.V, D, T, D, D, GEMM_BIAS);
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  A.text_ids.assign(ids, ids + T);
+  return DTK_OK;
+}
+
+// dummy_input.clamp(-1, 1) as fp32 pixels, `batch` times (the text-only prompt's image, reference add_hooks.forward_hook)
+static int dummy_pixels(dtk_ctx* c, int batch, std::vector<float>& out) {
+  Adapter& A = *c->ad;
+  const size_t img = (size_t)3 * c->cfg.vit_image * c->cfg.vit_image;
+  if (A.dummy_host.empty()) {
+    std::vector<uint16_t> bits(img);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(bits.data(), A.dummy, img * 2, hipMemcpyDeviceToHost));
+    A.dummy_host.resize(img);
+    for (size_t k = 0; k < img; ++k) A.dummy_host[k] = std::min(1.f, std::max(-1.f, host_bf2f(bits[k])));
+  }
+  out.resize(img * (size_t)batch);
+  for (int b = 0; b < batch; ++b) std::copy(A.dummy_host.begin(), A.dummy_host.end(), out.begin() + (size_t)b * img);
+  return DTK_OK;
+}
+
+static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_dst, DecState* st_dst, bool is_single,
+                        const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out,
+                        const int64_t* text_ids = nullptr, int T_text = 0) {
+  if (!c || !ids || T < 1) return fail(c, DTK_ERR_ARG, "dtk_prefill: bad argument");
+  if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
+  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  // drain pending decode steps (their tokens are dropped)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ensure_prefill_tiles(c);
+  if (is_single) c->waited = c->launched = 0;  // the device draw counter restarts with this prefill
+  else c->bwaited = c->blaunched;
+  // ---- locate the image placeholder run (reference v1/modeling_detikzify.py:179-184)
+  int img_start = -1, img_count = 0;
+  for (int t = 0; t < T; ++t) {
+    if (ids[t] < 0 || ids[t] >= c->V) return fail(c, DTK_ERR_ARG, "token id %lld out of range", (long long)ids[t]);
+    if (ids[t] == c->cfg.image_token_id) { if (img_start < 0) img_start = t; img_count++; }
+  }
+  const bool has_img = img_count > 0;
+  const bool use_img = has_img && (pixels != nullptr || ((flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key));
+  if (use_img) {
+    if (img_count != c->nImg)
+      return fail(c, DTK_ERR_ARG, "The number of image patch tokens should be the same as the number of image patches.");
+    for (int t = 0; t < c->nImg; ++t)
+      if (ids[img_start + t] != c->cfg.image_token_id)
+        return fail(c, DTK_ERR_ARG, "The image patch tokens should be consecutive.");
+  }
+  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
+  // ---- longest common prefix with the cached sequence (output-identical KV reuse).  The KV of the image positions
+  // depends on the image, not on the (all equal) placeholder ids: the cached sequence must have been computed with the
+  // same image key, and with / without spliced image features never mixes.
+  int start = 0;
+  const bool same_image = !has_img || (sh.cached_with_image == use_img && (!use_img || (image_key != 0 && sh.image_key == image_key)));
+  if ((flags & DTK_PREFILL_REUSE_PREFIX) && same_image && !sh.cached_ids.empty()) {
+    const int lim = (int)std::min<size_t>(sh.cached_ids.size(), (size_t)T - 1);
+    while (start < lim && sh.cached_ids[start] == ids[start]) ++start;
+  }
+  // ---- image features are needed only if an image position has to be recomputed
+  if (use_img && start < img_start + c->nImg) {
+    const bool reuse = (flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key;
+    if (!reuse) {
+      if (!pixels) return fail(c, DTK_ERR_ARG, "pixels required (no cached image for this key)");
+      const size_t img = (size_t)3 * c->cfg.vit_image * c->cfg.vit_image;
+      HIPCHK(c, hipMemcpyAsync(c->pixels_dev, pixels, img * 4, hipMemcpyHostToDevice, c->stream));
+      if (text_ids) { const int rc = text_prepare(c, text_ids, T_text, c->stream); if (rc != DTK_OK) return rc; }
+      vit_forward(c, false, c->stream, 1, text_ids != nullptr);
+      project_image(c);
+      c->stats.vit_images++;
+      c->have_image = true;
+      c->cached_image_key = image_key;
+    }
+  }
+  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
+  sh.last_reuse_start = start;
+  const int n = T - start;
+  std::vector<int32_t> ids32((size_t)n);
+  for (int t = 0; t < n; ++t) ids32[(size_t)t] = (int32_t)ids[start + t];
+  HIPCHK(c, hipMemcpyAsync(c->ids_dev, ids32.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  hipStream_t s = c->stream;
+  const int d = c->d;
+  launch_embed_gather(c->ids_dev, c->embed, c->X, n, d, s);
+  if (use_img) {  // splice projected image features over the placeholder embeddings
+    const int lo = std::max(img_start, start), hi = img_start + c->nImg;
+    if (hi > lo) launch_copy_rows(c->IMG + (size_t)(lo - img_start) * d, d, c->X + (size_t)(lo - start) * d, d, hi - lo, d, s);
+  }
+  c->launch_refused = false;      // (a batched step that was refused leaves it set: this prefill judges its own launches)
+  launch_rmsnorm_rows(c->X, d, c->layers[0].ln1, c->Xn, d, n, d, c->cfg.rms_eps, s);
+  decoder_layers(c, n, start, T, kvbase, s);
   if (c->launch_refused) { c->launch_refused = false; return fail(c, DTK_ERR_STATE, "prefill: a sliced-K projection was refused by its kernel (nothing launched for it)"); }
   // final norm + lm_head on the last position only (the sampler consumes logits[:, -1])
   GemvArgs g{};
@@ -2178,6 +2309,196 @@ static int op_scratch(dtk_ctx* c, size_t bytes, size_t& off, void** p) {
   T* var = nullptr;                                                         \
   { void* p_; int rc_ = op_scratch(c, (size_t)(n) * sizeof(T), off, &p_); if (rc_) return rc_; var = (T*)p_; }
 
+
+// ---- TikZero adapter (ABI 7) ------------------------------------------------------------------------------------------------------
+static void plan_adapter(dtk_ctx* c, Adapter& A, Planner& P, bool reg) {
+  const int D = c->vD, mlp = c->vMlp, hd = c->vHd, de = A.cfg.hidden, Tt = A.cfg.text_max;
+  const size_t img = (size_t)3 * c->cfg.vit_image * c->cfg.vit_image;
+  const float ws = 0.02f;
+  auto R = [&](const std::string& n, bf16_t* p, int64_t r, int64_t cl, float sc, float of) { if (reg) add_tensor(c, n, p, r, cl, cl, sc, of); };
+  A.conn_w = P.take<bf16_t>((size_t)D * de); A.conn_b = P.take<bf16_t>(D);
+  R("adapter.connector.weight", A.conn_w, D, de, ws, 0.f);
+  R("adapter.connector.bias", A.conn_b, 1, D, 0.01f, 0.f);
+  A.dummy = P.take<bf16_t>(img);
+  R("adapter.dummy_input", A.dummy, 1, (int64_t)img, 1.5f, 0.f);      // synthetic: partly outside [-1, 1], so the clamp is exercised
+  A.ctext = P.take<bf16_t>((size_t)Tt * D);
+  if (reg) { A.layers.assign((size_t)c->vDepth, CrossW{}); A.present.assign((size_t)c->vDepth, 0); }
+  for (int i = 0; i < c->vDepth; ++i) {
+    if ((i + 1) % A.cfg.every_n != 0) continue;
+    CrossW w{};
+    w.ln1w = P.take<bf16_t>(D); w.ln1b = P.take<bf16_t>(D);
+    w.qw = P.take<bf16_t>((size_t)D * D); w.qb = P.take<bf16_t>(D);
+    w.kw = P.take<bf16_t>((size_t)D * D); w.kb = P.take<bf16_t>(D);
+    w.vw = P.take<bf16_t>((size_t)D * D); w.vb = P.take<bf16_t>(D);
+    w.ow = P.take<bf16_t>((size_t)D * D); w.ob = P.take<bf16_t>(D);
+    w.qnw = P.take<bf16_t>(hd); w.qnb = P.take<bf16_t>(hd); w.knw = P.take<bf16_t>(hd); w.knb = P.take<bf16_t>(hd);
+    w.ln2w = P.take<bf16_t>(D); w.ln2b = P.take<bf16_t>(D);
+    w.f1w = P.take<bf16_t>((size_t)mlp * D); w.f1b = P.take<bf16_t>(mlp);
+    w.f2w = P.take<bf16_t>((size_t)D * mlp); w.f2b = P.take<bf16_t>(D);
+    w.gate_a = P.take<bf16_t>(1); w.gate_m = P.take<bf16_t>(1);
+    w.K = P.take<bf16_t>((size_t)Tt * D); w.V = P.take<bf16_t>((size_t)Tt * D);
+    if (!reg) continue;
+    A.layers[(size_t)i] = w; A.present[(size_t)i] = 1;
+    const std::string p = "adapter.layers." + std::to_string(i) + ".";
+    R(p + "layer_norm1.weight", w.ln1w, 1, D, 0.1f, 1.f); R(p + "layer_norm1.bias", w.ln1b, 1, D, 0.01f, 0.f);
+    R(p + "cross_attn.q_proj.weight", w.qw, D, D, ws, 0.f); R(p + "cross_attn.q_proj.bias", w.qb, 1, D, 0.01f, 0.f);
+    R(p + "cross_attn.k_proj.weight", w.kw, D, D, ws, 0.f); R(p + "cross_attn.k_proj.bias", w.kb, 1, D, 0.01f, 0.f);
+    R(p + "cross_attn.v_proj.weight", w.vw, D, D, ws, 0.f); R(p + "cross_attn.v_proj.bias", w.vb, 1, D, 0.01f, 0.f);
+    R(p + "cross_attn.out_proj.weight", w.ow, D, D, ws, 0.f); R(p + "cross_attn.out_proj.bias", w.ob, 1, D, 0.01f, 0.f);
+    R(p + "cross_attn.q_norm.weight", w.qnw, 1, hd, 0.1f, 1.f); R(p + "cross_attn.q_norm.bias", w.qnb, 1, hd, 0.01f, 0.f);
+    R(p + "cross_attn.k_norm.weight", w.knw, 1, hd, 0.1f, 1.f); R(p + "cross_attn.k_norm.bias", w.knb, 1, hd, 0.01f, 0.f);
+    R(p + "layer_norm2.weight", w.ln2w, 1, D, 0.1f, 1.f); R(p + "layer_norm2.bias", w.ln2b, 1, D, 0.01f, 0.f);
+    R(p + "mlp.fc1.weight", w.f1w, mlp, D, ws, 0.f); R(p + "mlp.fc1.bias", w.f1b, 1, mlp, 0.01f, 0.f);
+    R(p + "mlp.fc2.weight", w.f2w, D, mlp, ws, 0.f); R(p + "mlp.fc2.bias", w.f2b, 1, D, 0.01f, 0.f);
+    // gates: a trained adapter's are far from 0; synthetic ones are too (at 0 every gate would be 0.5 and nothing would show it is read)
+    R(p + "cross_attn_attn_gate", w.gate_a, 1, 1, 1.0f, 0.5f); R(p + "cross_attn_mlp_gate", w.gate_m, 1, 1, 1.0f, -0.5f);
+  }
+}
+
+int dtk_adapter_create(dtk_ctx* c, const dtk_adapter_config* cfg) {
+  if (!c || !cfg) return fail(c, DTK_ERR_ARG, "dtk_adapter_create: null argument");
+  if (c->ad) return fail(c, DTK_ERR_STATE, "an adapter is loaded already (dtk_adapter_destroy first)");
+  // the reference's hooks look for the HF SigLIP ModuleList; a v1 checkpoint's timm tower has none (add_hooks raises)
+  if (c->proj_bias) return fail(c, DTK_ERR_ARG, "Couldn't locate vision encoder layers! (the TikZero adapter needs a v2 checkpoint's SigLIP tower)");
+  if (cfg->every_n < 1 || cfg->text_max < 1 || cfg->text_max > 4096)
+    return fail(c, DTK_ERR_ARG, "adapter: every_n %d / text_max %d out of range", cfg->every_n, cfg->text_max);
+  HIPCHK(c, hipSetDevice(c->device));
+  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+  dtk_config ec{};
+  ec.hidden = cfg->hidden; ec.layers = cfg->layers; ec.heads = cfg->heads; ec.head_dim = cfg->head_dim; ec.ffn = cfg->ffn;
+  ec.vocab = cfg->vocab; ec.max_positions = cfg->text_max < 8 ? 8 : cfg->text_max; ec.rms_eps = cfg->rms_eps;
+  ec.rope_theta = cfg->rope_theta; ec.rope_factor = cfg->rope_factor;
+  // the embedding model has no tower: the smallest one dtk_create accepts (one 14 px patch), allocated, never run
+  ec.vit_dim = 32; ec.vit_depth = 1; ec.vit_heads = 1; ec.vit_mlp = 32; ec.vit_patch = 14; ec.vit_image = 14;
+  ec.vit_feature_layer = 0; ec.vit_ln_eps = 1e-6f; ec.concat_patches = 1; ec.image_token_id = -1;
+  ec.reserved[2] = cfg->kv_heads == cfg->heads ? 0 : cfg->kv_heads;
+  ec.reserved[3] = DTK_ARCH_PROJ_NO_BIAS;
+  Adapter* A = new Adapter();
+  A->cfg = *cfg;
+  if (dtk_create(&ec, c->device, &A->emb) != DTK_OK) {
+    const std::string why = g_create_error;
+    delete A;
+    return fail(c, DTK_ERR_ARG, "adapter embedding model: %s", why.c_str());
+  }
+  Planner sz;
+  plan_adapter(c, *A, sz, false);
+  const size_t bytes = align_up(sz.off, 256) + 256;
+  if (hipMalloc((void**)&A->arena, bytes) != hipSuccess) { dtk_destroy(A->emb); delete A; return fail(c, DTK_ERR_HIP, "adapter: hipMalloc of %zu bytes failed", bytes); }
+  (void)hipMemsetAsync(A->arena, 0, bytes, c->stream);
+  (void)hipStreamSynchronize(c->stream);
+  A->first_tensor = c->tensors.size();
+  Planner real;
+  real.base = A->arena;
+  plan_adapter(c, *A, real, true);
+  // the embedding model's tensors under the reference's names (AutoModel's state dict: no "model." prefix, no head)
+  for (const TensorEntry& t : A->emb->tensors) {
+    std::string n = t.name;
+    if (n.compare(0, 6, "model.") == 0 && n.compare(0, 16, "model.mm_project") != 0) n = n.substr(6);
+    else if (n != "rope.cos" && n != "rope.sin") continue;
+    add_tensor(c, "embedding_model." + n, t.ptr, t.rows, t.cols, t.stride, t.synth_scale, t.synth_offset);
+  }
+  c->ad = A;
+  c->have_image = false;                 // nothing cached before the adapter was there is keyed by a text
+  return DTK_OK;
+}
+
+int dtk_adapter_destroy(dtk_ctx* c) {
+  if (!c) return DTK_ERR_ARG;
+  if (!c->ad) return DTK_OK;
+  (void)hipSetDevice(c->device);
+  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  if (c->stream_vit) (void)hipStreamSynchronize(c->stream_vit);
+  Adapter* A = c->ad;
+  for (size_t i = A->first_tensor; i < c->tensors.size(); ++i) c->tindex.erase(c->tensors[i].name);
+  c->tensors.resize(A->first_tensor);
+  if (A->arena) (void)hipFree(A->arena);
+  dtk_destroy(A->emb);
+  delete A;
+  c->ad = nullptr;
+  c->have_image = false;                 // a text-conditioned image may be cached: drop every cached prefix
+  c->seq0.cached_ids.clear();
+  for (auto& b : c->bseq) b.cached_ids.clear();
+  return DTK_OK;
+}
+
+int dtk_has_adapter(const dtk_ctx* c) { return (c && c->ad) ? 1 : 0; }
+
+uint64_t dtk_text_image_key(uint64_t image_key, uint64_t text_key) {
+  if (image_key == 0 || text_key == 0) return 0;
+  uint64_t z = image_key ^ (text_key * 0x9E3779B97F4A7C15ull) ^ 0x5445585443524F53ull;    // splitmix64 finaliser of the pair
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z ? z : 1;
+}
+
+int dtk_vit_encode_text(dtk_ctx* c, const float* pixels, int batch, const int64_t* text_ids, int T_text, uint64_t text_key,
+                        void* feats_out, void* pooled_out) {
+  (void)text_key;      // the text cache compares the ids themselves
+  if (!c || batch < 1 || !text_ids) return fail(c, DTK_ERR_ARG, "dtk_vit_encode_text: bad argument");
+  if (!c->ad) return fail(c, DTK_ERR_STATE, "no adapter loaded (dtk_adapter_create)");
+  std::vector<float> dummy;
+  if (!pixels) {
+    std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+    const int rc = dummy_pixels(c, batch, dummy);
+    if (rc != DTK_OK) return rc;
+    pixels = dummy.data();
+  }
+  return vit_encode_impl(c, pixels, batch, feats_out, pooled_out, text_ids, T_text);
+}
+
+static int prefill_text_common(dtk_ctx* c, const float*& pixels, std::vector<float>& dummy, const int64_t* text_ids) {
+  if (!c) return DTK_ERR_ARG;
+  if (!text_ids) return fail(c, DTK_ERR_ARG, "dtk_prefill_text: no text");
+  if (!c->ad) return fail(c, DTK_ERR_STATE, "no adapter loaded (dtk_adapter_create)");
+  if (!pixels) {
+    std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+    const int rc = dummy_pixels(c, 1, dummy);
+    if (rc != DTK_OK) return rc;
+    pixels = dummy.data();
+  }
+  return DTK_OK;
+}
+
+int dtk_prefill_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
+                     const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_out) {
+  std::vector<float> dummy;
+  const int rc = prefill_text_common(c, pixels, dummy, text_ids);
+  if (rc != DTK_OK) return rc;
+  return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, dtk_text_image_key(image_key, text_key), flags, logits_out,
+                      text_ids, T_text);
+}
+
+int dtk_prefill_slot_text(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
+                          const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_out) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_prefill_slot_text: slot %d of %d", slot, c ? c->nb : 0);
+  std::vector<float> dummy;
+  const int rc0 = prefill_text_common(c, pixels, dummy, text_ids);
+  if (rc0 != DTK_OK) return rc0;
+  SeqHost& sh = c->bseq[(size_t)slot];
+  sh.last_reuse_start = 0;
+  const int rc = prefill_impl(c, sh, c->kvb + (size_t)slot * c->kv_slot_stride, c->logits_b + (size_t)slot * c->V,
+                              c->st_b + slot, false, ids, T, pixels, dtk_text_image_key(image_key, text_key), flags, logits_out,
+                              text_ids, T_text);
+  const int kept = rc == DTK_OK ? sh.last_reuse_start : 0;       // as dtk_prefill_slot
+  auto clip = [&](SeqHost& q) { q.share_len = std::min(q.share_len, kept); if (q.share_len <= 0) { q.share_src = -1; q.share_len = 0; } };
+  clip(sh);
+  for (int j = 0; j < c->nb; ++j)
+    if (j != slot && c->bseq[(size_t)j].share_src == slot) clip(c->bseq[(size_t)j]);
+  return rc;
+}
+
+int dtk_adapter_embed(dtk_ctx* c, const int64_t* text_ids, int T_text, void* hidden_out) {
+  if (!c || !text_ids || !hidden_out) return fail(c, DTK_ERR_ARG, "dtk_adapter_embed: bad argument");
+  if (!c->ad) return fail(c, DTK_ERR_STATE, "no adapter loaded (dtk_adapter_create)");
+  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+  dtk_ctx* e = c->ad->emb;
+  if (embed_pass(e, text_ids, T_text) != DTK_OK) return fail(c, DTK_ERR_STATE, "adapter embedding pass: %s", e->err.c_str());
+  HIPCHK(c, hipMemcpy(hidden_out, e->Xn, (size_t)T_text * e->d * 2, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
 int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual, int M, int N, int K, int flags, uint16_t* C) {
   if (!c || !A || !W || !C || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemm: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2212,6 +2533,29 @@ int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t
     }
   }
   else if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s); else launch_gemm_mfma(g, s);
+  HIPCHK(c, hipMemcpyAsync(C, dC, (size_t)M * N * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return DTK_OK;
+}
+
+int dtk_op_gemm_gated(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual,
+                      const uint16_t* gate, int M, int N, int K, int flags, uint16_t* C) {
+  if (!c || !A || !W || !C || !bias || !residual || !gate || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemm_gated: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t off = 0;
+  OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dB, N);
+  OPBUF(bf16_t, dR, (size_t)M * N); OPBUF(bf16_t, dC, (size_t)M * N); OPBUF(bf16_t, dG, 8);
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dB, bias, (size_t)N * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dR, residual, (size_t)M * N * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dG, gate, 2, hipMemcpyHostToDevice, s));
+  GemmArgs g;
+  g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = dB; g.residual = dR; g.ldr = N; g.C = dC; g.ldc = N;
+  g.M = M; g.N = N; g.K = K; g.flags = GEMM_BIAS | GEMM_RESIDUAL | GEMM_GATED_RESIDUAL; g.gate = dG;
+  if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s); else launch_gemm_mfma(g, s);
   HIPCHK(c, hipMemcpyAsync(C, dC, (size_t)M * N * 2, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());

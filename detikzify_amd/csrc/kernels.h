@@ -204,6 +204,8 @@ void set_gemv_mv_shape(int role, int shape);   // role = epilogue id (5 = o_proj
 #define GEMM_EPI_DIRECT 32768       // k_gemm_g3: the lanes store their accumulators directly (the epilogue before round 6's LDS-transposed one; A/B and bit-identity tests)
 #define GEMM_PROBE_NOFILL 65536    // k_gemm_g3 timing experiments (DTK_G3_PROBE): leave parts of the kernel out
 #define GEMM_PROBE_NOMFMA 131072
+#define GEMM_GATED_RESIDUAL 262144    // with GEMM_RESIDUAL: C = res + bf16(bf16(sigmoid(*gate)) * bf16(acc + bias)) (the TikZero adapter's gated residuals; every
+                                    // kernel launch_gemm_mfma / launch_gemm_naive can pick takes it)
 struct GemmArgs {
   const bf16_t* A; int lda;      // [M][K]
   const bf16_t* W; int ldw;      // [N][K]
@@ -221,6 +223,7 @@ struct GemmArgs {
   // it when present: a fill instruction then reads 1 KiB CONTIGUOUS instead of 8 rows x 128 B that lie K x 2 bytes apart (the row-major
   // stream of the prefill GEMMs reached 2.4 TB/s of HBM), and the piece lands in LDS as the MFMA operand.  Same values, same k order.
   const bf16_t* Wt = nullptr;
+  const bf16_t* gate = nullptr;  // GEMM_GATED_RESIDUAL: one bf16 scalar in device memory (the gate's logit)
 };
 __host__ __device__ inline int sk_tiles_per_slice(int K, int S) { const int T = K / 64; return (T + S - 1) / S; }
 // slices of a decoder-prefill role, from its WEIGHT shape alone: the largest power of two <= 8 that keeps 256 x 128 tiles x slices within

@@ -20,12 +20,18 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   return 0.5f * x * (1.f + tanhf(k0 * (x + k1 * x * x * x)));
 }
 
+// GEMM_GATED_RESIDUAL: the gate as the product uses it, torch's bf16 sigmoid (fp32 math, one rounding); 1 without the flag
+__device__ __forceinline__ float gemm_gate(const GemmArgs& a) {
+  return (a.flags & GEMM_GATED_RESIDUAL) ? rbf(1.f / (1.f + expf(-bf2f(*a.gate)))) : 1.f;
+}
+
 __device__ __forceinline__ float gemm_epilogue(float acc, int m, int n, const GemmArgs& a) {
   float v = acc;
   if (a.flags & GEMM_BIAS) v += bf2f(a.bias[n]);
   v = rbf(v);  // the Linear's bf16 output tensor
   if (a.flags & GEMM_GELU_ERF) v = rbf(gelu_erf(v));
   else if (a.flags & GEMM_GELU_TANH) v = rbf(gelu_tanh(v));
+  if (a.flags & GEMM_GATED_RESIDUAL) v = rbf(gemm_gate(a) * v);
   if (a.flags & GEMM_RESIDUAL) v = rbf(bf2f(a.residual[(size_t)m * a.ldr + n]) + v);
   return v;
 }
@@ -34,12 +40,13 @@ __device__ __forceinline__ float gemm_epilogue(float acc, int m, int n, const Ge
 // to be half of a ViT launch (k_gemm_g3 with neither fills nor MFMAs: 68.7 of 132 us, profiles/r04_vit8_g3_*_kernel_stats.csv):
 // every output element loaded its bias / residual value right before use inside a branchy loop, i.e. 16-64 dependent memory
 // round trips per lane.  The kernels now issue every epilogue load first (clamped addresses, no branch), then compute, then store.
-__device__ __forceinline__ float gemm_epilogue_pre(float acc, float bias, float res, int flags) {
+__device__ __forceinline__ float gemm_epilogue_pre(float acc, float bias, float res, int flags, float gate = 1.f) {
   float v = acc;
   if (flags & GEMM_BIAS) v += bias;
   v = rbf(v);  // the Linear's bf16 output tensor
   if (flags & GEMM_GELU_ERF) v = rbf(gelu_erf(v));
   else if (flags & GEMM_GELU_TANH) v = rbf(gelu_tanh(v));
+  if (flags & GEMM_GATED_RESIDUAL) v = rbf(gate * v);     // gate = gemm_gate(a), loaded once per lane
   if (flags & GEMM_RESIDUAL) v = rbf(res + v);
   return v;
 }
@@ -47,6 +54,7 @@ __device__ __forceinline__ float gemm_epilogue_pre(float acc, float bias, float 
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_store_tiles(const GemmArgs& a, const f32x4 (&acc)[TM][TN], int mbase, int nbase, int lane) {
   const int flags = a.flags;
+  const float gs = gemm_gate(a);
   float bv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -74,7 +82,7 @@ __device__ __forceinline__ void gemm_store_tiles(const GemmArgs& a, const f32x4 
       for (int r = 0; r < 4; ++r) {
         const int m = mbase + i * 16 + (lane >> 4) * 4 + r;
         const int n = nbase + j * 16 + (lane & 15);
-        const bf16_t o = f2bf(gemm_epilogue_pre(acc[i][j][r], bv[j], rv[i][j][r], flags));
+        const bf16_t o = f2bf(gemm_epilogue_pre(acc[i][j][r], bv[j], rv[i][j][r], flags, gs));
         if (m < a.M && n < a.N) a.C[(size_t)m * a.ldc + n] = o;
       }
 }
@@ -523,6 +531,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
         *reinterpret_cast<f32x4*>(reg + (unsigned)(i * 16 + (lane & 15)) * ROWB + (unsigned)(j * 16 + (lane >> 4) * 4) * 4u) = acc[i][j];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                   // the wave's own tile: no barrier
     const int flags = a.flags;
+    const float gs = gemm_gate(a);
     const int nl = (lane & 7) * 8, n = n0 + wc * 64 + nl;
     const bool nin = n < a.N;
     float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -564,7 +573,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float x0 = e < 2 ? v0[2 * e] : v1[2 * e - 4], x1 = e < 2 ? v0[2 * e + 1] : v1[2 * e - 3];
-        o[e] = (uint32_t)f2bf(gemm_epilogue_pre(x0, bv[2 * e], rv[2 * e], flags)) | ((uint32_t)f2bf(gemm_epilogue_pre(x1, bv[2 * e + 1], rv[2 * e + 1], flags)) << 16);
+        o[e] = (uint32_t)f2bf(gemm_epilogue_pre(x0, bv[2 * e], rv[2 * e], flags, gs)) | ((uint32_t)f2bf(gemm_epilogue_pre(x1, bv[2 * e + 1], rv[2 * e + 1], flags, gs)) << 16);
       }
       if (m < a.M && nin) *reinterpret_cast<u32x4*>(a.C + (size_t)m * a.ldc + n) = o;
     }
@@ -585,6 +594,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
   }
   // All bias / residual loads first (8 bytes each, clamped), then the arithmetic, then 8-byte stores.
   const int flags = a.flags;
+  const float gs = gemm_gate(a);
   const bool vec = (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
   const bool nvec = (a.N & 3) == 0;      // n is a multiple of 4: a lane's 4 columns are all inside or all outside the matrix
   const bool rvec = nvec && (flags & GEMM_RESIDUAL) && (a.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(a.residual) & 7) == 0;
@@ -622,10 +632,10 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wc * 64 + j * 16 + (lane >> 4) * 4;
-      const uint32_t o0 = f2bf(gemm_epilogue_pre(acc[i][j][0], bv[j][0], rv[i][j][0], flags));
-      const uint32_t o1 = f2bf(gemm_epilogue_pre(acc[i][j][1], bv[j][1], rv[i][j][1], flags));
-      const uint32_t o2 = f2bf(gemm_epilogue_pre(acc[i][j][2], bv[j][2], rv[i][j][2], flags));
-      const uint32_t o3 = f2bf(gemm_epilogue_pre(acc[i][j][3], bv[j][3], rv[i][j][3], flags));
+      const uint32_t o0 = f2bf(gemm_epilogue_pre(acc[i][j][0], bv[j][0], rv[i][j][0], flags, gs));
+      const uint32_t o1 = f2bf(gemm_epilogue_pre(acc[i][j][1], bv[j][1], rv[i][j][1], flags, gs));
+      const uint32_t o2 = f2bf(gemm_epilogue_pre(acc[i][j][2], bv[j][2], rv[i][j][2], flags, gs));
+      const uint32_t o3 = f2bf(gemm_epilogue_pre(acc[i][j][3], bv[j][3], rv[i][j][3], flags, gs));
       bf16_t* dst = a.C + (size_t)m * a.ldc + n;
       if (m < a.M && n < a.N) {
         if (vec && n + 3 < a.N) {
@@ -718,6 +728,7 @@ __global__ __launch_bounds__(1024) void k_sk_reduce(GemmArgs a, const bf16_t* no
   __shared__ float red[16];
   const int m = blockIdx.x, tid = threadIdx.x;
   const int flags = a.flags;
+  const float gs = gemm_gate(a);
   const float* p0 = a.part + (size_t)m * a.N;
   bf16_t* crow = a.C + (size_t)m * a.ldc;
   const bool vec = (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
@@ -733,7 +744,7 @@ __global__ __launch_bounds__(1024) void k_sk_reduce(GemmArgs a, const bf16_t* no
     if (rvec) { const u32x2 p2 = *reinterpret_cast<const u32x2*>(a.residual + (size_t)m * a.ldr + n); rv[0] = pk_lo(p2[0]); rv[1] = pk_hi(p2[0]); rv[2] = pk_lo(p2[1]); rv[3] = pk_hi(p2[1]); }
     else if (flags & GEMM_RESIDUAL) { for (int r = 0; r < 4; ++r) rv[r] = bf2f(a.residual[(size_t)m * a.ldr + n + r]); }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { keep[r] = bf2f(f2bf(gemm_epilogue_pre(v[r], bv[r], rv[r], flags))); ss += keep[r] * keep[r]; }
+    for (int r = 0; r < 4; ++r) { keep[r] = bf2f(f2bf(gemm_epilogue_pre(v[r], bv[r], rv[r], flags, gs))); ss += keep[r] * keep[r]; }
     if (vec) { const u32x2 pk = {pack2(keep[0], keep[1]), pack2(keep[2], keep[3])}; *reinterpret_cast<u32x2*>(crow + n) = pk; }
     else { for (int r = 0; r < 4; ++r) crow[n + r] = f2bf(keep[r]); }
   }

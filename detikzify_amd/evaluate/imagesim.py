@@ -19,7 +19,7 @@ The features of the *reference* image are identical for every rollout; `cache_re
 """
 from __future__ import annotations
 
-from typing import Dict, Literal, Union
+from typing import Any, Dict, Literal, Optional, Union
 
 import math
 import threading
@@ -68,7 +68,10 @@ class ImageSim:
         self.model, self.processor = model, processor
         self.mode, self.preprocess = mode, preprocess
         self.cache_reference = cache_reference
-        self._ref_cache: Dict[bytes, torch.Tensor] = {}
+        self._ref_cache: Dict[Any, torch.Tensor] = {}
+        # TikZero adapter (reference from_detikzify: AdapterVisionModel + AdapterProcessor): the embedding model's tokenizer; texts
+        # condition the tower through model._owner.vit_encode(adapter_input_ids=...).  None: texts are not used
+        self.text_tokenizer = None
         self._acc = threading.local()
         self.reset()
 
@@ -79,11 +82,16 @@ class ImageSim:
     def from_detikzify(cls, model, processor, mode=None, *args, **kwargs):
         mode = getattr(model.config, "pooling_mode", "emd") if mode is None else mode
         kwargs.pop("sync_on_compute", None)
-        return cls(model=model.model.vision_model, processor=unwrap_processor(processor).image_processor,
-                   mode=mode, *args, **kwargs)
+        sim = cls(model=model.model.vision_model, processor=unwrap_processor(processor).image_processor,
+                  mode=mode, *args, **kwargs)
+        if getattr(model, "has_adapter", lambda: False)():
+            sim.text_tokenizer = processor.tokenizer       # the AdapterProcessor's: the embedding model's tokenizer
+        return sim
 
     # ---- features --------------------------------------------------------------------------------
-    def get_vision_features(self, image: Union[Image.Image, str]) -> torch.Tensor:
+    def get_vision_features(self, image: Union[Image.Image, str, None], text: Optional[str] = None) -> torch.Tensor:
+        if text is not None and self.text_tokenizer is not None:
+            return self._text_features(image, text)
         image = load(image)
         if self.preprocess:
             image = expand(image, max(image.size), do_trim=True)
@@ -98,25 +106,53 @@ class ImageSim:
                 return out.last_hidden_state.squeeze().mean(dim=0)
             return out.last_hidden_state.squeeze()
 
-    def _reference_features(self, image) -> torch.Tensor:
-        if not self.cache_reference or not isinstance(image, Image.Image):
-            return self.get_vision_features(image)
-        key = image.tobytes()
+    def _text_features(self, image, text: str) -> torch.Tensor:
+        """the tower conditioned on `text` (image None: the adapter's dummy input), as the reference's AdapterVisionModel"""
+        px = None
+        if image is not None:
+            image = load(image)
+            if self.preprocess:
+                image = expand(image, max(image.size), do_trim=True)
+            px = self.processor(images=image, return_tensors="pt")["pixel_values"]
+        ids = torch.as_tensor(self.text_tokenizer(text=[text], truncation=True)["input_ids"][0], dtype=torch.int64).reshape(-1)
+        with torch.inference_mode():
+            feats, pooled = self.model._owner.vit_encode(px, want_pooled=self.mode == "cos", want_feats=self.mode != "cos",
+                                                         adapter_input_ids=ids)
+        if self.mode == "cos":
+            return pooled.squeeze()
+        if self.mode == "cos_avg":
+            return feats.squeeze().mean(dim=0)
+        return feats.squeeze()
+
+    def _reference_features(self, image, text: Optional[str] = None) -> torch.Tensor:
+        if text is not None and self.text_tokenizer is None:
+            text = None                                   # no adapter: texts are not used
+        if not self.cache_reference or not (isinstance(image, Image.Image) or (image is None and text is not None)):
+            return self.get_vision_features(image, text)
+        key = (None if image is None else image.tobytes(), text)
         if key not in self._ref_cache:
-            self._ref_cache[key] = self.get_vision_features(image)
+            self._ref_cache[key] = self.get_vision_features(image, text)
         return self._ref_cache[key]
 
-    def get_similarity(self, img1=None, img2=None, **_) -> float:
-        f1 = self.get_vision_features(img1)
-        f2 = self._reference_features(img2)
+    def get_similarity(self, img1=None, img2=None, text1=None, text2=None, **_) -> float:
+        f1 = self.get_vision_features(img1, text1)
+        f2 = self._reference_features(img2, text2)
         if f1.ndim > 1:   # patch features: earth mover's distance over pairwise cosine distances (:118-123)
             return 2.0 * math.tanh(-emd2_uniform(pairwise_cosine_distance(f1.double(), f2.double()))) + 1.0
         return F.cosine_similarity(f1.double(), f2.double(), dim=0).item()
 
     # ---- metric protocol (update / compute / reset) ---------------------------------------------
     def update(self, img1=None, img2=None, text1=None, text2=None):
-        if text1 is not None or text2 is not None:
-            pass  # text conditioning needs the TikZero adapter (out of scope)
+        if self.text_tokenizer is not None and (text1 is not None or text2 is not None):
+            # with an adapter (reference :127-144): every present input is a list of one length; each side needs an image or a text
+            inputs = {k: (v if isinstance(v, list) else [v]) for k, v in dict(img1=img1, img2=img2, text1=text1, text2=text2).items()
+                      if v is not None}
+            assert not ({"img1", "text1"}.isdisjoint(inputs) or {"img2", "text2"}.isdisjoint(inputs))
+            assert len(set(map(len, inputs.values()))) == 1
+            for values in zip(*inputs.values()):
+                self.score += self.get_similarity(**dict(zip(inputs, values)))
+                self.n_samples += 1
+            return
         a = img1 if isinstance(img1, list) else [img1]
         b = img2 if isinstance(img2, list) else [img2]
         assert len(a) == len(b)

@@ -40,7 +40,9 @@ class DetikzifyPipeline:
         return expand(image, max(image.size), do_trim=True) if preprocess else image
 
     def check_inputs(self, image, text):
-        assert text is None or hasattr(self.model, "adapter"), "You need to load an adapter for textual inputs!"
+        # (the adapter's processor nests the model's: a text only reaches the tower through it, reference adapter/__init__.py)
+        assert text is None or (hasattr(self.model, "adapter") and unwrap(self.processor) is not self.processor), \
+            "You need to load an adapter for textual inputs!"
         assert image or text, "Either image or text (or both) required!"
 
     def _generator(self, image, text, preprocess, **kw) -> DetikzifyGenerator:

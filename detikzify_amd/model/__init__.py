@@ -15,8 +15,9 @@ import os
 from pathlib import Path
 from typing import Optional, Tuple
 
-from .config import DetikzifyConfig, PRESETS, preset
+from .config import AdapterConfig, DetikzifyConfig, PRESETS, adapter_preset, preset
 from .modeling import DetikzifyForCausalLM, DetikzifyVisionModel, GenerationConfig
+from .adapter_processing import DUMMY_IMAGE, AdapterProcessor
 from .processing import BatchFeature, DetikzifyImageProcessor, DetikzifyProcessor
 from .tokenizer import SyntheticTokenizer, load_tokenizer
 
@@ -50,6 +51,7 @@ def _check_dtype(torch_dtype) -> None:
 def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v1: bool = False,
          synthetic: Optional[int] = None, device_map=None, torch_dtype=None, max_positions: Optional[int] = None,
          batch_slots: int = 0, weight_format: str = "bf16", synthetic_tokenizer: bool = False, vit_gelu_tanh: Optional[int] = None,
+         adapter: Optional[bool] = None, embedding_model: Optional[str] = None, cross_attn_every_n_layers: Optional[int] = None,
          **from_pretrained_kwargs) -> Tuple[DetikzifyForCausalLM, DetikzifyProcessor]:
     """(model, processor).  `device_map` may be an int GPU index (the reference passes
     device_map=RANK, examples/eval.py:112); torch_dtype must be bf16 / "auto" / None.
@@ -83,8 +85,13 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
             tokenizer = load_tokenizer(str(path), cfg.max_positions, cfg.arch)       # raises when the files are missing / broken
             if cfg.arch == "v1":
                 cfg.patch_token_id = tokenizer.bos_token_id      # v1/__init__.py:49
+        want_adapter = bool(adapter) or (adapter is None and (path / "adapter" / "model.safetensors").exists())   # model/__init__.py:58-59
+        if want_adapter:
+            _check_adapter_sources(cfg, path, embedding_model)
         model = DetikzifyForCausalLM(cfg, dev)
         _load_safetensors_dir(model, path)
+        if want_adapter:
+            _load_adapter(model, path, embedding_model, cross_attn_every_n_layers)
         if modality_projector:
             _load_projector(model, modality_projector)
         gc_file = path / "generation_config.json"
@@ -104,14 +111,33 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
                 f"{model_name_or_path!r} is not a local checkpoint directory and there is no network; "
                 "pass synthetic=<seed> for seeded synthetic weights at this preset's shapes")
         tokenizer = _synthetic_tokenizer(cfg)
+        if adapter:
+            _check_adapter_sources(cfg, None, None)
         model = DetikzifyForCausalLM(cfg, dev)
+        if adapter:     # seeded adapter at Llama-3.2-1B + tower shapes (a toy one for detikzify-tiny-v2); its tensors follow the model's
+            model.create_adapter(adapter_preset(model_name_or_path, int(cross_attn_every_n_layers or 1)))
         model.fill_synthetic(int(synthetic))
     model.generation_config.pad_token_id = tokenizer.pad_token_id     # v1/__init__.py:41
     image_processor = _checkpoint_image_processor(path, cfg)
     processor = DetikzifyProcessor(
         image_processor=image_processor, tokenizer=tokenizer, image_seq_len=cfg.num_patches,
         image_token=tokenizer.convert_ids_to_tokens(cfg.patch_token_id))
+    if getattr(model, "has_adapter", lambda: False)():     # reference model/adapter/__init__.py:9-23: the text goes to the embedding model's tokenizer
+        processor = AdapterProcessor(processor=processor, tokenizer=_adapter_tokenizer(model, path if synthetic is None else None,
+                                                                                      embedding_model))
     return model, processor
+
+
+def _adapter_tokenizer(model: DetikzifyForCausalLM, path: Optional[Path], embedding_model: Optional[str]):
+    """Llama-3.2-1B's tokenizer from the local embedding-model directory, configured as the reference does (pad
+    "<|finetune_right_pad_id|>", model_max_length 512); seeded models get the byte-level stand-in at the embedding vocabulary"""
+    a = model.adapter_config
+    if path is None:
+        return SyntheticTokenizer(a.vocab, bos_token_id=a.bos_token_id, eos_token_id=a.bos_token_id + 1, pad_token_id=a.pad_token_id,
+                                  model_max_length=a.text_max)
+    from transformers import AutoTokenizer
+    emb = Path(embedding_model) if embedding_model else path / "embedding_model"
+    return AutoTokenizer.from_pretrained(str(emb), pad_token="<|finetune_right_pad_id|>", model_max_length=a.text_max)
 
 
 def _synthetic_tokenizer(cfg: DetikzifyConfig) -> SyntheticTokenizer:
@@ -212,6 +238,43 @@ def _load_safetensors_dir(model: DetikzifyForCausalLM, path: Path):
     model._weights_ready = True
 
 
+def _check_adapter_sources(cfg: DetikzifyConfig, path: Optional[Path], embedding_model: Optional[str]) -> None:
+    """before anything is allocated: the tower must have the hooks, the embedding model must be on disk"""
+    if cfg.arch != "v2":
+        raise ValueError("Couldn't locate vision encoder layers! (the TikZero adapter hooks the HF SigLIP tower of a v2 checkpoint; "
+                         f"{cfg.name_or_path or 'this checkpoint'} is v1)")
+    if path is None:
+        return
+    emb = Path(embedding_model) if embedding_model else path / "embedding_model"
+    if not (emb / "config.json").exists():
+        raise FileNotFoundError(f"the TikZero adapter needs its embedding model (meta-llama/Llama-3.2-1B): no config.json under {emb}; "
+                                "pass embedding_model=<local directory> (there is no hub access)")
+    if not (path / "adapter" / "model.safetensors").exists():
+        raise FileNotFoundError(f"{path / 'adapter' / 'model.safetensors'} is missing")
+
+
+def _load_adapter(model: DetikzifyForCausalLM, path: Path, embedding_model: Optional[str], every_n: Optional[int]):
+    """<checkpoint>/adapter/model.safetensors (+ config.json) and the embedding model's directory (`embedding_model=` or
+    <checkpoint>/embedding_model/; there is no hub offline).  Tensor names as the reference's state dict: "adapter.*",
+    "embedding_model.*" (AutoModel: LlamaModel without head)."""
+    from safetensors import safe_open
+    emb = Path(embedding_model) if embedding_model else path / "embedding_model"
+    afile = path / "adapter" / "model.safetensors"
+    model.create_adapter(AdapterConfig.from_hf(str(emb / "config.json"), str(path / "adapter" / "config.json"), every_n or 0))
+    known, seen = set(model.tensor_names()), set()
+    for f, pre in [(afile, "adapter.")] + [(x, "embedding_model.") for x in sorted(emb.glob("*.safetensors"))]:
+        with safe_open(str(f), framework="pt") as sf:
+            for k in sf.keys():
+                name = pre + (k[len("model."):] if pre == "embedding_model." and k.startswith("model.") else k)
+                if name in known:
+                    model.load_tensor(name, sf.get_tensor(k))
+                    seen.add(name)
+    missing = [k for k in known if k.startswith(("adapter.", "embedding_model.")) and k not in seen and ".rope." not in k]
+    if missing:
+        raise KeyError(f"adapter / embedding model lack {len(missing)} tensors, e.g. {missing[:4]}")
+    model._install_rope_tables()
+
+
 def _load_projector(model: DetikzifyForCausalLM, filename: str):
     """modality_projector file (v1/modeling_detikzify.py:116-121): keys end in .weight / .bias."""
     from safetensors.torch import load_file
@@ -219,6 +282,6 @@ def _load_projector(model: DetikzifyForCausalLM, filename: str):
         model.load_tensor("model.mm_projector." + k.split(".")[-1], v)
 
 
-__all__ = ["load", "DetikzifyConfig", "DetikzifyForCausalLM", "DetikzifyVisionModel", "DetikzifyProcessor",
+__all__ = ["load", "AdapterProcessor", "DUMMY_IMAGE", "AdapterConfig", "adapter_preset", "DetikzifyConfig", "DetikzifyForCausalLM", "DetikzifyVisionModel", "DetikzifyProcessor",
            "DetikzifyImageProcessor", "BatchFeature", "SyntheticTokenizer", "GenerationConfig", "PRESETS",
            "preset", "v1_models", "v2_models"]

@@ -164,6 +164,73 @@ class DetikzifyConfig:
         return c
 
 
+@dataclass
+class AdapterConfig:
+    """The TikZero adapter (reference detikzify/model/adapter/modeling_adapter.py): its embedding model — a LlamaModel without
+    head, meta-llama/Llama-3.2-1B by default — and how often a cross-attention layer runs before a ViT block."""
+    every_n: int = 1                 # cross_attn_every_n_layers
+    text_max: int = 512              # the embedding tokenizer's model_max_length
+    hidden: int = 2048
+    layers: int = 16
+    heads: int = 32
+    kv_heads: int = 8
+    head_dim: int = 64
+    ffn: int = 8192
+    vocab: int = 128256
+    rms_eps: float = 1e-5
+    rope_theta: float = 500000.0
+    rope_factor: float = 32.0
+    rope_type: str = "llama3"
+    rope_low_freq_factor: float = 1.0
+    rope_high_freq_factor: float = 4.0
+    rope_original_max_position: int = 8192
+    bos_token_id: int = 128000
+    pad_token_id: int = 128004
+
+    @property
+    def max_positions(self) -> int:  # the embedding model's RoPE tables cover the longest text
+        return self.text_max
+
+    def oracle_dict(self) -> Dict[str, Any]:
+        """LlamaOracle's configuration of the embedding model"""
+        d = asdict(self)
+        d["max_positions"] = self.text_max
+        return d
+
+    @classmethod
+    def from_hf(cls, embedding_config: str, adapter_config: str = "", every_n: int = 0) -> "AdapterConfig":
+        """The embedding model's config.json (HF LlamaConfig) and, when there is one, the adapter's config.json: its
+        `cross_attn_every_n_layers` wins over `every_n` (default 1, the reference's)."""
+        t = json.loads(Path(embedding_config).read_text())
+        rs = t.get("rope_scaling") or {}
+        rtype = rs.get("rope_type", rs.get("type", "default"))
+        if rtype not in ("llama3", "default", "linear"):
+            raise NotImplementedError(f"embedding model rope scaling {rtype!r} is not supported by this build")
+        c = cls(hidden=t["hidden_size"], layers=t["num_hidden_layers"], heads=t["num_attention_heads"],
+                kv_heads=t.get("num_key_value_heads", t["num_attention_heads"]),
+                head_dim=t.get("head_dim") or t["hidden_size"] // t["num_attention_heads"], ffn=t["intermediate_size"],
+                vocab=t["vocab_size"], rms_eps=t.get("rms_norm_eps", 1e-5), rope_theta=t.get("rope_theta", 10000.0),
+                rope_factor=float(rs.get("factor", 1.0)), rope_type="llama3" if rtype == "llama3" else "linear",
+                rope_low_freq_factor=float(rs.get("low_freq_factor", 1.0)), rope_high_freq_factor=float(rs.get("high_freq_factor", 4.0)),
+                rope_original_max_position=int(rs.get("original_max_position_embeddings", 8192)),
+                bos_token_id=t.get("bos_token_id", 128000), pad_token_id=t.get("pad_token_id") or 128004)
+        c.every_n = int(every_n or 1)
+        if adapter_config and Path(adapter_config).exists():
+            c.every_n = int(json.loads(Path(adapter_config).read_text()).get("cross_attn_every_n_layers", c.every_n))
+        if c.every_n < 1:
+            raise ValueError(f"cross_attn_every_n_layers={c.every_n}")
+        return c
+
+
+def adapter_preset(model_name: str, every_n: int = 1) -> AdapterConfig:
+    """Seeded-weight adapters: Llama-3.2-1B for the real towers, a toy embedding LLaMA (hd 64, GQA G = 4, rope "llama3")
+    for detikzify-tiny-v2."""
+    if model_name.split("/")[-1] == "detikzify-tiny-v2":
+        return AdapterConfig(every_n=every_n, text_max=512, hidden=256, layers=2, heads=4, kv_heads=1, head_dim=64, ffn=512,
+                             vocab=300, rope_original_max_position=64, rope_factor=8.0, bos_token_id=1, pad_token_id=0)
+    return AdapterConfig(every_n=every_n)
+
+
 def v2_8b(name: str) -> DetikzifyConfig:
     """nllg/detikzify-v2-8b / v2.5-8b: HF SigLIP so400m/14 at 420 px (900 patches -> 300 tokens) + LLaMA-3.1-8B
     (dimensions from the upstream model cards; a real checkpoint's config.json overrides them)."""

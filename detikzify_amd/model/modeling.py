@@ -168,6 +168,49 @@ def _flat_ids(values) -> List[int]:
     return out
 
 
+def rope_tables(c) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cos/sin exactly as HF LlamaRotaryEmbedding computes them (modeling_llama.py:108-140): fp32 inv_freq (linear scaling:
+    / factor; "llama3": modeling_rope_utils._compute_llama3_parameters), fp32 pos*inv_freq, cos/sin cast to bf16.  `c` has the
+    DetikzifyConfig rope fields, head_dim and max_positions (a DetikzifyConfig or an AdapterConfig)."""
+    inv = 1.0 / (c.rope_theta ** (torch.arange(0, c.head_dim, 2, dtype=torch.int64).float() / c.head_dim))
+    if getattr(c, "rope_type", "linear") == "llama3":
+        low_wl = c.rope_original_max_position / c.rope_low_freq_factor
+        high_wl = c.rope_original_max_position / c.rope_high_freq_factor
+        wavelen = 2 * math.pi / inv
+        scaled = torch.where(wavelen > low_wl, inv / c.rope_factor, inv)
+        smooth = (c.rope_original_max_position / wavelen - c.rope_low_freq_factor) / (c.rope_high_freq_factor - c.rope_low_freq_factor)
+        mid = (1 - smooth) * scaled / c.rope_factor + smooth * scaled
+        inv = torch.where((wavelen <= low_wl) & (wavelen >= high_wl), mid, scaled)
+    elif c.rope_factor and c.rope_factor != 1.0:
+        inv = inv / c.rope_factor
+    freqs = torch.arange(c.max_positions, dtype=torch.float32)[:, None] * inv[None, :]
+    return freqs.cos().to(torch.bfloat16), freqs.sin().to(torch.bfloat16)
+
+
+def text_key(ids: torch.Tensor) -> int:
+    """content hash of a text's token ids (the C side keys text-conditioned image prefixes by (image key, text key))"""
+    b = ids.detach().to("cpu", torch.int64).reshape(-1).contiguous().numpy().tobytes()
+    return int.from_bytes(hashlib.blake2b(b, digest_size=8).digest(), "little") or 1
+
+
+DUMMY_IMAGE_KEY = 0x44554D4D59494D47     # image key of the adapter's dummy input (a text-only prompt)
+
+
+def adapter_text(adapter_input_ids, adapter_attention_mask=None) -> torch.Tensor:
+    """One prompt's text ids from the processor's adapter_input_ids / adapter_attention_mask.  One text has no padding; a
+    mask with zeros (several differently padded texts batched together) is not implemented."""
+    ids = torch.as_tensor(adapter_input_ids).detach().to("cpu", torch.int64)
+    if ids.dim() == 2:
+        if ids.shape[0] != 1:
+            raise ValueError("batch size 1 only (one text per prompt)")
+        ids = ids[0]
+    if adapter_attention_mask is not None and not bool(torch.as_tensor(adapter_attention_mask).bool().all()):
+        raise NotImplementedError("adapter_attention_mask with zeros (padded texts) is not supported: pass one unpadded text per prompt")
+    if ids.numel() < 1:
+        raise ValueError("empty adapter_input_ids")
+    return ids.contiguous()
+
+
 def _bf16_tensor_from_bits(bits: np.ndarray) -> torch.Tensor:
     return torch.from_numpy(bits.view(np.int16).copy()).view(torch.bfloat16)
 
@@ -281,24 +324,59 @@ class DetikzifyForCausalLM:
         """cos/sin exactly as HF LlamaRotaryEmbedding computes them (modeling_llama.py:108-140):
         fp32 inv_freq (linear scaling: / factor; "llama3": modeling_rope_utils._compute_llama3_parameters),
         fp32 pos*inv_freq, cos/sin cast to bf16."""
-        c = self.config
-        inv = 1.0 / (c.rope_theta ** (torch.arange(0, c.head_dim, 2, dtype=torch.int64).float() / c.head_dim))
-        if getattr(c, "rope_type", "linear") == "llama3":
-            low_wl = c.rope_original_max_position / c.rope_low_freq_factor
-            high_wl = c.rope_original_max_position / c.rope_high_freq_factor
-            wavelen = 2 * math.pi / inv
-            scaled = torch.where(wavelen > low_wl, inv / c.rope_factor, inv)
-            smooth = (c.rope_original_max_position / wavelen - c.rope_low_freq_factor) / (c.rope_high_freq_factor - c.rope_low_freq_factor)
-            mid = (1 - smooth) * scaled / c.rope_factor + smooth * scaled
-            inv = torch.where((wavelen <= low_wl) & (wavelen >= high_wl), mid, scaled)
-        elif c.rope_factor and c.rope_factor != 1.0:
-            inv = inv / c.rope_factor
-        freqs = torch.arange(c.max_positions, dtype=torch.float32)[:, None] * inv[None, :]
-        self.load_tensor("rope.cos", freqs.cos().to(torch.bfloat16))
-        self.load_tensor("rope.sin", freqs.sin().to(torch.bfloat16))
+        cos, sin = rope_tables(self.config)
+        self.load_tensor("rope.cos", cos)
+        self.load_tensor("rope.sin", sin)
+        if self.has_adapter():
+            cos, sin = rope_tables(self.adapter_config)
+            self.load_tensor("embedding_model.rope.cos", cos)
+            self.load_tensor("embedding_model.rope.sin", sin)
+
+    # ---- TikZero adapter (text conditioning) ----------------------------------------------------------------------------
+    def has_adapter(self) -> bool:
+        return hasattr(self, "adapter")
+
+    def create_adapter(self, acfg) -> None:
+        """Register the adapter and its embedding model with the context (weights still to be loaded / filled)."""
+        if self.config.arch == "v1":
+            raise ValueError("Couldn't locate vision encoder layers! (the TikZero adapter needs a v2 checkpoint's SigLIP tower)")
+        cc = _lib.DtkAdapterConfig(every_n=acfg.every_n, text_max=acfg.text_max, hidden=acfg.hidden, layers=acfg.layers,
+                                   heads=acfg.heads, kv_heads=acfg.kv_heads, head_dim=acfg.head_dim, ffn=acfg.ffn, vocab=acfg.vocab,
+                                   rms_eps=acfg.rms_eps, rope_theta=acfg.rope_theta, rope_factor=1.0,
+                                   rope_low_freq_factor=acfg.rope_low_freq_factor, rope_high_freq_factor=acfg.rope_high_freq_factor,
+                                   rope_original_max_position=acfg.rope_original_max_position)
+        self._check(self.lib.dtk_adapter_create(self._ctx, C.byref(cc)), "dtk_adapter_create")
+        self.adapter_config = acfg
+        self.adapter = SimpleNamespace(config=acfg)           # the reference's model.adapter / model.embedding_model attributes
+        self.embedding_model = SimpleNamespace(config=acfg)
+
+    def unload_cross_attn_adapter(self) -> None:
+        """reference CrossAttentionAdapterMixin.unload_cross_attn_adapter: frees the adapter; image-only calls afterwards are those
+        of a model that never had one"""
+        if not self.has_adapter():
+            raise AttributeError("no adapter is loaded")
+        with self._vit_lock:
+            self._check(self.lib.dtk_adapter_destroy(self._ctx), "dtk_adapter_destroy")
+        del self.adapter, self.embedding_model, self.adapter_config
+
+    def embed_text(self, adapter_input_ids: torch.Tensor) -> torch.Tensor:
+        """the embedding model's last_hidden_state [T, hidden] (bf16) of one text"""
+        ids = adapter_text(adapter_input_ids)
+        out = np.empty(ids.numel() * self.adapter_config.hidden, dtype=np.uint16)
+        with self._vit_lock:
+            self._check(self.lib.dtk_adapter_embed(self._ctx, ids.numpy().ctypes.data_as(C.c_void_p), ids.numel(),
+                                                   out.ctypes.data_as(C.c_void_p)), "dtk_adapter_embed")
+        return _bf16_tensor_from_bits(out).view(ids.numel(), self.adapter_config.hidden)
 
     # ---- vision tower -------------------------------------------------------------------------
-    def vit_encode(self, pixel_values: torch.Tensor, want_pooled: bool = True, want_feats: bool = True):
+    def vit_encode(self, pixel_values: Optional[torch.Tensor], want_pooled: bool = True, want_feats: bool = True,
+                   adapter_input_ids: Optional[torch.Tensor] = None, adapter_attention_mask: Optional[torch.Tensor] = None):
+        """(features, pooled); with adapter_input_ids the tower is conditioned on that text (pixel_values None: the adapter's
+        dummy input, one image)"""
+        if adapter_input_ids is not None:
+            return self._vit_encode_text(pixel_values, want_pooled, want_feats, adapter_text(adapter_input_ids, adapter_attention_mask))
+        if adapter_attention_mask is not None:
+            raise ValueError("adapter_attention_mask without adapter_input_ids")
         px = pixel_values.detach().to("cpu", torch.float32).contiguous()
         if px.dim() == 3:
             px = px[None]
@@ -315,9 +393,32 @@ class DetikzifyForCausalLM:
         p = _bf16_tensor_from_bits(pooled.reshape(-1)).view(B, c.vit_dim) if want_pooled else None
         return f, p
 
+    def _vit_encode_text(self, pixel_values, want_pooled, want_feats, tids):
+        if not self.has_adapter():
+            raise TypeError("adapter_input_ids given but no adapter is loaded (load(..., adapter=True))")
+        c = self.config
+        px = None if pixel_values is None else pixel_values.detach().to("cpu", torch.float32).contiguous()
+        if px is not None and px.dim() == 3:
+            px = px[None]
+        B = 1 if px is None else px.shape[0]
+        n = (c.vit_image // c.vit_patch) ** 2
+        feats = np.empty((B, n, c.vit_dim), dtype=np.uint16) if want_feats else None
+        pooled = np.empty((B, c.vit_dim), dtype=np.uint16)
+        with self._vit_lock:
+            self._check(self.lib.dtk_vit_encode_text(
+                self._ctx, None if px is None else px.numpy().ctypes.data_as(C.c_void_p), B, tids.numpy().ctypes.data_as(C.c_void_p),
+                tids.numel(), C.c_uint64(text_key(tids)), feats.ctypes.data_as(C.c_void_p) if want_feats else None,
+                pooled.ctypes.data_as(C.c_void_p) if want_pooled else None), "dtk_vit_encode_text")
+        f = _bf16_tensor_from_bits(feats.reshape(-1)).view(B, n, c.vit_dim) if want_feats else None
+        p = _bf16_tensor_from_bits(pooled.reshape(-1)).view(B, c.vit_dim) if want_pooled else None
+        return f, p
+
     # ---- decoder ------------------------------------------------------------------------------
     def prefill(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor] = None,
-                return_logits: bool = False, reuse: Optional[bool] = None, slot: Optional[int] = None) -> Optional[torch.Tensor]:
+                return_logits: bool = False, reuse: Optional[bool] = None, slot: Optional[int] = None,
+                adapter_input_ids: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        if adapter_input_ids is not None:
+            return self._prefill_text(input_ids, pixel_values, return_logits, reuse, slot, adapter_text(adapter_input_ids))
         ids = input_ids.detach().to("cpu", torch.int64).reshape(-1).contiguous()
         T = ids.numel()
         px_ptr, key = None, 0
@@ -341,6 +442,36 @@ class DetikzifyForCausalLM:
             else:
                 self._check(self.lib.dtk_prefill_slot(self._ctx, int(slot), ids.numpy().ctypes.data_as(C.c_void_p), T, px_ptr,
                                                       C.c_uint64(key), flags, lp), "dtk_prefill_slot")
+        return torch.from_numpy(logits) if return_logits else None
+
+    def _prefill_text(self, input_ids, pixel_values, return_logits, reuse, slot, tids):
+        """prefill with the tower conditioned on one text (pixel_values None: the adapter's dummy input); the cached image prefix
+        is keyed by (image, text)"""
+        if not self.has_adapter():
+            raise TypeError("adapter_input_ids given but no adapter is loaded (load(..., adapter=True))")
+        ids = input_ids.detach().to("cpu", torch.int64).reshape(-1).contiguous()
+        px_ptr, key = None, DUMMY_IMAGE_KEY
+        if pixel_values is not None:
+            px = pixel_values.detach().to("cpu", torch.float32).contiguous()
+            if px.dim() == 4:
+                if px.shape[0] != 1:
+                    raise ValueError("batch size 1 only")
+                px = px[0]
+            self._px_keepalive = px
+            px_ptr = px.numpy().ctypes.data_as(C.c_void_p)
+            key = self.image_key(pixel_values)
+        reuse = self.reuse_prefix if reuse is None else reuse
+        flags = (_lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE) if reuse else 0
+        logits = np.empty(self.config.vocab, dtype=np.float32) if return_logits else None
+        lp = logits.ctypes.data_as(C.c_void_p) if return_logits else None
+        tp, tk = tids.numpy().ctypes.data_as(C.c_void_p), C.c_uint64(text_key(tids))
+        with self._vit_lock:
+            if slot is None:
+                self._check(self.lib.dtk_prefill_text(self._ctx, ids.numpy().ctypes.data_as(C.c_void_p), ids.numel(), px_ptr,
+                                                      C.c_uint64(key), tp, tids.numel(), tk, flags, lp), "dtk_prefill_text")
+            else:
+                self._check(self.lib.dtk_prefill_slot_text(self._ctx, int(slot), ids.numpy().ctypes.data_as(C.c_void_p), ids.numel(),
+                                                           px_ptr, C.c_uint64(key), tp, tids.numel(), tk, flags, lp), "dtk_prefill_slot_text")
         return torch.from_numpy(logits) if return_logits else None
 
     def set_sampling(self, do_sample=False, temperature=1.0, top_p=1.0, top_k=0, seed=0,
@@ -496,6 +627,16 @@ class DetikzifyForCausalLM:
         unknown names — raises instead of being dropped: a drop-in must not silently decode something else."""
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
+        text_ids = None
+        if "adapter_input_ids" in hf_kwargs or "adapter_attention_mask" in hf_kwargs:
+            if not self.has_adapter():
+                raise TypeError("generate() got adapter_input_ids / adapter_attention_mask but no adapter is loaded "
+                                "(load(..., adapter=True))")
+            tids, tmask = hf_kwargs.pop("adapter_input_ids", None), hf_kwargs.pop("adapter_attention_mask", None)
+            if tids is None and tmask is not None:
+                raise ValueError("adapter_attention_mask without adapter_input_ids")
+            if tids is not None:
+                text_ids = adapter_text(tids, tmask)
         _reject_unsupported_generate_kwargs(hf_kwargs)
         if input_ids is None:
             input_ids = inputs
@@ -592,6 +733,9 @@ class DetikzifyForCausalLM:
         emit.many, emit.budget, emit.stop_ids = emit_many, (lambda: max_length - cur), eos_set
         emit.aborted = lambda: any(c.should_stop for c in light)
         engine = self.batch_engine
+        if n_new_max > 0 and engine is not None and text_ids is not None:
+            raise NotImplementedError("text-conditioned generation in a batch engine's slots is not implemented yet: "
+                                      "generate one text-conditioned sequence at a time")
         if n_new_max > 0 and engine is not None:
             # batched mode: this sequence decodes in a KV slot together with the other threads' sequences (infer/engine.py: the
             # native run loop; infer/batching.py: the Python-driven one); one pass over the weights serves all of them.  The
@@ -613,7 +757,10 @@ class DetikzifyForCausalLM:
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or ())
-                self.prefill(ids[0], pixel_values)
+                if text_ids is not None:
+                    self.prefill(ids[0], pixel_values, adapter_input_ids=text_ids)
+                else:
+                    self.prefill(ids[0], pixel_values)
                 launched = received = 0
                 stop = False
                 ahead = 2  # one step always in flight while the host handles the previous token

@@ -24,11 +24,11 @@
 extern "C" {
 #endif
 
-#define DTK_ABI_VERSION 6   /* 2: batch arrays of 32 entries (were 16); 3: DTK_MAX_BATCH = 64; 4: dtk_max_decode_slots,
+#define DTK_ABI_VERSION 7   /* 2: batch arrays of 32 entries (were 16); 3: DTK_MAX_BATCH = 64; 4: dtk_max_decode_slots,
                              * contexts with <= 5 slots decode in slots 0..3 (multi-vector kernels);
                              * 5: dtk_op_gemv_mx, dtk_mx_layout, dtk_stats.last_batch_step_fp8_mfma;
                              * 6: dtk_engine_* (the native run loop of a batch; replaces ABI 4's dtk_decode_batch_run), dtk_max_positions; dtk_last_error is
-                             * per calling thread */
+                             * per calling thread; 7: the TikZero adapter (dtk_adapter_*, *_text variants, dtk_op_gemm_gated) */
 
 typedef struct dtk_ctx dtk_ctx;
 
@@ -122,7 +122,7 @@ typedef struct dtk_stats {
 int  dtk_abi_version(void);
 /* layout check for bindings: sizeof of 0 dtk_config, 1 dtk_sampling, 2 dtk_stats; offsetof of 3 dtk_sampling.seed,
  * 4 dtk_config.reserved, 5 dtk_stats.probe_event_pair_ms; sizeof of 6 dtk_join, 7 dtk_engine_stats, 8 dtk_engine_ops; offsetof of
- * 9 dtk_join.sampling, 10 dtk_join.error_out; -1 for anything else */
+ * 9 dtk_join.sampling, 10 dtk_join.error_out; sizeof of 11 dtk_adapter_config; -1 for anything else */
 int  dtk_abi_struct_size(int which);
 /* last error of a context; ctx may be NULL for the error of a failed dtk_create */
 const char* dtk_last_error(const dtk_ctx* ctx);
@@ -226,6 +226,50 @@ int  dtk_get_logits_slot(dtk_ctx* ctx, int slot, float* logits_out);
 int  dtk_context_len_slot(const dtk_ctx* ctx, int slot);
 
 int  dtk_max_positions(const dtk_ctx* ctx);               /* KV capacity of a sequence in tokens (dtk_config.max_positions) */
+
+/* ---- Text conditioning: the TikZero cross-attention adapter (ABI 7) ---------------------------------------------------------------
+ * Replaces CrossAttentionAdapterMixin.load_cross_attn_adapter / add_hooks (reference detikzify/model/adapter/modeling_adapter.py,
+ * loaded by detikzify/model/__init__.py:58-59).  An embedding model (a LlamaModel without head: Llama-3.2-1B, hd 64, GQA) turns the
+ * text into final-norm hidden states; Linear(d_emb -> D, bias) connects them to the tower; before every ViT block i with
+ * (i + 1) % every_n == 0 a CrossAttentionLayer runs:
+ *   x = x + bf16(sigmoid(attn_gate)) * out_proj(attn(q_norm(q_proj(LN1(x))), k_norm(k_proj(c)), v_proj(c)))
+ *   x = x + bf16(sigmoid(mlp_gate)) * fc2(gelu(fc1(LN2(x))))                    (q_norm / k_norm: LayerNorm per head, eps = vit_ln_eps)
+ * Only the HF SigLIP tower of a v2 checkpoint has these hooks: dtk_adapter_create refuses a v1 context (DTK_ERR_ARG, "Couldn't
+ * locate vision encoder layers!", the reference's own refusal).  Tensors are registered with dtk_load_tensor / dtk_read_tensor /
+ * dtk_fill_synthetic under the reference's state-dict names: "embedding_model.embed_tokens.weight", "embedding_model.layers.3.
+ * self_attn.q_proj.weight", "embedding_model.norm.weight" (+ "embedding_model.rope.cos|sin", the embedding model's RoPE tables),
+ * "adapter.connector.weight|bias", "adapter.dummy_input", "adapter.layers.5.cross_attn.q_norm.weight",
+ * "adapter.layers.5.cross_attn_attn_gate", ...  The connector output and every cross layer's k / v (after k_norm) are computed once
+ * per text and kept for later calls with the same text ids (one text at a time; the cache compares the ids themselves, text_key
+ * only keys the image prefixes below).
+ * Text variants: text_ids (T_text int64, 1 <= T_text <= text_max, no padding) condition the tower; pixels = NULL means the adapter's
+ * dummy input (dummy_input.clamp(-1, 1)) for every image.  The KV prefix and image caches of the *_text prefills are keyed by the
+ * pair (image_key, text_key): the same pixels under another text are another image.  text_key 0 = unknown (never reused). */
+typedef struct dtk_adapter_config {
+  int32_t every_n;         /* cross_attn_every_n_layers (>= 1)                                  */
+  int32_t text_max;        /* longest text in tokens (tokenizer model_max_length: 512)          */
+  /* the embedding model (HF LlamaConfig fields) */
+  int32_t hidden, layers, heads, kv_heads, head_dim, ffn, vocab;
+  float   rms_eps;
+  float   rope_theta;      /* RoPE tables are loaded as "embedding_model.rope.cos|sin"; these seed the default (unscaled) ones */
+  float   rope_factor;
+  float   rope_low_freq_factor, rope_high_freq_factor;
+  int32_t rope_original_max_position;
+  int32_t reserved[3];
+} dtk_adapter_config;
+int  dtk_adapter_create(dtk_ctx* ctx, const dtk_adapter_config* cfg);
+int  dtk_adapter_destroy(dtk_ctx* ctx);          /* unload_cross_attn_adapter: image-only calls are as if it never existed */
+int  dtk_has_adapter(const dtk_ctx* ctx);
+int  dtk_vit_encode_text(dtk_ctx* ctx, const float* pixels, int batch, const int64_t* text_ids, int T_text, uint64_t text_key,
+                         void* feats_out_bf16, void* pooled_out_bf16);
+int  dtk_prefill_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
+                      const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_last_out);
+int  dtk_prefill_slot_text(dtk_ctx* ctx, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
+                           const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_last_out);
+/* diagnostic: the embedding model's last_hidden_state (T_text x hidden bf16) of text_ids */
+int  dtk_adapter_embed(dtk_ctx* ctx, const int64_t* text_ids, int T_text, void* hidden_out_bf16);
+/* the key the *_text prefills cache an image prefix under (image_key, text_key) -> key; 0 when either is 0 */
+uint64_t dtk_text_image_key(uint64_t image_key, uint64_t text_key);
 
 /* ---- The run loop of a batch of rollouts, native (ABI 6) ------------------------------------------------------------------------
  * Replaces, for every sequence decoded in a slot, the per-token host iteration of HF GenerationMixin._sample
@@ -389,6 +433,10 @@ int  dtk_set_option(dtk_ctx* ctx, const char* name, int value);
 /* C[M,N] = A[M,K] . W[N,K]^T (+epilogue) */
 int  dtk_op_gemm(dtk_ctx* ctx, const uint16_t* A, const uint16_t* W, const uint16_t* bias,
                  const uint16_t* residual, int M, int N, int K, int flags, uint16_t* C);
+/* C = residual + bf16(bf16(sigmoid(gate)) * bf16(A . W^T + bias)) (the adapter's gated residuals, GEMM_GATED_RESIDUAL); gate = one bf16;
+ * flags: DTK_GEMM_NAIVE only; the kernel is whatever the tuning switches ("gemm_impl", "gemm_tile", ...) select for the shape */
+int  dtk_op_gemm_gated(dtk_ctx* ctx, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual,
+                       const uint16_t* gate, int M, int N, int K, int flags, uint16_t* C);
 /* mode 0: y = W.x ; mode 1: y = W.rmsnorm(x, norm_w) ; fp32 result of the bf16-rounded output */
 int  dtk_op_gemv(dtk_ctx* ctx, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w,
                  int N, int K, int mode, float eps, uint16_t* y);
