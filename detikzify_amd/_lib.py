@@ -100,6 +100,8 @@ class DtkEngineOps(C.Structure):
     RESUME = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _I64P, C.c_int, C.c_uint64)
     CTXLEN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
     LASTERR = C.CFUNCTYPE(C.c_void_p, C.c_void_p)     # (const char*: the callee owns the text)
+    # not a field: dtk_engine_set_prefill_text_op's argument (dev, slot, ids, T, pixels, image_key, text_ids, n_text, text_key, flags)
+    PREFILL_TEXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _I64P, C.c_int, C.c_void_p, C.c_uint64, _I64P, C.c_int, C.c_uint64, C.c_int)
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -151,6 +153,9 @@ SYMBOLS = {
     "dtk_engine_read": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "dtk_engine_leave": (C.c_int, [_P, C.c_int]),
     "dtk_engine_get_stats": (C.c_int, [_P, C.POINTER(DtkEngineStats)]),
+    # ABI 7, additive: text-conditioned joins of the native run loop
+    "dtk_engine_submit_text": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_prefill_text_op": (C.c_int, [_P, DtkEngineOps.PREFILL_TEXT]),
     "dtk_prefill_slot": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_uint64, C.c_int, _P]),
     "dtk_set_sampling_slot": (C.c_int, [_P, C.c_int, C.POINTER(DtkSampling)]),
     "dtk_decode_batch_launch": (C.c_int, [_P, C.POINTER(C.c_int32)]),

@@ -13,6 +13,9 @@
 //   * wakes a slot's reader only at a flush token (a newline), after flush_max tokens, or at the end of the sequence;
 //   * executes queued joins (resume in place | fork the image prefix | prefill) between steps, after the steps in flight have been
 //     collected — a prefill drains the stream anyway, and a resumed slot must not be part of a step in flight.
+// A text-conditioned join (dtk_engine_submit_text, the TikZero adapter) is the same join under another identity: every lookup of a
+// slot's cache (resume, the prefix-cache fork) uses the pair key dtk_text_image_key(image_key, text_key), and every prefill goes
+// through the text prefill, so a slot never mixes KV of the same pixels under another text (or none).
 // A slot's arithmetic never depends on its company (csrc/dtk_api.hip), so which steps a sequence shares with which others —
 // the only thing this loop decides differently from the Python engine it replaces — does not change a token.
 #include <array>
@@ -50,6 +53,9 @@ struct Seq {
 
 struct Cmd {
   dtk_join* join = nullptr;
+  const int64_t* text = nullptr;    // the join's text ids (caller-owned until awaited), nullptr: an image-only join
+  int n_text = 0;
+  uint64_t text_key = 0;
   int rc = 0;
   bool done = false;
   std::condition_variable cv;
@@ -59,8 +65,12 @@ using ActiveSet = std::array<int32_t, DTK_MAX_BATCH>;
 
 }  // namespace
 
+using PrefillTextFn = int (*)(void* dev, int slot, const int64_t* ids, int T, const float* px, uint64_t image_key, const int64_t* text_ids,
+                              int n_text, uint64_t text_key, int flags);
+
 struct dtk_engine {
   dtk_engine_ops ops{};
+  PrefillTextFn prefill_text = nullptr;     // dtk_engine_set_prefill_text_op (dtk_engine_create: dtk_prefill_slot_text)
   std::mutex mu;
   std::condition_variable cv_run;
   std::thread th;
@@ -172,8 +182,16 @@ int set_error(dtk_engine* e, dtk_join* j, int rc, const char* what) {
 }
 
 // the device side of a join; runs on the loop's thread with no step in flight and e->mu released
-int do_join(dtk_engine* e, dtk_join* j) {
+int do_join(dtk_engine* e, const Cmd* c) {
   const dtk_engine_ops& o = e->ops;
+  dtk_join* j = c->join;
+  // the identity of the slot's cache: the pair key for a text join (what dtk_prefill_slot_text stores), else the image key
+  const uint64_t key = c->text ? dtk_text_image_key(j->image_key, c->text_key) : j->image_key;
+  auto prefill = [&](int s, int T, int flags) {
+    return c->text ? e->prefill_text(o.dev, s, j->ids, T, j->pixels, j->image_key, c->text, c->n_text, c->text_key, flags)
+                   : o.prefill_slot(o.dev, s, j->ids, T, j->pixels, j->image_key, flags);
+  };
+  const char* prefill_name = c->text ? "dtk_prefill_slot_text" : "dtk_prefill_slot";
   int slot = j->slot;
   j->slot_out = slot;
   if (j->try_resume && j->n_ids >= 2) {
@@ -183,7 +201,7 @@ int do_join(dtk_engine* e, dtk_join* j) {
       const int cand = j->n_candidates > 0 ? j->candidates[k] : slot;
       if (cand < 0 || cand >= o.decode_slots) return set_error(e, j, DTK_ERR_ARG, "dtk_engine_join: candidate slot out of range");
       int lcp = 0;
-      const int rc = o.slot_lcp(o.dev, cand, j->ids, j->n_ids, j->image_key, &lcp);
+      const int rc = o.slot_lcp(o.dev, cand, j->ids, j->n_ids, key, &lcp);
       if (rc) return set_error(e, j, rc, "dtk_slot_lcp");
       if (lcp > best_len) { best = cand; best_len = lcp; }
     }
@@ -191,7 +209,7 @@ int do_join(dtk_engine* e, dtk_join* j) {
       j->slot_out = slot = best;
       int rc = o.set_sampling_slot(o.dev, slot, &j->sampling);
       if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
-      rc = o.resume_slot(o.dev, slot, j->ids, j->n_ids, j->image_key);
+      rc = o.resume_slot(o.dev, slot, j->ids, j->n_ids, key);
       if (rc) return set_error(e, j, rc, "dtk_resume_slot");
       j->how_out = DTK_JOIN_RESUMED;
       return DTK_OK;
@@ -201,20 +219,29 @@ int do_join(dtk_engine* e, dtk_join* j) {
   if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
   const int reuse = DTK_PREFILL_REUSE_PREFIX | DTK_PREFILL_REUSE_IMAGE;
   if (j->prefix_len > 0 && j->prefix_in_place) {
-    rc = o.prefill_slot(o.dev, slot, j->ids, j->n_ids, j->pixels, j->image_key, reuse);
-    if (rc) return set_error(e, j, rc, "dtk_prefill_slot");
+    rc = prefill(slot, j->n_ids, reuse);
+    if (rc) return set_error(e, j, rc, prefill_name);
     j->how_out = DTK_JOIN_IN_PLACE;
     return DTK_OK;
   }
   if (j->prefix_len > 0 && j->prefix_src >= 0) {
     if (j->prefix_len > j->n_ids) return set_error(e, j, DTK_ERR_ARG, "dtk_engine_join: prefix longer than the prompt");
-    if (j->prefix_encode) {     // the image's first rollout: ViT + prefix prefill into the prefix-cache slot, greedy (its logits are forked)
+    bool encode = j->prefix_encode != 0;
+    if (!encode && j->prefix_src_whole) {
+      // a prefix-cache slot the caller believes holds this prefix: check before forking its rows (a failed join may have left the
+      // caller's bookkeeping behind the slot) and encode the prefix again if it does not
+      int lcp = 0;
+      rc = o.slot_lcp(o.dev, j->prefix_src, j->ids, j->prefix_len, key, &lcp);
+      if (rc) return set_error(e, j, rc, "dtk_slot_lcp(prefix slot)");
+      encode = lcp != j->prefix_len;
+    }
+    if (encode) {     // the image's first rollout: ViT + prefix prefill into the prefix-cache slot, greedy (its logits are forked)
       dtk_sampling g{};
       g.temperature = 1.0f; g.top_p = 1.0f;
       rc = o.set_sampling_slot(o.dev, j->prefix_src, &g);
       if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot(prefix slot)");
-      rc = o.prefill_slot(o.dev, j->prefix_src, j->ids, j->prefix_len, j->pixels, j->image_key, 0);
-      if (rc) return set_error(e, j, rc, "dtk_prefill_slot(prefix slot)");
+      rc = prefill(j->prefix_src, j->prefix_len, 0);
+      if (rc) return set_error(e, j, rc, c->text ? "dtk_prefill_slot_text(prefix slot)" : "dtk_prefill_slot(prefix slot)");
     }
     rc = o.kv_fork(o.dev, j->prefix_src, slot, j->prefix_len);
     if (rc) return set_error(e, j, rc, "dtk_kv_fork");
@@ -222,13 +249,13 @@ int do_join(dtk_engine* e, dtk_join* j) {
       j->how_out = DTK_JOIN_FORK_WHOLE;       // KV and next-token logits came with the fork
       return DTK_OK;
     }
-    rc = o.prefill_slot(o.dev, slot, j->ids, j->n_ids, j->pixels, j->image_key, reuse);
-    if (rc) return set_error(e, j, rc, "dtk_prefill_slot");
+    rc = prefill(slot, j->n_ids, reuse);
+    if (rc) return set_error(e, j, rc, prefill_name);
     j->how_out = DTK_JOIN_FORK_TAIL;
     return DTK_OK;
   }
-  rc = o.prefill_slot(o.dev, slot, j->ids, j->n_ids, j->pixels, j->image_key, j->full_flags);
-  if (rc) return set_error(e, j, rc, "dtk_prefill_slot");
+  rc = prefill(slot, j->n_ids, j->full_flags);
+  if (rc) return set_error(e, j, rc, prefill_name);
   j->how_out = DTK_JOIN_FULL;
   return DTK_OK;
 }
@@ -259,7 +286,7 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
   if (!rc) {
     lk.unlock();
     const double t0 = now_s();
-    rc = do_join(e, j);
+    rc = do_join(e, c);
     const double t1 = now_s();
     lk.lock();
     e->st.join_s += t1 - t0;
@@ -320,6 +347,23 @@ void run(dtk_engine* e) {
   }
 }
 
+// queue a join (text: its text ids, nullptr for an image-only join)
+int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  std::lock_guard<std::mutex> g(e->mu);
+  if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
+  if (text && !e->prefill_text) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_text: this engine's device has no text prefill (dtk_engine_set_prefill_text_op)");
+    return DTK_ERR_STATE;
+  }
+  Cmd* c = new Cmd();
+  c->join = j;
+  c->text = text; c->n_text = n_text; c->text_key = text_key;
+  e->cmds.push_back(c);
+  e->cv_run.notify_all();
+  *ticket_out = (uint64_t)(uintptr_t)c;
+  return DTK_OK;
+}
+
 // ---- the library's own context as the device --------------------------------------------------------------------------------------
 int ctx_launch(void* d, const int32_t* a) { return dtk_decode_batch_launch((dtk_ctx*)d, a); }
 int ctx_wait(void* d, int64_t* t) { return dtk_decode_batch_wait((dtk_ctx*)d, t); }
@@ -328,6 +372,10 @@ int ctx_sampling(void* d, int s, const dtk_sampling* sp) { return dtk_set_sampli
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
 int ctx_lcp(void* d, int s, const int64_t* ids, int n, uint64_t key, int* out) { return dtk_slot_lcp((dtk_ctx*)d, s, ids, n, key, out); }
 int ctx_resume(void* d, int s, const int64_t* ids, int n, uint64_t key) { return dtk_resume_slot((dtk_ctx*)d, s, ids, n, key); }
+int ctx_prefill_text(void* d, int s, const int64_t* ids, int T, const float* px, uint64_t key, const int64_t* tids, int n_text, uint64_t tkey,
+                     int flags) {
+  return dtk_prefill_slot_text((dtk_ctx*)d, s, ids, T, px, key, tids, n_text, tkey, flags, nullptr);
+}
 int ctx_len(void* d, int s) { return dtk_context_len_slot((const dtk_ctx*)d, s); }
 const char* ctx_err(void* d) { return dtk_last_error((const dtk_ctx*)d); }
 
@@ -355,7 +403,15 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
   o.slot_lcp = ctx_lcp; o.resume_slot = ctx_resume; o.context_len_slot = ctx_len; o.last_error = ctx_err;
   o.max_positions = dtk_max_positions(ctx);
   o.decode_slots = dtk_max_decode_slots(ctx);
-  return dtk_engine_create_ops(&o, out);
+  const int rc = dtk_engine_create_ops(&o, out);
+  return rc == DTK_OK ? dtk_engine_set_prefill_text_op(*out, ctx_prefill_text) : rc;
+}
+
+int dtk_engine_set_prefill_text_op(dtk_engine* e, PrefillTextFn prefill_slot_text) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->prefill_text = prefill_slot_text;
+  return DTK_OK;
 }
 
 void dtk_engine_destroy(dtk_engine* e) {
@@ -423,14 +479,13 @@ int dtk_engine_expect(dtk_engine* e, int n, int timeout_ms) {
 
 int dtk_engine_submit(dtk_engine* e, dtk_join* j, uint64_t* ticket_out) {
   if (!e || !j || !ticket_out) return DTK_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
-  if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
-  Cmd* c = new Cmd();
-  c->join = j;
-  e->cmds.push_back(c);
-  e->cv_run.notify_all();
-  *ticket_out = (uint64_t)(uintptr_t)c;
-  return DTK_OK;
+  return submit(e, j, nullptr, 0, 0, ticket_out);
+}
+
+int dtk_engine_submit_text(dtk_engine* e, dtk_join* j, const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  if (!e || !j || !ticket_out) return DTK_ERR_ARG;
+  if (!text_ids || n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_text: no text"); return DTK_ERR_ARG; }
+  return submit(e, j, text_ids, n_text, text_key, ticket_out);
 }
 
 int dtk_engine_await(dtk_engine* e, uint64_t ticket) {

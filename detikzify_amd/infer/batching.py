@@ -80,8 +80,10 @@ class BatchEngine:
         spare = n - self.capacity
         n_prefix = min(spare, 8 if prefix_slots is None else int(prefix_slots)) if self.share_prefix else 0
         self.prefix_slots: List[int] = list(range(n - n_prefix, n))
-        self.prefix_cache: "OrderedDict[Tuple[int, int], int]" = OrderedDict()     # (image key, prefix length) -> prefix slot, LRU order
-        self.slot_img: Dict[int, Tuple[int, int]] = {}      # slot -> (image key, prefix length) whose KV prefix it still holds
+        # (image key, text key, prefix length) -> prefix slot, LRU order; text key 0 = an image-only prompt, the adapter's text else
+        self.prefix_cache: "OrderedDict[Tuple[int, int, int], int]" = OrderedDict()
+        self.slot_img: Dict[int, Tuple[int, int, int]] = {}      # slot -> (image key, text key, prefix length) whose KV prefix it still holds
+        self._adapter_epoch = getattr(model, "adapter_epoch", 0)
         self.joins = 0
         # A sequence whose prompt (all but its last token) is still in a free slot's KV cache — an MCTS tree coming back to a node
         # of its own previous rollout — continues there without a prefill: the slot joins the batch at once and its first step
@@ -155,12 +157,26 @@ class BatchEngine:
             self._collect()
         self.model.batch_engine = None
 
+    def busy(self) -> bool:
+        """some sequence holds a slot (joined, or being joined)"""
+        with self._locked():
+            return len(self.free) + len(self.zombies) < self.capacity
+
     @contextmanager
-    def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, **_native_only) -> Iterator[_Sequence]:
+    def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, text_ids=None,
+                 **_native_only) -> Iterator[_Sequence]:
         """`owner`: whoever starts sequence after sequence (an MCTS tree: generate(sequence_owner=t)) — a join that cannot
         resume takes the slot its owner used last, so it does not overwrite a rollout ANOTHER owner may come back to.
+        `text_ids`: one unpadded text that conditions the tower (the adapter; pixel_values None = its dummy image): the slot's prefix is
+        that of the pair (image, text), and every prefill of the sequence is the text prefill.
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
-        want = self._prefix_key(ids, pixel_values) if (self.share_prefix and pixel_values is not None) else None
+        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_image_key, text_key
+        tids = adapter_text(text_ids) if text_ids is not None else None
+        tkey = text_key(tids) if tids is not None else 0
+        ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
+        slot_key = text_image_key(ikey, tkey) if tids is not None else ikey     # what the slot's cache is stored under (C side)
+        text = {} if tids is None else {"adapter_input_ids": tids}
+        want = self._prefix_key(ids, ikey, tkey) if (self.share_prefix and (pixel_values is not None or tids is not None)) else None
         with self._locked():
             while not self.free:
                 with self._plock:       # waiting for a slot is not wanting the lock: the driver must keep stepping
@@ -170,6 +186,11 @@ class BatchEngine:
                 finally:
                     with self._plock:
                         self.pending += 1
+            if getattr(self.model, "adapter_epoch", 0) != self._adapter_epoch:
+                # the adapter was created / unloaded: the C side cleared every slot's cached ids, so no slot holds a prefix any more
+                self._adapter_epoch = getattr(self.model, "adapter_epoch", 0)
+                self.prefix_cache.clear()
+                self.slot_img.clear()
             if self.zombies and self.error is None:
                 self._collect()     # a slot left while its last step was in flight is free once that step is read — and it may
                                     # be the very slot whose cache holds this prompt (a tree returning right after its rollout)
@@ -182,7 +203,7 @@ class BatchEngine:
             # (an image position takes the projected patch feature, not a token embedding: the forced token must be text)
             if (self.resume_in_place and n_ids >= 2 and (want is not None or pixel_values is None)
                     and int(ids.reshape(-1)[-1]) != self.model.config.image_token_id):
-                key = want[0] if want is not None else 0
+                key = slot_key if want is not None else 0
                 # an owner (an MCTS tree) resumes only in the slot IT used last: whether a join resumes or re-prefills must not
                 # depend on which other slots happen to be free at that moment (thread timing) — resumed rows were written by
                 # the decode kernels, prefilled rows by the GEMMs, so the choice is visible in the last bits of the logits and
@@ -216,20 +237,20 @@ class BatchEngine:
                 t0 = time.perf_counter()
                 self.model.set_sampling(slot=slot, **sampling)
                 if resume:
-                    self.model.resume_slot(slot, ids, want[0] if want is not None else 0)
+                    self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)
                     self.resumes += 1
                     forked = 2
                 else:
-                    forked = self._fork_prefix(slot, ids, pixel_values, want) if want is not None else 0
+                    forked = self._fork_prefix(slot, ids, pixel_values, want, text) if want is not None else 0
                     if want is None:
                         self.slot_img.pop(slot, None)
                 if forked == 2:
                     pass    # the prompt IS the prefix (rollout from the root): KV and logits were forked, nothing to run
                 elif forked:
-                    self.model.prefill(ids, pixel_values, slot=slot, reuse=True)    # only the tail beyond the prefix
+                    self.model.prefill(ids, pixel_values, slot=slot, reuse=True, **text)    # only the tail beyond the prefix
                 else:
-                    self.model.prefill(ids, pixel_values, slot=slot)
+                    self.model.prefill(ids, pixel_values, slot=slot, **text)
                 self.t_prefill += time.perf_counter() - t0
                 q = self.tokq[slot]
                 while not q.empty():       # leftovers of the slot's previous sequence
@@ -261,16 +282,16 @@ class BatchEngine:
                 self.cv.notify_all()   # a slot may have become free
 
     # -- called with self.cv held ---------------------------------------------------------------------
-    def _prefix_key(self, ids, pixel_values):
-        """(image key, prefix length) if the prompt starts with its image-token run, else None"""
+    def _prefix_key(self, ids, image_key: int, text_key: int):
+        """(image key, text key, prefix length) if the prompt starts with its image-token run, else None"""
         tok = self.model.config.image_token_id
         ids = ids.reshape(-1)
         n_img = int((ids == tok).sum())
         if n_img == 0 or not bool((ids[:n_img] == tok).all()):
             return None                       # the image run is not a leading prefix: no sharing
-        return (self.model.image_key(pixel_values), n_img)
+        return (image_key, text_key, n_img)
 
-    def _fork_prefix(self, slot: int, ids, pixel_values, key) -> int:
+    def _fork_prefix(self, slot: int, ids, pixel_values, key, text: Dict[str, Any]) -> int:
         """Give `slot` the KV of its image prefix without running ViT + prefill again.  Returns 1 (prefix KV in place: the
         caller prefills what follows with reuse), 2 (prefix == whole prompt and the next-token logits were forked too) or
         0 (nobody holds this image and there is no prefix-cache slot: the caller prefills in full and becomes a donor).
@@ -280,7 +301,7 @@ class BatchEngine:
         8 images x 4 rollouts encodes each image once either way; with a prefix-cache slot per image the joins of later
         rollouts are pure forks (no 1-token tail prefill to recover the logits)."""
         ids = ids.reshape(-1)
-        n_img = key[1]
+        n_img = key[2]
         src = self.prefix_cache.get(key)
         if src is None and self.slot_img.get(slot) == key:
             self.inplace_reuses += 1
@@ -299,7 +320,7 @@ class BatchEngine:
             if src is None:
                 _, src = self.prefix_cache.popitem(last=False)      # evict the least recently used image
             self.model.set_sampling(slot=src, do_sample=False)
-            self.model.prefill(ids[:n_img], pixel_values, slot=src)
+            self.model.prefill(ids[:n_img], pixel_values, slot=src, **text)
             self.prefix_cache[key] = src
         self.prefix_cache.move_to_end(key)
         self.model.kv_fork(src, slot, n_img)
@@ -495,28 +516,37 @@ def make_engine(model, processor=None, **kw):
 
 def simulate_parallel(pipeline, image, trees: int, expansions_per_tree: int, seed_base: int = 1000,
                       seeds: Optional[List[int]] = None, resume_in_place: bool = True, slots: Optional[int] = None,
-                      **gen_kwargs) -> Iterator[Tuple[float, Any]]:
+                      text: Optional[str] = None, **gen_kwargs) -> Iterator[Tuple[float, Any]]:
     """Root-parallel MCTS on one GPU: `trees` independent DetikzifyGenerator searches (tree t draws its sampling seeds
     from a torch generator seeded seeds[t], default seed_base + t) decoded as one batch.  Yields (score, document)
     pairs in completion order.  trees == 1 is the unmodified sequential search.  `slots` < trees: the trees take turns in that
-    many decode slots — a tree holds a slot only while it generates, so the others decode while it waits for its reward."""
+    many decode slots — a tree holds a slot only while it generates, so the others decode while it waits for its reward.
+    `text` (a model with the TikZero adapter): the searches are conditioned on it; `image` may then be None."""
     for _, score, doc in simulate_parallel_images(pipeline, [image], trees, expansions_per_tree, seed_base, seeds=seeds,
-                                                  resume_in_place=resume_in_place, slots=slots, **gen_kwargs):
+                                                  resume_in_place=resume_in_place, slots=slots,
+                                                  texts=None if text is None else [text], **gen_kwargs):
         yield score, doc
 
 
 def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_per_tree: int, seed_base: int = 1000,
                              seeds: Optional[List[int]] = None, resume_in_place: bool = True, slots: Optional[int] = None,
-                             **gen_kwargs) -> Iterator[Tuple[int, float, Any]]:
+                             texts: Optional[List[Optional[str]]] = None, **gen_kwargs) -> Iterator[Tuple[int, float, Any]]:
     """Several images in flight on one GPU (BASELINE config 5: 8 images x 4 rollouts): len(images) * trees_per_image
     independent searches decoded as one batch; the engine encodes every image once and forks its KV prefix into the
     slots of that image's trees.  A tree that comes back to a node of its own previous rollout continues in the slot that still
     holds it, without a prefill (BatchEngine resume_in_place; False = fork the image prefix + prefill the path on every join).  Yields (image index, score, document) in completion order.  Tree k (image k //
-    trees_per_image) samples with the seed stream seeds[k] (default seed_base + k)."""
+    trees_per_image) samples with the seed stream seeds[k] (default seed_base + k).
+    `texts` (a model with the TikZero adapter): one optional text per image that conditions its searches (the prompt, and the
+    reward's reference features); an image may be None when its text is given (the adapter's dummy image)."""
     import torch
-    imgs = [pipeline.load(im) for im in images]
+    texts = list(texts) if texts is not None else [None] * len(images)
+    assert len(texts) == len(images), "one text (or None) per image"
+    for im, txt in zip(images, texts):
+        pipeline.check_inputs(im, txt)
+    imgs = [pipeline.load(im) if im is not None else None for im in images]
     with torch.inference_mode():    # what every generator of an image would compute for itself (generate.py: _processed)
-        encs = [pipeline.processor(images=im, text=None, text_kwargs={"truncation": True}, return_tensors="pt") for im in imgs]
+        encs = [pipeline.processor(images=im, text=txt, text_kwargs={"truncation": True}, return_tensors="pt")
+                for im, txt in zip(imgs, texts)]
     trees = len(imgs) * trees_per_image
     if seeds is None:
         seeds = [seed_base + t for t in range(trees)]
@@ -535,7 +565,7 @@ def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_
         try:
             gen = torch.Generator().manual_seed(int(seeds[t]))
             draws = iter(lambda: int(torch.randint(0, 2 ** 62, (), generator=gen).item()), None)
-            g = generators[t] = pipeline._generator(imgs[t // trees_per_image], None, False, metric=pipeline.metric,
+            g = generators[t] = pipeline._generator(imgs[t // trees_per_image], texts[t // trees_per_image], False, metric=pipeline.metric,
                                                     processed=encs[t // trees_per_image], rng=random.Random(int(seeds[t])),
                                                     **gen_kwargs)      # (tie-breaks of the search from the tree's own stream too)
             base_generate = g.generate

@@ -10,6 +10,10 @@ max_length); the rollout threads block in dtk_engine_read — outside the interp
 per token.  Python keeps what is policy: which slot a sequence gets, which slot still holds which image prefix (fork / in-place
 reuse / prefix-cache LRU), and what each join therefore has to do; the native loop executes the joins in the order they were
 planned.  A slot's arithmetic does not depend on its company, so a sequence is the same tokens as under BatchEngine (tests).
+
+Text-conditioned sequences (the TikZero adapter: sequence(text_ids=...), dtk_engine_submit_text) share the slots with image-only
+ones.  Their prefix identity is (image key, text key, prefix length) — text key 0 for image-only prompts, DUMMY_IMAGE_KEY for a
+text without an image — so a prefix is forked or reused in place only under the same image AND text.
 """
 from __future__ import annotations
 
@@ -109,6 +113,10 @@ class _ScriptedOps:
             px = engine._pixels_by_key.get(int(key)) if pixels else None
             model.prefill(ids_of(ids, T), px, slot=slot, reuse=bool(flags & _lib.DTK_PREFILL_REUSE_PREFIX))
 
+        def prefill_text(dev, slot, ids, T, pixels, key, tids, n_text, tkey, flags):
+            px = engine._pixels_by_key.get(int(key)) if pixels else None
+            model.prefill(ids_of(ids, T), px, slot=slot, reuse=bool(flags & _lib.DTK_PREFILL_REUSE_PREFIX), adapter_input_ids=ids_of(tids, n_text))
+
         def sampling(dev, slot, sp):
             s = sp.contents
             model.set_sampling(slot=slot, do_sample=bool(s.do_sample), temperature=s.temperature, top_p=s.top_p, top_k=s.top_k, seed=s.seed,
@@ -134,6 +142,13 @@ class _ScriptedOps:
         self.keep = [O.LAUNCH(guard(launch)), O.WAIT(guard(wait)), O.PREFILL(guard(prefill)), O.SAMPLING(guard(sampling)), O.FORK(guard(fork)),
                      O.LCP(guard(lcp)), O.RESUME(guard(resume)), O.CTXLEN(ctxlen), O.LASTERR(lasterr)]
         self.ops = O(None, *self.keep, int(model.config.max_positions), int(engine.decode_slots))
+        # the text prefill only for a device that has an adapter (an engine without it refuses text joins in submit)
+        self.prefill_text = O.PREFILL_TEXT(guard(prefill_text)) if _has_adapter(model) else None
+
+
+def _has_adapter(model) -> bool:
+    probe = getattr(model, "has_adapter", None)
+    return bool(probe()) if callable(probe) else False
 
 
 class NativeBatchEngine:
@@ -157,8 +172,9 @@ class NativeBatchEngine:
         spare = n - self.capacity       # slots the decode batch does not need hold image prefixes (see BatchEngine)
         n_prefix = min(spare, 8 if prefix_slots is None else int(prefix_slots)) if self.share_prefix else 0
         self.prefix_slots: List[int] = list(range(n - n_prefix, n))
-        self.prefix_cache: "OrderedDict[Tuple[int, int], int]" = OrderedDict()
-        self.slot_img: Dict[int, Tuple[int, int]] = {}
+        self.prefix_cache: "OrderedDict[Tuple[int, int, int], int]" = OrderedDict()    # (image key, text key, prefix length) -> slot
+        self.slot_img: Dict[int, Tuple[int, int, int]] = {}
+        self._adapter_epoch = getattr(model, "adapter_epoch", 0)
         self.resume_in_place = resume_in_place
         self.last_slot: Dict[int, int] = {}
         self.joins = self.resumes = self.inplace_reuses = self.prefix_encodes = 0
@@ -174,6 +190,8 @@ class NativeBatchEngine:
         else:
             self._scripted = _ScriptedOps(model, self)
             rc = self.lib.dtk_engine_create_ops(C.byref(self._scripted.ops), C.byref(self._h))
+            if rc == 0 and self._scripted.prefill_text is not None and hasattr(self.lib, "dtk_engine_set_prefill_text_op"):
+                rc = self.lib.dtk_engine_set_prefill_text_op(self._h, self._scripted.prefill_text)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
         if not pipeline:
@@ -233,21 +251,36 @@ class NativeBatchEngine:
     def steps(self) -> int:
         return int((self.native_stats() if self._h else self._final)["steps"])
 
+    def busy(self) -> bool:
+        """some sequence holds a slot (joined, or being joined)"""
+        with self._cv:
+            return len(self.free) < self.capacity
+
     # ---- joins ---------------------------------------------------------------------------------------------------------------
-    def _prefix_key(self, ids, pixel_values):
+    def _prefix_key(self, ids, image_key: int, text_key: int):
+        """(image key, text key, prefix length) if the prompt starts with its image-token run, else None"""
         tok = self.model.config.image_token_id
         ids = ids.reshape(-1)
         n_img = int((ids == tok).sum())
         if n_img == 0 or not bool((ids[:n_img] == tok).all()):
             return None
-        return (self.model.image_key(pixel_values), n_img)
+        return (image_key, text_key, n_img)
+
+    def _check_adapter_epoch(self):
+        """(under _cv) creating or unloading the adapter clears every slot's cached ids on the C side: forget what the bookkeeping
+        says the slots hold"""
+        epoch = getattr(self.model, "adapter_epoch", 0)
+        if epoch != self._adapter_epoch:
+            self._adapter_epoch = epoch
+            self.prefix_cache.clear()
+            self.slot_img.clear()
 
     def _plan_prefix(self, j: "_lib.DtkJoin", slot: int, key) -> Callable[[], None]:
         """what a join of an image prompt into `slot` has to do to get the image prefix there (BatchEngine._fork_prefix, as a plan):
         fills j's prefix fields, returns the bookkeeping to apply once the plan is certain to run.  Sources, in order: a prefix-cache
         slot that holds this image (its fork also carries the logits); the slot itself (in place); any other slot that still holds
         the prefix (donor); else the image is encoded into a free — else the least recently used — prefix-cache slot."""
-        n_img = key[1]
+        n_img = key[2]
         j.prefix_len = n_img
         src = self.prefix_cache.get(key)
         if src is None and self.slot_img.get(slot) == key:
@@ -289,14 +322,21 @@ class NativeBatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 stop_ids: Iterable[int] = (), per_token: bool = True) -> Iterator[_NativeSequence]:
+                 stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None) -> Iterator[_NativeSequence]:
         """`owner`: see BatchEngine.sequence.  `max_new_tokens` / `stop_ids`: the sequence's own end (the native loop stops it there);
-        `per_token`: the reader is woken for every token (arbitrary stopping criteria / foreign streamers) instead of per line."""
+        `per_token`: the reader is woken for every token (arbitrary stopping criteria / foreign streamers) instead of per line.
+        `text_ids`: one unpadded text that conditions the tower (the adapter); pixel_values may then be None (the dummy image)."""
         if not self._h:
             raise _lib.DtkError("the batch engine is closed")
+        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_key
         ids = ids.detach().to("cpu", torch.int64).reshape(-1).contiguous()
         n_ids = int(ids.numel())
-        want = self._prefix_key(ids, pixel_values) if (self.share_prefix and pixel_values is not None) else None
+        tids = adapter_text(text_ids) if text_ids is not None else None
+        tkey = text_key(tids) if tids is not None else 0
+        if tids is not None and not hasattr(self.lib, "dtk_engine_submit_text"):
+            raise _lib.DtkError("this library has no dtk_engine_submit_text: text-conditioned sequences cannot join the batch")
+        ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
+        want = self._prefix_key(ids, ikey, tkey) if (self.share_prefix and (pixel_values is not None or tids is not None)) else None
         px = None
         if pixel_values is not None:
             px = pixel_values.detach().to("cpu", torch.float32).contiguous()
@@ -307,7 +347,7 @@ class NativeBatchEngine:
         j = _lib.DtkJoin()
         j.n_ids, j.ids = n_ids, ids.data_ptr()
         j.pixels = px.data_ptr() if px is not None else None
-        j.image_key = self.model.image_key(pixel_values) if pixel_values is not None else 0
+        j.image_key = ikey
         j.prefix_src = -1
         j.full_flags = (_lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE) if getattr(self.model, "reuse_prefix", False) else 0
         s = j.sampling
@@ -344,6 +384,7 @@ class NativeBatchEngine:
             # node of its own previous rollout.  Whether that holds is decided by the native loop when the join executes
             # (dtk_slot_lcp behind every step in flight); the plan here only names where to look.  An owner looks in the slot IT used
             # last (so that resume-or-prefill never depends on which other slots happen to be free: BatchEngine.sequence).
+            self._check_adapter_epoch()
             may_resume = (self.resume_in_place and n_ids >= 2 and (want is not None or pixel_values is None)
                           and int(ids[-1]) != self.model.config.image_token_id)
             holds = (lambda f: self.slot_img.get(f) == want) if want is not None else (lambda f: f not in self.slot_img)
@@ -370,7 +411,11 @@ class NativeBatchEngine:
             self.free.remove(slot)
             if owner is not None:
                 self.last_slot[owner] = slot
-            rc = self.lib.dtk_engine_submit(self._h, C.byref(j), C.byref(ticket))
+            if tids is not None:
+                rc = self.lib.dtk_engine_submit_text(self._h, C.byref(j), C.cast(tids.data_ptr(), C.POINTER(C.c_int64)), int(tids.numel()),
+                                                     C.c_uint64(tkey), C.byref(ticket))
+            else:
+                rc = self.lib.dtk_engine_submit(self._h, C.byref(j), C.byref(ticket))
             if rc != 0:
                 self.free.append(slot)
                 raise _lib.DtkError(f"dtk_engine_submit failed ({rc}): {j.error_out.decode(errors='replace')}")
@@ -416,4 +461,4 @@ class NativeBatchEngine:
                         self.prefix_cache.pop(want, None)      # ... and neither does the prefix-cache slot it was to be encoded into
                 self.free.append(slot)
                 self._cv.notify_all()
-            del ids, px     # (kept alive until here: the native join read them)
+            del ids, px, tids     # (kept alive until here: the native join read them)

@@ -141,14 +141,15 @@ class DetikzifyGenerator:
                  metric=None, compile_timeout: Optional[int] = 60, mcts_timeout: Optional[int] = None,
                  streamer=None, control: Optional[ExplicitAbort] = None, exploration: float = 0.6,
                  strict: bool = False, document_class: Type[TikzDocument] = TikzDocument, processed=None, rng=None, **gen_kwargs):
-        assert processed is None or text is None, "a shared processor output is for image-only prompts"
         self.model, self.processor = model, processor
         self.image, self.text, self.metric = image, text, metric
         self.compile_timeout, self.mcts_timeout = compile_timeout, mcts_timeout
         self.streamer, self.control = streamer, control or ExplicitAbort()
         self.exploration, self.strict, self.document_class = exploration, strict, document_class
         self.gen_kwargs = gen_kwargs
-        self._processed = processed             # processor output of (image, text); built on first use unless handed in
+        # processor output of (image, text) — the AdapterProcessor's for a text — built on first use unless handed in (the trees of
+        # simulate_parallel share one)
+        self._processed = processed
         self._newlines: Optional[Dict[int, NewlineToken]] = None
 
         self.norm = DynMinMaxNorm()

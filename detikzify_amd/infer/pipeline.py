@@ -61,14 +61,15 @@ class DetikzifyPipeline:
                  **gen_kwargs) -> Generator[Tuple[Numeric, TikzDocument], None, None]:
         """MCTS: yields (score, document) for every rollout until `expansions` / `timeout`.
 
-        `trees` > 1 (not in the reference): that many independent searches of the same image decoded as ONE batch on
-        this GPU (infer/batching.py; the model must have been loaded with batch_slots > trees), each with its own
+        `trees` > 1 (not in the reference): that many independent searches of the same image (and / or text) decoded as ONE
+        batch on this GPU (infer/batching.py; the model must have been loaded with batch_slots > trees), each with its own
         `expansions` / `timeout` budget — root parallelisation; results arrive in completion order."""
         if trees > 1:
             from .batching import simulate_parallel
-            assert preprocess and text is None, "parallel trees take an image and the default preprocessing"
+            assert preprocess, "parallel trees take the default preprocessing"
+            self.check_inputs(image, text)
             yield from simulate_parallel(self, image, trees=trees, expansions_per_tree=expansions or None,
-                                         mcts_timeout=timeout or None, **gen_kwargs)
+                                         mcts_timeout=timeout or None, text=text, **gen_kwargs)
             return
         generator = self._generator(image, text, preprocess, metric=self.metric,
                                     mcts_timeout=timeout or None, **gen_kwargs)

@@ -196,6 +196,11 @@ def text_key(ids: torch.Tensor) -> int:
 DUMMY_IMAGE_KEY = 0x44554D4D59494D47     # image key of the adapter's dummy input (a text-only prompt)
 
 
+def text_image_key(image_key: int, text_key_: int) -> int:
+    """the key a text-conditioned slot's cache is stored under (dtk_text_image_key: the pair (image, text); 0 if either is 0)"""
+    return int(_lib.load_library().dtk_text_image_key(C.c_uint64(int(image_key)), C.c_uint64(int(text_key_))))
+
+
 def adapter_text(adapter_input_ids, adapter_attention_mask=None) -> torch.Tensor:
     """One prompt's text ids from the processor's adapter_input_ids / adapter_attention_mask.  One text has no padding; a
     mask with zeros (several differently padded texts batched together) is not implemented."""
@@ -345,7 +350,9 @@ class DetikzifyForCausalLM:
                                    rms_eps=acfg.rms_eps, rope_theta=acfg.rope_theta, rope_factor=1.0,
                                    rope_low_freq_factor=acfg.rope_low_freq_factor, rope_high_freq_factor=acfg.rope_high_freq_factor,
                                    rope_original_max_position=acfg.rope_original_max_position)
+        self._refuse_while_batch_busy("create_adapter")
         self._check(self.lib.dtk_adapter_create(self._ctx, C.byref(cc)), "dtk_adapter_create")
+        self.adapter_epoch = getattr(self, "adapter_epoch", 0) + 1
         self.adapter_config = acfg
         self.adapter = SimpleNamespace(config=acfg)           # the reference's model.adapter / model.embedding_model attributes
         self.embedding_model = SimpleNamespace(config=acfg)
@@ -355,9 +362,18 @@ class DetikzifyForCausalLM:
         of a model that never had one"""
         if not self.has_adapter():
             raise AttributeError("no adapter is loaded")
+        self._refuse_while_batch_busy("unload_cross_attn_adapter")
         with self._vit_lock:
             self._check(self.lib.dtk_adapter_destroy(self._ctx), "dtk_adapter_destroy")
+        # every slot's cached ids are gone on the C side: a batch engine forgets which slot holds which prefix (it compares the epoch)
+        self.adapter_epoch = getattr(self, "adapter_epoch", 0) + 1
         del self.adapter, self.embedding_model, self.adapter_config
+
+    def _refuse_while_batch_busy(self, what: str) -> None:
+        engine = getattr(self, "batch_engine", None)
+        busy = getattr(engine, "busy", None)
+        if callable(busy) and busy():
+            raise _lib.DtkError(f"{what}() while sequences decode in the batch engine's slots: let them finish first")
 
     def embed_text(self, adapter_input_ids: torch.Tensor) -> torch.Tensor:
         """the embedding model's last_hidden_state [T, hidden] (bf16) of one text"""
@@ -733,19 +749,17 @@ class DetikzifyForCausalLM:
         emit.many, emit.budget, emit.stop_ids = emit_many, (lambda: max_length - cur), eos_set
         emit.aborted = lambda: any(c.should_stop for c in light)
         engine = self.batch_engine
-        if n_new_max > 0 and engine is not None and text_ids is not None:
-            raise NotImplementedError("text-conditioned generation in a batch engine's slots is not implemented yet: "
-                                      "generate one text-conditioned sequence at a time")
         if n_new_max > 0 and engine is not None:
             # batched mode: this sequence decodes in a KV slot together with the other threads' sequences (infer/engine.py: the
             # native run loop; infer/batching.py: the Python-driven one); one pass over the weights serves all of them.  The
             # sequence's own end (EOS, length budget) goes with it: the native loop stops the slot there.  Tokens come back in
-            # bursts (one per source line) unless something here needs to see every token as it is made.
+            # bursts (one per source line) unless something here needs to see every token as it is made.  A text (the adapter)
+            # goes with the sequence: its slot's prefix is keyed by (image, text).
             per_token = bool(heavy) or (streamer is not None and (put_token is None or bool(getattr(streamer, "per_token", put_tokens is None))))
             with engine.sequence(ids[0], pixel_values, dict(
                     do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, bad_ids=bad,
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or ()),
-                    owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token) as seq:
+                    owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
         elif n_new_max > 0:
             # the context has ONE un-slotted sequence: a second generate() on it from another thread would interleave its

@@ -368,6 +368,19 @@ int  dtk_engine_read(dtk_engine* e, int slot, int64_t* tokens_out, int cap, int3
 /* end slot's sequence now (its undelivered tokens stay readable); the slot can be joined again at once */
 int  dtk_engine_leave(dtk_engine* e, int slot);
 int  dtk_engine_get_stats(dtk_engine* e, dtk_engine_stats* out);
+/* ABI 7, additive: text-conditioned sequences (the TikZero adapter) in the engine's slots.  dtk_engine_submit_text queues a join like
+ * dtk_engine_submit whose tower is conditioned on text_ids (1 <= n_text, no padding; caller-owned until the join is awaited, as
+ * `ids` and `pixels`); pixels == NULL means the adapter's dummy input, as in dtk_prefill_slot_text.  Every prefill of such a join
+ * (prefix encode, in-place reuse, fork tail, full) is the text prefill, and resume / prefix-cache checks compare the slot's cache under
+ * the pair key dtk_text_image_key(image_key, text_key): the same pixels under another text, or under none, never share a slot's
+ * prefix.  dtk_engine_set_prefill_text_op gives an engine of dtk_engine_create_ops the device's text prefill (dtk_engine_create wires
+ * dtk_prefill_slot_text itself); a text join on an engine without it fails in submit with DTK_ERR_STATE (error_out says why).
+ * Every join that forks a whole prefix-cache slot first checks (slot_lcp under its key) that the slot still holds the prefix and
+ * encodes it again if not. */
+int  dtk_engine_submit_text(dtk_engine* e, dtk_join* j, const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out);
+int  dtk_engine_set_prefill_text_op(dtk_engine* e, int (*prefill_slot_text)(void* dev, int slot, const int64_t* ids, int T, const float* pixels,
+                                                                         uint64_t image_key, const int64_t* text_ids, int n_text,
+                                                                         uint64_t text_key, int flags));
 
 /* Tuning aids (tools/, bench): time one decode GEMV role (0 qkv, 1 o_proj, 2 gate/up, 3 down,
  * 4 lm_head; 5 / 6 = the batched gate/up kernel / its LDS-DMA twin with parts switched off, tools/probe_batch.py) in kernel
