@@ -179,6 +179,10 @@ SYMBOLS = {
     "dtk_adapter_embed": (C.c_int, [_P, _P, C.c_int, _P]),
     "dtk_text_image_key": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "dtk_op_gemm_gated": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    # additive (ABI stays 7): teacher-forced scoring — log-probabilities of a given program in one pass
+    "dtk_score": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P]),
+    "dtk_score_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P]),
+    "dtk_op_score": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

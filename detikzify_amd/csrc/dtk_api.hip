@@ -131,6 +131,10 @@ struct dtk_ctx {
   int qkv_rope_fused = 1;            // a sliced q/k/v role reduces inside the RoPE + KV-append kernel (dtk_set_option "qkv_rope_fused"; bit-identical)
   int prefill_sk = 1;                // sliced-K prefill GEMMs for the roles with <= 128 tiles of 256 x 128 (dtk_set_option "prefill_sk": 0 = the one-chain kernels, 2 / 4 / 8 = a cap on the slices)
   int32_t* ids_dev = nullptr;
+  // dtk_score: records of the log-softmax lm_head ([max_positions - 1][ceil(V / 128)] x 16 B) + the per-row results; allocated by the first
+  // scoring call and kept (hipMalloc of its own, not the arena: a context that never scores pays nothing)
+  float* score_rec = nullptr;
+  float* score_out = nullptr;         // [4][max_positions]: logprob, lse, argmax (int32), z[argmax]
   // decode step
   bf16_t *x, *q, *act;
   float *logits, *pm, *pl, *po;
@@ -1305,6 +1309,8 @@ void dtk_destroy(dtk_ctx* c) {
   for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
   if (c->tok_ring_host) (void)hipHostFree(c->tok_ring_host);
   if (c->arena) (void)hipFree(c->arena);
+  if (c->score_rec) (void)hipFree(c->score_rec);
+  if (c->score_out) (void)hipFree(c->score_out);
   if (c->stream_vit) (void)hipStreamDestroy(c->stream_vit);
   if (c->ev_va) (void)hipEventDestroy(c->ev_va);
   if (c->ev_vb) (void)hipEventDestroy(c->ev_vb);
@@ -1560,9 +1566,33 @@ static int dummy_pixels(dtk_ctx* c, int batch, std::vector<float>& out) {
   return DTK_OK;
 }
 
+// dtk_score's rider on a prefill: the log-probabilities of ids[first .. T-1] from the hidden states of rows first-1 .. T-2
+struct ScoreReq { int first; float* logprob; int32_t* argmax; float* lse; };
+
+static int score_buffers(dtk_ctx* c) {
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->score_rec) HIPCHK(c, hipMalloc(&c->score_rec, score_rec_floats(c->Tmax - 1, c->V) * sizeof(float)));
+  if (!c->score_out) HIPCHK(c, hipMalloc(&c->score_out, (size_t)4 * c->Tmax * sizeof(float)));
+  return DTK_OK;
+}
+
+// final norm of M rows of X -> Xn, lm_head with the log-softmax epilogue, merge: results in c->score_out.  targets: device, one per row
+static int score_rows(dtk_ctx* c, const bf16_t* X, int M, const int32_t* targets, hipStream_t s) {
+  const int d = c->d;
+  launch_rmsnorm_rows(X, d, c->final_norm, c->Xn, d, M, d, c->cfg.rms_eps, s);
+  GemmArgs g;
+  g.A = c->Xn; g.lda = d; g.W = c->lm_head; g.ldw = d; g.bias = nullptr; g.residual = nullptr; g.ldr = 0; g.C = nullptr; g.ldc = 0;
+  g.Wt = (c->t_lm_head && c->tiled_ready) ? c->t_lm_head : nullptr;
+  g.M = M; g.N = c->V; g.K = d; g.flags = 0; g.ls_target = targets; g.ls_rec = c->score_rec;
+  if (!launch_gemm_logsoftmax(g, s)) return fail(c, DTK_ERR_STATE, "dtk_score: the log-softmax lm_head kernel does not take this shape (d = %d)", d);
+  float* o = c->score_out;
+  launch_score_merge(c->score_rec, M, c->V, o, o + c->Tmax, reinterpret_cast<int32_t*>(o + 2 * (size_t)c->Tmax), o + 3 * (size_t)c->Tmax, s);
+  return DTK_OK;
+}
+
 static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_dst, DecState* st_dst, bool is_single,
                         const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out,
-                        const int64_t* text_ids = nullptr, int T_text = 0) {
+                        const int64_t* text_ids = nullptr, int T_text = 0, const ScoreReq* score = nullptr) {
   if (!c || !ids || T < 1) return fail(c, DTK_ERR_ARG, "dtk_prefill: bad argument");
   if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
   std::lock_guard<std::mutex> vit_guard(c->vit_mu);
@@ -1594,7 +1624,8 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
   int start = 0;
   const bool same_image = !has_img || (sh.cached_with_image == use_img && (!use_img || (image_key != 0 && sh.image_key == image_key)));
   if ((flags & DTK_PREFILL_REUSE_PREFIX) && same_image && !sh.cached_ids.empty()) {
-    const int lim = (int)std::min<size_t>(sh.cached_ids.size(), (size_t)T - 1);
+    int lim = (int)std::min<size_t>(sh.cached_ids.size(), (size_t)T - 1);
+    if (score) lim = std::min(lim, score->first - 1);      // the scored rows' hidden states are computed here, whatever the cache holds
     while (start < lim && sh.cached_ids[start] == ids[start]) ++start;
   }
   // ---- image features are needed only if an image position has to be recomputed
@@ -1637,8 +1668,20 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
   DecState st0{};
   st0.pos = T - 1; st0.next_pos = T; st0.token = (int32_t)ids[T - 1]; st0.draw = 0;
   HIPCHK(c, hipMemcpyAsync(st_dst, &st0, sizeof st0, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipEventRecord(c->ev_c, s));
+  if (score) {
+    // rows first-1 .. T-2 of the context = rows first-1-start .. of X; the target of row p is ids[p + 1], already on the device
+    const int rc = score_rows(c, c->X + (size_t)(score->first - 1 - start) * d, T - score->first, c->ids_dev + (score->first - start), s);
+    if (rc != DTK_OK) return rc;
+  }
+  HIPCHK(c, hipEventRecord(c->ev_c, s));      // stats.last_prefill_ms of a scoring call includes its lm_head pass
   if (logits_out) HIPCHK(c, hipMemcpyAsync(logits_out, logits_dst, (size_t)c->V * 4, hipMemcpyDeviceToHost, s));
+  if (score) {
+    const int M = T - score->first;
+    const float* o = c->score_out;
+    HIPCHK(c, hipMemcpyAsync(score->logprob, o, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    if (score->lse) HIPCHK(c, hipMemcpyAsync(score->lse, o + c->Tmax, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    if (score->argmax) HIPCHK(c, hipMemcpyAsync(score->argmax, o + 2 * (size_t)c->Tmax, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   float ms = 0.f;
@@ -1657,6 +1700,27 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
 int dtk_prefill(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
   if (!c) return DTK_ERR_ARG;
   return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, image_key, flags, logits_out);
+}
+
+// argument checks of dtk_score / dtk_score_text: everything is refused before anything is launched
+static int score_check(dtk_ctx* c, const int64_t* ids, int T, int first, const float* logprob_out) {
+  if (!ids || !logprob_out) return fail(c, DTK_ERR_ARG, "dtk_score: null argument");
+  if (T < 2) return fail(c, DTK_ERR_ARG, "dtk_score: %d token(s): scoring needs a context token and a target (T >= 2)", T);
+  if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "dtk_score: %d tokens exceed max_positions %d", T, c->Tmax);
+  if (first < 1 || first > T - 1) return fail(c, DTK_ERR_ARG, "dtk_score: first = %d (the first scored target position: 1 .. T-1 = %d)", first, T - 1);
+  for (int t = first; t < T; ++t)
+    if (ids[t] < 0 || ids[t] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_score: target id %lld at position %d outside [0, %d)", (long long)ids[t], t, c->V);
+  if (!gemm_logsoftmax_supported(c->d)) return fail(c, DTK_ERR_ARG, "dtk_score: the log-softmax lm_head kernel needs hidden %% 8 == 0 (d = %d)", c->d);
+  return score_buffers(c);
+}
+
+int dtk_score(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags, int first,
+              float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  if (!c) return DTK_ERR_ARG;
+  const int rc = score_check(c, ids, T, first, logprob_out);
+  if (rc != DTK_OK) return rc;
+  const ScoreReq rq{first, logprob_out, argmax_out, lse_out};
+  return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, image_key, (int)flags, nullptr, nullptr, 0, &rq);
 }
 
 int dtk_prefill_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
@@ -2470,6 +2534,19 @@ int dtk_prefill_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels,
                       text_ids, T_text);
 }
 
+int dtk_score_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, const int64_t* text_ids, int T_text,
+                   uint64_t text_key, uint32_t flags, int first, float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  if (!c) return DTK_ERR_ARG;
+  const int rc0 = score_check(c, ids, T, first, logprob_out);
+  if (rc0 != DTK_OK) return rc0;
+  std::vector<float> dummy;
+  const int rc = prefill_text_common(c, pixels, dummy, text_ids);
+  if (rc != DTK_OK) return rc;
+  const ScoreReq rq{first, logprob_out, argmax_out, lse_out};
+  return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, dtk_text_image_key(image_key, text_key), (int)flags, nullptr,
+                      text_ids, T_text, &rq);
+}
+
 int dtk_prefill_slot_text(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
                           const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_out) {
   if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_prefill_slot_text: slot %d of %d", slot, c ? c->nb : 0);
@@ -2534,6 +2611,38 @@ int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t
   }
   else if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s); else launch_gemm_mfma(g, s);
   HIPCHK(c, hipMemcpyAsync(C, dC, (size_t)M * N * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return DTK_OK;
+}
+
+int dtk_op_score(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
+                 float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out) {
+  if (!c || !Xn || !W || !targets || !logprob_out || M < 1 || N < 1 || K < 8 || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_score: bad argument");
+  for (int m = 0; m < M; ++m)
+    if (targets[m] < 0 || targets[m] >= N) return fail(c, DTK_ERR_ARG, "dtk_op_score: target %d of row %d outside [0, %d)", targets[m], m, N);
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t off = 0;
+  OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(int32_t, dT, M);
+  OPBUF(float, dRec, score_rec_floats(M, N)); OPBUF(float, dO, (size_t)4 * M);
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dA, Xn, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dT, targets, (size_t)M * 4, hipMemcpyHostToDevice, s));
+  GemmArgs g;
+  g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = nullptr; g.residual = nullptr; g.ldr = 0; g.C = nullptr; g.ldc = 0;
+  g.M = M; g.N = N; g.K = K; g.flags = 0; g.ls_target = dT; g.ls_rec = dRec;
+  if (flags & DTK_GEMM_WT) {
+    OPBUF(bf16_t, dWt, tiled_elems(N, K));
+    launch_retile(dW, dWt, N, K, s);
+    g.Wt = dWt;
+  }
+  if (!launch_gemm_logsoftmax(g, s)) return fail(c, DTK_ERR_ARG, "dtk_op_score: the kernel does not take this shape");
+  launch_score_merge(dRec, M, N, dO, dO + M, reinterpret_cast<int32_t*>(dO + 2 * (size_t)M), dO + 3 * (size_t)M, s);
+  HIPCHK(c, hipMemcpyAsync(logprob_out, dO, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  if (lse_out) HIPCHK(c, hipMemcpyAsync(lse_out, dO + M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  if (argmax_out) HIPCHK(c, hipMemcpyAsync(argmax_out, dO + 2 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+  if (zmax_out) HIPCHK(c, hipMemcpyAsync(zmax_out, dO + 3 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   return DTK_OK;

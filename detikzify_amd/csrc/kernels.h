@@ -224,6 +224,10 @@ struct GemmArgs {
   // stream of the prefill GEMMs reached 2.4 TB/s of HBM), and the piece lands in LDS as the MFMA operand.  Same values, same k order.
   const bf16_t* Wt = nullptr;
   const bf16_t* gate = nullptr;  // GEMM_GATED_RESIDUAL: one bf16 scalar in device memory (the gate's logit)
+  // launch_gemm_logsoftmax (the LS instantiations of k_gemm_g3 / k_gemm_mfma<64, 128>): no C; per (row, 128-column tile) one record
+  // (max, sum exp(z - max), z[ls_target[row]] or -inf, argmax) of the bf16-rounded outputs z
+  const int32_t* ls_target = nullptr;  // the column whose z each row reports [M]
+  float* ls_rec = nullptr;       // records [M][ceil(N / 128)][4] fp32 (16-byte aligned)
 };
 __host__ __device__ inline int sk_tiles_per_slice(int K, int S) { const int T = K / 64; return (T + S - 1) / S; }
 // slices of a decoder-prefill role, from its WEIGHT shape alone: the largest power of two <= 8 that keeps 256 x 128 tiles x slices within
@@ -268,6 +272,14 @@ void set_gemm_ring(int v);   // LDS stages of k_gemm_dma: 2..4
 void set_gemm_g3_min_blocks(int v);     // gemm_impl 4: 256 x 128 blocks a shape needs to take k_gemm_g3 (default 128)
 void set_gemm_glds_min_tiles(int v);   // gemm_impl 2: 128 x 128 tiles a shape needs to take k_gemm_glds
 void launch_gemm_naive(const GemmArgs& a, hipStream_t s);
+// Teacher-forced scoring (dtk_score): lm_head over M rows with the log-softmax folded into the GEMM's epilogue — a.A = the final-normed
+// rows, a.W (+ a.Wt) = lm_head, a.ls_target / a.ls_rec as above; then launch_score_merge folds each row's records into
+// logprob = z[target] - logsumexp(z), lse, argmax (lowest index on ties) and z[argmax].  No [M][N] buffer exists at any point.
+// false = operands misaligned / missing (nothing launched); gemm_logsoftmax_supported(K) = what dtk_score checks before it launches anything.
+static inline size_t score_rec_floats(int M, int N) { return (size_t)M * (size_t)((N + 127) / 128) * 4; }
+static inline bool gemm_logsoftmax_supported(int K) { return K >= 8 && (K % 8) == 0; }
+bool launch_gemm_logsoftmax(const GemmArgs& a, hipStream_t s);
+void launch_score_merge(const float* rec, int M, int N, float* logprob, float* lse, int32_t* argmax, float* zmax, hipStream_t s);
 
 void launch_layernorm_rows(const bf16_t* X, int ldx, const bf16_t* w, const bf16_t* b,
                            bf16_t* Y, int ldy, int M, int D, float eps, hipStream_t s);

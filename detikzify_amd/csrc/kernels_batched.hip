@@ -50,6 +50,35 @@ __device__ __forceinline__ float gemm_epilogue_pre(float acc, float bias, float 
   if (flags & GEMM_RESIDUAL) v = rbf(res + v);
   return v;
 }
+// ------------------------------------------------------------------------------------------
+// Log-softmax epilogue (template parameter LS) — lm_head over many rows for teacher-forced scoring (dtk_score): a tile never stores its logits.  z = rbf(acc) is the
+// logit the last-row path (PRO_RMSNORM + EPI_LOGITS) produces; per (row, 128-column tile) the block leaves ONE 16-byte record
+//   (m = max z, l = sum exp(z - m), z[target] or -inf, argmax as int bits; lowest column on ties — z[argmax] is m itself).
+// A wave reduces its 64 columns of a row with shuffles (a fixed butterfly: every lane ends with the same sums), the two waves that share
+// a 128-column tile meet in LDS and the lower one merges (lower columns first) and stores.  A record is a function of the row's hidden
+// state, lm_head and the target alone: not of M, of the tile orientation, or of the neighbouring rows.  k_score_merge folds a row's
+// records in an order fixed by the tile count.
+#define LS_NEG_INF (-__builtin_huge_valf())
+struct LsRec { float m, l, zt; int ix; };
+__device__ __forceinline__ void ls_take_max(float& m, int& ix, float om, int oi) {
+  if (om > m || (om == m && oi < ix)) { m = om; ix = oi; }
+}
+// a = the lower columns, b = the higher ones
+__device__ __forceinline__ LsRec ls_merge(const LsRec& a, const LsRec& b) {
+  LsRec o;
+  o.m = a.m; o.ix = a.ix;
+  ls_take_max(o.m, o.ix, b.m, b.ix);
+  const float la = a.m == LS_NEG_INF ? 0.f : a.l * expf(a.m - o.m), lb = b.m == LS_NEG_INF ? 0.f : b.l * expf(b.m - o.m);
+  o.l = la + lb;
+  o.zt = fmaxf(a.zt, b.zt);
+  return o;
+}
+__device__ __forceinline__ void ls_store(const GemmArgs& a, int m, int tile, const LsRec& r) {
+  const int NT = (a.N + 127) >> 7;
+  const f32x4 v = {r.m, r.l, r.zt, __int_as_float(r.ix)};
+  *reinterpret_cast<f32x4*>(a.ls_rec + ((size_t)m * NT + tile) * 4) = v;
+}
+
 // epilogue of the kernels whose lanes hold the standard C/D layout of TM x TN 16 x 16 tiles (col = lane & 15, row = (lane >> 4) * 4 + reg)
 template <int TM, int TN>
 __device__ __forceinline__ void gemm_store_tiles(const GemmArgs& a, const f32x4 (&acc)[TM][TN], int mbase, int nbase, int lane) {
@@ -91,7 +120,7 @@ __device__ __forceinline__ void gemm_store_tiles(const GemmArgs& a, const f32x4 
 // wave reads TM + TN fragments from LDS for TM*TN MFMAs.  64x64 (2+2 reads per 4 MFMAs) is LDS-read-bound; 128x64 and
 // 128x128 (4+4 per 16) are not, but need M*N large enough to fill 256 CUs: launch_gemm_mfma picks per shape.  The k order
 // per output element is the same for every tile shape, so all variants (and the naive twin) round identically.
-template <int TBM, int TBN, int D = 1, int TBK = 64>   // D = k-tiles of global loads kept in flight in registers; TBK = k-tile
+template <int TBM, int TBN, int D = 1, int TBK = 64, bool LS = false>   // D = k-tiles of global loads kept in flight in registers; TBK = k-tile; LS = the log-softmax epilogue
 __global__ __launch_bounds__(256) void k_gemm_mfma(GemmArgs a) {
   constexpr int TM = TBM / 32, TN = TBN / 32;      // MFMA tiles per wave (2 x 2 wave grid; TBM, TBN >= 32)
   constexpr int CH = TBK / 8;                      // 16-byte chunks per tile row
@@ -186,6 +215,54 @@ __global__ __launch_bounds__(256) void k_gemm_mfma(GemmArgs a) {
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
       }
     }
+  }
+  if (LS) {
+    // standard C/D layout: a lane holds column (lane & 15) of TN tiles for rows (lane >> 4) * 4 + r of TM tiles: the 16 lanes of a row
+    // group reduce a row's TBN / 2 = 64 columns (xor 1, 2, 4, 8); the wc = 1 wave parks its half-records in LDS, wc = 0 merges and stores
+    static_assert(!LS || TBN == 128, "a record is a 128-column tile");
+    __syncthreads();                               // the operand tiles are free
+    LsRec* park = reinterpret_cast<LsRec*>(As);    // [2][TBM / 2]
+    LsRec rec[TM][4];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wr * (TBM / 2) + i * 16 + (lane >> 4) * 4 + r;
+        const int tgt = a.ls_target[min(m, a.M - 1)];
+        float z[TN], mx = LS_NEG_INF, zt = LS_NEG_INF;
+        int ix = 0x7fffffff;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int n = n0 + wc * (TBN / 2) + j * 16 + (lane & 15);
+          z[j] = n < a.N ? rbf(acc[i][j][r]) : LS_NEG_INF;
+          if (z[j] > mx) { mx = z[j]; ix = n; }
+          if (n == tgt) zt = z[j];
+        }
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) {
+          const float om = __shfl_xor(mx, off, 64); const int oi = __shfl_xor(ix, off, 64);
+          ls_take_max(mx, ix, om, oi);
+          zt = fmaxf(zt, __shfl_xor(zt, off, 64));
+        }
+        float l = 0.f;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) l += z[j] == LS_NEG_INF ? 0.f : expf(z[j] - mx);
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) l += __shfl_xor(l, off, 64);
+        rec[i][r].m = mx; rec[i][r].l = l; rec[i][r].zt = zt; rec[i][r].ix = ix;
+        if (wc == 1 && (lane & 15) == 0) park[wr * (TBM / 2) + i * 16 + (lane >> 4) * 4 + r] = rec[i][r];
+      }
+    __syncthreads();
+    if (wc == 0 && (lane & 15) == 0) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int ml = wr * (TBM / 2) + i * 16 + (lane >> 4) * 4 + r, m = m0 + ml;
+          if (m < a.M) ls_store(a, m, n0 >> 7, ls_merge(rec[i][r], park[ml]));
+        }
+    }
+    return;
   }
   gemm_store_tiles<TM, TN>(a, acc, m0 + wr * (TBM / 2), n0 + wc * (TBN / 2), lane);
 }
@@ -361,7 +438,7 @@ static bool launch_gemm_glds(const GemmArgs& a, hipStream_t s) {
 // SL (a sliced-K role at an M that fills the chip by its tiles alone, launch_gemm_g3_sliced): ONE block per tile walks all k-tiles and keeps a
 // second accumulator set — at every slice boundary tot = tot + acc (the first: tot = acc), acc = 0, an empty slice adds its zeros — i.e. the
 // sums k_sk_reduce would have formed from the SK blocks' partials, in the same order: bit-identical to that pair, no partials in memory.
-template <int BM, int BN, bool SK = false, bool WT = false, bool SL = false>
+template <int BM, int BN, bool SK = false, bool WT = false, bool SL = false, bool LS = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
   constexpr int BK = 64, NST = 3, WAVES = 8;
   constexpr unsigned OPA = BM * BK * 2, OPW = BN * BK * 2, STB = OPA + OPW;   // 48 KiB per stage
@@ -490,6 +567,50 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = tot[i][j];
+  }
+  if (LS) {
+    // Log-softmax epilogue.  Transposed C/D layout: a lane holds, for row (lane & 15) of m tile i, columns j * 16 + (lane >> 4) * 4 + r — the four
+    // lanes l, l + 16, l + 32, l + 48 share a row's 64 columns (xor 16, 32: all four end with the same values).  Row tile i is then carried
+    // by lane group (lane >> 4) == i; the odd-wc wave parks its 64 half-records in LDS, its even neighbour merges and stores.
+    LsRec mine{LS_NEG_INF, 0.f, LS_NEG_INF, 0x7fffffff};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wr * 64 + i * 16 + (lane & 15);
+      const int tgt = a.ls_target[min(m, a.M - 1)];
+      float z[16], mx = LS_NEG_INF, zt = LS_NEG_INF;
+      int ix = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int n = n0 + wc * 64 + j * 16 + (lane >> 4) * 4 + r;
+          const float v = n < a.N ? rbf(acc[i][j][r]) : LS_NEG_INF;
+          z[j * 4 + r] = v;
+          if (v > mx) { mx = v; ix = n; }
+          if (n == tgt) zt = v;
+        }
+#pragma unroll
+      for (int off = 16; off < 64; off <<= 1) {
+        const float om = __shfl_xor(mx, off, 64); const int oi = __shfl_xor(ix, off, 64);
+        ls_take_max(mx, ix, om, oi);
+        zt = fmaxf(zt, __shfl_xor(zt, off, 64));
+      }
+      float l = 0.f;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) l += z[e] == LS_NEG_INF ? 0.f : expf(z[e] - mx);
+      l += __shfl_xor(l, 16, 64);
+      l += __shfl_xor(l, 32, 64);
+      if ((lane >> 4) == i) { mine.m = mx; mine.l = l; mine.zt = zt; mine.ix = ix; }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                  // every wave is done with the last stage
+    LsRec* park = reinterpret_cast<LsRec*>(gsm) + wave * 64;                          // 1 KiB per wave
+    if (wc & 1) park[lane] = mine;                                                    // lane = (lane >> 4) * 16 + (lane & 15) = the wave tile's row
+    __syncthreads();
+    if (!(wc & 1)) {
+      const int m = m0 + wr * 64 + lane;
+      if (m < a.M && n0 + wc * 64 < a.N) ls_store(a, m, (n0 + wc * 64) >> 7, ls_merge(mine, park[64 + lane]));   // wave + 1 = the same rows, the next 64 columns; a tile wholly beyond N has no record
+    }
+    return;
   }
   if (!SK && WT && (a.flags & GEMM_SWIGLU)) {
     // W row tiles arrive as (gate tile q, up tile q) pairs: this wave's tiles j = 0, 2 are gate tiles, j = 1, 3 the up tiles of the same 16
@@ -708,6 +829,72 @@ static void launch_gemm_sk_t(const GemmArgs& a, hipStream_t s) {
 static int g_gemm_wt = 1;      // 0: ignore GemmArgs::Wt (dtk_set_option "gemm_wt")
 void set_gemm_wt(int v) { g_gemm_wt = v; }
 static bool use_wt(const GemmArgs& a) { return g_gemm_wt && a.Wt && !(reinterpret_cast<uintptr_t>(a.Wt) & 15); }
+
+// ---- launchers of the log-softmax epilogue.  Which kernel family runs is decided by the WEIGHT shape alone (never by M), so a row's records are the
+// same bits whatever prompt it is scored in: k_gemm_g3 where ceil(N / 128) column tiles fill the chip by themselves (every real vocabulary),
+// k_gemm_mfma<64, 128> below.  Inside k_gemm_g3 the tile orientation follows M as in launch_gemm_g3: both give a wave the same 64 x 64 sub-tile.
+template <int BM, int BN, bool WT>
+static void launch_gemm_g3_ls_t(const GemmArgs& a, hipStream_t s) {
+  constexpr int lds = 3 * (BM + BN) * 64 * 2;
+  static unsigned long long attr_set = 0;
+  if (dtk_lds_attr_todo(attr_set)) { DTK_LDS_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_g3<BM, BN, false, WT, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); }
+  const long mbs = (a.M + BM - 1) / BM, nbs = (a.N + BN - 1) / BN;
+  hipLaunchKernelGGL((k_gemm_g3<BM, BN, false, WT, false, true>), dim3((unsigned)(8 * ((nbs + 7) / 8) * mbs)), dim3(512), lds, s, a);
+}
+bool launch_gemm_logsoftmax(const GemmArgs& a, hipStream_t s) {
+  if (a.M < 1 || a.N < 1 || !gemm_logsoftmax_supported(a.K) || (a.lda % 8) || (a.ldw % 8) || !a.ls_target || !a.ls_rec) return false;
+  if ((reinterpret_cast<uintptr_t>(a.A) | reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.ls_rec)) & 15) return false;
+  GemmArgs b = a;
+  b.flags = 0;
+  if (a.K >= 128 && (a.N + 127) / 128 >= 128) {       // the weight shape alone decides
+    int cus = 256;
+    { static int n = 0; if (!n) { int dev = 0; hipDeviceProp_t p; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount; if (n <= 0) n = 256; } cus = n; }
+    auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
+    const long tall = blocks(256, 128), wide = blocks(128, 256);
+    const long rt = (tall + cus - 1) / cus, rw = (wide + cus - 1) / cus;
+    const bool use_wide = rw < rt || (rw == rt && wide < tall && a.M < 256);
+    if (use_wt(b)) { if (use_wide) launch_gemm_g3_ls_t<128, 256, true>(b, s); else launch_gemm_g3_ls_t<256, 128, true>(b, s); }
+    else if (use_wide) launch_gemm_g3_ls_t<128, 256, false>(b, s); else launch_gemm_g3_ls_t<256, 128, false>(b, s);
+    return true;
+  }
+  const int mbs = (a.M + 63) / 64, nbs = (a.N + 127) / 128;
+  hipLaunchKernelGGL((k_gemm_mfma<64, 128, 1, 64, true>), dim3((unsigned)(8 * ((nbs + 7) / 8) * mbs)), dim3(256), 0, s, b);
+  return true;
+}
+
+// One wave per row folds the row's NT records.  The order is fixed by NT alone: the maximum (exact in any order; lowest column on ties)
+// first, then lane q adds l_t * exp(m_t - max) for tiles q, q + 64, ... in ascending order and the 64 lane sums meet in one butterfly.
+__global__ __launch_bounds__(64) void k_score_merge(const float* rec, int NT, float* logprob, float* lse, int32_t* argmax, float* zmax) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const f32x4* r4 = reinterpret_cast<const f32x4*>(rec) + (size_t)row * NT;
+  float mx = LS_NEG_INF, zt = LS_NEG_INF;
+  int ix = 0x7fffffff;
+  for (int t = lane; t < NT; t += 64) {
+    const f32x4 v = r4[t];
+    ls_take_max(mx, ix, v[0], __float_as_int(v[3]));
+    zt = fmaxf(zt, v[2]);
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const float om = __shfl_xor(mx, off, 64); const int oi = __shfl_xor(ix, off, 64);
+    ls_take_max(mx, ix, om, oi);
+    zt = fmaxf(zt, __shfl_xor(zt, off, 64));
+  }
+  float l = 0.f;
+  for (int t = lane; t < NT; t += 64) {
+    const f32x4 v = r4[t];
+    l += v[0] == LS_NEG_INF ? 0.f : v[1] * expf(v[0] - mx);
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) l += __shfl_xor(l, off, 64);
+  if (lane == 0) {
+    const float e = mx + logf(l);
+    logprob[row] = zt - e; lse[row] = e; argmax[row] = ix; zmax[row] = mx;
+  }
+}
+void launch_score_merge(const float* rec, int M, int N, float* logprob, float* lse, int32_t* argmax, float* zmax, hipStream_t s) {
+  hipLaunchKernelGGL(k_score_merge, dim3((unsigned)M), dim3(64), 0, s, rec, (N + 127) >> 7, logprob, lse, argmax, zmax);
+}
 
 // Partials added in slice order (fp32), the GEMM epilogue, the row stored as bf16; then — norm_w — the HF RMSNorm of the stored row.  1024
 // threads = 4096 columns of one row per pass, every slice's 16 bytes requested before the first add (S x 16 KiB in flight per block): without

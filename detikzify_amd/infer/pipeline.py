@@ -5,7 +5,7 @@ detikzify/infer/generate.py:356-467: sampling defaults temperature 0.8 / top-p 0
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Generator, Literal, Optional, Tuple, Union
+from typing import Any, Dict, Generator, List, Literal, Optional, Tuple, Union
 
 from PIL import Image
 
@@ -55,6 +55,23 @@ class DetikzifyPipeline:
     def sample(self, image=None, text: Optional[str] = None, preprocess: bool = True, **gen_kwargs) -> TikzDocument:
         """One sampled TikZ program for the image."""
         return self._generator(image, text, preprocess, **gen_kwargs).sample()
+
+    def score(self, image=None, code: str = "", text: Optional[str] = None, preprocess: bool = True) -> Tuple[float, List[float]]:
+        """(log-probability of `code`, its per-token log-probabilities) under the model, after the prompt sample() builds for
+        (image, text).  `code` is tokenised as the generator's output would be — no special tokens, EOS appended — and scored in one
+        teacher-forced pass (model.score)."""
+        import torch
+        self.check_inputs(image, text)
+        tokenizer = unwrap(self.processor).tokenizer
+        features = self.processor(images=self.load(image, preprocess=preprocess) if image is not None else None, text=text,
+                                  text_kwargs={"truncation": True}, return_tensors="pt")
+        prompt = features.input_ids.reshape(-1).to(torch.int64)
+        program = list(tokenizer.encode(code, add_special_tokens=False)) + [int(tokenizer.eos_token_id)]
+        ids = torch.cat([prompt, torch.tensor(program, dtype=torch.int64)])
+        conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}     # as DetikzifyGenerator.generate
+        out = self.model.score(ids, features.get("pixel_values"), first=prompt.numel(), **conditioning)
+        per_token = [float(v) for v in out.logprobs]
+        return float(out.logprobs.sum(dtype=torch.float64)), per_token
 
     def simulate(self, image=None, text: Optional[str] = None, preprocess: bool = True,
                  expansions: Optional[Numeric] = None, timeout: Optional[int] = None, trees: int = 1,

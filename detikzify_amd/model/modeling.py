@@ -157,6 +157,60 @@ def _reject_unsupported_generate_kwargs(kw: Dict[str, Any]) -> None:
                 f"sampling of one sequence (the calls DetikzifyGenerator.generate makes); only {name} in {allowed} is accepted")
 
 
+# forward() arguments of HF's LlamaForCausalLM / the reference's DetikzifyForConditionalGeneration that have no generate() twin, with
+# the values at which forward(labels=...) computes what this path computes
+_NEUTRAL_FORWARD_KWARGS: Dict[str, tuple] = {
+    "return_dict": (None, True), "position_ids": (None,), "cache_position": (None,), "image_hidden_states": (None,),
+    "pixel_attention_mask": (None,), "logits_to_keep": (None, 0), "num_logits_to_keep": (None, 0),
+}
+# the names of generate()'s table that HF's forward() has too: these pass generate()'s gate at its neutral values; every other name of
+# that table (max_new_tokens' relatives, beams, penalties, streamers ...) is a TypeError here, as it is for HF's forward()
+_FORWARD_SHARES_WITH_GENERATE = ("attention_mask", "use_cache", "past_key_values", "inputs_embeds", "output_attentions",
+                                 "output_hidden_states", "output_logits")
+
+
+def _reject_unsupported_forward_kwargs(kw: Dict[str, Any]) -> None:
+    """the neutral-value gate of generate(), for forward(): names forward() does not have raise TypeError, known ones away from their
+    neutral value NotImplementedError"""
+    for name, value in kw.items():
+        if name in _NEUTRAL_FORWARD_KWARGS:
+            allowed = _NEUTRAL_FORWARD_KWARGS[name]
+            if not any(_is_neutral(value, a) for a in allowed):
+                raise NotImplementedError(f"forward({name}={value!r}) is not supported: only {name} in {allowed} is accepted")
+        elif name in _FORWARD_SHARES_WITH_GENERATE:
+            _reject_unsupported_generate_kwargs({name: value})
+        else:
+            raise TypeError(f"forward() got an argument this decoder does not implement: {name!r}")
+
+
+def shifted_cross_entropy(logprobs: torch.Tensor, labels: torch.Tensor, first: int = 1, ignore_index: int = -100) -> torch.Tensor:
+    """The loss of HF's causal LMs (reference v1/modeling_detikzify.py:260-271: logits[..., :-1, :] against labels[..., 1:] under
+    CrossEntropyLoss()) from log-probabilities instead of logits: logprobs[k] = log p(ids[first + k] | ids[:first + k]) for the
+    positions first .. T-1 of a sequence whose `labels` has T entries; a position counts iff its label is not `ignore_index` (a label
+    that is kept equals the input id there: causal-LM labels are the ids with some positions masked).  Mean over the kept
+    positions, float32 scalar; no kept position gives NaN (0 / 0), as torch's CrossEntropyLoss does.  Positions before `first` must
+    all be ignored."""
+    labels = torch.as_tensor(labels).reshape(-1)
+    lp = torch.as_tensor(logprobs, dtype=torch.float32).reshape(-1)
+    if lp.numel() != labels.numel() - first:
+        raise ValueError(f"{lp.numel()} log-probabilities for labels[{first}:{labels.numel()}]")
+    if bool((labels[1:first] != ignore_index).any()):
+        raise ValueError("a label before `first` is not ignored: its log-probability was not computed")
+    keep = labels[first:] != ignore_index
+    # sum / count exactly as nll_loss(reduction="mean") reduces: float32 sum of the kept terms over their number
+    return -(lp[keep].sum(dtype=torch.float32) / keep.sum().to(torch.float32))
+
+
+class ScoreOutput(SimpleNamespace):
+    """model.score()'s result: logprobs float32 [T - first], argmax int64 [T - first] (the greedy token at each scored position),
+    lse float32 [T - first] (logsumexp of the position's logits), first (position of the first scored target)"""
+
+
+class CausalLMLoss(SimpleNamespace):
+    """CausalLMOutputWithPast stand-in of forward(labels=...): .loss (float32 scalar); .logits is never materialised (None).
+    .logprobs / .first: the per-position log-probabilities the loss was reduced from"""
+
+
 def _flat_ids(values) -> List[int]:
     """[id, [id, id], ...] -> flat list of ints (an eos_token_id may be a list in HF configs)"""
     out: List[int] = []
@@ -489,6 +543,102 @@ class DetikzifyForCausalLM:
                 self._check(self.lib.dtk_prefill_slot_text(self._ctx, int(slot), ids.numpy().ctypes.data_as(C.c_void_p), ids.numel(),
                                                            px_ptr, C.c_uint64(key), tp, tids.numel(), tk, flags, lp), "dtk_prefill_slot_text")
         return torch.from_numpy(logits) if return_logits else None
+
+    # ---- scoring: teacher-forced log-probabilities of a given sequence in one pass ---------------------------------------------
+    def default_first(self, ids: torch.Tensor) -> int:
+        """the token after the last image token, or 1: the first position whose log-probability means something"""
+        img = (ids == int(self.config.image_token_id)).nonzero()
+        return max(1, int(img[-1]) + 1) if img.numel() else 1
+
+    def score(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor] = None, first: Optional[int] = None,
+              adapter_input_ids: Optional[torch.Tensor] = None, reuse: Optional[bool] = None,
+              adapter_attention_mask: Optional[torch.Tensor] = None) -> ScoreOutput:
+        """log p(ids[t] | ids[:t], image) for t = first .. T-1 in one prefill-sized pass (dtk_score): the lm_head runs over all
+        scored rows with the log-softmax folded into its epilogue, no [T, V] logits exist.  Leaves the model as prefill() of the
+        same arguments does (decode may continue).  first=None: the token after the last image token, or 1."""
+        if not self._weights_ready:
+            raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
+        self._refuse_while_batch_busy("score")
+        ids = torch.as_tensor(input_ids).detach().to("cpu", torch.int64)
+        if ids.dim() == 2:
+            if ids.shape[0] != 1:
+                raise ValueError("batch size 1 only")
+            ids = ids[0]
+        ids = ids.reshape(-1).contiguous()
+        T = ids.numel()
+        first = self.default_first(ids) if first is None else int(first)
+        tids = None
+        if adapter_input_ids is not None:
+            if not self.has_adapter():
+                raise TypeError("adapter_input_ids given but no adapter is loaded (load(..., adapter=True))")
+            tids = adapter_text(adapter_input_ids, adapter_attention_mask)     # one unpadded text, as generate() takes it
+        elif adapter_attention_mask is not None:
+            raise ValueError("adapter_attention_mask without adapter_input_ids")
+        px_ptr, key = None, (DUMMY_IMAGE_KEY if tids is not None else 0)
+        if pixel_values is not None:
+            px = pixel_values.detach().to("cpu", torch.float32).contiguous()
+            if px.dim() == 4:
+                if px.shape[0] != 1:
+                    raise ValueError("batch size 1 only")
+                px = px[0]
+            self._px_keepalive = px
+            px_ptr = px.numpy().ctypes.data_as(C.c_void_p)
+            key = self.image_key(pixel_values)
+        reuse = self.reuse_prefix if reuse is None else reuse
+        flags = (_lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE) if reuse else 0
+        n = max(T - first, 1)
+        lp, am, lse = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+        outs = (int(first), lp.ctypes.data_as(C.c_void_p), am.ctypes.data_as(C.c_void_p), lse.ctypes.data_as(C.c_void_p))
+        idp = ids.numpy().ctypes.data_as(C.c_void_p)
+        if not self._single_busy.acquire(blocking=False):
+            raise _lib.DtkError("score() while a generate() decodes on this model's single sequence")
+        try:
+            with self._vit_lock:
+                if tids is None:
+                    self._check(self.lib.dtk_score(self._ctx, idp, T, px_ptr, C.c_uint64(key), C.c_uint32(flags), *outs), "dtk_score")
+                else:
+                    self._check(self.lib.dtk_score_text(self._ctx, idp, T, px_ptr, C.c_uint64(key), tids.numpy().ctypes.data_as(C.c_void_p),
+                                                        tids.numel(), C.c_uint64(text_key(tids)), C.c_uint32(flags), *outs), "dtk_score_text")
+        finally:
+            self._single_busy.release()
+        return ScoreOutput(logprobs=torch.from_numpy(lp), argmax=torch.from_numpy(am).to(torch.int64), lse=torch.from_numpy(lse), first=first)
+
+    def forward(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+                labels: Optional[torch.Tensor] = None, adapter_input_ids: Optional[torch.Tensor] = None, **hf_kwargs) -> CausalLMLoss:
+        """model(input_ids=..., pixel_values=..., labels=...).loss of the reference's causal LM (shift by one, CrossEntropyLoss():
+        mean over the positions whose label is not -100), reduced on the host from the device's log-probabilities.  Logits of
+        every position are never materialised: labels=None or output_logits=True raise."""
+        if hf_kwargs.get("output_logits"):
+            raise NotImplementedError("forward(output_logits=True): the [T, V] logits are never materialised; "
+                                      "model.prefill(ids, pixel_values, return_logits=True) returns one row")
+        tmask = hf_kwargs.pop("adapter_attention_mask", None)
+        _reject_unsupported_forward_kwargs(hf_kwargs)
+        if labels is None:
+            raise NotImplementedError("forward() without labels would return the logits of every position, which are never materialised: "
+                                      "pass labels for the loss, model.score() for log-probabilities, or "
+                                      "model.prefill(ids, pixel_values, return_logits=True) for one row of logits")
+        if input_ids is None:
+            raise ValueError("forward() needs input_ids")
+        ids = torch.as_tensor(input_ids).detach().to("cpu", torch.int64)
+        lab = torch.as_tensor(labels).detach().to("cpu", torch.int64)
+        if ids.dim() == 2:
+            if ids.shape[0] != 1:
+                raise ValueError("batch size 1 only")
+            ids = ids[0]
+        lab = lab.reshape(-1)
+        if lab.numel() != ids.numel():
+            raise ValueError(f"labels of {lab.numel()} entries for {ids.numel()} input ids")
+        kept = (lab != -100).nonzero().reshape(-1)
+        kept = kept[kept >= 1]                      # label 0 has no context: the shift drops it
+        if bool((lab[kept] != ids[kept]).any()):
+            raise NotImplementedError("labels that differ from input_ids at a position that is not -100")
+        if kept.numel() == 0:
+            return CausalLMLoss(loss=torch.tensor(float("nan"), dtype=torch.float32), logits=None, logprobs=torch.empty(0), first=ids.numel())
+        first = int(kept[0])
+        out = self.score(ids, pixel_values, first=first, adapter_input_ids=adapter_input_ids, adapter_attention_mask=tmask)
+        return CausalLMLoss(loss=shifted_cross_entropy(out.logprobs, lab, first=first), logits=None, logprobs=out.logprobs, first=first)
+
+    __call__ = forward
 
     def set_sampling(self, do_sample=False, temperature=1.0, top_p=1.0, top_k=0, seed=0,
                      bad_ids: Iterable[int] = (), begin_suppress_ids: Iterable[int] = (),

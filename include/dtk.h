@@ -103,7 +103,7 @@ typedef struct dtk_stats {
   uint64_t decode_steps;            /* decode-step launches since create              */
   uint64_t prefill_tokens;          /* tokens pushed through the batched prefill      */
   uint64_t vit_images;              /* images encoded                                 */
-  double   last_prefill_ms;         /* device time of last dtk_prefill (HIP events)   */
+  double   last_prefill_ms;         /* device time of last dtk_prefill / dtk_score (HIP events) */
   double   last_vit_ms;             /* ViT part of it                                 */
   double   probe_kernel_ms_sum;     /* in-graph event probe around the gate/up GEMV of the middle layer */
   uint64_t probe_kernel_launches;
@@ -170,6 +170,19 @@ int  dtk_vit_encode(dtk_ctx* ctx, const float* pixels, int batch,
 #define DTK_PREFILL_REUSE_IMAGE  2   /* skip the ViT when image_key equals the cached key        */
 int  dtk_prefill(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels,
                  uint64_t image_key, int flags, float* logits_last_out);
+
+/* Scoring: log p(ids[t] | ids[:t], image) for t = first .. T-1 in ONE pass — the teacher-forced half of
+ * DetikzifyForCausalLM.forward(input_ids, pixel_values, labels) (reference v1/modeling_detikzify.py:260-271,
+ * modeling_detikzify.py:361-376: logits of every position, shifted cross-entropy).  Runs the prefill of the same arguments
+ * (flags: DTK_PREFILL_*; prefix reuse stops at position first-1, whose hidden state is the first one scored) and leaves the
+ * context exactly as dtk_prefill does — KV, cached ids, last-row logits — so dtk_decode may continue from it.  Then the final
+ * norm and lm_head run over rows first-1 .. T-2 on the matrix cores with the log-softmax folded into the GEMM's epilogue: no
+ * [T][V] logits exist; a row's logits are the values dtk_prefill's last-row path gives (bf16-rounded), exp / log in fp32.
+ * 1 <= first <= T-1, T >= 2.  logprob_out [T-first]; argmax_out (the greedy token of each position, lowest id on ties) and
+ * lse_out (logsumexp of the row) [T-first] or NULL.  The first call allocates a workspace of (max_positions-1) x ceil(V/128) x
+ * 16 bytes that the context keeps. */
+int  dtk_score(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags,
+               int first, float* logprob_out, int32_t* argmax_out, float* lse_out);
 
 /* Sampling configuration for the following decode calls (resets the draw counter). */
 int  dtk_set_sampling(dtk_ctx* ctx, const dtk_sampling* s);
@@ -266,6 +279,10 @@ int  dtk_prefill_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixe
                       const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_last_out);
 int  dtk_prefill_slot_text(dtk_ctx* ctx, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
                            const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_last_out);
+/* dtk_score with the tower conditioned on text_ids (as dtk_prefill_text; pixels = NULL: the adapter's dummy input) */
+int  dtk_score_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
+                    const int64_t* text_ids, int T_text, uint64_t text_key, uint32_t flags,
+                    int first, float* logprob_out, int32_t* argmax_out, float* lse_out);
 /* diagnostic: the embedding model's last_hidden_state (T_text x hidden bf16) of text_ids */
 int  dtk_adapter_embed(dtk_ctx* ctx, const int64_t* text_ids, int T_text, void* hidden_out_bf16);
 /* the key the *_text prefills cache an image prefix under (image_key, text_key) -> key; 0 when either is 0 */
@@ -450,6 +467,11 @@ int  dtk_op_gemm(dtk_ctx* ctx, const uint16_t* A, const uint16_t* W, const uint1
  * flags: DTK_GEMM_NAIVE only; the kernel is whatever the tuning switches ("gemm_impl", "gemm_tile", ...) select for the shape */
 int  dtk_op_gemm_gated(dtk_ctx* ctx, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual,
                        const uint16_t* gate, int M, int N, int K, int flags, uint16_t* C);
+/* the scoring kernel pair alone: Xn [M][K] = final-normed hidden rows, W [N][K] = lm_head, targets [M] in [0, N).  Per row:
+ * logprob = z[target] - logsumexp(z), lse, argmax (lowest index on ties), zmax = z[argmax], z = bf16-rounded Xn . W^T.
+ * flags: DTK_GEMM_WT only.  lse_out / argmax_out / zmax_out may be NULL. */
+int  dtk_op_score(dtk_ctx* ctx, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
+                  float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out);
 /* mode 0: y = W.x ; mode 1: y = W.rmsnorm(x, norm_w) ; fp32 result of the bf16-rounded output */
 int  dtk_op_gemv(dtk_ctx* ctx, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w,
                  int N, int K, int mode, float eps, uint16_t* y);
