@@ -102,6 +102,8 @@ class DtkEngineOps(C.Structure):
     LASTERR = C.CFUNCTYPE(C.c_void_p, C.c_void_p)     # (const char*: the callee owns the text)
     # not a field: dtk_engine_set_prefill_text_op's argument (dev, slot, ids, T, pixels, image_key, text_ids, n_text, text_key, flags)
     PREFILL_TEXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _I64P, C.c_int, C.c_void_p, C.c_uint64, _I64P, C.c_int, C.c_uint64, C.c_int)
+    # not a field: dtk_engine_set_wait_lp_op's argument (dev, tokens_out[64], logprob_out[64], sample_logprob_out[64])
+    WAIT_LP = C.CFUNCTYPE(C.c_int, C.c_void_p, _I64P, C.POINTER(C.c_float), C.POINTER(C.c_float))
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -190,6 +192,13 @@ SYMBOLS = {
     "dtk_op_attention": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dtk_op_layernorm": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_sample": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P]),
+    # additive (ABI stays 7): log-probabilities of sampled tokens (dtk_set_option "logprobs")
+    "dtk_decode_wait_lp": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float)]),
+    "dtk_decode_batch_wait_lp": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "dtk_engine_read_lp": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    "dtk_engine_set_wait_lp_op": (C.c_int, [_P, DtkEngineOps.WAIT_LP]),
+    "dtk_op_sample_lp": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -160,7 +160,36 @@ struct SampleMB {
   // blocks read only these — its last block rewrites DecState while blocks of the same slot may not have started yet
   unsigned int draw_snap;
   int forced_snap, pad;
+  // log-probabilities (SampleArgs::lp_ring): every slice's online log-sum-exp state of its RAW logits, left by k_smb_max<true>
+  float lmax[DTK_SAMPLE_MB_MAX_SLICES];
+  float lsum[DTK_SAMPLE_MB_MAX_SLICES];
 };
+
+// Online log-sum-exp over raw logits, carried by the samplers next to their masked maximum (SampleArgs::lp_ring): the state is
+// (m, s) = (max so far, sum of exp(z - m)), the identity (-inf, 0).  lse_push takes one logit (one expf), lse_merge folds two states.
+// Every sampler applies them in an order fixed by the thread count and V alone, so a row's logsumexp is the same bits every time.
+__device__ __forceinline__ void lse_push(float& m, float& s, float z) {
+  if (z > m) { s = s * expf(m - z) + 1.f; m = z; }
+  else if (m != -INFINITY) s += expf(z - m);
+}
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+  const float M = fmaxf(m, om);
+  if (M == -INFINITY) { s = 0.f; return; }
+  s = s * expf(m - M) + os * expf(om - M);
+  m = M;
+}
+// the block's 16 waves: butterfly inside the wave, lane 0 of every wave to LDS; the caller's thread 0 folds s_m / s_s in wave order
+__device__ __forceinline__ void lse_wave(float& m, float& s) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, 64), os = __shfl_xor(s, off, 64);
+    lse_merge(m, s, om, os);
+  }
+}
+// (logprob, sample_logprob) of the delivered token: z_t - lse, and log(q / total) from the sampler's two integers in double
+__device__ __forceinline__ float2 lp_pair(float zt, float m, float s, bool sampling, unsigned long long q, unsigned long long total) {
+  return make_float2(zt - (m + logf(s)), sampling ? (float)log((double)q / (double)total) : 0.f);
+}
 
 // Top-p radix level: among the 256 (mass, count) bins of one level pick the LOWEST non-empty bin whose strictly-above
 // mass (above_in + mass of all higher bins) is still < pq; if even the highest non-empty bin fails, pick that one.  This

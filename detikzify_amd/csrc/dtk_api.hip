@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -146,6 +147,13 @@ struct dtk_ctx {
   int64_t* tok_ring_dev = nullptr;   // device ring
   int64_t* tok_ring_host = nullptr;  // pinned host mirror
   float* probs_dev = nullptr;        // op_sample output
+  // dtk_set_option "logprobs": (logprob, sample_logprob) of every sampled token, rings parallel to tok_ring_* / tokb_* (same index)
+  int logprobs = 0;
+  std::atomic<int> engine_holds{0};  // sequences an engine of dtk_engine_create holds in this context's slots (joined, not yet left)
+  float2* lp_ring_dev = nullptr;     // [DTK_MAX_INFLIGHT]
+  float2* lp_ring_host = nullptr;    // pinned mirror
+  float2* lpb_dev = nullptr;         // [DTK_MAX_INFLIGHT][DTK_MAX_BATCH] (contexts with slots)
+  float2* lpb_host = nullptr;
   // ViT
   float* pixels_dev = nullptr;
   bf16_t *patches, *VX, *VN, *VQKV, *VAO, *VH, *feats, *last_hidden;
@@ -563,6 +571,8 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
   }
   c->scratch_bytes = (size_t)64 << 20;
   c->scratch = P.take<unsigned char>(c->scratch_bytes);
+  c->lp_ring_dev = P.take<float2>(DTK_MAX_INFLIGHT);
+  if (c->nb > 0) c->lpb_dev = P.take<float2>((size_t)DTK_MAX_INFLIGHT * DTK_MAX_BATCH);
 }
 
 void gemm(dtk_ctx* c, const bf16_t* A, int lda, const bf16_t* W, int ldw, const bf16_t* bias,
@@ -743,12 +753,21 @@ void project_image(dtk_ctx* c) {
 #define TOKB_WORDS (TOKB_ERR + 1)
 static inline unsigned* batch_err_word(const dtk_ctx* c) { return reinterpret_cast<unsigned*>(c->tokb_dev + TOKB_ERR); }
 
+#define LPB_BYTES (sizeof(float2) * (size_t)DTK_MAX_INFLIGHT * DTK_MAX_BATCH)
+// the D2H copy of the log-probability ring that follows a step's token copy (nothing with the option off)
+static inline hipError_t copy_lp_ring(dtk_ctx* c, bool batch) {
+  if (!c->logprobs) return hipSuccess;
+  return batch ? hipMemcpyAsync(c->lpb_host, c->lpb_dev, LPB_BYTES, hipMemcpyDeviceToHost, c->stream)
+               : hipMemcpyAsync(c->lp_ring_host, c->lp_ring_dev, sizeof(float2) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream);
+}
+
 void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   hipStream_t s = c->stream;
   SampleArgs sa;
   sa.logits = c->logits; sa.V = c->V; sa.sp = c->sp; sa.st = c->st; sa.embed = c->embed;
   sa.x = c->x; sa.d = c->d; sa.tok_ring = c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
+  sa.lp_ring = c->logprobs ? c->lp_ring_dev : nullptr;
   if (c->mb_single) launch_sample_mb(sa, s); else launch_sample(sa, s);
   const float scale = 1.0f / sqrtf((float)c->hd);
   for (int l = 0; l < c->L; ++l) {
@@ -803,6 +822,7 @@ void batch_step_launches_mx(dtk_ctx* c) {
   sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = nslots; sa.mb = c->smb_b;
+  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -848,6 +868,7 @@ void batch_step_launches(dtk_ctx* c) {
   sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = 16 * c->nt_step; sa.mb = c->smb_b;
+  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -919,6 +940,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
   sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
+  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -1056,6 +1078,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   if (c->mv_step) batch_step_launches_mv(c); else batch_step_launches(c);
   HIPCHK(c, hipMemcpyAsync(c->tokb_host, c->tokb_dev, sizeof(int64_t) * TOKB_WORDS,
                            hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, copy_lp_ring(c, true));
   HIPCHK(c, hipStreamEndCapture(c->stream, &c->bgraph[gi]));
   if (c->launch_refused || dtk_lds_attr_error(c->device)) {       // an incomplete step must never be replayed
     (void)hipGraphDestroy(c->bgraph[gi]); c->bgraph[gi] = nullptr;
@@ -1076,6 +1099,7 @@ int ensure_graph(dtk_ctx* c) {
     decode_step_launches(c, false, v == 1);
     HIPCHK(c, hipMemcpyAsync(c->tok_ring_host, c->tok_ring_dev, sizeof(int64_t) * DTK_MAX_INFLIGHT,
                              hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, copy_lp_ring(c, false));
     HIPCHK(c, hipStreamEndCapture(c->stream, v ? &c->graph_short : &c->graph));
     HIPCHK(c, hipGraphInstantiate(v ? &c->graph_short_exec : &c->graph_exec, v ? c->graph_short : c->graph, nullptr, nullptr, 0));
   }
@@ -1100,6 +1124,11 @@ void compute_rope_tables(const dtk_config& cfg, std::vector<uint16_t>& cosv, std
 }
 
 }  // namespace
+
+// not part of the ABI (hidden): dtk_engine.cpp asks whether its context's steps carry log-probabilities
+extern "C" int dtk_internal_logprobs(const dtk_ctx* c) { return (c && c->logprobs) ? 1 : 0; }
+// ... and tells it how many sequences it holds in the slots (delta = +1 at a join, -1 when the sequence leaves): "logprobs" is refused meanwhile
+extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta) { if (c) c->engine_holds.fetch_add(delta); }
 
 // ============================================================================ C ABI
 // the library is built with -fvisibility=hidden: the C ABI of include/dtk.h is all it exports
@@ -1230,10 +1259,12 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   plan(c, real, true);
   CCHK(hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
   CCHK(hipHostMalloc((void**)&c->tok_ring_host, sizeof(int64_t) * DTK_MAX_INFLIGHT, hipHostMallocDefault));
+  CCHK(hipHostMalloc((void**)&c->lp_ring_host, sizeof(float2) * DTK_MAX_INFLIGHT, hipHostMallocDefault));
   for (int i = 0; i < DTK_MAX_INFLIGHT; ++i) CCHK(hipEventCreateWithFlags(&c->step_done[i], hipEventDisableTiming));
   if (c->nb > 0) {
     CCHK(hipHostMalloc((void**)&c->bs_host, sizeof(BatchState) * DTK_MAX_INFLIGHT, hipHostMallocDefault));
     CCHK(hipHostMalloc((void**)&c->tokb_host, sizeof(int64_t) * TOKB_WORDS, hipHostMallocDefault));
+    CCHK(hipHostMalloc((void**)&c->lpb_host, LPB_BYTES, hipHostMallocDefault));
     CCHK(hipHostMalloc((void**)&c->st_stage, sizeof(DecState) * (DTK_MAX_SLOTS), hipHostMallocDefault));
     CCHK(hipHostMalloc((void**)&c->sp_stage, sizeof(SamplingDev) * (DTK_MAX_SLOTS), hipHostMallocDefault));
     CCHK(hipHostMalloc((void**)&c->draw_stage, sizeof(uint32_t) * (DTK_MAX_SLOTS), hipHostMallocDefault));
@@ -1301,6 +1332,8 @@ void dtk_destroy(dtk_ctx* c) {
   for (int i = 0; i < DTK_MAX_INFLIGHT; ++i) if (c->bstep_done[i]) (void)hipEventDestroy(c->bstep_done[i]);
   if (c->bs_host) (void)hipHostFree(c->bs_host);
   if (c->tokb_host) (void)hipHostFree(c->tokb_host);
+  if (c->lpb_host) (void)hipHostFree(c->lpb_host);
+  if (c->lp_ring_host) (void)hipHostFree(c->lp_ring_host);
   if (c->st_stage) (void)hipHostFree(c->st_stage);
   if (c->sp_stage) (void)hipHostFree(c->sp_stage);
   if (c->draw_stage) (void)hipHostFree(c->draw_stage);
@@ -1878,6 +1911,7 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
       return fail(c, DTK_ERR_STATE, c->launch_refused ? "batched step: a projection's shape has no kernel in its family (nothing launched for it)"
                                                       : "batched step: raising a kernel's dynamic-LDS limit failed (hipFuncSetAttribute, see stderr)");
     HIPCHK(c, hipMemcpyAsync(c->tokb_host, c->tokb_dev, sizeof(int64_t) * TOKB_WORDS, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, copy_lp_ring(c, true));
   }
   HIPCHK(c, hipEventRecord(c->bstep_done[c->blaunched % DTK_MAX_INFLIGHT], c->stream));
   c->stats.last_batch_step_slots = (uint32_t)(c->mv_step ? c->mv_step : 16 * c->nt_step);
@@ -1890,8 +1924,7 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
 }
 
 // tokens_out[DTK_MAX_BATCH]: the token sampled for every slot that was active in the oldest un-read step (-1 otherwise)
-int dtk_decode_batch_wait(dtk_ctx* c, int64_t* tokens_out) {
-  if (!c || !tokens_out) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait: null argument");
+static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out) {
   if (c->bwaited >= c->blaunched) return fail(c, DTK_ERR_STATE, "no batch step in flight");
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t k = c->bwaited;
@@ -1907,9 +1940,14 @@ int dtk_decode_batch_wait(dtk_ctx* c, int64_t* tokens_out) {
   // how many steps were launched after step k for each slot (their cached ids are still -1)
   for (int j = 0; j < DTK_MAX_BATCH; ++j) {
     tokens_out[j] = -1;
+    if (logprob_out) logprob_out[j] = sample_logprob_out[j] = NAN;
     if (!hb->active[j]) continue;
     const int64_t tok = ((volatile int64_t*)c->tokb_host)[(size_t)ring * DTK_MAX_BATCH + j];
     tokens_out[j] = tok;
+    if (logprob_out) {
+      const volatile float* lp = (volatile float*)(c->lpb_host + (size_t)ring * DTK_MAX_BATCH + j);
+      logprob_out[j] = lp[0]; sample_logprob_out[j] = lp[1];
+    }
     SeqHost& sh = c->bseq[(size_t)j];
     size_t later = 0;
     for (uint64_t q = k + 1; q < c->blaunched; ++q) later += c->bs_host[q % DTK_MAX_INFLIGHT].active[j] ? 1 : 0;
@@ -1917,6 +1955,18 @@ int dtk_decode_batch_wait(dtk_ctx* c, int64_t* tokens_out) {
   }
   c->bwaited++;
   return DTK_OK;
+}
+
+int dtk_decode_batch_wait(dtk_ctx* c, int64_t* tokens_out) {
+  if (!c || !tokens_out) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait: null argument");
+  return decode_batch_wait_impl(c, tokens_out, nullptr, nullptr);
+}
+
+// dtk_decode_batch_wait + the (logprob, sample_logprob) of every token it returns (NaN where tokens_out is -1, and for a forced token)
+int dtk_decode_batch_wait_lp(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out) {
+  if (!c || !tokens_out || !logprob_out || !sample_logprob_out) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_lp: null argument");
+  if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  return decode_batch_wait_impl(c, tokens_out, logprob_out, sample_logprob_out);
 }
 
 // Copy the KV of the first n_tokens positions of slot src into slot dst (SURVEY §8 f1 / the proposed
@@ -2086,6 +2136,7 @@ int dtk_decode_launch(dtk_ctx* c) {
     decode_step_launches(c, c->probe != 0, c->seq0.host_next_pos < c->attn_full_max);
     if (c->probe) c->probe_pending = true;
     HIPCHK(c, hipMemcpyAsync(c->tok_ring_host, c->tok_ring_dev, sizeof(int64_t) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, copy_lp_ring(c, false));
   }
   HIPCHK(c, hipEventRecord(c->step_done[c->launched % DTK_MAX_INFLIGHT], c->stream));
   c->launched++;
@@ -2095,8 +2146,7 @@ int dtk_decode_launch(dtk_ctx* c) {
   return DTK_OK;
 }
 
-int dtk_decode_wait(dtk_ctx* c, int64_t* token_out) {
-  if (!c || !token_out) return fail(c, DTK_ERR_ARG, "dtk_decode_wait: null argument");
+static int decode_wait_impl(dtk_ctx* c, int64_t* token_out, float* lp_out) {
   if (c->waited >= c->launched) return fail(c, DTK_ERR_STATE, "no decode step in flight");
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t k = c->waited;
@@ -2105,10 +2155,26 @@ int dtk_decode_wait(dtk_ctx* c, int64_t* token_out) {
   // been launched yet; later copies of the whole ring rewrite it with the same value
   const int64_t tok = ((volatile int64_t*)c->tok_ring_host)[k % DTK_MAX_INFLIGHT];
   *token_out = tok;
+  if (lp_out) {
+    const volatile float* lp = (volatile float*)(c->lp_ring_host + k % DTK_MAX_INFLIGHT);
+    lp_out[0] = lp[0]; lp_out[1] = lp[1];
+  }
   const size_t idx = c->seq0.cached_ids.size() - (size_t)(c->launched - k);
   c->seq0.cached_ids[idx] = tok;
   c->waited++;
   return DTK_OK;
+}
+
+int dtk_decode_wait(dtk_ctx* c, int64_t* token_out) {
+  if (!c || !token_out) return fail(c, DTK_ERR_ARG, "dtk_decode_wait: null argument");
+  return decode_wait_impl(c, token_out, nullptr);
+}
+
+// dtk_decode_wait + lp_out[2] = (logprob, sample_logprob) of the token
+int dtk_decode_wait_lp(dtk_ctx* c, int64_t* token_out, float* lp_out) {
+  if (!c || !token_out || !lp_out) return fail(c, DTK_ERR_ARG, "dtk_decode_wait_lp: null argument");
+  if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_decode_wait_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  return decode_wait_impl(c, token_out, lp_out);
 }
 
 int dtk_decode(dtk_ctx* c, int64_t* token_out) {
@@ -2198,6 +2264,16 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!strcmp(name, "attn_full_max")) c->attn_full_max = value;
+  else if (!strcmp(name, "logprobs")) {     // every sampled token comes with (logprob, sample_logprob): the LP sampler instantiations + one more D2H copy per step
+    if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "logprobs must be 0 or 1");
+    if ((value != 0) != (c->logprobs != 0)) {
+      if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "logprobs: a batch step is in flight");
+      if (c->engine_holds.load() > 0) return fail(c, DTK_ERR_STATE, "logprobs: an engine holds %d sequence(s) in this context's slots", c->engine_holds.load());
+      // (their ring entries were written under the other setting; dtk_set_sampling / dtk_prefill start the single sequence afresh)
+      if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "logprobs: %d single-sequence decode step(s) are unread", (int)(c->launched - c->waited));
+      c->logprobs = value; drop_graph(c); drop_batch_graphs(c);
+    }
+  }
   else if (!strcmp(name, "gemm_tile")) {   // MFMA GEMM block tile: 0 auto, 1 = 64x64, 2 = 128x64, 3 = 128x128 (process-wide)
     if (value < 0 || value > 5) return fail(c, DTK_ERR_ARG, "gemm_tile must be 0..5");
     set_gemm_tile(value);
@@ -2824,24 +2900,39 @@ int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uin
   return DTK_OK;
 }
 
-int dtk_op_sample(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out) {
-  if (!c || !logits || !token_out || V < 1 || V > c->V) return fail(c, DTK_ERR_ARG, "dtk_op_sample: bad argument");
+static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out) {
   HIPCHK(c, hipSetDevice(c->device));
   size_t off = 0;
-  OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1);
+  OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1);
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(dl, logits, (size_t)V * 4, hipMemcpyHostToDevice, s));
   SampleArgs sa;
   sa.logits = dl; sa.V = V; sa.sp = c->sp; sa.st = c->st; sa.embed = c->embed; sa.x = c->x; sa.d = c->d;
   sa.tok_ring = dtok; sa.ring = 1; sa.probs_out = probs_out ? c->probs_dev : nullptr; sa.advance = 0;
   sa.step_override = step; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
+  sa.lp_ring = lp_out ? dlp : nullptr;
   const bool needs_topk = c->sampling.do_sample && c->sampling.top_k > 0 && c->sampling.top_k < V;
   if (sample_mb_preferred(V, c->sampling.do_sample != 0) && !needs_topk && !getenv("DTK_SAMPLER")) launch_sample_mb(sa, s); else launch_sample(sa, s);
   HIPCHK(c, hipMemcpyAsync(token_out, dtok, 8, hipMemcpyDeviceToHost, s));
+  if (lp_out) HIPCHK(c, hipMemcpyAsync(lp_out, dlp, sizeof(float2), hipMemcpyDeviceToHost, s));
   if (probs_out) HIPCHK(c, hipMemcpyAsync(probs_out, c->probs_dev, (size_t)V * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   return DTK_OK;
+}
+
+int dtk_op_sample(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out) {
+  if (!c || !logits || !token_out || V < 1 || V > c->V) return fail(c, DTK_ERR_ARG, "dtk_op_sample: bad argument");
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, nullptr);
+}
+
+// dtk_op_sample + lp_out[2] = (logprob, sample_logprob) of the token: the LP sampler instantiations over given logits.  The row may
+// be longer than the context's own vocabulary (any V the samplers take: <= 262 144) as long as probs_out is null
+int dtk_op_sample_lp(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out) {
+  if (!c || !logits || !token_out || !lp_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V))
+    return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: bad argument");
+  if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out);
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 // the only thing this loop decides differently from the Python engine it replaces — does not change a token.
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -41,6 +42,9 @@ struct Seq {
   int state = 0;            // 0 = no sequence yet, else DTK_SEQ_*
   bool decoding = false;    // takes part in further steps
   std::vector<int64_t> toks;
+  std::vector<float> lp, slp;       // (logprob, sample_logprob) of toks[i], kept only while a wait_lp op collects the steps (a shorter
+                                    // vector = NaN for the rest: dtk_engine_read_lp)
+  bool held = false;                // counted in the context's engine_holds (dtk_engine_create): from the join until the sequence leaves
   size_t read = 0, flushed = 0;     // toks[0, read) delivered; toks[read, flushed) may be delivered
   int budget = 0, emitted = 0;      // tokens the sequence may emit / has emitted
   int need = 0, launched = 0;       // steps to launch for it in total (budget + the forced step of a resumed slot) / launched so far
@@ -67,12 +71,18 @@ using ActiveSet = std::array<int32_t, DTK_MAX_BATCH>;
 
 using PrefillTextFn = int (*)(void* dev, int slot, const int64_t* ids, int T, const float* px, uint64_t image_key, const int64_t* text_ids,
                               int n_text, uint64_t text_key, int flags);
+using WaitLpFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out);
+extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
+extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
 struct dtk_engine {
   dtk_engine_ops ops{};
   PrefillTextFn prefill_text = nullptr;     // dtk_engine_set_prefill_text_op (dtk_engine_create: dtk_prefill_slot_text)
+  WaitLpFn wait_lp = nullptr;               // dtk_engine_set_wait_lp_op: collects a step instead of ops.wait
+  dtk_ctx* own_ctx = nullptr;               // dtk_engine_create: the context, whose "logprobs" option decides which wait collects
   std::mutex mu;
   std::condition_variable cv_run;
+  std::condition_variable cv_idle;          // no step in flight (dtk_engine_set_option "drain")
   std::thread th;
   bool quit = false;
   std::deque<Cmd*> cmds;
@@ -106,6 +116,7 @@ void poison(dtk_engine* e, int rc) {
   const char* t = e->ops.last_error ? e->ops.last_error(e->ops.dev) : nullptr;
   e->err = (t && *t) ? t : "device call failed";
   e->inflight.clear();
+  e->cv_idle.notify_all();
   for (Seq& q : e->seq) { q.decoding = false; q.cv.notify_all(); }
 }
 
@@ -138,15 +149,18 @@ void launch(dtk_engine* e, std::unique_lock<std::mutex>& lk, const ActiveSet& se
 void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
   const ActiveSet set = e->inflight.front();
   int64_t toks[DTK_MAX_BATCH];
+  float lp[DTK_MAX_BATCH], slp[DTK_MAX_BATCH];
+  const WaitLpFn wait_lp = (e->own_ctx && !dtk_internal_logprobs(e->own_ctx)) ? nullptr : e->wait_lp;
   lk.unlock();
   const double t0 = now_s();
-  const int rc = e->ops.wait(e->ops.dev, toks);
+  const int rc = wait_lp ? wait_lp(e->ops.dev, toks, lp, slp) : e->ops.wait(e->ops.dev, toks);
   const double t1 = now_s();
   lk.lock();
   if (e->err_rc) return;             // (poisoned while we waited: the queue of steps is gone)
   (drain ? e->st.drain_s : e->st.wait_s) += t1 - t0;
   if (t1 - t0 < 1e-4) e->st.host_bound_steps++;      // the device had finished already: this step waited for the host
   e->inflight.pop_front();
+  if (e->inflight.empty()) e->cv_idle.notify_all();
   e->st.steps++;
   e->st.last_collect_t = t1;
   if (rc) { poison(e, rc); return; }
@@ -157,6 +171,10 @@ void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
     if (q.skip) { q.skip = 0; continue; }
     const int64_t tok = toks[s];
     q.toks.push_back(tok);
+    if (wait_lp) {      // (an op given mid-sequence: the earlier tokens' pairs are NaN)
+      q.lp.resize(q.toks.size() - 1, NAN); q.slp.resize(q.toks.size() - 1, NAN);
+      q.lp.push_back(lp[s]); q.slp.push_back(slp[s]);
+    }
     q.emitted++;
     e->st.tokens_out++;
     bool end = q.emitted >= q.budget;
@@ -294,7 +312,7 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
   }
   if (!rc) {
     Seq& q = e->seq[j->slot_out];
-    q.toks.clear();
+    q.toks.clear(); q.lp.clear(); q.slp.clear();
     q.read = q.flushed = 0;
     q.emitted = q.launched = 0;
     q.skip = j->how_out == DTK_JOIN_RESUMED ? 1 : 0;
@@ -309,6 +327,7 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
     q.flush_max = j->flush_max > 0 ? j->flush_max : 64;
     q.decoding = q.budget > 0;
     q.state = q.decoding ? DTK_SEQ_RUNNING : DTK_SEQ_FINISHED;
+    if (e->own_ctx && !q.held) { q.held = true; dtk_internal_engine_holds(e->own_ctx, +1); }
     e->st.joins++;
     if (q.skip) e->st.resumed++;
     if (e->gather_left > 0) e->gather_left--;
@@ -367,6 +386,7 @@ int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t
 // ---- the library's own context as the device --------------------------------------------------------------------------------------
 int ctx_launch(void* d, const int32_t* a) { return dtk_decode_batch_launch((dtk_ctx*)d, a); }
 int ctx_wait(void* d, int64_t* t) { return dtk_decode_batch_wait((dtk_ctx*)d, t); }
+int ctx_wait_lp(void* d, int64_t* t, float* lp, float* slp) { return dtk_decode_batch_wait_lp((dtk_ctx*)d, t, lp, slp); }
 int ctx_prefill(void* d, int s, const int64_t* ids, int T, const float* px, uint64_t key, int flags) { return dtk_prefill_slot((dtk_ctx*)d, s, ids, T, px, key, flags, nullptr); }
 int ctx_sampling(void* d, int s, const dtk_sampling* sp) { return dtk_set_sampling_slot((dtk_ctx*)d, s, sp); }
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
@@ -404,7 +424,20 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
   o.max_positions = dtk_max_positions(ctx);
   o.decode_slots = dtk_max_decode_slots(ctx);
   const int rc = dtk_engine_create_ops(&o, out);
-  return rc == DTK_OK ? dtk_engine_set_prefill_text_op(*out, ctx_prefill_text) : rc;
+  if (rc != DTK_OK) return rc;
+  {
+    std::lock_guard<std::mutex> g((*out)->mu);
+    (*out)->own_ctx = ctx;
+    (*out)->wait_lp = ctx_wait_lp;
+  }
+  return dtk_engine_set_prefill_text_op(*out, ctx_prefill_text);
+}
+
+int dtk_engine_set_wait_lp_op(dtk_engine* e, WaitLpFn wait_lp) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->wait_lp = wait_lp;
+  return DTK_OK;
 }
 
 int dtk_engine_set_prefill_text_op(dtk_engine* e, PrefillTextFn prefill_slot_text) {
@@ -434,6 +467,7 @@ void dtk_engine_destroy(dtk_engine* e) {
     }
     for (Seq& q : e->seq) {
       q.decoding = false;
+      if (q.held) { q.held = false; dtk_internal_engine_holds(e->own_ctx, -1); }
       if (q.state == DTK_SEQ_RUNNING) q.state = DTK_SEQ_LEFT;
       q.flushed = q.toks.size();
       q.cv.notify_all();
@@ -458,10 +492,14 @@ int dtk_engine_set_flush_tokens(dtk_engine* e, const int64_t* ids, int n) {
 
 int dtk_engine_set_option(dtk_engine* e, const char* name, int value) {
   if (!e || !name) return DTK_ERR_ARG;
-  std::lock_guard<std::mutex> g(e->mu);
+  std::unique_lock<std::mutex> g(e->mu);
   if (!strcmp(name, "depth")) {
     if (value < 1 || value > 2) return DTK_ERR_ARG;
     e->depth = value;
+    return DTK_OK;
+  }
+  if (!strcmp(name, "drain")) {     // block until no step is in flight (the loop collects the last steps of sequences that left on its own)
+    e->cv_idle.wait(g, [&] { return e->inflight.empty() || e->err_rc != 0; });
     return DTK_OK;
   }
   return DTK_ERR_ARG;
@@ -509,7 +547,14 @@ int dtk_engine_join(dtk_engine* e, dtk_join* j) {
 }
 
 int dtk_engine_read(dtk_engine* e, int slot, int64_t* out, int cap, int32_t* n_out, int32_t* state_out, int timeout_ms) {
-  if (!e || slot < 0 || slot >= DTK_MAX_BATCH || !out || cap < 1 || !n_out || !state_out) return DTK_ERR_ARG;
+  return dtk_engine_read_lp(e, slot, out, nullptr, nullptr, cap, n_out, state_out, timeout_ms);
+}
+
+// (logprob_out == sample_logprob_out == nullptr: dtk_engine_read — the pairs are dropped)
+int dtk_engine_read_lp(dtk_engine* e, int slot, int64_t* out, float* logprob_out, float* sample_logprob_out, int cap, int32_t* n_out,
+                       int32_t* state_out, int timeout_ms) {
+  if (!e || slot < 0 || slot >= DTK_MAX_BATCH || !out || cap < 1 || !n_out || !state_out || !logprob_out != !sample_logprob_out) return DTK_ERR_ARG;
+  if (logprob_out && e->own_ctx && !dtk_internal_logprobs(e->own_ctx)) return DTK_ERR_ARG;     // the context's "logprobs" option is off
   std::unique_lock<std::mutex> lk(e->mu);
   Seq& q = e->seq[slot];
   *n_out = 0;
@@ -521,6 +566,13 @@ int dtk_engine_read(dtk_engine* e, int slot, int64_t* out, int cap, int32_t* n_o
   size_t n = q.flushed - q.read;
   if (n > (size_t)cap) n = (size_t)cap;
   if (n) memcpy(out, q.toks.data() + q.read, n * sizeof(int64_t));
+  if (n && logprob_out) {
+    for (size_t i = 0; i < n; ++i) {
+      const size_t k = q.read + i;
+      logprob_out[i] = k < q.lp.size() ? q.lp[k] : NAN;
+      sample_logprob_out[i] = k < q.slp.size() ? q.slp[k] : NAN;
+    }
+  }
   q.read += n;
   *n_out = (int32_t)n;
   if (n) e->st.reader_wakeups++;
@@ -534,6 +586,7 @@ int dtk_engine_leave(dtk_engine* e, int slot) {
   std::lock_guard<std::mutex> g(e->mu);
   Seq& q = e->seq[slot];
   q.decoding = false;
+  if (q.held) { q.held = false; dtk_internal_engine_holds(e->own_ctx, -1); }
   if (q.state == DTK_SEQ_RUNNING) q.state = DTK_SEQ_LEFT;
   q.flushed = q.toks.size();
   q.cv.notify_all();

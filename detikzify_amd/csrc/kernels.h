@@ -76,6 +76,8 @@ struct SampleArgs {
   int logits_stride;     // elements between slots' logits (batched mode)
   int nslots;            // batched mode: grid = 16, 32 or 64 slots
   SampleMB* mb;          // scratch of the multi-block sampler (slot 0's in batched mode), or null
+  float2* lp_ring = nullptr;   // dtk_set_option "logprobs": (logprob, sample_logprob) of the token, a ring indexed exactly as tok_ring; null = the
+                               // samplers without the log-probability code (the LP = false instantiations: what ran before the option existed)
 };
 void launch_sample_b(const SampleArgs& a, hipStream_t s);
 void launch_sample(const SampleArgs& a, hipStream_t s);

@@ -1040,6 +1040,10 @@ __device__ __forceinline__ bool is_banned(const SamplingDev* sp, int i, bool fir
   return false;
 }
 
+// LP (SampleArgs::lp_ring, dtk_set_option "logprobs"): the token's (logprob, sample_logprob) next to it.  Pass 1 carries an online
+// log-sum-exp of the RAW logits (no mask, no temperature) beside the masked maximum — no further walk over the row; the pair is
+// computed and stored by thread 0.  LP = false is the kernel as it was before the option existed.
+template <bool LP>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (a.bs) {  // batched decode: one block per slot, same code on that slot's buffers
     const int slot = blockIdx.x;
@@ -1049,6 +1053,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     a.st += slot;
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;        // the ring index was applied above
     a.step_override = -1;
   }
@@ -1065,6 +1070,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   __shared__ int s_token;
   __shared__ float s_max;
   __shared__ unsigned long long s_total;
+  __shared__ float s_lm[16], s_ls[16];     // LP: the waves' log-sum-exp states
+  __shared__ unsigned long long s_tokq;    // LP: the chosen token's integer mass, published by the thread that chose it
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V;
@@ -1083,6 +1090,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   // (the greedy path is one memory round trip + the block reduction)
   float best = -INFINITY;
   int besti = 0x7fffffff;
+  float lm = -INFINITY, ls = 0.f;
   const bool vec = ((V & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.logits) & 15) == 0);
   if (vec) {
     const int V4 = V >> 2;
@@ -1101,6 +1109,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = i4 * 4 + e;
+          if constexpr (LP) lse_push(lm, ls, v[u][e]);
           float z = v[u][e] * invT;
           if (is_banned(sp, i, first)) z = -INFINITY;
           if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1109,6 +1118,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     }
   } else {
     for (int i = tid; i < V; i += SAMPLE_THREADS) {
+      if constexpr (LP) lse_push(lm, ls, a.logits[i]);
       float z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1120,6 +1130,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     const int oi = __shfl_xor(besti, off, 64);
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
   }
+  if constexpr (LP) { lse_wave(lm, ls); if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; } }
   if (lane == 0) { s_f[wave] = best; s_i[wave] = besti; }
   __syncthreads();
   if (tid == 0) {
@@ -1127,9 +1138,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     for (int w = 1; w < 16; ++w)
       if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
     s_max = b; s_token = bi;
+    if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
+      for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
+    }
   }
   __syncthreads();
   const float zmax = s_max;
+  unsigned long long lp_q = 0, lp_total = 1;     // LP, thread 0: the chosen token's integer mass and the kept set's
 
   if (sampling) {
     // fixed-point mass q_i = floor(exp(z_i - zmax) * 2^31)  (fits 32 bits; exact integer sums)
@@ -1248,7 +1263,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       for (int i = i0; i < i1; ++i) {
         float z; const unsigned long long q = mass(i, z);
         if (fkey(z) >= thr) {
-          if (target < run + q) { s_token = i; break; }
+          if (target < run + q) { s_token = i; if constexpr (LP) s_tokq = q; break; }
           run += q;
         }
       }
@@ -1260,6 +1275,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       }
     }
     __syncthreads();
+    if constexpr (LP) if (tid == 0) { lp_q = s_tokq; lp_total = kept; }
   } else if (a.probs_out) {
     for (int i = tid; i < V; i += SAMPLE_THREADS) a.probs_out[i] = (i == s_token) ? 1.f : 0.f;
   }
@@ -1269,6 +1285,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   const int tok = forced > 0 ? forced - 1 : s_token;
   if (tid == 0) {
     a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
+    if constexpr (LP)      // a forced token was not sampled: NaN, NaN
+      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
+                                                                   : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
     if (a.advance) {
       a.st->token = tok;
       a.st->pos = a.st->next_pos;
@@ -1293,7 +1312,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
 // aggregated per thread (neighbouring logits mostly share the high key byte), which removes the
 // same-address LDS-atomic serialisation that dominated k_sample (190 us -> measured in profiles/).
 // Same integer semantics as k_sample / oracle/sampling.py (bit-exact kept set and draws).
+// LP as in k_sample: the raw logits are in registers before the temperature is applied, so the thread's log-sum-exp state is their
+// maximum and one expf per logit.
 #define SF_PER 32
+template <bool LP>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   if (a.bs) {
     const int slot = blockIdx.x;
@@ -1303,6 +1325,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     a.st += slot;
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;
     a.step_override = -1;
   }
@@ -1320,6 +1343,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   __shared__ unsigned long long s_total;
   __shared__ unsigned long long s_bw[8];
   __shared__ int s_bi[8];
+  __shared__ float s_lm[16], s_ls[16];     // LP: the waves' log-sum-exp states
+  __shared__ unsigned long long s_tokq;    // LP: the chosen token's integer mass, published by the thread that chose it
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int V = a.V;
   if (tid < (int)(sizeof(SamplingDev) / 4)) reinterpret_cast<uint32_t*>(&s_sp)[tid] = reinterpret_cast<const uint32_t*>(a.sp)[tid];
@@ -1334,8 +1359,29 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 
   // ---- the one pass over the logits
   float z[SF_PER];
+  float lm = -INFINITY, ls = 0.f;
   const bool vec = ((reinterpret_cast<uintptr_t>(a.logits) & 15) == 0) && (i0 + SF_PER <= V);
-  if (vec) {
+  if constexpr (LP) {     // the same loads; every 16-byte load is folded into the log-sum-exp state before the temperature is applied
+    if (vec) {
+      const f32x4* l4 = reinterpret_cast<const f32x4*>(a.logits + i0);
+#pragma unroll
+      for (int k = 0; k < SF_PER / 4; ++k) {
+        const f32x4 v = l4[k];
+        const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (m4 > lm) { ls *= expf(lm - m4); lm = m4; }
+        ls += (expf(v[0] - lm) + expf(v[1] - lm)) + (expf(v[2] - lm) + expf(v[3] - lm));
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < SF_PER; ++k) {
+        const float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
+        lse_push(lm, ls, v);
+        z[k] = v * invT;
+      }
+    }
+  } else if (vec) {
     const f32x4* l4 = reinterpret_cast<const f32x4*>(a.logits + i0);
 #pragma unroll
     for (int k = 0; k < SF_PER / 4; ++k) {
@@ -1370,6 +1416,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     const int oi = __shfl_xor(besti, off, 64);
     if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
   }
+  if constexpr (LP) { lse_wave(lm, ls); if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; } }
   if (lane == 0) { s_f[wave] = best; s_i[wave] = besti; }
   __syncthreads();
   if (tid == 0) {
@@ -1377,9 +1424,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     for (int w = 1; w < 16; ++w)
       if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
     s_max = b; s_token = bi;
+    if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
+      for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
+    }
   }
   __syncthreads();
   const float zmax = s_max;
+  unsigned long long lp_q = 0, lp_total = 1;     // LP, thread 0: the chosen token's integer mass and the kept set's
 
   if (sampling) {
     // integer mass floor(exp(z - zmax) * 2^31) <= 2^31 of logit k.  Recomputed from the key wherever it is needed (the key is an
@@ -1498,7 +1549,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       for (int k = 0; k < SF_PER; ++k) {
         if (!done && i0 + k < V && key(k) >= thr) {
           const unsigned long long qk = q_(k);
-          if (target < run + qk) { s_token = i0 + k; done = true; }
+          if (target < run + qk) { s_token = i0 + k; done = true; if constexpr (LP) s_tokq = qk; }
           run += qk;
         }
       }
@@ -1509,6 +1560,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
         if (i0 + k < V) a.probs_out[i0 + k] = (key(k) >= thr) ? (float)((double)q_(k) / (double)kept) : 0.f;
     }
     __syncthreads();
+    if constexpr (LP) if (tid == 0) { lp_q = s_tokq; lp_total = kept; }
   } else if (a.probs_out) {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) if (i0 + k < V) a.probs_out[i0 + k] = (i0 + k == s_token) ? 1.f : 0.f;
@@ -1519,6 +1571,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   const int tok = forced > 0 ? forced - 1 : s_token;
   if (tid == 0) {
     a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
+    if constexpr (LP)      // a forced token was not sampled: NaN, NaN
+      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
+                                                                   : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
     if (a.advance) {
       a.st->token = tok;
       a.st->pos = a.st->next_pos;
@@ -1542,10 +1597,15 @@ static bool sample_fast_ok(const SampleArgs& a) {
   return !force_generic && a.V <= SF_PER * SAMPLE_THREADS;
 }
 void launch_sample(const SampleArgs& a, hipStream_t s) {
-  if (sample_fast_ok(a)) hipLaunchKernelGGL(k_sample_fast, dim3(1), dim3(SAMPLE_THREADS), 0, s, a);
-  else hipLaunchKernelGGL(k_sample, dim3(1), dim3(SAMPLE_THREADS), 0, s, a);
+  launch_sample_b(a, s);       // a.nslots == 1 without a.bs
 }
 void launch_sample_b(const SampleArgs& a, hipStream_t s) {
-  if (sample_fast_ok(a)) { hipLaunchKernelGGL(k_sample_fast, dim3(a.nslots), dim3(SAMPLE_THREADS), 0, s, a); return; }
-  hipLaunchKernelGGL(k_sample, dim3(a.nslots), dim3(SAMPLE_THREADS), 0, s, a);
+  const dim3 g(a.bs ? a.nslots : 1), b(SAMPLE_THREADS);
+  if (sample_fast_ok(a)) {
+    if (a.lp_ring) hipLaunchKernelGGL(k_sample_fast<true>, g, b, 0, s, a);
+    else hipLaunchKernelGGL(k_sample_fast<false>, g, b, 0, s, a);
+    return;
+  }
+  if (a.lp_ring) hipLaunchKernelGGL(k_sample<true>, g, b, 0, s, a);
+  else hipLaunchKernelGGL(k_sample<false>, g, b, 0, s, a);
 }

@@ -42,6 +42,7 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
     a.st += slot;
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if (a.lp_ring) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;
     a.step_override = -1;
     a.mb += slot;
@@ -49,17 +50,27 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
   return true;
 }
 
-// this thread's 8 consecutive logits: scaled, suppressed ids -> -inf, keys; out-of-range -> -inf
-__device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* sp, bool first, float invT, int base, MbElems& e) {
+// this thread's 8 consecutive logits: scaled, suppressed ids -> -inf, keys; out-of-range -> -inf.  raw (k_smb_max<true> only): the
+// same loads before the temperature and the suppression lists, out-of-range -> -inf
+__device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* sp, bool first, float invT, int base, MbElems& e,
+                                        float* raw = nullptr) {
   const int V = a.V;
   if (base + MB_PER <= V && ((reinterpret_cast<uintptr_t>(a.logits + base) & 15) == 0)) {
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.logits + base);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.logits + base + 4);
 #pragma unroll
     for (int i = 0; i < 4; ++i) { e.z[i] = v0[i] * invT; e.z[4 + i] = v1[i] * invT; }
+    if (raw) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { raw[i] = v0[i]; raw[4 + i] = v1[i]; }
+    }
   } else {
 #pragma unroll
     for (int i = 0; i < MB_PER; ++i) e.z[i] = (base + i < V) ? a.logits[base + i] * invT : -INFINITY;
+    if (raw) {
+#pragma unroll
+      for (int i = 0; i < MB_PER; ++i) raw[i] = (base + i < V) ? a.logits[base + i] : -INFINITY;
+    }
   }
   // suppression lists: which of the (<= 24) ids fall into this thread's 8 elements
   auto ban = [&](int id) {
@@ -102,12 +113,14 @@ __device__ __forceinline__ void mb_common(const SampleArgs& a, int nblk, MbCommo
   __syncthreads();
 }
 
-// ---- P0
+// ---- P0.  LP (SampleArgs::lp_ring): the slice's log-sum-exp state of its raw logits goes out with its maximum
+template <bool LP>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
   if (!mb_bind(a, blockIdx.y)) return;
   __shared__ SamplingDev s_sp;
   __shared__ float s_f[16];
   __shared__ int s_i[16];
+  __shared__ float s_lm[16], s_ls[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
   if (tid < (int)(sizeof(SamplingDev) / 4)) reinterpret_cast<uint32_t*>(&s_sp)[tid] = reinterpret_cast<const uint32_t*>(a.sp)[tid];
   __syncthreads();
@@ -115,7 +128,21 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
   const float invT = s_sp.do_sample ? 1.f / s_sp.temperature : 1.f;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load(a, &s_sp, draw == 0, invT, base, e);
+  float lm = -INFINITY, ls = 0.f;
+  if constexpr (LP) {
+    float raw[MB_PER];
+    mb_load(a, &s_sp, draw == 0, invT, base, e, raw);
+#pragma unroll
+    for (int i = 0; i < MB_PER; ++i) lm = fmaxf(lm, raw[i]);
+    if (lm != -INFINITY) {
+#pragma unroll
+      for (int i = 0; i < MB_PER; ++i) ls += expf(raw[i] - lm);      // out of range: exp(-inf) = 0
+    }
+    lse_wave(lm, ls);
+    if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; }
+  } else {
+    mb_load(a, &s_sp, draw == 0, invT, base, e);
+  }
   float best = -INFINITY; int besti = 0x7fffffff;
 #pragma unroll
   for (int i = 0; i < MB_PER; ++i)
@@ -133,6 +160,10 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
     for (int w = 1; w < 16; ++w)
       if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
     a.mb->bmax[blk] = b; a.mb->barg[blk] = bi;
+    if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
+      for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
+      a.mb->lmax[blk] = lm; a.mb->lsum[blk] = ls;
+    }
     if (blk == 0) { a.mb->draw_snap = draw; a.mb->forced_snap = a.advance ? a.st->force_plus1 : 0; }
   }
   // the histograms of this step start from zero (P1 is a later kernel)
@@ -267,12 +298,15 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
   if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; a.mb->bkept[blk] = t; }
 }
 
-// ---- P6: draw (or arg-max), token ring, DecState, embedding gather
+// ---- P6: draw (or arg-max), token ring, DecState, embedding gather.  LP: thread 0 of the block that writes the token folds the
+// slices' log-sum-exp states in slice order and stores the token's (logprob, sample_logprob)
+template <bool LP>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk) {
   if (!mb_bind(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long scan[MB_THREADS];
   __shared__ int s_token;
+  __shared__ unsigned int s_tokq;          // LP: the chosen token's integer mass, published by the thread that chose it
   const int tid = threadIdx.x, blk = blockIdx.x;
   mb_common(a, nblk, &cm);
   // the snapshot of k_smb_max, NOT DecState: the block that owns the token advances DecState (draw, force_plus1) at its end,
@@ -328,7 +362,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
 #pragma unroll
           for (int i = 0; i < MB_PER; ++i) {
             if (base + i < a.V && e.key[i] >= thr) {
-              if (target < run + e.q[i] && s_token < 0) { s_token = base + i; }
+              if (target < run + e.q[i] && s_token < 0) { s_token = base + i; if constexpr (LP) s_tokq = e.q[i]; }
               run += e.q[i];
             }
           }
@@ -344,6 +378,15 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
   const int tok = forced > 0 ? forced - 1 : s_token;
   if (tid == 0) {
     a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
+    if constexpr (LP) {
+      float2 lp = make_float2(__builtin_nanf(""), __builtin_nanf(""));      // a forced token was not sampled
+      if (forced <= 0) {
+        float lm = a.mb->lmax[0], ls = a.mb->lsum[0];
+        for (int k = 1; k < nblk; ++k) lse_merge(lm, ls, a.mb->lmax[k], a.mb->lsum[k]);
+        lp = lp_pair(a.logits[tok], lm, ls, sampling, sampling ? s_tokq : 0u, kept);
+      }
+      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = lp;
+    }
     if (a.advance) {
       a.st->token = tok;
       a.st->pos = a.st->next_pos;
@@ -362,11 +405,13 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
 void launch_sample_mb(const SampleArgs& a, hipStream_t s) {
   const int nblk = (a.V + MB_SLICE - 1) / MB_SLICE;   // <= DTK_SAMPLE_MB_MAX_SLICES
   const dim3 g(nblk, a.bs ? a.nslots : 1), b(MB_THREADS);
-  hipLaunchKernelGGL(k_smb_max, g, b, 0, s, a);
+  if (a.lp_ring) hipLaunchKernelGGL(k_smb_max<true>, g, b, 0, s, a);
+  else hipLaunchKernelGGL(k_smb_max<false>, g, b, 0, s, a);
   hipLaunchKernelGGL((k_smb_hist<3>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL((k_smb_hist<2>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL((k_smb_hist<1>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL((k_smb_hist<0>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL(k_smb_kept, g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL(k_smb_draw, g, b, 0, s, a, nblk);
+  if (a.lp_ring) hipLaunchKernelGGL(k_smb_draw<true>, g, b, 0, s, a, nblk);
+  else hipLaunchKernelGGL(k_smb_draw<false>, g, b, 0, s, a, nblk);
 }

@@ -26,8 +26,11 @@ _NUDGE = object()      # wakes a thread that waits on its slot's queue without h
 
 
 class _Sequence:
-    def __init__(self, engine: "BatchEngine", slot: int):
+    def __init__(self, engine: "BatchEngine", slot: int, logprobs: bool = False):
         self.engine, self.slot = engine, slot
+        # sequence(logprobs=True): the (logprob, sample_logprob) of every token handed to this sequence so far, in token order
+        self.logprobs: Optional[List[float]] = [] if logprobs else None
+        self.sample_logprobs: Optional[List[float]] = [] if logprobs else None
 
     def next_token(self) -> int:
         """pull: the calling thread gets the slot's next token (one thread hand-off per token)"""
@@ -104,6 +107,8 @@ class BatchEngine:
         self.tokq: List["queue.SimpleQueue"] = [queue.SimpleQueue() for _ in range(n)]   # per-slot token hand-off
         self.sinks: Dict[int, Callable[[int], bool]] = {}   # push sequences: slot -> emit(token) -> stop
         self.finished: Dict[int, Optional[BaseException]] = {}   # push sequences that are done (what their emit raised)
+        self.lp = False                                      # steps are collected with their log-probabilities (first sequence(logprobs=True))
+        self.lp_sinks: Dict[int, _Sequence] = {}             # slot -> the sequence that collects its pairs
         self.driver: Optional[int] = None               # the push sequence whose thread currently drives the steps
         self.pending = 0                                # threads that want `cv` (joins, leaves): the driver lets them in
         self._plock = threading.Lock()
@@ -164,11 +169,14 @@ class BatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, text_ids=None,
-                 **_native_only) -> Iterator[_Sequence]:
+                 logprobs: bool = False, **_native_only) -> Iterator[_Sequence]:
         """`owner`: whoever starts sequence after sequence (an MCTS tree: generate(sequence_owner=t)) — a join that cannot
         resume takes the slot its owner used last, so it does not overwrite a rollout ANOTHER owner may come back to.
         `text_ids`: one unpadded text that conditions the tower (the adapter; pixel_values None = its dummy image): the slot's prefix is
         that of the pair (image, text), and every prefill of the sequence is the text prefill.
+        `logprobs`: the sequence collects its tokens' (logprob, sample_logprob) in `.logprobs` / `.sample_logprobs`.  The first such
+        sequence switches the device over (model.enable_logprobs()), which is done before the first join, not while other sequences
+        hold slots.
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_image_key, text_key
         tids = adapter_text(text_ids) if text_ids is not None else None
@@ -234,6 +242,13 @@ class BatchEngine:
                 self._collect()     # a prefill drops un-collected steps on the C side: collect first
                 if self.error is not None:
                     raise self.error
+                if logprobs and not self.lp:
+                    if (self.active or self.inflight is not None) and not self.model.logprobs_enabled:
+                        from .._lib import DtkError
+                        raise DtkError("sequence(logprobs=True): log-probabilities are switched on before the first join, not "
+                                            "while sequences hold slots")
+                    self.model.enable_logprobs()
+                    self.lp = True
                 t0 = time.perf_counter()
                 self.model.set_sampling(slot=slot, **sampling)
                 if resume:
@@ -261,9 +276,14 @@ class BatchEngine:
                 joined = True
                 if self.driver is not None:
                     self.tokq[self.driver].put(_NUDGE)      # it may be sleeping through the warm start
-            yield _Sequence(self, slot)
+            seq = _Sequence(self, slot, logprobs)
+            if logprobs:
+                with self._locked():
+                    self.lp_sinks[slot] = seq
+            yield seq
         finally:
             with self._locked():
+                self.lp_sinks.pop(slot, None)
                 self.skip_first.discard(slot)
                 if joined:
                     self.active.discard(slot)
@@ -366,7 +386,7 @@ class BatchEngine:
             return pushed
         try:
             t0 = time.perf_counter()
-            toks = self.model.decode_batch_wait()
+            toks, lps, slps = self.model.decode_batch_wait_lp() if self.lp else (self.model.decode_batch_wait(), None, None)
             dt = time.perf_counter() - t0
             self.t_wait += dt
             self.t_last_collect = t0 + dt
@@ -377,6 +397,9 @@ class BatchEngine:
                     if s in self.skip_first:        # the forced last prompt token of a resumed slot: already part of the prompt
                         self.skip_first.discard(s)
                         continue
+                    if s in self.lp_sinks:
+                        self.lp_sinks[s].logprobs.append(lps[s])
+                        self.lp_sinks[s].sample_logprobs.append(slps[s])
                     if s in self.sinks:
                         pushed.append((s, toks[s]))
                     else:

@@ -29,16 +29,26 @@ from .. import _lib
 
 
 class _NativeSequence:
-    def __init__(self, engine: "NativeBatchEngine", slot: int):
+    def __init__(self, engine: "NativeBatchEngine", slot: int, logprobs: bool = False):
         self.engine, self.slot = engine, slot
         self._buf = (C.c_int64 * 256)()
+        # sequence(logprobs=True): the (logprob, sample_logprob) of every token read so far, in token order (dtk_engine_read_lp)
+        self.logprobs: Optional[List[float]] = [] if logprobs else None
+        self.sample_logprobs: Optional[List[float]] = [] if logprobs else None
+        self._lp, self._slp = ((C.c_float * 256)(), (C.c_float * 256)()) if logprobs else (None, None)
         self._n, self._state = C.c_int32(0), C.c_int32(0)
         self._pending: List[int] = []
         self.ended = False
 
     def _read(self, cap: int, timeout_ms: int) -> List[int]:
         e = self.engine
-        rc = e.lib.dtk_engine_read(e._h, self.slot, self._buf, cap, C.byref(self._n), C.byref(self._state), timeout_ms)
+        if self.logprobs is not None:
+            rc = e.lib.dtk_engine_read_lp(e._h, self.slot, self._buf, self._lp, self._slp, cap, C.byref(self._n), C.byref(self._state), timeout_ms)
+            if rc == 0 and self._n.value:
+                self.logprobs.extend(self._lp[:self._n.value])
+                self.sample_logprobs.extend(self._slp[:self._n.value])
+        else:
+            rc = e.lib.dtk_engine_read(e._h, self.slot, self._buf, cap, C.byref(self._n), C.byref(self._state), timeout_ms)
         if rc != 0:
             raise _lib.DtkError(f"the batch engine's device failed ({rc}): {e.lib.dtk_engine_last_error(e._h).decode(errors='replace')}")
         n = self._n.value
@@ -109,6 +119,11 @@ class _ScriptedOps:
             for j in range(_lib.DTK_MAX_BATCH):
                 out[j] = toks[j]
 
+        def wait_lp(dev, out, lp_out, slp_out):
+            toks, lp, slp = model.decode_batch_wait_lp()
+            for j in range(_lib.DTK_MAX_BATCH):
+                out[j], lp_out[j], slp_out[j] = toks[j], lp[j], slp[j]
+
         def prefill(dev, slot, ids, T, pixels, key, flags):
             px = engine._pixels_by_key.get(int(key)) if pixels else None
             model.prefill(ids_of(ids, T), px, slot=slot, reuse=bool(flags & _lib.DTK_PREFILL_REUSE_PREFIX))
@@ -144,6 +159,7 @@ class _ScriptedOps:
         self.ops = O(None, *self.keep, int(model.config.max_positions), int(engine.decode_slots))
         # the text prefill only for a device that has an adapter (an engine without it refuses text joins in submit)
         self.prefill_text = O.PREFILL_TEXT(guard(prefill_text)) if _has_adapter(model) else None
+        self.wait_lp = O.WAIT_LP(guard(wait_lp))       # handed to the engine by the first sequence(logprobs=True)
 
 
 def _has_adapter(model) -> bool:
@@ -182,6 +198,7 @@ class NativeBatchEngine:
         self._cv = threading.Condition()        # protects the bookkeeping above and `free`; joins are queued natively under it
         self.free: List[int] = list(range(self.capacity))
         self._pixels_by_key: Dict[int, Any] = {}
+        self._lp = False                        # the device's steps deliver log-probabilities (first sequence(logprobs=True))
         self._h = C.c_void_p()
         ctx = getattr(model, "_ctx", None)
         if ctx:
@@ -256,6 +273,17 @@ class NativeBatchEngine:
         with self._cv:
             return len(self.free) < self.capacity
 
+    def _enable_logprobs(self):
+        """(under _cv, no sequence holding a slot) the device's steps deliver log-probabilities from here on"""
+        if not self.model.logprobs_enabled:
+            # the native loop may still be collecting the last steps behind sequences that have just left: wait until none is in flight
+            if self.lib.dtk_engine_set_option(self._h, b"drain", 0) != 0:
+                raise _lib.DtkError("dtk_engine_set_option(drain) failed")
+            self.model.enable_logprobs()
+        if self._scripted is not None and self.lib.dtk_engine_set_wait_lp_op(self._h, self._scripted.wait_lp) != 0:
+            raise _lib.DtkError("dtk_engine_set_wait_lp_op failed")
+        self._lp = True
+
     # ---- joins ---------------------------------------------------------------------------------------------------------------
     def _prefix_key(self, ids, image_key: int, text_key: int):
         """(image key, text key, prefix length) if the prompt starts with its image-token run, else None"""
@@ -322,10 +350,13 @@ class NativeBatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None) -> Iterator[_NativeSequence]:
+                 stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None, logprobs: bool = False) -> Iterator[_NativeSequence]:
         """`owner`: see BatchEngine.sequence.  `max_new_tokens` / `stop_ids`: the sequence's own end (the native loop stops it there);
         `per_token`: the reader is woken for every token (arbitrary stopping criteria / foreign streamers) instead of per line.
-        `text_ids`: one unpadded text that conditions the tower (the adapter); pixel_values may then be None (the dummy image)."""
+        `text_ids`: one unpadded text that conditions the tower (the adapter); pixel_values may then be None (the dummy image).
+        `logprobs`: the sequence collects its tokens' (logprob, sample_logprob) in `.logprobs` / `.sample_logprobs`.  The first such
+        sequence switches the device over, which needs every slot free: ask for it before other sequences join (or call
+        model.enable_logprobs() before the engine is built)."""
         if not self._h:
             raise _lib.DtkError("the batch engine is closed")
         from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_key
@@ -376,6 +407,11 @@ class NativeBatchEngine:
         ticket = C.c_uint64(0)
         held_through = False
         with self._cv:
+            if logprobs and not self._lp:
+                if len(self.free) < self.capacity and not self.model.logprobs_enabled:
+                    raise _lib.DtkError("sequence(logprobs=True): log-probabilities are switched on before the first join, not while "
+                                        "sequences hold slots")
+                self._enable_logprobs()
             while not self.free:
                 self._cv.wait()
             order = sorted(self.free)
@@ -450,7 +486,7 @@ class NativeBatchEngine:
                     self.resumes += 1
                 elif j.how_out == _lib.DTK_JOIN_IN_PLACE:
                     self.inplace_reuses += 1
-            yield _NativeSequence(self, slot)
+            yield _NativeSequence(self, slot, logprobs)
         finally:
             if joined and self._h:
                 self.lib.dtk_engine_leave(self._h, slot)

@@ -188,8 +188,20 @@ class DetikzifyGenerator:
 
     __call__ = simulate         # a generator object is callable like its simulate()
 
-    def sample(self) -> TikzDocument:
-        return self.decode(self.generate(input_ids=self.montecarlo.root_node.token_ids))
+    def sample(self, return_logprobs: bool = False) -> TikzDocument:
+        """return_logprobs: the document carries `.token_logprobs` / `.token_sample_logprobs`, one float per generated token (EOS
+        included): the model's log-probability of the token and the log of the probability the sampler drew it with"""
+        if not return_logprobs:
+            return self.decode(self.generate(input_ids=self.montecarlo.root_node.token_ids))
+        out = self.generate(input_ids=self.montecarlo.root_node.token_ids, return_logprobs=True)
+        if not hasattr(out, "sequences"):       # self.generate returned the prompt itself, without a model call (it ends in EOS / fills the budget)
+            document = self.decode(out)
+            document.token_logprobs, document.token_sample_logprobs = [], []
+            return document
+        document = self.decode(out.sequences.squeeze(0))
+        document.token_logprobs = [float(v) for v in out.logprobs[0]]
+        document.token_sample_logprobs = [float(v) for v in out.sample_logprobs[0]]
+        return document
 
     # ---- a·G: one call of the model ------------------------------------------------------------------------------------
     def _prompt_features(self):
@@ -217,7 +229,7 @@ class DetikzifyGenerator:
                 begin_suppress_tokens=[self.model.config.text_config.eos_token_id],     # never an empty program
                 streamer=sinks,
                 **conditioning, **options)
-        return out.squeeze()
+        return out if hasattr(out, "sequences") else out.squeeze()      # (return_logprobs=True: the GenerateOutput as it is)
 
     # ---- a·R: a generation as a stream of tree positions -------------------------------------------------------------------
     def rollout(self, state: NodeState) -> Iterator[Tuple[torch.Tensor, int]]:

@@ -52,9 +52,12 @@ class DetikzifyPipeline:
             image=self.load(image, preprocess=preprocess) if image is not None else None,
             text=text, **{**self.gen_kwargs, **kw})
 
-    def sample(self, image=None, text: Optional[str] = None, preprocess: bool = True, **gen_kwargs) -> TikzDocument:
-        """One sampled TikZ program for the image."""
-        return self._generator(image, text, preprocess, **gen_kwargs).sample()
+    def sample(self, image=None, text: Optional[str] = None, preprocess: bool = True, return_logprobs: bool = False,
+               **gen_kwargs) -> TikzDocument:
+        """One sampled TikZ program for the image.  return_logprobs=True attaches `.token_logprobs` and `.token_sample_logprobs` to
+        the document: per generated token (EOS included) the model's log-probability of it — comparable with score() — and the log
+        of the probability the sampler (temperature, top-k, top-p) chose it with."""
+        return self._generator(image, text, preprocess, **gen_kwargs).sample(return_logprobs=return_logprobs)
 
     def score(self, image=None, code: str = "", text: Optional[str] = None, preprocess: bool = True) -> Tuple[float, List[float]]:
         """(log-probability of `code`, its per-token log-probabilities) under the model, after the prompt sample() builds for

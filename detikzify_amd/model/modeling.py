@@ -18,7 +18,7 @@ import threading
 import ctypes as C
 import hashlib
 from types import SimpleNamespace
-from typing import Any, Dict, Iterable, List, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -136,6 +136,16 @@ _NEUTRAL_GENERATE_KWARGS: Dict[str, tuple] = {
     "generation_config": (None,), "stop_strings": (None,), "max_time": (None,), "cache_implementation": (None,),
     "past_key_values": (None,), "inputs_embeds": (None,), "tokenizer": "any",
 }
+
+
+class GenerateOutput:
+    """generate(return_logprobs=True): `.sequences` is what generate() returns without the flag; `.logprobs[0, i]` is the model's
+    log-probability of new token i (z[t] - logsumexp(z) over the raw logits: what model.score reports for that position),
+    `.sample_logprobs[0, i]` the log of the probability with which the sampler drew it (after the suppression lists, temperature,
+    top-k and top-p; 0 for greedy).  Both [1, new_tokens] float32 on the CPU."""
+
+    def __init__(self, sequences: torch.Tensor, logprobs: torch.Tensor, sample_logprobs: torch.Tensor):
+        self.sequences, self.logprobs, self.sample_logprobs = sequences, logprobs, sample_logprobs
 
 
 def _is_neutral(value: Any, neutral: Any) -> bool:
@@ -680,6 +690,25 @@ class DetikzifyForCausalLM:
         self._check(self.lib.dtk_decode_batch_wait(self._ctx, out), "dtk_decode_batch_wait")
         return [int(v) for v in out]
 
+    def decode_batch_wait_lp(self) -> Tuple[List[int], List[float], List[float]]:
+        """decode_batch_wait + every slot's (logprob, sample_logprob); needs enable_logprobs()"""
+        out = (C.c_int64 * _lib.DTK_MAX_BATCH)()
+        lp, slp = (C.c_float * _lib.DTK_MAX_BATCH)(), (C.c_float * _lib.DTK_MAX_BATCH)()
+        self._check(self.lib.dtk_decode_batch_wait_lp(self._ctx, out, lp, slp), "dtk_decode_batch_wait_lp")
+        return [int(v) for v in out], list(lp), list(slp)
+
+    # ---- log-probabilities of sampled tokens (dtk_set_option "logprobs") ------------------------------------
+    @property
+    def logprobs_enabled(self) -> bool:
+        return bool(getattr(self, "_logprobs", False))
+
+    def enable_logprobs(self) -> None:
+        """every decode step from here on also delivers its token's (logprob, sample_logprob); stays on.  Refused while a batch step
+        is in flight, single-sequence steps are unread or an engine holds a sequence: a batch engine switches it on before its first join"""
+        if not self.logprobs_enabled:
+            self.set_option("logprobs", 1)
+            self._logprobs = True
+
     def kv_fork(self, src_slot: int, dst_slot: int, n_tokens: int):
         self._check(self.lib.dtk_kv_fork(self._ctx, int(src_slot), int(dst_slot), int(n_tokens)), "dtk_kv_fork")
 
@@ -750,6 +779,12 @@ class DetikzifyForCausalLM:
         self._check(self.lib.dtk_decode_wait(self._ctx, C.byref(tok)), "dtk_decode_wait")
         return int(tok.value)
 
+    def decode_wait_lp(self) -> Tuple[int, float, float]:
+        """decode_wait + the token's (logprob, sample_logprob); needs enable_logprobs()"""
+        tok, lp = C.c_int64(), (C.c_float * 2)()
+        self._check(self.lib.dtk_decode_wait_lp(self._ctx, C.byref(tok), lp), "dtk_decode_wait_lp")
+        return int(tok.value), float(lp[0]), float(lp[1])
+
     def get_logits(self) -> torch.Tensor:
         out = np.empty(self.config.vocab, dtype=np.float32)
         self._check(self.lib.dtk_get_logits(self._ctx, out.ctypes.data_as(C.c_void_p)), "dtk_get_logits")
@@ -782,11 +817,16 @@ class DetikzifyForCausalLM:
                  temperature: Optional[float] = None, top_p: Optional[float] = None,
                  top_k: Optional[int] = None, max_length: Optional[int] = None,
                  max_new_tokens: Optional[int] = None, eos_token_id=None, seed: Optional[int] = None,
-                 inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, **hf_kwargs) -> torch.Tensor:
+                 inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, return_logprobs: bool = False,
+                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
         streamer.end().  Returns (1, T') int64 on the host.
+
+        return_logprobs=True (not an HF argument; HF's output_scores / compute_transition_scores stay refused) returns a
+        GenerateOutput instead: the same tensor as `.sequences` plus the per-token `.logprobs` / `.sample_logprobs` the sampler
+        kernel formed on its way (enable_logprobs(): switched on for this call if needed, and left on).
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -848,6 +888,7 @@ class DetikzifyForCausalLM:
         light = [c for c in criteria if type(c) is ExplicitAbort]        # polled flag: ignores its arguments
         heavy = [c for c in criteria if type(c) is not ExplicitAbort]
         new_tokens: List[int] = []
+        pairs: Tuple[List[float], List[float]] = ([], [])      # return_logprobs: one pair per delivered token (trimmed to new_tokens)
 
         def emit(tok: int) -> bool:
             nonlocal cur
@@ -909,8 +950,11 @@ class DetikzifyForCausalLM:
             with engine.sequence(ids[0], pixel_values, dict(
                     do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, bad_ids=bad,
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or ()),
-                    owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids) as seq:
+                    owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
+                    **({"logprobs": True} if return_logprobs else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
+                if return_logprobs:
+                    pairs = (seq.logprobs, seq.sample_logprobs)
         elif n_new_max > 0:
             # the context has ONE un-slotted sequence: a second generate() on it from another thread would interleave its
             # prefill / decode steps with ours and both would return garbage — refuse loudly (the reference never does
@@ -921,6 +965,8 @@ class DetikzifyForCausalLM:
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or ())
+                if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
+                    self.enable_logprobs()
                 if text_ids is not None:
                     self.prefill(ids[0], pixel_values, adapter_input_ids=text_ids)
                 else:
@@ -931,7 +977,12 @@ class DetikzifyForCausalLM:
                 while launched < min(ahead, n_new_max):
                     self.decode_launch(); launched += 1
                 while received < launched:
-                    tok = self.decode_wait(); received += 1
+                    if return_logprobs:
+                        tok, lp, slp = self.decode_wait_lp()
+                        pairs[0].append(lp); pairs[1].append(slp)
+                    else:
+                        tok = self.decode_wait()
+                    received += 1
                     stop = emit(tok)
                     if stop:
                         break
@@ -943,4 +994,8 @@ class DetikzifyForCausalLM:
             streamer.end()
         if new_tokens:
             buf[0, T:T + len(new_tokens)] = torch.tensor(new_tokens, dtype=torch.int64)
+        if return_logprobs:       # (an engine may have delivered pairs of tokens past the sequence's end: the first len(new_tokens) are its own)
+            n = len(new_tokens)
+            return GenerateOutput(buf[:, :cur].clone(), torch.tensor(pairs[0][:n], dtype=torch.float32)[None],
+                                  torch.tensor(pairs[1][:n], dtype=torch.float32)[None])
         return buf[:, :cur].clone()

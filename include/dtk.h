@@ -367,7 +367,8 @@ void dtk_engine_destroy(dtk_engine* e);            /* stops the loop (steps in f
 const char* dtk_engine_last_error(const dtk_engine* e);   /* text of the device failure that stopped the loop ("" = none)          */
 /* tokens that end a reader's burst (the newline table of DetikzifyGenerator.rollout, reference infer/generate.py:262-274) */
 int  dtk_engine_set_flush_tokens(dtk_engine* e, const int64_t* ids, int n);
-/* option "depth" = steps kept in flight (1 | 2, default 2) */
+/* option "depth" = steps kept in flight (1 | 2, default 2); "drain" (value ignored) = return once no step is in flight — the loop
+ * collects the last steps behind sequences that have left on its own; meant for an engine none of whose sequences is decoding */
 int  dtk_engine_set_option(dtk_engine* e, const char* name, int value);
 /* n sequences are about to join: no step before all of them have, or timeout_ms have passed (rollouts started together move together) */
 int  dtk_engine_expect(dtk_engine* e, int n, int timeout_ms);
@@ -445,7 +446,8 @@ int  dtk_set_gemv_variant(dtk_ctx* ctx, int epi, int variant);
  * SCOPE: the switches that select a kernel VARIANT ("gemv_*", "resid_*", "gemm_*", "mx_*", "attn_impl") are process-wide — they live in the
  * launchers, not in the context: a later context of the same process inherits what an earlier one set, and an A/B inside one process must set
  * the switch on both sides.  The per-context ones: "act_fp8", "prefix_mfma", "tail_threads", "pfx_splits", "share_prefix_reads", "mv_slots",
- * "attn_threads" / "attn_splits" / "attn_combine", "vit_feature_layer", "gemm_naive", "resid_kparts", "prefill_sk", "qkv_rope_fused", "swiglu_fused". */
+ * "attn_threads" / "attn_splits" / "attn_combine", "vit_feature_layer", "gemm_naive", "resid_kparts", "prefill_sk", "qkv_rope_fused", "swiglu_fused",
+ * "logprobs" (0 | 1, see "Log-probabilities of sampled tokens" below). */
 int  dtk_set_option(dtk_ctx* ctx, const char* name, int value);
 
 /* Op-level entry points used by the parity tests (tests/): run ONE kernel of the
@@ -497,6 +499,35 @@ int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const 
 /* run the sampler on host logits with the context's sampling config; step = draw index */
 int  dtk_op_sample(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out,
                    float* filtered_probs_out);
+
+/* Log-probabilities of sampled tokens (additive, ABI 7).  dtk_set_option(ctx, "logprobs", 1) (default 0; per context; a change of value is
+ * refused with DTK_ERR_STATE while a batch step is in flight, while single-sequence steps are unread (dtk_set_sampling / dtk_prefill
+ * start the sequence afresh) and while an engine of dtk_engine_create holds a sequence that has not left; it drops the captured decode graphs) makes every decode step deliver two fp32 values
+ * with its token t, from the passes over the logits the sampler runs anyway:
+ *   logprob        = z[t] - logsumexp(z) over the whole vocabulary, z = the fp32 row lm_head wrote (what dtk_prefill's logits_out
+ *                    reads back): no temperature, no suppression list — the quantity dtk_score reports for the same position;
+ *   sample_logprob = log(q[t] / total): the probability with which the sampler chose t, from its own integer masses
+ *                    q = floor(exp(z' - z'max) * 2^31) over the kept set after suppression, temperature, top-k and top-p
+ *                    (computed in double from the two integers); exactly 0 for a greedy step.
+ * Both are NaN for a forced token (the first step of a dtk_resume_slot'ed slot) and for slots that took no part in the step.  With the
+ * option off the steps run the same kernels and copies as before the option existed, and every *_lp call fails with DTK_ERR_ARG;
+ * with it on the plain calls keep working (they drop the pairs).
+ *   dtk_decode_wait_lp        dtk_decode_wait + lp_out[2] = (logprob, sample_logprob)
+ *   dtk_decode_batch_wait_lp  dtk_decode_batch_wait + the two values per slot
+ *   dtk_engine_read_lp        dtk_engine_read + the i-th pair of the i-th token returned.  The engine of dtk_engine_create collects the
+ *                             pairs while its context's option is on (switch it before the first join) and fails with DTK_ERR_ARG
+ *                             while it is off; an engine of dtk_engine_create_ops collects them through the op given to
+ *                             dtk_engine_set_wait_lp_op (same contract as dtk_decode_batch_wait_lp; it then replaces ops.wait) and
+ *                             delivers NaN pairs without one.
+ *   dtk_op_sample_lp          dtk_op_sample + lp_out[2]; V may exceed the context's vocabulary (<= 262 144) when filtered_probs_out is NULL */
+int  dtk_decode_wait_lp(dtk_ctx* ctx, int64_t* token_out, float* lp_out /* [2] */);
+int  dtk_decode_batch_wait_lp(dtk_ctx* ctx, int64_t* tokens_out /* [DTK_MAX_BATCH] */, float* logprob_out /* [DTK_MAX_BATCH] */,
+                              float* sample_logprob_out /* [DTK_MAX_BATCH] */);
+int  dtk_engine_read_lp(dtk_engine* e, int slot, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out, int cap,
+                        int32_t* n_out, int32_t* state_out, int timeout_ms);
+int  dtk_engine_set_wait_lp_op(dtk_engine* e, int (*wait_lp)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out));
+int  dtk_op_sample_lp(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
+                      float* lp_out /* [2] */);
 
 #ifdef __cplusplus
 }
