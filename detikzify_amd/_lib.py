@@ -185,6 +185,10 @@ SYMBOLS = {
     "dtk_score": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P]),
     "dtk_score_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P]),
     "dtk_op_score": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    # additive (ABI stays 7): N candidates of one prompt scored in one packed pass
+    "dtk_score_packed": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_int, _P, _P, _P]),
+    "dtk_score_packed_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, _P, _P, C.c_int, _P, _P, _P]),
+    "dtk_op_attention_seg": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -132,10 +132,13 @@ struct dtk_ctx {
   int qkv_rope_fused = 1;            // a sliced q/k/v role reduces inside the RoPE + KV-append kernel (dtk_set_option "qkv_rope_fused"; bit-identical)
   int prefill_sk = 1;                // sliced-K prefill GEMMs for the roles with <= 128 tiles of 256 x 128 (dtk_set_option "prefill_sk": 0 = the one-chain kernels, 2 / 4 / 8 = a cap on the slices)
   int32_t* ids_dev = nullptr;
-  // dtk_score: records of the log-softmax lm_head ([max_positions - 1][ceil(V / 128)] x 16 B) + the per-row results; allocated by the first
+  // dtk_score / dtk_score_packed: records of the log-softmax lm_head ([max_positions][ceil(V / 128)] x 16 B: a packed pass behind a one-token prompt scores max_positions rows) + the per-row results; allocated by the first
   // scoring call and kept (hipMalloc of its own, not the arena: a context that never scores pays nothing)
   float* score_rec = nullptr;
   float* score_out = nullptr;         // [4][max_positions]: logprob, lse, argmax (int32), z[argmax]
+  // dtk_score_packed: the row tables of one packed pass, [6][max_positions] int32 — {position, cache row} and {segment begin, cache row}
+  // per row (int2 each), the rows' input ids, the scored rows' targets; allocated by the first packed call and kept
+  int32_t* packed_rows = nullptr;
   // decode step
   bf16_t *x, *q, *act;
   float *logits, *pm, *pl, *po;
@@ -626,7 +629,8 @@ void gemm_role(dtk_ctx* c, const bf16_t* A, int lda, const bf16_t* W, const bf16
 
 // q/k/v of n <= SK_CHUNK_ROWS prefill rows as a sliced-K GEMM whose reduction is fused with RoPE + the KV append (no [n][qkvn] buffer);
 // false = the role is not sliced here (the caller runs Linear + k_rope_scatter).  Same values as that pair, bit for bit.
-bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, bf16_t* vc, hipStream_t s) {
+// rope_rows: the packed scoring pass's {position, cache row} per row instead of start + t for both.
+bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, bf16_t* vc, hipStream_t s, const int2* rope_rows = nullptr) {
   const int d = c->d, qkvn = d + 2 * c->KVH * c->hd;
   const int S = c->prefill_sk ? std::min(sk_role_slices(qkvn, d), c->prefill_sk == 1 ? 8 : c->prefill_sk) : 1;
   if (S <= 1 || c->gemm_naive || !c->qkv_rope_fused || n > SK_CHUNK_ROWS || n > c->sk_sl_min_rows || (size_t)S * SK_CHUNK_ROWS * (size_t)qkvn > c->skpart_floats) return false;
@@ -636,7 +640,8 @@ bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, b
   g.part = c->skpart; g.part_stride = (long)SK_CHUNK_ROWS * qkvn;
   if (!gemm_sk_supported(g)) return false;
   if (!launch_gemm_sk_partials(g, s)) { c->launch_refused = true; return true; }
-  launch_sk_rope_scatter(g.part, g.part_stride, S, c->Qh, kc, vc, c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, c->hd);
+  if (rope_rows) launch_sk_rope_scatter_rows(g.part, g.part_stride, S, c->Qh, kc, vc, c->rope_cos, c->rope_sin, n, rope_rows, c->H, c->KVH, c->Tmax, s, c->hd);
+  else launch_sk_rope_scatter(g.part, g.part_stride, S, c->Qh, kc, vc, c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, c->hd);
   return true;
 }
 
@@ -1344,6 +1349,7 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
   if (c->score_rec) (void)hipFree(c->score_rec);
   if (c->score_out) (void)hipFree(c->score_out);
+  if (c->packed_rows) (void)hipFree(c->packed_rows);
   if (c->stream_vit) (void)hipStreamDestroy(c->stream_vit);
   if (c->ev_va) (void)hipEventDestroy(c->ev_va);
   if (c->ev_vb) (void)hipEventDestroy(c->ev_vb);
@@ -1484,7 +1490,10 @@ static int vit_encode_impl(dtk_ctx* c, const float* pixels, int batch, void* fea
 // The decoder layers of a prefill: n rows at positions start .. start + n - 1 of a T-token context, X (+ Xn = layer 0's input norm) in,
 // X = the last layer's output out, K / V appended at kvbase ([L][2][KVH][Tmax][hd]).  Everything it reads — weights, dimensions, RoPE
 // tables, activation and KV scratch — is the context's own: the checkpoint's decoder, or the adapter's embedding model (Adapter::emb).
-static void decoder_layers(dtk_ctx* c, int n, int start, int T, bf16_t* kvbase, hipStream_t s) {
+// pk: the rows are a packed scoring pass instead (dtk_score_packed) — positions, cache rows and the attention's visibility come from its
+// tables, T = the cache rows in use; the same kernels by the same rule on n otherwise, so a row's arithmetic is a prefill's.
+struct PackedRows { const int2* rope; const int2* seg; int shared_len; };
+static void decoder_layers(dtk_ctx* c, int n, int start, int T, bf16_t* kvbase, hipStream_t s, const PackedRows* pk = nullptr) {
   const int hd = c->hd, d = c->d, ff = c->ff;
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * hd;
   auto kc = [&](int l) { return kvbase + (size_t)l * kv_layer; };
@@ -1493,9 +1502,10 @@ static void decoder_layers(dtk_ctx* c, int n, int start, int T, bf16_t* kvbase, 
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
     const int qkvn = d + 2 * c->KVH * hd;
-    if (!qkv_rope_fused(c, w, n, start, kc(l), vc(l), s)) {
+    if (!qkv_rope_fused(c, w, n, start, kc(l), vc(l), s, pk ? pk->rope : nullptr)) {
       gemm_role(c, c->Xn, d, w.wqkv, w.p_wqkv, d, nullptr, 0, c->QKV, qkvn, n, qkvn, d, 0, nullptr, nullptr, 0);
-      launch_rope_scatter(c->QKV, c->Qh, kc(l), vc(l), c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, hd);
+      if (pk) launch_rope_scatter_rows(c->QKV, c->Qh, kc(l), vc(l), c->rope_cos, c->rope_sin, n, pk->rope, c->H, c->KVH, c->Tmax, s, hd);
+      else launch_rope_scatter(c->QKV, c->Qh, kc(l), vc(l), c->rope_cos, c->rope_sin, n, start, c->H, c->KVH, c->Tmax, s, hd);
     }
     AttnArgs a;
     a.Q = c->Qh; a.q_sh = (long)n * hd; a.q_st = hd;
@@ -1503,7 +1513,8 @@ static void decoder_layers(dtk_ctx* c, int n, int start, int T, bf16_t* kvbase, 
     a.V = vc(l); a.v_sh = (long)c->Tmax * hd; a.v_st = hd;
     a.O = c->AO; a.o_sh = hd; a.o_st = d;
     a.H = c->H; a.Tq = n; a.Tk = T; a.hd = hd; a.causal = 1; a.q_offset = start; a.scale = scale; a.impl = c->attn_impl; a.kv_group = c->H / c->KVH;
-    launch_attention(a, s);
+    if (!pk) launch_attention(a, s);
+    else if (!launch_attention_seg(a, pk->shared_len, pk->seg, s)) c->launch_refused = true;
     gemm_role(c, c->AO, d, w.wo, w.p_wo, d, c->X, d, c->X, d, n, d, d, GEMM_RESIDUAL, w.ln2, c->Xn, d);     // + post_attention_layernorm -> Xn
     bool fused = false;      // gate/up + SiLU*mul in one launch where the role is one chain and the shape takes k_gemm_g3 (bit-identical to the pair below)
     if (c->swiglu_fused && w.p_wgui && !c->gemm_naive) {
@@ -1604,7 +1615,7 @@ struct ScoreReq { int first; float* logprob; int32_t* argmax; float* lse; };
 
 static int score_buffers(dtk_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->score_rec) HIPCHK(c, hipMalloc(&c->score_rec, score_rec_floats(c->Tmax - 1, c->V) * sizeof(float)));
+  if (!c->score_rec) HIPCHK(c, hipMalloc(&c->score_rec, score_rec_floats(c->Tmax, c->V) * sizeof(float)));
   if (!c->score_out) HIPCHK(c, hipMalloc(&c->score_out, (size_t)4 * c->Tmax * sizeof(float)));
   return DTK_OK;
 }
@@ -1754,6 +1765,183 @@ int dtk_score(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64
   if (rc != DTK_OK) return rc;
   const ScoreReq rq{first, logprob_out, argmax_out, lse_out};
   return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, image_key, (int)flags, nullptr, nullptr, 0, &rq);
+}
+
+// ---- dtk_score_packed: N candidate continuations of one prompt in ONE pass of the decoder layers -------------------
+// Rows: the prompt's positions start .. P-2 (ordinary causal rows, K / V at cache row = position), then one segment per candidate with
+// the input tokens prefix[P-1], cand_i[0 .. len_i-2] at positions P-1 + j and cache rows P-1 + b_i + j (b_i = the lengths before it).
+struct PackedReq {
+  const int64_t* prefix; int P;
+  const int64_t* cand_ids; const int32_t* cand_len; int N;
+  float* logprob; int32_t* argmax; float* lse;
+};
+
+// every refusal of dtk_score_packed / dtk_score_packed_text, before anything is launched or the context changes; total = sum of len_i
+static int packed_check(dtk_ctx* c, const PackedReq& r, int* total_out) {
+  if (!r.prefix || !r.cand_ids || !r.cand_len || !r.logprob) return fail(c, DTK_ERR_ARG, "dtk_score_packed: null argument");
+  if (r.P < 1) return fail(c, DTK_ERR_ARG, "dtk_score_packed: a prompt of %d tokens (P >= 1)", r.P);
+  if (r.N < 1) return fail(c, DTK_ERR_ARG, "dtk_score_packed: %d candidates (N >= 1)", r.N);
+  long total = 0;
+  for (int i = 0; i < r.N; ++i) {
+    if (r.cand_len[i] < 1) return fail(c, DTK_ERR_ARG, "dtk_score_packed: candidate %d has %d tokens (len >= 1)", i, r.cand_len[i]);
+    total += r.cand_len[i];
+  }
+  if ((long)r.P - 1 + total > (long)c->Tmax)
+    return fail(c, DTK_ERR_RANGE, "dtk_score_packed: %d prompt + %ld candidate rows exceed max_positions %d", r.P - 1, total, c->Tmax);
+  for (int t = 0; t < r.P; ++t)
+    if (r.prefix[t] < 0 || r.prefix[t] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_score_packed: token id %lld out of range", (long long)r.prefix[t]);
+  for (long k = 0; k < total; ++k) {
+    if (r.cand_ids[k] < 0 || r.cand_ids[k] >= c->V)
+      return fail(c, DTK_ERR_ARG, "dtk_score_packed: candidate id %lld at %ld outside [0, %d)", (long long)r.cand_ids[k], k, c->V);
+  }
+  if (c->attn_impl == 1)
+    return fail(c, DTK_ERR_STATE, "dtk_score_packed: attn_impl = 1 (the VALU attention kernel) has no segmented form; the packed pass needs the MFMA kernel (attn_impl 0 or 2)");
+  if (!gemm_logsoftmax_supported(c->d)) return fail(c, DTK_ERR_ARG, "dtk_score_packed: the log-softmax lm_head kernel needs hidden %% 8 == 0 (d = %d)", c->d);
+  const int rc = score_buffers(c);
+  if (rc != DTK_OK) return rc;
+  if (!c->packed_rows) HIPCHK(c, hipMalloc(&c->packed_rows, (size_t)6 * c->Tmax * sizeof(int32_t)));
+  *total_out = (int)total;
+  return DTK_OK;
+}
+
+static int score_packed_impl(dtk_ctx* c, const PackedReq& r, int total, const float* pixels, uint64_t image_key, int flags,
+                             const int64_t* text_ids = nullptr, int T_text = 0) {
+  SeqHost& sh = c->seq0;
+  const int P = r.P, shared = P - 1;
+  // ---- the image placeholder run of the prompt, as prefill_impl locates and checks it
+  int img_start = -1, img_count = 0;
+  for (int t = 0; t < P; ++t)
+    if (r.prefix[t] == c->cfg.image_token_id) { if (img_start < 0) img_start = t; img_count++; }
+  const bool has_img = img_count > 0;
+  const bool image_given = pixels != nullptr || ((flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key);
+  const bool use_img = has_img && image_given;
+  if (use_img) {
+    if (img_count != c->nImg)
+      return fail(c, DTK_ERR_ARG, "The number of image patch tokens should be the same as the number of image patches.");
+    for (int t = 0; t < c->nImg; ++t)
+      if (r.prefix[img_start + t] != c->cfg.image_token_id)
+        return fail(c, DTK_ERR_ARG, "The image patch tokens should be consecutive.");
+  }
+  // a placeholder inside a candidate: without an image it is a token like any other, as in dtk_score; with one, dtk_score(prefix +
+  // cand_i) would count it among the image's (one more than the image has, or a run that leaves the prompt): the image run must lie
+  // in the prompt
+  if (image_given)
+    for (int k = 0; k < total; ++k)
+      if (r.cand_ids[k] == c->cfg.image_token_id)
+        return fail(c, DTK_ERR_ARG, "The number of image patch tokens should be the same as the number of image patches.");
+  // ---- longest common prefix with the cached sequence, capped at P-1: position P-1 is computed once per candidate
+  int start = 0;
+  const bool same_image = !has_img || (sh.cached_with_image == use_img && (!use_img || (image_key != 0 && sh.image_key == image_key)));
+  if ((flags & DTK_PREFILL_REUSE_PREFIX) && same_image && !sh.cached_ids.empty()) {
+    const int lim = (int)std::min<size_t>(sh.cached_ids.size(), (size_t)shared);
+    while (start < lim && sh.cached_ids[start] == r.prefix[start]) ++start;
+  }
+  const bool need_img = use_img && start < img_start + c->nImg;
+  const bool reuse_img = (flags & DTK_PREFILL_REUSE_IMAGE) && c->have_image && c->cached_image_key == image_key;
+  if (need_img && !reuse_img && !pixels) return fail(c, DTK_ERR_ARG, "pixels required (no cached image for this key)");
+  // ---- nothing is refused from here on
+  std::lock_guard<std::mutex> vit_guard(c->vit_mu);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // drain pending decode steps (their tokens are dropped)
+  ensure_prefill_tiles(c);
+  c->waited = c->launched = 0;
+  // the cache rows from `start` on are rewritten: whatever happens below, the context holds no sequence to decode from
+  sh.cached_ids.resize((size_t)start);
+  sh.have_logits = false;
+  sh.host_next_pos = start;
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipEventRecord(c->ev_a, s));
+  if (need_img && !reuse_img) {
+    const size_t img = (size_t)3 * c->cfg.vit_image * c->cfg.vit_image;
+    HIPCHK(c, hipMemcpyAsync(c->pixels_dev, pixels, img * 4, hipMemcpyHostToDevice, s));
+    if (text_ids) { const int rc = text_prepare(c, text_ids, T_text, s); if (rc != DTK_OK) return rc; }
+    vit_forward(c, false, s, 1, text_ids != nullptr);
+    project_image(c);
+    c->stats.vit_images++;
+    c->have_image = true;
+    c->cached_image_key = image_key;
+  }
+  HIPCHK(c, hipEventRecord(c->ev_b, s));
+  sh.last_reuse_start = start;
+  // ---- the row tables
+  const int n_shared = shared - start, n = n_shared + total, Tm = c->Tmax;
+  std::vector<int32_t> tab((size_t)6 * Tm);
+  int32_t *rope = tab.data(), *seg = rope + 2 * (size_t)Tm, *ids32 = seg + 2 * (size_t)Tm, *targets = ids32 + Tm;
+  for (int t = 0; t < n_shared; ++t) {
+    rope[2 * t] = start + t; rope[2 * t + 1] = start + t;
+    seg[2 * t] = 0; seg[2 * t + 1] = start + t;
+    ids32[t] = (int32_t)r.prefix[start + t];
+  }
+  {
+    int row = n_shared, k = 0;
+    for (int i = 0; i < r.N; ++i) {
+      const int begin = shared + k;     // cache row of the segment's first row: k = b_i
+      for (int j = 0; j < r.cand_len[i]; ++j, ++row, ++k) {
+        rope[2 * row] = shared + j; rope[2 * row + 1] = begin + j;
+        seg[2 * row] = begin; seg[2 * row + 1] = begin + j;
+        ids32[row] = (int32_t)(j == 0 ? r.prefix[P - 1] : r.cand_ids[k - 1]);
+        targets[k] = (int32_t)r.cand_ids[k];
+      }
+    }
+  }
+  int32_t* dtab = c->packed_rows;
+  const int2* d_rope = reinterpret_cast<const int2*>(dtab);
+  const int2* d_seg = reinterpret_cast<const int2*>(dtab + 2 * (size_t)Tm);
+  const int32_t *d_ids = dtab + 4 * (size_t)Tm, *d_targets = dtab + 5 * (size_t)Tm;
+  // only the used part of each table travels; `tab` is pageable host memory, so the error returns below drain the stream first
+  HIPCHK(c, hipMemcpyAsync(dtab, rope, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dtab + 2 * (size_t)Tm, seg, (size_t)2 * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dtab + 4 * (size_t)Tm, ids32, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dtab + 5 * (size_t)Tm, targets, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  const int d = c->d;
+  launch_embed_gather(d_ids, c->embed, c->X, n, d, s);
+  if (use_img) {  // splice projected image features over the placeholder embeddings: the prompt's rows, and position P-1's copies
+    const int lo = std::max(img_start, start), hi = std::min(img_start + c->nImg, shared);
+    if (hi > lo) launch_copy_rows(c->IMG + (size_t)(lo - img_start) * d, d, c->X + (size_t)(lo - start) * d, d, hi - lo, d, s);
+    if (shared >= img_start && shared < img_start + c->nImg) {
+      int row = n_shared;
+      for (int i = 0; i < r.N; row += r.cand_len[i], ++i)
+        launch_copy_rows(c->IMG + (size_t)(shared - img_start) * d, d, c->X + (size_t)row * d, d, 1, d, s);
+    }
+  }
+  c->launch_refused = false;
+  launch_rmsnorm_rows(c->X, d, c->layers[0].ln1, c->Xn, d, n, d, c->cfg.rms_eps, s);
+  const PackedRows pk{d_rope, d_seg, shared};
+  decoder_layers(c, n, start, shared + total, c->kv, s, &pk);
+  if (c->launch_refused) {
+    c->launch_refused = false;
+    (void)hipStreamSynchronize(s);
+    return fail(c, DTK_ERR_STATE, "dtk_score_packed: a kernel refused its shape (nothing launched for it)");
+  }
+  const int rc = score_rows(c, c->X + (size_t)n_shared * d, total, d_targets, s);
+  if (rc != DTK_OK) { (void)hipStreamSynchronize(s); return rc; }
+  HIPCHK(c, hipEventRecord(c->ev_c, s));
+  const float* o = c->score_out;
+  HIPCHK(c, hipMemcpyAsync(r.logprob, o, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  if (r.lse) HIPCHK(c, hipMemcpyAsync(r.lse, o + Tm, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  if (r.argmax) HIPCHK(c, hipMemcpyAsync(r.argmax, o + 2 * (size_t)Tm, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->ev_a, c->ev_c) == hipSuccess) c->stats.last_prefill_ms = ms;
+  if (hipEventElapsedTime(&ms, c->ev_a, c->ev_b) == hipSuccess) c->stats.last_vit_ms = ms;
+  c->stats.prefill_tokens += (uint64_t)n;
+  // the prompt's first P-1 positions stay; no current sequence (have_logits is false: dtk_decode refuses until the next prefill)
+  sh.cached_ids.assign(r.prefix, r.prefix + shared);
+  sh.cached_with_image = use_img;
+  sh.image_key = use_img ? image_key : 0;
+  sh.host_next_pos = shared;
+  return DTK_OK;
+}
+
+int dtk_score_packed(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
+                     const int64_t* cand_ids, const int32_t* cand_len, int N, float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  if (!c) return DTK_ERR_ARG;
+  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out};
+  int total = 0;
+  const int rc = packed_check(c, rq, &total);
+  if (rc != DTK_OK) return rc;
+  return score_packed_impl(c, rq, total, pixels, image_key, (int)flags);
 }
 
 int dtk_prefill_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
@@ -2623,6 +2811,20 @@ int dtk_score_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, u
                       text_ids, T_text, &rq);
 }
 
+int dtk_score_packed_text(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, const int64_t* text_ids,
+                          int T_text, uint64_t text_key, uint32_t flags, const int64_t* cand_ids, const int32_t* cand_len, int N,
+                          float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  if (!c) return DTK_ERR_ARG;
+  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out};
+  int total = 0;
+  const int rc0 = packed_check(c, rq, &total);
+  if (rc0 != DTK_OK) return rc0;
+  std::vector<float> dummy;
+  const int rc = prefill_text_common(c, pixels, dummy, text_ids);
+  if (rc != DTK_OK) return rc;
+  return score_packed_impl(c, rq, total, pixels, dtk_text_image_key(image_key, text_key), (int)flags, text_ids, T_text);
+}
+
 int dtk_prefill_slot_text(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
                           const int64_t* text_ids, int T_text, uint64_t text_key, int flags, float* logits_out) {
   if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_prefill_slot_text: slot %d of %d", slot, c ? c->nb : 0);
@@ -2878,6 +3080,41 @@ int dtk_op_attention(dtk_ctx* c, const uint16_t* Q, const uint16_t* K, const uin
   a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal; a.q_offset = q_offset;
   a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = 1;
   launch_attention(a, s);
+  HIPCHK(c, hipMemcpyAsync(O, dO, (size_t)H * Tq * hd * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return DTK_OK;
+}
+
+int dtk_op_attention_seg(dtk_ctx* c, const uint16_t* Q, const uint16_t* K, const uint16_t* V, int H, int Tq, int Tk, int hd, int shared_len,
+                         const int32_t* seg_begin, const int32_t* kv_row, uint16_t* O) {
+  if (!c || !Q || !K || !V || !O || !seg_begin || !kv_row) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: null argument");
+  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: head dim %d (128 or 64)", hd);
+  if (H < 1 || Tq < 1 || Tk < 1 || shared_len < 0 || shared_len > Tk) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: bad shape");
+  if (c->attn_impl == 1) return fail(c, DTK_ERR_STATE, "dtk_op_attention_seg: attn_impl = 1 (the VALU attention kernel) has no segmented form");
+  std::vector<int32_t> rows((size_t)2 * Tq);
+  for (int t = 0; t < Tq; ++t) {
+    if (kv_row[t] < 0 || kv_row[t] >= Tk || seg_begin[t] < 0 || seg_begin[t] > kv_row[t])
+      return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: row %d: segment begin %d, cache row %d of %d keys", t, seg_begin[t], kv_row[t], Tk);
+    rows[2 * (size_t)t] = seg_begin[t]; rows[2 * (size_t)t + 1] = kv_row[t];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t off = 0;
+  OPBUF(bf16_t, dQ, (size_t)H * Tq * hd); OPBUF(bf16_t, dK, (size_t)H * Tk * hd);
+  OPBUF(bf16_t, dV, (size_t)H * Tk * hd); OPBUF(bf16_t, dO, (size_t)H * Tq * hd); OPBUF(int2, dR, (size_t)Tq);
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dQ, Q, (size_t)H * Tq * hd * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dK, K, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dV, V, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dR, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
+  AttnArgs a;
+  a.Q = dQ; a.q_sh = (long)Tq * hd; a.q_st = hd;
+  a.K = dK; a.k_sh = (long)Tk * hd; a.k_st = hd;
+  a.V = dV; a.v_sh = (long)Tk * hd; a.v_st = hd;
+  a.O = dO; a.o_sh = (long)Tq * hd; a.o_st = hd;
+  a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = 1; a.q_offset = 0;
+  a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = 1;
+  if (!launch_attention_seg(a, shared_len, dR, s)) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: the kernel does not take these operands");
   HIPCHK(c, hipMemcpyAsync(O, dO, (size_t)H * Tq * hd * 2, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());

@@ -264,6 +264,10 @@ bool launch_gemm_sk_partials(const GemmArgs& a, hipStream_t s);     // the GEMM 
 void launch_sk_rope_scatter(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                             const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s,
                             int hd = 128);
+// ... and with a row table (see launch_rope_scatter_rows)
+void launch_sk_rope_scatter_rows(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                 const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows, int H, int KVH, int T_max, hipStream_t s,
+                                 int hd = 128);
 void launch_sk_reduce_swiglu(const GemmArgs& a, bf16_t* ACT, int ldact, hipStream_t s);    // a sliced gate/up role's partials (a.part, a.N = 2 ff) -> SiLU(gate) * up, [M][ff]
 void launch_sk_reduce(const GemmArgs& a, const bf16_t* norm_w, bf16_t* Y, int ldy, float eps, hipStream_t s);
 void set_gemm_bk(int v);     // k-tile of the 64x64 GEMM: 64 | 128
@@ -298,6 +302,11 @@ void launch_im2col(const float* pixels, bf16_t* patches, int image, int patch, i
 void launch_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                          const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos,
                          int H, int KVH, int T_max, hipStream_t s, int hd = 128);
+// The packed scoring pass (dtk_score_packed): row t rotates by the angle of position rows[t].x and appends its K / V at cache row
+// rows[t].y — the two differ for every candidate but the first, whose rows all continue the one prompt.  Same arithmetic per row.
+void launch_rope_scatter_rows(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                              const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows,
+                              int H, int KVH, int T_max, hipStream_t s, int hd = 128);
 
 struct AttnArgs {
   const bf16_t* Q; long q_sh; long q_st;   // element strides: head, token
@@ -315,6 +324,11 @@ struct AttnArgs {
   long q_sb = 0, k_sb = 0, v_sb = 0, o_sb = 0;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
+// Segmented causal attention of the packed scoring pass: the keys are cache rows [0, a.Tk); rows [0, shared_len) are the prompt every
+// query sees, the rest are the candidates' segments.  Query row t (rows[t] = {its segment's first cache row, its own cache row}) sees key
+// j iff j <= rows[t].y and (j < shared_len or j >= rows[t].x); a prompt row has begin 0.  a.causal / a.q_offset are not read.  The MFMA
+// flash kernel only (hd 128 / 64): false = it does not take these operands (a.impl == 1, another hd, misaligned strides), nothing launched.
+bool launch_attention_seg(const AttnArgs& a, int shared_len, const int2* rows, hipStream_t s);
 
 // per-row fp8 quantisation with a power-of-two scale; W is overwritten with the de-quantised values
 void launch_quant_fp8_rows(bf16_t* W, uint8_t* W8, float* scale, int N, int K, hipStream_t s);

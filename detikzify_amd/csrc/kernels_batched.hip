@@ -1333,35 +1333,54 @@ void launch_im2col(const float* pixels, bf16_t* patches, int image, int patch, i
 
 // grid (T, H), HD / 2 threads: thread i owns the RoPE pair (i, i + HD/2) of q head h; blocks h < KVH also rotate k head h
 // and copy v head h.  QKV row layout: [H q heads | KVH k heads | KVH v heads] x HD (HD = 128, or 64: TinyLlama).
-template <int HD>
-__global__ void k_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
-                               const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos,
-                               int H, int KVH, int T_max) {
+// qk(n) = column n of the row as a float, vb(n) = its bf16 bits; the row rotates by position `pos` and its K / V go to cache row `krow`
+// (a prefill: both start_pos + t; the packed scoring pass reads them from a table).
+template <int HD, class QK, class VB>
+__device__ __forceinline__ void rope_scatter_row(QK qk, VB vb, int pos, int krow, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                                 const bf16_t* cos_t, const bf16_t* sin_t, int T, int H, int KVH, int T_max) {
   constexpr int HD2 = HD / 2;
   const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;
   const int qd = H * HD, kvd = KVH * HD;
-  const int pos = start_pos + t;
-  const bf16_t* row = QKV + (size_t)t * (qd + 2 * kvd);
   const float c = bf2f(cos_t[(size_t)pos * HD2 + i]);
   const float s = bf2f(sin_t[(size_t)pos * HD2 + i]);
   {
-    const float x1 = bf2f(row[h * HD + i]), x2 = bf2f(row[h * HD + i + HD2]);
+    const float x1 = qk(h * HD + i), x2 = qk(h * HD + i + HD2);
     bf16_t* dst = Qh + ((size_t)h * T + t) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
     dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   if (h >= KVH) return;
   {
-    const float x1 = bf2f(row[qd + h * HD + i]), x2 = bf2f(row[qd + h * HD + i + HD2]);
-    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * HD;
+    const float x1 = qk(qd + h * HD + i), x2 = qk(qd + h * HD + i + HD2);
+    bf16_t* dst = kcache + ((size_t)h * T_max + krow) * HD;
     dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
     dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
   }
   {
-    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * HD;
-    dst[i] = row[qd + kvd + h * HD + i];
-    dst[i + HD2] = row[qd + kvd + h * HD + i + HD2];
+    bf16_t* dst = vcache + ((size_t)h * T_max + krow) * HD;
+    dst[i] = vb(qd + kvd + h * HD + i);
+    dst[i + HD2] = vb(qd + kvd + h * HD + i + HD2);
   }
+}
+template <int HD>
+__device__ __forceinline__ void rope_scatter_qkv(const bf16_t* QKV, int pos, int krow, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                                 const bf16_t* cos_t, const bf16_t* sin_t, int T, int H, int KVH, int T_max) {
+  const bf16_t* row = QKV + (size_t)blockIdx.x * ((H + 2 * KVH) * HD);
+  rope_scatter_row<HD>([&](int n) { return bf2f(row[n]); }, [&](int n) { return row[n]; }, pos, krow, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
+}
+template <int HD>
+__global__ void k_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                               const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos,
+                               int H, int KVH, int T_max) {
+  const int pos = start_pos + blockIdx.x;
+  rope_scatter_qkv<HD>(QKV, pos, pos, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
+}
+template <int HD>
+__global__ void k_rope_scatter_rows(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                    const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows,
+                                    int H, int KVH, int T_max) {
+  const int2 r = rows[blockIdx.x];      // {position, cache row}: one 8-byte load, ahead of everything that depends on it
+  rope_scatter_qkv<HD>(QKV, r.x, r.y, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
 }
 void launch_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                          const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH,
@@ -1373,49 +1392,56 @@ void launch_rope_scatter(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* 
     hipLaunchKernelGGL(k_rope_scatter<128>, dim3(T, H), dim3(64), 0, s, QKV, Qh, kcache, vcache, cos_t,
                        sin_t, T, start_pos, H, KVH, T_max);
 }
+void launch_rope_scatter_rows(const bf16_t* QKV, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                              const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows, int H, int KVH,
+                              int T_max, hipStream_t s, int hd) {
+  if (hd == 64)
+    hipLaunchKernelGGL(k_rope_scatter_rows<64>, dim3(T, H), dim3(32), 0, s, QKV, Qh, kcache, vcache, cos_t,
+                       sin_t, T, rows, H, KVH, T_max);
+  else
+    hipLaunchKernelGGL(k_rope_scatter_rows<128>, dim3(T, H), dim3(64), 0, s, QKV, Qh, kcache, vcache, cos_t,
+                       sin_t, T, rows, H, KVH, T_max);
+}
 
 // The q/k/v role as a sliced-K GEMM: its reduction IS k_rope_scatter's input — the slices' fp32 sums added in order, rounded to bf16 (the
 // Linear's output: what k_sk_reduce would have stored), then k_rope_scatter's arithmetic; no [T][qkvn] buffer in between.
 template <int S, int HD>
-__global__ void k_sk_rope_scatter(const float* part, long part_stride, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
-                                  const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max) {
-  constexpr int HD2 = HD / 2;
-  const int t = blockIdx.x, h = blockIdx.y, i = threadIdx.x;
-  const int qd = H * HD, kvd = KVH * HD, N = qd + 2 * kvd;
-  const int pos = start_pos + t;
-  const float* row = part + (size_t)t * N;
+__device__ __forceinline__ void sk_rope_scatter_row(const float* part, long part_stride, int pos, int krow, bf16_t* Qh, bf16_t* kcache,
+                                                    bf16_t* vcache, const bf16_t* cos_t, const bf16_t* sin_t, int T, int H, int KVH, int T_max) {
+  const float* row = part + (size_t)blockIdx.x * ((H + 2 * KVH) * HD);
   auto val = [&](int n) {
     float v = row[n];
 #pragma unroll
     for (int k = 1; k < S; ++k) v += row[(size_t)k * (size_t)part_stride + n];
     return rbf(v);
   };
-  const float c = bf2f(cos_t[(size_t)pos * HD2 + i]);
-  const float s = bf2f(sin_t[(size_t)pos * HD2 + i]);
-  {
-    const float x1 = val(h * HD + i), x2 = val(h * HD + i + HD2);
-    bf16_t* dst = Qh + ((size_t)h * T + t) * HD;
-    dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
-  }
-  if (h >= KVH) return;
-  {
-    const float x1 = val(qd + h * HD + i), x2 = val(qd + h * HD + i + HD2);
-    bf16_t* dst = kcache + ((size_t)h * T_max + pos) * HD;
-    dst[i] = f2bf(rbf(x1 * c) + rbf(-x2 * s));
-    dst[i + HD2] = f2bf(rbf(x2 * c) + rbf(x1 * s));
-  }
-  {
-    bf16_t* dst = vcache + ((size_t)h * T_max + pos) * HD;
-    dst[i] = f2bf(val(qd + kvd + h * HD + i));
-    dst[i + HD2] = f2bf(val(qd + kvd + h * HD + i + HD2));
-  }
+  rope_scatter_row<HD>(val, [&](int n) { return f2bf(val(n)); }, pos, krow, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
+}
+template <int S, int HD>
+__global__ void k_sk_rope_scatter(const float* part, long part_stride, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                  const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max) {
+  const int pos = start_pos + blockIdx.x;
+  sk_rope_scatter_row<S, HD>(part, part_stride, pos, pos, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
+}
+template <int S, int HD>
+__global__ void k_sk_rope_scatter_rows(const float* part, long part_stride, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                       const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows, int H, int KVH, int T_max) {
+  const int2 r = rows[blockIdx.x];      // {position, cache row}
+  sk_rope_scatter_row<S, HD>(part, part_stride, r.x, r.y, Qh, kcache, vcache, cos_t, sin_t, T, H, KVH, T_max);
 }
 void launch_sk_rope_scatter(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
                             const bf16_t* cos_t, const bf16_t* sin_t, int T, int start_pos, int H, int KVH, int T_max, hipStream_t s,
                             int hd) {
 #define SK_ROPE(S_) case S_: if (hd == 64) hipLaunchKernelGGL((k_sk_rope_scatter<S_, 64>), dim3(T, H), dim3(32), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, start_pos, H, KVH, T_max); \
                              else hipLaunchKernelGGL((k_sk_rope_scatter<S_, 128>), dim3(T, H), dim3(64), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, start_pos, H, KVH, T_max); break;
+  switch (kslices) { SK_ROPE(1) SK_ROPE(2) SK_ROPE(3) SK_ROPE(4) SK_ROPE(5) SK_ROPE(6) SK_ROPE(7) SK_ROPE(8) default: break; }
+#undef SK_ROPE
+}
+void launch_sk_rope_scatter_rows(const float* part, long part_stride, int kslices, bf16_t* Qh, bf16_t* kcache, bf16_t* vcache,
+                                 const bf16_t* cos_t, const bf16_t* sin_t, int T, const int2* rows, int H, int KVH, int T_max, hipStream_t s,
+                                 int hd) {
+#define SK_ROPE(S_) case S_: if (hd == 64) hipLaunchKernelGGL((k_sk_rope_scatter_rows<S_, 64>), dim3(T, H), dim3(32), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, rows, H, KVH, T_max); \
+                             else hipLaunchKernelGGL((k_sk_rope_scatter_rows<S_, 128>), dim3(T, H), dim3(64), 0, s, part, part_stride, Qh, kcache, vcache, cos_t, sin_t, T, rows, H, KVH, T_max); break;
   switch (kslices) { SK_ROPE(1) SK_ROPE(2) SK_ROPE(3) SK_ROPE(4) SK_ROPE(5) SK_ROPE(6) SK_ROPE(7) SK_ROPE(8) default: break; }
 #undef SK_ROPE
 }
@@ -1513,6 +1539,7 @@ __global__ __launch_bounds__(256) void k_attention(AttnArgs a) {
 // Row max / sum: 16 in-lane values + two xor-shuffles (lane groups 16/32 apart).  fp32 scores, fp32 running
 // max/sum, probabilities fed to the P.V MFMA as a bf16 hi + lo pair (~fp32-probability semantics, the same
 // as the VALU kernel and the oracle), fp32 O, one bf16 rounding of the output.
+// k_attention_mfma_seg below is this body with a per-row visibility table (the packed scoring pass): a fix here belongs there too.
 template <int HD>
 __global__ __launch_bounds__(256) void k_attention_mfma(AttnArgs a) {
   constexpr int CH = HD / 8;                           // 16-byte chunks per row
@@ -1674,9 +1701,210 @@ __global__ __launch_bounds__(256) void k_attention_mfma(AttnArgs a) {
   }
 }
 
+// The packed scoring pass's form of k_attention_mfma (dtk_score_packed; hd 128 / 64): the same tiles, fragments, softmax and rounding
+// points — the body below is that kernel's with three differences.  The keys are cache rows, [0, shared_len) the prompt and behind it one
+// segment per candidate.  seg_rows[query] = {first cache row of its segment (0: a prompt row), its own cache row}; a query sees key j iff
+// j <= own row and (j < shared_len or j >= segment begin), applied per element where the causal kernel tests key < klim.  The tiles stay
+// aligned at key 0 and a query walks them in the same order as in a prefill of its own sequence; the tiles that lie wholly inside
+// [shared_len, the lowest segment begin among the block's queries) hold other candidates' keys only and are never loaded — a masked tile
+// leaves m, l and O as they are (p = 0, corr = exp(0)), so skipping one changes no bit, and N candidates cost N segments of keys, not
+// N^2.  The block's key range comes from the table (min begin, max row over its 64 queries): a block may hold rows of several
+// segments, in any order.  a.causal / a.q_offset are not read.
+template <int HD>
+__global__ __launch_bounds__(256) void k_attention_mfma_seg(AttnArgs a, int shared_len, const int2* seg_rows) {
+  constexpr int CH = HD / 8;                           // 16-byte chunks per row
+  constexpr int KS = (HD + 31) / 32;                   // k-steps over d for S^T
+  constexpr int DT = (HD + 15) / 16;                   // 16-row tiles of O^T
+  constexpr int HDP = (HD % 64 == 0) ? HD + 8 : HD;    // row stride (elements): 72 -> 36 dwords, 128 -> 68 dwords
+  constexpr int NLD = (64 * CH + 255) / 256;           // 16-byte chunks a thread stages per operand
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[64 * HDP + 32];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[64 * HDP + 32];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lq = lane & 15, g = lane >> 4;
+  const int h = blockIdx.y;
+  { const long bz = blockIdx.z; a.Q += bz * a.q_sb; a.K += bz * a.k_sb; a.V += bz * a.v_sb; a.O += bz * a.o_sb; }   // batched problems
+  const int hk = a.kv_group > 1 ? h / a.kv_group : h;   // GQA
+  const int myq = blockIdx.x * 64 + wave * 16 + lq;
+  const int qrow = myq < a.Tq ? myq : a.Tq - 1;
+  const int2 me = seg_rows[qrow];     // one 8-byte load per lane, in flight with the Q fragments below: nothing waits on it before they are requested
+
+  bf16x8_t qf[KS];
+  {
+    const bf16_t* qp = a.Q + (size_t)h * a.q_sh + (size_t)qrow * a.q_st;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int c = ks * 4 + g;
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (c < CH) v = *reinterpret_cast<const u32x4*>(qp + c * 8);
+      qf[ks] = __builtin_bit_cast(bf16x8_t, v);
+    }
+  }
+  // the block's key range, from the table: lowest segment begin and highest cache row among its 64 queries
+  __shared__ int red[8];
+  int gmin = me.x, rmax = me.y;
+  {
+#pragma unroll
+    for (int sh = 1; sh < 16; sh <<= 1) {     // a wave's 16 queries sit in lanes lq = 0 .. 15 of every lane group
+      gmin = min(gmin, __shfl_xor(gmin, sh, 64));
+      rmax = max(rmax, __shfl_xor(rmax, sh, 64));
+    }
+    if (lane == 0) { red[wave] = gmin; red[4 + wave] = rmax; }
+    __syncthreads();
+    gmin = min(min(red[0], red[1]), min(red[2], red[3]));
+    rmax = max(max(red[4], red[5]), max(red[6], red[7]));
+  }
+  const int kmax = min(a.Tk, rmax + 1);                            // keys this block needs
+  const int skip_lo = (shared_len + 63) & ~63, skip_hi = gmin & ~63;   // the tiles starting in [skip_lo, skip_hi) hold no key that a query of this block sees
+  auto visible = [&](int key) { return key <= me.y && (key < shared_len || key >= me.x); };
+  auto next_tile = [&](int j0) {      // the tile after j0 (j0 = -64: the first)
+    const int n = j0 + 64;
+    return (n >= skip_lo && n < skip_hi) ? skip_hi : n;
+  };
+
+  float m = -1e30f, l = 0.f;
+  f32x4 o[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) o[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  u32x4 rk[NLD], rv[NLD];
+  auto tile_load = [&](int j0) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = tid + i * 256;
+      if (idx < 64 * CH) {
+        const int r = idx / CH, c = idx - r * CH;
+        int j = j0 + r; if (j >= a.Tk) j = a.Tk - 1;
+        rk[i] = *reinterpret_cast<const u32x4*>(a.K + (size_t)hk * a.k_sh + (size_t)j * a.k_st + c * 8);
+        rv[i] = *reinterpret_cast<const u32x4*>(a.V + (size_t)hk * a.v_sh + (size_t)j * a.v_st + c * 8);
+      }
+    }
+  };
+  auto tile_write = [&]() {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = tid + i * 256;
+      if (idx < 64 * CH) {
+        const int r = idx / CH, c = idx - r * CH;
+        *reinterpret_cast<u32x4*>(&Ks[r * HDP + c * 8]) = rk[i];
+        *reinterpret_cast<u32x4*>(&Vs[r * HDP + c * 8]) = rv[i];
+      }
+    }
+  };
+
+  tile_load(next_tile(-64));
+  for (int j0 = next_tile(-64); j0 < kmax; j0 = next_tile(j0)) {
+    __syncthreads();   // the previous tile's fragment reads are done
+    tile_write();
+    __syncthreads();
+    if (next_tile(j0) < kmax) tile_load(next_tile(j0));
+
+    // ---- S^T = K . Q^T : s[t][r] = score(key j0 + t*16 + g*4 + r, query lq)
+    f32x4 sc[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      sc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const int c = ks * 4 + g;
+        u32x4 kv = *reinterpret_cast<const u32x4*>(&Ks[(t * 16 + lq) * HDP + c * 8]);
+        if ((HD % 32) != 0 && ks == KS - 1 && c >= CH) kv = (u32x4){0u, 0u, 0u, 0u};
+        sc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kv), qf[ks], sc[t], 0, 0, 0);
+      }
+    }
+    float tmax = -1e30f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = j0 + t * 16 + g * 4 + r;
+        const float v = visible(key) ? sc[t][r] * a.scale : -1e30f;
+        sc[t][r] = v;
+        tmax = fmaxf(tmax, v);
+      }
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float mn = fmaxf(m, tmax);
+    const float corr = __expf(m - mn);
+    float psum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = j0 + t * 16 + g * 4 + r;
+        const float p = visible(key) ? __expf(sc[t][r] - mn) : 0.f;
+        sc[t][r] = p;
+        psum += p;
+      }
+    psum += __shfl_xor(psum, 16, 64);
+    psum += __shfl_xor(psum, 32, 64);
+    l = l * corr + psum;
+    m = mn;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt] *= corr;
+
+    // ---- O^T += V^T . P^T
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      // p = hi + lo with hi = bf16(p), lo = bf16(p - hi): two MFMAs on the same V^T fragment keep ~16
+      // mantissa bits of the fp32 probabilities (a single bf16 P costs ~2e-3 relative L2 on the output)
+      u32x4 pw, pl;
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+          const float p0 = sc[2 * s2 + half][2 * pr], p1 = sc[2 * s2 + half][2 * pr + 1];
+          const uint32_t hi = pack2(p0, p1);
+          pw[half * 2 + pr] = hi;
+          pl[half * 2 + pr] = pack2(p0 - pk_lo(hi), p1 - pk_hi(hi));
+        }
+      const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
+      const bf16x8_t pfl = __builtin_bit_cast(bf16x8_t, pl);
+      const bf16_t* v0 = Vs + ((2 * s2) * 16 + g * 4) * HDP + lq;       // keys of sub-tile 2*s2
+      const bf16_t* v1 = v0 + 16 * HDP;                                  // keys of sub-tile 2*s2 + 1
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) {
+        u32x4 vw;
+        vw[0] = (uint32_t)v0[dt * 16] | ((uint32_t)v0[dt * 16 + HDP] << 16);
+        vw[1] = (uint32_t)v0[dt * 16 + 2 * HDP] | ((uint32_t)v0[dt * 16 + 3 * HDP] << 16);
+        vw[2] = (uint32_t)v1[dt * 16] | ((uint32_t)v1[dt * 16 + HDP] << 16);
+        vw[3] = (uint32_t)v1[dt * 16 + 2 * HDP] | ((uint32_t)v1[dt * 16 + 3 * HDP] << 16);
+        const bf16x8_t vf = __builtin_bit_cast(bf16x8_t, vw);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
+        o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pfl, o[dt], 0, 0, 0);
+      }
+    }
+  }
+  if (myq < a.Tq) {
+    const float inv = 1.f / l;
+    bf16_t* op = a.O + (size_t)h * a.o_sh + (size_t)myq * a.o_st;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      const int d = dt * 16 + g * 4;
+      if (d < HD) {   // HD % 4 == 0: a group of 4 is fully in or fully out
+        u32x2 w;
+        w[0] = pack2(o[dt][0] * inv, o[dt][1] * inv);
+        w[1] = pack2(o[dt][2] * inv, o[dt][3] * inv);
+        *reinterpret_cast<u32x2*>(op + d) = w;
+      }
+    }
+  }
+}
+
+static bool attention_mfma_operands(const AttnArgs& a) {
+  return (a.hd == 64 || a.hd == 72 || a.hd == 128) && (a.q_st % 8 == 0) && (a.k_st % 8 == 0) && (a.v_st % 8 == 0) &&
+         (a.o_st % 4 == 0) && (a.q_sh % 8 == 0) && (a.k_sh % 8 == 0) && (a.v_sh % 8 == 0) && (a.o_sh % 4 == 0);
+}
+
+bool launch_attention_seg(const AttnArgs& a, int shared_len, const int2* rows, hipStream_t s) {
+  if (!attention_mfma_operands(a) || a.hd == 72 || a.impl == 1 || !rows || a.Tq < 1 || a.Tk < 1 || shared_len < 0) return false;
+  dim3 grid((a.Tq + 63) / 64, a.H, a.nbatch > 0 ? a.nbatch : 1);
+  if (a.hd == 64) hipLaunchKernelGGL((k_attention_mfma_seg<64>), grid, dim3(256), 0, s, a, shared_len, rows);
+  else hipLaunchKernelGGL((k_attention_mfma_seg<128>), grid, dim3(256), 0, s, a, shared_len, rows);
+  return true;
+}
+
 void launch_attention(const AttnArgs& a, hipStream_t s) {
-  const bool can_mfma = (a.hd == 64 || a.hd == 72 || a.hd == 128) && (a.q_st % 8 == 0) && (a.k_st % 8 == 0) && (a.v_st % 8 == 0) &&
-                        (a.o_st % 4 == 0) && (a.q_sh % 8 == 0) && (a.k_sh % 8 == 0) && (a.v_sh % 8 == 0) && (a.o_sh % 4 == 0);
+  const bool can_mfma = attention_mfma_operands(a);
   // the choice must not depend on Tq: a tail prefill after a KV-prefix reuse (1 query) and the full prefill (all queries) have
   // to round identically, and they do when the same kernel scans the same 64-key tiles (a query's result does not depend on
   // which block / lane holds it)

@@ -76,6 +76,22 @@ class DetikzifyPipeline:
         per_token = [float(v) for v in out.logprobs]
         return float(out.logprobs.sum(dtype=torch.float64)), per_token
 
+    def score_candidates(self, image=None, codes: List[str] = (), text: Optional[str] = None,
+                         preprocess: bool = True) -> List[Tuple[float, List[float]]]:
+        """score() of every program in `codes` for one (image, text) — same prompt, same tokenisation (no special tokens, EOS
+        appended) — from one packed pass over all of them (model.score_candidates); one (sum, per-token) pair per code, in order."""
+        import torch
+        self.check_inputs(image, text)
+        tokenizer = unwrap(self.processor).tokenizer
+        features = self.processor(images=self.load(image, preprocess=preprocess) if image is not None else None, text=text,
+                                  text_kwargs={"truncation": True}, return_tensors="pt")
+        prompt = features.input_ids.reshape(-1).to(torch.int64)
+        programs = [torch.tensor(list(tokenizer.encode(code, add_special_tokens=False)) + [int(tokenizer.eos_token_id)], dtype=torch.int64)
+                    for code in codes]
+        conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}     # as DetikzifyGenerator.generate
+        outs = self.model.score_candidates(prompt, programs, features.get("pixel_values"), **conditioning)
+        return [(float(o.logprobs.sum(dtype=torch.float64)), [float(v) for v in o.logprobs]) for o in outs]
+
     def simulate(self, image=None, text: Optional[str] = None, preprocess: bool = True,
                  expansions: Optional[Numeric] = None, timeout: Optional[int] = None, trees: int = 1,
                  **gen_kwargs) -> Generator[Tuple[Numeric, TikzDocument], None, None]:

@@ -18,13 +18,14 @@ import threading
 import ctypes as C
 import hashlib
 from types import SimpleNamespace
-from typing import Any, Dict, Iterable, List, Optional, Tuple, Union
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
 from .. import _lib
 from .config import DetikzifyConfig
+from .packing import plan_packed_passes
 
 
 class GenerationConfig:
@@ -612,6 +613,79 @@ class DetikzifyForCausalLM:
         finally:
             self._single_busy.release()
         return ScoreOutput(logprobs=torch.from_numpy(lp), argmax=torch.from_numpy(am).to(torch.int64), lse=torch.from_numpy(lse), first=first)
+
+    def score_candidates(self, prefix_ids: torch.Tensor, candidates: Sequence[Any], pixel_values: Optional[torch.Tensor] = None,
+                         adapter_input_ids: Optional[torch.Tensor] = None, adapter_attention_mask: Optional[torch.Tensor] = None,
+                         reuse: Optional[bool] = None) -> List[ScoreOutput]:
+        """score(prefix + candidate, first=len(prefix)) for every candidate of one prompt, in input order, from ONE pass of the
+        decoder over all candidates' rows (dtk_score_packed): the weights stream once, each candidate attends to the prompt and to
+        itself.  Candidates that do not fit one pass (P - 1 + sum of lengths <= max_positions) are split by plan_packed_passes();
+        the later passes reuse the prompt's cache.  Leaves the prompt's first P-1 positions cached and NO sequence to decode from:
+        prefill() before decode_launch()."""
+        if not self._weights_ready:
+            raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
+        self._refuse_while_batch_busy("score_candidates")
+        prefix = torch.as_tensor(prefix_ids).detach().to("cpu", torch.int64)
+        if prefix.dim() == 2:
+            if prefix.shape[0] != 1:
+                raise ValueError("batch size 1 only")
+            prefix = prefix[0]
+        prefix = prefix.reshape(-1).contiguous()
+        P = prefix.numel()
+        cands = [torch.as_tensor(c).detach().to("cpu", torch.int64).reshape(-1).contiguous() for c in candidates]
+        if not cands:
+            raise ValueError("score_candidates: no candidates")
+        lens = [c.numel() for c in cands]
+        passes = plan_packed_passes(P, lens, int(self.config.max_positions))
+        tids = None
+        if adapter_input_ids is not None:
+            if not self.has_adapter():
+                raise TypeError("adapter_input_ids given but no adapter is loaded (load(..., adapter=True))")
+            tids = adapter_text(adapter_input_ids, adapter_attention_mask)
+        elif adapter_attention_mask is not None:
+            raise ValueError("adapter_attention_mask without adapter_input_ids")
+        px_ptr, key = None, (DUMMY_IMAGE_KEY if tids is not None else 0)
+        if pixel_values is not None:
+            px = pixel_values.detach().to("cpu", torch.float32).contiguous()
+            if px.dim() == 4:
+                if px.shape[0] != 1:
+                    raise ValueError("batch size 1 only")
+                px = px[0]
+            self._px_keepalive = px
+            px_ptr = px.numpy().ctypes.data_as(C.c_void_p)
+            key = self.image_key(pixel_values)
+        reuse = self.reuse_prefix if reuse is None else reuse
+        reuse_flags = _lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE
+        pfx = prefix.numpy().ctypes.data_as(C.c_void_p)
+        out: List[ScoreOutput] = []
+        if not self._single_busy.acquire(blocking=False):
+            raise _lib.DtkError("score_candidates() while a generate() decodes on this model's single sequence")
+        try:
+            for k, members in enumerate(passes):
+                ids = torch.cat([cands[i] for i in members]).contiguous()
+                clen = np.asarray([lens[i] for i in members], dtype=np.int32)
+                n = ids.numel()
+                lp, am, lse = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
+                flags = reuse_flags if (reuse or k > 0) else 0       # a later pass always continues the first one's prompt
+                tail = (ids.numpy().ctypes.data_as(C.c_void_p), clen.ctypes.data_as(C.c_void_p), len(members),
+                        lp.ctypes.data_as(C.c_void_p), am.ctypes.data_as(C.c_void_p), lse.ctypes.data_as(C.c_void_p))
+                with self._vit_lock:
+                    if tids is None:
+                        self._check(self.lib.dtk_score_packed(self._ctx, pfx, P, px_ptr, C.c_uint64(key), C.c_uint32(flags), *tail),
+                                    "dtk_score_packed")
+                    else:
+                        self._check(self.lib.dtk_score_packed_text(self._ctx, pfx, P, px_ptr, C.c_uint64(key),
+                                                                   tids.numpy().ctypes.data_as(C.c_void_p), tids.numel(),
+                                                                   C.c_uint64(text_key(tids)), C.c_uint32(flags), *tail), "dtk_score_packed_text")
+                lo = 0
+                for i in members:
+                    hi = lo + lens[i]
+                    out.append(ScoreOutput(logprobs=torch.from_numpy(lp[lo:hi].copy()), argmax=torch.from_numpy(am[lo:hi]).to(torch.int64),
+                                           lse=torch.from_numpy(lse[lo:hi].copy()), first=P))
+                    lo = hi
+        finally:
+            self._single_busy.release()
+        return out
 
     def forward(self, input_ids: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None, adapter_input_ids: Optional[torch.Tensor] = None, **hf_kwargs) -> CausalLMLoss:

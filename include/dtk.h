@@ -179,10 +179,31 @@ int  dtk_prefill(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels,
  * norm and lm_head run over rows first-1 .. T-2 on the matrix cores with the log-softmax folded into the GEMM's epilogue: no
  * [T][V] logits exist; a row's logits are the values dtk_prefill's last-row path gives (bf16-rounded), exp / log in fp32.
  * 1 <= first <= T-1, T >= 2.  logprob_out [T-first]; argmax_out (the greedy token of each position, lowest id on ties) and
- * lse_out (logsumexp of the row) [T-first] or NULL.  The first call allocates a workspace of (max_positions-1) x ceil(V/128) x
+ * lse_out (logsumexp of the row) [T-first] or NULL.  The first call allocates a workspace of max_positions x ceil(V/128) x
  * 16 bytes that the context keeps. */
 int  dtk_score(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags,
                int first, float* logprob_out, int32_t* argmax_out, float* lse_out);
+
+/* Scoring N candidate continuations of ONE prompt in one packed pass: log p(cand_i[j] | prefix, cand_i[:j]) for every candidate i and
+ * token j — what N calls of dtk_score(prefix + cand_i, first = P) give, for one stream of the decoder's weights instead of N.
+ * prefix_ids [P >= 1]: the prompt (image placeholders + text; pixels / image_key / flags as dtk_prefill).  cand_ids: the candidates
+ * concatenated, cand_len [N]: their lengths (each >= 1, N >= 1).  logprob_out, and argmax_out / lse_out or NULL: sum(cand_len) entries
+ * in the same order.  The pass runs the prompt's positions lcp .. P-2 (lcp = the longest common prefix with the cached sequence when
+ * DTK_PREFILL_REUSE_PREFIX is set, at most P-1) and one segment of len_i rows per candidate — inputs prefix[P-1], cand_i[0 .. len_i-2]
+ * at positions P-1 + j, K / V at cache rows P-1 + len_0 + .. + len_{i-1} + j; a row sees the prompt and the rows of its own segment up
+ * to itself.  Capacity: P-1 + sum(cand_len) <= max_positions, else DTK_ERR_RANGE.  Every argument is checked before anything is
+ * launched and a refused call leaves the context untouched; DTK_ERR_STATE under dtk_set_option("attn_impl", 1) (the VALU attention
+ * kernel has no segmented form).  The image placeholders must lie in the prompt: when an image is in use (pixels, or the cached image
+ * of image_key with DTK_PREFILL_REUSE_IMAGE) a candidate that holds image_token_id is refused with dtk_prefill's message for a wrong
+ * number of image tokens; without an image the id is a token like any other, as in dtk_score.
+ * Afterwards the context holds the prompt's first P-1 positions (cached ids, image key, K / V rows [0, P-1)), which a following
+ * dtk_prefill / dtk_score / dtk_score_packed with DTK_PREFILL_REUSE_PREFIX reuses, and NO current sequence: dtk_decode /
+ * dtk_decode_launch return DTK_ERR_STATE until the next prefill.  stats.last_prefill_ms / prefill_tokens count the pass as a
+ * prefill's.  The first call allocates dtk_score's workspace (max_positions rows: P = 1 leaves every row to the candidates) and
+ * 24 x max_positions bytes of row tables that the context keeps. */
+int  dtk_score_packed(dtk_ctx* ctx, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
+                      const int64_t* cand_ids, const int32_t* cand_len, int N,
+                      float* logprob_out, int32_t* argmax_out, float* lse_out);
 
 /* Sampling configuration for the following decode calls (resets the draw counter). */
 int  dtk_set_sampling(dtk_ctx* ctx, const dtk_sampling* s);
@@ -283,6 +304,11 @@ int  dtk_prefill_slot_text(dtk_ctx* ctx, int slot, const int64_t* ids, int T, co
 int  dtk_score_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key,
                     const int64_t* text_ids, int T_text, uint64_t text_key, uint32_t flags,
                     int first, float* logprob_out, int32_t* argmax_out, float* lse_out);
+/* dtk_score_packed with the tower conditioned on text_ids (as dtk_score_text) */
+int  dtk_score_packed_text(dtk_ctx* ctx, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key,
+                           const int64_t* text_ids, int T_text, uint64_t text_key, uint32_t flags,
+                           const int64_t* cand_ids, const int32_t* cand_len, int N,
+                           float* logprob_out, int32_t* argmax_out, float* lse_out);
 /* diagnostic: the embedding model's last_hidden_state (T_text x hidden bf16) of text_ids */
 int  dtk_adapter_embed(dtk_ctx* ctx, const int64_t* text_ids, int T_text, void* hidden_out_bf16);
 /* the key the *_text prefills cache an image prefix under (image_key, text_key) -> key; 0 when either is 0 */
@@ -494,6 +520,10 @@ int  dtk_op_gemv_mx(dtk_ctx* ctx, const uint8_t* W8, const float* wscale, const 
 /* softmax(Q K^T * scale [+ causal mask with q_offset]) V, heads-major [H][T][hd] bf16 */
 int  dtk_op_attention(dtk_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                       int H, int Tq, int Tk, int hd, int causal, int q_offset, uint16_t* O);
+/* the segmented causal attention of dtk_score_packed alone (hd 128 | 64, the MFMA kernel): Tk keys of which the first shared_len are
+ * visible to every query; query t sees key j iff j <= kv_row[t] and (j < shared_len or j >= seg_begin[t]); 0 <= seg_begin[t] <= kv_row[t] < Tk */
+int  dtk_op_attention_seg(dtk_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* V,
+                          int H, int Tq, int Tk, int hd, int shared_len, const int32_t* seg_begin, const int32_t* kv_row, uint16_t* O);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */

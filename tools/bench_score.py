@@ -59,7 +59,7 @@ res = dict(model=args.model, weight_format=args.weight_format, rows=int(ids.nume
            prefill_ms=round(a, 3), score_ms=round(b, 3), decode_step_ms=round(step, 4), decode_steps_total_ms=round(c, 1),
            lm_head_pass_ms=round(pass_ms, 3), lm_head_pass_tflops=round(flop / max(pass_ms, 1e-6) / 1e9, 1),
            prefill_ms_min_max=[round(min(ms_a), 3), round(max(ms_a), 3)], score_ms_min_max=[round(min(ms_b), 3), round(max(ms_b), 3)],
-           score_vs_decode_speedup=round(c / b, 1), workspace_bytes=(cfg.max_positions - 1) * ((cfg.vocab + 127) // 128) * 16,
+           score_vs_decode_speedup=round(c / b, 1), workspace_bytes=cfg.max_positions * ((cfg.vocab + 127) // 128) * 16,
            reps=args.reps, warmup=args.warmup)
 print(json.dumps(res))
 out = Path(args.out) if args.out else Path(__file__).resolve().parents[1] / "profiles" / f"score_{args.model.replace('detikzify-', '')}.json"
