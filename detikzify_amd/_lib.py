@@ -15,6 +15,7 @@ DTK_ARCH_PROJ_NO_BIAS = 1   # include/dtk.h: dtk_config.reserved[3] flag
 DTK_PREFILL_REUSE_PREFIX, DTK_PREFILL_REUSE_IMAGE = 1, 2
 DTK_MAX_INFLIGHT = 4
 DTK_MAX_BATCH = 64          # entries of the active / tokens_out arrays of dtk_decode_batch_*
+DTK_MAX_TOP = 8             # most alternatives per position (dtk_score_top, dtk_set_option "top_logprobs")
 DTK_EPI_BIAS, DTK_EPI_GELU, DTK_EPI_RESIDUAL, DTK_GEMM_NAIVE = 1, 2, 4, 256
 DTK_GEMM_WT = 512
 DTK_GEMM_SL = 1024
@@ -203,6 +204,17 @@ SYMBOLS = {
                                      C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "dtk_engine_set_wait_lp_op": (C.c_int, [_P, DtkEngineOps.WAIT_LP]),
     "dtk_op_sample_lp": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float)]),
+    # additive (ABI stays 7): the k <= DTK_MAX_TOP most likely tokens of every scored / sampled position
+    "dtk_score_top": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "dtk_score_top_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, C.c_int, _P, _P, _P,
+                                     C.c_int, _P, _P]),
+    "dtk_score_packed_top": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_int, _P, _P, _P, C.c_int, _P, _P]),
+    "dtk_score_packed_top_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, _P, _P, C.c_int,
+                                            _P, _P, _P, C.c_int, _P, _P]),
+    "dtk_op_score_top": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, _P, _P, _P]),
+    "dtk_decode_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "dtk_decode_batch_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
 }
 
 _lib = None

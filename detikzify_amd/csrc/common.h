@@ -91,6 +91,14 @@ struct DecState {
 #ifndef DTK_MAX_BATCH
 #define DTK_MAX_BATCH 64   // == include/dtk.h
 #endif
+#ifndef DTK_MAX_TOP
+#define DTK_MAX_TOP 8      // == include/dtk.h: the most alternatives per position ("top_logprobs", dtk_score_top)
+#endif
+// One position's top-k alternatives as the decode step leaves them (dtk_set_option "top_logprobs"): the k first entries of the
+// vocabulary ordered by raw logit descending, token id ascending on ties; entries >= k are not written.  A forced token: id -1, z NaN.
+struct TopRec { int32_t id[DTK_MAX_TOP]; float z[DTK_MAX_TOP]; };
+// (z, id) comes before (bz, bi) in that order
+__device__ __forceinline__ bool top_before(float z, int id, float bz, int bi) { return z > bz || (z == bz && id < bi); }
 #define DTK_PFX_GRID 16    // group rows of k_attn_prefix_g's grid: row y takes groups y, y + 16, ...
 #define DTK_PFX_GROUPS 64  // prefix groups a step can hand to k_attn_prefix_g: the worst case of 64 slots that share nothing (64 singleton groups), so that
                            // whether a slot's prefix goes through the matrix cores never depends on how many OTHER prefixes the step holds (was 16)

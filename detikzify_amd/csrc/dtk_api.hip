@@ -136,6 +136,7 @@ struct dtk_ctx {
   // scoring call and kept (hipMalloc of its own, not the arena: a context that never scores pays nothing)
   float* score_rec = nullptr;
   float* score_out = nullptr;         // [4][max_positions]: logprob, lse, argmax (int32), z[argmax]
+  float* score_top = nullptr;         // dtk_score_top: [2][max_positions][DTK_MAX_TOP]: ids (int32), logprob; allocated by the first call with k > 0
   // dtk_score_packed: the row tables of one packed pass, [6][max_positions] int32 — {position, cache row} and {segment begin, cache row}
   // per row (int2 each), the rows' input ids, the scored rows' targets; allocated by the first packed call and kept
   int32_t* packed_rows = nullptr;
@@ -157,6 +158,18 @@ struct dtk_ctx {
   float2* lp_ring_host = nullptr;    // pinned mirror
   float2* lpb_dev = nullptr;         // [DTK_MAX_INFLIGHT][DTK_MAX_BATCH] (contexts with slots)
   float2* lpb_host = nullptr;
+  // dtk_set_option "top_logprobs" = k (needs "logprobs"): every step also leaves the k most likely tokens of the logits it sampled from
+  // (k_top_logits, in front of the sampler) and the logsumexp its logprob was taken against; rings indexed as lp_ring / lpb.  Allocated
+  // (hipMalloc / pinned, not the arena) when the option is first switched on
+  int top_logprobs = 0;
+  TopRec* top_ring_dev = nullptr;    // [DTK_MAX_INFLIGHT]
+  TopRec* top_ring_host = nullptr;
+  float* lse_ring_dev = nullptr;     // [DTK_MAX_INFLIGHT]
+  float* lse_ring_host = nullptr;
+  TopRec* topb_dev = nullptr;        // [DTK_MAX_INFLIGHT][DTK_MAX_BATCH] (contexts with slots)
+  TopRec* topb_host = nullptr;
+  float* lseb_dev = nullptr;
+  float* lseb_host = nullptr;
   // ViT
   float* pixels_dev = nullptr;
   bf16_t *patches, *VX, *VN, *VQKV, *VAO, *VH, *feats, *last_hidden;
@@ -762,8 +775,25 @@ static inline unsigned* batch_err_word(const dtk_ctx* c) { return reinterpret_ca
 // the D2H copy of the log-probability ring that follows a step's token copy (nothing with the option off)
 static inline hipError_t copy_lp_ring(dtk_ctx* c, bool batch) {
   if (!c->logprobs) return hipSuccess;
+  if (c->top_logprobs) {
+    hipError_t e = batch ? hipMemcpyAsync(c->topb_host, c->topb_dev, sizeof(TopRec) * (size_t)DTK_MAX_INFLIGHT * DTK_MAX_BATCH, hipMemcpyDeviceToHost, c->stream)
+                         : hipMemcpyAsync(c->top_ring_host, c->top_ring_dev, sizeof(TopRec) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) return e;
+    e = batch ? hipMemcpyAsync(c->lseb_host, c->lseb_dev, sizeof(float) * (size_t)DTK_MAX_INFLIGHT * DTK_MAX_BATCH, hipMemcpyDeviceToHost, c->stream)
+              : hipMemcpyAsync(c->lse_ring_host, c->lse_ring_dev, sizeof(float) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream);
+    if (e != hipSuccess) return e;
+  }
   return batch ? hipMemcpyAsync(c->lpb_host, c->lpb_dev, LPB_BYTES, hipMemcpyDeviceToHost, c->stream)
                : hipMemcpyAsync(c->lp_ring_host, c->lp_ring_dev, sizeof(float2) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream);
+}
+
+// "top_logprobs": k_top_logits in front of the step's sampler, on the logits, DecState and BatchState the sampler is about to read
+static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
+  if (!c->top_logprobs || !c->logprobs) return;
+  TopArgs t;
+  t.logits = sa.logits; t.V = sa.V; t.logits_stride = sa.logits_stride; t.st = sa.st; t.bs = sa.bs; t.nslots = sa.nslots;
+  t.ring = sa.ring; t.k = c->top_logprobs; t.top_ring = sa.bs ? c->topb_dev : c->top_ring_dev;
+  launch_top_logits(t, c->stream);
 }
 
 void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
@@ -773,6 +803,8 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   sa.x = c->x; sa.d = c->d; sa.tok_ring = c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
   sa.lp_ring = c->logprobs ? c->lp_ring_dev : nullptr;
+  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lse_ring_dev : nullptr;
+  top_logits_launch(c, sa);
   if (c->mb_single) launch_sample_mb(sa, s); else launch_sample(sa, s);
   const float scale = 1.0f / sqrtf((float)c->hd);
   for (int l = 0; l < c->L; ++l) {
@@ -828,6 +860,8 @@ void batch_step_launches_mx(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = nslots; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -874,6 +908,8 @@ void batch_step_launches(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = 16 * c->nt_step; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -946,6 +982,8 @@ void batch_step_launches_mv(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -1349,6 +1387,15 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
   if (c->score_rec) (void)hipFree(c->score_rec);
   if (c->score_out) (void)hipFree(c->score_out);
+  if (c->score_top) (void)hipFree(c->score_top);
+  if (c->top_ring_dev) (void)hipFree(c->top_ring_dev);
+  if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
+  if (c->topb_dev) (void)hipFree(c->topb_dev);
+  if (c->lseb_dev) (void)hipFree(c->lseb_dev);
+  if (c->top_ring_host) (void)hipHostFree(c->top_ring_host);
+  if (c->lse_ring_host) (void)hipHostFree(c->lse_ring_host);
+  if (c->topb_host) (void)hipHostFree(c->topb_host);
+  if (c->lseb_host) (void)hipHostFree(c->lseb_host);
   if (c->packed_rows) (void)hipFree(c->packed_rows);
   if (c->stream_vit) (void)hipStreamDestroy(c->stream_vit);
   if (c->ev_va) (void)hipEventDestroy(c->ev_va);
@@ -1611,17 +1658,34 @@ static int dummy_pixels(dtk_ctx* c, int batch, std::vector<float>& out) {
 }
 
 // dtk_score's rider on a prefill: the log-probabilities of ids[first .. T-1] from the hidden states of rows first-1 .. T-2
-struct ScoreReq { int first; float* logprob; int32_t* argmax; float* lse; };
+// k > 0 (dtk_score_top): + every scored position's k most likely tokens, [rows][k] ids and log-probabilities
+struct ScoreReq { int first; float* logprob; int32_t* argmax; float* lse; int k = 0; int32_t* top_ids = nullptr; float* top_logprob = nullptr; };
 
-static int score_buffers(dtk_ctx* c) {
+static int score_buffers(dtk_ctx* c, int k = 0) {
   HIPCHK(c, hipSetDevice(c->device));
   if (!c->score_rec) HIPCHK(c, hipMalloc(&c->score_rec, score_rec_floats(c->Tmax, c->V) * sizeof(float)));
   if (!c->score_out) HIPCHK(c, hipMalloc(&c->score_out, (size_t)4 * c->Tmax * sizeof(float)));
+  if (k > 0 && !c->score_top) HIPCHK(c, hipMalloc(&c->score_top, (size_t)2 * c->Tmax * DTK_MAX_TOP * sizeof(float)));
+  return DTK_OK;
+}
+// the k / top_ids_out / top_logprob_out triple of the *_top calls: k = 0 with both NULL is the call without them
+static int top_check(dtk_ctx* c, const char* who, int k, const int32_t* top_ids_out, const float* top_logprob_out) {
+  if (k == 0 && !top_ids_out && !top_logprob_out) return DTK_OK;
+  if (k < 1 || k > DTK_MAX_TOP) return fail(c, DTK_ERR_ARG, "%s: k = %d (1 .. DTK_MAX_TOP = %d, or 0 with NULL outputs)", who, k, DTK_MAX_TOP);
+  if (k > c->V) return fail(c, DTK_ERR_ARG, "%s: k = %d exceeds the vocabulary (%d)", who, k, c->V);
+  if (!top_ids_out || !top_logprob_out) return fail(c, DTK_ERR_ARG, "%s: k = %d needs top_ids_out and top_logprob_out", who, k);
+  return DTK_OK;
+}
+// the device -> host copies of a scoring call's top-k results (rows x k, contiguous)
+static int score_top_copy(dtk_ctx* c, int M, int k, int32_t* top_ids, float* top_logprob, hipStream_t s) {
+  if (k <= 0) return DTK_OK;
+  HIPCHK(c, hipMemcpyAsync(top_ids, c->score_top, (size_t)M * k * 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(top_logprob, c->score_top + (size_t)c->Tmax * DTK_MAX_TOP, (size_t)M * k * 4, hipMemcpyDeviceToHost, s));
   return DTK_OK;
 }
 
 // final norm of M rows of X -> Xn, lm_head with the log-softmax epilogue, merge: results in c->score_out.  targets: device, one per row
-static int score_rows(dtk_ctx* c, const bf16_t* X, int M, const int32_t* targets, hipStream_t s) {
+static int score_rows(dtk_ctx* c, const bf16_t* X, int M, const int32_t* targets, hipStream_t s, int k = 0) {
   const int d = c->d;
   launch_rmsnorm_rows(X, d, c->final_norm, c->Xn, d, M, d, c->cfg.rms_eps, s);
   GemmArgs g;
@@ -1631,6 +1695,8 @@ static int score_rows(dtk_ctx* c, const bf16_t* X, int M, const int32_t* targets
   if (!launch_gemm_logsoftmax(g, s)) return fail(c, DTK_ERR_STATE, "dtk_score: the log-softmax lm_head kernel does not take this shape (d = %d)", d);
   float* o = c->score_out;
   launch_score_merge(c->score_rec, M, c->V, o, o + c->Tmax, reinterpret_cast<int32_t*>(o + 2 * (size_t)c->Tmax), o + 3 * (size_t)c->Tmax, s);
+  if (k > 0)
+    launch_score_top(g, o + c->Tmax, k, reinterpret_cast<int32_t*>(c->score_top), c->score_top + (size_t)c->Tmax * DTK_MAX_TOP, nullptr, s);
   return DTK_OK;
 }
 
@@ -1714,7 +1780,7 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
   HIPCHK(c, hipMemcpyAsync(st_dst, &st0, sizeof st0, hipMemcpyHostToDevice, s));
   if (score) {
     // rows first-1 .. T-2 of the context = rows first-1-start .. of X; the target of row p is ids[p + 1], already on the device
-    const int rc = score_rows(c, c->X + (size_t)(score->first - 1 - start) * d, T - score->first, c->ids_dev + (score->first - start), s);
+    const int rc = score_rows(c, c->X + (size_t)(score->first - 1 - start) * d, T - score->first, c->ids_dev + (score->first - start), s, score->k);
     if (rc != DTK_OK) return rc;
   }
   HIPCHK(c, hipEventRecord(c->ev_c, s));      // stats.last_prefill_ms of a scoring call includes its lm_head pass
@@ -1725,6 +1791,8 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
     HIPCHK(c, hipMemcpyAsync(score->logprob, o, (size_t)M * 4, hipMemcpyDeviceToHost, s));
     if (score->lse) HIPCHK(c, hipMemcpyAsync(score->lse, o + c->Tmax, (size_t)M * 4, hipMemcpyDeviceToHost, s));
     if (score->argmax) HIPCHK(c, hipMemcpyAsync(score->argmax, o + 2 * (size_t)c->Tmax, (size_t)M * 4, hipMemcpyDeviceToHost, s));
+    const int rc = score_top_copy(c, M, score->k, score->top_ids, score->top_logprob, s);
+    if (rc != DTK_OK) return rc;
   }
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
@@ -1747,7 +1815,8 @@ int dtk_prefill(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint
 }
 
 // argument checks of dtk_score / dtk_score_text: everything is refused before anything is launched
-static int score_check(dtk_ctx* c, const int64_t* ids, int T, int first, const float* logprob_out) {
+static int score_check(dtk_ctx* c, const int64_t* ids, int T, int first, const float* logprob_out, int k = 0, const int32_t* top_ids_out = nullptr,
+                       const float* top_logprob_out = nullptr) {
   if (!ids || !logprob_out) return fail(c, DTK_ERR_ARG, "dtk_score: null argument");
   if (T < 2) return fail(c, DTK_ERR_ARG, "dtk_score: %d token(s): scoring needs a context token and a target (T >= 2)", T);
   if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "dtk_score: %d tokens exceed max_positions %d", T, c->Tmax);
@@ -1755,16 +1824,23 @@ static int score_check(dtk_ctx* c, const int64_t* ids, int T, int first, const f
   for (int t = first; t < T; ++t)
     if (ids[t] < 0 || ids[t] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_score: target id %lld at position %d outside [0, %d)", (long long)ids[t], t, c->V);
   if (!gemm_logsoftmax_supported(c->d)) return fail(c, DTK_ERR_ARG, "dtk_score: the log-softmax lm_head kernel needs hidden %% 8 == 0 (d = %d)", c->d);
-  return score_buffers(c);
+  const int rc = top_check(c, "dtk_score_top", k, top_ids_out, top_logprob_out);
+  if (rc != DTK_OK) return rc;
+  return score_buffers(c, k);
+}
+
+int dtk_score_top(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags, int first,
+                  float* logprob_out, int32_t* argmax_out, float* lse_out, int k, int32_t* top_ids_out, float* top_logprob_out) {
+  if (!c) return DTK_ERR_ARG;
+  const int rc = score_check(c, ids, T, first, logprob_out, k, top_ids_out, top_logprob_out);
+  if (rc != DTK_OK) return rc;
+  const ScoreReq rq{first, logprob_out, argmax_out, lse_out, k, top_ids_out, top_logprob_out};
+  return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, image_key, (int)flags, nullptr, nullptr, 0, &rq);
 }
 
 int dtk_score(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags, int first,
               float* logprob_out, int32_t* argmax_out, float* lse_out) {
-  if (!c) return DTK_ERR_ARG;
-  const int rc = score_check(c, ids, T, first, logprob_out);
-  if (rc != DTK_OK) return rc;
-  const ScoreReq rq{first, logprob_out, argmax_out, lse_out};
-  return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, image_key, (int)flags, nullptr, nullptr, 0, &rq);
+  return dtk_score_top(c, ids, T, pixels, image_key, flags, first, logprob_out, argmax_out, lse_out, 0, nullptr, nullptr);
 }
 
 // ---- dtk_score_packed: N candidate continuations of one prompt in ONE pass of the decoder layers -------------------
@@ -1774,6 +1850,7 @@ struct PackedReq {
   const int64_t* prefix; int P;
   const int64_t* cand_ids; const int32_t* cand_len; int N;
   float* logprob; int32_t* argmax; float* lse;
+  int k = 0; int32_t* top_ids = nullptr; float* top_logprob = nullptr;      // dtk_score_packed_top
 };
 
 // every refusal of dtk_score_packed / dtk_score_packed_text, before anything is launched or the context changes; total = sum of len_i
@@ -1797,7 +1874,9 @@ static int packed_check(dtk_ctx* c, const PackedReq& r, int* total_out) {
   if (c->attn_impl == 1)
     return fail(c, DTK_ERR_STATE, "dtk_score_packed: attn_impl = 1 (the VALU attention kernel) has no segmented form; the packed pass needs the MFMA kernel (attn_impl 0 or 2)");
   if (!gemm_logsoftmax_supported(c->d)) return fail(c, DTK_ERR_ARG, "dtk_score_packed: the log-softmax lm_head kernel needs hidden %% 8 == 0 (d = %d)", c->d);
-  const int rc = score_buffers(c);
+  const int rct = top_check(c, "dtk_score_packed_top", r.k, r.top_ids, r.top_logprob);
+  if (rct != DTK_OK) return rct;
+  const int rc = score_buffers(c, r.k);
   if (rc != DTK_OK) return rc;
   if (!c->packed_rows) HIPCHK(c, hipMalloc(&c->packed_rows, (size_t)6 * c->Tmax * sizeof(int32_t)));
   *total_out = (int)total;
@@ -1913,13 +1992,14 @@ static int score_packed_impl(dtk_ctx* c, const PackedReq& r, int total, const fl
     (void)hipStreamSynchronize(s);
     return fail(c, DTK_ERR_STATE, "dtk_score_packed: a kernel refused its shape (nothing launched for it)");
   }
-  const int rc = score_rows(c, c->X + (size_t)n_shared * d, total, d_targets, s);
+  const int rc = score_rows(c, c->X + (size_t)n_shared * d, total, d_targets, s, r.k);
   if (rc != DTK_OK) { (void)hipStreamSynchronize(s); return rc; }
   HIPCHK(c, hipEventRecord(c->ev_c, s));
   const float* o = c->score_out;
   HIPCHK(c, hipMemcpyAsync(r.logprob, o, (size_t)total * 4, hipMemcpyDeviceToHost, s));
   if (r.lse) HIPCHK(c, hipMemcpyAsync(r.lse, o + Tm, (size_t)total * 4, hipMemcpyDeviceToHost, s));
   if (r.argmax) HIPCHK(c, hipMemcpyAsync(r.argmax, o + 2 * (size_t)Tm, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+  { const int rct = score_top_copy(c, total, r.k, r.top_ids, r.top_logprob, s); if (rct != DTK_OK) { (void)hipStreamSynchronize(s); return rct; } }
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   float ms = 0.f;
@@ -1934,14 +2014,20 @@ static int score_packed_impl(dtk_ctx* c, const PackedReq& r, int total, const fl
   return DTK_OK;
 }
 
-int dtk_score_packed(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
-                     const int64_t* cand_ids, const int32_t* cand_len, int N, float* logprob_out, int32_t* argmax_out, float* lse_out) {
+int dtk_score_packed_top(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
+                         const int64_t* cand_ids, const int32_t* cand_len, int N, float* logprob_out, int32_t* argmax_out, float* lse_out,
+                         int k, int32_t* top_ids_out, float* top_logprob_out) {
   if (!c) return DTK_ERR_ARG;
-  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out};
+  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out, k, top_ids_out, top_logprob_out};
   int total = 0;
   const int rc = packed_check(c, rq, &total);
   if (rc != DTK_OK) return rc;
   return score_packed_impl(c, rq, total, pixels, image_key, (int)flags);
+}
+
+int dtk_score_packed(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
+                     const int64_t* cand_ids, const int32_t* cand_len, int N, float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  return dtk_score_packed_top(c, prefix_ids, P, pixels, image_key, flags, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out, 0, nullptr, nullptr);
 }
 
 int dtk_prefill_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, const float* pixels, uint64_t image_key, int flags, float* logits_out) {
@@ -2112,7 +2198,19 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
 }
 
 // tokens_out[DTK_MAX_BATCH]: the token sampled for every slot that was active in the oldest un-read step (-1 otherwise)
-static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out) {
+// one TopRec + its logsumexp -> DTK_MAX_TOP (id, logprob = z - lse) pairs; entries >= k (and all of a NULL record): -1, NaN
+static void top_unpack(const TopRec* r, const float* lse, int k, int32_t* ids_out, float* lp_out) {
+  for (int i = 0; i < DTK_MAX_TOP; ++i) { ids_out[i] = -1; lp_out[i] = NAN; }
+  if (!r) return;
+  const float e = *(const volatile float*)lse;
+  for (int i = 0; i < k; ++i) {
+    ids_out[i] = ((const volatile int32_t*)r->id)[i];
+    lp_out[i] = ((const volatile float*)r->z)[i] - e;
+  }
+}
+
+static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out,
+                                  int32_t* top_ids_out = nullptr, float* top_logprob_out = nullptr) {
   if (c->bwaited >= c->blaunched) return fail(c, DTK_ERR_STATE, "no batch step in flight");
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t k = c->bwaited;
@@ -2129,6 +2227,7 @@ static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logpro
   for (int j = 0; j < DTK_MAX_BATCH; ++j) {
     tokens_out[j] = -1;
     if (logprob_out) logprob_out[j] = sample_logprob_out[j] = NAN;
+    if (top_ids_out) top_unpack(nullptr, nullptr, 0, top_ids_out + (size_t)j * DTK_MAX_TOP, top_logprob_out + (size_t)j * DTK_MAX_TOP);
     if (!hb->active[j]) continue;
     const int64_t tok = ((volatile int64_t*)c->tokb_host)[(size_t)ring * DTK_MAX_BATCH + j];
     tokens_out[j] = tok;
@@ -2136,6 +2235,9 @@ static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logpro
       const volatile float* lp = (volatile float*)(c->lpb_host + (size_t)ring * DTK_MAX_BATCH + j);
       logprob_out[j] = lp[0]; sample_logprob_out[j] = lp[1];
     }
+    if (top_ids_out)
+      top_unpack(c->topb_host + (size_t)ring * DTK_MAX_BATCH + j, c->lseb_host + (size_t)ring * DTK_MAX_BATCH + j, c->top_logprobs,
+                 top_ids_out + (size_t)j * DTK_MAX_TOP, top_logprob_out + (size_t)j * DTK_MAX_TOP);
     SeqHost& sh = c->bseq[(size_t)j];
     size_t later = 0;
     for (uint64_t q = k + 1; q < c->blaunched; ++q) later += c->bs_host[q % DTK_MAX_INFLIGHT].active[j] ? 1 : 0;
@@ -2155,6 +2257,16 @@ int dtk_decode_batch_wait_lp(dtk_ctx* c, int64_t* tokens_out, float* logprob_out
   if (!c || !tokens_out || !logprob_out || !sample_logprob_out) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_lp: null argument");
   if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
   return decode_batch_wait_impl(c, tokens_out, logprob_out, sample_logprob_out);
+}
+
+// dtk_decode_batch_wait_lp + every slot's top-k alternatives, [DTK_MAX_BATCH][DTK_MAX_TOP] (dtk_set_option "top_logprobs")
+int dtk_decode_batch_wait_top(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out, int32_t* top_ids_out,
+                              float* top_logprob_out) {
+  if (!c || !tokens_out || !logprob_out || !sample_logprob_out || !top_ids_out || !top_logprob_out)
+    return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_top: null argument");
+  if (!c->logprobs || !c->top_logprobs)
+    return fail(c, DTK_ERR_ARG, "dtk_decode_batch_wait_top: the context does not compute top-k alternatives (dtk_set_option \"logprobs\", 1 and \"top_logprobs\", k)");
+  return decode_batch_wait_impl(c, tokens_out, logprob_out, sample_logprob_out, top_ids_out, top_logprob_out);
 }
 
 // Copy the KV of the first n_tokens positions of slot src into slot dst (SURVEY §8 f1 / the proposed
@@ -2334,7 +2446,7 @@ int dtk_decode_launch(dtk_ctx* c) {
   return DTK_OK;
 }
 
-static int decode_wait_impl(dtk_ctx* c, int64_t* token_out, float* lp_out) {
+static int decode_wait_impl(dtk_ctx* c, int64_t* token_out, float* lp_out, int32_t* top_ids_out = nullptr, float* top_logprob_out = nullptr) {
   if (c->waited >= c->launched) return fail(c, DTK_ERR_STATE, "no decode step in flight");
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t k = c->waited;
@@ -2347,6 +2459,8 @@ static int decode_wait_impl(dtk_ctx* c, int64_t* token_out, float* lp_out) {
     const volatile float* lp = (volatile float*)(c->lp_ring_host + k % DTK_MAX_INFLIGHT);
     lp_out[0] = lp[0]; lp_out[1] = lp[1];
   }
+  if (top_ids_out)
+    top_unpack(c->top_ring_host + k % DTK_MAX_INFLIGHT, c->lse_ring_host + k % DTK_MAX_INFLIGHT, c->top_logprobs, top_ids_out, top_logprob_out);
   const size_t idx = c->seq0.cached_ids.size() - (size_t)(c->launched - k);
   c->seq0.cached_ids[idx] = tok;
   c->waited++;
@@ -2363,6 +2477,14 @@ int dtk_decode_wait_lp(dtk_ctx* c, int64_t* token_out, float* lp_out) {
   if (!c || !token_out || !lp_out) return fail(c, DTK_ERR_ARG, "dtk_decode_wait_lp: null argument");
   if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_decode_wait_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
   return decode_wait_impl(c, token_out, lp_out);
+}
+
+// dtk_decode_wait_lp + the top-k alternatives of the logits the token was sampled from, DTK_MAX_TOP entries each (dtk_set_option "top_logprobs")
+int dtk_decode_wait_top(dtk_ctx* c, int64_t* token_out, float* lp_out, int32_t* top_ids_out, float* top_logprob_out) {
+  if (!c || !token_out || !lp_out || !top_ids_out || !top_logprob_out) return fail(c, DTK_ERR_ARG, "dtk_decode_wait_top: null argument");
+  if (!c->logprobs || !c->top_logprobs)
+    return fail(c, DTK_ERR_ARG, "dtk_decode_wait_top: the context does not compute top-k alternatives (dtk_set_option \"logprobs\", 1 and \"top_logprobs\", k)");
+  return decode_wait_impl(c, token_out, lp_out, top_ids_out, top_logprob_out);
 }
 
 int dtk_decode(dtk_ctx* c, int64_t* token_out) {
@@ -2454,12 +2576,35 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
   if (!strcmp(name, "attn_full_max")) c->attn_full_max = value;
   else if (!strcmp(name, "logprobs")) {     // every sampled token comes with (logprob, sample_logprob): the LP sampler instantiations + one more D2H copy per step
     if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "logprobs must be 0 or 1");
+    if (value == 0 && c->top_logprobs) return fail(c, DTK_ERR_STATE, "logprobs: top_logprobs = %d needs it (set \"top_logprobs\" to 0 first)", c->top_logprobs);
     if ((value != 0) != (c->logprobs != 0)) {
       if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "logprobs: a batch step is in flight");
       if (c->engine_holds.load() > 0) return fail(c, DTK_ERR_STATE, "logprobs: an engine holds %d sequence(s) in this context's slots", c->engine_holds.load());
       // (their ring entries were written under the other setting; dtk_set_sampling / dtk_prefill start the single sequence afresh)
       if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "logprobs: %d single-sequence decode step(s) are unread", (int)(c->launched - c->waited));
       c->logprobs = value; drop_graph(c); drop_batch_graphs(c);
+    }
+  }
+  else if (!strcmp(name, "top_logprobs")) {     // + the k most likely tokens of every step's logits: k_top_logits in front of the sampler + two more D2H copies per step
+    if (value < 0 || value > DTK_MAX_TOP) return fail(c, DTK_ERR_ARG, "top_logprobs must be 0 .. %d", DTK_MAX_TOP);
+    if (value > c->V) return fail(c, DTK_ERR_ARG, "top_logprobs = %d exceeds the vocabulary (%d)", value, c->V);
+    if (value != 0 && !c->logprobs) return fail(c, DTK_ERR_STATE, "top_logprobs needs logprobs = 1 (dtk_set_option \"logprobs\", 1 first)");
+    if (value != c->top_logprobs) {
+      if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "top_logprobs: a batch step is in flight");
+      if (c->engine_holds.load() > 0) return fail(c, DTK_ERR_STATE, "top_logprobs: an engine holds %d sequence(s) in this context's slots", c->engine_holds.load());
+      if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "top_logprobs: %d single-sequence decode step(s) are unread", (int)(c->launched - c->waited));
+      if (value) {      // every buffer on its own: a call that failed part-way is completed by the next one
+        const size_t n1 = DTK_MAX_INFLIGHT, nb = c->nb > 0 ? (size_t)DTK_MAX_INFLIGHT * DTK_MAX_BATCH : 0;
+        if (!c->top_ring_dev) { HIPCHK(c, hipMalloc(&c->top_ring_dev, sizeof(TopRec) * n1)); HIPCHK(c, hipMemset(c->top_ring_dev, 0, sizeof(TopRec) * n1)); }
+        if (!c->lse_ring_dev) { HIPCHK(c, hipMalloc(&c->lse_ring_dev, sizeof(float) * n1)); HIPCHK(c, hipMemset(c->lse_ring_dev, 0, sizeof(float) * n1)); }
+        if (!c->top_ring_host) HIPCHK(c, hipHostMalloc((void**)&c->top_ring_host, sizeof(TopRec) * n1, hipHostMallocDefault));
+        if (!c->lse_ring_host) HIPCHK(c, hipHostMalloc((void**)&c->lse_ring_host, sizeof(float) * n1, hipHostMallocDefault));
+        if (nb && !c->topb_dev) { HIPCHK(c, hipMalloc(&c->topb_dev, sizeof(TopRec) * nb)); HIPCHK(c, hipMemset(c->topb_dev, 0, sizeof(TopRec) * nb)); }
+        if (nb && !c->lseb_dev) { HIPCHK(c, hipMalloc(&c->lseb_dev, sizeof(float) * nb)); HIPCHK(c, hipMemset(c->lseb_dev, 0, sizeof(float) * nb)); }
+        if (nb && !c->topb_host) HIPCHK(c, hipHostMalloc((void**)&c->topb_host, sizeof(TopRec) * nb, hipHostMallocDefault));
+        if (nb && !c->lseb_host) HIPCHK(c, hipHostMalloc((void**)&c->lseb_host, sizeof(float) * nb, hipHostMallocDefault));
+      }
+      c->top_logprobs = value; drop_graph(c); drop_batch_graphs(c);
     }
   }
   else if (!strcmp(name, "gemm_tile")) {   // MFMA GEMM block tile: 0 auto, 1 = 64x64, 2 = 128x64, 3 = 128x128 (process-wide)
@@ -2800,13 +2945,19 @@ int dtk_prefill_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels,
 
 int dtk_score_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, const int64_t* text_ids, int T_text,
                    uint64_t text_key, uint32_t flags, int first, float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  return dtk_score_top_text(c, ids, T, pixels, image_key, text_ids, T_text, text_key, flags, first, logprob_out, argmax_out, lse_out, 0, nullptr, nullptr);
+}
+
+int dtk_score_top_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, uint64_t image_key, const int64_t* text_ids, int T_text,
+                       uint64_t text_key, uint32_t flags, int first, float* logprob_out, int32_t* argmax_out, float* lse_out,
+                       int k, int32_t* top_ids_out, float* top_logprob_out) {
   if (!c) return DTK_ERR_ARG;
-  const int rc0 = score_check(c, ids, T, first, logprob_out);
+  const int rc0 = score_check(c, ids, T, first, logprob_out, k, top_ids_out, top_logprob_out);
   if (rc0 != DTK_OK) return rc0;
   std::vector<float> dummy;
   const int rc = prefill_text_common(c, pixels, dummy, text_ids);
   if (rc != DTK_OK) return rc;
-  const ScoreReq rq{first, logprob_out, argmax_out, lse_out};
+  const ScoreReq rq{first, logprob_out, argmax_out, lse_out, k, top_ids_out, top_logprob_out};
   return prefill_impl(c, c->seq0, c->kv, c->logits, c->st, true, ids, T, pixels, dtk_text_image_key(image_key, text_key), (int)flags, nullptr,
                       text_ids, T_text, &rq);
 }
@@ -2814,8 +2965,15 @@ int dtk_score_text(dtk_ctx* c, const int64_t* ids, int T, const float* pixels, u
 int dtk_score_packed_text(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, const int64_t* text_ids,
                           int T_text, uint64_t text_key, uint32_t flags, const int64_t* cand_ids, const int32_t* cand_len, int N,
                           float* logprob_out, int32_t* argmax_out, float* lse_out) {
+  return dtk_score_packed_top_text(c, prefix_ids, P, pixels, image_key, text_ids, T_text, text_key, flags, cand_ids, cand_len, N, logprob_out,
+                                   argmax_out, lse_out, 0, nullptr, nullptr);
+}
+
+int dtk_score_packed_top_text(dtk_ctx* c, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, const int64_t* text_ids,
+                              int T_text, uint64_t text_key, uint32_t flags, const int64_t* cand_ids, const int32_t* cand_len, int N,
+                              float* logprob_out, int32_t* argmax_out, float* lse_out, int k, int32_t* top_ids_out, float* top_logprob_out) {
   if (!c) return DTK_ERR_ARG;
-  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out};
+  const PackedReq rq{prefix_ids, P, cand_ids, cand_len, N, logprob_out, argmax_out, lse_out, k, top_ids_out, top_logprob_out};
   int total = 0;
   const int rc0 = packed_check(c, rq, &total);
   if (rc0 != DTK_OK) return rc0;
@@ -2896,13 +3054,24 @@ int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t
 
 int dtk_op_score(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
                  float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out) {
+  return dtk_op_score_top(c, Xn, W, targets, M, N, K, flags, logprob_out, lse_out, argmax_out, zmax_out, 0, nullptr, nullptr, nullptr);
+}
+
+int dtk_op_score_top(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
+                     float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out, int k, int32_t* top_ids_out,
+                     float* top_logprob_out, float* top_z_out) {
   if (!c || !Xn || !W || !targets || !logprob_out || M < 1 || N < 1 || K < 8 || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_score: bad argument");
+  if (k != 0 || top_ids_out || top_logprob_out || top_z_out) {
+    if (k < 1 || k > DTK_MAX_TOP || k > N) return fail(c, DTK_ERR_ARG, "dtk_op_score_top: k = %d (1 .. min(DTK_MAX_TOP = %d, N), or 0 with NULL outputs)", k, DTK_MAX_TOP);
+    if (!top_ids_out || !top_logprob_out) return fail(c, DTK_ERR_ARG, "dtk_op_score_top: k = %d needs top_ids_out and top_logprob_out", k);
+  }
   for (int m = 0; m < M; ++m)
     if (targets[m] < 0 || targets[m] >= N) return fail(c, DTK_ERR_ARG, "dtk_op_score: target %d of row %d outside [0, %d)", targets[m], m, N);
   HIPCHK(c, hipSetDevice(c->device));
   size_t off = 0;
   OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(int32_t, dT, M);
   OPBUF(float, dRec, score_rec_floats(M, N)); OPBUF(float, dO, (size_t)4 * M);
+  OPBUF(float, dTop, (size_t)3 * M * DTK_MAX_TOP);       // ids (int32), logprob, z: [M][k] each
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(dA, Xn, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
   HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
@@ -2917,6 +3086,13 @@ int dtk_op_score(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_
   }
   if (!launch_gemm_logsoftmax(g, s)) return fail(c, DTK_ERR_ARG, "dtk_op_score: the kernel does not take this shape");
   launch_score_merge(dRec, M, N, dO, dO + M, reinterpret_cast<int32_t*>(dO + 2 * (size_t)M), dO + 3 * (size_t)M, s);
+  if (k > 0) {
+    const size_t mk = (size_t)M * k;
+    launch_score_top(g, dO + M, k, reinterpret_cast<int32_t*>(dTop), dTop + mk, dTop + 2 * mk, s);
+    HIPCHK(c, hipMemcpyAsync(top_ids_out, dTop, mk * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(top_logprob_out, dTop + mk, mk * 4, hipMemcpyDeviceToHost, s));
+    if (top_z_out) HIPCHK(c, hipMemcpyAsync(top_z_out, dTop + 2 * mk, mk * 4, hipMemcpyDeviceToHost, s));
+  }
   HIPCHK(c, hipMemcpyAsync(logprob_out, dO, (size_t)M * 4, hipMemcpyDeviceToHost, s));
   if (lse_out) HIPCHK(c, hipMemcpyAsync(lse_out, dO + M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
   if (argmax_out) HIPCHK(c, hipMemcpyAsync(argmax_out, dO + 2 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, s));

@@ -78,11 +78,22 @@ struct SampleArgs {
   SampleMB* mb;          // scratch of the multi-block sampler (slot 0's in batched mode), or null
   float2* lp_ring = nullptr;   // dtk_set_option "logprobs": (logprob, sample_logprob) of the token, a ring indexed exactly as tok_ring; null = the
                                // samplers without the log-probability code (the LP = false instantiations: what ran before the option existed)
+  float* lse_ring = nullptr;   // dtk_set_option "top_logprobs" (with lp_ring): the logsumexp the logprob was taken against, indexed as lp_ring (NaN for a forced token)
 };
 void launch_sample_b(const SampleArgs& a, hipStream_t s);
 void launch_sample(const SampleArgs& a, hipStream_t s);
 // 7-kernel chain for V > 32768 (greedy / temperature / top-p; not top-k); single sequence or (a.bs) every active slot
 void launch_sample_mb(const SampleArgs& a, hipStream_t s);
+// dtk_set_option "top_logprobs": the k first entries of the pending raw logits in the order (z descending, id ascending), one block per
+// sequence / slot, launched in front of the sampler (it reads DecState and BatchState as the sampler will find them).  The record goes to
+// top_ring[draw % ring] (single sequence) or top_ring[(step % ring) * DTK_MAX_BATCH + slot] — the index of the token ring.
+struct TopArgs {
+  const float* logits; int V; int logits_stride;
+  const DecState* st; const BatchState* bs; int nslots;
+  int ring; int k;
+  TopRec* top_ring;
+};
+void launch_top_logits(const TopArgs& a, hipStream_t s);
 static inline bool sample_mb_supported(int V) { return V > 32768 && V <= DTK_SAMPLE_MB_MAX_SLICES * 8192; }
 // on the v1 vocabularies (<= 32768) the register-resident single-block kernel is as fast (ds-7b sampling decode 366.2 tok/s
 // vs 366.6 with the chain): one launch, so it stays the default there; DTK_SAMPLER=mb forces the chain for V >= 16384 (A/B)
@@ -286,6 +297,11 @@ static inline size_t score_rec_floats(int M, int N) { return (size_t)M * (size_t
 static inline bool gemm_logsoftmax_supported(int K) { return K >= 8 && (K % 8) == 0; }
 bool launch_gemm_logsoftmax(const GemmArgs& a, hipStream_t s);
 void launch_score_merge(const float* rec, int M, int N, float* logprob, float* lse, int32_t* argmax, float* zmax, hipStream_t s);
+// The k <= DTK_MAX_TOP most likely tokens of every scored row, behind launch_gemm_logsoftmax + launch_score_merge of the same a (its records
+// and the merge's lse): a row's top-k lies in the k tiles whose best elements (m, ix) come first, so only those k x 128 logits are computed
+// again — with the GEMM's own MFMA and k order, hence the same bits — and the k first of them in the order (z descending, id ascending)
+// go to top_ids / top_logprob (= z - lse) / top_z (optional), [M][k] each.  k <= N.  No [M][N] buffer.
+void launch_score_top(const GemmArgs& a, const float* lse, int k, int32_t* top_ids, float* top_logprob, float* top_z, hipStream_t s);
 
 void launch_layernorm_rows(const bf16_t* X, int ldx, const bf16_t* w, const bf16_t* b,
                            bf16_t* Y, int ldy, int M, int D, float eps, hipStream_t s);

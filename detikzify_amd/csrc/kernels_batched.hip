@@ -896,6 +896,101 @@ void launch_score_merge(const float* rec, int M, int N, float* logprob, float* l
   hipLaunchKernelGGL(k_score_merge, dim3((unsigned)M), dim3(64), 0, s, rec, (N + 127) >> 7, logprob, lse, argmax, zmax);
 }
 
+// Top-k alternatives of a scored row (launch_score_top).  One block per row, four waves.
+//   1. Wave 0 picks the nc = min(k, NT) tiles whose records' best elements (m, ix) come first in the order (z descending, id ascending):
+//      nc rounds, each the best record strictly behind the previous pick.  Every element of any other tile has nc elements in front of it
+//      (those tiles' best elements), so the row's top-k lies inside the picked tiles.
+//   2. Wave w computes the 128 logits of picked tiles w, w + 4 again: the row as all 16 rows of the MFMA's A operand, 16 lm_head rows as
+//      B, k-steps of 32 in ascending order up to the 64-wide k-tile that holds K's tail, zero-filled beyond K — the chain every GEMM
+//      kernel of this file runs per output element — then z = rbf(acc).  Columns >= N are -inf with id INT_MAX.
+//   3. Wave 0 holds the nc x 128 candidates (<= 16 per lane) and extracts the k first in k rounds of the same kind.
+__global__ __launch_bounds__(256) void k_score_top(const bf16_t* A, int lda, const bf16_t* W, int ldw, int N, int K, const float* rec,
+                                                   const float* lse, int k, int32_t* top_ids, float* top_logprob, float* top_z) {
+  __shared__ int s_tile[DTK_MAX_TOP];
+  __shared__ float s_z[DTK_MAX_TOP * 128];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int NT = (N + 127) >> 7, nc = min(k, NT);
+  if (wave == 0) {
+    const f32x4* r4 = reinterpret_cast<const f32x4*>(rec) + (size_t)row * NT;
+    float lz = __builtin_huge_valf(); int lid = -1;
+    for (int j = 0; j < nc; ++j) {
+      float bz = LS_NEG_INF; int bi = 0x7fffffff;
+      for (int t = lane; t < NT; t += 64) {
+        const f32x4 v = r4[t];
+        const int ix = __float_as_int(v[3]);
+        if (top_before(lz, lid, v[0], ix) && top_before(v[0], ix, bz, bi)) { bz = v[0]; bi = ix; }
+      }
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const float oz = __shfl_xor(bz, off, 64); const int oi = __shfl_xor(bi, off, 64);
+        if (top_before(oz, oi, bz, bi)) { bz = oz; bi = oi; }
+      }
+      lz = bz; lid = bi;
+      if (lane == 0) s_tile[j] = min(max(bi >> 7, 0), NT - 1);
+    }
+  }
+  __syncthreads();
+  const bf16_t* xr = A + (size_t)row * lda;
+  const int kend = ((K + 63) >> 6) << 6;
+  const bf16x8_t zero8 = __builtin_bit_cast(bf16x8_t, (u32x4){0u, 0u, 0u, 0u});
+  for (int j = wave; j < nc; j += 4) {
+    const int n0 = s_tile[j] << 7;
+    const bf16_t* wp[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) wp[t] = W + (size_t)min(n0 + t * 16 + (lane & 15), N - 1) * ldw;
+    f32x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < kend; k0 += 32) {
+      const int kk = k0 + (lane >> 4) * 8;
+      const bool ok = kk < K;              // K % 8 == 0: a chunk is fully in or fully out
+      const bf16x8_t xf = ok ? *reinterpret_cast<const bf16x8_t*>(xr + kk) : zero8;
+      bf16x8_t wf[8];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) wf[t] = ok ? *reinterpret_cast<const bf16x8_t*>(wp[t] + kk) : zero8;
+#pragma unroll
+      for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, wf[t], acc[t], 0, 0, 0);
+    }
+    if (lane < 16) {                       // C/D layout: register 0 of lanes 0..15 = row 0, column lane
+#pragma unroll
+      for (int t = 0; t < 8; ++t) s_z[j * 128 + t * 16 + lane] = (n0 + t * 16 + lane) < N ? rbf(acc[t][0]) : LS_NEG_INF;
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  float cz[2 * DTK_MAX_TOP]; int ci[2 * DTK_MAX_TOP];
+#pragma unroll
+  for (int i = 0; i < 2 * DTK_MAX_TOP; ++i) {
+    cz[i] = LS_NEG_INF; ci[i] = 0x7fffffff;
+    if (i < 2 * nc) {
+      const int n = (s_tile[i >> 1] << 7) + ((lane + 64 * i) & 127);
+      if (n < N) { cz[i] = s_z[lane + 64 * i]; ci[i] = n; }
+    }
+  }
+  const float e = lse[row];
+  float lz = __builtin_huge_valf(); int lid = -1;
+  for (int j = 0; j < k; ++j) {
+    float bz = LS_NEG_INF; int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < 2 * DTK_MAX_TOP; ++i)
+      if (top_before(lz, lid, cz[i], ci[i]) && top_before(cz[i], ci[i], bz, bi)) { bz = cz[i]; bi = ci[i]; }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float oz = __shfl_xor(bz, off, 64); const int oi = __shfl_xor(bi, off, 64);
+      if (top_before(oz, oi, bz, bi)) { bz = oz; bi = oi; }
+    }
+    lz = bz; lid = bi;
+    if (lane == 0) {
+      top_ids[(size_t)row * k + j] = bi;
+      top_logprob[(size_t)row * k + j] = bz - e;
+      if (top_z) top_z[(size_t)row * k + j] = bz;
+    }
+  }
+}
+void launch_score_top(const GemmArgs& a, const float* lse, int k, int32_t* top_ids, float* top_logprob, float* top_z, hipStream_t s) {
+  hipLaunchKernelGGL(k_score_top, dim3((unsigned)a.M), dim3(256), 0, s, a.A, a.lda, a.W, a.ldw, a.N, a.K, a.ls_rec, lse, k, top_ids, top_logprob, top_z);
+}
+
 // Partials added in slice order (fp32), the GEMM epilogue, the row stored as bf16; then — norm_w — the HF RMSNorm of the stored row.  1024
 // threads = 4096 columns of one row per pass, every slice's 16 bytes requested before the first add (S x 16 KiB in flight per block): without
 // a norm the grid is (row, 4096-column chunk); with one a block owns its whole row (fp32 sum of squares: per thread over its columns in

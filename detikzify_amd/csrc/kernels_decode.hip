@@ -1054,6 +1054,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;        // the ring index was applied above
     a.step_override = -1;
   }
@@ -1288,6 +1289,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     if constexpr (LP)      // a forced token was not sampled: NaN, NaN
       a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
                                                                    : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
+    if constexpr (LP) if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? __builtin_nanf("") : lm + logf(ls);
     if (a.advance) {
       a.st->token = tok;
       a.st->pos = a.st->next_pos;
@@ -1326,6 +1328,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;
     a.step_override = -1;
   }
@@ -1574,6 +1577,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     if constexpr (LP)      // a forced token was not sampled: NaN, NaN
       a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
                                                                    : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
+    if constexpr (LP) if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? __builtin_nanf("") : lm + logf(ls);
     if (a.advance) {
       a.st->token = tok;
       a.st->pos = a.st->next_pos;
@@ -1590,6 +1594,56 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 }
 #undef key
 #undef q_
+
+// dtk_set_option "top_logprobs": the k first entries of the pending RAW logits (no suppression list, no temperature) in the order
+// (z descending, id ascending), launched in front of the sampler.  k rounds; a round is the best element strictly behind the previous
+// pick: every thread walks its strided share of the row (the row stays in L2 between rounds), a butterfly per wave, the 16 waves' picks
+// through LDS.  Exact in any order, so the result does not depend on the thread count.
+#define TOP_THREADS 1024
+__global__ __launch_bounds__(TOP_THREADS) void k_top_logits(TopArgs a) {
+  const float* z = a.logits;
+  const DecState* st = a.st;
+  TopRec* out;
+  if (a.bs) {
+    const int slot = blockIdx.x;
+    if (!a.bs->active[slot]) return;
+    z += (size_t)slot * a.logits_stride;
+    st += slot;
+    out = a.top_ring + (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+  } else out = a.top_ring + st->draw % (uint32_t)a.ring;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (st->force_plus1 > 0) {          // a forced token was not sampled from these (stale) logits
+    if (tid < a.k) { out->id[tid] = -1; out->z[tid] = __builtin_nanf(""); }
+    return;
+  }
+  __shared__ float s_z[TOP_THREADS / 64];
+  __shared__ int s_i[TOP_THREADS / 64];
+  float lz = INFINITY; int lid = -1;
+  for (int j = 0; j < a.k; ++j) {
+    float bz = -INFINITY; int bi = 0x7fffffff;
+    for (int i = tid; i < a.V; i += TOP_THREADS) {
+      const float v = z[i];
+      if (top_before(lz, lid, v, i) && top_before(v, i, bz, bi)) { bz = v; bi = i; }
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float oz = __shfl_xor(bz, off, 64); const int oi = __shfl_xor(bi, off, 64);
+      if (top_before(oz, oi, bz, bi)) { bz = oz; bi = oi; }
+    }
+    if (lane == 0) { s_z[wave] = bz; s_i[wave] = bi; }
+    __syncthreads();
+    bz = s_z[0]; bi = s_i[0];
+#pragma unroll
+    for (int w = 1; w < TOP_THREADS / 64; ++w)
+      if (top_before(s_z[w], s_i[w], bz, bi)) { bz = s_z[w]; bi = s_i[w]; }
+    __syncthreads();
+    lz = bz; lid = bi;
+    if (tid == 0) { out->id[j] = bi; out->z[j] = bz; }
+  }
+}
+void launch_top_logits(const TopArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_top_logits, dim3(a.bs ? a.nslots : 1), dim3(TOP_THREADS), 0, s, a);
+}
 
 static bool sample_fast_ok(const SampleArgs& a) {
   static int force_generic = -1;

@@ -43,6 +43,7 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
     a.x += (size_t)slot * a.d;
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if (a.lp_ring) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     a.ring = 1;
     a.step_override = -1;
     a.mb += slot;
@@ -380,12 +381,15 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
     a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
     if constexpr (LP) {
       float2 lp = make_float2(__builtin_nanf(""), __builtin_nanf(""));      // a forced token was not sampled
+      float e = __builtin_nanf("");
       if (forced <= 0) {
         float lm = a.mb->lmax[0], ls = a.mb->lsum[0];
         for (int k = 1; k < nblk; ++k) lse_merge(lm, ls, a.mb->lmax[k], a.mb->lsum[k]);
         lp = lp_pair(a.logits[tok], lm, ls, sampling, sampling ? s_tokq : 0u, kept);
+        e = lm + logf(ls);
       }
       a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = lp;
+      if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = e;
     }
     if (a.advance) {
       a.st->token = tok;

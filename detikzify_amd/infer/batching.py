@@ -169,7 +169,7 @@ class BatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, text_ids=None,
-                 logprobs: bool = False, **_native_only) -> Iterator[_Sequence]:
+                 logprobs: bool = False, top_logprobs: Optional[int] = None, **_native_only) -> Iterator[_Sequence]:
         """`owner`: whoever starts sequence after sequence (an MCTS tree: generate(sequence_owner=t)) — a join that cannot
         resume takes the slot its owner used last, so it does not overwrite a rollout ANOTHER owner may come back to.
         `text_ids`: one unpadded text that conditions the tower (the adapter; pixel_values None = its dummy image): the slot's prefix is
@@ -178,6 +178,8 @@ class BatchEngine:
         sequence switches the device over (model.enable_logprobs()), which is done before the first join, not while other sequences
         hold slots.
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
+        if top_logprobs:
+            raise NotImplementedError("top_logprobs: not in the batch engines yet")
         from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_image_key, text_key
         tids = adapter_text(text_ids) if text_ids is not None else None
         tkey = text_key(tids) if tids is not None else 0

@@ -350,13 +350,16 @@ class NativeBatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None, logprobs: bool = False) -> Iterator[_NativeSequence]:
+                 stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None, logprobs: bool = False,
+                 top_logprobs: Optional[int] = None) -> Iterator[_NativeSequence]:
         """`owner`: see BatchEngine.sequence.  `max_new_tokens` / `stop_ids`: the sequence's own end (the native loop stops it there);
         `per_token`: the reader is woken for every token (arbitrary stopping criteria / foreign streamers) instead of per line.
         `text_ids`: one unpadded text that conditions the tower (the adapter); pixel_values may then be None (the dummy image).
         `logprobs`: the sequence collects its tokens' (logprob, sample_logprob) in `.logprobs` / `.sample_logprobs`.  The first such
         sequence switches the device over, which needs every slot free: ask for it before other sequences join (or call
         model.enable_logprobs() before the engine is built)."""
+        if top_logprobs:
+            raise NotImplementedError("top_logprobs: not in the batch engines yet")
         if not self._h:
             raise _lib.DtkError("the batch engine is closed")
         from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_key

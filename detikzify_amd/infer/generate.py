@@ -188,19 +188,27 @@ class DetikzifyGenerator:
 
     __call__ = simulate         # a generator object is callable like its simulate()
 
-    def sample(self, return_logprobs: bool = False) -> TikzDocument:
+    def sample(self, return_logprobs: bool = False, top_logprobs: Optional[int] = None) -> TikzDocument:
         """return_logprobs: the document carries `.token_logprobs` / `.token_sample_logprobs`, one float per generated token (EOS
-        included): the model's log-probability of the token and the log of the probability the sampler drew it with"""
+        included): the model's log-probability of the token and the log of the probability the sampler drew it with.  top_logprobs=k
+        (with return_logprobs): + `.token_top_ids` / `.token_top_logprobs`, per generated token the k most likely tokens at its position"""
+        from ..model.modeling import check_top_logprobs
+        topk = check_top_logprobs(top_logprobs, return_logprobs)
         if not return_logprobs:
             return self.decode(self.generate(input_ids=self.montecarlo.root_node.token_ids))
-        out = self.generate(input_ids=self.montecarlo.root_node.token_ids, return_logprobs=True)
+        out = self.generate(input_ids=self.montecarlo.root_node.token_ids, return_logprobs=True, **({"top_logprobs": topk} if topk else {}))
         if not hasattr(out, "sequences"):       # self.generate returned the prompt itself, without a model call (it ends in EOS / fills the budget)
             document = self.decode(out)
             document.token_logprobs, document.token_sample_logprobs = [], []
+            if topk:
+                document.token_top_ids, document.token_top_logprobs = [], []
             return document
         document = self.decode(out.sequences.squeeze(0))
         document.token_logprobs = [float(v) for v in out.logprobs[0]]
         document.token_sample_logprobs = [float(v) for v in out.sample_logprobs[0]]
+        if topk:
+            document.token_top_ids = [[int(v) for v in row] for row in out.top_ids[0]]
+            document.token_top_logprobs = [[float(v) for v in row] for row in out.top_logprobs[0]]
         return document
 
     # ---- a·G: one call of the model ------------------------------------------------------------------------------------

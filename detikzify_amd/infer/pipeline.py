@@ -53,17 +53,23 @@ class DetikzifyPipeline:
             text=text, **{**self.gen_kwargs, **kw})
 
     def sample(self, image=None, text: Optional[str] = None, preprocess: bool = True, return_logprobs: bool = False,
-               **gen_kwargs) -> TikzDocument:
+               top_logprobs: Optional[int] = None, **gen_kwargs) -> TikzDocument:
         """One sampled TikZ program for the image.  return_logprobs=True attaches `.token_logprobs` and `.token_sample_logprobs` to
         the document: per generated token (EOS included) the model's log-probability of it — comparable with score() — and the log
-        of the probability the sampler (temperature, top-k, top-p) chose it with."""
-        return self._generator(image, text, preprocess, **gen_kwargs).sample(return_logprobs=return_logprobs)
+        of the probability the sampler (temperature, top-k, top-p) chose it with.  top_logprobs=k (1 .. 8, with return_logprobs=True)
+        also attaches `.token_top_ids` / `.token_top_logprobs`: per generated token the k most likely tokens at its position."""
+        from ..model.modeling import check_top_logprobs
+        check_top_logprobs(top_logprobs, return_logprobs)
+        return self._generator(image, text, preprocess, **gen_kwargs).sample(return_logprobs=return_logprobs, top_logprobs=top_logprobs)
 
-    def score(self, image=None, code: str = "", text: Optional[str] = None, preprocess: bool = True) -> Tuple[float, List[float]]:
+    def score(self, image=None, code: str = "", text: Optional[str] = None, preprocess: bool = True, top_logprobs: Optional[int] = None):
         """(log-probability of `code`, its per-token log-probabilities) under the model, after the prompt sample() builds for
         (image, text).  `code` is tokenised as the generator's output would be — no special tokens, EOS appended — and scored in one
-        teacher-forced pass (model.score)."""
+        teacher-forced pass (model.score).  top_logprobs=k: a third and fourth element, per token the k most likely token ids at its
+        position and their log-probabilities."""
         import torch
+        from ..model.modeling import check_top_logprobs
+        check_top_logprobs(top_logprobs)
         self.check_inputs(image, text)
         tokenizer = unwrap(self.processor).tokenizer
         features = self.processor(images=self.load(image, preprocess=preprocess) if image is not None else None, text=text,
@@ -72,15 +78,21 @@ class DetikzifyPipeline:
         program = list(tokenizer.encode(code, add_special_tokens=False)) + [int(tokenizer.eos_token_id)]
         ids = torch.cat([prompt, torch.tensor(program, dtype=torch.int64)])
         conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}     # as DetikzifyGenerator.generate
-        out = self.model.score(ids, features.get("pixel_values"), first=prompt.numel(), **conditioning)
+        top = {"top_logprobs": top_logprobs} if top_logprobs else {}
+        out = self.model.score(ids, features.get("pixel_values"), first=prompt.numel(), **conditioning, **top)
         per_token = [float(v) for v in out.logprobs]
+        if top:
+            return float(out.logprobs.sum(dtype=torch.float64)), per_token, out.top_ids.tolist(), out.top_logprobs.tolist()
         return float(out.logprobs.sum(dtype=torch.float64)), per_token
 
     def score_candidates(self, image=None, codes: List[str] = (), text: Optional[str] = None,
-                         preprocess: bool = True) -> List[Tuple[float, List[float]]]:
+                         preprocess: bool = True, top_logprobs: Optional[int] = None) -> List[Tuple]:
         """score() of every program in `codes` for one (image, text) — same prompt, same tokenisation (no special tokens, EOS
-        appended) — from one packed pass over all of them (model.score_candidates); one (sum, per-token) pair per code, in order."""
+        appended) — from one packed pass over all of them (model.score_candidates); one (sum, per-token) pair per code, in order
+        (with top_logprobs=k: the four elements score() returns)."""
         import torch
+        from ..model.modeling import check_top_logprobs
+        check_top_logprobs(top_logprobs)
         self.check_inputs(image, text)
         tokenizer = unwrap(self.processor).tokenizer
         features = self.processor(images=self.load(image, preprocess=preprocess) if image is not None else None, text=text,
@@ -89,7 +101,11 @@ class DetikzifyPipeline:
         programs = [torch.tensor(list(tokenizer.encode(code, add_special_tokens=False)) + [int(tokenizer.eos_token_id)], dtype=torch.int64)
                     for code in codes]
         conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}     # as DetikzifyGenerator.generate
-        outs = self.model.score_candidates(prompt, programs, features.get("pixel_values"), **conditioning)
+        top = {"top_logprobs": top_logprobs} if top_logprobs else {}
+        outs = self.model.score_candidates(prompt, programs, features.get("pixel_values"), **conditioning, **top)
+        if top:
+            return [(float(o.logprobs.sum(dtype=torch.float64)), [float(v) for v in o.logprobs], o.top_ids.tolist(), o.top_logprobs.tolist())
+                    for o in outs]
         return [(float(o.logprobs.sum(dtype=torch.float64)), [float(v) for v in o.logprobs]) for o in outs]
 
     def simulate(self, image=None, text: Optional[str] = None, preprocess: bool = True,

@@ -143,10 +143,26 @@ class GenerateOutput:
     """generate(return_logprobs=True): `.sequences` is what generate() returns without the flag; `.logprobs[0, i]` is the model's
     log-probability of new token i (z[t] - logsumexp(z) over the raw logits: what model.score reports for that position),
     `.sample_logprobs[0, i]` the log of the probability with which the sampler drew it (after the suppression lists, temperature,
-    top-k and top-p; 0 for greedy).  Both [1, new_tokens] float32 on the CPU."""
+    top-k and top-p; 0 for greedy).  Both [1, new_tokens] float32 on the CPU.  With top_logprobs=k also `.top_ids` (int64) and
+    `.top_logprobs` (float32), [1, new_tokens, k]: the k most likely tokens of the raw logits each new token was sampled from, most
+    likely first (lower id first on ties), and their log-probabilities; None without the argument."""
 
-    def __init__(self, sequences: torch.Tensor, logprobs: torch.Tensor, sample_logprobs: torch.Tensor):
+    def __init__(self, sequences: torch.Tensor, logprobs: torch.Tensor, sample_logprobs: torch.Tensor,
+                 top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None):
         self.sequences, self.logprobs, self.sample_logprobs = sequences, logprobs, sample_logprobs
+        self.top_ids, self.top_logprobs = top_ids, top_logprobs
+
+
+def check_top_logprobs(top_logprobs: Optional[int], return_logprobs: bool = True) -> int:
+    """the `top_logprobs` argument of score / generate / sample -> k (0 = not asked for); ValueError before anything runs"""
+    if top_logprobs is None:
+        return 0
+    if not return_logprobs:
+        raise ValueError("top_logprobs needs return_logprobs=True")
+    k = int(top_logprobs)
+    if not 1 <= k <= _lib.DTK_MAX_TOP:
+        raise ValueError(f"top_logprobs = {top_logprobs}: 1 .. {_lib.DTK_MAX_TOP}")
+    return k
 
 
 def _is_neutral(value: Any, neutral: Any) -> bool:
@@ -563,10 +579,12 @@ class DetikzifyForCausalLM:
 
     def score(self, input_ids: torch.Tensor, pixel_values: Optional[torch.Tensor] = None, first: Optional[int] = None,
               adapter_input_ids: Optional[torch.Tensor] = None, reuse: Optional[bool] = None,
-              adapter_attention_mask: Optional[torch.Tensor] = None) -> ScoreOutput:
+              adapter_attention_mask: Optional[torch.Tensor] = None, top_logprobs: Optional[int] = None) -> ScoreOutput:
         """log p(ids[t] | ids[:t], image) for t = first .. T-1 in one prefill-sized pass (dtk_score): the lm_head runs over all
         scored rows with the log-softmax folded into its epilogue, no [T, V] logits exist.  Leaves the model as prefill() of the
-        same arguments does (decode may continue).  first=None: the token after the last image token, or 1."""
+        same arguments does (decode may continue).  first=None: the token after the last image token, or 1.  top_logprobs=k
+        (1 .. 8): + .top_ids int64 / .top_logprobs float32, [T - first, k]: every scored position's k most likely tokens."""
+        k = check_top_logprobs(top_logprobs)
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
         self._refuse_while_batch_busy("score")
@@ -600,28 +618,38 @@ class DetikzifyForCausalLM:
         n = max(T - first, 1)
         lp, am, lse = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float32)
         outs = (int(first), lp.ctypes.data_as(C.c_void_p), am.ctypes.data_as(C.c_void_p), lse.ctypes.data_as(C.c_void_p))
+        top_i, top_l = np.empty((n, k), dtype=np.int32), np.empty((n, k), dtype=np.float32)
+        tops = (k, top_i.ctypes.data_as(C.c_void_p), top_l.ctypes.data_as(C.c_void_p))
         idp = ids.numpy().ctypes.data_as(C.c_void_p)
         if not self._single_busy.acquire(blocking=False):
             raise _lib.DtkError("score() while a generate() decodes on this model's single sequence")
         try:
             with self._vit_lock:
-                if tids is None:
+                if tids is None and k:
+                    self._check(self.lib.dtk_score_top(self._ctx, idp, T, px_ptr, C.c_uint64(key), C.c_uint32(flags), *outs, *tops), "dtk_score_top")
+                elif k:
+                    self._check(self.lib.dtk_score_top_text(self._ctx, idp, T, px_ptr, C.c_uint64(key), tids.numpy().ctypes.data_as(C.c_void_p),
+                                                            tids.numel(), C.c_uint64(text_key(tids)), C.c_uint32(flags), *outs, *tops),
+                                "dtk_score_top_text")
+                elif tids is None:
                     self._check(self.lib.dtk_score(self._ctx, idp, T, px_ptr, C.c_uint64(key), C.c_uint32(flags), *outs), "dtk_score")
                 else:
                     self._check(self.lib.dtk_score_text(self._ctx, idp, T, px_ptr, C.c_uint64(key), tids.numpy().ctypes.data_as(C.c_void_p),
                                                         tids.numel(), C.c_uint64(text_key(tids)), C.c_uint32(flags), *outs), "dtk_score_text")
         finally:
             self._single_busy.release()
-        return ScoreOutput(logprobs=torch.from_numpy(lp), argmax=torch.from_numpy(am).to(torch.int64), lse=torch.from_numpy(lse), first=first)
+        return ScoreOutput(logprobs=torch.from_numpy(lp), argmax=torch.from_numpy(am).to(torch.int64), lse=torch.from_numpy(lse), first=first,
+                           top_ids=torch.from_numpy(top_i).to(torch.int64) if k else None, top_logprobs=torch.from_numpy(top_l) if k else None)
 
     def score_candidates(self, prefix_ids: torch.Tensor, candidates: Sequence[Any], pixel_values: Optional[torch.Tensor] = None,
                          adapter_input_ids: Optional[torch.Tensor] = None, adapter_attention_mask: Optional[torch.Tensor] = None,
-                         reuse: Optional[bool] = None) -> List[ScoreOutput]:
+                         reuse: Optional[bool] = None, top_logprobs: Optional[int] = None) -> List[ScoreOutput]:
         """score(prefix + candidate, first=len(prefix)) for every candidate of one prompt, in input order, from ONE pass of the
         decoder over all candidates' rows (dtk_score_packed): the weights stream once, each candidate attends to the prompt and to
         itself.  Candidates that do not fit one pass (P - 1 + sum of lengths <= max_positions) are split by plan_packed_passes();
         the later passes reuse the prompt's cache.  Leaves the prompt's first P-1 positions cached and NO sequence to decode from:
-        prefill() before decode_launch()."""
+        prefill() before decode_launch().  top_logprobs=k: as in score(), per candidate."""
+        topk = check_top_logprobs(top_logprobs)
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
         self._refuse_while_batch_busy("score_candidates")
@@ -669,8 +697,18 @@ class DetikzifyForCausalLM:
                 flags = reuse_flags if (reuse or k > 0) else 0       # a later pass always continues the first one's prompt
                 tail = (ids.numpy().ctypes.data_as(C.c_void_p), clen.ctypes.data_as(C.c_void_p), len(members),
                         lp.ctypes.data_as(C.c_void_p), am.ctypes.data_as(C.c_void_p), lse.ctypes.data_as(C.c_void_p))
+                top_i, top_l = np.empty((n, topk), dtype=np.int32), np.empty((n, topk), dtype=np.float32)
+                tops = (topk, top_i.ctypes.data_as(C.c_void_p), top_l.ctypes.data_as(C.c_void_p))
                 with self._vit_lock:
-                    if tids is None:
+                    if tids is None and topk:
+                        self._check(self.lib.dtk_score_packed_top(self._ctx, pfx, P, px_ptr, C.c_uint64(key), C.c_uint32(flags), *tail, *tops),
+                                    "dtk_score_packed_top")
+                    elif topk:
+                        self._check(self.lib.dtk_score_packed_top_text(self._ctx, pfx, P, px_ptr, C.c_uint64(key),
+                                                                       tids.numpy().ctypes.data_as(C.c_void_p), tids.numel(),
+                                                                       C.c_uint64(text_key(tids)), C.c_uint32(flags), *tail, *tops),
+                                    "dtk_score_packed_top_text")
+                    elif tids is None:
                         self._check(self.lib.dtk_score_packed(self._ctx, pfx, P, px_ptr, C.c_uint64(key), C.c_uint32(flags), *tail),
                                     "dtk_score_packed")
                     else:
@@ -681,7 +719,9 @@ class DetikzifyForCausalLM:
                 for i in members:
                     hi = lo + lens[i]
                     out.append(ScoreOutput(logprobs=torch.from_numpy(lp[lo:hi].copy()), argmax=torch.from_numpy(am[lo:hi]).to(torch.int64),
-                                           lse=torch.from_numpy(lse[lo:hi].copy()), first=P))
+                                           lse=torch.from_numpy(lse[lo:hi].copy()), first=P,
+                                           top_ids=torch.from_numpy(top_i[lo:hi]).to(torch.int64) if topk else None,
+                                           top_logprobs=torch.from_numpy(top_l[lo:hi].copy()) if topk else None))
                     lo = hi
         finally:
             self._single_busy.release()
@@ -759,8 +799,17 @@ class DetikzifyForCausalLM:
             arr[int(j)] = 1
         self._check(self.lib.dtk_decode_batch_launch(self._ctx, arr), "dtk_decode_batch_launch")
 
-    def decode_batch_wait(self) -> List[int]:
+    def decode_batch_wait(self, top: bool = False):
+        """every slot's token of the oldest unread step (-1: took no part).  top=True (needs enable_top_logprobs(k)): (tokens, logprobs,
+        sample_logprobs, top_ids, top_logprobs), the last two one list of k entries per slot ((-1, NaN) entries where there is no token)"""
         out = (C.c_int64 * _lib.DTK_MAX_BATCH)()
+        if top:
+            lp, slp = (C.c_float * _lib.DTK_MAX_BATCH)(), (C.c_float * _lib.DTK_MAX_BATCH)()
+            n, k = _lib.DTK_MAX_BATCH * _lib.DTK_MAX_TOP, self.top_logprobs_enabled
+            ti, tl = (C.c_int32 * n)(), (C.c_float * n)()
+            self._check(self.lib.dtk_decode_batch_wait_top(self._ctx, out, lp, slp, ti, tl), "dtk_decode_batch_wait_top")
+            rows = [slice(j * _lib.DTK_MAX_TOP, j * _lib.DTK_MAX_TOP + k) for j in range(_lib.DTK_MAX_BATCH)]
+            return [int(v) for v in out], list(lp), list(slp), [list(ti[r]) for r in rows], [list(tl[r]) for r in rows]
         self._check(self.lib.dtk_decode_batch_wait(self._ctx, out), "dtk_decode_batch_wait")
         return [int(v) for v in out]
 
@@ -782,6 +831,22 @@ class DetikzifyForCausalLM:
         if not self.logprobs_enabled:
             self.set_option("logprobs", 1)
             self._logprobs = True
+
+    @property
+    def top_logprobs_enabled(self) -> int:
+        return int(getattr(self, "_top_logprobs", 0))
+
+    def enable_top_logprobs(self, k: int) -> None:
+        """every decode step from here on also leaves the k (1 .. 8; 0: none again) most likely tokens of the logits it sampled from:
+        decode_wait(top=True) / decode_batch_wait(top=True).  Switches the log-probabilities on if needed; refused where they are."""
+        k = int(k)
+        if not 0 <= k <= _lib.DTK_MAX_TOP:
+            raise ValueError(f"top_logprobs = {k}: 0 .. {_lib.DTK_MAX_TOP}")
+        if k:
+            self.enable_logprobs()
+        if k != self.top_logprobs_enabled:
+            self.set_option("top_logprobs", k)
+            self._top_logprobs = k
 
     def kv_fork(self, src_slot: int, dst_slot: int, n_tokens: int):
         self._check(self.lib.dtk_kv_fork(self._ctx, int(src_slot), int(dst_slot), int(n_tokens)), "dtk_kv_fork")
@@ -848,8 +913,15 @@ class DetikzifyForCausalLM:
     def decode_launch(self):
         self._check(self.lib.dtk_decode_launch(self._ctx), "dtk_decode_launch")
 
-    def decode_wait(self) -> int:
+    def decode_wait(self, top: bool = False):
+        """the token of the oldest unread step.  top=True (needs enable_top_logprobs(k)): (token, logprob, sample_logprob, top_ids,
+        top_logprobs), the last two lists of k entries ((-1, NaN) for a forced token)"""
         tok = C.c_int64()
+        if top:
+            lp, k = (C.c_float * 2)(), self.top_logprobs_enabled
+            ti, tl = (C.c_int32 * _lib.DTK_MAX_TOP)(), (C.c_float * _lib.DTK_MAX_TOP)()
+            self._check(self.lib.dtk_decode_wait_top(self._ctx, C.byref(tok), lp, ti, tl), "dtk_decode_wait_top")
+            return int(tok.value), float(lp[0]), float(lp[1]), list(ti[:k]), list(tl[:k])
         self._check(self.lib.dtk_decode_wait(self._ctx, C.byref(tok)), "dtk_decode_wait")
         return int(tok.value)
 
@@ -892,7 +964,7 @@ class DetikzifyForCausalLM:
                  top_k: Optional[int] = None, max_length: Optional[int] = None,
                  max_new_tokens: Optional[int] = None, eos_token_id=None, seed: Optional[int] = None,
                  inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, return_logprobs: bool = False,
-                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 top_logprobs: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -900,11 +972,13 @@ class DetikzifyForCausalLM:
 
         return_logprobs=True (not an HF argument; HF's output_scores / compute_transition_scores stay refused) returns a
         GenerateOutput instead: the same tensor as `.sequences` plus the per-token `.logprobs` / `.sample_logprobs` the sampler
-        kernel formed on its way (enable_logprobs(): switched on for this call if needed, and left on).
+        kernel formed on its way (enable_logprobs(): switched on for this call if needed, and left on).  top_logprobs=k (1 .. 8,
+        with return_logprobs=True): + `.top_ids` / `.top_logprobs`, the k most likely tokens at every new position; not in the batch engines.  The option is on for this call only.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
         unknown names — raises instead of being dropped: a drop-in must not silently decode something else."""
+        topk = check_top_logprobs(top_logprobs, return_logprobs)
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
         text_ids = None
@@ -963,6 +1037,7 @@ class DetikzifyForCausalLM:
         heavy = [c for c in criteria if type(c) is not ExplicitAbort]
         new_tokens: List[int] = []
         pairs: Tuple[List[float], List[float]] = ([], [])      # return_logprobs: one pair per delivered token (trimmed to new_tokens)
+        tops: Tuple[List[List[int]], List[List[float]]] = ([], [])      # top_logprobs: k ids and k log-probabilities per delivered token
 
         def emit(tok: int) -> bool:
             nonlocal cur
@@ -1025,7 +1100,7 @@ class DetikzifyForCausalLM:
                     do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, bad_ids=bad,
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or ()),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
-                    **({"logprobs": True} if return_logprobs else {})) as seq:
+                    **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
                 if return_logprobs:
                     pairs = (seq.logprobs, seq.sample_logprobs)
@@ -1036,11 +1111,14 @@ class DetikzifyForCausalLM:
             if not self._single_busy.acquire(blocking=False):
                 raise _lib.DtkError("concurrent generate() calls on one model: decode them as a batch "
                                     "(detikzify_amd.infer.batching.BatchEngine / simulate_parallel)")
+            launched = received = 0
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or ())
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
+                    if topk:
+                        self.enable_top_logprobs(topk)
                 if text_ids is not None:
                     self.prefill(ids[0], pixel_values, adapter_input_ids=text_ids)
                 else:
@@ -1051,7 +1129,10 @@ class DetikzifyForCausalLM:
                 while launched < min(ahead, n_new_max):
                     self.decode_launch(); launched += 1
                 while received < launched:
-                    if return_logprobs:
+                    if topk:
+                        tok, lp, slp, ti, tl = self.decode_wait(top=True)
+                        pairs[0].append(lp); pairs[1].append(slp); tops[0].append(ti); tops[1].append(tl)
+                    elif return_logprobs:
                         tok, lp, slp = self.decode_wait_lp()
                         pairs[0].append(lp); pairs[1].append(slp)
                     else:
@@ -1063,7 +1144,14 @@ class DetikzifyForCausalLM:
                     if launched < n_new_max:
                         self.decode_launch(); launched += 1
             finally:
-                self._single_busy.release()
+                try:
+                    if topk:        # the call that asked for the alternatives switches them off again: later steps run without the extra kernel
+                        self.synchronize()
+                        while received < launched:      # (a step left in flight behind the last token: the switch refuses unread steps)
+                            self.decode_wait(); received += 1
+                        self.enable_top_logprobs(0)
+                finally:
+                    self._single_busy.release()
         if streamer is not None:
             streamer.end()
         if new_tokens:
@@ -1071,5 +1159,7 @@ class DetikzifyForCausalLM:
         if return_logprobs:       # (an engine may have delivered pairs of tokens past the sequence's end: the first len(new_tokens) are its own)
             n = len(new_tokens)
             return GenerateOutput(buf[:, :cur].clone(), torch.tensor(pairs[0][:n], dtype=torch.float32)[None],
-                                  torch.tensor(pairs[1][:n], dtype=torch.float32)[None])
+                                  torch.tensor(pairs[1][:n], dtype=torch.float32)[None],
+                                  torch.tensor(tops[0][:n], dtype=torch.int64).reshape(1, n, topk) if topk else None,
+                                  torch.tensor(tops[1][:n], dtype=torch.float32).reshape(1, n, topk) if topk else None)
         return buf[:, :cur].clone()

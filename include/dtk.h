@@ -559,6 +559,45 @@ int  dtk_engine_set_wait_lp_op(dtk_engine* e, int (*wait_lp)(void* dev, int64_t*
 int  dtk_op_sample_lp(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
                       float* lp_out /* [2] */);
 
+/* Top-k alternatives (additive, ABI 7): the k <= DTK_MAX_TOP most likely tokens of a position next to the one token the calls above
+ * report.  For raw logits z[0 .. V) — the bf16-rounded values of the scoring lm_head, or the fp32 row a decode step samples from;
+ * before suppression lists, temperature, top-k and top-p — the vocabulary is ordered by z descending, token id ascending on exact ties;
+ * top-k = the first k entries as (id, logprob = z[id] - logsumexp(z)), with the logsumexp of the call's own lse / logprob.  Entry 0 is
+ * the call's argmax; an entry whose id is the target (or the sampled token) carries that token's logprob, bit for bit.  1 <= k <= V.
+ *   dtk_score_top, dtk_score_packed_top (+ _text)   the call without `_top` + k, top_ids_out, top_logprob_out ([rows][k], rows as
+ *                             logprob_out).  k = 0 with both NULL is exactly the call without `_top`.  No [T][V] buffer: a selection
+ *                             kernel picks, from the log-softmax records, the k 128-column tiles whose best elements come first and
+ *                             computes only their logits again (same MFMA chain, same bits).
+ *   dtk_op_score_top          dtk_op_score + the same, + top_z_out (the entries' z; may be NULL); k <= N
+ *   dtk_set_option(ctx, "top_logprobs", k)   default 0, per context; needs "logprobs" = 1 (which cannot be switched off while k > 0); a change
+ *                             of value is refused in the states that refuse "logprobs" and drops the captured decode graphs.  Every decode
+ *                             step then runs one more kernel in front of its sampler and two more D2H copies; with 0 the steps are what
+ *                             they are without the option.
+ *   dtk_decode_wait_top       dtk_decode_wait_lp + top_ids_out / top_logprob_out [DTK_MAX_TOP]: entries >= k are (-1, NaN); a forced
+ *                             token has (-1, NaN) throughout
+ *   dtk_decode_batch_wait_top dtk_decode_batch_wait_lp + [DTK_MAX_BATCH][DTK_MAX_TOP] of the same; (-1, NaN) for slots that took no part
+ * The engines of dtk_engine_create* do not deliver them (dtk_engine_read's record is unchanged). */
+#define DTK_MAX_TOP 8
+int  dtk_score_top(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags, int first,
+                   float* logprob_out, int32_t* argmax_out, float* lse_out, int k, int32_t* top_ids_out, float* top_logprob_out);
+int  dtk_score_top_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, const int64_t* text_ids, int T_text,
+                        uint64_t text_key, uint32_t flags, int first, float* logprob_out, int32_t* argmax_out, float* lse_out,
+                        int k, int32_t* top_ids_out, float* top_logprob_out);
+int  dtk_score_packed_top(dtk_ctx* ctx, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, uint32_t flags,
+                          const int64_t* cand_ids, const int32_t* cand_len, int N, float* logprob_out, int32_t* argmax_out, float* lse_out,
+                          int k, int32_t* top_ids_out, float* top_logprob_out);
+int  dtk_score_packed_top_text(dtk_ctx* ctx, const int64_t* prefix_ids, int P, const float* pixels, uint64_t image_key, const int64_t* text_ids,
+                               int T_text, uint64_t text_key, uint32_t flags, const int64_t* cand_ids, const int32_t* cand_len, int N,
+                               float* logprob_out, int32_t* argmax_out, float* lse_out, int k, int32_t* top_ids_out, float* top_logprob_out);
+int  dtk_op_score_top(dtk_ctx* ctx, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
+                      float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out, int k, int32_t* top_ids_out,
+                      float* top_logprob_out, float* top_z_out);
+int  dtk_decode_wait_top(dtk_ctx* ctx, int64_t* token_out, float* lp_out /* [2] */, int32_t* top_ids_out /* [DTK_MAX_TOP] */,
+                         float* top_logprob_out /* [DTK_MAX_TOP] */);
+int  dtk_decode_batch_wait_top(dtk_ctx* ctx, int64_t* tokens_out /* [DTK_MAX_BATCH] */, float* logprob_out /* [DTK_MAX_BATCH] */,
+                               float* sample_logprob_out /* [DTK_MAX_BATCH] */, int32_t* top_ids_out /* [DTK_MAX_BATCH][DTK_MAX_TOP] */,
+                               float* top_logprob_out /* [DTK_MAX_BATCH][DTK_MAX_TOP] */);
+
 #ifdef __cplusplus
 }
 #endif
