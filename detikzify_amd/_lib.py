@@ -190,6 +190,11 @@ SYMBOLS = {
     "dtk_score_packed": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_int, _P, _P, _P]),
     "dtk_score_packed_text": (C.c_int, [_P, _P, C.c_int, _P, C.c_uint64, _P, C.c_int, C.c_uint64, C.c_uint32, _P, _P, C.c_int, _P, _P, _P]),
     "dtk_op_attention_seg": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    # additive (ABI stays 7): the decode attention kernels alone, single sequence and batched
+    "dtk_op_attn_decode": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _P, _P, _P, _P]),
+    "dtk_op_attn_decode_b": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -2118,6 +2118,35 @@ int dtk_num_slots(const dtk_ctx* c) { return c ? c->nb : 0; }
 int dtk_max_positions(const dtk_ctx* c) { return c ? c->Tmax : 0; }
 int dtk_max_decode_slots(const dtk_ctx* c) { return (c && c->nb > 0) ? max_decode_slots(c) : 0; }
 
+// Shared prefixes for k_attn_prefix_g: the active slots grouped by (share_src, share_len) — both properties of the slot alone, so a
+// slot's arithmetic never depends on which other slots decode with it — in chunks of 16 (one MFMA column tile), sources in slot
+// order.  A source slot that decodes itself is not a member of its forks' groups (that WOULD depend on the others); more than
+// DTK_PFX_GROUPS = 64 groups cover the worst case (64 slots that share nothing), so no slot ever falls back because of its company.
+// hb->active / share_src / share_len are read; n_groups, group_plus1, pfx_len_of and groups are written (enabled = false: no groups).
+static void build_prefix_groups(BatchState* hb, const int32_t* active, bool enabled) {
+  hb->n_groups = 0;
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) { hb->group_plus1[j] = 0; hb->pfx_len_of[j] = 0; }
+  if (!enabled) return;
+  for (int j = 0; j < DTK_MAX_BATCH && hb->n_groups < DTK_PFX_GROUPS; ++j) {
+    if (!active[j] || hb->group_plus1[j] || hb->share_src[j] < 0 || hb->share_len[j] < 4) continue;
+    const int src = hb->share_src[j], len = hb->share_len[j];
+    PfxGroup* g = nullptr;
+    for (int k = j; k < DTK_MAX_BATCH; ++k) {
+      if (!active[k] || hb->group_plus1[k] || hb->share_src[k] != src || hb->share_len[k] != len) continue;
+      if (!g || g->n == 16) {
+        if (hb->n_groups == DTK_PFX_GROUPS) break;
+        g = &hb->groups[hb->n_groups++];
+        g->src = src; g->len = len; g->n = 0; g->pad = 0;
+      }
+      g->slot[g->n++] = k;
+      hb->group_plus1[k] = hb->n_groups;
+      hb->pfx_len_of[k] = len;
+    }
+  }
+  for (int gi = 0; gi < hb->n_groups; ++gi)
+    for (int k = hb->groups[gi].n; k < 16; ++k) hb->groups[gi].slot[k] = hb->groups[gi].slot[0];
+}
+
 // One batched decode step for the slots with active[slot] != 0 (every one must have been prefilled).
 int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
   if (!c || !active) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_launch: null argument");
@@ -2143,32 +2172,7 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
     hb->share_len[j] = sh_ok ? c->bseq[(size_t)j].share_len : 0;
   }
   hb->step = (int32_t)(c->blaunched % DTK_MAX_INFLIGHT);
-  // Shared prefixes for k_attn_prefix_g: the active slots grouped by (share_src, share_len) — both properties of the slot alone, so a
-  // slot's arithmetic never depends on which other slots decode with it — in chunks of 16 (one MFMA column tile), sources in slot
-  // order.  A source slot that decodes itself is not a member of its forks' groups (that WOULD depend on the others); more than
-  // DTK_PFX_GROUPS = 64 groups cover the worst case (64 slots that share nothing), so no slot ever falls back because of its company.
-  hb->n_groups = 0;
-  for (int j = 0; j < DTK_MAX_BATCH; ++j) { hb->group_plus1[j] = 0; hb->pfx_len_of[j] = 0; }
-  if (c->prefix_mfma && !mv_family(c)) {
-    for (int j = 0; j < DTK_MAX_BATCH && hb->n_groups < DTK_PFX_GROUPS; ++j) {
-      if (!active[j] || hb->group_plus1[j] || hb->share_src[j] < 0 || hb->share_len[j] < 4) continue;
-      const int src = hb->share_src[j], len = hb->share_len[j];
-      PfxGroup* g = nullptr;
-      for (int k = j; k < DTK_MAX_BATCH; ++k) {
-        if (!active[k] || hb->group_plus1[k] || hb->share_src[k] != src || hb->share_len[k] != len) continue;
-        if (!g || g->n == 16) {
-          if (hb->n_groups == DTK_PFX_GROUPS) break;
-          g = &hb->groups[hb->n_groups++];
-          g->src = src; g->len = len; g->n = 0; g->pad = 0;
-        }
-        g->slot[g->n++] = k;
-        hb->group_plus1[k] = hb->n_groups;
-        hb->pfx_len_of[k] = len;
-      }
-    }
-    for (int gi = 0; gi < hb->n_groups; ++gi)
-      for (int k = hb->groups[gi].n; k < 16; ++k) hb->groups[gi].slot[k] = hb->groups[gi].slot[0];
-  }
+  build_prefix_groups(hb, active, c->prefix_mfma && !mv_family(c));
   int hi = 0;
   for (int j = 0; j < DTK_MAX_BATCH; ++j) if (active[j]) hi = j;
   c->nt_step = hi < 16 ? 1 : (hi < 32 ? 2 : 4);      // column tiles this step needs (per-column results do not depend on it)
@@ -3294,6 +3298,168 @@ int dtk_op_attention_seg(dtk_ctx* c, const uint16_t* Q, const uint16_t* K, const
   HIPCHK(c, hipMemcpyAsync(O, dO, (size_t)H * Tq * hd * 2, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
+  return DTK_OK;
+}
+
+// The single-sequence decode attention alone (launch_attn_decode as decode_step_launches calls it) on host operands: q [H*hd], K / V
+// [KVH][T_max][hd], scale hd^-0.5.  The caches are uploaded once; for each of the npos positions DecState.pos is set, the kernels of
+// (threads, splits, mode) run and that position's head outputs go to out[i][H*hd].  mode = AttnDecArgs::combine: 2 own combine kernel,
+// 1 in-kernel combine (threads 0; the arrival counters start at zero and must be zero again afterwards), 3 k_attn_decode_head (threads
+// 0), 0 consumer-side combine: o_proj's PRO_ATTN / EPI_RESID GEMV with an identity [d][d] weight onto a zero residual (variant -1: the
+// default of launch_gemv, 0..8: launch_gemv_variant), and the raw partials pm / pl [npos][H][S], po [npos][H][S][hd] come back too
+// (NaN where the kernels wrote none: threads != 0 with one split writes the head output itself and o_proj copies it, as in the step).
+int dtk_op_attn_decode(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int H, int KVH, int hd, int T_max,
+                       const int32_t* pos, int npos, int threads, int splits, int mode, int variant, uint16_t* out,
+                       float* pm_out, float* pl_out, float* po_out) {
+  if (!c || !q || !K || !V || !pos || !out) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: null argument");
+  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: head dim %d (128 or 64)", hd);
+  if (H < 1 || KVH < 1 || H % KVH || T_max < 1 || npos < 1 || npos > 4096) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: bad shape");
+  if (threads != 0 && threads != 256 && threads != 512 && threads != 1024) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: threads must be 0, 256, 512 or 1024");
+  if (threads == 0 && hd == 64) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: threads 0 (contiguous splits) has no head_dim-64 kernel: 256, 512 or 1024");
+  if (splits < 1 || splits > 16) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: splits must be 1..16");
+  if (mode < 0 || mode > 3) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode must be 0..3");
+  if ((mode == 1 || mode == 3) && threads != 0) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode %d needs threads 0 (the tile kernel has no such form)", mode);
+  if (variant < -1 || variant > 8) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: variant must be -1 (default) or 0..8");
+  if (mode == 0 && (!pm_out || !pl_out || !po_out)) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode 0 returns the partials");
+  for (int i = 0; i < npos; ++i)
+    if (pos[i] < 0 || pos[i] >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: position %d of %d rows", pos[i], T_max);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int d = H * hd, S = splits;
+  const size_t kv = (size_t)KVH * T_max * hd, part = (size_t)H * S * 130;   // 130: the in-kernel combine keeps (m, l) next to a split's 128 outputs
+  size_t off = 0;
+  OPBUF(bf16_t, dq, d); OPBUF(bf16_t, dK, kv); OPBUF(bf16_t, dV, kv); OPBUF(DecState, dst, npos);
+  OPBUF(float, dpm, (size_t)npos * H * S); OPBUF(float, dpl, (size_t)npos * H * S); OPBUF(float, dpo, (size_t)npos * part);
+  OPBUF(bf16_t, dout, (size_t)npos * d); OPBUF(bf16_t, dy, (size_t)npos * d); OPBUF(unsigned, dctr, H);
+  OPBUF(bf16_t, dW, mode == 0 ? (size_t)d * d : 1);
+  hipStream_t s = c->stream;
+  std::vector<DecState> hst((size_t)npos);
+  memset(hst.data(), 0, sizeof(DecState) * (size_t)npos);
+  for (int i = 0; i < npos; ++i) { hst[(size_t)i].pos = pos[i]; hst[(size_t)i].next_pos = pos[i] + 1; }
+  std::vector<bf16_t> eye;
+  if (mode == 0) {
+    eye.assign((size_t)d * d, 0);
+    for (int i = 0; i < d; ++i) eye[(size_t)i * d + i] = 0x3F80;   // bf16 1.0
+    HIPCHK(c, hipMemcpyAsync(dW, eye.data(), eye.size() * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(dy, 0, (size_t)npos * d * 2, s));       // the zero residual
+  }
+  HIPCHK(c, hipMemcpyAsync(dq, q, (size_t)d * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dK, K, kv * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dV, V, kv * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dst, hst.data(), sizeof(DecState) * (size_t)npos, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(dpm, 0xFF, (size_t)npos * H * S * 4, s));
+  HIPCHK(c, hipMemsetAsync(dpl, 0xFF, (size_t)npos * H * S * 4, s));
+  HIPCHK(c, hipMemsetAsync(dpo, 0xFF, (size_t)npos * part * 4, s));
+  HIPCHK(c, hipMemsetAsync(dout, 0xFF, (size_t)npos * d * 2, s));
+  HIPCHK(c, hipMemsetAsync(dctr, 0, (size_t)H * 4, s));
+  for (int i = 0; i < npos; ++i) {
+    AttnDecArgs ad;
+    ad.q = dq; ad.kcache = dK; ad.vcache = dV; ad.st = dst + i;
+    ad.pm = dpm + (size_t)i * H * S; ad.pl = dpl + (size_t)i * H * S; ad.po = dpo + (size_t)i * part;
+    ad.H = H; ad.S = S; ad.T_max = T_max; ad.G = H / KVH; ad.scale = 1.0f / sqrtf((float)hd); ad.hd = hd;
+    ad.threads = threads; ad.combine = mode; ad.out = dout + (size_t)i * d; ad.counters = dctr;
+    launch_attn_decode(ad, s);
+    if (mode != 0) continue;
+    GemvArgs g{};
+    g.W = dW; g.N = d; g.K = d; g.y = dy + (size_t)i * d; g.d = d; g.H = H; g.KVH = KVH; g.hd = hd; g.st = dst + i; g.T_max = T_max;
+    g.pm = ad.pm; g.pl = ad.pl; g.po = ad.po; g.S = S;
+    if (threads && S == 1) { g.x = ad.out; launch_gemv(PRO_COPY, EPI_RESID, g, s); }   // as decode_step_launches: no partials exist
+    else if (variant < 0) launch_gemv(PRO_ATTN, EPI_RESID, g, s);
+    else launch_gemv_variant(PRO_ATTN, EPI_RESID, variant, g, s);
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<unsigned> ctr((size_t)H, 0u);
+  HIPCHK(c, hipMemcpyAsync(out, mode == 0 ? dy : dout, (size_t)npos * d * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(ctr.data(), dctr, (size_t)H * 4, hipMemcpyDeviceToHost, s));
+  if (mode == 0) {
+    HIPCHK(c, hipMemcpyAsync(pm_out, dpm, (size_t)npos * H * S * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(pl_out, dpl, (size_t)npos * H * S * 4, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  if (mode == 0) {   // [H][S][hd] of every position's [H][S][130] room
+    std::vector<float> po((size_t)npos * part);
+    HIPCHK(c, hipMemcpy(po.data(), dpo, po.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < npos; ++i) memcpy(po_out + (size_t)i * H * S * hd, po.data() + (size_t)i * part, (size_t)H * S * hd * 4);
+  }
+  HIPCHK(c, hipGetLastError());
+  for (int h = 0; h < H; ++h)
+    if (ctr[(size_t)h]) return fail(c, DTK_ERR_STATE, "dtk_op_attn_decode: arrival counter of head %d is %u after the launches (not zero)", h, ctr[(size_t)h]);
+  return DTK_OK;
+}
+
+// The batched decode attention alone (launch_attn_decode_b as batch_step_launches / batch_step_launches_mv call it; bf16 output) on
+// host operands: nslots = the grid's y (1, 2, 4: the multi-vector step, no prefix kernel; 16, 32, 64), q [nslots][H*128], K / V
+// [nslots][KVH][T_max][128], per slot pos / active / share_src (-1: none) / share_len.  The prefix groups come from
+// build_prefix_groups, the step's own table.  out [nslots][H*128] row-major (the fragment-major order of the kernel is undone here);
+// every element is 0xFFFF first, so the rows of slots that did not decode keep that value.
+int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                         const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                         int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
+  if (!c || !q || !K || !V || !pos || !active || !share_src || !share_len || !out) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: null argument");
+  if (nslots != 1 && nslots != 2 && nslots != 4 && nslots != 16 && nslots != 32 && nslots != 64)
+    return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: nslots must be 1, 2, 4, 16, 32 or 64");
+  if (H < 1 || KVH < 1 || H % KVH || T_max < 1) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: bad shape");
+  const int G = H / KVH;
+  if (G != 1 && G != 2 && G != 4) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: %d query heads per K/V head (1, 2 or 4)", G);
+  if (pfx_splits < 1 || pfx_splits > 4) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: pfx_splits must be 1..4");
+  if (gqa_fused < 0 || gqa_fused > 2) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: gqa_fused must be 0, 1 or 2");
+  if (tail_threads != 64 && tail_threads != 128 && tail_threads != 256 && tail_threads != 512 && !(tail_threads == 1024 && nslots <= 4))
+    return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: tail_threads must be 64, 128, 256 or 512 (1024: the multi-vector step, nslots <= 4)");
+  if (use_prefix && nslots < 16) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: the multi-vector step has no prefix kernel");
+  BatchState hbs; memset(&hbs, 0, sizeof hbs);
+  int32_t act[DTK_MAX_BATCH] = {};
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) { hbs.share_src[j] = -1; hbs.share_len[j] = 0; }
+  for (int j = 0; j < nslots; ++j) {
+    if (pos[j] < 0 || pos[j] >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: slot %d: position %d of %d rows", j, pos[j], T_max);
+    if (share_src[j] >= nslots || share_src[j] == j || (share_src[j] >= 0 && (share_len[j] < 0 || share_len[j] > pos[j])))
+      return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: slot %d: source %d, %d shared rows, position %d", j, share_src[j], share_len[j], pos[j]);
+    act[j] = active[j] ? 1 : 0;
+    hbs.active[j] = act[j];
+    hbs.share_src[j] = share_src[j] >= 0 ? share_src[j] : -1;
+    hbs.share_len[j] = share_src[j] >= 0 ? share_len[j] : 0;
+  }
+  build_prefix_groups(&hbs, act, use_prefix != 0);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int d = H * 128, nsteps = (d + 31) >> 5;
+  const size_t kv_slot = (size_t)KVH * T_max * 128, kv = (size_t)nslots * kv_slot;
+  const size_t out_elems = (size_t)((nslots + 15) >> 4) * nsteps * 512, recs = (size_t)nslots * H * pfx_splits;
+  struct Big { void* p = nullptr; ~Big() { if (p) (void)hipFree(p); } } big;     // caches beyond the op scratch: allocated for this call
+  size_t off = 0;
+  bf16_t *dK = nullptr, *dV = nullptr;
+  if (kv * 4 + ((size_t)8 << 20) > c->scratch_bytes) {
+    HIPCHK(c, hipMalloc(&big.p, kv * 4));
+    dK = (bf16_t*)big.p; dV = dK + kv;
+  }
+  OPBUF(bf16_t, sK, big.p ? 1 : kv); OPBUF(bf16_t, sV, big.p ? 1 : kv);
+  if (!big.p) { dK = sK; dV = sV; }
+  OPBUF(bf16_t, dq, (size_t)nslots * d); OPBUF(DecState, dst, nslots); OPBUF(BatchState, dbs, 1); OPBUF(bf16_t, dout, out_elems);
+  OPBUF(float, dm, recs); OPBUF(float, dl, recs); OPBUF(float, dpo, recs * 128);
+  hipStream_t s = c->stream;
+  std::vector<DecState> hst((size_t)nslots);
+  memset(hst.data(), 0, sizeof(DecState) * (size_t)nslots);
+  for (int j = 0; j < nslots; ++j) { hst[(size_t)j].pos = pos[j]; hst[(size_t)j].next_pos = pos[j] + 1; }
+  HIPCHK(c, hipMemcpyAsync(dK, K, kv * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dV, V, kv * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dq, q, (size_t)nslots * d * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dst, hst.data(), sizeof(DecState) * (size_t)nslots, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dbs, &hbs, sizeof hbs, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemsetAsync(dout, 0xFF, out_elems * 2, s));
+  HIPCHK(c, hipMemsetAsync(dm, 0xFF, recs * 4, s));
+  HIPCHK(c, hipMemsetAsync(dl, 0xFF, recs * 4, s));
+  HIPCHK(c, hipMemsetAsync(dpo, 0xFF, recs * 128 * 4, s));
+  AttnDecBArgs ad;
+  ad.q = dq; ad.kcache = dK; ad.vcache = dV; ad.kv_slot_stride = kv_slot; ad.st = dst; ad.bs = dbs;
+  ad.out = dout; ad.H = H; ad.T_max = T_max; ad.d = d; ad.G = G; ad.nslots = nslots; ad.scale = 1.0f / sqrtf(128.f);
+  ad.use_prefix = use_prefix != 0; ad.pfx_splits = pfx_splits; ad.tail_threads = tail_threads; ad.gqa_fused = gqa_fused; ad.nt_private = attn_nt != 0;
+  ad.pfx_m = dm; ad.pfx_l = dl; ad.pfx_o = dpo;
+  launch_attn_decode_b(ad, s);
+  HIPCHK(c, hipGetLastError());
+  std::vector<bf16_t> frag(out_elems);
+  HIPCHK(c, hipMemcpyAsync(frag.data(), dout, out_elems * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  for (int j = 0; j < nslots; ++j)
+    for (int k = 0; k < d; ++k)    // xtile_off (common.h)
+      out[(size_t)j * d + k] = frag[((size_t)((j >> 4) * nsteps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (j & 15)) * 8 + (k & 7)];
   return DTK_OK;
 }
 

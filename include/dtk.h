@@ -524,6 +524,27 @@ int  dtk_op_attention(dtk_ctx* ctx, const uint16_t* Q, const uint16_t* K, const 
  * visible to every query; query t sees key j iff j <= kv_row[t] and (j < shared_len or j >= seg_begin[t]); 0 <= seg_begin[t] <= kv_row[t] < Tk */
 int  dtk_op_attention_seg(dtk_ctx* ctx, const uint16_t* Q, const uint16_t* K, const uint16_t* V,
                           int H, int Tq, int Tk, int hd, int shared_len, const int32_t* seg_begin, const int32_t* kv_row, uint16_t* O);
+/* Decode attention alone, op by op (additive, ABI 7); bf16 bits throughout, scale = hd^-0.5.
+ * dtk_op_attn_decode: the single-sequence kernels.  q [H*hd], K / V [KVH][T_max][hd] (query head h reads K/V head h / (H / KVH)), hd 128 | 64.
+ * The caches are uploaded once; for each of the npos positions the step's launcher runs over keys 0..pos[i] and out[i][H*hd] receives
+ * the head outputs.  threads 0 (contiguous key ranges per split, hd 128 only) | 256 | 512 | 1024 (tiles dealt round-robin), splits 1..16,
+ * mode 2 = own combine kernel, 1 = in-kernel combine (threads 0; fails with DTK_ERR_STATE unless the arrival counters are zero again),
+ * 3 = one block per head (threads 0), 0 = consumer-side combine: o_proj's prologue reduces the partials, run with an identity weight
+ * onto a zero residual (variant -1 = the step's default kernel, 0..8 = that tuning variant); mode 0 also returns the raw partials
+ * pm_out / pl_out [npos][H][splits] and po_out [npos][H][splits][hd] (NaN where none are written: threads != 0 with one split).
+ * pm_out / pl_out / po_out may be NULL in the other modes. */
+int  dtk_op_attn_decode(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, const uint16_t* V, int H, int KVH, int hd, int T_max,
+                        const int32_t* pos, int npos, int threads, int splits, int mode, int variant, uint16_t* out,
+                        float* pm_out, float* pl_out, float* po_out);
+/* dtk_op_attn_decode_b: the batched kernels (head dim 128, bf16 output).  nslots = the grid's slot dimension: 1 | 2 | 4 (the multi-vector
+ * step: use_prefix 0, tail_threads up to 1024) | 16 | 32 | 64; q [nslots][H*128], K / V [nslots][KVH][T_max][128]; per slot pos, active,
+ * share_src (-1 = none; else rows [0, share_len) are read from that slot's cache, share_len <= pos) and share_len.  use_prefix = score
+ * the shared prefixes per group on the matrix cores (the groups are formed as dtk_decode_batch_launch forms them), pfx_splits 1..4,
+ * tail_threads 64 | 128 | 256 | 512 (| 1024), gqa_fused 0..2, attn_nt 0 | 1: the options of the same names.  out [nslots][H*128] row-major;
+ * every element is set to 0xFFFF first, which the rows of inactive slots keep. */
+int  dtk_op_attn_decode_b(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                          const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                          int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */
