@@ -56,6 +56,11 @@ class DtkSampling(C.Structure):
     ]
 
 
+class DtkSamplingExt(C.Structure):
+    """dtk_sampling_ext: min_p / epsilon_cutoff, set after dtk_set_sampling[_slot] (which resets both to 0)"""
+    _fields_ = [("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("reserved", C.c_int32 * 6)]
+
+
 class DtkStats(C.Structure):
     _fields_ = [
         ("weight_bytes_per_token", C.c_uint64), ("kv_bytes_per_ctx_token", C.c_uint64),
@@ -105,6 +110,8 @@ class DtkEngineOps(C.Structure):
     PREFILL_TEXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _I64P, C.c_int, C.c_void_p, C.c_uint64, _I64P, C.c_int, C.c_uint64, C.c_int)
     # not a field: dtk_engine_set_wait_lp_op's argument (dev, tokens_out[64], logprob_out[64], sample_logprob_out[64])
     WAIT_LP = C.CFUNCTYPE(C.c_int, C.c_void_p, _I64P, C.POINTER(C.c_float), C.POINTER(C.c_float))
+    # not a field: dtk_engine_set_sampling_ext_op's argument (dev, slot, ext)
+    SAMPLING_EXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkSamplingExt))
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -220,6 +227,13 @@ SYMBOLS = {
     "dtk_decode_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "dtk_decode_batch_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    # additive (ABI stays 7): min_p / epsilon_cutoff behind top-p
+    "dtk_set_sampling_ext": (C.c_int, [_P, C.POINTER(DtkSamplingExt)]),
+    "dtk_set_sampling_slot_ext": (C.c_int, [_P, C.c_int, C.POINTER(DtkSamplingExt)]),
+    "dtk_op_sample_ext": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float), C.POINTER(DtkSamplingExt)]),
+    "dtk_engine_submit_ext": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.POINTER(C.c_int64), C.c_int, C.c_uint64,
+                                        C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_sampling_ext_op": (C.c_int, [_P, DtkEngineOps.SAMPLING_EXT]),
 }
 
 _lib = None
@@ -261,6 +275,9 @@ def load_library() -> C.CDLL:
     if lib.dtk_abi_struct_size(11) != C.sizeof(DtkAdapterConfig):
         raise DtkError(f"struct layout mismatch with include/dtk.h: DtkAdapterConfig is {C.sizeof(DtkAdapterConfig)} here, "
                        f"{lib.dtk_abi_struct_size(11)} in the library")
+    if lib.dtk_abi_struct_size(12) != C.sizeof(DtkSamplingExt):
+        raise DtkError(f"struct layout mismatch with include/dtk.h: DtkSamplingExt is {C.sizeof(DtkSamplingExt)} here, "
+                       f"{lib.dtk_abi_struct_size(12)} in the library")
     _lib = lib
     return lib
 

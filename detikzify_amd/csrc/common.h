@@ -150,6 +150,9 @@ struct SamplingDev {
   int32_t begin_ids[8];
   int32_t n_always;
   int32_t always_ids[8];
+  // min-p / epsilon cut-off (dtk_set_sampling_ext; both 0 = off).  Read only by the TR sampler instantiations (SampleArgs::trunc).
+  int64_t qmin;          // (int64)((double)min_p * 2^31): the smallest integer mass min-p keeps
+  float eps;             // epsilon_cutoff in [0, 1)
 };
 
 // scratch of the multi-block sampler (kernels_sample_mb.hip), one per sequence / slot
@@ -171,6 +174,11 @@ struct SampleMB {
   // log-probabilities (SampleArgs::lp_ring): every slice's online log-sum-exp state of its RAW logits, left by k_smb_max<true>
   float lmax[DTK_SAMPLE_MB_MAX_SLICES];
   float lsum[DTK_SAMPLE_MB_MAX_SLICES];
+  // min-p / epsilon cut-off (SampleArgs::trunc): every slice's mass of the set kept after top-p and min-p, left by k_smb_kept<true>;
+  // k_smb_trunc folds them in slice order into the epsilon threshold and publishes the mass floor (or the fallback flag) for k_smb_draw
+  unsigned long long bpre[DTK_SAMPLE_MB_MAX_SLICES];
+  unsigned int qfl;
+  int fb;
 };
 
 // Online log-sum-exp over raw logits, carried by the samplers next to their masked maximum (SampleArgs::lp_ring): the state is

@@ -255,6 +255,13 @@ struct dtk_ctx {
   bool mb_batch = false;             // ... the batched graph
   bool slot_topk[DTK_MAX_SLOTS] = {};   // slots whose sampling needs top-k (single-block sampler only)
   bool slot_samples[DTK_MAX_SLOTS] = {}; // slots that sample (not greedy)
+  // min_p / epsilon_cutoff (dtk_set_sampling_ext): which sampler instantiations the next captures must contain, and which the captured
+  // graphs do contain (ensure_graph / ensure_batch_graph drop a graph of the other kind: a sequence with the values set again after
+  // the reset of dtk_set_sampling keeps its graph)
+  dtk_sampling_ext sampling_ext{};
+  bool trunc_single = false, graph_trunc = false;
+  bool slot_trunc[DTK_MAX_SLOTS] = {};
+  bool trunc_batch = false, bgraph_trunc = false;
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
@@ -803,6 +810,7 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   sa.x = c->x; sa.d = c->d; sa.tok_ring = c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
   sa.lp_ring = c->logprobs ? c->lp_ring_dev : nullptr;
+  sa.trunc = c->trunc_single ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lse_ring_dev : nullptr;
   top_logits_launch(c, sa);
   if (c->mb_single) launch_sample_mb(sa, s); else launch_sample(sa, s);
@@ -860,6 +868,7 @@ void batch_step_launches_mx(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = nslots; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
@@ -908,6 +917,7 @@ void batch_step_launches(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = 16 * c->nt_step; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
@@ -982,6 +992,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
   sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
+  sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
   if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
@@ -1115,6 +1126,7 @@ void drop_graph(dtk_ctx* c) {          // the single-sequence step's two capture
 
 int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   const int gi = step_graph_index(c);
+  if (c->bgraph_trunc != c->trunc_batch) { drop_batch_graphs(c); c->bgraph_trunc = c->trunc_batch; }
   if (c->bgraph_ready[gi]) return DTK_OK;
   HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   c->launch_refused = false;
@@ -1134,6 +1146,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
 }
 
 int ensure_graph(dtk_ctx* c) {
+  if (c->graph_trunc != c->trunc_single) { drop_graph(c); c->graph_trunc = c->trunc_single; }
   if (c->graph_ready) return DTK_OK;
   // two captures of the same step: split-K attention (any context) and the one-block-per-head
   // attention used while the context is short; the host picks per step (it knows the position)
@@ -1194,6 +1207,7 @@ int dtk_abi_struct_size(int which) {
     case 9: return (int)offsetof(dtk_join, sampling);
     case 10: return (int)offsetof(dtk_join, error_out);
     case 11: return (int)sizeof(dtk_adapter_config);
+    case 12: return (int)sizeof(dtk_sampling_ext);
     default: return -1;
   }
 }
@@ -2075,7 +2089,8 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
     const uint32_t zero = 0;
     HIPCHK(c, hipMemcpy(&st_dst->draw, &zero, sizeof zero, hipMemcpyHostToDevice));
   }
-  if (is_single) { c->sampling = *sp; c->launched = c->waited = 0; }
+  if (is_single) { c->sampling = *sp; c->launched = c->waited = 0; c->sampling_ext = dtk_sampling_ext{}; c->trunc_single = false; }
+  else c->slot_trunc[(int)(sp_dst - c->sp_b)] = false;      // dv.qmin = dv.eps = 0: dtk_set_sampling_*_ext follows where they are wanted
   // which sampler the captured graphs must contain: the multi-block chain serves large vocabularies unless a
   // configuration needs top-k; a change of kind drops the graph (re-captured by the next launch)
   const bool needs_topk = sp->do_sample && sp->top_k > 0 && sp->top_k < c->V;
@@ -2100,7 +2115,58 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
       c->mb_batch = mb;
       drop_batch_graphs(c);
     }
+    bool tr = false;
+    for (int j = 0; j < c->nb; ++j) tr = tr || c->slot_trunc[j];
+    c->trunc_batch = tr;
   }
+  return DTK_OK;
+}
+
+// min_p / epsilon_cutoff of the configuration the last dtk_set_sampling[_slot] left at sp_dst: the two fields alone are rewritten
+static int ext_check(dtk_ctx* c, const dtk_sampling_ext* x, const char* who) {
+  if (!x) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
+  if (!(x->min_p >= 0.f && x->min_p <= 1.f)) return fail(c, DTK_ERR_ARG, "%s: min_p must be in [0, 1]", who);
+  if (!(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f)) return fail(c, DTK_ERR_ARG, "%s: epsilon_cutoff must be in [0, 1)", who);
+  return DTK_OK;
+}
+struct ExtDev { int64_t qmin; float eps; };       // SamplingDev's tail
+static_assert(offsetof(SamplingDev, eps) - offsetof(SamplingDev, qmin) == offsetof(ExtDev, eps) &&
+              sizeof(SamplingDev) - offsetof(SamplingDev, qmin) == sizeof(ExtDev), "SamplingDev ends with (qmin, eps)");
+static inline ExtDev ext_dev(const dtk_sampling_ext* x) {
+  ExtDev d{};
+  d.qmin = (int64_t)((double)x->min_p * 2147483648.0); d.eps = x->epsilon_cutoff;
+  return d;
+}
+
+int dtk_set_sampling_ext(dtk_ctx* c, const dtk_sampling_ext* x) {
+  if (!c) return DTK_ERR_ARG;
+  if (const int rc = ext_check(c, x, "dtk_set_sampling_ext")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const ExtDev dv = ext_dev(x);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(reinterpret_cast<char*>(c->sp) + offsetof(SamplingDev, qmin), &dv, sizeof dv, hipMemcpyHostToDevice));
+  c->sampling_ext = *x;
+  c->trunc_single = dv.qmin != 0 || dv.eps != 0.f;
+  return DTK_OK;
+}
+
+int dtk_set_sampling_slot_ext(dtk_ctx* c, int slot, const dtk_sampling_ext* x) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_set_sampling_slot_ext: slot %d of %d", slot, c ? c->nb : 0);
+  if (const int rc = ext_check(c, x, "dtk_set_sampling_slot_ext")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const ExtDev dv = ext_dev(x);
+  char* dst = reinterpret_cast<char*>(c->sp_b + slot) + offsetof(SamplingDev, qmin);
+  if (c->sp_stage) {        // queued behind the slot's dtk_set_sampling_slot upload, from the same staging record
+    c->sp_stage[slot].eps = dv.eps; c->sp_stage[slot].qmin = dv.qmin;
+    HIPCHK(c, hipMemcpyAsync(dst, &c->sp_stage[slot].qmin, sizeof dv, hipMemcpyHostToDevice, c->stream));
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dst, &dv, sizeof dv, hipMemcpyHostToDevice));
+  }
+  c->slot_trunc[slot] = dv.qmin != 0 || dv.eps != 0.f;
+  bool tr = false;
+  for (int j = 0; j < c->nb; ++j) tr = tr || c->slot_trunc[j];
+  c->trunc_batch = tr;
   return DTK_OK;
 }
 
@@ -3479,17 +3545,26 @@ int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uin
   return DTK_OK;
 }
 
-static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out) {
+static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
+                          const dtk_sampling_ext* ext = nullptr) {
   HIPCHK(c, hipSetDevice(c->device));
   size_t off = 0;
-  OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1);
+  OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1); OPBUF(SamplingDev, dsp, 1);
   hipStream_t s = c->stream;
   HIPCHK(c, hipMemcpyAsync(dl, logits, (size_t)V * 4, hipMemcpyHostToDevice, s));
+  ExtDev xd{};
+  if (ext) {      // the context's configuration with the call's own (min_p, epsilon_cutoff)
+    xd = ext_dev(ext);
+    HIPCHK(c, hipMemcpyAsync(dsp, c->sp, sizeof(SamplingDev), hipMemcpyDeviceToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char*>(dsp) + offsetof(SamplingDev, qmin), &xd, sizeof xd, hipMemcpyHostToDevice, s));
+  }
   SampleArgs sa;
   sa.logits = dl; sa.V = V; sa.sp = c->sp; sa.st = c->st; sa.embed = c->embed; sa.x = c->x; sa.d = c->d;
   sa.tok_ring = dtok; sa.ring = 1; sa.probs_out = probs_out ? c->probs_dev : nullptr; sa.advance = 0;
   sa.step_override = step; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
   sa.lp_ring = lp_out ? dlp : nullptr;
+  if (ext) { sa.sp = dsp; sa.trunc = (xd.qmin != 0 || xd.eps != 0.f) ? 1 : 0; }
+  else sa.trunc = c->trunc_single ? 1 : 0;
   const bool needs_topk = c->sampling.do_sample && c->sampling.top_k > 0 && c->sampling.top_k < V;
   if (sample_mb_preferred(V, c->sampling.do_sample != 0) && !needs_topk && !getenv("DTK_SAMPLER")) launch_sample_mb(sa, s); else launch_sample(sa, s);
   HIPCHK(c, hipMemcpyAsync(token_out, dtok, 8, hipMemcpyDeviceToHost, s));
@@ -3512,6 +3587,17 @@ int dtk_op_sample_lp(dtk_ctx* c, const float* logits, int V, int step, int64_t* 
     return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: bad argument");
   if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
   return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out);
+}
+
+// dtk_op_sample_lp under the context's configuration with the call's own (min_p, epsilon_cutoff): the TR sampler instantiations (both 0:
+// the kernels dtk_op_sample_lp runs).  lp_out may be null (the LP = false kernels; no "logprobs" option needed then)
+int dtk_op_sample_ext(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
+                      const dtk_sampling_ext* ext) {
+  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V))
+    return fail(c, DTK_ERR_ARG, "dtk_op_sample_ext: bad argument");
+  if (const int rc = ext_check(c, ext, "dtk_op_sample_ext")) return rc;
+  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_ext: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext);
 }
 
 }  // extern "C"

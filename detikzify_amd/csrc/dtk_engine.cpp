@@ -60,6 +60,7 @@ struct Cmd {
   const int64_t* text = nullptr;    // the join's text ids (caller-owned until awaited), nullptr: an image-only join
   int n_text = 0;
   uint64_t text_key = 0;
+  dtk_sampling_ext ext{};           // the sequence's min_p / epsilon_cutoff (dtk_engine_submit_ext), 0 / 0 for every other join
   int rc = 0;
   bool done = false;
   std::condition_variable cv;
@@ -72,6 +73,7 @@ using ActiveSet = std::array<int32_t, DTK_MAX_BATCH>;
 using PrefillTextFn = int (*)(void* dev, int slot, const int64_t* ids, int T, const float* px, uint64_t image_key, const int64_t* text_ids,
                               int n_text, uint64_t text_key, int flags);
 using WaitLpFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out);
+using SamplingExtFn = int (*)(void* dev, int slot, const dtk_sampling_ext* x);
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
@@ -79,6 +81,7 @@ struct dtk_engine {
   dtk_engine_ops ops{};
   PrefillTextFn prefill_text = nullptr;     // dtk_engine_set_prefill_text_op (dtk_engine_create: dtk_prefill_slot_text)
   WaitLpFn wait_lp = nullptr;               // dtk_engine_set_wait_lp_op: collects a step instead of ops.wait
+  SamplingExtFn sampling_ext = nullptr;     // dtk_engine_set_sampling_ext_op (dtk_engine_create: dtk_set_sampling_slot_ext)
   dtk_ctx* own_ctx = nullptr;               // dtk_engine_create: the context, whose "logprobs" option decides which wait collects
   std::mutex mu;
   std::condition_variable cv_run;
@@ -212,6 +215,16 @@ int do_join(dtk_engine* e, const Cmd* c) {
   const char* prefill_name = c->text ? "dtk_prefill_slot_text" : "dtk_prefill_slot";
   int slot = j->slot;
   j->slot_out = slot;
+  // the sequence's sampling: the plan's call, which resets min_p / epsilon_cutoff, then the join's own pair (0 / 0 without one)
+  auto set_sampling = [&](int s) -> int {
+    int rc = o.set_sampling_slot(o.dev, s, &j->sampling);
+    if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
+    if (e->sampling_ext) {
+      rc = e->sampling_ext(o.dev, s, &c->ext);
+      if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot_ext");
+    }
+    return DTK_OK;
+  };
   if (j->try_resume && j->n_ids >= 2) {
     int best = -1, best_len = 0;
     const int nc = j->n_candidates > 0 ? j->n_candidates : 1;
@@ -225,16 +238,16 @@ int do_join(dtk_engine* e, const Cmd* c) {
     }
     if (best >= 0 && best_len >= j->n_ids - 1) {
       j->slot_out = slot = best;
-      int rc = o.set_sampling_slot(o.dev, slot, &j->sampling);
-      if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
+      int rc = set_sampling(slot);
+      if (rc) return rc;
       rc = o.resume_slot(o.dev, slot, j->ids, j->n_ids, key);
       if (rc) return set_error(e, j, rc, "dtk_resume_slot");
       j->how_out = DTK_JOIN_RESUMED;
       return DTK_OK;
     }
   }
-  int rc = o.set_sampling_slot(o.dev, slot, &j->sampling);
-  if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
+  int rc = set_sampling(slot);
+  if (rc) return rc;
   const int reuse = DTK_PREFILL_REUSE_PREFIX | DTK_PREFILL_REUSE_IMAGE;
   if (j->prefix_len > 0 && j->prefix_in_place) {
     rc = prefill(slot, j->n_ids, reuse);
@@ -367,15 +380,21 @@ void run(dtk_engine* e) {
 }
 
 // queue a join (text: its text ids, nullptr for an image-only join)
-int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out,
+           const dtk_sampling_ext* ext = nullptr) {
   std::lock_guard<std::mutex> g(e->mu);
   if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
   if (text && !e->prefill_text) {
     snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_text: this engine's device has no text prefill (dtk_engine_set_prefill_text_op)");
     return DTK_ERR_STATE;
   }
+  if (ext && (ext->min_p != 0.f || ext->epsilon_cutoff != 0.f) && !e->sampling_ext) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_ext: this engine's device takes no min_p / epsilon_cutoff (dtk_engine_set_sampling_ext_op)");
+    return DTK_ERR_STATE;
+  }
   Cmd* c = new Cmd();
   c->join = j;
+  if (ext) c->ext = *ext;
   c->text = text; c->n_text = n_text; c->text_key = text_key;
   e->cmds.push_back(c);
   e->cv_run.notify_all();
@@ -389,6 +408,9 @@ int ctx_wait(void* d, int64_t* t) { return dtk_decode_batch_wait((dtk_ctx*)d, t)
 int ctx_wait_lp(void* d, int64_t* t, float* lp, float* slp) { return dtk_decode_batch_wait_lp((dtk_ctx*)d, t, lp, slp); }
 int ctx_prefill(void* d, int s, const int64_t* ids, int T, const float* px, uint64_t key, int flags) { return dtk_prefill_slot((dtk_ctx*)d, s, ids, T, px, key, flags, nullptr); }
 int ctx_sampling(void* d, int s, const dtk_sampling* sp) { return dtk_set_sampling_slot((dtk_ctx*)d, s, sp); }
+int ctx_sampling_ext(void* d, int s, const dtk_sampling_ext* x) {     // (0 / 0: dtk_set_sampling_slot has just left exactly that)
+  return (x->min_p == 0.f && x->epsilon_cutoff == 0.f) ? DTK_OK : dtk_set_sampling_slot_ext((dtk_ctx*)d, s, x);
+}
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
 int ctx_lcp(void* d, int s, const int64_t* ids, int n, uint64_t key, int* out) { return dtk_slot_lcp((dtk_ctx*)d, s, ids, n, key, out); }
 int ctx_resume(void* d, int s, const int64_t* ids, int n, uint64_t key) { return dtk_resume_slot((dtk_ctx*)d, s, ids, n, key); }
@@ -429,6 +451,7 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
     std::lock_guard<std::mutex> g((*out)->mu);
     (*out)->own_ctx = ctx;
     (*out)->wait_lp = ctx_wait_lp;
+    (*out)->sampling_ext = ctx_sampling_ext;
   }
   return dtk_engine_set_prefill_text_op(*out, ctx_prefill_text);
 }
@@ -437,6 +460,13 @@ int dtk_engine_set_wait_lp_op(dtk_engine* e, WaitLpFn wait_lp) {
   if (!e) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->wait_lp = wait_lp;
+  return DTK_OK;
+}
+
+int dtk_engine_set_sampling_ext_op(dtk_engine* e, SamplingExtFn set_sampling_slot_ext) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->sampling_ext = set_sampling_slot_ext;
   return DTK_OK;
 }
 
@@ -524,6 +554,17 @@ int dtk_engine_submit_text(dtk_engine* e, dtk_join* j, const int64_t* text_ids, 
   if (!e || !j || !ticket_out) return DTK_ERR_ARG;
   if (!text_ids || n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_text: no text"); return DTK_ERR_ARG; }
   return submit(e, j, text_ids, n_text, text_key, ticket_out);
+}
+
+int dtk_engine_submit_ext(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, const int64_t* text_ids, int n_text, uint64_t text_key,
+                          uint64_t* ticket_out) {
+  if (!e || !j || !ticket_out || !x) return DTK_ERR_ARG;
+  if (!(x->min_p >= 0.f && x->min_p <= 1.f) || !(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f)) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_ext: min_p must be in [0, 1] and epsilon_cutoff in [0, 1)");
+    return DTK_ERR_ARG;
+  }
+  if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_ext: no text"); return DTK_ERR_ARG; }
+  return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x);
 }
 
 int dtk_engine_await(dtk_engine* e, uint64_t ticket) {

@@ -78,6 +78,8 @@ struct SampleArgs {
   SampleMB* mb;          // scratch of the multi-block sampler (slot 0's in batched mode), or null
   float2* lp_ring = nullptr;   // dtk_set_option "logprobs": (logprob, sample_logprob) of the token, a ring indexed exactly as tok_ring; null = the
                                // samplers without the log-probability code (the LP = false instantiations: what ran before the option existed)
+  int trunc = 0;               // dtk_set_sampling_ext: some sequence of this launch has min_p or epsilon_cutoff != 0: the TR sampler instantiations, which
+                               // read SamplingDev::qmin / eps; 0 = the samplers without that code (TR = false: what ran before the two values existed)
   float* lse_ring = nullptr;   // dtk_set_option "top_logprobs" (with lp_ring): the logsumexp the logprob was taken against, indexed as lp_ring (NaN for a forced token)
 };
 void launch_sample_b(const SampleArgs& a, hipStream_t s);

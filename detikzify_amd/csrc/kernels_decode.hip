@@ -1043,7 +1043,11 @@ __device__ __forceinline__ bool is_banned(const SamplingDev* sp, int i, bool fir
 // LP (SampleArgs::lp_ring, dtk_set_option "logprobs"): the token's (logprob, sample_logprob) next to it.  Pass 1 carries an online
 // log-sum-exp of the RAW logits (no mask, no temperature) beside the masked maximum — no further walk over the row; the pair is
 // computed and stored by thread 0.  LP = false is the kernel as it was before the option existed.
-template <bool LP>
+// TR (SampleArgs::trunc, dtk_set_sampling_ext): min-p and the epsilon cut-off behind top-p, both thresholds on the integer masses.
+// min-p keeps q >= SamplingDev::qmin; epsilon keeps q >= (int64)((double)eps * (double)total_m), total_m the mass kept so far (one more
+// block reduction).  Both fold into one mass floor; a floor above 2^31 (epsilon left nothing) keeps the first arg-max alone.
+// TR = false is the kernel as it was before the two values existed.
+template <bool LP, bool TR>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (a.bs) {  // batched decode: one block per slot, same code on that slot's buffers
     const int slot = blockIdx.x;
@@ -1145,6 +1149,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   }
   __syncthreads();
   const float zmax = s_max;
+  const int amax = s_token;                      // TR: the fallback's survivor (the draw overwrites s_token)
+  (void)amax;
   unsigned long long lp_q = 0, lp_total = 1;     // LP, thread 0: the chosen token's integer mass and the kept set's
 
   if (sampling) {
@@ -1238,13 +1244,39 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       }
       thr = prefix > thr_k ? prefix : thr_k;
     }
+    // ---- TR: the mass floor of min-p and epsilon
+    uint32_t qfl = 0; bool fb = false;
+    if constexpr (TR) {
+      unsigned long long fl = (unsigned long long)sp->qmin;
+      if (sp->eps > 0.f) {      // block-uniform
+        unsigned long long pre = 0;
+        for (int i = tid; i < V; i += SAMPLE_THREADS) {
+          float z; const unsigned long long q = mass(i, z);
+          if (fkey(z) >= thr && q >= fl) pre += q;
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
+        if (lane == 0) s_q[wave] = pre;
+        __syncthreads();
+        if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
+        __syncthreads();
+        const unsigned long long qe = (unsigned long long)((double)sp->eps * (double)s_total);
+        if (qe > fl) fl = qe;
+      }
+      fb = fl > 2147483648ull;
+      qfl = fb ? 0u : (uint32_t)fl;
+    }
+    auto kept_el = [&](int i, float z, unsigned long long q) -> bool {
+      if constexpr (TR) return fb ? (i == amax) : (fkey(z) >= thr && q >= qfl);
+      else return fkey(z) >= thr;
+    };
     // ---- kept mass + inverse-CDF draw in index order
     const int per = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS;
     const int i0 = tid * per, i1 = min(V, i0 + per);
     unsigned long long mine = 0;
     for (int i = i0; i < i1; ++i) {
       float z; const unsigned long long q = mass(i, z);
-      if (fkey(z) >= thr) mine += q;
+      if (kept_el(i, z, q)) mine += q;
     }
     scan[tid] = mine;
     __syncthreads();
@@ -1263,7 +1295,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       unsigned long long run = excl;
       for (int i = i0; i < i1; ++i) {
         float z; const unsigned long long q = mass(i, z);
-        if (fkey(z) >= thr) {
+        if (kept_el(i, z, q)) {
           if (target < run + q) { s_token = i; if constexpr (LP) s_tokq = q; break; }
           run += q;
         }
@@ -1272,7 +1304,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     if (a.probs_out) {
       for (int i = tid; i < V; i += SAMPLE_THREADS) {
         float z; const unsigned long long q = mass(i, z);
-        a.probs_out[i] = (fkey(z) >= thr) ? (float)((double)q / (double)kept) : 0.f;
+        a.probs_out[i] = kept_el(i, z, q) ? (float)((double)q / (double)kept) : 0.f;
       }
     }
     __syncthreads();
@@ -1315,9 +1347,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
 // same-address LDS-atomic serialisation that dominated k_sample (190 us -> measured in profiles/).
 // Same integer semantics as k_sample / oracle/sampling.py (bit-exact kept set and draws).
 // LP as in k_sample: the raw logits are in registers before the temperature is applied, so the thread's log-sum-exp state is their
-// maximum and one expf per logit.
+// maximum and one expf per logit.  TR as in k_sample: the mass floor is one more walk over the 32 keys and one block reduction.
 #define SF_PER 32
-template <bool LP>
+template <bool LP, bool TR>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   if (a.bs) {
     const int slot = blockIdx.x;
@@ -1433,6 +1465,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   }
   __syncthreads();
   const float zmax = s_max;
+  const int amax = s_token;                      // TR: the fallback's survivor (the draw overwrites s_token)
+  (void)amax;
   unsigned long long lp_q = 0, lp_total = 1;     // LP, thread 0: the chosen token's integer mass and the kept set's
 
   if (sampling) {
@@ -1528,10 +1562,41 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       }
       thr = prefix > thr_k ? prefix : thr_k;
     }
+    // TR: the mass floor of min-p and epsilon
+    uint32_t qfl = 0; bool fb = false;
+    if constexpr (TR) {
+      unsigned long long fl = (unsigned long long)sp->qmin;
+      if (sp->eps > 0.f) {      // block-uniform
+        unsigned long long pre = 0;
+#pragma unroll
+        for (int k = 0; k < SF_PER; ++k)
+          if (i0 + k < V && key(k) >= thr) { const uint32_t qk = q_(k); if (qk >= fl) pre += qk; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
+        if (lane == 0) s_q[wave] = pre;
+        __syncthreads();
+        if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
+        __syncthreads();
+        const unsigned long long qe = (unsigned long long)((double)sp->eps * (double)s_total);
+        if (qe > fl) fl = qe;
+      }
+      fb = fl > 2147483648ull;
+      qfl = fb ? 0u : (uint32_t)fl;
+    }
+    // element k (i0 + k < V) of the final set; qk = q_(k)
+    auto kept_el = [&](int k, uint32_t kb, uint32_t qk) -> bool {
+      if constexpr (TR) return fb ? (i0 + k == amax) : (kb >= thr && qk >= qfl);
+      else return kb >= thr;
+    };
     // kept mass + inverse-CDF draw in index order (thread t's range is contiguous: a plain block scan)
     unsigned long long mine = 0;
+    if constexpr (TR) {
 #pragma unroll
-    for (int k = 0; k < SF_PER; ++k) if (i0 + k < V && key(k) >= thr) mine += q_(k);
+      for (int k = 0; k < SF_PER; ++k) if (i0 + k < V && (fb || key(k) >= thr)) { const uint32_t qk = q_(k); if (kept_el(k, key(k), qk)) mine += qk; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < SF_PER; ++k) if (i0 + k < V && key(k) >= thr) mine += q_(k);
+    }
     scan[tid] = mine;
     __syncthreads();
     for (int off = 1; off < SAMPLE_THREADS; off <<= 1) {
@@ -1550,8 +1615,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       bool done = false;
 #pragma unroll
       for (int k = 0; k < SF_PER; ++k) {
-        if (!done && i0 + k < V && key(k) >= thr) {
+        if (!done && i0 + k < V && (TR ? (fb || key(k) >= thr) : key(k) >= thr)) {
           const unsigned long long qk = q_(k);
+          if (TR && !kept_el(k, key(k), (uint32_t)qk)) continue;
           if (target < run + qk) { s_token = i0 + k; done = true; if constexpr (LP) s_tokq = qk; }
           run += qk;
         }
@@ -1560,7 +1626,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     if (a.probs_out) {
 #pragma unroll
       for (int k = 0; k < SF_PER; ++k)
-        if (i0 + k < V) a.probs_out[i0 + k] = (key(k) >= thr) ? (float)((double)q_(k) / (double)kept) : 0.f;
+        if (i0 + k < V) a.probs_out[i0 + k] = kept_el(k, key(k), TR ? q_(k) : 0u) ? (float)((double)q_(k) / (double)kept) : 0.f;
     }
     __syncthreads();
     if constexpr (LP) if (tid == 0) { lp_q = s_tokq; lp_total = kept; }
@@ -1655,11 +1721,18 @@ void launch_sample(const SampleArgs& a, hipStream_t s) {
 }
 void launch_sample_b(const SampleArgs& a, hipStream_t s) {
   const dim3 g(a.bs ? a.nslots : 1), b(SAMPLE_THREADS);
+  // a.trunc == 0 (no sequence of this launch has min_p / epsilon_cutoff): the TR = false instantiations, the kernels as they were
   if (sample_fast_ok(a)) {
-    if (a.lp_ring) hipLaunchKernelGGL(k_sample_fast<true>, g, b, 0, s, a);
-    else hipLaunchKernelGGL(k_sample_fast<false>, g, b, 0, s, a);
+    if (a.trunc) {
+      if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, true>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_sample_fast<false, true>), g, b, 0, s, a);
+    } else if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, false>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sample_fast<false, false>), g, b, 0, s, a);
     return;
   }
-  if (a.lp_ring) hipLaunchKernelGGL(k_sample<true>, g, b, 0, s, a);
-  else hipLaunchKernelGGL(k_sample<false>, g, b, 0, s, a);
+  if (a.trunc) {
+    if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sample<false, true>), g, b, 0, s, a);
+  } else if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, false>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((k_sample<false, false>), g, b, 0, s, a);
 }

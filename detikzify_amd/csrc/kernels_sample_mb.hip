@@ -14,6 +14,10 @@
 //       DecState; gather the token's embedding (first op of the next forward)
 // Integer semantics identical to k_sample / k_sample_fast / oracle/sampling.py (q = floor(exp(z - zmax) * 2^31), kept set
 // { key >= thr }, inverse-CDF draw in index order with the splitmix64 counter RNG): same tokens, bit for bit.
+// TR (SampleArgs::trunc, dtk_set_sampling_ext): min-p and the epsilon cut-off behind top-p.  P5 then leaves every slice's mass of the set
+// kept after top-p and min-p (bpre); one more kernel, k_smb_trunc, folds those in slice order into total_m, forms the mass floor
+// max(qmin, (int64)((double)eps * (double)total_m)) — above 2^31: the first arg-max alone survives — and leaves the final bkept; P6
+// applies the floor.  Without it the chain is the 7 kernels above, unchanged.
 // Supports greedy, temperature, top-p and the suppression lists; top-k > 0 stays on the single-block kernel (the API
 // re-captures the graph when a sampling configuration needs the other kind).
 #include "kernels.h"
@@ -260,7 +264,8 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk)
   (void)lane;
 }
 
-// ---- P5: threshold + kept mass per slice
+// ---- P5: threshold + kept mass per slice.  TR: the mass of the slice's entries that pass top-p and min-p, to bpre
+template <bool TR>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk) {
   if (!mb_bind(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
@@ -291,7 +296,50 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
   mb_mass(e, cm.zmax);
   unsigned long long mine = 0;
 #pragma unroll
-  for (int i = 0; i < MB_PER; ++i) if (base + i < a.V && e.key[i] >= thr) mine += e.q[i];
+  for (int i = 0; i < MB_PER; ++i)
+    if (base + i < a.V && e.key[i] >= thr && (!TR || (long long)e.q[i] >= cm.sp.qmin)) mine += e.q[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+  if (lane == 0) s_q[wave] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w];
+    if constexpr (TR) a.mb->bpre[blk] = t; else a.mb->bkept[blk] = t;
+  }
+}
+
+// element i of the final set under TR: the mass floor, or (fb) the first arg-max alone
+__device__ __forceinline__ bool mb_kept_tr(uint32_t key, uint32_t q, int id, uint32_t thr, uint32_t qfl, bool fb, int argmax) {
+  return fb ? (id == argmax) : (key >= thr && q >= qfl);
+}
+
+// ---- TR only, between P5 and P6: the mass floor from the slices' bpre (folded in slice order by every block), the final kept mass per slice
+__global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk) {
+  if (!mb_bind(a, blockIdx.y)) return;
+  __shared__ MbCommon cm;
+  __shared__ unsigned long long s_q[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
+  mb_common(a, nblk, &cm);
+  if (!cm.sp.do_sample) return;
+  const uint32_t draw = (a.step_override >= 0) ? (uint32_t)a.step_override : a.st->draw;
+  unsigned long long total_m = 0;
+  for (int k = 0; k < nblk; ++k) total_m += a.mb->bpre[k];
+  unsigned long long fl = (unsigned long long)cm.sp.qmin;
+  const unsigned long long qe = (unsigned long long)((double)cm.sp.eps * (double)total_m);
+  if (qe > fl) fl = qe;
+  const bool fb = fl > 2147483648ull;
+  const uint32_t qfl = fb ? 0u : (uint32_t)fl;
+  if (blk == 0 && tid == 0) { a.mb->qfl = qfl; a.mb->fb = fb ? 1 : 0; }
+  const uint32_t thr = a.mb->thr;
+  const float invT = 1.f / cm.sp.temperature;
+  MbElems e;
+  const int base = blk * MB_SLICE + tid * MB_PER;
+  mb_load(a, &cm.sp, draw == 0, invT, base, e);
+  mb_mass(e, cm.zmax);
+  unsigned long long mine = 0;
+#pragma unroll
+  for (int i = 0; i < MB_PER; ++i)
+    if (base + i < a.V && mb_kept_tr(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax)) mine += e.q[i];
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
   if (lane == 0) s_q[wave] = mine;
@@ -301,7 +349,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
 
 // ---- P6: draw (or arg-max), token ring, DecState, embedding gather.  LP: thread 0 of the block that writes the token folds the
 // slices' log-sum-exp states in slice order and stores the token's (logprob, sample_logprob)
-template <bool LP>
+template <bool LP, bool TR>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk) {
   if (!mb_bind(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
@@ -341,13 +389,19 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
       const int base = blk * MB_SLICE + tid * MB_PER;
       mb_load(a, &cm.sp, draw == 0, invT, base, e);
       mb_mass(e, cm.zmax);
+      uint32_t qfl = 0; bool fb = false;
+      if constexpr (TR) { qfl = a.mb->qfl; fb = a.mb->fb != 0; }
+      auto kept_el = [&](int i) -> bool {
+        if constexpr (TR) return mb_kept_tr(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax);
+        else return e.key[i] >= thr;
+      };
       if (a.probs_out)
         for (int i = 0; i < MB_PER; ++i)
-          if (base + i < a.V) a.probs_out[base + i] = (e.key[i] >= thr) ? (float)((double)e.q[i] / (double)kept) : 0.f;
+          if (base + i < a.V) a.probs_out[base + i] = kept_el(i) ? (float)((double)e.q[i] / (double)kept) : 0.f;
       if (owner) {
         unsigned long long mine = 0;
 #pragma unroll
-        for (int i = 0; i < MB_PER; ++i) if (base + i < a.V && e.key[i] >= thr) mine += e.q[i];
+        for (int i = 0; i < MB_PER; ++i) if (base + i < a.V && kept_el(i)) mine += e.q[i];
         scan[tid] = mine;
         __syncthreads();
         for (int off = 1; off < MB_THREADS; off <<= 1) {   // block-uniform branch (owner): barriers are safe
@@ -362,7 +416,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
           unsigned long long run = excl;
 #pragma unroll
           for (int i = 0; i < MB_PER; ++i) {
-            if (base + i < a.V && e.key[i] >= thr) {
+            if (base + i < a.V && kept_el(i)) {
               if (target < run + e.q[i] && s_token < 0) { s_token = base + i; if constexpr (LP) s_tokq = e.q[i]; }
               run += e.q[i];
             }
@@ -415,7 +469,14 @@ void launch_sample_mb(const SampleArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((k_smb_hist<2>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL((k_smb_hist<1>), g, b, 0, s, a, nblk);
   hipLaunchKernelGGL((k_smb_hist<0>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL(k_smb_kept, g, b, 0, s, a, nblk);
-  if (a.lp_ring) hipLaunchKernelGGL(k_smb_draw<true>, g, b, 0, s, a, nblk);
-  else hipLaunchKernelGGL(k_smb_draw<false>, g, b, 0, s, a, nblk);
+  if (a.trunc) {
+    hipLaunchKernelGGL(k_smb_kept<true>, g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL(k_smb_trunc, g, b, 0, s, a, nblk);
+    if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, true>), g, b, 0, s, a, nblk);
+    else hipLaunchKernelGGL((k_smb_draw<false, true>), g, b, 0, s, a, nblk);
+    return;
+  }
+  hipLaunchKernelGGL(k_smb_kept<false>, g, b, 0, s, a, nblk);
+  if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, false>), g, b, 0, s, a, nblk);
+  else hipLaunchKernelGGL((k_smb_draw<false, false>), g, b, 0, s, a, nblk);
 }

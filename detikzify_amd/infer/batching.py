@@ -180,7 +180,8 @@ class BatchEngine:
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
-        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_image_key, text_key
+        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, check_truncation, text_image_key, text_key
+        check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
         tids = adapter_text(text_ids) if text_ids is not None else None
         tkey = text_key(tids) if tids is not None else 0
         ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
@@ -252,7 +253,17 @@ class BatchEngine:
                     self.model.enable_logprobs()
                     self.lp = True
                 t0 = time.perf_counter()
-                self.model.set_sampling(slot=slot, **sampling)
+                # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
+                # without them leaves the slot at 0 / 0
+                plain = {k: v for k, v in sampling.items() if k not in ("min_p", "epsilon_cutoff")}
+                self.model.set_sampling(slot=slot, **plain)
+                ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
+                set_ext = getattr(self.model, "set_sampling_ext", None)
+                if set_ext is not None:
+                    set_ext(*ext, slot=slot)
+                elif any(ext):
+                    from .._lib import DtkError
+                    raise DtkError("this device takes no min_p / epsilon_cutoff")
                 if resume:
                     self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)

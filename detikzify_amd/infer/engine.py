@@ -138,6 +138,9 @@ class _ScriptedOps:
                                bad_ids=list(s.bad_ids[:s.n_bad]), begin_suppress_ids=list(s.begin_suppress_ids[:s.n_begin_suppress]),
                                always_suppress_ids=list(s.always_suppress_ids[:s.n_always_suppress]))
 
+        def sampling_ext(dev, slot, xp):
+            model.set_sampling_ext(float(xp.contents.min_p), float(xp.contents.epsilon_cutoff), slot=slot)
+
         def fork(dev, a, b, n):
             model.kv_fork(a, b, n)
 
@@ -160,6 +163,7 @@ class _ScriptedOps:
         # the text prefill only for a device that has an adapter (an engine without it refuses text joins in submit)
         self.prefill_text = O.PREFILL_TEXT(guard(prefill_text)) if _has_adapter(model) else None
         self.wait_lp = O.WAIT_LP(guard(wait_lp))       # handed to the engine by the first sequence(logprobs=True)
+        self.sampling_ext = O.SAMPLING_EXT(guard(sampling_ext)) if hasattr(model, "set_sampling_ext") else None
 
 
 def _has_adapter(model) -> bool:
@@ -209,6 +213,8 @@ class NativeBatchEngine:
             rc = self.lib.dtk_engine_create_ops(C.byref(self._scripted.ops), C.byref(self._h))
             if rc == 0 and self._scripted.prefill_text is not None and hasattr(self.lib, "dtk_engine_set_prefill_text_op"):
                 rc = self.lib.dtk_engine_set_prefill_text_op(self._h, self._scripted.prefill_text)
+            if rc == 0 and self._scripted.sampling_ext is not None:
+                rc = self.lib.dtk_engine_set_sampling_ext_op(self._h, self._scripted.sampling_ext)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
         if not pipeline:
@@ -397,6 +403,9 @@ class NativeBatchEngine:
             arr = getattr(s, field)
             for i, v in enumerate(vals):
                 arr[i] = v
+        from ..model.modeling import check_truncation
+        ext = _lib.DtkSamplingExt(*check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff")))
+        has_ext = bool(ext.min_p or ext.epsilon_cutoff)
         stops = [int(t) for t in stop_ids if int(t) >= 0][:8]
         j.n_stop = len(stops)
         for i, t in enumerate(stops):
@@ -450,7 +459,11 @@ class NativeBatchEngine:
             self.free.remove(slot)
             if owner is not None:
                 self.last_slot[owner] = slot
-            if tids is not None:
+            if has_ext:       # the sequence's min_p / epsilon_cutoff go with its join (text or not)
+                tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
+                rc = self.lib.dtk_engine_submit_ext(self._h, C.byref(j), C.byref(ext), tp, int(tids.numel()) if tids is not None else 0,
+                                                    C.c_uint64(tkey), C.byref(ticket))
+            elif tids is not None:
                 rc = self.lib.dtk_engine_submit_text(self._h, C.byref(j), C.cast(tids.data_ptr(), C.POINTER(C.c_int64)), int(tids.numel()),
                                                      C.c_uint64(tkey), C.byref(ticket))
             else:

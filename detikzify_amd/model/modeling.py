@@ -128,8 +128,8 @@ _NEUTRAL_GENERATE_KWARGS: Dict[str, tuple] = {
     "num_beams": (None, 1), "num_beam_groups": (None, 1), "num_return_sequences": (None, 1),
     "repetition_penalty": (None, 1.0), "encoder_repetition_penalty": (None, 1.0), "length_penalty": (None, 1.0),
     "diversity_penalty": (None, 0.0), "no_repeat_ngram_size": (None, 0), "encoder_no_repeat_ngram_size": (None, 0),
-    "min_length": (None, 0), "min_new_tokens": (None, 0), "typical_p": (None, 1.0), "min_p": (None, 0.0),
-    "epsilon_cutoff": (None, 0.0), "eta_cutoff": (None, 0.0), "penalty_alpha": (None, 0.0), "early_stopping": (None, False),
+    "min_length": (None, 0), "min_new_tokens": (None, 0), "typical_p": (None, 1.0),
+    "eta_cutoff": (None, 0.0), "penalty_alpha": (None, 0.0), "early_stopping": (None, False),
     "renormalize_logits": (None, False), "remove_invalid_values": (None, False), "guidance_scale": (None, 1.0),
     "forced_bos_token_id": (None,), "forced_eos_token_id": (None,), "exponential_decay_length_penalty": (None,),
     "sequence_bias": (None,), "logits_processor": (None, [], ()), "prefix_allowed_tokens_fn": (None,),
@@ -165,6 +165,18 @@ def check_top_logprobs(top_logprobs: Optional[int], return_logprobs: bool = True
     return k
 
 
+def check_truncation(min_p: Optional[float], epsilon_cutoff: Optional[float]) -> Tuple[float, float]:
+    """the `min_p` / `epsilon_cutoff` arguments of generate / sample -> (min_p, epsilon_cutoff), 0.0 = off (None, and HF's own "unset");
+    out of range: ValueError with the text of HF's MinPLogitsWarper / EpsilonLogitsWarper, before anything runs"""
+    mp = 0.0 if min_p is None else min_p
+    if not (isinstance(mp, (int, float)) and 0 <= mp <= 1.0):
+        raise ValueError(f"`min_p` has to be a float in the [0, 1] interval, but is {min_p}")
+    eps = 0.0 if epsilon_cutoff is None else epsilon_cutoff
+    if not (isinstance(eps, (int, float)) and 0 <= eps < 1):
+        raise ValueError(f"`epsilon_cutoff` has to be a float > 0 and < 1, but is {epsilon_cutoff}")
+    return float(mp), float(eps)
+
+
 def _is_neutral(value: Any, neutral: Any) -> bool:
     if neutral is None:
         return value is None
@@ -180,8 +192,8 @@ def _reject_unsupported_generate_kwargs(kw: Dict[str, Any]) -> None:
             raise TypeError(f"generate() got an argument this decoder does not implement: {name!r}")
         if allowed != "any" and not any(_is_neutral(value, a) for a in allowed):
             raise NotImplementedError(
-                f"generate({name}={value!r}) is not supported: this path implements greedy / temperature / top-k / top-p "
-                f"sampling of one sequence (the calls DetikzifyGenerator.generate makes); only {name} in {allowed} is accepted")
+                f"generate({name}={value!r}) is not supported: this path implements greedy / temperature / top-k / top-p / min-p / "
+                f"epsilon-cutoff sampling of one sequence (the calls DetikzifyGenerator.generate makes); only {name} in {allowed} is accepted")
 
 
 # forward() arguments of HF's LlamaForCausalLM / the reference's DetikzifyForConditionalGeneration that have no generate() twin, with
@@ -766,7 +778,11 @@ class DetikzifyForCausalLM:
 
     def set_sampling(self, do_sample=False, temperature=1.0, top_p=1.0, top_k=0, seed=0,
                      bad_ids: Iterable[int] = (), begin_suppress_ids: Iterable[int] = (),
-                     always_suppress_ids: Iterable[int] = (), slot: Optional[int] = None):
+                     always_suppress_ids: Iterable[int] = (), slot: Optional[int] = None, min_p: float = 0.0,
+                     epsilon_cutoff: float = 0.0):
+        """the sampling configuration of the single sequence (slot None) or of a slot.  min_p / epsilon_cutoff (HF's two warpers behind
+        top-p; 0 = off) travel in a call of their own, set_sampling_ext: the plain call resets both."""
+        min_p, epsilon_cutoff = check_truncation(min_p, epsilon_cutoff)
         s = _lib.DtkSampling()
         s.do_sample, s.temperature, s.top_p, s.top_k = int(bool(do_sample)), float(temperature), float(top_p), int(top_k or 0)
         s.seed = int(seed) & ((1 << 64) - 1)
@@ -783,6 +799,23 @@ class DetikzifyForCausalLM:
             self._check(self.lib.dtk_set_sampling(self._ctx, C.byref(s)), "dtk_set_sampling")
         else:
             self._check(self.lib.dtk_set_sampling_slot(self._ctx, int(slot), C.byref(s)), "dtk_set_sampling_slot")
+        if min_p or epsilon_cutoff:
+            self.set_sampling_ext(min_p, epsilon_cutoff, slot=slot)
+
+    def set_sampling_ext(self, min_p: float = 0.0, epsilon_cutoff: float = 0.0, slot: Optional[int] = None):
+        """min_p / epsilon_cutoff of the configuration the last set_sampling left (dtk_set_sampling_ext / dtk_set_sampling_slot_ext);
+        set_sampling itself resets both to 0"""
+        min_p, epsilon_cutoff = check_truncation(min_p, epsilon_cutoff)
+        fn = getattr(self.lib, "dtk_set_sampling_ext" if slot is None else "dtk_set_sampling_slot_ext", None)
+        if fn is None:          # a device without the two calls has nothing to reset
+            if min_p or epsilon_cutoff:
+                raise _lib.DtkError("this device takes no min_p / epsilon_cutoff")
+            return
+        x = _lib.DtkSamplingExt(min_p=min_p, epsilon_cutoff=epsilon_cutoff)
+        if slot is None:
+            self._check(fn(self._ctx, C.byref(x)), "dtk_set_sampling_ext")
+        else:
+            self._check(fn(self._ctx, int(slot), C.byref(x)), "dtk_set_sampling_slot_ext")
 
     # ---- batched decode (independent rollouts share one pass over the weights) -----------------------
     def num_slots(self) -> int:
@@ -964,7 +997,8 @@ class DetikzifyForCausalLM:
                  top_k: Optional[int] = None, max_length: Optional[int] = None,
                  max_new_tokens: Optional[int] = None, eos_token_id=None, seed: Optional[int] = None,
                  inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, return_logprobs: bool = False,
-                 top_logprobs: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 top_logprobs: Optional[int] = None, min_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
+                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -974,6 +1008,9 @@ class DetikzifyForCausalLM:
         GenerateOutput instead: the same tensor as `.sequences` plus the per-token `.logprobs` / `.sample_logprobs` the sampler
         kernel formed on its way (enable_logprobs(): switched on for this call if needed, and left on).  top_logprobs=k (1 .. 8,
         with return_logprobs=True): + `.top_ids` / `.top_logprobs`, the k most likely tokens at every new position; not in the batch engines.  The option is on for this call only.
+
+        min_p / epsilon_cutoff: HF's MinPLogitsWarper / EpsilonLogitsWarper behind top-p (HF's order), as thresholds on the sampler's
+        integer masses; 0 / None = off; ignored by greedy decoding like temperature, top-k and top-p.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1000,6 +1037,8 @@ class DetikzifyForCausalLM:
         if ids.shape[0] != 1:
             raise ValueError("batch size 1 only (the reference generates one sequence per call)")
         gc = self.generation_config
+        min_p, epsilon_cutoff = check_truncation(getattr(gc, "min_p", None) if min_p is None else min_p,
+                                                 getattr(gc, "epsilon_cutoff", None) if epsilon_cutoff is None else epsilon_cutoff)
         do_sample = gc.do_sample if do_sample is None else do_sample
         temperature = gc.temperature if temperature is None else temperature
         top_p = gc.top_p if top_p is None else top_p
@@ -1098,7 +1137,8 @@ class DetikzifyForCausalLM:
             per_token = bool(heavy) or (streamer is not None and (put_token is None or bool(getattr(streamer, "per_token", put_tokens is None))))
             with engine.sequence(ids[0], pixel_values, dict(
                     do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, bad_ids=bad,
-                    begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or ()),
+                    begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or (),
+                    **({"min_p": min_p, "epsilon_cutoff": epsilon_cutoff} if (min_p or epsilon_cutoff) else {})),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
                     **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
@@ -1115,6 +1155,8 @@ class DetikzifyForCausalLM:
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or ())
+                if min_p or epsilon_cutoff:       # (set_sampling reset both)
+                    self.set_sampling_ext(min_p, epsilon_cutoff)
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
                     if topk:

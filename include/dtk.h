@@ -97,6 +97,15 @@ typedef struct dtk_sampling {
   int32_t always_suppress_ids[8];
 } dtk_sampling;
 
+/* The two HF warpers behind top-p (additive, ABI 7; dtk_set_sampling_ext): MinPLogitsWarper and EpsilonLogitsWarper as thresholds on
+ * the sampler's integer masses q_i = floor(exp(z_i - zmax) * 2^31).  Both 0 = off. */
+typedef struct dtk_sampling_ext {
+  float   min_p;           /* [0, 1]: keep q_i >= (int64)((double)min_p * 2^31), i.e. p_i >= min_p * p_max (the maximum always stays)     */
+  float   epsilon_cutoff;  /* [0, 1): keep q_i >= (int64)((double)eps * (double)total_m), total_m = the mass kept after top-k, top-p and
+                            * min-p; if nothing is left: the first arg-max alone                                                         */
+  int32_t reserved[6];     /* zero                                                                                                       */
+} dtk_sampling_ext;
+
 typedef struct dtk_stats {
   uint64_t weight_bytes_per_token;  /* W: decoder layers + final norm + lm_head       */
   uint64_t kv_bytes_per_ctx_token;  /* K: 2*L*d*sizeof(bf16)                          */
@@ -122,7 +131,7 @@ typedef struct dtk_stats {
 int  dtk_abi_version(void);
 /* layout check for bindings: sizeof of 0 dtk_config, 1 dtk_sampling, 2 dtk_stats; offsetof of 3 dtk_sampling.seed,
  * 4 dtk_config.reserved, 5 dtk_stats.probe_event_pair_ms; sizeof of 6 dtk_join, 7 dtk_engine_stats, 8 dtk_engine_ops; offsetof of
- * 9 dtk_join.sampling, 10 dtk_join.error_out; sizeof of 11 dtk_adapter_config; -1 for anything else */
+ * 9 dtk_join.sampling, 10 dtk_join.error_out; sizeof of 11 dtk_adapter_config, 12 dtk_sampling_ext; -1 for anything else */
 int  dtk_abi_struct_size(int which);
 /* last error of a context; ctx may be NULL for the error of a failed dtk_create */
 const char* dtk_last_error(const dtk_ctx* ctx);
@@ -618,6 +627,29 @@ int  dtk_decode_wait_top(dtk_ctx* ctx, int64_t* token_out, float* lp_out /* [2] 
 int  dtk_decode_batch_wait_top(dtk_ctx* ctx, int64_t* tokens_out /* [DTK_MAX_BATCH] */, float* logprob_out /* [DTK_MAX_BATCH] */,
                                float* sample_logprob_out /* [DTK_MAX_BATCH] */, int32_t* top_ids_out /* [DTK_MAX_BATCH][DTK_MAX_TOP] */,
                                float* top_logprob_out /* [DTK_MAX_BATCH][DTK_MAX_TOP] */);
+
+/* min_p and epsilon_cutoff (additive, ABI 7).  HF's warper order is temperature -> top-k -> top-p -> min-p -> (typical) -> epsilon; the
+ * sampler's chain is now suppression lists -> temperature -> top-k -> top-p -> min-p -> epsilon -> draw, everything up to top-p (the total
+ * its threshold is taken from included) as before.  kept_total, the draw and sample_logprob are over the final set; logprob and the top-k
+ * records are over the raw logits and do not change; a greedy configuration ignores both values.
+ *   dtk_set_sampling_ext / dtk_set_sampling_slot_ext   called AFTER dtk_set_sampling / dtk_set_sampling_slot, which reset both values
+ *                             to 0 (a caller that knows nothing of them gets what it always got).  DTK_ERR_ARG outside the ranges or on NaN.
+ *                             A context none of whose sequences has a value set runs the sampler kernels it ran before the values
+ *                             existed; the first sequence that sets one makes the next step re-capture its graph with the kernels that
+ *                             read them (values then change without a re-capture).
+ *   dtk_op_sample_ext         dtk_op_sample_lp under the context's configuration with the call's own ext; lp_out may be NULL.
+ *   dtk_engine_submit_ext     dtk_engine_submit (text_ids == NULL) or dtk_engine_submit_text whose sequence carries ext (copied at
+ *                             submit): the loop applies it right after the join's set_sampling_slot.  dtk_engine_create wires dtk_set_sampling_slot_ext itself; an engine of
+ *                             dtk_engine_create_ops gets the op through dtk_engine_set_sampling_ext_op, and without one a join whose ext
+ *                             is not 0 / 0 fails in submit with DTK_ERR_STATE.  With the op every join calls it — a join without ext
+ *                             with 0 / 0 — so a slot never inherits its previous sequence's values. */
+int  dtk_set_sampling_ext(dtk_ctx* ctx, const dtk_sampling_ext* x);
+int  dtk_set_sampling_slot_ext(dtk_ctx* ctx, int slot, const dtk_sampling_ext* x);
+int  dtk_op_sample_ext(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
+                       float* lp_out /* [2] or NULL */, const dtk_sampling_ext* x);
+int  dtk_engine_submit_ext(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, const int64_t* text_ids, int n_text, uint64_t text_key,
+                           uint64_t* ticket_out);
+int  dtk_engine_set_sampling_ext_op(dtk_engine* e, int (*set_sampling_slot_ext)(void* dev, int slot, const dtk_sampling_ext* x));
 
 #ifdef __cplusplus
 }
