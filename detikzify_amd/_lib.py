@@ -202,6 +202,10 @@ SYMBOLS = {
                                      _P, _P, _P, _P]),
     "dtk_op_attn_decode_b": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    # additive (ABI stays 7): the weight kernels of the batched decode step alone
+    "dtk_op_gemv_b": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, C.c_int,
+                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "dtk_op_gemv_bkp": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),

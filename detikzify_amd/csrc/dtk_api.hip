@@ -3529,6 +3529,205 @@ int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const
   return DTK_OK;
 }
 
+// ---- the batched decode GEMV family alone (dtk_op_gemv_b / dtk_op_gemv_bkp): host operands into the op scratch, the step's own
+// launchers (launch_retile / launch_retile_f8, launch_rmsnorm_b, launch_gemv_b, launch_gemv_bkp, launch_resid_norm_b) unchanged
+static inline size_t host_xtile_off(int slot, int k, int nsteps) {      // xtile_off (common.h)
+  return ((size_t)((slot >> 4) * nsteps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (slot & 15)) * 8 + (k & 7);
+}
+static inline int op_nt_of(int nslots) { const int hi = nslots - 1; return hi < 16 ? 1 : (hi < 32 ? 2 : 4); }   // as dtk_decode_batch_launch: from the highest slot
+// the weights as the loader leaves them: row-major upload, then the fragment-major (bf16) or pair-tiled (fp8) copy
+static int op_tiled_weights(dtk_ctx* c, size_t& off, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, GemvBArgs& g) {
+  hipStream_t s = c->stream;
+  if (W8) {
+    OPBUF(uint8_t, dW, (size_t)N * K); OPBUF(uint8_t, dT, tiled_bytes_f8(N, K)); OPBUF(float, dS, N);
+    HIPCHK(c, hipMemcpyAsync(dW, W8, (size_t)N * K, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dS, wscale, (size_t)N * 4, hipMemcpyHostToDevice, s));
+    launch_retile_f8(dW, dT, N, K, s);
+    g.W8 = dT; g.wscale = dS;
+  } else {
+    OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dT, tiled_elems(N, K));
+    HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
+    launch_retile(dW, dT, N, K, s);
+    g.W = dT;
+  }
+  g.N = N; g.K = K;
+  return DTK_OK;
+}
+// the 64 slots' flags (slots >= nslots idle) and positions
+static int op_batch_state(dtk_ctx* c, size_t& off, const int32_t* active, const int32_t* pos, int nslots, GemvBArgs& g) {
+  OPBUF(BatchState, dbs, 1); OPBUF(DecState, dst, DTK_MAX_BATCH);
+  BatchState hbs; memset(&hbs, 0, sizeof hbs);
+  DecState hst[DTK_MAX_BATCH]; memset(hst, 0, sizeof hst);
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) hbs.share_src[j] = -1;
+  for (int j = 0; j < nslots; ++j) {
+    hbs.active[j] = active[j] ? 1 : 0;
+    if (pos) { hst[j].pos = pos[j]; hst[j].next_pos = pos[j] + 1; }
+  }
+  HIPCHK(c, hipMemcpyAsync(dbs, &hbs, sizeof hbs, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dst, hst, sizeof hst, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));      // (hbs / hst live on this frame)
+  g.bs = dbs; g.st = dst; g.nt = op_nt_of(nslots);
+  return DTK_OK;
+}
+// X [nslots][K] row-major -> the fragment-major input of 4 column tiles (zero beyond nslots and in the padding of the last k-step)
+static int op_x_fragments(dtk_ctx* c, size_t& off, const uint16_t* X, int nslots, int K, bf16_t** out) {
+  const int nsteps = (K + 31) >> 5;
+  const size_t elems = (size_t)4 * nsteps * 512;
+  OPBUF(bf16_t, dXf, elems);
+  std::vector<bf16_t> h(elems, (bf16_t)0);
+  for (int j = 0; j < nslots; ++j)
+    for (int k = 0; k < K; ++k) h[host_xtile_off(j, k, nsteps)] = X[(size_t)j * K + k];
+  HIPCHK(c, hipMemcpy(dXf, h.data(), elems * 2, hipMemcpyHostToDevice));
+  *out = dXf;
+  return DTK_OK;
+}
+
+int dtk_op_gemv_b(dtk_ctx* c, int epi, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K,
+                  const uint16_t* X, const uint16_t* norm_w, float eps, const int32_t* active, const int32_t* pos, int nslots,
+                  int d, int ff, int H, int KVH, int T_max, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                  uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, uint16_t* frag_io, float* logits_io,
+                  uint16_t* xn_out, uint32_t* err_out) {
+  if (!c || !X || !active || !err_out || (!W == !W8) || (W8 && !wscale)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: null argument, or not exactly one of W / W8 + wscale");
+  if (nslots < 1 || nslots > DTK_MAX_BATCH || N < 1 || K < 8 || (K & 7)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: nslots 1..64, N >= 1, K a multiple of 8");
+  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_QKV && epi != EPI_SWIGLU && epi != EPI_LOGITS) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: unknown epilogue %d", epi);
+  if (xn_out && !norm_w) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: xn_out without norm_w");
+  if (epi == EPI_QKV) {
+    if (H < 1 || KVH < 1 || H % KVH || N != (H + 2 * KVH) * 128 || d != H * 128 || T_max < 1 || !pos || !rope_cos || !rope_sin || !q_io || !k_io || !v_io)
+      return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: QKV needs N = (H + 2 KVH) * 128, d = H * 128, positions, rope tables and q / k / v buffers");
+    for (int j = 0; j < nslots; ++j)
+      if (active[j] && (pos[j] < 0 || pos[j] >= T_max)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: slot %d: position %d of %d rows", j, pos[j], T_max);
+  } else if (epi == EPI_SWIGLU) {
+    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io || !frag_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff, y and the fragment buffer");
+  } else if (epi == EPI_LOGITS) {
+    if (!logits_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: LOGITS needs the logits buffer");
+  } else if (!y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: RESID / STORE need y");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  size_t off = 0;
+  GemvBArgs g{};
+  int rc = op_tiled_weights(c, off, W, W8, wscale, N, K, g);
+  if (rc) return rc;
+  if ((rc = op_batch_state(c, off, active, pos, nslots, g))) return rc;
+  const int nsteps = (K + 31) >> 5;
+  bf16_t* dXf = nullptr;
+  if (norm_w) {      // X = residual streams: k_rmsnorm_b writes the fragments of the active slots
+    const size_t fe = (size_t)4 * nsteps * 512;
+    OPBUF(bf16_t, dXr, (size_t)DTK_MAX_BATCH * K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dF, fe);
+    HIPCHK(c, hipMemsetAsync(dXr, 0, (size_t)DTK_MAX_BATCH * K * 2, s));
+    HIPCHK(c, hipMemcpyAsync(dXr, X, (size_t)nslots * K * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(dF, 0, fe * 2, s));
+    launch_rmsnorm_b(dXr, K, dn, dF, K, K, eps, g.bs, 16 * g.nt, s);
+    dXf = dF;
+  } else if ((rc = op_x_fragments(c, off, X, nslots, K, &dXf))) return rc;
+  g.X = dXf; g.ldx = K;
+  OPBUF(unsigned, derr, 1);
+  HIPCHK(c, hipMemsetAsync(derr, 0, 4, s));
+  g.err = derr;
+  g.d = d; g.ff = ff; g.H = H; g.KVH = KVH; g.T_max = T_max;
+  const size_t kv_slot = (size_t)(KVH > 0 ? KVH : 0) * (T_max > 0 ? T_max : 0) * 128, kv = (size_t)DTK_MAX_BATCH * kv_slot;
+  const size_t frag_elems = (size_t)4 * ((ff + 31) >> 5) * 512;
+  bf16_t *dq = nullptr, *dK = nullptr, *dV = nullptr, *dY = nullptr;
+  float* dL = nullptr;
+  if (epi == EPI_QKV) {
+    OPBUF(bf16_t, q_, (size_t)DTK_MAX_BATCH * d); OPBUF(bf16_t, k_, kv); OPBUF(bf16_t, v_, kv);
+    OPBUF(bf16_t, cs_, (size_t)T_max * 64); OPBUF(bf16_t, sn_, (size_t)T_max * 64);
+    dq = q_; dK = k_; dV = v_;
+    HIPCHK(c, hipMemcpyAsync(dq, q_io, (size_t)DTK_MAX_BATCH * d * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dK, k_io, kv * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dV, v_io, kv * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(cs_, rope_cos, (size_t)T_max * 64 * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(sn_, rope_sin, (size_t)T_max * 64 * 2, hipMemcpyHostToDevice, s));
+    g.q_out = dq; g.kcache = dK; g.vcache = dV; g.kv_slot_stride = kv_slot; g.rope_cos = cs_; g.rope_sin = sn_;
+  } else if (epi == EPI_SWIGLU) {
+    OPBUF(bf16_t, y_, frag_elems);
+    dY = y_;
+    HIPCHK(c, hipMemcpyAsync(dY, frag_io, frag_elems * 2, hipMemcpyHostToDevice, s));
+    g.Y = dY; g.ldy = ff;
+  } else if (epi == EPI_LOGITS) {
+    OPBUF(float, l_, (size_t)DTK_MAX_BATCH * N);
+    dL = l_;
+    HIPCHK(c, hipMemcpyAsync(dL, logits_io, (size_t)DTK_MAX_BATCH * N * 4, hipMemcpyHostToDevice, s));
+    g.logits = dL;
+  } else {
+    OPBUF(bf16_t, y_, (size_t)DTK_MAX_BATCH * N);
+    dY = y_;
+    HIPCHK(c, hipMemcpyAsync(dY, y_io, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyHostToDevice, s));
+    g.Y = dY; g.ldy = N;
+  }
+  launch_gemv_b(epi, g, s);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  if (epi == EPI_QKV) {
+    HIPCHK(c, hipMemcpy(q_io, dq, (size_t)DTK_MAX_BATCH * d * 2, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(k_io, dK, kv * 2, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(v_io, dV, kv * 2, hipMemcpyDeviceToHost));
+  } else if (epi == EPI_SWIGLU) {
+    HIPCHK(c, hipMemcpy(frag_io, dY, frag_elems * 2, hipMemcpyDeviceToHost));
+    for (int j = 0; j < nslots; ++j)
+      for (int i = 0; i < ff; ++i) y_io[(size_t)j * ff + i] = frag_io[host_xtile_off(j, i, (ff + 31) >> 5)];
+  } else if (epi == EPI_LOGITS) {
+    HIPCHK(c, hipMemcpy(logits_io, dL, (size_t)DTK_MAX_BATCH * N * 4, hipMemcpyDeviceToHost));
+  } else HIPCHK(c, hipMemcpy(y_io, dY, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyDeviceToHost));
+  if (xn_out) {
+    std::vector<bf16_t> f((size_t)4 * nsteps * 512);
+    HIPCHK(c, hipMemcpy(f.data(), dXf, f.size() * 2, hipMemcpyDeviceToHost));
+    for (int j = 0; j < nslots; ++j)
+      for (int k = 0; k < K; ++k) xn_out[(size_t)j * K + k] = f[host_xtile_off(j, k, nsteps)];
+  }
+  HIPCHK(c, hipMemcpy(err_out, derr, 4, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
+int dtk_op_gemv_bkp(dtk_ctx* c, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, const uint16_t* X,
+                    const int32_t* active, int nslots, const uint16_t* norm_w, float eps, uint16_t* resid_io, uint16_t* xn_io,
+                    float* part_out, uint32_t* err_out) {
+  if (!c || !X || !active || !norm_w || !resid_io || !xn_io || !part_out || !err_out || (!W == !W8) || (W8 && !wscale))
+    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: null argument, or not exactly one of W / W8 + wscale");
+  if (nslots < 1 || nslots > DTK_MAX_BATCH || N < 1 || K < 8 || (K & 7)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: nslots 1..64, N >= 1, K a multiple of 8");
+  {   // the step's own question, asked before anything is uploaded or launched (only the shape, the format and the tile count are read)
+    GemvBArgs t{};
+    float dummy = 0.f;
+    t.N = N; t.K = K; t.nt = op_nt_of(nslots); t.kpart = &dummy; t.W8 = W8;
+    if (!resid_kparts_covers(t)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: N %d, K %d, %d slots, %s weights: not covered by the K-slice kernels", N, K, nslots, W8 ? "fp8" : "bf16");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  size_t off = 0;
+  GemvBArgs g{};
+  int rc = op_tiled_weights(c, off, W, W8, wscale, N, K, g);
+  if (rc) return rc;
+  if ((rc = op_batch_state(c, off, active, nullptr, nslots, g))) return rc;
+  bf16_t* dXf = nullptr;
+  if ((rc = op_x_fragments(c, off, X, nslots, K, &dXf))) return rc;
+  g.X = dXf; g.ldx = K;
+  const int nsteps_n = (N + 31) >> 5;
+  const size_t fe = (size_t)4 * nsteps_n * 512, pe = (size_t)8 * DTK_MAX_BATCH * N;
+  OPBUF(float, dP, pe); OPBUF(bf16_t, dR, (size_t)DTK_MAX_BATCH * N); OPBUF(bf16_t, dn, N); OPBUF(bf16_t, dF, fe); OPBUF(unsigned, derr, 1);
+  std::vector<bf16_t> f(fe, (bf16_t)0);
+  for (int j = 0; j < DTK_MAX_BATCH; ++j)
+    for (int k = 0; k < N; ++k) f[host_xtile_off(j, k, nsteps_n)] = xn_io[(size_t)j * N + k];
+  HIPCHK(c, hipMemsetAsync(dP, 0xFF, pe * 4, s));
+  HIPCHK(c, hipMemsetAsync(derr, 0, 4, s));
+  HIPCHK(c, hipMemcpyAsync(dR, resid_io, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)N * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dF, f.data(), fe * 2, hipMemcpyHostToDevice, s));
+  g.kpart = dP; g.err = derr; g.d = N; g.Y = dR; g.ldy = N;
+  launch_gemv_bkp(g, s);
+  launch_resid_norm_b(dP, dR, N, dn, dF, N, eps, g.bs, 16 * g.nt, s);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpy(part_out, dP, pe * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(resid_io, dR, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(f.data(), dF, fe * 2, hipMemcpyDeviceToHost));
+  for (int j = 0; j < DTK_MAX_BATCH; ++j)
+    for (int k = 0; k < N; ++k) xn_io[(size_t)j * N + k] = f[host_xtile_off(j, k, nsteps_n)];
+  HIPCHK(c, hipMemcpy(err_out, derr, 4, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
 int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uint16_t* b, int M, int D, float eps, uint16_t* Y) {
   if (!c || !X || !w || !b || !Y || D % 8) return fail(c, DTK_ERR_ARG, "dtk_op_layernorm: bad argument");
   HIPCHK(c, hipSetDevice(c->device));

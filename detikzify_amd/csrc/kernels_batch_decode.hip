@@ -83,6 +83,13 @@ __global__ __launch_bounds__(WAVES * 64, (MODE & 8) ? 4 : 1) void k_gemv_b(GemvB
     const int tn_max = ((a.N + 15) >> 4) - 1;
     if (tn > tn_max) tn = tn_max;
     wrow[t] = (F8 ? a.W8 : reinterpret_cast<const unsigned char*>(a.W)) + ((size_t)tn * units_per_row * 64 + lane) * 16;
+    if (EPI == EPI_SWIGLU && (a.ff & 15)) {
+      // ff % 16 == 8: the up rows start at ff, in the MIDDLE of a stored tile.  The lane's operand row is ff + ... + (lane & 15) wherever
+      // that lies: row r sits in stored tile r >> 4 at lane slot (lane >> 4) * 16 + (r & 15) — the address above when r0 % 16 == 0.
+      int r = gb_tile_row0<EPI, T>(a, blk, t) + (lane & 15);
+      if (r > tn_max * 16 + 15) r = tn_max * 16 + 15;
+      wrow[t] = (F8 ? a.W8 : reinterpret_cast<const unsigned char*>(a.W)) + ((size_t)(r >> 4) * units_per_row * 64 + (lane >> 4) * 16 + (r & 15)) * 16;
+    }
   }
   const bf16_t* xlane = a.X + lane * 8;   // B fragment of tile (nt, k-step): slot = nt*16 + (lane & 15), fragment-major X (common.h)
 
@@ -274,8 +281,8 @@ static int resid_waves() {
 // 6 = twice the tiles for qkv and lm_head only; 2 = auto = 6 at 64 slots, else 0.  Measured at 64 slots, ds-7b
 // (profiles/r02_batch_wide_kernel_stats.csv vs r02_batch_tail_kernel_stats.csv): qkv 33.1 -> 27.9 us (192 blocks: one round, half
 // the x fragments through L2), lm_head 67.9 -> 62.2, gate/up 48.5 -> 48.4 (344 blocks: 1.34 rounds on 256 CUs eat the gain),
-// o_proj / down 24.1 -> 29.2 (128 blocks).  Results are bit-identical across modes (a row's k order depends on the wave split
-// of K only).
+// o_proj / down 24.1 -> 29.2 (128 blocks).  Results are bit-identical across the 8-wave modes (a row's k order depends on the wave
+// split of K only; the 4-wave modes 3 / 5 cut K into 4 slices: equal to fp32 rounding, not bit for bit).
 static int g_resid_split = 1;   // 1 (default): N = d roles at 64 slots as 2 row tiles x 32 slots per block (dtk_set_option "resid_split"): o_proj + down 24.0 -> 22.5 us avg
 void set_resid_split(int v) { g_resid_split = v; }
 static int g_gb_wide = -1;

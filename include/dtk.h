@@ -554,6 +554,35 @@ int  dtk_op_attn_decode(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, cons
 int  dtk_op_attn_decode_b(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
                           const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
                           int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out);
+/* The weight kernels of the batched (<= 64 slot) decode step alone, op by op (additive, ABI 7); bf16 bits throughout.
+ * dtk_op_gemv_b: one role through the step's dispatcher; the process-wide options ("gemv_bx", "gemv_bl", "gemv_bc", "gemv_bus",
+ * "gemv_b_wide", "resid_split", "gemv_br_wd", "gemv_loaders", "gemv_xw") choose the kernel as they do in the step.  epi: 0 STORE,
+ * 1 RESID, 2 QKV, 3 SWIGLU, 4 LOGITS.  Weights: W [N][K] bf16, or W8 [N][K] e4m3 bytes + wscale [N] (per-row power of two) — exactly
+ * one of the two; they are tiled on the device by the loader's kernels.  X [nslots][K]; with norm_w [K] (+ eps) X is a residual stream
+ * and the step's RMSNorm kernel produces the GEMV input (xn_out [nslots][K], optional: those rows; idle slots' rows are 0), without
+ * it X is the input itself.  active [nslots], pos [nslots] (QKV; 0 <= pos < T_max for active slots); slots >= nslots are idle; the
+ * column-tile count follows from nslots as in dtk_decode_batch_launch (1: <= 16, 2: <= 32, else 4).  K % 8 == 0.
+ * Every result buffer is IN/OUT and sized for all 64 slots, so that a caller can pre-fill it and see what was written:
+ *   QKV (N = (H + 2 KVH) * 128, d = H * 128, rope_cos / rope_sin [T_max][64]): q_io [64][d], k_io / v_io [64][KVH][T_max][128];
+ *   RESID (y += bf16(W.x)) / STORE: y_io [64][N];   LOGITS: logits_io [64][N] fp32;
+ *   SWIGLU (N = 2 ff, ff % 8 == 0 as in dtk_create, rows = gate rows then up rows): frag_io = the raw fragment-major activation buffer, 4 * ceil(ff / 32) * 512
+ *   elements (slot s, row i at ((s / 16 * ceil(ff / 32) + i / 32) * 64 + i % 32 / 8 * 16 + s % 16) * 8 + i % 8), and y_io
+ *   [nslots][ff] (out only) = the same values row-major.
+ * Buffers a role does not use may be NULL.  err_out = the launch's count of expired in-kernel hand-off waits (0 unless a kernel hung). */
+int  dtk_op_gemv_b(dtk_ctx* ctx, int epi, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K,
+                   const uint16_t* X, const uint16_t* norm_w, float eps, const int32_t* active, const int32_t* pos, int nslots,
+                   int d, int ff, int H, int KVH, int T_max, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                   uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, uint16_t* frag_io, float* logits_io,
+                   uint16_t* xn_out, uint32_t* err_out);
+/* dtk_op_gemv_bkp: the N = d roles of the 33..64-slot step as its two launches — the K-slice weight kernel ("gemv_bkl" 0: k_gemv_bkp,
+ * 1: k_gemv_bkl, with "gemv_xw" x waves), then k_resid_norm_b with norm_w [N].  resid_io [64][N]: the residual streams, updated in place
+ * for the active slots; xn_io [64][N]: the normalised rows (row-major here, fragment-major on the device); part_out [8][64][N] fp32:
+ * the eight K-slice partials (written for all 64 columns).  DTK_ERR_ARG, with nothing launched and no buffer touched, for a shape the
+ * step itself would not give to these kernels (fewer than 33 slots, N other than 2048 / 4096, a K that leaves one of the 8 slices
+ * empty, fp8 weights with "gemv_bkl" 0). */
+int  dtk_op_gemv_bkp(dtk_ctx* ctx, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, const uint16_t* X,
+                     const int32_t* active, int nslots, const uint16_t* norm_w, float eps, uint16_t* resid_io, uint16_t* xn_io,
+                     float* part_out, uint32_t* err_out);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */
