@@ -208,6 +208,8 @@ SYMBOLS = {
     "dtk_op_gemv_bkp": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    # additive (ABI stays 7): dtk_op_gemv on MXFP4 weights (the loader's quantiser + the decode kernel); last = de-quantised W or NULL
+    "dtk_op_gemv_q4": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P]),
     "dtk_mx_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
     "dtk_op_gemv_mx": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "dtk_op_attention": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),

@@ -67,6 +67,8 @@ struct LayerW {
   bf16_t* p_wgui = nullptr;          // gate/up again with its row tiles in (gate, up) pair order: the W stage of the SwiGLU-fused prefill GEMM (models whose gate/up role is one chain)
   uint8_t *q_wqkv = nullptr, *q_wo = nullptr, *q_wgu = nullptr, *q_wdown = nullptr;  // fp8 e4m3 copies (weight_format 1)
   float *s_wqkv = nullptr, *s_wo = nullptr, *s_wgu = nullptr, *s_wdown = nullptr;    // per-row power-of-two scales
+  uint8_t *f4_wqkv = nullptr, *f4_wo = nullptr, *f4_wgu = nullptr, *f4_wdown = nullptr;  // MXFP4 E2M1 codes (weight_format 2): [N][ceil(K/32)*16] bytes
+  uint8_t *e4_wqkv = nullptr, *e4_wo = nullptr, *e4_wgu = nullptr, *e4_wdown = nullptr;  // ... and their E8M0 block scales: [N][ceil(K/32)]
   uint8_t *t8_wqkv = nullptr, *t8_wo = nullptr, *t8_wgu = nullptr, *t8_wdown = nullptr;  // fp8 pair-tiled copies (batched decode, fp8)
   uint8_t *m_wqkv = nullptr, *m_wo = nullptr, *m_wgu = nullptr, *m_wdown = nullptr;      // fp8 MX tiles (fp8 matrix-core step; down in groups of 16)
 };
@@ -182,8 +184,8 @@ struct dtk_ctx {
 
   // host state
   SeqHost seq0;              // the single-sequence API (dtk_prefill / dtk_decode*)
-  int wfmt = 0;              // 0 = bf16 decoder weights, 1 = fp8 e4m3 + per-row 2^e scale (dtk_config.reserved[1])
-  bool fp8_ready = false;
+  int wfmt = 0;              // 0 = bf16 decoder weights, 1 = fp8 e4m3 + per-row 2^e scale, 2 = MXFP4 layers + fp8 lm_head (dtk_config.reserved[1])
+  bool fp8_ready = false;    // the quantised copies of wfmt 1 / 2 match the bf16 masters
   uint8_t* q_lm_head = nullptr;
   float* s_lm_head = nullptr;
   uint64_t cached_image_key = 0;
@@ -527,6 +529,20 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
     c->q_lm_head = P.take<uint8_t>((size_t)V * d);
     c->s_lm_head = P.take<float>(V);
   }
+  if (c->wfmt == 2) {   // MXFP4 layers (codes + block scales, rows padded to whole 32-weight blocks) + the fp8 lm_head
+    for (int i = 0; i < L; ++i) {
+      uint8_t* q1 = P.take<uint8_t>((size_t)qkvn * mxfp4_row_bytes(d));   uint8_t* s1 = P.take<uint8_t>((size_t)qkvn * mxfp4_row_scales(d));
+      uint8_t* q2 = P.take<uint8_t>((size_t)d * mxfp4_row_bytes(d));      uint8_t* s2 = P.take<uint8_t>((size_t)d * mxfp4_row_scales(d));
+      uint8_t* q3 = P.take<uint8_t>((size_t)2 * ff * mxfp4_row_bytes(d)); uint8_t* s3 = P.take<uint8_t>((size_t)2 * ff * mxfp4_row_scales(d));
+      uint8_t* q4 = P.take<uint8_t>((size_t)d * mxfp4_row_bytes(ff));     uint8_t* s4 = P.take<uint8_t>((size_t)d * mxfp4_row_scales(ff));
+      if (reg) {
+        LayerW& w = c->layers[i];
+        w.f4_wqkv = q1; w.e4_wqkv = s1; w.f4_wo = q2; w.e4_wo = s2; w.f4_wgu = q3; w.e4_wgu = s3; w.f4_wdown = q4; w.e4_wdown = s4;
+      }
+    }
+    c->q_lm_head = P.take<uint8_t>((size_t)V * d);
+    c->s_lm_head = P.take<float>(V);
+  }
   if (c->nb > 0) {
     c->kv_slot_stride = (size_t)L * 2 * c->KVH * T * 128;
     c->kvb = P.take<bf16_t>((size_t)c->nb * c->kv_slot_stride);
@@ -823,6 +839,7 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
     g.pm = c->pm; g.pl = c->pl; g.po = c->po; g.S = c->S;
     // 1. input_layernorm + q/k/v projections + RoPE + KV append
     g.W = w.wqkv; g.W8 = w.q_wqkv; g.wscale = w.s_wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1;
+    g.W4 = w.f4_wqkv; g.S4 = w.e4_wqkv;      // MXFP4 contexts: the four layer roles stream codes + block scales (null otherwise)
     g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l);
     launch_gemv(PRO_RMSNORM, EPI_QKV, g, s);
     // 2. split-K attention over the cache
@@ -836,20 +853,23 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
     launch_attn_decode(ad, s);
     // 3. (combine +) o_proj + residual
     g.W = w.wo; g.W8 = w.q_wo; g.wscale = w.s_wo; g.N = c->d; g.K = c->d; g.y = c->x;
+    g.W4 = w.f4_wo; g.S4 = w.e4_wo;
     const bool partials = ad.combine == 0 && !(ad.threads && ad.S == 1);   // o_proj's prologue reduces the split partials
     if (!partials) { g.x = c->attn_out; launch_gemv(PRO_COPY, EPI_RESID, g, s); }
     else launch_gemv(PRO_ATTN, EPI_RESID, g, s);
     // 4. post_attention_layernorm + gate/up + SiLU*mul
     g.W = w.wgu; g.W8 = w.q_wgu; g.wscale = w.s_wgu; g.N = 2 * c->ff; g.K = c->d; g.x = c->x; g.norm_w = w.ln2; g.y = c->act;
+    g.W4 = w.f4_wgu; g.S4 = w.e4_wgu;
     const bool probe_here = with_probe && (l == c->L / 2);
     if (probe_here) (void)hipEventRecord(c->probe_a, s);
     launch_gemv(PRO_RMSNORM, EPI_SWIGLU, g, s);
     if (probe_here) (void)hipEventRecord(c->probe_b, s);
     // 5. down + residual
     g.W = w.wdown; g.W8 = w.q_wdown; g.wscale = w.s_wdown; g.N = c->d; g.K = c->ff; g.x = c->act; g.y = c->x;
+    g.W4 = w.f4_wdown; g.S4 = w.e4_wdown;
     launch_gemv(PRO_COPY, EPI_RESID, g, s);
   }
-  GemvArgs g{};
+  GemvArgs g{};      // lm_head: fp8 in an MXFP4 context too (q_lm_head / s_lm_head)
   g.W = c->lm_head; g.W8 = c->q_lm_head; g.wscale = c->s_lm_head; g.N = c->V; g.K = c->d; g.x = c->x; g.norm_w = c->final_norm;
   g.eps = c->cfg.rms_eps; g.logits = c->logits;
   launch_gemv(PRO_RMSNORM, EPI_LOGITS, g, s);
@@ -1035,9 +1055,17 @@ void batch_step_launches_mv(dtk_ctx* c) {
 // fp8 mode: quantise the decoder Linear weights (per-row power-of-two scale) and overwrite the bf16 masters
 // with the de-quantised values, so every consumer (prefill GEMM, tiled copy, read-back, oracle) sees the
 // same effective weights as the fp8 decode kernels
+// MXFP4 mode (wfmt 2): the same for the four layer roles with launch_quant_mxfp4_rows (block scales); lm_head takes the fp8 path
 void ensure_fp8_weights(dtk_ctx* c) {
-  if (c->wfmt != 1 || c->fp8_ready) return;
-  for (int l = 0; l < c->L; ++l) {
+  if (c->wfmt == 0 || c->fp8_ready) return;
+  for (int l = 0; l < c->L && c->wfmt == 2; ++l) {
+    LayerW& w = c->layers[l];
+    launch_quant_mxfp4_rows(w.wqkv, w.f4_wqkv, w.e4_wqkv, c->d + 2 * c->KVH * c->hd, c->d, c->stream);
+    launch_quant_mxfp4_rows(w.wo, w.f4_wo, w.e4_wo, c->d, c->d, c->stream);
+    launch_quant_mxfp4_rows(w.wgu, w.f4_wgu, w.e4_wgu, 2 * c->ff, c->d, c->stream);
+    launch_quant_mxfp4_rows(w.wdown, w.f4_wdown, w.e4_wdown, c->d, c->ff, c->stream);
+  }
+  for (int l = 0; l < c->L && c->wfmt == 1; ++l) {
     LayerW& w = c->layers[l];
     launch_quant_fp8_rows(w.wqkv, w.q_wqkv, w.s_wqkv, c->d + 2 * c->KVH * c->hd, c->d, c->stream);
     launch_quant_fp8_rows(w.wo, w.q_wo, w.s_wo, c->d, c->d, c->stream);
@@ -1228,6 +1256,8 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
     return fail(nullptr, DTK_ERR_ARG, "head_dim 64: batched decode slots (batch_slots = %d) have no head_dim-64 kernels yet", cfg->reserved[0]);
   if (cfg->head_dim == 64 && getenv("DTK_ATTN_THREADS") && atoi(getenv("DTK_ATTN_THREADS")) == 0)   // k_attn_decode / _head: hd 128 only
     return fail(nullptr, DTK_ERR_ARG, "DTK_ATTN_THREADS=0: the contiguous-split decode attention has no head_dim-64 kernel (256, 512 or 1024)");
+  if (cfg->reserved[1] == 2 && cfg->reserved[0] > 0)   // refused before anything is allocated
+    return fail(nullptr, DTK_ERR_ARG, "weight_format mxfp4: MXFP4 weights have no batched-slot or multi-vector kernels yet (batch_slots = %d; use batch_slots = 0)", cfg->reserved[0]);
   if (cfg->hidden != cfg->heads * cfg->head_dim)
     return fail(nullptr, DTK_ERR_ARG, "hidden (%d) != heads*head_dim", cfg->hidden);
   if (cfg->reserved[2] < 0 || (cfg->reserved[2] > 0 && cfg->heads % cfg->reserved[2] != 0))
@@ -1262,7 +1292,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   // (32 slots already give 8192 blocks: 4.53 ms/step vs 4.69 with 16)
   c->S = cfg->attn_splits > 0 ? cfg->attn_splits : 4;     // tile-interleaved splits: 4 x 128 rows cover 512 keys per memory round trip
   if (const char* es = getenv("DTK_ATTN_SPLITS")) { const int v = atoi(es); if (v >= 1 && v <= 16) c->S = v; }   // tuning aid
-  c->wfmt = cfg->reserved[1] == 1 ? 1 : 0;
+  c->wfmt = cfg->reserved[1] == 1 ? 1 : (cfg->reserved[1] == 2 ? 2 : 0);
   // up to 64 decoding slots (one, two or four 16-column MFMA tiles) + up to 8 slots that are only ever prefilled / forked from
   // (prefix cache: one per image in flight, BASELINE config 5 = 8 images)
   c->nb = cfg->reserved[0] < 0 ? 0 : (cfg->reserved[0] > DTK_MAX_SLOTS ? DTK_MAX_SLOTS : cfg->reserved[0]);
@@ -1347,8 +1377,14 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
     const uint64_t rows = (uint64_t)3 * c->d + 2 * kvd + (uint64_t)2 * c->ff;
     c->stats.weight_bytes_per_token = (lin + 4 * rows + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
   }
+  if (c->wfmt == 2) {  // 16 code bytes + 1 scale byte per 32-weight block (rows padded to whole blocks); lm_head fp8 + fp32 row scales; norms bf16
+    const uint64_t bd = mxfp4_row_scales(c->d), bf = mxfp4_row_scales(c->ff);
+    const uint64_t blocks = ((uint64_t)2 * c->d + 2 * kvd + (uint64_t)2 * c->ff) * bd + (uint64_t)c->d * bf;
+    c->stats.weight_bytes_per_token = (17 * blocks + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
+  }
   c->stats.kv_bytes_per_ctx_token = (uint64_t)2 * c->L * kvd * 2;
   c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * c->d * (c->wfmt == 1 ? 1 : 2);
+  if (c->wfmt == 2) c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * 17 * mxfp4_row_scales(c->d);
   *out = c;
   // Batched attention shape, a property of the CONTEXT (like the multi-vector family): 64 decoding slots -> shared prefixes on the
   // matrix cores + 2-wave tail blocks; fewer -> the per-slot walk with 4-wave blocks.  Measured over a rollout's private lengths
@@ -2591,6 +2627,8 @@ int dtk_get_stats(dtk_ctx* c, dtk_stats* out) {
 // In-situ microbenchmark of one decode GEMV role over all layers (distinct weights per launch,
 // so nothing is served from the 256 MB Infinity Cache): avg microseconds per launch via HIP events.
 // role: 0 qkv, 1 o_proj, 2 gate/up, 3 down, 4 lm_head.  Clobbers the decode state.
+// variant | 0x800 (with 0xff): the role streams the context's weight FORMAT as a decode step does (fp8 rows + row scales, MXFP4 codes +
+// block scales, lm_head fp8 in both); without the bit the bf16 masters are streamed whatever the format (what the bit-less callers measure).
 int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
   if (!c || !avg_us || reps < 1) return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: bad argument");
   HIPCHK(c, hipSetDevice(c->device));
@@ -2598,6 +2636,10 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
   if (role < 0 || role > 4) return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: role %d (0 qkv, 1 o_proj, 2 gate/up, 3 down, 4 lm_head)", role);
   const bool same_layer = (variant & 0x100) != 0;  // every launch re-reads layer 0 (Infinity Cache probe)
   const int plain = (variant >> 9) & 3;            // 0x200: same weights through PRO_COPY + EPI_STORE; 0x400: PRO_RMSNORM + EPI_STORE
+  const bool fmt = (variant & 0x800) != 0;
+  if (fmt && ((variant & 0xff) != 0xff || plain))   // the numbered variants and the plain probes are bf16 instantiations
+    return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: 0x800 (the context's weight format) goes with variant 0xff only");
+  if (fmt) ensure_fp8_weights(c);
   variant &= 0xff;
   const bool shipped = variant == 0xff;            // 0xff: whatever launch_gemv picks for this role and model (the kernel a decode step runs)
   auto launch = [&](int pro, int epi, const GemvArgs& g) { if (shipped) launch_gemv(pro, epi, g, s); else launch_gemv_variant(pro, epi, variant, g, s); };
@@ -2617,6 +2659,13 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
       }
       g.eps = c->cfg.rms_eps; g.st = c->st; g.T_max = c->Tmax; g.d = c->d; g.ff = c->ff; g.H = c->H; g.KVH = c->KVH; g.hd = c->hd;
       g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.pm = c->pm; g.pl = c->pl; g.po = c->po; g.S = c->S;
+      if (fmt) {
+        if (role == 0) { g.W8 = w.q_wqkv; g.wscale = w.s_wqkv; g.W4 = w.f4_wqkv; g.S4 = w.e4_wqkv; }
+        else if (role == 1) { g.W8 = w.q_wo; g.wscale = w.s_wo; g.W4 = w.f4_wo; g.S4 = w.e4_wo; }
+        else if (role == 2) { g.W8 = w.q_wgu; g.wscale = w.s_wgu; g.W4 = w.f4_wgu; g.S4 = w.e4_wgu; }
+        else if (role == 3) { g.W8 = w.q_wdown; g.wscale = w.s_wdown; g.W4 = w.f4_wdown; g.S4 = w.e4_wdown; }
+        else { g.W8 = c->q_lm_head; g.wscale = c->s_lm_head; }
+      }
       if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l); launch(PRO_RMSNORM, EPI_QKV, g); }
       else if (role == 1) { g.W = w.wo; g.N = c->d; g.K = c->d; g.x = c->attn_out; g.y = c->q; launch(PRO_COPY, EPI_RESID, g); }
       else if (role == 2) { g.W = w.wgu; g.N = 2 * c->ff; g.K = c->d; g.x = c->x; g.norm_w = w.ln2; g.y = c->act; launch(PRO_RMSNORM, EPI_SWIGLU, g); }
@@ -3208,6 +3257,30 @@ int dtk_op_gemv(dtk_ctx* c, const uint16_t* W, const uint16_t* x, const uint16_t
   g.W = dW; g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.y = dy;
   launch_gemv(mode == 1 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, g, s);
   HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)N * 2, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  return DTK_OK;
+}
+
+// The MXFP4 GEMV on host buffers: W [N][K] row-major bf16 goes through the shipped quantiser (launch_quant_mxfp4_rows) and the shipped
+// launch_gemv with EPI_STORE (mode 0: y = W_eff . x, mode 1: y = W_eff . rmsnorm(x, norm_w)); w_eff_out (optional, [N][K]) receives the
+// de-quantised weights the kernel computed with.  Any context serves (the op brings its own weights).
+int dtk_op_gemv_q4(dtk_ctx* c, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w, int N, int K, int mode, float eps, uint16_t* y, uint16_t* w_eff_out) {
+  if (!c || !W || !x || !y || N < 1 || K < 8 || (K % 8) || (mode != 0 && mode != 1) || (mode == 1 && !norm_w)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_q4: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t off = 0;
+  OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dy, N);
+  OPBUF(uint8_t, dQ, (size_t)N * mxfp4_row_bytes(K)); OPBUF(uint8_t, dS, (size_t)N * mxfp4_row_scales(K));
+  hipStream_t s = c->stream;
+  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)K * 2, hipMemcpyHostToDevice, s));
+  if (mode == 1) HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
+  launch_quant_mxfp4_rows(dW, dQ, dS, N, K, s);
+  GemvArgs g{};
+  g.W = dW; g.W4 = dQ; g.S4 = dS; g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.y = dy;
+  launch_gemv(mode == 1 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, g, s);
+  HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)N * 2, hipMemcpyDeviceToHost, s));
+  if (w_eff_out) HIPCHK(c, hipMemcpyAsync(w_eff_out, dW, (size_t)N * K * 2, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   HIPCHK(c, hipGetLastError());
   return DTK_OK;

@@ -38,9 +38,14 @@ struct GemvArgs {
   int H;                 // EPI_QKV: query heads; rows = [H q heads | KVH k heads | KVH v heads] x 128, N == (H + 2*KVH)*128
   int KVH;               //          key/value heads (GQA: H % KVH == 0; MHA: KVH == H)
   int hd = 128;          // EPI_QKV / PRO_ATTN: head dim, 128 or 64 (the "128" of the layouts above; every other role ignores it)
+  // MXFP4 copy of W, or null (then W8 / W decide): W4 = E2M1 codes [N][ceil(K/32)*16] bytes (byte i of a row = weights 2i low nibble,
+  // 2i + 1 high nibble; rows zero-padded to whole 32-weight blocks), S4 = E8M0 block scales [N][ceil(K/32)].  No row scale.
+  const uint8_t* W4 = nullptr;
+  const uint8_t* S4 = nullptr;
 };
 
 void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s);
+void launch_gemv_q4(int pro, int epi, const GemvArgs& a, hipStream_t s);   // the MXFP4 instantiations (launch_gemv dispatches here when a.W4)
 void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s);
 void set_gemv_default_variant(int epi, int variant);
 
@@ -350,6 +355,11 @@ bool launch_attention_seg(const AttnArgs& a, int shared_len, const int2* rows, h
 
 // per-row fp8 quantisation with a power-of-two scale; W is overwritten with the de-quantised values
 void launch_quant_fp8_rows(bf16_t* W, uint8_t* W8, float* scale, int N, int K, hipStream_t s);
+// OCP MXFP4 quantisation of [N][K] bf16 rows (contiguous), one 32-weight block along K at a time: E8M0 scale e = the smallest with
+// amax * 2^-e <= 6 (all-zero block: e = 0), codes = RNE of w * 2^-e onto the E2M1 grid.  W is overwritten with the de-quantised values.
+static inline size_t mxfp4_row_bytes(int K) { return (size_t)((K + 31) >> 5) * 16; }
+static inline size_t mxfp4_row_scales(int K) { return (size_t)((K + 31) >> 5); }
+void launch_quant_mxfp4_rows(bf16_t* W, uint8_t* W4, uint8_t* S4, int N, int K, hipStream_t s);
 void launch_fill_synth(bf16_t* dst, int64_t n, uint64_t seed, uint32_t tag, float scale,
                        float offset, hipStream_t s);
 void launch_f32_to_bf16(const float* src, bf16_t* dst, int64_t n, hipStream_t s);

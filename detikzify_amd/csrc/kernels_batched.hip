@@ -2095,3 +2095,70 @@ __global__ __launch_bounds__(256) void k_quant_fp8_rows(bf16_t* W, uint8_t* W8, 
 void launch_quant_fp8_rows(bf16_t* W, uint8_t* W8, float* scale, int N, int K, hipStream_t s) {
   hipLaunchKernelGGL(k_quant_fp8_rows, dim3(N), dim3(256), 0, s, W, W8, scale, N, K);
 }
+
+// ------------------------------------------------------------------------------------------
+// OCP MXFP4 weight quantisation (weight_format 2), a thread per 32-weight block along K, a thread block per row.  Block scale 2^e
+// with e the smallest exponent at which amax * 2^-e <= 6 (the largest E2M1 value): from the bits of amax = m * 2^E, e = E - 2, one
+// more if m > 1.5 (mx_exp's convention with 6 in place of 448); an all-zero block takes e = 0; e >= -126 so that the scale is a
+// normal float.  Codes: round-to-nearest-even of |w| * 2^-e (exact: a power of two) onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}, "even" being
+// the code's mantissa bit (2.5 -> 2, 3.5 -> 4, 5 -> 4, 0.25 -> 0, 0.75 -> 1), sign in bit 3.  It never saturates.  The ragged last
+// block of a row (K % 32 != 0) takes amax over its real weights and zero codes as padding.  Byte i of a block = weights 2i (low
+// nibble) and 2i + 1 (high nibble).  The bf16 master row is overwritten with the de-quantised values, as k_quant_fp8_rows does.
+__device__ __forceinline__ int mxfp4_exp(float amax) {
+  const unsigned u = __float_as_uint(amax) & 0x7fffffffu;
+  if (u == 0u) return 0;
+  const int e = (int)(u >> 23) - 127 - 2 + ((u & 0x7fffffu) > 0x400000u ? 1 : 0);
+  return max(-126, min(126, e));
+}
+__device__ __forceinline__ unsigned e2m1_code(float w, float inv) {
+  const float v = fabsf(w) * inv;
+  const unsigned m = (unsigned)(v > 0.25f) + (unsigned)(v >= 0.75f) + (unsigned)(v > 1.25f) + (unsigned)(v >= 1.75f) +
+                     (unsigned)(v > 2.5f) + (unsigned)(v >= 3.5f) + (unsigned)(v > 5.f);
+  return m | (w < 0.f ? 8u : 0u);
+}
+__device__ __forceinline__ float e2m1_value(unsigned code) {
+  const unsigned m = code & 7u;
+  const float mag = m < 4u ? 0.5f * (float)m : (m == 4u ? 2.f : (m == 5u ? 3.f : (m == 6u ? 4.f : 6.f)));
+  return (code & 8u) ? -mag : mag;
+}
+__global__ __launch_bounds__(256) void k_quant_mxfp4_rows(bf16_t* W, uint8_t* W4, uint8_t* S4, int N, int K) {
+  const int row = blockIdx.x;
+  const int KC = (K + 31) >> 5;
+  bf16_t* w = W + (size_t)row * K;
+  for (int c = threadIdx.x; c < KC; c += 256) {
+    const int k0 = c * 32, n = min(32, K - k0);
+    // the block as 16-byte loads (K % 8 == 0: n is 8, 16, 24 or 32 and the block starts 16-byte aligned)
+    u32x4* w4 = reinterpret_cast<u32x4*>(w + k0);
+    float v[32];
+    float amax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      u32x4 t = {0u, 0u, 0u, 0u};
+      if (8 * j < n) t = w4[j];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[8 * j + 2 * e] = pk_lo(t[e]); v[8 * j + 2 * e + 1] = pk_hi(t[e]);
+        amax = fmaxf(amax, fmaxf(fabsf(v[8 * j + 2 * e]), fabsf(v[8 * j + 2 * e + 1])));
+      }
+    }
+    const int e = mxfp4_exp(amax);
+    const float inv = __uint_as_float((unsigned)(127 - e) << 23), sc = __uint_as_float((unsigned)(127 + e) << 23);
+    u32x4 q = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      u32x4 d;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned c0 = e2m1_code(v[8 * j + 2 * e], inv), c1 = e2m1_code(v[8 * j + 2 * e + 1], inv);
+        q[j] |= (c0 | (c1 << 4)) << (8 * e);
+        d[e] = pack2(e2m1_value(c0) * sc, e2m1_value(c1) * sc);
+      }
+      if (8 * j < n) w4[j] = d;
+    }
+    *reinterpret_cast<u32x4*>(W4 + ((size_t)row * KC + c) * 16) = q;
+    S4[(size_t)row * KC + c] = (uint8_t)(e + 127);
+  }
+}
+void launch_quant_mxfp4_rows(bf16_t* W, uint8_t* W4, uint8_t* S4, int N, int K, hipStream_t s) {
+  hipLaunchKernelGGL(k_quant_mxfp4_rows, dim3(N), dim3(256), 0, s, W, W4, S4, N, K);
+}

@@ -86,8 +86,11 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0
 // sums meet in LDS in a fixed order (deterministic).  For the N = d roles (o_proj, down: only d rows) this puts KS times the
 // waves, hence loads, in flight per row; the block then owns WAVES / KS row-chunks.
 // HD: head dim of the EPI_QKV rows / the PRO_ATTN partials (128, or 64: a unit is the pair (i, i+32), a head 8 chunks of x).
-template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128>
+// F4: MXFP4 rows (a.W4 codes, a.S4 block scales; gemv_inl.h): a chunk = one 32-weight block, x swizzled in LDS (f4_xswz) and
+// zero-padded to whole blocks, no row scale in the epilogue.  Every F4 branch is compile-time: the bf16 / fp8 code is unchanged.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128, bool F4 = false>
 __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
+  static_assert(!(F4 && F8), "one weight format");
   constexpr bool PAIRED = (EPI == EPI_QKV) || (EPI == EPI_SWIGLU);
   constexpr int NR = PAIRED ? 2 * R : R;
   constexpr int THREADS = WAVES * 64;
@@ -99,10 +102,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* xs = reinterpret_cast<u32x4*>(smem);
   const int K8 = a.K >> 3;                     // 16-byte chunks of x (bf16)
-  const int KC = F8 ? (a.K >> 4) : K8;         // 16-byte chunks of one weight row
-  const size_t row_bytes = F8 ? (size_t)a.K : (size_t)a.K * 2;
-  const unsigned char* Wb = reinterpret_cast<const unsigned char*>(F8 ? (const void*)a.W8 : (const void*)a.W);
-  float* red = reinterpret_cast<float*>(smem + (size_t)K8 * 16);  // WAVES floats of scratch
+  const int KC = F4 ? ((a.K + 31) >> 5) : (F8 ? (a.K >> 4) : K8);         // 16-byte chunks of one weight row
+  const size_t row_bytes = F4 ? (size_t)KC * 16 : (F8 ? (size_t)a.K : (size_t)a.K * 2);
+  const unsigned char* Wb = reinterpret_cast<const unsigned char*>(F4 ? (const void*)a.W4 : (F8 ? (const void*)a.W8 : (const void*)a.W));
+  float* red = reinterpret_cast<float*>(smem + (size_t)(F4 ? f4_xrows(KC) : K8) * 16);  // WAVES floats of scratch
+#define XI(c) (F4 ? f4_xswz(c) : (c))          // where 16-byte piece c of x lies in LDS
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -119,6 +123,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   int unit0 = chunk * R;
 
   const u32x4* rows[NR];
+  const uint8_t* srows[NR];                    // F4: the rows' block scales
   auto set_rows = [&](int u0) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -140,6 +145,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       } else {
         rows[j] = reinterpret_cast<const u32x4*>(Wb + (size_t)r0 * row_bytes);
       }
+      if (F4) {
+        if (PAIRED) { srows[2 * j] = a.S4 + (size_t)r0 * KC; srows[2 * j + 1] = a.S4 + (size_t)r1 * KC; }
+        else srows[j] = a.S4 + (size_t)r0 * KC;
+      }
     }
   };
   set_rows(unit0);
@@ -149,10 +158,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   const int G = KS > 1 ? (Gall - ks + KS - 1) / KS : Gall;    // k-groups of this wave: ks, ks + KS, ...
 #define GIDX(g) (KS > 1 ? ks + KS * (g) : (g))
   u32x4 wa[NR][U], wb[NR][U];
+  unsigned sa[NR][U], sb[NR][U];               // F4: the stages' block scales
   float acc[NR];
+#define GLOAD(w, sc, g) do { if (F4) gemv_load_f4<NR, U>(w, sc, rows, srows, (g), lane, KC); else gemv_load<NR, U>(w, rows, (g), lane, KC); } while (0)
+#define GFMA(w, sc, g) do { if (F4) gemv_fma_f4<NR, U>(acc, w, sc, xs, (g), lane, KC); else if (F8) gemv_fma_f8<NR, U>(acc, w, xs, (g), lane, KC); else gemv_fma<NR, U>(acc, w, xs, (g), lane, KC); } while (0)
 
   // first stage of weights goes in flight before the prologue touches x
-  if (G > 0) gemv_load<NR, U>(wa, rows, GIDX(0), lane, KC);
+  if (G > 0) GLOAD(wa, sa, GIDX(0));
 
   // operands of the epilogue (see gemv_epilogue): issued now, consumed after the last weight chunk
   float pre0[R], pre1[R];
@@ -178,7 +190,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   // ---- prologue: build the bf16 input vector in LDS
   if (PRO == PRO_COPY) {
     const u32x4* x4 = reinterpret_cast<const u32x4*>(a.x);
-    for (int c = tid; c < K8; c += THREADS) xs[c] = x4[c];
+    for (int c = tid; c < K8; c += THREADS) xs[XI(c)] = x4[c];
   } else if (PRO == PRO_RMSNORM) {
     const u32x4* x4 = reinterpret_cast<const u32x4*>(a.x);
     const u32x4* w4 = reinterpret_cast<const u32x4*>(a.norm_w);
@@ -217,8 +229,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
         o0[e] = pack2(pk_lo(g0[e]) * rbf(pk_lo(v0[e]) * inv), pk_hi(g0[e]) * rbf(pk_hi(v0[e]) * inv));
         o1[e] = pack2(pk_lo(g1[e]) * rbf(pk_lo(v1[e]) * inv), pk_hi(g1[e]) * rbf(pk_hi(v1[e]) * inv));
       }
-      if (h0) xs[c0] = o0;
-      if (h1) xs[c1] = o1;
+      if (h0) xs[XI(c0)] = o0;
+      if (h1) xs[XI(c1)] = o1;
     } else {
       float ss = 0.f;
       for (int c = tid; c < K8; c += THREADS) {
@@ -246,7 +258,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
           const float nlo = rbf(pk_lo(v[e]) * inv), nhi = rbf(pk_hi(v[e]) * inv);
           o[e] = pack2(pk_lo(g[e]) * nlo, pk_hi(g[e]) * nhi);
         }
-        xs[c] = o;
+        xs[XI(c)] = o;
       }
     }
   } else {  // PRO_ATTN: reduce the S split-K partials of every head (flash-decode combine)
@@ -301,8 +313,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       u32x4 ov;
 #pragma unroll
       for (int e = 0; e < 4; ++e) ov[e] = pack2(o[2 * e] * invL, o[2 * e + 1] * invL);
-      xs[c] = ov;
+      xs[XI(c)] = ov;
     }
+  }
+  if (F4) {   // the ragged last block's padding: zero codes times zero x (at most 3 pieces; LDS is not zeroed between launches)
+    const u32x4 zz = {0u, 0u, 0u, 0u};
+    for (int c = K8 + tid; c < 4 * KC; c += THREADS) xs[XI(c)] = zz;
   }
   __syncthreads();
 
@@ -312,11 +328,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
     for (int r = 0; r < NR; ++r) acc[r] = 0.f;
     // ---- main loop: two register stages (wa holds stage 0 on entry)
     for (int g = 0; g < G; g += 2) {
-      if (g + 1 < G) gemv_load<NR, U>(wb, rows, GIDX(g + 1), lane, KC);
-      if (F8) gemv_fma_f8<NR, U>(acc, wa, xs, GIDX(g), lane, KC); else gemv_fma<NR, U>(acc, wa, xs, GIDX(g), lane, KC);
+      if (g + 1 < G) GLOAD(wb, sb, GIDX(g + 1));
+      GFMA(wa, sa, GIDX(g));
       if (g + 1 < G) {
-        if (g + 2 < G) gemv_load<NR, U>(wa, rows, GIDX(g + 2), lane, KC);
-        if (F8) gemv_fma_f8<NR, U>(acc, wb, xs, GIDX(g + 1), lane, KC); else gemv_fma<NR, U>(acc, wb, xs, GIDX(g + 1), lane, KC);
+        if (g + 2 < G) GLOAD(wa, sa, GIDX(g + 2));
+        GFMA(wb, sb, GIDX(g + 1));
       }
     }
     const int cur = unit0;
@@ -328,7 +344,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       unit0 = chunk * R;
       if (unit0 < n_units) {
         set_rows(unit0);
-        gemv_load<NR, U>(wa, rows, 0, lane, KC);
+        GLOAD(wa, sa, 0);
         if (EPI == EPI_RESID || EPI == EPI_QKV) prefetch_epilogue(unit0);
       }
     }
@@ -364,6 +380,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
     if (!PERSIST || unit0 >= n_units) break;
   }
 #undef GIDX
+#undef GLOAD
+#undef GFMA
+#undef XI
 }
 
 // number of CUs of the current device (cached) — persistent grids are sized from it
@@ -543,12 +562,48 @@ void launch_gemv_f8(int pro, int epi, const GemvArgs& a, hipStream_t s) {
 #undef F8
 #undef F8P
 
+// MXFP4-weight decode GEMVs (gemv_inl.h: dot32_f4): the four (prologue, epilogue) pairs of a layer at B = 1 plus the EPI_STORE pair
+// of dtk_op_gemv_q4; lm_head stays fp8.  A row is a quarter of its bf16 bytes (K = 4096: 2 KiB = two wave-loads), so the fixed cost
+// of a block — the prologue's x, the reduction — weighs more than for fp8.  Shapes by measurement (ds-7b, back-to-back chains over
+// all layers, us per launch; DESIGN 3.1c', profiles/mxfp4_shape_sweep_ds-7b.json): the RMSNorm roles run persistent grids sized to the
+// machine, R 1, U 2, 8 waves, 2 blocks per CU (gate/up 14.4 against 17.6 for one chunk per wave at R 2, 4 waves; 18.5 / 20.2 for the
+// persistent R 2 shapes; q/k/v 11.0 / 10.7 / 14.3 / 12.9); the N = d roles one chunk per wave, R 2, U 2, 4 waves (o_proj 5.4, down 10.0
+// against 7.9 / 12.6 for persistent R 1, U 4, 8 waves and 6.8 / 10.7, 6.8 / 13.5 for the other two).  The losing shapes are not built.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST = false, int BPC = 2>
+static void launch_gemv_q4_t(const GemvArgs& a, hipStream_t s) {
+  int n_units = (EPI == EPI_QKV) ? (a.N >> 1) : (EPI == EPI_SWIGLU ? a.ff : a.N);
+  const int per_block = WAVES * R;
+  int grid = (n_units + per_block - 1) / per_block;
+  if (PERSIST && grid > num_cus() * BPC) grid = num_cus() * BPC;
+  const int KC = (a.K + 31) >> 5;
+  const size_t lds = (size_t)((4 * KC + 63) & ~63) * 16 + 64 + 1024;   // swizzled x in whole 1 KiB tiles + the RMSNorm partials
+  if constexpr (EPI == EPI_QKV || PRO == PRO_ATTN) {
+    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, 1, 64, true>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
+  }
+  hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, 1, 128, true>), dim3(grid), dim3(WAVES * 64), lds, s, a);
+}
+#define Q4(PRO, EPI, R, U, W) return launch_gemv_q4_t<PRO, EPI, R, U, W>(a, s)
+#define Q4P(PRO, EPI, R, U, W, BPC) return launch_gemv_q4_t<PRO, EPI, R, U, W, true, BPC>(a, s)
+void launch_gemv_q4(int pro, int epi, const GemvArgs& a, hipStream_t s) {
+  if (pro == PRO_RMSNORM && epi == EPI_QKV) Q4P(PRO_RMSNORM, EPI_QKV, 1, 2, 8, 2);
+  if (pro == PRO_RMSNORM && epi == EPI_SWIGLU) Q4P(PRO_RMSNORM, EPI_SWIGLU, 1, 2, 8, 2);
+  if (pro == PRO_ATTN && epi == EPI_RESID) Q4(PRO_ATTN, EPI_RESID, 2, 2, 4);
+  if (pro == PRO_COPY && epi == EPI_RESID) Q4(PRO_COPY, EPI_RESID, 2, 2, 4);
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) Q4(PRO_RMSNORM, EPI_STORE, 2, 2, 4);
+  if (pro == PRO_COPY && epi == EPI_STORE) Q4(PRO_COPY, EPI_STORE, 2, 2, 4);
+  fprintf(stderr, "launch_gemv_q4: no MXFP4 kernel for prologue %d, epilogue %d\n", pro, epi);   // a missing kernel is an error, never a fall-back
+  abort();
+}
+#undef Q4
+#undef Q4P
+
 // per-role default variant (tuned): indexed by epilogue; slot 5 = o_proj (EPI_RESID with K == d) when it has its own choice
 // (-1: same as EPI_RESID), slot 6 = o_proj with the PRO_ATTN prologue
 static int g_variant[8] = {0, 0, 0, 0, 0, -1, 0, 0};
 void set_gemv_default_variant(int epi, int variant) { if (epi >= 0 && epi < 8) g_variant[epi] = variant; }
 
 void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s) {
+  if (a.W4) return launch_gemv_q4(pro, epi, a, s);
   if (a.W8) return launch_gemv_f8(pro, epi, a, s);
   if (pro == PRO_ATTN) {   // 0 = not chosen: 16 rows per 16-wave block with split-K 2 (d > 2048: 387.0 tok/s vs 385.9), 8 rows per block (d <= 2048)
     const int v = g_variant[6] ? g_variant[6] : (a.d > 2048 ? 8 : 1);

@@ -56,6 +56,12 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
     """(model, processor).  `device_map` may be an int GPU index (the reference passes
     device_map=RANK, examples/eval.py:112); torch_dtype must be bf16 / "auto" / None.
 
+    `weight_format`: "bf16" (default); "fp8" = e4m3 decoder Linear weights with per-row power-of-two scales; "mxfp4" = OCP MXFP4
+    (E2M1 codes + one E8M0 scale per 32 weights along K, 4.25 bits per weight) for q/k/v, o, gate/up and down of every layer, with
+    lm_head in fp8 and embedding / norms / tower / projector / adapter in bf16.  "mxfp4" is single-sequence decode only
+    (batch_slots=0; anything else raises NotImplementedError).  Both lossy formats quantise on the device at load and overwrite the
+    bf16 tensors with the de-quantised values, so prefill, score(), read_tensor() and the CPU oracle see the weights decode streams.
+
     A checkpoint directory must carry its tokenizer files, as the reference's loader requires
     (v1/__init__.py:26-34 fails hard otherwise); `synthetic_tokenizer=True` (or `"synthetic_tokenizer": true` in the
     directory's config.json, written by our weight-only test fixtures) opts into the byte-level stand-in.
@@ -156,6 +162,10 @@ def _require_supported(cfg: DetikzifyConfig) -> None:
         raise NotImplementedError(
             f"{cfg.name_or_path or 'this checkpoint'}: batch_slots={cfg.batch_slots} — batched decode slots have no head_dim-64 "
             "kernels yet (head_dim 64 runs one sequence per context: load with batch_slots=0)")
+    if cfg.weight_format == "mxfp4" and cfg.batch_slots > 0:
+        raise NotImplementedError(
+            f"{cfg.name_or_path or 'this checkpoint'}: weight_format='mxfp4' with batch_slots={cfg.batch_slots} — MXFP4 weights have no "
+            "batched-slot or multi-vector kernels yet (they stream in single-sequence decode only: load with batch_slots=0)")
     if cfg.concat_patches < 1 or ((cfg.vit_image // cfg.vit_patch) ** 2) % cfg.concat_patches:
         raise ValueError(f"concat_patches={cfg.concat_patches} does not divide the tower's {(cfg.vit_image // cfg.vit_patch) ** 2} patches")
 

@@ -50,7 +50,8 @@ class DetikzifyConfig:
     arch: str = "v1"                 # "v1" (timm tower + LlamaModel subclass) | "v2" (HF SigLIP + Idefics3-style merger)
     attn_splits: int = 0             # split-K factor of the decode attention; 0 = auto (16 for one sequence, 8 for the batched step)
     batch_slots: int = 0             # KV slots for batched decode of independent rollouts (0 = none)
-    weight_format: str = "bf16"      # "bf16" | "fp8" (e4m3 decoder Linear weights, per-row 2^e scales)
+    weight_format: str = "bf16"      # "bf16" | "fp8" (e4m3 decoder Linear weights, per-row 2^e scales) | "mxfp4" (OCP MXFP4 layer weights:
+                                     # E2M1 codes + an E8M0 scale per 32 weights along K; lm_head fp8; batch_slots = 0 only)
     model_type: str = "detikzify"
     name_or_path: str = ""
     vision_tower: str = "vit_so400m_patch14_siglip_384.webli"

@@ -321,7 +321,7 @@ class DetikzifyForCausalLM:
         kd = config.kernel_dict()
         cc = _lib.DtkConfig(**kd)
         cc.reserved[0] = int(getattr(config, "batch_slots", 0) or 0)
-        cc.reserved[1] = 1 if getattr(config, "weight_format", "bf16") == "fp8" else 0
+        cc.reserved[1] = {"fp8": 1, "mxfp4": 2}.get(getattr(config, "weight_format", "bf16"), 0)
         cc.reserved[2] = int(getattr(config, "kv_heads", 0) or 0)                       # GQA (v2)
         cc.reserved[3] = 0 if getattr(config, "proj_bias", True) else _lib.DTK_ARCH_PROJ_NO_BIAS
         ctx = C.c_void_p()

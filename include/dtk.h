@@ -73,7 +73,10 @@ typedef struct dtk_config {
   int32_t image_token_id;  /* == BOS for v1 (v1/__init__.py:49)    */
   int32_t attn_splits;     /* split-K factor of decode attention; 0 = default */
   int32_t reserved[7];     /* [0] = batch slots for dtk_decode_batch_* (0 = none)
-                            * [1] = 1: fp8 e4m3 decoder weights
+                            * [1] = weight format of the decoder's Linear weights: 0 bf16; 1 = fp8 e4m3 + per-row 2^e scales; 2 = OCP MXFP4
+                            *       (E2M1 codes + one E8M0 scale per 32 weights along K) for q/k/v, o, gate/up and down of every layer, fp8 for
+                            *       lm_head; single-sequence decode only: with [0] > 0 dtk_create fails with DTK_ERR_ARG.  Quantised on the
+                            *       device at load; the bf16 tensors are overwritten with the de-quantised (effective) weights
                             * [2] = key/value heads (GQA, num_key_value_heads); 0 = heads (MHA, all v1 models)
                             * [3] = architecture flags, DTK_ARCH_*                        */
 } dtk_config;
@@ -440,7 +443,9 @@ int  dtk_engine_set_prefill_text_op(dtk_engine* e, int (*prefill_slot_text)(void
  * variant `variant` over all layers with HIP events (clobbers the decode state); select the variant the decode step uses for a
  * role: epi 1 = residual roles (down, and o_proj unless slot 5 is set), 2 qkv, 3 gate/up, 4 lm_head, 5 = o_proj alone (-1: as
  * epi 1), 6 = o_proj with the attention-partials prologue.  Variant 0 = the measured default of the model's width;
- * dtk_bench_gemv variant 0xff = whatever the decode step itself launches for that role (bench.py's roofline leg). */
+ * dtk_bench_gemv variant 0xff = whatever the decode step itself launches for that role (bench.py's roofline leg); 0xff | 0x800 =
+ * the same on the context's weight format (fp8 rows, MXFP4 codes; without the bit the bf16 tensors are streamed); 0x800 with any
+ * other variant or with the plain-probe bits fails with DTK_ERR_ARG. */
 int  dtk_bench_gemv(dtk_ctx* ctx, int role, int variant, int reps, float* avg_us);
 int  dtk_set_gemv_variant(dtk_ctx* ctx, int epi, int variant);
 /* Tuning switches; every default is the measured-best setting.  Single-sequence decode: "attn_threads" (0 =
@@ -512,6 +517,10 @@ int  dtk_op_score(dtk_ctx* ctx, const uint16_t* Xn, const uint16_t* W, const int
 /* mode 0: y = W.x ; mode 1: y = W.rmsnorm(x, norm_w) ; fp32 result of the bf16-rounded output */
 int  dtk_op_gemv(dtk_ctx* ctx, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w,
                  int N, int K, int mode, float eps, uint16_t* y);
+/* dtk_op_gemv on MXFP4 weights: W [N][K] row-major bf16 is quantised by the loader's own quantiser (blocks of 32 along K, the last one
+ * of a row may be ragged) and streamed by the decode kernel; y [N] as dtk_op_gemv; w_eff_out (or NULL) [N][K] = the de-quantised weights */
+int  dtk_op_gemv_q4(dtk_ctx* ctx, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w,
+                    int N, int K, int mode, float eps, uint16_t* y, uint16_t* w_eff_out);
 /* the multi-vector GEMV of the <= 4-slot step on nb (1, 2, 4) row-major vectors X[nb][K] -> Y[nb][N]; per vector bit-identical
  * to dtk_op_gemv */
 int  dtk_op_gemv_mv(dtk_ctx* ctx, const uint16_t* W, const uint16_t* X, const uint16_t* norm_w,
