@@ -206,6 +206,9 @@ SYMBOLS = {
     "dtk_op_gemv_b": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "dtk_op_gemv_bkp": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_float, _P, _P, _P, _P]),
+    # additive (ABI stays 7): one role of the single-sequence decode GEMV family (prologue, epilogue, variant, weight format)
+    "dtk_op_gemv_role": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [C.c_float, _P, _P, _P, _P,
+                                   C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     # additive (ABI stays 7): dtk_op_gemv on MXFP4 weights (the loader's quantiser + the decode kernel); last = de-quantised W or NULL

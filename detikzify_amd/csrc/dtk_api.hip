@@ -3602,6 +3602,127 @@ int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const
   return DTK_OK;
 }
 
+// ---- the single-sequence decode GEMV family alone (dtk_op_gemv_role): one (prologue, epilogue, weight format, shape) of k_gemv on
+// host operands through the step's own launchers.  Everything the step would never hand these kernels is refused before anything is
+// allocated, uploaded or launched.
+static bool gemv_role_variant_ok(int fmt, int pro, int epi, int v) {     // fmt 0 bf16 (launch_gemv_variant), 1 fp8 (launch_gemv_f8_variant), 2 MXFP4 (launch_gemv_q4)
+  if (fmt == 2) {
+    const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_STORE)) || (pro == PRO_ATTN && epi == EPI_RESID) ||
+                      (pro == PRO_COPY && (epi == EPI_RESID || epi == EPI_STORE));
+    return pair && v == -1;
+  }
+  if (fmt == 1) {
+    const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_LOGITS)) || ((pro == PRO_ATTN || pro == PRO_COPY) && epi == EPI_RESID);
+    return pair && v >= -1 && v <= 9;
+  }
+  if (v < -1) return false;
+  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return v <= 11;
+  if (pro == PRO_COPY && epi == EPI_RESID) return v <= 22;
+  if (pro == PRO_ATTN && epi == EPI_RESID) return v <= 8;
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return v <= 4;
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) return v <= 0 || v == 20;
+  if (pro == PRO_COPY && epi == EPI_STORE) return v <= 0 || v == 20 || v == 21;
+  return false;
+}
+
+int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* W, const uint8_t* W8, const float* wscale,
+                     const uint8_t* W4, const uint8_t* S4, int N, int K, int d, int ff, int H, int KVH, int hd, int T_max, int pos, float eps,
+                     const uint16_t* x, const uint16_t* norm_w, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                     int S, const float* pm, const float* pl, const float* po, int scratch_fill,
+                     uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, float* logits_io) {
+  if (!c) return DTK_ERR_ARG;
+  if ((W != nullptr) + (W8 != nullptr) + (W4 != nullptr) != 1 || (W8 && !wscale) || (!W8 && wscale) || (!W4 != !S4))
+    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: exactly one of W | W8 + wscale | W4 + S4");
+  const int fmt = W4 ? 2 : (W8 ? 1 : 0);
+  if (N < 1 || K < 8 || (K & 7) || (fmt == 1 && (K & 15))) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: N >= 1, K a multiple of 8 (16 for fp8 weights)");
+  if (pro < PRO_COPY || pro > PRO_ATTN || epi < EPI_STORE || epi > EPI_LOGITS) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: unknown prologue %d or epilogue %d", pro, epi);
+  if (!gemv_role_variant_ok(fmt, pro, epi, variant))
+    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no %s kernel for prologue %d, epilogue %d, variant %d", fmt == 2 ? "MXFP4" : (fmt == 1 ? "fp8" : "bf16"), pro, epi, variant);
+  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: head dim %d (128 or 64)", hd);
+  if (scratch_fill < 0 || scratch_fill > 255 || d < 0) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: scratch_fill is a byte, d >= 0");
+  if (pro == PRO_ATTN) {
+    if (S < 1 || S > 16) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: S must be 1..16");
+    if (H < 1 || K != H * hd || !pm || !pl || !po) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: PRO_ATTN needs K = H * hd and the partials pm / pl / po");
+  } else if (!x || (pro == PRO_RMSNORM && !norm_w)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: x (and norm_w for PRO_RMSNORM) required");
+  if (epi == EPI_QKV) {
+    if (H < 1 || KVH < 1 || H % KVH) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: H %d query heads over KVH %d key / value heads", H, KVH);
+    if (N != (H + 2 * KVH) * hd || d != H * hd) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: QKV needs N = (H + 2 KVH) * hd and d = H * hd");
+    if (T_max < 1 || pos < 0 || pos >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: position %d of %d rows", pos, T_max);
+    if (!rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: QKV needs the rope tables and q / k / v buffers");
+  } else if (epi == EPI_SWIGLU) {
+    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff and y");
+  } else if (epi == EPI_LOGITS) {
+    if (!logits_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: LOGITS needs the logits buffer");
+  } else if (!y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: RESID / STORE need y");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int KC4 = (K + 31) >> 5, hd2 = hd / 2;
+  const size_t w_bytes = fmt == 2 ? (size_t)N * KC4 * 16 : (fmt == 1 ? (size_t)N * K : (size_t)N * K * 2);
+  const size_t kv = epi == EPI_QKV ? (size_t)KVH * T_max * hd : 0, qn = epi == EPI_QKV ? (size_t)H * hd : 0, rope = epi == EPI_QKV ? (size_t)T_max * hd2 : 0;
+  const size_t ny = epi == EPI_SWIGLU ? (size_t)ff : ((epi == EPI_STORE || epi == EPI_RESID) ? (size_t)N : 0), nl = epi == EPI_LOGITS ? (size_t)N : 0;
+  const size_t hs = pro == PRO_ATTN ? (size_t)H * S : 0;
+  size_t off = 0;
+  OPBUF(uint8_t, dW, w_bytes); OPBUF(float, dws, fmt == 1 ? N : 0); OPBUF(uint8_t, dS4, fmt == 2 ? (size_t)N * KC4 : 0);
+  OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dcos, rope); OPBUF(bf16_t, dsin, rope); OPBUF(DecState, dst, 1);
+  OPBUF(float, dpm, hs); OPBUF(float, dpl, hs); OPBUF(float, dpo, hs * hd);
+  constexpr size_t GUARD = 256;            // bytes behind every result buffer that must still hold scratch_fill after the launch
+  OPBUF(bf16_t, dq, qn + GUARD / 2); OPBUF(bf16_t, dk, kv + GUARD / 2); OPBUF(bf16_t, dv, kv + GUARD / 2); OPBUF(bf16_t, dy, ny + GUARD / 2);
+  OPBUF(float, dl, nl + GUARD / 4);
+  off = align_up(off, 256);
+  if (off + 256 > c->scratch_bytes) return fail(c, DTK_ERR_ARG, "op scratch exhausted (%zu bytes)", off + 256);
+  HIPCHK(c, hipMemsetAsync(c->scratch, scratch_fill, off + 256, s));      // whatever lies between and behind the operands: the caller's poison
+  HIPCHK(c, hipMemcpyAsync(dW, fmt == 2 ? (const void*)W4 : (fmt == 1 ? (const void*)W8 : (const void*)W), w_bytes, hipMemcpyHostToDevice, s));
+  if (fmt == 1) HIPCHK(c, hipMemcpyAsync(dws, wscale, (size_t)N * 4, hipMemcpyHostToDevice, s));
+  if (fmt == 2) HIPCHK(c, hipMemcpyAsync(dS4, S4, (size_t)N * KC4, hipMemcpyHostToDevice, s));
+  if (pro != PRO_ATTN) HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)K * 2, hipMemcpyHostToDevice, s));
+  if (pro == PRO_RMSNORM) HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
+  if (pro == PRO_ATTN) {
+    HIPCHK(c, hipMemcpyAsync(dpm, pm, hs * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dpl, pl, hs * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dpo, po, hs * hd * 4, hipMemcpyHostToDevice, s));
+  }
+  DecState hst; memset(&hst, 0, sizeof hst);
+  hst.pos = pos; hst.next_pos = pos + 1;
+  HIPCHK(c, hipMemcpyAsync(dst, &hst, sizeof hst, hipMemcpyHostToDevice, s));
+  if (epi == EPI_QKV) {
+    HIPCHK(c, hipMemcpyAsync(dcos, rope_cos, rope * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dsin, rope_sin, rope * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dq, q_io, qn * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dk, k_io, kv * 2, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(dv, v_io, kv * 2, hipMemcpyHostToDevice, s));
+  } else if (epi == EPI_LOGITS) HIPCHK(c, hipMemcpyAsync(dl, logits_io, nl * 4, hipMemcpyHostToDevice, s));
+  else HIPCHK(c, hipMemcpyAsync(dy, y_io, ny * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipStreamSynchronize(s));      // (hst lives on this frame)
+  GemvArgs g{};
+  if (fmt == 0) g.W = reinterpret_cast<const bf16_t*>(dW);
+  else if (fmt == 1) { g.W8 = dW; g.wscale = dws; }
+  else { g.W4 = dW; g.S4 = dS4; }
+  g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.pm = dpm; g.pl = dpl; g.po = dpo; g.S = S;
+  g.y = dy; g.logits = dl; g.q_out = dq; g.kcache = dk; g.vcache = dv; g.rope_cos = dcos; g.rope_sin = dsin; g.st = dst;
+  g.T_max = T_max; g.d = d; g.ff = ff; g.H = H; g.KVH = KVH; g.hd = hd;
+  if (variant < 0) launch_gemv(pro, epi, g, s);
+  else if (fmt == 1) launch_gemv_f8_variant(pro, epi, variant, g, s);
+  else launch_gemv_variant(pro, epi, variant, g, s);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  {   // a role writes its own cells only: nothing behind the end of q / k / v / y / logits
+    const unsigned char* ends[5] = {(unsigned char*)(dq + qn), (unsigned char*)(dk + kv), (unsigned char*)(dv + kv), (unsigned char*)(dy + ny), (unsigned char*)(dl + nl)};
+    unsigned char guard[5][GUARD];
+    for (int i = 0; i < 5; ++i) HIPCHK(c, hipMemcpy(guard[i], ends[i], GUARD, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 5; ++i)
+      for (size_t j = 0; j < GUARD; ++j)
+        if (guard[i][j] != (unsigned char)scratch_fill) return fail(c, DTK_ERR_STATE, "dtk_op_gemv_role: byte %zu behind the end of %s was written", j, i == 0 ? "q" : (i == 1 ? "k" : (i == 2 ? "v" : (i == 3 ? "y" : "logits"))));
+  }
+  if (epi == EPI_QKV) {
+    HIPCHK(c, hipMemcpy(q_io, dq, qn * 2, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(k_io, dk, kv * 2, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(v_io, dv, kv * 2, hipMemcpyDeviceToHost));
+  } else if (epi == EPI_LOGITS) HIPCHK(c, hipMemcpy(logits_io, dl, nl * 4, hipMemcpyDeviceToHost));
+  else HIPCHK(c, hipMemcpy(y_io, dy, ny * 2, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
 // ---- the batched decode GEMV family alone (dtk_op_gemv_b / dtk_op_gemv_bkp): host operands into the op scratch, the step's own
 // launchers (launch_retile / launch_retile_f8, launch_rmsnorm_b, launch_gemv_b, launch_gemv_bkp, launch_resid_norm_b) unchanged
 static inline size_t host_xtile_off(int slot, int k, int nsteps) {      // xtile_off (common.h)

@@ -47,6 +47,8 @@ struct GemvArgs {
 void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s);
 void launch_gemv_q4(int pro, int epi, const GemvArgs& a, hipStream_t s);   // the MXFP4 instantiations (launch_gemv dispatches here when a.W4)
 void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s);
+void launch_gemv_f8(int pro, int epi, const GemvArgs& a, hipStream_t s);       // the fp8 instantiations in the process default shape (DTK_F8_VARIANT, 8)
+void launch_gemv_f8_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s);   // ... in shape 0..9 of the same table
 void set_gemv_default_variant(int epi, int variant);
 
 struct AttnDecArgs {

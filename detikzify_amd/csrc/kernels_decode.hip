@@ -532,8 +532,9 @@ static int f8_variant() {
 }
 #define F8(PRO, EPI, R, U, W) return launch_gemv_f8_t<PRO, EPI, R, U, W>(a, s)
 #define F8P(PRO, EPI, R, U, W, BPC) return launch_gemv_f8_t<PRO, EPI, R, U, W, true, BPC>(a, s)
-void launch_gemv_f8(int pro, int epi, const GemvArgs& a, hipStream_t s) {
-  const int v = f8_variant();
+void launch_gemv_f8(int pro, int epi, const GemvArgs& a, hipStream_t s) { launch_gemv_f8_variant(pro, epi, f8_variant(), a, s); }
+// the same table with the shape given by the caller (dtk_op_gemv_role: one process reaches every shape)
+void launch_gemv_f8_variant(int pro, int epi, int v, const GemvArgs& a, hipStream_t s) {
   if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) {
     if (epi == EPI_QKV) {
       switch (v) { default: F8(PRO_RMSNORM, EPI_QKV, 2, 2, 4); case 0: F8(PRO_RMSNORM, EPI_QKV, 1, 2, 4);

@@ -592,6 +592,25 @@ int  dtk_op_gemv_b(dtk_ctx* ctx, int epi, const uint16_t* W, const uint8_t* W8, 
 int  dtk_op_gemv_bkp(dtk_ctx* ctx, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, const uint16_t* X,
                      const int32_t* active, int nslots, const uint16_t* norm_w, float eps, uint16_t* resid_io, uint16_t* xn_io,
                      float* part_out, uint32_t* err_out);
+/* The single-sequence decode GEMV family alone, one role at a time (additive, ABI 7); bf16 bits throughout.  pro: 0 COPY (x [K] is the
+ * input), 1 RMSNORM (x is a residual stream, norm_w [K], eps), 2 ATTN (the input is the combine of S = 1..16 split-K attention partials
+ * pm / pl [H][S], po [H][S][hd], K = H * hd).  epi: 0 STORE, 1 RESID, 2 QKV, 3 SWIGLU, 4 LOGITS.  Weights, exactly one of: W [N][K] bf16;
+ * W8 [N][K] e4m3 bytes + wscale [N] (per-row power of two; K % 16 == 0); W4 [N][ceil(K/32)*16] E2M1 codes + S4 [N][ceil(K/32)] E8M0 block
+ * scales (MXFP4: byte i of a row = weights 2i low nibble, 2i + 1 high nibble, rows padded with zero codes to whole blocks of 32).
+ * variant: bf16 -1 = the step's choice for hidden size d, else a row of the tuning table; fp8 -1 = the process default
+ * (DTK_F8_VARIANT), 0..9 = that shape; MXFP4 -1 only.  K % 8 == 0, hd 128 | 64, ff % 8 == 0 as in dtk_create.
+ * Result buffers are IN/OUT, so that a caller can pre-fill them and see what was written:
+ *   QKV (N = (H + 2 KVH) * hd, d = H * hd, H % KVH == 0, rope_cos / rope_sin [T_max][hd / 2], 0 <= pos < T_max): q_io [H * hd],
+ *   k_io / v_io [KVH][T_max][hd] (row pos of every head is written);   STORE: y_io [N];   RESID: y_io [N] += bf16(W . x);
+ *   SWIGLU (N = 2 ff, rows = gate rows then up rows): y_io [ff];   LOGITS: logits_io [N] fp32.
+ * scratch_fill: the byte the op's device scratch is filled with before the operands are uploaded (what a kernel reads beside them).
+ * DTK_ERR_ARG, with nothing launched and no buffer touched, for a shape or a (pro, epi, format, variant) the step would never run.
+ * DTK_ERR_STATE if the launch wrote behind the end of a result buffer (256 guard bytes each).  Buffers a role does not use may be NULL. */
+int  dtk_op_gemv_role(dtk_ctx* ctx, int pro, int epi, int variant, const uint16_t* W, const uint8_t* W8, const float* wscale,
+                      const uint8_t* W4, const uint8_t* S4, int N, int K, int d, int ff, int H, int KVH, int hd, int T_max, int pos, float eps,
+                      const uint16_t* x, const uint16_t* norm_w, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                      int S, const float* pm, const float* pl, const float* po, int scratch_fill,
+                      uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, float* logits_io);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */
