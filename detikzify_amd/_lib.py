@@ -112,6 +112,8 @@ class DtkEngineOps(C.Structure):
     WAIT_LP = C.CFUNCTYPE(C.c_int, C.c_void_p, _I64P, C.POINTER(C.c_float), C.POINTER(C.c_float))
     # not a field: dtk_engine_set_sampling_ext_op's argument (dev, slot, ext)
     SAMPLING_EXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkSamplingExt))
+    # not a field: dtk_engine_set_penalties_op's argument (dev, slot, presence, frequency, start)
+    PENALTIES = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int)
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -243,6 +245,15 @@ SYMBOLS = {
     "dtk_engine_submit_ext": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.POINTER(C.c_int64), C.c_int, C.c_uint64,
                                         C.POINTER(C.c_uint64)]),
     "dtk_engine_set_sampling_ext_op": (C.c_int, [_P, DtkEngineOps.SAMPLING_EXT]),
+    # additive (ABI stays 7): presence / frequency penalty in front of the sampler chain
+    "dtk_set_penalties": (C.c_int, [_P, C.c_float, C.c_float, C.c_int]),
+    "dtk_set_penalties_slot": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int]),
+    "dtk_op_sample_pen": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float), C.POINTER(DtkSamplingExt),
+                                    C.c_float, C.c_float, C.POINTER(C.c_int64), C.c_int]),
+    "dtk_token_counts": (C.c_int, [_P, C.c_int, C.POINTER(C.c_uint16), C.c_int]),
+    "dtk_engine_submit_pen": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int,
+                                        C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_penalties_op": (C.c_int, [_P, DtkEngineOps.PENALTIES]),
 }
 
 _lib = None

@@ -155,6 +155,18 @@ struct SamplingDev {
   float eps;             // epsilon_cutoff in [0, 1)
 };
 
+// presence / frequency penalty of one sequence (dtk_set_penalties; both 0 = off), a record of its own so that SamplingDev keeps its
+// tail.  Read only by the PN sampler instantiations (SampleArgs::pen), next to the sequence's uint16 count table.
+struct PenDev {
+  float pp;              // presence_penalty in [-2, 2]
+  float fp;              // frequency_penalty in [-2, 2]
+};
+// z' of a raw logit z whose id was counted c times: z - (float)((double)pp + (double)fp * c) for c > 0 (the product of a float and an
+// integer below 2^16 is exact in double: no contraction can change it), the untouched bits for c = 0
+__device__ __forceinline__ float pen_apply(float z, unsigned c, float pp, float fp) {
+  return c ? z - (float)((double)pp + (double)fp * (double)c) : z;
+}
+
 // scratch of the multi-block sampler (kernels_sample_mb.hip), one per sequence / slot
 #define DTK_SAMPLE_MB_MAX_SLICES 32      // 32 x 8192 = vocabularies up to 262 144
 struct SampleMB {

@@ -58,6 +58,7 @@ struct SeqHost {   // host-side mirror of one sequence's decode state
   int share_src = -1;              // slot whose first share_len cached tokens are bit-identical to ours (dtk_kv_fork), or -1
   int share_len = 0;
   int last_reuse_start = 0;        // tokens of the previous cache the last prefill kept
+  int64_t forced_pending = -1;     // dtk_resume_slot's last id until the step that forwards it is launched: part of the sequence, not yet of cached_ids
 };
 
 struct LayerW {
@@ -264,6 +265,21 @@ struct dtk_ctx {
   bool trunc_single = false, graph_trunc = false;
   bool slot_trunc[DTK_MAX_SLOTS] = {};
   bool trunc_batch = false, bgraph_trunc = false;
+  // presence / frequency penalties (dtk_set_penalties): sequence 0 is the single one, 1 + slot a slot's.  Everything below is allocated
+  // by the first call that sets a non-zero value (pen_alloc), so a context that never uses penalties allocates and launches nothing.
+  // pen_single / pen_batch: which sampler instantiations the next captures must contain, graph_pen / bgraph_pen: which the captured graphs
+  // do contain (as trunc_single / graph_trunc)
+  uint16_t* pen_tab = nullptr;       // [1 + nb][pen_stride] count tables
+  int pen_stride = 0;
+  PenDev* pen_dev = nullptr;         // [1 + DTK_MAX_SLOTS]
+  int32_t* pen_tok = nullptr;        // [1 + DTK_MAX_SLOTS] the step's sampled token, consumed by k_count_token (-1: nothing to count)
+  int32_t* pen_ids_dev = nullptr;    // [1 + nb][Tmax] the ids a rebuild scatters
+  int32_t* pen_ids_stage = nullptr;  // pinned mirror: a slot's rebuild is queued behind the step in flight, no drain
+  PenDev* pen_stage = nullptr;       // pinned [1 + DTK_MAX_SLOTS]
+  PenDev pen_val[1 + DTK_MAX_SLOTS] = {};   // the values as set
+  int pen_start[1 + DTK_MAX_SLOTS] = {};    // penalty_start
+  bool pen_single = false, graph_pen = false;
+  bool pen_batch = false, bgraph_pen = false;
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
@@ -810,6 +826,19 @@ static inline hipError_t copy_lp_ring(dtk_ctx* c, bool batch) {
                : hipMemcpyAsync(c->lp_ring_host, c->lp_ring_dev, sizeof(float2) * DTK_MAX_INFLIGHT, hipMemcpyDeviceToHost, c->stream);
 }
 
+// dtk_set_penalties: the PN samplers' view of the step's sequences (nothing without a sequence that has values), and the trailing
+// kernel that counts the tokens they sampled
+static void pen_args(const dtk_ctx* c, SampleArgs& sa, bool batch) {
+  if (!(batch ? c->pen_batch : c->pen_single) || !c->pen_tab) return;
+  const int first = batch ? 1 : 0;
+  sa.pen = c->pen_dev + first; sa.pen_cnt = c->pen_tab + (size_t)first * c->pen_stride; sa.pen_stride = c->pen_stride; sa.pen_tok = c->pen_tok + first;
+}
+static void sampler_launch(dtk_ctx* c, SampleArgs& sa, bool mb, bool batch) {
+  pen_args(c, sa, batch);
+  if (mb) launch_sample_mb(sa, c->stream); else launch_sample_b(sa, c->stream);
+  if (sa.pen) launch_count_token(sa, c->stream);
+}
+
 // "top_logprobs": k_top_logits in front of the step's sampler, on the logits, DecState and BatchState the sampler is about to read
 static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
   if (!c->top_logprobs || !c->logprobs) return;
@@ -829,7 +858,7 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   sa.trunc = c->trunc_single ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lse_ring_dev : nullptr;
   top_logits_launch(c, sa);
-  if (c->mb_single) launch_sample_mb(sa, s); else launch_sample(sa, s);
+  sampler_launch(c, sa, c->mb_single, false);
   const float scale = 1.0f / sqrtf((float)c->hd);
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
@@ -891,7 +920,7 @@ void batch_step_launches_mx(dtk_ctx* c) {
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
-  if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
+  sampler_launch(c, sa, c->mb_batch, true);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   for (int l = 0; l < c->L; ++l) {
@@ -940,7 +969,7 @@ void batch_step_launches(dtk_ctx* c) {
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
-  if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
+  sampler_launch(c, sa, c->mb_batch, true);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   bool kparts = false;
@@ -1015,7 +1044,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
   top_logits_launch(c, sa);
-  if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
+  sampler_launch(c, sa, c->mb_batch, true);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   GemvMvArgs g{};
@@ -1155,6 +1184,7 @@ void drop_graph(dtk_ctx* c) {          // the single-sequence step's two capture
 int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   const int gi = step_graph_index(c);
   if (c->bgraph_trunc != c->trunc_batch) { drop_batch_graphs(c); c->bgraph_trunc = c->trunc_batch; }
+  if (c->bgraph_pen != c->pen_batch) { drop_batch_graphs(c); c->bgraph_pen = c->pen_batch; }
   if (c->bgraph_ready[gi]) return DTK_OK;
   HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   c->launch_refused = false;
@@ -1175,6 +1205,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
 
 int ensure_graph(dtk_ctx* c) {
   if (c->graph_trunc != c->trunc_single) { drop_graph(c); c->graph_trunc = c->trunc_single; }
+  if (c->graph_pen != c->pen_single) { drop_graph(c); c->graph_pen = c->pen_single; }
   if (c->graph_ready) return DTK_OK;
   // two captures of the same step: split-K attention (any context) and the one-block-per-head
   // attention used while the context is short; the host picks per step (it knows the position)
@@ -1220,6 +1251,82 @@ extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta) { if (c) c->eng
 extern "C" {
 
 int dtk_abi_version(void) { return DTK_ABI_VERSION; }
+
+// ---- presence / frequency penalties: the count tables -----------------------------------------------------------------------------
+static inline int pen_index(const dtk_ctx* c, const SeqHost& sh) { return &sh == &c->seq0 ? 0 : 1 + (int)(&sh - c->bseq.data()); }
+static inline bool pen_on(const dtk_ctx* c, int q) { return c->pen_val[q].pp != 0.f || c->pen_val[q].fp != 0.f; }
+
+// everything the feature keeps on the device, at the first non-zero value
+static int pen_alloc(dtk_ctx* c) {
+  if (c->pen_tab) return DTK_OK;
+  if (c->Tmax >= 65536) return fail(c, DTK_ERR_RANGE, "penalties: max_positions %d does not fit the 16-bit counts (< 65536)", c->Tmax);
+  const int nseq = 1 + c->nb, nrec = 1 + DTK_MAX_SLOTS;
+  c->pen_stride = (c->V + 7) & ~7;
+  // (pen_tab, assigned last, says that everything exists; a buffer that a failed attempt left is kept for the next one and freed with
+  // the context)
+  if (!c->pen_dev) HIPCHK(c, hipMalloc(&c->pen_dev, sizeof(PenDev) * nrec));
+  HIPCHK(c, hipMemset(c->pen_dev, 0, sizeof(PenDev) * nrec));
+  if (!c->pen_tok) HIPCHK(c, hipMalloc(&c->pen_tok, sizeof(int32_t) * nrec));
+  HIPCHK(c, hipMemset(c->pen_tok, 0xff, sizeof(int32_t) * nrec));
+  if (!c->pen_ids_dev) HIPCHK(c, hipMalloc(&c->pen_ids_dev, sizeof(int32_t) * (size_t)nseq * c->Tmax));
+  if (!c->pen_ids_stage) HIPCHK(c, hipHostMalloc((void**)&c->pen_ids_stage, sizeof(int32_t) * (size_t)nseq * c->Tmax, hipHostMallocDefault));
+  if (!c->pen_stage) HIPCHK(c, hipHostMalloc((void**)&c->pen_stage, sizeof(PenDev) * nrec, hipHostMallocDefault));
+  uint16_t* tab = nullptr;
+  HIPCHK(c, hipMalloc(&tab, sizeof(uint16_t) * (size_t)nseq * c->pen_stride));
+  HIPCHK(c, hipMemset(tab, 0, sizeof(uint16_t) * (size_t)nseq * c->pen_stride));
+  c->pen_tab = tab;
+  return DTK_OK;
+}
+
+// Sequence q's table from its token list ids[0, n): zero-fill, then (values != 0 only: a sequence without values keeps an empty table)
+// the scatter of ids[start, n).  All on the context's stream from pinned per-sequence staging, so a slot's rebuild queues behind a step
+// of the other slots in flight like its sampling upload does.  Nothing before the tables exist.
+static int pen_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one_more = -1) {
+  if (!c->pen_tab) return DTK_OK;
+  uint16_t* tab = c->pen_tab + (size_t)q * c->pen_stride;
+  HIPCHK(c, hipMemsetAsync(tab, 0, sizeof(uint16_t) * (size_t)c->pen_stride, c->stream));
+  if (!pen_on(c, q) || !ids) return DTK_OK;
+  if (n > c->Tmax) n = c->Tmax;
+  int32_t* st = c->pen_ids_stage + (size_t)q * c->Tmax;
+  int m = 0;
+  for (int i = c->pen_start[q]; i < n; ++i) st[m++] = (int32_t)ids[i];      // (an un-read token, -1, is skipped by the kernel)
+  if (one_more >= 0 && n < c->Tmax && c->pen_start[q] <= n) st[m++] = (int32_t)one_more;      // position n: a resumed slot's forced id
+  if (m <= 0) return DTK_OK;
+  int32_t* dv = c->pen_ids_dev + (size_t)q * c->Tmax;
+  HIPCHK(c, hipMemcpyAsync(dv, st, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+  launch_count_scatter(dv, m, tab, c->V, c->stream);
+  return DTK_OK;
+}
+
+static int pen_check(dtk_ctx* c, float pp, float fp, int start, const char* who) {
+  if (!(pp >= -2.f && pp <= 2.f)) return fail(c, DTK_ERR_ARG, "%s: presence_penalty must be in [-2, 2]", who);
+  if (!(fp >= -2.f && fp <= 2.f)) return fail(c, DTK_ERR_ARG, "%s: frequency_penalty must be in [-2, 2]", who);
+  if (start < 0) return fail(c, DTK_ERR_ARG, "%s: penalty_start must be >= 0", who);
+  return DTK_OK;
+}
+
+// the values of sequence q (0 / 0 / 0: the reset of dtk_set_sampling[_slot]); the table follows them
+static int pen_set(dtk_ctx* c, int q, float pp, float fp, int start) {
+  const bool on = pp != 0.f || fp != 0.f;
+  if (!on && !pen_on(c, q)) { c->pen_start[q] = start; return DTK_OK; }      // nothing to switch off
+  if (on) { const int rc = pen_alloc(c); if (rc) return rc; }
+  c->pen_val[q].pp = pp; c->pen_val[q].fp = fp; c->pen_start[q] = start;
+  c->pen_stage[q] = c->pen_val[q];
+  HIPCHK(c, hipMemcpyAsync(c->pen_dev + q, &c->pen_stage[q], sizeof(PenDev), hipMemcpyHostToDevice, c->stream));
+  if (q == 0) c->pen_single = on;
+  else {
+    bool any = false;
+    for (int j = 1; j <= c->nb; ++j) any = any || pen_on(c, j);
+    c->pen_batch = any;
+  }
+  const SeqHost& sh = q == 0 ? c->seq0 : c->bseq[(size_t)q - 1];
+  return pen_rebuild(c, q, sh.cached_ids.data(), (int)sh.cached_ids.size(), sh.forced_pending);
+}
+
+// every table empty: the places that leave the context without any sequence (weights, adapter, options that clear the caches)
+static void pen_clear_all(dtk_ctx* c) {
+  if (c->pen_tab) (void)hipMemsetAsync(c->pen_tab, 0, sizeof(uint16_t) * (size_t)(1 + c->nb) * c->pen_stride, c->stream);
+}
 
 int dtk_abi_struct_size(int which) {
   switch (which) {
@@ -1438,6 +1545,12 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->score_rec) (void)hipFree(c->score_rec);
   if (c->score_out) (void)hipFree(c->score_out);
   if (c->score_top) (void)hipFree(c->score_top);
+  if (c->pen_tab) (void)hipFree(c->pen_tab);
+  if (c->pen_dev) (void)hipFree(c->pen_dev);
+  if (c->pen_tok) (void)hipFree(c->pen_tok);
+  if (c->pen_ids_dev) (void)hipFree(c->pen_ids_dev);
+  if (c->pen_ids_stage) (void)hipHostFree(c->pen_ids_stage);
+  if (c->pen_stage) (void)hipHostFree(c->pen_stage);
   if (c->top_ring_dev) (void)hipFree(c->top_ring_dev);
   if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
   if (c->topb_dev) (void)hipFree(c->topb_dev);
@@ -1498,6 +1611,7 @@ int dtk_load_tensor(dtk_ctx* c, const char* name, const void* host, int dtype, c
   c->have_image = false;
   c->seq0.cached_ids.clear();
   for (auto& b : c->bseq) b.cached_ids.clear();
+  pen_clear_all(c);
   c->tiled_ready = false;
   c->ptiled_ready = false;
   c->fp8_ready = false;
@@ -1538,6 +1652,7 @@ int dtk_fill_synthetic(dtk_ctx* c, uint64_t seed) {
   c->have_image = false;
   c->seq0.cached_ids.clear();
   for (auto& b : c->bseq) b.cached_ids.clear();
+  pen_clear_all(c);
   c->tiled_ready = false;
   c->ptiled_ready = false;
   c->fp8_ready = false;
@@ -1851,6 +1966,8 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
   if (hipEventElapsedTime(&ms, c->ev_a, c->ev_b) == hipSuccess) c->stats.last_vit_ms = ms;
   c->stats.prefill_tokens += (uint64_t)n;
   sh.cached_ids.assign(ids, ids + T);
+  sh.forced_pending = -1;
+  if (const int rc = pen_rebuild(c, pen_index(c, sh), ids, T)) return rc;
   sh.cached_with_image = use_img;
   sh.image_key = use_img ? image_key : 0;
   sh.host_next_pos = T;
@@ -1976,6 +2093,8 @@ static int score_packed_impl(dtk_ctx* c, const PackedReq& r, int total, const fl
   c->waited = c->launched = 0;
   // the cache rows from `start` on are rewritten: whatever happens below, the context holds no sequence to decode from
   sh.cached_ids.resize((size_t)start);
+  sh.forced_pending = -1;
+  if (const int rc = pen_rebuild(c, pen_index(c, sh), nullptr, 0)) return rc;     // no sequence from here on, whatever happens below: an empty table
   sh.have_logits = false;
   sh.host_next_pos = start;
   hipStream_t s = c->stream;
@@ -2127,6 +2246,7 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
   }
   if (is_single) { c->sampling = *sp; c->launched = c->waited = 0; c->sampling_ext = dtk_sampling_ext{}; c->trunc_single = false; }
   else c->slot_trunc[(int)(sp_dst - c->sp_b)] = false;      // dv.qmin = dv.eps = 0: dtk_set_sampling_*_ext follows where they are wanted
+  if (const int rc = pen_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), 0.f, 0.f, 0)) return rc;      // dtk_set_penalties[_slot] likewise
   // which sampler the captured graphs must contain: the multi-block chain serves large vocabularies unless a
   // configuration needs top-k; a change of kind drops the graph (re-captured by the next launch)
   const bool needs_topk = sp->do_sample && sp->top_k > 0 && sp->top_k < c->V;
@@ -2216,6 +2336,34 @@ int dtk_set_sampling_slot(dtk_ctx* c, int slot, const dtk_sampling* sp) {
   return set_sampling_impl(c, sp, c->sp_b + slot, c->st_b + slot, false);
 }
 
+// presence / frequency penalty of the sequence the last dtk_set_sampling[_slot] configured (include/dtk.h)
+int dtk_set_penalties(dtk_ctx* c, float presence, float frequency, int start) {
+  if (!c) return DTK_ERR_ARG;
+  if (const int rc = pen_check(c, presence, frequency, start, "dtk_set_penalties")) return rc;
+  if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "dtk_set_penalties: %d decode step(s) are unread", (int)(c->launched - c->waited));
+  HIPCHK(c, hipSetDevice(c->device));
+  return pen_set(c, 0, presence, frequency, start);
+}
+
+int dtk_set_penalties_slot(dtk_ctx* c, int slot, float presence, float frequency, int start) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_set_penalties_slot: slot %d of %d", slot, c ? c->nb : 0);
+  if (const int rc = pen_check(c, presence, frequency, start, "dtk_set_penalties_slot")) return rc;
+  for (uint64_t q = c->bwaited; q < c->blaunched; ++q)
+    if (c->bs_host[q % DTK_MAX_INFLIGHT].active[slot]) return fail(c, DTK_ERR_STATE, "dtk_set_penalties_slot: slot %d is part of an unread step", slot);
+  HIPCHK(c, hipSetDevice(c->device));
+  return pen_set(c, 1 + slot, presence, frequency, start);
+}
+
+// Diagnostic: the count table the next step of the sequence will read (slot -1: the single sequence); zeros while the feature is off
+int dtk_token_counts(dtk_ctx* c, int slot, uint16_t* out, int V) {
+  if (!c || !out || slot < -1 || slot >= c->nb || V < 1 || V > c->V) return fail(c, DTK_ERR_ARG, "dtk_token_counts: bad argument");
+  if (!c->pen_tab) { memset(out, 0, sizeof(uint16_t) * (size_t)V); return DTK_OK; }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(out, c->pen_tab + (size_t)(slot + 1) * c->pen_stride, sizeof(uint16_t) * (size_t)V, hipMemcpyDeviceToHost));
+  return DTK_OK;
+}
+
 int dtk_num_slots(const dtk_ctx* c) { return c ? c->nb : 0; }
 int dtk_max_positions(const dtk_ctx* c) { return c ? c->Tmax : 0; }
 int dtk_max_decode_slots(const dtk_ctx* c) { return (c && c->nb > 0) ? max_decode_slots(c) : 0; }
@@ -2299,7 +2447,7 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
   c->blaunched++;
   c->stats.decode_steps++;
   for (int j = 0; j < DTK_MAX_BATCH; ++j)
-    if (active[j]) { c->bseq[(size_t)j].host_next_pos++; c->bseq[(size_t)j].cached_ids.push_back(-1); }
+    if (active[j]) { c->bseq[(size_t)j].host_next_pos++; c->bseq[(size_t)j].cached_ids.push_back(-1); c->bseq[(size_t)j].forced_pending = -1; }
   return DTK_OK;
 }
 
@@ -2400,6 +2548,8 @@ int dtk_kv_fork(dtk_ctx* c, int src, int dst, int n_tokens) {
   if (a.share_src >= 0 && a.share_src != dst && n_tokens <= a.share_len) { b.share_src = a.share_src; b.share_len = n_tokens; }
   else { b.share_src = src; b.share_len = n_tokens; }
   b.cached_ids.assign(a.cached_ids.begin(), a.cached_ids.begin() + n_tokens);
+  b.forced_pending = -1;
+  if (const int rc = pen_rebuild(c, 1 + dst, b.cached_ids.data(), n_tokens)) return rc;
   b.cached_with_image = a.cached_with_image;
   b.image_key = a.image_key;
   b.host_next_pos = n_tokens;
@@ -2472,6 +2622,8 @@ int dtk_resume_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, uint64_t im
   if (sh.share_len > T - 1) sh.share_len = T - 1;
   if (sh.share_len <= 0) { sh.share_src = -1; sh.share_len = 0; }
   sh.cached_ids.resize((size_t)T - 1);
+  sh.forced_pending = ids[T - 1];          // (a dtk_set_penalties_slot before the step that forwards it counts it too)
+  if (const int rc = pen_rebuild(c, 1 + slot, ids, T)) return rc;      // with the forced ids[T-1]: the step that forwards it counts nothing
   sh.host_next_pos = T - 1;
   sh.have_logits = true;                   // "may decode": the first step does not read the logits buffer
   sh.last_reuse_start = T - 1;
@@ -2829,6 +2981,7 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
     c->have_image = false; c->cached_image_key = 0;   // a cached image prefix was projected from the old layer's features
     c->seq0.image_key = 0; c->seq0.cached_ids.clear();
     for (SeqHost& sh : c->bseq) { sh.image_key = 0; sh.cached_ids.clear(); sh.share_src = -1; sh.share_len = 0; }
+    pen_clear_all(c);
   }
   else if (!strcmp(name, "qkv_rope_fused")) c->qkv_rope_fused = value != 0;
   else if (!strcmp(name, "swiglu_fused")) c->swiglu_fused = value != 0;
@@ -2844,6 +2997,7 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
     c->prefill_sk = value;
     c->seq0.cached_ids.clear();
     for (SeqHost& sh : c->bseq) { sh.cached_ids.clear(); sh.share_src = -1; sh.share_len = 0; }
+    pen_clear_all(c);
   }
   else if (!strcmp(name, "gemm_bk")) {
     if (value != 64 && value != 128) return fail(c, DTK_ERR_ARG, "gemm_bk must be 64 or 128");
@@ -3011,6 +3165,7 @@ int dtk_adapter_destroy(dtk_ctx* c) {
   c->have_image = false;                 // a text-conditioned image may be cached: drop every cached prefix
   c->seq0.cached_ids.clear();
   for (auto& b : c->bseq) b.cached_ids.clear();
+  pen_clear_all(c);
   return DTK_OK;
 }
 
@@ -3938,12 +4093,26 @@ int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uin
   return DTK_OK;
 }
 
+struct OpPen { float pp, fp; const int64_t* ids; int n; };     // dtk_op_sample_pen's own arguments
 static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                          const dtk_sampling_ext* ext = nullptr) {
+                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr) {
   HIPCHK(c, hipSetDevice(c->device));
   size_t off = 0;
   OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1); OPBUF(SamplingDev, dsp, 1);
   hipStream_t s = c->stream;
+  PenDev* dpen = nullptr; uint16_t* dcnt = nullptr;
+  if (pen) {      // a count table of the call's own, built by the product scatter kernel from the token list
+    const int stride = (V + 7) & ~7;
+    OPBUF(PenDev, dpen_, 1); OPBUF(uint16_t, dcnt_, stride); OPBUF(int32_t, dids, pen->n > 0 ? pen->n : 1);
+    dpen = dpen_; dcnt = dcnt_;
+    const PenDev pv{pen->pp, pen->fp};
+    std::vector<int32_t> ids32((size_t)(pen->n > 0 ? pen->n : 0));
+    for (int i = 0; i < pen->n; ++i) ids32[(size_t)i] = (int32_t)pen->ids[i];
+    HIPCHK(c, hipMemcpy(dpen, &pv, sizeof pv, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dids, ids32.data(), sizeof(int32_t) * ids32.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(dcnt, 0, sizeof(uint16_t) * (size_t)stride, s));
+    launch_count_scatter(dids, pen->n, dcnt, V, s);
+  }
   HIPCHK(c, hipMemcpyAsync(dl, logits, (size_t)V * 4, hipMemcpyHostToDevice, s));
   ExtDev xd{};
   if (ext) {      // the context's configuration with the call's own (min_p, epsilon_cutoff)
@@ -3958,6 +4127,7 @@ static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int6
   sa.lp_ring = lp_out ? dlp : nullptr;
   if (ext) { sa.sp = dsp; sa.trunc = (xd.qmin != 0 || xd.eps != 0.f) ? 1 : 0; }
   else sa.trunc = c->trunc_single ? 1 : 0;
+  if (pen) { sa.pen = dpen; sa.pen_cnt = dcnt; sa.pen_stride = (V + 7) & ~7; }      // advance = 0: nothing is counted
   const bool needs_topk = c->sampling.do_sample && c->sampling.top_k > 0 && c->sampling.top_k < V;
   if (sample_mb_preferred(V, c->sampling.do_sample != 0) && !needs_topk && !getenv("DTK_SAMPLER")) launch_sample_mb(sa, s); else launch_sample(sa, s);
   HIPCHK(c, hipMemcpyAsync(token_out, dtok, 8, hipMemcpyDeviceToHost, s));
@@ -3991,6 +4161,22 @@ int dtk_op_sample_ext(dtk_ctx* c, const float* logits, int V, int step, int64_t*
   if (const int rc = ext_check(c, ext, "dtk_op_sample_ext")) return rc;
   if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_ext: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
   return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext);
+}
+
+// dtk_op_sample_ext (ext may be null: the context's own min_p / epsilon_cutoff) with a presence / frequency penalty over the counts of a
+// given token list: the PN sampler instantiations and k_count_scatter, whatever the two values are
+int dtk_op_sample_pen(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
+                      const dtk_sampling_ext* ext, float presence, float frequency, const int64_t* counted_ids, int n_counted) {
+  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V) || n_counted < 0 ||
+      n_counted > 65535 || (n_counted > 0 && !counted_ids))
+    return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: bad argument");
+  if (ext) if (const int rc = ext_check(c, ext, "dtk_op_sample_pen")) return rc;
+  if (const int rc = pen_check(c, presence, frequency, 0, "dtk_op_sample_pen")) return rc;
+  for (int i = 0; i < n_counted; ++i)
+    if (counted_ids[i] < 0 || counted_ids[i] >= V) return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: counted id %lld outside [0, %d)", (long long)counted_ids[i], V);
+  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  const OpPen pn{presence, frequency, counted_ids, n_counted};
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn);
 }
 
 }  // extern "C"

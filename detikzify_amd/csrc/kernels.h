@@ -88,7 +88,19 @@ struct SampleArgs {
   int trunc = 0;               // dtk_set_sampling_ext: some sequence of this launch has min_p or epsilon_cutoff != 0: the TR sampler instantiations, which
                                // read SamplingDev::qmin / eps; 0 = the samplers without that code (TR = false: what ran before the two values existed)
   float* lse_ring = nullptr;   // dtk_set_option "top_logprobs" (with lp_ring): the logsumexp the logprob was taken against, indexed as lp_ring (NaN for a forced token)
+  // dtk_set_penalties: some sequence of this launch has a presence or frequency penalty != 0: the PN sampler instantiations, which read
+  // the sequence's PenDev and (values != 0 only) its count table in front of everything else they do with a logit; null = the samplers
+  // without that code (PN = false: what ran before the penalties existed).  Pointers are slot 0's in batched mode
+  const PenDev* pen = nullptr;
+  const uint16_t* pen_cnt = nullptr;   // [pen_stride] per sequence: occurrences of every id among the sequence's counted tokens
+  int pen_stride = 0;                  // elements between two sequences' tables (a multiple of 8: every table is 16-byte aligned)
+  int32_t* pen_tok = nullptr;          // per sequence: the token this step sampled (-1: forced, already counted), for k_count_token
 };
+// dtk_set_penalties: the trailing kernel of a step with penalties, behind the sampler (every read of this step's tables is over): one
+// thread per sequence takes pen_tok and adds 1 to the token's count in the tables of the sequences that have values
+void launch_count_token(const SampleArgs& a, hipStream_t s);
+// count table of one sequence from its counted ids: cnt[ids[i]] += 1 for i < n (ids outside [0, V) are skipped); the table was zeroed
+void launch_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V, hipStream_t s);
 void launch_sample_b(const SampleArgs& a, hipStream_t s);
 void launch_sample(const SampleArgs& a, hipStream_t s);
 // 7-kernel chain for V > 32768 (greedy / temperature / top-p; not top-k); single sequence or (a.bs) every active slot

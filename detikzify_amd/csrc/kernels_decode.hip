@@ -1103,7 +1103,17 @@ __device__ __forceinline__ bool is_banned(const SamplingDev* sp, int i, bool fir
 // min-p keeps q >= SamplingDev::qmin; epsilon keeps q >= (int64)((double)eps * (double)total_m), total_m the mass kept so far (one more
 // block reduction).  Both fold into one mass floor; a floor above 2^31 (epsilon left nothing) keeps the first arg-max alone.
 // TR = false is the kernel as it was before the two values existed.
-template <bool LP, bool TR>
+// PN (SampleArgs::pen, dtk_set_penalties): the presence / frequency penalty.  Every load of a logit is followed by pen_apply with the
+// id's count (after the raw value has gone to the log-sum-exp, before the temperature and the suppression lists), so every pass sees the
+// same z'; a sequence whose two values are 0 reads no count (block-uniform).  The sampled token goes to pen_tok for k_count_token, which
+// runs behind this kernel: no block reads the table after its increment.  PN = false is the kernel as it was before the penalties existed.
+__device__ __forceinline__ unsigned pen_cnt4(uint2 cw, int e) { return ((e < 2 ? cw.x : cw.y) >> ((e & 1) * 16)) & 0xffffu; }
+__device__ __forceinline__ void pen_f32x4(f32x4& v, uint2 cw, float pp, float fp) {
+  if ((cw.x | cw.y) == 0u) return;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = pen_apply(v[e], pen_cnt4(cw, e), pp, fp);
+}
+template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (a.bs) {  // batched decode: one block per slot, same code on that slot's buffers
     const int slot = blockIdx.x;
@@ -1115,6 +1125,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
     a.ring = 1;        // the ring index was applied above
     a.step_override = -1;
   }
@@ -1146,6 +1157,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   const bool first = (draw == 0);
   const bool sampling = sp->do_sample != 0;
   const float invT = sampling ? 1.f / sp->temperature : 1.f;
+  float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
+  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
+  (void)pn_p; (void)pn_f; (void)pn;
 
   // ---- pass 1: masked (scaled) max and first argmax.  16-byte loads, four per thread in flight
   // (the greedy path is one memory round trip + the block reduction)
@@ -1163,6 +1177,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         const int i4 = base + u * SAMPLE_THREADS;
         v[u] = (i4 < V4) ? l4[i4] : (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       }
+      uint2 cw[4];       // PN: the four counts beside every 16-byte load
+      if constexpr (PN) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i4 = base + u * SAMPLE_THREADS;
+          cw[u] = (pn && i4 < V4) ? reinterpret_cast<const uint2*>(a.pen_cnt)[i4] : make_uint2(0u, 0u);
+        }
+      }
+      (void)cw;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i4 = base + u * SAMPLE_THREADS;
@@ -1171,7 +1194,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         for (int e = 0; e < 4; ++e) {
           const int i = i4 * 4 + e;
           if constexpr (LP) lse_push(lm, ls, v[u][e]);
-          float z = v[u][e] * invT;
+          float z;
+          if constexpr (PN) z = pen_apply(v[u][e], pen_cnt4(cw[u], e), pn_p, pn_f) * invT;
+          else z = v[u][e] * invT;
           if (is_banned(sp, i, first)) z = -INFINITY;
           if (z > best || (z == best && i < besti)) { best = z; besti = i; }
         }
@@ -1180,7 +1205,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   } else {
     for (int i = tid; i < V; i += SAMPLE_THREADS) {
       if constexpr (LP) lse_push(lm, ls, a.logits[i]);
-      float z = a.logits[i] * invT;
+      float z;
+      if constexpr (PN) z = (pn ? pen_apply(a.logits[i], a.pen_cnt[i], pn_p, pn_f) : a.logits[i]) * invT;
+      else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       if (z > best || (z == best && i < besti)) { best = z; besti = i; }
     }
@@ -1212,7 +1239,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (sampling) {
     // fixed-point mass q_i = floor(exp(z_i - zmax) * 2^31)  (fits 32 bits; exact integer sums)
     auto mass = [&](int i, float& z) -> unsigned long long {
-      z = a.logits[i] * invT;
+      if constexpr (PN) z = (pn ? pen_apply(a.logits[i], a.pen_cnt[i], pn_p, pn_f) : a.logits[i]) * invT;
+      else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       const float e = expf(z - zmax);
       return (unsigned long long)((double)e * 2147483648.0);
@@ -1384,6 +1412,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       a.st->next_pos = a.st->next_pos + 1;
       a.st->draw = forced > 0 ? draw : draw + 1;
       if (forced > 0) a.st->force_plus1 = 0;
+      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
     }
   }
   if (a.advance) {
@@ -1404,8 +1433,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
 // Same integer semantics as k_sample / oracle/sampling.py (bit-exact kept set and draws).
 // LP as in k_sample: the raw logits are in registers before the temperature is applied, so the thread's log-sum-exp state is their
 // maximum and one expf per logit.  TR as in k_sample: the mass floor is one more walk over the 32 keys and one block reduction.
+// PN as in k_sample: the thread's 32 counts are one 64-byte line, read as 8-byte words beside the 16-byte loads of the logits.
 #define SF_PER 32
-template <bool LP, bool TR>
+template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   if (a.bs) {
     const int slot = blockIdx.x;
@@ -1417,6 +1447,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
+    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
     a.ring = 1;
     a.step_override = -1;
   }
@@ -1446,6 +1477,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   const bool first = (draw == 0);
   const bool sampling = sp->do_sample != 0;
   const float invT = sampling ? 1.f / sp->temperature : 1.f;
+  float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
+  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
+  (void)pn_p; (void)pn_f; (void)pn;
   const int i0 = tid * SF_PER;
 
   // ---- the one pass over the logits
@@ -1457,18 +1491,20 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       const f32x4* l4 = reinterpret_cast<const f32x4*>(a.logits + i0);
 #pragma unroll
       for (int k = 0; k < SF_PER / 4; ++k) {
-        const f32x4 v = l4[k];
+        f32x4 v = l4[k];
         const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
         if (m4 > lm) { ls *= expf(lm - m4); lm = m4; }
         ls += (expf(v[0] - lm) + expf(v[1] - lm)) + (expf(v[2] - lm) + expf(v[3] - lm));
+        if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
       }
     } else {
 #pragma unroll
       for (int k = 0; k < SF_PER; ++k) {
-        const float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
+        float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
         lse_push(lm, ls, v);
+        if constexpr (PN) if (pn && i0 + k < V) v = pen_apply(v, a.pen_cnt[i0 + k], pn_p, pn_f);
         z[k] = v * invT;
       }
     }
@@ -1476,10 +1512,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     const f32x4* l4 = reinterpret_cast<const f32x4*>(a.logits + i0);
 #pragma unroll
     for (int k = 0; k < SF_PER / 4; ++k) {
-      const f32x4 v = l4[k];
+      f32x4 v = l4[k];
+      if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
     }
+  } else if constexpr (PN) {
+#pragma unroll
+    for (int k = 0; k < SF_PER; ++k)
+      z[k] = (i0 + k < V) ? (pn ? pen_apply(a.logits[i0 + k], a.pen_cnt[i0 + k], pn_p, pn_f) : a.logits[i0 + k]) * invT : -INFINITY;
   } else {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) z[k] = (i0 + k < V) ? a.logits[i0 + k] * invT : -INFINITY;
@@ -1706,6 +1747,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       a.st->next_pos = a.st->next_pos + 1;
       a.st->draw = forced > 0 ? draw : draw + 1;
       if (forced > 0) a.st->force_plus1 = 0;
+      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
     }
   }
   if (a.advance) {
@@ -1775,20 +1817,55 @@ static bool sample_fast_ok(const SampleArgs& a) {
 void launch_sample(const SampleArgs& a, hipStream_t s) {
   launch_sample_b(a, s);       // a.nslots == 1 without a.bs
 }
-void launch_sample_b(const SampleArgs& a, hipStream_t s) {
+// a.trunc == 0 (no sequence of this launch has min_p / epsilon_cutoff): the TR = false instantiations, the kernels as they were; a.pen
+// == nullptr (none has a presence / frequency penalty): the PN = false ones, likewise
+template <bool PN>
+static void launch_sample_t(const SampleArgs& a, hipStream_t s) {
   const dim3 g(a.bs ? a.nslots : 1), b(SAMPLE_THREADS);
-  // a.trunc == 0 (no sequence of this launch has min_p / epsilon_cutoff): the TR = false instantiations, the kernels as they were
   if (sample_fast_ok(a)) {
     if (a.trunc) {
-      if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, true>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_sample_fast<false, true>), g, b, 0, s, a);
-    } else if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, false>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_sample_fast<false, false>), g, b, 0, s, a);
+      if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, true, PN>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_sample_fast<false, true, PN>), g, b, 0, s, a);
+    } else if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, false, PN>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sample_fast<false, false, PN>), g, b, 0, s, a);
     return;
   }
   if (a.trunc) {
-    if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_sample<false, true>), g, b, 0, s, a);
-  } else if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, false>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_sample<false, false>), g, b, 0, s, a);
+    if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, true, PN>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sample<false, true, PN>), g, b, 0, s, a);
+  } else if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, false, PN>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((k_sample<false, false, PN>), g, b, 0, s, a);
+}
+void launch_sample_b(const SampleArgs& a, hipStream_t s) {
+  if (a.pen) launch_sample_t<true>(a, s); else launch_sample_t<false>(a, s);
+}
+
+// dtk_set_penalties: the count tables.  A count is one half of a 32-bit word; both kernels add to the word that holds it (vector
+// atomics); a count never reaches 65 536 (max_positions < 65 536, checked where the tables are allocated), so nothing carries over.
+__global__ __launch_bounds__(256) void k_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V) {
+  unsigned* w = reinterpret_cast<unsigned*>(cnt);
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int t = ids[i];
+    if (t >= 0 && t < V) atomicAdd(w + (t >> 1), (t & 1) ? 0x10000u : 1u);
+  }
+}
+void launch_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_count_scatter, dim3(1), dim3(256), 0, s, ids, n, cnt, V);
+}
+// behind the sampler of a step: thread j takes sequence j's pen_tok (left by the PN sampler: the sampled token, -1 for a forced one)
+// and counts it where the sequence has values; a sequence without values keeps no table
+__global__ __launch_bounds__(DTK_MAX_BATCH) void k_count_token(SampleArgs a) {
+  const int j = threadIdx.x;
+  if (j >= (a.bs ? a.nslots : 1)) return;
+  if (a.bs && !a.bs->active[j]) return;
+  const int t = a.pen_tok[j];
+  if (t < 0) return;
+  a.pen_tok[j] = -1;
+  const PenDev p = a.pen[j];
+  if ((p.pp == 0.f && p.fp == 0.f) || t >= a.V) return;
+  unsigned* w = reinterpret_cast<unsigned*>(const_cast<uint16_t*>(a.pen_cnt) + (size_t)j * a.pen_stride);
+  atomicAdd(w + (t >> 1), (t & 1) ? 0x10000u : 1u);
+}
+void launch_count_token(const SampleArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_count_token, dim3(1), dim3(DTK_MAX_BATCH), 0, s, a);
 }

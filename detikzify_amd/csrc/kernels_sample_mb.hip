@@ -18,6 +18,11 @@
 // kept after top-p and min-p (bpre); one more kernel, k_smb_trunc, folds those in slice order into total_m, forms the mass floor
 // max(qmin, (int64)((double)eps * (double)total_m)) — above 2^31: the first arg-max alone survives — and leaves the final bkept; P6
 // applies the floor.  Without it the chain is the 7 kernels above, unchanged.
+// PN (SampleArgs::pen, dtk_set_penalties): the presence / frequency penalty, applied by mb_load — so every kernel of the chain that
+// reloads the row sees the same z' — after the raw values have been handed out for the log-sum-exp, before the temperature and the
+// suppression lists.  The block of k_smb_draw that writes the token may run before other blocks of its slot have loaded their slice (the
+// hazard draw_snap exists for), so the token is NOT counted here: it goes to pen_tok, and k_count_token, a kernel behind the chain,
+// counts it.  PN = false are the kernels as they were before the penalties existed.
 // Supports greedy, temperature, top-p and the suppression lists; top-k > 0 stays on the single-block kernel (the API
 // re-captures the graph when a sampling configuration needs the other kind).
 #include "kernels.h"
@@ -38,6 +43,7 @@ struct MbElems {
 };
 
 // per-(sequence) view of the arguments in batched mode
+template <bool PN = false>
 __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
   if (a.bs) {
     if (!a.bs->active[slot]) return false;
@@ -51,27 +57,49 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
     a.ring = 1;
     a.step_override = -1;
     a.mb += slot;
+    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
   }
   return true;
 }
 
 // this thread's 8 consecutive logits: scaled, suppressed ids -> -inf, keys; out-of-range -> -inf.  raw (k_smb_max<true> only): the
 // same loads before the temperature and the suppression lists, out-of-range -> -inf
+// PN: z' = pen_apply(z, count) in place of every z (a sequence whose two values are 0 reads no count: block-uniform); raw stays raw
+template <bool PN = false>
 __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* sp, bool first, float invT, int base, MbElems& e,
                                         float* raw = nullptr) {
   const int V = a.V;
+  float pn_p = 0.f, pn_f = 0.f; bool pn = false;
+  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
+  (void)pn_p; (void)pn_f; (void)pn;
   if (base + MB_PER <= V && ((reinterpret_cast<uintptr_t>(a.logits + base) & 15) == 0)) {
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.logits + base);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.logits + base + 4);
+    if constexpr (PN) {
+      uint32_t cw[4] = {0u, 0u, 0u, 0u};      // the 8 counts: one 16-byte load (base is a multiple of 8, the table 16-byte aligned)
+      if (pn) { const u32x4 c4 = *reinterpret_cast<const u32x4*>(a.pen_cnt + base); cw[0] = c4[0]; cw[1] = c4[1]; cw[2] = c4[2]; cw[3] = c4[3]; }
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { e.z[i] = v0[i] * invT; e.z[4 + i] = v1[i] * invT; }
+      for (int i = 0; i < 4; ++i) {
+        e.z[i] = pen_apply(v0[i], (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f) * invT;
+        e.z[4 + i] = pen_apply(v1[i], (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f) * invT;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { e.z[i] = v0[i] * invT; e.z[4 + i] = v1[i] * invT; }
+    }
     if (raw) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) { raw[i] = v0[i]; raw[4 + i] = v1[i]; }
     }
   } else {
+    if constexpr (PN) {
 #pragma unroll
-    for (int i = 0; i < MB_PER; ++i) e.z[i] = (base + i < V) ? a.logits[base + i] * invT : -INFINITY;
+      for (int i = 0; i < MB_PER; ++i)
+        e.z[i] = (base + i < V) ? (pn ? pen_apply(a.logits[base + i], a.pen_cnt[base + i], pn_p, pn_f) : a.logits[base + i]) * invT : -INFINITY;
+    } else {
+#pragma unroll
+      for (int i = 0; i < MB_PER; ++i) e.z[i] = (base + i < V) ? a.logits[base + i] * invT : -INFINITY;
+    }
     if (raw) {
 #pragma unroll
       for (int i = 0; i < MB_PER; ++i) raw[i] = (base + i < V) ? a.logits[base + i] : -INFINITY;
@@ -119,9 +147,9 @@ __device__ __forceinline__ void mb_common(const SampleArgs& a, int nblk, MbCommo
 }
 
 // ---- P0.  LP (SampleArgs::lp_ring): the slice's log-sum-exp state of its raw logits goes out with its maximum
-template <bool LP>
+template <bool LP, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
-  if (!mb_bind(a, blockIdx.y)) return;
+  if (!mb_bind<PN>(a, blockIdx.y)) return;
   __shared__ SamplingDev s_sp;
   __shared__ float s_f[16];
   __shared__ int s_i[16];
@@ -136,7 +164,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
   float lm = -INFINITY, ls = 0.f;
   if constexpr (LP) {
     float raw[MB_PER];
-    mb_load(a, &s_sp, draw == 0, invT, base, e, raw);
+    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e, raw);
 #pragma unroll
     for (int i = 0; i < MB_PER; ++i) lm = fmaxf(lm, raw[i]);
     if (lm != -INFINITY) {
@@ -146,7 +174,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
     lse_wave(lm, ls);
     if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; }
   } else {
-    mb_load(a, &s_sp, draw == 0, invT, base, e);
+    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e);
   }
   float best = -INFINITY; int besti = 0x7fffffff;
 #pragma unroll
@@ -190,9 +218,9 @@ __device__ __forceinline__ void mb_select(const SampleArgs& a, int lv, unsigned 
 }
 
 // ---- P1..P4: LV = 3, 2, 1, 0
-template <int LV>
+template <int LV, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk) {
-  if (!mb_bind(a, blockIdx.y)) return;
+  if (!mb_bind<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long w_m[16][256];   // per-wave private histograms: conflicts only inside a wave
   __shared__ unsigned int w_c[16][256];
@@ -236,7 +264,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk)
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
   mb_mass(e, cm.zmax);
   constexpr int shift = LV * 8;
   // run-length aggregation over the thread's 8 consecutive elements (neighbours mostly share the digit), then atomics
@@ -265,9 +293,9 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk)
 }
 
 // ---- P5: threshold + kept mass per slice.  TR: the mass of the slice's entries that pass top-p and min-p, to bpre
-template <bool TR>
+template <bool TR, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk) {
-  if (!mb_bind(a, blockIdx.y)) return;
+  if (!mb_bind<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long s_m[256];
   __shared__ unsigned int s_c[256];
@@ -292,7 +320,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
   mb_mass(e, cm.zmax);
   unsigned long long mine = 0;
 #pragma unroll
@@ -314,8 +342,9 @@ __device__ __forceinline__ bool mb_kept_tr(uint32_t key, uint32_t q, int id, uin
 }
 
 // ---- TR only, between P5 and P6: the mass floor from the slices' bpre (folded in slice order by every block), the final kept mass per slice
+template <bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk) {
-  if (!mb_bind(a, blockIdx.y)) return;
+  if (!mb_bind<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long s_q[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
@@ -334,7 +363,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
   mb_mass(e, cm.zmax);
   unsigned long long mine = 0;
 #pragma unroll
@@ -349,9 +378,9 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk
 
 // ---- P6: draw (or arg-max), token ring, DecState, embedding gather.  LP: thread 0 of the block that writes the token folds the
 // slices' log-sum-exp states in slice order and stores the token's (logprob, sample_logprob)
-template <bool LP, bool TR>
+template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk) {
-  if (!mb_bind(a, blockIdx.y)) return;
+  if (!mb_bind<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long scan[MB_THREADS];
   __shared__ int s_token;
@@ -387,7 +416,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
       const float invT = 1.f / cm.sp.temperature;
       MbElems e;
       const int base = blk * MB_SLICE + tid * MB_PER;
-      mb_load(a, &cm.sp, draw == 0, invT, base, e);
+      mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
       mb_mass(e, cm.zmax);
       uint32_t qfl = 0; bool fb = false;
       if constexpr (TR) { qfl = a.mb->qfl; fb = a.mb->fb != 0; }
@@ -451,6 +480,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
       a.st->next_pos = a.st->next_pos + 1;
       a.st->draw = forced > 0 ? draw : draw + 1;
       if (forced > 0) a.st->force_plus1 = 0;
+      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
     }
   }
   if (a.advance) {
@@ -460,23 +490,28 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
   }
 }
 
-void launch_sample_mb(const SampleArgs& a, hipStream_t s) {
+template <bool PN>
+static void launch_sample_mb_t(const SampleArgs& a, hipStream_t s) {
   const int nblk = (a.V + MB_SLICE - 1) / MB_SLICE;   // <= DTK_SAMPLE_MB_MAX_SLICES
   const dim3 g(nblk, a.bs ? a.nslots : 1), b(MB_THREADS);
-  if (a.lp_ring) hipLaunchKernelGGL(k_smb_max<true>, g, b, 0, s, a);
-  else hipLaunchKernelGGL(k_smb_max<false>, g, b, 0, s, a);
-  hipLaunchKernelGGL((k_smb_hist<3>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<2>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<1>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<0>), g, b, 0, s, a, nblk);
+  if (a.lp_ring) hipLaunchKernelGGL((k_smb_max<true, PN>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((k_smb_max<false, PN>), g, b, 0, s, a);
+  hipLaunchKernelGGL((k_smb_hist<3, PN>), g, b, 0, s, a, nblk);
+  hipLaunchKernelGGL((k_smb_hist<2, PN>), g, b, 0, s, a, nblk);
+  hipLaunchKernelGGL((k_smb_hist<1, PN>), g, b, 0, s, a, nblk);
+  hipLaunchKernelGGL((k_smb_hist<0, PN>), g, b, 0, s, a, nblk);
   if (a.trunc) {
-    hipLaunchKernelGGL(k_smb_kept<true>, g, b, 0, s, a, nblk);
-    hipLaunchKernelGGL(k_smb_trunc, g, b, 0, s, a, nblk);
-    if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, true>), g, b, 0, s, a, nblk);
-    else hipLaunchKernelGGL((k_smb_draw<false, true>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_kept<true, PN>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL(k_smb_trunc<PN>, g, b, 0, s, a, nblk);
+    if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, true, PN>), g, b, 0, s, a, nblk);
+    else hipLaunchKernelGGL((k_smb_draw<false, true, PN>), g, b, 0, s, a, nblk);
     return;
   }
-  hipLaunchKernelGGL(k_smb_kept<false>, g, b, 0, s, a, nblk);
-  if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, false>), g, b, 0, s, a, nblk);
-  else hipLaunchKernelGGL((k_smb_draw<false, false>), g, b, 0, s, a, nblk);
+  hipLaunchKernelGGL((k_smb_kept<false, PN>), g, b, 0, s, a, nblk);
+  if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, false, PN>), g, b, 0, s, a, nblk);
+  else hipLaunchKernelGGL((k_smb_draw<false, false, PN>), g, b, 0, s, a, nblk);
+}
+// a.pen == nullptr (no sequence of this launch has a presence / frequency penalty): the PN = false instantiations, the chain as it was
+void launch_sample_mb(const SampleArgs& a, hipStream_t s) {
+  if (a.pen) launch_sample_mb_t<true>(a, s); else launch_sample_mb_t<false>(a, s);
 }

@@ -180,8 +180,9 @@ class BatchEngine:
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
-        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, check_truncation, text_image_key, text_key
+        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, check_penalties, check_truncation, text_image_key, text_key
         check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
+        pen = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
         tids = adapter_text(text_ids) if text_ids is not None else None
         tkey = text_key(tids) if tids is not None else 0
         ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
@@ -255,7 +256,8 @@ class BatchEngine:
                 t0 = time.perf_counter()
                 # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
                 # without them leaves the slot at 0 / 0
-                plain = {k: v for k, v in sampling.items() if k not in ("min_p", "epsilon_cutoff")}
+                plain = {k: v for k, v in sampling.items()
+                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start")}
                 self.model.set_sampling(slot=slot, **plain)
                 ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
                 set_ext = getattr(self.model, "set_sampling_ext", None)
@@ -264,6 +266,14 @@ class BatchEngine:
                 elif any(ext):
                     from .._lib import DtkError
                     raise DtkError("this device takes no min_p / epsilon_cutoff")
+                # the presence / frequency penalty likewise (penalty_start: the prompt length unless the sequence says otherwise); the
+                # fork / prefill / resume below builds the slot's count table from the sequence's ids
+                set_pen = getattr(self.model, "set_penalties", None)
+                if set_pen is not None:
+                    set_pen(pen[0], pen[1], (int(ids.numel()) if pen[2] is None else pen[2]) if (pen[0] or pen[1]) else 0, slot=slot)
+                elif pen[0] or pen[1]:
+                    from .._lib import DtkError
+                    raise DtkError("this device takes no presence / frequency penalty")
                 if resume:
                     self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)

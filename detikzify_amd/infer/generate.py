@@ -140,7 +140,12 @@ class DetikzifyGenerator:
     def __init__(self, model, processor, image: Optional[Image.Image], text: Optional[str] = None,
                  metric=None, compile_timeout: Optional[int] = 60, mcts_timeout: Optional[int] = None,
                  streamer=None, control: Optional[ExplicitAbort] = None, exploration: float = 0.6,
-                 strict: bool = False, document_class: Type[TikzDocument] = TikzDocument, processed=None, rng=None, **gen_kwargs):
+                 strict: bool = False, document_class: Type[TikzDocument] = TikzDocument, processed=None, rng=None,
+                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, **gen_kwargs):
+        """presence_penalty / frequency_penalty (model.generate's; None / 0 = off): counted from the end of the image prompt on, so a
+        rollout that continues a node of the tree penalises the whole program text so far, however its slot got there"""
+        if presence_penalty or frequency_penalty:
+            gen_kwargs = {**gen_kwargs, "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty}
         self.model, self.processor = model, processor
         self.image, self.text, self.metric = image, text, metric
         self.compile_timeout, self.mcts_timeout = compile_timeout, mcts_timeout
@@ -221,6 +226,8 @@ class DetikzifyGenerator:
     def generate(self, input_ids: torch.Tensor, streamer=None, **gen_kwargs) -> torch.Tensor:
         sinks = StreamerList([s for s in (streamer, self.streamer) if s])
         options = {**self.gen_kwargs, **gen_kwargs}
+        if (options.get("presence_penalty") or options.get("frequency_penalty")) and options.get("penalty_start") is None:
+            options["penalty_start"] = int(self.montecarlo.root_node.token_ids.numel())       # the program text so far counts, the prompt does not
         budget = options.get("max_length", self.model.generation_config.to_dict().get("max_length"))
         n = input_ids.numel()
         finished = n > 0 and input_ids[-1] == unwrap(self.processor).tokenizer.eos_token_id

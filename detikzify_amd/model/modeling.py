@@ -177,6 +177,22 @@ def check_truncation(min_p: Optional[float], epsilon_cutoff: Optional[float]) ->
     return float(mp), float(eps)
 
 
+def check_penalties(presence_penalty: Optional[float], frequency_penalty: Optional[float],
+                    penalty_start: Optional[int] = None) -> Tuple[float, float, Optional[int]]:
+    """the `presence_penalty` / `frequency_penalty` / `penalty_start` arguments of generate / sample -> (presence, frequency, start),
+    0.0 = off (None); start None = the caller's default (generate: the prompt length).  Out of range: ValueError before anything runs"""
+    out = []
+    for name, v in (("presence_penalty", presence_penalty), ("frequency_penalty", frequency_penalty)):
+        x = 0.0 if v is None else v
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not (-2.0 <= x <= 2.0):
+            raise ValueError(f"`{name}` has to be a float in the [-2, 2] interval, but is {v}")
+        out.append(float(x))
+    if penalty_start is not None:
+        if isinstance(penalty_start, bool) or not isinstance(penalty_start, int) or penalty_start < 0:
+            raise ValueError(f"`penalty_start` has to be an integer >= 0, but is {penalty_start}")
+    return out[0], out[1], penalty_start
+
+
 def _is_neutral(value: Any, neutral: Any) -> bool:
     if neutral is None:
         return value is None
@@ -817,6 +833,28 @@ class DetikzifyForCausalLM:
         else:
             self._check(fn(self._ctx, int(slot), C.byref(x)), "dtk_set_sampling_slot_ext")
 
+    def set_penalties(self, presence: float = 0.0, frequency: float = 0.0, start: int = 0, slot: Optional[int] = None):
+        """presence / frequency penalty of the sequence the last set_sampling configured (dtk_set_penalties / dtk_set_penalties_slot):
+        z'[i] = z[i] - (presence + frequency * count[i]) for every id counted among the sequence's tokens from position `start` on
+        (DESIGN §3.1h).  set_sampling itself resets the three values to 0"""
+        presence, frequency, start = check_penalties(presence, frequency, int(start))
+        fn = getattr(self.lib, "dtk_set_penalties" if slot is None else "dtk_set_penalties_slot", None)
+        if fn is None:          # a device without the two calls has nothing to reset
+            if presence or frequency:
+                raise _lib.DtkError("this device takes no presence / frequency penalty")
+            return
+        if slot is None:
+            self._check(fn(self._ctx, presence, frequency, start), "dtk_set_penalties")
+        else:
+            self._check(fn(self._ctx, int(slot), presence, frequency, start), "dtk_set_penalties_slot")
+
+    def token_counts(self, slot: Optional[int] = None) -> torch.Tensor:
+        """diagnostic: the count table the sequence's next step will read (uint16 per vocabulary entry, as int32)"""
+        V = int(self.config.vocab)
+        out = (C.c_uint16 * V)()
+        self._check(self.lib.dtk_token_counts(self._ctx, -1 if slot is None else int(slot), out, V), "dtk_token_counts")
+        return torch.tensor(list(out), dtype=torch.int32)
+
     # ---- batched decode (independent rollouts share one pass over the weights) -----------------------
     def num_slots(self) -> int:
         return int(self.lib.dtk_num_slots(self._ctx))
@@ -998,7 +1036,8 @@ class DetikzifyForCausalLM:
                  max_new_tokens: Optional[int] = None, eos_token_id=None, seed: Optional[int] = None,
                  inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, return_logprobs: bool = False,
                  top_logprobs: Optional[int] = None, min_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
-                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                 penalty_start: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1011,6 +1050,11 @@ class DetikzifyForCausalLM:
 
         min_p / epsilon_cutoff: HF's MinPLogitsWarper / EpsilonLogitsWarper behind top-p (HF's order), as thresholds on the sampler's
         integer masses; 0 / None = off; ignored by greedy decoding like temperature, top-k and top-p.
+
+        presence_penalty / frequency_penalty: the OpenAI / vLLM pair, in [-2, 2], 0 / None = off: every id that occurs c > 0 times
+        among the sequence's tokens from position penalty_start on (default: the prompt length, so only generated tokens count) has
+        presence + frequency * c taken off its raw logit in front of the whole sampler chain, greedy included.  The
+        reported log-probabilities stay the model's own.  HF's repetition_penalty stays refused.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1039,11 +1083,17 @@ class DetikzifyForCausalLM:
         gc = self.generation_config
         min_p, epsilon_cutoff = check_truncation(getattr(gc, "min_p", None) if min_p is None else min_p,
                                                  getattr(gc, "epsilon_cutoff", None) if epsilon_cutoff is None else epsilon_cutoff)
+        presence_penalty, frequency_penalty, penalty_start = check_penalties(
+            getattr(gc, "presence_penalty", None) if presence_penalty is None else presence_penalty,
+            getattr(gc, "frequency_penalty", None) if frequency_penalty is None else frequency_penalty,
+            getattr(gc, "penalty_start", None) if penalty_start is None else penalty_start)
         do_sample = gc.do_sample if do_sample is None else do_sample
         temperature = gc.temperature if temperature is None else temperature
         top_p = gc.top_p if top_p is None else top_p
         top_k = gc.top_k if top_k is None else top_k
         T = ids.shape[1]
+        if penalty_start is None:
+            penalty_start = T
         if max_new_tokens is not None:
             max_length = T + int(max_new_tokens)
         elif max_length is None:
@@ -1138,7 +1188,9 @@ class DetikzifyForCausalLM:
             with engine.sequence(ids[0], pixel_values, dict(
                     do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, seed=seed, bad_ids=bad,
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or (),
-                    **({"min_p": min_p, "epsilon_cutoff": epsilon_cutoff} if (min_p or epsilon_cutoff) else {})),
+                    **({"min_p": min_p, "epsilon_cutoff": epsilon_cutoff} if (min_p or epsilon_cutoff) else {}),
+                    **({"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "penalty_start": penalty_start}
+                       if (presence_penalty or frequency_penalty) else {})),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
                     **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
@@ -1157,6 +1209,8 @@ class DetikzifyForCausalLM:
                                   begin_suppress_tokens or (), suppress_tokens or ())
                 if min_p or epsilon_cutoff:       # (set_sampling reset both)
                     self.set_sampling_ext(min_p, epsilon_cutoff)
+                if presence_penalty or frequency_penalty:       # (likewise; the prefill below builds the count table)
+                    self.set_penalties(presence_penalty, frequency_penalty, penalty_start)
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
                     if topk:

@@ -708,6 +708,47 @@ int  dtk_engine_submit_ext(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x
                            uint64_t* ticket_out);
 int  dtk_engine_set_sampling_ext_op(dtk_engine* e, int (*set_sampling_slot_ext)(void* dev, int slot, const dtk_sampling_ext* x));
 
+/* presence_penalty and frequency_penalty (additive, ABI 7): the OpenAI / vLLM pair, a transform of the raw logits in front of the whole
+ * sampler chain.  Per sequence: presence pp and frequency fp, finite, in [-2, 2] (0 / 0 = off), and penalty_start s >= 0.  c[i] = the
+ * occurrences of id i among the sequence's tokens at positions [s, next_pos): the prompt from s on and every token sampled or forced
+ * since — a property of the token list, however the slot got there (prefill with or without DTK_PREFILL_REUSE_PREFIX, dtk_kv_fork,
+ * dtk_resume_slot, an engine's join).  For c[i] > 0:  z'[i] = z[i] - (float)((double)pp + (double)fp * (double)c[i]), one fp32
+ * subtraction on the raw fp32 logit; c[i] == 0 leaves the bits of z[i].  z' replaces z in front of the suppression lists (-inf stays
+ * -inf), the temperature, top-k, top-p, min-p, epsilon and the draw; greedy takes the arg-max of z' (lowest id on ties).  logprob, the
+ * top-k records and their logsumexp stay over the RAW logits (what dtk_score reports); sample_logprob and filtered_probs_out are over the
+ * final kept set of the penalised chain.  A sequence with 0 / 0 draws what it draws alone, whatever its company in a batched step.
+ * The counts are uint16 tables on the device (allocated with the first non-zero value: refused with DTK_ERR_RANGE if max_positions >=
+ * 65536), rebuilt wherever the host redefines the sequence and advanced by one kernel behind the step's sampler.
+ *   dtk_set_penalties / dtk_set_penalties_slot   called AFTER dtk_set_sampling / dtk_set_sampling_slot, which reset the three values to
+ *                             0 / 0 / 0.  DTK_ERR_ARG outside the ranges or on NaN; DTK_ERR_STATE while steps of the sequence are unread.
+ *                             A sequence that exists already gets its table rebuilt from its ids — a slot resumed by dtk_resume_slot
+ *                             whose forced step has not been launched yet included, forced id and all — so the values may be set
+ *                             before or after the call that defines the sequence.  (Set before it, as both engines do, the table
+ *                             is built twice: once here from whatever the slot held, once by the prefill / fork / resume; each build
+ *                             is a zero-fill, a copy of at most max_positions ids and a one-block kernel, queued on the stream.)
+ *                             A context none of whose sequences has a value runs
+ *                             the sampler kernels it ran before the penalties existed; the first that sets one makes the next step
+ *                             re-capture its graph with the kernels that read them.
+ *   dtk_op_sample_pen         dtk_op_sample_ext (x may be NULL: the context's own min_p / epsilon_cutoff) with the call's own values and a
+ *                             token list whose multiset is the counts (ids in [0, V), at most 65535).
+ *   dtk_token_counts          diagnostic: the V first counts the sequence's next step will read (slot -1: the single sequence); zeros
+ *                             while no sequence of the context ever had a value, for a sequence without values, and after whatever
+ *                             leaves a sequence undefined (weights or an adapter loaded, dtk_score_packed).
+ *   dtk_engine_submit_pen     dtk_engine_submit_ext (x may be NULL) whose sequence also carries the three values: the loop applies them
+ *                             right after the join's sampling calls.  dtk_engine_create wires dtk_set_penalties_slot itself; an engine of
+ *                             dtk_engine_create_ops gets the op through dtk_engine_set_penalties_op, and without one a join whose values
+ *                             are not 0 / 0 fails in submit with DTK_ERR_STATE.  With the op every join calls it — a join without
+ *                             values with 0 / 0 / 0 — so a slot never inherits its previous sequence's values. */
+int  dtk_set_penalties(dtk_ctx* ctx, float presence, float frequency, int start);
+int  dtk_set_penalties_slot(dtk_ctx* ctx, int slot, float presence, float frequency, int start);
+int  dtk_op_sample_pen(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
+                       float* lp_out /* [2] or NULL */, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency,
+                       const int64_t* counted_ids, int n_counted);
+int  dtk_token_counts(dtk_ctx* ctx, int slot, uint16_t* out, int V);
+int  dtk_engine_submit_pen(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency, int start,
+                           const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out);
+int  dtk_engine_set_penalties_op(dtk_engine* e, int (*set_penalties_slot)(void* dev, int slot, float presence, float frequency, int start));
+
 #ifdef __cplusplus
 }
 #endif
