@@ -69,7 +69,7 @@ class DtkStats(C.Structure):
         ("probe_kernel_ms_sum", C.c_double), ("probe_kernel_launches", C.c_uint64),
         ("probe_kernel_bytes", C.c_uint64), ("probe_event_pair_ms", C.c_double),
         ("last_batch_step_slots", C.c_uint32), ("device_errors", C.c_uint32),
-        ("last_batch_step_fp8_mfma", C.c_uint32), ("reserved0", C.c_uint32),
+        ("last_batch_step_fp8_mfma", C.c_uint32), ("w13_counts", C.c_uint32),
     ]
 
 
@@ -211,6 +211,11 @@ SYMBOLS = {
     # additive (ABI stays 7): one role of the single-sequence decode GEMV family (prologue, epilogue, variant, weight format)
     "dtk_op_gemv_role": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [C.c_float, _P, _P, _P, _P,
                                    C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    # additive (ABI stays 7): 13-bit planes of bf16 weight rows (csrc/w13.h): the host packer for the CPU tests, the op's packing outcome
+    "dtk_w13_row_bytes": (C.c_int, [C.c_int]),
+    "dtk_w13_pack_host": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
+    "dtk_w13_unpack_host": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "dtk_w13_op_bad_rows": (C.c_int, [_P]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     # additive (ABI stays 7): dtk_op_gemv on MXFP4 weights (the loader's quantiser + the decode kernel); last = de-quantised W or NULL

@@ -22,6 +22,10 @@
 
 #include "../../include/dtk.h"
 #include "kernels.h"
+#include "w13.h"
+#ifndef W13_DEFAULT
+#define W13_DEFAULT 1      // option "w13" of a new context (on: DESIGN 3.1c'')
+#endif
 #include "mx_quant.h"
 
 int& dtk_lds_attr_error(int device) {     // common.h: set by a launcher whose hipFuncSetAttribute was refused, per device
@@ -70,6 +74,8 @@ struct LayerW {
   float *s_wqkv = nullptr, *s_wo = nullptr, *s_wgu = nullptr, *s_wdown = nullptr;    // per-row power-of-two scales
   uint8_t *f4_wqkv = nullptr, *f4_wo = nullptr, *f4_wgu = nullptr, *f4_wdown = nullptr;  // MXFP4 E2M1 codes (weight_format 2): [N][ceil(K/32)*16] bytes
   uint8_t *e4_wqkv = nullptr, *e4_wo = nullptr, *e4_wgu = nullptr, *e4_wdown = nullptr;  // ... and their E8M0 block scales: [N][ceil(K/32)]
+  uint8_t *p13_wqkv = nullptr, *p13_wo = nullptr, *p13_wgu = nullptr, *p13_wdown = nullptr;  // 13-bit planes of the bf16 rows (w13.h; bf16 contexts, option "w13"): null = not packed
+  uint8_t *h13_wqkv = nullptr, *h13_wo = nullptr, *h13_wgu = nullptr, *h13_wdown = nullptr;  // ... and the rows' hb bytes
   uint8_t *t8_wqkv = nullptr, *t8_wo = nullptr, *t8_wgu = nullptr, *t8_wdown = nullptr;  // fp8 pair-tiled copies (batched decode, fp8)
   uint8_t *m_wqkv = nullptr, *m_wo = nullptr, *m_wgu = nullptr, *m_wdown = nullptr;      // fp8 MX tiles (fp8 matrix-core step; down in groups of 16)
 };
@@ -189,6 +195,13 @@ struct dtk_ctx {
   bool fp8_ready = false;    // the quantised copies of wfmt 1 / 2 match the bf16 masters
   uint8_t* q_lm_head = nullptr;
   float* s_lm_head = nullptr;
+  // 13-bit planes of the bf16 rows for the single-sequence step (w13.h): packed lazily by ensure_w13 from the bf16 masters, which stay
+  int w13 = W13_DEFAULT;     // dtk_set_option "w13"
+  bool w13_ready = false;    // the planes match the masters (load_tensor / fill_synthetic clear it)
+  uint8_t *p13_lm_head = nullptr, *h13_lm_head = nullptr;
+  unsigned* w13_bad = nullptr;                      // device counter of the packer
+  int w13_op_bad_rows = -1;                         // unpackable rows of the last dtk_op_gemv_role call that packed planes (-1: none yet)
+  uint32_t w13_packed = 0, w13_unpacked = 0, w13_bad_rows = 0;   // matrices with / without planes, unpackable rows (dtk_stats.w13_counts)
   uint64_t cached_image_key = 0;
   bool have_image = false;
   // ---- batched decode (dtk_*_slot / dtk_decode_batch_*): up to 64 decoding slots (+1) with their own KV
@@ -848,6 +861,8 @@ static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
   launch_top_logits(t, c->stream);
 }
 
+static inline bool w13_on(const dtk_ctx* c) { return c->wfmt == 0 && c->w13 != 0; }   // the single-sequence step streams 13-bit planes (ensure_w13)
+
 void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   hipStream_t s = c->stream;
   SampleArgs sa;
@@ -869,6 +884,8 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
     // 1. input_layernorm + q/k/v projections + RoPE + KV append
     g.W = w.wqkv; g.W8 = w.q_wqkv; g.wscale = w.s_wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1;
     g.W4 = w.f4_wqkv; g.S4 = w.e4_wqkv;      // MXFP4 contexts: the four layer roles stream codes + block scales (null otherwise)
+    const bool p13 = w13_on(c) && c->w13_ready;   // bf16 contexts: the roles whose matrix has 13-bit planes stream those (same results)
+    g.Wp = p13 ? w.p13_wqkv : nullptr; g.Wh = w.h13_wqkv;
     g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l);
     launch_gemv(PRO_RMSNORM, EPI_QKV, g, s);
     // 2. split-K attention over the cache
@@ -883,12 +900,14 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
     // 3. (combine +) o_proj + residual
     g.W = w.wo; g.W8 = w.q_wo; g.wscale = w.s_wo; g.N = c->d; g.K = c->d; g.y = c->x;
     g.W4 = w.f4_wo; g.S4 = w.e4_wo;
+    g.Wp = p13 ? w.p13_wo : nullptr; g.Wh = w.h13_wo;
     const bool partials = ad.combine == 0 && !(ad.threads && ad.S == 1);   // o_proj's prologue reduces the split partials
     if (!partials) { g.x = c->attn_out; launch_gemv(PRO_COPY, EPI_RESID, g, s); }
     else launch_gemv(PRO_ATTN, EPI_RESID, g, s);
     // 4. post_attention_layernorm + gate/up + SiLU*mul
     g.W = w.wgu; g.W8 = w.q_wgu; g.wscale = w.s_wgu; g.N = 2 * c->ff; g.K = c->d; g.x = c->x; g.norm_w = w.ln2; g.y = c->act;
     g.W4 = w.f4_wgu; g.S4 = w.e4_wgu;
+    g.Wp = p13 ? w.p13_wgu : nullptr; g.Wh = w.h13_wgu;
     const bool probe_here = with_probe && (l == c->L / 2);
     if (probe_here) (void)hipEventRecord(c->probe_a, s);
     launch_gemv(PRO_RMSNORM, EPI_SWIGLU, g, s);
@@ -896,9 +915,11 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
     // 5. down + residual
     g.W = w.wdown; g.W8 = w.q_wdown; g.wscale = w.s_wdown; g.N = c->d; g.K = c->ff; g.x = c->act; g.y = c->x;
     g.W4 = w.f4_wdown; g.S4 = w.e4_wdown;
+    g.Wp = p13 ? w.p13_wdown : nullptr; g.Wh = w.h13_wdown;
     launch_gemv(PRO_COPY, EPI_RESID, g, s);
   }
   GemvArgs g{};      // lm_head: fp8 in an MXFP4 context too (q_lm_head / s_lm_head)
+  if (w13_on(c) && c->w13_ready) { g.Wp = c->p13_lm_head; g.Wh = c->h13_lm_head; }
   g.W = c->lm_head; g.W8 = c->q_lm_head; g.wscale = c->s_lm_head; g.N = c->V; g.K = c->d; g.x = c->x; g.norm_w = c->final_norm;
   g.eps = c->cfg.rms_eps; g.logits = c->logits;
   launch_gemv(PRO_RMSNORM, EPI_LOGITS, g, s);
@@ -1105,6 +1126,100 @@ void ensure_fp8_weights(dtk_ctx* c) {
   c->fp8_ready = true;
   c->tiled_ready = false;
   c->ptiled_ready = false;
+}
+
+// accounting: W = decoder layers + final norm + lm_head as the single-sequence step streams them, and the bytes of the
+// probe's kernel (gate/up of the middle layer)
+static void set_weight_bytes(dtk_ctx* c) {
+  const uint64_t kvd = (uint64_t)c->KVH * c->hd;
+  const uint64_t attn_lin = (uint64_t)2 * c->d * c->d + 2 * kvd * c->d;   // q, o: d x d; k, v: kvd x d
+  const uint64_t per_layer = attn_lin + (uint64_t)3 * c->d * c->ff + 2 * (uint64_t)c->d;
+  c->stats.weight_bytes_per_token = 2 * (per_layer * c->L + (uint64_t)c->d + (uint64_t)c->V * c->d);
+  if (c->wfmt == 1) {  // 1 byte per Linear weight + fp32 scale per row; norm vectors stay bf16
+    const uint64_t lin = attn_lin + (uint64_t)3 * c->d * c->ff;
+    const uint64_t rows = (uint64_t)3 * c->d + 2 * kvd + (uint64_t)2 * c->ff;
+    c->stats.weight_bytes_per_token = (lin + 4 * rows + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
+  }
+  if (c->wfmt == 2) {  // 16 code bytes + 1 scale byte per 32-weight block (rows padded to whole blocks); lm_head fp8 + fp32 row scales; norms bf16
+    const uint64_t bd = mxfp4_row_scales(c->d), bf = mxfp4_row_scales(c->ff);
+    const uint64_t blocks = ((uint64_t)2 * c->d + 2 * kvd + (uint64_t)2 * c->ff) * bd + (uint64_t)c->d * bf;
+    c->stats.weight_bytes_per_token = (17 * blocks + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
+  }
+  c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * c->d * (c->wfmt == 1 ? 1 : 2);
+  if (c->wfmt == 2) c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * 17 * mxfp4_row_scales(c->d);
+  if (w13_on(c) && c->w13_ready) {   // planes + the row byte where a matrix has them, bf16 rows where it has not
+    auto mat = [](const uint8_t* planes, uint64_t N, int K) { return planes ? N * (w13_row_bytes(K) + 1) : 2 * N * (uint64_t)K; };
+    uint64_t W = 2 * ((uint64_t)2 * c->d * c->L + (uint64_t)c->d) + mat(c->p13_lm_head, (uint64_t)c->V, c->d);
+    for (int l = 0; l < c->L; ++l) {
+      const LayerW& w = c->layers[l];
+      W += mat(w.p13_wqkv, (uint64_t)c->d + 2 * kvd, c->d) + mat(w.p13_wo, (uint64_t)c->d, c->d) + mat(w.p13_wgu, (uint64_t)2 * c->ff, c->d) +
+           mat(w.p13_wdown, (uint64_t)c->d, c->ff);
+    }
+    c->stats.weight_bytes_per_token = W;
+    c->stats.probe_kernel_bytes = mat(c->layers[c->L / 2].p13_wgu, (uint64_t)2 * c->ff, c->d);
+  }
+}
+static void w13_set_stats(dtk_ctx* c) {
+  const uint32_t rows = c->w13_bad_rows > 4095u ? 4095u : c->w13_bad_rows;
+  c->stats.w13_counts = (c->w13_packed & 1023u) | ((c->w13_unpacked & 1023u) << 10) | (rows << 20);
+}
+static int w13_pack_one(dtk_ctx* c, int pro, int epi, const bf16_t* W, int N, int K, uint8_t** planes, uint8_t** hb) {
+  GemvArgs g{};
+  g.N = N; g.K = K; g.d = c->d; g.ff = c->ff; g.hd = c->hd;
+  if (!gemv_w13_takes(pro, epi, g)) {      // the role's bf16 kernel folds in an order no 13-bit shape has (a split-K default): it stays bf16
+    if (*planes) { (void)hipFree(*planes); *planes = nullptr; }
+    if (*hb) { (void)hipFree(*hb); *hb = nullptr; }
+    return DTK_OK;
+  }
+  if (!*planes) HIPCHK(c, hipMalloc((void**)planes, (size_t)N * w13_row_bytes(K)));
+  if (!*hb) HIPCHK(c, hipMalloc((void**)hb, (size_t)N));
+  HIPCHK(c, hipMemsetAsync(c->w13_bad, 0, sizeof(unsigned), c->stream));
+  launch_pack_w13_rows(W, *planes, *hb, c->w13_bad, N, K, c->stream);
+  unsigned bad = 0;
+  HIPCHK(c, hipMemcpyAsync(&bad, c->w13_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (bad) {
+    (void)hipFree(*planes); *planes = nullptr;
+    (void)hipFree(*hb); *hb = nullptr;
+    c->w13_unpacked++; c->w13_bad_rows += bad;
+  } else c->w13_packed++;
+  return DTK_OK;
+}
+static void w13_free(dtk_ctx* c);
+// 13-bit planes (w13.h) of the four Linear roles of every layer and of lm_head, for the single-sequence step of a bf16 context with
+// option "w13" on.  The bf16 masters are only read: prefill, scoring, the batched and multi-vector steps, read_tensor and the oracle
+// see them as before.  A matrix with an unpackable row keeps no planes, and its role then runs the bf16 kernel.  Never inside a capture
+// (it allocates and synchronises): the callers run it in front of ensure_graph.  A failure part-way (an allocation) frees every plane, so
+// the context is left as with no planes at all and the call can be repeated.
+int ensure_w13(dtk_ctx* c) {
+  if (!w13_on(c) || c->w13_ready) return DTK_OK;
+  if (!c->w13_bad) HIPCHK(c, hipMalloc((void**)&c->w13_bad, sizeof(unsigned)));
+  c->w13_packed = c->w13_unpacked = c->w13_bad_rows = 0;
+  const int qkvn = c->d + 2 * c->KVH * c->hd;
+  for (int l = 0; l < c->L; ++l) {
+    LayerW& w = c->layers[l];
+    int rc = w13_pack_one(c, PRO_RMSNORM, EPI_QKV, w.wqkv, qkvn, c->d, &w.p13_wqkv, &w.h13_wqkv);
+    if (!rc) rc = w13_pack_one(c, PRO_ATTN, EPI_RESID, w.wo, c->d, c->d, &w.p13_wo, &w.h13_wo);
+    if (!rc) rc = w13_pack_one(c, PRO_RMSNORM, EPI_SWIGLU, w.wgu, 2 * c->ff, c->d, &w.p13_wgu, &w.h13_wgu);
+    if (!rc) rc = w13_pack_one(c, PRO_COPY, EPI_RESID, w.wdown, c->d, c->ff, &w.p13_wdown, &w.h13_wdown);
+    if (rc) { w13_free(c); return rc; }
+  }
+  int rc = w13_pack_one(c, PRO_RMSNORM, EPI_LOGITS, c->lm_head, c->V, c->d, &c->p13_lm_head, &c->h13_lm_head);
+  if (rc) { w13_free(c); return rc; }
+  c->w13_ready = true;
+  w13_set_stats(c);
+  set_weight_bytes(c);
+  return DTK_OK;
+}
+static void w13_free(dtk_ctx* c) {
+  for (auto& w : c->layers) {
+    uint8_t** ps[8] = {&w.p13_wqkv, &w.h13_wqkv, &w.p13_wo, &w.h13_wo, &w.p13_wgu, &w.h13_wgu, &w.p13_wdown, &w.h13_wdown};
+    for (uint8_t** p : ps) if (*p) { (void)hipFree(*p); *p = nullptr; }
+  }
+  if (c->p13_lm_head) { (void)hipFree(c->p13_lm_head); c->p13_lm_head = nullptr; }
+  if (c->h13_lm_head) { (void)hipFree(c->h13_lm_head); c->h13_lm_head = nullptr; }
+  c->w13_ready = false;
+  c->w13_packed = c->w13_unpacked = c->w13_bad_rows = 0;
 }
 
 void ensure_tiled_weights(dtk_ctx* c);
@@ -1475,23 +1590,8 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   CCHK(hipStreamSynchronize(c->stream));
 #undef CCHK
   // accounting: W = decoder layers + final norm + lm_head, K = 2*L*d*2
-  const uint64_t kvd = (uint64_t)c->KVH * c->hd;
-  const uint64_t attn_lin = (uint64_t)2 * c->d * c->d + 2 * kvd * c->d;   // q, o: d x d; k, v: kvd x d
-  const uint64_t per_layer = attn_lin + (uint64_t)3 * c->d * c->ff + 2 * (uint64_t)c->d;
-  c->stats.weight_bytes_per_token = 2 * (per_layer * c->L + (uint64_t)c->d + (uint64_t)c->V * c->d);
-  if (c->wfmt == 1) {  // 1 byte per Linear weight + fp32 scale per row; norm vectors stay bf16
-    const uint64_t lin = attn_lin + (uint64_t)3 * c->d * c->ff;
-    const uint64_t rows = (uint64_t)3 * c->d + 2 * kvd + (uint64_t)2 * c->ff;
-    c->stats.weight_bytes_per_token = (lin + 4 * rows + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
-  }
-  if (c->wfmt == 2) {  // 16 code bytes + 1 scale byte per 32-weight block (rows padded to whole blocks); lm_head fp8 + fp32 row scales; norms bf16
-    const uint64_t bd = mxfp4_row_scales(c->d), bf = mxfp4_row_scales(c->ff);
-    const uint64_t blocks = ((uint64_t)2 * c->d + 2 * kvd + (uint64_t)2 * c->ff) * bd + (uint64_t)c->d * bf;
-    c->stats.weight_bytes_per_token = (17 * blocks + 4 * (uint64_t)c->d) * c->L + 2 * (uint64_t)c->d + (uint64_t)c->V * c->d + 4 * (uint64_t)c->V;
-  }
-  c->stats.kv_bytes_per_ctx_token = (uint64_t)2 * c->L * kvd * 2;
-  c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * c->d * (c->wfmt == 1 ? 1 : 2);
-  if (c->wfmt == 2) c->stats.probe_kernel_bytes = (uint64_t)2 * c->ff * 17 * mxfp4_row_scales(c->d);
+  set_weight_bytes(c);
+  c->stats.kv_bytes_per_ctx_token = (uint64_t)2 * c->L * (uint64_t)c->KVH * c->hd * 2;
   *out = c;
   // Batched attention shape, a property of the CONTEXT (like the multi-vector family): 64 decoding slots -> shared prefixes on the
   // matrix cores + 2-wave tail blocks; fewer -> the per-slot walk with 4-wave blocks.  Measured over a rollout's private lengths
@@ -1524,6 +1624,8 @@ void dtk_destroy(dtk_ctx* c) {
   (void)hipSetDevice(c->device);
   if (c->ad) (void)dtk_adapter_destroy(c);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  w13_free(c);
+  if (c->w13_bad) (void)hipFree(c->w13_bad);
   if (c->graph_exec) (void)hipGraphExecDestroy(c->graph_exec);
   if (c->graph) (void)hipGraphDestroy(c->graph);
   if (c->graph_short_exec) (void)hipGraphExecDestroy(c->graph_short_exec);
@@ -1615,6 +1717,7 @@ int dtk_load_tensor(dtk_ctx* c, const char* name, const void* host, int dtype, c
   c->tiled_ready = false;
   c->ptiled_ready = false;
   c->fp8_ready = false;
+  if (c->w13_ready) { c->w13_ready = false; drop_graph(c); set_weight_bytes(c); }   // the planes are packed again before the next single-sequence step
   return DTK_OK;
 }
 
@@ -1656,6 +1759,7 @@ int dtk_fill_synthetic(dtk_ctx* c, uint64_t seed) {
   c->tiled_ready = false;
   c->ptiled_ready = false;
   c->fp8_ready = false;
+  if (c->w13_ready) { c->w13_ready = false; drop_graph(c); set_weight_bytes(c); }   // the planes are packed again before the next single-sequence step
   return DTK_OK;
 }
 
@@ -2675,6 +2779,7 @@ int dtk_decode_launch(dtk_ctx* c) {
   if (c->seq0.host_next_pos >= c->Tmax) return fail(c, DTK_ERR_RANGE, "context length %d reached max_positions", c->seq0.host_next_pos);
   HIPCHK(c, hipSetDevice(c->device));
   ensure_fp8_weights(c);
+  if (int rc = ensure_w13(c)) return rc;
   if (c->use_graph) {
     int rc = ensure_graph(c);
     if (rc) return rc;
@@ -2789,12 +2894,52 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
   const bool same_layer = (variant & 0x100) != 0;  // every launch re-reads layer 0 (Infinity Cache probe)
   const int plain = (variant >> 9) & 3;            // 0x200: same weights through PRO_COPY + EPI_STORE; 0x400: PRO_RMSNORM + EPI_STORE
   const bool fmt = (variant & 0x800) != 0;
+  // bf16 contexts with option "w13": 0xff streams what the step streams - the 13-bit planes of the roles that have them, in the step's shape
+  // (so the time goes with dtk_stats.probe_kernel_bytes).  0x2000 | 0xff: the bf16 rows in the step's bf16 kernel whatever "w13" says.
+  // 0x1000 | shape: the planes in that 13-bit shape; a role whose matrices the step keeps as bf16 rows (o_proj) is packed for this call only.
+  const bool b13 = (variant & 0x1000) != 0, raw16 = (variant & 0x2000) != 0;
+  if (b13 && (fmt || raw16 || plain || same_layer || c->wfmt != 0 || !c->w13 || (variant & 0xff) == 0xff))
+    return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: 0x1000 | shape (13-bit planes) needs a bf16 context with w13 = 1, a shape number and no other flag");
+  if (raw16 && ((variant & 0xff) != 0xff || plain || fmt)) return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: 0x2000 (bf16 rows) goes with variant 0xff only");
+  const bool step13 = w13_on(c) && !raw16 && !plain && (variant & 0xff) == 0xff;      // the shipped kernel on what the step streams
+  struct Tmp13 { std::vector<uint8_t*> p, h; ~Tmp13() { for (auto x : p) if (x) (void)hipFree(x); for (auto x : h) if (x) (void)hipFree(x); } } tmp13;
+  if (b13 || step13) { if (int rc = ensure_w13(c)) return rc; }
+  if (b13) {
+    for (int l = 0; l < c->L && role != 4; ++l) {
+      const LayerW& w = c->layers[l];
+      const uint8_t* p = role == 0 ? w.p13_wqkv : (role == 1 ? w.p13_wo : (role == 2 ? w.p13_wgu : w.p13_wdown));
+      if (p) continue;
+      if (role != 1) return fail(c, DTK_ERR_STATE, "dtk_bench_gemv: role %d has no 13-bit planes in layer %d (an unpackable row, or a bf16 fold no 13-bit shape has)", role, l);
+      if (!c->w13_bad) HIPCHK(c, hipMalloc((void**)&c->w13_bad, sizeof(unsigned)));
+      uint8_t *pp = nullptr, *hh = nullptr;         // o_proj: planes of this call's own
+      HIPCHK(c, hipMalloc((void**)&pp, (size_t)c->d * w13_row_bytes(c->d)));
+      tmp13.p.push_back(pp);
+      HIPCHK(c, hipMalloc((void**)&hh, (size_t)c->d));
+      tmp13.h.push_back(hh);
+      unsigned bad = 0;
+      HIPCHK(c, hipMemsetAsync(c->w13_bad, 0, sizeof(unsigned), s));
+      launch_pack_w13_rows(w.wo, pp, hh, c->w13_bad, c->d, c->d, s);
+      HIPCHK(c, hipMemcpyAsync(&bad, c->w13_bad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+      HIPCHK(c, hipStreamSynchronize(s));
+      if (bad) return fail(c, DTK_ERR_STATE, "dtk_bench_gemv: o_proj of layer %d has %u unpackable row(s)", l, bad);
+    }
+    if (role == 4 && !c->p13_lm_head) return fail(c, DTK_ERR_STATE, "dtk_bench_gemv: lm_head has no 13-bit planes");
+  }
   if (fmt && ((variant & 0xff) != 0xff || plain))   // the numbered variants and the plain probes are bf16 instantiations
     return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: 0x800 (the context's weight format) goes with variant 0xff only");
   if (fmt) ensure_fp8_weights(c);
   variant &= 0xff;
   const bool shipped = variant == 0xff;            // 0xff: whatever launch_gemv picks for this role and model (the kernel a decode step runs)
-  auto launch = [&](int pro, int epi, const GemvArgs& g) { if (shipped) launch_gemv(pro, epi, g, s); else launch_gemv_variant(pro, epi, variant, g, s); };
+  if (b13) {
+    const int pro = (role == 1 || role == 3) ? PRO_COPY : PRO_RMSNORM;
+    const int epi = role == 0 ? EPI_QKV : (role == 2 ? EPI_SWIGLU : (role == 4 ? EPI_LOGITS : EPI_RESID));
+    if (!gemv_w13_has(pro, epi, variant)) return fail(c, DTK_ERR_ARG, "dtk_bench_gemv: no 13-bit shape %d for role %d", variant, role);
+  }
+  auto launch = [&](int pro, int epi, const GemvArgs& g) {
+    if (b13) launch_gemv_w13_variant(pro, epi, variant, g, s);
+    else if (shipped) launch_gemv(pro, epi, g, s);
+    else launch_gemv_variant(pro, epi, variant, g, s);
+  };
   auto one_pass = [&]() {
     for (int l = 0; l < c->L; ++l) {
       const LayerW& w = c->layers[same_layer ? 0 : l];
@@ -2817,6 +2962,13 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
         else if (role == 2) { g.W8 = w.q_wgu; g.wscale = w.s_wgu; g.W4 = w.f4_wgu; g.S4 = w.e4_wgu; }
         else if (role == 3) { g.W8 = w.q_wdown; g.wscale = w.s_wdown; g.W4 = w.f4_wdown; g.S4 = w.e4_wdown; }
         else { g.W8 = c->q_lm_head; g.wscale = c->s_lm_head; }
+      }
+      if (b13 || step13) {
+        if (role == 0) { g.Wp = w.p13_wqkv; g.Wh = w.h13_wqkv; }
+        else if (role == 1) { g.Wp = w.p13_wo; g.Wh = w.h13_wo; if (!g.Wp && b13) { g.Wp = tmp13.p[(size_t)l]; g.Wh = tmp13.h[(size_t)l]; } }
+        else if (role == 2) { g.Wp = w.p13_wgu; g.Wh = w.h13_wgu; }
+        else if (role == 3) { g.Wp = w.p13_wdown; g.Wh = w.h13_wdown; }
+        else { g.Wp = c->p13_lm_head; g.Wh = c->h13_lm_head; }
       }
       if (role == 0) { g.W = w.wqkv; g.N = c->d + 2 * c->KVH * c->hd; g.K = c->d; g.x = c->x; g.norm_w = w.ln1; g.q_out = c->q; g.kcache = kcache(c, l); g.vcache = vcache(c, l); launch(PRO_RMSNORM, EPI_QKV, g); }
       else if (role == 1) { g.W = w.wo; g.N = c->d; g.K = c->d; g.x = c->attn_out; g.y = c->q; launch(PRO_COPY, EPI_RESID, g); }
@@ -2845,6 +2997,15 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!strcmp(name, "attn_full_max")) c->attn_full_max = value;
+  else if (!strcmp(name, "w13")) {     // bf16 contexts: the single-sequence step streams the 13-bit planes of its weight rows (w13.h; same results)
+    if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "w13 must be 0 or 1");
+    if (value != c->w13) {
+      if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "w13: %d single-sequence decode step(s) are unread", (int)(c->launched - c->waited));
+      c->w13 = value; drop_graph(c);
+      if (!value) { w13_free(c); w13_set_stats(c); }
+      set_weight_bytes(c);
+    }
+  }
   else if (!strcmp(name, "logprobs")) {     // every sampled token comes with (logprob, sample_logprob): the LP sampler instantiations + one more D2H copy per step
     if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "logprobs must be 0 or 1");
     if (value == 0 && c->top_logprobs) return fail(c, DTK_ERR_STATE, "logprobs: top_logprobs = %d needs it (set \"top_logprobs\" to 0 first)", c->top_logprobs);
@@ -3789,6 +3950,16 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   if ((W != nullptr) + (W8 != nullptr) + (W4 != nullptr) != 1 || (W8 && !wscale) || (!W8 && wscale) || (!W4 != !S4))
     return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: exactly one of W | W8 + wscale | W4 + S4");
   const int fmt = W4 ? 2 : (W8 ? 1 : 0);
+  // variant 0x1000 + v on bf16 operands: W is packed into 13-bit planes on the device (launch_pack_w13_rows) and the role streams those in
+  // 13-bit shape v (0xff: the shape a decode step runs); with an unpackable row the planes are dropped and launch_gemv takes the bf16 kernel
+  const bool f13 = variant >= 0x1000;
+  const int v13 = variant - 0x1000;
+  if (f13) {
+    if (fmt != 0) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: the 13-bit planes are packed from bf16 operands (W)");
+    if (v13 != 0xff && !gemv_w13_has(pro, epi, v13)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no 13-bit kernel for prologue %d, epilogue %d, shape %d", pro, epi, v13);
+    if (v13 == 0xff && !gemv_w13_has(pro, epi, 0)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no 13-bit kernel for prologue %d, epilogue %d", pro, epi);
+    variant = -1;
+  }
   if (N < 1 || K < 8 || (K & 7) || (fmt == 1 && (K & 15))) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: N >= 1, K a multiple of 8 (16 for fp8 weights)");
   if (pro < PRO_COPY || pro > PRO_ATTN || epi < EPI_STORE || epi > EPI_LOGITS) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: unknown prologue %d or epilogue %d", pro, epi);
   if (!gemv_role_variant_ok(fmt, pro, epi, variant))
@@ -3818,6 +3989,7 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   const size_t hs = pro == PRO_ATTN ? (size_t)H * S : 0;
   size_t off = 0;
   OPBUF(uint8_t, dW, w_bytes); OPBUF(float, dws, fmt == 1 ? N : 0); OPBUF(uint8_t, dS4, fmt == 2 ? (size_t)N * KC4 : 0);
+  OPBUF(uint8_t, dWp, f13 ? (size_t)N * w13_row_bytes(K) : 0); OPBUF(uint8_t, dWh, f13 ? (size_t)N : 0); OPBUF(unsigned, dbad, f13 ? 1 : 0);
   OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dcos, rope); OPBUF(bf16_t, dsin, rope); OPBUF(DecState, dst, 1);
   OPBUF(float, dpm, hs); OPBUF(float, dpl, hs); OPBUF(float, dpo, hs * hd);
   constexpr size_t GUARD = 256;            // bytes behind every result buffer that must still hold scratch_fill after the launch
@@ -3855,7 +4027,18 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.pm = dpm; g.pl = dpl; g.po = dpo; g.S = S;
   g.y = dy; g.logits = dl; g.q_out = dq; g.kcache = dk; g.vcache = dv; g.rope_cos = dcos; g.rope_sin = dsin; g.st = dst;
   g.T_max = T_max; g.d = d; g.ff = ff; g.H = H; g.KVH = KVH; g.hd = hd;
-  if (variant < 0) launch_gemv(pro, epi, g, s);
+  if (f13) {
+    unsigned bad = 0;
+    HIPCHK(c, hipMemsetAsync(dbad, 0, sizeof(unsigned), s));
+    launch_pack_w13_rows(g.W, dWp, dWh, dbad, N, K, s);
+    HIPCHK(c, hipMemcpyAsync(&bad, dbad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipMemsetAsync(dbad, scratch_fill, sizeof(unsigned), s));
+    c->w13_op_bad_rows = (int)bad;
+    if (!bad) { g.Wp = dWp; g.Wh = dWh; }
+  }
+  if (f13 && g.Wp && v13 != 0xff) launch_gemv_w13_variant(pro, epi, v13, g, s);
+  else if (variant < 0) launch_gemv(pro, epi, g, s);
   else if (fmt == 1) launch_gemv_f8_variant(pro, epi, variant, g, s);
   else launch_gemv_variant(pro, epi, variant, g, s);
   HIPCHK(c, hipGetLastError());
@@ -3877,6 +4060,21 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   else HIPCHK(c, hipMemcpy(y_io, dy, ny * 2, hipMemcpyDeviceToHost));
   return DTK_OK;
 }
+
+// ---- w13.h's host code for the CPU tests: rows [N][K] bf16 <-> planes [N][dtk_w13_row_bytes(K)] + hb[N]; bad[N] = weights below the
+// row's window (0 = the row is packed exactly)
+int dtk_w13_row_bytes(int K) { return (K < 8 || (K & 7)) ? -1 : (int)w13_row_bytes(K); }
+int dtk_w13_pack_host(const uint16_t* W, int N, int K, uint8_t* planes, uint8_t* hb, int32_t* bad) {
+  if (!W || !planes || !hb || !bad || N < 1 || K < 8 || (K & 7)) return DTK_ERR_ARG;
+  for (int r = 0; r < N; ++r) bad[r] = w13_pack_row(W + (size_t)r * K, K, planes + (size_t)r * w13_row_bytes(K), hb + r);
+  return DTK_OK;
+}
+int dtk_w13_unpack_host(const uint8_t* planes, const uint8_t* hb, int N, int K, uint16_t* W) {
+  if (!W || !planes || !hb || N < 1 || K < 8 || (K & 7)) return DTK_ERR_ARG;
+  for (int r = 0; r < N; ++r) w13_unpack_row(planes + (size_t)r * w13_row_bytes(K), hb[r], K, W + (size_t)r * K);
+  return DTK_OK;
+}
+int dtk_w13_op_bad_rows(dtk_ctx* c) { return c ? c->w13_op_bad_rows : -1; }
 
 // ---- the batched decode GEMV family alone (dtk_op_gemv_b / dtk_op_gemv_bkp): host operands into the op scratch, the step's own
 // launchers (launch_retile / launch_retile_f8, launch_rmsnorm_b, launch_gemv_b, launch_gemv_bkp, launch_resid_norm_b) unchanged

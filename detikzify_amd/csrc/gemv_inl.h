@@ -5,6 +5,7 @@
 // order whatever U is, so every kernel built on these helpers produces the same fp32 sum for the same (row, x).
 #pragma once
 #include "common.h"
+#include "w13.h"
 
 template <int NR, int U>
 __device__ __forceinline__ void gemv_load(u32x4 (&w)[NR][U], const u32x4* (&rows)[NR],
@@ -132,5 +133,90 @@ __device__ __forceinline__ void gemv_fma_f4(float (&acc)[NR], const u32x4 (&w)[N
     }
 #pragma unroll
     for (int r = 0; r < NR; ++r) acc[r] = dot32_f4(w[r][u], f4_scale(sc[r][u]), x0, x1, x2, x3, acc[r]);
+  }
+}
+
+// 13-bit planes of a bf16 row (w13.h): a stage is U k-iterations (U a multiple of 4 = whole sign blocks): per row U / 2 dwordx4 of low
+// bytes, U / 2 dwordx2 of exponent codes and U / 4 dwords of signs.  The operands rebuilt in registers are the bf16 row's own bits, and
+// a lane folds chunk lane, lane + 64, ... with the same four chained v_dot2c_f32_bf16 as gemv_fma, so every fp32 sum equals the bf16
+// kernel's.  x lies linearly in LDS as for bf16.  Nothing in here branches on data: the only conditions are the wave-uniform "unit
+// inside the row" and gemv_fma's "chunk inside x".
+typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
+
+// four exponent codes (one per byte, 0 .. 15) -> the four high bytes without their signs: code ? lo + code : 0.  lo2 = lo | lo << 16;
+// a byte's "code != 0" is bit 4 of code + 15, and lo + 15 < 256, so the packed 16-bit multiply-add cannot carry between bytes
+__device__ __forceinline__ uint32_t w13_high4(uint32_t codes, uint32_t lo2) {
+  const uint32_t nz = ((codes + 0x0f0f0f0fu) >> 4) & 0x01010101u;
+  const u16x2_t r = __builtin_bit_cast(u16x2_t, nz) * __builtin_bit_cast(u16x2_t, lo2) + __builtin_bit_cast(u16x2_t, codes);
+  return __builtin_bit_cast(uint32_t, r);
+}
+
+// one chunk: la / lb = the low bytes of weights 0..3 / 4..7, n = the 8 codes, s = the block's sign dword, i = k-iteration in the block
+__device__ __forceinline__ float dot8_w13(uint32_t la, uint32_t lb, uint32_t n, uint32_t s, int i, uint32_t lo2, const u32x4& x, float c) {
+  const uint32_t he = w13_high4(n & 0x0f0f0f0fu, lo2) | ((s << (7 - 2 * i)) & 0x80808080u);
+  const uint32_t ho = w13_high4((n >> 4) & 0x0f0f0f0fu, lo2) | ((s << (6 - 2 * i)) & 0x80808080u);
+  // v_perm_b32: bytes 0..3 of the selector space are the second operand (low bytes), 4..7 the first (high bytes)
+  c = dot2(__builtin_amdgcn_perm(he, la, 0x05010400u), x[0], c);
+  c = dot2(__builtin_amdgcn_perm(he, la, 0x07030602u), x[1], c);
+  c = dot2(__builtin_amdgcn_perm(ho, lb, 0x05010400u), x[2], c);
+  c = dot2(__builtin_amdgcn_perm(ho, lb, 0x07030602u), x[3], c);
+  return c;
+}
+
+template <int NR, int U>
+__device__ __forceinline__ void gemv_load_w13(u32x4 (&wl)[NR][U / 2], u32x2 (&wn)[NR][U / 2], uint32_t (&ws)[NR][U / 4],
+                                              const u32x4* (&rows)[NR], int g, int lane, int J2, int n_off, int s_off) {
+  static_assert(U % 4 == 0, "a stage is whole sign blocks");
+  if (2 * (g * (U / 4) + U / 4) <= J2) {   // wave-uniform: every unit of the stage is inside the row -> no predication
+#pragma unroll
+    for (int ub = 0; ub < U / 4; ++ub) {
+      const int b = g * (U / 4) + ub;
+#pragma unroll
+      for (int r = 0; r < NR; ++r) {
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(rows[r]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          wl[r][2 * ub + h] = ld_nt(rows[r] + ((2 * b + h) * 64 + lane));
+          wn[r][2 * ub + h] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + n_off) + ((2 * b + h) * 64 + lane));
+        }
+        ws[r][ub] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p + s_off) + (b * 64 + lane));
+      }
+    }
+    return;
+  }
+#pragma unroll
+  for (int ub = 0; ub < U / 4; ++ub) {
+    const int b = g * (U / 4) + ub;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const unsigned char* p = reinterpret_cast<const unsigned char*>(rows[r]);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const bool ok = 2 * b + h < J2;    // rows end on a unit; what lies behind the end decodes to +0
+        const u32x4 zl = {0u, 0u, 0u, 0u};
+        const u32x2 zn = {0u, 0u};
+        wl[r][2 * ub + h] = ok ? ld_nt(rows[r] + ((2 * b + h) * 64 + lane)) : zl;
+        wn[r][2 * ub + h] = ok ? __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p + n_off) + ((2 * b + h) * 64 + lane)) : zn;
+      }
+      ws[r][ub] = (2 * b < J2) ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p + s_off) + (b * 64 + lane)) : 0u;
+    }
+  }
+}
+
+template <int NR, int U>
+__device__ __forceinline__ void gemv_fma_w13(float (&acc)[NR], const u32x4 (&wl)[NR][U / 2], const u32x2 (&wn)[NR][U / 2],
+                                             const uint32_t (&ws)[NR][U / 4], const uint32_t (&lo2)[NR],
+                                             const u32x4* xs, int g, int lane, int K8) {
+  const bool full = 64 * (g * U + U) <= K8;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int c = lane + 64 * (g * U + u);
+    u32x4 xv = {0u, 0u, 0u, 0u};
+    if (full || c < K8) xv = xs[c];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const u32x4& l = wl[r][u >> 1];
+      acc[r] = dot8_w13((u & 1) ? l[2] : l[0], (u & 1) ? l[3] : l[1], wn[r][u >> 1][u & 1], ws[r][u >> 2], u & 3, lo2[r], xv, acc[r]);
+    }
   }
 }

@@ -88,9 +88,12 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0
 // HD: head dim of the EPI_QKV rows / the PRO_ATTN partials (128, or 64: a unit is the pair (i, i+32), a head 8 chunks of x).
 // F4: MXFP4 rows (a.W4 codes, a.S4 block scales; gemv_inl.h): a chunk = one 32-weight block, x swizzled in LDS (f4_xswz) and
 // zero-padded to whole blocks, no row scale in the epilogue.  Every F4 branch is compile-time: the bf16 / fp8 code is unchanged.
-template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128, bool F4 = false>
+// W13: the 13-bit planes of bf16 rows (a.Wp rows, a.Wh row bytes; w13.h, gemv_inl.h): the operands rebuilt in registers are the bf16
+// row's bits and the fold order is gemv_fma's, so the sums are the bf16 kernel's; x lies linearly in LDS; U is a multiple of 4.  Every
+// W13 branch is compile-time as well.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128, bool F4 = false, bool W13 = false>
 __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
-  static_assert(!(F4 && F8), "one weight format");
+  static_assert(!(F4 && F8) && !(W13 && (F4 || F8)), "one weight format");
   constexpr bool PAIRED = (EPI == EPI_QKV) || (EPI == EPI_SWIGLU);
   constexpr int NR = PAIRED ? 2 * R : R;
   constexpr int THREADS = WAVES * 64;
@@ -103,8 +106,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   u32x4* xs = reinterpret_cast<u32x4*>(smem);
   const int K8 = a.K >> 3;                     // 16-byte chunks of x (bf16)
   const int KC = F4 ? ((a.K + 31) >> 5) : (F8 ? (a.K >> 4) : K8);         // 16-byte chunks of one weight row
-  const size_t row_bytes = F4 ? (size_t)KC * 16 : (F8 ? (size_t)a.K : (size_t)a.K * 2);
-  const unsigned char* Wb = reinterpret_cast<const unsigned char*>(F4 ? (const void*)a.W4 : (F8 ? (const void*)a.W8 : (const void*)a.W));
+  const size_t row_bytes = W13 ? w13_row_bytes(a.K) : (F4 ? (size_t)KC * 16 : (F8 ? (size_t)a.K : (size_t)a.K * 2));
+  const unsigned char* Wb = reinterpret_cast<const unsigned char*>(W13 ? (const void*)a.Wp : (F4 ? (const void*)a.W4 : (F8 ? (const void*)a.W8 : (const void*)a.W)));
+  const int J2 = W13 ? w13_units(a.K) : 0, n13 = W13 ? (int)w13_n_off(a.K) : 0, s13 = W13 ? (int)w13_s_off(a.K) : 0;   // W13: units of a row, plane offsets
   float* red = reinterpret_cast<float*>(smem + (size_t)(F4 ? f4_xrows(KC) : K8) * 16);  // WAVES floats of scratch
 #define XI(c) (F4 ? f4_xswz(c) : (c))          // where 16-byte piece c of x lies in LDS
 
@@ -124,6 +128,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
 
   const u32x4* rows[NR];
   const uint8_t* srows[NR];                    // F4: the rows' block scales
+  uint32_t lo2[NR];                            // W13: the rows' decode base, lo | lo << 16
   auto set_rows = [&](int u0) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -149,6 +154,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
         if (PAIRED) { srows[2 * j] = a.S4 + (size_t)r0 * KC; srows[2 * j + 1] = a.S4 + (size_t)r1 * KC; }
         else srows[j] = a.S4 + (size_t)r0 * KC;
       }
+      if (W13) {
+        if (PAIRED) { lo2[2 * j] = (uint32_t)w13_lo(a.Wh[r0]) * 0x10001u; lo2[2 * j + 1] = (uint32_t)w13_lo(a.Wh[r1]) * 0x10001u; }
+        else lo2[j] = (uint32_t)w13_lo(a.Wh[r0]) * 0x10001u;
+      }
     }
   };
   set_rows(unit0);
@@ -159,9 +168,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
 #define GIDX(g) (KS > 1 ? ks + KS * (g) : (g))
   u32x4 wa[NR][U], wb[NR][U];
   unsigned sa[NR][U], sb[NR][U];               // F4: the stages' block scales
+  constexpr int UW = W13 ? U : 4;              // W13: the stages' planes (the other formats leave them unused)
+  u32x4 lwa[NR][UW / 2], lwb[NR][UW / 2];
+  u32x2 nwa[NR][UW / 2], nwb[NR][UW / 2];
+  uint32_t zwa[NR][UW / 4], zwb[NR][UW / 4];
   float acc[NR];
-#define GLOAD(w, sc, g) do { if (F4) gemv_load_f4<NR, U>(w, sc, rows, srows, (g), lane, KC); else gemv_load<NR, U>(w, rows, (g), lane, KC); } while (0)
-#define GFMA(w, sc, g) do { if (F4) gemv_fma_f4<NR, U>(acc, w, sc, xs, (g), lane, KC); else if (F8) gemv_fma_f8<NR, U>(acc, w, xs, (g), lane, KC); else gemv_fma<NR, U>(acc, w, xs, (g), lane, KC); } while (0)
+#define GLOAD(w, sc, g) do { if (W13) gemv_load_w13<NR, UW>(l##w, n##w, z##w, rows, (g), lane, J2, n13, s13); else if (F4) gemv_load_f4<NR, U>(w, sc, rows, srows, (g), lane, KC); else gemv_load<NR, U>(w, rows, (g), lane, KC); } while (0)
+#define GFMA(w, sc, g) do { if (W13) gemv_fma_w13<NR, UW>(acc, l##w, n##w, z##w, lo2, xs, (g), lane, K8); else if (F4) gemv_fma_f4<NR, U>(acc, w, sc, xs, (g), lane, KC); else if (F8) gemv_fma_f8<NR, U>(acc, w, xs, (g), lane, KC); else gemv_fma<NR, U>(acc, w, xs, (g), lane, KC); } while (0)
 
   // first stage of weights goes in flight before the prologue touches x
   if (G > 0) GLOAD(wa, sa, GIDX(0));
@@ -415,9 +428,13 @@ static void launch_gemv_t(const GemvArgs& a, hipStream_t s, int blocks_per_cu) {
 
 // Tuning table: variant -> instantiation.  Variant 0 is the product default for each role; the
 // others exist for the in-situ microbenchmark (dtk_bench_gemv) that picked the default.
-#define GV(PRO, EPI, R, U, W, P, BPC) return launch_gemv_t<PRO, EPI, R, U, W, P>(a, s, BPC)
-#define GVK(PRO, EPI, R, U, W, KS) return launch_gemv_t<PRO, EPI, R, U, W, false, KS>(a, s, 0)
-void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s) {
+// The table serves two readers: launch_gemv_variant launches the row, gemv_variant_shape (q != null) only reads its shape - what decides
+// a kernel's fold order (U and KS: which k-groups a wave sums; waves: how the RMSNorm prologue folds the sum of squares) - so that
+// w13_shape_for below can never disagree with the rows here.
+struct GemvShape { int R, U, waves, ks; bool persist; };
+#define GV(PRO, EPI, R, U, W, P, BPC) do { if (q) { *q = GemvShape{R, U, W, 1, P}; return; } return launch_gemv_t<PRO, EPI, R, U, W, P>(a, s, BPC); } while (0)
+#define GVK(PRO, EPI, R, U, W, KS) do { if (q) { *q = GemvShape{R, U, W, KS, false}; return; } return launch_gemv_t<PRO, EPI, R, U, W, false, KS>(a, s, 0); } while (0)
+static void gemv_variant_row(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s, GemvShape* q) {
   if (pro == PRO_RMSNORM && epi == EPI_QKV) {
     switch (variant) {
       default: GV(PRO_RMSNORM, EPI_QKV, 1, 2, 4, false, 0);
@@ -510,6 +527,12 @@ void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipSt
 }
 #undef GV
 #undef GVK
+void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s) { gemv_variant_row(pro, epi, variant, a, s, nullptr); }
+static GemvShape gemv_variant_shape(int pro, int epi, int variant) {
+  GemvShape q{};
+  gemv_variant_row(pro, epi, variant, GemvArgs{}, nullptr, &q);
+  return q;
+}
 
 template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST = false, int BPC = 4>
 static void launch_gemv_f8_t(const GemvArgs& a, hipStream_t s) {
@@ -598,18 +621,163 @@ void launch_gemv_q4(int pro, int epi, const GemvArgs& a, hipStream_t s) {
 #undef Q4
 #undef Q4P
 
+// 13-bit planes of bf16 rows (w13.h; gemv_inl.h: dot8_w13): the four (prologue, epilogue) pairs of a layer, lm_head and the EPI_STORE
+// pairs, batch 1.  Variant 0 of a role is what a decode step runs; the others exist for dtk_bench_gemv (| 0x1000), which picked it.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST = false, int KS = 1, int BPC = 2>
+static void launch_gemv_w13_t(const GemvArgs& a, hipStream_t s) {
+  int n_units = (EPI == EPI_QKV) ? (a.N >> 1) : (EPI == EPI_SWIGLU ? a.ff : a.N);
+  const int per_block = (WAVES / KS) * R;
+  int grid = (n_units + per_block - 1) / per_block;
+  if (PERSIST && grid > num_cus() * BPC) grid = num_cus() * BPC;
+  const size_t lds = (size_t)(a.K >> 3) * 16 + 64 + 1024;   // x (bf16, linear) + per-wave RMSNorm partials + split-K partials
+  if constexpr (EPI == EPI_QKV || PRO == PRO_ATTN) {
+    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 64, false, true>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
+  }
+  hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 128, false, true>), dim3(grid), dim3(WAVES * 64), lds, s, a);
+}
+#define WV(PRO, EPI, R, U, W) return launch_gemv_w13_t<PRO, EPI, R, U, W>(a, s)
+#define WVP(PRO, EPI, R, U, W, BPC) return launch_gemv_w13_t<PRO, EPI, R, U, W, true, 1, BPC>(a, s)
+#define WVK(PRO, EPI, R, U, W, KS) return launch_gemv_w13_t<PRO, EPI, R, U, W, false, KS>(a, s)
+bool gemv_w13_has(int pro, int epi, int v) {
+  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return v >= 0 && v <= 5;
+  if (pro == PRO_COPY && epi == EPI_RESID) return v >= 0 && v <= 6;
+  if (pro == PRO_ATTN && epi == EPI_RESID) return v >= 0 && v <= 2;
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return v >= 0 && v <= 4;
+  if ((pro == PRO_RMSNORM || pro == PRO_COPY) && epi == EPI_STORE) return v == 0;
+  return false;
+}
+void launch_gemv_w13_variant(int pro, int epi, int v, const GemvArgs& a, hipStream_t s) {
+  if (pro == PRO_RMSNORM && epi == EPI_QKV) {
+    switch (v) { default: WV(PRO_RMSNORM, EPI_QKV, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_QKV, 2, 4, 4); case 2: WV(PRO_RMSNORM, EPI_QKV, 1, 4, 8);
+                 case 3: WVP(PRO_RMSNORM, EPI_QKV, 1, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_QKV, 1, 8, 4);
+                 case 5: WVP(PRO_RMSNORM, EPI_QKV, 1, 4, 4, 4); }
+  }
+  if (pro == PRO_RMSNORM && epi == EPI_SWIGLU) {
+    switch (v) { default: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_SWIGLU, 2, 4, 4); case 2: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 8);
+                 case 3: WVP(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 8, 4);
+                 case 5: WVP(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 4, 4); }
+  }
+  if (pro == PRO_COPY && epi == EPI_RESID) {
+    switch (v) { default: WV(PRO_COPY, EPI_RESID, 1, 8, 8); case 1: WV(PRO_COPY, EPI_RESID, 1, 4, 8); case 2: WV(PRO_COPY, EPI_RESID, 2, 4, 4);
+                 case 3: WVK(PRO_COPY, EPI_RESID, 1, 4, 8, 2); case 4: WVK(PRO_COPY, EPI_RESID, 2, 4, 8, 2);
+                 case 5: WV(PRO_COPY, EPI_RESID, 1, 4, 4); case 6: WV(PRO_COPY, EPI_RESID, 1, 4, 16); }
+  }
+  if (pro == PRO_ATTN && epi == EPI_RESID) {
+    switch (v) { default: WVK(PRO_ATTN, EPI_RESID, 2, 4, 16, 2); case 1: WV(PRO_ATTN, EPI_RESID, 2, 4, 8); case 2: WV(PRO_ATTN, EPI_RESID, 2, 4, 4); }
+  }
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) {
+    switch (v) { default: WV(PRO_RMSNORM, EPI_LOGITS, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_LOGITS, 2, 4, 4); case 2: WVP(PRO_RMSNORM, EPI_LOGITS, 1, 4, 8, 2);
+                 case 3: WVP(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8); }
+  }
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) WV(PRO_RMSNORM, EPI_STORE, 2, 4, 4);
+  if (pro == PRO_COPY && epi == EPI_STORE) WV(PRO_COPY, EPI_STORE, 2, 4, 4);
+  fprintf(stderr, "launch_gemv_w13: no 13-bit kernel for prologue %d, epilogue %d\n", pro, epi);   // a missing kernel is an error, never a fall-back
+  abort();
+}
+#undef WV
+#undef WVP
+#undef WVK
+// The 13-bit shape launch_gemv streams a.Wp in when the role's bf16 variant is `v`, or -1 = the bf16 rows stay.  The shape must give the
+// bf16 variant's bits, and two things of a shape enter them.  (1) The fold of a row: without split-K it is gemv_inl.h's whatever the
+// shape; a split-K variant deals k-groups of U iterations to KS waves, and only U = 4, KS = 2 has a 13-bit twin (a stage is whole sign
+// blocks: U % 4 == 0), so any other split-K choice keeps bf16.  (2) PRO_RMSNORM: the sum of squares is folded per thread, per wave and
+// over the waves, so it depends on the block's size - the 13-bit shape has the bf16 variant's number of waves (a 16-wave shape,
+// faster for q/k/v by 0.2 us, changed `inv` in the last place at K = 4096 and with it a token of the benchmark's rollout: removed).
+// Defaults by measurement among those (ds-7b, back-to-back chains over all layers' weights, us per launch, bf16 kernel -> 13-bit shape;
+// DESIGN 3.1c'', profiles/w13_ds-7b.json): q/k/v 18.20 -> 17.11 and gate/up 28.41 -> 26.14 (persistent, R 1, U 4, 4 waves, 4 blocks per
+// CU; one chunk per wave 19.3 / 27.2, R 2 18.6 / 32.9, U 8 = one stage 22.9 / 30.5); down 17.66 -> 15.46 (R 1, U 4, 8 waves; 16.10 at U 8,
+// 15.81 with 4 waves, 18.2 split-K); lm_head 37.73 -> 36.40 (R 2, U 4, 4 waves; 37.9 at R 1; the persistent 8-wave shapes reach 34.1 but
+// fold the norm differently from the 4-wave bf16 default).  o_proj (33.6 MB, latency-bound) is SLOWER on planes in every shape tried
+// (7.76 -> 8.03 at best): it keeps its bf16 rows.
+static int w13_shape_for(int pro, int epi, int v, const GemvArgs& a) {
+  const GemvShape sh = gemv_variant_shape(pro, epi, v);              // the bf16 row's own shape, from the table that launches it
+  if (pro == PRO_ATTN) return -1;                                    // o_proj
+  if (pro == PRO_COPY && epi == EPI_RESID) {
+    if (a.K == a.d) return -1;                                       // o_proj behind the combine kernel
+    if (sh.ks == 1) return 1;
+    return (sh.ks == 2 && sh.U == 4) ? 3 : -1;                       // split-K 2 over groups of 4 iterations has a twin; nothing else
+  }
+  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return sh.waves == 4 ? 5 : (sh.waves == 8 ? 3 : -1);
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return sh.waves == 4 ? 1 : (sh.waves == 8 ? 4 : -1);
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) return sh.waves == 4 ? 0 : -1;
+  if (pro == PRO_COPY && epi == EPI_STORE) return 0;
+  return -1;
+}
+
+// Packs [N][K] bf16 rows into 13-bit planes (w13.h), a block per row: hb = the row's largest e >> 1, then a thread per (sign block,
+// lane) writes its four chunks' pieces of the three planes.  A row with a weight below the window adds 1 to *bad_rows (the caller then
+// drops the matrix' packed copy; such weights are written as zero, never as another value).  W is only read.
+__global__ __launch_bounds__(256) void k_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const u32x4* w4 = reinterpret_cast<const u32x4*>(W + (size_t)row * K);
+  unsigned char* out = Wp + (size_t)row * w13_row_bytes(K);
+  __shared__ int red[4];
+  __shared__ int any_bad;
+  const int K8 = K >> 3, J2 = w13_units(K), J4 = w13_blocks(K);
+  int hb = 0;
+  for (int c = tid; c < K8; c += 256) {
+    const u32x4 v = w4[c];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) hb = max(hb, max((int)((v[e] >> 8) & 0x7fu), (int)((v[e] >> 24) & 0x7fu)));
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) hb = max(hb, __shfl_xor(hb, off));
+  if ((tid & 63) == 0) red[tid >> 6] = hb;
+  if (tid == 0) any_bad = 0;
+  __syncthreads();
+  hb = max(max(red[0], red[1]), max(red[2], red[3]));
+  if (tid == 0) Wh[row] = (uint8_t)hb;
+  const int lo = w13_lo(hb);
+  int bad = 0;
+  for (int t = tid; t < J4 * 64; t += 256) {
+    const int b = t >> 6, l = t & 63;
+    uint32_t sg = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = 2 * b + h;
+      if (j >= J2) break;
+      u32x4 lv;
+      u32x2 nv;
+#pragma unroll
+      for (int i2 = 0; i2 < 2; ++i2) {
+        const int i = 2 * h + i2, c = 256 * b + 64 * i + l;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (c < K8) v = w4[c];
+        uint32_t la = 0, lb = 0, n = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          unsigned wk = (v[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+          int code = w13_code(wk, lo);
+          if (code < 0) { ++bad; code = 0; wk = 0; }
+          const int kb = 8 * (k & 3);
+          if (k < 4) la |= (wk & 0xffu) << kb; else lb |= (wk & 0xffu) << kb;
+          n |= (uint32_t)code << (kb + 4 * (k >> 2));
+          sg |= (wk >> 15) << (kb + 2 * i + (k >> 2));
+        }
+        lv[2 * i2] = la; lv[2 * i2 + 1] = lb; nv[i2] = n;
+      }
+      reinterpret_cast<u32x4*>(out)[j * 64 + l] = lv;
+      reinterpret_cast<u32x2*>(out + w13_n_off(K))[j * 64 + l] = nv;
+    }
+    reinterpret_cast<uint32_t*>(out + w13_s_off(K))[b * 64 + l] = sg;
+  }
+  if (bad) atomicOr(&any_bad, 1);
+  __syncthreads();
+  if (tid == 0 && any_bad) atomicAdd(bad_rows, 1u);
+}
+void launch_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_w13_rows, dim3(N), dim3(256), 0, s, W, Wp, Wh, bad_rows, N, K);
+}
+
 // per-role default variant (tuned): indexed by epilogue; slot 5 = o_proj (EPI_RESID with K == d) when it has its own choice
 // (-1: same as EPI_RESID), slot 6 = o_proj with the PRO_ATTN prologue
 static int g_variant[8] = {0, 0, 0, 0, 0, -1, 0, 0};
 void set_gemv_default_variant(int epi, int variant) { if (epi >= 0 && epi < 8) g_variant[epi] = variant; }
 
-void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s) {
-  if (a.W4) return launch_gemv_q4(pro, epi, a, s);
-  if (a.W8) return launch_gemv_f8(pro, epi, a, s);
-  if (pro == PRO_ATTN) {   // 0 = not chosen: 16 rows per 16-wave block with split-K 2 (d > 2048: 387.0 tok/s vs 385.9), 8 rows per block (d <= 2048)
-    const int v = g_variant[6] ? g_variant[6] : (a.d > 2048 ? 8 : 1);
-    return launch_gemv_variant(pro, epi, v, a, s);
-  }
+// the bf16 variant of a role at this shape: the caller's (dtk_set_gemv_variant) or the measured default
+static int gemv_chosen_variant(int pro, int epi, const GemvArgs& a) {
+  // PRO_ATTN, 0 = not chosen: 16 rows per 16-wave block with split-K 2 (d > 2048: 387.0 tok/s vs 385.9), 8 rows per block (d <= 2048)
+  if (pro == PRO_ATTN) return g_variant[6] ? g_variant[6] : (a.d > 2048 ? 8 : 1);
   int v = g_variant[epi & 7];
   const bool o_proj = epi == EPI_RESID && a.K == a.d;
   if (o_proj && g_variant[5] >= 0) v = g_variant[5];
@@ -623,8 +791,20 @@ void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s) {
     if (epi == EPI_RESID) v = 10;                    // (R 1, U 8, 8 waves): o_proj 7.76 us, down 17.67; whole step 380 -> 383 tok/s
     else if (epi == EPI_LOGITS) v = 3;               // 37.9 us vs 38.9
   }
+  return v;
+}
+
+void launch_gemv(int pro, int epi, const GemvArgs& a, hipStream_t s) {
+  if (a.W4) return launch_gemv_q4(pro, epi, a, s);
+  if (a.W8) return launch_gemv_f8(pro, epi, a, s);
+  const int v = gemv_chosen_variant(pro, epi, a);
+  // a.Wp (13-bit planes of a.W): the shape that folds in the order of bf16 variant v, so the sums stay that kernel's bits; where no
+  // such shape exists the bf16 rows are streamed (gemv_w13_takes tells the packer, which then keeps no planes)
+  const int v13 = a.Wp ? w13_shape_for(pro, epi, v, a) : -1;
+  if (v13 >= 0) return launch_gemv_w13_variant(pro, epi, v13, a, s);
   launch_gemv_variant(pro, epi, v, a, s);
 }
+bool gemv_w13_takes(int pro, int epi, const GemvArgs& a) { return w13_shape_for(pro, epi, gemv_chosen_variant(pro, epi, a), a) >= 0; }
 
 // ------------------------------------------------------------------------------------------
 // Decode attention, split-K ("flash-decode"): grid (H, S).  Block (h, s) scans keys

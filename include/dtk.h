@@ -128,7 +128,9 @@ typedef struct dtk_stats {
                                      * non-zero value makes dtk_decode_batch_wait fail                          */
   uint32_t last_batch_step_fp8_mfma; /* 1: the last dtk_decode_batch_launch ran the fp8 matrix-core kernels (MXFP8 activations,
                                      * option "act_fp8"), 0: the bf16-activation kernels                        */
-  uint32_t reserved0;
+  uint32_t w13_counts;              /* bf16 contexts with option "w13": what the packer of the 13-bit weight planes found, valid once a
+                                     * single-sequence step has run: bits 0-9 matrices with planes, 10-19 matrices left as bf16 (an
+                                     * unpackable row), 20-31 unpackable rows (saturating at 4095); 0 otherwise (was reserved0)  */
 } dtk_stats;
 
 int  dtk_abi_version(void);
@@ -445,13 +447,19 @@ int  dtk_engine_set_prefill_text_op(dtk_engine* e, int (*prefill_slot_text)(void
  * epi 1), 6 = o_proj with the attention-partials prologue.  Variant 0 = the measured default of the model's width;
  * dtk_bench_gemv variant 0xff = whatever the decode step itself launches for that role (bench.py's roofline leg); 0xff | 0x800 =
  * the same on the context's weight format (fp8 rows, MXFP4 codes; without the bit the bf16 tensors are streamed); 0x800 with any
- * other variant or with the plain-probe bits fails with DTK_ERR_ARG. */
+ * other variant or with the plain-probe bits fails with DTK_ERR_ARG.  In a bf16 context with option "w13" = 1, 0xff streams what the
+ * step streams: the 13-bit planes of the roles that have them, in the step's shape (dtk_stats.probe_kernel_bytes describes role 2 of
+ * that); 0x2000 | 0xff = the bf16 rows in the step's bf16 kernel whatever "w13" says, so one process can time both; 0x1000 | shape
+ * (no other flag) = the role's planes in that 13-bit shape - o_proj, whose matrices the step keeps as bf16 rows, is packed for the
+ * call alone; DTK_ERR_STATE for a role without planes (an unpackable row, a bf16 fold order no 13-bit shape has). */
 int  dtk_bench_gemv(dtk_ctx* ctx, int role, int variant, int reps, float* avg_us);
 int  dtk_set_gemv_variant(dtk_ctx* ctx, int epi, int variant);
 /* Tuning switches; every default is the measured-best setting.  Single-sequence decode: "attn_threads" (0 =
  * contiguous key range per split | 256 | 512 | 1024 = tile-interleaved splits), "attn_splits" (1..16), "attn_combine" (0 = the
  * split partials are reduced in o_proj's prologue, 1 = by the last-arriving split block, 2 = by an own kernel),
- * "attn_full_max" (contexts below it use the one-block-per-head kernel).  Batched decode: "tail_threads" (64 | 128 | 256 | 512) and "prefix_mfma" (1: the prefix a group of <= 16 forked slots
+ * "attn_full_max" (contexts below it use the one-block-per-head kernel), "w13" (bf16 contexts: 1 = stream the 13-bit planes of the
+ * weight rows, packed lazily from the bf16 tensors, bit-identical results; 0 = the bf16 rows; drops the captured step; refused while
+ * single-sequence steps are unread).  Batched decode: "tail_threads" (64 | 128 | 256 | 512) and "prefix_mfma" (1: the prefix a group of <= 16 forked slots
  * shares — same source slot, same length — is scored once for the group on the matrix cores by k_attn_prefix_g, the slots' private
  * keys per slot; 0 = every slot walks its whole context) default by the CONTEXT's size: 128 / 1 with 64 decoding slots, 256 / 0 below;
  * "pfx_splits" (1..4 key splits of that kernel, default 4), "gemv_bus" (64-slot qkv / gate-up by k_gemv_bus — a block per CU whose 8
@@ -611,6 +619,18 @@ int  dtk_op_gemv_role(dtk_ctx* ctx, int pro, int epi, int variant, const uint16_
                       const uint16_t* x, const uint16_t* norm_w, const uint16_t* rope_cos, const uint16_t* rope_sin,
                       int S, const float* pm, const float* pl, const float* po, int scratch_fill,
                       uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, float* logits_io);
+/* 13-bit planes of bf16 weight rows (csrc/w13.h; additive, ABI 7): the single-sequence step of a bf16 context streams them instead of the
+ * 16-bit rows when dtk_set_option(ctx, "w13", 1); the kernels rebuild the rows' own bits, so every result is the bf16 step's.  A row
+ * holding a weight more than 30 binades below its largest cannot be packed; its whole matrix then stays bf16 (dtk_stats.w13_counts).
+ * dtk_op_gemv_role with bf16 operands and variant = 0x1000 + v packs W on the device and runs the role on the planes in 13-bit shape v
+ * (0xff: the shape a step runs; DTK_ERR_ARG for a shape that does not exist); if a row is unpackable the bf16 kernel runs instead.
+ * dtk_w13_op_bad_rows: the unpackable rows that call found (-1 before any).  dtk_w13_pack_host / dtk_w13_unpack_host: w13.h's host code
+ * on rows [N][K] (K % 8 == 0), planes [N][dtk_w13_row_bytes(K)], hb [N]; bad[r] = weights of row r below its window (0: packed exactly;
+ * otherwise the row must not be used).  No GPU needed. */
+int  dtk_w13_row_bytes(int K);
+int  dtk_w13_pack_host(const uint16_t* W, int N, int K, uint8_t* planes, uint8_t* hb, int32_t* bad);
+int  dtk_w13_unpack_host(const uint8_t* planes, const uint8_t* hb, int N, int K, uint16_t* W);
+int  dtk_w13_op_bad_rows(dtk_ctx* ctx);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */
