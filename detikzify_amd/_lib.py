@@ -211,6 +211,12 @@ SYMBOLS = {
     # additive (ABI stays 7): one role of the single-sequence decode GEMV family (prologue, epilogue, variant, weight format)
     "dtk_op_gemv_role": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [C.c_float, _P, _P, _P, _P,
                                    C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    # additive (ABI stays 7): the prefill's row kernels and attention layouts alone
+    "dtk_op_rope_scatter": (C.c_int, [_P, C.c_int, _P, _P] + [C.c_int] * 8 + [_P, C.c_int, _P, _P, C.c_int, _P, _P, _P]),
+    "dtk_op_rows_norm": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P, _P]),
+    "dtk_op_swiglu": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "dtk_op_attention_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int] * 9),
+    "dtk_op_rows_move": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 8 + [_P]),
     # additive (ABI stays 7): 13-bit planes of bf16 weight rows (csrc/w13.h): the host packer for the CPU tests, the op's packing outcome
     "dtk_w13_row_bytes": (C.c_int, [C.c_int]),
     "dtk_w13_pack_host": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),

@@ -4061,6 +4061,258 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   return DTK_OK;
 }
 
+// ---- the prefill's row kernels and attention layouts alone (dtk_op_rope_scatter / _rows_norm / _swiglu / _attention_ex / _rows_move):
+// host operands into the op scratch as dtk_op_gemv_role does it — the whole scratch the op uses is filled with scratch_fill first, every
+// result buffer is in/out with 256 guard bytes behind it that must still hold scratch_fill after the launch, and everything the prefill
+// would never hand a kernel is refused before anything is uploaded.
+extern "C++" {
+namespace {
+struct OpRun {
+  static constexpr size_t GUARD = 256;
+  dtk_ctx* c; const char* who; int fill; size_t off = 0; bool full = false;
+  struct In { void* dev; const void* host; size_t bytes; };
+  struct Io { void* dev; void* host; size_t bytes; const char* name; };
+  std::vector<In> ins; std::vector<Io> ios;
+  OpRun(dtk_ctx* c_, const char* who_, int fill_) : c(c_), who(who_), fill(fill_) {}
+  void* take(size_t bytes) {
+    off = align_up(off, 256);
+    if (off + bytes + 256 > c->scratch_bytes) { full = true; return c->scratch; }
+    void* p = c->scratch + off; off += bytes; return p;
+  }
+  template <class T> T* in(const void* host, size_t n) { T* p = (T*)take(n * sizeof(T)); if (host && n) ins.push_back({p, host, n * sizeof(T)}); return p; }
+  template <class T> T* io(void* host, size_t n, const char* name) { T* p = (T*)take(n * sizeof(T) + GUARD); if (host) ios.push_back({p, host, n * sizeof(T), name}); return p; }
+  int upload(hipStream_t s) {     // the caller's poison over everything between and behind the operands, then the operands
+    if (full) return fail(c, DTK_ERR_ARG, "%s: op scratch exhausted (%zu of %zu bytes)", who, off, c->scratch_bytes);
+    off = align_up(off, 256);
+    HIPCHK(c, hipMemsetAsync(c->scratch, fill, off + 256, s));
+    for (const In& i : ins) HIPCHK(c, hipMemcpyAsync(i.dev, i.host, i.bytes, hipMemcpyHostToDevice, s));
+    for (const Io& i : ios) HIPCHK(c, hipMemcpyAsync(i.dev, i.host, i.bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return DTK_OK;
+  }
+  int finish(hipStream_t s) {     // nothing behind the end of a result buffer was written; then the results go back
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    unsigned char guard[GUARD];
+    for (const Io& i : ios) {
+      HIPCHK(c, hipMemcpy(guard, (unsigned char*)i.dev + i.bytes, GUARD, hipMemcpyDeviceToHost));
+      for (size_t j = 0; j < GUARD; ++j)
+        if (guard[j] != (unsigned char)fill) return fail(c, DTK_ERR_STATE, "%s: byte %zu behind the end of %s was written", who, j, i.name);
+    }
+    for (const Io& i : ios) HIPCHK(c, hipMemcpy(i.host, i.dev, i.bytes, hipMemcpyDeviceToHost));
+    return DTK_OK;
+  }
+};
+}  // namespace
+}  // extern "C++"
+
+int dtk_op_rope_scatter(dtk_ctx* c, int form, const uint16_t* QKV, const float* part, int S, int part_rows, int T, int H, int KVH, int hd,
+                        int T_max, int start_pos, const int32_t* rows, int max_pos, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                        int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io) {
+  const char* who = "dtk_op_rope_scatter";
+  if (!c || !rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
+  if (form != 0 && form != 1) return fail(c, DTK_ERR_ARG, "%s: form %d (0 bf16 rows, 1 fp32 K-slice partials)", who, form);
+  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "%s: head dim %d (128 or 64)", who, hd);
+  if (T < 1 || H < 1 || KVH < 1 || H % KVH || T_max < 1 || max_pos < 1) return fail(c, DTK_ERR_ARG, "%s: T %d, H %d query heads over KVH %d key / value heads, T_max %d", who, T, H, KVH, T_max);
+  if (scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: scratch_fill is a byte", who);
+  if (form == 0 && !QKV) return fail(c, DTK_ERR_ARG, "%s: form 0 needs QKV", who);
+  if (form == 1 && (!part || S < 1 || S > 8 || part_rows < T)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs partials of S = 1..8 slices and part_rows >= T", who);
+  for (int t = 0; t < T; ++t) {
+    const int pos = rows ? rows[2 * t] : start_pos + t, row = rows ? rows[2 * t + 1] : start_pos + t;
+    if (pos < 0 || pos >= max_pos || row < 0 || row >= T_max)
+      return fail(c, DTK_ERR_ARG, "%s: row %d: position %d of %d, cache row %d of %d", who, t, pos, max_pos, row, T_max);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t qkvn = (size_t)(H + 2 * KVH) * hd, kv = (size_t)KVH * T_max * hd;
+  OpRun r(c, who, scratch_fill);
+  const bf16_t* dQKV = r.in<bf16_t>(form == 0 ? QKV : nullptr, form == 0 ? (size_t)T * qkvn : 0);
+  const float* dP = r.in<float>(form == 1 ? part : nullptr, form == 1 ? (size_t)S * part_rows * qkvn : 0);
+  const bf16_t* dcos = r.in<bf16_t>(rope_cos, (size_t)max_pos * (hd / 2));
+  const bf16_t* dsin = r.in<bf16_t>(rope_sin, (size_t)max_pos * (hd / 2));
+  const int2* dR = r.in<int2>(rows, rows ? (size_t)T : 0);
+  bf16_t* dq = r.io<bf16_t>(q_io, (size_t)H * T * hd, "q"); bf16_t* dk = r.io<bf16_t>(k_io, kv, "k"); bf16_t* dv = r.io<bf16_t>(v_io, kv, "v");
+  if (const int rc = r.upload(s)) return rc;
+  const long ps = (long)part_rows * (long)qkvn;
+  if (form == 0 && rows) launch_rope_scatter_rows(dQKV, dq, dk, dv, dcos, dsin, T, dR, H, KVH, T_max, s, hd);
+  else if (form == 0) launch_rope_scatter(dQKV, dq, dk, dv, dcos, dsin, T, start_pos, H, KVH, T_max, s, hd);
+  else if (rows) launch_sk_rope_scatter_rows(dP, ps, S, dq, dk, dv, dcos, dsin, T, dR, H, KVH, T_max, s, hd);
+  else launch_sk_rope_scatter(dP, ps, S, dq, dk, dv, dcos, dsin, T, start_pos, H, KVH, T_max, s, hd);
+  return r.finish(s);
+}
+
+int dtk_op_rows_norm(dtk_ctx* c, int form, const uint16_t* X, const float* part, int S, int part_rows, const uint16_t* norm_w,
+                     const uint16_t* ln_b, const uint16_t* bias, const uint16_t* residual, const uint16_t* gate, int flags, int M, int N,
+                     int ldx, int ldc, int ldr, int ldy, float eps, int scratch_fill, uint16_t* c_io, uint16_t* y_io) {
+  const char* who = "dtk_op_rows_norm";
+  if (!c) return DTK_ERR_ARG;
+  if (form < 0 || form > 3) return fail(c, DTK_ERR_ARG, "%s: form %d (0 rmsnorm_rows, 1 rmsnorm_rows_sk, 2 sk_reduce, 3 layernorm_rows)", who, form);
+  if (M < 1 || N < 1 || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: M, N >= 1, scratch_fill a byte", who);
+  const bool in_place = form == 3 && !X;              // Y == X (the cross layer's q_norm)
+  if (form != 2) {
+    if (!y_io || !norm_w || (!X && !in_place) || (form == 3 && !ln_b)) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
+    if (in_place) ldx = ldy;
+    if (ldx < N || ldy < N) return fail(c, DTK_ERR_ARG, "%s: ldx %d / ldy %d below the row length %d", who, ldx, ldy, N);
+    if ((form == 0 || form == 3) && ((N % 8) || (ldx % 8) || (ldy % 8))) return fail(c, DTK_ERR_ARG, "%s: form %d reads and writes 16-byte chunks: D, ldx, ldy multiples of 8", who, form);
+    if (form == 1 && (N % 4)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs N %% 4 == 0", who);
+  } else {
+    const int known = DTK_EPI_BIAS | DTK_EPI_RESIDUAL | DTK_EPI_GATED_RESIDUAL;
+    if (!part || !c_io || (norm_w && !y_io) || (flags & ~known)) return fail(c, DTK_ERR_ARG, "%s: form 2 needs partials and C (and Y with norm_w); flags: bias, residual, gated residual", who);
+    if ((N % 4) || S < 1 || S > 8 || part_rows < M) return fail(c, DTK_ERR_ARG, "%s: form 2 needs N %% 4 == 0, S = 1..8 and part_rows >= M", who);
+    if (((flags & DTK_EPI_BIAS) && !bias) || ((flags & DTK_EPI_RESIDUAL) && (!residual || ldr < N)) ||
+        ((flags & DTK_EPI_GATED_RESIDUAL) && (!gate || !(flags & DTK_EPI_RESIDUAL))))
+      return fail(c, DTK_ERR_ARG, "%s: a flag without its operand (the gated residual needs the residual too)", who);
+    if (ldc < N || (norm_w && ldy < N)) return fail(c, DTK_ERR_ARG, "%s: ldc / ldy below N", who);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, who, scratch_fill);
+  if (form != 2) {
+    const bf16_t* dX = in_place ? nullptr : r.in<bf16_t>(X, (size_t)M * ldx);
+    const bf16_t* dw = r.in<bf16_t>(norm_w, N);
+    const bf16_t* db = r.in<bf16_t>(form == 3 ? ln_b : nullptr, form == 3 ? N : 0);
+    bf16_t* dY = r.io<bf16_t>(y_io, (size_t)M * ldy, "y");
+    if (in_place) dX = dY;
+    if (const int rc = r.upload(s)) return rc;
+    if (form == 0) launch_rmsnorm_rows(dX, ldx, dw, dY, ldy, M, N, eps, s);
+    else if (form == 1) launch_rmsnorm_rows_sk(dX, ldx, dw, dY, ldy, M, N, eps, s);
+    else launch_layernorm_rows(dX, ldx, dw, db, dY, ldy, M, N, eps, s);
+    return r.finish(s);
+  }
+  GemmArgs g;
+  g.A = nullptr; g.lda = 0; g.W = nullptr; g.ldw = 0; g.M = M; g.N = N; g.K = 0; g.kslices = S;
+  g.part = r.in<float>(part, (size_t)S * part_rows * N); g.part_stride = (long)part_rows * N;
+  g.bias = r.in<bf16_t>((flags & DTK_EPI_BIAS) ? bias : nullptr, (flags & DTK_EPI_BIAS) ? N : 0);
+  g.residual = r.in<bf16_t>((flags & DTK_EPI_RESIDUAL) ? residual : nullptr, (flags & DTK_EPI_RESIDUAL) ? (size_t)M * ldr : 0); g.ldr = ldr;
+  g.gate = r.in<bf16_t>((flags & DTK_EPI_GATED_RESIDUAL) ? gate : nullptr, (flags & DTK_EPI_GATED_RESIDUAL) ? 1 : 0);
+  const bf16_t* dw = r.in<bf16_t>(norm_w, norm_w ? N : 0);
+  g.C = r.io<bf16_t>(c_io, (size_t)M * ldc, "c"); g.ldc = ldc;
+  bf16_t* dY = r.io<bf16_t>(norm_w ? y_io : nullptr, norm_w ? (size_t)M * ldy : 0, "y");
+  g.flags = ((flags & DTK_EPI_BIAS) ? GEMM_BIAS : 0) | ((flags & DTK_EPI_RESIDUAL) ? GEMM_RESIDUAL : 0) | ((flags & DTK_EPI_GATED_RESIDUAL) ? GEMM_GATED_RESIDUAL : 0);
+  if (const int rc = r.upload(s)) return rc;
+  launch_sk_reduce(g, norm_w ? dw : nullptr, dY, ldy, eps, s);
+  return r.finish(s);
+}
+
+int dtk_op_swiglu(dtk_ctx* c, int form, const uint16_t* GU, const float* part, int S, int part_rows, const uint16_t* A, const uint16_t* W,
+                  int M, int ff, int K, int ldact, int scratch_fill, uint16_t* act_io) {
+  const char* who = "dtk_op_swiglu";
+  if (!c) return DTK_ERR_ARG;
+  if (form < 0 || form > 2) return fail(c, DTK_ERR_ARG, "%s: form %d (0 silu_mul, 1 sk_reduce_swiglu, 2 the GEMM epilogue)", who, form);
+  if (!act_io || M < 1 || ff < 1 || ldact < ff || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: act, M, ff >= 1, ldact >= ff, scratch_fill a byte", who);
+  if (form == 0 && (!GU || (ff % 8) || ldact != ff)) return fail(c, DTK_ERR_ARG, "%s: form 0 needs GU, ff %% 8 == 0 (as dtk_create) and ldact == ff", who);
+  if (form == 1 && (!part || S < 1 || S > 8 || (ff % 4) || (ldact % 4) || part_rows < M)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs partials of S = 1..8 slices, ff %% 4 == 0, ldact %% 4 == 0, part_rows >= M", who);
+  if (form == 2 && (!A || !W || K < 8 || (K % 8))) return fail(c, DTK_ERR_ARG, "%s: form 2 needs A, W and K %% 8 == 0", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, who, scratch_fill);
+  if (form == 0) {
+    const bf16_t* dGU = r.in<bf16_t>(GU, (size_t)M * 2 * ff);
+    bf16_t* dA = r.io<bf16_t>(act_io, (size_t)M * ff, "act");
+    if (const int rc = r.upload(s)) return rc;
+    launch_silu_mul(dGU, ff, dA, M, s);
+    return r.finish(s);
+  }
+  GemmArgs g;
+  g.M = M; g.N = 2 * ff; g.K = K; g.flags = 0; g.bias = nullptr; g.residual = nullptr; g.ldr = 0;
+  if (form == 1) {
+    g.A = nullptr; g.lda = 0; g.W = nullptr; g.ldw = 0; g.C = nullptr; g.ldc = 0; g.kslices = S;
+    g.part = r.in<float>(part, (size_t)S * part_rows * 2 * ff); g.part_stride = (long)part_rows * 2 * ff;
+    bf16_t* dA = r.io<bf16_t>(act_io, (size_t)M * ldact, "act");
+    if (const int rc = r.upload(s)) return rc;
+    launch_sk_reduce_swiglu(g, dA, ldact, s);
+    return r.finish(s);
+  }
+  g.A = r.in<bf16_t>(A, (size_t)M * K); g.lda = K;
+  g.W = r.in<bf16_t>(W, (size_t)2 * ff * K); g.ldw = K;
+  bf16_t* dWt = (bf16_t*)r.take(tiled_elems(2 * ff, K) * sizeof(bf16_t));
+  g.Wt = dWt;
+  g.C = r.io<bf16_t>(act_io, (size_t)M * ldact, "act"); g.ldc = ldact;
+  if (r.full) return fail(c, DTK_ERR_ARG, "%s: op scratch exhausted", who);
+  // the launcher's own refusals, asked before anything is uploaded: a dry call is not possible (it launches), so its conditions are restated
+  if (K < 128 || ((2 * ff) & 31) || (ldact & 3)) return fail(c, DTK_ERR_ARG, "%s: k_gemm_g3's SwiGLU epilogue needs K >= 128, ff %% 16 == 0 and ldact %% 4 == 0", who);
+  if (const int rc = r.upload(s)) return rc;
+  launch_retile_pairs(g.W, dWt, ff, K, s);
+  if (!launch_gemm_g3_swiglu(g, s)) {
+    (void)hipStreamSynchronize(s);
+    return fail(c, DTK_ERR_ARG, "%s: launch_gemm_g3_swiglu does not take this shape (\"gemm_g3_min_blocks\", \"gemm_wt\")", who);
+  }
+  return r.finish(s);
+}
+
+int dtk_op_attention_ex(dtk_ctx* c, const uint16_t* Q, int64_t nq, const uint16_t* K, int64_t nk, const uint16_t* V, int64_t nv,
+                        uint16_t* o_io, int64_t no, const int64_t* strides, int H, int kv_group, int Tq, int Tk, int hd, int causal,
+                        int q_offset, int nbatch, int scratch_fill) {
+  const char* who = "dtk_op_attention_ex";
+  if (!c || !Q || !K || !V || !o_io || !strides) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
+  if (hd != 72 && hd != 128 && hd != 64 && hd != 32) return fail(c, DTK_ERR_ARG, "%s: unsupported head dim %d", who, hd);
+  if (H < 1 || Tq < 1 || Tk < 1 || nbatch < 1 || kv_group < 1 || H % kv_group || q_offset < 0 || scratch_fill < 0 || scratch_fill > 255)
+    return fail(c, DTK_ERR_ARG, "%s: bad shape (H %d, kv_group %d, Tq %d, Tk %d, nbatch %d, q_offset %d)", who, H, kv_group, Tq, Tk, nbatch, q_offset);
+  // strides = {q_sh, q_st, q_sb, k_sh, k_st, k_sb, v_sh, v_st, v_sb, o_sh, o_st, o_sb}, in elements
+  const int64_t n[4] = {nq, nk, nv, no};
+  const int heads[4] = {H, H / kv_group, H / kv_group, H}, toks[4] = {Tq, Tk, Tk, Tq};
+  for (int i = 0; i < 4; ++i) {
+    const int64_t sh = strides[3 * i], st = strides[3 * i + 1], sb = strides[3 * i + 2];
+    if (sh < 0 || st < 0 || sb < 0 || n[i] < 1 || (sh | st | sb) >> 40) return fail(c, DTK_ERR_ARG, "%s: negative or absurd stride / size of operand %d", who, i);
+    const int64_t last = (int64_t)(nbatch - 1) * sb + (int64_t)(heads[i] - 1) * sh + (int64_t)(toks[i] - 1) * st + hd;
+    if (last > n[i]) return fail(c, DTK_ERR_ARG, "%s: the strides of %s address element %lld of %lld", who, i == 0 ? "Q" : (i == 1 ? "K" : (i == 2 ? "V" : "O")), (long long)last, (long long)n[i]);
+    if ((sh | st | sb) & 1) return fail(c, DTK_ERR_ARG, "%s: odd stride (the kernels read and write bf16 pairs)", who);
+  }
+  AttnArgs a;
+  a.q_sh = (long)strides[0]; a.q_st = (long)strides[1]; a.q_sb = (long)strides[2];
+  a.k_sh = (long)strides[3]; a.k_st = (long)strides[4]; a.k_sb = (long)strides[5];
+  a.v_sh = (long)strides[6]; a.v_st = (long)strides[7]; a.v_sb = (long)strides[8];
+  a.o_sh = (long)strides[9]; a.o_st = (long)strides[10]; a.o_sb = (long)strides[11];
+  a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal ? 1 : 0; a.q_offset = q_offset;
+  a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = kv_group; a.nbatch = nbatch;
+  if (c->attn_impl == 2 && (!attention_mfma_operands(a) || (a.q_sb % 8) || (a.k_sb % 8) || (a.v_sb % 8) || (a.o_sb % 4)))
+    return fail(c, DTK_ERR_ARG, "%s: attn_impl = 2 and the MFMA kernel does not take these operands (hd 128 / 72 / 64, Q / K / V strides %% 8, O strides %% 4)", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, who, scratch_fill);
+  a.Q = r.in<bf16_t>(Q, (size_t)nq); a.K = r.in<bf16_t>(K, (size_t)nk); a.V = r.in<bf16_t>(V, (size_t)nv);
+  a.O = r.io<bf16_t>(o_io, (size_t)no, "o");
+  if (const int rc = r.upload(s)) return rc;
+  launch_attention(a, s);
+  return r.finish(s);
+}
+
+int dtk_op_rows_move(dtk_ctx* c, int form, const int32_t* ids, const uint16_t* src, const float* pixels, int M, int D, int V, int lds,
+                     int ldd, int image, int patch, int scratch_fill, uint16_t* dst_io) {
+  const char* who = "dtk_op_rows_move";
+  if (!c) return DTK_ERR_ARG;
+  if (form < 0 || form > 2) return fail(c, DTK_ERR_ARG, "%s: form %d (0 embed_gather, 1 copy_rows, 2 im2col)", who, form);
+  if (!dst_io || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: dst, scratch_fill a byte", who);
+  if (form == 0) {
+    if (!ids || !src || M < 1 || V < 1 || D < 8 || (D % 8)) return fail(c, DTK_ERR_ARG, "%s: form 0 needs ids, the table, d %% 8 == 0", who);
+    for (int t = 0; t < M; ++t) if (ids[t] < 0 || ids[t] >= V) return fail(c, DTK_ERR_ARG, "%s: id %d of row %d outside [0, %d)", who, ids[t], t, V);
+  } else if (form == 1) {
+    if (!src || M < 1 || D < 8 || (D % 8) || lds < D || ldd < D || (lds % 8) || (ldd % 8)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs src, D, lds, ldd multiples of 8, lds / ldd >= D", who);
+  } else if (!pixels || patch < 1 || image < patch || ldd < 3 * patch * patch) return fail(c, DTK_ERR_ARG, "%s: form 2 needs pixels, image >= patch >= 1, ldp >= 3 patch^2", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, who, scratch_fill);
+  if (form == 0) {
+    const int32_t* di = r.in<int32_t>(ids, M); const bf16_t* de = r.in<bf16_t>(src, (size_t)V * D);
+    bf16_t* dX = r.io<bf16_t>(dst_io, (size_t)M * D, "x");
+    if (const int rc = r.upload(s)) return rc;
+    launch_embed_gather(di, de, dX, M, D, s);
+  } else if (form == 1) {
+    const bf16_t* ds = r.in<bf16_t>(src, (size_t)M * lds);
+    bf16_t* dd = r.io<bf16_t>(dst_io, (size_t)M * ldd, "dst");
+    if (const int rc = r.upload(s)) return rc;
+    launch_copy_rows(ds, lds, dd, ldd, M, D, s);
+  } else {
+    const int np = image / patch;
+    const float* dp = r.in<float>(pixels, (size_t)3 * image * image);
+    bf16_t* dd = r.io<bf16_t>(dst_io, (size_t)np * np * ldd, "patches");
+    if (const int rc = r.upload(s)) return rc;
+    launch_im2col(dp, dd, image, patch, ldd, s);
+  }
+  return r.finish(s);
+}
+
 // ---- w13.h's host code for the CPU tests: rows [N][K] bf16 <-> planes [N][dtk_w13_row_bytes(K)] + hb[N]; bad[N] = weights below the
 // row's window (0 = the row is packed exactly)
 int dtk_w13_row_bytes(int K) { return (K < 8 || (K & 7)) ? -1 : (int)w13_row_bytes(K); }

@@ -369,6 +369,8 @@ struct AttnArgs {
   long q_sb = 0, k_sb = 0, v_sb = 0, o_sb = 0;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
+// the MFMA flash kernel takes these operands (head dim and stride alignment); otherwise launch_attention runs the VALU kernel whatever a.impl says
+bool attention_mfma_operands(const AttnArgs& a);
 // Segmented causal attention of the packed scoring pass: the keys are cache rows [0, a.Tk); rows [0, shared_len) are the prompt every
 // query sees, the rest are the candidates' segments.  Query row t (rows[t] = {its segment's first cache row, its own cache row}) sees key
 // j iff j <= rows[t].y and (j < shared_len or j >= rows[t].x); a prompt row has begin 0.  a.causal / a.q_offset are not read.  The MFMA

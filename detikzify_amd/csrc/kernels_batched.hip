@@ -553,7 +553,13 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
       u32x4 v = {0u, 0u, 0u, 0u};
       if (k < K) {
         if (isA) { int am = m0 + row; if (am >= a.M) am = a.M - 1; v = *reinterpret_cast<const u32x4*>(a.A + (size_t)am * a.lda + k); }
-        else { int wn = n0 + row; if (wn >= a.N) wn = a.N - 1; v = *reinterpret_cast<const u32x4*>(a.W + (size_t)wn * a.ldw + k); }
+        else {
+          int wn = n0 + row;
+          // GEMM_SWIGLU: the stage holds launch_retile_pairs' order (tile 2 q = gate rows 16 q .., tile 2 q + 1 = up rows ff + 16 q ..); a.W is row-major
+          if (!SK && WT && !SL && !LS && (a.flags & GEMM_SWIGLU)) wn =(((wn >> 4) & 1) ? (a.N >> 1) : 0) + (wn >> 5) * 16 + (wn & 15);
+          if (wn >= a.N) wn = a.N - 1;
+          v = *reinterpret_cast<const u32x4*>(a.W + (size_t)wn * a.ldw + k);
+        }
       }
       if (WT && !isA) *reinterpret_cast<u32x4*>(st + OPA + (unsigned)((row >> 4) * 2 + (chunk >> 2)) * 1024u + (unsigned)((chunk & 3) * 16 + (row & 15)) * 16u) = v;
       else *reinterpret_cast<u32x4*>(st + (isA ? 0u : OPA) + (unsigned)row * 128u + (unsigned)pos * 16u) = v;
@@ -1985,7 +1991,7 @@ __global__ __launch_bounds__(256) void k_attention_mfma_seg(AttnArgs a, int shar
   }
 }
 
-static bool attention_mfma_operands(const AttnArgs& a) {
+bool attention_mfma_operands(const AttnArgs& a) {
   return (a.hd == 64 || a.hd == 72 || a.hd == 128) && (a.q_st % 8 == 0) && (a.k_st % 8 == 0) && (a.v_st % 8 == 0) &&
          (a.o_st % 4 == 0) && (a.q_sh % 8 == 0) && (a.k_sh % 8 == 0) && (a.v_sh % 8 == 0) && (a.o_sh % 4 == 0);
 }

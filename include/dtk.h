@@ -619,6 +619,40 @@ int  dtk_op_gemv_role(dtk_ctx* ctx, int pro, int epi, int variant, const uint16_
                       const uint16_t* x, const uint16_t* norm_w, const uint16_t* rope_cos, const uint16_t* rope_sin,
                       int S, const float* pm, const float* pl, const float* po, int scratch_fill,
                       uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, float* logits_io);
+/* The prefill's row kernels and attention layouts alone (additive, ABI 7); bf16 bits throughout, every operand from the host.  As in
+ * dtk_op_gemv_role the result buffers (*_io) are IN/OUT, scratch_fill is the byte the op's device scratch holds around the operands, a
+ * write behind the end of a result buffer (256 guard bytes each) is DTK_ERR_STATE, and what the prefill would never hand a kernel is
+ * DTK_ERR_ARG with nothing launched and no buffer touched.
+ * dtk_op_rope_scatter: form 0 = launch_rope_scatter on QKV [T][(H + 2 KVH) hd]; form 1 = launch_sk_rope_scatter on fp32 partials
+ *   part [S][part_rows][(H + 2 KVH) hd] (S = 1..8, part_rows >= T).  rows = NULL: row t at position and cache row start_pos + t; else
+ *   rows [T][2] = {position, cache row} (the _rows launchers).  rope_cos / rope_sin [max_pos][hd / 2].  q_io [H][T][hd], k_io / v_io
+ *   [KVH][T_max][hd].  hd 128 | 64, H % KVH == 0, positions < max_pos, cache rows < T_max.
+ * dtk_op_rows_norm: form 0 launch_rmsnorm_rows, 1 launch_rmsnorm_rows_sk, 3 launch_layernorm_rows (norm_w, ln_b; X = NULL: in place on
+ *   y_io, ldx = ldy): X [M][ldx] -> y_io [M][ldy], N = the row length (N % 8 for forms 0 / 3, N % 4 for form 1).  form 2 = launch_sk_reduce
+ *   on part [S][part_rows][N] (N % 4 == 0): flags DTK_EPI_BIAS | DTK_EPI_RESIDUAL | DTK_EPI_GATED_RESIDUAL with bias [N], residual [M][ldr],
+ *   gate [1]; c_io [M][ldc]; norm_w [N] (optional) -> y_io [M][ldy], the fused RMSNorm.
+ * dtk_op_swiglu: form 0 launch_silu_mul on GU [M][2 ff] (ldact == ff); form 1 launch_sk_reduce_swiglu on part [S][part_rows][2 ff]
+ *   (ff % 4 == 0); form 2 A [M][K], W [2 ff][K] (gate rows, then up rows): launch_retile_pairs + launch_gemm_g3_swiglu, DTK_ERR_ARG where
+ *   that launcher declines (see "gemm_g3_min_blocks").  act_io [M][ldact].
+ * dtk_op_attention_ex: launch_attention on raw buffers of nq / nk / nv / no elements; strides [12] = {q_sh, q_st, q_sb, k_sh, k_st, k_sb,
+ *   v_sh, v_st, v_sb, o_sh, o_st, o_sb} (head, token, batch; elements).  Query head h reads K / V head h / kv_group.  Strides that address
+ *   outside a buffer are refused, and under "attn_impl" 2 so are operands the MFMA kernel does not take (no silent VALU fallback).
+ * dtk_op_rows_move: form 0 launch_embed_gather (ids [M] in [0, V), src = table [V][D]) -> dst_io [M][D]; form 1 launch_copy_rows
+ *   src [M][lds] -> dst_io [M][ldd]; form 2 launch_im2col pixels fp32 [3][image][image] -> dst_io [(image / patch)^2][ldd]. */
+#define DTK_EPI_GATED_RESIDUAL 8   /* dtk_op_rows_norm form 2, with DTK_EPI_RESIDUAL: residual + bf16(bf16(sigmoid(gate)) * bf16(sum + bias)) */
+int  dtk_op_rope_scatter(dtk_ctx* ctx, int form, const uint16_t* QKV, const float* part, int S, int part_rows, int T, int H, int KVH, int hd,
+                         int T_max, int start_pos, const int32_t* rows, int max_pos, const uint16_t* rope_cos, const uint16_t* rope_sin,
+                         int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io);
+int  dtk_op_rows_norm(dtk_ctx* ctx, int form, const uint16_t* X, const float* part, int S, int part_rows, const uint16_t* norm_w,
+                      const uint16_t* ln_b, const uint16_t* bias, const uint16_t* residual, const uint16_t* gate, int flags, int M, int N,
+                      int ldx, int ldc, int ldr, int ldy, float eps, int scratch_fill, uint16_t* c_io, uint16_t* y_io);
+int  dtk_op_swiglu(dtk_ctx* ctx, int form, const uint16_t* GU, const float* part, int S, int part_rows, const uint16_t* A, const uint16_t* W,
+                   int M, int ff, int K, int ldact, int scratch_fill, uint16_t* act_io);
+int  dtk_op_attention_ex(dtk_ctx* ctx, const uint16_t* Q, int64_t nq, const uint16_t* K, int64_t nk, const uint16_t* V, int64_t nv,
+                         uint16_t* o_io, int64_t no, const int64_t* strides, int H, int kv_group, int Tq, int Tk, int hd, int causal,
+                         int q_offset, int nbatch, int scratch_fill);
+int  dtk_op_rows_move(dtk_ctx* ctx, int form, const int32_t* ids, const uint16_t* src, const float* pixels, int M, int D, int V, int lds,
+                      int ldd, int image, int patch, int scratch_fill, uint16_t* dst_io);
 /* 13-bit planes of bf16 weight rows (csrc/w13.h; additive, ABI 7): the single-sequence step of a bf16 context streams them instead of the
  * 16-bit rows when dtk_set_option(ctx, "w13", 1); the kernels rebuild the rows' own bits, so every result is the bf16 step's.  A row
  * holding a weight more than 30 binades below its largest cannot be packed; its whole matrix then stays bf16 (dtk_stats.w13_counts).
