@@ -61,6 +61,16 @@ class DtkSamplingExt(C.Structure):
     _fields_ = [("min_p", C.c_float), ("epsilon_cutoff", C.c_float), ("reserved", C.c_int32 * 6)]
 
 
+DTK_DRY_MAX_MATCH = 64
+DTK_DRY_MAX_BREAKERS = 16
+
+
+class DtkDry(C.Structure):
+    """dtk_dry: DRY of one sequence, set after dtk_set_sampling[_slot] (which resets it to off); multiplier 0 = off"""
+    _fields_ = [("multiplier", C.c_float), ("base", C.c_float), ("allowed_length", C.c_int32), ("start", C.c_int32),
+                ("n_breakers", C.c_int32), ("breakers", C.c_int32 * DTK_DRY_MAX_BREAKERS)]
+
+
 class DtkStats(C.Structure):
     _fields_ = [
         ("weight_bytes_per_token", C.c_uint64), ("kv_bytes_per_ctx_token", C.c_uint64),
@@ -114,6 +124,8 @@ class DtkEngineOps(C.Structure):
     SAMPLING_EXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkSamplingExt))
     # not a field: dtk_engine_set_penalties_op's argument (dev, slot, presence, frequency, start)
     PENALTIES = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int)
+    # not a field: dtk_engine_set_dry_op's argument (dev, slot, dry)
+    DRY = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkDry))
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -265,6 +277,18 @@ SYMBOLS = {
     "dtk_engine_submit_pen": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int,
                                         C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dtk_engine_set_penalties_op": (C.c_int, [_P, DtkEngineOps.PENALTIES]),
+    # additive (ABI stays 7): DRY, the penalty on verbatim repetitions, behind the presence / frequency pair
+    "dtk_set_dry": (C.c_int, [_P, C.POINTER(DtkDry)]),
+    "dtk_set_dry_slot": (C.c_int, [_P, C.c_int, C.POINTER(DtkDry)]),
+    "dtk_dry_history": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "dtk_dry_state_bytes": (C.c_int64, [_P]),
+    "dtk_op_dry_scan": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(DtkDry),
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.c_int]),
+    "dtk_op_sample_dry": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float), C.POINTER(DtkSamplingExt),
+                                    C.c_float, C.c_float, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(DtkDry)]),
+    "dtk_engine_submit_dry": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int, C.POINTER(DtkDry),
+                                        C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_dry_op": (C.c_int, [_P, DtkEngineOps.DRY]),
 }
 
 _lib = None
@@ -309,6 +333,9 @@ def load_library() -> C.CDLL:
     if lib.dtk_abi_struct_size(12) != C.sizeof(DtkSamplingExt):
         raise DtkError(f"struct layout mismatch with include/dtk.h: DtkSamplingExt is {C.sizeof(DtkSamplingExt)} here, "
                        f"{lib.dtk_abi_struct_size(12)} in the library")
+    if lib.dtk_abi_struct_size(14) != C.sizeof(DtkDry):
+        raise DtkError(f"struct layout mismatch with include/dtk.h: DtkDry is {C.sizeof(DtkDry)} here, "
+                       f"{lib.dtk_abi_struct_size(14)} in the library")
     _lib = lib
     return lib
 

@@ -167,6 +167,24 @@ __device__ __forceinline__ float pen_apply(float z, unsigned c, float pp, float 
   return c ? z - (float)((double)pp + (double)fp * (double)c) : z;
 }
 
+// DRY (dtk_set_dry; multiplier 0 = off): the penalty of the token that would extend a verbatim repetition of the sequence's own recent
+// text.  One record per sequence, read by k_dry_scan (allowed, breakers) and by the PN sampler instantiations (pen) when SampleArgs::dry
+// is set.  pen[L] is the host's table (IEEE double, repeated multiplication): no pow runs on the device.
+#define DTK_DRY_MAX_MATCH 64
+#define DTK_DRY_MAX_BREAKERS 16
+struct DryDev {
+  float pen[DTK_DRY_MAX_MATCH + 1];   // pen[L] = 0 for L < allowed
+  int32_t on;                         // multiplier != 0
+  int32_t allowed;                    // dry_allowed_length in [1, 64]
+  int32_t n_brk;
+  int32_t brk[DTK_DRY_MAX_BREAKERS];  // dry_sequence_breakers
+};
+// the sequence's history on the device: n ids so far, and how many tokens are still to come before position dry_start is reached
+struct DryLen { int32_t n; int32_t skip; };
+// z' of a (possibly count-penalised) logit z whose id has match length m in the sequence's table (0: untouched bits; the table holds
+// only lengths >= allowed)
+__device__ __forceinline__ float dry_apply(float z, unsigned m, const float* pen) { return m ? z - pen[m] : z; }
+
 // scratch of the multi-block sampler (kernels_sample_mb.hip), one per sequence / slot
 #define DTK_SAMPLE_MB_MAX_SLICES 32      // 32 x 8192 = vocabularies up to 262 144
 struct SampleMB {

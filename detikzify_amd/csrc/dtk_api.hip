@@ -293,6 +293,25 @@ struct dtk_ctx {
   int pen_start[1 + DTK_MAX_SLOTS] = {};    // penalty_start
   bool pen_single = false, graph_pen = false;
   bool pen_batch = false, bgraph_pen = false;
+  // DRY (dtk_set_dry), indexed like the penalties: sequence 0 is the single one, 1 + slot a slot's.  Everything below is allocated by the
+  // first call that sets a multiplier != 0 (dry_alloc, which also makes the penalties' records exist: DRY rides the PN samplers and shares
+  // pen_tok and the trailing kernel), so a context that never uses DRY allocates and launches nothing.  dry_single / dry_batch and
+  // graph_dry / bgraph_dry as pen_single / graph_pen
+  uint8_t* dry_tab = nullptr;        // [1 + nb][dry_stride] match length per id, left by k_dry_scan for the step's sampler
+  int dry_stride = 0;
+  DryDev* dry_dev = nullptr;         // [1 + DTK_MAX_SLOTS]
+  DryDev* dry_stage = nullptr;       // pinned [1 + DTK_MAX_SLOTS]
+  int32_t* dry_hist = nullptr;       // [1 + nb][Tmax] the ids at positions [dry_start, next_pos)
+  int32_t* dry_hist_stage = nullptr; // pinned mirror a rebuild fills
+  DryLen* dry_len = nullptr;         // [1 + DTK_MAX_SLOTS]
+  DryLen* dry_len_stage = nullptr;   // pinned
+  int32_t* dry_touched = nullptr;    // [1 + nb][Tmax] the ids the last scan set
+  int32_t* dry_ntouched = nullptr;   // [1 + DTK_MAX_SLOTS]
+  DryDev dry_val[1 + DTK_MAX_SLOTS] = {};   // the records as set
+  int dry_start[1 + DTK_MAX_SLOTS] = {};    // dry_start
+  bool dry_live[1 + DTK_MAX_SLOTS] = {};    // the sequence's table / history may hold something (it has, or had, a multiplier)
+  bool dry_single = false, graph_dry = false;
+  bool dry_batch = false, bgraph_dry = false;
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
@@ -841,15 +860,29 @@ static inline hipError_t copy_lp_ring(dtk_ctx* c, bool batch) {
 
 // dtk_set_penalties: the PN samplers' view of the step's sequences (nothing without a sequence that has values), and the trailing
 // kernel that counts the tokens they sampled
-static void pen_args(const dtk_ctx* c, SampleArgs& sa, bool batch) {
-  if (!(batch ? c->pen_batch : c->pen_single) || !c->pen_tab) return;
+// dtk_set_dry: a step with a sequence that has a multiplier runs the PN samplers too (with 0 / 0 where there is no penalty), k_dry_scan in
+// front of them and the trailing kernel, which then also appends to the histories
+static void pen_args(const dtk_ctx* c, SampleArgs& sa, DryScanArgs& ds, bool batch) {
+  const bool dry = (batch ? c->dry_batch : c->dry_single) && c->dry_tab;
+  const bool pen = (batch ? c->pen_batch : c->pen_single) && c->pen_tab;
+  if (!(pen || dry) || !c->pen_dev || !c->pen_tok) return;
   const int first = batch ? 1 : 0;
-  sa.pen = c->pen_dev + first; sa.pen_cnt = c->pen_tab + (size_t)first * c->pen_stride; sa.pen_stride = c->pen_stride; sa.pen_tok = c->pen_tok + first;
+  // (a launch with DRY alone has records of 0 / 0 and no count tables: nothing reads pen_cnt)
+  sa.pen = c->pen_dev + first; sa.pen_cnt = c->pen_tab ? c->pen_tab + (size_t)first * c->pen_stride : nullptr; sa.pen_stride = c->pen_stride;
+  sa.pen_tok = c->pen_tok + first;
+  if (!dry) return;
+  sa.dry = c->dry_dev + first; sa.dry_m = c->dry_tab + (size_t)first * c->dry_stride; sa.dry_stride = c->dry_stride;
+  ds.dry = sa.dry; ds.hist = c->dry_hist + (size_t)first * c->Tmax; ds.len = c->dry_len + first; ds.hist_stride = c->Tmax;
+  ds.m = c->dry_tab + (size_t)first * c->dry_stride; ds.m_stride = c->dry_stride;
+  ds.touched = c->dry_touched + (size_t)first * c->Tmax; ds.n_touched = c->dry_ntouched + first;
+  ds.V = sa.V; ds.bs = sa.bs; ds.nslots = sa.bs ? sa.nslots : 1;
 }
 static void sampler_launch(dtk_ctx* c, SampleArgs& sa, bool mb, bool batch) {
-  pen_args(c, sa, batch);
+  DryScanArgs ds;
+  pen_args(c, sa, ds, batch);
+  if (sa.dry) launch_dry_scan(ds, c->stream);
   if (mb) launch_sample_mb(sa, c->stream); else launch_sample_b(sa, c->stream);
-  if (sa.pen) launch_count_token(sa, c->stream);
+  if (sa.pen) launch_count_token(sa, ds, c->stream);
 }
 
 // "top_logprobs": k_top_logits in front of the step's sampler, on the logits, DecState and BatchState the sampler is about to read
@@ -1300,6 +1333,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   const int gi = step_graph_index(c);
   if (c->bgraph_trunc != c->trunc_batch) { drop_batch_graphs(c); c->bgraph_trunc = c->trunc_batch; }
   if (c->bgraph_pen != c->pen_batch) { drop_batch_graphs(c); c->bgraph_pen = c->pen_batch; }
+  if (c->bgraph_dry != c->dry_batch) { drop_batch_graphs(c); c->bgraph_dry = c->dry_batch; }
   if (c->bgraph_ready[gi]) return DTK_OK;
   HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   c->launch_refused = false;
@@ -1321,6 +1355,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
 int ensure_graph(dtk_ctx* c) {
   if (c->graph_trunc != c->trunc_single) { drop_graph(c); c->graph_trunc = c->trunc_single; }
   if (c->graph_pen != c->pen_single) { drop_graph(c); c->graph_pen = c->pen_single; }
+  if (c->graph_dry != c->dry_single) { drop_graph(c); c->graph_dry = c->dry_single; }
   if (c->graph_ready) return DTK_OK;
   // two captures of the same step: split-K attention (any context) and the one-block-per-head
   // attention used while the context is short; the host picks per step (it knows the position)
@@ -1372,20 +1407,36 @@ static inline int pen_index(const dtk_ctx* c, const SeqHost& sh) { return &sh ==
 static inline bool pen_on(const dtk_ctx* c, int q) { return c->pen_val[q].pp != 0.f || c->pen_val[q].fp != 0.f; }
 
 // everything the feature keeps on the device, at the first non-zero value
+// the per-sequence records the PN samplers and the trailing kernel need whatever feature brought them in (penalties or DRY): PenDev
+// (0 / 0) and pen_tok (-1).  Each is initialised once, where it is allocated: DRY may have been stepping with them for a while when
+// the first penalty arrives
+static int pen_alloc_records(dtk_ctx* c) {
+  const int nrec = 1 + DTK_MAX_SLOTS;
+  if (!c->pen_dev) {
+    PenDev* p = nullptr;
+    HIPCHK(c, hipMalloc(&p, sizeof(PenDev) * nrec));
+    c->pen_dev = p;
+    HIPCHK(c, hipMemset(c->pen_dev, 0, sizeof(PenDev) * nrec));
+  }
+  if (!c->pen_tok) {
+    int32_t* p = nullptr;
+    HIPCHK(c, hipMalloc(&p, sizeof(int32_t) * nrec));
+    c->pen_tok = p;
+    HIPCHK(c, hipMemset(c->pen_tok, 0xff, sizeof(int32_t) * nrec));
+  }
+  if (!c->pen_stage) HIPCHK(c, hipHostMalloc((void**)&c->pen_stage, sizeof(PenDev) * nrec, hipHostMallocDefault));
+  return DTK_OK;
+}
 static int pen_alloc(dtk_ctx* c) {
   if (c->pen_tab) return DTK_OK;
   if (c->Tmax >= 65536) return fail(c, DTK_ERR_RANGE, "penalties: max_positions %d does not fit the 16-bit counts (< 65536)", c->Tmax);
-  const int nseq = 1 + c->nb, nrec = 1 + DTK_MAX_SLOTS;
+  const int nseq = 1 + c->nb;
   c->pen_stride = (c->V + 7) & ~7;
   // (pen_tab, assigned last, says that everything exists; a buffer that a failed attempt left is kept for the next one and freed with
   // the context)
-  if (!c->pen_dev) HIPCHK(c, hipMalloc(&c->pen_dev, sizeof(PenDev) * nrec));
-  HIPCHK(c, hipMemset(c->pen_dev, 0, sizeof(PenDev) * nrec));
-  if (!c->pen_tok) HIPCHK(c, hipMalloc(&c->pen_tok, sizeof(int32_t) * nrec));
-  HIPCHK(c, hipMemset(c->pen_tok, 0xff, sizeof(int32_t) * nrec));
+  if (const int rc = pen_alloc_records(c)) return rc;
   if (!c->pen_ids_dev) HIPCHK(c, hipMalloc(&c->pen_ids_dev, sizeof(int32_t) * (size_t)nseq * c->Tmax));
   if (!c->pen_ids_stage) HIPCHK(c, hipHostMalloc((void**)&c->pen_ids_stage, sizeof(int32_t) * (size_t)nseq * c->Tmax, hipHostMallocDefault));
-  if (!c->pen_stage) HIPCHK(c, hipHostMalloc((void**)&c->pen_stage, sizeof(PenDev) * nrec, hipHostMallocDefault));
   uint16_t* tab = nullptr;
   HIPCHK(c, hipMalloc(&tab, sizeof(uint16_t) * (size_t)nseq * c->pen_stride));
   HIPCHK(c, hipMemset(tab, 0, sizeof(uint16_t) * (size_t)nseq * c->pen_stride));
@@ -1396,7 +1447,9 @@ static int pen_alloc(dtk_ctx* c) {
 // Sequence q's table from its token list ids[0, n): zero-fill, then (values != 0 only: a sequence without values keeps an empty table)
 // the scatter of ids[start, n).  All on the context's stream from pinned per-sequence staging, so a slot's rebuild queues behind a step
 // of the other slots in flight like its sampling upload does.  Nothing before the tables exist.
+static int dry_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one_more);
 static int pen_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one_more = -1) {
+  if (const int rc = dry_rebuild(c, q, ids, n, one_more)) return rc;      // the DRY history is redefined in the same places
   if (!c->pen_tab) return DTK_OK;
   uint16_t* tab = c->pen_tab + (size_t)q * c->pen_stride;
   HIPCHK(c, hipMemsetAsync(tab, 0, sizeof(uint16_t) * (size_t)c->pen_stride, c->stream));
@@ -1441,6 +1494,106 @@ static int pen_set(dtk_ctx* c, int q, float pp, float fp, int start) {
 // every table empty: the places that leave the context without any sequence (weights, adapter, options that clear the caches)
 static void pen_clear_all(dtk_ctx* c) {
   if (c->pen_tab) (void)hipMemsetAsync(c->pen_tab, 0, sizeof(uint16_t) * (size_t)(1 + c->nb) * c->pen_stride, c->stream);
+  if (c->dry_tab) {      // ... and every DRY history
+    (void)hipMemsetAsync(c->dry_tab, 0, (size_t)(1 + c->nb) * c->dry_stride, c->stream);
+    (void)hipMemsetAsync(c->dry_len, 0, sizeof(DryLen) * (1 + DTK_MAX_SLOTS), c->stream);
+    (void)hipMemsetAsync(c->dry_ntouched, 0, sizeof(int32_t) * (1 + DTK_MAX_SLOTS), c->stream);
+    for (int q = 0; q <= DTK_MAX_SLOTS; ++q) c->dry_live[q] = c->dry_val[q].on != 0;
+  }
+}
+
+// ---- DRY: the histories and the match tables -----------------------------------------------------------------------------------------
+static inline bool dry_on(const dtk_ctx* c, int q) { return c->dry_val[q].on != 0; }
+
+static int dry_alloc(dtk_ctx* c) {
+  if (c->dry_tab) return DTK_OK;
+  if (const int rc = pen_alloc_records(c)) return rc;
+  const int nseq = 1 + c->nb, nrec = 1 + DTK_MAX_SLOTS;
+  c->dry_stride = (c->V + 15) & ~15;
+  // (dry_tab, assigned last, says that everything exists, as pen_tab does)
+  if (!c->dry_dev) HIPCHK(c, hipMalloc(&c->dry_dev, sizeof(DryDev) * nrec));
+  HIPCHK(c, hipMemset(c->dry_dev, 0, sizeof(DryDev) * nrec));
+  if (!c->dry_stage) HIPCHK(c, hipHostMalloc((void**)&c->dry_stage, sizeof(DryDev) * nrec, hipHostMallocDefault));
+  if (!c->dry_hist) HIPCHK(c, hipMalloc(&c->dry_hist, sizeof(int32_t) * (size_t)nseq * c->Tmax));
+  if (!c->dry_hist_stage) HIPCHK(c, hipHostMalloc((void**)&c->dry_hist_stage, sizeof(int32_t) * (size_t)nseq * c->Tmax, hipHostMallocDefault));
+  if (!c->dry_len) HIPCHK(c, hipMalloc(&c->dry_len, sizeof(DryLen) * nrec));
+  HIPCHK(c, hipMemset(c->dry_len, 0, sizeof(DryLen) * nrec));
+  if (!c->dry_len_stage) HIPCHK(c, hipHostMalloc((void**)&c->dry_len_stage, sizeof(DryLen) * nrec, hipHostMallocDefault));
+  if (!c->dry_touched) HIPCHK(c, hipMalloc(&c->dry_touched, sizeof(int32_t) * (size_t)nseq * c->Tmax));
+  if (!c->dry_ntouched) HIPCHK(c, hipMalloc(&c->dry_ntouched, sizeof(int32_t) * nrec));
+  HIPCHK(c, hipMemset(c->dry_ntouched, 0, sizeof(int32_t) * nrec));
+  uint8_t* tab = nullptr;
+  HIPCHK(c, hipMalloc(&tab, (size_t)nseq * c->dry_stride));
+  HIPCHK(c, hipMemset(tab, 0, (size_t)nseq * c->dry_stride));
+  c->dry_tab = tab;
+  return DTK_OK;
+}
+
+// Sequence q's history from its token list ids[0, n) (+ one_more at position n: a resumed slot's forced id): empty table, empty touched
+// list, then (multiplier != 0 only) the ids from dry_start on.  On the context's stream from pinned per-sequence staging, as pen_rebuild.
+static int dry_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one_more) {
+  if (!c->dry_tab) return DTK_OK;
+  if (!dry_on(c, q) && !c->dry_live[q]) return DTK_OK;      // never had a multiplier since its last clear: everything is empty already
+  c->dry_live[q] = dry_on(c, q);
+  HIPCHK(c, hipMemsetAsync(c->dry_tab + (size_t)q * c->dry_stride, 0, (size_t)c->dry_stride, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->dry_ntouched + q, 0, sizeof(int32_t), c->stream));
+  DryLen& ls = c->dry_len_stage[q];
+  ls.n = 0; ls.skip = 0;
+  if (dry_on(c, q) && ids) {
+    if (n > c->Tmax) n = c->Tmax;
+    const int start = c->dry_start[q];
+    int32_t* st = c->dry_hist_stage + (size_t)q * c->Tmax;
+    int m = 0;
+    for (int i = start; i < n; ++i) st[m++] = (int32_t)ids[i];
+    int total = n;
+    if (one_more >= 0 && n < c->Tmax) { if (start <= n) st[m++] = (int32_t)one_more; total = n + 1; }
+    ls.n = m; ls.skip = start > total ? start - total : 0;
+    if (m > 0) HIPCHK(c, hipMemcpyAsync(c->dry_hist + (size_t)q * c->Tmax, st, sizeof(int32_t) * (size_t)m, hipMemcpyHostToDevice, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(c->dry_len + q, &ls, sizeof(DryLen), hipMemcpyHostToDevice, c->stream));
+  return DTK_OK;
+}
+
+static int dry_check(dtk_ctx* c, const dtk_dry* d, int V, const char* who) {
+  if (!d) return fail(c, DTK_ERR_ARG, "%s: no dtk_dry", who);
+  if (!(d->multiplier >= 0.f && d->multiplier <= 100.f)) return fail(c, DTK_ERR_ARG, "%s: dry_multiplier must be in [0, 100]", who);
+  if (!(d->base >= 1.f && d->base <= 8.f)) return fail(c, DTK_ERR_ARG, "%s: dry_base must be in [1, 8]", who);
+  if (d->allowed_length < 1 || d->allowed_length > DTK_DRY_MAX_MATCH) return fail(c, DTK_ERR_ARG, "%s: dry_allowed_length must be in [1, %d]", who, DTK_DRY_MAX_MATCH);
+  if (d->start < 0) return fail(c, DTK_ERR_ARG, "%s: dry_start must be >= 0", who);
+  if (d->n_breakers < 0 || d->n_breakers > DTK_DRY_MAX_BREAKERS) return fail(c, DTK_ERR_ARG, "%s: at most %d dry_sequence_breakers", who, DTK_DRY_MAX_BREAKERS);
+  for (int i = 0; i < d->n_breakers; ++i)
+    if (d->breakers[i] < 0 || d->breakers[i] >= V) return fail(c, DTK_ERR_ARG, "%s: sequence breaker %d outside [0, %d)", who, d->breakers[i], V);
+  return DTK_OK;
+}
+
+// the device record of a dtk_dry: pen[L] = 0 below allowed_length, then multiplier * base^(L - allowed_length) by repeated multiplication
+// in double, clamped to 1e30 (include/dtk.h: the oracle reproduces it bit for bit)
+static DryDev dry_record(const dtk_dry* d) {
+  DryDev v{};
+  if (!d || d->multiplier == 0.f) return v;
+  v.on = 1; v.allowed = d->allowed_length; v.n_brk = d->n_breakers;
+  for (int i = 0; i < d->n_breakers; ++i) v.brk[i] = d->breakers[i];
+  double p = (double)d->multiplier;
+  for (int L = d->allowed_length; L <= DTK_DRY_MAX_MATCH; ++L) { v.pen[L] = (float)(p < 1e30 ? p : 1e30); p *= (double)d->base; }
+  return v;
+}
+
+// the record of sequence q (null / multiplier 0: off, the reset of dtk_set_sampling[_slot]); the history follows it
+static int dry_set(dtk_ctx* c, int q, const dtk_dry* d) {
+  const bool on = d && d->multiplier != 0.f;
+  if (!on && !dry_on(c, q)) { c->dry_start[q] = d ? d->start : 0; return DTK_OK; }      // nothing to switch off
+  if (on) { const int rc = dry_alloc(c); if (rc) return rc; }
+  c->dry_val[q] = dry_record(d); c->dry_start[q] = d ? d->start : 0;
+  c->dry_stage[q] = c->dry_val[q];
+  HIPCHK(c, hipMemcpyAsync(c->dry_dev + q, &c->dry_stage[q], sizeof(DryDev), hipMemcpyHostToDevice, c->stream));
+  if (q == 0) c->dry_single = on;
+  else {
+    bool any = false;
+    for (int j = 1; j <= c->nb; ++j) any = any || dry_on(c, j);
+    c->dry_batch = any;
+  }
+  const SeqHost& sh = q == 0 ? c->seq0 : c->bseq[(size_t)q - 1];
+  return dry_rebuild(c, q, sh.cached_ids.data(), (int)sh.cached_ids.size(), sh.forced_pending);
 }
 
 int dtk_abi_struct_size(int which) {
@@ -1458,6 +1611,7 @@ int dtk_abi_struct_size(int which) {
     case 10: return (int)offsetof(dtk_join, error_out);
     case 11: return (int)sizeof(dtk_adapter_config);
     case 12: return (int)sizeof(dtk_sampling_ext);
+    case 14: return (int)sizeof(dtk_dry);      // (13 stays unassigned: -1)
     default: return -1;
   }
 }
@@ -1653,6 +1807,15 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->pen_ids_dev) (void)hipFree(c->pen_ids_dev);
   if (c->pen_ids_stage) (void)hipHostFree(c->pen_ids_stage);
   if (c->pen_stage) (void)hipHostFree(c->pen_stage);
+  if (c->dry_tab) (void)hipFree(c->dry_tab);
+  if (c->dry_dev) (void)hipFree(c->dry_dev);
+  if (c->dry_stage) (void)hipHostFree(c->dry_stage);
+  if (c->dry_hist) (void)hipFree(c->dry_hist);
+  if (c->dry_hist_stage) (void)hipHostFree(c->dry_hist_stage);
+  if (c->dry_len) (void)hipFree(c->dry_len);
+  if (c->dry_len_stage) (void)hipHostFree(c->dry_len_stage);
+  if (c->dry_touched) (void)hipFree(c->dry_touched);
+  if (c->dry_ntouched) (void)hipFree(c->dry_ntouched);
   if (c->top_ring_dev) (void)hipFree(c->top_ring_dev);
   if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
   if (c->topb_dev) (void)hipFree(c->topb_dev);
@@ -2351,6 +2514,7 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
   if (is_single) { c->sampling = *sp; c->launched = c->waited = 0; c->sampling_ext = dtk_sampling_ext{}; c->trunc_single = false; }
   else c->slot_trunc[(int)(sp_dst - c->sp_b)] = false;      // dv.qmin = dv.eps = 0: dtk_set_sampling_*_ext follows where they are wanted
   if (const int rc = pen_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), 0.f, 0.f, 0)) return rc;      // dtk_set_penalties[_slot] likewise
+  if (const int rc = dry_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), nullptr)) return rc;      // dtk_set_dry[_slot] likewise
   // which sampler the captured graphs must contain: the multi-block chain serves large vocabularies unless a
   // configuration needs top-k; a change of kind drops the graph (re-captured by the next launch)
   const bool needs_topk = sp->do_sample && sp->top_k > 0 && sp->top_k < c->V;
@@ -2466,6 +2630,46 @@ int dtk_token_counts(dtk_ctx* c, int slot, uint16_t* out, int V) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(out, c->pen_tab + (size_t)(slot + 1) * c->pen_stride, sizeof(uint16_t) * (size_t)V, hipMemcpyDeviceToHost));
   return DTK_OK;
+}
+
+// DRY of the sequence the last dtk_set_sampling[_slot] configured (include/dtk.h)
+int dtk_set_dry(dtk_ctx* c, const dtk_dry* d) {
+  if (!c) return DTK_ERR_ARG;
+  if (const int rc = dry_check(c, d, c->V, "dtk_set_dry")) return rc;
+  if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "dtk_set_dry: %d decode step(s) are unread", (int)(c->launched - c->waited));
+  HIPCHK(c, hipSetDevice(c->device));
+  return dry_set(c, 0, d);
+}
+
+int dtk_set_dry_slot(dtk_ctx* c, int slot, const dtk_dry* d) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_set_dry_slot: slot %d of %d", slot, c ? c->nb : 0);
+  if (const int rc = dry_check(c, d, c->V, "dtk_set_dry_slot")) return rc;
+  for (uint64_t q = c->bwaited; q < c->blaunched; ++q)
+    if (c->bs_host[q % DTK_MAX_INFLIGHT].active[slot]) return fail(c, DTK_ERR_STATE, "dtk_set_dry_slot: slot %d is part of an unread step", slot);
+  HIPCHK(c, hipSetDevice(c->device));
+  return dry_set(c, 1 + slot, d);
+}
+
+// Diagnostic: the history the next scan of the sequence will read (slot -1: the single sequence): its length, or a negative error; at
+// most n_max ids go to ids_out.  0 while the feature is off
+int dtk_dry_history(dtk_ctx* c, int slot, int32_t* ids_out, int n_max) {
+  if (!c || slot < -1 || slot >= c->nb || n_max < 0 || (n_max > 0 && !ids_out)) return fail(c, DTK_ERR_ARG, "dtk_dry_history: bad argument");
+  if (!c->dry_tab) return 0;
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, DTK_ERR_HIP, "dtk_dry_history: the stream failed");
+  DryLen l{};
+  if (hipMemcpy(&l, c->dry_len + (slot + 1), sizeof l, hipMemcpyDeviceToHost) != hipSuccess) return fail(c, DTK_ERR_HIP, "dtk_dry_history: copy failed");
+  const int k = l.n < n_max ? l.n : n_max;
+  if (k > 0 && hipMemcpy(ids_out, c->dry_hist + (size_t)(slot + 1) * c->Tmax, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(c, DTK_ERR_HIP, "dtk_dry_history: copy failed");
+  return l.n;
+}
+
+// Diagnostic: the bytes of device and pinned memory the DRY state holds; 0 as long as no sequence of the context ever had a multiplier
+int64_t dtk_dry_state_bytes(const dtk_ctx* c) {
+  if (!c || !c->dry_tab) return 0;
+  const size_t nseq = (size_t)(1 + c->nb), nrec = 1 + DTK_MAX_SLOTS;
+  return (int64_t)(nseq * c->dry_stride + 2 * nrec * sizeof(DryDev) + 3 * nseq * c->Tmax * sizeof(int32_t) + 2 * nrec * sizeof(DryLen) +
+                   nrec * sizeof(int32_t));
 }
 
 int dtk_num_slots(const dtk_ctx* c) { return c ? c->nb : 0; }
@@ -4544,8 +4748,27 @@ int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uin
 }
 
 struct OpPen { float pp, fp; const int64_t* ids; int n; };     // dtk_op_sample_pen's own arguments
+struct OpDry { const dtk_dry* d; const int64_t* hist; int n; };   // dtk_op_sample_dry's / dtk_op_dry_scan's: the history h[0, n) itself
+// a DRY state of the call's own in the op scratch (record, history, empty table and touched list), ready for launch_dry_scan
+static int op_dry_state(dtk_ctx* c, size_t& off, const OpDry& od, int V, DryScanArgs& ds) {
+  const int stride = (V + 15) & ~15, cap = od.n > 0 ? od.n : 1;
+  OPBUF(DryDev, ddev, 1); OPBUF(int32_t, dh, cap); OPBUF(int32_t, dt, cap); OPBUF(DryLen, dlen, 1); OPBUF(int32_t, dnt, 1); OPBUF(uint8_t, dm, stride);
+  const DryDev rec = dry_record(od.d);
+  const DryLen l{od.n, 0};
+  std::vector<int32_t> h32((size_t)(od.n > 0 ? od.n : 0));
+  for (int i = 0; i < od.n; ++i) h32[(size_t)i] = (int32_t)od.hist[i];
+  HIPCHK(c, hipMemcpy(ddev, &rec, sizeof rec, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dlen, &l, sizeof l, hipMemcpyHostToDevice));
+  if (od.n > 0) HIPCHK(c, hipMemcpy(dh, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemset(dnt, 0, sizeof(int32_t)));
+  HIPCHK(c, hipMemset(dm, 0, (size_t)stride));
+  ds = DryScanArgs{};
+  ds.dry = ddev; ds.hist = dh; ds.len = dlen; ds.hist_stride = cap; ds.m = dm; ds.m_stride = stride; ds.touched = dt; ds.n_touched = dnt;
+  ds.V = V; ds.bs = nullptr; ds.nslots = 1;
+  return DTK_OK;
+}
 static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr) {
+                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr, const OpDry* dry = nullptr) {
   HIPCHK(c, hipSetDevice(c->device));
   size_t off = 0;
   OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1); OPBUF(SamplingDev, dsp, 1);
@@ -4578,6 +4801,12 @@ static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int6
   if (ext) { sa.sp = dsp; sa.trunc = (xd.qmin != 0 || xd.eps != 0.f) ? 1 : 0; }
   else sa.trunc = c->trunc_single ? 1 : 0;
   if (pen) { sa.pen = dpen; sa.pen_cnt = dcnt; sa.pen_stride = (V + 7) & ~7; }      // advance = 0: nothing is counted
+  if (dry && pen) {      // the product scan over the call's own history, then the PN samplers with its table
+    DryScanArgs ds;
+    if (const int rc = op_dry_state(c, off, *dry, V, ds)) return rc;
+    launch_dry_scan(ds, s);
+    sa.dry = ds.dry; sa.dry_m = ds.m; sa.dry_stride = ds.m_stride;
+  }
   const bool needs_topk = c->sampling.do_sample && c->sampling.top_k > 0 && c->sampling.top_k < V;
   if (sample_mb_preferred(V, c->sampling.do_sample != 0) && !needs_topk && !getenv("DTK_SAMPLER")) launch_sample_mb(sa, s); else launch_sample(sa, s);
   HIPCHK(c, hipMemcpyAsync(token_out, dtok, 8, hipMemcpyDeviceToHost, s));
@@ -4627,6 +4856,72 @@ int dtk_op_sample_pen(dtk_ctx* c, const float* logits, int V, int step, int64_t*
   if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
   const OpPen pn{presence, frequency, counted_ids, n_counted};
   return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn);
+}
+
+static int op_dry_check(dtk_ctx* c, const dtk_dry* d, int V, const int64_t* hist, int n, const char* who) {
+  if (const int rc = dry_check(c, d, V, who)) return rc;
+  if (n < 0 || n > 65535 || (n > 0 && !hist)) return fail(c, DTK_ERR_ARG, "%s: a history of 0 .. 65535 ids", who);
+  for (int i = 0; i < n; ++i)
+    if (hist[i] < 0 || hist[i] >= V) return fail(c, DTK_ERR_ARG, "%s: history id %lld outside [0, %d)", who, (long long)hist[i], V);
+  return DTK_OK;
+}
+
+// dtk_op_sample_pen with DRY over a given history h[0, n) (dry->start is not used: the history is given as it stands): k_dry_scan, then
+// the PN sampler instantiations with both the count table and the match table, whatever the values are
+int dtk_op_sample_dry(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
+                      const dtk_sampling_ext* ext, float presence, float frequency, const int64_t* counted_ids, int n_counted,
+                      const int64_t* history, int n_history, const dtk_dry* dry) {
+  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V) || n_counted < 0 ||
+      n_counted > 65535 || (n_counted > 0 && !counted_ids))
+    return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: bad argument");
+  if (ext) if (const int rc = ext_check(c, ext, "dtk_op_sample_dry")) return rc;
+  if (const int rc = pen_check(c, presence, frequency, 0, "dtk_op_sample_dry")) return rc;
+  if (const int rc = op_dry_check(c, dry, V, history, n_history, "dtk_op_sample_dry")) return rc;
+  for (int i = 0; i < n_counted; ++i)
+    if (counted_ids[i] < 0 || counted_ids[i] >= V) return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: counted id %lld outside [0, %d)", (long long)counted_ids[i], V);
+  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  const OpPen pn{presence, frequency, counted_ids, n_counted};
+  const OpDry od{dry, history, n_history};
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn, &od);
+}
+
+// k_dry_scan alone over a given history; with history2, a second scan of that history on the state the first one left (table and
+// touched list), as two consecutive steps of a sequence do.  The result is read from the WHOLE table behind the last scan: every id
+// with M != 0 in ascending order, so an entry a scan failed to clear shows.  Returns their number (the first n_max go out) or an error
+int dtk_op_dry_scan(dtk_ctx* c, int V, const int64_t* history, int n_history, const int64_t* history2, int n_history2, const dtk_dry* dry,
+                    int32_t* ids_out, uint8_t* m_out, int n_max) {
+  if (!c || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || n_max < 0 || (n_max > 0 && (!ids_out || !m_out)))
+    return fail(c, DTK_ERR_ARG, "dtk_op_dry_scan: bad argument");
+  if (const int rc = op_dry_check(c, dry, V, history, n_history, "dtk_op_dry_scan")) return rc;
+  if (history2) if (const int rc = op_dry_check(c, dry, V, history2, n_history2, "dtk_op_dry_scan")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t off = 0;
+  hipStream_t s = c->stream;
+  const int cap = history2 && n_history2 > n_history ? n_history2 : n_history;
+  std::vector<int64_t> first(history, history + n_history);
+  first.resize((size_t)cap, 0);      // (room for the longer of the two; the length says what counts)
+  DryScanArgs ds;
+  if (const int rc = op_dry_state(c, off, OpDry{dry, first.data(), cap}, V, ds)) return rc;
+  const DryLen l1{n_history, 0};
+  HIPCHK(c, hipMemcpy(ds.len, &l1, sizeof l1, hipMemcpyHostToDevice));
+  launch_dry_scan(ds, s);
+  if (history2) {
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::vector<int32_t> h32((size_t)n_history2);
+    for (int i = 0; i < n_history2; ++i) h32[(size_t)i] = (int32_t)history2[i];
+    const DryLen l2{n_history2, 0};
+    if (n_history2 > 0) HIPCHK(c, hipMemcpy(ds.hist, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ds.len, &l2, sizeof l2, hipMemcpyHostToDevice));
+    launch_dry_scan(ds, s);
+  }
+  HIPCHK(c, hipStreamSynchronize(s));
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint8_t> tab((size_t)ds.m_stride);
+  HIPCHK(c, hipMemcpy(tab.data(), ds.m, tab.size(), hipMemcpyDeviceToHost));
+  int k = 0;
+  for (int t = 0; t < V; ++t)
+    if (tab[(size_t)t]) { if (k < n_max) { ids_out[k] = t; m_out[k] = tab[(size_t)t]; } ++k; }
+  return k;
 }
 
 }  // extern "C"

@@ -63,6 +63,7 @@ struct Cmd {
   dtk_sampling_ext ext{};           // the sequence's min_p / epsilon_cutoff (dtk_engine_submit_ext), 0 / 0 for every other join
   float pen_p = 0.f, pen_f = 0.f;   // the sequence's presence / frequency penalty and penalty_start (dtk_engine_submit_pen), 0 / 0 / 0 for
   int pen_start = 0;                // every other join
+  dtk_dry dry{0.f, 1.75f, 2, 0, 0, {}};   // the sequence's DRY (dtk_engine_submit_dry); off, at the defaults, for every other join
   int rc = 0;
   bool done = false;
   std::condition_variable cv;
@@ -77,6 +78,7 @@ using PrefillTextFn = int (*)(void* dev, int slot, const int64_t* ids, int T, co
 using WaitLpFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out);
 using SamplingExtFn = int (*)(void* dev, int slot, const dtk_sampling_ext* x);
 using PenaltiesFn = int (*)(void* dev, int slot, float presence, float frequency, int start);
+using DryFn = int (*)(void* dev, int slot, const dtk_dry* d);
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
@@ -86,6 +88,7 @@ struct dtk_engine {
   WaitLpFn wait_lp = nullptr;               // dtk_engine_set_wait_lp_op: collects a step instead of ops.wait
   SamplingExtFn sampling_ext = nullptr;     // dtk_engine_set_sampling_ext_op (dtk_engine_create: dtk_set_sampling_slot_ext)
   PenaltiesFn penalties = nullptr;          // dtk_engine_set_penalties_op (dtk_engine_create: dtk_set_penalties_slot)
+  DryFn dry = nullptr;                      // dtk_engine_set_dry_op (dtk_engine_create: dtk_set_dry_slot)
   dtk_ctx* own_ctx = nullptr;               // dtk_engine_create: the context, whose "logprobs" option decides which wait collects
   std::mutex mu;
   std::condition_variable cv_run;
@@ -230,6 +233,10 @@ int do_join(dtk_engine* e, const Cmd* c) {
     if (e->penalties) {       // likewise the join's own presence / frequency penalty (0 / 0 / 0 without one)
       rc = e->penalties(o.dev, s, c->pen_p, c->pen_f, c->pen_start);
       if (rc) return set_error(e, j, rc, "dtk_set_penalties_slot");
+    }
+    if (e->dry) {             // likewise the join's own DRY (off without one)
+      rc = e->dry(o.dev, s, &c->dry);
+      if (rc) return set_error(e, j, rc, "dtk_set_dry_slot");
     }
     return DTK_OK;
   };
@@ -390,7 +397,7 @@ void run(dtk_engine* e) {
 // queue a join (text: its text ids, nullptr for an image-only join)
 struct JoinPen { float presence, frequency; int start; };
 int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out,
-           const dtk_sampling_ext* ext = nullptr, const JoinPen* pen = nullptr) {
+           const dtk_sampling_ext* ext = nullptr, const JoinPen* pen = nullptr, const dtk_dry* dry = nullptr) {
   std::lock_guard<std::mutex> g(e->mu);
   if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
   if (text && !e->prefill_text) {
@@ -405,9 +412,14 @@ int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t
     snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_pen: this engine's device takes no presence / frequency penalty (dtk_engine_set_penalties_op)");
     return DTK_ERR_STATE;
   }
+  if (dry && dry->multiplier != 0.f && !e->dry) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: this engine's device takes no DRY (dtk_engine_set_dry_op)");
+    return DTK_ERR_STATE;
+  }
   Cmd* c = new Cmd();
   c->join = j;
   if (ext) c->ext = *ext;
+  if (dry) c->dry = *dry;
   if (pen) { c->pen_p = pen->presence; c->pen_f = pen->frequency; c->pen_start = pen->start; }
   c->text = text; c->n_text = n_text; c->text_key = text_key;
   e->cmds.push_back(c);
@@ -427,6 +439,9 @@ int ctx_sampling_ext(void* d, int s, const dtk_sampling_ext* x) {     // (0 / 0:
 }
 int ctx_penalties(void* d, int s, float pp, float fp, int start) {     // (0 / 0: dtk_set_sampling_slot has just left exactly that)
   return (pp == 0.f && fp == 0.f) ? DTK_OK : dtk_set_penalties_slot((dtk_ctx*)d, s, pp, fp, start);
+}
+int ctx_dry(void* d, int s, const dtk_dry* x) {     // (off: dtk_set_sampling_slot has just left exactly that)
+  return x->multiplier == 0.f ? DTK_OK : dtk_set_dry_slot((dtk_ctx*)d, s, x);
 }
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
 int ctx_lcp(void* d, int s, const int64_t* ids, int n, uint64_t key, int* out) { return dtk_slot_lcp((dtk_ctx*)d, s, ids, n, key, out); }
@@ -470,6 +485,7 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
     (*out)->wait_lp = ctx_wait_lp;
     (*out)->sampling_ext = ctx_sampling_ext;
     (*out)->penalties = ctx_penalties;
+    (*out)->dry = ctx_dry;
   }
   return dtk_engine_set_prefill_text_op(*out, ctx_prefill_text);
 }
@@ -492,6 +508,13 @@ int dtk_engine_set_penalties_op(dtk_engine* e, PenaltiesFn set_penalties_slot) {
   if (!e) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->penalties = set_penalties_slot;
+  return DTK_OK;
+}
+
+int dtk_engine_set_dry_op(dtk_engine* e, DryFn set_dry_slot) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->dry = set_dry_slot;
   return DTK_OK;
 }
 
@@ -606,6 +629,28 @@ int dtk_engine_submit_pen(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x,
   if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_pen: no text"); return DTK_ERR_ARG; }
   const JoinPen pn{presence, frequency, start};
   return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn);
+}
+
+int dtk_engine_submit_dry(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, float presence, float frequency, int start,
+                          const dtk_dry* d, const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  if (!e || !j || !ticket_out) return DTK_ERR_ARG;
+  if (x && (!(x->min_p >= 0.f && x->min_p <= 1.f) || !(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f))) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: min_p must be in [0, 1] and epsilon_cutoff in [0, 1)");
+    return DTK_ERR_ARG;
+  }
+  if (!(presence >= -2.f && presence <= 2.f) || !(frequency >= -2.f && frequency <= 2.f) || start < 0) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: presence_penalty and frequency_penalty must be in [-2, 2], penalty_start >= 0");
+    return DTK_ERR_ARG;
+  }
+  if (d && (!(d->multiplier >= 0.f && d->multiplier <= 100.f) || !(d->base >= 1.f && d->base <= 8.f) || d->allowed_length < 1 ||
+            d->allowed_length > DTK_DRY_MAX_MATCH || d->start < 0 || d->n_breakers < 0 || d->n_breakers > DTK_DRY_MAX_BREAKERS)) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: dry_multiplier in [0, 100], dry_base in [1, 8], dry_allowed_length in [1, 64], "
+             "dry_start >= 0, at most 16 breakers");
+    return DTK_ERR_ARG;
+  }
+  if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: no text"); return DTK_ERR_ARG; }
+  const JoinPen pn{presence, frequency, start};
+  return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn, d);
 }
 
 int dtk_engine_await(dtk_engine* e, uint64_t ticket) {

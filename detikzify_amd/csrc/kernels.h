@@ -103,10 +103,32 @@ struct SampleArgs {
   const uint16_t* pen_cnt = nullptr;   // [pen_stride] per sequence: occurrences of every id among the sequence's counted tokens
   int pen_stride = 0;                  // elements between two sequences' tables (a multiple of 8: every table is 16-byte aligned)
   int32_t* pen_tok = nullptr;          // per sequence: the token this step sampled (-1: forced, already counted), for k_count_token
+  // dtk_set_dry: some sequence of this launch has a DRY multiplier != 0.  Rides the PN instantiations (pen is then set too, with 0 / 0 for
+  // a sequence without penalties) behind a block-uniform test; null = the PN samplers read nothing of it.  Slot 0's in batched mode
+  const DryDev* dry = nullptr;
+  const uint8_t* dry_m = nullptr;      // [dry_stride] per sequence: the match length M of every id (k_dry_scan), 0 = not penalised
+  int dry_stride = 0;                  // bytes between two sequences' tables (a multiple of 16)
 };
-// dtk_set_penalties: the trailing kernel of a step with penalties, behind the sampler (every read of this step's tables is over): one
-// thread per sequence takes pen_tok and adds 1 to the token's count in the tables of the sequences that have values
-void launch_count_token(const SampleArgs& a, hipStream_t s);
+// dtk_set_dry: what k_dry_scan (in front of the sampler) and the trailing kernel (behind it) work on; sequence 0's pointers
+struct DryScanArgs {
+  const DryDev* dry = nullptr;
+  int32_t* hist = nullptr;             // [hist_stride] per sequence: the ids at positions [dry_start, next_pos)
+  DryLen* len = nullptr;               // per sequence
+  int hist_stride = 0;
+  uint8_t* m = nullptr;                // SampleArgs::dry_m
+  int m_stride = 0;
+  int32_t* touched = nullptr;          // [hist_stride] per sequence: the ids whose M the last scan set (with repeats), cleared by the next
+  int32_t* n_touched = nullptr;        // per sequence
+  int V = 0;
+  const BatchState* bs = nullptr;      // batched mode: block = slot, inactive slots return
+  int nslots = 1;
+};
+// one block per sequence: clears what the previous scan set, then M[h[i+1]] = max L(i) over the positions i that match the tail
+void launch_dry_scan(const DryScanArgs& d, hipStream_t s);
+// dtk_set_penalties / dtk_set_dry: the trailing kernel of a step with either, behind the sampler (every read of this step's tables is
+// over): one thread per sequence takes pen_tok, adds 1 to the token's count in the tables of the sequences that have penalty values and
+// (d.hist set) appends it to the histories of the sequences that have DRY
+void launch_count_token(const SampleArgs& a, const DryScanArgs& d, hipStream_t s);
 // count table of one sequence from its counted ids: cnt[ids[i]] += 1 for i < n (ids outside [0, V) are skipped); the table was zeroed
 void launch_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V, hipStream_t s);
 void launch_sample_b(const SampleArgs& a, hipStream_t s);

@@ -1293,6 +1293,20 @@ __device__ __forceinline__ void pen_f32x4(f32x4& v, uint2 cw, float pp, float fp
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = pen_apply(v[e], pen_cnt4(cw, e), pp, fp);
 }
+// DRY (SampleArgs::dry, dtk_set_dry) rides PN: behind pen_apply, a second fp32 subtraction of the table's pen[M] where the id's match
+// length M (one byte beside every logit, left by k_dry_scan in front of this kernel) is not 0; a sequence without a multiplier reads no
+// byte (block-uniform), a launch without DRY (a.dry null) likewise.  The trailing kernel appends pen_tok to the history.
+__device__ __forceinline__ void dry_f32x4(f32x4& v, uint32_t mw, const float* pen) {
+  if (mw == 0u) return;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = dry_apply(v[e], (mw >> (8 * e)) & 0xffu, pen);
+}
+__device__ __forceinline__ float pen_dry1(const SampleArgs& a, int i, bool pn, float pp, float fp, bool dr, const float* dpen) {
+  float z = a.logits[i];
+  if (pn) z = pen_apply(z, a.pen_cnt[i], pp, fp);
+  if (dr) z = dry_apply(z, a.dry_m[i], dpen);
+  return z;
+}
 template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (a.bs) {  // batched decode: one block per slot, same code on that slot's buffers
@@ -1306,6 +1320,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
+    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
     a.ring = 1;        // the ring index was applied above
     a.step_override = -1;
   }
@@ -1340,6 +1355,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
   if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
   (void)pn_p; (void)pn_f; (void)pn;
+  const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
+  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
+  (void)dpen; (void)dr;
 
   // ---- pass 1: masked (scaled) max and first argmax.  16-byte loads, four per thread in flight
   // (the greedy path is one memory round trip + the block reduction)
@@ -1366,6 +1384,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         }
       }
       (void)cw;
+      uint32_t dw[4];    // PN, DRY: the four match lengths likewise
+      if constexpr (PN) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i4 = base + u * SAMPLE_THREADS;
+          dw[u] = (dr && i4 < V4) ? reinterpret_cast<const uint32_t*>(a.dry_m)[i4] : 0u;
+        }
+      }
+      (void)dw;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i4 = base + u * SAMPLE_THREADS;
@@ -1375,7 +1402,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
           const int i = i4 * 4 + e;
           if constexpr (LP) lse_push(lm, ls, v[u][e]);
           float z;
-          if constexpr (PN) z = pen_apply(v[u][e], pen_cnt4(cw[u], e), pn_p, pn_f) * invT;
+          if constexpr (PN) z = dry_apply(pen_apply(v[u][e], pen_cnt4(cw[u], e), pn_p, pn_f), (dw[u] >> (8 * e)) & 0xffu, dpen) * invT;
           else z = v[u][e] * invT;
           if (is_banned(sp, i, first)) z = -INFINITY;
           if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1386,7 +1413,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     for (int i = tid; i < V; i += SAMPLE_THREADS) {
       if constexpr (LP) lse_push(lm, ls, a.logits[i]);
       float z;
-      if constexpr (PN) z = (pn ? pen_apply(a.logits[i], a.pen_cnt[i], pn_p, pn_f) : a.logits[i]) * invT;
+      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen) * invT;
       else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1419,7 +1446,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (sampling) {
     // fixed-point mass q_i = floor(exp(z_i - zmax) * 2^31)  (fits 32 bits; exact integer sums)
     auto mass = [&](int i, float& z) -> unsigned long long {
-      if constexpr (PN) z = (pn ? pen_apply(a.logits[i], a.pen_cnt[i], pn_p, pn_f) : a.logits[i]) * invT;
+      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen) * invT;
       else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       const float e = expf(z - zmax);
@@ -1628,6 +1655,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
+    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
     a.ring = 1;
     a.step_override = -1;
   }
@@ -1660,6 +1688,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
   if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
   (void)pn_p; (void)pn_f; (void)pn;
+  const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
+  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
+  (void)dpen; (void)dr;
   const int i0 = tid * SF_PER;
 
   // ---- the one pass over the logits
@@ -1676,6 +1707,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
         if (m4 > lm) { ls *= expf(lm - m4); lm = m4; }
         ls += (expf(v[0] - lm) + expf(v[1] - lm)) + (expf(v[2] - lm) + expf(v[3] - lm));
         if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
+        if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
       }
@@ -1685,6 +1717,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
         float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
         lse_push(lm, ls, v);
         if constexpr (PN) if (pn && i0 + k < V) v = pen_apply(v, a.pen_cnt[i0 + k], pn_p, pn_f);
+        if constexpr (PN) if (dr && i0 + k < V) v = dry_apply(v, a.dry_m[i0 + k], dpen);
         z[k] = v * invT;
       }
     }
@@ -1694,13 +1727,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     for (int k = 0; k < SF_PER / 4; ++k) {
       f32x4 v = l4[k];
       if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
+      if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
     }
   } else if constexpr (PN) {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k)
-      z[k] = (i0 + k < V) ? (pn ? pen_apply(a.logits[i0 + k], a.pen_cnt[i0 + k], pn_p, pn_f) : a.logits[i0 + k]) * invT : -INFINITY;
+      z[k] = (i0 + k < V) ? pen_dry1(a, i0 + k, pn, pn_p, pn_f, dr, dpen) * invT : -INFINITY;
   } else {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) z[k] = (i0 + k < V) ? a.logits[i0 + k] * invT : -INFINITY;
@@ -2032,20 +2066,92 @@ __global__ __launch_bounds__(256) void k_count_scatter(const int32_t* ids, int n
 void launch_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_count_scatter, dim3(1), dim3(256), 0, s, ids, n, cnt, V);
 }
-// behind the sampler of a step: thread j takes sequence j's pen_tok (left by the PN sampler: the sampled token, -1 for a forced one)
-// and counts it where the sequence has values; a sequence without values keeps no table
-__global__ __launch_bounds__(DTK_MAX_BATCH) void k_count_token(SampleArgs a) {
+// behind the sampler of a step: thread j takes sequence j's pen_tok (left by the PN sampler: the sampled token, -1 for a forced one),
+// counts it where the sequence has penalty values (a sequence without values keeps no table) and appends it to the sequence's DRY
+// history where it has a multiplier (d.hist null: a step without DRY); tokens in front of dry_start (DryLen::skip) are not kept
+__global__ __launch_bounds__(DTK_MAX_BATCH) void k_count_token(SampleArgs a, DryScanArgs d) {
   const int j = threadIdx.x;
   if (j >= (a.bs ? a.nslots : 1)) return;
   if (a.bs && !a.bs->active[j]) return;
   const int t = a.pen_tok[j];
   if (t < 0) return;
   a.pen_tok[j] = -1;
+  if (t >= a.V) return;
   const PenDev p = a.pen[j];
-  if ((p.pp == 0.f && p.fp == 0.f) || t >= a.V) return;
-  unsigned* w = reinterpret_cast<unsigned*>(const_cast<uint16_t*>(a.pen_cnt) + (size_t)j * a.pen_stride);
-  atomicAdd(w + (t >> 1), (t & 1) ? 0x10000u : 1u);
+  if (p.pp != 0.f || p.fp != 0.f) {
+    unsigned* w = reinterpret_cast<unsigned*>(const_cast<uint16_t*>(a.pen_cnt) + (size_t)j * a.pen_stride);
+    atomicAdd(w + (t >> 1), (t & 1) ? 0x10000u : 1u);
+  }
+  if (d.hist && d.dry[j].on) {
+    DryLen l = d.len[j];
+    if (l.skip > 0) l.skip--;
+    else if (l.n < d.hist_stride) { d.hist[(size_t)j * d.hist_stride + l.n] = t; l.n++; }
+    d.len[j] = l;
+  }
 }
-void launch_count_token(const SampleArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(k_count_token, dim3(1), dim3(DTK_MAX_BATCH), 0, s, a);
+void launch_count_token(const SampleArgs& a, const DryScanArgs& d, hipStream_t s) {
+  hipLaunchKernelGGL(k_count_token, dim3(1), dim3(DTK_MAX_BATCH), 0, s, a, d);
+}
+
+// ---- DRY (dtk_set_dry): the suffix-match scan in front of the sampler -------------------------------------------------------------
+// One block per sequence.  h[0, n) is the history, tail[k] = h[n-1-k].  Position i in [0, n-2] matches when h[i] == tail[0] and h[i+1] is
+// no breaker; its length L(i) is 1 + the number of k = 1, 2, ... with i-k >= 0, h[i-k] == tail[k] and tail[k] no breaker, capped at
+// DTK_DRY_MAX_MATCH; M[h[i+1]] = max L(i), kept only where it reaches `allowed`.  M is a byte per vocabulary entry; the maximum is taken
+// with a compare-and-swap on the word that holds the byte (vector atomics), so the result does not depend on the order of the threads.
+// Every id whose byte is set goes to the `touched` list (with repeats: at most one per position), which the NEXT scan of the sequence
+// zeroes first: a step clears in O(n), and no entry of one step survives into the next.  Latency-bound (a few thousand compares): the
+// scalars, the breakers and the list's length are requested together; the tail needs n, one more round trip.
+#define DRY_THREADS 256
+__global__ __launch_bounds__(DRY_THREADS) void k_dry_scan(DryScanArgs d) {
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int is_active = d.bs ? d.bs->active[q] : 1;
+  const DryDev* dv = d.dry + q;
+  const int on = dv->on, allowed = dv->allowed, nb = dv->n_brk;
+  const int n = d.len[q].n;
+  const int nt = d.n_touched[q];
+  const int brk = tid < DTK_DRY_MAX_BREAKERS ? dv->brk[tid] : -1;
+  if (!is_active || !on) return;      // (block-uniform)
+  const int32_t* h = d.hist + (size_t)q * d.hist_stride;
+  int32_t* tl = d.touched + (size_t)q * d.hist_stride;
+  unsigned* mw = reinterpret_cast<unsigned*>(d.m + (size_t)q * d.m_stride);
+  __shared__ int s_tail[DTK_DRY_MAX_MATCH];
+  __shared__ int s_tb[DTK_DRY_MAX_MATCH];       // tail[k] is a breaker
+  __shared__ int s_brk[DTK_DRY_MAX_BREAKERS];
+  __shared__ int s_nt;
+  const int tv = (tid < DTK_DRY_MAX_MATCH && tid < n) ? h[n - 1 - tid] : -1;
+  for (int i = tid; i < nt; i += DRY_THREADS) {
+    const int t = tl[i];
+    atomicAnd(mw + (t >> 2), ~(0xffu << ((t & 3) * 8)));
+  }
+  if (tid < DTK_DRY_MAX_BREAKERS) s_brk[tid] = brk;
+  if (tid < DTK_DRY_MAX_MATCH) s_tail[tid] = tv;
+  if (tid == 0) s_nt = 0;
+  __syncthreads();
+  auto is_brk = [&](int t) { bool b = false; for (int j = 0; j < nb; ++j) b = b || s_brk[j] == t; return b; };
+  if (tid < DTK_DRY_MAX_MATCH) s_tb[tid] = is_brk(tv) ? 1 : 0;
+  __syncthreads();
+  if (n < 2 || s_tb[0]) { if (tid == 0) d.n_touched[q] = 0; return; }
+  const int last = s_tail[0];
+  for (int i = tid; i <= n - 2; i += DRY_THREADS) {
+    if (h[i] != last) continue;
+    const int t = h[i + 1];
+    if (t < 0 || t >= d.V || is_brk(t)) continue;
+    int L = 1;
+    while (L < DTK_DRY_MAX_MATCH && i - L >= 0 && h[i - L] == s_tail[L] && !s_tb[L]) ++L;
+    if (L < allowed) continue;
+    unsigned* w = mw + (t >> 2);
+    const int sh = (t & 3) * 8;
+    unsigned old = atomicOr(w, 0u);      // (the word as the atomics above left it, not a cached copy)
+    while (((old >> sh) & 0xffu) < (unsigned)L) {
+      const unsigned prev = atomicCAS(w, old, (old & ~(0xffu << sh)) | ((unsigned)L << sh));
+      if (prev == old) break;
+      old = prev;
+    }
+    tl[atomicAdd(&s_nt, 1)] = t;
+  }
+  __syncthreads();
+  if (tid == 0) d.n_touched[q] = s_nt;
+}
+void launch_dry_scan(const DryScanArgs& d, hipStream_t s) {
+  hipLaunchKernelGGL(k_dry_scan, dim3(d.nslots), dim3(DRY_THREADS), 0, s, d);
 }

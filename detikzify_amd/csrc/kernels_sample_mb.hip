@@ -58,6 +58,7 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
     a.step_override = -1;
     a.mb += slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
+    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
   }
   return true;
 }
@@ -72,16 +73,21 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
   float pn_p = 0.f, pn_f = 0.f; bool pn = false;
   if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
   (void)pn_p; (void)pn_f; (void)pn;
+  const float* dpen = nullptr; bool dr = false;       // DRY (SampleArgs::dry) rides PN: pen[M] off z' where the id's match length M != 0
+  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
+  (void)dpen; (void)dr;
   if (base + MB_PER <= V && ((reinterpret_cast<uintptr_t>(a.logits + base) & 15) == 0)) {
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.logits + base);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.logits + base + 4);
     if constexpr (PN) {
       uint32_t cw[4] = {0u, 0u, 0u, 0u};      // the 8 counts: one 16-byte load (base is a multiple of 8, the table 16-byte aligned)
       if (pn) { const u32x4 c4 = *reinterpret_cast<const u32x4*>(a.pen_cnt + base); cw[0] = c4[0]; cw[1] = c4[1]; cw[2] = c4[2]; cw[3] = c4[3]; }
+      uint2 dw = make_uint2(0u, 0u);          // the 8 match lengths: one 8-byte load
+      if (dr) dw = *reinterpret_cast<const uint2*>(a.dry_m + base);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        e.z[i] = pen_apply(v0[i], (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f) * invT;
-        e.z[4 + i] = pen_apply(v1[i], (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f) * invT;
+        e.z[i] = dry_apply(pen_apply(v0[i], (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.x >> (8 * i)) & 0xffu, dpen) * invT;
+        e.z[4 + i] = dry_apply(pen_apply(v1[i], (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.y >> (8 * i)) & 0xffu, dpen) * invT;
       }
     } else {
 #pragma unroll
@@ -94,8 +100,16 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
   } else {
     if constexpr (PN) {
 #pragma unroll
-      for (int i = 0; i < MB_PER; ++i)
-        e.z[i] = (base + i < V) ? (pn ? pen_apply(a.logits[base + i], a.pen_cnt[base + i], pn_p, pn_f) : a.logits[base + i]) * invT : -INFINITY;
+      for (int i = 0; i < MB_PER; ++i) {
+        float z = -INFINITY;
+        if (base + i < V) {
+          z = a.logits[base + i];
+          if (pn) z = pen_apply(z, a.pen_cnt[base + i], pn_p, pn_f);
+          if (dr) z = dry_apply(z, a.dry_m[base + i], dpen);
+          z *= invT;
+        }
+        e.z[i] = z;
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < MB_PER; ++i) e.z[i] = (base + i < V) ? a.logits[base + i] * invT : -INFINITY;

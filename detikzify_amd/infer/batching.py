@@ -180,9 +180,10 @@ class BatchEngine:
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
-        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, check_penalties, check_truncation, text_image_key, text_key
+        from ..model.modeling import DRY_KEYS, DUMMY_IMAGE_KEY, adapter_text, check_dry, check_penalties, check_truncation, text_image_key, text_key
         check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
         pen = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
+        dry = check_dry(*(sampling.get(k) for k in DRY_KEYS))
         tids = adapter_text(text_ids) if text_ids is not None else None
         tkey = text_key(tids) if tids is not None else 0
         ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
@@ -257,7 +258,7 @@ class BatchEngine:
                 # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
                 # without them leaves the slot at 0 / 0
                 plain = {k: v for k, v in sampling.items()
-                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start")}
+                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start") + DRY_KEYS}
                 self.model.set_sampling(slot=slot, **plain)
                 ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
                 set_ext = getattr(self.model, "set_sampling_ext", None)
@@ -274,6 +275,14 @@ class BatchEngine:
                 elif pen[0] or pen[1]:
                     from .._lib import DtkError
                     raise DtkError("this device takes no presence / frequency penalty")
+                # DRY likewise (dry_start: the prompt length unless the sequence says otherwise); the fork / prefill / resume below
+                # builds the slot's history from the sequence's ids
+                set_dry = getattr(self.model, "set_dry", None)
+                if set_dry is not None:
+                    set_dry(dry[0], dry[1], dry[2], (int(ids.numel()) if dry[3] is None else dry[3]) if dry[0] else 0, dry[4], slot=slot)
+                elif dry[0]:
+                    from .._lib import DtkError
+                    raise DtkError("this device takes no DRY penalty")
                 if resume:
                     self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)

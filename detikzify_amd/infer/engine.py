@@ -144,6 +144,11 @@ class _ScriptedOps:
         def penalties(dev, slot, presence, frequency, start):
             model.set_penalties(float(presence), float(frequency), int(start), slot=slot)
 
+        def dry(dev, slot, dp):
+            d = dp.contents
+            model.set_dry(float(d.multiplier), float(d.base), int(d.allowed_length), int(d.start),
+                          tuple(int(d.breakers[i]) for i in range(int(d.n_breakers))), slot=slot)
+
         def fork(dev, a, b, n):
             model.kv_fork(a, b, n)
 
@@ -168,6 +173,7 @@ class _ScriptedOps:
         self.wait_lp = O.WAIT_LP(guard(wait_lp))       # handed to the engine by the first sequence(logprobs=True)
         self.sampling_ext = O.SAMPLING_EXT(guard(sampling_ext)) if hasattr(model, "set_sampling_ext") else None
         self.penalties = O.PENALTIES(guard(penalties)) if hasattr(model, "set_penalties") else None
+        self.dry = O.DRY(guard(dry)) if hasattr(model, "set_dry") else None
 
 
 def _has_adapter(model) -> bool:
@@ -221,6 +227,8 @@ class NativeBatchEngine:
                 rc = self.lib.dtk_engine_set_sampling_ext_op(self._h, self._scripted.sampling_ext)
             if rc == 0 and self._scripted.penalties is not None:
                 rc = self.lib.dtk_engine_set_penalties_op(self._h, self._scripted.penalties)
+            if rc == 0 and self._scripted.dry is not None and hasattr(self.lib, "dtk_engine_set_dry_op"):
+                rc = self.lib.dtk_engine_set_dry_op(self._h, self._scripted.dry)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
         if not pipeline:
@@ -409,12 +417,17 @@ class NativeBatchEngine:
             arr = getattr(s, field)
             for i, v in enumerate(vals):
                 arr[i] = v
-        from ..model.modeling import check_penalties, check_truncation
+        from ..model.modeling import DRY_KEYS, check_dry, check_penalties, check_truncation, dry_struct
         ext = _lib.DtkSamplingExt(*check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff")))
         has_ext = bool(ext.min_p or ext.epsilon_cutoff)
         pen_p, pen_f, pen_s = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
         has_pen = bool(pen_p or pen_f)
         pen_s = (n_ids if pen_s is None else pen_s) if has_pen else 0      # penalty_start: the prompt length unless the sequence says otherwise
+        dry_m, dry_b, dry_a, dry_s, dry_brk = check_dry(*(sampling.get(k) for k in DRY_KEYS))
+        has_dry = bool(dry_m)
+        dry = dry_struct(dry_m, dry_b, dry_a, (n_ids if dry_s is None else dry_s) if has_dry else 0, dry_brk)      # dry_start as penalty_start
+        if has_dry and not hasattr(self.lib, "dtk_engine_submit_dry"):
+            raise _lib.DtkError("this device takes no DRY penalty")
         stops = [int(t) for t in stop_ids if int(t) >= 0][:8]
         j.n_stop = len(stops)
         for i, t in enumerate(stops):
@@ -468,7 +481,11 @@ class NativeBatchEngine:
             self.free.remove(slot)
             if owner is not None:
                 self.last_slot[owner] = slot
-            if has_pen:       # the sequence's presence / frequency penalty (and its min_p / epsilon_cutoff) go with its join (text or not)
+            if has_dry:       # the sequence's DRY (and its penalties, min_p / epsilon_cutoff) go with its join (text or not)
+                tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
+                rc = self.lib.dtk_engine_submit_dry(self._h, C.byref(j), C.byref(ext), C.c_float(pen_p), C.c_float(pen_f), int(pen_s), C.byref(dry),
+                                                    tp, int(tids.numel()) if tids is not None else 0, C.c_uint64(tkey), C.byref(ticket))
+            elif has_pen:     # the sequence's presence / frequency penalty (and its min_p / epsilon_cutoff) go with its join (text or not)
                 tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
                 rc = self.lib.dtk_engine_submit_pen(self._h, C.byref(j), C.byref(ext), C.c_float(pen_p), C.c_float(pen_f), int(pen_s), tp,
                                                     int(tids.numel()) if tids is not None else 0, C.c_uint64(tkey), C.byref(ticket))

@@ -141,11 +141,16 @@ class DetikzifyGenerator:
                  metric=None, compile_timeout: Optional[int] = 60, mcts_timeout: Optional[int] = None,
                  streamer=None, control: Optional[ExplicitAbort] = None, exploration: float = 0.6,
                  strict: bool = False, document_class: Type[TikzDocument] = TikzDocument, processed=None, rng=None,
-                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None, **gen_kwargs):
+                 presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
+                 dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None, dry_allowed_length: Optional[int] = None,
+                 dry_sequence_breakers=None, **gen_kwargs):
         """presence_penalty / frequency_penalty (model.generate's; None / 0 = off): counted from the end of the image prompt on, so a
         rollout that continues a node of the tree penalises the whole program text so far, however its slot got there"""
         if presence_penalty or frequency_penalty:
             gen_kwargs = {**gen_kwargs, "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty}
+        if dry_multiplier:      # DRY (model.generate's) likewise: its history starts at the end of the image prompt
+            gen_kwargs = {**gen_kwargs, "dry_multiplier": dry_multiplier, "dry_base": dry_base, "dry_allowed_length": dry_allowed_length,
+                          "dry_sequence_breakers": dry_sequence_breakers}
         self.model, self.processor = model, processor
         self.image, self.text, self.metric = image, text, metric
         self.compile_timeout, self.mcts_timeout = compile_timeout, mcts_timeout
@@ -228,6 +233,8 @@ class DetikzifyGenerator:
         options = {**self.gen_kwargs, **gen_kwargs}
         if (options.get("presence_penalty") or options.get("frequency_penalty")) and options.get("penalty_start") is None:
             options["penalty_start"] = int(self.montecarlo.root_node.token_ids.numel())       # the program text so far counts, the prompt does not
+        if options.get("dry_multiplier") and options.get("dry_start") is None:
+            options["dry_start"] = int(self.montecarlo.root_node.token_ids.numel())           # likewise: a rollout sees the whole program text so far
         budget = options.get("max_length", self.model.generation_config.to_dict().get("max_length"))
         n = input_ids.numel()
         finished = n > 0 and input_ids[-1] == unwrap(self.processor).tokenizer.eos_token_id

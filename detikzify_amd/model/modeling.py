@@ -193,6 +193,45 @@ def check_penalties(presence_penalty: Optional[float], frequency_penalty: Option
     return out[0], out[1], penalty_start
 
 
+DRY_KEYS = ("dry_multiplier", "dry_base", "dry_allowed_length", "dry_start", "dry_sequence_breakers")
+
+
+def check_dry(dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None, dry_allowed_length: Optional[int] = None,
+              dry_start: Optional[int] = None, dry_sequence_breakers=None, vocab: Optional[int] = None):
+    """the `dry_*` arguments of generate / sample -> (multiplier, base, allowed_length, start, breakers): multiplier 0.0 = off (None),
+    base 1.75 and allowed_length 2 by default, start None = the caller's default (generate: the prompt length), breakers a tuple of at
+    most 16 token ids (in [0, vocab) where the vocabulary is known).  Out of range: ValueError before anything runs"""
+    def number(name, v, default, lo, hi):
+        x = default if v is None else v
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not (lo <= x <= hi):      # (NaN fails the comparison)
+            raise ValueError(f"`{name}` has to be a float in the [{lo}, {hi}] interval, but is {v}")
+        return float(x)
+    m = number("dry_multiplier", dry_multiplier, 0.0, 0.0, 100.0)
+    b = number("dry_base", dry_base, 1.75, 1.0, 8.0)
+    a = 2 if dry_allowed_length is None else dry_allowed_length
+    if isinstance(a, bool) or not isinstance(a, int) or not (1 <= a <= _lib.DTK_DRY_MAX_MATCH):
+        raise ValueError(f"`dry_allowed_length` has to be an integer in [1, {_lib.DTK_DRY_MAX_MATCH}], but is {dry_allowed_length}")
+    if dry_start is not None:
+        if isinstance(dry_start, bool) or not isinstance(dry_start, int) or dry_start < 0:
+            raise ValueError(f"`dry_start` has to be an integer >= 0, but is {dry_start}")
+    if isinstance(dry_sequence_breakers, (str, bytes)):
+        raise ValueError("`dry_sequence_breakers` has to be a list of token ids, not a string")
+    brk = tuple(dry_sequence_breakers) if dry_sequence_breakers is not None else ()
+    if len(brk) > _lib.DTK_DRY_MAX_BREAKERS:
+        raise ValueError(f"`dry_sequence_breakers` takes at most {_lib.DTK_DRY_MAX_BREAKERS} token ids, but has {len(brk)}")
+    for t in brk:
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError(f"`dry_sequence_breakers` has to hold token ids in [0, vocabulary), but holds {t!r}")
+    return m, b, a, dry_start, brk
+
+
+def dry_struct(multiplier: float, base: float, allowed_length: int, start: int, breakers=()) -> "_lib.DtkDry":
+    d = _lib.DtkDry(float(multiplier), float(base), int(allowed_length), int(start), len(breakers))
+    for i, t in enumerate(breakers):
+        d.breakers[i] = int(t)
+    return d
+
+
 def _is_neutral(value: Any, neutral: Any) -> bool:
     if neutral is None:
         return value is None
@@ -848,6 +887,32 @@ class DetikzifyForCausalLM:
         else:
             self._check(fn(self._ctx, int(slot), presence, frequency, start), "dtk_set_penalties_slot")
 
+    def set_dry(self, multiplier: float = 0.0, base: float = 1.75, allowed_length: int = 2, start: int = 0, breakers=(),
+                slot: Optional[int] = None):
+        """DRY of the sequence the last set_sampling configured (dtk_set_dry / dtk_set_dry_slot): the token that would extend a verbatim
+        repetition of length M >= allowed_length of the sequence's own text from position `start` on has multiplier * base^(M -
+        allowed_length) taken off its logit.  set_sampling itself resets it to off"""
+        m, b, a, st, brk = check_dry(multiplier, base, allowed_length, int(start), breakers, int(self.config.vocab))
+        fn = getattr(self.lib, "dtk_set_dry" if slot is None else "dtk_set_dry_slot", None)
+        if fn is None:          # a device without the two calls has nothing to reset
+            if m:
+                raise _lib.DtkError("this device takes no DRY penalty")
+            return
+        d = dry_struct(m, b, a, st, brk)
+        if slot is None:
+            self._check(fn(self._ctx, C.byref(d)), "dtk_set_dry")
+        else:
+            self._check(fn(self._ctx, int(slot), C.byref(d)), "dtk_set_dry_slot")
+
+    def dry_history(self, slot: Optional[int] = None) -> torch.Tensor:
+        """diagnostic: the token history the sequence's next DRY scan will read (empty while DRY is off)"""
+        cap = int(self.lib.dtk_max_positions(self._ctx))
+        out = (C.c_int32 * cap)()
+        n = int(self.lib.dtk_dry_history(self._ctx, -1 if slot is None else int(slot), out, cap))
+        if n < 0:
+            self._check(n, "dtk_dry_history")
+        return torch.tensor(list(out[:n]), dtype=torch.int64)
+
     def token_counts(self, slot: Optional[int] = None) -> torch.Tensor:
         """diagnostic: the count table the sequence's next step will read (uint16 per vocabulary entry, as int32)"""
         V = int(self.config.vocab)
@@ -1037,7 +1102,9 @@ class DetikzifyForCausalLM:
                  inputs: Optional[torch.Tensor] = None, sequence_owner: Optional[int] = None, return_logprobs: bool = False,
                  top_logprobs: Optional[int] = None, min_p: Optional[float] = None, epsilon_cutoff: Optional[float] = None,
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
-                 penalty_start: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 penalty_start: Optional[int] = None, dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None,
+                 dry_allowed_length: Optional[int] = None, dry_start: Optional[int] = None, dry_sequence_breakers=None,
+                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1055,6 +1122,12 @@ class DetikzifyForCausalLM:
         among the sequence's tokens from position penalty_start on (default: the prompt length, so only generated tokens count) has
         presence + frequency * c taken off its raw logit in front of the whole sampler chain, greedy included.  The
         reported log-probabilities stay the model's own.  HF's repetition_penalty stays refused.
+
+        dry_multiplier / dry_base / dry_allowed_length / dry_start / dry_sequence_breakers: DRY (text-generation-webui, llama.cpp): the
+        token that would extend a verbatim repetition of M >= dry_allowed_length (default 2) tokens of the sequence's own text from
+        position dry_start on (default: the prompt length) has dry_multiplier * dry_base^(M - dry_allowed_length) taken off its logit,
+        behind the presence / frequency pair and in front of everything else; dry_multiplier 0 / None = off; breakers
+        are token ids across which no repetition is matched.  The reported log-probabilities stay the model's own.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1087,6 +1160,13 @@ class DetikzifyForCausalLM:
             getattr(gc, "presence_penalty", None) if presence_penalty is None else presence_penalty,
             getattr(gc, "frequency_penalty", None) if frequency_penalty is None else frequency_penalty,
             getattr(gc, "penalty_start", None) if penalty_start is None else penalty_start)
+        dry_multiplier, dry_base, dry_allowed_length, dry_start, dry_sequence_breakers = check_dry(
+            getattr(gc, "dry_multiplier", None) if dry_multiplier is None else dry_multiplier,
+            getattr(gc, "dry_base", None) if dry_base is None else dry_base,
+            getattr(gc, "dry_allowed_length", None) if dry_allowed_length is None else dry_allowed_length,
+            getattr(gc, "dry_start", None) if dry_start is None else dry_start,
+            getattr(gc, "dry_sequence_breakers", None) if dry_sequence_breakers is None else dry_sequence_breakers,
+            int(self.config.vocab))
         do_sample = gc.do_sample if do_sample is None else do_sample
         temperature = gc.temperature if temperature is None else temperature
         top_p = gc.top_p if top_p is None else top_p
@@ -1094,6 +1174,10 @@ class DetikzifyForCausalLM:
         T = ids.shape[1]
         if penalty_start is None:
             penalty_start = T
+        if dry_start is None:
+            dry_start = T
+        dry = dict(dry_multiplier=dry_multiplier, dry_base=dry_base, dry_allowed_length=dry_allowed_length, dry_start=dry_start,
+                   dry_sequence_breakers=dry_sequence_breakers) if dry_multiplier else {}
         if max_new_tokens is not None:
             max_length = T + int(max_new_tokens)
         elif max_length is None:
@@ -1190,7 +1274,7 @@ class DetikzifyForCausalLM:
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or (),
                     **({"min_p": min_p, "epsilon_cutoff": epsilon_cutoff} if (min_p or epsilon_cutoff) else {}),
                     **({"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "penalty_start": penalty_start}
-                       if (presence_penalty or frequency_penalty) else {})),
+                       if (presence_penalty or frequency_penalty) else {}), **dry),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
                     **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
@@ -1211,6 +1295,8 @@ class DetikzifyForCausalLM:
                     self.set_sampling_ext(min_p, epsilon_cutoff)
                 if presence_penalty or frequency_penalty:       # (likewise; the prefill below builds the count table)
                     self.set_penalties(presence_penalty, frequency_penalty, penalty_start)
+                if dry_multiplier:       # (likewise; the prefill below builds the history)
+                    self.set_dry(dry_multiplier, dry_base, dry_allowed_length, dry_start, dry_sequence_breakers)
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
                     if topk:

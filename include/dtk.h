@@ -803,6 +803,60 @@ int  dtk_engine_submit_pen(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x
                            const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out);
 int  dtk_engine_set_penalties_op(dtk_engine* e, int (*set_penalties_slot)(void* dev, int slot, float presence, float frequency, int start));
 
+/* DRY ("don't repeat yourself"; additive, ABI 7): a penalty on the token that would extend a verbatim repetition of the sequence's own
+ * recent text, growing exponentially with the length of the repetition.  Per sequence:
+ *   multiplier m   finite, in [0, 100]; 0 = off            base b            finite, in [1, 8]
+ *   allowed_length a   in [1, 64]                           start s >= 0      with the meaning of penalty_start
+ *   breakers       at most DTK_DRY_MAX_BREAKERS ids in [0, V), the set B
+ * Penalty table (host, IEEE double, repeated multiplication; the device only looks it up): pen[L] = 0 for L < a; p = (double)m; for
+ * L = a .. DTK_DRY_MAX_MATCH: pen[L] = (float)min(p, 1e30), p *= (double)b.
+ * History h[0, n): the sequence's ids at positions [s, next_pos) — the prompt from s on and every token sampled or forced since; a
+ * property of the token list, however the slot got there.  If n < 2 or h[n-1] in B nothing is penalised.  Otherwise, for every i in
+ * [0, n-2] with h[i] == h[n-1] and h[i+1] not in B:  L(i) = the largest L in [1, 64] such that for every k in [1, L): i-k >= 0,
+ * h[i-k] == h[n-1-k] and h[n-1-k] not in B (overlap with the tail is allowed).  M[t] = max L(i) over the i with h[i+1] == t, else 0.
+ * z'[t] = z[t] - pen[M[t]] where M[t] >= a, else the untouched bits of z[t]; behind the presence / frequency subtraction where both
+ * are on (two fp32 subtractions in that order), in front of the suppression lists, the temperature, top-k, top-p, min-p, epsilon and
+ * the draw; greedy takes the arg-max of z' (lowest id on ties).  logprob, the top-k records and their logsumexp stay over the RAW
+ * logits; sample_logprob and filtered_probs_out are over the final kept set.  A sequence with m = 0 reads no DRY state and draws what it
+ * draws alone.  State (allocated with the first m != 0, together with the penalties' per-sequence records, not their tables): an int32 history
+ * and its length per sequence, rebuilt wherever the host redefines the sequence (the places of the count tables) and appended to by the
+ * trailing kernel behind the sampler; a byte table of M per sequence, written by k_dry_scan in front of every step's sampler.
+ *   dtk_set_dry / dtk_set_dry_slot   called AFTER dtk_set_sampling / dtk_set_sampling_slot, which reset DRY to off.  DTK_ERR_ARG outside
+ *                             the ranges or on NaN; DTK_ERR_STATE while steps of the sequence are unread.  A sequence that exists
+ *                             already gets its history rebuilt from its ids, a resumed slot's pending forced id included.
+ *   dtk_dry_history           diagnostic: the length of the history the sequence's next scan will read (slot -1: the single sequence),
+ *                             its first n_max ids to ids_out; 0 while the feature is off; a negative error code otherwise.
+ *   dtk_dry_state_bytes       diagnostic: the device and pinned bytes the DRY state holds; 0 until a sequence of the context has had m != 0.
+ *   dtk_op_dry_scan           k_dry_scan over a given history (d->start is not used); with history2 a second scan on the state the
+ *                             first left.  Returns the number of ids with M != 0 in the whole table behind the last scan; the first
+ *                             n_max, ascending, go to ids_out / m_out.  A negative error code otherwise.
+ *   dtk_op_sample_dry         dtk_op_sample_pen with a history and a dtk_dry: scan, then the sampler.
+ *   dtk_engine_submit_dry     dtk_engine_submit_pen whose sequence also carries a dtk_dry record (d; NULL: off); dtk_engine_create wires
+ *                             dtk_set_dry_slot itself, an engine of dtk_engine_create_ops gets the op through dtk_engine_set_dry_op, and
+ *                             without one a join with m != 0 fails in submit with DTK_ERR_STATE.  With the op every join calls it. */
+#define DTK_DRY_MAX_MATCH 64
+#define DTK_DRY_MAX_BREAKERS 16
+typedef struct dtk_dry {
+  float multiplier;
+  float base;
+  int32_t allowed_length;
+  int32_t start;
+  int32_t n_breakers;
+  int32_t breakers[DTK_DRY_MAX_BREAKERS];
+} dtk_dry;
+int  dtk_set_dry(dtk_ctx* ctx, const dtk_dry* d);
+int  dtk_set_dry_slot(dtk_ctx* ctx, int slot, const dtk_dry* d);
+int  dtk_dry_history(dtk_ctx* ctx, int slot, int32_t* ids_out, int n_max);
+int64_t dtk_dry_state_bytes(const dtk_ctx* ctx);
+int  dtk_op_dry_scan(dtk_ctx* ctx, int V, const int64_t* history, int n_history, const int64_t* history2 /* or NULL */, int n_history2,
+                     const dtk_dry* d, int32_t* ids_out, uint8_t* m_out, int n_max);
+int  dtk_op_sample_dry(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
+                       float* lp_out /* [2] or NULL */, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency,
+                       const int64_t* counted_ids, int n_counted, const int64_t* history, int n_history, const dtk_dry* d);
+int  dtk_engine_submit_dry(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency, int start,
+                           const dtk_dry* d /* or NULL */, const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out);
+int  dtk_engine_set_dry_op(dtk_engine* e, int (*set_dry_slot)(void* dev, int slot, const dtk_dry* d));
+
 #ifdef __cplusplus
 }
 #endif
