@@ -234,6 +234,8 @@ SYMBOLS = {
     "dtk_w13_pack_host": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "dtk_w13_unpack_host": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "dtk_w13_op_bad_rows": (C.c_int, [_P]),
+    "dtk_w13_row_bytes_host": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "dtk_w13_flagged_rows": (C.c_int, [_P, C.c_int]),
     "dtk_op_gemv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P]),
     "dtk_op_gemv_mv": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     # additive (ABI stays 7): dtk_op_gemv on MXFP4 weights (the loader's quantiser + the decode kernel); last = de-quantised W or NULL

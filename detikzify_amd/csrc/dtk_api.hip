@@ -197,11 +197,13 @@ struct dtk_ctx {
   float* s_lm_head = nullptr;
   // 13-bit planes of the bf16 rows for the single-sequence step (w13.h): packed lazily by ensure_w13 from the bf16 masters, which stay
   int w13 = W13_DEFAULT;     // dtk_set_option "w13"
+  int w13_nz = 1;            // dtk_set_option "w13_nz": 0 = the packer flags every row (W13_ZROW), so every row takes the general decode
   bool w13_ready = false;    // the planes match the masters (load_tensor / fill_synthetic clear it)
   uint8_t *p13_lm_head = nullptr, *h13_lm_head = nullptr;
   unsigned* w13_bad = nullptr;                      // device counter of the packer
   int w13_op_bad_rows = -1;                         // unpackable rows of the last dtk_op_gemv_role call that packed planes (-1: none yet)
   uint32_t w13_packed = 0, w13_unpacked = 0, w13_bad_rows = 0;   // matrices with / without planes, unpackable rows (dtk_stats.w13_counts)
+  uint32_t w13_zrows[5] = {0, 0, 0, 0, 0};         // rows with W13_ZROW in their byte, per role of dtk_bench_gemv (dtk_w13_flagged_rows)
   uint64_t cached_image_key = 0;
   bool have_image = false;
   // ---- batched decode (dtk_*_slot / dtk_decode_batch_*): up to 64 decoding slots (+1) with their own KV
@@ -1196,7 +1198,7 @@ static void w13_set_stats(dtk_ctx* c) {
   const uint32_t rows = c->w13_bad_rows > 4095u ? 4095u : c->w13_bad_rows;
   c->stats.w13_counts = (c->w13_packed & 1023u) | ((c->w13_unpacked & 1023u) << 10) | (rows << 20);
 }
-static int w13_pack_one(dtk_ctx* c, int pro, int epi, const bf16_t* W, int N, int K, uint8_t** planes, uint8_t** hb) {
+static int w13_pack_one(dtk_ctx* c, int role, int pro, int epi, const bf16_t* W, int N, int K, uint8_t** planes, uint8_t** hb) {
   GemvArgs g{};
   g.N = N; g.K = K; g.d = c->d; g.ff = c->ff; g.hd = c->hd;
   if (!gemv_w13_takes(pro, epi, g)) {      // the role's bf16 kernel folds in an order no 13-bit shape has (a split-K default): it stays bf16
@@ -1207,7 +1209,7 @@ static int w13_pack_one(dtk_ctx* c, int pro, int epi, const bf16_t* W, int N, in
   if (!*planes) HIPCHK(c, hipMalloc((void**)planes, (size_t)N * w13_row_bytes(K)));
   if (!*hb) HIPCHK(c, hipMalloc((void**)hb, (size_t)N));
   HIPCHK(c, hipMemsetAsync(c->w13_bad, 0, sizeof(unsigned), c->stream));
-  launch_pack_w13_rows(W, *planes, *hb, c->w13_bad, N, K, c->stream);
+  launch_pack_w13_rows(W, *planes, *hb, c->w13_bad, N, K, !c->w13_nz, c->stream);
   unsigned bad = 0;
   HIPCHK(c, hipMemcpyAsync(&bad, c->w13_bad, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1215,7 +1217,12 @@ static int w13_pack_one(dtk_ctx* c, int pro, int epi, const bf16_t* W, int N, in
     (void)hipFree(*planes); *planes = nullptr;
     (void)hipFree(*hb); *hb = nullptr;
     c->w13_unpacked++; c->w13_bad_rows += bad;
-  } else c->w13_packed++;
+  } else {
+    c->w13_packed++;
+    std::vector<uint8_t> bytes((size_t)N);      // the row bytes: how many rows take the general decode (a figure for the tests and tools)
+    HIPCHK(c, hipMemcpy(bytes.data(), *hb, (size_t)N, hipMemcpyDeviceToHost));
+    for (uint8_t b : bytes) c->w13_zrows[role] += (b & W13_ZROW) ? 1u : 0u;
+  }
   return DTK_OK;
 }
 static void w13_free(dtk_ctx* c);
@@ -1228,16 +1235,17 @@ int ensure_w13(dtk_ctx* c) {
   if (!w13_on(c) || c->w13_ready) return DTK_OK;
   if (!c->w13_bad) HIPCHK(c, hipMalloc((void**)&c->w13_bad, sizeof(unsigned)));
   c->w13_packed = c->w13_unpacked = c->w13_bad_rows = 0;
+  for (uint32_t& z : c->w13_zrows) z = 0;
   const int qkvn = c->d + 2 * c->KVH * c->hd;
   for (int l = 0; l < c->L; ++l) {
     LayerW& w = c->layers[l];
-    int rc = w13_pack_one(c, PRO_RMSNORM, EPI_QKV, w.wqkv, qkvn, c->d, &w.p13_wqkv, &w.h13_wqkv);
-    if (!rc) rc = w13_pack_one(c, PRO_ATTN, EPI_RESID, w.wo, c->d, c->d, &w.p13_wo, &w.h13_wo);
-    if (!rc) rc = w13_pack_one(c, PRO_RMSNORM, EPI_SWIGLU, w.wgu, 2 * c->ff, c->d, &w.p13_wgu, &w.h13_wgu);
-    if (!rc) rc = w13_pack_one(c, PRO_COPY, EPI_RESID, w.wdown, c->d, c->ff, &w.p13_wdown, &w.h13_wdown);
+    int rc = w13_pack_one(c, 0, PRO_RMSNORM, EPI_QKV, w.wqkv, qkvn, c->d, &w.p13_wqkv, &w.h13_wqkv);
+    if (!rc) rc = w13_pack_one(c, 1, PRO_ATTN, EPI_RESID, w.wo, c->d, c->d, &w.p13_wo, &w.h13_wo);
+    if (!rc) rc = w13_pack_one(c, 2, PRO_RMSNORM, EPI_SWIGLU, w.wgu, 2 * c->ff, c->d, &w.p13_wgu, &w.h13_wgu);
+    if (!rc) rc = w13_pack_one(c, 3, PRO_COPY, EPI_RESID, w.wdown, c->d, c->ff, &w.p13_wdown, &w.h13_wdown);
     if (rc) { w13_free(c); return rc; }
   }
-  int rc = w13_pack_one(c, PRO_RMSNORM, EPI_LOGITS, c->lm_head, c->V, c->d, &c->p13_lm_head, &c->h13_lm_head);
+  int rc = w13_pack_one(c, 4, PRO_RMSNORM, EPI_LOGITS, c->lm_head, c->V, c->d, &c->p13_lm_head, &c->h13_lm_head);
   if (rc) { w13_free(c); return rc; }
   c->w13_ready = true;
   w13_set_stats(c);
@@ -1253,6 +1261,7 @@ static void w13_free(dtk_ctx* c) {
   if (c->h13_lm_head) { (void)hipFree(c->h13_lm_head); c->h13_lm_head = nullptr; }
   c->w13_ready = false;
   c->w13_packed = c->w13_unpacked = c->w13_bad_rows = 0;
+  for (uint32_t& z : c->w13_zrows) z = 0;
 }
 
 void ensure_tiled_weights(dtk_ctx* c);
@@ -3122,7 +3131,7 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
       tmp13.h.push_back(hh);
       unsigned bad = 0;
       HIPCHK(c, hipMemsetAsync(c->w13_bad, 0, sizeof(unsigned), s));
-      launch_pack_w13_rows(w.wo, pp, hh, c->w13_bad, c->d, c->d, s);
+      launch_pack_w13_rows(w.wo, pp, hh, c->w13_bad, c->d, c->d, !c->w13_nz, s);
       HIPCHK(c, hipMemcpyAsync(&bad, c->w13_bad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
       HIPCHK(c, hipStreamSynchronize(s));
       if (bad) return fail(c, DTK_ERR_STATE, "dtk_bench_gemv: o_proj of layer %d has %u unpackable row(s)", l, bad);
@@ -3210,7 +3219,15 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
       set_weight_bytes(c);
     }
   }
-  else if (!strcmp(name, "logprobs")) {     // every sampled token comes with (logprob, sample_logprob): the LP sampler instantiations + one more D2H copy per step
+  else if (!strcmp(name, "w13_nz")) {  // 1: rows without a zero code take the short decode (w13.h: W13_ZROW); 0: the packer flags every row (same results; tools/bench_w13.py)
+    if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "w13_nz must be 0 or 1");
+    if (value != c->w13_nz) {
+      if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "w13_nz: %d single-sequence decode step(s) are unread", (int)(c->launched - c->waited));
+      c->w13_nz = value;
+      if (c->w13_ready) { c->w13_ready = false; drop_graph(c); }   // the planes' row bytes are written again before the next single-sequence step
+    }
+  }
+  else if (!strcmp(name, "logprobs")) {    // every sampled token comes with (logprob, sample_logprob): the LP sampler instantiations + one more D2H copy per step
     if (value != 0 && value != 1) return fail(c, DTK_ERR_ARG, "logprobs must be 0 or 1");
     if (value == 0 && c->top_logprobs) return fail(c, DTK_ERR_STATE, "logprobs: top_logprobs = %d needs it (set \"top_logprobs\" to 0 first)", c->top_logprobs);
     if ((value != 0) != (c->logprobs != 0)) {
@@ -4234,7 +4251,7 @@ int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* 
   if (f13) {
     unsigned bad = 0;
     HIPCHK(c, hipMemsetAsync(dbad, 0, sizeof(unsigned), s));
-    launch_pack_w13_rows(g.W, dWp, dWh, dbad, N, K, s);
+    launch_pack_w13_rows(g.W, dWp, dWh, dbad, N, K, !c->w13_nz, s);
     HIPCHK(c, hipMemcpyAsync(&bad, dbad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipMemsetAsync(dbad, scratch_fill, sizeof(unsigned), s));
@@ -4531,6 +4548,12 @@ int dtk_w13_unpack_host(const uint8_t* planes, const uint8_t* hb, int N, int K, 
   return DTK_OK;
 }
 int dtk_w13_op_bad_rows(dtk_ctx* c) { return c ? c->w13_op_bad_rows : -1; }
+int dtk_w13_flagged_rows(dtk_ctx* c, int role) { return (c && role >= 0 && role < 5 && c->w13_ready) ? (int)c->w13_zrows[role] : -1; }
+int dtk_w13_row_bytes_host(const uint16_t* W, int N, int K, uint8_t* bytes) {
+  if (!W || !bytes || N < 0 || K < 8 || (K & 7)) return DTK_ERR_ARG;
+  for (int r = 0; r < N; ++r) bytes[r] = (uint8_t)w13_row_byte(W + (size_t)r * K, K);
+  return DTK_OK;
+}
 
 // ---- the batched decode GEMV family alone (dtk_op_gemv_b / dtk_op_gemv_bkp): host operands into the op scratch, the step's own
 // launchers (launch_retile / launch_retile_f8, launch_rmsnorm_b, launch_gemv_b, launch_gemv_bkp, launch_resid_norm_b) unchanged

@@ -139,8 +139,9 @@ __device__ __forceinline__ void gemv_fma_f4(float (&acc)[NR], const u32x4 (&w)[N
 // 13-bit planes of a bf16 row (w13.h): a stage is U k-iterations (U a multiple of 4 = whole sign blocks): per row U / 2 dwordx4 of low
 // bytes, U / 2 dwordx2 of exponent codes and U / 4 dwords of signs.  The operands rebuilt in registers are the bf16 row's own bits, and
 // a lane folds chunk lane, lane + 64, ... with the same four chained v_dot2c_f32_bf16 as gemv_fma, so every fp32 sum equals the bf16
-// kernel's.  x lies linearly in LDS as for bf16.  Nothing in here branches on data: the only conditions are the wave-uniform "unit
-// inside the row" and gemv_fma's "chunk inside x".
+// kernel's.  x lies linearly in LDS as for bf16.  No lane branches on data: the conditions are the wave-uniform "unit inside the row",
+// gemv_fma's "chunk inside x" and the caller's choice of NZ, which is uniform too (a wave owns whole rows: k_gemv takes the short decode
+// when none of the wave's NR rows has W13_ZROW in its row byte).
 typedef __attribute__((ext_vector_type(2))) unsigned short u16x2_t;
 
 // four exponent codes (one per byte, 0 .. 15) -> the four high bytes without their signs: code ? lo + code : 0.  lo2 = lo | lo << 16;
@@ -151,10 +152,14 @@ __device__ __forceinline__ uint32_t w13_high4(uint32_t codes, uint32_t lo2) {
   return __builtin_bit_cast(uint32_t, r);
 }
 
-// one chunk: la / lb = the low bytes of weights 0..3 / 4..7, n = the 8 codes, s = the block's sign dword, i = k-iteration in the block
-__device__ __forceinline__ float dot8_w13(uint32_t la, uint32_t lb, uint32_t n, uint32_t s, int i, uint32_t lo2, const u32x4& x, float c) {
-  const uint32_t he = w13_high4(n & 0x0f0f0f0fu, lo2) | ((s << (7 - 2 * i)) & 0x80808080u);
-  const uint32_t ho = w13_high4((n >> 4) & 0x0f0f0f0fu, lo2) | ((s << (6 - 2 * i)) & 0x80808080u);
+// one chunk: la / lb = the low bytes of weights 0..3 / 4..7, n = the 8 codes, s = the block's sign dword, i = k-iteration in the block,
+// lo4 = lo in every byte.  NZ: the row has no code 0 (w13.h: W13_ZROW clear), so the high bytes are codes + lo4 (lo + 15 < 128: no carry
+// between bytes) - one v_add where the general rule needs four operations; both rebuild the row's own bits
+template <bool NZ>
+__device__ __forceinline__ float dot8_w13(uint32_t la, uint32_t lb, uint32_t n, uint32_t s, int i, uint32_t lo4, const u32x4& x, float c) {
+  const uint32_t ce = n & 0x0f0f0f0fu, co = (n >> 4) & 0x0f0f0f0fu;
+  const uint32_t he = (NZ ? ce + lo4 : w13_high4(ce, lo4 & 0x00ff00ffu)) | ((s << (7 - 2 * i)) & 0x80808080u);
+  const uint32_t ho = (NZ ? co + lo4 : w13_high4(co, lo4 & 0x00ff00ffu)) | ((s << (6 - 2 * i)) & 0x80808080u);
   // v_perm_b32: bytes 0..3 of the selector space are the second operand (low bytes), 4..7 the first (high bytes)
   c = dot2(__builtin_amdgcn_perm(he, la, 0x05010400u), x[0], c);
   c = dot2(__builtin_amdgcn_perm(he, la, 0x07030602u), x[1], c);
@@ -203,9 +208,9 @@ __device__ __forceinline__ void gemv_load_w13(u32x4 (&wl)[NR][U / 2], u32x2 (&wn
   }
 }
 
-template <int NR, int U>
+template <int NR, int U, bool NZ>
 __device__ __forceinline__ void gemv_fma_w13(float (&acc)[NR], const u32x4 (&wl)[NR][U / 2], const u32x2 (&wn)[NR][U / 2],
-                                             const uint32_t (&ws)[NR][U / 4], const uint32_t (&lo2)[NR],
+                                             const uint32_t (&ws)[NR][U / 4], const uint32_t (&lo4)[NR],
                                              const u32x4* xs, int g, int lane, int K8) {
   const bool full = 64 * (g * U + U) <= K8;
 #pragma unroll
@@ -216,7 +221,7 @@ __device__ __forceinline__ void gemv_fma_w13(float (&acc)[NR], const u32x4 (&wl)
 #pragma unroll
     for (int r = 0; r < NR; ++r) {
       const u32x4& l = wl[r][u >> 1];
-      acc[r] = dot8_w13((u & 1) ? l[2] : l[0], (u & 1) ? l[3] : l[1], wn[r][u >> 1][u & 1], ws[r][u >> 2], u & 3, lo2[r], xv, acc[r]);
+      acc[r] = dot8_w13<NZ>((u & 1) ? l[2] : l[0], (u & 1) ? l[3] : l[1], wn[r][u >> 1][u & 1], ws[r][u >> 2], u & 3, lo4[r], xv, acc[r]);
     }
   }
 }

@@ -42,7 +42,7 @@ struct GemvArgs {
   // 2i + 1 high nibble; rows zero-padded to whole 32-weight blocks), S4 = E8M0 block scales [N][ceil(K/32)].  No row scale.
   const uint8_t* W4 = nullptr;
   const uint8_t* S4 = nullptr;
-  // 13-bit planes of W (w13.h), or null (then W4 / W8 / W decide): Wp = [N] rows of w13_row_bytes(K), Wh = the rows' hb bytes [N].  The
+  // 13-bit planes of W (w13.h), or null (then W4 / W8 / W decide): Wp = [N] rows of w13_row_bytes(K), Wh = the rows' bytes [N] (hb | W13_ZROW).  The
   // kernel rebuilds W's own bits, so the results are the bf16 kernel's
   const uint8_t* Wp = nullptr;
   const uint8_t* Wh = nullptr;
@@ -54,7 +54,7 @@ void launch_gemv_variant(int pro, int epi, int variant, const GemvArgs& a, hipSt
 void launch_gemv_w13_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s);   // ... in the shape the caller names (gemv_w13_has says which exist)
 bool gemv_w13_has(int pro, int epi, int variant);
 bool gemv_w13_takes(int pro, int epi, const GemvArgs& a);   // launch_gemv would stream a.Wp for this role at this shape (it keeps the bf16 kernel's fold order)
-void launch_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, hipStream_t s);   // w13.h planes of [N][K] bf16 rows; *bad_rows += unpackable rows
+void launch_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, bool zflag_all, hipStream_t s);   // w13.h planes of [N][K] bf16 rows; *bad_rows += unpackable rows; zflag_all: W13_ZROW in every row byte
 void launch_gemv_f8(int pro, int epi, const GemvArgs& a, hipStream_t s);       // the fp8 instantiations in the process default shape (DTK_F8_VARIANT, 8)
 void launch_gemv_f8_variant(int pro, int epi, int variant, const GemvArgs& a, hipStream_t s);   // ... in shape 0..9 of the same table
 void set_gemv_default_variant(int epi, int variant);

@@ -90,10 +90,19 @@ __device__ __forceinline__ void gemv_epilogue(const GemvArgs& a, int u, float a0
 // zero-padded to whole blocks, no row scale in the epilogue.  Every F4 branch is compile-time: the bf16 / fp8 code is unchanged.
 // W13: the 13-bit planes of bf16 rows (a.Wp rows, a.Wh row bytes; w13.h, gemv_inl.h): the operands rebuilt in registers are the bf16
 // row's bits and the fold order is gemv_fma's, so the sums are the bf16 kernel's; x lies linearly in LDS; U is a multiple of 4.  Every
-// W13 branch is compile-time as well.
-template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128, bool F4 = false, bool W13 = false>
+// W13 branch is compile-time as well.  Rows whose byte a.Wh has W13_ZROW hold a zero code: under PRO_RMSNORM a wave decodes its row
+// group by the general rule if any of its NR rows has the bit and by the short one otherwise (gemv_inl.h: dot8_w13<NZ>; wave-uniform,
+// the same bits); the other prologues' roles (down, o_proj) gained nothing from the short decode and keep the general one alone.
+// FW: PRO_RMSNORM folds the sum of squares per thread, per wave and over the waves, so `inv` depends on how many threads fold.  The
+// first FW x 64 threads of the block fold exactly as a block of FW waves does (the same chunks per thread in the same order, in both
+// forms of the prologue, whose choice follows FW as well), so a kernel of any block size gives the bits of the FW-wave kernel.  FW = WAVES
+// is the code without the parameter.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST, bool F8 = false, int KS = 1, int HD = 128, bool F4 = false, bool W13 = false, int FW = WAVES>
 __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   static_assert(!(F4 && F8) && !(W13 && (F4 || F8)), "one weight format");
+  static_assert(FW >= 1 && FW <= WAVES, "the folding threads are the block's first");
+  constexpr int FT = FW * 64;                  // PRO_RMSNORM: threads that fold the sum of squares
+  constexpr bool FALL = FW == WAVES;           // ... all of the block
   constexpr bool PAIRED = (EPI == EPI_QKV) || (EPI == EPI_SWIGLU);
   constexpr int NR = PAIRED ? 2 * R : R;
   constexpr int THREADS = WAVES * 64;
@@ -128,8 +137,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
 
   const u32x4* rows[NR];
   const uint8_t* srows[NR];                    // F4: the rows' block scales
-  uint32_t lo2[NR];                            // W13: the rows' decode base, lo | lo << 16
+  uint32_t lo4[NR];                            // W13: the rows' decode base lo in every byte
+  bool zrow = false;                           // W13: one of the wave's rows holds a zero code (wave-uniform)
   auto set_rows = [&](int u0) {
+    unsigned zb = 0;                           // W13: the row bytes of the group, or-ed
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       int u = u0 + j;
@@ -155,10 +166,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
         else srows[j] = a.S4 + (size_t)r0 * KC;
       }
       if (W13) {
-        if (PAIRED) { lo2[2 * j] = (uint32_t)w13_lo(a.Wh[r0]) * 0x10001u; lo2[2 * j + 1] = (uint32_t)w13_lo(a.Wh[r1]) * 0x10001u; }
-        else lo2[j] = (uint32_t)w13_lo(a.Wh[r0]) * 0x10001u;
+        const unsigned b0 = a.Wh[r0], b1 = PAIRED ? a.Wh[r1] : 0u;
+        if (PAIRED) { lo4[2 * j] = (uint32_t)w13_lo(b0) * 0x01010101u; lo4[2 * j + 1] = (uint32_t)w13_lo(b1) * 0x01010101u; }
+        else lo4[j] = (uint32_t)w13_lo(b0) * 0x01010101u;
+        zb |= b0 | b1;
       }
     }
+    if (W13 && PRO == PRO_RMSNORM) zrow = (__builtin_amdgcn_readfirstlane((int)zb) & W13_ZROW) != 0;   // every lane of the wave read the same bytes
   };
   set_rows(unit0);
 
@@ -174,7 +188,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   uint32_t zwa[NR][UW / 4], zwb[NR][UW / 4];
   float acc[NR];
 #define GLOAD(w, sc, g) do { if (W13) gemv_load_w13<NR, UW>(l##w, n##w, z##w, rows, (g), lane, J2, n13, s13); else if (F4) gemv_load_f4<NR, U>(w, sc, rows, srows, (g), lane, KC); else gemv_load<NR, U>(w, rows, (g), lane, KC); } while (0)
-#define GFMA(w, sc, g) do { if (W13) gemv_fma_w13<NR, UW>(acc, l##w, n##w, z##w, lo2, xs, (g), lane, K8); else if (F4) gemv_fma_f4<NR, U>(acc, w, sc, xs, (g), lane, KC); else if (F8) gemv_fma_f8<NR, U>(acc, w, xs, (g), lane, KC); else gemv_fma<NR, U>(acc, w, xs, (g), lane, KC); } while (0)
+#define GFMA(w, sc, g) do { if (W13) gemv_fma_w13<NR, UW, NZ>(acc, l##w, n##w, z##w, lo4, xs, (g), lane, K8); else if (F4) gemv_fma_f4<NR, U>(acc, w, sc, xs, (g), lane, KC); else if (F8) gemv_fma_f8<NR, U>(acc, w, xs, (g), lane, KC); else gemv_fma<NR, U>(acc, w, xs, (g), lane, KC); } while (0)
 
   // first stage of weights goes in flight before the prologue touches x
   if (G > 0) GLOAD(wa, sa, GIDX(0));
@@ -207,11 +221,12 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
   } else if (PRO == PRO_RMSNORM) {
     const u32x4* x4 = reinterpret_cast<const u32x4*>(a.x);
     const u32x4* w4 = reinterpret_cast<const u32x4*>(a.norm_w);
-    if (K8 <= 2 * THREADS) {
+    if (K8 <= 2 * FT) {
       // x and the norm weight in ONE memory round trip, kept in registers across the block reduction (the two-pass form
-      // re-read x after the barrier: a second dependent L1 / L2 trip in front of every RMSNorm GEMV)
-      const int c0 = tid, c1 = tid + THREADS;
-      const bool h0 = c0 < K8, h1 = c1 < K8;
+      // re-read x after the barrier: a second dependent L1 / L2 trip in front of every RMSNorm GEMV).  FW < WAVES: the folding
+      // threads hold all of x; the others only meet them at the barriers.
+      const int c0 = tid, c1 = tid + FT;
+      const bool h0 = (FALL || tid < FT) && c0 < K8, h1 = (FALL || tid < FT) && c1 < K8;
       const u32x4 zz = {0u, 0u, 0u, 0u};
       const u32x4 v0 = h0 ? x4[c0] : zz, v1 = h1 ? x4[c1] : zz;
       const u32x4 g0 = h0 ? w4[c0] : zz, g1 = h1 ? w4[c1] : zz;
@@ -233,7 +248,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       __syncthreads();
       float tot = 0.f;
 #pragma unroll
-      for (int w = 0; w < WAVES; ++w) tot += red[w];
+      for (int w = 0; w < FW; ++w) tot += red[w];
       const float inv = rsqrtf(tot / (float)a.K + a.eps);
       u32x4 o0, o1;
 #pragma unroll
@@ -246,7 +261,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       if (h1) xs[XI(c1)] = o1;
     } else {
       float ss = 0.f;
-      for (int c = tid; c < K8; c += THREADS) {
+      for (int c = (FALL || tid < FT) ? tid : K8; c < K8; c += FT) {   // FW < WAVES: only the folding threads sum; all normalise below
         const u32x4 v = x4[c];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -260,7 +275,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
       __syncthreads();
       float tot = 0.f;
 #pragma unroll
-      for (int w = 0; w < WAVES; ++w) tot += red[w];
+      for (int w = 0; w < FW; ++w) tot += red[w];
       const float inv = rsqrtf(tot / (float)a.K + a.eps);
       for (int c = tid; c < K8; c += THREADS) {
         const u32x4 v = x4[c];
@@ -339,15 +354,26 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv(GemvArgs a) {
     const bool active = unit0 < n_units;  // wave-uniform
 #pragma unroll
     for (int r = 0; r < NR; ++r) acc[r] = 0.f;
-    // ---- main loop: two register stages (wa holds stage 0 on entry)
-    for (int g = 0; g < G; g += 2) {
-      if (g + 1 < G) GLOAD(wb, sb, GIDX(g + 1));
-      GFMA(wa, sa, GIDX(g));
-      if (g + 1 < G) {
-        if (g + 2 < G) GLOAD(wa, sa, GIDX(g + 2));
-        GFMA(wb, sb, GIDX(g + 1));
-      }
+    // ---- main loop: two register stages (wa holds stage 0 on entry).  W13 under PRO_RMSNORM: one copy of the loop per decode, chosen
+    // once per row group (a branch around every stage instead cost the general decode 0.5 us per launch against the loop without it)
+#define MAIN_LOOP(NZV) do {                                   \
+      constexpr bool NZ = NZV;                                 \
+      for (int g = 0; g < G; g += 2) {                         \
+        if (g + 1 < G) GLOAD(wb, sb, GIDX(g + 1));             \
+        GFMA(wa, sa, GIDX(g));                                 \
+        if (g + 1 < G) {                                       \
+          if (g + 2 < G) GLOAD(wa, sa, GIDX(g + 2));           \
+          GFMA(wb, sb, GIDX(g + 1));                           \
+        }                                                      \
+      }                                                        \
+    } while (0)
+    if constexpr (W13 && PRO == PRO_RMSNORM) {
+      if (zrow) MAIN_LOOP(false);
+      else MAIN_LOOP(true);
+    } else {
+      MAIN_LOOP(false);
     }
+#undef MAIN_LOOP
     const int cur = unit0;
     float q0[R], q1[R];          // this chunk's epilogue operands (the next chunk's are fetched below)
 #pragma unroll
@@ -623,39 +649,45 @@ void launch_gemv_q4(int pro, int epi, const GemvArgs& a, hipStream_t s) {
 
 // 13-bit planes of bf16 rows (w13.h; gemv_inl.h: dot8_w13): the four (prologue, epilogue) pairs of a layer, lm_head and the EPI_STORE
 // pairs, batch 1.  Variant 0 of a role is what a decode step runs; the others exist for dtk_bench_gemv (| 0x1000), which picked it.
-template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST = false, int KS = 1, int BPC = 2>
+// FW: the waves that fold the RMSNorm sum of squares (k_gemv), 0 = all of the block.
+template <int PRO, int EPI, int R, int U, int WAVES, bool PERSIST = false, int KS = 1, int BPC = 2, int FW0 = 0>
 static void launch_gemv_w13_t(const GemvArgs& a, hipStream_t s) {
   int n_units = (EPI == EPI_QKV) ? (a.N >> 1) : (EPI == EPI_SWIGLU ? a.ff : a.N);
   const int per_block = (WAVES / KS) * R;
   int grid = (n_units + per_block - 1) / per_block;
   if (PERSIST && grid > num_cus() * BPC) grid = num_cus() * BPC;
   const size_t lds = (size_t)(a.K >> 3) * 16 + 64 + 1024;   // x (bf16, linear) + per-wave RMSNorm partials + split-K partials
+  constexpr int FW = FW0 ? FW0 : WAVES;
   if constexpr (EPI == EPI_QKV || PRO == PRO_ATTN) {
-    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 64, false, true>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
+    if (a.hd == 64) { hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 64, false, true, FW>), dim3(grid), dim3(WAVES * 64), lds, s, a); return; }
   }
-  hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 128, false, true>), dim3(grid), dim3(WAVES * 64), lds, s, a);
+  hipLaunchKernelGGL((k_gemv<PRO, EPI, R, U, WAVES, PERSIST, false, KS, 128, false, true, FW>), dim3(grid), dim3(WAVES * 64), lds, s, a);
 }
 #define WV(PRO, EPI, R, U, W) return launch_gemv_w13_t<PRO, EPI, R, U, W>(a, s)
 #define WVP(PRO, EPI, R, U, W, BPC) return launch_gemv_w13_t<PRO, EPI, R, U, W, true, 1, BPC>(a, s)
 #define WVK(PRO, EPI, R, U, W, KS) return launch_gemv_w13_t<PRO, EPI, R, U, W, false, KS>(a, s)
+#define WVF(PRO, EPI, R, U, W, BPC, FW) return launch_gemv_w13_t<PRO, EPI, R, U, W, true, 1, BPC, FW>(a, s)   // persistent, norm fold of FW waves
 bool gemv_w13_has(int pro, int epi, int v) {
-  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return v >= 0 && v <= 5;
+  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return v >= 0 && v <= 7;
   if (pro == PRO_COPY && epi == EPI_RESID) return v >= 0 && v <= 6;
   if (pro == PRO_ATTN && epi == EPI_RESID) return v >= 0 && v <= 2;
-  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return v >= 0 && v <= 4;
-  if ((pro == PRO_RMSNORM || pro == PRO_COPY) && epi == EPI_STORE) return v == 0;
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return v >= 0 && v <= 7;
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) return v >= 0 && v <= 1;
+  if (pro == PRO_COPY && epi == EPI_STORE) return v == 0;
   return false;
 }
 void launch_gemv_w13_variant(int pro, int epi, int v, const GemvArgs& a, hipStream_t s) {
   if (pro == PRO_RMSNORM && epi == EPI_QKV) {
     switch (v) { default: WV(PRO_RMSNORM, EPI_QKV, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_QKV, 2, 4, 4); case 2: WV(PRO_RMSNORM, EPI_QKV, 1, 4, 8);
                  case 3: WVP(PRO_RMSNORM, EPI_QKV, 1, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_QKV, 1, 8, 4);
-                 case 5: WVP(PRO_RMSNORM, EPI_QKV, 1, 4, 4, 4); }
+                 case 5: WVP(PRO_RMSNORM, EPI_QKV, 1, 4, 4, 4);
+                 case 6: WVF(PRO_RMSNORM, EPI_QKV, 1, 4, 8, 2, 4); case 7: WVF(PRO_RMSNORM, EPI_QKV, 1, 4, 16, 1, 4); }   // the 4-wave norm fold in 8 / 16 waves
   }
   if (pro == PRO_RMSNORM && epi == EPI_SWIGLU) {
     switch (v) { default: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_SWIGLU, 2, 4, 4); case 2: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 8);
                  case 3: WVP(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_SWIGLU, 1, 8, 4);
-                 case 5: WVP(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 4, 4); }
+                 case 5: WVP(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 4, 4);
+                 case 6: WVF(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 8, 2, 4); case 7: WVF(PRO_RMSNORM, EPI_SWIGLU, 1, 4, 16, 1, 4); }
   }
   if (pro == PRO_COPY && epi == EPI_RESID) {
     switch (v) { default: WV(PRO_COPY, EPI_RESID, 1, 8, 8); case 1: WV(PRO_COPY, EPI_RESID, 1, 4, 8); case 2: WV(PRO_COPY, EPI_RESID, 2, 4, 4);
@@ -667,9 +699,11 @@ void launch_gemv_w13_variant(int pro, int epi, int v, const GemvArgs& a, hipStre
   }
   if (pro == PRO_RMSNORM && epi == EPI_LOGITS) {
     switch (v) { default: WV(PRO_RMSNORM, EPI_LOGITS, 1, 4, 4); case 1: WV(PRO_RMSNORM, EPI_LOGITS, 2, 4, 4); case 2: WVP(PRO_RMSNORM, EPI_LOGITS, 1, 4, 8, 2);
-                 case 3: WVP(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8); }
+                 case 3: WVP(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8, 2); case 4: WV(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8);
+                 case 5: WVF(PRO_RMSNORM, EPI_LOGITS, 2, 4, 8, 2, 4); case 6: WVF(PRO_RMSNORM, EPI_LOGITS, 1, 4, 8, 2, 4);
+                 case 7: WVF(PRO_RMSNORM, EPI_LOGITS, 2, 4, 16, 1, 4); }
   }
-  if (pro == PRO_RMSNORM && epi == EPI_STORE) WV(PRO_RMSNORM, EPI_STORE, 2, 4, 4);
+  if (pro == PRO_RMSNORM && epi == EPI_STORE) { if (v == 1) WVF(PRO_RMSNORM, EPI_STORE, 2, 4, 8, 2, 4); WV(PRO_RMSNORM, EPI_STORE, 2, 4, 4); }
   if (pro == PRO_COPY && epi == EPI_STORE) WV(PRO_COPY, EPI_STORE, 2, 4, 4);
   fprintf(stderr, "launch_gemv_w13: no 13-bit kernel for prologue %d, epilogue %d\n", pro, epi);   // a missing kernel is an error, never a fall-back
   abort();
@@ -677,17 +711,22 @@ void launch_gemv_w13_variant(int pro, int epi, int v, const GemvArgs& a, hipStre
 #undef WV
 #undef WVP
 #undef WVK
+#undef WVF
 // The 13-bit shape launch_gemv streams a.Wp in when the role's bf16 variant is `v`, or -1 = the bf16 rows stay.  The shape must give the
 // bf16 variant's bits, and two things of a shape enter them.  (1) The fold of a row: without split-K it is gemv_inl.h's whatever the
 // shape; a split-K variant deals k-groups of U iterations to KS waves, and only U = 4, KS = 2 has a 13-bit twin (a stage is whole sign
 // blocks: U % 4 == 0), so any other split-K choice keeps bf16.  (2) PRO_RMSNORM: the sum of squares is folded per thread, per wave and
-// over the waves, so it depends on the block's size - the 13-bit shape has the bf16 variant's number of waves (a 16-wave shape,
-// faster for q/k/v by 0.2 us, changed `inv` in the last place at K = 4096 and with it a token of the benchmark's rollout: removed).
+// over the waves, so it depends on how many waves fold - the 13-bit shape folds with the bf16 variant's number of waves, which is its
+// own block's or, in the shapes built with k_gemv's FW (q/k/v, gate/up 6 and 7, lm_head 5 to 7, STORE 1), that of a 4-wave block in a
+// persistent block of 8 or 16 (a 16-wave shape folding with all 16 changed `inv` in the last place at K = 4096 and with it a token of the
+// benchmark's rollout).
 // Defaults by measurement among those (ds-7b, back-to-back chains over all layers' weights, us per launch, bf16 kernel -> 13-bit shape;
 // DESIGN 3.1c'', profiles/w13_ds-7b.json): q/k/v 18.20 -> 17.11 and gate/up 28.41 -> 26.14 (persistent, R 1, U 4, 4 waves, 4 blocks per
 // CU; one chunk per wave 19.3 / 27.2, R 2 18.6 / 32.9, U 8 = one stage 22.9 / 30.5); down 17.66 -> 15.46 (R 1, U 4, 8 waves; 16.10 at U 8,
-// 15.81 with 4 waves, 18.2 split-K); lm_head 37.73 -> 36.40 (R 2, U 4, 4 waves; 37.9 at R 1; the persistent 8-wave shapes reach 34.1 but
-// fold the norm differently from the 4-wave bf16 default).  o_proj (33.6 MB, latency-bound) is SLOWER on planes in every shape tried
+// 15.81 with 4 waves, 18.2 split-K); lm_head 37.73 -> 36.40 (R 2, U 4, 4 waves; 37.9 at R 1).  With the short decode of rows without a zero
+// code and the 4-wave fold in larger blocks (one later visit, same chains): q/k/v 17.37 -> 16.82 in the same shape and 16.37 persistent
+// in 8 waves (shape 6; 16.61 in 16), gate/up 27.14 -> 25.72 in the same shape (26.15 / 26.58 in shapes 6 / 7), lm_head 36.25 -> 34.64 in
+// the same shape and 33.53 persistent in 8 waves, R 2 (shape 5; 34.70 at R 1, 34.60 in 16 waves).  o_proj (33.6 MB, latency-bound) is SLOWER on planes in every shape tried
 // (7.76 -> 8.03 at best): it keeps its bf16 rows.
 static int w13_shape_for(int pro, int epi, int v, const GemvArgs& a) {
   const GemvShape sh = gemv_variant_shape(pro, epi, v);              // the bf16 row's own shape, from the table that launches it
@@ -697,8 +736,11 @@ static int w13_shape_for(int pro, int epi, int v, const GemvArgs& a) {
     if (sh.ks == 1) return 1;
     return (sh.ks == 2 && sh.U == 4) ? 3 : -1;                       // split-K 2 over groups of 4 iterations has a twin; nothing else
   }
-  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return sh.waves == 4 ? 5 : (sh.waves == 8 ? 3 : -1);
-  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return sh.waves == 4 ? 1 : (sh.waves == 8 ? 4 : -1);
+  // K >= 4096 (where the chains were run): q/k/v and lm_head in the persistent 8-wave shapes that fold the norm as the 4-wave bf16 kernel does
+  const bool big = a.K >= 4096;
+  if (pro == PRO_RMSNORM && epi == EPI_QKV) return sh.waves == 4 ? (big ? 6 : 5) : (sh.waves == 8 ? 3 : -1);
+  if (pro == PRO_RMSNORM && epi == EPI_SWIGLU) return sh.waves == 4 ? 5 : (sh.waves == 8 ? 3 : -1);
+  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return sh.waves == 4 ? (big ? 5 : 1) : (sh.waves == 8 ? 4 : -1);
   if (pro == PRO_RMSNORM && epi == EPI_STORE) return sh.waves == 4 ? 0 : -1;
   if (pro == PRO_COPY && epi == EPI_STORE) return 0;
   return -1;
@@ -706,27 +748,34 @@ static int w13_shape_for(int pro, int epi, int v, const GemvArgs& a) {
 
 // Packs [N][K] bf16 rows into 13-bit planes (w13.h), a block per row: hb = the row's largest e >> 1, then a thread per (sign block,
 // lane) writes its four chunks' pieces of the three planes.  A row with a weight below the window adds 1 to *bad_rows (the caller then
-// drops the matrix' packed copy; such weights are written as zero, never as another value).  W is only read.
-__global__ __launch_bounds__(256) void k_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K) {
+// drops the matrix' packed copy; such weights are written as zero, never as another value).  W is only read.  The row byte Wh is
+// w13.h's device byte: hb, and W13_ZROW if a weight of the row has e >> 1 == 0 (`zflag_all`: in every row - the kernels then decode
+// every row by the general rule; option "w13_nz" = 0).
+__global__ __launch_bounds__(256) void k_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, int zflag_all) {
   const int row = blockIdx.x, tid = threadIdx.x;
   const u32x4* w4 = reinterpret_cast<const u32x4*>(W + (size_t)row * K);
   unsigned char* out = Wp + (size_t)row * w13_row_bytes(K);
-  __shared__ int red[4];
+  __shared__ int red[4], redq[4];
   __shared__ int any_bad;
   const int K8 = K >> 3, J2 = w13_units(K), J4 = w13_blocks(K);
-  int hb = 0;
+  int hb = 0, qmin = 127;                      // the row's largest and smallest e >> 1
   for (int c = tid; c < K8; c += 256) {
     const u32x4 v = w4[c];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) hb = max(hb, max((int)((v[e] >> 8) & 0x7fu), (int)((v[e] >> 24) & 0x7fu)));
+    for (int e = 0; e < 4; ++e) {
+      const int q0 = (int)((v[e] >> 8) & 0x7fu), q1 = (int)((v[e] >> 24) & 0x7fu);
+      hb = max(hb, max(q0, q1));
+      qmin = min(qmin, min(q0, q1));
+    }
   }
 #pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) hb = max(hb, __shfl_xor(hb, off));
-  if ((tid & 63) == 0) red[tid >> 6] = hb;
+  for (int off = 32; off >= 1; off >>= 1) { hb = max(hb, __shfl_xor(hb, off)); qmin = min(qmin, __shfl_xor(qmin, off)); }
+  if ((tid & 63) == 0) { red[tid >> 6] = hb; redq[tid >> 6] = qmin; }
   if (tid == 0) any_bad = 0;
   __syncthreads();
   hb = max(max(red[0], red[1]), max(red[2], red[3]));
-  if (tid == 0) Wh[row] = (uint8_t)hb;
+  qmin = min(min(redq[0], redq[1]), min(redq[2], redq[3]));
+  if (tid == 0) Wh[row] = (uint8_t)(hb | ((qmin == 0 || zflag_all) ? W13_ZROW : 0));
   const int lo = w13_lo(hb);
   int bad = 0;
   for (int t = tid; t < J4 * 64; t += 256) {
@@ -765,8 +814,8 @@ __global__ __launch_bounds__(256) void k_pack_w13_rows(const bf16_t* W, uint8_t*
   __syncthreads();
   if (tid == 0 && any_bad) atomicAdd(bad_rows, 1u);
 }
-void launch_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, hipStream_t s) {
-  hipLaunchKernelGGL(k_pack_w13_rows, dim3(N), dim3(256), 0, s, W, Wp, Wh, bad_rows, N, K);
+void launch_pack_w13_rows(const bf16_t* W, uint8_t* Wp, uint8_t* Wh, unsigned* bad_rows, int N, int K, bool zflag_all, hipStream_t s) {
+  hipLaunchKernelGGL(k_pack_w13_rows, dim3(N), dim3(256), 0, s, W, Wp, Wh, bad_rows, N, K, zflag_all ? 1 : 0);
 }
 
 // per-role default variant (tuned): indexed by epilogue; slot 5 = o_proj (EPI_RESID with K == d) when it has its own choice

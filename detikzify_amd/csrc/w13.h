@@ -20,6 +20,12 @@
 //      k-iteration i = 0 .. 3 of the block (chunk 256 b + 64 i + l); the sign of weight k of group g is bit 8 k + g              (dword)
 // so the four codes of a group are the bytes of (N >> 4 h) & 0x0f0f0f0f and their signs the bits 7 of the bytes of S << (7 - g).
 // Chunks behind the row's end hold zero in every plane (code 0, L 0 = +0).  K = 4096: 6656 B (13 / 16 of 8192); K = 11008: 18432.
+//
+// The row byte on the DEVICE is hb | W13_ZROW: hb <= 127, and its free top bit says that some weight of the row (inside K, the padding
+// does not count) has code 0, i.e. e >> 1 == 0.  In a row without the bit every code is 1 .. 15, so the high byte is lo + code without
+// the "code ?" (w13_high_nz): the kernels decode such rows in fewer operations and take the general rule (w13_high) for the others.
+// Behind the row's end the short rule gives lo << 8, a finite value that only ever meets x = 0.  The host packer's *hb stays plain hb;
+// w13_row_byte is the device's byte, and w13_lo takes either.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -35,7 +41,11 @@ W13_HD static inline int w13_blocks(int K) { return (w13_units(K) + 1) >> 1; }
 W13_HD static inline size_t w13_n_off(int K) { return (size_t)w13_units(K) * 1024; }
 W13_HD static inline size_t w13_s_off(int K) { return (size_t)w13_units(K) * 1536; }
 W13_HD static inline size_t w13_row_bytes(int K) { return (size_t)w13_units(K) * 1536 + (size_t)w13_blocks(K) * 256; }
-W13_HD static inline int w13_lo(int hb) { return hb > 15 ? hb - 15 : 0; }
+#define W13_ZROW 0x80   // device row byte: some weight of the row has code 0
+W13_HD static inline int w13_lo(int hb) { hb &= 0x7f; return hb > 15 ? hb - 15 : 0; }   // hb, or the device's row byte
+// the exponent part of the high byte: any row, and a row without W13_ZROW (no code is 0)
+W13_HD static inline int w13_high(int code, int lo) { return code ? lo + code : 0; }
+W13_HD static inline int w13_high_nz(int code, int lo) { return lo + code; }
 
 // where weight k of a row lies: byte offsets into the row, the nibble's shift and the sign's bit inside its byte
 struct W13Pos { size_t l, n, s; int nshift, sbit; };
@@ -55,6 +65,12 @@ static inline int w13_row_hb(const uint16_t* w, int K) {
   int hb = 0;
   for (int k = 0; k < K; ++k) { const int q = (w[k] >> 8) & 0x7f; if (q > hb) hb = q; }
   return hb;
+}
+// the device's row byte: hb, and W13_ZROW if a weight of the row has e >> 1 == 0 (+-0, a denormal, e = 1)
+static inline int w13_row_byte(const uint16_t* w, int K) {
+  int z = 0;
+  for (int k = 0; k < K; ++k) if (((w[k] >> 8) & 0x7f) == 0) z = W13_ZROW;
+  return w13_row_hb(w, K) | z;
 }
 // code of one weight under decode base lo, or -1: below the window
 W13_HD static inline int w13_code(unsigned w, int lo) {
@@ -81,11 +97,21 @@ static inline int w13_pack_row(const uint16_t* w, int K, uint8_t* row, uint8_t* 
   *hb_out = (uint8_t)hb;
   return bad;
 }
+// hb: the row's hb or the device's row byte
 static inline void w13_unpack_row(const uint8_t* row, int hb, int K, uint16_t* w) {
   const int lo = w13_lo(hb);
   for (int k = 0; k < K; ++k) {
     const W13Pos p = w13_pos(K, k);
     const int code = (row[p.n] >> p.nshift) & 15, sign = (row[p.s] >> p.sbit) & 1;
-    w[k] = (uint16_t)((sign << 15) | ((code ? lo + code : 0) << 8) | row[p.l]);
+    w[k] = (uint16_t)((sign << 15) | (w13_high(code, lo) << 8) | row[p.l]);
+  }
+}
+// the short rule over a whole row: equal to w13_unpack_row exactly when the row's byte has no W13_ZROW
+static inline void w13_unpack_row_nz(const uint8_t* row, int hb, int K, uint16_t* w) {
+  const int lo = w13_lo(hb);
+  for (int k = 0; k < K; ++k) {
+    const W13Pos p = w13_pos(K, k);
+    const int code = (row[p.n] >> p.nshift) & 15, sign = (row[p.s] >> p.sbit) & 1;
+    w[k] = (uint16_t)((sign << 15) | (w13_high_nz(code, lo) << 8) | row[p.l]);
   }
 }

@@ -665,6 +665,12 @@ int  dtk_w13_row_bytes(int K);
 int  dtk_w13_pack_host(const uint16_t* W, int N, int K, uint8_t* planes, uint8_t* hb, int32_t* bad);
 int  dtk_w13_unpack_host(const uint8_t* planes, const uint8_t* hb, int N, int K, uint16_t* W);
 int  dtk_w13_op_bad_rows(dtk_ctx* ctx);
+/* The row byte the device keeps beside the planes is hb | 0x80 where a weight of the row has e >> 1 == 0 (w13.h: W13_ZROW): such rows
+ * take the general decode, the others a shorter one with the same bits.  dtk_w13_row_bytes_host: that byte for rows [N][K] (no GPU).
+ * dtk_w13_flagged_rows: rows with the bit among the packed matrices of role 0 q/k/v, 1 o_proj, 2 gate/up, 3 down, 4 lm_head (-1: no
+ * planes yet).  Option "w13_nz" = 0 makes the packer set the bit in every row. */
+int  dtk_w13_row_bytes_host(const uint16_t* W, int N, int K, uint8_t* bytes);
+int  dtk_w13_flagged_rows(dtk_ctx* ctx, int role);
 int  dtk_op_layernorm(dtk_ctx* ctx, const uint16_t* X, const uint16_t* w, const uint16_t* b,
                       int M, int D, float eps, uint16_t* Y);
 /* run the sampler on host logits with the context's sampling config; step = draw index */

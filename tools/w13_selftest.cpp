@@ -36,6 +36,21 @@ static int check_row(int K, int hb, int span, int zeros, int below) {
   w13_unpack_row(row.data(), hbyte, K, back.data());
   for (int k = 0; k < K; ++k)
     if (back[(size_t)k] != w[(size_t)k]) { std::printf("K %d hb %d: weight %d is %04x, was %04x\n", K, hb, k, back[(size_t)k], w[(size_t)k]); return 1; }
+  // the device's row byte, from the format's definition: hb, and W13_ZROW iff a weight has e >> 1 == 0.  The general rule decodes
+  // under either byte; the short rule (no "code ?") gives the row exactly when the bit is clear
+  int want_z = 0;
+  for (int k = 0; k < K; ++k) want_z |= (((w[(size_t)k] >> 8) & 0x7f) == 0) ? W13_ZROW : 0;
+  const int byte = w13_row_byte(w.data(), K);
+  if (byte != (real_hb | want_z)) { std::printf("K %d hb %d: row byte %02x, want %02x\n", K, hb, byte, real_hb | want_z); return 1; }
+  w13_unpack_row(row.data(), byte, K, back.data());
+  for (int k = 0; k < K; ++k)
+    if (back[(size_t)k] != w[(size_t)k]) { std::printf("K %d row byte %02x: weight %d is %04x, was %04x\n", K, byte, k, back[(size_t)k], w[(size_t)k]); return 1; }
+  w13_unpack_row_nz(row.data(), byte, K, back.data());
+  int differ = 0;
+  for (int k = 0; k < K; ++k) differ += back[(size_t)k] != w[(size_t)k];
+  // (with lo == 0 the two rules coincide, so a flagged row may still decode alike: the bit is then merely conservative)
+  if (!(byte & W13_ZROW) && differ) { std::printf("K %d row byte %02x: the short rule changes %d weights of an unflagged row\n", K, byte, differ); return 1; }
+  if ((byte & W13_ZROW) && w13_lo(byte) > 0 && !differ) { std::printf("K %d row byte %02x: flagged, lo > 0, and the short rule changes nothing\n", K, byte); return 1; }
   return 0;
 }
 
