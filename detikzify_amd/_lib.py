@@ -229,6 +229,9 @@ SYMBOLS = {
     "dtk_op_swiglu": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dtk_op_attention_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int] * 9),
     "dtk_op_rows_move": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 8 + [_P]),
+    # additive (ABI stays 7): one role of the multi-vector decode GEMV family (prologue, epilogue, nb slots, block shape)
+    "dtk_op_gemv_mv_role": (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, _P] + [C.c_int] * 7 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_float,
+                                      _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     # additive (ABI stays 7): 13-bit planes of bf16 weight rows (csrc/w13.h): the host packer for the CPU tests, the op's packing outcome
     "dtk_w13_row_bytes": (C.c_int, [C.c_int]),
     "dtk_w13_pack_host": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),

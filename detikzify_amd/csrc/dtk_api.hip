@@ -4534,6 +4534,88 @@ int dtk_op_rows_move(dtk_ctx* c, int form, const int32_t* ids, const uint16_t* s
   return r.finish(s);
 }
 
+// ---- the multi-vector decode GEMV family alone (dtk_op_gemv_mv_role): one (prologue, epilogue) of k_gemv_mv on host operands through
+// the step's own launcher, nb = 1 | 2 | 4 slots with their own positions and active flags.  Fragment-order buffers (x_layout 1, the SwiGLU
+// activation) cross the ABI as the kernel holds them, whole 16-slot tiles.  The block shape is set for this call alone.
+extern "C++" {
+namespace {
+struct MvShapeScope {      // launch_gemv_mv reads the shape table: o_proj (K == d) looks at role 5 first
+  int epi;
+  MvShapeScope(int epi_, int shape) : epi(epi_) { set_gemv_mv_shape(epi, shape); if (epi == EPI_RESID) set_gemv_mv_shape(5, shape); }
+  ~MvShapeScope() { set_gemv_mv_shape(epi, -1); if (epi == EPI_RESID) set_gemv_mv_shape(5, -1); }
+};
+}  // namespace
+}  // extern "C++"
+
+int dtk_op_gemv_mv_role(dtk_ctx* c, int pro, int epi, int nb, int shape, const uint16_t* W, const uint8_t* W8, const float* wscale,
+                        int N, int K, int d, int ff, int H, int KVH, int T_max, const int32_t* pos, const int32_t* active, int bs_null,
+                        int x_layout, const uint16_t* X, const uint16_t* norm_w, float eps, const uint16_t* rope_cos,
+                        const uint16_t* rope_sin, int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io,
+                        float* logits_io) {
+  const char* who = "dtk_op_gemv_mv_role";
+  if (!c) return DTK_ERR_ARG;
+  if ((W != nullptr) + (W8 != nullptr) != 1 || (W8 && !wscale) || (!W8 && wscale)) return fail(c, DTK_ERR_ARG, "%s: exactly one of W | W8 + wscale", who);
+  const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_LOGITS || epi == EPI_STORE)) ||
+                    (pro == PRO_COPY && (epi == EPI_RESID || epi == EPI_STORE));
+  if (!pair) return fail(c, DTK_ERR_ARG, "%s: the step has no launch with prologue %d and epilogue %d", who, pro, epi);
+  if (nb != 1 && nb != 2 && nb != 4) return fail(c, DTK_ERR_ARG, "%s: nb %d (1, 2 or 4)", who, nb);
+  if (shape < -1 || shape > 3) return fail(c, DTK_ERR_ARG, "%s: shape %d (-1 = the step's choice, 0..3)", who, shape);
+  if (N < 1 || K < 8 || (K & 7) || (W8 && (K & 15))) return fail(c, DTK_ERR_ARG, "%s: N >= 1, K a multiple of 8 (16 for fp8 weights)", who);
+  if (scratch_fill < 0 || scratch_fill > 255 || d < 0) return fail(c, DTK_ERR_ARG, "%s: scratch_fill is a byte, d >= 0", who);
+  if (x_layout != 0 && x_layout != 1) return fail(c, DTK_ERR_ARG, "%s: x_layout %d (0 rows, 1 fragment order)", who, x_layout);
+  if (x_layout == 1 && pro == PRO_RMSNORM) return fail(c, DTK_ERR_ARG, "%s: PRO_RMSNORM reads residual streams, which are rows", who);
+  if (!X || !pos || !active || (pro == PRO_RMSNORM && !norm_w)) return fail(c, DTK_ERR_ARG, "%s: X, pos, active (and norm_w for PRO_RMSNORM) required", who);
+  for (int b = 0; b < nb; ++b)
+    if (bs_null && !active[b]) return fail(c, DTK_ERR_ARG, "%s: without a BatchState every slot decodes (slot %d is idle)", who, b);
+  if ((size_t)nb * K * 2 + (size_t)nb * 16 * 4 + 64 > (size_t)160 * 1024)
+    return fail(c, DTK_ERR_ARG, "%s: %d vectors of K = %d do not fit a CU's 160 KiB of LDS", who, nb, K);
+  if (epi == EPI_QKV) {
+    if (H < 1 || KVH < 1 || H % KVH) return fail(c, DTK_ERR_ARG, "%s: H %d query heads over KVH %d key / value heads", who, H, KVH);
+    if (N != (H + 2 * KVH) * 128 || d != H * 128) return fail(c, DTK_ERR_ARG, "%s: QKV needs N = (H + 2 KVH) * 128 and d = H * 128", who);
+    if (T_max < 1) return fail(c, DTK_ERR_ARG, "%s: T_max %d", who, T_max);
+    for (int b = 0; b < nb; ++b)
+      if (pos[b] < 0 || pos[b] >= T_max) return fail(c, DTK_ERR_ARG, "%s: slot %d: position %d of %d rows", who, b, pos[b], T_max);
+    if (!rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "%s: QKV needs the rope tables and q / k / v buffers", who);
+  } else if (epi == EPI_SWIGLU) {
+    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io) return fail(c, DTK_ERR_ARG, "%s: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff and y", who);
+  } else if (epi == EPI_LOGITS) {
+    if (!logits_io) return fail(c, DTK_ERR_ARG, "%s: LOGITS needs the logits buffer", who);
+  } else if (!y_io) return fail(c, DTK_ERR_ARG, "%s: RESID / STORE need y", who);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const bool qkv = epi == EPI_QKV;
+  const size_t kv_slot = qkv ? (size_t)KVH * T_max * 128 : 0;
+  const size_t ny = epi == EPI_SWIGLU ? (size_t)((ff + 31) >> 5) * 512 : ((epi == EPI_STORE || epi == EPI_RESID) ? (size_t)nb * N : 0);
+  BatchState hbs; memset(&hbs, 0, sizeof hbs);
+  DecState hst[4]; memset(hst, 0, sizeof hst);
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) hbs.share_src[j] = -1;
+  for (int b = 0; b < nb; ++b) { hbs.active[b] = active[b] ? 1 : 0; hst[b].pos = pos[b]; hst[b].next_pos = pos[b] + 1; }
+  OpRun r(c, who, scratch_fill);
+  GemvMvArgs g{};
+  if (W8) { g.W8 = r.in<uint8_t>(W8, (size_t)N * K); g.wscale = r.in<float>(wscale, N); }
+  else g.W = r.in<bf16_t>(W, (size_t)N * K);
+  g.X = r.in<bf16_t>(X, x_layout ? (size_t)((K + 31) >> 5) * 512 : (size_t)nb * K);
+  g.norm_w = r.in<bf16_t>(pro == PRO_RMSNORM ? norm_w : nullptr, pro == PRO_RMSNORM ? K : 0);
+  g.rope_cos = r.in<bf16_t>(qkv ? rope_cos : nullptr, qkv ? (size_t)T_max * 64 : 0);
+  g.rope_sin = r.in<bf16_t>(qkv ? rope_sin : nullptr, qkv ? (size_t)T_max * 64 : 0);
+  g.st = r.in<DecState>(hst, 4);
+  const BatchState* dbs = r.in<BatchState>(&hbs, 1);
+  g.bs = bs_null ? nullptr : dbs;
+  g.q_out = r.io<bf16_t>(qkv ? q_io : nullptr, qkv ? (size_t)nb * d : 0, "q");
+  g.kcache = r.io<bf16_t>(qkv ? k_io : nullptr, (size_t)nb * kv_slot, "k");
+  g.vcache = r.io<bf16_t>(qkv ? v_io : nullptr, (size_t)nb * kv_slot, "v");
+  g.Y = r.io<bf16_t>(ny ? y_io : nullptr, ny, "y");
+  g.logits = r.io<float>(epi == EPI_LOGITS ? logits_io : nullptr, epi == EPI_LOGITS ? (size_t)nb * N : 0, "logits");
+  g.N = N; g.K = K; g.ldx = K; g.x_rowmajor = x_layout == 0; g.eps = eps; g.ldy = N; g.kv_slot_stride = kv_slot;
+  g.T_max = T_max; g.d = d; g.ff = ff; g.H = H; g.KVH = KVH;
+  if (const int rc = r.upload(s)) return rc;      // (hbs and hst live on this frame: upload() waits for the copies)
+  {
+    MvShapeScope scope(epi, shape);
+    launch_gemv_mv(pro, epi, nb, g, s);
+  }
+  return r.finish(s);
+}
+
 // ---- w13.h's host code for the CPU tests: rows [N][K] bf16 <-> planes [N][dtk_w13_row_bytes(K)] + hb[N]; bad[N] = weights below the
 // row's window (0 = the row is packed exactly)
 int dtk_w13_row_bytes(int K) { return (K < 8 || (K & 7)) ? -1 : (int)w13_row_bytes(K); }

@@ -9,7 +9,9 @@
 // HBM-bound — 2.5 dot2 lanes per clock and CU per vector against 64 available).  Per slot the arithmetic is exactly k_gemv's:
 // the same chunk order per lane, the same wave reduction, the same HF rounding points in the epilogues — a slot's result does
 // not depend on NB or on which other slots are active, and a PRO_COPY role equals the single-sequence kernel bit for bit
-// (tests/test_gpu_parity.py::test_multi_vector_gemv_is_the_single_sequence_gemv_per_vector).
+// (tests/test_gpu_parity_mv.py::test_multi_vector_gemv_is_the_single_sequence_gemv_per_vector for EPI_STORE; every role, shape, NB
+// and active set alone against float64 and against k_gemv: tests/gemv_mv_cases.py, tests/test_gemv_mv_host.py,
+// tests/test_gpu_gemv_mv.py through dtk_op_gemv_mv_role).
 //
 // One step = sampler + L x [ rmsnorm+qkv+RoPE+KV | attention per (head, slot) | o_proj+residual | rmsnorm+gate/up+SiLU*mul |
 // down+residual ] + rmsnorm+lm_head: five launches per layer like the single-sequence step (the MFMA step needs seven: its

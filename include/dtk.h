@@ -653,6 +653,23 @@ int  dtk_op_attention_ex(dtk_ctx* ctx, const uint16_t* Q, int64_t nq, const uint
                          int q_offset, int nbatch, int scratch_fill);
 int  dtk_op_rows_move(dtk_ctx* ctx, int form, const int32_t* ids, const uint16_t* src, const float* pixels, int M, int D, int V, int lds,
                       int ldd, int image, int patch, int scratch_fill, uint16_t* dst_io);
+/* The multi-vector decode GEMV family (the step of a context with at most 5 slots) alone, one role at a time (additive, ABI 7): one
+ * (pro, epi) of launch_gemv_mv on host operands, nb = 1 | 2 | 4 slots, head dim 128.  pro / epi as in dtk_op_gemv_role; the pairs are the
+ * step's (RMSNORM, QKV), (COPY, RESID), (RMSNORM, SWIGLU), (RMSNORM, LOGITS) and the tests' (COPY, STORE), (RMSNORM, STORE).  shape: -1 =
+ * the step's measured choice (d tells o_proj, K == d, from down), 0..3 = that block shape; the choice holds for this call only.  Weights:
+ * W [N][K] bf16, or W8 [N][K] e4m3 bytes + wscale [N] (K % 16 == 0).  pos [nb], active [nb] (0 = the slot is idle); bs_null != 0 hands the
+ * kernel no BatchState at all (every slot must be active).  X: x_layout 0 = rows [nb][K]; 1 (PRO_COPY only) = the kernel's fragment order
+ * as whole 16-slot tiles, ceil(K / 32) * 512 elements, value (slot, k) at ((k >> 5) * 64 + ((k & 31) >> 3) * 16 + slot) * 8 + (k & 7).
+ * Result buffers are IN/OUT as in dtk_op_gemv_role: QKV (N = (H + 2 KVH) * 128, d = H * 128, H % KVH == 0, rope tables [T_max][64],
+ * 0 <= pos[b] < T_max): q_io [nb][d], k_io / v_io [nb][KVH][T_max][128];   STORE / RESID: y_io [nb][N];   SWIGLU (N = 2 ff, ff % 8 == 0):
+ * y_io = ceil(ff / 32) * 512 elements in fragment order;   LOGITS: logits_io [nb][N] fp32.  scratch_fill, the 256 guard bytes behind
+ * every result buffer (DTK_ERR_STATE) and DTK_ERR_ARG with nothing uploaded or launched as in dtk_op_gemv_role; refused besides: an
+ * LDS request (nb * K * 2 bytes of x plus the reduction words) beyond the CU's 160 KiB.  Buffers a role does not use may be NULL. */
+int  dtk_op_gemv_mv_role(dtk_ctx* ctx, int pro, int epi, int nb, int shape, const uint16_t* W, const uint8_t* W8, const float* wscale,
+                         int N, int K, int d, int ff, int H, int KVH, int T_max, const int32_t* pos, const int32_t* active, int bs_null,
+                         int x_layout, const uint16_t* X, const uint16_t* norm_w, float eps, const uint16_t* rope_cos,
+                         const uint16_t* rope_sin, int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io,
+                         float* logits_io);
 /* 13-bit planes of bf16 weight rows (csrc/w13.h; additive, ABI 7): the single-sequence step of a bf16 context streams them instead of the
  * 16-bit rows when dtk_set_option(ctx, "w13", 1); the kernels rebuild the rows' own bits, so every result is the bf16 step's.  A row
  * holding a weight more than 30 binades below its largest cannot be packed; its whole matrix then stays bf16 (dtk_stats.w13_counts).
