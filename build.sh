@@ -6,21 +6,39 @@ SRC=detikzify_amd/csrc
 OUT=detikzify_amd/lib
 mkdir -p "$OUT" build
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+OBJCOPY=${OBJCOPY:-$("$(dirname "$(command -v "$HIPCC")")/hipconfig" -l)/llvm-objcopy}      # the toolchain's own (hipconfig -l: its clang directory)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -Wno-unused-variable"
+UNITS="kernels_decode kernels_decode_mv kernels_batch_decode kernels_batch_gemm kernels_batch_ks kernels_batch_mx kernels_batched kernels_sample_mb dtk_api dtk_ops"
 
 if [ "$(cat build/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f build/*.o; mkdir -p build; echo "$FLAGS" > build/.flags; fi
+# an object is stale when its source or any header is newer: every header under csrc/ and the public one
+stale() {
+  [ ! -f "$1" ] && return 0
+  local h
+  for h in "$2" $SRC/*.h include/dtk.h; do [ "$h" -nt "$1" ] && return 0; done
+  return 1
+}
 pids=()
-for f in kernels_decode kernels_decode_mv kernels_batch_decode kernels_batch_gemm kernels_batch_ks kernels_batch_mx kernels_batched kernels_sample_mb dtk_api; do
-  if [ ! -f build/$f.o ] || [ $SRC/$f.hip -nt build/$f.o ] || [ $SRC/common.h -nt build/$f.o ] || [ $SRC/kernels.h -nt build/$f.o ] || [ $SRC/gemv_inl.h -nt build/$f.o ] || [ $SRC/batch_epi.h -nt build/$f.o ] || [ $SRC/mx_quant.h -nt build/$f.o ] || [ $SRC/w13.h -nt build/$f.o ] || [ include/dtk.h -nt build/$f.o ]; then
-    $HIPCC $FLAGS -c $SRC/$f.hip -o build/$f.o &
+objs=()
+for f in $UNITS; do
+  objs+=(build/$f.o)
+  if stale build/$f.o $SRC/$f.hip; then
+    if [ $f = dtk_ops ]; then
+      # a unit without device code: the id symbol hipcc gives every HIP unit (__hip_cuid_*, exported whatever the visibility flag
+      # says) is made local, so the library exports what it exported before the test entry points had a unit of their own
+      ( $HIPCC $FLAGS -c $SRC/$f.hip -o build/$f.o && $OBJCOPY -w -L '__hip_cuid_*' build/$f.o ) &
+    else
+      $HIPCC $FLAGS -c $SRC/$f.hip -o build/$f.o &
+    fi
     pids+=($!)
   fi
 done
 # the run loop of a batch (host code only; same flags so the exports stay include/dtk.h's)
+objs+=(build/dtk_engine.o)
 if [ ! -f build/dtk_engine.o ] || [ $SRC/dtk_engine.cpp -nt build/dtk_engine.o ] || [ include/dtk.h -nt build/dtk_engine.o ]; then
   $HIPCC $FLAGS -x c++ -pthread -c $SRC/dtk_engine.cpp -o build/dtk_engine.o &
   pids+=($!)
 fi
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libdtk_hip.so build/kernels_decode.o build/kernels_decode_mv.o build/kernels_batch_decode.o build/kernels_batch_gemm.o build/kernels_batch_ks.o build/kernels_batch_mx.o build/kernels_batched.o build/kernels_sample_mb.o build/dtk_api.o build/dtk_engine.o -pthread
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o $OUT/libdtk_hip.so "${objs[@]}" -pthread
 echo "built $OUT/libdtk_hip.so"

@@ -20,12 +20,8 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/dtk.h"
-#include "kernels.h"
+#include "dtk_ctx.h"
 #include "w13.h"
-#ifndef W13_DEFAULT
-#define W13_DEFAULT 1      // option "w13" of a new context (on: DESIGN 3.1c'')
-#endif
 #include "mx_quant.h"
 
 int& dtk_lds_attr_error(int device) {     // common.h: set by a launcher whose hipFuncSetAttribute was refused, per device
@@ -41,303 +37,9 @@ thread_local std::string g_create_error;
 thread_local std::string g_thread_error;
 thread_local const void* g_thread_error_ctx = nullptr;
 
-struct TensorEntry {
-  std::string name;
-  bf16_t* ptr = nullptr;   // destination (view into the arena)
-  int64_t rows = 1;        // logical rows
-  int64_t cols = 0;        // logical row length (elements)
-  int64_t stride = 0;      // destination row stride (elements), >= cols
-  float synth_scale = 0.02f;
-  float synth_offset = 0.f;
-  bool loaded = false;     // written by dtk_load_tensor / dtk_fill_synthetic
-  int64_t numel() const { return rows * cols; }
-};
-
-struct SeqHost {   // host-side mirror of one sequence's decode state
-  std::vector<int64_t> cached_ids;
-  bool cached_with_image = false;  // the cached KV was computed with image features spliced in
-  uint64_t image_key = 0;          // ... of the image with this caller-supplied key (0 = unknown: never reused across images)
-  int host_next_pos = 0;           // tokens with KV after all launched steps
-  bool have_logits = false;
-  int share_src = -1;              // slot whose first share_len cached tokens are bit-identical to ours (dtk_kv_fork), or -1
-  int share_len = 0;
-  int last_reuse_start = 0;        // tokens of the previous cache the last prefill kept
-  int64_t forced_pending = -1;     // dtk_resume_slot's last id until the step that forwards it is launched: part of the sequence, not yet of cached_ids
-};
-
-struct LayerW {
-  bf16_t *wqkv, *wo, *wgu, *wdown, *ln1, *ln2;
-  bf16_t *t_wqkv = nullptr, *t_wo = nullptr, *t_wgu = nullptr, *t_wdown = nullptr;  // fragment-major copies (batched decode)
-  bf16_t *p_wqkv = nullptr, *p_wo = nullptr, *p_wgu = nullptr, *p_wdown = nullptr;  // fragment-major bf16 copies the prefill GEMMs stream (= t_* where those exist)
-  bf16_t* p_wgui = nullptr;          // gate/up again with its row tiles in (gate, up) pair order: the W stage of the SwiGLU-fused prefill GEMM (models whose gate/up role is one chain)
-  uint8_t *q_wqkv = nullptr, *q_wo = nullptr, *q_wgu = nullptr, *q_wdown = nullptr;  // fp8 e4m3 copies (weight_format 1)
-  float *s_wqkv = nullptr, *s_wo = nullptr, *s_wgu = nullptr, *s_wdown = nullptr;    // per-row power-of-two scales
-  uint8_t *f4_wqkv = nullptr, *f4_wo = nullptr, *f4_wgu = nullptr, *f4_wdown = nullptr;  // MXFP4 E2M1 codes (weight_format 2): [N][ceil(K/32)*16] bytes
-  uint8_t *e4_wqkv = nullptr, *e4_wo = nullptr, *e4_wgu = nullptr, *e4_wdown = nullptr;  // ... and their E8M0 block scales: [N][ceil(K/32)]
-  uint8_t *p13_wqkv = nullptr, *p13_wo = nullptr, *p13_wgu = nullptr, *p13_wdown = nullptr;  // 13-bit planes of the bf16 rows (w13.h; bf16 contexts, option "w13"): null = not packed
-  uint8_t *h13_wqkv = nullptr, *h13_wo = nullptr, *h13_wgu = nullptr, *h13_wdown = nullptr;  // ... and the rows' hb bytes
-  uint8_t *t8_wqkv = nullptr, *t8_wo = nullptr, *t8_wgu = nullptr, *t8_wdown = nullptr;  // fp8 pair-tiled copies (batched decode, fp8)
-  uint8_t *m_wqkv = nullptr, *m_wo = nullptr, *m_wgu = nullptr, *m_wdown = nullptr;      // fp8 MX tiles (fp8 matrix-core step; down in groups of 16)
-};
-struct VitBlockW {
-  bf16_t *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
-};
-// one CrossAttentionLayer of the TikZero adapter (reference adapter/modeling_adapter.py) + the text's keys / values it attends to
-struct CrossW {
-  bf16_t *ln1w, *ln1b, *qw, *qb, *kw, *kb, *vw, *vb, *ow, *ob, *qnw, *qnb, *knw, *knb, *ln2w, *ln2b, *f1w, *f1b, *f2w, *f2b;
-  bf16_t *gate_a, *gate_m;           // cross_attn_attn_gate / cross_attn_mlp_gate: one bf16 logit each
-  bf16_t *K, *V;                     // the cached text's k_norm(k_proj(c)) / v_proj(c): [text_max][D]
-};
-struct Adapter {
-  dtk_adapter_config cfg{};
-  dtk_ctx* emb = nullptr;            // the embedding model: a decoder-only context (its tower is a 1-patch stub that never runs)
-  unsigned char* arena = nullptr;
-  size_t first_tensor = 0;           // the adapter's entries are the tail of the owner's tensor table from here on
-  bf16_t *conn_w = nullptr, *conn_b = nullptr, *dummy = nullptr, *ctext = nullptr;
-  std::vector<CrossW> layers;        // per ViT block; present[i]: a cross layer runs before block i
-  std::vector<char> present;
-  std::vector<int64_t> text_ids;     // the text whose connector output and k / v are cached (empty: none)
-  std::vector<float> dummy_host;     // dummy_input.clamp(-1, 1) as fp32 pixels (empty: not built since the last weight load)
-};
-
 }  // namespace
 
-struct dtk_ctx {
-  dtk_config cfg;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  std::mutex err_mu;
-  // dtk_vit_encode (own stream, any thread: the SelfSim rewards) and a prefill (the engine's loop thread) share the ViT activation
-  // buffers and `cur_stream`: one at a time
-  std::mutex vit_mu;
-
-  // derived sizes
-  int d, L, H, ff, V, Tmax, S;           // S: split-K factor of the single-sequence decode attention
-  int vD, vDepth, vH, vHd, vMlp, vN, vPatchK, vPatchLd, nImg;
-
-  // weights
-  unsigned char* arena = nullptr;
-  size_t arena_bytes = 0;
-  std::vector<TensorEntry> tensors;
-  std::unordered_map<std::string, int> tindex;
-  std::vector<LayerW> layers;
-  bf16_t *embed, *final_norm, *lm_head, *mm_w, *mm_b;
-  bf16_t *rope_cos, *rope_sin;
-  std::vector<VitBlockW> vblocks;
-  bf16_t *pe_w, *pe_b, *pos_embed, *vnorm_w, *vnorm_b;
-  bf16_t *ap_latent, *ap_qw, *ap_qb, *ap_kvw, *ap_kvb, *ap_pw, *ap_pb, *ap_nw, *ap_nb, *ap_f1w,
-      *ap_f1b, *ap_f2w, *ap_f2b;
-
-  // KV cache [L][2][KVH][Tmax][hd]
-  bf16_t* kv = nullptr;
-
-  // activations: decoder prefill
-  bf16_t *X, *Xn, *QKV, *Qh, *AO, *GU, *ACT;
-  int sk_sl_min_rows = SK_SL_MIN_ROWS;   // above this many rows a sliced role is one launch with the slices folded in registers (dtk_set_option "sk_sl_min_rows"; bit-identical)
-  float* skpart = nullptr;           // fp32 partials of the sliced-K prefill GEMMs: [kslices][SK_CHUNK_ROWS][N], one role at a time
-  size_t skpart_floats = 0;
-  int swiglu_fused = 1;              // gate/up's epilogue is SiLU*mul (dtk_set_option "swiglu_fused"; bit-identical)
-  int qkv_rope_fused = 1;            // a sliced q/k/v role reduces inside the RoPE + KV-append kernel (dtk_set_option "qkv_rope_fused"; bit-identical)
-  int prefill_sk = 1;                // sliced-K prefill GEMMs for the roles with <= 128 tiles of 256 x 128 (dtk_set_option "prefill_sk": 0 = the one-chain kernels, 2 / 4 / 8 = a cap on the slices)
-  int32_t* ids_dev = nullptr;
-  // dtk_score / dtk_score_packed: records of the log-softmax lm_head ([max_positions][ceil(V / 128)] x 16 B: a packed pass behind a one-token prompt scores max_positions rows) + the per-row results; allocated by the first
-  // scoring call and kept (hipMalloc of its own, not the arena: a context that never scores pays nothing)
-  float* score_rec = nullptr;
-  float* score_out = nullptr;         // [4][max_positions]: logprob, lse, argmax (int32), z[argmax]
-  float* score_top = nullptr;         // dtk_score_top: [2][max_positions][DTK_MAX_TOP]: ids (int32), logprob; allocated by the first call with k > 0
-  // dtk_score_packed: the row tables of one packed pass, [6][max_positions] int32 — {position, cache row} and {segment begin, cache row}
-  // per row (int2 each), the rows' input ids, the scored rows' targets; allocated by the first packed call and kept
-  int32_t* packed_rows = nullptr;
-  // decode step
-  bf16_t *x, *q, *act;
-  float *logits, *pm, *pl, *po;
-  bf16_t* attn_out = nullptr;        // combined attention output [d] (in-kernel combine)
-  unsigned* attn_ctr = nullptr;      // [H] arrival tickets
-  int attn_combine = 0;              // 0: consumer (o_proj prologue), 1: last-arriver in k_attn_decode, 2: own kernel
-  DecState* st = nullptr;
-  SamplingDev* sp = nullptr;
-  int64_t* tok_ring_dev = nullptr;   // device ring
-  int64_t* tok_ring_host = nullptr;  // pinned host mirror
-  float* probs_dev = nullptr;        // op_sample output
-  // dtk_set_option "logprobs": (logprob, sample_logprob) of every sampled token, rings parallel to tok_ring_* / tokb_* (same index)
-  int logprobs = 0;
-  std::atomic<int> engine_holds{0};  // sequences an engine of dtk_engine_create holds in this context's slots (joined, not yet left)
-  float2* lp_ring_dev = nullptr;     // [DTK_MAX_INFLIGHT]
-  float2* lp_ring_host = nullptr;    // pinned mirror
-  float2* lpb_dev = nullptr;         // [DTK_MAX_INFLIGHT][DTK_MAX_BATCH] (contexts with slots)
-  float2* lpb_host = nullptr;
-  // dtk_set_option "top_logprobs" = k (needs "logprobs"): every step also leaves the k most likely tokens of the logits it sampled from
-  // (k_top_logits, in front of the sampler) and the logsumexp its logprob was taken against; rings indexed as lp_ring / lpb.  Allocated
-  // (hipMalloc / pinned, not the arena) when the option is first switched on
-  int top_logprobs = 0;
-  TopRec* top_ring_dev = nullptr;    // [DTK_MAX_INFLIGHT]
-  TopRec* top_ring_host = nullptr;
-  float* lse_ring_dev = nullptr;     // [DTK_MAX_INFLIGHT]
-  float* lse_ring_host = nullptr;
-  TopRec* topb_dev = nullptr;        // [DTK_MAX_INFLIGHT][DTK_MAX_BATCH] (contexts with slots)
-  TopRec* topb_host = nullptr;
-  float* lseb_dev = nullptr;
-  float* lseb_host = nullptr;
-  // ViT
-  float* pixels_dev = nullptr;
-  bf16_t *patches, *VX, *VN, *VQKV, *VAO, *VH, *feats, *last_hidden;
-  bf16_t *pq, *pkv, *pao, *px, *pn, *ph, *pooled;
-  bf16_t* IMG;  // projected image embeddings [nImg][d]
-  Adapter* ad = nullptr;             // TikZero text adapter (dtk_adapter_create), or none
-  // op-level scratch
-  unsigned char* scratch = nullptr;
-  size_t scratch_bytes = 0;
-
-  // host state
-  SeqHost seq0;              // the single-sequence API (dtk_prefill / dtk_decode*)
-  int wfmt = 0;              // 0 = bf16 decoder weights, 1 = fp8 e4m3 + per-row 2^e scale, 2 = MXFP4 layers + fp8 lm_head (dtk_config.reserved[1])
-  bool fp8_ready = false;    // the quantised copies of wfmt 1 / 2 match the bf16 masters
-  uint8_t* q_lm_head = nullptr;
-  float* s_lm_head = nullptr;
-  // 13-bit planes of the bf16 rows for the single-sequence step (w13.h): packed lazily by ensure_w13 from the bf16 masters, which stay
-  int w13 = W13_DEFAULT;     // dtk_set_option "w13"
-  int w13_nz = 1;            // dtk_set_option "w13_nz": 0 = the packer flags every row (W13_ZROW), so every row takes the general decode
-  bool w13_ready = false;    // the planes match the masters (load_tensor / fill_synthetic clear it)
-  uint8_t *p13_lm_head = nullptr, *h13_lm_head = nullptr;
-  unsigned* w13_bad = nullptr;                      // device counter of the packer
-  int w13_op_bad_rows = -1;                         // unpackable rows of the last dtk_op_gemv_role call that packed planes (-1: none yet)
-  uint32_t w13_packed = 0, w13_unpacked = 0, w13_bad_rows = 0;   // matrices with / without planes, unpackable rows (dtk_stats.w13_counts)
-  uint32_t w13_zrows[5] = {0, 0, 0, 0, 0};         // rows with W13_ZROW in their byte, per role of dtk_bench_gemv (dtk_w13_flagged_rows)
-  uint64_t cached_image_key = 0;
-  bool have_image = false;
-  // ---- batched decode (dtk_*_slot / dtk_decode_batch_*): up to 64 decoding slots (+1) with their own KV
-  int KVH = 0;                       // key/value heads (dtk_config.reserved[2]; 0 -> heads)
-  int hd = 128;                      // decoder head dim: 128, or 64 (TinyLlama; no batched slots)
-  bool proj_bias = true;             // mm_projector has a bias (v1) / bias-free connector (v2)
-  int nb = 0;                        // number of batch slots (dtk_config.reserved[0])
-  bool share_reads = true;           // forked slots read their shared prefix from the source slot (dtk_set_option "share_prefix_reads")
-  int nt = 1;                        // 16-slot column tiles of the batched kernels (2 when nb > 17)
-  std::vector<SeqHost> bseq;
-  bf16_t* kvb = nullptr;             // [nb][L][2][H][Tmax][128]
-  size_t kv_slot_stride = 0;
-  bf16_t *xb = nullptr, *xnb = nullptr, *qb = nullptr, *aob = nullptr, *actb = nullptr;  // [16][d|ff]
-  float* logits_b = nullptr;
-  float* kpart = nullptr; unsigned* kctr = nullptr;   // k_gemv_bk / k_gemv_bkp partial sums + arrival counters
-  int attn_nt = 1;             // batched attention: non-temporal loads of private K / V tiles (64 slots x 500 private keys: 7.14 -> 6.74 ms per step) (dtk_set_option "attn_nt")
-  bool resid_kparts = true;    // batched N = d roles at 64 slots as two launches (k_gemv_bkp + k_resid_norm_b; measured 20.2 -> 21.2 rollouts/s): dtk_set_option("resid_kparts")
-  float *pfx_m = nullptr, *pfx_l = nullptr, *pfx_o = nullptr;   // shared-prefix states [64][H][4] (+ x 128)
-  int prefix_mfma = 0;               // shared prefixes (forks of one image) scored once per group of <= 16 slots on the matrix cores (k_attn_prefix_g); dtk_set_option "prefix_mfma".
-                                     // Set at dtk_create from the context's size: 1 with 64 decoding slots, 0 below (see there)
-  int pfx_splits = 4;                // key splits of that kernel (its grid z)
-  int gqa_fused = 1;                 // batched attention: one block per (K/V head, slot) for GQA models
-  int tail_threads = 256;            // block of k_attn_tail_b (rows per memory round trip = threads / 4); dtk_create: 128 with 64 decoding slots (the blocks then walk
-                                     // private keys only and 2048 blocks of 2 waves are all resident), 256 below
-  DecState* st_b = nullptr;          // [16]
-  SamplingDev* sp_b = nullptr;       // [16]
-  BatchState* bs_dev = nullptr;
-  bf16_t* t_lm_head = nullptr;       // fragment-major copy of lm_head
-  uint8_t* t8_lm_head = nullptr;     // fp8 pair-tiled copy of lm_head (weight_format fp8)
-  // fp8 matrix-core step (kernels_batch_mx.hip; dtk_set_option "act_fp8"): the MFMA-family step of an fp8 model runs its GEMVs as
-  // v_mfma_scale_f32_16x16x128_f8f6f4 on MXFP8 activations.  mx_ok = the model's shapes are covered and the buffers exist
-  uint8_t* m_lm_head = nullptr;
-  uint8_t *xn8 = nullptr, *xns = nullptr, *ao8 = nullptr, *aos = nullptr, *act8 = nullptr, *acts = nullptr;
-  bool mx_ok = false;
-  // act_fp8: 0 (default since round 5) = bf16 activations (fp8 weights widened in registers, bf16 MFMA: rounds 1-3); 1 = opt-in.  MXFP8
-  // activations keep 3 mantissa bits: logits move ~1e-1 rel-L2 from the bf16-activation result (tests/test_gpu_parity_mx.py,
-  // test_mxfp8_activations_against_bf16_activations), so the faster step is the caller's choice, not the library's.
-  int act_fp8 = 0;
-  bool launch_refused = false;       // a launcher of the step being issued had no kernel for its shape (nothing was launched for that role)
-  bool tiled_ready = false;          // the fragment-major copies match the row-major weights
-  bool ptiled_ready = false;         // ... and the prefill's own (LayerW::p_*)
-  BatchState* bs_host = nullptr;     // pinned ring [DTK_MAX_INFLIGHT]
-  SamplingDev* sp_stage = nullptr; uint32_t* draw_stage = nullptr;   // pinned [DTK_MAX_SLOTS]: per-slot set_sampling uploads queued on the stream
-  DecState* st_stage = nullptr;      // pinned [DTK_MAX_SLOTS]: dtk_resume_slot's state upload (no stream sync: a slot is resumed again only sequences later)
-  int64_t* tokb_dev = nullptr;       // [DTK_MAX_INFLIGHT][16]
-  int64_t* tokb_host = nullptr;      // pinned mirror
-  uint64_t blaunched = 0, bwaited = 0;
-  hipEvent_t bstep_done[DTK_MAX_INFLIGHT] = {};
-  // one captured step per column-tile count (1, 2, 4 tiles of 16 slots): a step only pays for the tiles up to its highest
-  // active slot (32 trees on a 65-slot context run the 2-tile kernels)
-  // (+ three more for the multi-vector step of a context with <= 5 slots: 1, 2 or 4 vectors)
-  bool bgraph_ready[6] = {false, false, false, false, false, false};
-  hipGraph_t bgraph[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  hipGraphExec_t bgraph_exec[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  int nt_step = 1;                   // tile count of the step being launched / captured
-  // Contexts with at most 5 slots (<= 4 decoding + a prefix slot: BASELINE config 4's 2 / 4 trees per rank at N = 8 / 4) decode
-  // with the multi-vector kernels (kernels_decode_mv.hip): the single-sequence GEMVs carrying 1, 2 or 4 x vectors instead of a
-  // 16-column MFMA tile.  The kernel family is a property of the CONTEXT (slot count at dtk_create, dtk_set_option "mv_slots"),
-  // never of the active set, so a sequence's logits do not depend on which other slots happen to decode with it.
-  int mv_slots = 4;                  // contexts with nb <= mv_slots + 1 use the family (0 = never)
-  int mv_step = 0;                   // vectors of the step being launched / captured (0 = an MFMA step)
-  int mv_tail_threads = 512;         // block of k_attn_tail_b in a multi-vector step (few blocks: more rows per round trip)
-  dtk_sampling sampling{};
-  SampleMB* smb = nullptr;           // multi-block sampler scratch (single sequence) / per slot
-  SampleMB* smb_b = nullptr;
-  bool mb_single = false;            // the captured single-sequence graph uses the multi-block sampler
-  bool mb_batch = false;             // ... the batched graph
-  bool slot_topk[DTK_MAX_SLOTS] = {};   // slots whose sampling needs top-k (single-block sampler only)
-  bool slot_samples[DTK_MAX_SLOTS] = {}; // slots that sample (not greedy)
-  // min_p / epsilon_cutoff (dtk_set_sampling_ext): which sampler instantiations the next captures must contain, and which the captured
-  // graphs do contain (ensure_graph / ensure_batch_graph drop a graph of the other kind: a sequence with the values set again after
-  // the reset of dtk_set_sampling keeps its graph)
-  dtk_sampling_ext sampling_ext{};
-  bool trunc_single = false, graph_trunc = false;
-  bool slot_trunc[DTK_MAX_SLOTS] = {};
-  bool trunc_batch = false, bgraph_trunc = false;
-  // presence / frequency penalties (dtk_set_penalties): sequence 0 is the single one, 1 + slot a slot's.  Everything below is allocated
-  // by the first call that sets a non-zero value (pen_alloc), so a context that never uses penalties allocates and launches nothing.
-  // pen_single / pen_batch: which sampler instantiations the next captures must contain, graph_pen / bgraph_pen: which the captured graphs
-  // do contain (as trunc_single / graph_trunc)
-  uint16_t* pen_tab = nullptr;       // [1 + nb][pen_stride] count tables
-  int pen_stride = 0;
-  PenDev* pen_dev = nullptr;         // [1 + DTK_MAX_SLOTS]
-  int32_t* pen_tok = nullptr;        // [1 + DTK_MAX_SLOTS] the step's sampled token, consumed by k_count_token (-1: nothing to count)
-  int32_t* pen_ids_dev = nullptr;    // [1 + nb][Tmax] the ids a rebuild scatters
-  int32_t* pen_ids_stage = nullptr;  // pinned mirror: a slot's rebuild is queued behind the step in flight, no drain
-  PenDev* pen_stage = nullptr;       // pinned [1 + DTK_MAX_SLOTS]
-  PenDev pen_val[1 + DTK_MAX_SLOTS] = {};   // the values as set
-  int pen_start[1 + DTK_MAX_SLOTS] = {};    // penalty_start
-  bool pen_single = false, graph_pen = false;
-  bool pen_batch = false, bgraph_pen = false;
-  // DRY (dtk_set_dry), indexed like the penalties: sequence 0 is the single one, 1 + slot a slot's.  Everything below is allocated by the
-  // first call that sets a multiplier != 0 (dry_alloc, which also makes the penalties' records exist: DRY rides the PN samplers and shares
-  // pen_tok and the trailing kernel), so a context that never uses DRY allocates and launches nothing.  dry_single / dry_batch and
-  // graph_dry / bgraph_dry as pen_single / graph_pen
-  uint8_t* dry_tab = nullptr;        // [1 + nb][dry_stride] match length per id, left by k_dry_scan for the step's sampler
-  int dry_stride = 0;
-  DryDev* dry_dev = nullptr;         // [1 + DTK_MAX_SLOTS]
-  DryDev* dry_stage = nullptr;       // pinned [1 + DTK_MAX_SLOTS]
-  int32_t* dry_hist = nullptr;       // [1 + nb][Tmax] the ids at positions [dry_start, next_pos)
-  int32_t* dry_hist_stage = nullptr; // pinned mirror a rebuild fills
-  DryLen* dry_len = nullptr;         // [1 + DTK_MAX_SLOTS]
-  DryLen* dry_len_stage = nullptr;   // pinned
-  int32_t* dry_touched = nullptr;    // [1 + nb][Tmax] the ids the last scan set
-  int32_t* dry_ntouched = nullptr;   // [1 + DTK_MAX_SLOTS]
-  DryDev dry_val[1 + DTK_MAX_SLOTS] = {};   // the records as set
-  int dry_start[1 + DTK_MAX_SLOTS] = {};    // dry_start
-  bool dry_live[1 + DTK_MAX_SLOTS] = {};    // the sequence's table / history may hold something (it has, or had, a multiplier)
-  bool dry_single = false, graph_dry = false;
-  bool dry_batch = false, bgraph_dry = false;
-  uint64_t launched = 0, waited = 0;
-  hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
-  // dtk_vit_encode (the SelfSim reward's ViT passes) runs on its own stream so it overlaps with decode steps of other
-  // sequences; the caller serialises it with prefills (they share the ViT activation buffers), see model/modeling.py
-  hipStream_t stream_vit = nullptr;
-  hipStream_t cur_stream = nullptr;   // stream of the GEMMs being issued (vit_forward sets it)
-  hipEvent_t ev_va = nullptr, ev_vb = nullptr;
-  hipEvent_t probe_a = nullptr, probe_b = nullptr;
-  bool use_graph = true;
-  bool graph_ready = false;
-  hipGraph_t graph = nullptr, graph_short = nullptr;
-  hipGraphExec_t graph_exec = nullptr, graph_short_exec = nullptr;
-  int attn_full_max = 0;             // contexts below this use the one-block-per-head attention (measured slower: off)
-  int attn_threads = 0;              // decode attention: 0 = k_attn_decode (contiguous key range per split), 256 | 512 | 1024 = k_attn_decode_t
-  int attn_impl = 0;                 // prefill / ViT attention kernel: 0 auto, 1 VALU, 2 MFMA flash (dtk_set_option "attn_impl")
-  bool gemm_naive = false;
-  int probe = 0;
-  bool probe_pending = false;
-  dtk_stats stats{};
-};
-
-namespace {
-
+// ---- dtk_ctx.h's helpers (shared with dtk_ops.hip)
 int fail(dtk_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -353,14 +55,6 @@ int fail(dtk_ctx* c, int code, const char* fmt, ...) {
   }
   return code;
 }
-
-#define HIPCHK(c, call)                                                                   \
-  do {                                                                                    \
-    hipError_t e_ = (call);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail((c), DTK_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                  __FILE__, __LINE__);                                                    \
-  } while (0)
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -385,6 +79,8 @@ float host_h2f(uint16_t h) {
   else v = ldexpf((float)(man | 0x400u), (int)exp - 25);
   return sign ? -v : v;
 }
+
+namespace {
 
 // ---- arena planning: first pass sums sizes, second pass hands out pointers
 struct Planner {
@@ -731,7 +427,11 @@ bool qkv_rope_fused(dtk_ctx* c, const LayerW& w, int n, int start, bf16_t* kc, b
   return true;
 }
 
+}  // namespace
+
 int gelu_flag(const dtk_ctx* c) { return c->cfg.vit_gelu_tanh ? GEMM_GELU_TANH : GEMM_GELU_ERF; }
+
+namespace {
 
 bf16_t* kcache(dtk_ctx* c, int layer) { return c->kv + (size_t)layer * 2 * c->KVH * c->Tmax * c->hd; }
 bf16_t* vcache(dtk_ctx* c, int layer) { return kcache(c, layer) + (size_t)c->KVH * c->Tmax * c->hd; }
@@ -1475,7 +1175,9 @@ static int pen_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one
   return DTK_OK;
 }
 
-static int pen_check(dtk_ctx* c, float pp, float fp, int start, const char* who) {
+// (extern "C++" here and below: a helper dtk_ops.hip calls too — declared in dtk_ctx.h with C++ linkage and hidden visibility, which the
+// definition inside this extern "C" / default-visibility region keeps)
+extern "C++" int pen_check(dtk_ctx* c, float pp, float fp, int start, const char* who) {
   if (!(pp >= -2.f && pp <= 2.f)) return fail(c, DTK_ERR_ARG, "%s: presence_penalty must be in [-2, 2]", who);
   if (!(fp >= -2.f && fp <= 2.f)) return fail(c, DTK_ERR_ARG, "%s: frequency_penalty must be in [-2, 2]", who);
   if (start < 0) return fail(c, DTK_ERR_ARG, "%s: penalty_start must be >= 0", who);
@@ -1563,7 +1265,7 @@ static int dry_rebuild(dtk_ctx* c, int q, const int64_t* ids, int n, int64_t one
   return DTK_OK;
 }
 
-static int dry_check(dtk_ctx* c, const dtk_dry* d, int V, const char* who) {
+extern "C++" int dry_check(dtk_ctx* c, const dtk_dry* d, int V, const char* who) {
   if (!d) return fail(c, DTK_ERR_ARG, "%s: no dtk_dry", who);
   if (!(d->multiplier >= 0.f && d->multiplier <= 100.f)) return fail(c, DTK_ERR_ARG, "%s: dry_multiplier must be in [0, 100]", who);
   if (!(d->base >= 1.f && d->base <= 8.f)) return fail(c, DTK_ERR_ARG, "%s: dry_base must be in [1, 8]", who);
@@ -1577,7 +1279,7 @@ static int dry_check(dtk_ctx* c, const dtk_dry* d, int V, const char* who) {
 
 // the device record of a dtk_dry: pen[L] = 0 below allowed_length, then multiplier * base^(L - allowed_length) by repeated multiplication
 // in double, clamped to 1e30 (include/dtk.h: the oracle reproduces it bit for bit)
-static DryDev dry_record(const dtk_dry* d) {
+extern "C++" DryDev dry_record(const dtk_dry* d) {
   DryDev v{};
   if (!d || d->multiplier == 0.f) return v;
   v.on = 1; v.allowed = d->allowed_length; v.n_brk = d->n_breakers;
@@ -2556,16 +2258,13 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
 }
 
 // min_p / epsilon_cutoff of the configuration the last dtk_set_sampling[_slot] left at sp_dst: the two fields alone are rewritten
-static int ext_check(dtk_ctx* c, const dtk_sampling_ext* x, const char* who) {
+extern "C++" int ext_check(dtk_ctx* c, const dtk_sampling_ext* x, const char* who) {
   if (!x) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
   if (!(x->min_p >= 0.f && x->min_p <= 1.f)) return fail(c, DTK_ERR_ARG, "%s: min_p must be in [0, 1]", who);
   if (!(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f)) return fail(c, DTK_ERR_ARG, "%s: epsilon_cutoff must be in [0, 1)", who);
   return DTK_OK;
 }
-struct ExtDev { int64_t qmin; float eps; };       // SamplingDev's tail
-static_assert(offsetof(SamplingDev, eps) - offsetof(SamplingDev, qmin) == offsetof(ExtDev, eps) &&
-              sizeof(SamplingDev) - offsetof(SamplingDev, qmin) == sizeof(ExtDev), "SamplingDev ends with (qmin, eps)");
-static inline ExtDev ext_dev(const dtk_sampling_ext* x) {
+extern "C++" ExtDev ext_dev(const dtk_sampling_ext* x) {
   ExtDev d{};
   d.qmin = (int64_t)((double)x->min_p * 2147483648.0); d.eps = x->epsilon_cutoff;
   return d;
@@ -2690,7 +2389,7 @@ int dtk_max_decode_slots(const dtk_ctx* c) { return (c && c->nb > 0) ? max_decod
 // order.  A source slot that decodes itself is not a member of its forks' groups (that WOULD depend on the others); more than
 // DTK_PFX_GROUPS = 64 groups cover the worst case (64 slots that share nothing), so no slot ever falls back because of its company.
 // hb->active / share_src / share_len are read; n_groups, group_plus1, pfx_len_of and groups are written (enabled = false: no groups).
-static void build_prefix_groups(BatchState* hb, const int32_t* active, bool enabled) {
+extern "C++" void build_prefix_groups(BatchState* hb, const int32_t* active, bool enabled) {
   hb->n_groups = 0;
   for (int j = 0; j < DTK_MAX_BATCH; ++j) { hb->group_plus1[j] = 0; hb->pfx_len_of[j] = 0; }
   if (!enabled) return;
@@ -3425,19 +3124,6 @@ int dtk_set_gemv_variant(dtk_ctx* c, int epi, int variant) {
   return DTK_OK;
 }
 
-// ------------------------------------------------------------------ op-level test entry points
-static int op_scratch(dtk_ctx* c, size_t bytes, size_t& off, void** p) {
-  off = align_up(off, 256);
-  if (off + bytes > c->scratch_bytes) return fail(c, DTK_ERR_ARG, "op scratch exhausted (%zu bytes)", off + bytes);
-  *p = c->scratch + off;
-  off += bytes;
-  return DTK_OK;
-}
-#define OPBUF(T, var, n)                                                    \
-  T* var = nullptr;                                                         \
-  { void* p_; int rc_ = op_scratch(c, (size_t)(n) * sizeof(T), off, &p_); if (rc_) return rc_; var = (T*)p_; }
-
-
 // ---- TikZero adapter (ABI 7) ------------------------------------------------------------------------------------------------------
 static void plan_adapter(dtk_ctx* c, Adapter& A, Planner& P, bool reg) {
   const int D = c->vD, mlp = c->vMlp, hd = c->vHd, de = A.cfg.hidden, Tt = A.cfg.text_max;
@@ -3668,1366 +3354,6 @@ int dtk_adapter_embed(dtk_ctx* c, const int64_t* text_ids, int T_text, void* hid
   return DTK_OK;
 }
 
-int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual, int M, int N, int K, int flags, uint16_t* C) {
-  if (!c || !A || !W || !C || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemm: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dB, N);
-  OPBUF(bf16_t, dR, (size_t)M * N); OPBUF(bf16_t, dC, (size_t)M * N);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-  int gf = 0;
-  if ((flags & (DTK_EPI_BIAS | DTK_EPI_GELU)) && bias) { HIPCHK(c, hipMemcpyAsync(dB, bias, (size_t)N * 2, hipMemcpyHostToDevice, s)); gf |= GEMM_BIAS; }
-  if (flags & DTK_EPI_GELU) gf |= gelu_flag(c);
-  if ((flags & DTK_EPI_RESIDUAL) && residual) { HIPCHK(c, hipMemcpyAsync(dR, residual, (size_t)M * N * 2, hipMemcpyHostToDevice, s)); gf |= GEMM_RESIDUAL; }
-  GemmArgs g;
-  g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = dB; g.residual = dR; g.ldr = N; g.C = dC; g.ldc = N;
-  g.M = M; g.N = N; g.K = K; g.flags = gf;
-  if (flags & DTK_GEMM_WT) {          // + the fragment-major copy of W (k_gemm_g3's W stage is filled from it)
-    OPBUF(bf16_t, dWt, tiled_elems(N, K));
-    launch_retile(dW, dWt, N, K, s);
-    g.Wt = dWt;
-  }
-  const int S = (flags >> DTK_GEMM_KSLICES_SHIFT) & 15;       // 0 = a one-chain GEMM; 1..8 = the sliced-K family (1: one slice through the partial + reduce path)
-  if (S) {
-    if (S > 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemm: at most 8 K slices");
-    g.kslices = S;
-    if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s);
-    else {
-      OPBUF(float, dP, (size_t)S * M * N);
-      g.part = dP; g.part_stride = (long)M * N;
-      if (flags & DTK_GEMM_SL) { if (!launch_gemm_g3_sliced(g, s)) return fail(c, DTK_ERR_ARG, "dtk_op_gemm: the in-register sliced kernel does not take this shape"); }
-      else if (!launch_gemm_sk(g, nullptr, nullptr, 0, 0.f, s)) return fail(c, DTK_ERR_ARG, "dtk_op_gemm: the sliced-K kernel does not take this shape");
-    }
-  }
-  else if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s); else launch_gemm_mfma(g, s);
-  HIPCHK(c, hipMemcpyAsync(C, dC, (size_t)M * N * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-int dtk_op_score(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
-                 float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out) {
-  return dtk_op_score_top(c, Xn, W, targets, M, N, K, flags, logprob_out, lse_out, argmax_out, zmax_out, 0, nullptr, nullptr, nullptr);
-}
-
-int dtk_op_score_top(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
-                     float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out, int k, int32_t* top_ids_out,
-                     float* top_logprob_out, float* top_z_out) {
-  if (!c || !Xn || !W || !targets || !logprob_out || M < 1 || N < 1 || K < 8 || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_score: bad argument");
-  if (k != 0 || top_ids_out || top_logprob_out || top_z_out) {
-    if (k < 1 || k > DTK_MAX_TOP || k > N) return fail(c, DTK_ERR_ARG, "dtk_op_score_top: k = %d (1 .. min(DTK_MAX_TOP = %d, N), or 0 with NULL outputs)", k, DTK_MAX_TOP);
-    if (!top_ids_out || !top_logprob_out) return fail(c, DTK_ERR_ARG, "dtk_op_score_top: k = %d needs top_ids_out and top_logprob_out", k);
-  }
-  for (int m = 0; m < M; ++m)
-    if (targets[m] < 0 || targets[m] >= N) return fail(c, DTK_ERR_ARG, "dtk_op_score: target %d of row %d outside [0, %d)", targets[m], m, N);
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(int32_t, dT, M);
-  OPBUF(float, dRec, score_rec_floats(M, N)); OPBUF(float, dO, (size_t)4 * M);
-  OPBUF(float, dTop, (size_t)3 * M * DTK_MAX_TOP);       // ids (int32), logprob, z: [M][k] each
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dA, Xn, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dT, targets, (size_t)M * 4, hipMemcpyHostToDevice, s));
-  GemmArgs g;
-  g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = nullptr; g.residual = nullptr; g.ldr = 0; g.C = nullptr; g.ldc = 0;
-  g.M = M; g.N = N; g.K = K; g.flags = 0; g.ls_target = dT; g.ls_rec = dRec;
-  if (flags & DTK_GEMM_WT) {
-    OPBUF(bf16_t, dWt, tiled_elems(N, K));
-    launch_retile(dW, dWt, N, K, s);
-    g.Wt = dWt;
-  }
-  if (!launch_gemm_logsoftmax(g, s)) return fail(c, DTK_ERR_ARG, "dtk_op_score: the kernel does not take this shape");
-  launch_score_merge(dRec, M, N, dO, dO + M, reinterpret_cast<int32_t*>(dO + 2 * (size_t)M), dO + 3 * (size_t)M, s);
-  if (k > 0) {
-    const size_t mk = (size_t)M * k;
-    launch_score_top(g, dO + M, k, reinterpret_cast<int32_t*>(dTop), dTop + mk, dTop + 2 * mk, s);
-    HIPCHK(c, hipMemcpyAsync(top_ids_out, dTop, mk * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(top_logprob_out, dTop + mk, mk * 4, hipMemcpyDeviceToHost, s));
-    if (top_z_out) HIPCHK(c, hipMemcpyAsync(top_z_out, dTop + 2 * mk, mk * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(c, hipMemcpyAsync(logprob_out, dO, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-  if (lse_out) HIPCHK(c, hipMemcpyAsync(lse_out, dO + M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-  if (argmax_out) HIPCHK(c, hipMemcpyAsync(argmax_out, dO + 2 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-  if (zmax_out) HIPCHK(c, hipMemcpyAsync(zmax_out, dO + 3 * (size_t)M, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-int dtk_op_gemm_gated(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t* bias, const uint16_t* residual,
-                      const uint16_t* gate, int M, int N, int K, int flags, uint16_t* C) {
-  if (!c || !A || !W || !C || !bias || !residual || !gate || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemm_gated: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dA, (size_t)M * K); OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dB, N);
-  OPBUF(bf16_t, dR, (size_t)M * N); OPBUF(bf16_t, dC, (size_t)M * N); OPBUF(bf16_t, dG, 8);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dA, A, (size_t)M * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dB, bias, (size_t)N * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dR, residual, (size_t)M * N * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dG, gate, 2, hipMemcpyHostToDevice, s));
-  GemmArgs g;
-  g.A = dA; g.lda = K; g.W = dW; g.ldw = K; g.bias = dB; g.residual = dR; g.ldr = N; g.C = dC; g.ldc = N;
-  g.M = M; g.N = N; g.K = K; g.flags = GEMM_BIAS | GEMM_RESIDUAL | GEMM_GATED_RESIDUAL; g.gate = dG;
-  if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s); else launch_gemm_mfma(g, s);
-  HIPCHK(c, hipMemcpyAsync(C, dC, (size_t)M * N * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-int dtk_op_gemv(dtk_ctx* c, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w, int N, int K, int mode, float eps, uint16_t* y) {
-  if (!c || !W || !x || !y || K % 8) return fail(c, DTK_ERR_ARG, "dtk_op_gemv: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dy, N);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)K * 2, hipMemcpyHostToDevice, s));
-  if (mode == 1) { if (!norm_w) return fail(c, DTK_ERR_ARG, "norm_w required"); HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s)); }
-  GemvArgs g{};
-  g.W = dW; g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.y = dy;
-  launch_gemv(mode == 1 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, g, s);
-  HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)N * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-// The MXFP4 GEMV on host buffers: W [N][K] row-major bf16 goes through the shipped quantiser (launch_quant_mxfp4_rows) and the shipped
-// launch_gemv with EPI_STORE (mode 0: y = W_eff . x, mode 1: y = W_eff . rmsnorm(x, norm_w)); w_eff_out (optional, [N][K]) receives the
-// de-quantised weights the kernel computed with.  Any context serves (the op brings its own weights).
-int dtk_op_gemv_q4(dtk_ctx* c, const uint16_t* W, const uint16_t* x, const uint16_t* norm_w, int N, int K, int mode, float eps, uint16_t* y, uint16_t* w_eff_out) {
-  if (!c || !W || !x || !y || N < 1 || K < 8 || (K % 8) || (mode != 0 && mode != 1) || (mode == 1 && !norm_w)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_q4: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dy, N);
-  OPBUF(uint8_t, dQ, (size_t)N * mxfp4_row_bytes(K)); OPBUF(uint8_t, dS, (size_t)N * mxfp4_row_scales(K));
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)K * 2, hipMemcpyHostToDevice, s));
-  if (mode == 1) HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
-  launch_quant_mxfp4_rows(dW, dQ, dS, N, K, s);
-  GemvArgs g{};
-  g.W = dW; g.W4 = dQ; g.S4 = dS; g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.y = dy;
-  launch_gemv(mode == 1 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, g, s);
-  HIPCHK(c, hipMemcpyAsync(y, dy, (size_t)N * 2, hipMemcpyDeviceToHost, s));
-  if (w_eff_out) HIPCHK(c, hipMemcpyAsync(w_eff_out, dW, (size_t)N * K * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-// nb (1, 2 or 4) input vectors through k_gemv_mv: y[b] = W . x[b] (mode 0) or W . rmsnorm(x[b], norm_w) (mode 1); per vector
-// the result must equal dtk_op_gemv's bit for bit (same lane / chunk order, same wave reduction, same block size)
-int dtk_op_gemv_mv(dtk_ctx* c, const uint16_t* W, const uint16_t* X, const uint16_t* norm_w, int N, int K, int mode, float eps, int nb, uint16_t* Y) {
-  if (!c || !W || !X || !Y || N < 1 || K < 8 || (K & 7) || (nb != 1 && nb != 2 && nb != 4) || (mode == 1 && !norm_w))
-    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mv: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dW, (size_t)N * K);
-  OPBUF(bf16_t, dX, (size_t)nb * K);
-  OPBUF(bf16_t, dG, (size_t)K);
-  OPBUF(bf16_t, dY, (size_t)nb * N);
-  HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)nb * K * 2, hipMemcpyHostToDevice, c->stream));
-  if (norm_w) HIPCHK(c, hipMemcpyAsync(dG, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, c->stream));
-  GemvMvArgs g{};
-  g.W = dW; g.N = N; g.K = K; g.X = dX; g.ldx = K; g.x_rowmajor = 1; g.norm_w = dG; g.eps = eps; g.Y = dY; g.ldy = N; g.d = K; g.ff = N;
-  launch_gemv_mv(mode == 1 ? PRO_RMSNORM : PRO_COPY, EPI_STORE, nb, g, c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(Y, dY, (size_t)nb * N * 2, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return DTK_OK;
-}
-
-// Where value k of slot `slot` and the E8M0 scale of its group live in the MXFP8 buffers (csrc/mx_quant.h): pure host arithmetic (no
-// GPU, no context) — tests/test_mx_layout.py checks on the CPU that this fragment order is the inverse of the operand map the
-// instruction was measured to have.
-int dtk_mx_layout(int G, int slot, int k, int64_t* data_off, int64_t* scale_off) {
-  if ((G != 32 && G != 16) || slot < 0 || slot >= DTK_MAX_BATCH || k < 0 || !data_off || !scale_off) return DTK_ERR_ARG;
-  *data_off = (int64_t)(G == 32 ? mx32_off(slot, k) : mx16_off(slot, k));
-  *scale_off = (int64_t)(G == 32 ? mx32_soff(slot, k) : mx16_soff(slot, k));
-  return DTK_OK;
-}
-
-// The fp8 matrix-core GEMVs of kernels_batch_mx.hip on host buffers.  W8 [N][K] e4m3 bytes + wscale [N]; X [nslots][K] bf16 rows,
-// quantised to MXFP8 (groups of G = 32 | 16) by the step's own quantiser; nslots = 16 | 32 | 64 (1 / 2 / 4 slot tiles).
-//   mode 0: unit kernel, logits epilogue (G = 32): Y [nslots][N] = bf16-rounded acc * wscale
-//   mode 1: K-slice kernel of the N = d roles: Y [nslots][N] = the 8 slice partials added in order (fp32)
-//   mode 2: unit kernel, SwiGLU epilogue (G = 32 in, N = 2 ff): y8_out / ys_out = the activation as MXFP8 groups of 16 (mx_x_bytes(ff, 16) / mx_s_bytes)
-// x8_out / xs_out (optional): the quantised input as the kernels read it.
-int dtk_op_gemv_mx(dtk_ctx* c, const uint8_t* W8, const float* wscale, const uint16_t* X, int N, int K, int G, int nslots, int mode,
-                   float* Y, uint8_t* x8_out, uint8_t* xs_out, uint8_t* y8_out, uint8_t* ys_out) {
-  if (!c || !W8 || !wscale || !X || (G != 32 && G != 16) || (nslots != 16 && nslots != 32 && nslots != 64) || mode < 0 || mode > 2)
-    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mx: bad argument");
-  if (mode != 1 && (G != 32 || !mx_unit_covers(K) || (N & 31))) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mx: unit kernel needs G = 32, K %% 512 == 0, N %% 32 == 0");
-  if (mode == 1 && !mx_kparts_covers(N, K, G)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mx: N = %d, K = %d, G = %d is not covered by the K-slice kernel", N, K, G);
-  if ((mode != 2 && !Y) || (mode == 2 && (!y8_out || !ys_out || (N & 127)))) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mx: missing output");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  const int ff = N / 2;
-  OPBUF(uint8_t, dW, (size_t)N * K); OPBUF(uint8_t, dWm, mx_w_bytes(N, K, G)); OPBUF(float, dS, N);
-  OPBUF(bf16_t, dX, (size_t)64 * K); OPBUF(uint8_t, dX8, mx_x_bytes(K, G)); OPBUF(uint8_t, dXS, mx_s_bytes(K, G));
-  OPBUF(float, dY, (size_t)(mode == 1 ? 8 : 1) * 64 * N); OPBUF(BatchState, dBS, 1);
-  OPBUF(uint8_t, dY8, mx_x_bytes(ff, 16)); OPBUF(uint8_t, dYS, mx_s_bytes(ff, 16));
-  hipStream_t s = c->stream;
-  BatchState hbs; memset(&hbs, 0, sizeof hbs);
-  for (int i = 0; i < nslots; ++i) hbs.active[i] = 1;
-  for (int i = 0; i < DTK_MAX_BATCH; ++i) hbs.share_src[i] = -1;
-  HIPCHK(c, hipMemcpyAsync(dBS, &hbs, sizeof hbs, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dW, W8, (size_t)N * K, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dS, wscale, (size_t)N * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(dX, 0, (size_t)64 * K * 2, s));
-  HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)nslots * K * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(dY, 0, (size_t)(mode == 1 ? 8 : 1) * 64 * N * 4, s));
-  HIPCHK(c, hipMemsetAsync(dY8, 0, mx_x_bytes(ff, 16), s));
-  HIPCHK(c, hipMemsetAsync(dYS, 0, mx_s_bytes(ff, 16), s));
-  launch_retile_mx(dW, dWm, N, K, G, s);
-  launch_quant_mx_rows(dX, K, dX8, dXS, G, 64, s);
-  GemvBArgs g{};
-  g.Wm = dWm; g.wscale = dS; g.N = N; g.K = K; g.X8 = dX8; g.XS = dXS; g.bs = dBS; g.nt = nslots / 16; g.logits = dY; g.kpart = dY;
-  g.d = K; g.ff = ff; g.H = 1; g.KVH = 1; g.Y8 = dY8; g.YS = dYS;
-  if (mode == 0) launch_gemv_mxu(EPI_LOGITS, g, s);
-  else if (mode == 2) launch_gemv_mxu(EPI_SWIGLU, g, s);
-  else if (!launch_gemv_mxk(g, G, s)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_mx: no K-slice kernel for N %d K %d G %d", N, K, G);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (mode == 0) HIPCHK(c, hipMemcpy(Y, dY, (size_t)nslots * N * 4, hipMemcpyDeviceToHost));
-  else if (mode == 1) {
-    std::vector<float> part((size_t)8 * 64 * N);
-    HIPCHK(c, hipMemcpy(part.data(), dY, part.size() * 4, hipMemcpyDeviceToHost));
-    for (int sl = 0; sl < nslots; ++sl)
-      for (int n = 0; n < N; ++n) {
-        float sum = 0.f;
-        for (int ks = 0; ks < 8; ++ks) sum += part[((size_t)ks * 64 + sl) * N + n];
-        Y[(size_t)sl * N + n] = sum;
-      }
-  } else {
-    HIPCHK(c, hipMemcpy(y8_out, dY8, mx_x_bytes(ff, 16), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(ys_out, dYS, mx_s_bytes(ff, 16), hipMemcpyDeviceToHost));
-  }
-  if (x8_out) HIPCHK(c, hipMemcpy(x8_out, dX8, mx_x_bytes(K, G), hipMemcpyDeviceToHost));
-  if (xs_out) HIPCHK(c, hipMemcpy(xs_out, dXS, mx_s_bytes(K, G), hipMemcpyDeviceToHost));
-  return DTK_OK;
-}
-
-int dtk_op_attention(dtk_ctx* c, const uint16_t* Q, const uint16_t* K, const uint16_t* V, int H, int Tq, int Tk, int hd, int causal, int q_offset, uint16_t* O) {
-  if (!c || !Q || !K || !V || !O) return fail(c, DTK_ERR_ARG, "dtk_op_attention: null argument");
-  if (hd != 72 && hd != 128 && hd != 64 && hd != 32) return fail(c, DTK_ERR_ARG, "unsupported head dim %d", hd);
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dQ, (size_t)H * Tq * hd); OPBUF(bf16_t, dK, (size_t)H * Tk * hd);
-  OPBUF(bf16_t, dV, (size_t)H * Tk * hd); OPBUF(bf16_t, dO, (size_t)H * Tq * hd);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dQ, Q, (size_t)H * Tq * hd * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dK, K, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dV, V, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
-  AttnArgs a;
-  a.Q = dQ; a.q_sh = (long)Tq * hd; a.q_st = hd;
-  a.K = dK; a.k_sh = (long)Tk * hd; a.k_st = hd;
-  a.V = dV; a.v_sh = (long)Tk * hd; a.v_st = hd;
-  a.O = dO; a.o_sh = (long)Tq * hd; a.o_st = hd;
-  a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal; a.q_offset = q_offset;
-  a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = 1;
-  launch_attention(a, s);
-  HIPCHK(c, hipMemcpyAsync(O, dO, (size_t)H * Tq * hd * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-int dtk_op_attention_seg(dtk_ctx* c, const uint16_t* Q, const uint16_t* K, const uint16_t* V, int H, int Tq, int Tk, int hd, int shared_len,
-                         const int32_t* seg_begin, const int32_t* kv_row, uint16_t* O) {
-  if (!c || !Q || !K || !V || !O || !seg_begin || !kv_row) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: null argument");
-  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: head dim %d (128 or 64)", hd);
-  if (H < 1 || Tq < 1 || Tk < 1 || shared_len < 0 || shared_len > Tk) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: bad shape");
-  if (c->attn_impl == 1) return fail(c, DTK_ERR_STATE, "dtk_op_attention_seg: attn_impl = 1 (the VALU attention kernel) has no segmented form");
-  std::vector<int32_t> rows((size_t)2 * Tq);
-  for (int t = 0; t < Tq; ++t) {
-    if (kv_row[t] < 0 || kv_row[t] >= Tk || seg_begin[t] < 0 || seg_begin[t] > kv_row[t])
-      return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: row %d: segment begin %d, cache row %d of %d keys", t, seg_begin[t], kv_row[t], Tk);
-    rows[2 * (size_t)t] = seg_begin[t]; rows[2 * (size_t)t + 1] = kv_row[t];
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dQ, (size_t)H * Tq * hd); OPBUF(bf16_t, dK, (size_t)H * Tk * hd);
-  OPBUF(bf16_t, dV, (size_t)H * Tk * hd); OPBUF(bf16_t, dO, (size_t)H * Tq * hd); OPBUF(int2, dR, (size_t)Tq);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dQ, Q, (size_t)H * Tq * hd * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dK, K, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dV, V, (size_t)H * Tk * hd * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dR, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, s));
-  AttnArgs a;
-  a.Q = dQ; a.q_sh = (long)Tq * hd; a.q_st = hd;
-  a.K = dK; a.k_sh = (long)Tk * hd; a.k_st = hd;
-  a.V = dV; a.v_sh = (long)Tk * hd; a.v_st = hd;
-  a.O = dO; a.o_sh = (long)Tq * hd; a.o_st = hd;
-  a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = 1; a.q_offset = 0;
-  a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = 1;
-  if (!launch_attention_seg(a, shared_len, dR, s)) return fail(c, DTK_ERR_ARG, "dtk_op_attention_seg: the kernel does not take these operands");
-  HIPCHK(c, hipMemcpyAsync(O, dO, (size_t)H * Tq * hd * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-// The single-sequence decode attention alone (launch_attn_decode as decode_step_launches calls it) on host operands: q [H*hd], K / V
-// [KVH][T_max][hd], scale hd^-0.5.  The caches are uploaded once; for each of the npos positions DecState.pos is set, the kernels of
-// (threads, splits, mode) run and that position's head outputs go to out[i][H*hd].  mode = AttnDecArgs::combine: 2 own combine kernel,
-// 1 in-kernel combine (threads 0; the arrival counters start at zero and must be zero again afterwards), 3 k_attn_decode_head (threads
-// 0), 0 consumer-side combine: o_proj's PRO_ATTN / EPI_RESID GEMV with an identity [d][d] weight onto a zero residual (variant -1: the
-// default of launch_gemv, 0..8: launch_gemv_variant), and the raw partials pm / pl [npos][H][S], po [npos][H][S][hd] come back too
-// (NaN where the kernels wrote none: threads != 0 with one split writes the head output itself and o_proj copies it, as in the step).
-int dtk_op_attn_decode(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int H, int KVH, int hd, int T_max,
-                       const int32_t* pos, int npos, int threads, int splits, int mode, int variant, uint16_t* out,
-                       float* pm_out, float* pl_out, float* po_out) {
-  if (!c || !q || !K || !V || !pos || !out) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: null argument");
-  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: head dim %d (128 or 64)", hd);
-  if (H < 1 || KVH < 1 || H % KVH || T_max < 1 || npos < 1 || npos > 4096) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: bad shape");
-  if (threads != 0 && threads != 256 && threads != 512 && threads != 1024) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: threads must be 0, 256, 512 or 1024");
-  if (threads == 0 && hd == 64) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: threads 0 (contiguous splits) has no head_dim-64 kernel: 256, 512 or 1024");
-  if (splits < 1 || splits > 16) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: splits must be 1..16");
-  if (mode < 0 || mode > 3) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode must be 0..3");
-  if ((mode == 1 || mode == 3) && threads != 0) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode %d needs threads 0 (the tile kernel has no such form)", mode);
-  if (variant < -1 || variant > 8) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: variant must be -1 (default) or 0..8");
-  if (mode == 0 && (!pm_out || !pl_out || !po_out)) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: mode 0 returns the partials");
-  for (int i = 0; i < npos; ++i)
-    if (pos[i] < 0 || pos[i] >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode: position %d of %d rows", pos[i], T_max);
-  HIPCHK(c, hipSetDevice(c->device));
-  const int d = H * hd, S = splits;
-  const size_t kv = (size_t)KVH * T_max * hd, part = (size_t)H * S * 130;   // 130: the in-kernel combine keeps (m, l) next to a split's 128 outputs
-  size_t off = 0;
-  OPBUF(bf16_t, dq, d); OPBUF(bf16_t, dK, kv); OPBUF(bf16_t, dV, kv); OPBUF(DecState, dst, npos);
-  OPBUF(float, dpm, (size_t)npos * H * S); OPBUF(float, dpl, (size_t)npos * H * S); OPBUF(float, dpo, (size_t)npos * part);
-  OPBUF(bf16_t, dout, (size_t)npos * d); OPBUF(bf16_t, dy, (size_t)npos * d); OPBUF(unsigned, dctr, H);
-  OPBUF(bf16_t, dW, mode == 0 ? (size_t)d * d : 1);
-  hipStream_t s = c->stream;
-  std::vector<DecState> hst((size_t)npos);
-  memset(hst.data(), 0, sizeof(DecState) * (size_t)npos);
-  for (int i = 0; i < npos; ++i) { hst[(size_t)i].pos = pos[i]; hst[(size_t)i].next_pos = pos[i] + 1; }
-  std::vector<bf16_t> eye;
-  if (mode == 0) {
-    eye.assign((size_t)d * d, 0);
-    for (int i = 0; i < d; ++i) eye[(size_t)i * d + i] = 0x3F80;   // bf16 1.0
-    HIPCHK(c, hipMemcpyAsync(dW, eye.data(), eye.size() * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(dy, 0, (size_t)npos * d * 2, s));       // the zero residual
-  }
-  HIPCHK(c, hipMemcpyAsync(dq, q, (size_t)d * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dK, K, kv * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dV, V, kv * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dst, hst.data(), sizeof(DecState) * (size_t)npos, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(dpm, 0xFF, (size_t)npos * H * S * 4, s));
-  HIPCHK(c, hipMemsetAsync(dpl, 0xFF, (size_t)npos * H * S * 4, s));
-  HIPCHK(c, hipMemsetAsync(dpo, 0xFF, (size_t)npos * part * 4, s));
-  HIPCHK(c, hipMemsetAsync(dout, 0xFF, (size_t)npos * d * 2, s));
-  HIPCHK(c, hipMemsetAsync(dctr, 0, (size_t)H * 4, s));
-  for (int i = 0; i < npos; ++i) {
-    AttnDecArgs ad;
-    ad.q = dq; ad.kcache = dK; ad.vcache = dV; ad.st = dst + i;
-    ad.pm = dpm + (size_t)i * H * S; ad.pl = dpl + (size_t)i * H * S; ad.po = dpo + (size_t)i * part;
-    ad.H = H; ad.S = S; ad.T_max = T_max; ad.G = H / KVH; ad.scale = 1.0f / sqrtf((float)hd); ad.hd = hd;
-    ad.threads = threads; ad.combine = mode; ad.out = dout + (size_t)i * d; ad.counters = dctr;
-    launch_attn_decode(ad, s);
-    if (mode != 0) continue;
-    GemvArgs g{};
-    g.W = dW; g.N = d; g.K = d; g.y = dy + (size_t)i * d; g.d = d; g.H = H; g.KVH = KVH; g.hd = hd; g.st = dst + i; g.T_max = T_max;
-    g.pm = ad.pm; g.pl = ad.pl; g.po = ad.po; g.S = S;
-    if (threads && S == 1) { g.x = ad.out; launch_gemv(PRO_COPY, EPI_RESID, g, s); }   // as decode_step_launches: no partials exist
-    else if (variant < 0) launch_gemv(PRO_ATTN, EPI_RESID, g, s);
-    else launch_gemv_variant(PRO_ATTN, EPI_RESID, variant, g, s);
-  }
-  HIPCHK(c, hipGetLastError());
-  std::vector<unsigned> ctr((size_t)H, 0u);
-  HIPCHK(c, hipMemcpyAsync(out, mode == 0 ? dy : dout, (size_t)npos * d * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(ctr.data(), dctr, (size_t)H * 4, hipMemcpyDeviceToHost, s));
-  if (mode == 0) {
-    HIPCHK(c, hipMemcpyAsync(pm_out, dpm, (size_t)npos * H * S * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(pl_out, dpl, (size_t)npos * H * S * 4, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (mode == 0) {   // [H][S][hd] of every position's [H][S][130] room
-    std::vector<float> po((size_t)npos * part);
-    HIPCHK(c, hipMemcpy(po.data(), dpo, po.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < npos; ++i) memcpy(po_out + (size_t)i * H * S * hd, po.data() + (size_t)i * part, (size_t)H * S * hd * 4);
-  }
-  HIPCHK(c, hipGetLastError());
-  for (int h = 0; h < H; ++h)
-    if (ctr[(size_t)h]) return fail(c, DTK_ERR_STATE, "dtk_op_attn_decode: arrival counter of head %d is %u after the launches (not zero)", h, ctr[(size_t)h]);
-  return DTK_OK;
-}
-
-// The batched decode attention alone (launch_attn_decode_b as batch_step_launches / batch_step_launches_mv call it; bf16 output) on
-// host operands: nslots = the grid's y (1, 2, 4: the multi-vector step, no prefix kernel; 16, 32, 64), q [nslots][H*128], K / V
-// [nslots][KVH][T_max][128], per slot pos / active / share_src (-1: none) / share_len.  The prefix groups come from
-// build_prefix_groups, the step's own table.  out [nslots][H*128] row-major (the fragment-major order of the kernel is undone here);
-// every element is 0xFFFF first, so the rows of slots that did not decode keep that value.
-int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
-                         const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
-                         int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
-  if (!c || !q || !K || !V || !pos || !active || !share_src || !share_len || !out) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: null argument");
-  if (nslots != 1 && nslots != 2 && nslots != 4 && nslots != 16 && nslots != 32 && nslots != 64)
-    return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: nslots must be 1, 2, 4, 16, 32 or 64");
-  if (H < 1 || KVH < 1 || H % KVH || T_max < 1) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: bad shape");
-  const int G = H / KVH;
-  if (G != 1 && G != 2 && G != 4) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: %d query heads per K/V head (1, 2 or 4)", G);
-  if (pfx_splits < 1 || pfx_splits > 4) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: pfx_splits must be 1..4");
-  if (gqa_fused < 0 || gqa_fused > 2) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: gqa_fused must be 0, 1 or 2");
-  if (tail_threads != 64 && tail_threads != 128 && tail_threads != 256 && tail_threads != 512 && !(tail_threads == 1024 && nslots <= 4))
-    return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: tail_threads must be 64, 128, 256 or 512 (1024: the multi-vector step, nslots <= 4)");
-  if (use_prefix && nslots < 16) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: the multi-vector step has no prefix kernel");
-  BatchState hbs; memset(&hbs, 0, sizeof hbs);
-  int32_t act[DTK_MAX_BATCH] = {};
-  for (int j = 0; j < DTK_MAX_BATCH; ++j) { hbs.share_src[j] = -1; hbs.share_len[j] = 0; }
-  for (int j = 0; j < nslots; ++j) {
-    if (pos[j] < 0 || pos[j] >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: slot %d: position %d of %d rows", j, pos[j], T_max);
-    if (share_src[j] >= nslots || share_src[j] == j || (share_src[j] >= 0 && (share_len[j] < 0 || share_len[j] > pos[j])))
-      return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: slot %d: source %d, %d shared rows, position %d", j, share_src[j], share_len[j], pos[j]);
-    act[j] = active[j] ? 1 : 0;
-    hbs.active[j] = act[j];
-    hbs.share_src[j] = share_src[j] >= 0 ? share_src[j] : -1;
-    hbs.share_len[j] = share_src[j] >= 0 ? share_len[j] : 0;
-  }
-  build_prefix_groups(&hbs, act, use_prefix != 0);
-  HIPCHK(c, hipSetDevice(c->device));
-  const int d = H * 128, nsteps = (d + 31) >> 5;
-  const size_t kv_slot = (size_t)KVH * T_max * 128, kv = (size_t)nslots * kv_slot;
-  const size_t out_elems = (size_t)((nslots + 15) >> 4) * nsteps * 512, recs = (size_t)nslots * H * pfx_splits;
-  struct Big { void* p = nullptr; ~Big() { if (p) (void)hipFree(p); } } big;     // caches beyond the op scratch: allocated for this call
-  size_t off = 0;
-  bf16_t *dK = nullptr, *dV = nullptr;
-  if (kv * 4 + ((size_t)8 << 20) > c->scratch_bytes) {
-    HIPCHK(c, hipMalloc(&big.p, kv * 4));
-    dK = (bf16_t*)big.p; dV = dK + kv;
-  }
-  OPBUF(bf16_t, sK, big.p ? 1 : kv); OPBUF(bf16_t, sV, big.p ? 1 : kv);
-  if (!big.p) { dK = sK; dV = sV; }
-  OPBUF(bf16_t, dq, (size_t)nslots * d); OPBUF(DecState, dst, nslots); OPBUF(BatchState, dbs, 1); OPBUF(bf16_t, dout, out_elems);
-  OPBUF(float, dm, recs); OPBUF(float, dl, recs); OPBUF(float, dpo, recs * 128);
-  hipStream_t s = c->stream;
-  std::vector<DecState> hst((size_t)nslots);
-  memset(hst.data(), 0, sizeof(DecState) * (size_t)nslots);
-  for (int j = 0; j < nslots; ++j) { hst[(size_t)j].pos = pos[j]; hst[(size_t)j].next_pos = pos[j] + 1; }
-  HIPCHK(c, hipMemcpyAsync(dK, K, kv * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dV, V, kv * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dq, q, (size_t)nslots * d * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dst, hst.data(), sizeof(DecState) * (size_t)nslots, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dbs, &hbs, sizeof hbs, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemsetAsync(dout, 0xFF, out_elems * 2, s));
-  HIPCHK(c, hipMemsetAsync(dm, 0xFF, recs * 4, s));
-  HIPCHK(c, hipMemsetAsync(dl, 0xFF, recs * 4, s));
-  HIPCHK(c, hipMemsetAsync(dpo, 0xFF, recs * 128 * 4, s));
-  AttnDecBArgs ad;
-  ad.q = dq; ad.kcache = dK; ad.vcache = dV; ad.kv_slot_stride = kv_slot; ad.st = dst; ad.bs = dbs;
-  ad.out = dout; ad.H = H; ad.T_max = T_max; ad.d = d; ad.G = G; ad.nslots = nslots; ad.scale = 1.0f / sqrtf(128.f);
-  ad.use_prefix = use_prefix != 0; ad.pfx_splits = pfx_splits; ad.tail_threads = tail_threads; ad.gqa_fused = gqa_fused; ad.nt_private = attn_nt != 0;
-  ad.pfx_m = dm; ad.pfx_l = dl; ad.pfx_o = dpo;
-  launch_attn_decode_b(ad, s);
-  HIPCHK(c, hipGetLastError());
-  std::vector<bf16_t> frag(out_elems);
-  HIPCHK(c, hipMemcpyAsync(frag.data(), dout, out_elems * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  for (int j = 0; j < nslots; ++j)
-    for (int k = 0; k < d; ++k)    // xtile_off (common.h)
-      out[(size_t)j * d + k] = frag[((size_t)((j >> 4) * nsteps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (j & 15)) * 8 + (k & 7)];
-  return DTK_OK;
-}
-
-// ---- the single-sequence decode GEMV family alone (dtk_op_gemv_role): one (prologue, epilogue, weight format, shape) of k_gemv on
-// host operands through the step's own launchers.  Everything the step would never hand these kernels is refused before anything is
-// allocated, uploaded or launched.
-static bool gemv_role_variant_ok(int fmt, int pro, int epi, int v) {     // fmt 0 bf16 (launch_gemv_variant), 1 fp8 (launch_gemv_f8_variant), 2 MXFP4 (launch_gemv_q4)
-  if (fmt == 2) {
-    const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_STORE)) || (pro == PRO_ATTN && epi == EPI_RESID) ||
-                      (pro == PRO_COPY && (epi == EPI_RESID || epi == EPI_STORE));
-    return pair && v == -1;
-  }
-  if (fmt == 1) {
-    const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_LOGITS)) || ((pro == PRO_ATTN || pro == PRO_COPY) && epi == EPI_RESID);
-    return pair && v >= -1 && v <= 9;
-  }
-  if (v < -1) return false;
-  if (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU)) return v <= 11;
-  if (pro == PRO_COPY && epi == EPI_RESID) return v <= 22;
-  if (pro == PRO_ATTN && epi == EPI_RESID) return v <= 8;
-  if (pro == PRO_RMSNORM && epi == EPI_LOGITS) return v <= 4;
-  if (pro == PRO_RMSNORM && epi == EPI_STORE) return v <= 0 || v == 20;
-  if (pro == PRO_COPY && epi == EPI_STORE) return v <= 0 || v == 20 || v == 21;
-  return false;
-}
-
-int dtk_op_gemv_role(dtk_ctx* c, int pro, int epi, int variant, const uint16_t* W, const uint8_t* W8, const float* wscale,
-                     const uint8_t* W4, const uint8_t* S4, int N, int K, int d, int ff, int H, int KVH, int hd, int T_max, int pos, float eps,
-                     const uint16_t* x, const uint16_t* norm_w, const uint16_t* rope_cos, const uint16_t* rope_sin,
-                     int S, const float* pm, const float* pl, const float* po, int scratch_fill,
-                     uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, float* logits_io) {
-  if (!c) return DTK_ERR_ARG;
-  if ((W != nullptr) + (W8 != nullptr) + (W4 != nullptr) != 1 || (W8 && !wscale) || (!W8 && wscale) || (!W4 != !S4))
-    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: exactly one of W | W8 + wscale | W4 + S4");
-  const int fmt = W4 ? 2 : (W8 ? 1 : 0);
-  // variant 0x1000 + v on bf16 operands: W is packed into 13-bit planes on the device (launch_pack_w13_rows) and the role streams those in
-  // 13-bit shape v (0xff: the shape a decode step runs); with an unpackable row the planes are dropped and launch_gemv takes the bf16 kernel
-  const bool f13 = variant >= 0x1000;
-  const int v13 = variant - 0x1000;
-  if (f13) {
-    if (fmt != 0) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: the 13-bit planes are packed from bf16 operands (W)");
-    if (v13 != 0xff && !gemv_w13_has(pro, epi, v13)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no 13-bit kernel for prologue %d, epilogue %d, shape %d", pro, epi, v13);
-    if (v13 == 0xff && !gemv_w13_has(pro, epi, 0)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no 13-bit kernel for prologue %d, epilogue %d", pro, epi);
-    variant = -1;
-  }
-  if (N < 1 || K < 8 || (K & 7) || (fmt == 1 && (K & 15))) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: N >= 1, K a multiple of 8 (16 for fp8 weights)");
-  if (pro < PRO_COPY || pro > PRO_ATTN || epi < EPI_STORE || epi > EPI_LOGITS) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: unknown prologue %d or epilogue %d", pro, epi);
-  if (!gemv_role_variant_ok(fmt, pro, epi, variant))
-    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: no %s kernel for prologue %d, epilogue %d, variant %d", fmt == 2 ? "MXFP4" : (fmt == 1 ? "fp8" : "bf16"), pro, epi, variant);
-  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: head dim %d (128 or 64)", hd);
-  if (scratch_fill < 0 || scratch_fill > 255 || d < 0) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: scratch_fill is a byte, d >= 0");
-  if (pro == PRO_ATTN) {
-    if (S < 1 || S > 16) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: S must be 1..16");
-    if (H < 1 || K != H * hd || !pm || !pl || !po) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: PRO_ATTN needs K = H * hd and the partials pm / pl / po");
-  } else if (!x || (pro == PRO_RMSNORM && !norm_w)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: x (and norm_w for PRO_RMSNORM) required");
-  if (epi == EPI_QKV) {
-    if (H < 1 || KVH < 1 || H % KVH) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: H %d query heads over KVH %d key / value heads", H, KVH);
-    if (N != (H + 2 * KVH) * hd || d != H * hd) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: QKV needs N = (H + 2 KVH) * hd and d = H * hd");
-    if (T_max < 1 || pos < 0 || pos >= T_max) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: position %d of %d rows", pos, T_max);
-    if (!rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: QKV needs the rope tables and q / k / v buffers");
-  } else if (epi == EPI_SWIGLU) {
-    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff and y");
-  } else if (epi == EPI_LOGITS) {
-    if (!logits_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: LOGITS needs the logits buffer");
-  } else if (!y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_role: RESID / STORE need y");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const int KC4 = (K + 31) >> 5, hd2 = hd / 2;
-  const size_t w_bytes = fmt == 2 ? (size_t)N * KC4 * 16 : (fmt == 1 ? (size_t)N * K : (size_t)N * K * 2);
-  const size_t kv = epi == EPI_QKV ? (size_t)KVH * T_max * hd : 0, qn = epi == EPI_QKV ? (size_t)H * hd : 0, rope = epi == EPI_QKV ? (size_t)T_max * hd2 : 0;
-  const size_t ny = epi == EPI_SWIGLU ? (size_t)ff : ((epi == EPI_STORE || epi == EPI_RESID) ? (size_t)N : 0), nl = epi == EPI_LOGITS ? (size_t)N : 0;
-  const size_t hs = pro == PRO_ATTN ? (size_t)H * S : 0;
-  size_t off = 0;
-  OPBUF(uint8_t, dW, w_bytes); OPBUF(float, dws, fmt == 1 ? N : 0); OPBUF(uint8_t, dS4, fmt == 2 ? (size_t)N * KC4 : 0);
-  OPBUF(uint8_t, dWp, f13 ? (size_t)N * w13_row_bytes(K) : 0); OPBUF(uint8_t, dWh, f13 ? (size_t)N : 0); OPBUF(unsigned, dbad, f13 ? 1 : 0);
-  OPBUF(bf16_t, dx, K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dcos, rope); OPBUF(bf16_t, dsin, rope); OPBUF(DecState, dst, 1);
-  OPBUF(float, dpm, hs); OPBUF(float, dpl, hs); OPBUF(float, dpo, hs * hd);
-  constexpr size_t GUARD = 256;            // bytes behind every result buffer that must still hold scratch_fill after the launch
-  OPBUF(bf16_t, dq, qn + GUARD / 2); OPBUF(bf16_t, dk, kv + GUARD / 2); OPBUF(bf16_t, dv, kv + GUARD / 2); OPBUF(bf16_t, dy, ny + GUARD / 2);
-  OPBUF(float, dl, nl + GUARD / 4);
-  off = align_up(off, 256);
-  if (off + 256 > c->scratch_bytes) return fail(c, DTK_ERR_ARG, "op scratch exhausted (%zu bytes)", off + 256);
-  HIPCHK(c, hipMemsetAsync(c->scratch, scratch_fill, off + 256, s));      // whatever lies between and behind the operands: the caller's poison
-  HIPCHK(c, hipMemcpyAsync(dW, fmt == 2 ? (const void*)W4 : (fmt == 1 ? (const void*)W8 : (const void*)W), w_bytes, hipMemcpyHostToDevice, s));
-  if (fmt == 1) HIPCHK(c, hipMemcpyAsync(dws, wscale, (size_t)N * 4, hipMemcpyHostToDevice, s));
-  if (fmt == 2) HIPCHK(c, hipMemcpyAsync(dS4, S4, (size_t)N * KC4, hipMemcpyHostToDevice, s));
-  if (pro != PRO_ATTN) HIPCHK(c, hipMemcpyAsync(dx, x, (size_t)K * 2, hipMemcpyHostToDevice, s));
-  if (pro == PRO_RMSNORM) HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
-  if (pro == PRO_ATTN) {
-    HIPCHK(c, hipMemcpyAsync(dpm, pm, hs * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dpl, pl, hs * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dpo, po, hs * hd * 4, hipMemcpyHostToDevice, s));
-  }
-  DecState hst; memset(&hst, 0, sizeof hst);
-  hst.pos = pos; hst.next_pos = pos + 1;
-  HIPCHK(c, hipMemcpyAsync(dst, &hst, sizeof hst, hipMemcpyHostToDevice, s));
-  if (epi == EPI_QKV) {
-    HIPCHK(c, hipMemcpyAsync(dcos, rope_cos, rope * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dsin, rope_sin, rope * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dq, q_io, qn * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dk, k_io, kv * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dv, v_io, kv * 2, hipMemcpyHostToDevice, s));
-  } else if (epi == EPI_LOGITS) HIPCHK(c, hipMemcpyAsync(dl, logits_io, nl * 4, hipMemcpyHostToDevice, s));
-  else HIPCHK(c, hipMemcpyAsync(dy, y_io, ny * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipStreamSynchronize(s));      // (hst lives on this frame)
-  GemvArgs g{};
-  if (fmt == 0) g.W = reinterpret_cast<const bf16_t*>(dW);
-  else if (fmt == 1) { g.W8 = dW; g.wscale = dws; }
-  else { g.W4 = dW; g.S4 = dS4; }
-  g.N = N; g.K = K; g.x = dx; g.norm_w = dn; g.eps = eps; g.pm = dpm; g.pl = dpl; g.po = dpo; g.S = S;
-  g.y = dy; g.logits = dl; g.q_out = dq; g.kcache = dk; g.vcache = dv; g.rope_cos = dcos; g.rope_sin = dsin; g.st = dst;
-  g.T_max = T_max; g.d = d; g.ff = ff; g.H = H; g.KVH = KVH; g.hd = hd;
-  if (f13) {
-    unsigned bad = 0;
-    HIPCHK(c, hipMemsetAsync(dbad, 0, sizeof(unsigned), s));
-    launch_pack_w13_rows(g.W, dWp, dWh, dbad, N, K, !c->w13_nz, s);
-    HIPCHK(c, hipMemcpyAsync(&bad, dbad, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipMemsetAsync(dbad, scratch_fill, sizeof(unsigned), s));
-    c->w13_op_bad_rows = (int)bad;
-    if (!bad) { g.Wp = dWp; g.Wh = dWh; }
-  }
-  if (f13 && g.Wp && v13 != 0xff) launch_gemv_w13_variant(pro, epi, v13, g, s);
-  else if (variant < 0) launch_gemv(pro, epi, g, s);
-  else if (fmt == 1) launch_gemv_f8_variant(pro, epi, variant, g, s);
-  else launch_gemv_variant(pro, epi, variant, g, s);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  {   // a role writes its own cells only: nothing behind the end of q / k / v / y / logits
-    const unsigned char* ends[5] = {(unsigned char*)(dq + qn), (unsigned char*)(dk + kv), (unsigned char*)(dv + kv), (unsigned char*)(dy + ny), (unsigned char*)(dl + nl)};
-    unsigned char guard[5][GUARD];
-    for (int i = 0; i < 5; ++i) HIPCHK(c, hipMemcpy(guard[i], ends[i], GUARD, hipMemcpyDeviceToHost));
-    for (int i = 0; i < 5; ++i)
-      for (size_t j = 0; j < GUARD; ++j)
-        if (guard[i][j] != (unsigned char)scratch_fill) return fail(c, DTK_ERR_STATE, "dtk_op_gemv_role: byte %zu behind the end of %s was written", j, i == 0 ? "q" : (i == 1 ? "k" : (i == 2 ? "v" : (i == 3 ? "y" : "logits"))));
-  }
-  if (epi == EPI_QKV) {
-    HIPCHK(c, hipMemcpy(q_io, dq, qn * 2, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(k_io, dk, kv * 2, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(v_io, dv, kv * 2, hipMemcpyDeviceToHost));
-  } else if (epi == EPI_LOGITS) HIPCHK(c, hipMemcpy(logits_io, dl, nl * 4, hipMemcpyDeviceToHost));
-  else HIPCHK(c, hipMemcpy(y_io, dy, ny * 2, hipMemcpyDeviceToHost));
-  return DTK_OK;
-}
-
-// ---- the prefill's row kernels and attention layouts alone (dtk_op_rope_scatter / _rows_norm / _swiglu / _attention_ex / _rows_move):
-// host operands into the op scratch as dtk_op_gemv_role does it — the whole scratch the op uses is filled with scratch_fill first, every
-// result buffer is in/out with 256 guard bytes behind it that must still hold scratch_fill after the launch, and everything the prefill
-// would never hand a kernel is refused before anything is uploaded.
-extern "C++" {
-namespace {
-struct OpRun {
-  static constexpr size_t GUARD = 256;
-  dtk_ctx* c; const char* who; int fill; size_t off = 0; bool full = false;
-  struct In { void* dev; const void* host; size_t bytes; };
-  struct Io { void* dev; void* host; size_t bytes; const char* name; };
-  std::vector<In> ins; std::vector<Io> ios;
-  OpRun(dtk_ctx* c_, const char* who_, int fill_) : c(c_), who(who_), fill(fill_) {}
-  void* take(size_t bytes) {
-    off = align_up(off, 256);
-    if (off + bytes + 256 > c->scratch_bytes) { full = true; return c->scratch; }
-    void* p = c->scratch + off; off += bytes; return p;
-  }
-  template <class T> T* in(const void* host, size_t n) { T* p = (T*)take(n * sizeof(T)); if (host && n) ins.push_back({p, host, n * sizeof(T)}); return p; }
-  template <class T> T* io(void* host, size_t n, const char* name) { T* p = (T*)take(n * sizeof(T) + GUARD); if (host) ios.push_back({p, host, n * sizeof(T), name}); return p; }
-  int upload(hipStream_t s) {     // the caller's poison over everything between and behind the operands, then the operands
-    if (full) return fail(c, DTK_ERR_ARG, "%s: op scratch exhausted (%zu of %zu bytes)", who, off, c->scratch_bytes);
-    off = align_up(off, 256);
-    HIPCHK(c, hipMemsetAsync(c->scratch, fill, off + 256, s));
-    for (const In& i : ins) HIPCHK(c, hipMemcpyAsync(i.dev, i.host, i.bytes, hipMemcpyHostToDevice, s));
-    for (const Io& i : ios) HIPCHK(c, hipMemcpyAsync(i.dev, i.host, i.bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    return DTK_OK;
-  }
-  int finish(hipStream_t s) {     // nothing behind the end of a result buffer was written; then the results go back
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    unsigned char guard[GUARD];
-    for (const Io& i : ios) {
-      HIPCHK(c, hipMemcpy(guard, (unsigned char*)i.dev + i.bytes, GUARD, hipMemcpyDeviceToHost));
-      for (size_t j = 0; j < GUARD; ++j)
-        if (guard[j] != (unsigned char)fill) return fail(c, DTK_ERR_STATE, "%s: byte %zu behind the end of %s was written", who, j, i.name);
-    }
-    for (const Io& i : ios) HIPCHK(c, hipMemcpy(i.host, i.dev, i.bytes, hipMemcpyDeviceToHost));
-    return DTK_OK;
-  }
-};
-}  // namespace
-}  // extern "C++"
-
-int dtk_op_rope_scatter(dtk_ctx* c, int form, const uint16_t* QKV, const float* part, int S, int part_rows, int T, int H, int KVH, int hd,
-                        int T_max, int start_pos, const int32_t* rows, int max_pos, const uint16_t* rope_cos, const uint16_t* rope_sin,
-                        int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io) {
-  const char* who = "dtk_op_rope_scatter";
-  if (!c || !rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
-  if (form != 0 && form != 1) return fail(c, DTK_ERR_ARG, "%s: form %d (0 bf16 rows, 1 fp32 K-slice partials)", who, form);
-  if (hd != 128 && hd != 64) return fail(c, DTK_ERR_ARG, "%s: head dim %d (128 or 64)", who, hd);
-  if (T < 1 || H < 1 || KVH < 1 || H % KVH || T_max < 1 || max_pos < 1) return fail(c, DTK_ERR_ARG, "%s: T %d, H %d query heads over KVH %d key / value heads, T_max %d", who, T, H, KVH, T_max);
-  if (scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: scratch_fill is a byte", who);
-  if (form == 0 && !QKV) return fail(c, DTK_ERR_ARG, "%s: form 0 needs QKV", who);
-  if (form == 1 && (!part || S < 1 || S > 8 || part_rows < T)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs partials of S = 1..8 slices and part_rows >= T", who);
-  for (int t = 0; t < T; ++t) {
-    const int pos = rows ? rows[2 * t] : start_pos + t, row = rows ? rows[2 * t + 1] : start_pos + t;
-    if (pos < 0 || pos >= max_pos || row < 0 || row >= T_max)
-      return fail(c, DTK_ERR_ARG, "%s: row %d: position %d of %d, cache row %d of %d", who, t, pos, max_pos, row, T_max);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const size_t qkvn = (size_t)(H + 2 * KVH) * hd, kv = (size_t)KVH * T_max * hd;
-  OpRun r(c, who, scratch_fill);
-  const bf16_t* dQKV = r.in<bf16_t>(form == 0 ? QKV : nullptr, form == 0 ? (size_t)T * qkvn : 0);
-  const float* dP = r.in<float>(form == 1 ? part : nullptr, form == 1 ? (size_t)S * part_rows * qkvn : 0);
-  const bf16_t* dcos = r.in<bf16_t>(rope_cos, (size_t)max_pos * (hd / 2));
-  const bf16_t* dsin = r.in<bf16_t>(rope_sin, (size_t)max_pos * (hd / 2));
-  const int2* dR = r.in<int2>(rows, rows ? (size_t)T : 0);
-  bf16_t* dq = r.io<bf16_t>(q_io, (size_t)H * T * hd, "q"); bf16_t* dk = r.io<bf16_t>(k_io, kv, "k"); bf16_t* dv = r.io<bf16_t>(v_io, kv, "v");
-  if (const int rc = r.upload(s)) return rc;
-  const long ps = (long)part_rows * (long)qkvn;
-  if (form == 0 && rows) launch_rope_scatter_rows(dQKV, dq, dk, dv, dcos, dsin, T, dR, H, KVH, T_max, s, hd);
-  else if (form == 0) launch_rope_scatter(dQKV, dq, dk, dv, dcos, dsin, T, start_pos, H, KVH, T_max, s, hd);
-  else if (rows) launch_sk_rope_scatter_rows(dP, ps, S, dq, dk, dv, dcos, dsin, T, dR, H, KVH, T_max, s, hd);
-  else launch_sk_rope_scatter(dP, ps, S, dq, dk, dv, dcos, dsin, T, start_pos, H, KVH, T_max, s, hd);
-  return r.finish(s);
-}
-
-int dtk_op_rows_norm(dtk_ctx* c, int form, const uint16_t* X, const float* part, int S, int part_rows, const uint16_t* norm_w,
-                     const uint16_t* ln_b, const uint16_t* bias, const uint16_t* residual, const uint16_t* gate, int flags, int M, int N,
-                     int ldx, int ldc, int ldr, int ldy, float eps, int scratch_fill, uint16_t* c_io, uint16_t* y_io) {
-  const char* who = "dtk_op_rows_norm";
-  if (!c) return DTK_ERR_ARG;
-  if (form < 0 || form > 3) return fail(c, DTK_ERR_ARG, "%s: form %d (0 rmsnorm_rows, 1 rmsnorm_rows_sk, 2 sk_reduce, 3 layernorm_rows)", who, form);
-  if (M < 1 || N < 1 || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: M, N >= 1, scratch_fill a byte", who);
-  const bool in_place = form == 3 && !X;              // Y == X (the cross layer's q_norm)
-  if (form != 2) {
-    if (!y_io || !norm_w || (!X && !in_place) || (form == 3 && !ln_b)) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
-    if (in_place) ldx = ldy;
-    if (ldx < N || ldy < N) return fail(c, DTK_ERR_ARG, "%s: ldx %d / ldy %d below the row length %d", who, ldx, ldy, N);
-    if ((form == 0 || form == 3) && ((N % 8) || (ldx % 8) || (ldy % 8))) return fail(c, DTK_ERR_ARG, "%s: form %d reads and writes 16-byte chunks: D, ldx, ldy multiples of 8", who, form);
-    if (form == 1 && (N % 4)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs N %% 4 == 0", who);
-  } else {
-    const int known = DTK_EPI_BIAS | DTK_EPI_RESIDUAL | DTK_EPI_GATED_RESIDUAL;
-    if (!part || !c_io || (norm_w && !y_io) || (flags & ~known)) return fail(c, DTK_ERR_ARG, "%s: form 2 needs partials and C (and Y with norm_w); flags: bias, residual, gated residual", who);
-    if ((N % 4) || S < 1 || S > 8 || part_rows < M) return fail(c, DTK_ERR_ARG, "%s: form 2 needs N %% 4 == 0, S = 1..8 and part_rows >= M", who);
-    if (((flags & DTK_EPI_BIAS) && !bias) || ((flags & DTK_EPI_RESIDUAL) && (!residual || ldr < N)) ||
-        ((flags & DTK_EPI_GATED_RESIDUAL) && (!gate || !(flags & DTK_EPI_RESIDUAL))))
-      return fail(c, DTK_ERR_ARG, "%s: a flag without its operand (the gated residual needs the residual too)", who);
-    if (ldc < N || (norm_w && ldy < N)) return fail(c, DTK_ERR_ARG, "%s: ldc / ldy below N", who);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  OpRun r(c, who, scratch_fill);
-  if (form != 2) {
-    const bf16_t* dX = in_place ? nullptr : r.in<bf16_t>(X, (size_t)M * ldx);
-    const bf16_t* dw = r.in<bf16_t>(norm_w, N);
-    const bf16_t* db = r.in<bf16_t>(form == 3 ? ln_b : nullptr, form == 3 ? N : 0);
-    bf16_t* dY = r.io<bf16_t>(y_io, (size_t)M * ldy, "y");
-    if (in_place) dX = dY;
-    if (const int rc = r.upload(s)) return rc;
-    if (form == 0) launch_rmsnorm_rows(dX, ldx, dw, dY, ldy, M, N, eps, s);
-    else if (form == 1) launch_rmsnorm_rows_sk(dX, ldx, dw, dY, ldy, M, N, eps, s);
-    else launch_layernorm_rows(dX, ldx, dw, db, dY, ldy, M, N, eps, s);
-    return r.finish(s);
-  }
-  GemmArgs g;
-  g.A = nullptr; g.lda = 0; g.W = nullptr; g.ldw = 0; g.M = M; g.N = N; g.K = 0; g.kslices = S;
-  g.part = r.in<float>(part, (size_t)S * part_rows * N); g.part_stride = (long)part_rows * N;
-  g.bias = r.in<bf16_t>((flags & DTK_EPI_BIAS) ? bias : nullptr, (flags & DTK_EPI_BIAS) ? N : 0);
-  g.residual = r.in<bf16_t>((flags & DTK_EPI_RESIDUAL) ? residual : nullptr, (flags & DTK_EPI_RESIDUAL) ? (size_t)M * ldr : 0); g.ldr = ldr;
-  g.gate = r.in<bf16_t>((flags & DTK_EPI_GATED_RESIDUAL) ? gate : nullptr, (flags & DTK_EPI_GATED_RESIDUAL) ? 1 : 0);
-  const bf16_t* dw = r.in<bf16_t>(norm_w, norm_w ? N : 0);
-  g.C = r.io<bf16_t>(c_io, (size_t)M * ldc, "c"); g.ldc = ldc;
-  bf16_t* dY = r.io<bf16_t>(norm_w ? y_io : nullptr, norm_w ? (size_t)M * ldy : 0, "y");
-  g.flags = ((flags & DTK_EPI_BIAS) ? GEMM_BIAS : 0) | ((flags & DTK_EPI_RESIDUAL) ? GEMM_RESIDUAL : 0) | ((flags & DTK_EPI_GATED_RESIDUAL) ? GEMM_GATED_RESIDUAL : 0);
-  if (const int rc = r.upload(s)) return rc;
-  launch_sk_reduce(g, norm_w ? dw : nullptr, dY, ldy, eps, s);
-  return r.finish(s);
-}
-
-int dtk_op_swiglu(dtk_ctx* c, int form, const uint16_t* GU, const float* part, int S, int part_rows, const uint16_t* A, const uint16_t* W,
-                  int M, int ff, int K, int ldact, int scratch_fill, uint16_t* act_io) {
-  const char* who = "dtk_op_swiglu";
-  if (!c) return DTK_ERR_ARG;
-  if (form < 0 || form > 2) return fail(c, DTK_ERR_ARG, "%s: form %d (0 silu_mul, 1 sk_reduce_swiglu, 2 the GEMM epilogue)", who, form);
-  if (!act_io || M < 1 || ff < 1 || ldact < ff || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: act, M, ff >= 1, ldact >= ff, scratch_fill a byte", who);
-  if (form == 0 && (!GU || (ff % 8) || ldact != ff)) return fail(c, DTK_ERR_ARG, "%s: form 0 needs GU, ff %% 8 == 0 (as dtk_create) and ldact == ff", who);
-  if (form == 1 && (!part || S < 1 || S > 8 || (ff % 4) || (ldact % 4) || part_rows < M)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs partials of S = 1..8 slices, ff %% 4 == 0, ldact %% 4 == 0, part_rows >= M", who);
-  if (form == 2 && (!A || !W || K < 8 || (K % 8))) return fail(c, DTK_ERR_ARG, "%s: form 2 needs A, W and K %% 8 == 0", who);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  OpRun r(c, who, scratch_fill);
-  if (form == 0) {
-    const bf16_t* dGU = r.in<bf16_t>(GU, (size_t)M * 2 * ff);
-    bf16_t* dA = r.io<bf16_t>(act_io, (size_t)M * ff, "act");
-    if (const int rc = r.upload(s)) return rc;
-    launch_silu_mul(dGU, ff, dA, M, s);
-    return r.finish(s);
-  }
-  GemmArgs g;
-  g.M = M; g.N = 2 * ff; g.K = K; g.flags = 0; g.bias = nullptr; g.residual = nullptr; g.ldr = 0;
-  if (form == 1) {
-    g.A = nullptr; g.lda = 0; g.W = nullptr; g.ldw = 0; g.C = nullptr; g.ldc = 0; g.kslices = S;
-    g.part = r.in<float>(part, (size_t)S * part_rows * 2 * ff); g.part_stride = (long)part_rows * 2 * ff;
-    bf16_t* dA = r.io<bf16_t>(act_io, (size_t)M * ldact, "act");
-    if (const int rc = r.upload(s)) return rc;
-    launch_sk_reduce_swiglu(g, dA, ldact, s);
-    return r.finish(s);
-  }
-  g.A = r.in<bf16_t>(A, (size_t)M * K); g.lda = K;
-  g.W = r.in<bf16_t>(W, (size_t)2 * ff * K); g.ldw = K;
-  bf16_t* dWt = (bf16_t*)r.take(tiled_elems(2 * ff, K) * sizeof(bf16_t));
-  g.Wt = dWt;
-  g.C = r.io<bf16_t>(act_io, (size_t)M * ldact, "act"); g.ldc = ldact;
-  if (r.full) return fail(c, DTK_ERR_ARG, "%s: op scratch exhausted", who);
-  // the launcher's own refusals, asked before anything is uploaded: a dry call is not possible (it launches), so its conditions are restated
-  if (K < 128 || ((2 * ff) & 31) || (ldact & 3)) return fail(c, DTK_ERR_ARG, "%s: k_gemm_g3's SwiGLU epilogue needs K >= 128, ff %% 16 == 0 and ldact %% 4 == 0", who);
-  if (const int rc = r.upload(s)) return rc;
-  launch_retile_pairs(g.W, dWt, ff, K, s);
-  if (!launch_gemm_g3_swiglu(g, s)) {
-    (void)hipStreamSynchronize(s);
-    return fail(c, DTK_ERR_ARG, "%s: launch_gemm_g3_swiglu does not take this shape (\"gemm_g3_min_blocks\", \"gemm_wt\")", who);
-  }
-  return r.finish(s);
-}
-
-int dtk_op_attention_ex(dtk_ctx* c, const uint16_t* Q, int64_t nq, const uint16_t* K, int64_t nk, const uint16_t* V, int64_t nv,
-                        uint16_t* o_io, int64_t no, const int64_t* strides, int H, int kv_group, int Tq, int Tk, int hd, int causal,
-                        int q_offset, int nbatch, int scratch_fill) {
-  const char* who = "dtk_op_attention_ex";
-  if (!c || !Q || !K || !V || !o_io || !strides) return fail(c, DTK_ERR_ARG, "%s: null argument", who);
-  if (hd != 72 && hd != 128 && hd != 64 && hd != 32) return fail(c, DTK_ERR_ARG, "%s: unsupported head dim %d", who, hd);
-  if (H < 1 || Tq < 1 || Tk < 1 || nbatch < 1 || kv_group < 1 || H % kv_group || q_offset < 0 || scratch_fill < 0 || scratch_fill > 255)
-    return fail(c, DTK_ERR_ARG, "%s: bad shape (H %d, kv_group %d, Tq %d, Tk %d, nbatch %d, q_offset %d)", who, H, kv_group, Tq, Tk, nbatch, q_offset);
-  // strides = {q_sh, q_st, q_sb, k_sh, k_st, k_sb, v_sh, v_st, v_sb, o_sh, o_st, o_sb}, in elements
-  const int64_t n[4] = {nq, nk, nv, no};
-  const int heads[4] = {H, H / kv_group, H / kv_group, H}, toks[4] = {Tq, Tk, Tk, Tq};
-  for (int i = 0; i < 4; ++i) {
-    const int64_t sh = strides[3 * i], st = strides[3 * i + 1], sb = strides[3 * i + 2];
-    if (sh < 0 || st < 0 || sb < 0 || n[i] < 1 || (sh | st | sb) >> 40) return fail(c, DTK_ERR_ARG, "%s: negative or absurd stride / size of operand %d", who, i);
-    const int64_t last = (int64_t)(nbatch - 1) * sb + (int64_t)(heads[i] - 1) * sh + (int64_t)(toks[i] - 1) * st + hd;
-    if (last > n[i]) return fail(c, DTK_ERR_ARG, "%s: the strides of %s address element %lld of %lld", who, i == 0 ? "Q" : (i == 1 ? "K" : (i == 2 ? "V" : "O")), (long long)last, (long long)n[i]);
-    if ((sh | st | sb) & 1) return fail(c, DTK_ERR_ARG, "%s: odd stride (the kernels read and write bf16 pairs)", who);
-  }
-  AttnArgs a;
-  a.q_sh = (long)strides[0]; a.q_st = (long)strides[1]; a.q_sb = (long)strides[2];
-  a.k_sh = (long)strides[3]; a.k_st = (long)strides[4]; a.k_sb = (long)strides[5];
-  a.v_sh = (long)strides[6]; a.v_st = (long)strides[7]; a.v_sb = (long)strides[8];
-  a.o_sh = (long)strides[9]; a.o_st = (long)strides[10]; a.o_sb = (long)strides[11];
-  a.H = H; a.Tq = Tq; a.Tk = Tk; a.hd = hd; a.causal = causal ? 1 : 0; a.q_offset = q_offset;
-  a.scale = 1.0f / sqrtf((float)hd); a.impl = c->attn_impl; a.kv_group = kv_group; a.nbatch = nbatch;
-  if (c->attn_impl == 2 && (!attention_mfma_operands(a) || (a.q_sb % 8) || (a.k_sb % 8) || (a.v_sb % 8) || (a.o_sb % 4)))
-    return fail(c, DTK_ERR_ARG, "%s: attn_impl = 2 and the MFMA kernel does not take these operands (hd 128 / 72 / 64, Q / K / V strides %% 8, O strides %% 4)", who);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  OpRun r(c, who, scratch_fill);
-  a.Q = r.in<bf16_t>(Q, (size_t)nq); a.K = r.in<bf16_t>(K, (size_t)nk); a.V = r.in<bf16_t>(V, (size_t)nv);
-  a.O = r.io<bf16_t>(o_io, (size_t)no, "o");
-  if (const int rc = r.upload(s)) return rc;
-  launch_attention(a, s);
-  return r.finish(s);
-}
-
-int dtk_op_rows_move(dtk_ctx* c, int form, const int32_t* ids, const uint16_t* src, const float* pixels, int M, int D, int V, int lds,
-                     int ldd, int image, int patch, int scratch_fill, uint16_t* dst_io) {
-  const char* who = "dtk_op_rows_move";
-  if (!c) return DTK_ERR_ARG;
-  if (form < 0 || form > 2) return fail(c, DTK_ERR_ARG, "%s: form %d (0 embed_gather, 1 copy_rows, 2 im2col)", who, form);
-  if (!dst_io || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: dst, scratch_fill a byte", who);
-  if (form == 0) {
-    if (!ids || !src || M < 1 || V < 1 || D < 8 || (D % 8)) return fail(c, DTK_ERR_ARG, "%s: form 0 needs ids, the table, d %% 8 == 0", who);
-    for (int t = 0; t < M; ++t) if (ids[t] < 0 || ids[t] >= V) return fail(c, DTK_ERR_ARG, "%s: id %d of row %d outside [0, %d)", who, ids[t], t, V);
-  } else if (form == 1) {
-    if (!src || M < 1 || D < 8 || (D % 8) || lds < D || ldd < D || (lds % 8) || (ldd % 8)) return fail(c, DTK_ERR_ARG, "%s: form 1 needs src, D, lds, ldd multiples of 8, lds / ldd >= D", who);
-  } else if (!pixels || patch < 1 || image < patch || ldd < 3 * patch * patch) return fail(c, DTK_ERR_ARG, "%s: form 2 needs pixels, image >= patch >= 1, ldp >= 3 patch^2", who);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  OpRun r(c, who, scratch_fill);
-  if (form == 0) {
-    const int32_t* di = r.in<int32_t>(ids, M); const bf16_t* de = r.in<bf16_t>(src, (size_t)V * D);
-    bf16_t* dX = r.io<bf16_t>(dst_io, (size_t)M * D, "x");
-    if (const int rc = r.upload(s)) return rc;
-    launch_embed_gather(di, de, dX, M, D, s);
-  } else if (form == 1) {
-    const bf16_t* ds = r.in<bf16_t>(src, (size_t)M * lds);
-    bf16_t* dd = r.io<bf16_t>(dst_io, (size_t)M * ldd, "dst");
-    if (const int rc = r.upload(s)) return rc;
-    launch_copy_rows(ds, lds, dd, ldd, M, D, s);
-  } else {
-    const int np = image / patch;
-    const float* dp = r.in<float>(pixels, (size_t)3 * image * image);
-    bf16_t* dd = r.io<bf16_t>(dst_io, (size_t)np * np * ldd, "patches");
-    if (const int rc = r.upload(s)) return rc;
-    launch_im2col(dp, dd, image, patch, ldd, s);
-  }
-  return r.finish(s);
-}
-
-// ---- the multi-vector decode GEMV family alone (dtk_op_gemv_mv_role): one (prologue, epilogue) of k_gemv_mv on host operands through
-// the step's own launcher, nb = 1 | 2 | 4 slots with their own positions and active flags.  Fragment-order buffers (x_layout 1, the SwiGLU
-// activation) cross the ABI as the kernel holds them, whole 16-slot tiles.  The block shape is set for this call alone.
-extern "C++" {
-namespace {
-struct MvShapeScope {      // launch_gemv_mv reads the shape table: o_proj (K == d) looks at role 5 first
-  int epi;
-  MvShapeScope(int epi_, int shape) : epi(epi_) { set_gemv_mv_shape(epi, shape); if (epi == EPI_RESID) set_gemv_mv_shape(5, shape); }
-  ~MvShapeScope() { set_gemv_mv_shape(epi, -1); if (epi == EPI_RESID) set_gemv_mv_shape(5, -1); }
-};
-}  // namespace
-}  // extern "C++"
-
-int dtk_op_gemv_mv_role(dtk_ctx* c, int pro, int epi, int nb, int shape, const uint16_t* W, const uint8_t* W8, const float* wscale,
-                        int N, int K, int d, int ff, int H, int KVH, int T_max, const int32_t* pos, const int32_t* active, int bs_null,
-                        int x_layout, const uint16_t* X, const uint16_t* norm_w, float eps, const uint16_t* rope_cos,
-                        const uint16_t* rope_sin, int scratch_fill, uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io,
-                        float* logits_io) {
-  const char* who = "dtk_op_gemv_mv_role";
-  if (!c) return DTK_ERR_ARG;
-  if ((W != nullptr) + (W8 != nullptr) != 1 || (W8 && !wscale) || (!W8 && wscale)) return fail(c, DTK_ERR_ARG, "%s: exactly one of W | W8 + wscale", who);
-  const bool pair = (pro == PRO_RMSNORM && (epi == EPI_QKV || epi == EPI_SWIGLU || epi == EPI_LOGITS || epi == EPI_STORE)) ||
-                    (pro == PRO_COPY && (epi == EPI_RESID || epi == EPI_STORE));
-  if (!pair) return fail(c, DTK_ERR_ARG, "%s: the step has no launch with prologue %d and epilogue %d", who, pro, epi);
-  if (nb != 1 && nb != 2 && nb != 4) return fail(c, DTK_ERR_ARG, "%s: nb %d (1, 2 or 4)", who, nb);
-  if (shape < -1 || shape > 3) return fail(c, DTK_ERR_ARG, "%s: shape %d (-1 = the step's choice, 0..3)", who, shape);
-  if (N < 1 || K < 8 || (K & 7) || (W8 && (K & 15))) return fail(c, DTK_ERR_ARG, "%s: N >= 1, K a multiple of 8 (16 for fp8 weights)", who);
-  if (scratch_fill < 0 || scratch_fill > 255 || d < 0) return fail(c, DTK_ERR_ARG, "%s: scratch_fill is a byte, d >= 0", who);
-  if (x_layout != 0 && x_layout != 1) return fail(c, DTK_ERR_ARG, "%s: x_layout %d (0 rows, 1 fragment order)", who, x_layout);
-  if (x_layout == 1 && pro == PRO_RMSNORM) return fail(c, DTK_ERR_ARG, "%s: PRO_RMSNORM reads residual streams, which are rows", who);
-  if (!X || !pos || !active || (pro == PRO_RMSNORM && !norm_w)) return fail(c, DTK_ERR_ARG, "%s: X, pos, active (and norm_w for PRO_RMSNORM) required", who);
-  for (int b = 0; b < nb; ++b)
-    if (bs_null && !active[b]) return fail(c, DTK_ERR_ARG, "%s: without a BatchState every slot decodes (slot %d is idle)", who, b);
-  if ((size_t)nb * K * 2 + (size_t)nb * 16 * 4 + 64 > (size_t)160 * 1024)
-    return fail(c, DTK_ERR_ARG, "%s: %d vectors of K = %d do not fit a CU's 160 KiB of LDS", who, nb, K);
-  if (epi == EPI_QKV) {
-    if (H < 1 || KVH < 1 || H % KVH) return fail(c, DTK_ERR_ARG, "%s: H %d query heads over KVH %d key / value heads", who, H, KVH);
-    if (N != (H + 2 * KVH) * 128 || d != H * 128) return fail(c, DTK_ERR_ARG, "%s: QKV needs N = (H + 2 KVH) * 128 and d = H * 128", who);
-    if (T_max < 1) return fail(c, DTK_ERR_ARG, "%s: T_max %d", who, T_max);
-    for (int b = 0; b < nb; ++b)
-      if (pos[b] < 0 || pos[b] >= T_max) return fail(c, DTK_ERR_ARG, "%s: slot %d: position %d of %d rows", who, b, pos[b], T_max);
-    if (!rope_cos || !rope_sin || !q_io || !k_io || !v_io) return fail(c, DTK_ERR_ARG, "%s: QKV needs the rope tables and q / k / v buffers", who);
-  } else if (epi == EPI_SWIGLU) {
-    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io) return fail(c, DTK_ERR_ARG, "%s: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff and y", who);
-  } else if (epi == EPI_LOGITS) {
-    if (!logits_io) return fail(c, DTK_ERR_ARG, "%s: LOGITS needs the logits buffer", who);
-  } else if (!y_io) return fail(c, DTK_ERR_ARG, "%s: RESID / STORE need y", who);
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  const bool qkv = epi == EPI_QKV;
-  const size_t kv_slot = qkv ? (size_t)KVH * T_max * 128 : 0;
-  const size_t ny = epi == EPI_SWIGLU ? (size_t)((ff + 31) >> 5) * 512 : ((epi == EPI_STORE || epi == EPI_RESID) ? (size_t)nb * N : 0);
-  BatchState hbs; memset(&hbs, 0, sizeof hbs);
-  DecState hst[4]; memset(hst, 0, sizeof hst);
-  for (int j = 0; j < DTK_MAX_BATCH; ++j) hbs.share_src[j] = -1;
-  for (int b = 0; b < nb; ++b) { hbs.active[b] = active[b] ? 1 : 0; hst[b].pos = pos[b]; hst[b].next_pos = pos[b] + 1; }
-  OpRun r(c, who, scratch_fill);
-  GemvMvArgs g{};
-  if (W8) { g.W8 = r.in<uint8_t>(W8, (size_t)N * K); g.wscale = r.in<float>(wscale, N); }
-  else g.W = r.in<bf16_t>(W, (size_t)N * K);
-  g.X = r.in<bf16_t>(X, x_layout ? (size_t)((K + 31) >> 5) * 512 : (size_t)nb * K);
-  g.norm_w = r.in<bf16_t>(pro == PRO_RMSNORM ? norm_w : nullptr, pro == PRO_RMSNORM ? K : 0);
-  g.rope_cos = r.in<bf16_t>(qkv ? rope_cos : nullptr, qkv ? (size_t)T_max * 64 : 0);
-  g.rope_sin = r.in<bf16_t>(qkv ? rope_sin : nullptr, qkv ? (size_t)T_max * 64 : 0);
-  g.st = r.in<DecState>(hst, 4);
-  const BatchState* dbs = r.in<BatchState>(&hbs, 1);
-  g.bs = bs_null ? nullptr : dbs;
-  g.q_out = r.io<bf16_t>(qkv ? q_io : nullptr, qkv ? (size_t)nb * d : 0, "q");
-  g.kcache = r.io<bf16_t>(qkv ? k_io : nullptr, (size_t)nb * kv_slot, "k");
-  g.vcache = r.io<bf16_t>(qkv ? v_io : nullptr, (size_t)nb * kv_slot, "v");
-  g.Y = r.io<bf16_t>(ny ? y_io : nullptr, ny, "y");
-  g.logits = r.io<float>(epi == EPI_LOGITS ? logits_io : nullptr, epi == EPI_LOGITS ? (size_t)nb * N : 0, "logits");
-  g.N = N; g.K = K; g.ldx = K; g.x_rowmajor = x_layout == 0; g.eps = eps; g.ldy = N; g.kv_slot_stride = kv_slot;
-  g.T_max = T_max; g.d = d; g.ff = ff; g.H = H; g.KVH = KVH;
-  if (const int rc = r.upload(s)) return rc;      // (hbs and hst live on this frame: upload() waits for the copies)
-  {
-    MvShapeScope scope(epi, shape);
-    launch_gemv_mv(pro, epi, nb, g, s);
-  }
-  return r.finish(s);
-}
-
-// ---- w13.h's host code for the CPU tests: rows [N][K] bf16 <-> planes [N][dtk_w13_row_bytes(K)] + hb[N]; bad[N] = weights below the
-// row's window (0 = the row is packed exactly)
-int dtk_w13_row_bytes(int K) { return (K < 8 || (K & 7)) ? -1 : (int)w13_row_bytes(K); }
-int dtk_w13_pack_host(const uint16_t* W, int N, int K, uint8_t* planes, uint8_t* hb, int32_t* bad) {
-  if (!W || !planes || !hb || !bad || N < 1 || K < 8 || (K & 7)) return DTK_ERR_ARG;
-  for (int r = 0; r < N; ++r) bad[r] = w13_pack_row(W + (size_t)r * K, K, planes + (size_t)r * w13_row_bytes(K), hb + r);
-  return DTK_OK;
-}
-int dtk_w13_unpack_host(const uint8_t* planes, const uint8_t* hb, int N, int K, uint16_t* W) {
-  if (!W || !planes || !hb || N < 1 || K < 8 || (K & 7)) return DTK_ERR_ARG;
-  for (int r = 0; r < N; ++r) w13_unpack_row(planes + (size_t)r * w13_row_bytes(K), hb[r], K, W + (size_t)r * K);
-  return DTK_OK;
-}
-int dtk_w13_op_bad_rows(dtk_ctx* c) { return c ? c->w13_op_bad_rows : -1; }
-int dtk_w13_flagged_rows(dtk_ctx* c, int role) { return (c && role >= 0 && role < 5 && c->w13_ready) ? (int)c->w13_zrows[role] : -1; }
-int dtk_w13_row_bytes_host(const uint16_t* W, int N, int K, uint8_t* bytes) {
-  if (!W || !bytes || N < 0 || K < 8 || (K & 7)) return DTK_ERR_ARG;
-  for (int r = 0; r < N; ++r) bytes[r] = (uint8_t)w13_row_byte(W + (size_t)r * K, K);
-  return DTK_OK;
-}
-
-// ---- the batched decode GEMV family alone (dtk_op_gemv_b / dtk_op_gemv_bkp): host operands into the op scratch, the step's own
-// launchers (launch_retile / launch_retile_f8, launch_rmsnorm_b, launch_gemv_b, launch_gemv_bkp, launch_resid_norm_b) unchanged
-static inline size_t host_xtile_off(int slot, int k, int nsteps) {      // xtile_off (common.h)
-  return ((size_t)((slot >> 4) * nsteps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (slot & 15)) * 8 + (k & 7);
-}
-static inline int op_nt_of(int nslots) { const int hi = nslots - 1; return hi < 16 ? 1 : (hi < 32 ? 2 : 4); }   // as dtk_decode_batch_launch: from the highest slot
-// the weights as the loader leaves them: row-major upload, then the fragment-major (bf16) or pair-tiled (fp8) copy
-static int op_tiled_weights(dtk_ctx* c, size_t& off, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, GemvBArgs& g) {
-  hipStream_t s = c->stream;
-  if (W8) {
-    OPBUF(uint8_t, dW, (size_t)N * K); OPBUF(uint8_t, dT, tiled_bytes_f8(N, K)); OPBUF(float, dS, N);
-    HIPCHK(c, hipMemcpyAsync(dW, W8, (size_t)N * K, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dS, wscale, (size_t)N * 4, hipMemcpyHostToDevice, s));
-    launch_retile_f8(dW, dT, N, K, s);
-    g.W8 = dT; g.wscale = dS;
-  } else {
-    OPBUF(bf16_t, dW, (size_t)N * K); OPBUF(bf16_t, dT, tiled_elems(N, K));
-    HIPCHK(c, hipMemcpyAsync(dW, W, (size_t)N * K * 2, hipMemcpyHostToDevice, s));
-    launch_retile(dW, dT, N, K, s);
-    g.W = dT;
-  }
-  g.N = N; g.K = K;
-  return DTK_OK;
-}
-// the 64 slots' flags (slots >= nslots idle) and positions
-static int op_batch_state(dtk_ctx* c, size_t& off, const int32_t* active, const int32_t* pos, int nslots, GemvBArgs& g) {
-  OPBUF(BatchState, dbs, 1); OPBUF(DecState, dst, DTK_MAX_BATCH);
-  BatchState hbs; memset(&hbs, 0, sizeof hbs);
-  DecState hst[DTK_MAX_BATCH]; memset(hst, 0, sizeof hst);
-  for (int j = 0; j < DTK_MAX_BATCH; ++j) hbs.share_src[j] = -1;
-  for (int j = 0; j < nslots; ++j) {
-    hbs.active[j] = active[j] ? 1 : 0;
-    if (pos) { hst[j].pos = pos[j]; hst[j].next_pos = pos[j] + 1; }
-  }
-  HIPCHK(c, hipMemcpyAsync(dbs, &hbs, sizeof hbs, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(dst, hst, sizeof hst, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));      // (hbs / hst live on this frame)
-  g.bs = dbs; g.st = dst; g.nt = op_nt_of(nslots);
-  return DTK_OK;
-}
-// X [nslots][K] row-major -> the fragment-major input of 4 column tiles (zero beyond nslots and in the padding of the last k-step)
-static int op_x_fragments(dtk_ctx* c, size_t& off, const uint16_t* X, int nslots, int K, bf16_t** out) {
-  const int nsteps = (K + 31) >> 5;
-  const size_t elems = (size_t)4 * nsteps * 512;
-  OPBUF(bf16_t, dXf, elems);
-  std::vector<bf16_t> h(elems, (bf16_t)0);
-  for (int j = 0; j < nslots; ++j)
-    for (int k = 0; k < K; ++k) h[host_xtile_off(j, k, nsteps)] = X[(size_t)j * K + k];
-  HIPCHK(c, hipMemcpy(dXf, h.data(), elems * 2, hipMemcpyHostToDevice));
-  *out = dXf;
-  return DTK_OK;
-}
-
-int dtk_op_gemv_b(dtk_ctx* c, int epi, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K,
-                  const uint16_t* X, const uint16_t* norm_w, float eps, const int32_t* active, const int32_t* pos, int nslots,
-                  int d, int ff, int H, int KVH, int T_max, const uint16_t* rope_cos, const uint16_t* rope_sin,
-                  uint16_t* q_io, uint16_t* k_io, uint16_t* v_io, uint16_t* y_io, uint16_t* frag_io, float* logits_io,
-                  uint16_t* xn_out, uint32_t* err_out) {
-  if (!c || !X || !active || !err_out || (!W == !W8) || (W8 && !wscale)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: null argument, or not exactly one of W / W8 + wscale");
-  if (nslots < 1 || nslots > DTK_MAX_BATCH || N < 1 || K < 8 || (K & 7)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: nslots 1..64, N >= 1, K a multiple of 8");
-  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_QKV && epi != EPI_SWIGLU && epi != EPI_LOGITS) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: unknown epilogue %d", epi);
-  if (xn_out && !norm_w) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: xn_out without norm_w");
-  if (epi == EPI_QKV) {
-    if (H < 1 || KVH < 1 || H % KVH || N != (H + 2 * KVH) * 128 || d != H * 128 || T_max < 1 || !pos || !rope_cos || !rope_sin || !q_io || !k_io || !v_io)
-      return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: QKV needs N = (H + 2 KVH) * 128, d = H * 128, positions, rope tables and q / k / v buffers");
-    for (int j = 0; j < nslots; ++j)
-      if (active[j] && (pos[j] < 0 || pos[j] >= T_max)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: slot %d: position %d of %d rows", j, pos[j], T_max);
-  } else if (epi == EPI_SWIGLU) {
-    if (ff < 8 || (ff & 7) || N != 2 * ff || !y_io || !frag_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: SWIGLU needs ff a multiple of 8 (as dtk_create), N = 2 ff, y and the fragment buffer");
-  } else if (epi == EPI_LOGITS) {
-    if (!logits_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: LOGITS needs the logits buffer");
-  } else if (!y_io) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_b: RESID / STORE need y");
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  size_t off = 0;
-  GemvBArgs g{};
-  int rc = op_tiled_weights(c, off, W, W8, wscale, N, K, g);
-  if (rc) return rc;
-  if ((rc = op_batch_state(c, off, active, pos, nslots, g))) return rc;
-  const int nsteps = (K + 31) >> 5;
-  bf16_t* dXf = nullptr;
-  if (norm_w) {      // X = residual streams: k_rmsnorm_b writes the fragments of the active slots
-    const size_t fe = (size_t)4 * nsteps * 512;
-    OPBUF(bf16_t, dXr, (size_t)DTK_MAX_BATCH * K); OPBUF(bf16_t, dn, K); OPBUF(bf16_t, dF, fe);
-    HIPCHK(c, hipMemsetAsync(dXr, 0, (size_t)DTK_MAX_BATCH * K * 2, s));
-    HIPCHK(c, hipMemcpyAsync(dXr, X, (size_t)nslots * K * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)K * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(dF, 0, fe * 2, s));
-    launch_rmsnorm_b(dXr, K, dn, dF, K, K, eps, g.bs, 16 * g.nt, s);
-    dXf = dF;
-  } else if ((rc = op_x_fragments(c, off, X, nslots, K, &dXf))) return rc;
-  g.X = dXf; g.ldx = K;
-  OPBUF(unsigned, derr, 1);
-  HIPCHK(c, hipMemsetAsync(derr, 0, 4, s));
-  g.err = derr;
-  g.d = d; g.ff = ff; g.H = H; g.KVH = KVH; g.T_max = T_max;
-  const size_t kv_slot = (size_t)(KVH > 0 ? KVH : 0) * (T_max > 0 ? T_max : 0) * 128, kv = (size_t)DTK_MAX_BATCH * kv_slot;
-  const size_t frag_elems = (size_t)4 * ((ff + 31) >> 5) * 512;
-  bf16_t *dq = nullptr, *dK = nullptr, *dV = nullptr, *dY = nullptr;
-  float* dL = nullptr;
-  if (epi == EPI_QKV) {
-    OPBUF(bf16_t, q_, (size_t)DTK_MAX_BATCH * d); OPBUF(bf16_t, k_, kv); OPBUF(bf16_t, v_, kv);
-    OPBUF(bf16_t, cs_, (size_t)T_max * 64); OPBUF(bf16_t, sn_, (size_t)T_max * 64);
-    dq = q_; dK = k_; dV = v_;
-    HIPCHK(c, hipMemcpyAsync(dq, q_io, (size_t)DTK_MAX_BATCH * d * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dK, k_io, kv * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(dV, v_io, kv * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(cs_, rope_cos, (size_t)T_max * 64 * 2, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(sn_, rope_sin, (size_t)T_max * 64 * 2, hipMemcpyHostToDevice, s));
-    g.q_out = dq; g.kcache = dK; g.vcache = dV; g.kv_slot_stride = kv_slot; g.rope_cos = cs_; g.rope_sin = sn_;
-  } else if (epi == EPI_SWIGLU) {
-    OPBUF(bf16_t, y_, frag_elems);
-    dY = y_;
-    HIPCHK(c, hipMemcpyAsync(dY, frag_io, frag_elems * 2, hipMemcpyHostToDevice, s));
-    g.Y = dY; g.ldy = ff;
-  } else if (epi == EPI_LOGITS) {
-    OPBUF(float, l_, (size_t)DTK_MAX_BATCH * N);
-    dL = l_;
-    HIPCHK(c, hipMemcpyAsync(dL, logits_io, (size_t)DTK_MAX_BATCH * N * 4, hipMemcpyHostToDevice, s));
-    g.logits = dL;
-  } else {
-    OPBUF(bf16_t, y_, (size_t)DTK_MAX_BATCH * N);
-    dY = y_;
-    HIPCHK(c, hipMemcpyAsync(dY, y_io, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyHostToDevice, s));
-    g.Y = dY; g.ldy = N;
-  }
-  launch_gemv_b(epi, g, s);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  if (epi == EPI_QKV) {
-    HIPCHK(c, hipMemcpy(q_io, dq, (size_t)DTK_MAX_BATCH * d * 2, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(k_io, dK, kv * 2, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(v_io, dV, kv * 2, hipMemcpyDeviceToHost));
-  } else if (epi == EPI_SWIGLU) {
-    HIPCHK(c, hipMemcpy(frag_io, dY, frag_elems * 2, hipMemcpyDeviceToHost));
-    for (int j = 0; j < nslots; ++j)
-      for (int i = 0; i < ff; ++i) y_io[(size_t)j * ff + i] = frag_io[host_xtile_off(j, i, (ff + 31) >> 5)];
-  } else if (epi == EPI_LOGITS) {
-    HIPCHK(c, hipMemcpy(logits_io, dL, (size_t)DTK_MAX_BATCH * N * 4, hipMemcpyDeviceToHost));
-  } else HIPCHK(c, hipMemcpy(y_io, dY, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyDeviceToHost));
-  if (xn_out) {
-    std::vector<bf16_t> f((size_t)4 * nsteps * 512);
-    HIPCHK(c, hipMemcpy(f.data(), dXf, f.size() * 2, hipMemcpyDeviceToHost));
-    for (int j = 0; j < nslots; ++j)
-      for (int k = 0; k < K; ++k) xn_out[(size_t)j * K + k] = f[host_xtile_off(j, k, nsteps)];
-  }
-  HIPCHK(c, hipMemcpy(err_out, derr, 4, hipMemcpyDeviceToHost));
-  return DTK_OK;
-}
-
-int dtk_op_gemv_bkp(dtk_ctx* c, const uint16_t* W, const uint8_t* W8, const float* wscale, int N, int K, const uint16_t* X,
-                    const int32_t* active, int nslots, const uint16_t* norm_w, float eps, uint16_t* resid_io, uint16_t* xn_io,
-                    float* part_out, uint32_t* err_out) {
-  if (!c || !X || !active || !norm_w || !resid_io || !xn_io || !part_out || !err_out || (!W == !W8) || (W8 && !wscale))
-    return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: null argument, or not exactly one of W / W8 + wscale");
-  if (nslots < 1 || nslots > DTK_MAX_BATCH || N < 1 || K < 8 || (K & 7)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: nslots 1..64, N >= 1, K a multiple of 8");
-  {   // the step's own question, asked before anything is uploaded or launched (only the shape, the format and the tile count are read)
-    GemvBArgs t{};
-    float dummy = 0.f;
-    t.N = N; t.K = K; t.nt = op_nt_of(nslots); t.kpart = &dummy; t.W8 = W8;
-    if (!resid_kparts_covers(t)) return fail(c, DTK_ERR_ARG, "dtk_op_gemv_bkp: N %d, K %d, %d slots, %s weights: not covered by the K-slice kernels", N, K, nslots, W8 ? "fp8" : "bf16");
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  hipStream_t s = c->stream;
-  size_t off = 0;
-  GemvBArgs g{};
-  int rc = op_tiled_weights(c, off, W, W8, wscale, N, K, g);
-  if (rc) return rc;
-  if ((rc = op_batch_state(c, off, active, nullptr, nslots, g))) return rc;
-  bf16_t* dXf = nullptr;
-  if ((rc = op_x_fragments(c, off, X, nslots, K, &dXf))) return rc;
-  g.X = dXf; g.ldx = K;
-  const int nsteps_n = (N + 31) >> 5;
-  const size_t fe = (size_t)4 * nsteps_n * 512, pe = (size_t)8 * DTK_MAX_BATCH * N;
-  OPBUF(float, dP, pe); OPBUF(bf16_t, dR, (size_t)DTK_MAX_BATCH * N); OPBUF(bf16_t, dn, N); OPBUF(bf16_t, dF, fe); OPBUF(unsigned, derr, 1);
-  std::vector<bf16_t> f(fe, (bf16_t)0);
-  for (int j = 0; j < DTK_MAX_BATCH; ++j)
-    for (int k = 0; k < N; ++k) f[host_xtile_off(j, k, nsteps_n)] = xn_io[(size_t)j * N + k];
-  HIPCHK(c, hipMemsetAsync(dP, 0xFF, pe * 4, s));
-  HIPCHK(c, hipMemsetAsync(derr, 0, 4, s));
-  HIPCHK(c, hipMemcpyAsync(dR, resid_io, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dn, norm_w, (size_t)N * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dF, f.data(), fe * 2, hipMemcpyHostToDevice, s));
-  g.kpart = dP; g.err = derr; g.d = N; g.Y = dR; g.ldy = N;
-  launch_gemv_bkp(g, s);
-  launch_resid_norm_b(dP, dR, N, dn, dF, N, eps, g.bs, 16 * g.nt, s);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpy(part_out, dP, pe * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(resid_io, dR, (size_t)DTK_MAX_BATCH * N * 2, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(f.data(), dF, fe * 2, hipMemcpyDeviceToHost));
-  for (int j = 0; j < DTK_MAX_BATCH; ++j)
-    for (int k = 0; k < N; ++k) xn_io[(size_t)j * N + k] = f[host_xtile_off(j, k, nsteps_n)];
-  HIPCHK(c, hipMemcpy(err_out, derr, 4, hipMemcpyDeviceToHost));
-  return DTK_OK;
-}
-
-int dtk_op_layernorm(dtk_ctx* c, const uint16_t* X, const uint16_t* w, const uint16_t* b, int M, int D, float eps, uint16_t* Y) {
-  if (!c || !X || !w || !b || !Y || D % 8) return fail(c, DTK_ERR_ARG, "dtk_op_layernorm: bad argument");
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(bf16_t, dX, (size_t)M * D); OPBUF(bf16_t, dw, D); OPBUF(bf16_t, db, D); OPBUF(bf16_t, dY, (size_t)M * D);
-  hipStream_t s = c->stream;
-  HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)M * D * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(dw, w, (size_t)D * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(db, b, (size_t)D * 2, hipMemcpyHostToDevice, s));
-  launch_layernorm_rows(dX, D, dw, db, dY, D, M, D, eps, s);
-  HIPCHK(c, hipMemcpyAsync(Y, dY, (size_t)M * D * 2, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-struct OpPen { float pp, fp; const int64_t* ids; int n; };     // dtk_op_sample_pen's own arguments
-struct OpDry { const dtk_dry* d; const int64_t* hist; int n; };   // dtk_op_sample_dry's / dtk_op_dry_scan's: the history h[0, n) itself
-// a DRY state of the call's own in the op scratch (record, history, empty table and touched list), ready for launch_dry_scan
-static int op_dry_state(dtk_ctx* c, size_t& off, const OpDry& od, int V, DryScanArgs& ds) {
-  const int stride = (V + 15) & ~15, cap = od.n > 0 ? od.n : 1;
-  OPBUF(DryDev, ddev, 1); OPBUF(int32_t, dh, cap); OPBUF(int32_t, dt, cap); OPBUF(DryLen, dlen, 1); OPBUF(int32_t, dnt, 1); OPBUF(uint8_t, dm, stride);
-  const DryDev rec = dry_record(od.d);
-  const DryLen l{od.n, 0};
-  std::vector<int32_t> h32((size_t)(od.n > 0 ? od.n : 0));
-  for (int i = 0; i < od.n; ++i) h32[(size_t)i] = (int32_t)od.hist[i];
-  HIPCHK(c, hipMemcpy(ddev, &rec, sizeof rec, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dlen, &l, sizeof l, hipMemcpyHostToDevice));
-  if (od.n > 0) HIPCHK(c, hipMemcpy(dh, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(dnt, 0, sizeof(int32_t)));
-  HIPCHK(c, hipMemset(dm, 0, (size_t)stride));
-  ds = DryScanArgs{};
-  ds.dry = ddev; ds.hist = dh; ds.len = dlen; ds.hist_stride = cap; ds.m = dm; ds.m_stride = stride; ds.touched = dt; ds.n_touched = dnt;
-  ds.V = V; ds.bs = nullptr; ds.nslots = 1;
-  return DTK_OK;
-}
-static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr, const OpDry* dry = nullptr) {
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  OPBUF(float, dl, V); OPBUF(int64_t, dtok, 1); OPBUF(float2, dlp, 1); OPBUF(SamplingDev, dsp, 1);
-  hipStream_t s = c->stream;
-  PenDev* dpen = nullptr; uint16_t* dcnt = nullptr;
-  if (pen) {      // a count table of the call's own, built by the product scatter kernel from the token list
-    const int stride = (V + 7) & ~7;
-    OPBUF(PenDev, dpen_, 1); OPBUF(uint16_t, dcnt_, stride); OPBUF(int32_t, dids, pen->n > 0 ? pen->n : 1);
-    dpen = dpen_; dcnt = dcnt_;
-    const PenDev pv{pen->pp, pen->fp};
-    std::vector<int32_t> ids32((size_t)(pen->n > 0 ? pen->n : 0));
-    for (int i = 0; i < pen->n; ++i) ids32[(size_t)i] = (int32_t)pen->ids[i];
-    HIPCHK(c, hipMemcpy(dpen, &pv, sizeof pv, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dids, ids32.data(), sizeof(int32_t) * ids32.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemsetAsync(dcnt, 0, sizeof(uint16_t) * (size_t)stride, s));
-    launch_count_scatter(dids, pen->n, dcnt, V, s);
-  }
-  HIPCHK(c, hipMemcpyAsync(dl, logits, (size_t)V * 4, hipMemcpyHostToDevice, s));
-  ExtDev xd{};
-  if (ext) {      // the context's configuration with the call's own (min_p, epsilon_cutoff)
-    xd = ext_dev(ext);
-    HIPCHK(c, hipMemcpyAsync(dsp, c->sp, sizeof(SamplingDev), hipMemcpyDeviceToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char*>(dsp) + offsetof(SamplingDev, qmin), &xd, sizeof xd, hipMemcpyHostToDevice, s));
-  }
-  SampleArgs sa;
-  sa.logits = dl; sa.V = V; sa.sp = c->sp; sa.st = c->st; sa.embed = c->embed; sa.x = c->x; sa.d = c->d;
-  sa.tok_ring = dtok; sa.ring = 1; sa.probs_out = probs_out ? c->probs_dev : nullptr; sa.advance = 0;
-  sa.step_override = step; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
-  sa.lp_ring = lp_out ? dlp : nullptr;
-  if (ext) { sa.sp = dsp; sa.trunc = (xd.qmin != 0 || xd.eps != 0.f) ? 1 : 0; }
-  else sa.trunc = c->trunc_single ? 1 : 0;
-  if (pen) { sa.pen = dpen; sa.pen_cnt = dcnt; sa.pen_stride = (V + 7) & ~7; }      // advance = 0: nothing is counted
-  if (dry && pen) {      // the product scan over the call's own history, then the PN samplers with its table
-    DryScanArgs ds;
-    if (const int rc = op_dry_state(c, off, *dry, V, ds)) return rc;
-    launch_dry_scan(ds, s);
-    sa.dry = ds.dry; sa.dry_m = ds.m; sa.dry_stride = ds.m_stride;
-  }
-  const bool needs_topk = c->sampling.do_sample && c->sampling.top_k > 0 && c->sampling.top_k < V;
-  if (sample_mb_preferred(V, c->sampling.do_sample != 0) && !needs_topk && !getenv("DTK_SAMPLER")) launch_sample_mb(sa, s); else launch_sample(sa, s);
-  HIPCHK(c, hipMemcpyAsync(token_out, dtok, 8, hipMemcpyDeviceToHost, s));
-  if (lp_out) HIPCHK(c, hipMemcpyAsync(lp_out, dlp, sizeof(float2), hipMemcpyDeviceToHost, s));
-  if (probs_out) HIPCHK(c, hipMemcpyAsync(probs_out, c->probs_dev, (size_t)V * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  return DTK_OK;
-}
-
-int dtk_op_sample(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out) {
-  if (!c || !logits || !token_out || V < 1 || V > c->V) return fail(c, DTK_ERR_ARG, "dtk_op_sample: bad argument");
-  return op_sample_impl(c, logits, V, step, token_out, probs_out, nullptr);
-}
-
-// dtk_op_sample + lp_out[2] = (logprob, sample_logprob) of the token: the LP sampler instantiations over given logits.  The row may
-// be longer than the context's own vocabulary (any V the samplers take: <= 262 144) as long as probs_out is null
-int dtk_op_sample_lp(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out) {
-  if (!c || !logits || !token_out || !lp_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V))
-    return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: bad argument");
-  if (!c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_lp: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
-  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out);
-}
-
-// dtk_op_sample_lp under the context's configuration with the call's own (min_p, epsilon_cutoff): the TR sampler instantiations (both 0:
-// the kernels dtk_op_sample_lp runs).  lp_out may be null (the LP = false kernels; no "logprobs" option needed then)
-int dtk_op_sample_ext(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                      const dtk_sampling_ext* ext) {
-  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V))
-    return fail(c, DTK_ERR_ARG, "dtk_op_sample_ext: bad argument");
-  if (const int rc = ext_check(c, ext, "dtk_op_sample_ext")) return rc;
-  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_ext: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
-  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext);
-}
-
-// dtk_op_sample_ext (ext may be null: the context's own min_p / epsilon_cutoff) with a presence / frequency penalty over the counts of a
-// given token list: the PN sampler instantiations and k_count_scatter, whatever the two values are
-int dtk_op_sample_pen(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                      const dtk_sampling_ext* ext, float presence, float frequency, const int64_t* counted_ids, int n_counted) {
-  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V) || n_counted < 0 ||
-      n_counted > 65535 || (n_counted > 0 && !counted_ids))
-    return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: bad argument");
-  if (ext) if (const int rc = ext_check(c, ext, "dtk_op_sample_pen")) return rc;
-  if (const int rc = pen_check(c, presence, frequency, 0, "dtk_op_sample_pen")) return rc;
-  for (int i = 0; i < n_counted; ++i)
-    if (counted_ids[i] < 0 || counted_ids[i] >= V) return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: counted id %lld outside [0, %d)", (long long)counted_ids[i], V);
-  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_pen: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
-  const OpPen pn{presence, frequency, counted_ids, n_counted};
-  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn);
-}
-
-static int op_dry_check(dtk_ctx* c, const dtk_dry* d, int V, const int64_t* hist, int n, const char* who) {
-  if (const int rc = dry_check(c, d, V, who)) return rc;
-  if (n < 0 || n > 65535 || (n > 0 && !hist)) return fail(c, DTK_ERR_ARG, "%s: a history of 0 .. 65535 ids", who);
-  for (int i = 0; i < n; ++i)
-    if (hist[i] < 0 || hist[i] >= V) return fail(c, DTK_ERR_ARG, "%s: history id %lld outside [0, %d)", who, (long long)hist[i], V);
-  return DTK_OK;
-}
-
-// dtk_op_sample_pen with DRY over a given history h[0, n) (dry->start is not used: the history is given as it stands): k_dry_scan, then
-// the PN sampler instantiations with both the count table and the match table, whatever the values are
-int dtk_op_sample_dry(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                      const dtk_sampling_ext* ext, float presence, float frequency, const int64_t* counted_ids, int n_counted,
-                      const int64_t* history, int n_history, const dtk_dry* dry) {
-  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V) || n_counted < 0 ||
-      n_counted > 65535 || (n_counted > 0 && !counted_ids))
-    return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: bad argument");
-  if (ext) if (const int rc = ext_check(c, ext, "dtk_op_sample_dry")) return rc;
-  if (const int rc = pen_check(c, presence, frequency, 0, "dtk_op_sample_dry")) return rc;
-  if (const int rc = op_dry_check(c, dry, V, history, n_history, "dtk_op_sample_dry")) return rc;
-  for (int i = 0; i < n_counted; ++i)
-    if (counted_ids[i] < 0 || counted_ids[i] >= V) return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: counted id %lld outside [0, %d)", (long long)counted_ids[i], V);
-  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_dry: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
-  const OpPen pn{presence, frequency, counted_ids, n_counted};
-  const OpDry od{dry, history, n_history};
-  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn, &od);
-}
-
-// k_dry_scan alone over a given history; with history2, a second scan of that history on the state the first one left (table and
-// touched list), as two consecutive steps of a sequence do.  The result is read from the WHOLE table behind the last scan: every id
-// with M != 0 in ascending order, so an entry a scan failed to clear shows.  Returns their number (the first n_max go out) or an error
-int dtk_op_dry_scan(dtk_ctx* c, int V, const int64_t* history, int n_history, const int64_t* history2, int n_history2, const dtk_dry* dry,
-                    int32_t* ids_out, uint8_t* m_out, int n_max) {
-  if (!c || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || n_max < 0 || (n_max > 0 && (!ids_out || !m_out)))
-    return fail(c, DTK_ERR_ARG, "dtk_op_dry_scan: bad argument");
-  if (const int rc = op_dry_check(c, dry, V, history, n_history, "dtk_op_dry_scan")) return rc;
-  if (history2) if (const int rc = op_dry_check(c, dry, V, history2, n_history2, "dtk_op_dry_scan")) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  size_t off = 0;
-  hipStream_t s = c->stream;
-  const int cap = history2 && n_history2 > n_history ? n_history2 : n_history;
-  std::vector<int64_t> first(history, history + n_history);
-  first.resize((size_t)cap, 0);      // (room for the longer of the two; the length says what counts)
-  DryScanArgs ds;
-  if (const int rc = op_dry_state(c, off, OpDry{dry, first.data(), cap}, V, ds)) return rc;
-  const DryLen l1{n_history, 0};
-  HIPCHK(c, hipMemcpy(ds.len, &l1, sizeof l1, hipMemcpyHostToDevice));
-  launch_dry_scan(ds, s);
-  if (history2) {
-    HIPCHK(c, hipStreamSynchronize(s));
-    std::vector<int32_t> h32((size_t)n_history2);
-    for (int i = 0; i < n_history2; ++i) h32[(size_t)i] = (int32_t)history2[i];
-    const DryLen l2{n_history2, 0};
-    if (n_history2 > 0) HIPCHK(c, hipMemcpy(ds.hist, h32.data(), sizeof(int32_t) * h32.size(), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ds.len, &l2, sizeof l2, hipMemcpyHostToDevice));
-    launch_dry_scan(ds, s);
-  }
-  HIPCHK(c, hipStreamSynchronize(s));
-  HIPCHK(c, hipGetLastError());
-  std::vector<uint8_t> tab((size_t)ds.m_stride);
-  HIPCHK(c, hipMemcpy(tab.data(), ds.m, tab.size(), hipMemcpyDeviceToHost));
-  int k = 0;
-  for (int t = 0; t < V; ++t)
-    if (tab[(size_t)t]) { if (k < n_max) { ids_out[k] = t; m_out[k] = tab[(size_t)t]; } ++k; }
-  return k;
-}
 
 }  // extern "C"
 #pragma GCC visibility pop

@@ -186,7 +186,7 @@ def test_header_declares_the_function_and_symbols_list_it():
     assert re.search(r"#define\s+DTK_ABI_VERSION\s+7\b", header) and _lib.DTK_ABI_VERSION == 7
     table = (ROOT / "INTEGRATION.md").read_text()
     assert all(f"`{name}(" in table for name in NEW)
-    src = (ROOT / "detikzify_amd" / "csrc" / "dtk_api.hip").read_text()
+    src = (ROOT / "detikzify_amd" / "csrc" / "dtk_ops.hip").read_text()
     body = src[src.index("int dtk_op_gemv_mv_role("):]
     body = body[:body.index("\n}\n")]
     assert "MvShapeScope scope(epi, shape);" in body and "set_gemv_mv_shape(epi, -1)" in src          # the shape is restored on every exit path

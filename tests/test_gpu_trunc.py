@@ -20,7 +20,7 @@ from tests.helpers import TINY, sketch_image
 
 pytestmark = pytest.mark.gpu
 
-# One V per sampler family, by the launchers' own rule (csrc/kernels_decode.hip launch_sample_b, csrc/dtk_api.hip op_sample_impl):
+# One V per sampler family, by the launchers' own rule (csrc/kernels_decode.hip launch_sample_b, csrc/dtk_ops.hip op_sample_impl):
 #   "if (sample_mb_preferred(V, do_sample) && !needs_topk) launch_sample_mb(...); else launch_sample(...)"  with
 #   sample_mb_supported(V) = V > 32768,  needs_topk = do_sample && 0 < top_k < V,  and inside launch_sample:
 #   "sample_fast_ok(a) = a.V <= SF_PER * SAMPLE_THREADS" (= 32 768) -> k_sample_fast, else k_sample.
