@@ -71,6 +71,16 @@ class DtkDry(C.Structure):
                 ("n_breakers", C.c_int32), ("breakers", C.c_int32 * DTK_DRY_MAX_BREAKERS)]
 
 
+DTK_BIAS_MAX = 256
+DTK_LEN_MAX_EOS = 8
+
+
+class DtkLengthCtl(C.Structure):
+    """dtk_length_ctl: the length rules of one sequence, set after dtk_set_sampling[_slot] (which resets them to off); all 0 = off"""
+    _fields_ = [("min_new_tokens", C.c_int32), ("decay_start", C.c_int32), ("decay_factor", C.c_double), ("start", C.c_int32),
+                ("n_eos", C.c_int32), ("eos_ids", C.c_int32 * DTK_LEN_MAX_EOS)]
+
+
 class DtkStats(C.Structure):
     _fields_ = [
         ("weight_bytes_per_token", C.c_uint64), ("kv_bytes_per_ctx_token", C.c_uint64),
@@ -126,6 +136,9 @@ class DtkEngineOps(C.Structure):
     PENALTIES = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int)
     # not a field: dtk_engine_set_dry_op's argument (dev, slot, dry)
     DRY = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkDry))
+    # not fields: dtk_engine_set_length_control_op's (dev, slot, ctl) and dtk_engine_set_logit_bias_op's (dev, slot, ids, values, n)
+    LENGTH_CTL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkLengthCtl))
+    LOGIT_BIAS = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int)
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -294,6 +307,20 @@ SYMBOLS = {
     "dtk_engine_submit_dry": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int, C.POINTER(DtkDry),
                                         C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dtk_engine_set_dry_op": (C.c_int, [_P, DtkEngineOps.DRY]),
+    # additive (ABI stays 7): min_new_tokens, the EOS length decay and the logit bias, around the penalties
+    "dtk_set_length_control": (C.c_int, [_P, C.POINTER(DtkLengthCtl)]),
+    "dtk_set_length_control_slot": (C.c_int, [_P, C.c_int, C.POINTER(DtkLengthCtl)]),
+    "dtk_set_logit_bias": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]),
+    "dtk_set_logit_bias_slot": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]),
+    "dtk_logit_bias_table": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), C.c_int]),
+    "dtk_op_sample_shape": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64), _P, C.POINTER(C.c_float), C.POINTER(DtkSamplingExt),
+                                      C.c_float, C.c_float, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(DtkDry),
+                                      C.c_int, C.POINTER(DtkLengthCtl), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]),
+    "dtk_engine_submit_shape": (C.c_int, [_P, C.POINTER(DtkJoin), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int, C.POINTER(DtkDry),
+                                          C.POINTER(DtkLengthCtl), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                          C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_length_control_op": (C.c_int, [_P, DtkEngineOps.LENGTH_CTL]),
+    "dtk_engine_set_logit_bias_op": (C.c_int, [_P, DtkEngineOps.LOGIT_BIAS]),
 }
 
 _lib = None
@@ -341,6 +368,9 @@ def load_library() -> C.CDLL:
     if lib.dtk_abi_struct_size(14) != C.sizeof(DtkDry):
         raise DtkError(f"struct layout mismatch with include/dtk.h: DtkDry is {C.sizeof(DtkDry)} here, "
                        f"{lib.dtk_abi_struct_size(14)} in the library")
+    if lib.dtk_abi_struct_size(16) != C.sizeof(DtkLengthCtl):
+        raise DtkError(f"struct layout mismatch with include/dtk.h: DtkLengthCtl is {C.sizeof(DtkLengthCtl)} here, "
+                       f"{lib.dtk_abi_struct_size(16)} in the library")
     _lib = lib
     return lib
 

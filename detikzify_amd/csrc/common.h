@@ -185,6 +185,60 @@ struct DryLen { int32_t n; int32_t skip; };
 // only lengths >= allowed)
 __device__ __forceinline__ float dry_apply(float z, unsigned m, const float* pen) { return m ? z - pen[m] : z; }
 
+// Length control and logit bias (dtk_set_length_control / dtk_set_logit_bias; all off by default): a record of its own per sequence,
+// read only by the PN sampler instantiations when SampleArgs::len is set.  n = next_pos - start at the sampler.  The EOS rules touch the
+// ids eos[0, n_eos): below min_new their logit is -inf; above decay_begin it grows by |z| * m[n - decay_begin], m the sequence's host-built
+// table (no pow runs on the device).  n_bias != 0: the sequence's dense float [V] bias table holds something.
+#define DTK_BIAS_MAX 256
+#define DTK_LEN_MAX_EOS 8
+#define DTK_LEN_NO_DECAY 0x7fffffff
+struct LenDev {
+  int32_t on;                         // an EOS rule can apply: n_eos > 0 and (min_new > 0 or a decay)
+  int32_t start;                      // length_start
+  int32_t min_new;                    // min_new_tokens
+  int32_t decay_begin;                // decay_start, DTK_LEN_NO_DECAY without a decay
+  int32_t n_eos;
+  int32_t eos[DTK_LEN_MAX_EOS];
+  int32_t n_bias;                     // entries of the bias table that are not 0
+};
+// what a sampler block derives from the record and the sequence's length, once (block-uniform)
+struct ShapeRt {
+  const float* bias = nullptr;        // the sequence's table, null = no bias
+  const int32_t* eos = nullptr;
+  int ne = 0;                         // 0 = no EOS rule applies at this length
+  float mk = 0.f;                     // m[n - decay_begin]
+  bool dec = false, neg = false;      // the decay / the -inf applies
+};
+__device__ __forceinline__ ShapeRt shape_bind(const LenDev* l, const float* m, const float* bias, int cur) {
+  ShapeRt s;
+  if (l->n_bias != 0) s.bias = bias;
+  if (l->on) {
+    const int n = cur - l->start;
+    s.neg = n < l->min_new;
+    s.dec = n > l->decay_begin;
+    if (s.dec) s.mk = m[n - l->decay_begin];
+    if (s.neg || s.dec) { s.ne = l->n_eos; s.eos = l->eos; }
+  }
+  return s;
+}
+// z + b as one fp32 addition; the untouched bits of z where the table holds 0
+__device__ __forceinline__ float bias_apply(float z, float b) { return b != 0.f ? z + b : z; }
+// z + fl(|z| * m) in two fp32 roundings.  Contraction is switched off for this body: the build's default would fuse the pair into one fma
+// (one rounding), and so would a detour through double, which the compiler narrows back to the fp32 pair first
+__device__ __forceinline__ float decay_apply(float z, float m) {
+#pragma clang fp contract(off)
+  const float p = fabsf(z) * m;
+  return z + p;
+}
+// the EOS rules on the (biased, penalised) logit z of id i: the decay, then -inf
+__device__ __forceinline__ float eos_apply(float z, int i, const ShapeRt& s) {
+  bool hit = false;
+  for (int j = 0; j < s.ne; ++j) hit = hit || s.eos[j] == i;
+  if (!hit) return z;
+  if (s.dec) z = decay_apply(z, s.mk);
+  return s.neg ? -INFINITY : z;
+}
+
 // scratch of the multi-block sampler (kernels_sample_mb.hip), one per sequence / slot
 #define DTK_SAMPLE_MB_MAX_SLICES 32      // 32 x 8192 = vocabularies up to 262 144
 struct SampleMB {
@@ -200,7 +254,8 @@ struct SampleMB {
   // DecState.draw / .force_plus1 as they were BEFORE this step's draw kernel (written by block 0 of k_smb_max): k_smb_draw's
   // blocks read only these — its last block rewrites DecState while blocks of the same slot may not have started yet
   unsigned int draw_snap;
-  int forced_snap, pad;
+  int forced_snap;
+  int cur_snap;      // (was padding) DecState.next_pos likewise, written by the PN chain with SampleArgs::len alone: the sequence's length
   // log-probabilities (SampleArgs::lp_ring): every slice's online log-sum-exp state of its RAW logits, left by k_smb_max<true>
   float lmax[DTK_SAMPLE_MB_MAX_SLICES];
   float lsum[DTK_SAMPLE_MB_MAX_SLICES];

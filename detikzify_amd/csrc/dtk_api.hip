@@ -9,6 +9,7 @@
 //   HF GenerationMixin._sample loop body                      via infer/generate.py:218-227
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -567,8 +568,14 @@ static inline hipError_t copy_lp_ring(dtk_ctx* c, bool batch) {
 static void pen_args(const dtk_ctx* c, SampleArgs& sa, DryScanArgs& ds, bool batch) {
   const bool dry = (batch ? c->dry_batch : c->dry_single) && c->dry_tab;
   const bool pen = (batch ? c->pen_batch : c->pen_single) && c->pen_tab;
-  if (!(pen || dry) || !c->pen_dev || !c->pen_tok) return;
+  // dtk_set_length_control / dtk_set_logit_bias: likewise the PN samplers, which then read the sequences' LenDev records
+  const bool len = (batch ? c->len_batch : c->len_single) && c->len_dev;
+  if (!(pen || dry || len) || !c->pen_dev || !c->pen_tok) return;
   const int first = batch ? 1 : 0;
+  if (len) {
+    sa.len = c->len_dev + first; sa.len_m = c->len_m + (size_t)first * c->len_m_stride; sa.len_m_stride = c->len_m_stride;
+    sa.bias = c->bias_tab + (size_t)first * c->bias_stride; sa.bias_stride = c->bias_stride;
+  }
   // (a launch with DRY alone has records of 0 / 0 and no count tables: nothing reads pen_cnt)
   sa.pen = c->pen_dev + first; sa.pen_cnt = c->pen_tab ? c->pen_tab + (size_t)first * c->pen_stride : nullptr; sa.pen_stride = c->pen_stride;
   sa.pen_tok = c->pen_tok + first;
@@ -1043,6 +1050,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   if (c->bgraph_trunc != c->trunc_batch) { drop_batch_graphs(c); c->bgraph_trunc = c->trunc_batch; }
   if (c->bgraph_pen != c->pen_batch) { drop_batch_graphs(c); c->bgraph_pen = c->pen_batch; }
   if (c->bgraph_dry != c->dry_batch) { drop_batch_graphs(c); c->bgraph_dry = c->dry_batch; }
+  if (c->bgraph_len != c->len_batch) { drop_batch_graphs(c); c->bgraph_len = c->len_batch; }
   if (c->bgraph_ready[gi]) return DTK_OK;
   HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   c->launch_refused = false;
@@ -1065,6 +1073,7 @@ int ensure_graph(dtk_ctx* c) {
   if (c->graph_trunc != c->trunc_single) { drop_graph(c); c->graph_trunc = c->trunc_single; }
   if (c->graph_pen != c->pen_single) { drop_graph(c); c->graph_pen = c->pen_single; }
   if (c->graph_dry != c->dry_single) { drop_graph(c); c->graph_dry = c->dry_single; }
+  if (c->graph_len != c->len_single) { drop_graph(c); c->graph_len = c->len_single; }
   if (c->graph_ready) return DTK_OK;
   // two captures of the same step: split-K attention (any context) and the one-block-per-head
   // attention used while the context is short; the host picks per step (it knows the position)
@@ -1307,6 +1316,140 @@ static int dry_set(dtk_ctx* c, int q, const dtk_dry* d) {
   return dry_rebuild(c, q, sh.cached_ids.data(), (int)sh.cached_ids.size(), sh.forced_pending);
 }
 
+// ---- length control and logit bias: the records, the decay tables and the bias tables ------------------------------------------------
+static inline bool len_on(const dtk_ctx* c, int q) { return c->len_val[q].on != 0 || c->len_val[q].n_bias != 0; }
+
+extern "C++" int len_check(dtk_ctx* c, const dtk_length_ctl* l, int V, const char* who) {
+  if (!l) return fail(c, DTK_ERR_ARG, "%s: no dtk_length_ctl", who);
+  if (l->min_new_tokens < 0) return fail(c, DTK_ERR_ARG, "%s: min_new_tokens must be >= 0", who);
+  if (l->decay_start < 0) return fail(c, DTK_ERR_ARG, "%s: decay_start must be >= 0", who);
+  if (l->start < 0) return fail(c, DTK_ERR_ARG, "%s: length_start must be >= 0", who);
+  if (l->decay_factor != 0.) {
+    if (!(l->decay_factor > 0. && l->decay_factor <= DBL_MAX)) return fail(c, DTK_ERR_ARG, "%s: decay_factor must be finite and > 0 (0 = no decay)", who);
+    if (l->decay_start < l->min_new_tokens) return fail(c, DTK_ERR_ARG, "%s: decay_start %d is below min_new_tokens %d", who, l->decay_start, l->min_new_tokens);
+  }
+  if (l->n_eos < 0 || l->n_eos > DTK_LEN_MAX_EOS) return fail(c, DTK_ERR_ARG, "%s: at most %d EOS ids", who, DTK_LEN_MAX_EOS);
+  for (int i = 0; i < l->n_eos; ++i)
+    if (l->eos_ids[i] < 0 || l->eos_ids[i] >= V) return fail(c, DTK_ERR_ARG, "%s: EOS id %d outside [0, %d)", who, l->eos_ids[i], V);
+  return DTK_OK;
+}
+
+// the device record of a dtk_length_ctl (null: off); a repeated EOS id is kept once.  n_bias stays with the caller
+extern "C++" LenDev len_record(const dtk_length_ctl* l) {
+  LenDev v{};
+  v.decay_begin = DTK_LEN_NO_DECAY;
+  if (!l) return v;
+  v.start = l->start; v.min_new = l->min_new_tokens;
+  if (l->decay_factor != 0.) v.decay_begin = l->decay_start;
+  for (int i = 0; i < l->n_eos; ++i) {
+    bool seen = false;
+    for (int j = 0; j < v.n_eos; ++j) seen = seen || v.eos[j] == l->eos_ids[i];
+    if (!seen) v.eos[v.n_eos++] = l->eos_ids[i];
+  }
+  v.on = (v.n_eos > 0 && (v.min_new > 0 || v.decay_begin != DTK_LEN_NO_DECAY)) ? 1 : 0;
+  return v;
+}
+
+// m[k] = min((float)(pow(factor, k) - 1.0), 2^100) for k < n (include/dtk.h: the oracle reproduces it bit for bit)
+extern "C++" void len_table(double factor, float* m, int n) {
+  for (int k = 0; k < n; ++k) {
+    const double v = pow(factor, (double)k) - 1.0;      // (clamped in double: the same value, and no out-of-range conversion)
+    m[k] = v < 0x1p100 ? (float)v : 0x1p100f;
+  }
+}
+
+extern "C++" int bias_check(dtk_ctx* c, const int32_t* ids, const float* values, int n, int V, const char* who) {
+  if (n < 0 || n > DTK_BIAS_MAX || (n > 0 && (!ids || !values))) return fail(c, DTK_ERR_ARG, "%s: at most %d (id, value) pairs", who, DTK_BIAS_MAX);
+  for (int i = 0; i < n; ++i) {
+    if (ids[i] < 0 || ids[i] >= V) return fail(c, DTK_ERR_ARG, "%s: biased id %d outside [0, %d)", who, ids[i], V);
+    if (!(values[i] >= -100.f && values[i] <= 100.f)) return fail(c, DTK_ERR_ARG, "%s: a bias must be finite and in [-100, 100]", who);
+    for (int j = 0; j < i; ++j)
+      if (ids[j] == ids[i]) return fail(c, DTK_ERR_ARG, "%s: id %d is listed twice", who, ids[i]);
+  }
+  return DTK_OK;
+}
+
+// everything the two features keep on the device (with the penalties' records: the rules ride the PN samplers), at the first value that
+// is set: the records, the decay tables and the bias tables together, so that a captured step never holds a pointer that is still null
+// (len_dev, assigned last, says that everything exists; a buffer that a failed attempt left is kept for the next one)
+static int len_alloc_records(dtk_ctx* c) {
+  if (c->len_dev) return DTK_OK;
+  if (const int rc = pen_alloc_records(c)) return rc;
+  const int nrec = 1 + DTK_MAX_SLOTS;
+  const size_t nseq = (size_t)(1 + c->nb);
+  if (!c->len_stage) HIPCHK(c, hipHostMalloc((void**)&c->len_stage, sizeof(LenDev) * nrec, hipHostMallocDefault));
+  c->len_m_stride = c->Tmax + 1;
+  if (!c->len_m_stage) HIPCHK(c, hipHostMalloc((void**)&c->len_m_stage, sizeof(float) * nseq * c->len_m_stride, hipHostMallocDefault));
+  if (!c->len_m_up) HIPCHK(c, hipEventCreateWithFlags(&c->len_m_up, hipEventDisableTiming));
+  if (!c->len_m) {
+    float* t = nullptr;
+    HIPCHK(c, hipMalloc(&t, sizeof(float) * nseq * c->len_m_stride));
+    c->len_m = t;
+    HIPCHK(c, hipMemset(c->len_m, 0, sizeof(float) * nseq * c->len_m_stride));
+  }
+  c->bias_stride = (c->V + 7) & ~7;
+  if (!c->bias_tab) {
+    float* t = nullptr;
+    HIPCHK(c, hipMalloc(&t, sizeof(float) * nseq * c->bias_stride));
+    c->bias_tab = t;
+    HIPCHK(c, hipMemset(c->bias_tab, 0, sizeof(float) * nseq * c->bias_stride));
+  }
+  LenDev* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, sizeof(LenDev) * nrec));
+  for (int q = 0; q < nrec; ++q) c->len_stage[q] = len_record(nullptr);
+  if (hipMemcpy(p, c->len_stage, sizeof(LenDev) * nrec, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return fail(c, DTK_ERR_HIP, "length control: the records' upload failed"); }
+  c->len_dev = p;
+  return DTK_OK;
+}
+static int len_upload(dtk_ctx* c, int q) {
+  c->len_stage[q] = c->len_val[q];
+  HIPCHK(c, hipMemcpyAsync(c->len_dev + q, &c->len_stage[q], sizeof(LenDev), hipMemcpyHostToDevice, c->stream));
+  if (q == 0) c->len_single = len_on(c, 0);
+  else {
+    bool any = false;
+    for (int j = 1; j <= c->nb; ++j) any = any || len_on(c, j);
+    c->len_batch = any;
+  }
+  return DTK_OK;
+}
+
+// the rules of sequence q (null: off, the reset of dtk_set_sampling[_slot]).  The decay table is rebuilt only when the factor changes
+static int len_set(dtk_ctx* c, int q, const dtk_length_ctl* l) {
+  LenDev v = len_record(l);
+  if (!v.on && !c->len_val[q].on) return DTK_OK;      // nothing to switch on or off
+  if (const int rc = len_alloc_records(c)) return rc;
+  if (v.on && v.decay_begin != DTK_LEN_NO_DECAY) {
+    if (c->len_factor[q] != l->decay_factor) {
+      HIPCHK(c, hipEventSynchronize(c->len_m_up));      // (the mirror's last upload; done long ago unless two setters follow each other)
+      float* st = c->len_m_stage + (size_t)q * c->len_m_stride;
+      len_table(l->decay_factor, st, c->len_m_stride);
+      HIPCHK(c, hipMemcpyAsync(c->len_m + (size_t)q * c->len_m_stride, st, sizeof(float) * (size_t)c->len_m_stride, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipEventRecord(c->len_m_up, c->stream));
+      c->len_factor[q] = l->decay_factor;
+    }
+  }
+  v.n_bias = c->len_val[q].n_bias;
+  c->len_val[q] = v;
+  return len_upload(c, q);
+}
+
+// the bias table of sequence q from n (id, value) pairs (n = 0: none, the reset of dtk_set_sampling[_slot]): the ids the table holds
+// go back to 0, then the new pairs are written; pairs whose value is 0 are not kept
+static int bias_set(dtk_ctx* c, int q, const int32_t* ids, const float* values, int n) {
+  std::vector<int32_t>& held = c->bias_ids[q];
+  std::vector<int32_t> nid; std::vector<float> nval;
+  for (int i = 0; i < n; ++i) if (values[i] != 0.f) { nid.push_back(ids[i]); nval.push_back(values[i]); }
+  if (nid.empty() && held.empty()) return DTK_OK;      // nothing to switch on or off
+  if (const int rc = len_alloc_records(c)) return rc;
+  float* tab = c->bias_tab + (size_t)q * c->bias_stride;
+  launch_bias_scatter(held.data(), nullptr, (int)held.size(), tab, c->V, c->stream);
+  launch_bias_scatter(nid.data(), nval.data(), (int)nid.size(), tab, c->V, c->stream);
+  HIPCHK(c, hipGetLastError());
+  held = nid;
+  c->len_val[q].n_bias = (int32_t)nid.size();
+  return len_upload(c, q);
+}
+
 int dtk_abi_struct_size(int which) {
   switch (which) {
     case 0: return (int)sizeof(dtk_config);
@@ -1323,6 +1466,7 @@ int dtk_abi_struct_size(int which) {
     case 11: return (int)sizeof(dtk_adapter_config);
     case 12: return (int)sizeof(dtk_sampling_ext);
     case 14: return (int)sizeof(dtk_dry);      // (13 stays unassigned: -1)
+    case 16: return (int)sizeof(dtk_length_ctl);      // (15 stays unassigned too)
     default: return -1;
   }
 }
@@ -1527,6 +1671,12 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->dry_len_stage) (void)hipHostFree(c->dry_len_stage);
   if (c->dry_touched) (void)hipFree(c->dry_touched);
   if (c->dry_ntouched) (void)hipFree(c->dry_ntouched);
+  if (c->len_dev) (void)hipFree(c->len_dev);
+  if (c->len_stage) (void)hipHostFree(c->len_stage);
+  if (c->len_m) (void)hipFree(c->len_m);
+  if (c->len_m_stage) (void)hipHostFree(c->len_m_stage);
+  if (c->bias_tab) (void)hipFree(c->bias_tab);
+  if (c->len_m_up) (void)hipEventDestroy(c->len_m_up);
   if (c->top_ring_dev) (void)hipFree(c->top_ring_dev);
   if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
   if (c->topb_dev) (void)hipFree(c->topb_dev);
@@ -2226,6 +2376,8 @@ static int set_sampling_impl(dtk_ctx* c, const dtk_sampling* sp, SamplingDev* sp
   else c->slot_trunc[(int)(sp_dst - c->sp_b)] = false;      // dv.qmin = dv.eps = 0: dtk_set_sampling_*_ext follows where they are wanted
   if (const int rc = pen_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), 0.f, 0.f, 0)) return rc;      // dtk_set_penalties[_slot] likewise
   if (const int rc = dry_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), nullptr)) return rc;      // dtk_set_dry[_slot] likewise
+  if (const int rc = len_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), nullptr)) return rc;      // dtk_set_length_control[_slot] and
+  if (const int rc = bias_set(c, is_single ? 0 : 1 + (int)(sp_dst - c->sp_b), nullptr, nullptr, 0)) return rc;      // dtk_set_logit_bias[_slot] likewise
   // which sampler the captured graphs must contain: the multi-block chain serves large vocabularies unless a
   // configuration needs top-k; a change of kind drops the graph (re-captured by the next launch)
   const bool needs_topk = sp->do_sample && sp->top_k > 0 && sp->top_k < c->V;
@@ -2378,6 +2530,62 @@ int64_t dtk_dry_state_bytes(const dtk_ctx* c) {
   const size_t nseq = (size_t)(1 + c->nb), nrec = 1 + DTK_MAX_SLOTS;
   return (int64_t)(nseq * c->dry_stride + 2 * nrec * sizeof(DryDev) + 3 * nseq * c->Tmax * sizeof(int32_t) + 2 * nrec * sizeof(DryLen) +
                    nrec * sizeof(int32_t));
+}
+
+// length control / logit bias of the sequence the last dtk_set_sampling[_slot] configured (include/dtk.h)
+static int single_idle(dtk_ctx* c, const char* who) {
+  if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "%s: %d decode step(s) are unread", who, (int)(c->launched - c->waited));
+  return DTK_OK;
+}
+static int slot_idle(dtk_ctx* c, int slot, const char* who) {
+  for (uint64_t q = c->bwaited; q < c->blaunched; ++q)
+    if (c->bs_host[q % DTK_MAX_INFLIGHT].active[slot]) return fail(c, DTK_ERR_STATE, "%s: slot %d is part of an unread step", who, slot);
+  return DTK_OK;
+}
+
+int dtk_set_length_control(dtk_ctx* c, const dtk_length_ctl* l) {
+  if (!c) return DTK_ERR_ARG;
+  if (const int rc = len_check(c, l, c->V, "dtk_set_length_control")) return rc;
+  if (const int rc = single_idle(c, "dtk_set_length_control")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return len_set(c, 0, l);
+}
+
+int dtk_set_length_control_slot(dtk_ctx* c, int slot, const dtk_length_ctl* l) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_set_length_control_slot: slot %d of %d", slot, c ? c->nb : 0);
+  if (const int rc = len_check(c, l, c->V, "dtk_set_length_control_slot")) return rc;
+  if (const int rc = slot_idle(c, slot, "dtk_set_length_control_slot")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return len_set(c, 1 + slot, l);
+}
+
+int dtk_set_logit_bias(dtk_ctx* c, const int32_t* ids, const float* values, int n) {
+  if (!c) return DTK_ERR_ARG;
+  if (const int rc = bias_check(c, ids, values, n, c->V, "dtk_set_logit_bias")) return rc;
+  if (const int rc = single_idle(c, "dtk_set_logit_bias")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return bias_set(c, 0, ids, values, n);
+}
+
+int dtk_set_logit_bias_slot(dtk_ctx* c, int slot, const int32_t* ids, const float* values, int n) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_set_logit_bias_slot: slot %d of %d", slot, c ? c->nb : 0);
+  if (const int rc = bias_check(c, ids, values, n, c->V, "dtk_set_logit_bias_slot")) return rc;
+  if (const int rc = slot_idle(c, slot, "dtk_set_logit_bias_slot")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return bias_set(c, 1 + slot, ids, values, n);
+}
+
+// Diagnostic: the dense bias table the sequence's next sampler will read (slot -1: the single sequence) to out[0, V): the number of
+// entries != 0, or a negative error; zeros while the feature is off
+int dtk_logit_bias_table(dtk_ctx* c, int slot, float* out, int V) {
+  if (!c || slot < -1 || slot >= c->nb || !out || V != c->V) return fail(c, DTK_ERR_ARG, "dtk_logit_bias_table: bad argument");
+  if (!c->bias_tab) { memset(out, 0, sizeof(float) * (size_t)V); return 0; }
+  if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return fail(c, DTK_ERR_HIP, "dtk_logit_bias_table: the stream failed");
+  if (hipMemcpy(out, c->bias_tab + (size_t)(slot + 1) * c->bias_stride, sizeof(float) * (size_t)V, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(c, DTK_ERR_HIP, "dtk_logit_bias_table: copy failed");
+  int k = 0;
+  for (int i = 0; i < V; ++i) k += out[i] != 0.f;
+  return k;
 }
 
 int dtk_num_slots(const dtk_ctx* c) { return c ? c->nb : 0; }

@@ -289,6 +289,23 @@ struct dtk_ctx {
   bool dry_live[1 + DTK_MAX_SLOTS] = {};    // the sequence's table / history may hold something (it has, or had, a multiplier)
   bool dry_single = false, graph_dry = false;
   bool dry_batch = false, bgraph_dry = false;
+  // length control and logit bias (dtk_set_length_control / dtk_set_logit_bias), indexed like the penalties.  Everything below is allocated
+  // by the first call that sets a value (len_alloc, which also makes the penalties' records exist: the rules ride the PN samplers), so a
+  // context that never uses them allocates and launches nothing.  All of it is static for a sequence: nothing is rebuilt when the host
+  // redefines one (the length comes from DecState::next_pos).  len_single / len_batch and graph_len / bgraph_len as pen_single / graph_pen
+  LenDev* len_dev = nullptr;         // [1 + DTK_MAX_SLOTS]
+  LenDev* len_stage = nullptr;       // pinned [1 + DTK_MAX_SLOTS]
+  float* len_m = nullptr;            // [1 + nb][len_m_stride] the decay tables m[k]
+  float* len_m_stage = nullptr;      // pinned mirror
+  int len_m_stride = 0;              // Tmax + 1
+  hipEvent_t len_m_up = nullptr;     // behind the last upload from len_m_stage: waited for before the mirror is written again
+  double len_factor[1 + DTK_MAX_SLOTS] = {};          // the factor each decay table was built for (0: none yet)
+  float* bias_tab = nullptr;         // [1 + nb][bias_stride] dense bias tables, 0 = no bias; the pairs travel as kernel arguments
+  int bias_stride = 0;
+  LenDev len_val[1 + DTK_MAX_SLOTS] = {};            // the records as set
+  std::vector<int32_t> bias_ids[1 + DTK_MAX_SLOTS];  // the ids each table holds a value for
+  bool len_single = false, graph_len = false;
+  bool len_batch = false, bgraph_len = false;
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;
@@ -334,6 +351,10 @@ DTK_INTERNAL int gelu_flag(const dtk_ctx* c);
 DTK_INTERNAL int pen_check(dtk_ctx* c, float pp, float fp, int start, const char* who);
 DTK_INTERNAL int dry_check(dtk_ctx* c, const dtk_dry* d, int V, const char* who);
 DTK_INTERNAL DryDev dry_record(const dtk_dry* d);
+DTK_INTERNAL int len_check(dtk_ctx* c, const dtk_length_ctl* l, int V, const char* who);
+DTK_INTERNAL LenDev len_record(const dtk_length_ctl* l);
+DTK_INTERNAL void len_table(double factor, float* m, int n);
+DTK_INTERNAL int bias_check(dtk_ctx* c, const int32_t* ids, const float* values, int n, int V, const char* who);
 DTK_INTERNAL int ext_check(dtk_ctx* c, const dtk_sampling_ext* x, const char* who);
 struct ExtDev { int64_t qmin; float eps; };       // SamplingDev's tail
 static_assert(offsetof(SamplingDev, eps) - offsetof(SamplingDev, qmin) == offsetof(ExtDev, eps) &&

@@ -64,6 +64,9 @@ struct Cmd {
   float pen_p = 0.f, pen_f = 0.f;   // the sequence's presence / frequency penalty and penalty_start (dtk_engine_submit_pen), 0 / 0 / 0 for
   int pen_start = 0;                // every other join
   dtk_dry dry{0.f, 1.75f, 2, 0, 0, {}};   // the sequence's DRY (dtk_engine_submit_dry); off, at the defaults, for every other join
+  dtk_length_ctl len{};             // the sequence's length rules and bias pairs (dtk_engine_submit_shape); off for every other join
+  std::vector<int32_t> bias_ids;
+  std::vector<float> bias_val;
   int rc = 0;
   bool done = false;
   std::condition_variable cv;
@@ -79,6 +82,8 @@ using WaitLpFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, flo
 using SamplingExtFn = int (*)(void* dev, int slot, const dtk_sampling_ext* x);
 using PenaltiesFn = int (*)(void* dev, int slot, float presence, float frequency, int start);
 using DryFn = int (*)(void* dev, int slot, const dtk_dry* d);
+using LenFn = int (*)(void* dev, int slot, const dtk_length_ctl* l);
+using BiasFn = int (*)(void* dev, int slot, const int32_t* ids, const float* values, int n);
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
@@ -89,6 +94,8 @@ struct dtk_engine {
   SamplingExtFn sampling_ext = nullptr;     // dtk_engine_set_sampling_ext_op (dtk_engine_create: dtk_set_sampling_slot_ext)
   PenaltiesFn penalties = nullptr;          // dtk_engine_set_penalties_op (dtk_engine_create: dtk_set_penalties_slot)
   DryFn dry = nullptr;                      // dtk_engine_set_dry_op (dtk_engine_create: dtk_set_dry_slot)
+  LenFn length_control = nullptr;           // dtk_engine_set_length_control_op (dtk_engine_create: dtk_set_length_control_slot)
+  BiasFn logit_bias = nullptr;              // dtk_engine_set_logit_bias_op (dtk_engine_create: dtk_set_logit_bias_slot)
   dtk_ctx* own_ctx = nullptr;               // dtk_engine_create: the context, whose "logprobs" option decides which wait collects
   std::mutex mu;
   std::condition_variable cv_run;
@@ -237,6 +244,14 @@ int do_join(dtk_engine* e, const Cmd* c) {
     if (e->dry) {             // likewise the join's own DRY (off without one)
       rc = e->dry(o.dev, s, &c->dry);
       if (rc) return set_error(e, j, rc, "dtk_set_dry_slot");
+    }
+    if (e->length_control) {  // likewise the join's own length rules (off without them)
+      rc = e->length_control(o.dev, s, &c->len);
+      if (rc) return set_error(e, j, rc, "dtk_set_length_control_slot");
+    }
+    if (e->logit_bias) {      // ... and its bias pairs (none without them)
+      rc = e->logit_bias(o.dev, s, c->bias_ids.data(), c->bias_val.data(), (int)c->bias_ids.size());
+      if (rc) return set_error(e, j, rc, "dtk_set_logit_bias_slot");
     }
     return DTK_OK;
   };
@@ -396,8 +411,11 @@ void run(dtk_engine* e) {
 
 // queue a join (text: its text ids, nullptr for an image-only join)
 struct JoinPen { float presence, frequency; int start; };
+struct JoinShape { const dtk_length_ctl* len; const int32_t* ids; const float* val; int n; };
+inline bool len_ctl_on(const dtk_length_ctl* l) { return l && l->n_eos > 0 && (l->min_new_tokens > 0 || l->decay_factor != 0.); }
 int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out,
-           const dtk_sampling_ext* ext = nullptr, const JoinPen* pen = nullptr, const dtk_dry* dry = nullptr) {
+           const dtk_sampling_ext* ext = nullptr, const JoinPen* pen = nullptr, const dtk_dry* dry = nullptr,
+           const JoinShape* shp = nullptr) {
   std::lock_guard<std::mutex> g(e->mu);
   if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
   if (text && !e->prefill_text) {
@@ -416,8 +434,18 @@ int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t
     snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: this engine's device takes no DRY (dtk_engine_set_dry_op)");
     return DTK_ERR_STATE;
   }
+  if (shp && len_ctl_on(shp->len) && !e->length_control) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: this engine's device takes no length control (dtk_engine_set_length_control_op)");
+    return DTK_ERR_STATE;
+  }
+  if (shp && shp->n > 0 && !e->logit_bias) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: this engine's device takes no logit bias (dtk_engine_set_logit_bias_op)");
+    return DTK_ERR_STATE;
+  }
   Cmd* c = new Cmd();
   c->join = j;
+  if (shp && shp->len) c->len = *shp->len;
+  if (shp && shp->n > 0) { c->bias_ids.assign(shp->ids, shp->ids + shp->n); c->bias_val.assign(shp->val, shp->val + shp->n); }
   if (ext) c->ext = *ext;
   if (dry) c->dry = *dry;
   if (pen) { c->pen_p = pen->presence; c->pen_f = pen->frequency; c->pen_start = pen->start; }
@@ -442,6 +470,12 @@ int ctx_penalties(void* d, int s, float pp, float fp, int start) {     // (0 / 0
 }
 int ctx_dry(void* d, int s, const dtk_dry* x) {     // (off: dtk_set_sampling_slot has just left exactly that)
   return x->multiplier == 0.f ? DTK_OK : dtk_set_dry_slot((dtk_ctx*)d, s, x);
+}
+int ctx_length_control(void* d, int s, const dtk_length_ctl* l) {     // (off: dtk_set_sampling_slot has just left exactly that)
+  return len_ctl_on(l) ? dtk_set_length_control_slot((dtk_ctx*)d, s, l) : DTK_OK;
+}
+int ctx_logit_bias(void* d, int s, const int32_t* ids, const float* values, int n) {
+  return n > 0 ? dtk_set_logit_bias_slot((dtk_ctx*)d, s, ids, values, n) : DTK_OK;
 }
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
 int ctx_lcp(void* d, int s, const int64_t* ids, int n, uint64_t key, int* out) { return dtk_slot_lcp((dtk_ctx*)d, s, ids, n, key, out); }
@@ -486,6 +520,8 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
     (*out)->sampling_ext = ctx_sampling_ext;
     (*out)->penalties = ctx_penalties;
     (*out)->dry = ctx_dry;
+    (*out)->length_control = ctx_length_control;
+    (*out)->logit_bias = ctx_logit_bias;
   }
   return dtk_engine_set_prefill_text_op(*out, ctx_prefill_text);
 }
@@ -515,6 +551,20 @@ int dtk_engine_set_dry_op(dtk_engine* e, DryFn set_dry_slot) {
   if (!e) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->dry = set_dry_slot;
+  return DTK_OK;
+}
+
+int dtk_engine_set_length_control_op(dtk_engine* e, LenFn set_length_control_slot) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->length_control = set_length_control_slot;
+  return DTK_OK;
+}
+
+int dtk_engine_set_logit_bias_op(dtk_engine* e, BiasFn set_logit_bias_slot) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->logit_bias = set_logit_bias_slot;
   return DTK_OK;
 }
 
@@ -651,6 +701,44 @@ int dtk_engine_submit_dry(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x,
   if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_dry: no text"); return DTK_ERR_ARG; }
   const JoinPen pn{presence, frequency, start};
   return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn, d);
+}
+
+// dtk_engine_submit_dry + the sequence's length rules and bias pairs; the values are checked here as far as they can be without the
+// device (the vocabulary: an id outside it fails the join)
+int dtk_engine_submit_shape(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, float presence, float frequency, int start,
+                            const dtk_dry* d, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                            const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  if (!e || !j || !ticket_out) return DTK_ERR_ARG;
+  if (x && (!(x->min_p >= 0.f && x->min_p <= 1.f) || !(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f))) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: min_p must be in [0, 1] and epsilon_cutoff in [0, 1)");
+    return DTK_ERR_ARG;
+  }
+  if (!(presence >= -2.f && presence <= 2.f) || !(frequency >= -2.f && frequency <= 2.f) || start < 0) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: presence_penalty and frequency_penalty must be in [-2, 2], penalty_start >= 0");
+    return DTK_ERR_ARG;
+  }
+  if (d && (!(d->multiplier >= 0.f && d->multiplier <= 100.f) || !(d->base >= 1.f && d->base <= 8.f) || d->allowed_length < 1 ||
+            d->allowed_length > DTK_DRY_MAX_MATCH || d->start < 0 || d->n_breakers < 0 || d->n_breakers > DTK_DRY_MAX_BREAKERS)) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: dry_multiplier in [0, 100], dry_base in [1, 8], dry_allowed_length in [1, 64], "
+             "dry_start >= 0, at most 16 breakers");
+    return DTK_ERR_ARG;
+  }
+  if (l && (l->min_new_tokens < 0 || l->decay_start < 0 || l->start < 0 || l->n_eos < 0 || l->n_eos > 8 ||
+            (l->decay_factor != 0. && (!(l->decay_factor > 0. && l->decay_factor <= 1.7976931348623157e308) || l->decay_start < l->min_new_tokens)))) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: min_new_tokens, decay_start, length_start >= 0, decay_factor finite and > 0 "
+             "(0 = none) with decay_start >= min_new_tokens, at most 8 EOS ids");
+    return DTK_ERR_ARG;
+  }
+  bool bias_ok = n_bias >= 0 && n_bias <= DTK_BIAS_MAX && (n_bias == 0 || (bias_ids && bias_values));
+  for (int i = 0; bias_ok && i < n_bias; ++i) bias_ok = bias_values[i] >= -100.f && bias_values[i] <= 100.f;
+  if (!bias_ok) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: at most %d bias pairs, values finite and in [-100, 100]", DTK_BIAS_MAX);
+    return DTK_ERR_ARG;
+  }
+  if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: no text"); return DTK_ERR_ARG; }
+  const JoinPen pn{presence, frequency, start};
+  const JoinShape sh{l, bias_ids, bias_values, n_bias};
+  return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn, d, &sh);
 }
 
 int dtk_engine_await(dtk_engine* e, uint64_t ticket) {

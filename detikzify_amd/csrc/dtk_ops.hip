@@ -1090,8 +1090,11 @@ struct OpDryState {
 }  // namespace
 }  // extern "C++"
 
+// dtk_op_sample_shape's: the sequence's length, its length rules and its bias pairs
+struct OpShape { int cur; const dtk_length_ctl* l; const int32_t* ids; const float* val; int n; };
 static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
-                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr, const OpDry* dry = nullptr) {
+                          const dtk_sampling_ext* ext = nullptr, const OpPen* pen = nullptr, const OpDry* dry = nullptr,
+                          const OpShape* shp = nullptr) {
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   OpRun r(c, "dtk_op_sample");
@@ -1110,11 +1113,30 @@ static int op_sample_impl(dtk_ctx* c, const float* logits, int V, int step, int6
   }
   std::optional<OpDryState> dst;      // the product scan over the call's own history, then the PN samplers with its table
   if (dry && pen) dst.emplace(r, *dry, dry->n, V, nullptr);
+  // a record, a decay table (as far as this length reads it) and a dense bias table of the call's own, filled by the product scatter kernel
+  LenDev lrec = len_record(shp ? shp->l : nullptr);
+  std::vector<float> mtab(1, 0.f);
+  float* dbias = nullptr;
+  const int bias_stride = (V + 7) & ~7;
+  if (shp && pen) {
+    for (int i = 0; i < shp->n; ++i) lrec.n_bias += shp->val[i] != 0.f;
+    if (lrec.decay_begin != DTK_LEN_NO_DECAY) {
+      const long k = (long)shp->cur - lrec.start - lrec.decay_begin;
+      mtab.resize((size_t)(k > 0 ? k + 1 : 1));
+      len_table(shp->l->decay_factor, mtab.data(), (int)mtab.size());
+    }
+    sa.len = r.in<LenDev>(&lrec, 1); sa.len_m = r.in<float>(mtab.data(), mtab.size()); sa.len_m_stride = (int)mtab.size();
+    sa.bias = dbias = (float*)r.take(sizeof(float) * (size_t)bias_stride); sa.bias_stride = bias_stride; sa.len_cur = shp->cur;
+  }
   if (probs_out) r.res.push_back({c->probs_dev, probs_out, (size_t)V * 4, "probs", false});      // (the context's own buffer, not in the scratch)
   if (const int rc = r.upload(s)) return rc;
   if (pen) {
     HIPCHK(c, hipMemsetAsync(dcnt, 0, sizeof(uint16_t) * (size_t)pen_stride, s));
     launch_count_scatter(dids, pen->n, dcnt, V, s);
+  }
+  if (dbias) {
+    HIPCHK(c, hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)bias_stride, s));
+    launch_bias_scatter(shp->ids, shp->val, shp->n, dbias, V, s);
   }
   ExtDev xd{};
   if (ext) {      // the context's configuration with the call's own (min_p, epsilon_cutoff)
@@ -1204,6 +1226,29 @@ int dtk_op_sample_dry(dtk_ctx* c, const float* logits, int V, int step, int64_t*
   const OpPen pn{presence, frequency, counted_ids, n_counted};
   const OpDry od{dry, history, n_history};
   return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn, &od);
+}
+
+// dtk_op_sample_dry at sequence length cur with a dtk_length_ctl and bias pairs: k_bias_scatter, k_dry_scan, then the PN sampler
+// instantiations with the count table, the match table, the decay table and the bias table, whatever the values are
+int dtk_op_sample_shape(dtk_ctx* c, const float* logits, int V, int step, int64_t* token_out, float* probs_out, float* lp_out,
+                        const dtk_sampling_ext* ext, float presence, float frequency, const int64_t* counted_ids, int n_counted,
+                        const int64_t* history, int n_history, const dtk_dry* dry, int cur, const dtk_length_ctl* l,
+                        const int32_t* bias_ids, const float* bias_values, int n_bias) {
+  if (!c || !logits || !token_out || V < 1 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || (probs_out && V > c->V) || n_counted < 0 ||
+      n_counted > 65535 || (n_counted > 0 && !counted_ids) || cur < 0 || cur > (1 << 20))
+    return fail(c, DTK_ERR_ARG, "dtk_op_sample_shape: bad argument");
+  if (ext) if (const int rc = ext_check(c, ext, "dtk_op_sample_shape")) return rc;
+  if (const int rc = pen_check(c, presence, frequency, 0, "dtk_op_sample_shape")) return rc;
+  if (const int rc = op_dry_check(c, dry, V, history, n_history, "dtk_op_sample_shape")) return rc;
+  if (const int rc = len_check(c, l, V, "dtk_op_sample_shape")) return rc;
+  if (const int rc = bias_check(c, bias_ids, bias_values, n_bias, V, "dtk_op_sample_shape")) return rc;
+  for (int i = 0; i < n_counted; ++i)
+    if (counted_ids[i] < 0 || counted_ids[i] >= V) return fail(c, DTK_ERR_ARG, "dtk_op_sample_shape: counted id %lld outside [0, %d)", (long long)counted_ids[i], V);
+  if (lp_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_op_sample_shape: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  const OpPen pn{presence, frequency, counted_ids, n_counted};
+  const OpDry od{dry, history, n_history};
+  const OpShape sh{cur, l, bias_ids, bias_values, n_bias};
+  return op_sample_impl(c, logits, V, step, token_out, probs_out, lp_out, ext, &pn, &od, &sh);
 }
 
 // k_dry_scan alone over a given history; with history2, a second scan of that history on the state the first one left (table and

@@ -108,7 +108,18 @@ struct SampleArgs {
   const DryDev* dry = nullptr;
   const uint8_t* dry_m = nullptr;      // [dry_stride] per sequence: the match length M of every id (k_dry_scan), 0 = not penalised
   int dry_stride = 0;                  // bytes between two sequences' tables (a multiple of 16)
+  // dtk_set_length_control / dtk_set_logit_bias: some sequence of this launch has a length rule or a bias.  Rides the PN instantiations as
+  // DRY does (pen is then set too); null = the PN samplers read nothing of it.  Slot 0's in batched mode
+  const LenDev* len = nullptr;
+  const float* len_m = nullptr;        // [len_m_stride] per sequence: the decay table m[k]
+  int len_m_stride = 0;
+  const float* bias = nullptr;         // [bias_stride] per sequence: the dense bias table, 0 = no bias
+  int bias_stride = 0;                 // elements between two sequences' tables (a multiple of 8: every table is 16-byte aligned)
+  int len_cur = -1;                    // >= 0: the sequence's length in place of DecState::next_pos (tests)
 };
+// dtk_set_logit_bias: one block writes val[i] (or, val null, 0) to tab[ids[i]] for i < n <= DTK_BIAS_MAX; ids outside [0, V) are skipped.
+// ids and val are HOST arrays: the pairs go to the kernel as its arguments
+void launch_bias_scatter(const int32_t* ids, const float* val, int n, float* tab, int V, hipStream_t s);
 // dtk_set_dry: what k_dry_scan (in front of the sampler) and the trailing kernel (behind it) work on; sequence 0's pointers
 struct DryScanArgs {
   const DryDev* dry = nullptr;

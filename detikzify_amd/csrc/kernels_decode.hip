@@ -1350,10 +1350,30 @@ __device__ __forceinline__ void dry_f32x4(f32x4& v, uint32_t mw, const float* pe
 #pragma unroll
   for (int e = 0; e < 4; ++e) v[e] = dry_apply(v[e], (mw >> (8 * e)) & 0xffu, pen);
 }
-__device__ __forceinline__ float pen_dry1(const SampleArgs& a, int i, bool pn, float pp, float fp, bool dr, const float* dpen) {
+// Length control and logit bias (SampleArgs::len, dtk_set_length_control / dtk_set_logit_bias) ride PN: the bias is added to the raw logit
+// in front of pen_apply (one float beside every logit, read only where the sequence has a bias), the EOS rules (at most 8 ids, and only at
+// a length where one applies) come behind dry_apply; sh is bound once per block from the sequence's record and its length
+__device__ __forceinline__ void bias_f32x4(f32x4& v, const f32x4 b) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = bias_apply(v[e], b[e]);
+}
+__device__ __forceinline__ void eos_f32x4(f32x4& v, int i, const ShapeRt& sh) {
+  for (int j = 0; j < sh.ne; ++j) {
+    const int o = sh.eos[j] - i;
+    if (o < 0 || o >= 4) continue;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) if (e == o) v[e] = eos_apply(v[e], i + e, sh);
+  }
+}
+__device__ __forceinline__ ShapeRt shape_of(const SampleArgs& a) {
+  return shape_bind(a.len, a.len_m, a.bias, a.len_cur >= 0 ? a.len_cur : a.st->next_pos);
+}
+__device__ __forceinline__ float pen_dry1(const SampleArgs& a, int i, bool pn, float pp, float fp, bool dr, const float* dpen, const ShapeRt& sh) {
   float z = a.logits[i];
+  if (sh.bias) z = bias_apply(z, sh.bias[i]);
   if (pn) z = pen_apply(z, a.pen_cnt[i], pp, fp);
   if (dr) z = dry_apply(z, a.dry_m[i], dpen);
+  if (sh.ne) z = eos_apply(z, i, sh);
   return z;
 }
 template <bool LP, bool TR, bool PN>
@@ -1370,6 +1390,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
     if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
+    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
     a.ring = 1;        // the ring index was applied above
     a.step_override = -1;
   }
@@ -1407,6 +1428,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
   if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
   (void)dpen; (void)dr;
+  ShapeRt sh;                                         // PN with SampleArgs::len: the sequence's bias table and the EOS rule of this length (block-uniform)
+  if constexpr (PN) if (a.len) sh = shape_of(a);
+  (void)sh;
 
   // ---- pass 1: masked (scaled) max and first argmax.  16-byte loads, four per thread in flight
   // (the greedy path is one memory round trip + the block reduction)
@@ -1442,6 +1466,15 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         }
       }
       (void)dw;
+      f32x4 bw[4];       // PN, bias: the four biases likewise
+      if constexpr (PN) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int i4 = base + u * SAMPLE_THREADS;
+          bw[u] = (sh.bias && i4 < V4) ? reinterpret_cast<const f32x4*>(sh.bias)[i4] : (f32x4){0.f, 0.f, 0.f, 0.f};
+        }
+      }
+      (void)bw;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i4 = base + u * SAMPLE_THREADS;
@@ -1451,8 +1484,11 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
           const int i = i4 * 4 + e;
           if constexpr (LP) lse_push(lm, ls, v[u][e]);
           float z;
-          if constexpr (PN) z = dry_apply(pen_apply(v[u][e], pen_cnt4(cw[u], e), pn_p, pn_f), (dw[u] >> (8 * e)) & 0xffu, dpen) * invT;
-          else z = v[u][e] * invT;
+          if constexpr (PN) {
+            z = dry_apply(pen_apply(bias_apply(v[u][e], bw[u][e]), pen_cnt4(cw[u], e), pn_p, pn_f), (dw[u] >> (8 * e)) & 0xffu, dpen);
+            if (sh.ne) z = eos_apply(z, i, sh);
+            z *= invT;
+          } else z = v[u][e] * invT;
           if (is_banned(sp, i, first)) z = -INFINITY;
           if (z > best || (z == best && i < besti)) { best = z; besti = i; }
         }
@@ -1462,7 +1498,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     for (int i = tid; i < V; i += SAMPLE_THREADS) {
       if constexpr (LP) lse_push(lm, ls, a.logits[i]);
       float z;
-      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen) * invT;
+      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen, sh) * invT;
       else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1495,7 +1531,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (sampling) {
     // fixed-point mass q_i = floor(exp(z_i - zmax) * 2^31)  (fits 32 bits; exact integer sums)
     auto mass = [&](int i, float& z) -> unsigned long long {
-      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen) * invT;
+      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen, sh) * invT;
       else z = a.logits[i] * invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       const float e = expf(z - zmax);
@@ -1705,6 +1741,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
     if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
+    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
     a.ring = 1;
     a.step_override = -1;
   }
@@ -1740,6 +1777,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
   if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
   (void)dpen; (void)dr;
+  ShapeRt sh;                                         // PN with SampleArgs::len: the sequence's bias table and the EOS rule of this length (block-uniform)
+  if constexpr (PN) if (a.len) sh = shape_of(a);
+  (void)sh;
   const int i0 = tid * SF_PER;
 
   // ---- the one pass over the logits
@@ -1755,8 +1795,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
         const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
         if (m4 > lm) { ls *= expf(lm - m4); lm = m4; }
         ls += (expf(v[0] - lm) + expf(v[1] - lm)) + (expf(v[2] - lm) + expf(v[3] - lm));
+        if constexpr (PN) if (sh.bias) bias_f32x4(v, reinterpret_cast<const f32x4*>(sh.bias + i0)[k]);
         if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
         if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
+        if constexpr (PN) if (sh.ne) eos_f32x4(v, i0 + 4 * k, sh);
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
       }
@@ -1765,8 +1807,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       for (int k = 0; k < SF_PER; ++k) {
         float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
         lse_push(lm, ls, v);
+        if constexpr (PN) if (sh.bias && i0 + k < V) v = bias_apply(v, sh.bias[i0 + k]);
         if constexpr (PN) if (pn && i0 + k < V) v = pen_apply(v, a.pen_cnt[i0 + k], pn_p, pn_f);
         if constexpr (PN) if (dr && i0 + k < V) v = dry_apply(v, a.dry_m[i0 + k], dpen);
+        if constexpr (PN) if (sh.ne && i0 + k < V) v = eos_apply(v, i0 + k, sh);
         z[k] = v * invT;
       }
     }
@@ -1775,15 +1819,17 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 #pragma unroll
     for (int k = 0; k < SF_PER / 4; ++k) {
       f32x4 v = l4[k];
+      if constexpr (PN) if (sh.bias) bias_f32x4(v, reinterpret_cast<const f32x4*>(sh.bias + i0)[k]);
       if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
       if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
+      if constexpr (PN) if (sh.ne) eos_f32x4(v, i0 + 4 * k, sh);
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
     }
   } else if constexpr (PN) {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k)
-      z[k] = (i0 + k < V) ? pen_dry1(a, i0 + k, pn, pn_p, pn_f, dr, dpen) * invT : -INFINITY;
+      z[k] = (i0 + k < V) ? pen_dry1(a, i0 + k, pn, pn_p, pn_f, dr, dpen, sh) * invT : -INFINITY;
   } else {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) z[k] = (i0 + k < V) ? a.logits[i0 + k] * invT : -INFINITY;
@@ -2111,6 +2157,23 @@ __global__ __launch_bounds__(256) void k_count_scatter(const int32_t* ids, int n
     const int t = ids[i];
     if (t >= 0 && t < V) atomicAdd(w + (t >> 1), (t & 1) ? 0x10000u : 1u);
   }
+}
+// dtk_set_logit_bias: the (id, value) pairs of one sequence into its dense table (val null on the host: the listed ids back to 0, which is
+// how a table is cleared).  The pairs travel as kernel arguments (2 KiB), so nothing is staged; plain vector stores, one thread per pair
+// (the host refuses a repeated id, so no two threads write one entry)
+struct BiasPairs { int32_t ids[DTK_BIAS_MAX]; float val[DTK_BIAS_MAX]; };
+__global__ __launch_bounds__(DTK_BIAS_MAX) void k_bias_scatter(BiasPairs p, int n, float* tab, int V) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  const int t = p.ids[i];
+  if (t >= 0 && t < V) tab[t] = p.val[i];
+}
+void launch_bias_scatter(const int32_t* ids, const float* val, int n, float* tab, int V, hipStream_t s) {
+  if (n <= 0) return;
+  if (n > DTK_BIAS_MAX) n = DTK_BIAS_MAX;
+  BiasPairs p;
+  for (int i = 0; i < DTK_BIAS_MAX; ++i) { p.ids[i] = i < n ? ids[i] : -1; p.val[i] = (i < n && val) ? val[i] : 0.f; }
+  hipLaunchKernelGGL(k_bias_scatter, dim3(1), dim3(DTK_BIAS_MAX), 0, s, p, n, tab, V);
 }
 void launch_count_scatter(const int32_t* ids, int n, uint16_t* cnt, int V, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_count_scatter, dim3(1), dim3(256), 0, s, ids, n, cnt, V);

@@ -23,6 +23,8 @@
 // suppression lists.  The block of k_smb_draw that writes the token may run before other blocks of its slot have loaded their slice (the
 // hazard draw_snap exists for), so the token is NOT counted here: it goes to pen_tok, and k_count_token, a kernel behind the chain,
 // counts it.  PN = false are the kernels as they were before the penalties existed.
+// Length control and logit bias (SampleArgs::len) ride PN in mb_load as well: the bias in front of pen_apply, the EOS rules behind
+// dry_apply.  The rules need the sequence's length, which k_smb_draw's owner block advances: k_smb_max leaves it in SampleMB::cur_snap.
 // Supports greedy, temperature, top-p and the suppression lists; top-k > 0 stays on the single-block kernel (the API
 // re-captures the graph when a sampling configuration needs the other kind).
 #include "kernels.h"
@@ -59,8 +61,17 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
     a.mb += slot;
     if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
     if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
+    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
   }
   return true;
+}
+
+// the sequence's length for the kernels behind k_smb_max: its snapshot, NOT DecState (k_smb_draw's owner block advances next_pos while
+// other blocks of the slot may not have loaded their slice yet)
+template <bool PN>
+__device__ __forceinline__ int mb_cur(const SampleArgs& a) {
+  if constexpr (PN) if (a.len) return a.mb->cur_snap;
+  return 0;
 }
 
 // this thread's 8 consecutive logits: scaled, suppressed ids -> -inf, keys; out-of-range -> -inf.  raw (k_smb_max<true> only): the
@@ -68,7 +79,7 @@ __device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
 // PN: z' = pen_apply(z, count) in place of every z (a sequence whose two values are 0 reads no count: block-uniform); raw stays raw
 template <bool PN = false>
 __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* sp, bool first, float invT, int base, MbElems& e,
-                                        float* raw = nullptr) {
+                                        float* raw = nullptr, int cur = 0) {
   const int V = a.V;
   float pn_p = 0.f, pn_f = 0.f; bool pn = false;
   if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
@@ -76,6 +87,11 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
   const float* dpen = nullptr; bool dr = false;       // DRY (SampleArgs::dry) rides PN: pen[M] off z' where the id's match length M != 0
   if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
   (void)dpen; (void)dr;
+  // length control / logit bias (SampleArgs::len) ride PN: the bias in front of pen_apply, the EOS rules behind dry_apply.  `cur` is the
+  // sequence's length as k_smb_max found it (DecState::next_pos; the later kernels of the chain read its snapshot, as they read draw_snap)
+  ShapeRt sh;
+  if constexpr (PN) if (a.len) sh = shape_bind(a.len, a.len_m, a.bias, cur);
+  (void)sh;
   if (base + MB_PER <= V && ((reinterpret_cast<uintptr_t>(a.logits + base) & 15) == 0)) {
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.logits + base);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.logits + base + 4);
@@ -84,11 +100,20 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
       if (pn) { const u32x4 c4 = *reinterpret_cast<const u32x4*>(a.pen_cnt + base); cw[0] = c4[0]; cw[1] = c4[1]; cw[2] = c4[2]; cw[3] = c4[3]; }
       uint2 dw = make_uint2(0u, 0u);          // the 8 match lengths: one 8-byte load
       if (dr) dw = *reinterpret_cast<const uint2*>(a.dry_m + base);
+      f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};      // the 8 biases: two 16-byte loads
+      if (sh.bias) { b0 = *reinterpret_cast<const f32x4*>(sh.bias + base); b1 = *reinterpret_cast<const f32x4*>(sh.bias + base + 4); }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        e.z[i] = dry_apply(pen_apply(v0[i], (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.x >> (8 * i)) & 0xffu, dpen) * invT;
-        e.z[4 + i] = dry_apply(pen_apply(v1[i], (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.y >> (8 * i)) & 0xffu, dpen) * invT;
+        e.z[i] = dry_apply(pen_apply(bias_apply(v0[i], b0[i]), (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.x >> (8 * i)) & 0xffu, dpen);
+        e.z[4 + i] = dry_apply(pen_apply(bias_apply(v1[i], b1[i]), (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.y >> (8 * i)) & 0xffu, dpen);
       }
+      for (int j = 0; j < sh.ne; ++j) {
+        const int o = sh.eos[j] - base;
+#pragma unroll
+        for (int i = 0; i < MB_PER; ++i) if (o == i) e.z[i] = eos_apply(e.z[i], base + i, sh);
+      }
+#pragma unroll
+      for (int i = 0; i < MB_PER; ++i) e.z[i] *= invT;
     } else {
 #pragma unroll
       for (int i = 0; i < 4; ++i) { e.z[i] = v0[i] * invT; e.z[4 + i] = v1[i] * invT; }
@@ -104,8 +129,10 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
         float z = -INFINITY;
         if (base + i < V) {
           z = a.logits[base + i];
+          if (sh.bias) z = bias_apply(z, sh.bias[base + i]);
           if (pn) z = pen_apply(z, a.pen_cnt[base + i], pn_p, pn_f);
           if (dr) z = dry_apply(z, a.dry_m[base + i], dpen);
+          if (sh.ne) z = eos_apply(z, base + i, sh);
           z *= invT;
         }
         e.z[i] = z;
@@ -173,12 +200,14 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
   __syncthreads();
   const uint32_t draw = (a.step_override >= 0) ? (uint32_t)a.step_override : a.st->draw;
   const float invT = s_sp.do_sample ? 1.f / s_sp.temperature : 1.f;
+  int cur = 0;       // PN with SampleArgs::len: the sequence's length, for the EOS rules
+  if constexpr (PN) if (a.len) cur = a.len_cur >= 0 ? a.len_cur : a.st->next_pos;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
   float lm = -INFINITY, ls = 0.f;
   if constexpr (LP) {
     float raw[MB_PER];
-    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e, raw);
+    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e, raw, cur);
 #pragma unroll
     for (int i = 0; i < MB_PER; ++i) lm = fmaxf(lm, raw[i]);
     if (lm != -INFINITY) {
@@ -188,7 +217,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
     lse_wave(lm, ls);
     if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; }
   } else {
-    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e);
+    mb_load<PN>(a, &s_sp, draw == 0, invT, base, e, nullptr, cur);
   }
   float best = -INFINITY; int besti = 0x7fffffff;
 #pragma unroll
@@ -212,6 +241,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
       a.mb->lmax[blk] = lm; a.mb->lsum[blk] = ls;
     }
     if (blk == 0) { a.mb->draw_snap = draw; a.mb->forced_snap = a.advance ? a.st->force_plus1 : 0; }
+    if constexpr (PN) if (a.len && blk == 0) a.mb->cur_snap = cur;
   }
   // the histograms of this step start from zero (P1 is a later kernel)
   if (blk == 0) {
@@ -278,7 +308,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk)
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e, nullptr, mb_cur<PN>(a));
   mb_mass(e, cm.zmax);
   constexpr int shift = LV * 8;
   // run-length aggregation over the thread's 8 consecutive elements (neighbours mostly share the digit), then atomics
@@ -334,7 +364,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e, nullptr, mb_cur<PN>(a));
   mb_mass(e, cm.zmax);
   unsigned long long mine = 0;
 #pragma unroll
@@ -377,7 +407,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk
   const float invT = 1.f / cm.sp.temperature;
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
-  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
+  mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e, nullptr, mb_cur<PN>(a));
   mb_mass(e, cm.zmax);
   unsigned long long mine = 0;
 #pragma unroll
@@ -430,7 +460,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
       const float invT = 1.f / cm.sp.temperature;
       MbElems e;
       const int base = blk * MB_SLICE + tid * MB_PER;
-      mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e);
+      mb_load<PN>(a, &cm.sp, draw == 0, invT, base, e, nullptr, mb_cur<PN>(a));
       mb_mass(e, cm.zmax);
       uint32_t qfl = 0; bool fb = false;
       if constexpr (TR) { qfl = a.mb->qfl; fb = a.mb->fb != 0; }

@@ -180,10 +180,12 @@ class BatchEngine:
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
-        from ..model.modeling import DRY_KEYS, DUMMY_IMAGE_KEY, adapter_text, check_dry, check_penalties, check_truncation, text_image_key, text_key
+        from ..model.modeling import (DRY_KEYS, DUMMY_IMAGE_KEY, SHAPE_KEYS, adapter_text, check_dry, check_penalties, check_truncation,
+                                      shape_of_sampling, text_image_key, text_key)
         check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
         pen = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
         dry = check_dry(*(sampling.get(k) for k in DRY_KEYS))
+        shape = shape_of_sampling(sampling, int(ids.numel()))      # (min_new_tokens, decay, length_start, eos ids, bias pairs)
         tids = adapter_text(text_ids) if text_ids is not None else None
         tkey = text_key(tids) if tids is not None else 0
         ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
@@ -258,7 +260,7 @@ class BatchEngine:
                 # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
                 # without them leaves the slot at 0 / 0
                 plain = {k: v for k, v in sampling.items()
-                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start") + DRY_KEYS}
+                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start") + DRY_KEYS + SHAPE_KEYS}
                 self.model.set_sampling(slot=slot, **plain)
                 ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
                 set_ext = getattr(self.model, "set_sampling_ext", None)
@@ -283,6 +285,20 @@ class BatchEngine:
                 elif dry[0]:
                     from .._lib import DtkError
                     raise DtkError("this device takes no DRY penalty")
+                # the length rules and the bias table likewise (length_start: the prompt length unless the sequence says otherwise);
+                # both are static for the sequence, whatever the fork / prefill / resume below does
+                set_len = getattr(self.model, "set_length_control", None)
+                if set_len is not None:
+                    set_len(shape[0], shape[1], shape[2], shape[3], slot=slot)
+                elif shape[3]:
+                    from .._lib import DtkError
+                    raise DtkError("this device takes no length control")
+                set_bias = getattr(self.model, "set_logit_bias", None)
+                if set_bias is not None:
+                    set_bias(shape[4], slot=slot)
+                elif shape[4]:
+                    from .._lib import DtkError
+                    raise DtkError("this device takes no logit bias")
                 if resume:
                     self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)

@@ -149,6 +149,14 @@ class _ScriptedOps:
             model.set_dry(float(d.multiplier), float(d.base), int(d.allowed_length), int(d.start),
                           tuple(int(d.breakers[i]) for i in range(int(d.n_breakers))), slot=slot)
 
+        def length_control(dev, slot, lp):
+            l = lp.contents
+            model.set_length_control(int(l.min_new_tokens), (int(l.decay_start), float(l.decay_factor)) if l.decay_factor else None, int(l.start),
+                                     tuple(int(l.eos_ids[i]) for i in range(int(l.n_eos))), slot=slot)
+
+        def logit_bias(dev, slot, ids, values, n):
+            model.set_logit_bias(tuple((int(ids[i]), float(values[i])) for i in range(int(n))), slot=slot)
+
         def fork(dev, a, b, n):
             model.kv_fork(a, b, n)
 
@@ -174,6 +182,8 @@ class _ScriptedOps:
         self.sampling_ext = O.SAMPLING_EXT(guard(sampling_ext)) if hasattr(model, "set_sampling_ext") else None
         self.penalties = O.PENALTIES(guard(penalties)) if hasattr(model, "set_penalties") else None
         self.dry = O.DRY(guard(dry)) if hasattr(model, "set_dry") else None
+        self.length_control = O.LENGTH_CTL(guard(length_control)) if hasattr(model, "set_length_control") else None
+        self.logit_bias = O.LOGIT_BIAS(guard(logit_bias)) if hasattr(model, "set_logit_bias") else None
 
 
 def _has_adapter(model) -> bool:
@@ -229,6 +239,10 @@ class NativeBatchEngine:
                 rc = self.lib.dtk_engine_set_penalties_op(self._h, self._scripted.penalties)
             if rc == 0 and self._scripted.dry is not None and hasattr(self.lib, "dtk_engine_set_dry_op"):
                 rc = self.lib.dtk_engine_set_dry_op(self._h, self._scripted.dry)
+            if rc == 0 and self._scripted.length_control is not None and hasattr(self.lib, "dtk_engine_set_length_control_op"):
+                rc = self.lib.dtk_engine_set_length_control_op(self._h, self._scripted.length_control)
+            if rc == 0 and self._scripted.logit_bias is not None and hasattr(self.lib, "dtk_engine_set_logit_bias_op"):
+                rc = self.lib.dtk_engine_set_logit_bias_op(self._h, self._scripted.logit_bias)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
         if not pipeline:
@@ -417,7 +431,7 @@ class NativeBatchEngine:
             arr = getattr(s, field)
             for i, v in enumerate(vals):
                 arr[i] = v
-        from ..model.modeling import DRY_KEYS, check_dry, check_penalties, check_truncation, dry_struct
+        from ..model.modeling import DRY_KEYS, check_dry, check_penalties, check_truncation, dry_struct, length_struct, shape_of_sampling
         ext = _lib.DtkSamplingExt(*check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff")))
         has_ext = bool(ext.min_p or ext.epsilon_cutoff)
         pen_p, pen_f, pen_s = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
@@ -428,6 +442,14 @@ class NativeBatchEngine:
         dry = dry_struct(dry_m, dry_b, dry_a, (n_ids if dry_s is None else dry_s) if has_dry else 0, dry_brk)      # dry_start as penalty_start
         if has_dry and not hasattr(self.lib, "dtk_engine_submit_dry"):
             raise _lib.DtkError("this device takes no DRY penalty")
+        # the length rules and the bias pairs (length_start as penalty_start)
+        len_m, len_d, len_s, len_eos, bias_pairs = shape_of_sampling(sampling, n_ids)
+        has_shape = bool(len_eos or bias_pairs)
+        lctl = length_struct(len_m, len_d, len_s, len_eos)
+        bias_ids = (C.c_int32 * max(len(bias_pairs), 1))(*[t for t, _ in bias_pairs])
+        bias_val = (C.c_float * max(len(bias_pairs), 1))(*[v for _, v in bias_pairs])
+        if has_shape and not hasattr(self.lib, "dtk_engine_submit_shape"):
+            raise _lib.DtkError("this device takes no length control / logit bias")
         stops = [int(t) for t in stop_ids if int(t) >= 0][:8]
         j.n_stop = len(stops)
         for i, t in enumerate(stops):
@@ -481,7 +503,12 @@ class NativeBatchEngine:
             self.free.remove(slot)
             if owner is not None:
                 self.last_slot[owner] = slot
-            if has_dry:       # the sequence's DRY (and its penalties, min_p / epsilon_cutoff) go with its join (text or not)
+            if has_shape:     # the sequence's length rules and bias pairs (and everything below) go with its join (text or not)
+                tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
+                rc = self.lib.dtk_engine_submit_shape(self._h, C.byref(j), C.byref(ext), C.c_float(pen_p), C.c_float(pen_f), int(pen_s), C.byref(dry),
+                                                      C.byref(lctl), bias_ids, bias_val, len(bias_pairs),
+                                                      tp, int(tids.numel()) if tids is not None else 0, C.c_uint64(tkey), C.byref(ticket))
+            elif has_dry:     # the sequence's DRY (and its penalties, min_p / epsilon_cutoff) go with its join (text or not)
                 tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
                 rc = self.lib.dtk_engine_submit_dry(self._h, C.byref(j), C.byref(ext), C.c_float(pen_p), C.c_float(pen_f), int(pen_s), C.byref(dry),
                                                     tp, int(tids.numel()) if tids is not None else 0, C.c_uint64(tkey), C.byref(ticket))

@@ -143,14 +143,21 @@ class DetikzifyGenerator:
                  strict: bool = False, document_class: Type[TikzDocument] = TikzDocument, processed=None, rng=None,
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None, dry_allowed_length: Optional[int] = None,
-                 dry_sequence_breakers=None, **gen_kwargs):
+                 dry_sequence_breakers=None, min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None,
+                 logit_bias=None, sequence_bias=None, **gen_kwargs):
         """presence_penalty / frequency_penalty (model.generate's; None / 0 = off): counted from the end of the image prompt on, so a
-        rollout that continues a node of the tree penalises the whole program text so far, however its slot got there"""
+        rollout that continues a node of the tree penalises the whole program text so far, however its slot got there.
+        min_new_tokens / exponential_decay_length_penalty (model.generate's) likewise count the program's tokens from the end of the
+        image prompt (length_start); logit_bias / sequence_bias hold for every rollout"""
         if presence_penalty or frequency_penalty:
             gen_kwargs = {**gen_kwargs, "presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty}
         if dry_multiplier:      # DRY (model.generate's) likewise: its history starts at the end of the image prompt
             gen_kwargs = {**gen_kwargs, "dry_multiplier": dry_multiplier, "dry_base": dry_base, "dry_allowed_length": dry_allowed_length,
                           "dry_sequence_breakers": dry_sequence_breakers}
+        if min_new_tokens or exponential_decay_length_penalty is not None:      # length control (model.generate's): the program's length
+            gen_kwargs = {**gen_kwargs, "min_new_tokens": min_new_tokens, "exponential_decay_length_penalty": exponential_decay_length_penalty}
+        if logit_bias or sequence_bias:
+            gen_kwargs = {**gen_kwargs, "logit_bias": logit_bias, "sequence_bias": sequence_bias}
         self.model, self.processor = model, processor
         self.image, self.text, self.metric = image, text, metric
         self.compile_timeout, self.mcts_timeout = compile_timeout, mcts_timeout
@@ -235,6 +242,8 @@ class DetikzifyGenerator:
             options["penalty_start"] = int(self.montecarlo.root_node.token_ids.numel())       # the program text so far counts, the prompt does not
         if options.get("dry_multiplier") and options.get("dry_start") is None:
             options["dry_start"] = int(self.montecarlo.root_node.token_ids.numel())           # likewise: a rollout sees the whole program text so far
+        if (options.get("min_new_tokens") or options.get("exponential_decay_length_penalty") is not None) and options.get("length_start") is None:
+            options["length_start"] = int(self.montecarlo.root_node.token_ids.numel())        # likewise: the whole program's length counts
         budget = options.get("max_length", self.model.generation_config.to_dict().get("max_length"))
         n = input_ids.numel()
         finished = n > 0 and input_ids[-1] == unwrap(self.processor).tokenizer.eos_token_id

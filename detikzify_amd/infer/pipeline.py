@@ -57,7 +57,8 @@ class DetikzifyPipeline:
         """One sampled TikZ program for the image.  return_logprobs=True attaches `.token_logprobs` and `.token_sample_logprobs` to
         the document: per generated token (EOS included) the model's log-probability of it — comparable with score() — and the log
         of the probability the sampler (temperature, top-k, top-p, min_p, epsilon_cutoff, presence_penalty, frequency_penalty,
-        dry_multiplier / dry_base / dry_allowed_length / dry_sequence_breakers: all gen_kwargs, here and in simulate) chose it with.  top_logprobs=k (1 .. 8, with return_logprobs=True)
+        dry_multiplier / dry_base / dry_allowed_length / dry_sequence_breakers, min_new_tokens, exponential_decay_length_penalty,
+        logit_bias / sequence_bias: all gen_kwargs, here and in simulate) chose it with.  top_logprobs=k (1 .. 8, with return_logprobs=True)
         also attaches `.token_top_ids` / `.token_top_logprobs`: per generated token the k most likely tokens at its position."""
         from ..model.modeling import check_top_logprobs
         check_top_logprobs(top_logprobs, return_logprobs)

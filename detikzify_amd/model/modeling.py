@@ -128,11 +128,11 @@ _NEUTRAL_GENERATE_KWARGS: Dict[str, tuple] = {
     "num_beams": (None, 1), "num_beam_groups": (None, 1), "num_return_sequences": (None, 1),
     "repetition_penalty": (None, 1.0), "encoder_repetition_penalty": (None, 1.0), "length_penalty": (None, 1.0),
     "diversity_penalty": (None, 0.0), "no_repeat_ngram_size": (None, 0), "encoder_no_repeat_ngram_size": (None, 0),
-    "min_length": (None, 0), "min_new_tokens": (None, 0), "typical_p": (None, 1.0),
+    "min_length": (None, 0), "typical_p": (None, 1.0),
     "eta_cutoff": (None, 0.0), "penalty_alpha": (None, 0.0), "early_stopping": (None, False),
     "renormalize_logits": (None, False), "remove_invalid_values": (None, False), "guidance_scale": (None, 1.0),
-    "forced_bos_token_id": (None,), "forced_eos_token_id": (None,), "exponential_decay_length_penalty": (None,),
-    "sequence_bias": (None,), "logits_processor": (None, [], ()), "prefix_allowed_tokens_fn": (None,),
+    "forced_bos_token_id": (None,), "forced_eos_token_id": (None,),
+    "logits_processor": (None, [], ()), "prefix_allowed_tokens_fn": (None,),
     "assistant_model": (None,), "negative_prompt_ids": (None,), "negative_prompt_attention_mask": (None,),
     "generation_config": (None,), "stop_strings": (None,), "max_time": (None,), "cache_implementation": (None,),
     "past_key_values": (None,), "inputs_embeds": (None,), "tokenizer": "any",
@@ -230,6 +230,101 @@ def dry_struct(multiplier: float, base: float, allowed_length: int, start: int, 
     for i, t in enumerate(breakers):
         d.breakers[i] = int(t)
     return d
+
+
+LENGTH_KEYS = ("min_new_tokens", "exponential_decay_length_penalty", "length_start")
+SHAPE_KEYS = LENGTH_KEYS + ("logit_bias", "length_eos_ids")      # what a sequence's sampling dict carries of §3.1j
+
+
+def check_length_control(min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None, length_start: Optional[int] = None):
+    """the length arguments of generate / sample -> (min_new_tokens, decay, length_start): min_new_tokens 0 = off (None), decay None = off
+    or (decay_start, factor) with factor finite and > 0, length_start None = the caller's default (generate: the prompt length).  A decay
+    that starts below min_new_tokens is refused (HF would form -inf + inf there).  Out of range: ValueError before anything runs"""
+    m = 0 if min_new_tokens is None else min_new_tokens
+    if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+        raise ValueError(f"`min_new_tokens` has to be a positive integer, but is {min_new_tokens}")
+    decay = None
+    if exponential_decay_length_penalty is not None:
+        d = exponential_decay_length_penalty
+        if not isinstance(d, (tuple, list)) or len(d) != 2:
+            raise ValueError(f"`exponential_decay_length_penalty` has to be a (start_index, decay_factor) pair, but is {d!r}")
+        s, f = d
+        if isinstance(s, bool) or not isinstance(s, int) or s < 0:
+            raise ValueError(f"`exponential_decay_length_penalty`: start_index has to be an integer >= 0, but is {s!r}")
+        if isinstance(f, bool) or not isinstance(f, (int, float)) or not (0.0 < f < math.inf):      # (NaN fails the comparison)
+            raise ValueError(f"`exponential_decay_length_penalty`: decay_factor has to be a finite float > 0, but is {f!r}")
+        if s < m:
+            raise ValueError(f"`exponential_decay_length_penalty` starts at {s}, below `min_new_tokens` = {m}: the EOS logit would be "
+                             f"-inf and decayed at once")
+        decay = (int(s), float(f))      # (the double itself goes to the device: HF raises it, not its fp32 value, to the power k)
+    if length_start is not None:
+        if isinstance(length_start, bool) or not isinstance(length_start, int) or length_start < 0:
+            raise ValueError(f"`length_start` has to be an integer >= 0, but is {length_start}")
+    return int(m), decay, length_start
+
+
+def check_logit_bias(logit_bias=None, sequence_bias=None, vocab: Optional[int] = None) -> Tuple[Tuple[int, float], ...]:
+    """`logit_bias` ({id: value}, the OpenAI / vLLM argument) and HF's `sequence_bias` (dict with tuple keys, or list of [ids, value]) ->
+    ((id, value), ...) in ascending id order without the entries whose value is 0.  Values finite in [-100, 100], at most DTK_BIAS_MAX ids
+    in [0, vocab), every sequence of `sequence_bias` one token long (longer: NotImplementedError), no id in both (ValueError)"""
+    out: Dict[int, float] = {}
+
+    def put(name, t, v):
+        if isinstance(t, str) and t.strip().lstrip("+").isdigit():      # (JSON object keys are strings)
+            t = int(t)
+        if isinstance(t, bool) or not isinstance(t, int) or t < 0 or (vocab is not None and t >= vocab):
+            raise ValueError(f"`{name}` has to hold token ids in [0, vocabulary), but holds {t!r}")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (-100.0 <= v <= 100.0):      # (NaN fails the comparison)
+            raise ValueError(f"`{name}` has to hold finite biases in the [-100, 100] interval, but holds {v!r}")
+        if t in out:
+            raise ValueError(f"token id {t} is biased twice (`logit_bias` and `sequence_bias` are merged into one table)")
+        out[t] = float(C.c_float(float(v)).value)
+
+    if logit_bias is not None:
+        if not isinstance(logit_bias, dict):
+            raise ValueError(f"`logit_bias` has to be a dictionary {{token id: bias}}, but is {logit_bias!r}")
+        for t, v in logit_bias.items():
+            put("logit_bias", t, v)
+    if sequence_bias is not None:
+        if not isinstance(sequence_bias, (dict, list)) or len(sequence_bias) == 0:
+            raise ValueError(f"`sequence_bias` has to be a non-empty dictionary, or non-empty list of lists but is {sequence_bias}.")
+        items = list(sequence_bias.items()) if isinstance(sequence_bias, dict) else [tuple(e) if isinstance(e, (list, tuple)) else (e,) for e in sequence_bias]
+        for e in items:
+            if len(e) != 2 or not isinstance(e[0], (tuple, list)) or len(e[0]) == 0:
+                raise ValueError(f"Each key in `sequence_bias` has to be a non-empty tuple of positive integers, but is {sequence_bias}.")
+            if len(e[0]) > 1:
+                raise NotImplementedError(f"sequence_bias: the multi-token sequence {tuple(e[0])} is not supported (single tokens only)")
+            put("sequence_bias", e[0][0], e[1])
+    pairs = tuple((t, out[t]) for t in sorted(out) if out[t] != 0.0)
+    if len(pairs) > _lib.DTK_BIAS_MAX:
+        raise ValueError(f"at most {_lib.DTK_BIAS_MAX} biased token ids, but {len(pairs)} are given")
+    return pairs
+
+
+def length_eos_ids(eos_ids, vocab: int) -> Tuple[int, ...]:
+    """the EOS ids the length rules act on: the valid ones (an id outside the vocabulary, as -1, names none), ascending"""
+    ids = tuple(sorted({int(t) for t in (eos_ids or ()) if 0 <= int(t) < vocab}))
+    if len(ids) > _lib.DTK_LEN_MAX_EOS:
+        raise ValueError(f"length control acts on at most {_lib.DTK_LEN_MAX_EOS} EOS ids, but {len(ids)} are given")
+    return ids
+
+
+def length_struct(min_new_tokens: int = 0, decay=None, start: int = 0, eos_ids=()) -> "_lib.DtkLengthCtl":
+    s = _lib.DtkLengthCtl(int(min_new_tokens), int(decay[0]) if decay else 0, float(decay[1]) if decay else 0.0, int(start), len(eos_ids))
+    for i, t in enumerate(eos_ids):
+        s.eos_ids[i] = int(t)
+    return s
+
+
+def shape_of_sampling(sampling: Dict[str, Any], n_ids: int, vocab: Optional[int] = None):
+    """a batch engine's view of a sequence's sampling dict -> (min_new_tokens, decay, length_start, eos ids, bias pairs), checked;
+    length_start defaults to the sequence's prompt length, as penalty_start does"""
+    m, decay, start = check_length_control(*(sampling.get(k) for k in LENGTH_KEYS))
+    pairs = sampling.get("logit_bias") or ()
+    pairs = check_logit_bias(dict(pairs) if not isinstance(pairs, dict) else pairs, None, vocab)
+    eos = tuple(sampling.get("length_eos_ids") or ())
+    on = bool(eos) and bool(m or decay)
+    return (m if on else 0), (decay if on else None), ((n_ids if start is None else start) if on else 0), (eos if on else ()), pairs
 
 
 def _is_neutral(value: Any, neutral: Any) -> bool:
@@ -913,6 +1008,50 @@ class DetikzifyForCausalLM:
             self._check(n, "dtk_dry_history")
         return torch.tensor(list(out[:n]), dtype=torch.int64)
 
+    def set_length_control(self, min_new_tokens: int = 0, decay=None, start: int = 0, eos_ids=(), slot: Optional[int] = None):
+        """the length rules of the sequence the last set_sampling configured (dtk_set_length_control[_slot]): with n = the sequence's
+        length - `start`, the logits of `eos_ids` are -inf while n < min_new_tokens and grow by |z| * (factor^(n - decay_start) - 1)
+        once n > decay_start, decay = (decay_start, factor).  set_sampling itself resets them to off"""
+        m, decay, st = check_length_control(min_new_tokens, decay, int(start))
+        eos = length_eos_ids(eos_ids, int(self.config.vocab))
+        on = bool(eos) and bool(m or decay)
+        fn = getattr(self.lib, "dtk_set_length_control" if slot is None else "dtk_set_length_control_slot", None)
+        if fn is None:          # a device without the two calls has nothing to reset
+            if on:
+                raise _lib.DtkError("this device takes no length control")
+            return
+        s = length_struct(m, decay, st, eos)
+        if slot is None:
+            self._check(fn(self._ctx, C.byref(s)), "dtk_set_length_control")
+        else:
+            self._check(fn(self._ctx, int(slot), C.byref(s)), "dtk_set_length_control_slot")
+
+    def set_logit_bias(self, logit_bias=None, slot: Optional[int] = None):
+        """the bias table of the sequence the last set_sampling configured (dtk_set_logit_bias[_slot]): {id: value} or (id, value) pairs,
+        at most 256, added to the raw logits in front of everything else.  None / empty clears; set_sampling itself does"""
+        pairs = check_logit_bias(dict(logit_bias or ()), None, int(self.config.vocab))
+        fn = getattr(self.lib, "dtk_set_logit_bias" if slot is None else "dtk_set_logit_bias_slot", None)
+        if fn is None:          # a device without the two calls has nothing to reset
+            if pairs:
+                raise _lib.DtkError("this device takes no logit bias")
+            return
+        n = len(pairs)
+        ids = (C.c_int32 * max(n, 1))(*[t for t, _ in pairs])
+        vals = (C.c_float * max(n, 1))(*[v for _, v in pairs])
+        if slot is None:
+            self._check(fn(self._ctx, ids, vals, n), "dtk_set_logit_bias")
+        else:
+            self._check(fn(self._ctx, int(slot), ids, vals, n), "dtk_set_logit_bias_slot")
+
+    def logit_bias_table(self, slot: Optional[int] = None) -> torch.Tensor:
+        """diagnostic: the dense bias table the sequence's next sampler will read (float32 per vocabulary entry; zeros while off)"""
+        V = int(self.config.vocab)
+        out = np.zeros(V, dtype=np.float32)
+        n = int(self.lib.dtk_logit_bias_table(self._ctx, -1 if slot is None else int(slot), out.ctypes.data_as(C.POINTER(C.c_float)), V))
+        if n < 0:
+            self._check(n, "dtk_logit_bias_table")
+        return torch.from_numpy(out)
+
     def token_counts(self, slot: Optional[int] = None) -> torch.Tensor:
         """diagnostic: the count table the sequence's next step will read (uint16 per vocabulary entry, as int32)"""
         V = int(self.config.vocab)
@@ -1104,7 +1243,8 @@ class DetikzifyForCausalLM:
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  penalty_start: Optional[int] = None, dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None,
                  dry_allowed_length: Optional[int] = None, dry_start: Optional[int] = None, dry_sequence_breakers=None,
-                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None, logit_bias=None, sequence_bias=None,
+                 length_start: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1128,6 +1268,12 @@ class DetikzifyForCausalLM:
         position dry_start on (default: the prompt length) has dry_multiplier * dry_base^(M - dry_allowed_length) taken off its logit,
         behind the presence / frequency pair and in front of everything else; dry_multiplier 0 / None = off; breakers
         are token ids across which no repetition is matched.  The reported log-probabilities stay the model's own.
+
+        min_new_tokens / exponential_decay_length_penalty=(start, factor): HF's MinNewTokensLength processor (the EOS logits are -inf
+        until the sequence holds min_new_tokens tokens behind position length_start) and its ExponentialDecayLengthPenalty (from
+        start + 1 tokens on the EOS logits grow by |z| * (factor^k - 1)); length_start defaults to the prompt length.  logit_bias={id:
+        value} (OpenAI / vLLM) and HF's sequence_bias with single-token sequences: one table of at most 256 biases in [-100, 100] added
+        to the raw logits in front of the penalties.  0 / None = off.  The reported log-probabilities stay the model's own.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1167,11 +1313,19 @@ class DetikzifyForCausalLM:
             getattr(gc, "dry_start", None) if dry_start is None else dry_start,
             getattr(gc, "dry_sequence_breakers", None) if dry_sequence_breakers is None else dry_sequence_breakers,
             int(self.config.vocab))
+        min_new_tokens, decay, length_start = check_length_control(
+            getattr(gc, "min_new_tokens", None) if min_new_tokens is None else min_new_tokens,
+            getattr(gc, "exponential_decay_length_penalty", None) if exponential_decay_length_penalty is None else exponential_decay_length_penalty,
+            getattr(gc, "length_start", None) if length_start is None else length_start)
+        bias_pairs = check_logit_bias(getattr(gc, "logit_bias", None) if logit_bias is None else logit_bias,
+                                      getattr(gc, "sequence_bias", None) if sequence_bias is None else sequence_bias, int(self.config.vocab))
         do_sample = gc.do_sample if do_sample is None else do_sample
         temperature = gc.temperature if temperature is None else temperature
         top_p = gc.top_p if top_p is None else top_p
         top_k = gc.top_k if top_k is None else top_k
         T = ids.shape[1]
+        if length_start is None:
+            length_start = T
         if penalty_start is None:
             penalty_start = T
         if dry_start is None:
@@ -1185,6 +1339,13 @@ class DetikzifyForCausalLM:
         max_length = min(int(max_length), self.config.max_positions)
         eos = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_set = set(_flat_ids([eos]))
+        # the length rules act on the valid EOS ids (none, as with eos_token_id=-1: nothing to do)
+        len_eos = length_eos_ids(eos_set, int(self.config.vocab)) if (min_new_tokens or decay) else ()
+        shape = {}
+        if len_eos:
+            shape.update(min_new_tokens=min_new_tokens, exponential_decay_length_penalty=decay, length_start=length_start, length_eos_ids=len_eos)
+        if bias_pairs:
+            shape.update(logit_bias=bias_pairs)
         begin_suppress_tokens = _flat_ids(begin_suppress_tokens)
         suppress_tokens = _flat_ids(suppress_tokens)
         bad = []
@@ -1274,7 +1435,7 @@ class DetikzifyForCausalLM:
                     begin_suppress_ids=begin_suppress_tokens or (), always_suppress_ids=suppress_tokens or (),
                     **({"min_p": min_p, "epsilon_cutoff": epsilon_cutoff} if (min_p or epsilon_cutoff) else {}),
                     **({"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "penalty_start": penalty_start}
-                       if (presence_penalty or frequency_penalty) else {}), **dry),
+                       if (presence_penalty or frequency_penalty) else {}), **dry, **shape),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
                     **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
@@ -1297,6 +1458,10 @@ class DetikzifyForCausalLM:
                     self.set_penalties(presence_penalty, frequency_penalty, penalty_start)
                 if dry_multiplier:       # (likewise; the prefill below builds the history)
                     self.set_dry(dry_multiplier, dry_base, dry_allowed_length, dry_start, dry_sequence_breakers)
+                if len_eos:              # (likewise; static for the sequence: the length comes from the device's own position)
+                    self.set_length_control(min_new_tokens, decay, length_start, len_eos)
+                if bias_pairs:
+                    self.set_logit_bias(bias_pairs)
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
                     if topk:

@@ -880,6 +880,58 @@ int  dtk_engine_submit_dry(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x
                            const dtk_dry* d /* or NULL */, const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out);
 int  dtk_engine_set_dry_op(dtk_engine* e, int (*set_dry_slot)(void* dev, int slot, const dtk_dry* d));
 
+/* Length control and logit bias (additive, ABI 7): min_new_tokens, an exponential decay of the EOS logit with the length, and a bias
+ * per token id.  Transforms of the raw logits around the penalties, per sequence, all off by default.  cur = the number of tokens the
+ * sequence holds when a token is sampled (DecState::next_pos), n = cur - start, E = the sequence's eos_ids.  For a raw logit z[i]:
+ *   1. bias     b[i] != 0: z1 = z[i] + b[i], one fp32 addition; b[i] == 0: the untouched bits of z[i].  At most DTK_BIAS_MAX ids in
+ *               [0, V), no id twice, values finite in [-100, 100].
+ *   2. dtk_set_penalties, then dtk_set_dry, on z1, unchanged.
+ *   3. decay    i in E and n > decay_start: with k = n - decay_start, z3 = fl(z2 + fl(|z2| * m[k])), two fp32 roundings, never an fma;
+ *               m[k] = min((float)(pow(decay_factor, k) - 1.0), 0x1p100f), a host-built table of max_positions + 1 floats (the
+ *               device only looks it up).  decay_factor 0 = no decay; otherwise finite and > 0.
+ *   4. minimum  i in E and n < min_new_tokens: -inf.
+ *   5. the suppression lists, the temperature, top-k, top-p, min-p, epsilon and the draw; greedy takes the arg-max (lowest id on ties).
+ * logprob, the top-k records and their logsumexp stay over the RAW logits.  decay_start >= min_new_tokens is required with a decay (the
+ * two rules never meet: -inf + inf would be NaN); m saturates at 2^100 where pow would reach inf.  All of it is static for a sequence:
+ * nothing is rebuilt when the host redefines one (prefill, fork, resume, prefix reuse), n follows the token list.  A sequence without
+ * values reads no table and draws what it draws alone.  State (allocated with the first value that is set): one record per sequence,
+ * a float [max_positions + 1] decay table per sequence with the first decay, a dense float [V] bias table per sequence with the first bias.
+ *   dtk_set_length_control[_slot]  called AFTER dtk_set_sampling[_slot], which reset the rules to off.  DTK_ERR_ARG outside the ranges,
+ *                             on NaN, on an EOS id outside [0, V); DTK_ERR_STATE while steps of the sequence are unread.
+ *   dtk_set_logit_bias[_slot] likewise; n = 0 clears.  The table is filled by k_bias_scatter and cleared by re-zeroing the listed ids.
+ *   dtk_logit_bias_table      diagnostic: the sequence's dense table (slot -1: the single sequence) to out[0, V); zeros while the
+ *                             feature is off.  Returns the number of entries != 0, or a negative error code.
+ *   dtk_op_sample_shape       dtk_op_sample_dry at sequence length cur (l->start is honoured: n = cur - l->start) with a dtk_length_ctl
+ *                             and bias pairs: the PN sampler instantiations with every table, whatever the values are.
+ *   dtk_engine_submit_shape   dtk_engine_submit_dry whose sequence also carries the two new records (NULL / 0: off); dtk_engine_create
+ *                             wires the slot setters itself, an engine of dtk_engine_create_ops gets them through
+ *                             dtk_engine_set_length_control_op / dtk_engine_set_logit_bias_op, and without one a join with values
+ *                             fails in submit with DTK_ERR_STATE.  With the op every join calls it. */
+#define DTK_BIAS_MAX 256
+typedef struct dtk_length_ctl {
+  int32_t min_new_tokens;
+  int32_t decay_start;
+  double  decay_factor;   /* a double: HF raises the Python float itself to the power k */
+  int32_t start;
+  int32_t n_eos;
+  int32_t eos_ids[8];
+} dtk_length_ctl;
+int  dtk_set_length_control(dtk_ctx* ctx, const dtk_length_ctl* l);
+int  dtk_set_length_control_slot(dtk_ctx* ctx, int slot, const dtk_length_ctl* l);
+int  dtk_set_logit_bias(dtk_ctx* ctx, const int32_t* ids, const float* values, int n);
+int  dtk_set_logit_bias_slot(dtk_ctx* ctx, int slot, const int32_t* ids, const float* values, int n);
+int  dtk_logit_bias_table(dtk_ctx* ctx, int slot, float* out, int V);
+int  dtk_op_sample_shape(dtk_ctx* ctx, const float* logits, int V, int step, int64_t* token_out, float* filtered_probs_out,
+                         float* lp_out /* [2] or NULL */, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency,
+                         const int64_t* counted_ids, int n_counted, const int64_t* history, int n_history, const dtk_dry* d,
+                         int cur, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias);
+int  dtk_engine_submit_shape(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency, int start,
+                             const dtk_dry* d /* or NULL */, const dtk_length_ctl* l /* or NULL */, const int32_t* bias_ids,
+                             const float* bias_values, int n_bias, const int64_t* text_ids, int n_text, uint64_t text_key,
+                             uint64_t* ticket_out);
+int  dtk_engine_set_length_control_op(dtk_engine* e, int (*set_length_control_slot)(void* dev, int slot, const dtk_length_ctl* l));
+int  dtk_engine_set_logit_bias_op(dtk_engine* e, int (*set_logit_bias_slot)(void* dev, int slot, const int32_t* ids, const float* values, int n));
+
 #ifdef __cplusplus
 }
 #endif
