@@ -321,6 +321,11 @@ SYMBOLS = {
                                           C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dtk_engine_set_length_control_op": (C.c_int, [_P, DtkEngineOps.LENGTH_CTL]),
     "dtk_engine_set_logit_bias_op": (C.c_int, [_P, DtkEngineOps.LOGIT_BIAS]),
+    # classifier-free guidance: pairs of batch slots
+    "dtk_set_guidance": (C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
+    "dtk_get_guidance": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "dtk_op_cfg_mix": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_float)]),
+    "dtk_bench_cfg": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -603,6 +603,24 @@ static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
   launch_top_logits(t, c->stream);
 }
 
+// dtk_set_guidance: the batched step of a context with guided pairs mixes each pair's two pending logits rows into the conditional
+// one in front of everything that reads it (guidance_launch), and hands the chosen token to the unconditional slot behind the sampler
+// (follow_launch).  A context without a pair: both return at once, the step launches what it launched before
+static void guidance_launch(dtk_ctx* c, const SampleArgs& sa) {
+  if (!c->cfg_n) return;
+  CfgArgs g;
+  g.logits = const_cast<float*>(sa.logits); g.V = sa.V; g.stride = sa.logits_stride; g.pairs = c->cfg_dev; g.n_pairs = c->cfg_n; g.bs = sa.bs;
+  g.part = c->cfg_part; g.lse = c->cfg_lse;
+  launch_cfg_mix(g, c->stream);
+}
+static void follow_launch(dtk_ctx* c, const SampleArgs& sa) {
+  if (!c->cfg_n) return;
+  CfgFollowArgs f;
+  f.pairs = c->cfg_dev; f.n_pairs = c->cfg_n; f.bs = sa.bs; f.st = sa.st; f.x = sa.x; f.d = sa.d; f.tok_ring = sa.tok_ring; f.ring = sa.ring;
+  f.lp_ring = sa.lp_ring; f.lse_ring = sa.lse_ring; f.top_ring = (c->logprobs && c->top_logprobs) ? c->topb_dev : nullptr;
+  launch_cfg_follow(f, c->stream);
+}
+
 static inline bool w13_on(const dtk_ctx* c) { return c->wfmt == 0 && c->w13 != 0; }   // the single-sequence step streams 13-bit planes (ensure_w13)
 
 void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
@@ -682,8 +700,10 @@ void batch_step_launches_mx(dtk_ctx* c) {
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  guidance_launch(c, sa);            // (nothing without a guided pair)
   top_logits_launch(c, sa);
   sampler_launch(c, sa, c->mb_batch, true);
+  follow_launch(c, sa);              // (likewise)
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   for (int l = 0; l < c->L; ++l) {
@@ -731,8 +751,10 @@ void batch_step_launches(dtk_ctx* c) {
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  guidance_launch(c, sa);            // (nothing without a guided pair)
   top_logits_launch(c, sa);
   sampler_launch(c, sa, c->mb_batch, true);
+  follow_launch(c, sa);              // (likewise)
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   bool kparts = false;
@@ -806,8 +828,10 @@ void batch_step_launches_mv(dtk_ctx* c) {
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  guidance_launch(c, sa);            // (nothing without a guided pair)
   top_logits_launch(c, sa);
   sampler_launch(c, sa, c->mb_batch, true);
+  follow_launch(c, sa);              // (likewise)
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   GemvMvArgs g{};
@@ -1681,6 +1705,9 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
   if (c->topb_dev) (void)hipFree(c->topb_dev);
   if (c->lseb_dev) (void)hipFree(c->lseb_dev);
+  if (c->cfg_dev) (void)hipFree(c->cfg_dev);
+  if (c->cfg_part) (void)hipFree(c->cfg_part);
+  if (c->cfg_lse) (void)hipFree(c->cfg_lse);
   if (c->top_ring_host) (void)hipHostFree(c->top_ring_host);
   if (c->lse_ring_host) (void)hipHostFree(c->lse_ring_host);
   if (c->topb_host) (void)hipHostFree(c->topb_host);
@@ -2588,6 +2615,78 @@ int dtk_logit_bias_table(dtk_ctx* c, int slot, float* out, int V) {
   return k;
 }
 
+// ---- classifier-free guidance: pairs of decoding slots --------------------------------------------------------------------------
+static int cfg_find(const dtk_ctx* c, int slot) {      // the pair `slot` belongs to, or -1
+  for (int p = 0; p < c->cfg_n; ++p)
+    if (c->cfg_pairs[p].cond == slot || c->cfg_pairs[p].uncond == slot) return p;
+  return -1;
+}
+int dtk_set_guidance(dtk_ctx* c, int cond_slot, int uncond_slot, float scale) {
+  if (!c) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: null context");
+  if (c->nb <= 0) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: the context was created without batch slots");
+  const int lim = max_decode_slots(c);
+  if (cond_slot < 0 || cond_slot >= lim) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: slot %d cannot decode: slots 0..%d of this %d-slot context do", cond_slot, lim - 1, c->nb);
+  if (!std::isfinite(scale) || scale < 0.f || scale > 100.f) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: guidance scale %g is not a finite value in [0, 100]", (double)scale);
+  const bool dissolve = uncond_slot < 0 || scale == 1.f;
+  if (!dissolve) {
+    if (uncond_slot >= lim) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: slot %d cannot decode: slots 0..%d of this %d-slot context do", uncond_slot, lim - 1, c->nb);
+    if (uncond_slot == cond_slot) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: a pair needs two distinct slots (got %d twice)", cond_slot);
+  }
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_set_guidance: a batch step is in flight");
+  const int pc = cfg_find(c, cond_slot);
+  int n = c->cfg_n;
+  CfgPair next[DTK_MAX_BATCH / 2];
+  memcpy(next, c->cfg_pairs, sizeof next);
+  if (dissolve) {
+    if (pc < 0 || next[pc].cond != cond_slot) return DTK_OK;      // heads no pair: nothing to dissolve
+    for (int p = pc; p + 1 < n; ++p) next[p] = next[p + 1];
+    --n;
+  } else {
+    const int pu = cfg_find(c, uncond_slot);
+    const bool same = pc >= 0 && pc == pu && next[pc].cond == cond_slot && next[pc].uncond == uncond_slot;   // the pair again: a new scale
+    if (!same && pc >= 0) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: slot %d is already in the pair (%d, %d)", cond_slot, next[pc].cond, next[pc].uncond);
+    if (!same && pu >= 0) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: slot %d is already in the pair (%d, %d)", uncond_slot, next[pu].cond, next[pu].uncond);
+    if (same) next[pc].scale = scale;
+    else {
+      if (n >= DTK_MAX_BATCH / 2) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: at most %d pairs", DTK_MAX_BATCH / 2);
+      next[n++] = CfgPair{cond_slot, uncond_slot, scale, 0};
+    }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n) {      // every buffer on its own: a call that failed part-way is completed by the next one
+    const size_t np = DTK_MAX_BATCH / 2;
+    if (!c->cfg_dev) HIPCHK(c, hipMalloc(&c->cfg_dev, sizeof(CfgPair) * np));
+    if (!c->cfg_part) HIPCHK(c, hipMalloc(&c->cfg_part, sizeof(float2) * np * 2 * DTK_CFG_MAX_SLICES));
+    if (!c->cfg_lse) { HIPCHK(c, hipMalloc(&c->cfg_lse, sizeof(float2) * np)); HIPCHK(c, hipMemset(c->cfg_lse, 0, sizeof(float2) * np)); }
+  }
+  if (c->cfg_dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (no step is in flight; a direct-launch step of before may still read the table)
+    HIPCHK(c, hipMemcpy(c->cfg_dev, next, sizeof next, hipMemcpyHostToDevice));
+  }
+  memcpy(c->cfg_pairs, next, sizeof next);
+  c->cfg_n = n;
+  drop_batch_graphs(c);      // the captured steps hold the pair count (the grid) and whether the kernels run at all
+  return DTK_OK;
+}
+
+// diagnostic: the pair `slot` is in.  partner -1 = none (is_cond 0, scale 1, lse NaN); lse_out[2] = (Lc, Lu) of the pair's last step
+int dtk_get_guidance(dtk_ctx* c, int slot, int* partner_out, int* is_cond_out, float* scale_out, float* lse_out) {
+  if (!c || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_get_guidance: bad argument");
+  const int p = cfg_find(c, slot);
+  if (partner_out) *partner_out = p < 0 ? -1 : (c->cfg_pairs[p].cond == slot ? c->cfg_pairs[p].uncond : c->cfg_pairs[p].cond);
+  if (is_cond_out) *is_cond_out = p >= 0 && c->cfg_pairs[p].cond == slot;
+  if (scale_out) *scale_out = p < 0 ? 1.f : c->cfg_pairs[p].scale;
+  if (lse_out) {
+    lse_out[0] = lse_out[1] = NAN;
+    if (p >= 0) {
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipMemcpy(lse_out, c->cfg_lse + p, sizeof(float2), hipMemcpyDeviceToHost));
+    }
+  }
+  return DTK_OK;
+}
+
 int dtk_num_slots(const dtk_ctx* c) { return c ? c->nb : 0; }
 int dtk_max_positions(const dtk_ctx* c) { return c ? c->Tmax : 0; }
 int dtk_max_decode_slots(const dtk_ctx* c) { return (c && c->nb > 0) ? max_decode_slots(c) : 0; }
@@ -2636,6 +2735,12 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
     ++n_active;
   }
   if (!n_active) return fail(c, DTK_ERR_ARG, "no active slot");
+  for (int p = 0; p < c->cfg_n; ++p) {      // a guided pair decodes together or not at all
+    const CfgPair& gp = c->cfg_pairs[p];
+    if ((active[gp.cond] != 0) != (active[gp.uncond] != 0))
+      return fail(c, DTK_ERR_ARG, "dtk_decode_batch_launch: guided pair (%d, %d): slot %d is active without slot %d (dtk_set_guidance pairs them; both or neither take part in a step)",
+                  gp.cond, gp.uncond, active[gp.cond] ? gp.cond : gp.uncond, active[gp.cond] ? gp.uncond : gp.cond);
+  }
   HIPCHK(c, hipSetDevice(c->device));
   ensure_tiled_weights(c);
   BatchState* hb = c->bs_host + (c->blaunched % DTK_MAX_INFLIGHT);
@@ -3112,6 +3217,31 @@ int dtk_bench_gemv(dtk_ctx* c, int role, int variant, int reps, float* avg_us) {
 
 // Runtime options (tests / tuning): "attn_full_max" = contexts below this use the one-block-per-head
 // decode attention (0 = always split-K); "attn_combine" = 0 consumer | 1 in-kernel | 2 own kernel.
+// tools/bench_cfg.py: what the guidance launches of a step cost on this context's own pairs, rows and step state (HIP events around `reps`
+// back-to-back launches): avg_us[0] = k_cfg_lse + k_cfg_mix, avg_us[1] = k_cfg_follow.  The pending rows of the conditional slots are
+// mixed `reps` times over: prefill the pairs again before decoding on
+int dtk_bench_cfg(dtk_ctx* c, int reps, float* avg_us) {
+  if (!c || !avg_us || reps < 1 || reps > 64) return fail(c, DTK_ERR_ARG, "dtk_bench_cfg: bad argument (1 <= reps <= 64)");
+  if (!c->cfg_n) return fail(c, DTK_ERR_STATE, "dtk_bench_cfg: the context has no guided pair (dtk_set_guidance)");
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_bench_cfg: a batch step is in flight");
+  HIPCHK(c, hipSetDevice(c->device));
+  SampleArgs sa;
+  sa.logits = c->logits_b; sa.V = c->V; sa.logits_stride = c->V; sa.bs = c->bs_dev; sa.st = c->st_b; sa.x = c->xb; sa.d = c->d;
+  sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
+  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr; sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  for (int which = 0; which < 2; ++which) {
+    for (int i = 0; i < 3; ++i) { if (which) follow_launch(c, sa); else guidance_launch(c, sa); }      // warm-up
+    HIPCHK(c, hipEventRecord(c->probe_a, c->stream));
+    for (int i = 0; i < reps; ++i) { if (which) follow_launch(c, sa); else guidance_launch(c, sa); }
+    HIPCHK(c, hipEventRecord(c->probe_b, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->probe_b));
+    float ms = 0.f;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->probe_a, c->probe_b));
+    avg_us[which] = ms * 1000.f / (float)reps;
+  }
+  return DTK_OK;
+}
+
 int dtk_set_option(dtk_ctx* c, const char* name, int value) {
   if (!c || !name) return DTK_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->device));

@@ -306,6 +306,15 @@ struct dtk_ctx {
   std::vector<int32_t> bias_ids[1 + DTK_MAX_SLOTS];  // the ids each table holds a value for
   bool len_single = false, graph_len = false;
   bool len_batch = false, bgraph_len = false;
+  // classifier-free guidance (dtk_set_guidance): disjoint pairs of decoding slots.  cfg_n == 0: guidance_launch / follow_launch return
+  // at once and the step launches what it launched before the feature existed.  The device table and the scratch are allocated by the
+  // first call that forms a pair (hipMalloc of their own), so a context that never uses guidance allocates nothing.  Static for a
+  // sequence, as length control: only dtk_set_guidance changes the table, and every change drops the captured batch steps
+  CfgPair cfg_pairs[DTK_MAX_BATCH / 2] = {};   // the pairs as set, [0, cfg_n)
+  int cfg_n = 0;
+  CfgPair* cfg_dev = nullptr;        // [DTK_MAX_BATCH / 2]
+  float2* cfg_part = nullptr;        // [DTK_MAX_BATCH / 2][2][DTK_CFG_MAX_SLICES]
+  float2* cfg_lse = nullptr;         // [DTK_MAX_BATCH / 2] (Lc, Lu) of the last step
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;

@@ -1286,5 +1286,29 @@ int dtk_op_dry_scan(dtk_ctx* c, int V, const int64_t* history, int n_history, co
   return k;
 }
 
+// dtk_set_guidance's two mixing kernels on a pair of the call's own: the rows lie at stride V as two slots' rows do (row 0 = zu, row 1 =
+// zc, which becomes out: the guard bytes lie behind it), the pair is (1, 0), the launch shape is launch_cfg_mix's for that V
+int dtk_op_cfg_mix(dtk_ctx* c, const float* zc, const float* zu, int V, float scale, float* out, float* lse_out) {
+  if (!c || !zc || !zu || !out || !lse_out || V < 2 || V > DTK_SAMPLE_MB_MAX_SLICES * 8192 || !std::isfinite(scale) || scale < 0.f || scale > 100.f)
+    return fail(c, DTK_ERR_ARG, "dtk_op_cfg_mix: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, "dtk_op_cfg_mix", 0x5a);
+  std::vector<float> rows((size_t)2 * V);
+  memcpy(rows.data(), zu, sizeof(float) * (size_t)V);
+  memcpy(rows.data() + V, zc, sizeof(float) * (size_t)V);
+  const CfgPair pair{1, 0, scale, 0};
+  CfgArgs g;
+  g.logits = (float*)r.take(sizeof(float) * 2 * (size_t)V + OpRun::GUARD);
+  r.ins.push_back({g.logits, rows.data(), sizeof(float) * 2 * (size_t)V});
+  r.res.push_back({g.logits + V, out, sizeof(float) * (size_t)V, "out", false});
+  g.V = V; g.stride = V; g.pairs = r.in<CfgPair>(&pair, 1); g.n_pairs = 1; g.bs = nullptr;
+  g.part = (float2*)r.take(sizeof(float2) * 2 * DTK_CFG_MAX_SLICES);
+  g.lse = reinterpret_cast<float2*>(r.out<float>(lse_out, 2, "lse"));
+  if (const int rc = r.upload(s)) return rc;
+  launch_cfg_mix(g, s);
+  return r.finish(s);
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -156,6 +156,30 @@ struct TopArgs {
   TopRec* top_ring;
 };
 void launch_top_logits(const TopArgs& a, hipStream_t s);
+// dtk_set_guidance (kernels_cfg.hip): classifier-free guidance of the batched step.  A pair = the slot whose pending raw logits row is
+// replaced, in place and in front of k_top_logits and the sampler chain, by g * (log_softmax(zc) - log_softmax(zu)) + log_softmax(zu),
+// and the slot whose row is zu and which forwards the token the first one's chain chose.
+#define DTK_CFG_MAX_SLICES 128
+struct CfgPair { int32_t cond; int32_t uncond; float scale; int32_t pad; };
+struct CfgArgs {
+  float* logits; int V; int stride;    // rows at logits + slot * stride
+  const CfgPair* pairs; int n_pairs;   // device table; grid y
+  const BatchState* bs;                // a pair whose conditional slot is inactive is skipped; null = every pair runs
+  float2* part;                        // [n_pairs][2][DTK_CFG_MAX_SLICES] (max, sum exp(z - max)) per (pair, row, slice)
+  float2* lse;                         // [n_pairs] (Lc, Lu) of the last launch
+  int per = 0;                         // elements per slice (launch_cfg_mix sets it from V)
+};
+void cfg_shape(int V, int* per_out, int* nslices_out);      // the launch shape, a function of V alone
+void launch_cfg_mix(const CfgArgs& a, hipStream_t s);       // k_cfg_lse + k_cfg_mix; nothing with n_pairs == 0
+struct CfgFollowArgs {
+  const CfgPair* pairs; int n_pairs;
+  const BatchState* bs;
+  DecState* st;                        // [slots]
+  bf16_t* x; int d;                    // residual streams [slot][d]
+  int64_t* tok_ring; int ring;         // the step's rings, indexed (step % ring) * DTK_MAX_BATCH + slot
+  float2* lp_ring; float* lse_ring; TopRec* top_ring;   // or null
+};
+void launch_cfg_follow(const CfgFollowArgs& a, hipStream_t s);   // one block per pair, behind the sampler (and k_count_token)
 static inline bool sample_mb_supported(int V) { return V > 32768 && V <= DTK_SAMPLE_MB_MAX_SLICES * 8192; }
 // on the v1 vocabularies (<= 32768) the register-resident single-block kernel is as fast (ds-7b sampling decode 366.2 tok/s
 // vs 366.6 with the chain): one launch, so it stays the default there; DTK_SAMPLER=mb forces the chain for V >= 16384 (A/B)

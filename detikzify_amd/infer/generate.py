@@ -235,9 +235,42 @@ class DetikzifyGenerator:
                                              return_tensors="pt")
         return self._processed
 
+    def _negative_features(self, negative_image: Optional[Image.Image], negative_text: Optional[str]) -> Dict[str, torch.Tensor]:
+        """the negative branch of a guided rollout (model.generate's guidance_scale) as model.generate's arguments: the negative image
+        through the same processor (default: a white canvas of the processor's size), the negative text through the adapter's
+        tokenizer.  A text-only prompt needs a negative text: the adapter's dummy input cannot be prefilled without one.  Built once
+        per (image, text)"""
+        key = (id(negative_image), negative_text)
+        cached = getattr(self, "_negative", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if self.image is None and negative_text is None:
+            raise ValueError("guidance_scale with a text-only prompt needs negative_text: the negative branch is the adapter's dummy input "
+                             "under another text (it cannot be prefilled without one)")
+        out: Dict[str, torch.Tensor] = {}
+        if self.image is not None:
+            if negative_image is None:
+                size = getattr(getattr(unwrap(self.processor), "image_processor", None), "size", None) or {}
+                w, h = (size["width"], size["height"]) if "width" in size and "height" in size else self.image.size
+                negative_image = Image.new("RGB", (int(w), int(h)), color="white")
+            feats = self.processor(images=negative_image, return_tensors="pt", **({"text": negative_text} if negative_text is not None else {}))
+            out["negative_pixel_values"] = feats["pixel_values"]
+        else:
+            feats = self.processor(text=negative_text, return_tensors="pt")
+        if negative_text is not None:
+            if "adapter_input_ids" not in feats:
+                raise ValueError("negative_text needs the adapter's processor (a model loaded with adapter=True)")
+            out["negative_adapter_input_ids"] = feats["adapter_input_ids"]
+        self._negative = (key, out)
+        return out
+
     def generate(self, input_ids: torch.Tensor, streamer=None, **gen_kwargs) -> torch.Tensor:
         sinks = StreamerList([s for s in (streamer, self.streamer) if s])
         options = {**self.gen_kwargs, **gen_kwargs}
+        # classifier-free guidance (model.generate's guidance_scale): negative_image / negative_text become the negative branch's tensors
+        negative_image, negative_text = options.pop("negative_image", None), options.pop("negative_text", None)
+        from ..model.modeling import check_guidance_scale
+        guided = check_guidance_scale(options.get("guidance_scale")) != 1.0
         if (options.get("presence_penalty") or options.get("frequency_penalty")) and options.get("penalty_start") is None:
             options["penalty_start"] = int(self.montecarlo.root_node.token_ids.numel())       # the program text so far counts, the prompt does not
         if options.get("dry_multiplier") and options.get("dry_start") is None:
@@ -253,6 +286,8 @@ class DetikzifyGenerator:
         with torch.inference_mode():
             features = self._prompt_features().to(self.model.device)
             conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}
+            if guided:
+                conditioning.update({name: value.to(self.model.device) for name, value in self._negative_features(negative_image, negative_text).items()})
             out = self.model.generate(
                 input_ids=input_ids[None],
                 pixel_values=features.get("pixel_values"),

@@ -47,6 +47,8 @@ class DetikzifyPipeline:
 
     def _generator(self, image, text, preprocess, **kw) -> DetikzifyGenerator:
         self.check_inputs(image, text)
+        if kw.get("negative_image") is not None:        # guidance_scale's negative image goes the way of the image itself
+            kw = {**kw, "negative_image": self.load(kw["negative_image"], preprocess=preprocess)}
         return DetikzifyGenerator(
             model=self.model, processor=self.processor,
             image=self.load(image, preprocess=preprocess) if image is not None else None,
@@ -59,7 +61,12 @@ class DetikzifyPipeline:
         of the probability the sampler (temperature, top-k, top-p, min_p, epsilon_cutoff, presence_penalty, frequency_penalty,
         dry_multiplier / dry_base / dry_allowed_length / dry_sequence_breakers, min_new_tokens, exponential_decay_length_penalty,
         logit_bias / sequence_bias: all gen_kwargs, here and in simulate) chose it with.  top_logprobs=k (1 .. 8, with return_logprobs=True)
-        also attaches `.token_top_ids` / `.token_top_logprobs`: per generated token the k most likely tokens at its position."""
+        also attaches `.token_top_ids` / `.token_top_logprobs`: per generated token the k most likely tokens at its position.
+
+        guidance_scale=g (with negative_image= / negative_text=; gen_kwargs too, here and in the sequential simulate): classifier-free
+        guidance of model.generate against a negative prompt — by default a white canvas of the processor's size; a text-only prompt
+        needs negative_text.  The model must have been loaded with batch_slots >= 2.  Under guidance the attached log-probabilities
+        and alternatives describe the guided distribution."""
         from ..model.modeling import check_top_logprobs
         check_top_logprobs(top_logprobs, return_logprobs)
         return self._generator(image, text, preprocess, **gen_kwargs).sample(return_logprobs=return_logprobs, top_logprobs=top_logprobs)

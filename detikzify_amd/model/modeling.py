@@ -130,10 +130,10 @@ _NEUTRAL_GENERATE_KWARGS: Dict[str, tuple] = {
     "diversity_penalty": (None, 0.0), "no_repeat_ngram_size": (None, 0), "encoder_no_repeat_ngram_size": (None, 0),
     "min_length": (None, 0), "typical_p": (None, 1.0),
     "eta_cutoff": (None, 0.0), "penalty_alpha": (None, 0.0), "early_stopping": (None, False),
-    "renormalize_logits": (None, False), "remove_invalid_values": (None, False), "guidance_scale": (None, 1.0),
+    "renormalize_logits": (None, False), "remove_invalid_values": (None, False),
     "forced_bos_token_id": (None,), "forced_eos_token_id": (None,),
     "logits_processor": (None, [], ()), "prefix_allowed_tokens_fn": (None,),
-    "assistant_model": (None,), "negative_prompt_ids": (None,), "negative_prompt_attention_mask": (None,),
+    "assistant_model": (None,), "negative_prompt_attention_mask": (None,),
     "generation_config": (None,), "stop_strings": (None,), "max_time": (None,), "cache_implementation": (None,),
     "past_key_values": (None,), "inputs_embeds": (None,), "tokenizer": "any",
 }
@@ -163,6 +163,19 @@ def check_top_logprobs(top_logprobs: Optional[int], return_logprobs: bool = True
     if not 1 <= k <= _lib.DTK_MAX_TOP:
         raise ValueError(f"top_logprobs = {top_logprobs}: 1 .. {_lib.DTK_MAX_TOP}")
     return k
+
+
+def check_guidance_scale(guidance_scale) -> float:
+    """the `guidance_scale` argument of generate -> g (1.0 = off: None and 1); a finite real number in [0, 100], ValueError before
+    anything runs"""
+    if guidance_scale is None:
+        return 1.0
+    if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)):
+        raise ValueError(f"guidance_scale = {guidance_scale!r}: a number in [0, 100]")
+    g = float(guidance_scale)
+    if not math.isfinite(g) or not 0.0 <= g <= 100.0:
+        raise ValueError(f"guidance_scale = {guidance_scale!r}: a finite number in [0, 100]")
+    return g
 
 
 def check_truncation(min_p: Optional[float], epsilon_cutoff: Optional[float]) -> Tuple[float, float]:
@@ -1095,6 +1108,24 @@ class DetikzifyForCausalLM:
         self._check(self.lib.dtk_decode_batch_wait_lp(self._ctx, out, lp, slp), "dtk_decode_batch_wait_lp")
         return [int(v) for v in out], list(lp), list(slp)
 
+    # ---- classifier-free guidance: pairs of batch slots (dtk_set_guidance) ------------------------------------
+    def set_guidance(self, scale: Optional[float], cond_slot: int, uncond_slot: Optional[int]):
+        """pairs two decoding slots for classifier-free guidance: in every batched step the conditional slot's pending
+        logits row becomes scale * (log_softmax(zc) - log_softmax(zu)) + log_softmax(zu) in front of its whole sampler chain, and the
+        unconditional slot forwards the token that chain chose.  scale None / 1 or uncond_slot None / < 0 dissolves the pair cond_slot
+        heads.  Refused while a batch step is in flight"""
+        g = check_guidance_scale(scale)
+        u = -1 if uncond_slot is None else int(uncond_slot)
+        self._check(self.lib.dtk_set_guidance(self._ctx, int(cond_slot), u, g), "dtk_set_guidance")
+
+    def guidance(self, slot: int) -> Optional[Dict[str, Any]]:
+        """diagnostic: the guided pair `slot` is in — {partner, is_cond, scale, lse: (Lc, Lu) of the pair's last step} — or None"""
+        partner, is_cond, scale, lse = C.c_int(-1), C.c_int(0), C.c_float(1.0), (C.c_float * 2)()
+        self._check(self.lib.dtk_get_guidance(self._ctx, int(slot), C.byref(partner), C.byref(is_cond), C.byref(scale), lse), "dtk_get_guidance")
+        if partner.value < 0:
+            return None
+        return dict(partner=int(partner.value), is_cond=bool(is_cond.value), scale=float(scale.value), lse=(float(lse[0]), float(lse[1])))
+
     # ---- log-probabilities of sampled tokens (dtk_set_option "logprobs") ------------------------------------
     @property
     def logprobs_enabled(self) -> bool:
@@ -1244,7 +1275,9 @@ class DetikzifyForCausalLM:
                  penalty_start: Optional[int] = None, dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None,
                  dry_allowed_length: Optional[int] = None, dry_start: Optional[int] = None, dry_sequence_breakers=None,
                  min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None, logit_bias=None, sequence_bias=None,
-                 length_start: Optional[int] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 length_start: Optional[int] = None, guidance_scale: Optional[float] = None,
+                 negative_prompt_ids: Optional[torch.Tensor] = None, negative_pixel_values: Optional[torch.Tensor] = None,
+                 negative_adapter_input_ids: Optional[torch.Tensor] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1275,10 +1308,23 @@ class DetikzifyForCausalLM:
         value} (OpenAI / vLLM) and HF's sequence_bias with single-token sequences: one table of at most 256 biases in [-100, 100] added
         to the raw logits in front of the penalties.  0 / None = off.  The reported log-probabilities stay the model's own.
 
+        guidance_scale=g (HF's UnbatchedClassifierFreeGuidanceLogitsProcessor; a finite number in [0, 100]; None / 1 = off): classifier-free
+        guidance against a negative prompt — negative_prompt_ids (default: input_ids, so a rollout that continues a node carries the program
+        text so far in both branches), negative_pixel_values (default: pixel_values) and, with an adapter, negative_adapter_input_ids
+        (default: no text).  At least one of the three must be given: the negative branch has to differ in something.  The two sequences
+        decode as a pair in slots 0 and 1 of a model loaded with batch_slots >= 2, one pass over the weights for both; every step the raw
+        logits become g * (log_softmax(z) - log_softmax(z_neg)) + log_softmax(z_neg) on the device, in front of EVERYTHING else: the
+        alternatives of top_logprobs, logit_bias, the penalties, DRY, the length rules, the suppression lists, temperature, top-k,
+        top-p, min-p, epsilon, greedy included (HF's processor order).  Consequently `.logprobs`, `.top_ids` and
+        `.top_logprobs` of a guided call describe the GUIDED distribution (out[t] - logsumexp(out)), not the model's own.  Not in the
+        batch engines yet; contexts without slots (tl-1.1b, MXFP4) have no guidance.
+
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
         unknown names — raises instead of being dropped: a drop-in must not silently decode something else."""
         topk = check_top_logprobs(top_logprobs, return_logprobs)
+        if guidance_scale is not None:      # (a bad value raises before anything else is looked at)
+            check_guidance_scale(guidance_scale)
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
         text_ids = None
@@ -1292,6 +1338,18 @@ class DetikzifyForCausalLM:
             if tids is not None:
                 text_ids = adapter_text(tids, tmask)
         _reject_unsupported_generate_kwargs(hf_kwargs)
+        guide = check_guidance_scale(getattr(self.generation_config, "guidance_scale", None) if guidance_scale is None else guidance_scale)
+        guided = guide != 1.0
+        if guided:      # everything that refuses a guided call, before anything runs
+            if negative_prompt_ids is None and negative_pixel_values is None and negative_adapter_input_ids is None:
+                raise ValueError(f"guidance_scale = {guide}: the negative branch must differ from the prompt in something — pass "
+                                 "negative_prompt_ids, negative_pixel_values and / or negative_adapter_input_ids")
+            if self.batch_engine is not None:
+                raise NotImplementedError("guidance_scale: not in the batch engines yet")
+            if self.num_slots() < 2:
+                raise ValueError("guidance_scale needs two batch slots for the guided pair: load(..., batch_slots=2) or more "
+                                 "(contexts without slots — tl-1.1b, MXFP4 — have no guidance)")
+            self._refuse_while_batch_busy("generate")
         if input_ids is None:
             input_ids = inputs
         ids = input_ids.detach().to("cpu", torch.int64)
@@ -1299,6 +1357,17 @@ class DetikzifyForCausalLM:
             ids = ids[None]
         if ids.shape[0] != 1:
             raise ValueError("batch size 1 only (the reference generates one sequence per call)")
+        neg_ids = neg_px = neg_text = None
+        if guided:
+            neg_ids = ids if negative_prompt_ids is None else negative_prompt_ids.detach().to("cpu", torch.int64).reshape(1, -1)
+            neg_px = pixel_values if negative_pixel_values is None else negative_pixel_values
+            if negative_adapter_input_ids is not None:
+                if not self.has_adapter():
+                    raise TypeError("generate() got negative_adapter_input_ids but no adapter is loaded (load(..., adapter=True))")
+                neg_text = adapter_text(negative_adapter_input_ids)
+            if neg_px is None and neg_text is None:
+                raise ValueError("guidance_scale with a text-only prompt: the adapter's dummy input cannot be prefilled without a text, so "
+                                 "the negative branch needs one of its own — pass negative_adapter_input_ids (the pipeline's negative_text)")
         gc = self.generation_config
         min_p, epsilon_cutoff = check_truncation(getattr(gc, "min_p", None) if min_p is None else min_p,
                                                  getattr(gc, "epsilon_cutoff", None) if epsilon_cutoff is None else epsilon_cutoff)
@@ -1337,6 +1406,8 @@ class DetikzifyForCausalLM:
         elif max_length is None:
             max_length = gc.max_length
         max_length = min(int(max_length), self.config.max_positions)
+        if guided and neg_ids.shape[1] > T:      # both sequences grow by the same tokens: the longer prompt bounds the new ones
+            max_length = min(max_length, T + self.config.max_positions - int(neg_ids.shape[1]))
         eos = eos_token_id if eos_token_id is not None else gc.eos_token_id
         eos_set = set(_flat_ids([eos]))
         # the length rules act on the valid EOS ids (none, as with eos_token_id=-1: nothing to do)
@@ -1449,33 +1520,63 @@ class DetikzifyForCausalLM:
                 raise _lib.DtkError("concurrent generate() calls on one model: decode them as a batch "
                                     "(detikzify_amd.infer.batching.BatchEngine / simulate_parallel)")
             launched = received = 0
+            at = {"slot": 0} if guided else {}      # a guided pair decodes in slots 0 (this call's sampling state) and 1 (the negative prompt)
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
-                                  begin_suppress_tokens or (), suppress_tokens or ())
+                                  begin_suppress_tokens or (), suppress_tokens or (), **at)
                 if min_p or epsilon_cutoff:       # (set_sampling reset both)
-                    self.set_sampling_ext(min_p, epsilon_cutoff)
+                    self.set_sampling_ext(min_p, epsilon_cutoff, **at)
                 if presence_penalty or frequency_penalty:       # (likewise; the prefill below builds the count table)
-                    self.set_penalties(presence_penalty, frequency_penalty, penalty_start)
+                    self.set_penalties(presence_penalty, frequency_penalty, penalty_start, **at)
                 if dry_multiplier:       # (likewise; the prefill below builds the history)
-                    self.set_dry(dry_multiplier, dry_base, dry_allowed_length, dry_start, dry_sequence_breakers)
+                    self.set_dry(dry_multiplier, dry_base, dry_allowed_length, dry_start, dry_sequence_breakers, **at)
                 if len_eos:              # (likewise; static for the sequence: the length comes from the device's own position)
-                    self.set_length_control(min_new_tokens, decay, length_start, len_eos)
+                    self.set_length_control(min_new_tokens, decay, length_start, len_eos, **at)
                 if bias_pairs:
-                    self.set_logit_bias(bias_pairs)
+                    self.set_logit_bias(bias_pairs, **at)
+                if guided:               # the unconditional slot: neutral greedy sampling, no tables (its own choice is never used)
+                    self.set_sampling(slot=1)
                 if return_logprobs:       # (after set_sampling: steps an earlier call left unread are forgotten there, the switch refuses them)
                     self.enable_logprobs()
                     if topk:
                         self.enable_top_logprobs(topk)
                 if text_ids is not None:
-                    self.prefill(ids[0], pixel_values, adapter_input_ids=text_ids)
+                    self.prefill(ids[0], pixel_values, adapter_input_ids=text_ids, **at)
                 else:
-                    self.prefill(ids[0], pixel_values)
+                    self.prefill(ids[0], pixel_values, **at)
+                if guided:
+                    if neg_text is not None:
+                        self.prefill(neg_ids[0], neg_px, adapter_input_ids=neg_text, slot=1)
+                    else:
+                        self.prefill(neg_ids[0], neg_px, slot=1)
+                    self.set_guidance(guide, 0, 1)
+
                 launched = received = 0
                 stop = False
                 ahead = 2  # one step always in flight while the host handles the previous token
-                while launched < min(ahead, n_new_max):
+                if guided:      # the same loop over steps of the pair: slot 0's token and records are the sequence's
+                    while launched < min(ahead, n_new_max):
+                        self.decode_batch_launch([0, 1]); launched += 1
+                    while received < launched:
+                        if topk:
+                            toks, lps, slps, tis, tls = self.decode_batch_wait(top=True)
+                            pairs[0].append(lps[0]); pairs[1].append(slps[0]); tops[0].append(tis[0]); tops[1].append(tls[0])
+                        elif return_logprobs:
+                            toks, lps, slps = self.decode_batch_wait_lp()
+                            pairs[0].append(lps[0]); pairs[1].append(slps[0])
+                        else:
+                            toks = self.decode_batch_wait()
+                        received += 1
+                        if toks[0] != toks[1]:      # the follower hands slot 1 the token slot 0's chain chose: one token per pair per step
+                            raise _lib.DtkError(f"guided pair: slot 0 reports token {toks[0]}, slot 1 token {toks[1]}")
+                        stop = emit(toks[0])
+                        if stop:
+                            break
+                        if launched < n_new_max:
+                            self.decode_batch_launch([0, 1]); launched += 1
+                while not guided and launched < min(ahead, n_new_max):
                     self.decode_launch(); launched += 1
-                while received < launched:
+                while not guided and received < launched:
                     if topk:
                         tok, lp, slp, ti, tl = self.decode_wait(top=True)
                         pairs[0].append(lp); pairs[1].append(slp); tops[0].append(ti); tops[1].append(tl)
@@ -1492,11 +1593,18 @@ class DetikzifyForCausalLM:
                         self.decode_launch(); launched += 1
             finally:
                 try:
-                    if topk:        # the call that asked for the alternatives switches them off again: later steps run without the extra kernel
+                    if topk or guided:      # the call that asked for the alternatives / the pair switches them off again: later steps run without the extra kernels
                         self.synchronize()
-                        while received < launched:      # (a step left in flight behind the last token: the switch refuses unread steps)
-                            self.decode_wait(); received += 1
-                        self.enable_top_logprobs(0)
+                        while received < launched:      # (a step left in flight behind the last token: the switches refuse unread steps)
+                            received += 1
+                            if guided:
+                                self.decode_batch_wait()
+                            else:
+                                self.decode_wait()
+                        if guided:
+                            self.set_guidance(None, 0, None)
+                        if topk:
+                            self.enable_top_logprobs(0)
                 finally:
                     self._single_busy.release()
         if streamer is not None:

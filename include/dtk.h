@@ -932,6 +932,38 @@ int  dtk_engine_submit_shape(dtk_engine* e, dtk_join* j, const dtk_sampling_ext*
 int  dtk_engine_set_length_control_op(dtk_engine* e, int (*set_length_control_slot)(void* dev, int slot, const dtk_length_ctl* l));
 int  dtk_engine_set_logit_bias_op(dtk_engine* e, int (*set_logit_bias_slot)(void* dev, int slot, const int32_t* ids, const float* values, int n));
 
+/* Classifier-free guidance (additive, ABI 7): HF's UnbatchedClassifierFreeGuidanceLogitsProcessor for two batch slots that decode in
+ * one step.  A pair is a conditional slot c and an unconditional slot u (two prompts, e.g. the sketch and an empty canvas).  In every
+ * batched step, in front of everything else that reads the pending raw logits (the top-k records, bias, penalties, DRY, the length
+ * rules, the suppression lists, temperature, top-k, top-p, min-p, epsilon; greedy included), row c is replaced in place by
+ *     Lc = logsumexp(zc)   Lu = logsumexp(zu)   lc = zc[v] - Lc   lu = zu[v] - Lu   out[v] = g * (lc - lu) + lu
+ * in fp32, every subtraction, multiplication and addition rounded on its own (never an fma), so a host that is given the device's
+ * (Lc, Lu) reproduces out bit for bit.  Consequently a guided sequence's logprob, its top-k records and their logsumexp describe the
+ * GUIDED distribution out[t] - logsumexp(out).  Behind the sampler slot u takes over the token slot c's chain chose (its DecState, the
+ * gathered embedding, the step's ring entries): one token per pair per step, both slots report it.  Slot u's own sampling state is
+ * not consulted; keep it at neutral greedy sampling with no tables.  The two launches in front (k_cfg_lse, k_cfg_mix: grid (slice,
+ * pair), the slice count a function of V alone, no atomics) and the one behind (k_cfg_follow) exist only in the steps of a context
+ * with a pair: without one the step launches exactly what it launched before, and nothing is allocated before the first pair.
+ * Contexts without slots (tl-1.1b's head_dim 64, MXFP4) have no guidance.
+ *   dtk_set_guidance   pairs two distinct decoding slots (scale finite in [0, 100]); the same pair again changes its scale;
+ *                      uncond_slot < 0 or scale == 1 dissolves the pair cond_slot heads (no pair: DTK_OK).  DTK_ERR_ARG for a slot out of
+ *                      range, a slot already in another pair, equal slots, a scale outside the range or not finite; DTK_ERR_STATE while a
+ *                      batch step is in flight.  At most DTK_MAX_BATCH / 2 pairs.  A pair is static for a sequence: dtk_prefill_slot,
+ *                      dtk_resume_slot and dtk_kv_fork leave it alone.  Every change re-captures the batched step.
+ *   dtk_get_guidance   diagnostic: slot's partner (-1: none), whether slot is the conditional one, the scale (1 without a pair) and
+ *                      lse_out[2] = (Lc, Lu) of the pair's last step (NaN without a pair; meaningful once the pair has decoded a step since
+ *                      the last dtk_set_guidance that changed the set of pairs); any out pointer may be NULL.
+ *   dtk_decode_batch_launch   refuses (DTK_ERR_ARG, nothing launched) a step in which exactly one slot of a pair is active.
+ *   dtk_op_cfg_mix     the two mixing kernels in the launch shape the step uses for that V, on two rows at stride V of the op scratch:
+ *                      out[V] and lse_out[2] = (Lc, Lu).  2 <= V <= 262 144.  The 256 bytes behind out are checked (DTK_ERR_STATE).
+ *   dtk_bench_cfg      tools/bench_cfg.py: HIP events around reps (1 .. 64) back-to-back launches on the context's own pairs and rows:
+ *                      avg_us[0] = k_cfg_lse + k_cfg_mix, avg_us[1] = k_cfg_follow.  The conditional slots' pending rows are mixed over
+ *                      and over: prefill the pairs again before decoding on. */
+int  dtk_set_guidance(dtk_ctx* ctx, int cond_slot, int uncond_slot, float scale);
+int  dtk_get_guidance(dtk_ctx* ctx, int slot, int* partner_out, int* is_cond_out, float* scale_out, float* lse_out /* [2] */);
+int  dtk_op_cfg_mix(dtk_ctx* ctx, const float* zc, const float* zu, int V, float scale, float* out /* [V] */, float* lse_out /* [2] */);
+int  dtk_bench_cfg(dtk_ctx* ctx, int reps, float* avg_us /* [2] */);
+
 #ifdef __cplusplus
 }
 #endif
