@@ -229,6 +229,11 @@ SYMBOLS = {
                                      _P, _P, _P, _P]),
     "dtk_op_attn_decode_b": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    # additive (ABI stays 7): kv_format "mxfp8" — the boundary, the diagnostic read, and the attention op on shadow planes
+    "dtk_kv8_info": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "dtk_read_kv8": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "dtk_op_attn_decode_b8": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     # additive (ABI stays 7): the weight kernels of the batched decode step alone
     "dtk_op_gemv_b": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P, C.c_int,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

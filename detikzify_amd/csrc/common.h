@@ -128,6 +128,10 @@ struct BatchState {
   int32_t group_plus1[DTK_MAX_BATCH];
   int32_t pfx_len_of[DTK_MAX_BATCH];   // = groups[group_plus1[slot] - 1].len, or 0: what k_attn_tail_b needs, without the dependent lookup
   PfxGroup groups[DTK_PFX_GROUPS];
+  // MXFP8 key/value shadow (kv_format "mxfp8"): rows [kv8_from[slot], pos) of the slot were written by decode steps and are read from the
+  // shadow planes; rows below it (prefill, fork) exist in bf16 only.  kv8_from[slot] <= pos at every step the slot takes.  Last member:
+  // every offset above is what it was.
+  int32_t kv8_from[DTK_MAX_BATCH];
 };
 
 // Batched decode keeps the GEMV INPUT vectors (normalised x, attention output, SwiGLU activation) of the slots in

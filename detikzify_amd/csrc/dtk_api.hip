@@ -293,6 +293,11 @@ void plan(dtk_ctx* c, Planner& P, bool reg) {
   if (c->nb > 0) {
     c->kv_slot_stride = (size_t)L * 2 * c->KVH * T * 128;
     c->kvb = P.take<bf16_t>((size_t)c->nb * c->kv_slot_stride);
+    if (c->kv8) {      // MXFP8 shadow of the decoding slots' decoded rows: 1 + 1/32 bytes per bf16 element of their caches
+      c->kv8_slots = c->nb < 16 * c->nt ? c->nb : 16 * c->nt;
+      c->kv8c = P.take<uint8_t>((size_t)c->kv8_slots * c->kv_slot_stride);
+      c->kv8s = P.take<uint8_t>((size_t)c->kv8_slots * c->kv_slot_stride / 32);
+    }
     c->xb = P.take<bf16_t>((size_t)DTK_MAX_BATCH * d);
     // xnb / aob / actb are fragment-major GEMV inputs (common.h xtile_off): K rounded up to whole 32-wide k-steps
     c->xnb = P.take<bf16_t>((size_t)DTK_MAX_BATCH * align_up((size_t)(d > ff ? d : ff), 32));
@@ -686,6 +691,14 @@ void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
 }
 
 static inline bool mx_step(const dtk_ctx* c) { return c->wfmt == 1 && c->mx_ok && c->act_fp8 != 0; }
+// kv_format "mxfp8": layer l's shadow planes for the attention of a batched step (a bf16 context: nothing, the bf16 instantiations run)
+static inline void kv8_args(const dtk_ctx* c, int l, AttnDecBArgs& ad) {
+  if (!c->kv8) return;
+  const size_t head_rows = (size_t)c->KVH * c->Tmax, kv_layer = 2 * head_rows * 128;
+  ad.k8 = c->kv8c + (size_t)l * kv_layer; ad.v8 = ad.k8 + head_rows * 128;
+  ad.k8s = c->kv8s + (size_t)l * (kv_layer / 32); ad.v8s = ad.k8s + head_rows * 4;
+  ad.kv8_slot_stride = c->kv_slot_stride;
+}
 
 // The MFMA-family step of an fp8 model on the fp8 matrix cores (kernels_batch_mx.hip): 7 launches per layer as the 64-slot bf16
 // step — q/k/v, attention, o_proj partials, reduce + residual + RMSNorm, gate/up, down partials, reduce + residual + RMSNorm —
@@ -723,6 +736,7 @@ void batch_step_launches_mx(dtk_ctx* c) {
     ad.use_prefix = c->prefix_mfma; ad.pfx_splits = c->pfx_splits; ad.tail_threads = c->tail_threads; ad.gqa_fused = c->gqa_fused; ad.nt_private = c->attn_nt;
     ad.pfx_m = c->pfx_m; ad.pfx_l = c->pfx_l; ad.pfx_o = c->pfx_o;
     ad.out8 = c->ao8; ad.outs = c->aos;
+    kv8_args(c, l, ad);
     launch_attn_decode_b(ad, s);
     g.Wm = w.m_wo; g.wscale = w.s_wo; g.N = d; g.K = d; g.X8 = c->ao8; g.XS = c->aos;
     if (!launch_gemv_mxk(g, 32, s)) c->launch_refused = true;
@@ -784,6 +798,7 @@ void batch_step_launches(dtk_ctx* c) {
     ad.scale = scale;
     ad.use_prefix = c->prefix_mfma; ad.pfx_splits = c->pfx_splits; ad.tail_threads = c->tail_threads; ad.gqa_fused = c->gqa_fused; ad.nt_private = c->attn_nt;
     ad.pfx_m = c->pfx_m; ad.pfx_l = c->pfx_l; ad.pfx_o = c->pfx_o;
+    kv8_args(c, l, ad);
     launch_attn_decode_b(ad, s);
     g.W = w.t_wo; g.W8 = w.t8_wo; g.wscale = w.s_wo; g.N = d; g.K = d; g.X = c->aob; g.ldx = d; g.Y = c->xb; g.ldy = d;
     if (kparts) {
@@ -852,6 +867,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
     ad.scale = scale;
     ad.use_prefix = 0; ad.pfx_splits = c->pfx_splits; ad.tail_threads = c->mv_tail_threads; ad.gqa_fused = c->gqa_fused; ad.nt_private = c->attn_nt;
     ad.pfx_m = c->pfx_m; ad.pfx_l = c->pfx_l; ad.pfx_o = c->pfx_o;
+    kv8_args(c, l, ad);
     launch_attn_decode_b(ad, s);
     // 3. o_proj + residual
     g.W = w.wo; g.W8 = w.q_wo; g.wscale = w.s_wo; g.N = d; g.K = d; g.X = c->aob; g.Y = c->xb; g.ldy = d;
@@ -1513,6 +1529,10 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
     return fail(nullptr, DTK_ERR_ARG, "DTK_ATTN_THREADS=0: the contiguous-split decode attention has no head_dim-64 kernel (256, 512 or 1024)");
   if (cfg->reserved[1] == 2 && cfg->reserved[0] > 0)   // refused before anything is allocated
     return fail(nullptr, DTK_ERR_ARG, "weight_format mxfp4: MXFP4 weights have no batched-slot or multi-vector kernels yet (batch_slots = %d; use batch_slots = 0)", cfg->reserved[0]);
+  if (cfg->reserved[4] != 0 && cfg->reserved[4] != 1)      // key/value row format of decoded tokens: 0 bf16, 1 MXFP8 shadow
+    return fail(nullptr, DTK_ERR_ARG, "kv_format %d: 0 (bf16) or 1 (MXFP8 shadow rows for decoded tokens)", cfg->reserved[4]);
+  if (cfg->reserved[4] == 1 && cfg->reserved[0] <= 0)
+    return fail(nullptr, DTK_ERR_ARG, "kv_format mxfp8: only the batched decode steps read MXFP8 rows (batch_slots = %d; the single-sequence step has no such kernel)", cfg->reserved[0]);
   if (cfg->hidden != cfg->heads * cfg->head_dim)
     return fail(nullptr, DTK_ERR_ARG, "hidden (%d) != heads*head_dim", cfg->hidden);
   if (cfg->reserved[2] < 0 || (cfg->reserved[2] > 0 && cfg->heads % cfg->reserved[2] != 0))
@@ -1552,6 +1572,7 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   // (prefix cache: one per image in flight, BASELINE config 5 = 8 images)
   c->nb = cfg->reserved[0] < 0 ? 0 : (cfg->reserved[0] > DTK_MAX_SLOTS ? DTK_MAX_SLOTS : cfg->reserved[0]);
   c->nt = c->nb > 33 ? 4 : (c->nb > 17 ? 2 : 1);   // 17 / 33 / 65 = 16 / 32 / 64 decoding slots + the prefix slot
+  c->kv8 = cfg->reserved[4] == 1 ? 1 : 0;
   c->bseq.resize((size_t)c->nb);
   c->vD = cfg->vit_dim; c->vDepth = cfg->vit_depth; c->vH = cfg->vit_heads; c->vHd = vhd;
   c->vMlp = cfg->vit_mlp; c->vN = np * np;
@@ -1600,6 +1621,10 @@ int dtk_create(const dtk_config* cfg, int device, dtk_ctx** out) {
   real.base = c->arena;
   plan(c, real, true);
   CCHK(hipMemsetAsync(c->arena, 0, c->arena_bytes, c->stream));
+  if (c->kv8) {      // a shadow row read before it was written is NaN, as a code and as a scale
+    CCHK(hipMemsetAsync(c->kv8c, 0xFF, (size_t)c->kv8_slots * c->kv_slot_stride, c->stream));
+    CCHK(hipMemsetAsync(c->kv8s, 0xFF, (size_t)c->kv8_slots * c->kv_slot_stride / 32, c->stream));
+  }
   CCHK(hipHostMalloc((void**)&c->tok_ring_host, sizeof(int64_t) * DTK_MAX_INFLIGHT, hipHostMallocDefault));
   CCHK(hipHostMalloc((void**)&c->lp_ring_host, sizeof(float2) * DTK_MAX_INFLIGHT, hipHostMallocDefault));
   for (int i = 0; i < DTK_MAX_INFLIGHT; ++i) CCHK(hipEventCreateWithFlags(&c->step_done[i], hipEventDisableTiming));
@@ -2366,6 +2391,8 @@ int dtk_prefill_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, const floa
   clip(sh);
   for (int j = 0; j < c->nb; ++j)
     if (j != slot && c->bseq[(size_t)j].share_src == slot) clip(c->bseq[(size_t)j]);
+  if (rc == DTK_OK) sh.kv8_from = sh.host_next_pos;      // every row of the slot is now a prefill row (kept ones included): bf16 only
+  else sh.kv8_from = std::min(sh.kv8_from, sh.host_next_pos);      // a refused or failed prefill may have cut the context: never above its length
   return rc;
 }
 
@@ -2749,6 +2776,7 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
     const bool sh_ok = c->share_reads && j < c->nb && c->bseq[(size_t)j].share_src >= 0;
     hb->share_src[j] = sh_ok ? c->bseq[(size_t)j].share_src : -1;
     hb->share_len[j] = sh_ok ? c->bseq[(size_t)j].share_len : 0;
+    hb->kv8_from[j] = c->kv8 && j < c->nb ? c->bseq[(size_t)j].kv8_from : 0;
   }
   hb->step = (int32_t)(c->blaunched % DTK_MAX_INFLIGHT);
   build_prefix_groups(hb, active, c->prefix_mfma && !mv_family(c));
@@ -2882,6 +2910,7 @@ int dtk_kv_fork(dtk_ctx* c, int src, int dst, int n_tokens) {
   b.cached_with_image = a.cached_with_image;
   b.image_key = a.image_key;
   b.host_next_pos = n_tokens;
+  b.kv8_from = n_tokens;                   // nothing of the shadow is copied: the destination's rows [0, n) are bf16 rows
   b.have_logits = false;
   // a fork of the WHOLE source sequence also inherits its next-token logits: the destination can decode at
   // once (a rollout from the MCTS root needs no prefill at all).  The source must not have decoded since its
@@ -2895,6 +2924,32 @@ int dtk_kv_fork(dtk_ctx* c, int src, int dst, int n_tokens) {
     HIPCHK(c, hipMemcpyAsync(c->st_b + dst, &st0, sizeof st0, hipMemcpyHostToDevice, c->stream));
     b.have_logits = true;
   }
+  return DTK_OK;
+}
+
+// kv_format "mxfp8": the slot's boundary — its rows [from, length) were written by decode steps and are read from the MXFP8 shadow.
+int dtk_kv8_info(dtk_ctx* c, int slot, int* from_out) {
+  if (!c || !from_out || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_kv8_info: bad argument");
+  if (!c->kv8) return fail(c, DTK_ERR_STATE, "dtk_kv8_info: the context keeps bf16 key/value rows only (kv_format bf16)");
+  *from_out = c->bseq[(size_t)slot].kv8_from;
+  return DTK_OK;
+}
+
+// Diagnostic: rows [row0, row0 + nrows) of one layer's K (which = 0) or V (1) planes of a decoding slot, every kv head: the shadow's
+// codes [KVH][nrows][128] and scales [KVH][nrows][4] and the bf16 rows beside them [KVH][nrows][128] (any of the three may be NULL).
+// Waits for the launched steps first.
+int dtk_read_kv8(dtk_ctx* c, int slot, int layer, int which, int row0, int nrows, uint8_t* codes_out, uint8_t* scales_out, uint16_t* bf16_out) {
+  if (!c || slot < 0 || slot >= c->nb || layer < 0 || layer >= c->L || which < 0 || which > 1 || row0 < 0 || nrows < 1 || row0 + nrows > c->Tmax)
+    return fail(c, DTK_ERR_ARG, "dtk_read_kv8: bad argument");
+  if (!c->kv8) return fail(c, DTK_ERR_STATE, "dtk_read_kv8: the context keeps bf16 key/value rows only (kv_format bf16)");
+  if (slot >= c->kv8_slots) return fail(c, DTK_ERR_ARG, "dtk_read_kv8: slot %d never decodes and has no shadow rows (slots 0..%d do)", slot, c->kv8_slots - 1);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t plane = ((size_t)slot * c->L * 2 + (size_t)layer * 2 + which) * c->KVH * c->Tmax;      // rows before this (slot, layer, k|v) plane
+  const size_t first = plane + row0;
+  if (codes_out) HIPCHK(c, hipMemcpy2D(codes_out, (size_t)nrows * 128, c->kv8c + first * 128, (size_t)c->Tmax * 128, (size_t)nrows * 128, c->KVH, hipMemcpyDeviceToHost));
+  if (scales_out) HIPCHK(c, hipMemcpy2D(scales_out, (size_t)nrows * 4, c->kv8s + first * 4, (size_t)c->Tmax * 4, (size_t)nrows * 4, c->KVH, hipMemcpyDeviceToHost));
+  if (bf16_out) HIPCHK(c, hipMemcpy2D(bf16_out, (size_t)nrows * 256, c->kvb + first * 128, (size_t)c->Tmax * 256, (size_t)nrows * 256, c->KVH, hipMemcpyDeviceToHost));
   return DTK_OK;
 }
 
@@ -2954,6 +3009,7 @@ int dtk_resume_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, uint64_t im
   sh.forced_pending = ids[T - 1];          // (a dtk_set_penalties_slot before the step that forwards it counts it too)
   if (const int rc = pen_rebuild(c, 1 + slot, ids, T)) return rc;      // with the forced ids[T-1]: the step that forwards it counts nothing
   sh.host_next_pos = T - 1;
+  sh.kv8_from = std::min(sh.kv8_from, T - 1);      // the rows this slot decoded earlier and keeps stay MXFP8 rows
   sh.have_logits = true;                   // "may decode": the first step does not read the logits buffer
   sh.last_reuse_start = T - 1;
   DecState& st0 = c->st_stage[slot];
@@ -3679,6 +3735,8 @@ int dtk_prefill_slot_text(dtk_ctx* c, int slot, const int64_t* ids, int T, const
   clip(sh);
   for (int j = 0; j < c->nb; ++j)
     if (j != slot && c->bseq[(size_t)j].share_src == slot) clip(c->bseq[(size_t)j]);
+  if (rc == DTK_OK) sh.kv8_from = sh.host_next_pos;      // every row of the slot is now a prefill row (kept ones included): bf16 only
+  else sh.kv8_from = std::min(sh.kv8_from, sh.host_next_pos);      // a refused or failed prefill may have cut the context: never above its length
   return rc;
 }
 

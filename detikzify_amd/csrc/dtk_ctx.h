@@ -40,6 +40,7 @@ struct SeqHost {   // host-side mirror of one sequence's decode state
   int share_len = 0;
   int last_reuse_start = 0;        // tokens of the previous cache the last prefill kept
   int64_t forced_pending = -1;     // dtk_resume_slot's last id until the step that forwards it is launched: part of the sequence, not yet of cached_ids
+  int kv8_from = 0;                // kv_format "mxfp8": rows [kv8_from, length) were written by decode steps and have MXFP8 shadow rows (BatchState::kv8_from)
 };
 
 struct LayerW {
@@ -191,6 +192,12 @@ struct dtk_ctx {
   std::vector<SeqHost> bseq;
   bf16_t* kvb = nullptr;             // [nb][L][2][H][Tmax][128]
   size_t kv_slot_stride = 0;
+  // kv_format "mxfp8" (dtk_config.reserved[4] = 1): the MXFP8 shadow of the rows decode steps wrote, for the kv8_slots decoding slots
+  // (prefix-cache slots never decode and have none).  Codes [kv8_slots][L][2][KVH][Tmax][128] u8 — the bf16 cache's own element
+  // strides in bytes — and E8M0 scales [kv8_slots][L][2][KVH][Tmax][4].  Written by k_attn_tail_b<.., KV8> alone; poisoned (0xFF:
+  // NaN as a code and as a scale) at dtk_create.  The bf16 cache stays the master of every row.
+  int kv8 = 0; int kv8_slots = 0;
+  uint8_t* kv8c = nullptr; uint8_t* kv8s = nullptr;
   bf16_t *xb = nullptr, *xnb = nullptr, *qb = nullptr, *aob = nullptr, *actb = nullptr;  // [16][d|ff]
   float* logits_b = nullptr;
   float* kpart = nullptr; unsigned* kctr = nullptr;   // k_gemv_bk / k_gemv_bkp partial sums + arrival counters

@@ -413,9 +413,13 @@ int dtk_op_attn_decode(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const u
 // [nslots][KVH][T_max][128], per slot pos / active / share_src (-1: none) / share_len.  The prefix groups come from
 // build_prefix_groups, the step's own table.  out [nslots][H*128] row-major (the fragment-major order of the kernel is undone here);
 // every element is 0xFFFF first, so the rows of slots that did not decode keep that value.
-int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
-                         const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
-                         int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
+//
+// kv8_from != nullptr (dtk_op_attn_decode_b8): the KV8 instantiations on the caller's shadow planes — codes [nslots][KVH][T_max][128],
+// scales [nslots][KVH][T_max][4], uploaded as they are (the caller's poison included) and read back after the launch.
+static int op_attn_decode_b(dtk_ctx* c, const char* who, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                            const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                            const int32_t* kv8_from, uint8_t* k8, uint8_t* k8s, uint8_t* v8, uint8_t* v8s,
+                            int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
   if (!c || !q || !K || !V || !pos || !active || !share_src || !share_len || !out) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: null argument");
   if (nslots != 1 && nslots != 2 && nslots != 4 && nslots != 16 && nslots != 32 && nslots != 64)
     return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b: nslots must be 1, 2, 4, 16, 32 or 64");
@@ -438,6 +442,11 @@ int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const
     hbs.active[j] = act[j];
     hbs.share_src[j] = share_src[j] >= 0 ? share_src[j] : -1;
     hbs.share_len[j] = share_src[j] >= 0 ? share_len[j] : 0;
+    if (kv8_from) {
+      if (act[j] && (kv8_from[j] < hbs.share_len[j] || kv8_from[j] > pos[j]))
+        return fail(c, DTK_ERR_ARG, "%s: slot %d: kv8_from %d outside [%d shared rows, position %d]", who, j, kv8_from[j], hbs.share_len[j], pos[j]);
+      hbs.kv8_from[j] = kv8_from[j];
+    }
   }
   build_prefix_groups(&hbs, act, use_prefix != 0);
   HIPCHK(c, hipSetDevice(c->device));
@@ -452,12 +461,25 @@ int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const
   struct Big { void* p = nullptr; ~Big() { if (p) (void)hipFree(p); } } big;     // caches beyond the op scratch: allocated for this call
   OpRun r(c, "dtk_op_attn_decode_b");
   AttnDecBArgs ad;
-  if (kv * 4 + ((size_t)8 << 20) > c->scratch_bytes) {
-    HIPCHK(c, hipMalloc(&big.p, kv * 4));
+  const size_t sh = kv8_from ? kv : 0;      // bytes of one shadow code plane (its scales: / 32)
+  if (kv * 4 + sh * 2 + sh / 16 + ((size_t)8 << 20) > c->scratch_bytes) {
+    HIPCHK(c, hipMalloc(&big.p, kv * 4 + sh * 2 + sh / 16));
     bf16_t* dK = (bf16_t*)big.p;
     ad.kcache = dK; ad.vcache = dK + kv;
     r.ins.push_back({dK, K, kv * 2}); r.ins.push_back({dK + kv, V, kv * 2});      // uploaded with the operands in the scratch
-  } else { ad.kcache = r.in<bf16_t>(K, kv); ad.vcache = r.in<bf16_t>(V, kv); }
+    if (kv8_from) {
+      ad.k8 = (uint8_t*)(dK + 2 * kv); ad.v8 = ad.k8 + sh; ad.k8s = ad.v8 + sh; ad.v8s = ad.k8s + sh / 32;
+      r.res.push_back({ad.k8, k8, sh, "k8", true}); r.res.push_back({ad.v8, v8, sh, "v8", true});
+      r.res.push_back({ad.k8s, k8s, sh / 32, "k8s", true}); r.res.push_back({ad.v8s, v8s, sh / 32, "v8s", true});
+    }
+  } else {
+    ad.kcache = r.in<bf16_t>(K, kv); ad.vcache = r.in<bf16_t>(V, kv);
+    if (kv8_from) {
+      ad.k8 = r.io<uint8_t>(k8, sh, "k8"); ad.v8 = r.io<uint8_t>(v8, sh, "v8");
+      ad.k8s = r.io<uint8_t>(k8s, sh / 32, "k8s"); ad.v8s = r.io<uint8_t>(v8s, sh / 32, "v8s");
+    }
+  }
+  ad.kv8_slot_stride = kv_slot;
   ad.q = r.in<bf16_t>(q, (size_t)nslots * d); ad.st = r.in<DecState>(hst.data(), nslots); ad.bs = r.in<BatchState>(&hbs, 1);
   ad.out = r.out<bf16_t>(frag.data(), out_elems, "out");
   ad.pfx_m = (float*)r.take(recs * 4); ad.pfx_l = (float*)r.take(recs * 4); ad.pfx_o = (float*)r.take(recs * 128 * 4);
@@ -470,9 +492,36 @@ int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const
   HIPCHK(c, hipMemsetAsync(ad.pfx_o, 0xFF, recs * 128 * 4, s));
   launch_attn_decode_b(ad, s);
   if (const int rc = r.finish(s)) return rc;
+  if (kv8_from) {      // the bf16 caches are the master copy: the KV8 kernels read them and must leave every byte as it was uploaded
+    std::vector<uint16_t> back(kv);
+    for (int w = 0; w < 2; ++w) {
+      HIPCHK(c, hipMemcpy(back.data(), w ? ad.vcache : ad.kcache, kv * 2, hipMemcpyDeviceToHost));
+      const uint16_t* src = w ? V : K;
+      if (memcmp(back.data(), src, kv * 2)) {
+        size_t i = 0;
+        while (back[i] == src[i]) ++i;
+        return fail(c, DTK_ERR_STATE, "%s: bf16 %s element %zu (slot %zu, row %zu) changed during the launch: %#x -> %#x", who, w ? "V" : "K", i,
+                    i / kv_slot, i % ((size_t)T_max * 128) / 128, (unsigned)src[i], (unsigned)back[i]);
+      }
+    }
+  }
   for (int j = 0; j < nslots; ++j)
     for (int k = 0; k < d; ++k) out[(size_t)j * d + k] = frag[host_xtile_off(j, k, nsteps)];
   return DTK_OK;
+}
+int dtk_op_attn_decode_b(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                         const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                         int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
+  return op_attn_decode_b(c, "dtk_op_attn_decode_b", q, K, V, nslots, H, KVH, T_max, pos, active, share_src, share_len, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, use_prefix, pfx_splits, tail_threads, gqa_fused, attn_nt, out);
+}
+int dtk_op_attn_decode_b8(dtk_ctx* c, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                          const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                          const int32_t* kv8_from, uint8_t* k8_codes, uint8_t* k8_scales, uint8_t* v8_codes, uint8_t* v8_scales,
+                          int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out) {
+  if (!kv8_from || !k8_codes || !k8_scales || !v8_codes || !v8_scales) return fail(c, DTK_ERR_ARG, "dtk_op_attn_decode_b8: null argument");
+  return op_attn_decode_b(c, "dtk_op_attn_decode_b8", q, K, V, nslots, H, KVH, T_max, pos, active, share_src, share_len, kv8_from, k8_codes,
+                          k8_scales, v8_codes, v8_scales, use_prefix, pfx_splits, tail_threads, gqa_fused, attn_nt, out);
 }
 
 // ---- the single-sequence decode GEMV family alone (dtk_op_gemv_role): one (prologue, epilogue, weight format, shape) of k_gemv on

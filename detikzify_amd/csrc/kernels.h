@@ -266,6 +266,10 @@ struct AttnDecBArgs {
   int nt_private = 0;        // k_attn_tail_b: non-temporal loads for key / value tiles beyond the shared prefix
   float* pfx_m; float* pfx_l; float* pfx_o;   // [slots][H][pfx_splits], ..., [slots][H][pfx_splits][128]: un-normalised prefix states
   uint8_t* out8 = nullptr; uint8_t* outs = nullptr;   // k_attn_tail_b: the head outputs as MXFP8 (groups of 32) instead of bf16 fragments
+  // MXFP8 shadow of the rows decode steps wrote (kv_format "mxfp8"; k8 == nullptr: none, the bf16 instantiations run): this layer's code
+  // planes [slot][KVH][T_max][128] and scale planes [slot][KVH][T_max][4] (E8M0, one per 32 dims), slot stride kv8_slot_stride code
+  // bytes (/ 32 scale bytes).  Rows [BatchState::kv8_from[slot], pos) are read from them, row pos is written to them.
+  uint8_t* k8 = nullptr; uint8_t* v8 = nullptr; uint8_t* k8s = nullptr; uint8_t* v8s = nullptr; size_t kv8_slot_stride = 0;
 };
 void launch_attn_decode_b(const AttnDecBArgs& a, hipStream_t s);
 

@@ -538,7 +538,16 @@ __global__ __launch_bounds__(64) void k_attn_prefix_g(AttnDecBArgs a) {
 // keys, the order of the online-softmax updates, the cross-lane and cross-wave merges — is exactly that of GQ = 1 (the compiler
 // contracts the multiply-adds differently in the two instantiations: equal to fp32 rounding, tested, not bit for bit); the key /
 // value traffic through L2 drops by GQ (ds-7b has no groups: GQ = 1).  A slot's result still does not depend on the other slots.
-template <int THREADS, int GQ = 1>
+//
+// KV8 (kv_format "mxfp8"): the rows that decode steps wrote are read from the MXFP8 shadow planes (AttnDecBArgs::k8 ...: 8 code bytes
+// per lane where the bf16 row has 16, plus the row's four E8M0 scales as one dword) and widened to the bf16 pairs the scoring code
+// takes by v_cvt_scalef32_pk_bf16_fp8 — code * 2^e, exact — so per head the arithmetic on the de-quantised rows is that of the bf16
+// kernel.  With from8 = kv8_from[slot] clamped into [share_len, pos]: rows below from8 are bf16 rows as before, rows [from8, pos) are
+// shadow rows, and row pos — written in bf16 by the step's q/k/v launch — is quantised in registers (mx_quant.h's quantiser), scored
+// from the widened codes like every later step will, and stored to the shadow by the first block of its kv head.  The three ranges are
+// walked one after the other (the bf16 walk of the parent with from8 for its end, then tiles of shadow rows that start at from8), so
+// the two register sets of one range are free when the next begins and no tile decides anything per row.
+template <int THREADS, int GQ = 1, bool KV8 = false>
 __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
   constexpr int WAVES = THREADS / 64, ROWS = WAVES * 16;
   const int h0 = blockIdx.x * GQ, slot = blockIdx.y;
@@ -553,6 +562,8 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
   const int ssrc = bs->share_src[slot], slen_raw = bs->share_len[slot];
   const int start = a.use_prefix ? bs->pfx_len_of[slot] : 0;       // keys [0, start) were scored by k_attn_prefix_g (0: none)
   const int n = a.st[slot].pos + 1;
+  int from_raw = 0;
+  if constexpr (KV8) from_raw = bs->kv8_from[slot];
   u32x4 qv[GQ];
 #pragma unroll
   for (int g = 0; g < GQ; ++g) qv[g] = reinterpret_cast<const u32x4*>(a.q + (size_t)slot * a.d + (h0 + g) * 128)[sub];
@@ -576,12 +587,16 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
   // alone, so what round 4 fetched there by clamping (up to 63 rows x 512 B per block: with 2048 blocks a tile that holds 4 real
   // keys cost 63 MB of HBM reads per layer, 13 us of a 19.5 us launch) was pure waste.
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
+  // KV8: the bf16 walk below ends at from8 (lim), rows [from8, n - 1) are shadow rows, row n - 1 is this step's own
+  const int from8 = KV8 ? min(max(from_raw, slen), n - 1) : 0;
+  const int lim = KV8 ? from8 : n;
+  const size_t r8 = KV8 ? (size_t)slot * a.kv8_slot_stride + (size_t)kvh * a.T_max * 128 : (size_t)0;
   auto load_tile = [&](u32x4 (&kk)[4], u32x4 (&vv)[4], int j0) {
     if (nt_ok && j0 >= slen) {      // block-uniform
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int j = j0 + i * (ROWS / 4) + wave * 4 + grp;
-        if (j < n) {
+        if (j < lim) {
           kk[i] = ld_nt(reinterpret_cast<const u32x4*>(kbase + (size_t)j * 128) + sub);
           vv[i] = ld_nt(reinterpret_cast<const u32x4*>(vbase + (size_t)j * 128) + sub);
         } else { kk[i] = zero4; vv[i] = zero4; }
@@ -591,15 +606,15 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int j = j0 + i * (ROWS / 4) + wave * 4 + grp;
-      if (j < n) {
+      if (j < lim) {
         const size_t off = (size_t)j * 128 + (j < slen ? sdelta : (size_t)0);
         kk[i] = reinterpret_cast<const u32x4*>(kbase + off)[sub];
         vv[i] = reinterpret_cast<const u32x4*>(vbase + off)[sub];
       } else { kk[i] = zero4; vv[i] = zero4; }
     }
   };
-  if (start < n) load_tile(kA, vA, start);
-  if (start + ROWS < n) load_tile(kB, vB, start + ROWS);
+  if (start < lim) load_tile(kA, vA, start);
+  if (start + ROWS < lim) load_tile(kB, vB, start + ROWS);
   float m[GQ], l[GQ], o[GQ][8];
 #pragma unroll
   for (int g = 0; g < GQ; ++g) {
@@ -637,6 +652,44 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
       }
     }
   }
+  // KV8: one widened row (kw, vw: 8 dims of it as bf16 pairs) against the block's queries — score_tile's steps for one row; the 16
+  // lanes of the row call it together.  A second copy of that body on purpose: with score_tile calling this lambda the GQ = 1 bf16
+  // instantiations came out with another schedule and register assignment than the parent's (same arithmetic), and the bf16 kernels
+  // are to stay instruction for instruction what they were.  Whoever changes one body changes the other.
+  auto score_row = [&](const u32x4& kw, const u32x4& vw, bool valid) {
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) {
+      float s = dot8(qv[g], kw, 0.f);
+      s += __shfl_xor(s, 1, 64);
+      s += __shfl_xor(s, 2, 64);
+      s += __shfl_xor(s, 4, 64);
+      s += __shfl_xor(s, 8, 64);
+      s *= a.scale;
+      if (valid) {
+        const float mn = fmaxf(m[g], s);
+        const float corr = __expf(m[g] - mn);
+        const float p = __expf(s - mn);
+        l[g] = l[g] * corr + p;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[g][2 * e] = o[g][2 * e] * corr + p * pk_lo(vw[e]);
+          o[g][2 * e + 1] = o[g][2 * e + 1] * corr + p * pk_hi(vw[e]);
+        }
+        m[g] = mn;
+      }
+    }
+  };
+  // 8 codes of a shadow row as the bf16 pairs of their de-quantised values: code * 2^e, e from the lane's byte of the row's scale dword
+  auto widen8 = [&](const u32x2& c, uint32_t sw) -> u32x4 {
+    const uint32_t sb = (sw >> ((sub >> 2) * 8)) & 0xffu;
+    const float sc = __uint_as_float(sb ? sb << 23 : 0x00400000u);      // 2^(sb - 127); sb = 0: 2^-127
+    u32x4 w;
+    w[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], sc, false));
+    w[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[0], sc, true));
+    w[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], sc, false));
+    w[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(c[1], sc, true));
+    return w;
+  };
   auto score_tile = [&](const u32x4 (&kc)[4], const u32x4 (&vc)[4], int j0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -649,7 +702,7 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
         s += __shfl_xor(s, 4, 64);
         s += __shfl_xor(s, 8, 64);
         s *= a.scale;
-        if (j < n) {
+        if (j < lim) {
           const float mn = fmaxf(m[g], s);
           const float corr = __expf(m[g] - mn);
           const float p = __expf(s - mn);
@@ -664,12 +717,84 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
       }
     }
   };
-  for (int j0 = start; j0 < n; j0 += 2 * ROWS) {
+  for (int j0 = start; j0 < lim; j0 += 2 * ROWS) {
     score_tile(kA, vA, j0);
-    if (j0 + 2 * ROWS < n) load_tile(kA, vA, j0 + 2 * ROWS);
-    if (j0 + ROWS < n) {
+    if (j0 + 2 * ROWS < lim) load_tile(kA, vA, j0 + 2 * ROWS);
+    if (j0 + ROWS < lim) {
       score_tile(kB, vB, j0 + ROWS);
-      if (j0 + 3 * ROWS < n) load_tile(kB, vB, j0 + 3 * ROWS);
+      if (j0 + 3 * ROWS < lim) load_tile(kB, vB, j0 + 3 * ROWS);
+    }
+  }
+  if constexpr (KV8) {
+    // The shadow rows [from8, n - 1), in tiles of their own that start at from8: the same ownership of rows by lanes, the same two
+    // tiles in flight; a row is 8 code bytes per lane and its scale dword, loaded non-temporally (shadow rows are private rows) and
+    // never at or beyond n - 1.
+    constexpr int R8 = 4, ROWS8 = R8 * WAVES * 4;
+    const int n8 = n - 1;
+    const uint8_t* k8c = a.k8 + r8;
+    const uint8_t* v8c = a.v8 + r8;
+    const uint32_t* k8s = reinterpret_cast<const uint32_t*>(a.k8s + (r8 >> 5));
+    const uint32_t* v8s = reinterpret_cast<const uint32_t*>(a.v8s + (r8 >> 5));
+    const u32x2 zero2 = {0u, 0u};
+    u32x2 ckA[R8], cvA[R8], ckB[R8], cvB[R8];
+    uint32_t skA[R8], svA[R8], skB[R8], svB[R8];
+    auto load_tile8 = [&](u32x2 (&ck)[R8], uint32_t (&sk)[R8], u32x2 (&cv)[R8], uint32_t (&sv)[R8], int j0) {
+#pragma unroll
+      for (int i = 0; i < R8; ++i) {
+        const int j = j0 + i * (ROWS8 / R8) + wave * 4 + grp;
+        if (j < n8) {
+          const u32x2* pk = reinterpret_cast<const u32x2*>(k8c + (size_t)j * 128) + sub;
+          const u32x2* pv = reinterpret_cast<const u32x2*>(v8c + (size_t)j * 128) + sub;
+          if (nt_ok) {
+            ck[i] = __builtin_nontemporal_load(pk); sk[i] = __builtin_nontemporal_load(k8s + j);
+            cv[i] = __builtin_nontemporal_load(pv); sv[i] = __builtin_nontemporal_load(v8s + j);
+          } else { ck[i] = *pk; sk[i] = k8s[j]; cv[i] = *pv; sv[i] = v8s[j]; }
+        } else { ck[i] = zero2; sk[i] = 0u; cv[i] = zero2; sv[i] = 0u; }
+      }
+    };
+    auto score_tile8 = [&](const u32x2 (&ck)[R8], const uint32_t (&sk)[R8], const u32x2 (&cv)[R8], const uint32_t (&sv)[R8], int j0) {
+#pragma unroll
+      for (int i = 0; i < R8; ++i) {
+        const int j = j0 + i * (ROWS8 / R8) + wave * 4 + grp;
+        score_row(widen8(ck[i], sk[i]), widen8(cv[i], sv[i]), j < n8);
+      }
+    };
+    // The step's own row n - 1 (a private row, just written in bf16: it is in L2) is requested first, by one 16-lane group of the
+    // block, then the first two shadow tiles; while those are in flight it is quantised as mx_quant.h's producers do (amax over the
+    // four lanes of a group of 32), stored by the first block of its kv head, and scored from the widened codes — the numbers every
+    // later step reads back.
+    const bool own_new = wave == 0 && grp == 0;
+    u32x4 nk = zero4, nv = zero4;
+    if (own_new) {
+      nk = reinterpret_cast<const u32x4*>(kbase + (size_t)n8 * 128)[sub];
+      nv = reinterpret_cast<const u32x4*>(vbase + (size_t)n8 * 128)[sub];
+    }
+    if (from8 < n8) load_tile8(ckA, skA, cvA, svA, from8);
+    if (from8 + ROWS8 < n8) load_tile8(ckB, skB, cvB, svB, from8 + ROWS8);
+    if (own_new) {
+      float ak = mx_amax8(nk), av = mx_amax8(nv);
+      ak = fmaxf(ak, __shfl_xor(ak, 1, 64)); av = fmaxf(av, __shfl_xor(av, 1, 64));
+      ak = fmaxf(ak, __shfl_xor(ak, 2, 64)); av = fmaxf(av, __shfl_xor(av, 2, 64));
+      const int ek = mx_exp(ak), ev = mx_exp(av);
+      const u32x2 ck = mx_cvt8(nk, mx_inv(ek)), cv = mx_cvt8(nv, mx_inv(ev));
+      if (h0 % a.G == 0) {
+        const size_t row = r8 + (size_t)n8 * 128;
+        *reinterpret_cast<u32x2*>(a.k8 + row + sub * 8) = ck;
+        *reinterpret_cast<u32x2*>(a.v8 + row + sub * 8) = cv;
+        if ((sub & 3) == 0) {
+          a.k8s[(row >> 5) + (sub >> 2)] = (uint8_t)(ek + 127);
+          a.v8s[(row >> 5) + (sub >> 2)] = (uint8_t)(ev + 127);
+        }
+      }
+      score_row(widen8(ck, (uint32_t)(ek + 127) * 0x01010101u), widen8(cv, (uint32_t)(ev + 127) * 0x01010101u), true);
+    }
+    for (int j0 = from8; j0 < n8; j0 += 2 * ROWS8) {
+      score_tile8(ckA, skA, cvA, svA, j0);
+      if (j0 + 2 * ROWS8 < n8) load_tile8(ckA, skA, cvA, svA, j0 + 2 * ROWS8);
+      if (j0 + ROWS8 < n8) {
+        score_tile8(ckB, skB, cvB, svB, j0 + ROWS8);
+        if (j0 + 3 * ROWS8 < n8) load_tile8(ckB, skB, cvB, svB, j0 + 3 * ROWS8);
+      }
     }
   }
 #pragma unroll
@@ -725,34 +850,41 @@ __global__ __launch_bounds__(THREADS) void k_attn_tail_b(AttnDecBArgs a) {
   }
 }
 
-void launch_attn_decode_b(const AttnDecBArgs& a, hipStream_t s) {
-  {   // shared prefixes once per group on the matrix cores (optional) + one block per (head, slot) for the private keys
-    if (a.use_prefix) hipLaunchKernelGGL(k_attn_prefix_g, dim3(a.H, DTK_PFX_GRID, a.pfx_splits), dim3(64), 0, s, a);
+// KV8: the instantiations that read and write the MXFP8 shadow (a.k8 set), one per block shape of the bf16 kernel
+template <bool KV8>
+static void launch_attn_tail_b(const AttnDecBArgs& a, hipStream_t s) {
+  {
     // one block shape for every slot count: a slot's result must not depend on how many column tiles the step has
     if (a.G == 4 && a.gqa_fused == 2) {   // pairs of query heads: half the sharing, twice the blocks
-      hipLaunchKernelGGL((k_attn_tail_b<256, 2>), dim3(a.H / 2, a.nslots), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((k_attn_tail_b<256, 2, KV8>), dim3(a.H / 2, a.nslots), dim3(256), 0, s, a);
       return;
     }
     if (a.G == 4 && a.gqa_fused) {   // GQA: the four query heads of a K / V head in one block (same arithmetic per head, a quarter of the K / V reads)
-      if (a.tail_threads == 64) hipLaunchKernelGGL((k_attn_tail_b<64, 4>), dim3(a.H / 4, a.nslots), dim3(64), 0, s, a);
-      else if (a.tail_threads == 128) hipLaunchKernelGGL((k_attn_tail_b<128, 4>), dim3(a.H / 4, a.nslots), dim3(128), 0, s, a);
-      else if (a.tail_threads == 512) hipLaunchKernelGGL((k_attn_tail_b<512, 4>), dim3(a.H / 4, a.nslots), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_tail_b<256, 4>), dim3(a.H / 4, a.nslots), dim3(256), 0, s, a);
+      if (a.tail_threads == 64) hipLaunchKernelGGL((k_attn_tail_b<64, 4, KV8>), dim3(a.H / 4, a.nslots), dim3(64), 0, s, a);
+      else if (a.tail_threads == 128) hipLaunchKernelGGL((k_attn_tail_b<128, 4, KV8>), dim3(a.H / 4, a.nslots), dim3(128), 0, s, a);
+      else if (a.tail_threads == 512) hipLaunchKernelGGL((k_attn_tail_b<512, 4, KV8>), dim3(a.H / 4, a.nslots), dim3(512), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_tail_b<256, 4, KV8>), dim3(a.H / 4, a.nslots), dim3(256), 0, s, a);
       return;
     }
     if (a.G == 2 && a.gqa_fused) {
-      if (a.tail_threads == 64) hipLaunchKernelGGL((k_attn_tail_b<64, 2>), dim3(a.H / 2, a.nslots), dim3(64), 0, s, a);
-      else if (a.tail_threads == 128) hipLaunchKernelGGL((k_attn_tail_b<128, 2>), dim3(a.H / 2, a.nslots), dim3(128), 0, s, a);
-      else hipLaunchKernelGGL((k_attn_tail_b<256, 2>), dim3(a.H / 2, a.nslots), dim3(256), 0, s, a);
+      if (a.tail_threads == 64) hipLaunchKernelGGL((k_attn_tail_b<64, 2, KV8>), dim3(a.H / 2, a.nslots), dim3(64), 0, s, a);
+      else if (a.tail_threads == 128) hipLaunchKernelGGL((k_attn_tail_b<128, 2, KV8>), dim3(a.H / 2, a.nslots), dim3(128), 0, s, a);
+      else hipLaunchKernelGGL((k_attn_tail_b<256, 2, KV8>), dim3(a.H / 2, a.nslots), dim3(256), 0, s, a);
       return;
     }
-    if (a.tail_threads == 64) hipLaunchKernelGGL(k_attn_tail_b<64>, dim3(a.H, a.nslots), dim3(64), 0, s, a);
-    else if (a.tail_threads == 128) hipLaunchKernelGGL(k_attn_tail_b<128>, dim3(a.H, a.nslots), dim3(128), 0, s, a);
-    else if (a.tail_threads == 256) hipLaunchKernelGGL(k_attn_tail_b<256>, dim3(a.H, a.nslots), dim3(256), 0, s, a);
-    else if (a.tail_threads == 1024) hipLaunchKernelGGL(k_attn_tail_b<1024>, dim3(a.H, a.nslots), dim3(1024), 0, s, a);   // multi-vector step: 256 keys per tile
-    else hipLaunchKernelGGL(k_attn_tail_b<512>, dim3(a.H, a.nslots), dim3(512), 0, s, a);
+    if (a.tail_threads == 64) hipLaunchKernelGGL((k_attn_tail_b<64, 1, KV8>), dim3(a.H, a.nslots), dim3(64), 0, s, a);
+    else if (a.tail_threads == 128) hipLaunchKernelGGL((k_attn_tail_b<128, 1, KV8>), dim3(a.H, a.nslots), dim3(128), 0, s, a);
+    else if (a.tail_threads == 256) hipLaunchKernelGGL((k_attn_tail_b<256, 1, KV8>), dim3(a.H, a.nslots), dim3(256), 0, s, a);
+    else if (a.tail_threads == 1024) hipLaunchKernelGGL((k_attn_tail_b<1024, 1, KV8>), dim3(a.H, a.nslots), dim3(1024), 0, s, a);   // multi-vector step: 256 keys per tile
+    else hipLaunchKernelGGL((k_attn_tail_b<512, 1, KV8>), dim3(a.H, a.nslots), dim3(512), 0, s, a);
     return;
   }
+}
+void launch_attn_decode_b(const AttnDecBArgs& a, hipStream_t s) {
+  // shared prefixes once per group on the matrix cores (optional) + one block per (head, slot) for the private keys
+  if (a.use_prefix) hipLaunchKernelGGL(k_attn_prefix_g, dim3(a.H, DTK_PFX_GRID, a.pfx_splits), dim3(64), 0, s, a);
+  if (a.k8) launch_attn_tail_b<true>(a, s);
+  else launch_attn_tail_b<false>(a, s);
 }
 
 // Row-major [N][K] bf16 -> fragment-major tiles (see the header): storage = ceil(N/16)*ceil(K/32) tiles

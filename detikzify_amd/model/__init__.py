@@ -52,7 +52,7 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
          synthetic: Optional[int] = None, device_map=None, torch_dtype=None, max_positions: Optional[int] = None,
          batch_slots: int = 0, weight_format: str = "bf16", synthetic_tokenizer: bool = False, vit_gelu_tanh: Optional[int] = None,
          adapter: Optional[bool] = None, embedding_model: Optional[str] = None, cross_attn_every_n_layers: Optional[int] = None,
-         **from_pretrained_kwargs) -> Tuple[DetikzifyForCausalLM, DetikzifyProcessor]:
+         kv_format: str = "bf16", **from_pretrained_kwargs) -> Tuple[DetikzifyForCausalLM, DetikzifyProcessor]:
     """(model, processor).  `device_map` may be an int GPU index (the reference passes
     device_map=RANK, examples/eval.py:112); torch_dtype must be bf16 / "auto" / None.
 
@@ -61,6 +61,12 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
     lm_head in fp8 and embedding / norms / tower / projector / adapter in bf16.  "mxfp4" is single-sequence decode only
     (batch_slots=0; anything else raises NotImplementedError).  Both lossy formats quantise on the device at load and overwrite the
     bf16 tensors with the de-quantised values, so prefill, score(), read_tensor() and the CPU oracle see the weights decode streams.
+
+    `kv_format`: "bf16" (default) or "mxfp8" (needs batch_slots > 0, else NotImplementedError; anything else raises ValueError).
+    With "mxfp8" the batched and multi-vector decode steps read the key/value rows that decode steps wrote as OCP MXFP8 (E4M3 codes +
+    one E8M0 scale per 32 dims: 132 bytes per head row instead of 256) from shadow planes kept beside the bf16 cache.  The bf16 cache
+    stays complete, so the format costs memory (+0.516 x a decoding slot's cache) and buys attention bandwidth at depth; prefill,
+    score(), forks and the single-sequence step keep reading bf16.  `model.kv8_from(slot)` reports from which row on a slot reads MXFP8.
 
     A checkpoint directory must carry its tokenizer files, as the reference's loader requires
     (v1/__init__.py:26-34 fails hard otherwise); `synthetic_tokenizer=True` (or `"synthetic_tokenizer": true` in the
@@ -83,7 +89,7 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
             cfg.max_positions = max_positions
         if vit_gelu_tanh is not None:
             cfg.vit_gelu_tanh = int(bool(vit_gelu_tanh))
-        cfg.batch_slots, cfg.weight_format = batch_slots, weight_format
+        cfg.batch_slots, cfg.weight_format, cfg.kv_format = batch_slots, weight_format, kv_format
         _require_supported(cfg)
         if synthetic_tokenizer or json.loads((path / "config.json").read_text()).get("synthetic_tokenizer"):
             tokenizer = _synthetic_tokenizer(cfg)
@@ -110,7 +116,7 @@ def load(model_name_or_path: str, modality_projector: Optional[str] = None, is_v
             cfg.max_positions = max_positions
         if vit_gelu_tanh is not None:
             cfg.vit_gelu_tanh = int(bool(vit_gelu_tanh))
-        cfg.batch_slots, cfg.weight_format = batch_slots, weight_format
+        cfg.batch_slots, cfg.weight_format, cfg.kv_format = batch_slots, weight_format, kv_format
         _require_supported(cfg)
         if synthetic is None:
             raise FileNotFoundError(
@@ -166,6 +172,12 @@ def _require_supported(cfg: DetikzifyConfig) -> None:
         raise NotImplementedError(
             f"{cfg.name_or_path or 'this checkpoint'}: weight_format='mxfp4' with batch_slots={cfg.batch_slots} — MXFP4 weights have no "
             "batched-slot or multi-vector kernels yet (they stream in single-sequence decode only: load with batch_slots=0)")
+    if cfg.kv_format not in ("bf16", "mxfp8"):
+        raise ValueError(f"kv_format={cfg.kv_format!r}: 'bf16' or 'mxfp8'")
+    if cfg.kv_format == "mxfp8" and cfg.batch_slots <= 0:
+        raise NotImplementedError(
+            f"{cfg.name_or_path or 'this checkpoint'}: kv_format='mxfp8' with batch_slots={cfg.batch_slots} — only the batched and "
+            "multi-vector decode steps read MXFP8 key/value rows (the single-sequence step has no such kernel: load with batch_slots > 0)")
     if cfg.concat_patches < 1 or ((cfg.vit_image // cfg.vit_patch) ** 2) % cfg.concat_patches:
         raise ValueError(f"concat_patches={cfg.concat_patches} does not divide the tower's {(cfg.vit_image // cfg.vit_patch) ** 2} patches")
 

@@ -52,6 +52,8 @@ class DetikzifyConfig:
     batch_slots: int = 0             # KV slots for batched decode of independent rollouts (0 = none)
     weight_format: str = "bf16"      # "bf16" | "fp8" (e4m3 decoder Linear weights, per-row 2^e scales) | "mxfp4" (OCP MXFP4 layer weights:
                                      # E2M1 codes + an E8M0 scale per 32 weights along K; lm_head fp8; batch_slots = 0 only)
+    kv_format: str = "bf16"          # "bf16" | "mxfp8" (the batched decode steps read the rows decode steps wrote as OCP MXFP8 from shadow
+                                     # planes beside the bf16 cache: more memory, less attention traffic; batch_slots > 0 only)
     model_type: str = "detikzify"
     name_or_path: str = ""
     vision_tower: str = "vit_so400m_patch14_siglip_384.webli"

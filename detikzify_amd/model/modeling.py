@@ -487,6 +487,7 @@ class DetikzifyForCausalLM:
         cc.reserved[1] = {"fp8": 1, "mxfp4": 2}.get(getattr(config, "weight_format", "bf16"), 0)
         cc.reserved[2] = int(getattr(config, "kv_heads", 0) or 0)                       # GQA (v2)
         cc.reserved[3] = 0 if getattr(config, "proj_bias", True) else _lib.DTK_ARCH_PROJ_NO_BIAS
+        cc.reserved[4] = {"bf16": 0, "mxfp8": 1}[getattr(config, "kv_format", "bf16")]   # key/value rows of decoded tokens
         ctx = C.c_void_p()
         rc = self.lib.dtk_create(C.byref(cc), self.hip_device, C.byref(ctx))
         if rc != 0:
@@ -1215,6 +1216,29 @@ class DetikzifyForCausalLM:
 
     def context_len_slot(self, slot: int) -> int:
         return int(self.lib.dtk_context_len_slot(self._ctx, int(slot)))
+
+    @property
+    def kv_format(self) -> str:
+        """ "bf16" or "mxfp8": the format in which the batched decode steps read the rows that decode steps wrote (load(kv_format=))"""
+        return getattr(self.config, "kv_format", "bf16")
+
+    def kv8_from(self, slot: int) -> int:
+        """kv_format "mxfp8": the first row of the slot that its decode steps read as MXFP8 (the rows below it are prefill or forked
+        rows and exist in bf16 only).  A bf16 context raises DtkError."""
+        out = C.c_int(0)
+        self._check(self.lib.dtk_kv8_info(self._ctx, int(slot), C.byref(out)), "dtk_kv8_info")
+        return int(out.value)
+
+    def read_kv8(self, slot: int, layer: int, which: int, row0: int, nrows: int):
+        """diagnostic (kv_format "mxfp8"): (codes uint8 [KVH, nrows, 128], scales uint8 [KVH, nrows, 4], bf16 rows [KVH, nrows, 128]) of
+        rows [row0, row0 + nrows) of a layer's keys (which = 0) or values (1) in a decoding slot"""
+        kvh = int(getattr(self.config, "kv_heads", 0) or 0) or int(self.config.heads)
+        codes = torch.empty(kvh, nrows, 128, dtype=torch.uint8)
+        scales = torch.empty(kvh, nrows, 4, dtype=torch.uint8)
+        rows = torch.empty(kvh, nrows, 128, dtype=torch.int16)
+        self._check(self.lib.dtk_read_kv8(self._ctx, int(slot), int(layer), int(which), int(row0), int(nrows),
+                                          C.c_void_p(codes.data_ptr()), C.c_void_p(scales.data_ptr()), C.c_void_p(rows.data_ptr())), "dtk_read_kv8")
+        return codes, scales, rows.view(torch.bfloat16)
 
     def decode_launch(self):
         self._check(self.lib.dtk_decode_launch(self._ctx), "dtk_decode_launch")

@@ -78,7 +78,14 @@ typedef struct dtk_config {
                             *       lm_head; single-sequence decode only: with [0] > 0 dtk_create fails with DTK_ERR_ARG.  Quantised on the
                             *       device at load; the bf16 tensors are overwritten with the de-quantised (effective) weights
                             * [2] = key/value heads (GQA, num_key_value_heads); 0 = heads (MHA, all v1 models)
-                            * [3] = architecture flags, DTK_ARCH_*                        */
+                            * [3] = architecture flags, DTK_ARCH_*
+                            * [4] = key/value row format of the batched and multi-vector decode steps: 0 = bf16; 1 = the rows that DECODE STEPS
+                            *       wrote are also kept as OCP MXFP8 (E4M3 codes + one E8M0 scale per 32 dims of a head's row: 132 bytes where the
+                            *       bf16 row has 256) in shadow planes that only the batched attention kernel writes, and those steps read them
+                            *       from there.  The bf16 cache stays the master of every row and every other reader (prefill, scoring, forks,
+                            *       the single-sequence step, dtk_read_tensor) keeps reading it: the format COSTS memory (+0.516 x the bf16 cache
+                            *       of every decoding slot) and buys attention bandwidth.  Needs [0] > 0; any other value, or 1 with [0] == 0,
+                            *       fails dtk_create with DTK_ERR_ARG before anything is allocated.  See dtk_kv8_info.              */
 } dtk_config;
 /* v2 connector (reference detikzify/model/modeling_detikzify.py:62-70): Linear(concat*D -> d, bias=False) */
 #define DTK_ARCH_PROJ_NO_BIAS 1
@@ -272,6 +279,20 @@ int  dtk_resume_slot(dtk_ctx* ctx, int slot, const int64_t* ids, int n_tokens, u
 int  dtk_slot_cached_ids(dtk_ctx* ctx, int slot, int64_t* ids_out, int n_max);   /* diagnostic: what the slot's cache holds; returns the count */
 int  dtk_get_logits_slot(dtk_ctx* ctx, int slot, float* logits_out);
 int  dtk_context_len_slot(const dtk_ctx* ctx, int slot);
+/* kv_format mxfp8 (dtk_config.reserved[4] = 1; additive, ABI 7).  Every slot has a boundary kv8_from: a batched step of the slot at
+ * position pos reads rows [.., kv8_from) in bf16 as a bf16 context does and rows [kv8_from, pos) from the shadow; row pos, which the
+ * step's q/k/v launch has just written in bf16, is quantised by the attention kernel (groups of 32 dims: e = the smallest exponent with
+ * amax * 2^-e <= 448, codes = e4m3(x * 2^-e) — oracle.llama.mx_quantise bit for bit), scored from the de-quantised values code * 2^e,
+ * and stored, so a row contributes the same numbers in the step that writes it and in every later one.  The boundary is set to the
+ * slot's new length by every prefill into it (with prefix reuse too: all of [0, T) then counts as prefill rows) and to n_tokens by
+ * dtk_kv_fork for the destination (nothing of the shadow is copied: shared rows are bf16 rows); dtk_resume_slot replaces it by
+ * min(kv8_from, T - 1), so the rows the slot decoded earlier and keeps stay MXFP8 rows.
+ *   dtk_kv8_info: the slot's boundary; DTK_ERR_STATE in a bf16 context.
+ *   dtk_read_kv8: diagnostic — rows [row0, row0 + nrows) of layer `layer`, which = 0 keys | 1 values, of a decoding slot, all kv heads:
+ *                 codes_out [KVH][nrows][128], scales_out [KVH][nrows][4] (E8M0) and the bf16 rows beside them bf16_out [KVH][nrows][128];
+ *                 any of the three may be NULL.  Shadow rows no step has written hold 0xFF.  Waits for the launched steps. */
+int  dtk_kv8_info(dtk_ctx* ctx, int slot, int* from_out);
+int  dtk_read_kv8(dtk_ctx* ctx, int slot, int layer, int which, int row0, int nrows, uint8_t* codes_out, uint8_t* scales_out, uint16_t* bf16_out);
 
 int  dtk_max_positions(const dtk_ctx* ctx);               /* KV capacity of a sequence in tokens (dtk_config.max_positions) */
 
@@ -571,6 +592,16 @@ int  dtk_op_attn_decode(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, cons
 int  dtk_op_attn_decode_b(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
                           const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
                           int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out);
+/* dtk_op_attn_decode_b8 (additive, ABI 7): the same launch through the instantiations of a kv_format-mxfp8 context.  kv8_from[nslots]
+ * (share_len <= kv8_from <= pos for active slots) and the four shadow planes, IN/OUT host arrays: codes [nslots][KVH][T_max][128] and
+ * E8M0 scales [nslots][KVH][T_max][4] for K and for V.  Rows [kv8_from, pos) of an active slot are read from them (code * 2^(scale - 127));
+ * row pos is read in bf16, quantised, scored de-quantised, and its codes and scales are stored — by exactly one block per (slot, kv head).
+ * Nothing else of the planes is written: they come back as they went in but for those rows.  After the launch the op reads the bf16 K
+ * and V back and compares them with the caller's arrays: a changed byte fails the call with DTK_ERR_STATE (the first element is named). */
+int  dtk_op_attn_decode_b8(dtk_ctx* ctx, const uint16_t* q, const uint16_t* K, const uint16_t* V, int nslots, int H, int KVH, int T_max,
+                           const int32_t* pos, const int32_t* active, const int32_t* share_src, const int32_t* share_len,
+                           const int32_t* kv8_from, uint8_t* k8_codes, uint8_t* k8_scales, uint8_t* v8_codes, uint8_t* v8_scales,
+                           int use_prefix, int pfx_splits, int tail_threads, int gqa_fused, int attn_nt, uint16_t* out);
 /* The weight kernels of the batched (<= 64 slot) decode step alone, op by op (additive, ABI 7); bf16 bits throughout.
  * dtk_op_gemv_b: one role through the step's dispatcher; the process-wide options ("gemv_bx", "gemv_bl", "gemv_bc", "gemv_bus",
  * "gemv_b_wide", "resid_split", "gemv_br_wd", "gemv_loaders", "gemv_xw") choose the kernel as they do in the step.  epi: 0 STORE,
