@@ -106,6 +106,12 @@ class DtkJoin(C.Structure):
     ]
 
 
+class DtkGuided(C.Structure):
+    """dtk_guided: a guided sequence for dtk_engine_submit_guided — the sequence's join, the negative branch's plan and text, the scale"""
+    _fields_ = [("cond", C.POINTER(DtkJoin)), ("uncond", C.POINTER(DtkJoin)), ("uncond_text_ids", C.c_void_p),
+                ("n_uncond_text", C.c_int32), ("scale", C.c_float), ("uncond_text_key", C.c_uint64)]
+
+
 class DtkEngineStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("steps", "tokens_out", "joins", "resumed", "steps_below_half_occupancy", "host_bound_steps",
                                           "reader_wakeups", "wasted_slot_steps")] + \
@@ -139,6 +145,8 @@ class DtkEngineOps(C.Structure):
     # not fields: dtk_engine_set_length_control_op's (dev, slot, ctl) and dtk_engine_set_logit_bias_op's (dev, slot, ids, values, n)
     LENGTH_CTL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkLengthCtl))
     LOGIT_BIAS = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int)
+    # not a field: dtk_engine_set_guidance_op's argument (dev, cond_slot, uncond_slot, scale)
+    GUIDANCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float)
     _fields_ = [
         ("dev", C.c_void_p), ("launch", LAUNCH), ("wait", WAIT), ("prefill_slot", PREFILL), ("set_sampling_slot", SAMPLING),
         ("kv_fork", FORK), ("slot_lcp", LCP), ("resume_slot", RESUME), ("context_len_slot", CTXLEN), ("last_error", LASTERR),
@@ -331,6 +339,12 @@ SYMBOLS = {
     "dtk_get_guidance": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "dtk_op_cfg_mix": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_float)]),
     "dtk_bench_cfg": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    "dtk_reserve_guidance": (C.c_int, [_P, C.c_int]),
+    "dtk_batch_graph_captures": (C.c_int64, [_P]),
+    "dtk_engine_submit_guided": (C.c_int, [_P, C.POINTER(DtkGuided), C.POINTER(DtkSamplingExt), C.c_float, C.c_float, C.c_int, C.POINTER(DtkDry),
+                                           C.POINTER(DtkLengthCtl), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                           C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dtk_engine_set_guidance_op": (C.c_int, [_P, DtkEngineOps.GUIDANCE]),
 }
 
 _lib = None

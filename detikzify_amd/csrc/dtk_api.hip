@@ -611,17 +611,19 @@ static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
 // dtk_set_guidance: the batched step of a context with guided pairs mixes each pair's two pending logits rows into the conditional
 // one in front of everything that reads it (guidance_launch), and hands the chosen token to the unconditional slot behind the sampler
 // (follow_launch).  A context without a pair: both return at once, the step launches what it launched before
+// The pair dimension of the three kernels' grids: the reservation (dtk_reserve_guidance) while the live pairs fit it, else their count
+static inline int cfg_grid(const dtk_ctx* c) { return c->cfg_res > c->cfg_n ? c->cfg_res : c->cfg_n; }
 static void guidance_launch(dtk_ctx* c, const SampleArgs& sa) {
-  if (!c->cfg_n) return;
+  if (!cfg_grid(c)) return;
   CfgArgs g;
-  g.logits = const_cast<float*>(sa.logits); g.V = sa.V; g.stride = sa.logits_stride; g.pairs = c->cfg_dev; g.n_pairs = c->cfg_n; g.bs = sa.bs;
-  g.part = c->cfg_part; g.lse = c->cfg_lse;
+  g.logits = const_cast<float*>(sa.logits); g.V = sa.V; g.stride = sa.logits_stride; g.pairs = c->cfg_dev; g.n_pairs = cfg_grid(c); g.bs = sa.bs;
+  g.part = c->cfg_part; g.lse = c->cfg_lse; g.st = sa.st; g.forced = c->cfg_forced;
   launch_cfg_mix(g, c->stream);
 }
 static void follow_launch(dtk_ctx* c, const SampleArgs& sa) {
-  if (!c->cfg_n) return;
+  if (!cfg_grid(c)) return;
   CfgFollowArgs f;
-  f.pairs = c->cfg_dev; f.n_pairs = c->cfg_n; f.bs = sa.bs; f.st = sa.st; f.x = sa.x; f.d = sa.d; f.tok_ring = sa.tok_ring; f.ring = sa.ring;
+  f.pairs = c->cfg_dev; f.n_pairs = cfg_grid(c); f.bs = sa.bs; f.forced = c->cfg_forced; f.st = sa.st; f.x = sa.x; f.d = sa.d; f.tok_ring = sa.tok_ring; f.ring = sa.ring;
   f.lp_ring = sa.lp_ring; f.lse_ring = sa.lse_ring; f.top_ring = (c->logprobs && c->top_logprobs) ? c->topb_dev : nullptr;
   launch_cfg_follow(f, c->stream);
 }
@@ -1106,6 +1108,7 @@ int ensure_batch_graph(dtk_ctx* c) {   // for c->nt_step / c->mv_step
   }
   HIPCHK(c, hipGraphInstantiate(&c->bgraph_exec[gi], c->bgraph[gi], nullptr, nullptr, 0));
   c->bgraph_ready[gi] = true;
+  c->bgraph_captures++;
   return DTK_OK;
 }
 
@@ -1507,6 +1510,7 @@ int dtk_abi_struct_size(int which) {
     case 12: return (int)sizeof(dtk_sampling_ext);
     case 14: return (int)sizeof(dtk_dry);      // (13 stays unassigned: -1)
     case 16: return (int)sizeof(dtk_length_ctl);      // (15 stays unassigned too)
+    case 18: return (int)sizeof(dtk_guided);          // (and 17)
     default: return -1;
   }
 }
@@ -1733,6 +1737,7 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->cfg_dev) (void)hipFree(c->cfg_dev);
   if (c->cfg_part) (void)hipFree(c->cfg_part);
   if (c->cfg_lse) (void)hipFree(c->cfg_lse);
+  if (c->cfg_forced) (void)hipFree(c->cfg_forced);
   if (c->top_ring_host) (void)hipHostFree(c->top_ring_host);
   if (c->lse_ring_host) (void)hipHostFree(c->lse_ring_host);
   if (c->topb_host) (void)hipHostFree(c->topb_host);
@@ -2648,6 +2653,26 @@ static int cfg_find(const dtk_ctx* c, int slot) {      // the pair `slot` belong
     if (c->cfg_pairs[p].cond == slot || c->cfg_pairs[p].uncond == slot) return p;
   return -1;
 }
+// the device table and the scratch: every buffer on its own, so a call that failed part-way is completed by the next one
+static int cfg_alloc(dtk_ctx* c) {
+  const size_t np = DTK_MAX_BATCH / 2;
+  if (!c->cfg_dev) HIPCHK(c, hipMalloc(&c->cfg_dev, sizeof(CfgPair) * np));
+  if (!c->cfg_part) HIPCHK(c, hipMalloc(&c->cfg_part, sizeof(float2) * np * 2 * DTK_CFG_MAX_SLICES));
+  if (!c->cfg_lse) { HIPCHK(c, hipMalloc(&c->cfg_lse, sizeof(float2) * np)); HIPCHK(c, hipMemset(c->cfg_lse, 0, sizeof(float2) * np)); }
+  if (!c->cfg_forced) { HIPCHK(c, hipMalloc(&c->cfg_forced, sizeof(int32_t) * np)); HIPCHK(c, hipMemset(c->cfg_forced, 0, sizeof(int32_t) * np)); }
+  return DTK_OK;
+}
+// next[0, n) become the pairs, on the host and (where the table exists) on the device; every other entry is unused (cond < 0)
+static int cfg_upload(dtk_ctx* c, CfgPair* next, int n) {
+  for (int p = n; p < DTK_MAX_BATCH / 2; ++p) next[p] = CfgPair{-1, -1, 1.f, 0};
+  if (c->cfg_dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // (no step is in flight; a direct-launch step of before may still read the table)
+    HIPCHK(c, hipMemcpy(c->cfg_dev, next, sizeof(CfgPair) * (DTK_MAX_BATCH / 2), hipMemcpyHostToDevice));
+  }
+  memcpy(c->cfg_pairs, next, sizeof(CfgPair) * (DTK_MAX_BATCH / 2));
+  c->cfg_n = n;
+  return DTK_OK;
+}
 int dtk_set_guidance(dtk_ctx* c, int cond_slot, int uncond_slot, float scale) {
   if (!c) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: null context");
   if (c->nb <= 0) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: the context was created without batch slots");
@@ -2680,21 +2705,37 @@ int dtk_set_guidance(dtk_ctx* c, int cond_slot, int uncond_slot, float scale) {
     }
   }
   HIPCHK(c, hipSetDevice(c->device));
-  if (n) {      // every buffer on its own: a call that failed part-way is completed by the next one
-    const size_t np = DTK_MAX_BATCH / 2;
-    if (!c->cfg_dev) HIPCHK(c, hipMalloc(&c->cfg_dev, sizeof(CfgPair) * np));
-    if (!c->cfg_part) HIPCHK(c, hipMalloc(&c->cfg_part, sizeof(float2) * np * 2 * DTK_CFG_MAX_SLICES));
-    if (!c->cfg_lse) { HIPCHK(c, hipMalloc(&c->cfg_lse, sizeof(float2) * np)); HIPCHK(c, hipMemset(c->cfg_lse, 0, sizeof(float2) * np)); }
-  }
-  if (c->cfg_dev) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));      // (no step is in flight; a direct-launch step of before may still read the table)
-    HIPCHK(c, hipMemcpy(c->cfg_dev, next, sizeof next, hipMemcpyHostToDevice));
-  }
-  memcpy(c->cfg_pairs, next, sizeof next);
-  c->cfg_n = n;
-  drop_batch_graphs(c);      // the captured steps hold the pair count (the grid) and whether the kernels run at all
+  if (n) if (const int rc = cfg_alloc(c)) return rc;
+  const int grid_was = cfg_grid(c);
+  if (const int rc = cfg_upload(c, next, n)) return rc;
+  // the captured steps hold the pair dimension of the grid and whether the kernels run at all.  Standing pairs (dtk_reserve_guidance)
+  // that still fit: neither changed, the captures go on reading the table
+  if (!c->cfg_res || cfg_grid(c) != grid_was) drop_batch_graphs(c);
   return DTK_OK;
 }
+
+int dtk_reserve_guidance(dtk_ctx* c, int n_pairs) {
+  if (!c) return fail(c, DTK_ERR_ARG, "dtk_reserve_guidance: null context");
+  if (c->nb <= 0) return fail(c, DTK_ERR_ARG, "dtk_reserve_guidance: the context was created without batch slots");
+  if (n_pairs < 0 || n_pairs > DTK_MAX_BATCH / 2) return fail(c, DTK_ERR_ARG, "dtk_reserve_guidance: %d pairs is outside 0..%d", n_pairs, DTK_MAX_BATCH / 2);
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_reserve_guidance: a batch step is in flight");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n_pairs) if (const int rc = cfg_alloc(c)) return rc;
+  const int grid_was = cfg_grid(c);
+  c->cfg_res = n_pairs;
+  CfgPair next[DTK_MAX_BATCH / 2];
+  memcpy(next, c->cfg_pairs, sizeof next);
+  if (const int rc = cfg_upload(c, next, c->cfg_n)) return rc;
+  if (cfg_grid(c) != grid_was) drop_batch_graphs(c);
+  if (!cfg_grid(c)) {      // 0 with no live pair: the table goes back (cfg_upload has waited for the stream)
+    if (c->cfg_dev) { (void)hipFree(c->cfg_dev); c->cfg_dev = nullptr; }
+    if (c->cfg_part) { (void)hipFree(c->cfg_part); c->cfg_part = nullptr; }
+    if (c->cfg_lse) { (void)hipFree(c->cfg_lse); c->cfg_lse = nullptr; }
+    if (c->cfg_forced) { (void)hipFree(c->cfg_forced); c->cfg_forced = nullptr; }
+  }
+  return DTK_OK;
+}
+int64_t dtk_batch_graph_captures(const dtk_ctx* c) { return c ? c->bgraph_captures : 0; }
 
 // diagnostic: the pair `slot` is in.  partner -1 = none (is_cond 0, scale 1, lse NaN); lse_out[2] = (Lc, Lu) of the pair's last step
 int dtk_get_guidance(dtk_ctx* c, int slot, int* partner_out, int* is_cond_out, float* scale_out, float* lse_out) {
@@ -2767,6 +2808,10 @@ int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
     if ((active[gp.cond] != 0) != (active[gp.uncond] != 0))
       return fail(c, DTK_ERR_ARG, "dtk_decode_batch_launch: guided pair (%d, %d): slot %d is active without slot %d (dtk_set_guidance pairs them; both or neither take part in a step)",
                   gp.cond, gp.uncond, active[gp.cond] ? gp.cond : gp.uncond, active[gp.cond] ? gp.uncond : gp.cond);
+    const bool fc = c->bseq[(size_t)gp.cond].forced_pending >= 0, fu = c->bseq[(size_t)gp.uncond].forced_pending >= 0;
+    if (active[gp.cond] && fc != fu)      // one slot would forward its last prompt token while the other one samples: the rows would not belong together
+      return fail(c, DTK_ERR_ARG, "dtk_decode_batch_launch: guided pair (%d, %d): slot %d was resumed (dtk_resume_slot) and forwards its last prompt token in this step, slot %d does not; resume both slots or prefill both",
+                  gp.cond, gp.uncond, fc ? gp.cond : gp.uncond, fc ? gp.uncond : gp.cond);
   }
   HIPCHK(c, hipSetDevice(c->device));
   ensure_tiled_weights(c);

@@ -316,10 +316,15 @@ struct dtk_ctx {
   // classifier-free guidance (dtk_set_guidance): disjoint pairs of decoding slots.  cfg_n == 0: guidance_launch / follow_launch return
   // at once and the step launches what it launched before the feature existed.  The device table and the scratch are allocated by the
   // first call that forms a pair (hipMalloc of their own), so a context that never uses guidance allocates nothing.  Static for a
-  // sequence, as length control: only dtk_set_guidance changes the table, and every change drops the captured batch steps
+  // sequence, as length control: only dtk_set_guidance changes the table, and every change drops the captured batch steps — unless
+  // dtk_reserve_guidance made the pairs standing: the three kernels then launch with cfg_res as their pair dimension whatever cfg_n is
+  // (cfg_grid), entries [cfg_n, cfg_res) of the device table have cond = -1, and a change that fits only rewrites the table
   CfgPair cfg_pairs[DTK_MAX_BATCH / 2] = {};   // the pairs as set, [0, cfg_n)
   int cfg_n = 0;
+  int cfg_res = 0;                   // dtk_reserve_guidance: pairs the captured steps are shaped for (0: none reserved, the grid is cfg_n)
+  int64_t bgraph_captures = 0;       // captures of a batched step since creation (dtk_batch_graph_captures)
   CfgPair* cfg_dev = nullptr;        // [DTK_MAX_BATCH / 2]
+  int32_t* cfg_forced = nullptr;     // [DTK_MAX_BATCH / 2] 1: the pair forwarded forced tokens in the last step (k_cfg_lse -> k_cfg_follow)
   float2* cfg_part = nullptr;        // [DTK_MAX_BATCH / 2][2][DTK_CFG_MAX_SLICES]
   float2* cfg_lse = nullptr;         // [DTK_MAX_BATCH / 2] (Lc, Lu) of the last step
   uint64_t launched = 0, waited = 0;

@@ -18,6 +18,7 @@
 // through the text prefill, so a slot never mixes KV of the same pixels under another text (or none).
 // A slot's arithmetic never depends on its company (csrc/dtk_api.hip), so which steps a sequence shares with which others —
 // the only thing this loop decides differently from the Python engine it replaces — does not change a token.
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <cmath>
@@ -52,11 +53,18 @@ struct Seq {
   int n_stop = 0;
   int64_t stop[8] = {};
   int flush_mode = 0, flush_max = 64;
+  int pair = -1;                    // a guided sequence (dtk_engine_submit_guided): the other slot of the pair, -1 otherwise
+  bool follower = false;            // ... and this is its unconditional slot: stepped with slot `pair`, never delivered
   std::condition_variable cv;
 };
 
 struct Cmd {
   dtk_join* join = nullptr;
+  dtk_join* uncond = nullptr;       // a guided sequence: the negative branch's plan, its own text and the scale
+  const int64_t* utext = nullptr;
+  int n_utext = 0;
+  uint64_t utext_key = 0;
+  float scale = 1.f;
   const int64_t* text = nullptr;    // the join's text ids (caller-owned until awaited), nullptr: an image-only join
   int n_text = 0;
   uint64_t text_key = 0;
@@ -84,6 +92,7 @@ using PenaltiesFn = int (*)(void* dev, int slot, float presence, float frequency
 using DryFn = int (*)(void* dev, int slot, const dtk_dry* d);
 using LenFn = int (*)(void* dev, int slot, const dtk_length_ctl* l);
 using BiasFn = int (*)(void* dev, int slot, const int32_t* ids, const float* values, int n);
+using GuidanceFn = int (*)(void* dev, int cond_slot, int uncond_slot, float scale);
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
@@ -96,6 +105,9 @@ struct dtk_engine {
   DryFn dry = nullptr;                      // dtk_engine_set_dry_op (dtk_engine_create: dtk_set_dry_slot)
   LenFn length_control = nullptr;           // dtk_engine_set_length_control_op (dtk_engine_create: dtk_set_length_control_slot)
   BiasFn logit_bias = nullptr;              // dtk_engine_set_logit_bias_op (dtk_engine_create: dtk_set_logit_bias_slot)
+  GuidanceFn guidance = nullptr;            // dtk_engine_set_guidance_op (dtk_engine_create: dtk_set_guidance)
+  int dev_pair[DTK_MAX_BATCH];              // the pairs this engine has set on the device: the partner of a slot, -1 = none ...
+  bool dev_cond[DTK_MAX_BATCH] = {};        // ... and whether the slot heads its pair (only the loop's thread touches the two)
   dtk_ctx* own_ctx = nullptr;               // dtk_engine_create: the context, whose "logprobs" option decides which wait collects
   std::mutex mu;
   std::condition_variable cv_run;
@@ -113,6 +125,7 @@ struct dtk_engine {
   int err_rc = 0;
   std::string err;
   double idle_from = -1.0;      // since when sequences are decoding with no step in flight (< 0: not the case)
+  dtk_engine() { for (int& p : dev_pair) p = -1; }
 };
 
 namespace {
@@ -137,11 +150,19 @@ void poison(dtk_engine* e, int rc) {
   for (Seq& q : e->seq) { q.decoding = false; q.cv.notify_all(); }
 }
 
+// the loop itself found the device's results inconsistent
+void poison_text(dtk_engine* e, int rc, const char* text) {
+  if (e->err_rc) return;
+  poison(e, rc);
+  e->err = text;
+}
+
 int launch_set(dtk_engine* e, ActiveSet& set) {
   int n = 0;
   for (int s = 0; s < DTK_MAX_BATCH; ++s) {
     Seq& q = e->seq[s];
-    set[s] = (q.decoding && q.launched < q.need) ? 1 : 0;
+    const Seq& lead = q.follower ? e->seq[q.pair] : q;      // a pair steps together or not at all: the follower copies its leader
+    set[s] = (q.decoding && lead.decoding && lead.launched < lead.need) ? 1 : 0;
     n += set[s];
   }
   return n;
@@ -184,9 +205,18 @@ void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
   for (int s = 0; s < DTK_MAX_BATCH; ++s) {
     if (!set[s]) continue;
     Seq& q = e->seq[s];
-    if (!q.decoding) { e->st.wasted_slot_steps++; continue; }     // ended (stop id) or left while this step was in flight
-    if (q.skip) { q.skip = 0; continue; }
+    if (q.follower) continue;                                    // handled with its leader
+    Seq* f = q.pair >= 0 ? &e->seq[q.pair] : nullptr;
+    if (!q.decoding) { e->st.wasted_slot_steps += f ? 2 : 1; continue; }     // ended (stop id) or left while this step was in flight (a pair: both slots)
+    if (q.skip) { q.skip = 0; if (f) f->skip = 0; continue; }
     const int64_t tok = toks[s];
+    if (f && toks[q.pair] != tok) {      // k_cfg_follow hands the leader's token over: anything else means the pair's caches have parted
+      char text[200];
+      snprintf(text, sizeof text, "guided pair (%d, %d): the unconditional slot reported token %lld, the conditional slot %lld (step %llu)",
+               s, q.pair, (long long)toks[q.pair], (long long)tok, (unsigned long long)e->st.steps);
+      poison_text(e, DTK_ERR_STATE, text);
+      return;
+    }
     q.toks.push_back(tok);
     if (wait_lp) {      // (an op given mid-sequence: the earlier tokens' pairs are NaN)
       q.lp.resize(q.toks.size() - 1, NAN); q.slp.resize(q.toks.size() - 1, NAN);
@@ -201,6 +231,7 @@ void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
       q.state = DTK_SEQ_FINISHED;
       q.flushed = q.toks.size();
       q.cv.notify_all();
+      if (f) { f->decoding = false; f->state = DTK_SEQ_FINISHED; }
     } else if (q.flush_mode == 0 || (tok >= 0 && (size_t)tok < e->flush_tok.size() && e->flush_tok[(size_t)tok]) ||
                q.toks.size() - q.flushed >= (size_t)q.flush_max) {
       q.flushed = q.toks.size();
@@ -216,108 +247,185 @@ int set_error(dtk_engine* e, dtk_join* j, int rc, const char* what) {
   return rc;
 }
 
-// the device side of a join; runs on the loop's thread with no step in flight and e->mu released
-int do_join(dtk_engine* e, const Cmd* c) {
+// One prompt on its way into a slot: a join, or one of the two halves of a guided sequence.  `tab` = the Cmd whose tables the slot's
+// sampling gets (nullptr: neutral greedy sampling and no tables, the unconditional slot); errors are written to `err`
+struct Side {
+  dtk_join* j;
+  const int64_t* text; int n_text; uint64_t text_key;
+  const Cmd* tab;
+  dtk_join* err;
+};
+
+// the identity of the slot's cache: the pair key for a text join (what dtk_prefill_slot_text stores), else the image key
+uint64_t side_key(const Side& d) { return d.text ? dtk_text_image_key(d.j->image_key, d.text_key) : d.j->image_key; }
+
+// the sequence's sampling: the plan's call, which resets min_p / epsilon_cutoff, then the join's own pair (0 / 0 without one)
+int side_sampling(dtk_engine* e, const Side& d, int s) {
   const dtk_engine_ops& o = e->ops;
-  dtk_join* j = c->join;
-  // the identity of the slot's cache: the pair key for a text join (what dtk_prefill_slot_text stores), else the image key
-  const uint64_t key = c->text ? dtk_text_image_key(j->image_key, c->text_key) : j->image_key;
-  auto prefill = [&](int s, int T, int flags) {
-    return c->text ? e->prefill_text(o.dev, s, j->ids, T, j->pixels, j->image_key, c->text, c->n_text, c->text_key, flags)
-                   : o.prefill_slot(o.dev, s, j->ids, T, j->pixels, j->image_key, flags);
-  };
-  const char* prefill_name = c->text ? "dtk_prefill_slot_text" : "dtk_prefill_slot";
-  int slot = j->slot;
-  j->slot_out = slot;
-  // the sequence's sampling: the plan's call, which resets min_p / epsilon_cutoff, then the join's own pair (0 / 0 without one)
-  auto set_sampling = [&](int s) -> int {
-    int rc = o.set_sampling_slot(o.dev, s, &j->sampling);
-    if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
-    if (e->sampling_ext) {
-      rc = e->sampling_ext(o.dev, s, &c->ext);
-      if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot_ext");
-    }
-    if (e->penalties) {       // likewise the join's own presence / frequency penalty (0 / 0 / 0 without one)
-      rc = e->penalties(o.dev, s, c->pen_p, c->pen_f, c->pen_start);
-      if (rc) return set_error(e, j, rc, "dtk_set_penalties_slot");
-    }
-    if (e->dry) {             // likewise the join's own DRY (off without one)
-      rc = e->dry(o.dev, s, &c->dry);
-      if (rc) return set_error(e, j, rc, "dtk_set_dry_slot");
-    }
-    if (e->length_control) {  // likewise the join's own length rules (off without them)
-      rc = e->length_control(o.dev, s, &c->len);
-      if (rc) return set_error(e, j, rc, "dtk_set_length_control_slot");
-    }
-    if (e->logit_bias) {      // ... and its bias pairs (none without them)
-      rc = e->logit_bias(o.dev, s, c->bias_ids.data(), c->bias_val.data(), (int)c->bias_ids.size());
-      if (rc) return set_error(e, j, rc, "dtk_set_logit_bias_slot");
-    }
-    return DTK_OK;
-  };
-  if (j->try_resume && j->n_ids >= 2) {
-    int best = -1, best_len = 0;
-    const int nc = j->n_candidates > 0 ? j->n_candidates : 1;
-    for (int k = 0; k < nc; ++k) {
-      const int cand = j->n_candidates > 0 ? j->candidates[k] : slot;
-      if (cand < 0 || cand >= o.decode_slots) return set_error(e, j, DTK_ERR_ARG, "dtk_engine_join: candidate slot out of range");
-      int lcp = 0;
-      const int rc = o.slot_lcp(o.dev, cand, j->ids, j->n_ids, key, &lcp);
-      if (rc) return set_error(e, j, rc, "dtk_slot_lcp");
-      if (lcp > best_len) { best = cand; best_len = lcp; }
-    }
-    if (best >= 0 && best_len >= j->n_ids - 1) {
-      j->slot_out = slot = best;
-      int rc = set_sampling(slot);
-      if (rc) return rc;
-      rc = o.resume_slot(o.dev, slot, j->ids, j->n_ids, key);
-      if (rc) return set_error(e, j, rc, "dtk_resume_slot");
-      j->how_out = DTK_JOIN_RESUMED;
-      return DTK_OK;
-    }
+  dtk_join* j = d.err;
+  static const Cmd neutral_tab;
+  const Cmd* c = d.tab ? d.tab : &neutral_tab;
+  dtk_sampling neutral{};
+  neutral.temperature = 1.0f; neutral.top_p = 1.0f;
+  int rc = o.set_sampling_slot(o.dev, s, d.tab ? &d.j->sampling : &neutral);
+  if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot");
+  if (e->sampling_ext) {
+    rc = e->sampling_ext(o.dev, s, &c->ext);
+    if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot_ext");
   }
-  int rc = set_sampling(slot);
+  if (e->penalties) {       // likewise the join's own presence / frequency penalty (0 / 0 / 0 without one)
+    rc = e->penalties(o.dev, s, c->pen_p, c->pen_f, c->pen_start);
+    if (rc) return set_error(e, j, rc, "dtk_set_penalties_slot");
+  }
+  if (e->dry) {             // likewise the join's own DRY (off without one)
+    rc = e->dry(o.dev, s, &c->dry);
+    if (rc) return set_error(e, j, rc, "dtk_set_dry_slot");
+  }
+  if (e->length_control) {  // likewise the join's own length rules (off without them)
+    rc = e->length_control(o.dev, s, &c->len);
+    if (rc) return set_error(e, j, rc, "dtk_set_length_control_slot");
+  }
+  if (e->logit_bias) {      // ... and its bias pairs (none without them)
+    rc = e->logit_bias(o.dev, s, c->bias_ids.data(), c->bias_val.data(), (int)c->bias_ids.size());
+    if (rc) return set_error(e, j, rc, "dtk_set_logit_bias_slot");
+  }
+  return DTK_OK;
+}
+
+// *slot_out = the slot the join can resume in (the candidate with the longest match), -1: none
+int side_can_resume(dtk_engine* e, const Side& d, int* slot_out) {
+  const dtk_engine_ops& o = e->ops;
+  dtk_join* j = d.j;
+  *slot_out = -1;
+  if (!j->try_resume || j->n_ids < 2) return DTK_OK;
+  int best = -1, best_len = 0;
+  const int nc = j->n_candidates > 0 ? j->n_candidates : 1;
+  for (int k = 0; k < nc; ++k) {
+    const int cand = j->n_candidates > 0 ? j->candidates[k] : j->slot;
+    if (cand < 0 || cand >= o.decode_slots) return set_error(e, d.err, DTK_ERR_ARG, "dtk_engine_join: candidate slot out of range");
+    int lcp = 0;
+    const int rc = o.slot_lcp(o.dev, cand, j->ids, j->n_ids, side_key(d), &lcp);
+    if (rc) return set_error(e, d.err, rc, "dtk_slot_lcp");
+    if (lcp > best_len) { best = cand; best_len = lcp; }
+  }
+  if (best >= 0 && best_len >= j->n_ids - 1) *slot_out = best;
+  return DTK_OK;
+}
+
+int side_resume(dtk_engine* e, const Side& d, int slot) {
+  const dtk_engine_ops& o = e->ops;
+  d.j->slot_out = slot;
+  int rc = side_sampling(e, d, slot);
+  if (rc) return rc;
+  rc = o.resume_slot(o.dev, slot, d.j->ids, d.j->n_ids, side_key(d));
+  if (rc) return set_error(e, d.err, rc, "dtk_resume_slot");
+  d.j->how_out = DTK_JOIN_RESUMED;
+  return DTK_OK;
+}
+
+// the join's non-resume plan: in place | fork the prefix (+ tail) | full prefill
+int side_fresh(dtk_engine* e, const Side& d) {
+  const dtk_engine_ops& o = e->ops;
+  dtk_join* j = d.j;
+  const uint64_t key = side_key(d);
+  auto prefill = [&](int s, int T, int flags) {
+    return d.text ? e->prefill_text(o.dev, s, j->ids, T, j->pixels, j->image_key, d.text, d.n_text, d.text_key, flags)
+                  : o.prefill_slot(o.dev, s, j->ids, T, j->pixels, j->image_key, flags);
+  };
+  const char* prefill_name = d.text ? "dtk_prefill_slot_text" : "dtk_prefill_slot";
+  const int slot = j->slot;
+  j->slot_out = slot;
+  int rc = side_sampling(e, d, slot);
   if (rc) return rc;
   const int reuse = DTK_PREFILL_REUSE_PREFIX | DTK_PREFILL_REUSE_IMAGE;
   if (j->prefix_len > 0 && j->prefix_in_place) {
     rc = prefill(slot, j->n_ids, reuse);
-    if (rc) return set_error(e, j, rc, prefill_name);
+    if (rc) return set_error(e, d.err, rc, prefill_name);
     j->how_out = DTK_JOIN_IN_PLACE;
     return DTK_OK;
   }
   if (j->prefix_len > 0 && j->prefix_src >= 0) {
-    if (j->prefix_len > j->n_ids) return set_error(e, j, DTK_ERR_ARG, "dtk_engine_join: prefix longer than the prompt");
+    if (j->prefix_len > j->n_ids) return set_error(e, d.err, DTK_ERR_ARG, "dtk_engine_join: prefix longer than the prompt");
     bool encode = j->prefix_encode != 0;
     if (!encode && j->prefix_src_whole) {
       // a prefix-cache slot the caller believes holds this prefix: check before forking its rows (a failed join may have left the
       // caller's bookkeeping behind the slot) and encode the prefix again if it does not
       int lcp = 0;
       rc = o.slot_lcp(o.dev, j->prefix_src, j->ids, j->prefix_len, key, &lcp);
-      if (rc) return set_error(e, j, rc, "dtk_slot_lcp(prefix slot)");
+      if (rc) return set_error(e, d.err, rc, "dtk_slot_lcp(prefix slot)");
       encode = lcp != j->prefix_len;
     }
     if (encode) {     // the image's first rollout: ViT + prefix prefill into the prefix-cache slot, greedy (its logits are forked)
       dtk_sampling g{};
       g.temperature = 1.0f; g.top_p = 1.0f;
       rc = o.set_sampling_slot(o.dev, j->prefix_src, &g);
-      if (rc) return set_error(e, j, rc, "dtk_set_sampling_slot(prefix slot)");
+      if (rc) return set_error(e, d.err, rc, "dtk_set_sampling_slot(prefix slot)");
       rc = prefill(j->prefix_src, j->prefix_len, 0);
-      if (rc) return set_error(e, j, rc, c->text ? "dtk_prefill_slot_text(prefix slot)" : "dtk_prefill_slot(prefix slot)");
+      if (rc) return set_error(e, d.err, rc, d.text ? "dtk_prefill_slot_text(prefix slot)" : "dtk_prefill_slot(prefix slot)");
     }
     rc = o.kv_fork(o.dev, j->prefix_src, slot, j->prefix_len);
-    if (rc) return set_error(e, j, rc, "dtk_kv_fork");
+    if (rc) return set_error(e, d.err, rc, "dtk_kv_fork");
     if (j->prefix_src_whole && j->n_ids == j->prefix_len) {
       j->how_out = DTK_JOIN_FORK_WHOLE;       // KV and next-token logits came with the fork
       return DTK_OK;
     }
     rc = prefill(slot, j->n_ids, reuse);
-    if (rc) return set_error(e, j, rc, prefill_name);
+    if (rc) return set_error(e, d.err, rc, prefill_name);
     j->how_out = DTK_JOIN_FORK_TAIL;
     return DTK_OK;
   }
   rc = prefill(slot, j->n_ids, j->full_flags);
-  if (rc) return set_error(e, j, rc, prefill_name);
+  if (rc) return set_error(e, d.err, rc, prefill_name);
   j->how_out = DTK_JOIN_FULL;
+  return DTK_OK;
+}
+
+// a pair of an earlier guided sequence still holds `slot` on the device: dissolve it before the slot gets another prompt
+int dissolve_stale(dtk_engine* e, dtk_join* err, int slot) {
+  const int other = e->dev_pair[slot];
+  if (other < 0) return DTK_OK;
+  const int cond = e->dev_cond[slot] ? slot : other;
+  const int rc = e->guidance(e->ops.dev, cond, -1, 1.f);
+  if (rc) return set_error(e, err, rc, "dtk_set_guidance(dissolve)");
+  e->dev_pair[slot] = e->dev_pair[other] = -1;
+  e->dev_cond[slot] = e->dev_cond[other] = false;
+  return DTK_OK;
+}
+
+// the device side of a join; runs on the loop's thread with no step in flight and e->mu released
+int do_join(dtk_engine* e, const Cmd* c) {
+  dtk_join* j = c->join;
+  const Side cs{j, c->text, c->n_text, c->text_key, c, j};
+  j->slot_out = j->slot;
+  if (!c->uncond) {
+    int at = -1;
+    int rc = side_can_resume(e, cs, &at);
+    if (rc) return rc;
+    rc = dissolve_stale(e, j, at >= 0 ? at : j->slot);
+    if (rc) return rc;
+    return at >= 0 ? side_resume(e, cs, at) : side_fresh(e, cs);
+  }
+  // a guided sequence: both prompts in, then the pair.  Nothing is paired before both halves have succeeded, and the slots' Seq records
+  // are only set up after this returns DTK_OK, so a failure leaves no half-pair and both slots free
+  dtk_join* u = c->uncond;
+  const Side us{u, c->utext, c->n_utext, c->utext_key, nullptr, j};
+  u->slot_out = u->slot;
+  u->how_out = -1;
+  int rc = dissolve_stale(e, j, j->slot);
+  if (!rc) rc = dissolve_stale(e, j, u->slot);
+  if (rc) return rc;
+  int ac = -1, au = -1;
+  rc = side_can_resume(e, cs, &ac);
+  if (!rc) rc = side_can_resume(e, us, &au);
+  if (rc) return rc;
+  const bool resume = ac >= 0 && au >= 0;      // in place only if both can: the pair's slots are always in the same phase
+  rc = resume ? side_resume(e, cs, ac) : side_fresh(e, cs);
+  if (!rc) rc = resume ? side_resume(e, us, au) : side_fresh(e, us);
+  if (rc) return rc;
+  rc = e->guidance(e->ops.dev, j->slot_out, u->slot_out, c->scale);
+  if (rc) return set_error(e, j, rc, "dtk_set_guidance");
+  e->dev_pair[j->slot_out] = u->slot_out; e->dev_pair[u->slot_out] = j->slot_out;
+  e->dev_cond[j->slot_out] = true; e->dev_cond[u->slot_out] = false;
   return DTK_OK;
 }
 
@@ -337,6 +445,13 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
   } else if (busy(j->slot)) {
     rc = DTK_ERR_STATE;
     snprintf(j->error_out, sizeof j->error_out, "dtk_engine_join: slot %d is not a free decoding slot (0..%d)", j->slot, e->ops.decode_slots - 1);
+  } else if (c->uncond && (!c->uncond->ids || c->uncond->n_ids < 1 || j->n_candidates || c->uncond->n_candidates)) {
+    rc = DTK_ERR_ARG;
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: bad argument (the negative branch needs ids; neither join takes candidates)");
+  } else if (c->uncond && (busy(c->uncond->slot) || c->uncond->slot == j->slot)) {
+    rc = DTK_ERR_STATE;
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: slots %d and %d are not two free, distinct decoding slots (0..%d)", j->slot,
+             c->uncond->slot, e->ops.decode_slots - 1);
   } else {
     for (int k = 0; k < j->n_candidates && !rc; ++k)
       if (busy(j->candidates[k])) {
@@ -354,14 +469,26 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
     if (rc == DTK_ERR_HIP) poison(e, rc);
   }
   if (!rc) {
+    // the slots' records may still name partners of earlier guided sequences (they keep them past their end, for the refusals of
+    // dtk_engine_read / _leave): the new sequence starts without
+    auto unlink = [&](int s) {
+      Seq& o = e->seq[s];
+      if (o.pair >= 0 && e->seq[o.pair].pair == s) { e->seq[o.pair].pair = -1; e->seq[o.pair].follower = false; }
+      o.pair = -1; o.follower = false;
+    };
+    unlink(j->slot_out);
+    if (c->uncond) unlink(c->uncond->slot_out);
     Seq& q = e->seq[j->slot_out];
     q.toks.clear(); q.lp.clear(); q.slp.clear();
     q.read = q.flushed = 0;
     q.emitted = q.launched = 0;
     q.skip = j->how_out == DTK_JOIN_RESUMED ? 1 : 0;
     q.budget = j->max_new_tokens;
-    // never past the KV capacity: every launched step appends one position
-    const int room = e->ops.max_positions - e->ops.context_len_slot(e->ops.dev, j->slot_out);
+    q.pair = c->uncond ? c->uncond->slot_out : -1;
+    q.follower = false;
+    // never past the KV capacity: every launched step appends one position (a pair: in both slots)
+    int room = e->ops.max_positions - e->ops.context_len_slot(e->ops.dev, j->slot_out);
+    if (c->uncond) room = std::min(room, e->ops.max_positions - e->ops.context_len_slot(e->ops.dev, c->uncond->slot_out));
     q.need = q.budget + q.skip;
     if (q.need > room) { q.need = room > 0 ? room : 0; q.budget = q.need - q.skip; }
     q.n_stop = j->n_stop;
@@ -371,6 +498,16 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
     q.decoding = q.budget > 0;
     q.state = q.decoding ? DTK_SEQ_RUNNING : DTK_SEQ_FINISHED;
     if (e->own_ctx && !q.held) { q.held = true; dtk_internal_engine_holds(e->own_ctx, +1); }
+    if (c->uncond) {      // the follower: launched and stopped with its leader, nothing of it is delivered
+      Seq& f = e->seq[c->uncond->slot_out];
+      f.toks.clear(); f.lp.clear(); f.slp.clear();
+      f.read = f.flushed = 0;
+      f.emitted = f.launched = 0;
+      f.skip = q.skip; f.budget = q.budget; f.need = q.need; f.n_stop = 0;
+      f.pair = j->slot_out; f.follower = true;
+      f.decoding = q.decoding; f.state = q.state;
+      if (e->own_ctx && !f.held) { f.held = true; dtk_internal_engine_holds(e->own_ctx, +1); }
+    }
     e->st.joins++;
     if (q.skip) e->st.resumed++;
     if (e->gather_left > 0) e->gather_left--;
@@ -415,9 +552,17 @@ struct JoinShape { const dtk_length_ctl* len; const int32_t* ids; const float* v
 inline bool len_ctl_on(const dtk_length_ctl* l) { return l && l->n_eos > 0 && (l->min_new_tokens > 0 || l->decay_factor != 0.); }
 int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t text_key, uint64_t* ticket_out,
            const dtk_sampling_ext* ext = nullptr, const JoinPen* pen = nullptr, const dtk_dry* dry = nullptr,
-           const JoinShape* shp = nullptr) {
+           const JoinShape* shp = nullptr, const dtk_guided* gd = nullptr) {
   std::lock_guard<std::mutex> g(e->mu);
   if (e->quit) { snprintf(j->error_out, sizeof j->error_out, "the engine is being destroyed"); return DTK_ERR_STATE; }
+  if (gd && !e->guidance) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: this engine's device pairs no slots (dtk_engine_set_guidance_op)");
+    return DTK_ERR_STATE;
+  }
+  if (gd && gd->uncond_text_ids && !e->prefill_text) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: this engine's device has no text prefill (dtk_engine_set_prefill_text_op)");
+    return DTK_ERR_STATE;
+  }
   if (text && !e->prefill_text) {
     snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_text: this engine's device has no text prefill (dtk_engine_set_prefill_text_op)");
     return DTK_ERR_STATE;
@@ -450,6 +595,7 @@ int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t
   if (dry) c->dry = *dry;
   if (pen) { c->pen_p = pen->presence; c->pen_f = pen->frequency; c->pen_start = pen->start; }
   c->text = text; c->n_text = n_text; c->text_key = text_key;
+  if (gd) { c->uncond = gd->uncond; c->utext = gd->uncond_text_ids; c->n_utext = gd->uncond_text_ids ? gd->n_uncond_text : 0; c->utext_key = gd->uncond_text_ids ? gd->uncond_text_key : 0; c->scale = gd->scale; }
   e->cmds.push_back(c);
   e->cv_run.notify_all();
   *ticket_out = (uint64_t)(uintptr_t)c;
@@ -477,6 +623,7 @@ int ctx_length_control(void* d, int s, const dtk_length_ctl* l) {     // (off: d
 int ctx_logit_bias(void* d, int s, const int32_t* ids, const float* values, int n) {
   return n > 0 ? dtk_set_logit_bias_slot((dtk_ctx*)d, s, ids, values, n) : DTK_OK;
 }
+int ctx_guidance(void* d, int c, int u, float g) { return dtk_set_guidance((dtk_ctx*)d, c, u, g); }
 int ctx_fork(void* d, int a, int b, int n) { return dtk_kv_fork((dtk_ctx*)d, a, b, n); }
 int ctx_lcp(void* d, int s, const int64_t* ids, int n, uint64_t key, int* out) { return dtk_slot_lcp((dtk_ctx*)d, s, ids, n, key, out); }
 int ctx_resume(void* d, int s, const int64_t* ids, int n, uint64_t key) { return dtk_resume_slot((dtk_ctx*)d, s, ids, n, key); }
@@ -522,6 +669,7 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
     (*out)->dry = ctx_dry;
     (*out)->length_control = ctx_length_control;
     (*out)->logit_bias = ctx_logit_bias;
+    (*out)->guidance = ctx_guidance;
   }
   return dtk_engine_set_prefill_text_op(*out, ctx_prefill_text);
 }
@@ -565,6 +713,13 @@ int dtk_engine_set_logit_bias_op(dtk_engine* e, BiasFn set_logit_bias_slot) {
   if (!e) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->logit_bias = set_logit_bias_slot;
+  return DTK_OK;
+}
+
+int dtk_engine_set_guidance_op(dtk_engine* e, GuidanceFn set_guidance) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->guidance = set_guidance;
   return DTK_OK;
 }
 
@@ -705,40 +860,62 @@ int dtk_engine_submit_dry(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x,
 
 // dtk_engine_submit_dry + the sequence's length rules and bias pairs; the values are checked here as far as they can be without the
 // device (the vocabulary: an id outside it fails the join)
-int dtk_engine_submit_shape(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, float presence, float frequency, int start,
-                            const dtk_dry* d, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias,
-                            const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
-  if (!e || !j || !ticket_out) return DTK_ERR_ARG;
+static int submit_shape(dtk_engine* e, dtk_join* j, const char* who, const dtk_sampling_ext* x, float presence, float frequency, int start,
+                        const dtk_dry* d, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                        const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out, const dtk_guided* gd) {
   if (x && (!(x->min_p >= 0.f && x->min_p <= 1.f) || !(x->epsilon_cutoff >= 0.f && x->epsilon_cutoff < 1.f))) {
-    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: min_p must be in [0, 1] and epsilon_cutoff in [0, 1)");
+    snprintf(j->error_out, sizeof j->error_out, "%s: min_p must be in [0, 1] and epsilon_cutoff in [0, 1)", who);
     return DTK_ERR_ARG;
   }
   if (!(presence >= -2.f && presence <= 2.f) || !(frequency >= -2.f && frequency <= 2.f) || start < 0) {
-    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: presence_penalty and frequency_penalty must be in [-2, 2], penalty_start >= 0");
+    snprintf(j->error_out, sizeof j->error_out, "%s: presence_penalty and frequency_penalty must be in [-2, 2], penalty_start >= 0", who);
     return DTK_ERR_ARG;
   }
   if (d && (!(d->multiplier >= 0.f && d->multiplier <= 100.f) || !(d->base >= 1.f && d->base <= 8.f) || d->allowed_length < 1 ||
             d->allowed_length > DTK_DRY_MAX_MATCH || d->start < 0 || d->n_breakers < 0 || d->n_breakers > DTK_DRY_MAX_BREAKERS)) {
-    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: dry_multiplier in [0, 100], dry_base in [1, 8], dry_allowed_length in [1, 64], "
-             "dry_start >= 0, at most 16 breakers");
+    snprintf(j->error_out, sizeof j->error_out, "%s: dry_multiplier in [0, 100], dry_base in [1, 8], dry_allowed_length in [1, 64], "
+             "dry_start >= 0, at most 16 breakers", who);
     return DTK_ERR_ARG;
   }
   if (l && (l->min_new_tokens < 0 || l->decay_start < 0 || l->start < 0 || l->n_eos < 0 || l->n_eos > 8 ||
             (l->decay_factor != 0. && (!(l->decay_factor > 0. && l->decay_factor <= 1.7976931348623157e308) || l->decay_start < l->min_new_tokens)))) {
-    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: min_new_tokens, decay_start, length_start >= 0, decay_factor finite and > 0 "
-             "(0 = none) with decay_start >= min_new_tokens, at most 8 EOS ids");
+    snprintf(j->error_out, sizeof j->error_out, "%s: min_new_tokens, decay_start, length_start >= 0, decay_factor finite and > 0 "
+             "(0 = none) with decay_start >= min_new_tokens, at most 8 EOS ids", who);
     return DTK_ERR_ARG;
   }
   bool bias_ok = n_bias >= 0 && n_bias <= DTK_BIAS_MAX && (n_bias == 0 || (bias_ids && bias_values));
   for (int i = 0; bias_ok && i < n_bias; ++i) bias_ok = bias_values[i] >= -100.f && bias_values[i] <= 100.f;
   if (!bias_ok) {
-    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: at most %d bias pairs, values finite and in [-100, 100]", DTK_BIAS_MAX);
+    snprintf(j->error_out, sizeof j->error_out, "%s: at most %d bias pairs, values finite and in [-100, 100]", who, DTK_BIAS_MAX);
     return DTK_ERR_ARG;
   }
-  if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_shape: no text"); return DTK_ERR_ARG; }
+  if (text_ids && n_text < 1) { snprintf(j->error_out, sizeof j->error_out, "%s: no text", who); return DTK_ERR_ARG; }
   const JoinPen pn{presence, frequency, start};
   const JoinShape sh{l, bias_ids, bias_values, n_bias};
-  return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn, d, &sh);
+  return submit(e, j, text_ids, text_ids ? n_text : 0, text_ids ? text_key : 0, ticket_out, x, &pn, d, &sh, gd);
+}
+
+int dtk_engine_submit_shape(dtk_engine* e, dtk_join* j, const dtk_sampling_ext* x, float presence, float frequency, int start,
+                            const dtk_dry* d, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                            const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  if (!e || !j || !ticket_out) return DTK_ERR_ARG;
+  return submit_shape(e, j, "dtk_engine_submit_shape", x, presence, frequency, start, d, l, bias_ids, bias_values, n_bias, text_ids, n_text,
+                      text_key, ticket_out, nullptr);
+}
+
+// a guided sequence: dtk_engine_submit_shape for the conditional join + the negative branch's plan, its text and the scale
+int dtk_engine_submit_guided(dtk_engine* e, const dtk_guided* g, const dtk_sampling_ext* x, float presence, float frequency, int start,
+                             const dtk_dry* d, const dtk_length_ctl* l, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                             const int64_t* text_ids, int n_text, uint64_t text_key, uint64_t* ticket_out) {
+  if (!e || !g || !g->cond || !g->uncond || !ticket_out) return DTK_ERR_ARG;
+  dtk_join* j = g->cond;
+  if (!std::isfinite(g->scale) || g->scale < 0.f || g->scale > 100.f || g->scale == 1.f) {
+    snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: the guidance scale must be finite, in [0, 100] and not 1");
+    return DTK_ERR_ARG;
+  }
+  if (g->uncond_text_ids && g->n_uncond_text < 1) { snprintf(j->error_out, sizeof j->error_out, "dtk_engine_submit_guided: no negative text"); return DTK_ERR_ARG; }
+  return submit_shape(e, j, "dtk_engine_submit_guided", x, presence, frequency, start, d, l, bias_ids, bias_values, n_bias, text_ids, n_text,
+                      text_key, ticket_out, g);
 }
 
 int dtk_engine_await(dtk_engine* e, uint64_t ticket) {
@@ -772,6 +949,7 @@ int dtk_engine_read_lp(dtk_engine* e, int slot, int64_t* out, float* logprob_out
   if (logprob_out && e->own_ctx && !dtk_internal_logprobs(e->own_ctx)) return DTK_ERR_ARG;     // the context's "logprobs" option is off
   std::unique_lock<std::mutex> lk(e->mu);
   Seq& q = e->seq[slot];
+  if (q.follower) return DTK_ERR_ARG;      // the unconditional slot of a guided sequence: its tokens are the leader's
   *n_out = 0;
   *state_out = q.state;
   if (q.state == 0) return DTK_ERR_STATE;
@@ -800,6 +978,13 @@ int dtk_engine_leave(dtk_engine* e, int slot) {
   if (!e || slot < 0 || slot >= DTK_MAX_BATCH) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   Seq& q = e->seq[slot];
+  if (q.follower) return DTK_ERR_ARG;      // a guided sequence leaves through its conditional slot
+  if (q.pair >= 0) {                       // ... which ends both
+    Seq& f = e->seq[q.pair];
+    f.decoding = false;
+    if (f.held) { f.held = false; dtk_internal_engine_holds(e->own_ctx, -1); }
+    if (f.state == DTK_SEQ_RUNNING) f.state = DTK_SEQ_LEFT;
+  }
   q.decoding = false;
   if (q.held) { q.held = false; dtk_internal_engine_holds(e->own_ctx, -1); }
   if (q.state == DTK_SEQ_RUNNING) q.state = DTK_SEQ_LEFT;

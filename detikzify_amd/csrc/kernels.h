@@ -163,8 +163,10 @@ void launch_top_logits(const TopArgs& a, hipStream_t s);
 struct CfgPair { int32_t cond; int32_t uncond; float scale; int32_t pad; };
 struct CfgArgs {
   float* logits; int V; int stride;    // rows at logits + slot * stride
-  const CfgPair* pairs; int n_pairs;   // device table; grid y
+  const CfgPair* pairs; int n_pairs;   // device table; grid y.  An entry with cond < 0 is unused (dtk_reserve_guidance): its blocks return at once
   const BatchState* bs;                // a pair whose conditional slot is inactive is skipped; null = every pair runs
+  const DecState* st = nullptr;        // [slots], or null: a pair whose conditional slot forwards a forced token this step (force_plus1) is skipped
+  int32_t* forced = nullptr;           // [n_pairs] with st: 1 = the pair was skipped for that reason this step (k_cfg_follow reads it behind the sampler)
   float2* part;                        // [n_pairs][2][DTK_CFG_MAX_SLICES] (max, sum exp(z - max)) per (pair, row, slice)
   float2* lse;                         // [n_pairs] (Lc, Lu) of the last launch
   int per = 0;                         // elements per slice (launch_cfg_mix sets it from V)
@@ -174,6 +176,7 @@ void launch_cfg_mix(const CfgArgs& a, hipStream_t s);       // k_cfg_lse + k_cfg
 struct CfgFollowArgs {
   const CfgPair* pairs; int n_pairs;
   const BatchState* bs;
+  const int32_t* forced = nullptr;     // [n_pairs] as k_cfg_lse left it: both slots forwarded their own forced token, nothing is handed over (null: never)
   DecState* st;                        // [slots]
   bf16_t* x; int d;                    // residual streams [slot][d]
   int64_t* tok_ring; int ring;         // the step's rings, indexed (step % ring) * DTK_MAX_BATCH + slot

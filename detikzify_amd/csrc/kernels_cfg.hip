@@ -79,9 +79,21 @@ __device__ __forceinline__ float2 cfg_row_state(const float* row, int i0, int i1
   return r;
 }
 
+// Block-uniform: the entry is unused (cond < 0: a reserved table position without a pair — nothing else of the step is read), its
+// conditional slot sits this step out, or the pair forwards forced tokens this step (dtk_resume_slot; dtk_decode_batch_launch lets a pair
+// through only with both slots in that phase or neither).  The forced step reads no logits: the rows are those of the slots' earlier
+// sequences, or were never written, so nothing is folded or mixed — the sampler forwards each slot's own token whatever the rows hold
+__device__ __forceinline__ bool cfg_pair_idle(const CfgArgs& a, const CfgPair& p) {
+  if (p.cond < 0) return true;
+  if (a.bs && !a.bs->active[p.cond]) return true;
+  return a.st && a.st[p.cond].force_plus1 != 0;
+}
+
 __global__ __launch_bounds__(CFG_THREADS) void k_cfg_lse(CfgArgs a) {
   const CfgPair p = a.pairs[blockIdx.y];
-  if (a.bs && !a.bs->active[p.cond]) return;
+  if (a.forced && p.cond >= 0 && blockIdx.x == 0 && threadIdx.x == 0 && (!a.bs || a.bs->active[p.cond]))
+    a.forced[blockIdx.y] = a.st[p.cond].force_plus1 != 0;
+  if (cfg_pair_idle(a, p)) return;
   __shared__ float s_m[CFG_THREADS / 64], s_s[CFG_THREADS / 64];
   const int i0 = blockIdx.x * a.per, i1 = min(a.V, i0 + a.per);
   float2* part = a.part + (size_t)blockIdx.y * 2 * DTK_CFG_MAX_SLICES;
@@ -92,7 +104,7 @@ __global__ __launch_bounds__(CFG_THREADS) void k_cfg_lse(CfgArgs a) {
 
 __global__ __launch_bounds__(CFG_THREADS) void k_cfg_mix(CfgArgs a) {
   const CfgPair p = a.pairs[blockIdx.y];
-  if (a.bs && !a.bs->active[p.cond]) return;
+  if (cfg_pair_idle(a, p)) return;      // (the sampler, which clears force_plus1, runs behind this kernel)
   __shared__ float s_t[2][DTK_CFG_MAX_SLICES];
   __shared__ float s_max[2][2];
   __shared__ float s_L[2];
@@ -131,10 +143,11 @@ __global__ __launch_bounds__(CFG_THREADS) void k_cfg_mix(CfgArgs a) {
 
 // behind the sampler (and k_count_token): the unconditional slot of every active pair takes over what the conditional slot's chain
 // left — DecState::token, the gathered embedding row, the token ring entry and the lp / lse / top ring entries of the step.  The
-// unconditional slot's own sampler block has advanced that slot's position already
+// unconditional slot's own sampler block has advanced that slot's position already.  On the forced step of a resumed pair both samplers
+// have forwarded their slot's own last prompt token (token, embedding row, token ring, NaN log-probabilities): nothing is handed over
 __global__ __launch_bounds__(CFG_THREADS) void k_cfg_follow(CfgFollowArgs a) {
   const CfgPair p = a.pairs[blockIdx.x];
-  if (!a.bs->active[p.cond]) return;
+  if (p.cond < 0 || !a.bs->active[p.cond] || (a.forced && a.forced[blockIdx.x])) return;
   const int tid = threadIdx.x;
   const size_t ri = (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH;
   if (tid == 0) {

@@ -63,7 +63,8 @@ class BatchEngine:
     The SelfSim ViT passes do not take `cv`: they run on their own stream under the model's ViT lock."""
 
     def __init__(self, model, max_batch: Optional[int] = None, share_prefix: bool = True, pipeline: bool = True,
-                 gather: int = 0, gather_timeout: float = 0.5, prefix_slots: Optional[int] = None, resume_in_place: bool = True):
+                 gather: int = 0, gather_timeout: float = 0.5, prefix_slots: Optional[int] = None, resume_in_place: bool = True,
+                 guided_pairs: int = 0):
         n = model.num_slots()
         if n <= 0:
             raise ValueError("model was loaded without batch slots (load(..., batch_slots=N))")
@@ -83,6 +84,15 @@ class BatchEngine:
         spare = n - self.capacity
         n_prefix = min(spare, 8 if prefix_slots is None else int(prefix_slots)) if self.share_prefix else 0
         self.prefix_slots: List[int] = list(range(n - n_prefix, n))
+        # guided_pairs = P > 0: up to P classifier-free-guided sequences (sequence(guidance=...)) decode at once, each in two slots: its
+        # own, which is `active` like any sequence's, and the negative branch's — a follower that every step takes along with its
+        # leader and whose token is only compared.  The device's pair table is reserved for P standing pairs (model.reserve_guidance),
+        # so pairs come and go without a re-capture.  0: nothing is reserved, guided sequences are refused
+        self.guided_pairs = int(guided_pairs)
+        if self.guided_pairs < 0 or 2 * self.guided_pairs > self.capacity:
+            raise ValueError(f"guided_pairs = {guided_pairs}: every guided sequence takes two of the engine's {self.capacity} decode slots")
+        self.partner: Dict[int, int] = {}                   # conditional slot of a joined guided sequence -> its unconditional slot
+        self.dev_pairs: Dict[int, int] = {}                 # the pairs as set on the device (dissolved by the next join that uses a slot)
         # (image key, text key, prefix length) -> prefix slot, LRU order; text key 0 = an image-only prompt, the adapter's text else
         self.prefix_cache: "OrderedDict[Tuple[int, int, int], int]" = OrderedDict()
         self.slot_img: Dict[int, Tuple[int, int, int]] = {}      # slot -> (image key, text key, prefix length) whose KV prefix it still holds
@@ -127,6 +137,8 @@ class BatchEngine:
         # trickle in one pipeline flush at a time); gives up after gather_timeout seconds
         self.gather_left = min(int(gather), self.capacity)
         self.gather_deadline = time.perf_counter() + gather_timeout
+        if self.guided_pairs:
+            model.reserve_guidance(self.guided_pairs)
         model.batch_engine = self
 
     @contextmanager
@@ -160,6 +172,11 @@ class BatchEngine:
     def close(self):
         with self._locked():
             self._collect()
+            if self.guided_pairs and self.error is None:      # no step is in flight: the pairs left behind and the reservation go
+                for c in list(self.dev_pairs):
+                    self.model.set_guidance(None, c, None)
+                self.dev_pairs.clear()
+                self.model.reserve_guidance(0)
         self.model.batch_engine = None
 
     def busy(self) -> bool:
@@ -169,7 +186,8 @@ class BatchEngine:
 
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, text_ids=None,
-                 logprobs: bool = False, top_logprobs: Optional[int] = None, **_native_only) -> Iterator[_Sequence]:
+                 logprobs: bool = False, top_logprobs: Optional[int] = None, guidance: Optional[Dict[str, Any]] = None,
+                 **_native_only) -> Iterator[_Sequence]:
         """`owner`: whoever starts sequence after sequence (an MCTS tree: generate(sequence_owner=t)) — a join that cannot
         resume takes the slot its owner used last, so it does not overwrite a rollout ANOTHER owner may come back to.
         `text_ids`: one unpadded text that conditions the tower (the adapter; pixel_values None = its dummy image): the slot's prefix is
@@ -177,9 +195,18 @@ class BatchEngine:
         `logprobs`: the sequence collects its tokens' (logprob, sample_logprob) in `.logprobs` / `.sample_logprobs`.  The first such
         sequence switches the device over (model.enable_logprobs()), which is done before the first join, not while other sequences
         hold slots.
+        `guidance`: dict(scale=, ids=, pixel_values=, text_ids=) — a classifier-free-guided sequence (an engine built with guided_pairs >
+        0): the negative branch gets a second slot, planned like the sequence's own (its own prefix key, so one negative image is encoded
+        once and forked; its own slot per owner), neutral greedy sampling and no tables; the two resume in place only if both can; the
+        pair is set once both prompts are in, and both slots are released together.
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
+        if guidance is not None:
+            if not self.guided_pairs:
+                raise NotImplementedError("guidance_scale: not in the batch engines yet (this engine was built without guided_pairs=)")
+            yield from self._guided_sequence(ids, pixel_values, sampling, owner, text_ids, logprobs, guidance)
+            return
         from ..model.modeling import (DRY_KEYS, DUMMY_IMAGE_KEY, SHAPE_KEYS, adapter_text, check_dry, check_penalties, check_truncation,
                                       shape_of_sampling, text_image_key, text_key)
         check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
@@ -209,35 +236,7 @@ class BatchEngine:
             if self.zombies and self.error is None:
                 self._collect()     # a slot left while its last step was in flight is free once that step is read — and it may
                                     # be the very slot whose cache holds this prompt (a tree returning right after its rollout)
-            # slot choice: a free slot that holds no prefix worth keeping; else one that already holds THIS image's prefix
-            # (re-used in place); else evict the prefix of some other image
-            # (lowest index first: a step only runs the 16-slot column tiles up to its highest active slot)
-            order = sorted(self.free)
-            slot, resume = None, False
-            n_ids = int(ids.numel())
-            # (an image position takes the projected patch feature, not a token embedding: the forced token must be text)
-            if (self.resume_in_place and n_ids >= 2 and (want is not None or pixel_values is None)
-                    and int(ids.reshape(-1)[-1]) != self.model.config.image_token_id):
-                key = slot_key if want is not None else 0
-                # an owner (an MCTS tree) resumes only in the slot IT used last: whether a join resumes or re-prefills must not
-                # depend on which other slots happen to be free at that moment (thread timing) — resumed rows were written by
-                # the decode kernels, prefilled rows by the GEMMs, so the choice is visible in the last bits of the logits and
-                # a fixed-seed parallel search would stop being reproducible.  Owner-less sequences may take any free slot.
-                if owner is not None:
-                    candidates = [self.last_slot[owner]] if self.last_slot.get(owner) in self.free else []
-                else:
-                    candidates = order
-                best = self.model.best_lcp_slot(candidates, ids, key) if candidates else None
-                if best is not None and best[1] >= n_ids - 1:
-                    slot, resume = best[0], True
-            if slot is None and owner is not None and self.last_slot.get(owner) in self.free:
-                slot = self.last_slot[owner]
-            if slot is None:
-                slot = next((f for f in order if f not in self.slot_img), None)
-            if slot is None and want is not None:
-                slot = next((f for f in order if self.slot_img.get(f) == want), None)
-            if slot is None:
-                slot = order[0]
+            slot, resume = self._choose(sorted(self.free), owner, ids, pixel_values, want, slot_key)
             self.free.remove(slot)
             if owner is not None:
                 self.last_slot[owner] = slot
@@ -257,63 +256,12 @@ class BatchEngine:
                     self.model.enable_logprobs()
                     self.lp = True
                 t0 = time.perf_counter()
-                # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
-                # without them leaves the slot at 0 / 0
-                plain = {k: v for k, v in sampling.items()
-                         if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start") + DRY_KEYS + SHAPE_KEYS}
-                self.model.set_sampling(slot=slot, **plain)
-                ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
-                set_ext = getattr(self.model, "set_sampling_ext", None)
-                if set_ext is not None:
-                    set_ext(*ext, slot=slot)
-                elif any(ext):
-                    from .._lib import DtkError
-                    raise DtkError("this device takes no min_p / epsilon_cutoff")
-                # the presence / frequency penalty likewise (penalty_start: the prompt length unless the sequence says otherwise); the
-                # fork / prefill / resume below builds the slot's count table from the sequence's ids
-                set_pen = getattr(self.model, "set_penalties", None)
-                if set_pen is not None:
-                    set_pen(pen[0], pen[1], (int(ids.numel()) if pen[2] is None else pen[2]) if (pen[0] or pen[1]) else 0, slot=slot)
-                elif pen[0] or pen[1]:
-                    from .._lib import DtkError
-                    raise DtkError("this device takes no presence / frequency penalty")
-                # DRY likewise (dry_start: the prompt length unless the sequence says otherwise); the fork / prefill / resume below
-                # builds the slot's history from the sequence's ids
-                set_dry = getattr(self.model, "set_dry", None)
-                if set_dry is not None:
-                    set_dry(dry[0], dry[1], dry[2], (int(ids.numel()) if dry[3] is None else dry[3]) if dry[0] else 0, dry[4], slot=slot)
-                elif dry[0]:
-                    from .._lib import DtkError
-                    raise DtkError("this device takes no DRY penalty")
-                # the length rules and the bias table likewise (length_start: the prompt length unless the sequence says otherwise);
-                # both are static for the sequence, whatever the fork / prefill / resume below does
-                set_len = getattr(self.model, "set_length_control", None)
-                if set_len is not None:
-                    set_len(shape[0], shape[1], shape[2], shape[3], slot=slot)
-                elif shape[3]:
-                    from .._lib import DtkError
-                    raise DtkError("this device takes no length control")
-                set_bias = getattr(self.model, "set_logit_bias", None)
-                if set_bias is not None:
-                    set_bias(shape[4], slot=slot)
-                elif shape[4]:
-                    from .._lib import DtkError
-                    raise DtkError("this device takes no logit bias")
+                self._dissolve_stale(slot)
+                self._set_tables(slot, sampling, int(ids.numel()), pen, dry, shape)
+                self._enter(slot, ids, pixel_values, want, text, slot_key, resume)
                 if resume:
-                    self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
                     self.skip_first.add(slot)
                     self.resumes += 1
-                    forked = 2
-                else:
-                    forked = self._fork_prefix(slot, ids, pixel_values, want, text) if want is not None else 0
-                    if want is None:
-                        self.slot_img.pop(slot, None)
-                if forked == 2:
-                    pass    # the prompt IS the prefix (rollout from the root): KV and logits were forked, nothing to run
-                elif forked:
-                    self.model.prefill(ids, pixel_values, slot=slot, reuse=True, **text)    # only the tail beyond the prefix
-                else:
-                    self.model.prefill(ids, pixel_values, slot=slot, **text)
                 self.t_prefill += time.perf_counter() - t0
                 q = self.tokq[slot]
                 while not q.empty():       # leftovers of the slot's previous sequence
@@ -349,7 +297,219 @@ class BatchEngine:
                     self.free.append(slot)
                 self.cv.notify_all()   # a slot may have become free
 
+    def _guided_sequence(self, ids, pixel_values, sampling, owner, text_ids, logprobs, guidance):
+        """BatchEngine.sequence(guidance=...): two slots, two plans, one join under the engine's lock"""
+        from .._lib import DtkError
+        from ..model.modeling import (DRY_KEYS, DUMMY_IMAGE_KEY, adapter_text, check_dry, check_guidance_scale, check_penalties, check_truncation,
+                                      shape_of_sampling, text_image_key, text_key)
+        scale = check_guidance_scale(guidance.get("scale"))
+        if scale == 1.0:
+            raise ValueError("sequence(guidance=...): a scale of 1 is no guidance")
+        check_truncation(sampling.get("min_p"), sampling.get("epsilon_cutoff"))      # ValueError before a slot is taken
+        pen = check_penalties(sampling.get("presence_penalty"), sampling.get("frequency_penalty"), sampling.get("penalty_start"))
+        dry = check_dry(*(sampling.get(k) for k in DRY_KEYS))
+        shape = shape_of_sampling(sampling, int(ids.numel()))
+        off = (check_penalties(None, None, None), check_dry(*(None for _ in DRY_KEYS)), shape_of_sampling({}, 0))
+
+        def identity(ids, px, text_ids):
+            tids = adapter_text(text_ids) if text_ids is not None else None
+            tkey = text_key(tids) if tids is not None else 0
+            ikey = self.model.image_key(px) if px is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
+            slot_key = text_image_key(ikey, tkey) if tids is not None else ikey
+            want = self._prefix_key(ids, ikey, tkey) if (self.share_prefix and (px is not None or tids is not None)) else None
+            return dict(ids=ids, px=px, text={} if tids is None else {"adapter_input_ids": tids}, slot_key=slot_key, want=want)
+
+        gids = guidance.get("ids")
+        sides = [identity(ids, pixel_values, text_ids),
+                 identity(ids if gids is None else gids, guidance.get("pixel_values"), guidance.get("text_ids"))]
+        with self._locked():
+            while len(self.free) < 2:
+                with self._plock:       # waiting for slots is not wanting the lock: the driver must keep stepping
+                    self.pending -= 1
+                try:
+                    self.cv.wait()
+                finally:
+                    with self._plock:
+                        self.pending += 1
+            if getattr(self.model, "adapter_epoch", 0) != self._adapter_epoch:
+                self._adapter_epoch = getattr(self.model, "adapter_epoch", 0)
+                self.prefix_cache.clear()
+                self.slot_img.clear()
+            if self.zombies and self.error is None:
+                self._collect()
+            order = sorted(self.free)
+            okeys = (owner, None if owner is None else (owner, "uncond"))
+            for side, okey in zip(sides, okeys):
+                side["slot"], side["resume"] = self._choose(order, okey, side["ids"], side["px"], side["want"], side["slot_key"])
+                order = [f for f in order if f != side["slot"]]
+                self.free.remove(side["slot"])
+                if okey is not None:
+                    self.last_slot[okey] = side["slot"]
+        c, u = sides[0]["slot"], sides[1]["slot"]
+        resume = sides[0]["resume"] and sides[1]["resume"]      # in place only if both can: the pair's slots are always in the same phase
+        joined = False
+        try:
+            with self._locked():
+                if self.error is not None:
+                    raise self.error
+                self._collect()
+                if self.error is not None:
+                    raise self.error
+                if logprobs and not self.lp:
+                    if (self.active or self.inflight is not None) and not self.model.logprobs_enabled:
+                        raise DtkError("sequence(logprobs=True): log-probabilities are switched on before the first join, not "
+                                       "while sequences hold slots")
+                    self.model.enable_logprobs()
+                    self.lp = True
+                t0 = time.perf_counter()
+                self._dissolve_stale(c)
+                self._dissolve_stale(u)
+                self._set_tables(c, sampling, int(ids.numel()), pen, dry, shape)
+                self._set_tables(u, {}, int(sides[1]["ids"].numel()), *off)      # neutral greedy sampling, no tables
+                for side in sides:
+                    self._enter(side["slot"], side["ids"], side["px"], side["want"], side["text"], side["slot_key"], resume)
+                self.model.set_guidance(scale, c, u)        # both prompts are in; no step is in flight
+                self.dev_pairs[c] = u
+                self.partner[c] = u
+                if resume:
+                    self.skip_first.add(c)
+                    self.resumes += 1
+                self.t_prefill += time.perf_counter() - t0
+                q = self.tokq[c]
+                while not q.empty():
+                    q.get_nowait()
+                self.active.add(c)
+                self.joins += 1
+                self.gather_left = max(0, self.gather_left - 1)
+                joined = True
+                if self.driver is not None:
+                    self.tokq[self.driver].put(_NUDGE)
+            seq = _Sequence(self, c, logprobs)
+            seq.uncond_slot, seq.resumed = u, resume
+            if logprobs:
+                with self._locked():
+                    self.lp_sinks[c] = seq
+            yield seq
+        finally:
+            with self._locked():
+                self.lp_sinks.pop(c, None)
+                self.skip_first.discard(c)
+                self.partner.pop(c, None)
+                if joined:
+                    self.active.discard(c)
+                    self.ready.discard(c)
+                    for s_ in (c, u):
+                        if self.inflight is not None and s_ in self.inflight:
+                            self.zombies.add(s_)      # recycled by _collect()
+                        else:
+                            self.free.append(s_)
+                    if not self.active:
+                        self._collect()
+                    elif self.driver is None:
+                        self._maybe_step()
+                else:
+                    for s_ in (c, u):
+                        self.slot_img.pop(s_, None)   # the join did not complete: the slots hold nobody's prefix
+                        self.free.append(s_)
+                self.cv.notify_all()
+
     # -- called with self.cv held ---------------------------------------------------------------------
+    def _choose(self, order: List[int], okey, ids, pixel_values, want, slot_key) -> Tuple[int, bool]:
+        """the slot of one prompt among the free slots `order`, and whether it resumes there.  A free slot that holds no prefix worth
+        keeping; else one that already holds THIS image's prefix (re-used in place); else evict the prefix of some other image
+        (lowest index first: a step only runs the 16-slot column tiles up to its highest active slot)"""
+        slot, resume = None, False
+        n_ids = int(ids.numel())
+        # (an image position takes the projected patch feature, not a token embedding: the forced token must be text)
+        if (self.resume_in_place and n_ids >= 2 and (want is not None or pixel_values is None)
+                and int(ids.reshape(-1)[-1]) != self.model.config.image_token_id):
+            key = slot_key if want is not None else 0
+            # an owner (an MCTS tree) resumes only in the slot IT used last: whether a join resumes or re-prefills must not
+            # depend on which other slots happen to be free at that moment (thread timing) — resumed rows were written by
+            # the decode kernels, prefilled rows by the GEMMs, so the choice is visible in the last bits of the logits and
+            # a fixed-seed parallel search would stop being reproducible.  Owner-less sequences may take any free slot.
+            if okey is not None:
+                candidates = [self.last_slot[okey]] if self.last_slot.get(okey) in order else []
+            else:
+                candidates = order
+            best = self.model.best_lcp_slot(candidates, ids, key) if candidates else None
+            if best is not None and best[1] >= n_ids - 1:
+                slot, resume = best[0], True
+        if slot is None and okey is not None and self.last_slot.get(okey) in order:
+            slot = self.last_slot[okey]
+        if slot is None:
+            slot = next((f for f in order if f not in self.slot_img), None)
+        if slot is None and want is not None:
+            slot = next((f for f in order if self.slot_img.get(f) == want), None)
+        if slot is None:
+            slot = order[0]
+        return slot, resume
+
+    def _dissolve_stale(self, slot: int):
+        """(no step in flight) a pair of an earlier guided sequence still holds `slot` on the device: dissolve it before the slot gets
+        another prompt"""
+        for c, u in list(self.dev_pairs.items()):
+            if slot in (c, u):
+                self.model.set_guidance(None, c, None)
+                del self.dev_pairs[c]
+
+    def _set_tables(self, slot: int, sampling: Dict[str, Any], n_ids: int, pen, dry, shape):
+        """the sequence's sampling state into its slot"""
+        from .._lib import DtkError
+        from ..model.modeling import DRY_KEYS, SHAPE_KEYS
+        # min_p / epsilon_cutoff travel in a call of their own, right after the plain one (which resets them): a sequence
+        # without them leaves the slot at 0 / 0
+        plain = {k: v for k, v in sampling.items()
+                 if k not in ("min_p", "epsilon_cutoff", "presence_penalty", "frequency_penalty", "penalty_start") + DRY_KEYS + SHAPE_KEYS}
+        self.model.set_sampling(slot=slot, **plain)
+        ext = (float(sampling.get("min_p") or 0.0), float(sampling.get("epsilon_cutoff") or 0.0))
+        set_ext = getattr(self.model, "set_sampling_ext", None)
+        if set_ext is not None:
+            set_ext(*ext, slot=slot)
+        elif any(ext):
+            raise DtkError("this device takes no min_p / epsilon_cutoff")
+        # the presence / frequency penalty likewise (penalty_start: the prompt length unless the sequence says otherwise); the
+        # fork / prefill / resume that follows builds the slot's count table from the sequence's ids
+        set_pen = getattr(self.model, "set_penalties", None)
+        if set_pen is not None:
+            set_pen(pen[0], pen[1], (n_ids if pen[2] is None else pen[2]) if (pen[0] or pen[1]) else 0, slot=slot)
+        elif pen[0] or pen[1]:
+            raise DtkError("this device takes no presence / frequency penalty")
+        # DRY likewise (dry_start: the prompt length unless the sequence says otherwise)
+        set_dry = getattr(self.model, "set_dry", None)
+        if set_dry is not None:
+            set_dry(dry[0], dry[1], dry[2], (n_ids if dry[3] is None else dry[3]) if dry[0] else 0, dry[4], slot=slot)
+        elif dry[0]:
+            raise DtkError("this device takes no DRY penalty")
+        # the length rules and the bias table likewise (length_start: the prompt length unless the sequence says otherwise); both are
+        # static for the sequence, whatever the fork / prefill / resume does
+        set_len = getattr(self.model, "set_length_control", None)
+        if set_len is not None:
+            set_len(shape[0], shape[1], shape[2], shape[3], slot=slot)
+        elif shape[3]:
+            raise DtkError("this device takes no length control")
+        set_bias = getattr(self.model, "set_logit_bias", None)
+        if set_bias is not None:
+            set_bias(shape[4], slot=slot)
+        elif shape[4]:
+            raise DtkError("this device takes no logit bias")
+
+    def _enter(self, slot: int, ids, pixel_values, want, text: Dict[str, Any], slot_key: int, resume: bool):
+        """the prompt into its slot: resume in place | fork the prefix (+ tail prefill) | full prefill"""
+        if resume:
+            self.model.resume_slot(slot, ids, slot_key if want is not None else 0)
+            forked = 2
+        else:
+            forked = self._fork_prefix(slot, ids, pixel_values, want, text) if want is not None else 0
+            if want is None:
+                self.slot_img.pop(slot, None)
+        if forked == 2:
+            pass    # the prompt IS the prefix (rollout from the root): KV and logits were forked, nothing to run
+        elif forked:
+            self.model.prefill(ids, pixel_values, slot=slot, reuse=True, **text)    # only the tail beyond the prefix
+        else:
+            self.model.prefill(ids, pixel_values, slot=slot, **text)
+
     def _prefix_key(self, ids, image_key: int, text_key: int):
         """(image key, text key, prefix length) if the prompt starts with its image-token run, else None"""
         tok = self.model.config.image_token_id
@@ -402,7 +562,9 @@ class BatchEngine:
     def _launch(self):
         # a slot whose context is full cannot take another (speculative) step; its sequence is at max_length
         lim = self.model.config.max_positions
-        slots = [s for s in sorted(self.active) if self.model.lib.dtk_context_len_slot(self.model._ctx, s) < lim]
+        room = lambda s: self.model.lib.dtk_context_len_slot(self.model._ctx, s) < lim      # noqa: E731
+        lead = [s for s in self.active if room(s) and (s not in self.partner or room(self.partner[s]))]
+        slots = sorted(lead + [self.partner[s] for s in lead if s in self.partner])      # a pair steps together or not at all
         if not slots or self.error is not None:
             return
         try:
@@ -442,9 +604,13 @@ class BatchEngine:
                 self.host_bound_steps += 1      # the GPU had already finished: this step waited for the host
             for s in self.inflight:
                 if s in self.active:
-                    if s in self.skip_first:        # the forced last prompt token of a resumed slot: already part of the prompt
+                    if s in self.skip_first:        # the forced last prompt token of a resumed slot (a pair: of both): already part of the prompt
                         self.skip_first.discard(s)
                         continue
+                    u = self.partner.get(s)
+                    if u is not None and u in self.inflight and toks[u] != toks[s]:      # the follower hands the leader's token over
+                        from .._lib import DtkError
+                        raise DtkError(f"guided pair ({s}, {u}): the unconditional slot reported token {toks[u]}, the conditional slot {toks[s]}")
                     if s in self.lp_sinks:
                         self.lp_sinks[s].logprobs.append(lps[s])
                         self.lp_sinks[s].sample_logprobs.append(slps[s])
@@ -608,7 +774,12 @@ def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_
     holds it, without a prefill (BatchEngine resume_in_place; False = fork the image prefix + prefill the path on every join).  Yields (image index, score, document) in completion order.  Tree k (image k //
     trees_per_image) samples with the seed stream seeds[k] (default seed_base + k).
     `texts` (a model with the TikZero adapter): one optional text per image that conditions its searches (the prompt, and the
-    reward's reference features); an image may be None when its text is given (the adapter's dummy image)."""
+    reward's reference features); an image may be None when its text is given (the adapter's dummy image).
+    guidance_scale= (with negative_image= / negative_text=, in gen_kwargs or the pipeline's): every rollout is classifier-free-guided.
+    A guided tree decodes in two slots — its own and the negative branch's — so at most decode_slots // 2 trees decode at once (the
+    rest take turns, as with `slots` < trees) and the engine reserves that many standing pairs; the negative image is encoded once and
+    forked into every tree's second slot.  A text-only entry without negative_text raises the generator's ValueError before any thread
+    starts."""
     import torch
     texts = list(texts) if texts is not None else [None] * len(images)
     assert len(texts) == len(images), "one text (or None) per image"
@@ -624,8 +795,24 @@ def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_
     assert len(seeds) == trees, "one seed per tree"
     # more trees than decode slots (the model's, or `slots`): a join waits for a slot to come free (BatchEngine.sequence), i.e. for
     # another tree to finish its rollout and go off to its reward — with rewards that take seconds that keeps the batch full
-    engine = make_engine(pipeline.model, processor=pipeline.processor, max_batch=min(trees, slots) if slots else trees, gather=trees,
-                         resume_in_place=resume_in_place) if trees > 1 else None
+    from ..model.modeling import check_guidance_scale
+    options = {**getattr(pipeline, "gen_kwargs", {}), **gen_kwargs}
+    guided = check_guidance_scale(options.get("guidance_scale")) != 1.0
+    if guided:
+        for im, txt in zip(imgs, texts):
+            if im is None and options.get("negative_text") is None:
+                raise ValueError("guidance_scale with a text-only prompt needs negative_text: the negative branch is the adapter's dummy input "
+                                 "under another text (it cannot be prefilled without one)")
+    width = min(trees, slots) if slots else trees
+    pairs = {}
+    if guided and trees > 1:
+        probe = getattr(pipeline.model, "max_decode_slots", None)
+        dec = int(probe()) if callable(probe) else int(pipeline.model.num_slots())
+        width = max(1, min(width, dec // 2))
+        pairs = dict(guided_pairs=width)
+        width *= 2
+    engine = make_engine(pipeline.model, processor=pipeline.processor, max_batch=width, gather=min(trees, width // 2) if guided else trees,
+                         resume_in_place=resume_in_place, **pairs) if trees > 1 else None
     out: "queue.Queue" = queue.Queue()
     trace_path = os.environ.get("DTK_TRACE_MCTS")
     trace: Optional[List[Tuple[float, int, str]]] = [(time.perf_counter(), -1, "start")] if trace_path else None

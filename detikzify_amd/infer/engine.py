@@ -157,6 +157,9 @@ class _ScriptedOps:
         def logit_bias(dev, slot, ids, values, n):
             model.set_logit_bias(tuple((int(ids[i]), float(values[i])) for i in range(int(n))), slot=slot)
 
+        def guidance(dev, cond, uncond, scale):
+            model.set_guidance(float(scale), int(cond), int(uncond) if uncond >= 0 else None)
+
         def fork(dev, a, b, n):
             model.kv_fork(a, b, n)
 
@@ -184,6 +187,7 @@ class _ScriptedOps:
         self.dry = O.DRY(guard(dry)) if hasattr(model, "set_dry") else None
         self.length_control = O.LENGTH_CTL(guard(length_control)) if hasattr(model, "set_length_control") else None
         self.logit_bias = O.LOGIT_BIAS(guard(logit_bias)) if hasattr(model, "set_logit_bias") else None
+        self.guidance = O.GUIDANCE(guard(guidance)) if hasattr(model, "set_guidance") else None
 
 
 def _has_adapter(model) -> bool:
@@ -198,7 +202,10 @@ class NativeBatchEngine:
 
     def __init__(self, model, max_batch: Optional[int] = None, share_prefix: bool = True, pipeline: bool = True, gather: int = 0,
                  gather_timeout: float = 0.5, prefix_slots: Optional[int] = None, resume_in_place: bool = True,
-                 flush_tokens: Optional[Iterable[int]] = None, flush_max: int = 32):
+                 flush_tokens: Optional[Iterable[int]] = None, flush_max: int = 32, guided_pairs: int = 0):
+        """`guided_pairs`=P > 0: up to P classifier-free-guided sequences (sequence(guidance=...), model.generate's guidance_scale)
+        decode at once, each in two slots; the device's pair table is reserved for P standing pairs (model.reserve_guidance), so a
+        pair that forms or dissolves re-captures nothing.  0 (the default): nothing is reserved and guided sequences are refused."""
         n = model.num_slots()
         if n <= 0:
             raise ValueError("model was loaded without batch slots (load(..., batch_slots=N))")
@@ -209,6 +216,9 @@ class NativeBatchEngine:
         self.decode_slots = dec
         self.share_prefix = share_prefix and n >= 2
         self.capacity = min(dec, max_batch) if max_batch else (dec if n > dec else dec - 1)
+        self.guided_pairs = int(guided_pairs)
+        if self.guided_pairs < 0 or 2 * self.guided_pairs > self.capacity:
+            raise ValueError(f"guided_pairs = {guided_pairs}: every guided sequence takes two of the engine's {self.capacity} decode slots")
         spare = n - self.capacity       # slots the decode batch does not need hold image prefixes (see BatchEngine)
         n_prefix = min(spare, 8 if prefix_slots is None else int(prefix_slots)) if self.share_prefix else 0
         self.prefix_slots: List[int] = list(range(n - n_prefix, n))
@@ -243,8 +253,17 @@ class NativeBatchEngine:
                 rc = self.lib.dtk_engine_set_length_control_op(self._h, self._scripted.length_control)
             if rc == 0 and self._scripted.logit_bias is not None and hasattr(self.lib, "dtk_engine_set_logit_bias_op"):
                 rc = self.lib.dtk_engine_set_logit_bias_op(self._h, self._scripted.logit_bias)
+            if rc == 0 and self.guided_pairs and self._scripted.guidance is not None:
+                rc = self.lib.dtk_engine_set_guidance_op(self._h, self._scripted.guidance)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
+        if self.guided_pairs:
+            try:
+                model.reserve_guidance(self.guided_pairs)
+            except BaseException:
+                self.lib.dtk_engine_destroy(self._h)
+                self._h = C.c_void_p()
+                raise
         if not pipeline:
             self.lib.dtk_engine_set_option(self._h, b"depth", 1)
         self.has_flush_tokens = False
@@ -285,6 +304,12 @@ class NativeBatchEngine:
             self._final = self.native_stats()
             h, self._h = self._h, C.c_void_p()
             self.lib.dtk_engine_destroy(h)
+            if self.guided_pairs:       # the loop has stopped, no step is in flight: the pairs it left and the reservation go
+                for slot in range(self.decode_slots):
+                    g = self.model.guidance(slot)
+                    if g is not None and g["is_cond"]:
+                        self.model.set_guidance(None, slot, None)
+                self.model.reserve_guidance(0)
         if getattr(self.model, "batch_engine", None) is self:
             self.model.batch_engine = None
 
@@ -385,39 +410,62 @@ class NativeBatchEngine:
     @contextmanager
     def sequence(self, ids, pixel_values, sampling: Dict[str, Any], owner: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  stop_ids: Iterable[int] = (), per_token: bool = True, text_ids=None, logprobs: bool = False,
-                 top_logprobs: Optional[int] = None) -> Iterator[_NativeSequence]:
+                 top_logprobs: Optional[int] = None, guidance: Optional[Dict[str, Any]] = None) -> Iterator[_NativeSequence]:
         """`owner`: see BatchEngine.sequence.  `max_new_tokens` / `stop_ids`: the sequence's own end (the native loop stops it there);
         `per_token`: the reader is woken for every token (arbitrary stopping criteria / foreign streamers) instead of per line.
         `text_ids`: one unpadded text that conditions the tower (the adapter); pixel_values may then be None (the dummy image).
         `logprobs`: the sequence collects its tokens' (logprob, sample_logprob) in `.logprobs` / `.sample_logprobs`.  The first such
         sequence switches the device over, which needs every slot free: ask for it before other sequences join (or call
-        model.enable_logprobs() before the engine is built)."""
+        model.enable_logprobs() before the engine is built).
+        `guidance`: dict(scale=, ids=, pixel_values=, text_ids=) — a classifier-free-guided sequence (an engine built with
+        guided_pairs > 0): the negative branch (its prompt, image and / or text) decodes in a second slot of its own, planned like the
+        sequence's — its own prefix key, so one negative image is encoded once and forked into every guided sequence's second slot, its
+        own slot per owner for resume — and both slots are released together.  `sampling`, `max_new_tokens` and `stop_ids` describe the
+        sequence; the second slot samples nothing of its own."""
         if top_logprobs:
             raise NotImplementedError("top_logprobs: not in the batch engines yet")
         if not self._h:
             raise _lib.DtkError("the batch engine is closed")
-        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, text_key
-        ids = ids.detach().to("cpu", torch.int64).reshape(-1).contiguous()
+        if guidance is not None and not self.guided_pairs:
+            raise NotImplementedError("guidance_scale: not in the batch engines yet (this engine was built without guided_pairs=)")
+        from ..model.modeling import DUMMY_IMAGE_KEY, adapter_text, check_guidance_scale, text_key
+
+        def plan_of(ids, pixel_values, text_ids):
+            """the part of a join that is the prompt's own: (join, prefix key, the tensors it points into)"""
+            ids = ids.detach().to("cpu", torch.int64).reshape(-1).contiguous()
+            tids = adapter_text(text_ids) if text_ids is not None else None
+            tkey = text_key(tids) if tids is not None else 0
+            if tids is not None and not hasattr(self.lib, "dtk_engine_submit_text"):
+                raise _lib.DtkError("this library has no dtk_engine_submit_text: text-conditioned sequences cannot join the batch")
+            ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
+            want = self._prefix_key(ids, ikey, tkey) if (self.share_prefix and (pixel_values is not None or tids is not None)) else None
+            px = None
+            if pixel_values is not None:
+                px = pixel_values.detach().to("cpu", torch.float32).contiguous()
+                if px.dim() == 4:
+                    if px.shape[0] != 1:
+                        raise ValueError("batch size 1 only")
+                    px = px[0]
+            j = _lib.DtkJoin()
+            j.n_ids, j.ids = int(ids.numel()), ids.data_ptr()
+            j.pixels = px.data_ptr() if px is not None else None
+            j.image_key = ikey
+            j.prefix_src = -1
+            j.full_flags = (_lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE) if getattr(self.model, "reuse_prefix", False) else 0
+            if self._scripted is not None and pixel_values is not None:
+                self._pixels_by_key[int(ikey)] = pixel_values
+            return j, want, ids, px, tids, tkey
+
+        j, want, ids, px, tids, tkey = plan_of(ids, pixel_values, text_ids)
         n_ids = int(ids.numel())
-        tids = adapter_text(text_ids) if text_ids is not None else None
-        tkey = text_key(tids) if tids is not None else 0
-        if tids is not None and not hasattr(self.lib, "dtk_engine_submit_text"):
-            raise _lib.DtkError("this library has no dtk_engine_submit_text: text-conditioned sequences cannot join the batch")
-        ikey = self.model.image_key(pixel_values) if pixel_values is not None else (DUMMY_IMAGE_KEY if tids is not None else 0)
-        want = self._prefix_key(ids, ikey, tkey) if (self.share_prefix and (pixel_values is not None or tids is not None)) else None
-        px = None
-        if pixel_values is not None:
-            px = pixel_values.detach().to("cpu", torch.float32).contiguous()
-            if px.dim() == 4:
-                if px.shape[0] != 1:
-                    raise ValueError("batch size 1 only")
-                px = px[0]
-        j = _lib.DtkJoin()
-        j.n_ids, j.ids = n_ids, ids.data_ptr()
-        j.pixels = px.data_ptr() if px is not None else None
-        j.image_key = ikey
-        j.prefix_src = -1
-        j.full_flags = (_lib.DTK_PREFILL_REUSE_PREFIX | _lib.DTK_PREFILL_REUSE_IMAGE) if getattr(self.model, "reuse_prefix", False) else 0
+        gj = gwant = gids = gpx = gtids = None
+        gtkey, gscale = 0, 1.0
+        if guidance is not None:
+            gscale = check_guidance_scale(guidance.get("scale"))
+            if gscale == 1.0:
+                raise ValueError("sequence(guidance=...): a scale of 1 is no guidance")
+            g_in = guidance.get("ids")
+            gj, gwant, gids, gpx, gtids, gtkey = plan_of(ids if g_in is None else g_in, guidance.get("pixel_values"), guidance.get("text_ids"))
         s = j.sampling
         s.do_sample, s.temperature = int(bool(sampling.get("do_sample", False))), float(sampling.get("temperature", 1.0))
         s.top_p, s.top_k = float(sampling.get("top_p", 1.0)), int(sampling.get("top_k", 0) or 0)
@@ -457,37 +505,25 @@ class NativeBatchEngine:
         j.max_new_tokens = int(max_new_tokens) if max_new_tokens is not None else (1 << 30)
         j.flush_mode = 0 if per_token else 1
         j.flush_max = self.flush_max
-        if self._scripted is not None and pixel_values is not None:
-            self._pixels_by_key[int(j.image_key)] = pixel_values
 
-        ticket = C.c_uint64(0)
-        held_through = False
-        with self._cv:
-            if logprobs and not self._lp:
-                if len(self.free) < self.capacity and not self.model.logprobs_enabled:
-                    raise _lib.DtkError("sequence(logprobs=True): log-probabilities are switched on before the first join, not while "
-                                        "sequences hold slots")
-                self._enable_logprobs()
-            while not self.free:
-                self._cv.wait()
-            order = sorted(self.free)
-            slot, cands = None, []
+        def pick(j, want, n_ids, last_tok, has_px, order, okey, cands_ok):
+            """(under _cv) the slot of one prompt among the free slots `order` and where it may resume: fills j.slot / j.try_resume"""
             # resume in place: the prompt (all but its last token) is still in a free slot's cache — an MCTS tree coming back to a
             # node of its own previous rollout.  Whether that holds is decided by the native loop when the join executes
             # (dtk_slot_lcp behind every step in flight); the plan here only names where to look.  An owner looks in the slot IT used
             # last (so that resume-or-prefill never depends on which other slots happen to be free: BatchEngine.sequence).
-            self._check_adapter_epoch()
-            may_resume = (self.resume_in_place and n_ids >= 2 and (want is not None or pixel_values is None)
-                          and int(ids[-1]) != self.model.config.image_token_id)
+            slot, cands = None, []
+            may_resume = (self.resume_in_place and n_ids >= 2 and (want is not None or not has_px)
+                          and last_tok != self.model.config.image_token_id)
             holds = (lambda f: self.slot_img.get(f) == want) if want is not None else (lambda f: f not in self.slot_img)
-            if may_resume and owner is not None:
-                last = self.last_slot.get(owner)
-                if last in self.free and holds(last):
+            if may_resume and okey is not None:
+                last = self.last_slot.get(okey)
+                if last in order and holds(last):
                     slot, j.try_resume = last, 1
-            elif may_resume:
+            elif may_resume and cands_ok:
                 cands = [f for f in order if holds(f)]
-            if slot is None and owner is not None and self.last_slot.get(owner) in self.free:
-                slot = self.last_slot[owner]
+            if slot is None and okey is not None and self.last_slot.get(okey) in order:
+                slot = self.last_slot[okey]
             if slot is None:
                 slot = next((f for f in order if f not in self.slot_img), None)
             if slot is None and want is not None:
@@ -495,14 +531,32 @@ class NativeBatchEngine:
             if slot is None:
                 slot = order[0]
             j.slot = slot
+            if okey is not None:
+                self.last_slot[okey] = slot
+            return slot, cands
+
+        ticket = C.c_uint64(0)
+        held_through = False
+        if guidance is not None:
+            cond = dict(j=j, want=want, ids=ids, tids=tids, tkey=tkey, has_px=pixel_values is not None, keep=px)
+            neg = dict(j=gj, want=gwant, ids=gids, tids=gtids, tkey=gtkey, has_px=guidance.get("pixel_values") is not None, keep=gpx)
+            tables = dict(ext=ext, pen=(pen_p, pen_f, pen_s), dry=dry, lctl=lctl, bias=(bias_ids, bias_val, len(bias_pairs)))
+            yield from self._guided(cond, neg, gscale, owner, logprobs, tables, pick)
+            return
+        with self._cv:
+            if logprobs:
+                self._want_logprobs()
+            while not self.free:
+                self._cv.wait()
+            order = sorted(self.free)
+            self._check_adapter_epoch()
+            slot, cands = pick(j, want, n_ids, int(ids[-1]), pixel_values is not None, order, owner, True)
             if cands:
                 j.try_resume, j.n_candidates = 1, len(cands)
                 for i, f in enumerate(cands):
                     j.candidates[i] = f
             apply = self._plan_prefix(j, slot, want) if want is not None else (lambda: self.slot_img.pop(slot, None))
             self.free.remove(slot)
-            if owner is not None:
-                self.last_slot[owner] = slot
             if has_shape:     # the sequence's length rules and bias pairs (and everything below) go with its join (text or not)
                 tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
                 rc = self.lib.dtk_engine_submit_shape(self._h, C.byref(j), C.byref(ext), C.c_float(pen_p), C.c_float(pen_f), int(pen_s), C.byref(dry),
@@ -548,26 +602,99 @@ class NativeBatchEngine:
             rc = self.lib.dtk_engine_await(self._h, ticket.value)
         joined = rc == 0
         try:
-            if not joined:
-                text = j.error_out.decode(errors="replace")
-                if "image patch tokens" in text:
-                    raise ValueError(text[text.index("The "):] if "The " in text else text)      # the reference's own ValueErrors
-                raise _lib.DtkError(f"join of a sequence failed ({rc}): {text}")
-            with self._cv:
-                self.joins += 1
-                if j.how_out == _lib.DTK_JOIN_RESUMED:
-                    self.resumes += 1
-                elif j.how_out == _lib.DTK_JOIN_IN_PLACE:
-                    self.inplace_reuses += 1
+            self._joined(j, joined, f"join of a sequence failed ({rc})")
             yield _NativeSequence(self, slot, logprobs)
         finally:
             if joined and self._h:
                 self.lib.dtk_engine_leave(self._h, slot)
             with self._cv:
                 if not joined:
-                    self.slot_img.pop(slot, None)       # the prompt did not get there: the slot holds nobody's prefix
-                    if j.prefix_encode and want is not None and self.prefix_cache.get(want) == j.prefix_src:
-                        self.prefix_cache.pop(want, None)      # ... and neither does the prefix-cache slot it was to be encoded into
+                    self._forget(slot, j, want)
                 self.free.append(slot)
                 self._cv.notify_all()
             del ids, px, tids     # (kept alive until here: the native join read them)
+
+    def _want_logprobs(self):
+        """(under _cv) sequence(logprobs=True): the first such sequence switches the device over, before any sequence holds a slot"""
+        if not self._lp:
+            if len(self.free) < self.capacity and not self.model.logprobs_enabled:
+                raise _lib.DtkError("sequence(logprobs=True): log-probabilities are switched on before the first join, not while "
+                                    "sequences hold slots")
+            self._enable_logprobs()
+
+    def _joined(self, j, joined: bool, what: str):
+        """the outcome of an awaited join: its error, or the engine's counters"""
+        if not joined:
+            text = j.error_out.decode(errors="replace")
+            if "image patch tokens" in text:
+                raise ValueError(text[text.index("The "):] if "The " in text else text)      # the reference's own ValueErrors
+            raise _lib.DtkError(f"{what}: {text}")
+        with self._cv:
+            self.joins += 1
+            if j.how_out == _lib.DTK_JOIN_RESUMED:
+                self.resumes += 1
+            elif j.how_out == _lib.DTK_JOIN_IN_PLACE:
+                self.inplace_reuses += 1
+
+    def _guided(self, cond, neg, scale, owner, logprobs, tables, pick):
+        """sequence(guidance=...): two slots, two plans (`cond`, `neg`: join, prefix key and tensors of each prompt), one native command
+        (dtk_engine_submit_guided) that carries the sequence's `tables`.  The negative branch is planned after the sequence's own
+        bookkeeping has been applied, so the two never claim the same prefix-cache slot; an owner's negative branch remembers its slot
+        under (owner, "uncond")."""
+        ticket = C.c_uint64(0)
+        j, gj, tids = cond["j"], neg["j"], cond["tids"]
+        g = _lib.DtkGuided()
+        g.cond, g.uncond = C.pointer(j), C.pointer(gj)
+        g.uncond_text_ids = neg["tids"].data_ptr() if neg["tids"] is not None else None
+        g.n_uncond_text = int(neg["tids"].numel()) if neg["tids"] is not None else 0
+        g.uncond_text_key, g.scale = neg["tkey"], scale
+        slots = []
+        with self._cv:
+            if logprobs:
+                self._want_logprobs()
+            while len(self.free) < 2:
+                self._cv.wait()
+            self._check_adapter_epoch()
+            order = sorted(self.free)
+            for side, okey in ((cond, owner), (neg, None if owner is None else (owner, "uncond"))):
+                slot, _ = pick(side["j"], side["want"], int(side["ids"].numel()), int(side["ids"][-1]), side["has_px"], order, okey, False)
+                (self._plan_prefix(side["j"], slot, side["want"]) if side["want"] is not None else (lambda s_=slot: self.slot_img.pop(s_, None)))()
+                order = [f for f in order if f != slot]
+                slots.append(slot)
+            slot, uslot = slots
+            self.free.remove(slot)
+            self.free.remove(uslot)
+            (pen_p, pen_f, pen_s), (bias_ids, bias_val, n_bias) = tables["pen"], tables["bias"]
+            tp = C.cast(tids.data_ptr(), C.POINTER(C.c_int64)) if tids is not None else None
+            rc = self.lib.dtk_engine_submit_guided(self._h, C.byref(g), C.byref(tables["ext"]), C.c_float(pen_p), C.c_float(pen_f), int(pen_s),
+                                                   C.byref(tables["dry"]), C.byref(tables["lctl"]), bias_ids, bias_val, n_bias, tp,
+                                                   int(tids.numel()) if tids is not None else 0, C.c_uint64(cond["tkey"]), C.byref(ticket))
+            if rc != 0:
+                self._forget(slot, j, cond["want"])
+                self._forget(uslot, gj, neg["want"])
+                self.free += [slot, uslot]
+                self._cv.notify_all()
+                raise _lib.DtkError(f"dtk_engine_submit_guided failed ({rc}): {j.error_out.decode(errors='replace')}")
+        joined = self.lib.dtk_engine_await(self._h, ticket.value) == 0
+        try:
+            self._joined(j, joined, "join of a guided sequence failed")
+            seq = _NativeSequence(self, slot, logprobs)
+            seq.uncond_slot, seq.how, seq.uncond_how = uslot, int(j.how_out), int(gj.how_out)
+            yield seq
+        finally:
+            if joined and self._h:
+                self.lib.dtk_engine_leave(self._h, slot)       # ends both
+            with self._cv:
+                if not joined:
+                    self._forget(slot, j, cond["want"])
+                    self._forget(uslot, gj, neg["want"])
+                self.free += [slot, uslot]
+                self._cv.notify_all()
+            del cond, neg     # (the tensors the native join read were kept alive until here)
+
+    def _forget(self, slot, j, want):
+        """(under _cv) the prompt did not get into `slot`: it holds nobody's prefix, and neither does the prefix-cache slot the prefix
+        was to be encoded into"""
+        self.slot_img.pop(slot, None)
+        if j.prefix_encode and want is not None and self.prefix_cache.get(want) == j.prefix_src:
+            self.prefix_cache.pop(want, None)

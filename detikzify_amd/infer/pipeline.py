@@ -63,7 +63,7 @@ class DetikzifyPipeline:
         logit_bias / sequence_bias: all gen_kwargs, here and in simulate) chose it with.  top_logprobs=k (1 .. 8, with return_logprobs=True)
         also attaches `.token_top_ids` / `.token_top_logprobs`: per generated token the k most likely tokens at its position.
 
-        guidance_scale=g (with negative_image= / negative_text=; gen_kwargs too, here and in the sequential simulate): classifier-free
+        guidance_scale=g (with negative_image= / negative_text=; gen_kwargs too, here and in simulate, sequential or trees=N): classifier-free
         guidance of model.generate against a negative prompt — by default a white canvas of the processor's size; a text-only prompt
         needs negative_text.  The model must have been loaded with batch_slots >= 2.  Under guidance the attached log-probabilities
         and alternatives describe the guided distribution."""
@@ -124,7 +124,9 @@ class DetikzifyPipeline:
 
         `trees` > 1 (not in the reference): that many independent searches of the same image (and / or text) decoded as ONE
         batch on this GPU (infer/batching.py; the model must have been loaded with batch_slots > trees), each with its own
-        `expansions` / `timeout` budget — root parallelisation; results arrive in completion order."""
+        `expansions` / `timeout` budget — root parallelisation; results arrive in completion order.  guidance_scale= (with
+        negative_image= / negative_text=) works here too: every tree then decodes in two of the engine's slots (its own and the
+        negative branch's), so at most decode_slots // 2 trees decode at once and the rest take turns."""
         if trees > 1:
             from .batching import simulate_parallel
             assert preprocess, "parallel trees take the default preprocessing"

@@ -1119,6 +1119,17 @@ class DetikzifyForCausalLM:
         u = -1 if uncond_slot is None else int(uncond_slot)
         self._check(self.lib.dtk_set_guidance(self._ctx, int(cond_slot), u, g), "dtk_set_guidance")
 
+    def reserve_guidance(self, n_pairs: int) -> None:
+        """standing pairs (dtk_reserve_guidance): the captured batched steps are shaped for n_pairs guided pairs from here on, so forming
+        or dissolving a pair or changing its scale only writes the device's pair table and re-captures nothing; a live pair computes what
+        it computes without a reservation, bit for bit.  0 ends the reservation.  Refused while a batch step is in flight"""
+        self._check(self.lib.dtk_reserve_guidance(self._ctx, int(n_pairs)), "dtk_reserve_guidance")
+
+    @property
+    def batch_graph_captures(self) -> int:
+        """captures of a batched decode step since the context was created (a re-capture shows as an increment)"""
+        return int(self.lib.dtk_batch_graph_captures(self._ctx))
+
     def guidance(self, slot: int) -> Optional[Dict[str, Any]]:
         """diagnostic: the guided pair `slot` is in — {partner, is_cond, scale, lse: (Lc, Lu) of the pair's last step} — or None"""
         partner, is_cond, scale, lse = C.c_int(-1), C.c_int(0), C.c_float(1.0), (C.c_float * 2)()
@@ -1341,7 +1352,8 @@ class DetikzifyForCausalLM:
         alternatives of top_logprobs, logit_bias, the penalties, DRY, the length rules, the suppression lists, temperature, top-k,
         top-p, min-p, epsilon, greedy included (HF's processor order).  Consequently `.logprobs`, `.top_ids` and
         `.top_logprobs` of a guided call describe the GUIDED distribution (out[t] - logsumexp(out)), not the model's own.  Not in the
-        batch engines yet; contexts without slots (tl-1.1b, MXFP4) have no guidance.
+        batch engines yet, unless the engine was built with guided_pairs=P (the pair then decodes in two of the engine's slots, the same
+        tokens and log-probabilities); contexts without slots (tl-1.1b, MXFP4) have no guidance.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1368,12 +1380,14 @@ class DetikzifyForCausalLM:
             if negative_prompt_ids is None and negative_pixel_values is None and negative_adapter_input_ids is None:
                 raise ValueError(f"guidance_scale = {guide}: the negative branch must differ from the prompt in something — pass "
                                  "negative_prompt_ids, negative_pixel_values and / or negative_adapter_input_ids")
-            if self.batch_engine is not None:
-                raise NotImplementedError("guidance_scale: not in the batch engines yet")
+            if self.batch_engine is not None and not getattr(self.batch_engine, "guided_pairs", 0):
+                raise NotImplementedError("guidance_scale: not in the batch engines yet — unless the engine was built for it "
+                                          "(NativeBatchEngine / make_engine(..., guided_pairs=P))")
             if self.num_slots() < 2:
                 raise ValueError("guidance_scale needs two batch slots for the guided pair: load(..., batch_slots=2) or more "
                                  "(contexts without slots — tl-1.1b, MXFP4 — have no guidance)")
-            self._refuse_while_batch_busy("generate")
+            if self.batch_engine is None:
+                self._refuse_while_batch_busy("generate")
         if input_ids is None:
             input_ids = inputs
         ids = input_ids.detach().to("cpu", torch.int64)
@@ -1532,7 +1546,8 @@ class DetikzifyForCausalLM:
                     **({"presence_penalty": presence_penalty, "frequency_penalty": frequency_penalty, "penalty_start": penalty_start}
                        if (presence_penalty or frequency_penalty) else {}), **dry, **shape),
                     owner=sequence_owner, max_new_tokens=n_new_max, stop_ids=eos_set, per_token=per_token, text_ids=text_ids,
-                    **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {})) as seq:
+                    **({"logprobs": True} if return_logprobs else {}), **({"top_logprobs": topk} if topk else {}),
+                    **({"guidance": dict(scale=guide, ids=neg_ids[0], pixel_values=neg_px, text_ids=neg_text)} if guided else {})) as seq:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
                 if return_logprobs:
                     pairs = (seq.logprobs, seq.sample_logprobs)

@@ -980,11 +980,25 @@ int  dtk_engine_set_logit_bias_op(dtk_engine* e, int (*set_logit_bias_slot)(void
  *                      uncond_slot < 0 or scale == 1 dissolves the pair cond_slot heads (no pair: DTK_OK).  DTK_ERR_ARG for a slot out of
  *                      range, a slot already in another pair, equal slots, a scale outside the range or not finite; DTK_ERR_STATE while a
  *                      batch step is in flight.  At most DTK_MAX_BATCH / 2 pairs.  A pair is static for a sequence: dtk_prefill_slot,
- *                      dtk_resume_slot and dtk_kv_fork leave it alone.  Every change re-captures the batched step.
+ *                      dtk_resume_slot and dtk_kv_fork leave it alone.  Every change re-captures the batched step, unless the
+ *                      pairs stand (dtk_reserve_guidance).
+ *   dtk_reserve_guidance   standing pairs: from here on the captured batched steps (three tile counts, three multi-vector widths) launch
+ *                      the three kernels with n_pairs as the pair dimension of their grids whatever the number of live pairs; a block
+ *                      learns from the device table whether its entry is live (an unused entry has cond < 0 and returns before it reads
+ *                      anything else).  While the live pairs fit, dtk_set_guidance (form, dissolve, new scale) only writes the table
+ *                      and no capture is dropped; a pair beyond the reservation behaves as without one.  A live pair's blocks compute
+ *                      what they compute without a reservation, bit for bit.  n_pairs in 0 .. DTK_MAX_BATCH / 2 (DTK_ERR_ARG); 0 ends
+ *                      the reservation and, with no live pair, frees the table.  DTK_ERR_STATE while a batch step is in flight.  It
+ *                      allocates what the first dtk_set_guidance allocates.  A context that never calls it behaves as before.
+ *   dtk_batch_graph_captures   captures of a batched step since the context was created (a re-capture shows as an increment).
+ *   resumed pairs      dtk_resume_slot on both slots of a pair: in the step that forwards the two last prompt tokens k_cfg_lse and
+ *                      k_cfg_mix skip the pair (its rows are stale or were never written) and k_cfg_follow hands nothing over: each
+ *                      slot reports its own forced token with NaN log-probabilities; (Lc, Lu) keep their earlier values.
  *   dtk_get_guidance   diagnostic: slot's partner (-1: none), whether slot is the conditional one, the scale (1 without a pair) and
  *                      lse_out[2] = (Lc, Lu) of the pair's last step (NaN without a pair; meaningful once the pair has decoded a step since
  *                      the last dtk_set_guidance that changed the set of pairs); any out pointer may be NULL.
- *   dtk_decode_batch_launch   refuses (DTK_ERR_ARG, nothing launched) a step in which exactly one slot of a pair is active.
+ *   dtk_decode_batch_launch   refuses (DTK_ERR_ARG, nothing launched) a step in which exactly one slot of a pair is active, or in which
+ *                      exactly one slot of an active pair forwards a forced token (resume both slots or prefill both).
  *   dtk_op_cfg_mix     the two mixing kernels in the launch shape the step uses for that V, on two rows at stride V of the op scratch:
  *                      out[V] and lse_out[2] = (Lc, Lu).  2 <= V <= 262 144.  The 256 bytes behind out are checked (DTK_ERR_STATE).
  *   dtk_bench_cfg      tools/bench_cfg.py: HIP events around reps (1 .. 64) back-to-back launches on the context's own pairs and rows:
@@ -994,6 +1008,42 @@ int  dtk_set_guidance(dtk_ctx* ctx, int cond_slot, int uncond_slot, float scale)
 int  dtk_get_guidance(dtk_ctx* ctx, int slot, int* partner_out, int* is_cond_out, float* scale_out, float* lse_out /* [2] */);
 int  dtk_op_cfg_mix(dtk_ctx* ctx, const float* zc, const float* zu, int V, float scale, float* out /* [V] */, float* lse_out /* [2] */);
 int  dtk_bench_cfg(dtk_ctx* ctx, int reps, float* avg_us /* [2] */);
+int  dtk_reserve_guidance(dtk_ctx* ctx, int n_pairs);
+int64_t dtk_batch_graph_captures(const dtk_ctx* ctx);
+
+/* Guided sequences in the engine's slots (additive, ABI 7; dtk_abi_struct_size(18) = sizeof(dtk_guided)).  A guided sequence is ONE
+ * command that carries two joins: `cond`, the sequence itself (everything a dtk_join says), and `uncond`, the negative branch's own plan
+ * — slot, ids, pixels, image key, try_resume and the prefix plan; its sampling, budget, stop ids, flush fields and candidates are not
+ * used (n_candidates must be 0 in both: a pair is resumed where its owner left it).  dtk_engine_submit_guided takes the arguments of
+ * dtk_engine_submit_shape, which all describe the conditional slot; the unconditional slot gets neutral greedy sampling and no tables.
+ *   joining    both slots must be free, distinct decoding slots.  Pairs of earlier sequences that still hold either slot are dissolved
+ *              first (so are those an unguided join re-uses).  The two joins execute back to back with no step in flight.  The pair
+ *              resumes in place only if BOTH slots hold their prompt (dtk_slot_lcp >= n - 1 under each one's own key) and both joins ask
+ *              for it; otherwise both take their non-resume plan.  Then set_guidance(cond, uncond, scale).  A failure anywhere leaves no
+ *              pair and both slots free; cond->error_out has the text, cond->how_out / uncond->how_out each join's way.
+ *   stepping   the unconditional slot is a follower: it is launched and stopped with its leader (the budget is bounded by the smaller
+ *              room of the two slots), its tokens are not delivered, and dtk_engine_read / _read_lp / _leave on it return DTK_ERR_ARG.
+ *              Every collected step checks that both slots report the same token; a difference stops the engine (dtk_engine_last_error
+ *              names the pair).  The forced tokens of a resumed pair are dropped unseen.
+ *   ending     a stop id, the budget or dtk_engine_leave(cond) ends both at once; a step still in flight counts both slots as wasted.
+ *              dtk_engine_stats: tokens_out, joins and resumed count a pair once.  The device's pair is dissolved by the next join
+ *              that uses one of its slots (a pair with neither slot active launches nothing).
+ * Engines from dtk_engine_create_ops get the device's pairing through dtk_engine_set_guidance_op (the signature of dtk_set_guidance;
+ * cond, -1, 1 dissolves); without it dtk_engine_submit_guided fails with DTK_ERR_STATE and says so.  dtk_engine_create wires
+ * dtk_set_guidance itself. */
+typedef struct dtk_guided {
+  dtk_join* cond;                   /* the sequence's join                                                                    */
+  dtk_join* uncond;                 /* the negative branch's plan                                                             */
+  const int64_t* uncond_text_ids;   /* the negative branch's own text (the adapter), or NULL                                   */
+  int32_t n_uncond_text;
+  float   scale;                    /* finite, in [0, 100], not 1                                                              */
+  uint64_t uncond_text_key;
+} dtk_guided;
+int  dtk_engine_submit_guided(dtk_engine* e, const dtk_guided* g, const dtk_sampling_ext* x /* or NULL */, float presence, float frequency,
+                              int start, const dtk_dry* d /* or NULL */, const dtk_length_ctl* l /* or NULL */, const int32_t* bias_ids,
+                              const float* bias_values, int n_bias, const int64_t* text_ids, int n_text, uint64_t text_key,
+                              uint64_t* ticket_out);
+int  dtk_engine_set_guidance_op(dtk_engine* e, int (*set_guidance)(void* dev, int cond_slot, int uncond_slot, float scale));
 
 #ifdef __cplusplus
 }
