@@ -345,7 +345,16 @@ SYMBOLS = {
                                            C.POINTER(DtkLengthCtl), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
                                            C.POINTER(C.c_int64), C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dtk_engine_set_guidance_op": (C.c_int, [_P, DtkEngineOps.GUIDANCE]),
+    # prompt-lookup speculative decoding of slot 0 in the multi-vector step
+    "dtk_spec_begin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
+    "dtk_spec_set_drafts": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
+    "dtk_spec_launch": (C.c_int, [_P]),
+    "dtk_spec_wait": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "dtk_spec_end": (C.c_int, [_P, C.c_int]),
+    "dtk_bench_spec": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
+    "dtk_op_spec_lookup": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
 }
+DTK_SPEC_LOOKUP, DTK_SPEC_TABLE, DTK_SPEC_MAX_NGRAM = 0, 1, 16
 
 _lib = None
 

@@ -838,22 +838,42 @@ static inline int max_decode_slots(const dtk_ctx* c) {
 void batch_step_launches_mv(dtk_ctx* c) {
   hipStream_t s = c->stream;
   const int d = c->d, ff = c->ff, NB = c->mv_step;
+  // a speculative step (dtk_spec_launch): the same launches over the vectors of ONE sequence — their own DecStates, slot 0's sampling
+  // record for every row, the step's own device BatchState, and every vector in slot 0's cache (slot stride 0, no shared-prefix source)
+  const bool spec = c->spec_step;
+  DecState* const st = spec ? c->spec_st : c->st_b;
+  const BatchState* const bs = spec ? c->spec_bs : c->bs_dev;
+  const size_t kv_stride = spec ? 0 : c->kv_slot_stride;
   SampleArgs sa;
-  sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
+  sa.logits = c->logits_b; sa.V = c->V; sa.sp = spec ? c->spec_sp : c->sp_b; sa.st = st; sa.embed = c->embed;
   sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
-  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
+  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = bs; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
   sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
   sa.trunc = c->trunc_batch ? 1 : 0;
   sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
-  guidance_launch(c, sa);            // (nothing without a guided pair)
-  top_logits_launch(c, sa);
-  sampler_launch(c, sa, c->mb_batch, true);
-  follow_launch(c, sa);              // (likewise)
+  if (spec) {
+    // the batched sampler over the pending rows of the vectors that were live in the previous step (dtk_spec_begin refuses a context
+    // with penalties, DRY, length rules, a bias, top_logprobs or a guided pair: the plain step's launch is this one), then the two
+    // kernels that turn the rows' tokens into the sequence's next tokens and the next step's vectors
+    if (c->mb_batch) launch_sample_mb(sa, s); else launch_sample_b(sa, s);
+    SpecArgs sv;
+    sv.sd = c->spec_sd; sv.hist = c->spec_hist; sv.table = c->spec_table;      // (K, the n-gram size and the draft source are read from spec_sd)
+    sv.K = 0; sv.max_ngram = 0; sv.NV = 0; sv.T_max = c->Tmax; sv.V = c->V;
+    sv.st_true = c->st_b; sv.st_vec = c->spec_st; sv.bs = c->spec_bs; sv.tok_ring = c->tokb_dev; sv.ring = DTK_MAX_INFLIGHT;
+    sv.embed = c->embed; sv.x = c->xb; sv.d = d;
+    launch_spec_accept(sv, s);
+    launch_spec_draft(sv, s);
+  } else {
+    guidance_launch(c, sa);            // (nothing without a guided pair)
+    top_logits_launch(c, sa);
+    sampler_launch(c, sa, c->mb_batch, true);
+    follow_launch(c, sa);              // (likewise)
+  }
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   GemvMvArgs g{};
-  g.bs = c->bs_dev; g.st = c->st_b; g.T_max = c->Tmax; g.d = d; g.ff = ff; g.H = c->H; g.KVH = c->KVH; g.eps = c->cfg.rms_eps;
-  g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.kv_slot_stride = c->kv_slot_stride;
+  g.bs = bs; g.st = st; g.T_max = c->Tmax; g.d = d; g.ff = ff; g.H = c->H; g.KVH = c->KVH; g.eps = c->cfg.rms_eps;
+  g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.kv_slot_stride = kv_stride;
   for (int l = 0; l < c->L; ++l) {
     const LayerW& w = c->layers[l];
     bf16_t* kc = c->kvb + (size_t)l * kv_layer;
@@ -864,7 +884,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
     launch_gemv_mv(PRO_RMSNORM, EPI_QKV, NB, g, s);
     // 2. attention: one block per (head, slot), output in fragment order
     AttnDecBArgs ad;
-    ad.q = c->qb; ad.kcache = kc; ad.vcache = vc; ad.kv_slot_stride = c->kv_slot_stride; ad.st = c->st_b; ad.bs = c->bs_dev;
+    ad.q = c->qb; ad.kcache = kc; ad.vcache = vc; ad.kv_slot_stride = kv_stride; ad.st = st; ad.bs = bs;
     ad.out = c->aob; ad.H = c->H; ad.T_max = c->Tmax; ad.d = d; ad.G = c->H / c->KVH; ad.nslots = NB;
     ad.scale = scale;
     ad.use_prefix = 0; ad.pfx_splits = c->pfx_splits; ad.tail_threads = c->mv_tail_threads; ad.gqa_fused = c->gqa_fused; ad.nt_private = c->attn_nt;
@@ -1076,6 +1096,11 @@ void drop_batch_graphs(dtk_ctx* c) {
     if (c->bgraph_exec[i]) { (void)hipGraphExecDestroy(c->bgraph_exec[i]); c->bgraph_exec[i] = nullptr; }
     if (c->bgraph[i]) { (void)hipGraphDestroy(c->bgraph[i]); c->bgraph[i] = nullptr; }
     c->bgraph_ready[i] = false;
+  }
+  for (int i = 0; i < 2; ++i) {      // the speculative steps are captures of the same launches (nothing there without dtk_spec_launch)
+    if (c->sgraph_exec[i]) { (void)hipGraphExecDestroy(c->sgraph_exec[i]); c->sgraph_exec[i] = nullptr; }
+    if (c->sgraph[i]) { (void)hipGraphDestroy(c->sgraph[i]); c->sgraph[i] = nullptr; }
+    c->sgraph_ready[i] = false;
   }
 }
 
@@ -1743,6 +1768,7 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->topb_host) (void)hipHostFree(c->topb_host);
   if (c->lseb_host) (void)hipHostFree(c->lseb_host);
   if (c->packed_rows) (void)hipFree(c->packed_rows);
+  if (c->spec_mem) (void)hipFree(c->spec_mem);
   if (c->stream_vit) (void)hipStreamDestroy(c->stream_vit);
   if (c->ev_va) (void)hipEventDestroy(c->ev_va);
   if (c->ev_vb) (void)hipEventDestroy(c->ev_vb);
@@ -2055,6 +2081,7 @@ static int prefill_impl(dtk_ctx* c, SeqHost& sh, bf16_t* kvbase, float* logits_d
                         const int64_t* text_ids = nullptr, int T_text = 0, const ScoreReq* score = nullptr) {
   if (!c || !ids || T < 1) return fail(c, DTK_ERR_ARG, "dtk_prefill: bad argument");
   if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
+  if (!is_single && c->spec_on) return fail(c, DTK_ERR_STATE, "prefill into a slot while slot 0 is speculating (dtk_spec_end first)");
   std::lock_guard<std::mutex> vit_guard(c->vit_mu);
   HIPCHK(c, hipSetDevice(c->device));
   // drain pending decode steps (their tokens are dropped)
@@ -2685,6 +2712,7 @@ int dtk_set_guidance(dtk_ctx* c, int cond_slot, int uncond_slot, float scale) {
     if (uncond_slot == cond_slot) return fail(c, DTK_ERR_ARG, "dtk_set_guidance: a pair needs two distinct slots (got %d twice)", cond_slot);
   }
   if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_set_guidance: a batch step is in flight");
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_set_guidance: slot 0 is speculating (dtk_spec_end first)");
   const int pc = cfg_find(c, cond_slot);
   int n = c->cfg_n;
   CfgPair next[DTK_MAX_BATCH / 2];
@@ -2792,6 +2820,7 @@ extern "C++" void build_prefix_groups(BatchState* hb, const int32_t* active, boo
 int dtk_decode_batch_launch(dtk_ctx* c, const int32_t* active) {
   if (!c || !active) return fail(c, DTK_ERR_ARG, "dtk_decode_batch_launch: null argument");
   if (c->nb <= 0) return fail(c, DTK_ERR_STATE, "context was created without batch slots");
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_decode_batch_launch: slot 0 is speculating (dtk_spec_end first)");
   if (c->blaunched - c->bwaited >= DTK_MAX_INFLIGHT) return fail(c, DTK_ERR_STATE, "too many batch steps in flight");
   int n_active = 0;
   for (int j = 0; j < DTK_MAX_BATCH; ++j) {
@@ -2867,6 +2896,7 @@ static void top_unpack(const TopRec* r, const float* lse, int k, int32_t* ids_ou
 
 static int decode_batch_wait_impl(dtk_ctx* c, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out,
                                   int32_t* top_ids_out = nullptr, float* top_logprob_out = nullptr) {
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_decode_batch_wait: the steps in flight are speculative ones (dtk_spec_wait)");
   if (c->bwaited >= c->blaunched) return fail(c, DTK_ERR_STATE, "no batch step in flight");
   HIPCHK(c, hipSetDevice(c->device));
   const uint64_t k = c->bwaited;
@@ -2925,6 +2955,202 @@ int dtk_decode_batch_wait_top(dtk_ctx* c, int64_t* tokens_out, float* logprob_ou
   return decode_batch_wait_impl(c, tokens_out, logprob_out, sample_logprob_out, top_ids_out, top_logprob_out);
 }
 
+// ---- prompt-lookup speculative decoding of slot 0 (include/dtk.h)
+static int spec_alloc(dtk_ctx* c) {
+  if (c->spec_mem) return DTK_OK;
+  size_t off = 0;
+  auto room = [&](size_t bytes) { const size_t at = off; off = align_up(off + bytes, 256); return at; };
+  const size_t o_sd = room(sizeof(SpecDev)), o_hist = room((size_t)c->Tmax * 4), o_tab = room((size_t)c->Tmax * 4);
+  const size_t o_st = room(4 * sizeof(DecState)), o_sp = room(4 * sizeof(SamplingDev)), o_bs = room(sizeof(BatchState));
+  HIPCHK(c, hipMalloc((void**)&c->spec_mem, off));
+  c->spec_sd = reinterpret_cast<SpecDev*>(c->spec_mem + o_sd);
+  c->spec_hist = reinterpret_cast<int32_t*>(c->spec_mem + o_hist);
+  c->spec_table = reinterpret_cast<int32_t*>(c->spec_mem + o_tab);
+  c->spec_st = reinterpret_cast<DecState*>(c->spec_mem + o_st);
+  c->spec_sp = reinterpret_cast<SamplingDev*>(c->spec_mem + o_sp);
+  c->spec_bs = reinterpret_cast<BatchState*>(c->spec_mem + o_bs);
+  return DTK_OK;
+}
+
+int dtk_spec_begin(dtk_ctx* c, int K, int max_ngram, int source) {
+  if (!c) return fail(c, DTK_ERR_ARG, "dtk_spec_begin: null context");
+  if (K < 1 || K > 3) return fail(c, DTK_ERR_ARG, "dtk_spec_begin: %d drafts per step is outside 1..3", K);
+  if (max_ngram < 1 || max_ngram > DTK_SPEC_MAX_NGRAM) return fail(c, DTK_ERR_ARG, "dtk_spec_begin: max_ngram %d is outside 1..%d", max_ngram, DTK_SPEC_MAX_NGRAM);
+  if (source != DTK_SPEC_LOOKUP && source != DTK_SPEC_TABLE) return fail(c, DTK_ERR_ARG, "dtk_spec_begin: draft source %d (DTK_SPEC_LOOKUP | DTK_SPEC_TABLE)", source);
+  if (!mv_family(c)) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: the context is outside the multi-vector family (2..5 batch slots): the verify pass is the multi-vector step");
+  if (max_decode_slots(c) < K + 1) return fail(c, DTK_ERR_ARG, "dtk_spec_begin: %d drafts per step need %d decoding slots, the context has %d", K, K + 1, max_decode_slots(c));
+  if (c->kv8) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: kv_format mxfp8 (the vectors of a step share slot 0's rows: bf16 contexts only)");
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot 0 is speculating already");
+  if (c->engine_holds.load() > 0) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: a batch engine holds sequences in the context's slots");
+  if (c->cfg_n) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: the context has a guided pair (dtk_set_guidance)");
+  if (c->top_logprobs) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: top_logprobs is on (its records are per slot and step)");
+  for (int j = 0; j < c->nb; ++j) {      // their tables depend on the position (and any slot's values change the sampler the step launches)
+    if (pen_on(c, 1 + j)) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot %d has a presence / frequency penalty", j);
+    if (dry_on(c, 1 + j)) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot %d has DRY", j);
+    if (len_on(c, 1 + j)) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot %d has length control or a logit bias", j);
+  }
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: a batch step is in flight");
+  SeqHost& sh = c->bseq[0];
+  if (!sh.have_logits) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot 0 has no pending logits (prefill it first)");
+  if (sh.forced_pending >= 0) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot 0 was resumed and forwards its last prompt token first (prefill it, or decode that step)");
+  const int n = (int)sh.cached_ids.size();
+  if (n < 1 || n != sh.host_next_pos || n > c->Tmax) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot 0 holds %d ids at length %d", n, sh.host_next_pos);
+  std::vector<int32_t> h((size_t)c->Tmax, 0), none((size_t)c->Tmax, -1);
+  for (int i = 0; i < n; ++i) {
+    if (sh.cached_ids[(size_t)i] < 0) return fail(c, DTK_ERR_STATE, "dtk_spec_begin: slot 0 has un-read tokens");
+    h[(size_t)i] = (int32_t)sh.cached_ids[(size_t)i];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (const int rc = spec_alloc(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->spec_hist, h.data(), (size_t)c->Tmax * 4, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->spec_table, none.data(), (size_t)c->Tmax * 4, hipMemcpyHostToDevice));
+  std::vector<BatchState> hb(1);
+  memset(hb.data(), 0, sizeof(BatchState));
+  hb[0].active[0] = 1;                     // only vector 0 has a pending row: slot 0's own
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) hb[0].share_src[j] = -1;
+  hb[0].step = (int32_t)(c->blaunched % DTK_MAX_INFLIGHT);
+  HIPCHK(c, hipMemcpy(c->spec_bs, hb.data(), sizeof(BatchState), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(c->spec_st, c->st_b, sizeof(DecState), hipMemcpyDeviceToDevice));
+  for (int j = 0; j < 4; ++j) HIPCHK(c, hipMemcpy(c->spec_sp + j, c->sp_b, sizeof(SamplingDev), hipMemcpyDeviceToDevice));
+  SpecDev sd{};
+  sd.drafts[0] = h[(size_t)n - 1]; sd.drafts[1] = sd.drafts[2] = sd.drafts[3] = -1; sd.n_live = 1;
+  sd.K = K; sd.NV = K + 1; sd.max_ngram = max_ngram; sd.use_table = source == DTK_SPEC_TABLE ? 1 : 0;
+  HIPCHK(c, hipMemcpy(c->spec_sd, &sd, sizeof sd, hipMemcpyHostToDevice));
+  for (int j = 1; j <= K; ++j) c->bseq[(size_t)j].have_logits = false;      // their logits rows and residual rows become the vectors'; their KV stays
+  c->spec_K = K; c->spec_src = source; c->spec_nv = K + 1;      // (the n-gram size lives in spec_sd alone)
+  c->spec_known_pos = n;
+  c->spec_on = true;
+  return DTK_OK;
+}
+
+int dtk_spec_set_drafts(dtk_ctx* c, const int32_t* table, int n) {
+  if (!c || (!table && n > 0) || n < 0) return fail(c, DTK_ERR_ARG, "dtk_spec_set_drafts: bad argument");
+  if (!c->spec_on || c->spec_src != DTK_SPEC_TABLE) return fail(c, DTK_ERR_STATE, "dtk_spec_set_drafts: slot 0 is not speculating from a table (dtk_spec_begin(.., DTK_SPEC_TABLE))");
+  if (n > c->Tmax) return fail(c, DTK_ERR_ARG, "dtk_spec_set_drafts: %d positions exceed max_positions %d", n, c->Tmax);
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_spec_set_drafts: a step is in flight");
+  std::vector<int32_t> t((size_t)c->Tmax, -1);
+  for (int i = 0; i < n; ++i) {
+    if (table[i] < -1 || table[i] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_spec_set_drafts: id %d at position %d (-1 or a token id)", table[i], i);
+    t[(size_t)i] = table[i];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(c->spec_table, t.data(), (size_t)c->Tmax * 4, hipMemcpyHostToDevice));
+  return DTK_OK;
+}
+
+static int ensure_spec_graph(dtk_ctx* c, int gi) {      // c->spec_step and c->mv_step are set
+  if (c->bgraph_trunc != c->trunc_batch) { drop_batch_graphs(c); c->bgraph_trunc = c->trunc_batch; }
+  if (c->sgraph_ready[gi]) return DTK_OK;
+  HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  c->launch_refused = false;
+  batch_step_launches_mv(c);
+  HIPCHK(c, hipMemcpyAsync(c->tokb_host, c->tokb_dev, sizeof(int64_t) * TOKB_WORDS, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, copy_lp_ring(c, true));
+  HIPCHK(c, hipStreamEndCapture(c->stream, &c->sgraph[gi]));
+  if (c->launch_refused || dtk_lds_attr_error(c->device)) {       // an incomplete step must never be replayed
+    (void)hipGraphDestroy(c->sgraph[gi]); c->sgraph[gi] = nullptr;
+    return fail(c, DTK_ERR_STATE, c->launch_refused ? "speculative step: a projection's shape has no kernel in its family (nothing launched for it)"
+                                                    : "speculative step: raising a kernel's dynamic-LDS limit failed (hipFuncSetAttribute, see stderr)");
+  }
+  HIPCHK(c, hipGraphInstantiate(&c->sgraph_exec[gi], c->sgraph[gi], nullptr, nullptr, 0));
+  c->sgraph_ready[gi] = true;
+  c->bgraph_captures++;
+  return DTK_OK;
+}
+
+static int spec_launch_impl(dtk_ctx* c) {
+  const int gi = c->spec_nv <= 2 ? 0 : 1;
+  if (c->use_graph) {
+    if (const int rc = ensure_spec_graph(c, gi)) return rc;
+    HIPCHK(c, hipGraphLaunch(c->sgraph_exec[gi], c->stream));
+  } else {
+    c->launch_refused = false;
+    batch_step_launches_mv(c);
+    if (c->launch_refused || dtk_lds_attr_error(c->device))
+      return fail(c, DTK_ERR_STATE, c->launch_refused ? "speculative step: a projection's shape has no kernel in its family (nothing launched for it)"
+                                                      : "speculative step: raising a kernel's dynamic-LDS limit failed (hipFuncSetAttribute, see stderr)");
+    HIPCHK(c, hipMemcpyAsync(c->tokb_host, c->tokb_dev, sizeof(int64_t) * TOKB_WORDS, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, copy_lp_ring(c, true));
+  }
+  return DTK_OK;
+}
+
+int dtk_spec_launch(dtk_ctx* c) {
+  if (!c) return fail(c, DTK_ERR_ARG, "dtk_spec_launch: null context");
+  if (!c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_spec_launch: slot 0 is not speculating (dtk_spec_begin)");
+  const int inflight = (int)(c->blaunched - c->bwaited);
+  if (inflight >= DTK_MAX_INFLIGHT) return fail(c, DTK_ERR_STATE, "too many batch steps in flight");
+  // the position this step starts at is known only once the steps in flight have been read: each of them accepts at most 4 tokens
+  if (c->spec_known_pos + 4 * inflight >= c->Tmax)
+    return fail(c, DTK_ERR_RANGE, "slot 0: context length %d (+ at most %d of %d steps in flight) reached max_positions", c->spec_known_pos, 4 * inflight, inflight);
+  HIPCHK(c, hipSetDevice(c->device));
+  ensure_tiled_weights(c);
+  BatchState* hb = c->bs_host + (c->blaunched % DTK_MAX_INFLIGHT);      // the host's record of the step: which slots it keeps busy
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) hb->active[j] = j <= c->spec_K ? 1 : 0;
+  hb->step = (int32_t)(c->blaunched % DTK_MAX_INFLIGHT);
+  c->nt_step = 1;
+  c->mv_step = c->spec_nv <= 2 ? 2 : 4;
+  c->spec_step = true;
+  const int rc = spec_launch_impl(c);
+  c->spec_step = false;
+  if (rc) return rc;
+  HIPCHK(c, hipEventRecord(c->bstep_done[c->blaunched % DTK_MAX_INFLIGHT], c->stream));
+  c->stats.last_batch_step_slots = (uint32_t)c->mv_step;
+  c->stats.last_batch_step_fp8_mfma = 0u;
+  c->blaunched++;
+  c->stats.decode_steps++;
+  return DTK_OK;
+}
+
+int dtk_spec_wait(dtk_ctx* c, int64_t* tokens_out, int* n_out, float* logprob_out, float* sample_logprob_out) {
+  if (!c || !tokens_out || !n_out || (logprob_out == nullptr) != (sample_logprob_out == nullptr)) return fail(c, DTK_ERR_ARG, "dtk_spec_wait: bad argument");
+  if (logprob_out && !c->logprobs) return fail(c, DTK_ERR_ARG, "dtk_spec_wait: the context does not compute log-probabilities (dtk_set_option \"logprobs\", 1)");
+  if (!c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_spec_wait: slot 0 is not speculating (dtk_spec_begin)");
+  if (c->bwaited >= c->blaunched) return fail(c, DTK_ERR_STATE, "no batch step in flight");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int ring = (int)(c->bwaited % DTK_MAX_INFLIGHT);
+  HIPCHK(c, hipEventSynchronize(c->bstep_done[ring]));
+  const volatile int64_t* rec = (volatile int64_t*)c->tokb_host + (size_t)ring * DTK_MAX_BATCH;
+  const int64_t cnt = rec[DTK_SPEC_COUNT_AT];
+  c->bwaited++;
+  if (cnt < 1 || cnt > c->spec_nv) return fail(c, DTK_ERR_HIP, "dtk_spec_wait: the step reports %lld accepted tokens (1..%d)", (long long)cnt, c->spec_nv);
+  SeqHost& sh = c->bseq[0];
+  for (int i = 0; i < 4; ++i) {
+    tokens_out[i] = i < cnt ? rec[i] : -1;
+    if (logprob_out) {
+      const volatile float* lp = (volatile float*)(c->lpb_host + (size_t)ring * DTK_MAX_BATCH + i);
+      logprob_out[i] = i < cnt ? lp[0] : NAN; sample_logprob_out[i] = i < cnt ? lp[1] : NAN;
+    }
+    if (i < cnt) sh.cached_ids.push_back(tokens_out[i]);
+  }
+  sh.host_next_pos += (int)cnt;
+  c->spec_known_pos += (int)cnt;
+  *n_out = (int)cnt;
+  return DTK_OK;
+}
+
+int dtk_spec_end(dtk_ctx* c, int keep_len) {
+  if (!c) return fail(c, DTK_ERR_ARG, "dtk_spec_end: null context");
+  if (!c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_spec_end: slot 0 is not speculating (dtk_spec_begin)");
+  while (c->bwaited < c->blaunched) {      // the steps still in flight: their tokens are the sequence's too (keep_len says which stay)
+    int64_t toks[4]; int n = 0;
+    if (dtk_spec_wait(c, toks, &n, nullptr, nullptr)) { c->bwaited = c->blaunched; c->spec_on = false; c->bseq[0].have_logits = false; return DTK_ERR_HIP; }
+  }
+  SeqHost& sh = c->bseq[0];
+  if (keep_len < 1 || (size_t)keep_len > sh.cached_ids.size())
+    return fail(c, DTK_ERR_ARG, "dtk_spec_end: keep_len %d, slot 0 holds %zu ids", keep_len, sh.cached_ids.size());
+  sh.cached_ids.resize((size_t)keep_len);
+  sh.host_next_pos = keep_len;
+  sh.have_logits = false;                  // the pending rows belong to positions that may have been dropped: the next prefill recomputes one
+  if (sh.share_len > keep_len) sh.share_len = keep_len;
+  if (sh.share_len <= 0) { sh.share_src = -1; sh.share_len = 0; }
+  sh.last_reuse_start = keep_len;
+  c->spec_on = false;
+  return DTK_OK;
+}
+
 // Copy the KV of the first n_tokens positions of slot src into slot dst (SURVEY §8 f1 / the proposed
 // dtk_kv_fork): rollouts that share a prefix (always: the 243 image tokens) reuse its KV bit for bit instead
 // of re-running ViT + prefill.  dst then needs a dtk_prefill_slot(..., DTK_PREFILL_REUSE_PREFIX) of the full
@@ -2932,6 +3158,7 @@ int dtk_decode_batch_wait_top(dtk_ctx* c, int64_t* tokens_out, float* logprob_ou
 int dtk_kv_fork(dtk_ctx* c, int src, int dst, int n_tokens) {
   if (!c || src < 0 || dst < 0 || src >= c->nb || dst >= c->nb || src == dst)
     return fail(c, DTK_ERR_ARG, "dtk_kv_fork: bad slots %d -> %d of %d", src, dst, c ? c->nb : 0);
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_kv_fork: slot 0 is speculating (dtk_spec_end first)");
   SeqHost& a = c->bseq[(size_t)src];
   if (n_tokens < 1 || (size_t)n_tokens > a.cached_ids.size() || n_tokens > c->Tmax)
     return fail(c, DTK_ERR_ARG, "dtk_kv_fork: %d tokens but slot %d holds %zu", n_tokens, src, a.cached_ids.size());
@@ -3035,6 +3262,7 @@ int dtk_slot_cached_ids(dtk_ctx* c, int slot, int64_t* out, int n_max) {
 int dtk_resume_slot(dtk_ctx* c, int slot, const int64_t* ids, int T, uint64_t image_key) {
   if (!c || !ids || T < 2 || slot < 0 || slot >= c->nb) return fail(c, DTK_ERR_ARG, "dtk_resume_slot: bad argument");
   if (T > c->Tmax) return fail(c, DTK_ERR_RANGE, "prompt of %d tokens exceeds max_positions %d", T, c->Tmax);
+  if (c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_resume_slot: slot 0 is speculating (dtk_spec_end first)");
   if (ids[T - 1] == c->cfg.image_token_id) return fail(c, DTK_ERR_ARG, "dtk_resume_slot: the last prompt token is an image position (its input is a patch feature, not an embedding)");
   int lcp = 0;
   const int rc = dtk_slot_lcp(c, slot, ids, T, image_key, &lcp);
@@ -3340,6 +3568,30 @@ int dtk_bench_cfg(dtk_ctx* c, int reps, float* avg_us) {
     HIPCHK(c, hipEventElapsedTime(&ms, c->probe_a, c->probe_b));
     avg_us[which] = ms * 1000.f / (float)reps;
   }
+  return DTK_OK;
+}
+
+// tools/bench_spec.py: HIP events around reps back-to-back launches of the speculative step's two own kernels on the sequence's state
+int dtk_bench_spec(dtk_ctx* c, int reps, float* avg_us) {
+  if (!c || !avg_us || reps < 1 || reps > 64) return fail(c, DTK_ERR_ARG, "dtk_bench_spec: bad argument (1 <= reps <= 64)");
+  if (!c->spec_on) return fail(c, DTK_ERR_STATE, "dtk_bench_spec: slot 0 is not speculating (dtk_spec_begin)");
+  if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_bench_spec: a step is in flight");
+  HIPCHK(c, hipSetDevice(c->device));
+  SpecArgs sv;
+  sv.sd = c->spec_sd; sv.hist = c->spec_hist; sv.table = c->spec_table; sv.K = 0; sv.max_ngram = 0; sv.NV = 0; sv.T_max = c->Tmax; sv.V = c->V;
+  sv.st_true = c->st_b; sv.st_vec = c->spec_st; sv.bs = c->spec_bs; sv.tok_ring = c->tokb_dev; sv.ring = DTK_MAX_INFLIGHT;
+  sv.embed = c->embed; sv.x = c->xb; sv.d = c->d;
+  for (int i = 0; i < 3; ++i) { launch_spec_accept(sv, c->stream); launch_spec_draft(sv, c->stream); }      // warm-up
+  HIPCHK(c, hipEventRecord(c->probe_a, c->stream));
+  for (int i = 0; i < reps; ++i) { launch_spec_accept(sv, c->stream); launch_spec_draft(sv, c->stream); }
+  HIPCHK(c, hipEventRecord(c->probe_b, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->probe_b));
+  float ms = 0.f;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->probe_a, c->probe_b));
+  *avg_us = ms * 1000.f / (float)reps;
+  // the pairs re-read stale token records and moved the position (never beyond max_positions): the sequence is only good for dtk_spec_end
+  const uint32_t ring_was = (uint32_t)(c->blaunched % DTK_MAX_INFLIGHT);
+  HIPCHK(c, hipMemcpy(&c->spec_bs->step, &ring_was, sizeof ring_was, hipMemcpyHostToDevice));
   return DTK_OK;
 }
 

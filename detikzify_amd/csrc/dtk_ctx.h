@@ -327,6 +327,25 @@ struct dtk_ctx {
   int32_t* cfg_forced = nullptr;     // [DTK_MAX_BATCH / 2] 1: the pair forwarded forced tokens in the last step (k_cfg_lse -> k_cfg_follow)
   float2* cfg_part = nullptr;        // [DTK_MAX_BATCH / 2][2][DTK_CFG_MAX_SLICES]
   float2* cfg_lse = nullptr;         // [DTK_MAX_BATCH / 2] (Lc, Lu) of the last step
+  // prompt-lookup speculative decoding of slot 0 (dtk_spec_*): between dtk_spec_begin and dtk_spec_end the multi-vector step runs with
+  // its vectors as consecutive positions of slot 0 (batch_step_launches_mv with spec_step set: the vectors' own DecStates, copies of
+  // slot 0's SamplingDev, a device BatchState of its own, kv_slot_stride 0).  The steps share the batched steps' counters, events and
+  // rings.  Everything below is one hipMalloc of the first dtk_spec_begin: a context that never speculates allocates nothing, and its
+  // steps launch what they launched before.
+  bool spec_on = false;
+  bool spec_step = false;            // the step being launched / captured is a speculative one
+  int spec_K = 0, spec_src = 0, spec_nv = 0;      // drafts per step, DTK_SPEC_LOOKUP | DTK_SPEC_TABLE, K + 1
+  int spec_known_pos = 0;            // slot 0's length after the steps that have been waited for
+  unsigned char* spec_mem = nullptr;
+  SpecDev* spec_sd = nullptr;
+  int32_t* spec_hist = nullptr;      // [Tmax]
+  int32_t* spec_table = nullptr;     // [Tmax]
+  DecState* spec_st = nullptr;       // [4]
+  SamplingDev* spec_sp = nullptr;    // [4] copies of slot 0's record
+  BatchState* spec_bs = nullptr;
+  bool sgraph_ready[2] = {false, false};       // the captured speculative step with 2 / 4 vectors
+  hipGraph_t sgraph[2] = {nullptr, nullptr};
+  hipGraphExec_t sgraph_exec[2] = {nullptr, nullptr};
   uint64_t launched = 0, waited = 0;
   hipEvent_t step_done[DTK_MAX_INFLIGHT] = {};
   hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;

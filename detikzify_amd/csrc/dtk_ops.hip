@@ -1359,5 +1359,26 @@ int dtk_op_cfg_mix(dtk_ctx* c, const float* zc, const float* zu, int V, float sc
   return r.finish(s);
 }
 
+// dtk_spec_begin(.., DTK_SPEC_LOOKUP)'s lookup alone: k_spec_draft over a history of the call's own, nothing but the drafts written
+int dtk_op_spec_lookup(dtk_ctx* c, const int32_t* ids, int len, int K, int max_ngram, int T_max, int32_t* drafts_out, int* n_out) {
+  if (!c || (!ids && len > 0) || len < 0 || K < 1 || K > 3 || max_ngram < 1 || max_ngram > DTK_SPEC_MAX_NGRAM || T_max < len || T_max < 1 || !drafts_out || !n_out)
+    return fail(c, DTK_ERR_ARG, "dtk_op_spec_lookup: bad argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, "dtk_op_spec_lookup", 0x5a);
+  int32_t res[5] = {-1, -1, -1, -1, 0};
+  SpecArgs a{};
+  a.hist = r.in<int32_t>(len > 0 ? ids : nullptr, (size_t)(len > 0 ? len : 1));
+  a.table = nullptr; a.K = K; a.max_ngram = max_ngram; a.NV = K + 1; a.T_max = T_max; a.V = c->V;
+  a.len_override = len;
+  a.drafts_out = r.out<int32_t>(res, 5, "drafts");
+  if (const int rc = r.upload(s)) return rc;
+  launch_spec_draft(a, s);
+  if (const int rc = r.finish(s)) return rc;
+  for (int i = 0; i < 4; ++i) drafts_out[i] = res[i];
+  *n_out = res[4];
+  return DTK_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -183,6 +183,34 @@ struct CfgFollowArgs {
   float2* lp_ring; float* lse_ring; TopRec* top_ring;   // or null
 };
 void launch_cfg_follow(const CfgFollowArgs& a, hipStream_t s);   // one block per pair, behind the sampler (and k_count_token)
+// dtk_spec_* (kernels_spec.hip): prompt-lookup speculative decoding of slot 0 inside the multi-vector step.  The step's vectors are
+// consecutive positions of the one sequence; these two kernels run between its sampler launch and its first GEMV.
+#define DTK_SPEC_COUNT_AT (DTK_MAX_BATCH - 1)      // entry of the step's token record that holds the number of accepted tokens (no multi-vector slot decodes there)
+struct SpecDev {
+  int32_t drafts[4];     // what vector j of the last forward carried: [0] the last accepted token, [j] the draft d_j (-1: the vector was not live)
+  int32_t n_live;        // live vectors of the last forward (1 + its drafts)
+  // the sequence's settings (dtk_spec_begin): read from here by the kernels of a step, so one captured step serves them all
+  int32_t K;             // drafts per step (1..3)
+  int32_t NV;            // vectors that may be live (K + 1)
+  int32_t max_ngram;     // longest n-gram the lookup matches
+  int32_t use_table;     // 1: the drafts come from SpecArgs::table, 0: from the lookup over SpecArgs::hist
+};
+struct SpecArgs {
+  SpecDev* sd;
+  int32_t* hist;                 // [T_max] the sequence's ids by position (prompt and image placeholders included)
+  const int32_t* table;          // draft source "host table" (SpecDev::use_table): an id per absolute position, -1 = none
+  int K; int max_ngram; int NV;  // sd == null (op entry point) only: drafts per step, longest n-gram matched, K + 1
+  int T_max; int V;
+  DecState* st_true;             // slot 0's true state (position, draw index, last token of the ACCEPTED sequence)
+  DecState* st_vec;              // [4] the vectors' states the sampler and the forward read
+  BatchState* bs;                // the speculative step's own device BatchState: active = live vectors, step = its record index
+  int64_t* tok_ring; int ring;   // the step's token record, indexed (step % ring) * DTK_MAX_BATCH + vector
+  const bf16_t* embed; bf16_t* x; int d;
+  int len_override = -1;         // >= 0: the history's length in place of st_true->next_pos (op entry point)
+  int32_t* drafts_out = nullptr; // op entry point: [5] = the drafts (-1 beyond the count) and their count; nothing else is written
+};
+void launch_spec_accept(const SpecArgs& a, hipStream_t s);   // one thread, behind the sampler
+void launch_spec_draft(const SpecArgs& a, hipStream_t s);    // one block, behind k_spec_accept
 static inline bool sample_mb_supported(int V) { return V > 32768 && V <= DTK_SAMPLE_MB_MAX_SLICES * 8192; }
 // on the v1 vocabularies (<= 32768) the register-resident single-block kernel is as fast (ds-7b sampling decode 366.2 tok/s
 // vs 366.6 with the chain): one launch, so it stays the default there; DTK_SAMPLER=mb forces the chain for V >= 16384 (A/B)

@@ -151,6 +151,22 @@ class GenerateOutput:
                  top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None):
         self.sequences, self.logprobs, self.sample_logprobs = sequences, logprobs, sample_logprobs
         self.top_ids, self.top_logprobs = top_ids, top_logprobs
+        self.accepted_per_step: Optional[List[int]] = None      # prompt_lookup_num_tokens: tokens every speculative step accepted
+
+
+def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size=None) -> Tuple[int, int]:
+    """the `prompt_lookup_num_tokens` / `max_matching_ngram_size` arguments of generate (HF's names and defaults) -> (K, n): K = 0 is
+    off (None and 0); K in 1 .. 3 drafts per step, n in 1 .. 16 (default 2); ValueError before anything runs"""
+    n = 2 if max_matching_ngram_size is None else max_matching_ngram_size
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= _lib.DTK_SPEC_MAX_NGRAM:
+        raise ValueError(f"max_matching_ngram_size = {max_matching_ngram_size!r}: an integer in 1 .. {_lib.DTK_SPEC_MAX_NGRAM}")
+    k = prompt_lookup_num_tokens
+    if k is None:
+        return 0, n
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 3:
+        raise ValueError(f"prompt_lookup_num_tokens = {prompt_lookup_num_tokens!r}: an integer in 1 .. 3 (the multi-vector step carries "
+                         "at most 4 positions of one sequence; None / 0 = off)")
+    return k, n
 
 
 def check_top_logprobs(top_logprobs: Optional[int], return_logprobs: bool = True) -> int:
@@ -1109,6 +1125,44 @@ class DetikzifyForCausalLM:
         self._check(self.lib.dtk_decode_batch_wait_lp(self._ctx, out, lp, slp), "dtk_decode_batch_wait_lp")
         return [int(v) for v in out], list(lp), list(slp)
 
+    # ---- prompt-lookup speculative decoding of slot 0 (dtk_spec_*) ------------------------------
+    def spec_begin(self, num_tokens: int, max_ngram: int = 2, table: bool = False) -> None:
+        """slot 0 (prefilled, logits pending) decodes up to num_tokens + 1 tokens per step from here to spec_end(): the step's vectors
+        are consecutive positions of the one sequence.  table=True: the drafts come from spec_set_drafts (tests) instead of the lookup"""
+        self._check(self.lib.dtk_spec_begin(self._ctx, int(num_tokens), int(max_ngram),
+                                            _lib.DTK_SPEC_TABLE if table else _lib.DTK_SPEC_LOOKUP), "dtk_spec_begin")
+
+    def spec_set_drafts(self, table: Sequence[int]) -> None:
+        """the draft of every absolute position (-1 = none) for spec_begin(table=True)"""
+        arr = (C.c_int32 * max(1, len(table)))(*[int(v) for v in table])
+        self._check(self.lib.dtk_spec_set_drafts(self._ctx, arr, len(table)), "dtk_spec_set_drafts")
+
+    def spec_launch(self) -> None:
+        self._check(self.lib.dtk_spec_launch(self._ctx), "dtk_spec_launch")
+
+    def spec_wait(self, logprobs: bool = False):
+        """the tokens the oldest unread speculative step accepted (1 .. num_tokens + 1); logprobs=True: (tokens, logprobs,
+        sample_logprobs)"""
+        out, n = (C.c_int64 * 4)(), C.c_int(0)
+        lp, slp = ((C.c_float * 4)(), (C.c_float * 4)()) if logprobs else (None, None)
+        self._check(self.lib.dtk_spec_wait(self._ctx, out, C.byref(n), lp, slp), "dtk_spec_wait")
+        toks = [int(out[i]) for i in range(n.value)]
+        return (toks, [float(lp[i]) for i in range(n.value)], [float(slp[i]) for i in range(n.value)]) if logprobs else toks
+
+    def spec_end(self, keep_len: int) -> None:
+        """end the speculation: slot 0 keeps its first keep_len ids and has no pending logits (the next prefill recomputes one row)"""
+        self._check(self.lib.dtk_spec_end(self._ctx, int(keep_len)), "dtk_spec_end")
+
+    def op_spec_lookup(self, ids: Sequence[int], num_tokens: int, max_ngram: int = 2, max_positions: Optional[int] = None) -> List[int]:
+        """the lookup kernel alone over ids: the drafts a step whose vector 0 forwards ids[-1] would carry"""
+        n = len(ids)
+        arr = (C.c_int32 * max(1, n))(*[int(v) for v in ids])
+        out, k = (C.c_int32 * 4)(), C.c_int(0)
+        self._check(self.lib.dtk_op_spec_lookup(self._ctx, arr, n, int(num_tokens), int(max_ngram),
+                                                int(max(n, 1) + 8 if max_positions is None else max_positions), out, C.byref(k)),
+                    "dtk_op_spec_lookup")
+        return [int(out[i]) for i in range(k.value)]
+
     # ---- classifier-free guidance: pairs of batch slots (dtk_set_guidance) ------------------------------------
     def set_guidance(self, scale: Optional[float], cond_slot: int, uncond_slot: Optional[int]):
         """pairs two decoding slots for classifier-free guidance: in every batched step the conditional slot's pending
@@ -1312,7 +1366,9 @@ class DetikzifyForCausalLM:
                  min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None, logit_bias=None, sequence_bias=None,
                  length_start: Optional[int] = None, guidance_scale: Optional[float] = None,
                  negative_prompt_ids: Optional[torch.Tensor] = None, negative_pixel_values: Optional[torch.Tensor] = None,
-                 negative_adapter_input_ids: Optional[torch.Tensor] = None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 negative_adapter_input_ids: Optional[torch.Tensor] = None, prompt_lookup_num_tokens: Optional[int] = None,
+                 max_matching_ngram_size: Optional[int] = None, prompt_lookup_drafts: Optional[Sequence[int]] = None,
+                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1355,12 +1411,25 @@ class DetikzifyForCausalLM:
         batch engines yet, unless the engine was built with guided_pairs=P (the pair then decodes in two of the engine's slots, the same
         tokens and log-probabilities); contexts without slots (tl-1.1b, MXFP4) have no guidance.
 
+        prompt_lookup_num_tokens=K (HF's name; 1 .. 3, None / 0 = off) with max_matching_ngram_size (default 2): prompt-lookup
+        speculative decoding.  The sequence decodes in SLOT 0 of a model loaded with batch_slots = K + 1 .. 5: one
+        multi-vector step verifies up to K drafted tokens — the continuation of the earlier occurrence of the sequence's last n-gram,
+        HF's PromptLookupCandidateGenerator — and accepts 1 .. K + 1 tokens.  Tokens, `.logprobs` and `.sample_logprobs` are, bit for
+        bit, what plain steps of slot 0 on the same context (decode_batch_launch([0])) give, greedy or sampled; a call WITHOUT the
+        argument runs the single-sequence step, whose kernels differ, so no identity with it (or with a batch_slots=0 context) is
+        claimed — classifier-free guidance lives with the same fact.  `.accepted_per_step` of the GenerateOutput lists what every step
+        accepted.  Not with guidance, penalties, DRY, the length rules, a bias, top_logprobs, kv_format mxfp8 or a batch engine
+        (NotImplementedError).  prompt_lookup_drafts (not an HF argument; tests): an id per absolute position, -1 = none, used as the
+        drafts instead of the lookup.
+
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
         unknown names — raises instead of being dropped: a drop-in must not silently decode something else."""
         topk = check_top_logprobs(top_logprobs, return_logprobs)
         if guidance_scale is not None:      # (a bad value raises before anything else is looked at)
             check_guidance_scale(guidance_scale)
+        if prompt_lookup_num_tokens is not None or max_matching_ngram_size is not None:      # (likewise)
+            check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size)
         if not self._weights_ready:
             raise _lib.DtkError("no weights loaded (load_state_dict / fill_synthetic first)")
         text_ids = None
@@ -1388,6 +1457,28 @@ class DetikzifyForCausalLM:
                                  "(contexts without slots — tl-1.1b, MXFP4 — have no guidance)")
             if self.batch_engine is None:
                 self._refuse_while_batch_busy("generate")
+        spec_k, spec_n = check_prompt_lookup(
+            getattr(self.generation_config, "prompt_lookup_num_tokens", None) if prompt_lookup_num_tokens is None else prompt_lookup_num_tokens,
+            getattr(self.generation_config, "max_matching_ngram_size", None) if max_matching_ngram_size is None else max_matching_ngram_size)
+        if prompt_lookup_drafts is not None and not spec_k:
+            raise ValueError("prompt_lookup_drafts without prompt_lookup_num_tokens")
+        if spec_k:      # everything that refuses a speculative call, before anything runs
+            if guided:
+                raise NotImplementedError("prompt_lookup_num_tokens: not together with guidance_scale (the guided pair needs the step's slots)")
+            if topk:
+                raise NotImplementedError("prompt_lookup_num_tokens: not together with top_logprobs (its records are per slot and step)")
+            if self.batch_engine is not None:
+                raise NotImplementedError("prompt_lookup_num_tokens: not in the batch engines (the speculative step takes the "
+                                          "multi-vector step's slots for one sequence)")
+            if self.num_slots() < spec_k + 1:
+                raise ValueError(f"prompt_lookup_num_tokens = {spec_k} needs {spec_k + 1} batch slots for the positions one step verifies: "
+                                 f"load(..., batch_slots={spec_k + 1}) up to 5 (contexts without slots — tl-1.1b, MXFP4 — do not speculate)")
+            if self.num_slots() > 5:
+                raise NotImplementedError(f"prompt_lookup_num_tokens: not on a context with {self.num_slots()} batch slots (the verify pass is the "
+                                          "multi-vector step of contexts with 2 .. 5 slots: load(..., batch_slots=4))")
+            if self.kv_format != "bf16":
+                raise NotImplementedError("prompt_lookup_num_tokens: not with kv_format mxfp8 (the positions of a step share slot 0's rows)")
+            self._refuse_while_batch_busy("generate")
         if input_ids is None:
             input_ids = inputs
         ids = input_ids.detach().to("cpu", torch.int64)
@@ -1426,6 +1517,12 @@ class DetikzifyForCausalLM:
             getattr(gc, "length_start", None) if length_start is None else length_start)
         bias_pairs = check_logit_bias(getattr(gc, "logit_bias", None) if logit_bias is None else logit_bias,
                                       getattr(gc, "sequence_bias", None) if sequence_bias is None else sequence_bias, int(self.config.vocab))
+        if spec_k:      # their tables depend on the position: they come later
+            for name, on in (("presence_penalty / frequency_penalty", presence_penalty or frequency_penalty), ("dry_multiplier", dry_multiplier),
+                             ("min_new_tokens / exponential_decay_length_penalty", min_new_tokens or decay),
+                             ("logit_bias / sequence_bias", bias_pairs)):
+                if on:
+                    raise NotImplementedError(f"prompt_lookup_num_tokens: not together with {name} yet")
         do_sample = gc.do_sample if do_sample is None else do_sample
         temperature = gc.temperature if temperature is None else temperature
         top_p = gc.top_p if top_p is None else top_p
@@ -1559,7 +1656,8 @@ class DetikzifyForCausalLM:
                 raise _lib.DtkError("concurrent generate() calls on one model: decode them as a batch "
                                     "(detikzify_amd.infer.batching.BatchEngine / simulate_parallel)")
             launched = received = 0
-            at = {"slot": 0} if guided else {}      # a guided pair decodes in slots 0 (this call's sampling state) and 1 (the negative prompt)
+            at = {"slot": 0} if (guided or spec_k) else {}      # a guided pair decodes in slots 0 (this call's sampling state) and 1 (the negative prompt); a speculating sequence in slot 0
+            spec_open, accepted = False, []
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or (), **at)
@@ -1593,6 +1691,29 @@ class DetikzifyForCausalLM:
                 launched = received = 0
                 stop = False
                 ahead = 2  # one step always in flight while the host handles the previous token
+                if spec_k:      # the same pipelining over speculative steps: every step read hands over 1 .. K + 1 tokens
+                    self.spec_begin(spec_k, spec_n, table=prompt_lookup_drafts is not None)
+                    spec_open = True
+                    if prompt_lookup_drafts is not None:
+                        self.spec_set_drafts(prompt_lookup_drafts)
+                    inflight = 0
+                    while not stop:
+                        # a step in flight yields at least one token and moves the position by at most four (the library's own bound)
+                        while (inflight < ahead and len(new_tokens) + inflight < n_new_max
+                               and cur + 4 * inflight < self.config.max_positions):
+                            self.spec_launch(); inflight += 1
+                        if not inflight:
+                            break
+                        got = self.spec_wait(logprobs=return_logprobs); inflight -= 1
+                        toks = got[0] if return_logprobs else got
+                        accepted.append(len(toks))
+                        for i, tok in enumerate(toks):      # the streamer sees them one by one; what lies behind the stop is dropped
+                            if return_logprobs:
+                                pairs[0].append(got[1][i]); pairs[1].append(got[2][i])
+                            stop = emit(tok)
+                            if stop:
+                                break
+                    launched = received = n_new_max      # (the plain loops below have nothing to do)
                 if guided:      # the same loop over steps of the pair: slot 0's token and records are the sequence's
                     while launched < min(ahead, n_new_max):
                         self.decode_batch_launch([0, 1]); launched += 1
@@ -1632,6 +1753,8 @@ class DetikzifyForCausalLM:
                         self.decode_launch(); launched += 1
             finally:
                 try:
+                    if spec_open:      # the steps in flight are read, slot 0 keeps exactly the sequence as returned (no pending logits)
+                        self.spec_end(cur)
                     if topk or guided:      # the call that asked for the alternatives / the pair switches them off again: later steps run without the extra kernels
                         self.synchronize()
                         while received < launched:      # (a step left in flight behind the last token: the switches refuse unread steps)
@@ -1652,8 +1775,11 @@ class DetikzifyForCausalLM:
             buf[0, T:T + len(new_tokens)] = torch.tensor(new_tokens, dtype=torch.int64)
         if return_logprobs:       # (an engine may have delivered pairs of tokens past the sequence's end: the first len(new_tokens) are its own)
             n = len(new_tokens)
-            return GenerateOutput(buf[:, :cur].clone(), torch.tensor(pairs[0][:n], dtype=torch.float32)[None],
+            out = GenerateOutput(buf[:, :cur].clone(), torch.tensor(pairs[0][:n], dtype=torch.float32)[None],
                                   torch.tensor(pairs[1][:n], dtype=torch.float32)[None],
                                   torch.tensor(tops[0][:n], dtype=torch.int64).reshape(1, n, topk) if topk else None,
                                   torch.tensor(tops[1][:n], dtype=torch.float32).reshape(1, n, topk) if topk else None)
+            if spec_k and engine is None and n_new_max > 0:
+                out.accepted_per_step = accepted
+            return out
         return buf[:, :cur].clone()

@@ -1045,6 +1045,55 @@ int  dtk_engine_submit_guided(dtk_engine* e, const dtk_guided* g, const dtk_samp
                               uint64_t* ticket_out);
 int  dtk_engine_set_guidance_op(dtk_engine* e, int (*set_guidance)(void* dev, int cond_slot, int uncond_slot, float scale));
 
+/* ---- Prompt-lookup speculative decoding of slot 0 in the multi-vector step (additive, ABI 7) --------------------------
+ * Between dtk_spec_begin and dtk_spec_end one step of a multi-vector context (2..5 slots) decodes up to K + 1 tokens of the sequence in
+ * SLOT 0: the step's NV = K + 1 vectors (2 vectors for K = 1, the 4-vector step for K = 2 | 3) are consecutive positions of that one
+ * sequence, all in slot 0's key/value cache.  Vector 0 forwards the last accepted token, vector i the draft d_i; the next step's sampler
+ * launch runs over the NV pending logits rows with slot 0's sampling record and draw index c + i for row i, k_spec_accept keeps the
+ * leading rows whose sampled token equals the draft the next vector forwarded (+ the first that does not), and k_spec_draft makes the
+ * next drafts.  Every GEMV, attention and sampler launch of a row is the instantiation a plain dtk_decode_batch_launch step of slot 0
+ * runs (only launch arguments differ), and a slot's result in that family depends neither on its index nor on its neighbours, so the
+ * tokens and log-probabilities are, bit for bit, those of plain steps of slot 0 on the same context.  Rows a rejected draft wrote beyond
+ * the accepted position are dead: the next step overwrites them before anything reads them.
+ *   dtk_spec_begin      K = 1..3 drafts per step; max_ngram = 1..DTK_SPEC_MAX_NGRAM; source = DTK_SPEC_LOOKUP (HF's
+ *                       PromptLookupCandidateGenerator over the sequence's ids on the device, prompt and image placeholders included: for
+ *                       n = min(max_ngram, len - 1) down to 1 the first window, in ascending index, that equals the last n ids and is not
+ *                       the tail itself gives its continuation, at most K ids; no match: no drafts) or DTK_SPEC_TABLE (an id per absolute
+ *                       position from dtk_spec_set_drafts, -1 = none: tests decide acceptance with it).  Drafts are cut so that no vector's
+ *                       position reaches max_positions.  Slot 0 must hold pending logits (a prefill, or plain steps that were read).
+ *                       Refused before anything is allocated or changed — DTK_ERR_ARG: K or max_ngram or source out of range, fewer than
+ *                       K + 1 decoding slots; DTK_ERR_STATE: a context outside the multi-vector family, kv_format mxfp8, a guided pair,
+ *                       top_logprobs, a presence / frequency penalty, DRY, length control or a logit bias on any slot, a batch step in
+ *                       flight, an engine holding the slots, a resumed slot 0 that has not forwarded its last prompt token yet.
+ *                       Slots 1..K lose their pending logits (they need a prefill before they decode again) and keep their KV.  The
+ *                       first call allocates 8 x max_positions bytes + a few records; a context that never calls it allocates nothing
+ *                       and its steps launch what they launched before.
+ *   dtk_spec_set_drafts the table of DTK_SPEC_TABLE: ids for positions [0, n), -1 beyond; DTK_ERR_STATE with a step in flight.
+ *   dtk_spec_launch     one speculative step, captured like the batched steps (two more graphs: 2 and 4 vectors); up to DTK_MAX_INFLIGHT
+ *                       in flight.  DTK_ERR_RANGE once length + 4 x (steps in flight) reaches max_positions: the host knows the
+ *                       position only of the steps it has read.
+ *   dtk_spec_wait       the oldest unread step: *n_out = 1..K + 1 accepted tokens in tokens_out[0 .. n) (-1 beyond), with their
+ *                       (logprob, sample_logprob) when both pointers are given (needs option "logprobs"; NaN beyond n).
+ *   dtk_spec_end        reads the steps still in flight, then leaves slot 0 holding exactly its first keep_len ids (1 .. its length) with
+ *                       NO pending logits: a following prefill with DTK_PREFILL_REUSE_PREFIX recomputes one row, as after any truncation.
+ *                       The caller decides where the sequence stops (EOS, a line end): tokens accepted past the stop are dropped here.
+ * While slot 0 speculates dtk_decode_batch_launch / _wait, prefills into slots, dtk_kv_fork, dtk_resume_slot and dtk_set_guidance return
+ * DTK_ERR_STATE.
+ *   dtk_op_spec_lookup  k_spec_draft's lookup alone on ids[0, len) (len >= 0): drafts_out[4] (-1 beyond the count) and *n_out, cut as a
+ *                       step whose vector 0 sits at position len - 1 of a max_positions = T_max context cuts them.
+ *   dtk_bench_spec      tools/bench_spec.py: HIP events around reps (1 .. 64) back-to-back launches of k_spec_accept + k_spec_draft on the
+ *                       speculating sequence's own state: *avg_us per pair.  The pairs move the position over stale records (never
+ *                       beyond max_positions): afterwards the sequence is good for dtk_spec_end and a new prefill only. */
+enum { DTK_SPEC_LOOKUP = 0, DTK_SPEC_TABLE = 1 };
+#define DTK_SPEC_MAX_NGRAM 16
+int  dtk_spec_begin(dtk_ctx* ctx, int K, int max_ngram, int source);
+int  dtk_spec_set_drafts(dtk_ctx* ctx, const int32_t* table, int n);
+int  dtk_spec_launch(dtk_ctx* ctx);
+int  dtk_spec_wait(dtk_ctx* ctx, int64_t* tokens_out /* [4] */, int* n_out, float* logprob_out /* [4] or NULL */, float* sample_logprob_out /* [4] or NULL */);
+int  dtk_spec_end(dtk_ctx* ctx, int keep_len);
+int  dtk_op_spec_lookup(dtk_ctx* ctx, const int32_t* ids, int len, int K, int max_ngram, int T_max, int32_t* drafts_out /* [4] */, int* n_out);
+int  dtk_bench_spec(dtk_ctx* ctx, int reps, float* avg_us);
+
 #ifdef __cplusplus
 }
 #endif
