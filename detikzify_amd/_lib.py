@@ -17,6 +17,7 @@ DTK_MAX_INFLIGHT = 4
 DTK_MAX_BATCH = 64          # entries of the active / tokens_out arrays of dtk_decode_batch_*
 DTK_MAX_TOP = 8             # most alternatives per position (dtk_score_top, dtk_set_option "top_logprobs")
 DTK_EPI_BIAS, DTK_EPI_GELU, DTK_EPI_RESIDUAL, DTK_GEMM_NAIVE = 1, 2, 4, 256
+DTK_EPI_GATED_RESIDUAL, DTK_EPI_GELU_ERF, DTK_EPI_GELU_TANH, DTK_GEMM_INPLACE = 8, 16, 32, 64      # dtk_op_gemm_ex
 DTK_GEMM_WT = 512
 DTK_GEMM_SL = 1024
 DTK_GEMM_KSLICES_SHIFT = 12     # dtk_op_gemm: flags |= S << 12 selects the sliced-K family (include/dtk.h)
@@ -255,6 +256,9 @@ SYMBOLS = {
     "dtk_op_swiglu": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "dtk_op_attention_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P] + [C.c_int] * 9),
     "dtk_op_rows_move": (C.c_int, [_P, C.c_int, _P, _P, _P] + [C.c_int] * 8 + [_P]),
+    # additive (ABI stays 7): one prefill GEMM launch as the product makes it (strides, offsets, in place) + the launchers' kernel record
+    "dtk_op_gemm_ex": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64] + [C.c_int] * 12 + [_P]),
+    "dtk_gemm_last_kernel": (C.c_int, []),
     # additive (ABI stays 7): one role of the multi-vector decode GEMV family (prologue, epilogue, nb slots, block shape)
     "dtk_op_gemv_mv_role": (C.c_int, [_P] + [C.c_int] * 4 + [_P, _P, _P] + [C.c_int] * 7 + [_P, _P, C.c_int, C.c_int, _P, _P, C.c_float,
                                       _P, _P, C.c_int, _P, _P, _P, _P, _P]),

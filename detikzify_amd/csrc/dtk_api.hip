@@ -3671,6 +3671,10 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
     if (value < 1) return fail(c, DTK_ERR_ARG, "gemm_g3_min_blocks must be >= 1");
     set_gemm_g3_min_blocks(value);
   }
+  else if (!strcmp(name, "gemm_g3_tile")) {   // block tile of the one-chain k_gemm_g3: 0 = by shape, 1 = 256 x 128, 2 = 128 x 256 (process-wide; bit-identical)
+    if (value < 0 || value > 2) return fail(c, DTK_ERR_ARG, "gemm_g3_tile must be 0, 1 or 2");
+    set_gemm_g3_tile(value);
+  }
   else if (!strcmp(name, "gemm_glds_min_tiles")) {
     if (value < 1) return fail(c, DTK_ERR_ARG, "gemm_glds_min_tiles must be >= 1");
     set_gemm_glds_min_tiles(value);

@@ -114,6 +114,80 @@ int dtk_op_gemm(dtk_ctx* c, const uint16_t* A, const uint16_t* W, const uint16_t
   return r.finish(s);
 }
 
+int dtk_gemm_last_kernel(void) { return gemm_last_kernel(); }
+
+// One GEMM launch as the product makes it: strided operands, bias / residual / C at element offsets inside their buffers (a pointer that is
+// 2-, 4- or 8-byte aligned only), the residual in place, either GELU whatever the context's config.  c_io is IN/OUT: what the kernel leaves
+// alone keeps the caller's bits; guard bytes behind it; *kernel_out = the launchers' record (kernels.h: GEMM_KCODE).
+int dtk_op_gemm_ex(dtk_ctx* c, const uint16_t* A, int64_t na, const uint16_t* W, int64_t nw, const uint16_t* bias, int64_t nb,
+                   const uint16_t* residual, int64_t nr, const uint16_t* gate, uint16_t* c_io, int64_t nc, int M, int N, int K,
+                   int lda, int ldw, int ldr, int ldc, int b_off, int r_off, int c_off, int flags, int scratch_fill, int* kernel_out) {
+  const char* who = "dtk_op_gemm_ex";
+  if (!c) return DTK_ERR_ARG;
+  if (!A || !W || !c_io) return fail(c, DTK_ERR_ARG, "%s: A, W and c_io required", who);
+  if (M < 1 || N < 1 || K < 8 || (K % 8) || scratch_fill < 0 || scratch_fill > 255) return fail(c, DTK_ERR_ARG, "%s: M, N >= 1, K a multiple of 8, scratch_fill a byte", who);
+  if (b_off < 0 || r_off < 0 || c_off < 0 || na < 1 || nw < 1 || nc < 1) return fail(c, DTK_ERR_ARG, "%s: negative offset or empty buffer", who);
+  const int known = DTK_EPI_BIAS | DTK_EPI_GELU | DTK_EPI_RESIDUAL | DTK_EPI_GATED_RESIDUAL | DTK_EPI_GELU_ERF | DTK_EPI_GELU_TANH | DTK_GEMM_INPLACE |
+                    DTK_GEMM_NAIVE | DTK_GEMM_WT | DTK_GEMM_SL | (15 << DTK_GEMM_KSLICES_SHIFT);
+  if (flags & ~known) return fail(c, DTK_ERR_ARG, "%s: unknown flag bits %#x", who, flags & ~known);
+  const bool has_bias = (flags & DTK_EPI_BIAS) != 0, has_res = (flags & DTK_EPI_RESIDUAL) != 0, inplace = (flags & DTK_GEMM_INPLACE) != 0;
+  const bool gated = (flags & DTK_EPI_GATED_RESIDUAL) != 0;
+  const int ngelu = ((flags & DTK_EPI_GELU) != 0) + ((flags & DTK_EPI_GELU_ERF) != 0) + ((flags & DTK_EPI_GELU_TANH) != 0);
+  const int S = (flags >> DTK_GEMM_KSLICES_SHIFT) & 15;
+  if (ngelu > 1) return fail(c, DTK_ERR_ARG, "%s: one GELU at most", who);
+  if (has_bias && !bias) return fail(c, DTK_ERR_ARG, "%s: DTK_EPI_BIAS without a bias", who);
+  if (inplace && (!has_res || residual)) return fail(c, DTK_ERR_ARG, "%s: DTK_GEMM_INPLACE needs DTK_EPI_RESIDUAL and residual = NULL (c_io holds it)", who);
+  if (has_res && !inplace && !residual) return fail(c, DTK_ERR_ARG, "%s: DTK_EPI_RESIDUAL without a residual", who);
+  if (gated && (!has_res || !gate)) return fail(c, DTK_ERR_ARG, "%s: DTK_EPI_GATED_RESIDUAL needs DTK_EPI_RESIDUAL and a gate", who);
+  if (S > 8) return fail(c, DTK_ERR_ARG, "%s: at most 8 K slices", who);
+  if ((flags & DTK_GEMM_SL) && S < 2) return fail(c, DTK_ERR_ARG, "%s: DTK_GEMM_SL needs 2..8 K slices", who);
+  if ((lda % 8) || (ldw % 8) || lda < K || ldw < K) return fail(c, DTK_ERR_ARG, "%s: A and W rows are 16-byte aligned: lda (%d), ldw (%d) multiples of 8 and >= K", who, lda, ldw);
+  if (ldc < N || (has_res && !inplace && ldr < N)) return fail(c, DTK_ERR_ARG, "%s: ldc (%d) / ldr (%d) below N", who, ldc, ldr);
+  if ((int64_t)(M - 1) * lda + K > na) return fail(c, DTK_ERR_ARG, "%s: the strides of A address element %lld of %lld", who, (long long)((int64_t)(M - 1) * lda + K), (long long)na);
+  if ((int64_t)(N - 1) * ldw + K > nw) return fail(c, DTK_ERR_ARG, "%s: the strides of W address element %lld of %lld", who, (long long)((int64_t)(N - 1) * ldw + K), (long long)nw);
+  if (has_bias && (int64_t)b_off + N > nb) return fail(c, DTK_ERR_ARG, "%s: the offset of bias addresses element %lld of %lld", who, (long long)((int64_t)b_off + N), (long long)nb);
+  if (has_res && !inplace && (int64_t)r_off + (int64_t)(M - 1) * ldr + N > nr)
+    return fail(c, DTK_ERR_ARG, "%s: the strides of residual address element %lld of %lld", who, (long long)((int64_t)r_off + (int64_t)(M - 1) * ldr + N), (long long)nr);
+  if ((int64_t)c_off + (int64_t)(M - 1) * ldc + N > nc)
+    return fail(c, DTK_ERR_ARG, "%s: the strides of C address element %lld of %lld", who, (long long)((int64_t)c_off + (int64_t)(M - 1) * ldc + N), (long long)nc);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  std::vector<bf16_t> packed;      // DTK_GEMM_WT: launch_retile reads contiguous rows
+  if ((flags & DTK_GEMM_WT) && ldw != K) {
+    packed.resize((size_t)N * K);
+    for (int n = 0; n < N; ++n) memcpy(packed.data() + (size_t)n * K, W + (size_t)n * ldw, (size_t)K * 2);
+  }
+  OpRun r(c, who, scratch_fill);
+  GemmArgs g;
+  g.A = r.in<bf16_t>(A, (size_t)na); g.lda = lda; g.W = r.in<bf16_t>(W, (size_t)nw); g.ldw = ldw;
+  const bf16_t* dB = r.in<bf16_t>(has_bias ? bias : nullptr, has_bias ? (size_t)nb : 0);
+  const bf16_t* dR = r.in<bf16_t>(has_res && !inplace ? residual : nullptr, has_res && !inplace ? (size_t)nr : 0);
+  g.gate = r.in<bf16_t>(gated ? gate : nullptr, gated ? 1 : 0);
+  bf16_t* dC = r.io<bf16_t>(c_io, (size_t)nc, "C");
+  g.bias = has_bias ? dB + b_off : nullptr;
+  g.C = dC + c_off; g.ldc = ldc;
+  g.residual = !has_res ? nullptr : (inplace ? g.C : dR + r_off); g.ldr = inplace ? ldc : ldr;
+  g.M = M; g.N = N; g.K = K;
+  g.flags = (has_bias ? GEMM_BIAS : 0) | ((flags & DTK_EPI_GELU) ? gelu_flag(c) : 0) | ((flags & DTK_EPI_GELU_ERF) ? GEMM_GELU_ERF : 0) |
+            ((flags & DTK_EPI_GELU_TANH) ? GEMM_GELU_TANH : 0) | (has_res ? GEMM_RESIDUAL : 0) | (gated ? GEMM_GATED_RESIDUAL : 0);
+  const bf16_t* dWp = packed.empty() ? g.W : r.in<bf16_t>(packed.data(), packed.size());
+  bf16_t* dWt = (flags & DTK_GEMM_WT) ? (bf16_t*)r.take(tiled_elems(N, K) * sizeof(bf16_t)) : nullptr;
+  if (S) g.kslices = S;
+  const bool sliced_mfma = S && !(flags & DTK_GEMM_NAIVE);
+  if (sliced_mfma && !(flags & DTK_GEMM_SL)) { g.part = (float*)r.take((size_t)S * M * N * sizeof(float)); g.part_stride = (long)M * N; }
+  if (r.full) return r.upload(s);
+  if (sliced_mfma && !gemm_sk_supported(g))      // (asked before anything is uploaded)
+    return fail(c, DTK_ERR_ARG, "%s: the sliced-K kernels need K >= 128 and N %% 4 == 0", who);
+  if (const int rc = r.upload(s)) return rc;
+  if (dWt) { launch_retile(dWp, dWt, N, K, s); g.Wt = dWt; }
+  if (flags & DTK_GEMM_NAIVE) launch_gemm_naive(g, s);
+  else if (S && (flags & DTK_GEMM_SL)) { if (!launch_gemm_g3_sliced(g, s)) return fail(c, DTK_ERR_ARG, "%s: the in-register sliced kernel does not take this shape", who); }
+  else if (S) { if (!launch_gemm_sk(g, nullptr, nullptr, 0, 0.f, s)) return fail(c, DTK_ERR_ARG, "%s: the sliced-K kernel does not take this shape", who); }
+  else launch_gemm_mfma(g, s);
+  if (kernel_out) *kernel_out = gemm_last_kernel();
+  return r.finish(s);
+}
+
 int dtk_op_score(dtk_ctx* c, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
                  float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out) {
   return dtk_op_score_top(c, Xn, W, targets, M, N, K, flags, logprob_out, lse_out, argmax_out, zmax_out, 0, nullptr, nullptr, nullptr);

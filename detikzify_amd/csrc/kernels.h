@@ -363,6 +363,24 @@ struct GemmArgs {
   const int32_t* ls_target = nullptr;  // the column whose z each row reports [M]
   float* ls_rec = nullptr;       // records [M][ceil(N / 128)][4] fp32 (16-byte aligned)
 };
+// Host-side record of the last GEMM launch of this process (gemm_last_kernel(); the launchers below set it, nothing on the device knows of
+// it): which kernel the launchers' fall-through (k_gemm_g3 -> k_gemm_glds -> k_gemm_mfma) ended at.  dtk_op_gemm_ex returns it.  One relaxed
+// atomic int for the process, for the op tests: with several launching threads it is the record of whichever stored last;
+// launch_gemm_logsoftmax does not set it.
+//   bits  0..3  family: 1 k_gemm_mfma, 2 k_gemm_glds, 3 k_gemm_g3 (one chain), 4 k_gemm_g3<SK> (+ k_sk_reduce behind launch_gemm_sk),
+//                       5 k_gemm_g3<SL>, 6 k_gemm_naive
+//   bits  4..7  block tile: 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (k_gemm_glds: always), 4 = 64 x 32, 5 = 32 x 32, 6 = 256 x 128, 7 = 128 x 256;
+//                       0 for the naive kernel
+//   bits  8..11 register stages D of k_gemm_mfma (1..4), else 0
+//   bit  12     k_gemm_mfma's 128-wide k-tile
+//   bit  13     WT: the W stage filled from the fragment-major copy
+//   bits 14..15 epilogue of a k_gemm_g3 form: 1 = through LDS (the slices' partials of SK likewise), 2 = direct from the accumulator layout,
+//                       3 = the GEMM_SWIGLU epilogue; else 0
+//   bits 16..19 K slices (SK, SL, the naive kernel's sliced form), else 0
+#define GEMM_KCODE(family, tile, stages, bk128, wt, epi, slices) \
+  ((family) | ((tile) << 4) | ((stages) << 8) | ((bk128) << 12) | ((wt) << 13) | ((epi) << 14) | ((slices) << 16))
+int gemm_last_kernel();
+void set_gemm_g3_tile(int v);   // one-chain k_gemm_g3: 0 = by shape (default), 1 = 256 x 128, 2 = 128 x 256; bit-identical
 __host__ __device__ inline int sk_tiles_per_slice(int K, int S) { const int T = K / 64; return (T + S - 1) / S; }
 // slices of a decoder-prefill role, from its WEIGHT shape alone: the largest power of two <= 8 that keeps 256 x 128 tiles x slices within
 // the 256 CUs, every slice at least 4 k-tiles long; 1 = the role stays a one-chain GEMM (it fills the chip, or the sliced kernel does not take it)

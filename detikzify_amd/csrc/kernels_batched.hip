@@ -10,6 +10,7 @@
 #include "kernels.h"
 #include <stdlib.h>
 #include <string.h>
+#include <atomic>
 
 
 __device__ __forceinline__ float gelu_erf(float x) {
@@ -398,6 +399,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_glds(GemmArgs a) {
   }
   gemm_store_tiles<4, 4>(a, acc, m0 + wr * 64, n0 + wc * 64, lane);
 }
+static std::atomic<int> g_last_gemm{0};     // GEMM_KCODE of the last launch (kernels.h): host bookkeeping of the launchers below
+int gemm_last_kernel() { return g_last_gemm.load(std::memory_order_relaxed); }
+static void gemm_record(int code) { g_last_gemm.store(code, std::memory_order_relaxed); }
 static int g_glds_min_tiles = 160;   // 128 x 128 tiles a shape must have for k_gemm_glds (gemm_impl 2 / 3); below that the small-tile kernel fills the chip better
 void set_gemm_glds_min_tiles(int v) { g_glds_min_tiles = v; }
 static bool launch_gemm_glds(const GemmArgs& a, hipStream_t s) {
@@ -409,6 +413,7 @@ static bool launch_gemm_glds(const GemmArgs& a, hipStream_t s) {
   static unsigned long long attr_set = 0;
   if (dtk_lds_attr_todo(attr_set)) { DTK_LDS_ATTR(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_glds), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); }
   hipLaunchKernelGGL(k_gemm_glds, dim3((unsigned)(8 * ((nbs + 7) / 8) * mbs)), dim3(256), lds, s, a);
+  gemm_record(GEMM_KCODE(2, 3, 0, 0, 0, 0, 0));
   return true;
 }
 
@@ -647,6 +652,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
   // 17 KiB of LDS (row stride 272 B: the 16-byte slots of a store instruction spread evenly over the banks), then walks it row by row — 8
   // lanes per row, 8 consecutive columns each: bias / residual arrive as 16-byte loads, the output leaves as 16-byte stores, 8 rows x 128 B
   // per instruction (a K slice: 32-byte stores, 256 B per row).  Same arithmetic per element.
+  // (this condition is restated on the host: g3_epi_code() below, for the launch record, and g3_epi() / branches() of tests/gemm_cases.py — keep them in step)
   if (!(a.flags & GEMM_EPI_DIRECT) && (a.N & 7) == 0 && (SK || ((a.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0))) {
     constexpr unsigned ROWB = 272u, WREG = 64u * ROWB;
     unsigned char* reg = gsm + (unsigned)wave * WREG;
@@ -720,6 +726,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_g3(GemmArgs a) {
     return;
   }
   // All bias / residual loads first (8 bytes each, clamped), then the arithmetic, then 8-byte stores.
+  // (vec / nvec / rvec / bvec and the LDS walk's bias and rvec tests above are mirrored by branches() of tests/gemm_cases.py)
   const int flags = a.flags;
   const float gs = gemm_gate(a);
   const bool vec = (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
@@ -782,7 +789,16 @@ static int g_g3_epi_direct = 0;       // 1: k_gemm_g3's lanes store their accumu
 void set_gemm_epi_direct(int v) { g_g3_epi_direct = v; }
 static int g_g3_min_blocks = 128;     // blocks a shape must give k_gemm_g3 (one per CU): below that the smaller tiles fill the chip better
 void set_gemm_g3_min_blocks(int v) { g_g3_min_blocks = v; }
+static int g_g3_tile = 0;             // one-chain k_gemm_g3: 0 = orientation by shape, 1 = 256 x 128, 2 = 128 x 256 (dtk_set_option "gemm_g3_tile"; bit-identical)
+void set_gemm_g3_tile(int v) { g_g3_tile = v; }
 static bool use_wt(const GemmArgs& a);
+// which epilogue a k_gemm_g3 form takes for these operands: 1 through LDS, 2 direct, 3 the SwiGLU epilogue.  A host-side COPY of the kernel's
+// own conditions (k_gemm_g3, "Epilogue through LDS"), not the kernel's decision: whoever changes one changes the other
+static int g3_epi_code(const GemmArgs& a, bool sk, bool wt) {
+  if (!sk && wt && (a.flags & GEMM_SWIGLU)) return 3;
+  const bool lds = !(a.flags & GEMM_EPI_DIRECT) && (a.N & 7) == 0 && (sk || ((a.ldc & 7) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0));
+  return lds ? 1 : 2;
+}
 template <int BM, int BN, bool WT = false>
 static void launch_gemm_g3_t(const GemmArgs& a, hipStream_t s) {
   constexpr int lds = 3 * (BM + BN) * 64 * 2;
@@ -800,7 +816,7 @@ static bool launch_gemm_g3(const GemmArgs& a, hipStream_t s) {
   auto blocks = [&](int bm, int bn) { return (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn); };
   const long tall = blocks(256, 128), wide = blocks(128, 256);
   const long rt = (tall + cus - 1) / cus, rw = (wide + cus - 1) / cus;
-  const bool use_wide = rw < rt || (rw == rt && wide < tall && a.M < 256);
+  const bool use_wide = g_g3_tile ? g_g3_tile == 2 : (rw < rt || (rw == rt && wide < tall && a.M < 256));
   if ((use_wide ? wide : tall) < g_g3_min_blocks) return false;
   static int probe = -1;          // DTK_G3_PROBE: 1 = no fills after the first two k-tiles, 2 = no MFMAs (timing experiments: wrong results)
   if (probe < 0) { const char* e = getenv("DTK_G3_PROBE"); probe = e ? atoi(e) : 0; }
@@ -810,6 +826,7 @@ static bool launch_gemm_g3(const GemmArgs& a, hipStream_t s) {
   if (probe & 2) b.flags |= GEMM_PROBE_NOMFMA;
   if (use_wt(b)) { if (use_wide) launch_gemm_g3_t<128, 256, true>(b, s); else launch_gemm_g3_t<256, 128, true>(b, s); }
   else if (use_wide) launch_gemm_g3_t<128, 256>(b, s); else launch_gemm_g3_t<256, 128>(b, s);
+  gemm_record(GEMM_KCODE(3, use_wide ? 7 : 6, 0, 0, use_wt(b) ? 1 : 0, g3_epi_code(b, false, use_wt(b)), 0));
   return true;
 }
 
@@ -1019,6 +1036,7 @@ __global__ __launch_bounds__(1024) void k_sk_reduce(GemmArgs a, const bf16_t* no
   const float gs = gemm_gate(a);
   const float* p0 = a.part + (size_t)m * a.N;
   bf16_t* crow = a.C + (size_t)m * a.ldc;
+  // (vec / rvec / bvec are mirrored by branches() of tests/gemm_cases.py: red_vec, red_rvec, red_bvec)
   const bool vec = (a.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
   const bool rvec = (flags & GEMM_RESIDUAL) && (a.ldr & 3) == 0 && (reinterpret_cast<uintptr_t>(a.residual) & 7) == 0;
   const bool bvec = (flags & GEMM_BIAS) && (reinterpret_cast<uintptr_t>(a.bias) & 7) == 0;
@@ -1132,13 +1150,16 @@ bool launch_gemm_sk_partials(const GemmArgs& a, hipStream_t s) {
   if (g_g3_epi_direct && !probe) { GemmArgs b = a; b.flags |= GEMM_EPI_DIRECT;
     if (use_wt(b)) { if (wide) launch_gemm_sk_t<128, 256, true>(b, s); else launch_gemm_sk_t<256, 128, true>(b, s); }
     else if (wide) launch_gemm_sk_t<128, 256, false>(b, s); else launch_gemm_sk_t<256, 128, false>(b, s);
+    gemm_record(GEMM_KCODE(4, wide ? 7 : 6, 0, 0, use_wt(b) ? 1 : 0, g3_epi_code(b, true, use_wt(b)), a.kslices));
     return true; }
   if (probe) { GemmArgs b = a; if (probe & 1) b.flags |= GEMM_PROBE_NOFILL; if (probe & 2) b.flags |= GEMM_PROBE_NOMFMA;
                if (use_wt(b)) { if (wide) launch_gemm_sk_t<128, 256, true>(b, s); else launch_gemm_sk_t<256, 128, true>(b, s); }
                else if (wide) launch_gemm_sk_t<128, 256, false>(b, s); else launch_gemm_sk_t<256, 128, false>(b, s);
+               gemm_record(GEMM_KCODE(4, wide ? 7 : 6, 0, 0, use_wt(b) ? 1 : 0, g3_epi_code(b, true, use_wt(b)), a.kslices));
                return true; }
   if (use_wt(a)) { if (wide) launch_gemm_sk_t<128, 256, true>(a, s); else launch_gemm_sk_t<256, 128, true>(a, s); }
   else if (wide) launch_gemm_sk_t<128, 256, false>(a, s); else launch_gemm_sk_t<256, 128, false>(a, s);
+  gemm_record(GEMM_KCODE(4, wide ? 7 : 6, 0, 0, use_wt(a) ? 1 : 0, g3_epi_code(a, true, use_wt(a)), a.kslices));
   return true;
 }
 
@@ -1187,6 +1208,7 @@ bool launch_gemm_g3_sliced(const GemmArgs& a, hipStream_t s) {
   if (g_g3_epi_direct) b.flags |= GEMM_EPI_DIRECT;
   if (use_wt(b)) { if (wide) launch_gemm_g3_sl_t<128, 256, true>(b, s); else launch_gemm_g3_sl_t<256, 128, true>(b, s); }
   else if (wide) launch_gemm_g3_sl_t<128, 256, false>(b, s); else launch_gemm_g3_sl_t<256, 128, false>(b, s);
+  gemm_record(GEMM_KCODE(5, wide ? 7 : 6, 0, 0, use_wt(b) ? 1 : 0, g3_epi_code(b, false, use_wt(b)), a.kslices));
   return true;
 }
 
@@ -1250,6 +1272,9 @@ void launch_gemm_mfma(const GemmArgs& a, hipStream_t s) {
   }
   else { GEMM_LAUNCH(64, 64) }
 #undef GEMM_LAUNCH
+  const int ran = (tile >= 2 && tile <= 5) ? tile : 1;      // (whatever else the override holds took the 64 x 64 branch above)
+  const bool bk128 = ran == 1 && g_gemm_bk == 128;       // (the 128-wide k-tile has register stages 1, 2 and 3)
+  gemm_record(GEMM_KCODE(1, ran, (D == 1 || D == 2 || (D == 4 && !bk128)) ? D : 3, bk128 ? 1 : 0, 0, 0, 0));
 }
 
 // Plain one-thread-per-output GEMM: the obviously-correct twin of k_gemm_mfma (selected
@@ -1277,6 +1302,7 @@ __global__ void k_gemm_naive(GemmArgs a) {
 void launch_gemm_naive(const GemmArgs& a, hipStream_t s) {
   dim3 grid((a.N + 63) / 64, (a.M + 3) / 4);
   hipLaunchKernelGGL(k_gemm_naive, grid, dim3(256), 0, s, a);
+  gemm_record(GEMM_KCODE(6, 0, 0, 0, 0, 0, a.kslices > 1 ? a.kslices : 0));
 }
 
 // ------------------------------------------------------------------------------------------

@@ -509,7 +509,7 @@ int  dtk_set_gemv_variant(dtk_ctx* ctx, int epi, int variant);
  * Decoder prefill: "prefill_sk" (1 = roles sliced along K by their weight shape, the default; 0 = one-chain GEMMs — another fp32
  * summation order, cached prefixes are dropped; 2 / 4 / 8 = a cap on the slices), and three bit-identical choices: "gemm_wt" (k_gemm_g3's W stage from the
  * fragment-major weight copy), "gemm_epi_direct" (k_gemm_g3 stores from the accumulator layout instead of through LDS), "qkv_rope_fused" (the
- * sliced q/k/v role reduces inside the RoPE + KV-append kernel), "swiglu_fused" (SiLU*mul is the epilogue of the gate/up GEMM), "gemm_sk_tile" (0 = 256 x 128, 1 = 128 x 256, 2 = by M).  "sk_sl_min_rows": above this many prefill rows a sliced role is ONE launch that folds
+ * sliced q/k/v role reduces inside the RoPE + KV-append kernel), "swiglu_fused" (SiLU*mul is the epilogue of the gate/up GEMM), "gemm_sk_tile" (0 = 256 x 128, 1 = 128 x 256, 2 = by M), "gemm_g3_tile" (the one-chain k_gemm_g3: 0 = by shape, 1 = 256 x 128, 2 = 128 x 256).  "sk_sl_min_rows": above this many prefill rows a sliced role is ONE launch that folds
  * its slices in registers (k_gemm_g3<.., SL>) instead of (tile, slice) blocks + reduction per 512 rows; bit-identical.
  * The environment variable DTK_OPTIONS="name=value,name=value" applies the same switches at dtk_create.
  * SCOPE: the switches that select a kernel VARIANT ("gemv_*", "resid_*", "gemm_*", "mx_*", "attn_impl") are process-wide — they live in the
@@ -684,6 +684,31 @@ int  dtk_op_attention_ex(dtk_ctx* ctx, const uint16_t* Q, int64_t nq, const uint
                          int q_offset, int nbatch, int scratch_fill);
 int  dtk_op_rows_move(dtk_ctx* ctx, int form, const int32_t* ids, const uint16_t* src, const float* pixels, int M, int D, int V, int lds,
                       int ldd, int image, int patch, int scratch_fill, uint16_t* dst_io);
+/* The prefill GEMM family alone, as the product calls it (additive, ABI 7): ONE call of launch_gemm_mfma (default), launch_gemm_naive
+ * (DTK_GEMM_NAIVE), launch_gemm_sk (S << DTK_GEMM_KSLICES_SHIFT) or launch_gemm_g3_sliced (+ DTK_GEMM_SL) on host operands.  A [.. na], W [.. nw],
+ * bias [.. nb], residual [.. nr] and c_io [.. nc] are whole buffers of that many elements; row m of A starts at m * lda, row n of W at n * ldw, and
+ * the first used element of bias / residual / C lies b_off / r_off / c_off elements inside its buffer (every buffer is uploaded 256-byte aligned,
+ * so an offset of 1, 2 or 4 elements gives the kernel a pointer that is 2-, 4- or 8-byte aligned only); rows of residual / C are ldr / ldc apart.
+ * flags: DTK_EPI_BIAS, DTK_EPI_GELU (the context's GELU) or DTK_EPI_GELU_ERF / DTK_EPI_GELU_TANH (that GELU whatever the context's config),
+ * DTK_EPI_RESIDUAL, DTK_EPI_GATED_RESIDUAL (with DTK_EPI_RESIDUAL; gate = one bf16), DTK_GEMM_INPLACE (with DTK_EPI_RESIDUAL: residual = NULL,
+ * c_io holds the residual on entry, the kernel gets residual = C and ldr = ldc — every ViT and adapter block), DTK_GEMM_NAIVE, DTK_GEMM_WT,
+ * DTK_GEMM_SL, S << DTK_GEMM_KSLICES_SHIFT.  c_io is IN/OUT (uploaded first): what the launch does not write keeps the caller's bits.
+ * scratch_fill and the 256 guard bytes behind c_io (DTK_ERR_STATE) as in dtk_op_gemv_role.  DTK_ERR_ARG with nothing launched: lda / ldw not a
+ * multiple of 8 or below K (A and W are 16-byte aligned rows in the product), strides or offsets that address past na / nw / nb / nr / nc (the
+ * message names the operand), more than 8 slices, a shape the sliced kernels do not take (K < 128, N % 4).
+ * *kernel_out (may be NULL) = the launchers' record of the kernel that ran: family | tile << 4 | stages << 8 | bk128 << 12 | WT << 13 |
+ * epilogue << 14 | slices << 16 — family 1 k_gemm_mfma, 2 k_gemm_glds, 3 k_gemm_g3, 4 k_gemm_g3<SK> + k_sk_reduce, 5 k_gemm_g3<SL>, 6 k_gemm_naive;
+ * tile 1 = 64x64, 2 = 128x64, 3 = 128x128, 4 = 64x32, 5 = 32x32, 6 = 256x128, 7 = 128x256; epilogue (k_gemm_g3 forms) 1 = through LDS, 2 = direct.
+ * dtk_gemm_last_kernel(): the same record after any GEMM launch of the process (dtk_op_gemm, dtk_op_gemm_gated, ...).
+ * Option "gemm_g3_tile" (process-wide; bit-identical): the block tile of the one-chain k_gemm_g3 — 0 = by shape (default), 1 = 256 x 128,
+ * 2 = 128 x 256 — as "gemm_sk_tile" for the sliced kernels. */
+#define DTK_EPI_GELU_ERF 16    /* dtk_op_gemm_ex: gelu_erf(acc + bias), whatever the context's config */
+#define DTK_EPI_GELU_TANH 32   /* dtk_op_gemm_ex: gelu_tanh(acc + bias) */
+#define DTK_GEMM_INPLACE 64    /* dtk_op_gemm_ex: the residual is C itself */
+int  dtk_op_gemm_ex(dtk_ctx* ctx, const uint16_t* A, int64_t na, const uint16_t* W, int64_t nw, const uint16_t* bias, int64_t nb,
+                    const uint16_t* residual, int64_t nr, const uint16_t* gate, uint16_t* c_io, int64_t nc, int M, int N, int K,
+                    int lda, int ldw, int ldr, int ldc, int b_off, int r_off, int c_off, int flags, int scratch_fill, int* kernel_out);
+int  dtk_gemm_last_kernel(void);
 /* The multi-vector decode GEMV family (the step of a context with at most 5 slots) alone, one role at a time (additive, ABI 7): one
  * (pro, epi) of launch_gemv_mv on host operands, nb = 1 | 2 | 4 slots, head dim 128.  pro / epi as in dtk_op_gemv_role; the pairs are the
  * step's (RMSNORM, QKV), (COPY, RESID), (RMSNORM, SWIGLU), (RMSNORM, LOGITS) and the tests' (COPY, STORE), (RMSNORM, STORE).  shape: -1 =

@@ -134,9 +134,13 @@ def test_op_gemm_tile_variants_are_bit_identical(tiny, M, N, K, flags):
         model._check(model.lib.dtk_op_gemm(model._ctx, p(Ab), p(Wb), p(bb), p(Rb), M, N, K,
                                            flags | (_lib.DTK_GEMM_NAIVE if tile == "naive" else 0), p(out)), "dtk_op_gemm")
         outs[tile] = out
+        code = model.lib.dtk_gemm_last_kernel()      # the launchers' record (csrc/kernels.h: GEMM_KCODE): the kernel that ran is the one meant
+        assert (code & 15, (code >> 4) & 15) == ((6, 0) if tile == "naive" else (1, tile)), hex(code)
     model.set_option("gemm_tile", 1); model.set_option("gemm_bk", 128)      # 128-wide k-tile of the 64x64 kernel
     out = np.empty((M, N), dtype=np.uint16)
     model._check(model.lib.dtk_op_gemm(model._ctx, p(Ab), p(Wb), p(bb), p(Rb), M, N, K, flags, p(out)), "dtk_op_gemm")
+    code = model.lib.dtk_gemm_last_kernel()
+    assert (code & 15, (code >> 4) & 15, (code >> 12) & 1) == (1, 1, 1), hex(code)
     model.set_option("gemm_bk", 64); model.set_option("gemm_tile", 0)
     assert np.array_equal(out, outs[1])
     # k_gemm_glds: 128 x 128 tiles, both operands by LDS-DMA in full 128-byte lines into an XOR-swizzled [row][chunk] image, two
@@ -146,6 +150,7 @@ def test_op_gemm_tile_variants_are_bit_identical(tiny, M, N, K, flags):
         out = np.empty((M, N), dtype=np.uint16)
         model._check(model.lib.dtk_op_gemm(model._ctx, p(Ab), p(Wb), p(bb), p(Rb), M, N, K, flags, p(out)), "dtk_op_gemm")
         assert np.array_equal(out, outs[1]), "k_gemm_glds"
+        assert model.lib.dtk_gemm_last_kernel() & 15 == (2 if K >= 64 else 1)
     finally:
         model.set_option("gemm_impl", 3); model.set_option("gemm_glds_min_tiles", 160)
     assert all(np.array_equal(outs[1], outs[t]) for t in (2, 3, 4, 5))
@@ -175,6 +180,9 @@ def test_op_gemm_three_stage_kernel_is_bit_identical(tiny, M, N, K, flags):
             out = np.empty((M, N), dtype=np.uint16)
             model._check(model.lib.dtk_op_gemm(model._ctx, p(Ab), p(Wb), p(bb), p(Rb), M, N, K, flags | (_lib.DTK_GEMM_WT if impl == "wt" else 0), p(out)), "dtk_op_gemm")
             outs[impl] = out
+            code = model.lib.dtk_gemm_last_kernel()      # k_gemm_g3 ran where it was meant to (no silent fall-through to k_gemm_mfma)
+            assert code & 15 == (1 if impl == 0 else 3) and (code >> 13) & 1 == int(impl == "wt"), hex(code)
+            assert impl != "direct" or (code >> 14) & 3 == 2, hex(code)
     finally:
         model.set_option("gemm_impl", 3); model.set_option("gemm_epi_direct", 0)
         model.set_option("gemm_g3_min_blocks", 128)
@@ -203,6 +211,10 @@ def test_op_gemm_sliced_k_family(tiny, M, N, K, flags):
     def run(a_bits, m, fl):
         out = np.empty((m, N), dtype=np.uint16)
         model._check(model.lib.dtk_op_gemm(model._ctx, p(a_bits), p(Wb), p(bb), p(Rb), m, N, K, fl, p(out)), "dtk_op_gemm")
+        code, S = model.lib.dtk_gemm_last_kernel(), (fl >> _lib.DTK_GEMM_KSLICES_SHIFT) & 15      # the launchers' record: the family that was asked for ran
+        want = 6 if fl & _lib.DTK_GEMM_NAIVE else (5 if S and fl & _lib.DTK_GEMM_SL else (4 if S else None))
+        assert want is None or code & 15 == want, hex(code)
+        assert want not in (4, 5) or ((code >> 16) & 15 == S and (code >> 13) & 1 == int(bool(fl & _lib.DTK_GEMM_WT))), hex(code)
         return out
     sk = lambda S: S << _lib.DTK_GEMM_KSLICES_SHIFT
     try:
@@ -211,8 +223,10 @@ def test_op_gemm_sliced_k_family(tiny, M, N, K, flags):
         assert np.array_equal(run(Ab, M, flags | sk(1)), one_chain), "one slice through partials + reduce"
         for S in (2, 4, 8):
             tall = run(Ab, M, flags | sk(S))
+            assert (model.lib.dtk_gemm_last_kernel() >> 4) & 15 == 6
             model.set_option("gemm_sk_tile", 1)
             wide = run(Ab, M, flags | sk(S))
+            assert (model.lib.dtk_gemm_last_kernel() >> 4) & 15 == 7
             model.set_option("gemm_sk_tile", 0)
             assert np.array_equal(tall, wide), f"S = {S}: 256 x 128 vs 128 x 256"
             assert np.array_equal(run(Ab, M, flags | sk(S) | _lib.DTK_GEMM_SL), tall), f"S = {S}: one launch, slices folded in registers"
@@ -230,10 +244,10 @@ def test_op_gemm_sliced_k_family(tiny, M, N, K, flags):
             frac = float((tall != naive).mean())
             print(f"sliced-K {M}x{N}x{K} S={S}: vs naive twin differing {frac:.5f}")
             assert frac < 2e-3      # fmaf chain vs the MFMA's tree inside a 32-wide k-step: rare 1-ulp flips only
-        # exact operands: small integers (|sum| < 2^24 in fp32 whatever the order), results kept below 256 so that bf16 holds them
-        Ai = torch.randint(-2, 3, (M, K), generator=g).float(); Wi = (torch.rand(N, K, generator=g) < 8.0 / K).float()
+        # exact operands: the dense grid of small integers (every fp32 partial sum is an integer below 2^24 whatever the order), ONE rounding to bf16
+        Ai = torch.randint(-4, 5, (M, K), generator=g).float(); Wi = torch.randint(-4, 5, (N, K), generator=g).float()
         exact = (Ai.double() @ Wi.double().T)
-        assert float(exact.abs().max()) < 256
+        assert 16 * K < 2 ** 24
         Aib, Wb = bf16_bits(Ai), bf16_bits(Wi)
         for S in (1, 2, 4, 8):
             got = run(Aib, M, sk(S))
