@@ -365,12 +365,12 @@ struct GemmArgs {
 };
 // Host-side record of the last GEMM launch of this process (gemm_last_kernel(); the launchers below set it, nothing on the device knows of
 // it): which kernel the launchers' fall-through (k_gemm_g3 -> k_gemm_glds -> k_gemm_mfma) ended at.  dtk_op_gemm_ex returns it.  One relaxed
-// atomic int for the process, for the op tests: with several launching threads it is the record of whichever stored last;
-// launch_gemm_logsoftmax does not set it.
+// atomic int for the process, for the op tests: with several launching threads it is the record of whichever stored last.
 //   bits  0..3  family: 1 k_gemm_mfma, 2 k_gemm_glds, 3 k_gemm_g3 (one chain), 4 k_gemm_g3<SK> (+ k_sk_reduce behind launch_gemm_sk),
-//                       5 k_gemm_g3<SL>, 6 k_gemm_naive
-//   bits  4..7  block tile: 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (k_gemm_glds: always), 4 = 64 x 32, 5 = 32 x 32, 6 = 256 x 128, 7 = 128 x 256;
-//                       0 for the naive kernel
+//                       5 k_gemm_g3<SL>, 6 k_gemm_naive, 7 the log-softmax epilogue (launch_gemm_logsoftmax: k_gemm_g3<LS> with tile 6 / 7
+//                       and the WT bit, or k_gemm_mfma<64, 128, LS> as tile 3; every other field 0)
+//   bits  4..7  block tile: 1 = 64 x 64, 2 = 128 x 64, 3 = 128 x 128 (k_gemm_glds: always; family 7: k_gemm_mfma's 64 x 128), 4 = 64 x 32,
+//                       5 = 32 x 32, 6 = 256 x 128, 7 = 128 x 256; 0 for the naive kernel
 //   bits  8..11 register stages D of k_gemm_mfma (1..4), else 0
 //   bit  12     k_gemm_mfma's 128-wide k-tile
 //   bit  13     WT: the W stage filled from the fragment-major copy

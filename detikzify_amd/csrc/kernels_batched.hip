@@ -878,10 +878,12 @@ bool launch_gemm_logsoftmax(const GemmArgs& a, hipStream_t s) {
     const bool use_wide = rw < rt || (rw == rt && wide < tall && a.M < 256);
     if (use_wt(b)) { if (use_wide) launch_gemm_g3_ls_t<128, 256, true>(b, s); else launch_gemm_g3_ls_t<256, 128, true>(b, s); }
     else if (use_wide) launch_gemm_g3_ls_t<128, 256, false>(b, s); else launch_gemm_g3_ls_t<256, 128, false>(b, s);
+    gemm_record(GEMM_KCODE(7, use_wide ? 7 : 6, 0, 0, use_wt(b) ? 1 : 0, 0, 0));
     return true;
   }
   const int mbs = (a.M + 63) / 64, nbs = (a.N + 127) / 128;
   hipLaunchKernelGGL((k_gemm_mfma<64, 128, 1, 64, true>), dim3((unsigned)(8 * ((nbs + 7) / 8) * mbs)), dim3(256), 0, s, b);
+  gemm_record(GEMM_KCODE(7, 3, 0, 0, 0, 0, 0));
   return true;
 }
 

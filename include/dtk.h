@@ -540,7 +540,9 @@ int  dtk_op_gemm_gated(dtk_ctx* ctx, const uint16_t* A, const uint16_t* W, const
                        const uint16_t* gate, int M, int N, int K, int flags, uint16_t* C);
 /* the scoring kernel pair alone: Xn [M][K] = final-normed hidden rows, W [N][K] = lm_head, targets [M] in [0, N).  Per row:
  * logprob = z[target] - logsumexp(z), lse, argmax (lowest index on ties), zmax = z[argmax], z = bf16-rounded Xn . W^T.
- * flags: DTK_GEMM_WT only.  lse_out / argmax_out / zmax_out may be NULL. */
+ * flags: DTK_GEMM_WT only.  lse_out / argmax_out / zmax_out may be NULL.  The op's scratch (the records included) starts as 0xFF bytes
+ * and the 256 guard bytes behind every result must still hold them (DTK_ERR_STATE).  dtk_gemm_last_kernel() afterwards: family 7, tile
+ * 6 / 7 (k_gemm_g3<LS> 256x128 / 128x256, + WT << 13) or 3 (k_gemm_mfma<64, 128, LS>). */
 int  dtk_op_score(dtk_ctx* ctx, const uint16_t* Xn, const uint16_t* W, const int32_t* targets, int M, int N, int K, int flags,
                   float* logprob_out, float* lse_out, int32_t* argmax_out, float* zmax_out);
 /* mode 0: y = W.x ; mode 1: y = W.rmsnorm(x, norm_w) ; fp32 result of the bf16-rounded output */
@@ -697,8 +699,8 @@ int  dtk_op_rows_move(dtk_ctx* ctx, int form, const int32_t* ids, const uint16_t
  * multiple of 8 or below K (A and W are 16-byte aligned rows in the product), strides or offsets that address past na / nw / nb / nr / nc (the
  * message names the operand), more than 8 slices, a shape the sliced kernels do not take (K < 128, N % 4).
  * *kernel_out (may be NULL) = the launchers' record of the kernel that ran: family | tile << 4 | stages << 8 | bk128 << 12 | WT << 13 |
- * epilogue << 14 | slices << 16 — family 1 k_gemm_mfma, 2 k_gemm_glds, 3 k_gemm_g3, 4 k_gemm_g3<SK> + k_sk_reduce, 5 k_gemm_g3<SL>, 6 k_gemm_naive;
- * tile 1 = 64x64, 2 = 128x64, 3 = 128x128, 4 = 64x32, 5 = 32x32, 6 = 256x128, 7 = 128x256; epilogue (k_gemm_g3 forms) 1 = through LDS, 2 = direct.
+ * epilogue << 14 | slices << 16 — family 1 k_gemm_mfma, 2 k_gemm_glds, 3 k_gemm_g3, 4 k_gemm_g3<SK> + k_sk_reduce, 5 k_gemm_g3<SL>, 6 k_gemm_naive
+ * (7: the log-softmax epilogue behind dtk_op_score, see there); tile 1 = 64x64, 2 = 128x64, 3 = 128x128, 4 = 64x32, 5 = 32x32, 6 = 256x128, 7 = 128x256; epilogue (k_gemm_g3 forms) 1 = through LDS, 2 = direct.
  * dtk_gemm_last_kernel(): the same record after any GEMM launch of the process (dtk_op_gemm, dtk_op_gemm_gated, ...).
  * Option "gemm_g3_tile" (process-wide; bit-identical): the block tile of the one-chain k_gemm_g3 — 0 = by shape (default), 1 = 256 x 128,
  * 2 = 128 x 256 — as "gemm_sk_tile" for the sliced kernels. */
