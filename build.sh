@@ -8,7 +8,7 @@ mkdir -p "$OUT" build
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 OBJCOPY=${OBJCOPY:-$("$(dirname "$(command -v "$HIPCC")")/hipconfig" -l)/llvm-objcopy}      # the toolchain's own (hipconfig -l: its clang directory)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -Wno-unused-variable"
-UNITS="kernels_decode kernels_decode_mv kernels_batch_decode kernels_batch_gemm kernels_batch_ks kernels_batch_mx kernels_batched kernels_sample_mb kernels_cfg kernels_spec dtk_api dtk_ops"
+UNITS="kernels_decode kernels_decode_mv kernels_batch_decode kernels_batch_gemm kernels_batch_ks kernels_batch_mx kernels_batched kernels_sample_mb kernels_cfg kernels_spec kernels_top dtk_api dtk_ops"
 
 if [ "$(cat build/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f build/*.o; mkdir -p build; echo "$FLAGS" > build/.flags; fi
 # an object is stale when its source or any header is newer: every header under csrc/ and the public one

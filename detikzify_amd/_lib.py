@@ -137,6 +137,8 @@ class DtkEngineOps(C.Structure):
     PREFILL_TEXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, _I64P, C.c_int, C.c_void_p, C.c_uint64, _I64P, C.c_int, C.c_uint64, C.c_int)
     # not a field: dtk_engine_set_wait_lp_op's argument (dev, tokens_out[64], logprob_out[64], sample_logprob_out[64])
     WAIT_LP = C.CFUNCTYPE(C.c_int, C.c_void_p, _I64P, C.POINTER(C.c_float), C.POINTER(C.c_float))
+    # not a field: dtk_engine_set_wait_top_op's argument (WAIT_LP's + top_ids_out[64][8], top_logprob_out[64][8])
+    WAIT_TOP = C.CFUNCTYPE(C.c_int, C.c_void_p, _I64P, C.POINTER(C.c_float), C.POINTER(C.c_float), _I32P, C.POINTER(C.c_float))
     # not a field: dtk_engine_set_sampling_ext_op's argument (dev, slot, ext)
     SAMPLING_EXT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(DtkSamplingExt))
     # not a field: dtk_engine_set_penalties_op's argument (dev, slot, presence, frequency, start)
@@ -296,6 +298,11 @@ SYMBOLS = {
     "dtk_decode_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "dtk_decode_batch_wait_top": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                             C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    # additive (ABI stays 7): the records in the batch engines, and the selection kernels on host rows
+    "dtk_engine_read_top": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    "dtk_engine_set_wait_top_op": (C.c_int, [_P, DtkEngineOps.WAIT_TOP]),
+    "dtk_op_top_logits": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     # additive (ABI stays 7): min_p / epsilon_cutoff behind top-p
     "dtk_set_sampling_ext": (C.c_int, [_P, C.POINTER(DtkSamplingExt)]),
     "dtk_set_sampling_slot_ext": (C.c_int, [_P, C.c_int, C.POINTER(DtkSamplingExt)]),

@@ -599,13 +599,23 @@ static void sampler_launch(dtk_ctx* c, SampleArgs& sa, bool mb, bool batch) {
   if (sa.pen) launch_count_token(sa, ds, c->stream);
 }
 
-// "top_logprobs": k_top_logits in front of the step's sampler, on the logits, DecState and BatchState the sampler is about to read
+// "top_logprobs": the selection in front of the step's sampler, on the logits, DecState and BatchState the sampler is about to read.
+// Which kernel: "top_kernel" 1 = k_top_logits, 2 = the sliced pair (kernels_top.hip), 0 = the sliced pair where the row has more than
+// one slice (V > 8192) and k_top_logits below, where the pair would be the single block's work in two launches.  Measured at the two
+// vocabularies the presets have: the pair is the faster one at V = 128 256 and at V = 32 256, single sequence and 64
+// slots (a rule that followed the multi-block sampler, V > 32 768, would leave the v1 vocabularies the slower kernel).  The
+// records are the same bits either way.  (top_scratch is allocated with the rings: it is there whenever top_logprobs > 0)
+static bool top_use_sliced(const dtk_ctx* c, int V) {
+  if (c->top_kernel == 1 || !c->top_scratch || !top_sliced_ok(V, c->top_slice)) return false;
+  return c->top_kernel == 2 || V > DTK_TOP_MAX_L;
+}
 static void top_logits_launch(dtk_ctx* c, const SampleArgs& sa) {
   if (!c->top_logprobs || !c->logprobs) return;
   TopArgs t;
   t.logits = sa.logits; t.V = sa.V; t.logits_stride = sa.logits_stride; t.st = sa.st; t.bs = sa.bs; t.nslots = sa.nslots;
   t.ring = sa.ring; t.k = c->top_logprobs; t.top_ring = sa.bs ? c->topb_dev : c->top_ring_dev;
-  launch_top_logits(t, c->stream);
+  if (top_use_sliced(c, sa.V)) { t.L = c->top_slice; t.scratch = c->top_scratch; launch_top_sliced(t, c->stream); }
+  else launch_top_logits(t, c->stream);
 }
 
 // dtk_set_guidance: the batched step of a context with guided pairs mixes each pair's two pending logits rows into the conditional
@@ -1178,6 +1188,8 @@ void compute_rope_tables(const dtk_config& cfg, std::vector<uint16_t>& cosv, std
 
 // not part of the ABI (hidden): dtk_engine.cpp asks whether its context's steps carry log-probabilities
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c) { return (c && c->logprobs) ? 1 : 0; }
+// ... likewise "top_logprobs" (k, 0 = off; it cannot be on without "logprobs"): dtk_engine_read_top
+extern "C" int dtk_internal_top_logprobs(const dtk_ctx* c) { return (c && c->logprobs) ? c->top_logprobs : 0; }
 // ... and tells it how many sequences it holds in the slots (delta = +1 at a join, -1 when the sequence leaves): "logprobs" is refused meanwhile
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta) { if (c) c->engine_holds.fetch_add(delta); }
 
@@ -1759,6 +1771,7 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->lse_ring_dev) (void)hipFree(c->lse_ring_dev);
   if (c->topb_dev) (void)hipFree(c->topb_dev);
   if (c->lseb_dev) (void)hipFree(c->lseb_dev);
+  if (c->top_scratch) (void)hipFree(c->top_scratch);
   if (c->cfg_dev) (void)hipFree(c->cfg_dev);
   if (c->cfg_part) (void)hipFree(c->cfg_part);
   if (c->cfg_lse) (void)hipFree(c->cfg_lse);
@@ -3646,8 +3659,23 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
         if (nb && !c->lseb_dev) { HIPCHK(c, hipMalloc(&c->lseb_dev, sizeof(float) * nb)); HIPCHK(c, hipMemset(c->lseb_dev, 0, sizeof(float) * nb)); }
         if (nb && !c->topb_host) HIPCHK(c, hipHostMalloc((void**)&c->topb_host, sizeof(TopRec) * nb, hipHostMallocDefault));
         if (nb && !c->lseb_host) HIPCHK(c, hipHostMalloc((void**)&c->lseb_host, sizeof(float) * nb, hipHostMallocDefault));
+        if (!c->top_scratch) HIPCHK(c, hipMalloc(&c->top_scratch, sizeof(TopRec) * (size_t)DTK_MAX_BATCH * DTK_TOP_MAX_SLICES));
       }
       c->top_logprobs = value; drop_graph(c); drop_batch_graphs(c);
+    }
+  }
+  else if (!strcmp(name, "top_kernel") || !strcmp(name, "top_slice")) {     // which kernel leaves the records of "top_logprobs" (top_logits_launch); same bits
+    const bool kern = !strcmp(name, "top_kernel");
+    if (kern && (value < 0 || value > 2)) return fail(c, DTK_ERR_ARG, "top_kernel must be 0 (by vocabulary), 1 (k_top_logits) or 2 (k_top_slice + k_top_merge)");
+    if (!kern && !top_sliced_ok(c->V, value))
+      return fail(c, DTK_ERR_ARG, "top_slice must be 1 .. %d with at most %d slices of the vocabulary (%d)", DTK_TOP_MAX_L, DTK_TOP_MAX_SLICES, c->V);
+    if (kern && value == 2 && !top_sliced_ok(c->V, c->top_slice))
+      return fail(c, DTK_ERR_ARG, "top_kernel = 2: the vocabulary (%d) has more than %d slices of %d", c->V, DTK_TOP_MAX_SLICES, c->top_slice);
+    if (value != (kern ? c->top_kernel : c->top_slice)) {
+      if (c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "%s: a batch step is in flight", name);
+      if (c->engine_holds.load() > 0) return fail(c, DTK_ERR_STATE, "%s: an engine holds %d sequence(s) in this context's slots", name, c->engine_holds.load());
+      if (c->launched != c->waited) return fail(c, DTK_ERR_STATE, "%s: %d single-sequence decode step(s) are unread", name, (int)(c->launched - c->waited));
+      (kern ? c->top_kernel : c->top_slice) = value; drop_graph(c); drop_batch_graphs(c);
     }
   }
   else if (!strcmp(name, "gemm_tile")) {   // MFMA GEMM block tile: 0 auto, 1 = 64x64, 2 = 128x64, 3 = 128x128 (process-wide)

@@ -155,6 +155,11 @@ struct dtk_ctx {
   TopRec* topb_host = nullptr;
   float* lseb_dev = nullptr;
   float* lseb_host = nullptr;
+  // which kernel leaves the records (top_logits_launch): "top_kernel" 0 = by vocabulary (the sliced pair where V > 8192: more than one slice), 1 =
+  // k_top_logits, 2 = the sliced pair; "top_slice" = its L (tests run several slices at a small vocabulary with it)
+  int top_kernel = 0;
+  int top_slice = DTK_TOP_MAX_L;
+  TopRec* top_scratch = nullptr;     // [DTK_MAX_BATCH][DTK_TOP_MAX_SLICES] the slices' candidates (allocated with the rings)
   // ViT
   float* pixels_dev = nullptr;
   bf16_t *patches, *VX, *VN, *VQKV, *VAO, *VH, *feats, *last_hidden;

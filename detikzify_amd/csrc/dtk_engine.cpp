@@ -45,6 +45,8 @@ struct Seq {
   std::vector<int64_t> toks;
   std::vector<float> lp, slp;       // (logprob, sample_logprob) of toks[i], kept only while a wait_lp op collects the steps (a shorter
                                     // vector = NaN for the rest: dtk_engine_read_lp)
+  std::vector<int32_t> tid;         // DTK_MAX_TOP (id, logprob) entries per token, kept only while a wait_top op collects the steps (shorter
+  std::vector<float> tlp;           // vectors = (-1, NaN) for the rest: dtk_engine_read_top)
   bool held = false;                // counted in the context's engine_holds (dtk_engine_create): from the join until the sequence leaves
   size_t read = 0, flushed = 0;     // toks[0, read) delivered; toks[read, flushed) may be delivered
   int budget = 0, emitted = 0;      // tokens the sequence may emit / has emitted
@@ -87,6 +89,8 @@ using ActiveSet = std::array<int32_t, DTK_MAX_BATCH>;
 using PrefillTextFn = int (*)(void* dev, int slot, const int64_t* ids, int T, const float* px, uint64_t image_key, const int64_t* text_ids,
                               int n_text, uint64_t text_key, int flags);
 using WaitLpFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out);
+using WaitTopFn = int (*)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out, int32_t* top_ids_out,
+                         float* top_logprob_out);
 using SamplingExtFn = int (*)(void* dev, int slot, const dtk_sampling_ext* x);
 using PenaltiesFn = int (*)(void* dev, int slot, float presence, float frequency, int start);
 using DryFn = int (*)(void* dev, int slot, const dtk_dry* d);
@@ -94,12 +98,14 @@ using LenFn = int (*)(void* dev, int slot, const dtk_length_ctl* l);
 using BiasFn = int (*)(void* dev, int slot, const int32_t* ids, const float* values, int n);
 using GuidanceFn = int (*)(void* dev, int cond_slot, int uncond_slot, float scale);
 extern "C" int dtk_internal_logprobs(const dtk_ctx* c);     // dtk_api.hip, not exported: the context's "logprobs" option
+extern "C" int dtk_internal_top_logprobs(const dtk_ctx* c); // ... and its "top_logprobs" (0 = off)
 extern "C" void dtk_internal_engine_holds(dtk_ctx* c, int delta);   // ... which is refused while this engine holds sequences
 
 struct dtk_engine {
   dtk_engine_ops ops{};
   PrefillTextFn prefill_text = nullptr;     // dtk_engine_set_prefill_text_op (dtk_engine_create: dtk_prefill_slot_text)
   WaitLpFn wait_lp = nullptr;               // dtk_engine_set_wait_lp_op: collects a step instead of ops.wait
+  WaitTopFn wait_top = nullptr;             // dtk_engine_set_wait_top_op: collects a step instead of both (dtk_engine_create: dtk_decode_batch_wait_top)
   SamplingExtFn sampling_ext = nullptr;     // dtk_engine_set_sampling_ext_op (dtk_engine_create: dtk_set_sampling_slot_ext)
   PenaltiesFn penalties = nullptr;          // dtk_engine_set_penalties_op (dtk_engine_create: dtk_set_penalties_slot)
   DryFn dry = nullptr;                      // dtk_engine_set_dry_op (dtk_engine_create: dtk_set_dry_slot)
@@ -188,10 +194,14 @@ void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
   const ActiveSet set = e->inflight.front();
   int64_t toks[DTK_MAX_BATCH];
   float lp[DTK_MAX_BATCH], slp[DTK_MAX_BATCH];
+  int32_t tid[DTK_MAX_BATCH * DTK_MAX_TOP];
+  float tlp[DTK_MAX_BATCH * DTK_MAX_TOP];
   const WaitLpFn wait_lp = (e->own_ctx && !dtk_internal_logprobs(e->own_ctx)) ? nullptr : e->wait_lp;
+  const WaitTopFn wait_top = (e->own_ctx && !dtk_internal_top_logprobs(e->own_ctx)) ? nullptr : e->wait_top;
   lk.unlock();
   const double t0 = now_s();
-  const int rc = wait_lp ? wait_lp(e->ops.dev, toks, lp, slp) : e->ops.wait(e->ops.dev, toks);
+  const int rc = wait_top ? wait_top(e->ops.dev, toks, lp, slp, tid, tlp)
+                          : wait_lp ? wait_lp(e->ops.dev, toks, lp, slp) : e->ops.wait(e->ops.dev, toks);
   const double t1 = now_s();
   lk.lock();
   if (e->err_rc) return;             // (poisoned while we waited: the queue of steps is gone)
@@ -218,9 +228,15 @@ void collect(dtk_engine* e, std::unique_lock<std::mutex>& lk, bool drain) {
       return;
     }
     q.toks.push_back(tok);
-    if (wait_lp) {      // (an op given mid-sequence: the earlier tokens' pairs are NaN)
+    if (wait_lp || wait_top) {      // (an op given mid-sequence: the earlier tokens' pairs are NaN)
       q.lp.resize(q.toks.size() - 1, NAN); q.slp.resize(q.toks.size() - 1, NAN);
       q.lp.push_back(lp[s]); q.slp.push_back(slp[s]);
+    }
+    if (wait_top) {                 // (likewise: the earlier tokens' records are (-1, NaN)).  A pair: the leader's record
+      const size_t at = (q.toks.size() - 1) * DTK_MAX_TOP;
+      q.tid.resize(at, -1); q.tlp.resize(at, NAN);
+      q.tid.insert(q.tid.end(), tid + (size_t)s * DTK_MAX_TOP, tid + (size_t)(s + 1) * DTK_MAX_TOP);
+      q.tlp.insert(q.tlp.end(), tlp + (size_t)s * DTK_MAX_TOP, tlp + (size_t)(s + 1) * DTK_MAX_TOP);
     }
     q.emitted++;
     e->st.tokens_out++;
@@ -479,7 +495,7 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
     unlink(j->slot_out);
     if (c->uncond) unlink(c->uncond->slot_out);
     Seq& q = e->seq[j->slot_out];
-    q.toks.clear(); q.lp.clear(); q.slp.clear();
+    q.toks.clear(); q.lp.clear(); q.slp.clear(); q.tid.clear(); q.tlp.clear();
     q.read = q.flushed = 0;
     q.emitted = q.launched = 0;
     q.skip = j->how_out == DTK_JOIN_RESUMED ? 1 : 0;
@@ -500,7 +516,7 @@ void exec_join(dtk_engine* e, std::unique_lock<std::mutex>& lk, Cmd* c) {
     if (e->own_ctx && !q.held) { q.held = true; dtk_internal_engine_holds(e->own_ctx, +1); }
     if (c->uncond) {      // the follower: launched and stopped with its leader, nothing of it is delivered
       Seq& f = e->seq[c->uncond->slot_out];
-      f.toks.clear(); f.lp.clear(); f.slp.clear();
+      f.toks.clear(); f.lp.clear(); f.slp.clear(); f.tid.clear(); f.tlp.clear();
       f.read = f.flushed = 0;
       f.emitted = f.launched = 0;
       f.skip = q.skip; f.budget = q.budget; f.need = q.need; f.n_stop = 0;
@@ -606,6 +622,7 @@ int submit(dtk_engine* e, dtk_join* j, const int64_t* text, int n_text, uint64_t
 int ctx_launch(void* d, const int32_t* a) { return dtk_decode_batch_launch((dtk_ctx*)d, a); }
 int ctx_wait(void* d, int64_t* t) { return dtk_decode_batch_wait((dtk_ctx*)d, t); }
 int ctx_wait_lp(void* d, int64_t* t, float* lp, float* slp) { return dtk_decode_batch_wait_lp((dtk_ctx*)d, t, lp, slp); }
+int ctx_wait_top(void* d, int64_t* t, float* lp, float* slp, int32_t* ti, float* tl) { return dtk_decode_batch_wait_top((dtk_ctx*)d, t, lp, slp, ti, tl); }
 int ctx_prefill(void* d, int s, const int64_t* ids, int T, const float* px, uint64_t key, int flags) { return dtk_prefill_slot((dtk_ctx*)d, s, ids, T, px, key, flags, nullptr); }
 int ctx_sampling(void* d, int s, const dtk_sampling* sp) { return dtk_set_sampling_slot((dtk_ctx*)d, s, sp); }
 int ctx_sampling_ext(void* d, int s, const dtk_sampling_ext* x) {     // (0 / 0: dtk_set_sampling_slot has just left exactly that)
@@ -664,6 +681,7 @@ int dtk_engine_create(dtk_ctx* ctx, dtk_engine** out) {
     std::lock_guard<std::mutex> g((*out)->mu);
     (*out)->own_ctx = ctx;
     (*out)->wait_lp = ctx_wait_lp;
+    (*out)->wait_top = ctx_wait_top;
     (*out)->sampling_ext = ctx_sampling_ext;
     (*out)->penalties = ctx_penalties;
     (*out)->dry = ctx_dry;
@@ -678,6 +696,13 @@ int dtk_engine_set_wait_lp_op(dtk_engine* e, WaitLpFn wait_lp) {
   if (!e) return DTK_ERR_ARG;
   std::lock_guard<std::mutex> g(e->mu);
   e->wait_lp = wait_lp;
+  return DTK_OK;
+}
+
+int dtk_engine_set_wait_top_op(dtk_engine* e, WaitTopFn wait_top) {
+  if (!e) return DTK_ERR_ARG;
+  std::lock_guard<std::mutex> g(e->mu);
+  e->wait_top = wait_top;
   return DTK_OK;
 }
 
@@ -942,12 +967,22 @@ int dtk_engine_read(dtk_engine* e, int slot, int64_t* out, int cap, int32_t* n_o
   return dtk_engine_read_lp(e, slot, out, nullptr, nullptr, cap, n_out, state_out, timeout_ms);
 }
 
-// (logprob_out == sample_logprob_out == nullptr: dtk_engine_read — the pairs are dropped)
 int dtk_engine_read_lp(dtk_engine* e, int slot, int64_t* out, float* logprob_out, float* sample_logprob_out, int cap, int32_t* n_out,
                        int32_t* state_out, int timeout_ms) {
-  if (!e || slot < 0 || slot >= DTK_MAX_BATCH || !out || cap < 1 || !n_out || !state_out || !logprob_out != !sample_logprob_out) return DTK_ERR_ARG;
+  return dtk_engine_read_top(e, slot, out, logprob_out, sample_logprob_out, nullptr, nullptr, cap, n_out, state_out, timeout_ms);
+}
+
+// (logprob_out == sample_logprob_out == nullptr: dtk_engine_read — the pairs are dropped; top_ids_out == top_logprob_out == nullptr:
+// dtk_engine_read_lp — the records are dropped)
+int dtk_engine_read_top(dtk_engine* e, int slot, int64_t* out, float* logprob_out, float* sample_logprob_out, int32_t* top_ids_out,
+                        float* top_logprob_out, int cap, int32_t* n_out, int32_t* state_out, int timeout_ms) {
+  if (!e || slot < 0 || slot >= DTK_MAX_BATCH || !out || cap < 1 || !n_out || !state_out || !logprob_out != !sample_logprob_out ||
+      !top_ids_out != !top_logprob_out || (top_ids_out && !logprob_out))
+    return DTK_ERR_ARG;
   if (logprob_out && e->own_ctx && !dtk_internal_logprobs(e->own_ctx)) return DTK_ERR_ARG;     // the context's "logprobs" option is off
+  if (top_ids_out && e->own_ctx && !dtk_internal_top_logprobs(e->own_ctx)) return DTK_ERR_ARG; // ... its "top_logprobs" option
   std::unique_lock<std::mutex> lk(e->mu);
+  if (top_ids_out && !e->wait_top) return DTK_ERR_ARG;      // the engine collects no records (dtk_engine_set_wait_top_op)
   Seq& q = e->seq[slot];
   if (q.follower) return DTK_ERR_ARG;      // the unconditional slot of a guided sequence: its tokens are the leader's
   *n_out = 0;
@@ -964,6 +999,13 @@ int dtk_engine_read_lp(dtk_engine* e, int slot, int64_t* out, float* logprob_out
       const size_t k = q.read + i;
       logprob_out[i] = k < q.lp.size() ? q.lp[k] : NAN;
       sample_logprob_out[i] = k < q.slp.size() ? q.slp[k] : NAN;
+    }
+  }
+  if (n && top_ids_out) {
+    for (size_t i = 0; i < n * DTK_MAX_TOP; ++i) {
+      const size_t k = q.read * DTK_MAX_TOP + i;
+      top_ids_out[i] = k < q.tid.size() ? q.tid[k] : -1;
+      top_logprob_out[i] = k < q.tlp.size() ? q.tlp[k] : NAN;
     }
   }
   q.read += n;

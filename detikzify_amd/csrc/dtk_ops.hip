@@ -1454,5 +1454,41 @@ int dtk_op_spec_lookup(dtk_ctx* c, const int32_t* ids, int len, int K, int max_n
   return DTK_OK;
 }
 
+// dtk_set_option "top_logprobs"'s selection alone, on rows of the call's own: kernel 1 = k_top_logits, 2 = k_top_slice + k_top_merge
+// with slices of L, through the shipped launchers.  The rows are the slots of a batched step (record index 0 of a ring of one);
+// active / forced (NULL: every row active / none forced) are the BatchState flags and DecState::force_plus1 the kernels read.
+// ids_out / z_out [rows][DTK_MAX_TOP] are uploaded first: what a kernel does not write (an inactive row, entries >= k) comes back as
+// the caller left it
+int dtk_op_top_logits(dtk_ctx* c, const float* logits, int rows, int V, int k, int kernel, int L, const int32_t* active, const int32_t* forced,
+                      int32_t* ids_out, float* z_out) {
+  if (!c || !logits || !ids_out || !z_out || rows < 1 || rows > DTK_MAX_BATCH || V < 1 || V > DTK_TOP_MAX_SLICES * DTK_TOP_MAX_L || k < 1 ||
+      k > DTK_MAX_TOP || k > V || (kernel != 1 && kernel != 2))
+    return fail(c, DTK_ERR_ARG, "dtk_op_top_logits: bad argument (rows 1..%d, V 1..%d, k 1..%d and <= V, kernel 1 or 2)", DTK_MAX_BATCH,
+                DTK_TOP_MAX_SLICES * DTK_TOP_MAX_L, DTK_MAX_TOP);
+  if (kernel == 2 && !top_sliced_ok(V, L))
+    return fail(c, DTK_ERR_ARG, "dtk_op_top_logits: L must be 1..%d with at most %d slices of V = %d", DTK_TOP_MAX_L, DTK_TOP_MAX_SLICES, V);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, "dtk_op_top_logits", 0x5a);
+  BatchState hbs; DecState hst[DTK_MAX_BATCH];
+  memset(&hbs, 0, sizeof hbs); memset(hst, 0, sizeof hst);
+  for (int j = 0; j < DTK_MAX_BATCH; ++j) hbs.share_src[j] = -1;
+  for (int j = 0; j < rows; ++j) { hbs.active[j] = (!active || active[j]) ? 1 : 0; hst[j].force_plus1 = (forced && forced[j]) ? 1 : 0; }
+  std::vector<TopRec> recs((size_t)rows);
+  for (int j = 0; j < rows; ++j)
+    for (int i = 0; i < DTK_MAX_TOP; ++i) { recs[(size_t)j].id[i] = ids_out[(size_t)j * DTK_MAX_TOP + i]; recs[(size_t)j].z[i] = z_out[(size_t)j * DTK_MAX_TOP + i]; }
+  TopArgs t;
+  t.logits = r.in<float>(logits, (size_t)rows * V); t.V = V; t.logits_stride = V;
+  t.bs = r.in<BatchState>(&hbs, 1); t.st = r.in<DecState>(hst, DTK_MAX_BATCH); t.nslots = rows; t.ring = 1; t.k = k;
+  t.top_ring = r.io<TopRec>(recs.data(), (size_t)rows, "records");
+  if (kernel == 2) { t.L = L; t.scratch = (TopRec*)r.take(sizeof(TopRec) * (size_t)rows * DTK_TOP_MAX_SLICES); }
+  if (const int rc = r.upload(s)) return rc;
+  if (kernel == 2) launch_top_sliced(t, s); else launch_top_logits(t, s);
+  if (const int rc = r.finish(s)) return rc;
+  for (int j = 0; j < rows; ++j)
+    for (int i = 0; i < DTK_MAX_TOP; ++i) { ids_out[(size_t)j * DTK_MAX_TOP + i] = recs[(size_t)j].id[i]; z_out[(size_t)j * DTK_MAX_TOP + i] = recs[(size_t)j].z[i]; }
+  return DTK_OK;
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -154,8 +154,16 @@ struct TopArgs {
   const DecState* st; const BatchState* bs; int nslots;
   int ring; int k;
   TopRec* top_ring;
+  int L = 0;                           // launch_top_sliced: logits per slice (1 .. DTK_TOP_MAX_L, at most DTK_TOP_MAX_SLICES slices)
+  TopRec* scratch = nullptr;           // launch_top_sliced: [rows][DTK_TOP_MAX_SLICES] the slices' k first entries, between its two launches
 };
 void launch_top_logits(const TopArgs& a, hipStream_t s);
+// the same record in two launches (kernels_top.hip): k_top_slice, grid (ceil(V / L), rows), leaves every slice's k first entries in
+// a.scratch, k_top_merge, one block per row, selects among them.  Exact, so which of the two ran never shows in a record
+#define DTK_TOP_MAX_L 8192             // the sampler chain's slice (kernels_sample_mb.hip)
+#define DTK_TOP_MAX_SLICES 32
+bool top_sliced_ok(int V, int L);      // the shapes launch_top_sliced takes
+void launch_top_sliced(const TopArgs& a, hipStream_t s);
 // dtk_set_guidance (kernels_cfg.hip): classifier-free guidance of the batched step.  A pair = the slot whose pending raw logits row is
 // replaced, in place and in front of k_top_logits and the sampler chain, by g * (log_softmax(zc) - log_softmax(zu)) + log_softmax(zu),
 // and the slot whose row is zu and which forwards the token the first one's chain chose.

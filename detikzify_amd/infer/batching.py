@@ -26,8 +26,12 @@ _NUDGE = object()      # wakes a thread that waits on its slot's queue without h
 
 
 class _Sequence:
-    def __init__(self, engine: "BatchEngine", slot: int, logprobs: bool = False):
+    def __init__(self, engine: "BatchEngine", slot: int, logprobs: bool = False, top: int = 0):
         self.engine, self.slot = engine, slot
+        # sequence(logprobs=True, top_logprobs=j): per token handed to this sequence its j most likely tokens and their log-probabilities
+        self._top = int(top)
+        self.top_ids: Optional[List[List[int]]] = [] if top else None
+        self.top_logprobs: Optional[List[List[float]]] = [] if top else None
         # sequence(logprobs=True): the (logprob, sample_logprob) of every token handed to this sequence so far, in token order
         self.logprobs: Optional[List[float]] = [] if logprobs else None
         self.sample_logprobs: Optional[List[float]] = [] if logprobs else None
@@ -64,7 +68,15 @@ class BatchEngine:
 
     def __init__(self, model, max_batch: Optional[int] = None, share_prefix: bool = True, pipeline: bool = True,
                  gather: int = 0, gather_timeout: float = 0.5, prefix_slots: Optional[int] = None, resume_in_place: bool = True,
-                 guided_pairs: int = 0):
+                 guided_pairs: int = 0, top_logprobs: Optional[int] = None):
+        from ..model.modeling import check_top_logprobs
+        # top_logprobs = k (1 .. 8): every step also delivers the k most likely tokens of the logits each token was sampled from;
+        # sequence(logprobs=True, top_logprobs=j <= k) collects them.  The model is switched over below, before any join, and close()
+        # restores what it found.  The switches refuse unread single-sequence steps, and a plain generate() usually leaves one behind, so
+        # the model's single-sequence sampling state is reset first (model.set_sampling(): default greedy sampling, unread steps forgotten);
+        # close() does not bring that back — every generate() sets its own.  None: sequences that ask are refused
+        self.top_logprobs = check_top_logprobs(top_logprobs)
+        self._found_options: Optional[Tuple[bool, int]] = None
         n = model.num_slots()
         if n <= 0:
             raise ValueError("model was loaded without batch slots (load(..., batch_slots=N))")
@@ -137,9 +149,42 @@ class BatchEngine:
         # trickle in one pipeline flush at a time); gives up after gather_timeout seconds
         self.gather_left = min(int(gather), self.capacity)
         self.gather_deadline = time.perf_counter() + gather_timeout
+        if self.top_logprobs:
+            self._found_options = (model.logprobs_enabled, model.top_logprobs_enabled)
+            try:
+                model.set_sampling()        # the single sequence starts afresh: see the constructor's docstring / comment on top_logprobs
+                model.enable_top_logprobs(self.top_logprobs)
+            except BaseException:
+                self._restore_options()
+                raise
+            self.lp = True
         if self.guided_pairs:
-            model.reserve_guidance(self.guided_pairs)
+            try:
+                model.reserve_guidance(self.guided_pairs)
+            except BaseException:
+                self._restore_options()
+                raise
         model.batch_engine = self
+
+    def _restore_options(self):
+        """top_logprobs=k: the model's two options as the constructor found them (no step is in flight)"""
+        if self._found_options is not None:
+            (lp, k), self._found_options = self._found_options, None
+            self.model.enable_top_logprobs(k)
+            if not lp:
+                self.model.disable_logprobs()
+
+    def _check_top(self, top_logprobs, logprobs) -> int:
+        """sequence(top_logprobs=j) -> j (0: not asked for); the refusals of an engine built without top_logprobs=, or with a smaller k"""
+        if not top_logprobs:
+            return 0
+        if not self.top_logprobs:
+            raise NotImplementedError("top_logprobs: not in the batch engines yet")
+        from ..model.modeling import check_top_logprobs
+        j = check_top_logprobs(top_logprobs, logprobs)
+        if j > self.top_logprobs:
+            raise ValueError(f"top_logprobs = {j}: this engine was built with top_logprobs={self.top_logprobs}")
+        return j
 
     @contextmanager
     def _locked(self):
@@ -177,6 +222,8 @@ class BatchEngine:
                     self.model.set_guidance(None, c, None)
                 self.dev_pairs.clear()
                 self.model.reserve_guidance(0)
+            if self.error is None:
+                self._restore_options()
         self.model.batch_engine = None
 
     def busy(self) -> bool:
@@ -200,12 +247,11 @@ class BatchEngine:
         once and forked; its own slot per owner), neutral greedy sampling and no tables; the two resume in place only if both can; the
         pair is set once both prompts are in, and both slots are released together.
         (max_new_tokens / stop_ids / per_token are for infer/engine.NativeBatchEngine: here the sequence's end is emit's verdict.)"""
-        if top_logprobs:
-            raise NotImplementedError("top_logprobs: not in the batch engines yet")
+        top = self._check_top(top_logprobs, logprobs)
         if guidance is not None:
             if not self.guided_pairs:
                 raise NotImplementedError("guidance_scale: not in the batch engines yet (this engine was built without guided_pairs=)")
-            yield from self._guided_sequence(ids, pixel_values, sampling, owner, text_ids, logprobs, guidance)
+            yield from self._guided_sequence(ids, pixel_values, sampling, owner, text_ids, logprobs, guidance, top)
             return
         from ..model.modeling import (DRY_KEYS, DUMMY_IMAGE_KEY, SHAPE_KEYS, adapter_text, check_dry, check_penalties, check_truncation,
                                       shape_of_sampling, text_image_key, text_key)
@@ -272,7 +318,7 @@ class BatchEngine:
                 joined = True
                 if self.driver is not None:
                     self.tokq[self.driver].put(_NUDGE)      # it may be sleeping through the warm start
-            seq = _Sequence(self, slot, logprobs)
+            seq = _Sequence(self, slot, logprobs, top)
             if logprobs:
                 with self._locked():
                     self.lp_sinks[slot] = seq
@@ -297,7 +343,7 @@ class BatchEngine:
                     self.free.append(slot)
                 self.cv.notify_all()   # a slot may have become free
 
-    def _guided_sequence(self, ids, pixel_values, sampling, owner, text_ids, logprobs, guidance):
+    def _guided_sequence(self, ids, pixel_values, sampling, owner, text_ids, logprobs, guidance, top=0):
         """BatchEngine.sequence(guidance=...): two slots, two plans, one join under the engine's lock"""
         from .._lib import DtkError
         from ..model.modeling import (DRY_KEYS, DUMMY_IMAGE_KEY, adapter_text, check_dry, check_guidance_scale, check_penalties, check_truncation,
@@ -384,7 +430,7 @@ class BatchEngine:
                 joined = True
                 if self.driver is not None:
                     self.tokq[self.driver].put(_NUDGE)
-            seq = _Sequence(self, c, logprobs)
+            seq = _Sequence(self, c, logprobs, top)
             seq.uncond_slot, seq.resumed = u, resume
             if logprobs:
                 with self._locked():
@@ -596,7 +642,11 @@ class BatchEngine:
             return pushed
         try:
             t0 = time.perf_counter()
-            toks, lps, slps = self.model.decode_batch_wait_lp() if self.lp else (self.model.decode_batch_wait(), None, None)
+            tis = tls = None
+            if self.top_logprobs:
+                toks, lps, slps, tis, tls = self.model.decode_batch_wait(top=True)
+            else:
+                toks, lps, slps = self.model.decode_batch_wait_lp() if self.lp else (self.model.decode_batch_wait(), None, None)
             dt = time.perf_counter() - t0
             self.t_wait += dt
             self.t_last_collect = t0 + dt
@@ -614,6 +664,10 @@ class BatchEngine:
                     if s in self.lp_sinks:
                         self.lp_sinks[s].logprobs.append(lps[s])
                         self.lp_sinks[s].sample_logprobs.append(slps[s])
+                        j = self.lp_sinks[s]._top
+                        if j:       # (a pair: the leader's record, of the guided distribution)
+                            self.lp_sinks[s].top_ids.append(list(tis[s][:j]))
+                            self.lp_sinks[s].top_logprobs.append(list(tls[s][:j]))
                     if s in self.sinks:
                         pushed.append((s, toks[s]))
                     else:
@@ -779,7 +833,9 @@ def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_
     A guided tree decodes in two slots — its own and the negative branch's — so at most decode_slots // 2 trees decode at once (the
     rest take turns, as with `slots` < trees) and the engine reserves that many standing pairs; the negative image is encoded once and
     forked into every tree's second slot.  A text-only entry without negative_text raises the generator's ValueError before any thread
-    starts."""
+    starts.
+    top_logprobs=j (1 .. 8, in gen_kwargs or the pipeline's): the engine is built with it and every document carries `.token_top_ids` /
+    `.token_top_logprobs` (and `.token_logprobs` / `.token_sample_logprobs`), as DetikzifyGenerator.sample attaches them."""
     import torch
     texts = list(texts) if texts is not None else [None] * len(images)
     assert len(texts) == len(images), "one text (or None) per image"
@@ -811,6 +867,10 @@ def simulate_parallel_images(pipeline, images, trees_per_image: int, expansions_
         width = max(1, min(width, dec // 2))
         pairs = dict(guided_pairs=width)
         width *= 2
+    from ..model.modeling import check_top_logprobs
+    topk = check_top_logprobs(options.get("top_logprobs"))      # top_logprobs=j: every document carries its tokens' j alternatives
+    if topk:
+        pairs["top_logprobs"] = topk
     engine = make_engine(pipeline.model, processor=pipeline.processor, max_batch=width, gather=min(trees, width // 2) if guided else trees,
                          resume_in_place=resume_in_place, **pairs) if trees > 1 else None
     out: "queue.Queue" = queue.Queue()

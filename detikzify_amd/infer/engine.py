@@ -29,8 +29,14 @@ from .. import _lib
 
 
 class _NativeSequence:
-    def __init__(self, engine: "NativeBatchEngine", slot: int, logprobs: bool = False):
+    def __init__(self, engine: "NativeBatchEngine", slot: int, logprobs: bool = False, top: int = 0):
         self.engine, self.slot = engine, slot
+        # sequence(logprobs=True, top_logprobs=j): per token read so far its j most likely tokens and their log-probabilities
+        # (dtk_engine_read_top; the engine's own k >= j columns are cut to j)
+        self._top = int(top)
+        self.top_ids: Optional[List[List[int]]] = [] if top else None
+        self.top_logprobs: Optional[List[List[float]]] = [] if top else None
+        self._ti, self._tl = ((C.c_int32 * (256 * _lib.DTK_MAX_TOP))(), (C.c_float * (256 * _lib.DTK_MAX_TOP))()) if top else (None, None)
         self._buf = (C.c_int64 * 256)()
         # sequence(logprobs=True): the (logprob, sample_logprob) of every token read so far, in token order (dtk_engine_read_lp)
         self.logprobs: Optional[List[float]] = [] if logprobs else None
@@ -42,7 +48,17 @@ class _NativeSequence:
 
     def _read(self, cap: int, timeout_ms: int) -> List[int]:
         e = self.engine
-        if self.logprobs is not None:
+        if self._top:
+            rc = e.lib.dtk_engine_read_top(e._h, self.slot, self._buf, self._lp, self._slp, self._ti, self._tl, cap, C.byref(self._n),
+                                           C.byref(self._state), timeout_ms)
+            if rc == 0 and self._n.value:
+                self.logprobs.extend(self._lp[:self._n.value])
+                self.sample_logprobs.extend(self._slp[:self._n.value])
+                for i in range(self._n.value):
+                    at = i * _lib.DTK_MAX_TOP
+                    self.top_ids.append(list(self._ti[at:at + self._top]))
+                    self.top_logprobs.append(list(self._tl[at:at + self._top]))
+        elif self.logprobs is not None:
             rc = e.lib.dtk_engine_read_lp(e._h, self.slot, self._buf, self._lp, self._slp, cap, C.byref(self._n), C.byref(self._state), timeout_ms)
             if rc == 0 and self._n.value:
                 self.logprobs.extend(self._lp[:self._n.value])
@@ -124,6 +140,15 @@ class _ScriptedOps:
             for j in range(_lib.DTK_MAX_BATCH):
                 out[j], lp_out[j], slp_out[j] = toks[j], lp[j], slp[j]
 
+        def wait_top(dev, out, lp_out, slp_out, ti_out, tl_out):
+            toks, lp, slp, ti, tl = model.decode_batch_wait(top=True)
+            for j in range(_lib.DTK_MAX_BATCH):
+                out[j], lp_out[j], slp_out[j] = toks[j], lp[j], slp[j]
+                for i in range(_lib.DTK_MAX_TOP):
+                    has = i < len(ti[j])
+                    ti_out[j * _lib.DTK_MAX_TOP + i] = ti[j][i] if has else -1
+                    tl_out[j * _lib.DTK_MAX_TOP + i] = tl[j][i] if has else float("nan")
+
         def prefill(dev, slot, ids, T, pixels, key, flags):
             px = engine._pixels_by_key.get(int(key)) if pixels else None
             model.prefill(ids_of(ids, T), px, slot=slot, reuse=bool(flags & _lib.DTK_PREFILL_REUSE_PREFIX))
@@ -182,6 +207,7 @@ class _ScriptedOps:
         # the text prefill only for a device that has an adapter (an engine without it refuses text joins in submit)
         self.prefill_text = O.PREFILL_TEXT(guard(prefill_text)) if _has_adapter(model) else None
         self.wait_lp = O.WAIT_LP(guard(wait_lp))       # handed to the engine by the first sequence(logprobs=True)
+        self.wait_top = O.WAIT_TOP(guard(wait_top))    # handed to an engine built with top_logprobs=k
         self.sampling_ext = O.SAMPLING_EXT(guard(sampling_ext)) if hasattr(model, "set_sampling_ext") else None
         self.penalties = O.PENALTIES(guard(penalties)) if hasattr(model, "set_penalties") else None
         self.dry = O.DRY(guard(dry)) if hasattr(model, "set_dry") else None
@@ -202,10 +228,19 @@ class NativeBatchEngine:
 
     def __init__(self, model, max_batch: Optional[int] = None, share_prefix: bool = True, pipeline: bool = True, gather: int = 0,
                  gather_timeout: float = 0.5, prefix_slots: Optional[int] = None, resume_in_place: bool = True,
-                 flush_tokens: Optional[Iterable[int]] = None, flush_max: int = 32, guided_pairs: int = 0):
-        """`guided_pairs`=P > 0: up to P classifier-free-guided sequences (sequence(guidance=...), model.generate's guidance_scale)
+                 flush_tokens: Optional[Iterable[int]] = None, flush_max: int = 32, guided_pairs: int = 0,
+                 top_logprobs: Optional[int] = None):
+        """`top_logprobs`=k (1 .. 8): every step of this engine also delivers the k most likely tokens of the logits each token was sampled
+        from; sequence(logprobs=True, top_logprobs=j <= k) collects them.  The constructor switches the model over (enable_logprobs() +
+        enable_top_logprobs(k)) before any join, close() restores what it found.  The switches refuse unread single-sequence steps, and a
+        plain generate() usually leaves one behind, so the constructor first resets the model's single-sequence sampling state
+        (model.set_sampling(): default greedy sampling, unread steps forgotten); close() does not bring that back — every generate() sets
+        its own.  None (the default): sequences that ask are refused.
+        `guided_pairs`=P > 0: up to P classifier-free-guided sequences (sequence(guidance=...), model.generate's guidance_scale)
         decode at once, each in two slots; the device's pair table is reserved for P standing pairs (model.reserve_guidance), so a
         pair that forms or dissolves re-captures nothing.  0 (the default): nothing is reserved and guided sequences are refused."""
+        from ..model.modeling import check_top_logprobs
+        self.top_logprobs = check_top_logprobs(top_logprobs)
         n = model.num_slots()
         if n <= 0:
             raise ValueError("model was loaded without batch slots (load(..., batch_slots=N))")
@@ -257,10 +292,25 @@ class NativeBatchEngine:
                 rc = self.lib.dtk_engine_set_guidance_op(self._h, self._scripted.guidance)
         if rc != 0:
             raise _lib.DtkError(f"dtk_engine_create failed ({rc})")
+        self._found_options = None
+        if self.top_logprobs:
+            try:        # no sequence has joined: the switches' own refusals (unread single-sequence steps, another engine's sequences) hold
+                self._found_options = (model.logprobs_enabled, model.top_logprobs_enabled)
+                model.set_sampling()        # the single sequence starts afresh: see the constructor's docstring / comment on top_logprobs
+                model.enable_top_logprobs(self.top_logprobs)
+                if self._scripted is not None and self.lib.dtk_engine_set_wait_top_op(self._h, self._scripted.wait_top) != 0:
+                    raise _lib.DtkError("dtk_engine_set_wait_top_op failed")
+                self._lp = True
+            except BaseException:
+                self._restore_options()
+                self.lib.dtk_engine_destroy(self._h)
+                self._h = C.c_void_p()
+                raise
         if self.guided_pairs:
             try:
                 model.reserve_guidance(self.guided_pairs)
             except BaseException:
+                self._restore_options()
                 self.lib.dtk_engine_destroy(self._h)
                 self._h = C.c_void_p()
                 raise
@@ -310,8 +360,17 @@ class NativeBatchEngine:
                     if g is not None and g["is_cond"]:
                         self.model.set_guidance(None, slot, None)
                 self.model.reserve_guidance(0)
+            self._restore_options()
         if getattr(self.model, "batch_engine", None) is self:
             self.model.batch_engine = None
+
+    def _restore_options(self):
+        """top_logprobs=k: the model's two options as the constructor found them (the loop has stopped: nothing is in flight)"""
+        if self._found_options is not None:
+            (lp, k), self._found_options = self._found_options, None
+            self.model.enable_top_logprobs(k)
+            if not lp:
+                self.model.disable_logprobs()
 
     def __del__(self):
         try:
@@ -422,8 +481,7 @@ class NativeBatchEngine:
         sequence's — its own prefix key, so one negative image is encoded once and forked into every guided sequence's second slot, its
         own slot per owner for resume — and both slots are released together.  `sampling`, `max_new_tokens` and `stop_ids` describe the
         sequence; the second slot samples nothing of its own."""
-        if top_logprobs:
-            raise NotImplementedError("top_logprobs: not in the batch engines yet")
+        top = self._check_top(top_logprobs, logprobs)
         if not self._h:
             raise _lib.DtkError("the batch engine is closed")
         if guidance is not None and not self.guided_pairs:
@@ -541,7 +599,7 @@ class NativeBatchEngine:
             cond = dict(j=j, want=want, ids=ids, tids=tids, tkey=tkey, has_px=pixel_values is not None, keep=px)
             neg = dict(j=gj, want=gwant, ids=gids, tids=gtids, tkey=gtkey, has_px=guidance.get("pixel_values") is not None, keep=gpx)
             tables = dict(ext=ext, pen=(pen_p, pen_f, pen_s), dry=dry, lctl=lctl, bias=(bias_ids, bias_val, len(bias_pairs)))
-            yield from self._guided(cond, neg, gscale, owner, logprobs, tables, pick)
+            yield from self._guided(cond, neg, gscale, owner, logprobs, tables, pick, top)
             return
         with self._cv:
             if logprobs:
@@ -603,7 +661,7 @@ class NativeBatchEngine:
         joined = rc == 0
         try:
             self._joined(j, joined, f"join of a sequence failed ({rc})")
-            yield _NativeSequence(self, slot, logprobs)
+            yield _NativeSequence(self, slot, logprobs, top)
         finally:
             if joined and self._h:
                 self.lib.dtk_engine_leave(self._h, slot)
@@ -613,6 +671,18 @@ class NativeBatchEngine:
                 self.free.append(slot)
                 self._cv.notify_all()
             del ids, px, tids     # (kept alive until here: the native join read them)
+
+    def _check_top(self, top_logprobs, logprobs) -> int:
+        """sequence(top_logprobs=j) -> j (0: not asked for); the refusals of an engine built without top_logprobs=, or with a smaller k"""
+        if not top_logprobs:
+            return 0
+        if not self.top_logprobs:
+            raise NotImplementedError("top_logprobs: not in the batch engines yet")
+        from ..model.modeling import check_top_logprobs
+        j = check_top_logprobs(top_logprobs, logprobs)
+        if j > self.top_logprobs:
+            raise ValueError(f"top_logprobs = {j}: this engine was built with top_logprobs={self.top_logprobs}")
+        return j
 
     def _want_logprobs(self):
         """(under _cv) sequence(logprobs=True): the first such sequence switches the device over, before any sequence holds a slot"""
@@ -636,7 +706,7 @@ class NativeBatchEngine:
             elif j.how_out == _lib.DTK_JOIN_IN_PLACE:
                 self.inplace_reuses += 1
 
-    def _guided(self, cond, neg, scale, owner, logprobs, tables, pick):
+    def _guided(self, cond, neg, scale, owner, logprobs, tables, pick, top=0):
         """sequence(guidance=...): two slots, two plans (`cond`, `neg`: join, prefix key and tensors of each prompt), one native command
         (dtk_engine_submit_guided) that carries the sequence's `tables`.  The negative branch is planned after the sequence's own
         bookkeeping has been applied, so the two never claim the same prefix-cache slot; an owner's negative branch remembers its slot
@@ -678,7 +748,7 @@ class NativeBatchEngine:
         joined = self.lib.dtk_engine_await(self._h, ticket.value) == 0
         try:
             self._joined(j, joined, "join of a guided sequence failed")
-            seq = _NativeSequence(self, slot, logprobs)
+            seq = _NativeSequence(self, slot, logprobs, top)
             seq.uncond_slot, seq.how, seq.uncond_how = uslot, int(j.how_out), int(gj.how_out)
             yield seq
         finally:

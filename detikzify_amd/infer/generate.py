@@ -144,8 +144,12 @@ class DetikzifyGenerator:
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None, dry_allowed_length: Optional[int] = None,
                  dry_sequence_breakers=None, min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None,
-                 logit_bias=None, sequence_bias=None, **gen_kwargs):
-        """presence_penalty / frequency_penalty (model.generate's; None / 0 = off): counted from the end of the image prompt on, so a
+                 logit_bias=None, sequence_bias=None, top_logprobs: Optional[int] = None, **gen_kwargs):
+        """top_logprobs=j (1 .. 8): every rollout of simulate() is generated with return_logprobs=True, top_logprobs=j, and every
+        document it yields carries `.token_logprobs` / `.token_sample_logprobs` / `.token_top_ids` / `.token_top_logprobs`, one entry
+        per token behind the prompt, as sample(return_logprobs=True, top_logprobs=j) attaches them.  Under a batch engine that needs an
+        engine built with top_logprobs >= j (simulate_parallel builds it).
+        presence_penalty / frequency_penalty (model.generate's; None / 0 = off): counted from the end of the image prompt on, so a
         rollout that continues a node of the tree penalises the whole program text so far, however its slot got there.
         min_new_tokens / exponential_decay_length_penalty (model.generate's) likewise count the program's tokens from the end of the
         image prompt (length_start); logit_bias / sequence_bias hold for every rollout"""
@@ -158,6 +162,15 @@ class DetikzifyGenerator:
             gen_kwargs = {**gen_kwargs, "min_new_tokens": min_new_tokens, "exponential_decay_length_penalty": exponential_decay_length_penalty}
         if logit_bias or sequence_bias:
             gen_kwargs = {**gen_kwargs, "logit_bias": logit_bias, "sequence_bias": sequence_bias}
+        from ..model.modeling import check_top_logprobs
+        self.top_logprobs = check_top_logprobs(top_logprobs)
+        # the records of every token a rollout of this search produced, as a trie over the token sequences behind the root: a rollout
+        # continues a node of an earlier one, so a document's records come from several calls.  (parent entry, token) -> entry;
+        # _records[entry] = (logprob, sample_logprob, top ids, top logprobs).  It grows by one entry per token a rollout produces and is
+        # never pruned: it lives as long as the search, like the tree itself (some hundred bytes per token)
+        self._record_at: Dict[Tuple[int, int], int] = {}
+        self._records: List[Tuple[float, float, List[int], List[float]]] = [(float("nan"), float("nan"), [], [])]      # entry 0: the root
+        self._records_lock = threading.Lock()
         self.model, self.processor = model, processor
         self.image, self.text, self.metric = image, text, metric
         self.compile_timeout, self.mcts_timeout = compile_timeout, mcts_timeout
@@ -297,6 +310,44 @@ class DetikzifyGenerator:
                 **conditioning, **options)
         return out if hasattr(out, "sequences") else out.squeeze()      # (return_logprobs=True: the GenerateOutput as it is)
 
+    def _generate_recorded(self, input_ids: torch.Tensor, **kw) -> torch.Tensor:
+        """generate() of a rollout under top_logprobs: the same tokens, and the new tokens' records filed under their sequence"""
+        out = self.generate(input_ids, return_logprobs=True, top_logprobs=self.top_logprobs, **kw)
+        if not hasattr(out, "sequences"):       # the prompt itself came back, without a model call
+            return out
+        seq = out.sequences.reshape(-1)
+        result = out.sequences.squeeze()      # what generate() returns for a plain call
+        n0, root = int(input_ids.numel()), int(self.montecarlo.root_node.token_ids.numel())
+        toks = [int(t) for t in seq[root:]]
+        with self._records_lock:
+            at = 0
+            for i, tok in enumerate(toks):
+                nxt = self._record_at.get((at, tok))
+                new = root + i - n0        # index among this call's new tokens (< 0: a token of the node the rollout continued)
+                if nxt is None:
+                    nxt = len(self._records)
+                    self._record_at[(at, tok)] = nxt
+                    self._records.append((float("nan"), float("nan"), [-1] * self.top_logprobs, [float("nan")] * self.top_logprobs))
+                if new >= 0:
+                    self._records[nxt] = (float(out.logprobs[0, new]), float(out.sample_logprobs[0, new]),
+                                          [int(v) for v in out.top_ids[0, new]], [float(v) for v in out.top_logprobs[0, new]])
+                at = nxt
+        return result
+
+    def _attach_records(self, document: TikzDocument, token_ids: torch.Tensor) -> None:
+        """top_logprobs: the four per-token lists of `document`, whose tokens are token_ids behind the root"""
+        root = int(self.montecarlo.root_node.token_ids.numel())
+        nan = (float("nan"), float("nan"), [-1] * self.top_logprobs, [float("nan")] * self.top_logprobs)
+        rows, at = [], 0
+        with self._records_lock:
+            for tok in token_ids.reshape(-1)[root:].tolist():
+                at = self._record_at.get((at, int(tok)), -1) if at >= 0 else -1
+                rows.append(self._records[at] if at >= 0 else nan)
+        document.token_logprobs = [r[0] for r in rows]
+        document.token_sample_logprobs = [r[1] for r in rows]
+        document.token_top_ids = [list(r[2]) for r in rows]
+        document.token_top_logprobs = [list(r[3]) for r in rows]
+
     # ---- a·R: a generation as a stream of tree positions -------------------------------------------------------------------
     def rollout(self, state: NodeState) -> Iterator[Tuple[torch.Tensor, int]]:
         """continue `state` to the end in a worker thread; yields (token prefix, #lines) after every completed source line
@@ -305,7 +356,7 @@ class DetikzifyGenerator:
         table = self.newlineinfo
         cutter = _LineCutter(state.token_ids, state.num_lines, table)
         tokens = TokenStreamer(flush_on=table)       # same tokens, handed over one source line at a time
-        worker = _BackgroundCall(self.generate, args=[state.token_ids], error_callback=tokens.propagate_error,
+        worker = _BackgroundCall(self._generate_recorded if self.top_logprobs else self.generate, args=[state.token_ids], error_callback=tokens.propagate_error,
                                  kwds=dict(stopping_criteria=[self.control.reset()], streamer=tokens))
         try:
             for token in tokens:
@@ -396,6 +447,8 @@ class DetikzifyGenerator:
             node, chain = self.merge(node.parent, chain)
 
         document = self.decode(chain[-1].token_ids if chain else node.token_ids)
+        if self.top_logprobs:
+            self._attach_records(document, chain[-1].token_ids if chain else node.token_ids)
         cap = round(sqrt(len(chain)))       # sqrt(n) of n new lines enter the tree
         rewardable = bool(document.is_rasterizable) and not (self.strict and document.compiled_with_errors)
 

@@ -126,7 +126,11 @@ class DetikzifyPipeline:
         batch on this GPU (infer/batching.py; the model must have been loaded with batch_slots > trees), each with its own
         `expansions` / `timeout` budget — root parallelisation; results arrive in completion order.  guidance_scale= (with
         negative_image= / negative_text=) works here too: every tree then decodes in two of the engine's slots (its own and the
-        negative branch's), so at most decode_slots // 2 trees decode at once and the rest take turns."""
+        negative branch's), so at most decode_slots // 2 trees decode at once and the rest take turns.
+
+        top_logprobs=j (1 .. 8, sequential or trees=N): every yielded document carries `.token_logprobs` / `.token_sample_logprobs` /
+        `.token_top_ids` / `.token_top_logprobs`, one entry per token behind the prompt, as sample(return_logprobs=True,
+        top_logprobs=j) attaches them; with trees > 1 the batch engine is built with top_logprobs=j."""
         if trees > 1:
             from .batching import simulate_parallel
             assert preprocess, "parallel trees take the default preprocessing"

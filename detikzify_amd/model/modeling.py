@@ -1204,6 +1204,13 @@ class DetikzifyForCausalLM:
             self.set_option("logprobs", 1)
             self._logprobs = True
 
+    def disable_logprobs(self) -> None:
+        """the steps stop delivering the pairs (refused where enable_logprobs() is, and while top_logprobs_enabled): what a batch engine
+        built with top_logprobs= does on close() for a model it found without them"""
+        if self.logprobs_enabled:
+            self.set_option("logprobs", 0)
+            self._logprobs = False
+
     @property
     def top_logprobs_enabled(self) -> int:
         return int(getattr(self, "_top_logprobs", 0))
@@ -1377,7 +1384,8 @@ class DetikzifyForCausalLM:
         return_logprobs=True (not an HF argument; HF's output_scores / compute_transition_scores stay refused) returns a
         GenerateOutput instead: the same tensor as `.sequences` plus the per-token `.logprobs` / `.sample_logprobs` the sampler
         kernel formed on its way (enable_logprobs(): switched on for this call if needed, and left on).  top_logprobs=k (1 .. 8,
-        with return_logprobs=True): + `.top_ids` / `.top_logprobs`, the k most likely tokens at every new position; not in the batch engines.  The option is on for this call only.
+        with return_logprobs=True): + `.top_ids` / `.top_logprobs`, the k most likely tokens at every new position; under a batch engine only
+        one built with top_logprobs >= k (NativeBatchEngine / make_engine(..., top_logprobs=)).  Without an engine the option is on for this call only.
 
         min_p / epsilon_cutoff: HF's MinPLogitsWarper / EpsilonLogitsWarper behind top-p (HF's order), as thresholds on the sampler's
         integer masses; 0 / None = off; ignored by greedy decoding like temperature, top-k and top-p.
@@ -1648,6 +1656,8 @@ class DetikzifyForCausalLM:
                 seq.run(emit)       # emit.many() per burst in this thread (native engine) / emit() per token by the driving thread
                 if return_logprobs:
                     pairs = (seq.logprobs, seq.sample_logprobs)
+                if topk:
+                    tops = (seq.top_ids, seq.top_logprobs)
         elif n_new_max > 0:
             # the context has ONE un-slotted sequence: a second generate() on it from another thread would interleave its
             # prefill / decode steps with ours and both would return garbage — refuse loudly (the reference never does

@@ -798,8 +798,33 @@ int  dtk_op_sample_lp(dtk_ctx* ctx, const float* logits, int V, int step, int64_
  *   dtk_decode_wait_top       dtk_decode_wait_lp + top_ids_out / top_logprob_out [DTK_MAX_TOP]: entries >= k are (-1, NaN); a forced
  *                             token has (-1, NaN) throughout
  *   dtk_decode_batch_wait_top dtk_decode_batch_wait_lp + [DTK_MAX_BATCH][DTK_MAX_TOP] of the same; (-1, NaN) for slots that took no part
- * The engines of dtk_engine_create* do not deliver them (dtk_engine_read's record is unchanged). */
+ *   dtk_set_option(ctx, "top_kernel", v)     which kernel selects a step's records: 1 = k_top_logits, one block per sequence that walks
+ *                             the row k times; 2 = k_top_slice + k_top_merge, the row cut into slices of "top_slice" logits that are
+ *                             loaded once into registers, the slices' k first entries merged by a second launch; 0 (default) = 2 where the
+ *                             row has more than one slice (V > 8192; measured faster at V = 32 256 and 128 256), else 1.  The order is total, so the records are
+ *                             the same bits either way.  "top_slice" (default 8192 = the most; at most 32 slices of the vocabulary) is
+ *                             there for tests.  Both are refused in the states that refuse "top_logprobs" and drop the captured graphs.
+ *   dtk_op_top_logits         the selection alone on host rows [rows][V] (rows <= DTK_MAX_BATCH, V <= 262 144, k <= min(V, DTK_MAX_TOP)),
+ *                             through the shipped launcher: kernel 1 or 2, L = the slice of kernel 2.  active / forced [rows] or NULL
+ *                             (all active / none forced): an inactive row's outputs are not written, a forced row gets (-1, NaN) in
+ *                             its first k entries.  ids_out / z_out [rows][DTK_MAX_TOP] are in/out: entries >= k keep the caller's bytes.
+ * The engines deliver them too (dtk_engine_read's and dtk_engine_read_lp's records are unchanged):
+ *   dtk_engine_read_top       dtk_engine_read_lp + top_ids_out / top_logprob_out [cap][DTK_MAX_TOP]; the i-th record belongs to the i-th
+ *                             token returned.  A record is (-1, NaN) beyond k, for a forced token and for tokens produced before
+ *                             collection began.  Of a guided sequence the records are its conditional slot's, i.e. of the guided
+ *                             distribution (the selection runs behind the mix).  The engine of dtk_engine_create collects through
+ *                             dtk_decode_batch_wait_top while its context's "top_logprobs" is > 0 (switch it before the first join); an
+ *                             engine of dtk_engine_create_ops through the op given to dtk_engine_set_wait_top_op (the contract of
+ *                             dtk_decode_batch_wait_top; it then replaces ops.wait and the wait_lp op).  DTK_ERR_ARG while the engine
+ *                             collects none. */
 #define DTK_MAX_TOP 8
+int  dtk_op_top_logits(dtk_ctx* ctx, const float* logits /* [rows][V] */, int rows, int V, int k, int kernel, int L, const int32_t* active,
+                       const int32_t* forced, int32_t* ids_out /* [rows][DTK_MAX_TOP] */, float* z_out /* [rows][DTK_MAX_TOP] */);
+int  dtk_engine_read_top(dtk_engine* e, int slot, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out,
+                         int32_t* top_ids_out /* [cap][DTK_MAX_TOP] */, float* top_logprob_out /* [cap][DTK_MAX_TOP] */, int cap,
+                         int32_t* n_out, int32_t* state_out, int timeout_ms);
+int  dtk_engine_set_wait_top_op(dtk_engine* e, int (*wait_top)(void* dev, int64_t* tokens_out, float* logprob_out, float* sample_logprob_out,
+                                                               int32_t* top_ids_out, float* top_logprob_out));
 int  dtk_score_top(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, uint32_t flags, int first,
                    float* logprob_out, int32_t* argmax_out, float* lse_out, int k, int32_t* top_ids_out, float* top_logprob_out);
 int  dtk_score_top_text(dtk_ctx* ctx, const int64_t* ids, int T, const float* pixels, uint64_t image_key, const int64_t* text_ids, int T_text,
