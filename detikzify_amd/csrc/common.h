@@ -342,6 +342,12 @@ __device__ __forceinline__ void bin_select_mass(const unsigned long long* s_m, c
   __syncthreads();
 }
 
+// order-preserving float -> uint key of the samplers' radix descents (a > b as floats <=> fkey(a) > fkey(b) as unsigned)
+__device__ __forceinline__ uint32_t fkey(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 // splitmix64: the counter-based RNG shared with oracle/sampling.py
 __host__ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;

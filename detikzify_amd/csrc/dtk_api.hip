@@ -638,17 +638,33 @@ static void follow_launch(dtk_ctx* c, const SampleArgs& sa) {
   launch_cfg_follow(f, c->stream);
 }
 
+// what a decode step hands its sampler: the single sequence's buffers, or (batch) slot 0's of the batched step over every slot column of
+// this step's tiles.  The penalties' tables are bound behind it (pen_args, in sampler_launch)
+static SampleArgs step_sample_args(const dtk_ctx* c, bool batch) {
+  SampleArgs sa;
+  sa.logits = batch ? c->logits_b : c->logits; sa.V = c->V; sa.sp = batch ? c->sp_b : c->sp; sa.st = batch ? c->st_b : c->st; sa.embed = c->embed;
+  sa.x = batch ? c->xb : c->x; sa.d = c->d; sa.tok_ring = batch ? c->tokb_dev : c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
+  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1;
+  sa.bs = batch ? c->bs_dev : nullptr; sa.logits_stride = batch ? c->V : 0; sa.nslots = batch ? 16 * c->nt_step : 1; sa.mb = batch ? c->smb_b : c->smb;
+  sa.lp_ring = !c->logprobs ? nullptr : batch ? c->lpb_dev : c->lp_ring_dev;
+  sa.trunc = (batch ? c->trunc_batch : c->trunc_single) ? 1 : 0;
+  sa.lse_ring = !(c->logprobs && c->top_logprobs) ? nullptr : batch ? c->lseb_dev : c->lse_ring_dev;
+  return sa;
+}
+// the sampling part of a batched step: the guided pairs' mix in front of everything that reads the logits, the top-k records, the sampler,
+// the pairs' follower slots behind it (the first and the last: nothing without a guided pair)
+static void step_sampler_chain(dtk_ctx* c, SampleArgs& sa, bool mb) {
+  guidance_launch(c, sa);
+  top_logits_launch(c, sa);
+  sampler_launch(c, sa, mb, true);
+  follow_launch(c, sa);
+}
+
 static inline bool w13_on(const dtk_ctx* c) { return c->wfmt == 0 && c->w13 != 0; }   // the single-sequence step streams 13-bit planes (ensure_w13)
 
 void decode_step_launches(dtk_ctx* c, bool with_probe, bool short_ctx = false) {
   hipStream_t s = c->stream;
-  SampleArgs sa;
-  sa.logits = c->logits; sa.V = c->V; sa.sp = c->sp; sa.st = c->st; sa.embed = c->embed;
-  sa.x = c->x; sa.d = c->d; sa.tok_ring = c->tok_ring_dev; sa.ring = DTK_MAX_INFLIGHT;
-  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = nullptr; sa.logits_stride = 0; sa.nslots = 1; sa.mb = c->smb;
-  sa.lp_ring = c->logprobs ? c->lp_ring_dev : nullptr;
-  sa.trunc = c->trunc_single ? 1 : 0;
-  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lse_ring_dev : nullptr;
+  SampleArgs sa = step_sample_args(c, false);
   top_logits_launch(c, sa);
   sampler_launch(c, sa, c->mb_single, false);
   const float scale = 1.0f / sqrtf((float)c->hd);
@@ -718,17 +734,8 @@ static inline void kv8_args(const dtk_ctx* c, int l, AttnDecBArgs& ad) {
 void batch_step_launches_mx(dtk_ctx* c) {
   hipStream_t s = c->stream;
   const int d = c->d, ff = c->ff, nslots = 16 * c->nt_step;
-  SampleArgs sa;
-  sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
-  sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
-  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = nslots; sa.mb = c->smb_b;
-  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
-  sa.trunc = c->trunc_batch ? 1 : 0;
-  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
-  guidance_launch(c, sa);            // (nothing without a guided pair)
-  top_logits_launch(c, sa);
-  sampler_launch(c, sa, c->mb_batch, true);
-  follow_launch(c, sa);              // (likewise)
+  SampleArgs sa = step_sample_args(c, true);
+  step_sampler_chain(c, sa, c->mb_batch);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   for (int l = 0; l < c->L; ++l) {
@@ -770,17 +777,8 @@ void batch_step_launches(dtk_ctx* c) {
   if (mx_step(c)) { batch_step_launches_mx(c); return; }
   hipStream_t s = c->stream;
   const int d = c->d, ff = c->ff;
-  SampleArgs sa;
-  sa.logits = c->logits_b; sa.V = c->V; sa.sp = c->sp_b; sa.st = c->st_b; sa.embed = c->embed;
-  sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
-  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = c->bs_dev; sa.logits_stride = c->V; sa.nslots = 16 * c->nt_step; sa.mb = c->smb_b;
-  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
-  sa.trunc = c->trunc_batch ? 1 : 0;
-  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
-  guidance_launch(c, sa);            // (nothing without a guided pair)
-  top_logits_launch(c, sa);
-  sampler_launch(c, sa, c->mb_batch, true);
-  follow_launch(c, sa);              // (likewise)
+  SampleArgs sa = step_sample_args(c, true);
+  step_sampler_chain(c, sa, c->mb_batch);
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
   bool kparts = false;
@@ -854,13 +852,8 @@ void batch_step_launches_mv(dtk_ctx* c) {
   DecState* const st = spec ? c->spec_st : c->st_b;
   const BatchState* const bs = spec ? c->spec_bs : c->bs_dev;
   const size_t kv_stride = spec ? 0 : c->kv_slot_stride;
-  SampleArgs sa;
-  sa.logits = c->logits_b; sa.V = c->V; sa.sp = spec ? c->spec_sp : c->sp_b; sa.st = st; sa.embed = c->embed;
-  sa.x = c->xb; sa.d = d; sa.tok_ring = c->tokb_dev; sa.ring = DTK_MAX_INFLIGHT;
-  sa.probs_out = nullptr; sa.advance = 1; sa.step_override = -1; sa.bs = bs; sa.logits_stride = c->V; sa.nslots = NB; sa.mb = c->smb_b;
-  sa.lp_ring = c->logprobs ? c->lpb_dev : nullptr;
-  sa.trunc = c->trunc_batch ? 1 : 0;
-  sa.lse_ring = (c->logprobs && c->top_logprobs) ? c->lseb_dev : nullptr;
+  SampleArgs sa = step_sample_args(c, true);
+  sa.sp = spec ? c->spec_sp : c->sp_b; sa.st = st; sa.bs = bs; sa.nslots = NB;
   if (spec) {
     // the batched sampler over the pending rows of the vectors that were live in the previous step (dtk_spec_begin refuses a context
     // with penalties, DRY, length rules, a bias, top_logprobs or a guided pair: the plain step's launch is this one), then the two
@@ -874,10 +867,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
     launch_spec_accept(sv, s);
     launch_spec_draft(sv, s);
   } else {
-    guidance_launch(c, sa);            // (nothing without a guided pair)
-    top_logits_launch(c, sa);
-    sampler_launch(c, sa, c->mb_batch, true);
-    follow_launch(c, sa);              // (likewise)
+    step_sampler_chain(c, sa, c->mb_batch);
   }
   const float scale = 1.0f / sqrtf(128.f);
   const size_t kv_layer = (size_t)2 * c->KVH * c->Tmax * 128;
@@ -3827,22 +3817,14 @@ int dtk_set_option(dtk_ctx* c, const char* name, int value) {
       if (value < 0 || value > 2) return fail(c, DTK_ERR_ARG, "attn_combine must be 0..2");
       c->attn_combine = value;
     }
-    if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-    if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
-    if (c->graph_short_exec) { (void)hipGraphExecDestroy(c->graph_short_exec); c->graph_short_exec = nullptr; }
-    if (c->graph_short) { (void)hipGraphDestroy(c->graph_short); c->graph_short = nullptr; }
-    c->graph_ready = false;
+    drop_graph(c);
   } else return fail(c, DTK_ERR_ARG, "unknown option '%s'", name);
   return DTK_OK;
 }
 
 int dtk_set_gemv_variant(dtk_ctx* c, int epi, int variant) {
   if (!c) return DTK_ERR_ARG;
-  if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
-  if (c->graph) { (void)hipGraphDestroy(c->graph); c->graph = nullptr; }
-  if (c->graph_short_exec) { (void)hipGraphExecDestroy(c->graph_short_exec); c->graph_short_exec = nullptr; }
-  if (c->graph_short) { (void)hipGraphDestroy(c->graph_short); c->graph_short = nullptr; }
-  c->graph_ready = false;
+  drop_graph(c);
   set_gemv_default_variant(epi, variant);
   return DTK_OK;
 }

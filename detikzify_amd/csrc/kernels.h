@@ -3,6 +3,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 // ---------------------------------------------------------------- decode-step GEMV family
 enum { PRO_COPY = 0, PRO_RMSNORM = 1, PRO_ATTN = 2 };
@@ -117,6 +118,14 @@ struct SampleArgs {
   int bias_stride = 0;                 // elements between two sequences' tables (a multiple of 8: every table is 16-byte aligned)
   int len_cur = -1;                    // >= 0: the sequence's length in place of DecState::next_pos (tests)
 };
+// the samplers' launchers: which (LP, TR) instantiation a launch runs, handed to f as two compile-time booleans.  a.lp_ring == nullptr: the
+// LP = false kernels; a.trunc == 0 (no sequence of this launch has min_p / epsilon_cutoff): the TR = false ones, the kernels as they were
+template <class F>
+static inline void dispatch_lp_tr(const SampleArgs& a, F f) {
+  if (a.lp_ring) { if (a.trunc) f(std::true_type{}, std::true_type{}); else f(std::true_type{}, std::false_type{}); }
+  else if (a.trunc) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
 // dtk_set_logit_bias: one block writes val[i] (or, val null, 0) to tab[ids[i]] for i < n <= DTK_BIAS_MAX; ids outside [0, V) are skipped.
 // ids and val are HOST arrays: the pairs go to the kernel as its arguments
 void launch_bias_scatter(const int32_t* ids, const float* val, int n, float* tab, int V, hipStream_t s);

@@ -21,6 +21,7 @@
 #include <cstring>
 #include "kernels.h"
 #include "gemv_inl.h"
+#include "sample_inl.h"
 
 // Epilogue of one output unit (one lane per wave): `a0` is the fp32 dot product of the unit's row (paired epilogues:
 // a0 / a1 = the two rows of the pair: RoPE partners i, i + HD/2 or gate, up).  HD = head dim (EPI_QKV): 128, or 64 (TinyLlama).  Same HF rounding points as the reference.
@@ -1309,11 +1310,6 @@ void launch_attn_decode(const AttnDecArgs& a, hipStream_t s) {
 // into the residual stream (first op of the next forward).
 #define SAMPLE_THREADS 1024
 
-__device__ __forceinline__ uint32_t fkey(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 __device__ __forceinline__ bool is_banned(const SamplingDev* sp, int i, bool first) {
   for (int k = 0; k < sp->n_bad; ++k)
     if (sp->bad_ids[k] == i) return true;
@@ -1332,68 +1328,16 @@ __device__ __forceinline__ bool is_banned(const SamplingDev* sp, int i, bool fir
 // min-p keeps q >= SamplingDev::qmin; epsilon keeps q >= (int64)((double)eps * (double)total_m), total_m the mass kept so far (one more
 // block reduction).  Both fold into one mass floor; a floor above 2^31 (epsilon left nothing) keeps the first arg-max alone.
 // TR = false is the kernel as it was before the two values existed.
-// PN (SampleArgs::pen, dtk_set_penalties): the presence / frequency penalty.  Every load of a logit is followed by pen_apply with the
-// id's count (after the raw value has gone to the log-sum-exp, before the temperature and the suppression lists), so every pass sees the
-// same z'; a sequence whose two values are 0 reads no count (block-uniform).  The sampled token goes to pen_tok for k_count_token, which
-// runs behind this kernel: no block reads the table after its increment.  PN = false is the kernel as it was before the penalties existed.
-__device__ __forceinline__ unsigned pen_cnt4(uint2 cw, int e) { return ((e < 2 ? cw.x : cw.y) >> ((e & 1) * 16)) & 0xffffu; }
-__device__ __forceinline__ void pen_f32x4(f32x4& v, uint2 cw, float pp, float fp) {
-  if ((cw.x | cw.y) == 0u) return;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = pen_apply(v[e], pen_cnt4(cw, e), pp, fp);
-}
-// DRY (SampleArgs::dry, dtk_set_dry) rides PN: behind pen_apply, a second fp32 subtraction of the table's pen[M] where the id's match
-// length M (one byte beside every logit, left by k_dry_scan in front of this kernel) is not 0; a sequence without a multiplier reads no
-// byte (block-uniform), a launch without DRY (a.dry null) likewise.  The trailing kernel appends pen_tok to the history.
-__device__ __forceinline__ void dry_f32x4(f32x4& v, uint32_t mw, const float* pen) {
-  if (mw == 0u) return;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = dry_apply(v[e], (mw >> (8 * e)) & 0xffu, pen);
-}
-// Length control and logit bias (SampleArgs::len, dtk_set_length_control / dtk_set_logit_bias) ride PN: the bias is added to the raw logit
-// in front of pen_apply (one float beside every logit, read only where the sequence has a bias), the EOS rules (at most 8 ids, and only at
-// a length where one applies) come behind dry_apply; sh is bound once per block from the sequence's record and its length
-__device__ __forceinline__ void bias_f32x4(f32x4& v, const f32x4 b) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = bias_apply(v[e], b[e]);
-}
-__device__ __forceinline__ void eos_f32x4(f32x4& v, int i, const ShapeRt& sh) {
-  for (int j = 0; j < sh.ne; ++j) {
-    const int o = sh.eos[j] - i;
-    if (o < 0 || o >= 4) continue;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) if (e == o) v[e] = eos_apply(v[e], i + e, sh);
-  }
-}
-__device__ __forceinline__ ShapeRt shape_of(const SampleArgs& a) {
-  return shape_bind(a.len, a.len_m, a.bias, a.len_cur >= 0 ? a.len_cur : a.st->next_pos);
-}
-__device__ __forceinline__ float pen_dry1(const SampleArgs& a, int i, bool pn, float pp, float fp, bool dr, const float* dpen, const ShapeRt& sh) {
-  float z = a.logits[i];
-  if (sh.bias) z = bias_apply(z, sh.bias[i]);
-  if (pn) z = pen_apply(z, a.pen_cnt[i], pp, fp);
-  if (dr) z = dry_apply(z, a.dry_m[i], dpen);
-  if (sh.ne) z = eos_apply(z, i, sh);
-  return z;
-}
+// PN (SampleArgs::pen, dtk_set_penalties): the logit transform of sample_inl.h's LogitXf.  Every load of a logit goes through it (after
+// the raw value has gone to the log-sum-exp, before the temperature and the suppression lists), so every pass sees the same z':
+// the logit bias (dtk_set_logit_bias), the presence / frequency penalty with the id's count, the DRY penalty with the id's match length
+// (dtk_set_dry; k_dry_scan leaves the lengths in front of this kernel) and the EOS rules of the sequence's length
+// (dtk_set_length_control), each behind a block-uniform test: a sequence without the value reads nothing of its table.  The sampled token
+// goes to pen_tok (sample_commit) for k_count_token, which runs behind this kernel: no block reads the tables after its update.
+// PN = false is the kernel as it was before the penalties existed.
 template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
-  if (a.bs) {  // batched decode: one block per slot, same code on that slot's buffers
-    const int slot = blockIdx.x;
-    if (!a.bs->active[slot]) return;
-    a.logits += (size_t)slot * a.logits_stride;
-    a.sp += slot;
-    a.st += slot;
-    a.x += (size_t)slot * a.d;
-    a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
-    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
-    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
-    a.ring = 1;        // the ring index was applied above
-    a.step_override = -1;
-  }
+  if (!sample_bind_slot<PN>(a, blockIdx.x)) return;      // batched decode: one block per slot, same code on that slot's buffers
   __shared__ float s_f[16];
   __shared__ int s_i[16];
   __shared__ unsigned long long s_q[16];
@@ -1422,15 +1366,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   const bool first = (draw == 0);
   const bool sampling = sp->do_sample != 0;
   const float invT = sampling ? 1.f / sp->temperature : 1.f;
-  float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
-  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
-  (void)pn_p; (void)pn_f; (void)pn;
-  const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
-  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
-  (void)dpen; (void)dr;
-  ShapeRt sh;                                         // PN with SampleArgs::len: the sequence's bias table and the EOS rule of this length (block-uniform)
-  if constexpr (PN) if (a.len) sh = shape_of(a);
-  (void)sh;
+  LogitXf xf;                                         // PN: the sequence's transform (block-uniform)
+  xf.bind<PN>(a, sample_cur<PN>(a));
 
   // ---- pass 1: masked (scaled) max and first argmax.  16-byte loads, four per thread in flight
   // (the greedy path is one memory round trip + the block reduction)
@@ -1448,47 +1385,19 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
         const int i4 = base + u * SAMPLE_THREADS;
         v[u] = (i4 < V4) ? l4[i4] : (f32x4){-INFINITY, -INFINITY, -INFINITY, -INFINITY};
       }
-      uint2 cw[4];       // PN: the four counts beside every 16-byte load
-      if constexpr (PN) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i4 = base + u * SAMPLE_THREADS;
-          cw[u] = (pn && i4 < V4) ? reinterpret_cast<const uint2*>(a.pen_cnt)[i4] : make_uint2(0u, 0u);
-        }
-      }
-      (void)cw;
-      uint32_t dw[4];    // PN, DRY: the four match lengths likewise
-      if constexpr (PN) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i4 = base + u * SAMPLE_THREADS;
-          dw[u] = (dr && i4 < V4) ? reinterpret_cast<const uint32_t*>(a.dry_m)[i4] : 0u;
-        }
-      }
-      (void)dw;
-      f32x4 bw[4];       // PN, bias: the four biases likewise
-      if constexpr (PN) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int i4 = base + u * SAMPLE_THREADS;
-          bw[u] = (sh.bias && i4 < V4) ? reinterpret_cast<const f32x4*>(sh.bias)[i4] : (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-      }
-      (void)bw;
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int i4 = base + u * SAMPLE_THREADS;
         if (i4 >= V4) continue;
+        if constexpr (LP) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) lse_push(lm, ls, v[u][e]);
+        }
+        if constexpr (PN) xf.vec<4>(a, i4 * 4, v[u]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int i = i4 * 4 + e;
-          if constexpr (LP) lse_push(lm, ls, v[u][e]);
-          float z;
-          if constexpr (PN) {
-            z = dry_apply(pen_apply(bias_apply(v[u][e], bw[u][e]), pen_cnt4(cw[u], e), pn_p, pn_f), (dw[u] >> (8 * e)) & 0xffu, dpen);
-            if (sh.ne) z = eos_apply(z, i, sh);
-            z *= invT;
-          } else z = v[u][e] * invT;
+          float z = v[u][e] * invT;
           if (is_banned(sp, i, first)) z = -INFINITY;
           if (z > best || (z == best && i < besti)) { best = z; besti = i; }
         }
@@ -1496,28 +1405,18 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     }
   } else {
     for (int i = tid; i < V; i += SAMPLE_THREADS) {
-      if constexpr (LP) lse_push(lm, ls, a.logits[i]);
-      float z;
-      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen, sh) * invT;
-      else z = a.logits[i] * invT;
+      float z = a.logits[i];
+      if constexpr (LP) lse_push(lm, ls, z);
+      if constexpr (PN) z = xf.one(a, i, z);
+      z *= invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       if (z > best || (z == best && i < besti)) { best = z; besti = i; }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ob = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(besti, off, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
   if constexpr (LP) { lse_wave(lm, ls); if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; } }
-  if (lane == 0) { s_f[wave] = best; s_i[wave] = besti; }
-  __syncthreads();
+  block_argmax_first<SAMPLE_THREADS>(best, besti, s_f, s_i);
   if (tid == 0) {
-    float b = s_f[0]; int bi = s_i[0];
-    for (int w = 1; w < 16; ++w)
-      if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
-    s_max = b; s_token = bi;
+    s_max = best; s_token = besti;
     if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
       for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
     }
@@ -1531,8 +1430,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
   if (sampling) {
     // fixed-point mass q_i = floor(exp(z_i - zmax) * 2^31)  (fits 32 bits; exact integer sums)
     auto mass = [&](int i, float& z) -> unsigned long long {
-      if constexpr (PN) z = pen_dry1(a, i, pn, pn_p, pn_f, dr, dpen, sh) * invT;
-      else z = a.logits[i] * invT;
+      z = a.logits[i];
+      if constexpr (PN) z = xf.one(a, i, z);
+      z *= invT;
       if (is_banned(sp, i, first)) z = -INFINITY;
       const float e = expf(z - zmax);
       return (unsigned long long)((double)e * 2147483648.0);
@@ -1576,11 +1476,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       float z; const unsigned long long q = mass(i, z);
       if (fkey(z) >= thr_k) loc += q;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) loc += __shfl_xor(loc, off, 64);
-    if (lane == 0) s_q[wave] = loc;
-    __syncthreads();
-    if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
+    loc = block_sum_u64<SAMPLE_THREADS>(loc, s_q);
+    if (tid == 0) s_total = loc;
     __syncthreads();
     const unsigned long long total_k = s_total;
 
@@ -1623,29 +1520,22 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     // ---- TR: the mass floor of min-p and epsilon
     uint32_t qfl = 0; bool fb = false;
     if constexpr (TR) {
-      unsigned long long fl = (unsigned long long)sp->qmin;
+      unsigned long long total_m = 0;      // the mass kept behind top-p and min-p: read by epsilon alone
       if (sp->eps > 0.f) {      // block-uniform
+        const unsigned long long fl = (unsigned long long)sp->qmin;
         unsigned long long pre = 0;
         for (int i = tid; i < V; i += SAMPLE_THREADS) {
           float z; const unsigned long long q = mass(i, z);
           if (fkey(z) >= thr && q >= fl) pre += q;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
-        if (lane == 0) s_q[wave] = pre;
+        pre = block_sum_u64<SAMPLE_THREADS>(pre, s_q);
+        if (tid == 0) s_total = pre;
         __syncthreads();
-        if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
-        __syncthreads();
-        const unsigned long long qe = (unsigned long long)((double)sp->eps * (double)s_total);
-        if (qe > fl) fl = qe;
+        total_m = s_total;
       }
-      fb = fl > 2147483648ull;
-      qfl = fb ? 0u : (uint32_t)fl;
+      trunc_floor(sp->qmin, sp->eps, total_m, qfl, fb);
     }
-    auto kept_el = [&](int i, float z, unsigned long long q) -> bool {
-      if constexpr (TR) return fb ? (i == amax) : (fkey(z) >= thr && q >= qfl);
-      else return fkey(z) >= thr;
-    };
+    auto kept_el = [&](int i, float z, unsigned long long q) -> bool { return sample_kept<TR>(fkey(z), (uint32_t)q, i, thr, qfl, fb, amax); };
     // ---- kept mass + inverse-CDF draw in index order
     const int per = (V + SAMPLE_THREADS - 1) / SAMPLE_THREADS;
     const int i0 = tid * per, i1 = min(V, i0 + per);
@@ -1654,18 +1544,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
       float z; const unsigned long long q = mass(i, z);
       if (kept_el(i, z, q)) mine += q;
     }
-    scan[tid] = mine;
-    __syncthreads();
-    for (int off = 1; off < SAMPLE_THREADS; off <<= 1) {
-      unsigned long long v = 0;
-      if (tid >= off) v = scan[tid - off];
-      __syncthreads();
-      scan[tid] += v;
-      __syncthreads();
-    }
+    block_scan_u64<SAMPLE_THREADS>(scan, mine);
     const unsigned long long kept = scan[SAMPLE_THREADS - 1];
-    const uint64_t r = splitmix64(sp->seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(draw + 1))) >> 32;
-    const unsigned long long target = __umul64hi(kept, r << 32);  // floor(kept * r / 2^32)
+    const unsigned long long target = draw_target(sp->seed, draw, kept);
     const unsigned long long excl = scan[tid] - mine;
     if (mine > 0 && target >= excl && target < excl + mine) {
       unsigned long long run = excl;
@@ -1689,30 +1570,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
     for (int i = tid; i < V; i += SAMPLE_THREADS) a.probs_out[i] = (i == s_token) ? 1.f : 0.f;
   }
 
-  // a resumed slot (dtk_resume_slot) forwards the last token of its prompt instead of a sampled one: the draw counter (and
-  // with it the begin-suppress rule of the first SAMPLED token) does not move
-  const int tok = forced > 0 ? forced - 1 : s_token;
-  if (tid == 0) {
-    a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
-    if constexpr (LP)      // a forced token was not sampled: NaN, NaN
-      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
-                                                                   : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
-    if constexpr (LP) if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? __builtin_nanf("") : lm + logf(ls);
-    if (a.advance) {
-      a.st->token = tok;
-      a.st->pos = a.st->next_pos;
-      a.st->next_pos = a.st->next_pos + 1;
-      a.st->draw = forced > 0 ? draw : draw + 1;
-      if (forced > 0) a.st->force_plus1 = 0;
-      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
-    }
-  }
-  if (a.advance) {
-    // embedding gather: first op of the forward that follows
-    const u32x4* src = reinterpret_cast<const u32x4*>(a.embed + (size_t)tok * a.d);
-    u32x4* dst = reinterpret_cast<u32x4*>(a.x);
-    for (int c = tid; c < (a.d >> 3); c += SAMPLE_THREADS) dst[c] = src[c];
-  }
+  float2 lp = make_float2(0.f, 0.f); float lse = 0.f;      // LP, thread 0: against the block's log-sum-exp state of the raw row
+  if constexpr (LP) if (tid == 0 && forced <= 0) { lp = lp_pair(a.logits[s_token], lm, ls, sampling, lp_q, lp_total); lse = lm + logf(ls); }
+  sample_commit<LP, PN, SAMPLE_THREADS>(a, s_token, forced, draw, lp, lse);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1729,22 +1589,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample(SampleArgs a) {
 #define SF_PER 32
 template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
-  if (a.bs) {
-    const int slot = blockIdx.x;
-    if (!a.bs->active[slot]) return;
-    a.logits += (size_t)slot * a.logits_stride;
-    a.sp += slot;
-    a.st += slot;
-    a.x += (size_t)slot * a.d;
-    a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (LP) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (LP) if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
-    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
-    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
-    a.ring = 1;
-    a.step_override = -1;
-  }
+  if (!sample_bind_slot<PN>(a, blockIdx.x)) return;
   __shared__ SamplingDev s_sp;
   __shared__ float s_f[16];
   __shared__ int s_i[16];
@@ -1771,15 +1616,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
   const bool first = (draw == 0);
   const bool sampling = sp->do_sample != 0;
   const float invT = sampling ? 1.f / sp->temperature : 1.f;
-  float pn_p = 0.f, pn_f = 0.f; bool pn = false;      // PN: the sequence's values; pn = it has some (block-uniform)
-  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
-  (void)pn_p; (void)pn_f; (void)pn;
-  const float* dpen = nullptr; bool dr = false;       // PN with SampleArgs::dry: the sequence's DRY table; dr = it has a multiplier (block-uniform)
-  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
-  (void)dpen; (void)dr;
-  ShapeRt sh;                                         // PN with SampleArgs::len: the sequence's bias table and the EOS rule of this length (block-uniform)
-  if constexpr (PN) if (a.len) sh = shape_of(a);
-  (void)sh;
+  LogitXf xf;                                         // PN: the sequence's transform (block-uniform)
+  xf.bind<PN>(a, sample_cur<PN>(a));
   const int i0 = tid * SF_PER;
 
   // ---- the one pass over the logits
@@ -1795,10 +1633,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
         const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
         if (m4 > lm) { ls *= expf(lm - m4); lm = m4; }
         ls += (expf(v[0] - lm) + expf(v[1] - lm)) + (expf(v[2] - lm) + expf(v[3] - lm));
-        if constexpr (PN) if (sh.bias) bias_f32x4(v, reinterpret_cast<const f32x4*>(sh.bias + i0)[k]);
-        if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
-        if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
-        if constexpr (PN) if (sh.ne) eos_f32x4(v, i0 + 4 * k, sh);
+        if constexpr (PN) xf.vec<4>(a, i0 + 4 * k, v);
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
       }
@@ -1807,10 +1642,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
       for (int k = 0; k < SF_PER; ++k) {
         float v = (i0 + k < V) ? a.logits[i0 + k] : -INFINITY;
         lse_push(lm, ls, v);
-        if constexpr (PN) if (sh.bias && i0 + k < V) v = bias_apply(v, sh.bias[i0 + k]);
-        if constexpr (PN) if (pn && i0 + k < V) v = pen_apply(v, a.pen_cnt[i0 + k], pn_p, pn_f);
-        if constexpr (PN) if (dr && i0 + k < V) v = dry_apply(v, a.dry_m[i0 + k], dpen);
-        if constexpr (PN) if (sh.ne && i0 + k < V) v = eos_apply(v, i0 + k, sh);
+        if constexpr (PN) if (i0 + k < V) v = xf.one(a, i0 + k, v);
         z[k] = v * invT;
       }
     }
@@ -1819,17 +1651,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 #pragma unroll
     for (int k = 0; k < SF_PER / 4; ++k) {
       f32x4 v = l4[k];
-      if constexpr (PN) if (sh.bias) bias_f32x4(v, reinterpret_cast<const f32x4*>(sh.bias + i0)[k]);
-      if constexpr (PN) if (pn) pen_f32x4(v, reinterpret_cast<const uint2*>(a.pen_cnt + i0)[k], pn_p, pn_f);
-      if constexpr (PN) if (dr) dry_f32x4(v, reinterpret_cast<const uint32_t*>(a.dry_m + i0)[k], dpen);
-      if constexpr (PN) if (sh.ne) eos_f32x4(v, i0 + 4 * k, sh);
+      if constexpr (PN) xf.vec<4>(a, i0 + 4 * k, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[4 * k + e] = v[e] * invT;
     }
   } else if constexpr (PN) {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k)
-      z[k] = (i0 + k < V) ? pen_dry1(a, i0 + k, pn, pn_p, pn_f, dr, dpen, sh) * invT : -INFINITY;
+      z[k] = (i0 + k < V) ? xf.one(a, i0 + k, a.logits[i0 + k]) * invT : -INFINITY;
   } else {
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) z[k] = (i0 + k < V) ? a.logits[i0 + k] * invT : -INFINITY;
@@ -1851,20 +1680,10 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 #pragma unroll
   for (int k = 0; k < SF_PER; ++k)
     if (i0 + k < V && (z[k] > best || (z[k] == best && i0 + k < besti))) { best = z[k]; besti = i0 + k; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ob = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(besti, off, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
   if constexpr (LP) { lse_wave(lm, ls); if (lane == 0) { s_lm[wave] = lm; s_ls[wave] = ls; } }
-  if (lane == 0) { s_f[wave] = best; s_i[wave] = besti; }
-  __syncthreads();
+  block_argmax_first<SAMPLE_THREADS>(best, besti, s_f, s_i);
   if (tid == 0) {
-    float b = s_f[0]; int bi = s_i[0];
-    for (int w = 1; w < 16; ++w)
-      if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
-    s_max = b; s_token = bi;
+    s_max = best; s_token = besti;
     if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
       for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
     }
@@ -1929,11 +1748,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     unsigned long long loc = 0;
 #pragma unroll
     for (int k = 0; k < SF_PER; ++k) if (i0 + k < V && key(k) >= thr_k) loc += q_(k);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) loc += __shfl_xor(loc, off, 64);
-    if (lane == 0) s_q[wave] = loc;
-    __syncthreads();
-    if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
+    loc = block_sum_u64<SAMPLE_THREADS>(loc, s_q);
+    if (tid == 0) s_total = loc;
     __syncthreads();
     const unsigned long long total_k = s_total;
 
@@ -1971,29 +1787,26 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     // TR: the mass floor of min-p and epsilon
     uint32_t qfl = 0; bool fb = false;
     if constexpr (TR) {
-      unsigned long long fl = (unsigned long long)sp->qmin;
+      unsigned long long total_m = 0;      // the mass kept behind top-p and min-p: read by epsilon alone
       if (sp->eps > 0.f) {      // block-uniform
+        const unsigned long long fl = (unsigned long long)sp->qmin;
         unsigned long long pre = 0;
 #pragma unroll
         for (int k = 0; k < SF_PER; ++k)
           if (i0 + k < V && key(k) >= thr) { const uint32_t qk = q_(k); if (qk >= fl) pre += qk; }
+        // (block_sum_u64 written out: through the helper the two non-LP TR instantiations spill one more register, 52 -> 56 B of scratch)
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) pre += __shfl_xor(pre, off, 64);
         if (lane == 0) s_q[wave] = pre;
         __syncthreads();
         if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; s_total = t; }
         __syncthreads();
-        const unsigned long long qe = (unsigned long long)((double)sp->eps * (double)s_total);
-        if (qe > fl) fl = qe;
+        total_m = s_total;
       }
-      fb = fl > 2147483648ull;
-      qfl = fb ? 0u : (uint32_t)fl;
+      trunc_floor(sp->qmin, sp->eps, total_m, qfl, fb);
     }
     // element k (i0 + k < V) of the final set; qk = q_(k)
-    auto kept_el = [&](int k, uint32_t kb, uint32_t qk) -> bool {
-      if constexpr (TR) return fb ? (i0 + k == amax) : (kb >= thr && qk >= qfl);
-      else return kb >= thr;
-    };
+    auto kept_el = [&](int k, uint32_t kb, uint32_t qk) -> bool { return sample_kept<TR>(kb, qk, i0 + k, thr, qfl, fb, amax); };
     // kept mass + inverse-CDF draw in index order (thread t's range is contiguous: a plain block scan)
     unsigned long long mine = 0;
     if constexpr (TR) {
@@ -2003,18 +1816,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
 #pragma unroll
       for (int k = 0; k < SF_PER; ++k) if (i0 + k < V && key(k) >= thr) mine += q_(k);
     }
-    scan[tid] = mine;
-    __syncthreads();
-    for (int off = 1; off < SAMPLE_THREADS; off <<= 1) {
-      unsigned long long v = 0;
-      if (tid >= off) v = scan[tid - off];
-      __syncthreads();
-      scan[tid] += v;
-      __syncthreads();
-    }
+    block_scan_u64<SAMPLE_THREADS>(scan, mine);
     const unsigned long long kept = scan[SAMPLE_THREADS - 1];
-    const uint64_t r = splitmix64(sp->seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(draw + 1))) >> 32;
-    const unsigned long long target = __umul64hi(kept, r << 32);
+    const unsigned long long target = draw_target(sp->seed, draw, kept);
     const unsigned long long excl = scan[tid] - mine;
     if (mine > 0 && target >= excl && target < excl + mine) {
       unsigned long long run = excl;
@@ -2041,29 +1845,9 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(SampleArgs a) {
     for (int k = 0; k < SF_PER; ++k) if (i0 + k < V) a.probs_out[i0 + k] = (i0 + k == s_token) ? 1.f : 0.f;
   }
 
-  // a resumed slot (dtk_resume_slot) forwards the last token of its prompt instead of a sampled one: the draw counter (and
-  // with it the begin-suppress rule of the first SAMPLED token) does not move
-  const int tok = forced > 0 ? forced - 1 : s_token;
-  if (tid == 0) {
-    a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
-    if constexpr (LP)      // a forced token was not sampled: NaN, NaN
-      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? make_float2(__builtin_nanf(""), __builtin_nanf(""))
-                                                                   : lp_pair(a.logits[tok], lm, ls, sampling, lp_q, lp_total);
-    if constexpr (LP) if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = forced > 0 ? __builtin_nanf("") : lm + logf(ls);
-    if (a.advance) {
-      a.st->token = tok;
-      a.st->pos = a.st->next_pos;
-      a.st->next_pos = a.st->next_pos + 1;
-      a.st->draw = forced > 0 ? draw : draw + 1;
-      if (forced > 0) a.st->force_plus1 = 0;
-      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
-    }
-  }
-  if (a.advance) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(a.embed + (size_t)tok * a.d);
-    u32x4* dst = reinterpret_cast<u32x4*>(a.x);
-    for (int c = tid; c < (a.d >> 3); c += SAMPLE_THREADS) dst[c] = src[c];
-  }
+  float2 lp = make_float2(0.f, 0.f); float lse = 0.f;      // LP, thread 0: against the block's log-sum-exp state of the raw row
+  if constexpr (LP) if (tid == 0 && forced <= 0) { lp = lp_pair(a.logits[s_token], lm, ls, sampling, lp_q, lp_total); lse = lm + logf(ls); }
+  sample_commit<LP, PN, SAMPLE_THREADS>(a, s_token, forced, draw, lp, lse);
 }
 #undef key
 #undef q_
@@ -2131,19 +1915,12 @@ void launch_sample(const SampleArgs& a, hipStream_t s) {
 template <bool PN>
 static void launch_sample_t(const SampleArgs& a, hipStream_t s) {
   const dim3 g(a.bs ? a.nslots : 1), b(SAMPLE_THREADS);
-  if (sample_fast_ok(a)) {
-    if (a.trunc) {
-      if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, true, PN>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((k_sample_fast<false, true, PN>), g, b, 0, s, a);
-    } else if (a.lp_ring) hipLaunchKernelGGL((k_sample_fast<true, false, PN>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_sample_fast<false, false, PN>), g, b, 0, s, a);
-    return;
-  }
-  if (a.trunc) {
-    if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, true, PN>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_sample<false, true, PN>), g, b, 0, s, a);
-  } else if (a.lp_ring) hipLaunchKernelGGL((k_sample<true, false, PN>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_sample<false, false, PN>), g, b, 0, s, a);
+  const bool fast = sample_fast_ok(a);
+  dispatch_lp_tr(a, [&](auto lp, auto tr) {
+    constexpr bool LP = decltype(lp)::value, TR = decltype(tr)::value;
+    if (fast) hipLaunchKernelGGL((k_sample_fast<LP, TR, PN>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((k_sample<LP, TR, PN>), g, b, 0, s, a);
+  });
 }
 void launch_sample_b(const SampleArgs& a, hipStream_t s) {
   if (a.pen) launch_sample_t<true>(a, s); else launch_sample_t<false>(a, s);

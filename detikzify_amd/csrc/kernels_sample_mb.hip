@@ -18,53 +18,26 @@
 // kept after top-p and min-p (bpre); one more kernel, k_smb_trunc, folds those in slice order into total_m, forms the mass floor
 // max(qmin, (int64)((double)eps * (double)total_m)) — above 2^31: the first arg-max alone survives — and leaves the final bkept; P6
 // applies the floor.  Without it the chain is the 7 kernels above, unchanged.
-// PN (SampleArgs::pen, dtk_set_penalties): the presence / frequency penalty, applied by mb_load — so every kernel of the chain that
-// reloads the row sees the same z' — after the raw values have been handed out for the log-sum-exp, before the temperature and the
-// suppression lists.  The block of k_smb_draw that writes the token may run before other blocks of its slot have loaded their slice (the
-// hazard draw_snap exists for), so the token is NOT counted here: it goes to pen_tok, and k_count_token, a kernel behind the chain,
-// counts it.  PN = false are the kernels as they were before the penalties existed.
-// Length control and logit bias (SampleArgs::len) ride PN in mb_load as well: the bias in front of pen_apply, the EOS rules behind
-// dry_apply.  The rules need the sequence's length, which k_smb_draw's owner block advances: k_smb_max leaves it in SampleMB::cur_snap.
+// PN (SampleArgs::pen, dtk_set_penalties): the logit transform of sample_inl.h's LogitXf (bias, presence / frequency penalty, DRY, the
+// EOS length rules), applied by mb_load — so every kernel of the chain that reloads the row sees the same z' — after the raw values
+// have been handed out for the log-sum-exp, before the temperature and the suppression lists.  The block of k_smb_draw that writes the
+// token may run before other blocks of its slot have loaded their slice (the hazard draw_snap exists for), so the token is NOT counted
+// here: sample_commit leaves it in pen_tok, and k_count_token, a kernel behind the chain, counts it.  The EOS rules need the sequence's
+// length, which k_smb_draw's owner block advances: k_smb_max leaves it in SampleMB::cur_snap.  PN = false are the kernels as they were
+// before the penalties existed.
 // Supports greedy, temperature, top-p and the suppression lists; top-k > 0 stays on the single-block kernel (the API
 // re-captures the graph when a sampling configuration needs the other kind).
-#include "kernels.h"
+#include "sample_inl.h"
 
 #define MB_THREADS 1024
 #define MB_PER 8
 #define MB_SLICE (MB_THREADS * MB_PER)
-
-__device__ __forceinline__ uint32_t mb_fkey(float f) {   // order-preserving float -> uint key (as kernels_decode.hip fkey)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 struct MbElems {
   float z[MB_PER];
   uint32_t key[MB_PER];
   uint32_t q[MB_PER];
 };
-
-// per-(sequence) view of the arguments in batched mode
-template <bool PN = false>
-__device__ __forceinline__ bool mb_bind(SampleArgs& a, int slot) {
-  if (a.bs) {
-    if (!a.bs->active[slot]) return false;
-    a.logits += (size_t)slot * a.logits_stride;
-    a.sp += slot;
-    a.st += slot;
-    a.x += (size_t)slot * a.d;
-    a.tok_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if (a.lp_ring) a.lp_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    if (a.lse_ring) a.lse_ring += (size_t)((unsigned)a.bs->step % (unsigned)a.ring) * DTK_MAX_BATCH + slot;
-    a.ring = 1;
-    a.step_override = -1;
-    a.mb += slot;
-    if constexpr (PN) { a.pen += slot; a.pen_cnt += (size_t)slot * a.pen_stride; a.pen_tok += slot; }
-    if constexpr (PN) if (a.dry) { a.dry += slot; a.dry_m += (size_t)slot * a.dry_stride; }
-    if constexpr (PN) if (a.len) { a.len += slot; a.len_m += (size_t)slot * a.len_m_stride; a.bias += (size_t)slot * a.bias_stride; }
-  }
-  return true;
-}
 
 // the sequence's length for the kernels behind k_smb_max: its snapshot, NOT DecState (k_smb_draw's owner block advances next_pos while
 // other blocks of the slot may not have loaded their slice yet)
@@ -76,74 +49,33 @@ __device__ __forceinline__ int mb_cur(const SampleArgs& a) {
 
 // this thread's 8 consecutive logits: scaled, suppressed ids -> -inf, keys; out-of-range -> -inf.  raw (k_smb_max<true> only): the
 // same loads before the temperature and the suppression lists, out-of-range -> -inf
-// PN: z' = pen_apply(z, count) in place of every z (a sequence whose two values are 0 reads no count: block-uniform); raw stays raw
+// PN: z' = LogitXf of every z (bound to the sequence's records and its length `cur`); raw stays raw
 template <bool PN = false>
 __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* sp, bool first, float invT, int base, MbElems& e,
                                         float* raw = nullptr, int cur = 0) {
   const int V = a.V;
-  float pn_p = 0.f, pn_f = 0.f; bool pn = false;
-  if constexpr (PN) { pn_p = a.pen->pp; pn_f = a.pen->fp; pn = pn_p != 0.f || pn_f != 0.f; }
-  (void)pn_p; (void)pn_f; (void)pn;
-  const float* dpen = nullptr; bool dr = false;       // DRY (SampleArgs::dry) rides PN: pen[M] off z' where the id's match length M != 0
-  if constexpr (PN) if (a.dry) { dr = a.dry->on != 0; dpen = a.dry->pen; }
-  (void)dpen; (void)dr;
-  // length control / logit bias (SampleArgs::len) ride PN: the bias in front of pen_apply, the EOS rules behind dry_apply.  `cur` is the
-  // sequence's length as k_smb_max found it (DecState::next_pos; the later kernels of the chain read its snapshot, as they read draw_snap)
-  ShapeRt sh;
-  if constexpr (PN) if (a.len) sh = shape_bind(a.len, a.len_m, a.bias, cur);
-  (void)sh;
+  LogitXf xf;
+  xf.bind<PN>(a, cur);
   if (base + MB_PER <= V && ((reinterpret_cast<uintptr_t>(a.logits + base) & 15) == 0)) {
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(a.logits + base);
     const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.logits + base + 4);
-    if constexpr (PN) {
-      uint32_t cw[4] = {0u, 0u, 0u, 0u};      // the 8 counts: one 16-byte load (base is a multiple of 8, the table 16-byte aligned)
-      if (pn) { const u32x4 c4 = *reinterpret_cast<const u32x4*>(a.pen_cnt + base); cw[0] = c4[0]; cw[1] = c4[1]; cw[2] = c4[2]; cw[3] = c4[3]; }
-      uint2 dw = make_uint2(0u, 0u);          // the 8 match lengths: one 8-byte load
-      if (dr) dw = *reinterpret_cast<const uint2*>(a.dry_m + base);
-      f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};      // the 8 biases: two 16-byte loads
-      if (sh.bias) { b0 = *reinterpret_cast<const f32x4*>(sh.bias + base); b1 = *reinterpret_cast<const f32x4*>(sh.bias + base + 4); }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        e.z[i] = dry_apply(pen_apply(bias_apply(v0[i], b0[i]), (cw[i >> 1] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.x >> (8 * i)) & 0xffu, dpen);
-        e.z[4 + i] = dry_apply(pen_apply(bias_apply(v1[i], b1[i]), (cw[2 + (i >> 1)] >> ((i & 1) * 16)) & 0xffffu, pn_p, pn_f), (dw.y >> (8 * i)) & 0xffu, dpen);
-      }
-      for (int j = 0; j < sh.ne; ++j) {
-        const int o = sh.eos[j] - base;
-#pragma unroll
-        for (int i = 0; i < MB_PER; ++i) if (o == i) e.z[i] = eos_apply(e.z[i], base + i, sh);
-      }
-#pragma unroll
-      for (int i = 0; i < MB_PER; ++i) e.z[i] *= invT;
-    } else {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { e.z[i] = v0[i] * invT; e.z[4 + i] = v1[i] * invT; }
-    }
+    for (int i = 0; i < 4; ++i) { e.z[i] = v0[i]; e.z[4 + i] = v1[i]; }
     if (raw) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) { raw[i] = v0[i]; raw[4 + i] = v1[i]; }
+      for (int i = 0; i < MB_PER; ++i) raw[i] = e.z[i];
     }
+    if constexpr (PN) xf.vec<MB_PER>(a, base, e.z);      // (base is a multiple of 8, the tables 16-byte aligned)
+#pragma unroll
+    for (int i = 0; i < MB_PER; ++i) e.z[i] *= invT;
   } else {
-    if constexpr (PN) {
 #pragma unroll
-      for (int i = 0; i < MB_PER; ++i) {
-        float z = -INFINITY;
-        if (base + i < V) {
-          z = a.logits[base + i];
-          if (sh.bias) z = bias_apply(z, sh.bias[base + i]);
-          if (pn) z = pen_apply(z, a.pen_cnt[base + i], pn_p, pn_f);
-          if (dr) z = dry_apply(z, a.dry_m[base + i], dpen);
-          if (sh.ne) z = eos_apply(z, base + i, sh);
-          z *= invT;
-        }
-        e.z[i] = z;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < MB_PER; ++i) e.z[i] = (base + i < V) ? a.logits[base + i] * invT : -INFINITY;
-    }
-    if (raw) {
-#pragma unroll
-      for (int i = 0; i < MB_PER; ++i) raw[i] = (base + i < V) ? a.logits[base + i] : -INFINITY;
+    for (int i = 0; i < MB_PER; ++i) {
+      const bool in = base + i < V;
+      float z = in ? a.logits[base + i] : -INFINITY;
+      if (raw) raw[i] = z;
+      if constexpr (PN) if (in) z = xf.one(a, base + i, z);
+      e.z[i] = in ? z * invT : -INFINITY;
     }
   }
   // suppression lists: which of the (<= 24) ids fall into this thread's 8 elements
@@ -156,7 +88,7 @@ __device__ __forceinline__ void mb_load(const SampleArgs& a, const SamplingDev* 
   for (int j = 0; j < sp->n_always; ++j) ban(sp->always_ids[j]);
   if (first) for (int j = 0; j < sp->n_begin; ++j) ban(sp->begin_ids[j]);
 #pragma unroll
-  for (int i = 0; i < MB_PER; ++i) e.key[i] = mb_fkey(e.z[i]);
+  for (int i = 0; i < MB_PER; ++i) e.key[i] = fkey(e.z[i]);
 }
 
 __device__ __forceinline__ void mb_mass(MbElems& e, float zmax) {
@@ -190,7 +122,7 @@ __device__ __forceinline__ void mb_common(const SampleArgs& a, int nblk, MbCommo
 // ---- P0.  LP (SampleArgs::lp_ring): the slice's log-sum-exp state of its raw logits goes out with its maximum
 template <bool LP, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
-  if (!mb_bind<PN>(a, blockIdx.y)) return;
+  if (!sample_bind_slot<PN>(a, blockIdx.y)) return;
   __shared__ SamplingDev s_sp;
   __shared__ float s_f[16];
   __shared__ int s_i[16];
@@ -200,8 +132,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
   __syncthreads();
   const uint32_t draw = (a.step_override >= 0) ? (uint32_t)a.step_override : a.st->draw;
   const float invT = s_sp.do_sample ? 1.f / s_sp.temperature : 1.f;
-  int cur = 0;       // PN with SampleArgs::len: the sequence's length, for the EOS rules
-  if constexpr (PN) if (a.len) cur = a.len_cur >= 0 ? a.len_cur : a.st->next_pos;
+  const int cur = sample_cur<PN>(a);       // PN with SampleArgs::len: the sequence's length, for the EOS rules
   MbElems e;
   const int base = blk * MB_SLICE + tid * MB_PER;
   float lm = -INFINITY, ls = 0.f;
@@ -223,19 +154,9 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_max(SampleArgs a) {
 #pragma unroll
   for (int i = 0; i < MB_PER; ++i)
     if (base + i < a.V && (e.z[i] > best || (e.z[i] == best && base + i < besti))) { best = e.z[i]; besti = base + i; }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const float ob = __shfl_xor(best, off, 64);
-    const int oi = __shfl_xor(besti, off, 64);
-    if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-  }
-  if (lane == 0) { s_f[wave] = best; s_i[wave] = besti; }
-  __syncthreads();
+  block_argmax_first<MB_THREADS>(best, besti, s_f, s_i);
   if (tid == 0) {
-    float b = s_f[0]; int bi = s_i[0];
-    for (int w = 1; w < 16; ++w)
-      if (s_f[w] > b || (s_f[w] == b && s_i[w] < bi)) { b = s_f[w]; bi = s_i[w]; }
-    a.mb->bmax[blk] = b; a.mb->barg[blk] = bi;
+    a.mb->bmax[blk] = best; a.mb->barg[blk] = besti;
     if constexpr (LP) {      // thread 0 holds wave 0's state: fold the others in wave order
       for (int w = 1; w < 16; ++w) lse_merge(lm, ls, s_lm[w], s_ls[w]);
       a.mb->lmax[blk] = lm; a.mb->lsum[blk] = ls;
@@ -264,7 +185,7 @@ __device__ __forceinline__ void mb_select(const SampleArgs& a, int lv, unsigned 
 // ---- P1..P4: LV = 3, 2, 1, 0
 template <int LV, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk) {
-  if (!mb_bind<PN>(a, blockIdx.y)) return;
+  if (!sample_bind_slot<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long w_m[16][256];   // per-wave private histograms: conflicts only inside a wave
   __shared__ unsigned int w_c[16][256];
@@ -339,14 +260,14 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_hist(SampleArgs a, int nblk)
 // ---- P5: threshold + kept mass per slice.  TR: the mass of the slice's entries that pass top-p and min-p, to bpre
 template <bool TR, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk) {
-  if (!mb_bind<PN>(a, blockIdx.y)) return;
+  if (!sample_bind_slot<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long s_m[256];
   __shared__ unsigned int s_c[256];
   __shared__ unsigned long long s_w[8];
   __shared__ int s_i[8];
   __shared__ unsigned long long s_q[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
+  const int tid = threadIdx.x, blk = blockIdx.x;
   mb_common(a, nblk, &cm);
   if (!cm.sp.do_sample) return;
   const uint32_t draw = (a.step_override >= 0) ? (uint32_t)a.step_override : a.st->draw;
@@ -370,38 +291,26 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_kept(SampleArgs a, int nblk)
 #pragma unroll
   for (int i = 0; i < MB_PER; ++i)
     if (base + i < a.V && e.key[i] >= thr && (!TR || (long long)e.q[i] >= cm.sp.qmin)) mine += e.q[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if (lane == 0) s_q[wave] = mine;
-  __syncthreads();
+  const unsigned long long t = block_sum_u64<MB_THREADS>(mine, s_q);
   if (tid == 0) {
-    unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w];
     if constexpr (TR) a.mb->bpre[blk] = t; else a.mb->bkept[blk] = t;
   }
-}
-
-// element i of the final set under TR: the mass floor, or (fb) the first arg-max alone
-__device__ __forceinline__ bool mb_kept_tr(uint32_t key, uint32_t q, int id, uint32_t thr, uint32_t qfl, bool fb, int argmax) {
-  return fb ? (id == argmax) : (key >= thr && q >= qfl);
 }
 
 // ---- TR only, between P5 and P6: the mass floor from the slices' bpre (folded in slice order by every block), the final kept mass per slice
 template <bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk) {
-  if (!mb_bind<PN>(a, blockIdx.y)) return;
+  if (!sample_bind_slot<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long s_q[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, blk = blockIdx.x;
+  const int tid = threadIdx.x, blk = blockIdx.x;
   mb_common(a, nblk, &cm);
   if (!cm.sp.do_sample) return;
   const uint32_t draw = (a.step_override >= 0) ? (uint32_t)a.step_override : a.st->draw;
   unsigned long long total_m = 0;
   for (int k = 0; k < nblk; ++k) total_m += a.mb->bpre[k];
-  unsigned long long fl = (unsigned long long)cm.sp.qmin;
-  const unsigned long long qe = (unsigned long long)((double)cm.sp.eps * (double)total_m);
-  if (qe > fl) fl = qe;
-  const bool fb = fl > 2147483648ull;
-  const uint32_t qfl = fb ? 0u : (uint32_t)fl;
+  uint32_t qfl; bool fb;
+  trunc_floor(cm.sp.qmin, cm.sp.eps, total_m, qfl, fb);
   if (blk == 0 && tid == 0) { a.mb->qfl = qfl; a.mb->fb = fb ? 1 : 0; }
   const uint32_t thr = a.mb->thr;
   const float invT = 1.f / cm.sp.temperature;
@@ -412,19 +321,16 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_trunc(SampleArgs a, int nblk
   unsigned long long mine = 0;
 #pragma unroll
   for (int i = 0; i < MB_PER; ++i)
-    if (base + i < a.V && mb_kept_tr(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax)) mine += e.q[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
-  if (lane == 0) s_q[wave] = mine;
-  __syncthreads();
-  if (tid == 0) { unsigned long long t = 0; for (int w = 0; w < 16; ++w) t += s_q[w]; a.mb->bkept[blk] = t; }
+    if (base + i < a.V && sample_kept<true>(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax)) mine += e.q[i];
+  const unsigned long long t = block_sum_u64<MB_THREADS>(mine, s_q);
+  if (tid == 0) a.mb->bkept[blk] = t;
 }
 
 // ---- P6: draw (or arg-max), token ring, DecState, embedding gather.  LP: thread 0 of the block that writes the token folds the
 // slices' log-sum-exp states in slice order and stores the token's (logprob, sample_logprob)
 template <bool LP, bool TR, bool PN>
 __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk) {
-  if (!mb_bind<PN>(a, blockIdx.y)) return;
+  if (!sample_bind_slot<PN>(a, blockIdx.y)) return;
   __shared__ MbCommon cm;
   __shared__ unsigned long long scan[MB_THREADS];
   __shared__ int s_token;
@@ -451,8 +357,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
   } else {
     unsigned long long before = 0;
     for (int k = 0; k < nblk; ++k) { const unsigned long long v = a.mb->bkept[k]; if (k < blk) before += v; kept += v; }
-    const uint64_t r = splitmix64(cm.sp.seed ^ (0xD1B54A32D192ED03ull * (uint64_t)(draw + 1))) >> 32;
-    const unsigned long long target = __umul64hi(kept, r << 32);  // floor(kept * r / 2^32)
+    const unsigned long long target = draw_target(cm.sp.seed, draw, kept);
     const unsigned long long mine_blk = a.mb->bkept[blk];
     owner = mine_blk > 0 && target >= before && target < before + mine_blk;     // exactly one slice
     if (owner || a.probs_out) {
@@ -464,10 +369,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
       mb_mass(e, cm.zmax);
       uint32_t qfl = 0; bool fb = false;
       if constexpr (TR) { qfl = a.mb->qfl; fb = a.mb->fb != 0; }
-      auto kept_el = [&](int i) -> bool {
-        if constexpr (TR) return mb_kept_tr(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax);
-        else return e.key[i] >= thr;
-      };
+      auto kept_el = [&](int i) -> bool { return sample_kept<TR>(e.key[i], e.q[i], base + i, thr, qfl, fb, cm.argmax); };
       if (a.probs_out)
         for (int i = 0; i < MB_PER; ++i)
           if (base + i < a.V) a.probs_out[base + i] = kept_el(i) ? (float)((double)e.q[i] / (double)kept) : 0.f;
@@ -475,15 +377,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
         unsigned long long mine = 0;
 #pragma unroll
         for (int i = 0; i < MB_PER; ++i) if (base + i < a.V && kept_el(i)) mine += e.q[i];
-        scan[tid] = mine;
-        __syncthreads();
-        for (int off = 1; off < MB_THREADS; off <<= 1) {   // block-uniform branch (owner): barriers are safe
-          unsigned long long v = 0;
-          if (tid >= off) v = scan[tid - off];
-          __syncthreads();
-          scan[tid] += v;
-          __syncthreads();
-        }
+        block_scan_u64<MB_THREADS>(scan, mine);      // block-uniform branch (owner): barriers are safe
         const unsigned long long excl = before + scan[tid] - mine;
         if (mine > 0 && target >= excl && target < excl + mine) {
           unsigned long long run = excl;
@@ -501,59 +395,31 @@ __global__ __launch_bounds__(MB_THREADS) void k_smb_draw(SampleArgs a, int nblk)
   __syncthreads();
   if (forced > 0) owner = blk == 0;     // nothing was asked of the (stale) logits: exactly one block writes the token
   if (!owner) return;
-  // a resumed slot (dtk_resume_slot) forwards the last token of its prompt instead of a sampled one: the draw counter (and
-  // with it the begin-suppress rule of the first SAMPLED token) does not move
-  const int tok = forced > 0 ? forced - 1 : s_token;
-  if (tid == 0) {
-    a.tok_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = (int64_t)tok;
-    if constexpr (LP) {
-      float2 lp = make_float2(__builtin_nanf(""), __builtin_nanf(""));      // a forced token was not sampled
-      float e = __builtin_nanf("");
-      if (forced <= 0) {
-        float lm = a.mb->lmax[0], ls = a.mb->lsum[0];
-        for (int k = 1; k < nblk; ++k) lse_merge(lm, ls, a.mb->lmax[k], a.mb->lsum[k]);
-        lp = lp_pair(a.logits[tok], lm, ls, sampling, sampling ? s_tokq : 0u, kept);
-        e = lm + logf(ls);
-      }
-      a.lp_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = lp;
-      if (a.lse_ring) a.lse_ring[a.bs ? 0u : draw % (uint32_t)a.ring] = e;
-    }
-    if (a.advance) {
-      a.st->token = tok;
-      a.st->pos = a.st->next_pos;
-      a.st->next_pos = a.st->next_pos + 1;
-      a.st->draw = forced > 0 ? draw : draw + 1;
-      if (forced > 0) a.st->force_plus1 = 0;
-      if constexpr (PN) *a.pen_tok = forced > 0 ? -1 : tok;      // a forced token is among the ids the table was built from
-    }
+  float2 lp = make_float2(0.f, 0.f); float lse = 0.f;
+  if constexpr (LP) if (tid == 0 && forced <= 0) {      // the slices' log-sum-exp states, folded in slice order
+    float lm = a.mb->lmax[0], ls = a.mb->lsum[0];
+    for (int k = 1; k < nblk; ++k) lse_merge(lm, ls, a.mb->lmax[k], a.mb->lsum[k]);
+    lp = lp_pair(a.logits[s_token], lm, ls, sampling, sampling ? s_tokq : 0u, kept);
+    lse = lm + logf(ls);
   }
-  if (a.advance) {
-    const u32x4* src = reinterpret_cast<const u32x4*>(a.embed + (size_t)tok * a.d);
-    u32x4* dst = reinterpret_cast<u32x4*>(a.x);
-    for (int c = tid; c < (a.d >> 3); c += MB_THREADS) dst[c] = src[c];
-  }
+  sample_commit<LP, PN, MB_THREADS>(a, s_token, forced, draw, lp, lse);
 }
 
 template <bool PN>
 static void launch_sample_mb_t(const SampleArgs& a, hipStream_t s) {
   const int nblk = (a.V + MB_SLICE - 1) / MB_SLICE;   // <= DTK_SAMPLE_MB_MAX_SLICES
   const dim3 g(nblk, a.bs ? a.nslots : 1), b(MB_THREADS);
-  if (a.lp_ring) hipLaunchKernelGGL((k_smb_max<true, PN>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((k_smb_max<false, PN>), g, b, 0, s, a);
-  hipLaunchKernelGGL((k_smb_hist<3, PN>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<2, PN>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<1, PN>), g, b, 0, s, a, nblk);
-  hipLaunchKernelGGL((k_smb_hist<0, PN>), g, b, 0, s, a, nblk);
-  if (a.trunc) {
-    hipLaunchKernelGGL((k_smb_kept<true, PN>), g, b, 0, s, a, nblk);
-    hipLaunchKernelGGL(k_smb_trunc<PN>, g, b, 0, s, a, nblk);
-    if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, true, PN>), g, b, 0, s, a, nblk);
-    else hipLaunchKernelGGL((k_smb_draw<false, true, PN>), g, b, 0, s, a, nblk);
-    return;
-  }
-  hipLaunchKernelGGL((k_smb_kept<false, PN>), g, b, 0, s, a, nblk);
-  if (a.lp_ring) hipLaunchKernelGGL((k_smb_draw<true, false, PN>), g, b, 0, s, a, nblk);
-  else hipLaunchKernelGGL((k_smb_draw<false, false, PN>), g, b, 0, s, a, nblk);
+  dispatch_lp_tr(a, [&](auto lp, auto tr) {
+    constexpr bool LP = decltype(lp)::value, TR = decltype(tr)::value;
+    hipLaunchKernelGGL((k_smb_max<LP, PN>), g, b, 0, s, a);
+    hipLaunchKernelGGL((k_smb_hist<3, PN>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_hist<2, PN>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_hist<1, PN>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_hist<0, PN>), g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_kept<TR, PN>), g, b, 0, s, a, nblk);
+    if constexpr (TR) hipLaunchKernelGGL(k_smb_trunc<PN>, g, b, 0, s, a, nblk);
+    hipLaunchKernelGGL((k_smb_draw<LP, TR, PN>), g, b, 0, s, a, nblk);
+  });
 }
 // a.pen == nullptr (no sequence of this launch has a presence / frequency penalty): the PN = false instantiations, the chain as it was
 void launch_sample_mb(const SampleArgs& a, hipStream_t s) {

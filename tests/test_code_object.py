@@ -25,7 +25,7 @@ def _kernel_metadata(obj: Path, tmp: Path):
     # a kernel is one YAML map item with alphabetically ordered keys (.agpr_count opens it, .name sits in the middle): collect the item,
     # file it under its name when the next one starts
     kernels, item = {}, None
-    wanted = ("private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "agpr_count")
+    wanted = ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count", "vgpr_count", "agpr_count")
 
     def close(item):
         name = item.get("name") if item else None
@@ -61,6 +61,33 @@ def test_kernels_with_hand_issued_loads_do_not_spill(tmp_path):
         assert meta["vgpr_count"] <= (512 if deep else 256), (name, meta)
     assert any(k.endswith("ELb1ELi4EEv9GemvBArgs") for k in br), "the fp8 ring-of-4 instantiations are the shipped fp8 kernels"
     assert not any("k_gemv_brILi" in k and re.search(r"k_gemv_brILi\dELi\dELi2E", k) for k in kernels), "the K = 2048 instantiations spill: not to be built"
+
+
+@pytest.mark.skipif(not (LLVM / "clang-offload-bundler").exists(), reason="needs the ROCm LLVM tools")
+def test_sampler_kernels_keep_their_registers_and_scratch(tmp_path):
+    """The three sampler families share their load sites, reductions and commit (csrc/sample_inl.h), and k_sample_fast sits on the
+    128-register ceiling of a 1024-thread block: a helper that costs it a register costs it scratch.  The shipped code objects,
+    instantiation by instantiation: (LP, TR, PN) of both single-block kernels and the 26 kernels of the chain are all there; k_sample and
+    the chain spill nothing, k_sample has no scratch, the chain no more than the 32 bytes it had before the helpers existed, and no
+    k_sample_fast more than its largest instantiation had then (164 bytes: <LP, no TR>).  Caps on what exists, not targets
+    (profiles/sampler_shared_resources.txt has both tables)."""
+    if not (ROOT / "build" / "kernels_decode.o").exists() or not (ROOT / "build" / "kernels_sample_mb.o").exists():
+        subprocess.run(["bash", str(ROOT / "build.sh")], check=True, capture_output=True, cwd=str(ROOT))
+    (tmp_path / "d").mkdir()
+    (tmp_path / "m").mkdir()
+    dec = _kernel_metadata(ROOT / "build" / "kernels_decode.o", tmp_path / "d")
+    generic = {k: v for k, v in dec.items() if k.startswith("_Z8k_sampleIL")}
+    fast = {k: v for k, v in dec.items() if k.startswith("_Z13k_sample_fastIL")}
+    chain = {k: v for k, v in _kernel_metadata(ROOT / "build" / "kernels_sample_mb.o", tmp_path / "m").items() if "k_smb_" in k}
+    assert len(generic) == 8 and len(fast) == 8 and len(chain) == 26, (sorted(generic), sorted(fast), sorted(chain))
+    for name, m in {**generic, **chain}.items():
+        assert m["vgpr_spill_count"] == 0, (name, m)
+    for name, m in generic.items():
+        assert m["private_segment_fixed_size"] == 0, (name, m)
+    for name, m in chain.items():
+        assert m["private_segment_fixed_size"] <= 32, (name, m)
+    for name, m in fast.items():
+        assert m["private_segment_fixed_size"] <= 164, (name, m)
 
 
 def test_hand_load_checker_sees_a_register_read_before_its_wait():

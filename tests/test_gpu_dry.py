@@ -483,7 +483,7 @@ def test_engines_carry_the_values_with_the_joins(batched, engine):
 
 # ------------------------------------------------------------------------------------------ the chain, batched
 def test_two_slots_of_the_chain_with_their_own_values():
-    """the 40 000-token toy with slots: the multi-block chain with a slot offset on the match table (mb_bind), k_dry_scan with one block
+    """the 40 000-token toy with slots: the multi-block chain with a slot offset on the match table (sample_bind_slot), k_dry_scan with one block
     per slot in front of it and the trailing kernel behind it, 10 steps of two slots under different values.  Every token is the
     oracle's draw over z' of the slot's own row, and in each slot some step's draw is not the raw row's"""
     model = _bigvocab(slots=3)

@@ -49,6 +49,11 @@ def _pairs(pairs):
 
 
 # ------------------------------------------------------------------------------------------ the samplers with the tables
+# the op-level rows run over FAMILIES and two more load-site forms with every table on: k_sample's 16-byte pass 1 (V % 4 == 0; at 32 769 it
+# runs scalar) and a sampling row over the chain's ragged tail (the last slice ends inside a thread's 8 ids, 3 of them valid; at 40 000
+# every thread is full, at 32 769 only greedy rows reach the chain).  Both below the fixture's vocabulary: probs_out is allowed
+OP_V = {**FAMILIES, 36864: "k_sample-16B", 36867: "k_smb_*-ragged"}
+TOPK_V = (32769, 36864)          # the vocabularies whose sampling rows ask top_k = V - 1: k_sample
 START = 5          # length_start of every op-level row
 MIN_NEW, DSTART = 4, 6
 
@@ -58,9 +63,9 @@ def _rows(V):
     moves = whether the transformed row must differ from the raw one.  EOS ids 0, V - 2 and V - 1; biased ids in the last 8 columns (the
     ragged tail of mb_load at 32 769: id 32 768 alone) and 256 of them in one row; n = cur - START on both sides of both thresholds; k at
     the 2^100 clamp.  Which kernels a row runs is the launchers' rule (tests/test_gpu_penalty.py::_rows): everything k_sample_fast at
-    32 000; at 32 769 and 40 000 a sampling row with 0 < top_k < V runs k_sample, and a row with top_k = 0 or a greedy one the chain."""
+    32 000; above 32 768 a sampling row with 0 < top_k < V (TOPK_V) runs k_sample, and a row with top_k = 0 or a greedy one the chain."""
     g = torch.Generator().manual_seed(V + 23)
-    nk = V - 1 if V == 32769 else 0
+    nk = V - 1 if V in TOPK_V else 0
     wide = lambda: rb(torch.randn(V, generator=g) * 4)
     E = [0, V - 2, V - 1]
     S = dict(do_sample=True, temperature=1.1, top_k=nk, top_p=0.9, min_p=0.05, eps=3e-4)
@@ -111,7 +116,7 @@ def _device_args(shape, V):
     return l, d, _pairs(pairs), _i64(shape.get("counted", ())), _i64(shape.get("h", ()))
 
 
-@pytest.mark.parametrize("V", list(FAMILIES), ids=[f"{v}-{k}" for v, k in FAMILIES.items()])
+@pytest.mark.parametrize("V", list(OP_V), ids=[f"{v}-{k}" for v, k in OP_V.items()])
 def test_op_sample_shape_matches_the_oracle(big, V):
     """every draw: the token is the oracle's over the transformed row z'; the token, probs_out and sample_logprob are, bit for bit, what
     the same kernels give for the oracle's z' handed in as the row (dtk_op_sample_ext: everything behind the load sites is a function of
@@ -169,7 +174,7 @@ def test_op_sample_shape_matches_the_oracle(big, V):
     assert n_rows == 12
 
 
-@pytest.mark.parametrize("V", list(FAMILIES), ids=[f"{v}-{k}" for v, k in FAMILIES.items()])
+@pytest.mark.parametrize("V", list(OP_V), ids=[f"{v}-{k}" for v, k in OP_V.items()])
 def test_off_means_off_at_op_level(big, V):
     """no rule and no bias (a record that is all off, at a length far beyond every threshold): the token, the probabilities and both
     log-probabilities of dtk_op_sample_ext, bit for bit; likewise rules without an EOS id, and a bias table of zeros"""
@@ -181,7 +186,7 @@ def test_off_means_off_at_op_level(big, V):
     tok, tok2, lp, lp2 = C.c_int64(), C.c_int64(), (C.c_float * 2)(), (C.c_float * 2)()
     p1, p2 = np.empty(V, dtype=np.float32), np.empty(V, dtype=np.float32)
     offs = [(length_struct(0, None, 0, ()), []), (length_struct(50, (60, 2.0), 0, ()), []), (length_struct(0, None, 3, (0, V - 1)), [(V - 1, 0.0), (7, -0.0)])]
-    for T, k, p, mp, eps in ((0.8, V - 1 if V == 32769 else 0, 0.95, 0.0, 0.0), (1.3, 50, 1.0, 0.1, 3e-4)):
+    for T, k, p, mp, eps in ((0.8, V - 1 if V in TOPK_V else 0, 0.95, 0.0, 0.0), (1.3, 50, 1.0, 0.1, 3e-4)):
         model.set_sampling(do_sample=True, temperature=T, top_p=p, top_k=k, seed=SEED, bad_ids=BAD, begin_suppress_ids=BEGIN)
         x = _lib.DtkSamplingExt(min_p=mp, epsilon_cutoff=eps)
         for l, pairs in offs:
@@ -440,7 +445,7 @@ def test_engines_carry_the_values_with_the_joins(batched, engine):
 
 # ------------------------------------------------------------------------------------------ the chain, batched
 def test_two_slots_of_the_chain_with_their_own_values():
-    """the 40 000-token toy with slots: the multi-block chain with a slot offset on the records and the tables (mb_bind) and the length
+    """the 40 000-token toy with slots: the multi-block chain with a slot offset on the records and the tables (sample_bind_slot) and the length
     read from the snapshot k_smb_max leaves, 9 steps of three slots: a minimum with a certain EOS, a decay with biases in the last 8
     columns, and one without values, which draws what it draws alone.  Every token is the oracle's draw over the slot's own row"""
     model = _bigvocab(slots=4)

@@ -412,7 +412,7 @@ def test_engines_carry_the_values_with_the_joins(batched, engine):
 
 # ------------------------------------------------------------------------------------------ the chain, batched
 def test_two_slots_of_the_chain_with_their_own_values():
-    """the 40 000-token toy with slots: the multi-block chain under PN with a slot offset on pen / pen_cnt / pen_tok (mb_bind) and
+    """the 40 000-token toy with slots: the multi-block chain under PN with a slot offset on pen / pen_cnt / pen_tok (sample_bind_slot) and
     k_count_token behind it for several slots.  6 steps of two slots under different values, every token the oracle's over the slot's own
     row, the tables read back; slot 1 counts from position 0 (the image placeholder, banned, counted num_patches times) with negative
     values"""
