@@ -364,8 +364,26 @@ SYMBOLS = {
     "dtk_spec_end": (C.c_int, [_P, C.c_int]),
     "dtk_bench_spec": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float)]),
     "dtk_op_spec_lookup": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    # ... and its second draft source, a corpus of earlier programs (CORPUS_SYMBOLS: a library without them loads, and speculates
+    # without a corpus)
+    "dtk_spec_set_corpus": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int]),
+    "dtk_spec_corpus_len": (C.c_int, [_P]),
+    "dtk_spec_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "dtk_op_spec_lookup_corpus": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 DTK_SPEC_LOOKUP, DTK_SPEC_TABLE, DTK_SPEC_MAX_NGRAM = 0, 1, 16
+DTK_SPEC_CORPUS_MAX = 65536
+DTK_SPEC_FROM_NONE, DTK_SPEC_FROM_HISTORY, DTK_SPEC_FROM_CORPUS = 0, 1, 2
+CORPUS_SYMBOLS = ("dtk_spec_set_corpus", "dtk_spec_corpus_len", "dtk_spec_counters", "dtk_op_spec_lookup_corpus")
+
+
+def corpus_call(lib, name: str):
+    """the corpus entry point `name` of lib, or a DtkError that says what is missing: only a call that uses a corpus needs them"""
+    fn = getattr(lib, name, None)
+    if fn is None:
+        raise DtkError(f"{name} is missing: this library has no prompt-lookup corpus (prompt_lookup_corpus needs a build of this tree)")
+    return fn
 
 _lib = None
 
@@ -393,6 +411,8 @@ def load_library() -> C.CDLL:
             pass
     lib = C.CDLL(str(LIB_PATH), mode=C.RTLD_GLOBAL)
     for name, (res, args) in SYMBOLS.items():
+        if name in CORPUS_SYMBOLS and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError here = ABI mismatch, loud by design
         fn.restype, fn.argtypes = res, args
     if lib.dtk_abi_version() != DTK_ABI_VERSION:

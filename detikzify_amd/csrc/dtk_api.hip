@@ -865,6 +865,7 @@ void batch_step_launches_mv(dtk_ctx* c) {
     sv.st_true = c->st_b; sv.st_vec = c->spec_st; sv.bs = c->spec_bs; sv.tok_ring = c->tokb_dev; sv.ring = DTK_MAX_INFLIGHT;
     sv.embed = c->embed; sv.x = c->xb; sv.d = d;
     launch_spec_accept(sv, s);
+    if (c->spec_corpus_len > 0) launch_spec_corpus(sv, s);      // (dtk_spec_set_corpus drops the captured steps when this changes)
     launch_spec_draft(sv, s);
   } else {
     step_sampler_chain(c, sa, c->mb_batch);
@@ -1772,6 +1773,7 @@ void dtk_destroy(dtk_ctx* c) {
   if (c->lseb_host) (void)hipHostFree(c->lseb_host);
   if (c->packed_rows) (void)hipFree(c->packed_rows);
   if (c->spec_mem) (void)hipFree(c->spec_mem);
+  if (c->spec_corpus) (void)hipFree(c->spec_corpus);
   if (c->stream_vit) (void)hipStreamDestroy(c->stream_vit);
   if (c->ev_va) (void)hipEventDestroy(c->ev_va);
   if (c->ev_vb) (void)hipEventDestroy(c->ev_vb);
@@ -3019,6 +3021,7 @@ int dtk_spec_begin(dtk_ctx* c, int K, int max_ngram, int source) {
   SpecDev sd{};
   sd.drafts[0] = h[(size_t)n - 1]; sd.drafts[1] = sd.drafts[2] = sd.drafts[3] = -1; sd.n_live = 1;
   sd.K = K; sd.NV = K + 1; sd.max_ngram = max_ngram; sd.use_table = source == DTK_SPEC_TABLE ? 1 : 0;
+  sd.corpus_len = c->spec_corpus_len; sd.corpus = c->spec_corpus; sd.corpus_best = c->spec_corpus_best;      // (the step counters start at 0)
   HIPCHK(c, hipMemcpy(c->spec_sd, &sd, sizeof sd, hipMemcpyHostToDevice));
   for (int j = 1; j <= K; ++j) c->bseq[(size_t)j].have_logits = false;      // their logits rows and residual rows become the vectors'; their KV stays
   c->spec_K = K; c->spec_src = source; c->spec_nv = K + 1;      // (the n-gram size lives in spec_sd alone)
@@ -3040,6 +3043,56 @@ int dtk_spec_set_drafts(dtk_ctx* c, const int32_t* table, int n) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(c->spec_table, t.data(), (size_t)c->Tmax * 4, hipMemcpyHostToDevice));
+  return DTK_OK;
+}
+
+// the corpus of earlier programs, the lookup's second draft source (include/dtk.h).  Pointer and length reach the kernels through
+// spec_sd, so the captured steps serve every corpus; only the change between none and some changes what a step launches
+int dtk_spec_set_corpus(dtk_ctx* c, const int32_t* ids, int n) {
+  if (!c || (!ids && n > 0) || n < 0) return fail(c, DTK_ERR_ARG, "dtk_spec_set_corpus: bad argument");
+  if (n > DTK_SPEC_CORPUS_MAX) return fail(c, DTK_ERR_RANGE, "dtk_spec_set_corpus: a corpus of %d entries exceeds DTK_SPEC_CORPUS_MAX = %d", n, DTK_SPEC_CORPUS_MAX);
+  if (!mv_family(c)) return fail(c, DTK_ERR_STATE, "dtk_spec_set_corpus: the context is outside the multi-vector family (2..5 batch slots): it has no speculative step");
+  if (c->spec_on && c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_spec_set_corpus: a speculative step is in flight");
+  for (int i = 0; i < n; ++i)
+    if (ids[i] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_spec_set_corpus: corpus id %d at entry %d (a token id below %d, or a negative separator)", ids[i], i, c->V);
+  if (n == 0 && c->spec_corpus_len == 0) return DTK_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (n > 0 && !c->spec_corpus) {
+    const size_t ids_bytes = (size_t)DTK_SPEC_CORPUS_MAX * sizeof(int32_t);
+    HIPCHK(c, hipMalloc((void**)&c->spec_corpus, ids_bytes + DTK_SPEC_CORPUS_BLOCKS * sizeof(unsigned long long)));
+    c->spec_corpus_best = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(c->spec_corpus) + ids_bytes);
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n > 0) HIPCHK(c, hipMemcpy(c->spec_corpus, ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  if ((n > 0) != (c->spec_corpus_len > 0)) {      // a step with k_spec_corpus <-> a step without it: the two captures go (one re-capture each)
+    for (int i = 0; i < 2; ++i) {
+      if (c->sgraph_exec[i]) { (void)hipGraphExecDestroy(c->sgraph_exec[i]); c->sgraph_exec[i] = nullptr; }
+      if (c->sgraph[i]) { (void)hipGraphDestroy(c->sgraph[i]); c->sgraph[i] = nullptr; }
+      c->sgraph_ready[i] = false;
+    }
+  }
+  c->spec_corpus_len = n;
+  if (c->spec_sd) {      // (a context that has not speculated yet has no record: dtk_spec_begin writes these three)
+    const int32_t len32 = n;
+    HIPCHK(c, hipMemcpy(&c->spec_sd->corpus_len, &len32, sizeof len32, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(&c->spec_sd->corpus, &c->spec_corpus, sizeof c->spec_corpus, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(&c->spec_sd->corpus_best, &c->spec_corpus_best, sizeof c->spec_corpus_best, hipMemcpyHostToDevice));
+  }
+  return DTK_OK;
+}
+
+int dtk_spec_corpus_len(const dtk_ctx* c) { return c ? c->spec_corpus_len : 0; }
+
+int dtk_spec_counters(dtk_ctx* c, int64_t* out) {
+  if (!c || !out) return fail(c, DTK_ERR_ARG, "dtk_spec_counters: bad argument");
+  if (c->spec_on && c->blaunched != c->bwaited) return fail(c, DTK_ERR_STATE, "dtk_spec_counters: a step is in flight");
+  out[0] = out[1] = out[2] = 0;
+  if (!c->spec_sd) return DTK_OK;      // the context has never speculated
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  long long steps[3];
+  HIPCHK(c, hipMemcpy(steps, c->spec_sd->steps, sizeof steps, hipMemcpyDeviceToHost));
+  out[0] = steps[DTK_SPEC_FROM_HISTORY]; out[1] = steps[DTK_SPEC_FROM_CORPUS]; out[2] = steps[DTK_SPEC_FROM_NONE];
   return DTK_OK;
 }
 
@@ -3584,9 +3637,10 @@ int dtk_bench_spec(dtk_ctx* c, int reps, float* avg_us) {
   sv.sd = c->spec_sd; sv.hist = c->spec_hist; sv.table = c->spec_table; sv.K = 0; sv.max_ngram = 0; sv.NV = 0; sv.T_max = c->Tmax; sv.V = c->V;
   sv.st_true = c->st_b; sv.st_vec = c->spec_st; sv.bs = c->spec_bs; sv.tok_ring = c->tokb_dev; sv.ring = DTK_MAX_INFLIGHT;
   sv.embed = c->embed; sv.x = c->xb; sv.d = c->d;
-  for (int i = 0; i < 3; ++i) { launch_spec_accept(sv, c->stream); launch_spec_draft(sv, c->stream); }      // warm-up
+  const bool corpus = c->spec_corpus_len > 0;      // the step's third kernel, as a step launches it
+  for (int i = 0; i < 3; ++i) { launch_spec_accept(sv, c->stream); if (corpus) launch_spec_corpus(sv, c->stream); launch_spec_draft(sv, c->stream); }      // warm-up
   HIPCHK(c, hipEventRecord(c->probe_a, c->stream));
-  for (int i = 0; i < reps; ++i) { launch_spec_accept(sv, c->stream); launch_spec_draft(sv, c->stream); }
+  for (int i = 0; i < reps; ++i) { launch_spec_accept(sv, c->stream); if (corpus) launch_spec_corpus(sv, c->stream); launch_spec_draft(sv, c->stream); }
   HIPCHK(c, hipEventRecord(c->probe_b, c->stream));
   HIPCHK(c, hipEventSynchronize(c->probe_b));
   float ms = 0.f;

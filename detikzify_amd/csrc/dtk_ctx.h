@@ -348,6 +348,11 @@ struct dtk_ctx {
   DecState* spec_st = nullptr;       // [4]
   SamplingDev* spec_sp = nullptr;    // [4] copies of slot 0's record
   BatchState* spec_bs = nullptr;
+  // the corpus of earlier programs (dtk_spec_set_corpus): one hipMalloc of the first non-empty call, [DTK_SPEC_CORPUS_MAX] ids and
+  // [DTK_SPEC_CORPUS_BLOCKS] block results behind them.  spec_corpus_len > 0: a speculative step launches k_spec_corpus too
+  int32_t* spec_corpus = nullptr;
+  unsigned long long* spec_corpus_best = nullptr;
+  int spec_corpus_len = 0;
   bool sgraph_ready[2] = {false, false};       // the captured speculative step with 2 / 4 vectors
   hipGraph_t sgraph[2] = {nullptr, nullptr};
   hipGraphExec_t sgraph_exec[2] = {nullptr, nullptr};

@@ -1440,17 +1440,50 @@ int dtk_op_spec_lookup(dtk_ctx* c, const int32_t* ids, int len, int K, int max_n
   HIPCHK(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;
   OpRun r(c, "dtk_op_spec_lookup", 0x5a);
-  int32_t res[5] = {-1, -1, -1, -1, 0};
+  int32_t res[7] = {-1, -1, -1, -1, 0, 0, 0};
   SpecArgs a{};
   a.hist = r.in<int32_t>(len > 0 ? ids : nullptr, (size_t)(len > 0 ? len : 1));
   a.table = nullptr; a.K = K; a.max_ngram = max_ngram; a.NV = K + 1; a.T_max = T_max; a.V = c->V;
   a.len_override = len;
-  a.drafts_out = r.out<int32_t>(res, 5, "drafts");
+  a.drafts_out = r.out<int32_t>(res, 7, "drafts");
   if (const int rc = r.upload(s)) return rc;
   launch_spec_draft(a, s);
   if (const int rc = r.finish(s)) return rc;
   for (int i = 0; i < 4; ++i) drafts_out[i] = res[i];
   *n_out = res[4];
+  return DTK_OK;
+}
+
+// the lookup with a corpus: k_spec_corpus + k_spec_draft as a step launches them, on a history, a corpus, block results and a SpecDev of
+// the call's own (the kernels read the corpus through the record, as in a step)
+int dtk_op_spec_lookup_corpus(dtk_ctx* c, const int32_t* ids, int len, const int32_t* corpus, int n_corpus, int K, int max_ngram, int T_max,
+                              int32_t* drafts_out, int* n_out, int* source_out, int* ngram_out) {
+  if (!c || (!ids && len > 0) || len < 0 || (!corpus && n_corpus > 0) || n_corpus < 0 || K < 1 || K > 3 || max_ngram < 1 ||
+      max_ngram > DTK_SPEC_MAX_NGRAM || T_max < len || T_max < 1 || !drafts_out || !n_out || !source_out || !ngram_out)
+    return fail(c, DTK_ERR_ARG, "dtk_op_spec_lookup_corpus: bad argument");
+  if (n_corpus > DTK_SPEC_CORPUS_MAX) return fail(c, DTK_ERR_RANGE, "dtk_op_spec_lookup_corpus: a corpus of %d entries exceeds DTK_SPEC_CORPUS_MAX = %d", n_corpus, DTK_SPEC_CORPUS_MAX);
+  for (int i = 0; i < n_corpus; ++i)
+    if (corpus[i] >= c->V) return fail(c, DTK_ERR_ARG, "dtk_op_spec_lookup_corpus: corpus id %d at entry %d", corpus[i], i);
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  OpRun r(c, "dtk_op_spec_lookup_corpus", 0x5a);
+  int32_t res[7] = {-1, -1, -1, -1, 0, 0, 0};
+  SpecDev sd{};
+  sd.K = K; sd.NV = K + 1; sd.max_ngram = max_ngram; sd.use_table = 0; sd.corpus_len = n_corpus;
+  SpecArgs a{};
+  a.hist = r.in<int32_t>(len > 0 ? ids : nullptr, (size_t)(len > 0 ? len : 1));
+  sd.corpus = r.in<int32_t>(n_corpus > 0 ? corpus : nullptr, (size_t)(n_corpus > 0 ? n_corpus : 1));
+  sd.corpus_best = r.out<unsigned long long>(nullptr, DTK_SPEC_CORPUS_BLOCKS, "block results");
+  a.sd = r.in<SpecDev>(&sd, 1);
+  a.table = nullptr; a.T_max = T_max; a.V = c->V;
+  a.len_override = len;
+  a.drafts_out = r.out<int32_t>(res, 7, "drafts");
+  if (const int rc = r.upload(s)) return rc;
+  if (n_corpus > 0) launch_spec_corpus(a, s);
+  launch_spec_draft(a, s);
+  if (const int rc = r.finish(s)) return rc;
+  for (int i = 0; i < 4; ++i) drafts_out[i] = res[i];
+  *n_out = res[4]; *source_out = res[5]; *ngram_out = res[6];
   return DTK_OK;
 }
 

@@ -203,6 +203,17 @@ void launch_cfg_follow(const CfgFollowArgs& a, hipStream_t s);   // one block pe
 // dtk_spec_* (kernels_spec.hip): prompt-lookup speculative decoding of slot 0 inside the multi-vector step.  The step's vectors are
 // consecutive positions of the one sequence; these two kernels run between its sampler launch and its first GEMV.
 #define DTK_SPEC_COUNT_AT (DTK_MAX_BATCH - 1)      // entry of the step's token record that holds the number of accepted tokens (no multi-vector slot decodes there)
+#ifndef DTK_SPEC_CORPUS_MAX
+#define DTK_SPEC_CORPUS_MAX 65536   // == include/dtk.h
+#endif
+#ifndef DTK_SPEC_MAX_NGRAM
+#define DTK_SPEC_MAX_NGRAM 16       // == include/dtk.h
+#endif
+#ifndef DTK_SPEC_FROM_NONE          // where a step's drafts came from (== include/dtk.h)
+#define DTK_SPEC_FROM_NONE 0
+#define DTK_SPEC_FROM_HISTORY 1
+#define DTK_SPEC_FROM_CORPUS 2
+#endif
 struct SpecDev {
   int32_t drafts[4];     // what vector j of the last forward carried: [0] the last accepted token, [j] the draft d_j (-1: the vector was not live)
   int32_t n_live;        // live vectors of the last forward (1 + its drafts)
@@ -211,7 +222,14 @@ struct SpecDev {
   int32_t NV;            // vectors that may be live (K + 1)
   int32_t max_ngram;     // longest n-gram the lookup matches
   int32_t use_table;     // 1: the drafts come from SpecArgs::table, 0: from the lookup over SpecArgs::hist
+  // the corpus of earlier programs (dtk_spec_set_corpus): pointer and length live here, so a captured step serves every corpus
+  int32_t corpus_len;    // entries of corpus (0: none; k_spec_corpus is not launched then and k_spec_draft reads no block result)
+  const int32_t* corpus; // [DTK_SPEC_CORPUS_MAX] id sequences joined by negative separator entries
+  unsigned long long* corpus_best;   // [DTK_SPEC_CORPUS_BLOCKS] k_spec_corpus: block b's best window, (n << 32) | (0xffffffff - e), 0 = none
+  long long steps[3];    // steps since dtk_spec_begin whose drafts came from nowhere / the history (or the table) / the corpus (DTK_SPEC_FROM_*)
 };
+#define DTK_SPEC_CORPUS_THREADS 1024
+#define DTK_SPEC_CORPUS_BLOCKS (DTK_SPEC_CORPUS_MAX / DTK_SPEC_CORPUS_THREADS)
 struct SpecArgs {
   SpecDev* sd;
   int32_t* hist;                 // [T_max] the sequence's ids by position (prompt and image placeholders included)
@@ -224,10 +242,12 @@ struct SpecArgs {
   int64_t* tok_ring; int ring;   // the step's token record, indexed (step % ring) * DTK_MAX_BATCH + vector
   const bf16_t* embed; bf16_t* x; int d;
   int len_override = -1;         // >= 0: the history's length in place of st_true->next_pos (op entry point)
-  int32_t* drafts_out = nullptr; // op entry point: [5] = the drafts (-1 beyond the count) and their count; nothing else is written
+  int32_t* drafts_out = nullptr; // op entry point: [7] = the drafts (-1 beyond the count), their count, their source (DTK_SPEC_FROM_*) and the
+                                 // n-gram size that matched (0: none); nothing else is written
 };
 void launch_spec_accept(const SpecArgs& a, hipStream_t s);   // one thread, behind the sampler
-void launch_spec_draft(const SpecArgs& a, hipStream_t s);    // one block, behind k_spec_accept
+void launch_spec_corpus(const SpecArgs& a, hipStream_t s);   // DTK_SPEC_CORPUS_BLOCKS blocks, behind k_spec_accept, only while a corpus is set (a.sd != null)
+void launch_spec_draft(const SpecArgs& a, hipStream_t s);    // one block, behind k_spec_accept (and k_spec_corpus)
 static inline bool sample_mb_supported(int V) { return V > 32768 && V <= DTK_SAMPLE_MB_MAX_SLICES * 8192; }
 // on the v1 vocabularies (<= 32768) the register-resident single-block kernel is as fast (ds-7b sampling decode 366.2 tok/s
 // vs 366.6 with the chain): one launch, so it stays the default there; DTK_SAMPLER=mb forces the chain for V >= 16384 (A/B)

@@ -144,8 +144,12 @@ class DetikzifyGenerator:
                  presence_penalty: Optional[float] = None, frequency_penalty: Optional[float] = None,
                  dry_multiplier: Optional[float] = None, dry_base: Optional[float] = None, dry_allowed_length: Optional[int] = None,
                  dry_sequence_breakers=None, min_new_tokens: Optional[int] = None, exponential_decay_length_penalty=None,
-                 logit_bias=None, sequence_bias=None, top_logprobs: Optional[int] = None, **gen_kwargs):
-        """top_logprobs=j (1 .. 8): every rollout of simulate() is generated with return_logprobs=True, top_logprobs=j, and every
+                 logit_bias=None, sequence_bias=None, top_logprobs: Optional[int] = None, prompt_lookup_rollouts: int = 0, **gen_kwargs):
+        """prompt_lookup_rollouts=R (0 = off): with prompt_lookup_num_tokens on, the program part (the ids behind the root prompt) of the
+        last R finished generate() results is passed to model.generate as prompt_lookup_corpus, newest first, behind the sequences of an
+        explicit prompt_lookup_corpus= (tokenised boilerplate, say); the oldest are left out until model.generate's cap on the corpus
+        holds.  Sibling rollouts share whole lines the new rollout's own history does not hold yet; the tokens are the same either way.
+        top_logprobs=j (1 .. 8): every rollout of simulate() is generated with return_logprobs=True, top_logprobs=j, and every
         document it yields carries `.token_logprobs` / `.token_sample_logprobs` / `.token_top_ids` / `.token_top_logprobs`, one entry
         per token behind the prompt, as sample(return_logprobs=True, top_logprobs=j) attaches them.  Under a batch engine that needs an
         engine built with top_logprobs >= j (simulate_parallel builds it).
@@ -177,6 +181,11 @@ class DetikzifyGenerator:
         self.streamer, self.control = streamer, control or ExplicitAbort()
         self.exploration, self.strict, self.document_class = exploration, strict, document_class
         self.gen_kwargs = gen_kwargs
+        if isinstance(prompt_lookup_rollouts, bool) or not isinstance(prompt_lookup_rollouts, int) or prompt_lookup_rollouts < 0:
+            raise ValueError(f"prompt_lookup_rollouts = {prompt_lookup_rollouts!r}: a number of rollouts >= 0")
+        self.prompt_lookup_rollouts = prompt_lookup_rollouts
+        self._rollouts: deque = deque(maxlen=prompt_lookup_rollouts or None)      # program parts of the last R results, oldest first
+        self._rollouts_lock = threading.Lock()
         # processor output of (image, text) — the AdapterProcessor's for a text — built on first use unless handed in (the trees of
         # simulate_parallel share one)
         self._processed = processed
@@ -296,6 +305,11 @@ class DetikzifyGenerator:
         if finished or n >= budget:         # nothing may follow EOS, nothing fits beyond the budget
             sinks.end()
             return input_ids
+        keep = bool(self.prompt_lookup_rollouts and options.get("prompt_lookup_num_tokens"))
+        if keep:
+            corpus = self._lookup_corpus(options.get("prompt_lookup_corpus"))
+            if corpus:
+                options["prompt_lookup_corpus"] = corpus
         with torch.inference_mode():
             features = self._prompt_features().to(self.model.device)
             conditioning = {name: value for name, value in features.items() if name.startswith("adapter")}
@@ -308,7 +322,31 @@ class DetikzifyGenerator:
                 begin_suppress_tokens=[self.model.config.text_config.eos_token_id],     # never an empty program
                 streamer=sinks,
                 **conditioning, **options)
+        if keep:      # the program part of a finished result: a later rollout of this image drafts from it
+            seq = (out.sequences if hasattr(out, "sequences") else out).reshape(-1)
+            program = [int(t) for t in seq[int(self.montecarlo.root_node.token_ids.numel()):]]
+            if program:
+                with self._rollouts_lock:
+                    self._rollouts.append(program)
         return out if hasattr(out, "sequences") else out.squeeze()      # (return_logprobs=True: the GenerateOutput as it is)
+
+    def _lookup_corpus(self, explicit) -> List[List[int]]:
+        """model.generate's prompt_lookup_corpus: the caller's own sequences first, then the kept rollouts, newest first; the oldest
+        rollouts are left out until the ids and one separator between sequences fit the cap (the caller's sequences are never cut:
+        model.generate refuses them if they alone exceed it)"""
+        from .. import _lib
+        first = [s for s in ([t.tolist() if isinstance(t, torch.Tensor) else list(t) for t in explicit] if explicit is not None else []) if s]
+        with self._rollouts_lock:
+            kept = list(self._rollouts)[::-1]
+        room = _lib.DTK_SPEC_CORPUS_MAX - (sum(len(s) for s in first) + max(0, len(first) - 1))
+        out = list(first)
+        for program in kept:
+            cost = len(program) + (1 if out else 0)
+            if cost > room:
+                break
+            out.append(program)
+            room -= cost
+        return out
 
     def _generate_recorded(self, input_ids: torch.Tensor, **kw) -> torch.Tensor:
         """generate() of a rollout under top_logprobs: the same tokens, and the new tokens' records filed under their sequence"""

@@ -152,6 +152,7 @@ class GenerateOutput:
         self.sequences, self.logprobs, self.sample_logprobs = sequences, logprobs, sample_logprobs
         self.top_ids, self.top_logprobs = top_ids, top_logprobs
         self.accepted_per_step: Optional[List[int]] = None      # prompt_lookup_num_tokens: tokens every speculative step accepted
+        self.draft_sources: Optional[Tuple[int, int, int]] = None      # prompt_lookup_corpus: steps whose drafts came from (history, corpus, nowhere)
 
 
 def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size=None) -> Tuple[int, int]:
@@ -167,6 +168,34 @@ def check_prompt_lookup(prompt_lookup_num_tokens, max_matching_ngram_size=None) 
         raise ValueError(f"prompt_lookup_num_tokens = {prompt_lookup_num_tokens!r}: an integer in 1 .. 3 (the multi-vector step carries "
                          "at most 4 positions of one sequence; None / 0 = off)")
     return k, n
+
+
+def flatten_corpus(seqs, vocab: int) -> List[int]:
+    """the `prompt_lookup_corpus` argument of generate — 1-D id sequences, lists or tensors — as the flat corpus the device holds: the
+    non-empty sequences in order, a -1 separator between two of them.  ValueError for an id outside [0, vocab), for anything that is
+    not a 1-D sequence of integers, and when the ids plus their separators exceed DTK_SPEC_CORPUS_MAX"""
+    if seqs is None:
+        return []
+    if isinstance(seqs, torch.Tensor) or (len(seqs) > 0 and isinstance(seqs[0], int)):
+        raise ValueError("prompt_lookup_corpus: a list of 1-D id sequences (lists or tensors), not one sequence")
+    flat: List[int] = []
+    for seq in seqs:
+        if isinstance(seq, torch.Tensor):
+            if seq.dim() != 1 or seq.is_floating_point():
+                raise ValueError(f"prompt_lookup_corpus: a 1-D tensor of ids per sequence, got shape {tuple(seq.shape)} of {seq.dtype}")
+            seq = seq.tolist()
+        seq = list(seq)
+        if not seq:
+            continue
+        for t in seq:
+            if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab:
+                raise ValueError(f"prompt_lookup_corpus: id {t!r} is outside [0, {vocab})")
+        if flat:
+            flat.append(-1)
+        flat.extend(seq)
+        if len(flat) > _lib.DTK_SPEC_CORPUS_MAX:
+            raise ValueError(f"prompt_lookup_corpus: the sequences and their separators exceed {_lib.DTK_SPEC_CORPUS_MAX} entries")
+    return flat
 
 
 def check_top_logprobs(top_logprobs: Optional[int], return_logprobs: bool = True) -> int:
@@ -1163,6 +1192,41 @@ class DetikzifyForCausalLM:
                     "dtk_op_spec_lookup")
         return [int(out[i]) for i in range(k.value)]
 
+    def spec_set_corpus(self, seqs) -> int:
+        """the lookup's second draft source: 1-D id sequences (earlier programs, boilerplate), joined by a -1 separator into one corpus of
+        at most DTK_SPEC_CORPUS_MAX entries; empty sequences are dropped, no sequence clears it.  Returns the entries set.  It stays
+        until it is cleared (generate(prompt_lookup_corpus=) sets it for one call)"""
+        flat = flatten_corpus(seqs, int(self.config.vocab))
+        self._spec_set_corpus(flat)
+        return len(flat)
+
+    def _spec_set_corpus(self, flat: Sequence[int]) -> None:
+        """the flat corpus as flatten_corpus makes it (generate() has checked it already); [] clears"""
+        arr = (C.c_int32 * max(1, len(flat)))(*flat)
+        self._check(_lib.corpus_call(self.lib, "dtk_spec_set_corpus")(self._ctx, arr, len(flat)), "dtk_spec_set_corpus")
+
+    def spec_corpus_len(self) -> int:
+        return int(_lib.corpus_call(self.lib, "dtk_spec_corpus_len")(self._ctx))
+
+    def spec_counters(self) -> Tuple[int, int, int]:
+        """(history, corpus, none): the steps launched since spec_begin whose drafts came from there"""
+        out = (C.c_int64 * 3)()
+        self._check(_lib.corpus_call(self.lib, "dtk_spec_counters")(self._ctx, out), "dtk_spec_counters")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def spec_lookup_corpus(self, ids: Sequence[int], corpus: Sequence[int], num_tokens: int, max_ngram: int = 2,
+                           max_positions: Optional[int] = None) -> Tuple[List[int], int, int]:
+        """the two lookup kernels alone over ids and a flat corpus (negative entries separate its sequences): (drafts, source, n) — the
+        drafts a step whose vector 0 forwards ids[-1] would carry, where they came from (DTK_SPEC_FROM_*) and the n-gram size that matched"""
+        n, nc = len(ids), len(corpus)
+        arr = (C.c_int32 * max(1, n))(*[int(v) for v in ids])
+        carr = (C.c_int32 * max(1, nc))(*[int(v) for v in corpus])
+        out, k, src, ng = (C.c_int32 * 4)(), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(_lib.corpus_call(self.lib, "dtk_op_spec_lookup_corpus")(
+            self._ctx, arr, n, carr, nc, int(num_tokens), int(max_ngram), int(max(n, 1) + 8 if max_positions is None else max_positions),
+            out, C.byref(k), C.byref(src), C.byref(ng)), "dtk_op_spec_lookup_corpus")
+        return [int(out[i]) for i in range(k.value)], int(src.value), int(ng.value)
+
     # ---- classifier-free guidance: pairs of batch slots (dtk_set_guidance) ------------------------------------
     def set_guidance(self, scale: Optional[float], cond_slot: int, uncond_slot: Optional[int]):
         """pairs two decoding slots for classifier-free guidance: in every batched step the conditional slot's pending
@@ -1375,7 +1439,7 @@ class DetikzifyForCausalLM:
                  negative_prompt_ids: Optional[torch.Tensor] = None, negative_pixel_values: Optional[torch.Tensor] = None,
                  negative_adapter_input_ids: Optional[torch.Tensor] = None, prompt_lookup_num_tokens: Optional[int] = None,
                  max_matching_ngram_size: Optional[int] = None, prompt_lookup_drafts: Optional[Sequence[int]] = None,
-                 **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
+                 prompt_lookup_corpus=None, **hf_kwargs) -> Union[torch.Tensor, GenerateOutput]:
         """One sequence of HF GenerationMixin.generate/_sample semantics (generation/utils.py
         :2783-2950): streamer.put(prompt) once, then per token: processors -> argmax|draw ->
         append -> streamer.put(token) -> stopping criteria (max length, EOS, user criteria);
@@ -1428,7 +1492,13 @@ class DetikzifyForCausalLM:
         claimed — classifier-free guidance lives with the same fact.  `.accepted_per_step` of the GenerateOutput lists what every step
         accepted.  Not with guidance, penalties, DRY, the length rules, a bias, top_logprobs, kv_format mxfp8 or a batch engine
         (NotImplementedError).  prompt_lookup_drafts (not an HF argument; tests): an id per absolute position, -1 = none, used as the
-        drafts instead of the lookup.
+        drafts instead of the lookup.  prompt_lookup_corpus=[seq, ...] (not an HF argument; retrieval-based drafting as in REST): 1-D id
+        sequences, lists or tensors — earlier programs of the same image, tokenised boilerplate — as a second place to look.  At every
+        n-gram size the sequence's own ids are searched first, then the corpus (first window whose continuation holds an id; a window
+        never spans two sequences); a longer n-gram beats a shorter one whatever its source.  The verify pass decides every token, so
+        the output is the same with any corpus; `.draft_sources` = (history, corpus, none) counts the steps by where their drafts came
+        from.  The corpus is set for this call alone.  ValueError without prompt_lookup_num_tokens, for ids outside the vocabulary,
+        and when the ids plus one separator between sequences exceed 65536 entries; empty sequences are dropped.
 
         Any other HF generation argument is accepted only at the value that leaves `_sample` unchanged
         (`_NEUTRAL_GENERATE_KWARGS`); everything else — beams, penalties, several return sequences, constraints,
@@ -1470,6 +1540,9 @@ class DetikzifyForCausalLM:
             getattr(self.generation_config, "max_matching_ngram_size", None) if max_matching_ngram_size is None else max_matching_ngram_size)
         if prompt_lookup_drafts is not None and not spec_k:
             raise ValueError("prompt_lookup_drafts without prompt_lookup_num_tokens")
+        if prompt_lookup_corpus is not None and not spec_k:
+            raise ValueError("prompt_lookup_corpus without prompt_lookup_num_tokens")
+        corpus = flatten_corpus(prompt_lookup_corpus, int(self.config.vocab))
         if spec_k:      # everything that refuses a speculative call, before anything runs
             if guided:
                 raise NotImplementedError("prompt_lookup_num_tokens: not together with guidance_scale (the guided pair needs the step's slots)")
@@ -1668,6 +1741,7 @@ class DetikzifyForCausalLM:
             launched = received = 0
             at = {"slot": 0} if (guided or spec_k) else {}      # a guided pair decodes in slots 0 (this call's sampling state) and 1 (the negative prompt); a speculating sequence in slot 0
             spec_open, accepted = False, []
+            corpus_set, sources = False, None
             try:
                 self.set_sampling(do_sample, temperature, top_p, top_k, seed, bad,
                                   begin_suppress_tokens or (), suppress_tokens or (), **at)
@@ -1702,6 +1776,9 @@ class DetikzifyForCausalLM:
                 stop = False
                 ahead = 2  # one step always in flight while the host handles the previous token
                 if spec_k:      # the same pipelining over speculative steps: every step read hands over 1 .. K + 1 tokens
+                    if corpus:      # the second draft source, for this call alone (cleared where the speculation ends)
+                        self._spec_set_corpus(corpus)
+                        corpus_set = True
                     self.spec_begin(spec_k, spec_n, table=prompt_lookup_drafts is not None)
                     spec_open = True
                     if prompt_lookup_drafts is not None:
@@ -1763,8 +1840,14 @@ class DetikzifyForCausalLM:
                         self.decode_launch(); launched += 1
             finally:
                 try:
-                    if spec_open:      # the steps in flight are read, slot 0 keeps exactly the sequence as returned (no pending logits)
-                        self.spec_end(cur)
+                    try:
+                        if spec_open:      # the steps in flight are read, slot 0 keeps exactly the sequence as returned (no pending logits)
+                            self.spec_end(cur)
+                            if corpus_set:
+                                sources = self.spec_counters()
+                    finally:
+                        if corpus_set:     # a later call without the argument sees no corpus
+                            self._spec_set_corpus([])
                     if topk or guided:      # the call that asked for the alternatives / the pair switches them off again: later steps run without the extra kernels
                         self.synchronize()
                         while received < launched:      # (a step left in flight behind the last token: the switches refuse unread steps)
@@ -1791,5 +1874,6 @@ class DetikzifyForCausalLM:
                                   torch.tensor(tops[1][:n], dtype=torch.float32).reshape(1, n, topk) if topk else None)
             if spec_k and engine is None and n_new_max > 0:
                 out.accepted_per_step = accepted
+                out.draft_sources = sources
             return out
         return buf[:, :cur].clone()

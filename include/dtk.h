@@ -1135,9 +1135,36 @@ int  dtk_engine_set_guidance_op(dtk_engine* e, int (*set_guidance)(void* dev, in
  *                       step whose vector 0 sits at position len - 1 of a max_positions = T_max context cuts them.
  *   dtk_bench_spec      tools/bench_spec.py: HIP events around reps (1 .. 64) back-to-back launches of k_spec_accept + k_spec_draft on the
  *                       speculating sequence's own state: *avg_us per pair.  The pairs move the position over stale records (never
- *                       beyond max_positions): afterwards the sequence is good for dtk_spec_end and a new prefill only. */
+ *                       beyond max_positions): afterwards the sequence is good for dtk_spec_end and a new prefill only.  With a corpus
+ *                       set, k_spec_corpus runs between the two, as in a step.
+ * A second draft source for DTK_SPEC_LOOKUP: a CORPUS of earlier programs (the boilerplate of every TikZ program, sibling rollouts of one
+ * tree), a flat int32 array of at most DTK_SPEC_CORPUS_MAX entries that holds id sequences joined by a negative separator entry (-1).
+ * With len ids h in the history, C corpus entries c and kmax = min(K, max_positions - 1 - (len - 1), NV - 1, 3):
+ *     for n = min(max_ngram, len - 1) down to 1, tail = h[len - n : len]:
+ *       1. the history, unchanged: the first idx in [0, len - n) with h[idx : idx + n] == tail gives h[idx + n : idx + n + kmax];
+ *       2. otherwise the corpus: the first idx in [0, C - n) with c[idx : idx + n] == tail and c[idx + n] >= 0 gives
+ *          c[idx + n : idx + n + kmax], cut in front of the first negative entry or at C;
+ *     no match anywhere: no drafts.
+ * A longer n-gram beats a shorter one whatever its source, at equal n the history wins, a window that contains a separator never matches
+ * (tail ids are >= 0), a corpus window without a continuation id is skipped, and an empty corpus leaves the rule above.  The verify pass
+ * decides every token, so a corpus changes how many tokens a step accepts and nothing else.  DTK_SPEC_TABLE ignores the corpus.
+ *   dtk_spec_set_corpus  n = 0 clears.  DTK_ERR_ARG: an id >= the vocabulary size; DTK_ERR_RANGE: n > DTK_SPEC_CORPUS_MAX; DTK_ERR_STATE: a
+ *                       speculative step in flight, or a context outside the multi-vector family.  The first non-empty call allocates
+ *                       the corpus buffer (256 KiB) and 64 block results; a context that never calls it allocates nothing.  The corpus
+ *                       persists over dtk_spec_begin / dtk_spec_end until it is cleared.  While one is set the captured speculative steps
+ *                       hold one more kernel (k_spec_corpus, 64 blocks: one pass over the corpus per step): the change between none and
+ *                       some drops the two speculative graphs (one re-capture each), replacing one corpus by another re-captures nothing.
+ *   dtk_spec_corpus_len  the entries set (0: none).
+ *   dtk_spec_counters   out[3] = the steps launched since dtk_spec_begin whose drafts (those the step made for the next one) came from the
+ *                       history (or the table), from the corpus, from nowhere.  DTK_ERR_STATE with a step in flight.
+ *   dtk_op_spec_lookup_corpus  dtk_op_spec_lookup with a corpus: k_spec_corpus + k_spec_draft on the op scratch in the step's launch
+ *                       shape; + *source_out = DTK_SPEC_FROM_* and *ngram_out = the n that matched (0: none). */
 enum { DTK_SPEC_LOOKUP = 0, DTK_SPEC_TABLE = 1 };
 #define DTK_SPEC_MAX_NGRAM 16
+#define DTK_SPEC_CORPUS_MAX 65536
+#define DTK_SPEC_FROM_NONE 0
+#define DTK_SPEC_FROM_HISTORY 1
+#define DTK_SPEC_FROM_CORPUS 2
 int  dtk_spec_begin(dtk_ctx* ctx, int K, int max_ngram, int source);
 int  dtk_spec_set_drafts(dtk_ctx* ctx, const int32_t* table, int n);
 int  dtk_spec_launch(dtk_ctx* ctx);
@@ -1145,6 +1172,11 @@ int  dtk_spec_wait(dtk_ctx* ctx, int64_t* tokens_out /* [4] */, int* n_out, floa
 int  dtk_spec_end(dtk_ctx* ctx, int keep_len);
 int  dtk_op_spec_lookup(dtk_ctx* ctx, const int32_t* ids, int len, int K, int max_ngram, int T_max, int32_t* drafts_out /* [4] */, int* n_out);
 int  dtk_bench_spec(dtk_ctx* ctx, int reps, float* avg_us);
+int  dtk_spec_set_corpus(dtk_ctx* ctx, const int32_t* ids, int n);
+int  dtk_spec_corpus_len(const dtk_ctx* ctx);
+int  dtk_spec_counters(dtk_ctx* ctx, int64_t* out /* [3] */);
+int  dtk_op_spec_lookup_corpus(dtk_ctx* ctx, const int32_t* ids, int len, const int32_t* corpus, int n_corpus, int K, int max_ngram, int T_max,
+                               int32_t* drafts_out /* [4] */, int* n_out, int* source_out, int* ngram_out);
 
 #ifdef __cplusplus
 }

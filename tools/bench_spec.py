@@ -25,6 +25,69 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
 
+def corpus_cost(args):
+    """--corpus-ids: the COST of a corpus, nothing else.  The lookup source at K = 3 over a sampled run of slot 0, with a corpus of n
+    copies of an id the sequence never holds (the image placeholder: banned from sampling, absent from the prompt), so no window
+    matches and every corpus size decodes the same tokens with the same drafts.  Per size, alternating in one process: the step time
+    (one step in flight, as generate() keeps it) and the step's own kernels from HIP events around back-to-back launches
+    (dtk_bench_spec: k_spec_accept + k_spec_draft, with k_spec_corpus between them when a corpus is set).  What a corpus BUYS — the
+    acceptance on real TikZ — is not measured here."""
+    from detikzify_amd.model import load
+    sizes = [int(v) for v in args.corpus_ids.split(",")]
+    model, _ = load(args.model, synthetic=1234, max_positions=2048, batch_slots=4)
+    cfg = model.config
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(3, cfg.vocab - 1, (args.prompt + 8,), generator=g)
+    ids = ids[ids != cfg.image_token_id][:args.prompt].contiguous()
+    T = int(ids.numel())
+    samp = dict(do_sample=True, temperature=0.8, top_p=0.95, seed=7, bad_ids=[cfg.image_token_id])
+    warm, K = 8, 3
+    assert T + 4 * (args.steps + warm + 4) + 8 < 2048, "fewer steps or a shorter prompt: a step accepts up to 4 tokens"
+    legs = [f"corpus_{n}" for n in sizes]
+    res = {"model": args.model, "vocab": int(cfg.vocab), "prompt_tokens": T, "timed_steps": args.steps, "K": K, "max_ngram": args.ngram,
+           "step_us": {k: [] for k in legs}, "kernels_us_per_step": {k: [] for k in legs}, "tokens": {}}
+
+    def leg(n):
+        if n:
+            model.spec_set_corpus([[int(cfg.image_token_id)] * n])
+        model.set_sampling(slot=0, **samp)
+        model.prefill(ids, None, slot=0)
+        model.spec_begin(K, args.ngram)
+        kept = T
+        try:
+            toks = []
+            for _ in range(warm):
+                model.spec_launch(); toks += model.spec_wait()
+            model.spec_launch()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                model.spec_launch(); toks += model.spec_wait()
+            dt = time.perf_counter() - t0
+            toks += model.spec_wait()
+            kept = T + len(toks)
+            us = C.c_float(0)
+            model._check(model.lib.dtk_bench_spec(model._ctx, 50, C.byref(us)), "dtk_bench_spec")
+        finally:
+            model.spec_end(kept)
+            if n:
+                model.spec_set_corpus([])
+        return dt / args.steps, float(us.value), toks
+
+    for _ in range(args.rounds):
+        for n in sizes:
+            step_s, us, toks = leg(n)
+            res["step_us"][f"corpus_{n}"].append(round(step_s * 1e6, 2))
+            res["kernels_us_per_step"][f"corpus_{n}"].append(round(us, 3))
+            assert res["tokens"].setdefault("first", toks) == toks, "a corpus that cannot match changed the tokens"
+    res["tokens"] = {"per_leg": len(res["tokens"]["first"])}
+    res["median_step_us"] = {k: round(statistics.median(v), 2) for k, v in res["step_us"].items()}
+    res["median_kernels_us_per_step"] = {k: round(statistics.median(v), 3) for k, v in res["kernels_us_per_step"].items()}
+    out = Path(args.out) if args.out else ROOT / "profiles" / f"spec_corpus_{args.model.replace('detikzify-', '')}.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=1) + "\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="detikzify-ds-7b")
@@ -32,7 +95,12 @@ def main():
     ap.add_argument("--steps", type=int, default=160, help="timed steps per leg")
     ap.add_argument("--rounds", type=int, default=3, help="alternations")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--corpus-ids", default=None, help="comma-separated corpus sizes, e.g. 0,4096,65536: measure what a prompt-lookup "
+                                                       "corpus costs instead (writes profiles/spec_corpus_<model>.json)")
+    ap.add_argument("--ngram", type=int, default=16, help="--corpus-ids: max_matching_ngram_size of the lookup")
     args = ap.parse_args()
+    if args.corpus_ids is not None:
+        return corpus_cost(args)
     from detikzify_amd.model import load
     model, _ = load(args.model, synthetic=1234, max_positions=2048, batch_slots=4)
     lone, _ = load(args.model, synthetic=1234, max_positions=2048, batch_slots=0)
